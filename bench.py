@@ -606,6 +606,28 @@ def host_fed_overlapped(cal, frames, fp, sp, streams, resident_records, batches=
         ctx.close()
 
 
+DUMP_MASKS = 8                        # masks of the last timed step written by --dump-outputs (float32: 4.75 MB each)
+
+
+def dump_sample(ctx, NL, indices):
+    """Right after the timed steps: the records of the last one and a fixed, seeded sample of its masks."""
+    rng = np.random.default_rng(0)
+    pick = np.sort(rng.choice(NL, min(DUMP_MASKS, NL), replace=False))
+    masks = np.stack([ctx.download_masks(1, first=int(i))[0] for i in pick])
+    return ctx.download_records(NL), masks, np.asarray([indices[int(i)] for i in pick])
+
+
+def write_outputs(out_dir, records, masks, mask_frames):
+    """--dump-outputs: what a caller of the timed path receives, as float64 (records) / float32 (masks) .npy files."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {f: np.asarray(records[f], np.float64) for f in ("left_coeffs", "right_coeffs", "n_left", "n_right", "detected",
+                                                              "fit_flags", "mode", "frame")}
+    arrays["masks_sample"] = masks.astype(np.float32)
+    arrays["masks_sample_frames"] = mask_frames.astype(np.float64)
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+
+
 def launcher(a):
     """--gpus N > 1 and no RANK in the environment: start the N ranks.  This process never touches the GPU."""
     from lane_tracker_amd import distributed
@@ -632,6 +654,8 @@ def main():
     ap.add_argument("--no-stream", action="store_true", help="skip the stateful-stream leg (process / process_batch frames/s)")
     ap.add_argument("--no-settings", action="store_true", help="skip the parameter-set leg (defaults, demo 1-3, second try)")
     ap.add_argument("--only-settings", action="store_true", help="development probe: print the parameter-set leg alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (lane records, a fixed sample of masks) as DIR/<name>.npy")
     a = ap.parse_args()
     if a.gpus < 1 or a.steps < 1 or a.warmup < 0:
         ap.error("--gpus >= 1, --steps >= 1, --warmup >= 0")
@@ -731,6 +755,7 @@ def main():
         step(k)
     fence(a.steps)
     dt = time.perf_counter() - t0
+    dumped = dump_sample(ctx, NL, indices) if a.dump_outputs and rank == 0 else None   # outside the timed region
     if os.environ.get("LT_BENCH_VERBOSE") and rank == 0:
         print("timed region: drained %.3f ms, +gather %.3f ms, +barrier %.3f ms" % (
             (marks["drained"] - t0) * 1e3, (marks.get("gathered", marks["drained"]) - marks["drained"]) * 1e3,
@@ -772,6 +797,8 @@ def main():
         assert list(rec_all["frame"]) == list(range(first_frame, first_frame + total_frames)), "gathered records are not rank-major"
     else:
         rec_all, total_frames = my_records, NL
+    if dumped is not None:
+        write_outputs(a.dump_outputs, rec_all if gather is not None else dumped[0], dumped[1], dumped[2])
     if gather is not None:            # the collective part is over: release the communicator before rank 0 reports
         gather.barrier()
         gather.close()

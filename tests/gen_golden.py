@@ -13,6 +13,9 @@ What is pinned, and how:
     losslessly) and what the reference's process() makes of them: masks of each try, search mode, pixel
     counts, coefficients, validity (BASELINE config 1; cv2 answered by the oracle as above).
   * process_trace.npz -- the reference's process() state machine run over a synthetic stream.
+  * fuzz_reference.npz -- sliding_window_search / band_search on seeded random cases, as SHA-256 digests of the
+    pixel and centroid arrays (tests/test_oracle_vs_reference.py); ref_cam_calib.npz / ref_warp_params.npz -- the
+    values of the reference's cam_calib.p / warp_params.p (tests/test_native_abi.py).
     process() needs cv2, which does not exist in this image.  The harness registers a stand-in
     `cv2` module whose functions are answered by this repo's CPU oracle (oracle/), so this fixture
     pins ONLY the reference's control flow (two tries, search-mode choice, history/averaging,
@@ -381,6 +384,93 @@ def run_photos(ref, ref_dir, out_dir):
     print("photos:", names)
 
 
+def run_calib(ref_dir, out_dir):
+    """The reference's cam_calib.p / warp_params.p, read with the same loaders, stored as npz (values only)."""
+    import contextlib
+    import io
+    from lane_tracker_amd import utils
+    with contextlib.redirect_stdout(io.StringIO()):
+        K, D = utils.load_camera_calib(os.path.join(ref_dir, "cam_calib.p"))
+        M, Minv, isz, wsz, mppv, mpph = utils.load_warp_params(os.path.join(ref_dir, "warp_params.p"))
+    utils.save_calibration_npz(os.path.join(out_dir, "ref_cam_calib.npz"), os.path.join(out_dir, "ref_warp_params.npz"),
+                               K, D, M, Minv, isz, wsz, mppv, mpph)
+
+
+# ---- fuzz digests: the reference's searches on seeded random cases, stored as SHA-256 of the outputs --------------
+FUZZ_FIELDS = ("left_y", "left_x", "right_y", "right_x", "left_centroids", "right_centroids")
+FUZZ_SWS_SEED, FUZZ_SWS_N = 2024, 120
+FUZZ_BAND_SEED, FUZZ_BAND_N = 77, 40
+
+
+def digest(a):
+    return hashlib.sha256(np.ascontiguousarray(np.asarray(a, dtype=np.int64)).tobytes()).hexdigest().encode()
+
+
+def fuzz_sws_case(rng):
+    kind = rng.integers(0, 6)
+    seed = int(rng.integers(0, 1 << 30))
+    if kind == 0:
+        m = synth.random_mask(seed, density=float(10 ** rng.uniform(-4, -0.3)))
+    elif kind == 1:
+        m = synth.synth_mask(seed, noise=float(10 ** rng.uniform(-4, -1.3)), curv=3e-4, slope=0.25)[0]
+    elif kind == 2:
+        m = synth.synth_mask(seed, noise=0.0, left_base=(0, 40), sep=(200, 1000))[0]
+    elif kind == 3:
+        m = synth.synth_mask(seed, noise=1e-3)[0]
+        y0, y1 = sorted(rng.integers(0, 1100, 2))
+        m[y0:y1, : int(rng.integers(0, 1080))] = 0
+    elif kind == 4:
+        m = synth.synth_mask(seed, noise=1e-4, drop_left=bool(rng.integers(0, 2)), drop_right=bool(rng.integers(0, 2)))[0]
+    else:
+        m = synth.synth_mask(seed, noise=float(10 ** rng.uniform(-4, -2)))[0]
+    p = dict(window_width=int(rng.choice([30, 30, 20, 31, 60])), window_height=int(rng.choice([40, 40, 25, 118])),
+             search_range=int(rng.choice([20, 20, 60, 5])), mu=float(rng.choice([0.1, 0.1, 0.5, 1.0, 0.0])),
+             no_success_limit=int(rng.choice([8, 8, 3, 50, 1])), start_slice=float(rng.choice([0.25, 0.25, 0.1, 1.0])),
+             ignore_sides=int(rng.choice([360, 360, 0, 100])), ignore_bottom=int(rng.choice([30, 30, 0, 7])),
+             partial=rng.choice([1, 1, 0.5, 0.3]).item())
+    return m, p
+
+
+def fuzz_sws_cases():
+    rng = np.random.default_rng(FUZZ_SWS_SEED)
+    return [fuzz_sws_case(rng) for _ in range(FUZZ_SWS_N)]
+
+
+def fuzz_band_cases():
+    rng = np.random.default_rng(FUZZ_BAND_SEED)
+    cases = []
+    for _ in range(FUZZ_BAND_N):
+        seed = int(rng.integers(0, 1 << 30))
+        m, lc, rc = synth.synth_mask(seed, noise=float(10 ** rng.uniform(-4, -0.5)))
+        lc = lc + rng.normal(0, [1e-6, 1e-3, 3.0])
+        rc = rc + rng.normal(0, [1e-6, 1e-3, 3.0])
+        p = dict(bandwidth=int(rng.choice([25, 30, 5, 80])), ignore_bottom=int(rng.choice([30, 0, 11])), partial=1)
+        cases.append((m, lc, rc, p))
+    return cases
+
+
+def run_fuzz(ref):
+    """-> fuzz_reference.npz: per case the reference's detected flag and the digests of FUZZ_FIELDS (empty when not
+    detected; band_search has no centroids)."""
+    def digests(lt, fields):
+        return [digest(getattr(lt, f)) if lt.detected_pixels else b"" for f in fields] + [b""] * (len(FUZZ_FIELDS) - len(fields))
+    sws_det, sws_dig = [], []
+    for m, p in fuzz_sws_cases():
+        lt = new_tracker(ref)
+        lt.sliding_window_search(m, **p)
+        sws_det.append(bool(lt.detected_pixels))
+        sws_dig.append(digests(lt, ("left_y", "left_x", "right_y", "right_x", "left_window_centroids", "right_window_centroids")))
+    band_det, band_dig = [], []
+    for m, lc, rc, p in fuzz_band_cases():
+        lt = new_tracker(ref)
+        lt.last_left_coeffs, lt.last_right_coeffs = lc, rc
+        lt.band_search(m, **p)
+        band_det.append(bool(lt.detected_pixels))
+        band_dig.append(digests(lt, FUZZ_FIELDS[:4]))
+    return dict(sws_detected=np.asarray(sws_det), sws_digests=np.asarray(sws_dig, "S64"),
+                band_detected=np.asarray(band_det), band_digests=np.asarray(band_dig, "S64"))
+
+
 def pack(mask):
     return dict(mask_bits=np.packbits(mask != 0), mask_shape=np.asarray(mask.shape, np.int64),
                 mask_value=np.asarray(int(mask.max()) if mask.any() else 255, np.int64))
@@ -391,9 +481,18 @@ def main():
     ap.add_argument("--ref", default="/root/reference")
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden"))
     ap.add_argument("--skip-trace", action="store_true")
+    ap.add_argument("--only", choices=["calib", "fuzz"], help="write only ref_*_calib/params.npz or fuzz_reference.npz")
     a = ap.parse_args()
     ref = import_reference(a.ref)
     os.makedirs(a.out, exist_ok=True)
+    if a.only in (None, "calib"):
+        run_calib(a.ref, a.out)
+    if a.only in (None, "fuzz"):
+        fz = run_fuzz(ref)
+        np.savez_compressed(os.path.join(a.out, "fuzz_reference.npz"), **fz)
+        print("fuzz: %d/%d sws cases detected, %d/%d band" % (fz["sws_detected"].sum(), FUZZ_SWS_N, fz["band_detected"].sum(), FUZZ_BAND_N))
+    if a.only:
+        return
     names = []
     for name, mask, params in sws_cases():
         p, out = run_sws(ref, mask, params)
