@@ -47,7 +47,9 @@ extern "C" {
  *    switch), lt_host_memory_stats, lt_mask_rerun (a second parameter set over frames whose front end has run), lt_download_lane_lists (a search's lists in one
  *    round trip), lt_set_direct_upload + lt_direct_upload_count (one frame's rows stored through the PCIe aperture),
  *    lt_host_text_now_group (a frame's text lines drawn at once, behind the group's copies), lt_frame_tail (validity, average,
- *    plot points, radius and eccentricity of a valid first try in one host call).  Nothing removed or changed. */
+ *    plot points, radius and eccentricity of a valid first try in one host call).  Later additions, still 5:
+ *    lt_search_item + lt_search_fit_list (the searches of frames of unrelated streams in one launch), lt_upload_frame_rows_list +
+ *    lt_upload_frame_rest_list (the uploads of frames that lie in separate host arrays).  Nothing removed or changed. */
 #define LT_ABI_VERSION 5
 
 typedef enum lt_status {
@@ -95,6 +97,15 @@ typedef struct lt_lane_record {
     uint8_t _pad;                /* reserved (the library records how the slot's lane pixels are stored) */
     int32_t frame;               /* caller-defined global frame index */
 } lt_lane_record;
+
+/* One frame of a search list (lt_search_fit_list), 64 bytes: the slot its mask is in, the search it gets (0 sliding window,
+ * 1 band) and, for a band search, the coefficients its band is drawn around (last_left_coeffs, last_right_coeffs). */
+typedef struct lt_search_item {
+    int32_t slot;
+    int32_t mode;
+    int32_t _pad[2];
+    double  prev_coeffs[6];
+} lt_search_item;
 
 typedef struct lt_info {
     int32_t abi_version, device, capacity, cu_count;
@@ -176,6 +187,14 @@ int  lt_upload_frame_rest(lt_ctx* ctx, const uint8_t* frames_rgb, int first_slot
  * lt_present_frame with the same runs reads.  The other rows of the slots keep whatever they held -- an overlay over the whole
  * frame needs lt_upload_frame_rest first. */
 int  lt_upload_frame_rest_rows(lt_ctx* ctx, const uint8_t* frames_rgb, int first_slot, int n, const int32_t* rows4);
+/* The pointer-list forms of lt_upload_frame_rows_enqueue and lt_upload_frame_rest: frame k comes from its own host array
+ * frames_rgb[k] (img_h * img_w * 3 bytes) and goes into slot first_slot + k -- the camera frames of n unrelated streams, one
+ * each, without gathering them into one block on the host first.  Slot by slot they are the range forms' calls: the same rows,
+ * the same ways (a frame's rows may take the PCIe aperture, lt_set_direct_upload), the same ordering against the slots' readers
+ * and writers, and frames_rgb[k] must stay valid as long as the range form's frames_rgb.  The list itself is read before the
+ * call returns. */
+int  lt_upload_frame_rows_list(lt_ctx* ctx, const uint8_t* const* frames_rgb, int first_slot, int n);
+int  lt_upload_frame_rest_list(lt_ctx* ctx, const uint8_t* const* frames_rgb, int first_slot, int n);
 /* masks: n * warp_h * warp_w bytes; lets the search stages run on caller-supplied binary images */
 int  lt_upload_masks(lt_ctx* ctx, const uint8_t* masks, int first_slot, int n);
 int  lt_download_masks(lt_ctx* ctx, int first_slot, int n, uint8_t* masks);
@@ -215,6 +234,17 @@ int  lt_filter_run(lt_ctx* ctx, int first_slot, int n, const lt_filter_params* p
 int  lt_sws_fit_run(lt_ctx* ctx, int first_slot, int n, const lt_search_params* p);
 /* band_search() + fit_poly() (:449-509); prev_coeffs: n * 6 doubles (last_left_coeffs, last_right_coeffs) */
 int  lt_band_fit_run(lt_ctx* ctx, int first_slot, int n, const lt_search_params* p, const double* prev_coeffs);
+/* The searches of n frames of UNRELATED streams, each in its own mode, in one launch: items[i] names the slot, the mode (0:
+ * sliding_window_search with `sws`, 1: band_search with `band` around items[i].prev_coeffs) -- every slot holds what
+ * lt_sws_fit_run / lt_band_fit_run over that slot alone would leave there: record, lane pixels and (sliding window) window
+ * centroids.  The slots need not be contiguous or in order; each may appear once.  sws / band may be NULL when no item has
+ * that mode.  Frames whose geometry the one-launch kernel does not take (a window wider than 64 columns, a band wider than
+ * 64, masks without bit planes) are searched slot by slot with the kernels of the range forms -- same results.  Enqueued behind
+ * the work on every listed slot (every slot stream holding one waits for the search before its later work); `items` is read
+ * before the call returns.  The context stages one list at a time: a call first waits, on the host, until the searches of the
+ * previous list call have finished reading theirs (nothing to wait for when its records have been downloaded).  LT_ERR_INVALID: n < 0, a NULL list or parameter set that is needed, a slot outside the capacity or
+ * listed twice, a mode other than 0 / 1. */
+int  lt_search_fit_list(lt_ctx* ctx, int n, const lt_search_item* items, const lt_search_params* sws, const lt_search_params* band);
 /* The warm path of ONE stateful stream, chained on the device (band_search :449-500 + fit_poly :502-509 per frame, with
  * the cross-frame dependence of :474-489 / :1182-1183 kept in HBM): the slots first_slot .. first_slot + n - 1 hold
  * consecutive frames of one video; the band of the first is drawn around seed_coeffs (6 doubles: last_left_coeffs,

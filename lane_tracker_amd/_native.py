@@ -54,6 +54,15 @@ RECORD_DTYPE = np.dtype([("left_coeffs", "<f8", 3), ("right_coeffs", "<f8", 3), 
 assert RECORD_DTYPE.itemsize == 64 and C.sizeof(LaneRecord) == 64
 
 
+class SearchItem(C.Structure):
+    """lt_search_item: one frame of lt_search_fit_list (slot, 0 sliding window / 1 band, the band's prior coefficients)."""
+    _fields_ = [("slot", C.c_int32), ("mode", C.c_int32), ("_pad", C.c_int32 * 2), ("prev_coeffs", C.c_double * 6)]
+
+
+SEARCH_ITEM_DTYPE = np.dtype([("slot", "<i4"), ("mode", "<i4"), ("_pad", "<i4", 2), ("prev_coeffs", "<f8", 6)])
+assert SEARCH_ITEM_DTYPE.itemsize == 64 and C.sizeof(SearchItem) == 64
+
+
 class Info(C.Structure):
     _fields_ = [("abi_version", C.c_int32), ("device", C.c_int32), ("capacity", C.c_int32),
                 ("cu_count", C.c_int32), ("src_row0", C.c_int32), ("src_row1", C.c_int32),
@@ -136,6 +145,9 @@ _SIGNATURES = {
     "lt_filter_run": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(FilterParams)]),
     "lt_sws_fit_run": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(SearchParams)]),
     "lt_band_fit_run": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(SearchParams), _P]),
+    "lt_search_fit_list": (C.c_int, [_P, C.c_int, _P, C.POINTER(SearchParams), C.POINTER(SearchParams)]),
+    "lt_upload_frame_rows_list": (C.c_int, [_P, _P, C.c_int, C.c_int]),
+    "lt_upload_frame_rest_list": (C.c_int, [_P, _P, C.c_int, C.c_int]),
     "lt_band_fit_chain_run": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(SearchParams), _P]),
     "lt_band_fit_chain_collect": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "lt_band_fit_chain_cancel": (C.c_int, [_P]),
@@ -634,6 +646,44 @@ class Context:
         else:
             _check(self.lib.lt_upload_frame_rest_rows(self._h, f.ctypes.data, first, f.shape[0], rows))
         return f
+
+    def _frame_list(self, frames):
+        fs = [_u8(f) for f in frames]
+        for f in fs:
+            if f.shape != (self.img_h, self.img_w, 3):
+                raise ValueError("expected frames of shape %r, got %r" % ((self.img_h, self.img_w, 3), f.shape))
+        ptrs = (C.c_void_p * max(len(fs), 1))(*[f.ctypes.data for f in fs])
+        return fs, ptrs
+
+    def upload_frame_rows_list(self, frames, first=0):
+        """upload_frame_rows(enqueue=True) of separate frames (a sequence of (H, W, 3) arrays) into slots first, first + 1, ...
+        (lt_upload_frame_rows_list).  Returns the arrays handed to the library: keep them alive as upload_frame_rows' result."""
+        fs, ptrs = self._frame_list(frames)
+        _check(self.lib.lt_upload_frame_rows_list(self._h, C.cast(ptrs, C.c_void_p), first, len(fs)))
+        return fs
+
+    def upload_frame_rest_list(self, frames, first=0):
+        """upload_frame_rest of separate frames into slots first, first + 1, ... (lt_upload_frame_rest_list).  Returns the arrays
+        handed to the library: keep them alive until the next sync() / download."""
+        fs, ptrs = self._frame_list(frames)
+        _check(self.lib.lt_upload_frame_rest_list(self._h, C.cast(ptrs, C.c_void_p), first, len(fs)))
+        return fs
+
+    def search_fit_list(self, items, sws=None, band=None):
+        """The searches of a list of frames, each in its own slot and mode, in one launch (lt_search_fit_list).  `items`: an array
+        of SEARCH_ITEM_DTYPE, or (slot, mode, prev_coeffs or None) tuples; sws / band: search_params() (None: the defaults)."""
+        if not (isinstance(items, np.ndarray) and items.dtype == SEARCH_ITEM_DTYPE):
+            lst = list(items)
+            arr = np.zeros(len(lst), SEARCH_ITEM_DTYPE)
+            for i, (slot, mode, prev) in enumerate(lst):
+                arr[i]["slot"], arr[i]["mode"] = slot, mode
+                if prev is not None:
+                    arr[i]["prev_coeffs"] = np.asarray(prev, np.float64).reshape(6)
+            items = arr
+        items = np.ascontiguousarray(items)
+        sws = sws or search_params()
+        band = band or search_params()
+        _check(self.lib.lt_search_fit_list(self._h, len(items), items.ctypes.data if len(items) else None, C.byref(sws), C.byref(band)))
 
     def upload_frames(self, frames, first=0):
         f = _u8(frames).reshape(-1, self.img_h, self.img_w, 3)

@@ -200,10 +200,13 @@ __global__ __launch_bounds__(64 * BS_RG) void k_band_sums(const uint8_t* __restr
 // per column, and walks the rows with broadcast LDS reads (all lanes read the same word).
 constexpr int BSB_ROWS = 256;   // rows staged at a time (35 KB at 17 words per row)
 constexpr int BSB_NT = 1024;    // 16 waves: the start slice of a single frame is one workgroup's job
-__global__ __launch_bounds__(BSB_NT) void k_band_sums_bits(MaskBits mb, SearchGeom g, uint32_t* __restrict__ sums) {
+// `items` (k_search_list's list, sliding-window items first): blockIdx.z is an index into it, the frame its item's slot; null: the
+// frame is blockIdx.z.
+__global__ __launch_bounds__(BSB_NT) void k_band_sums_bits(MaskBits mb, SearchGeom g, uint32_t* __restrict__ sums,
+                                                           const lt_search_item* __restrict__ items) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     unsigned long long* sw = reinterpret_cast<unsigned long long*>(smem);
-    const int band = blockIdx.y, frame = blockIdx.z, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int band = blockIdx.y, frame = items ? __builtin_amdgcn_readfirstlane(items[blockIdx.z].slot) : (int)blockIdx.z, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int r0 = max(band == 0 ? max(g.y_start, 0) : g.img_height - (1 + band) * g.wh, 0);
     const int r1 = band == 0 ? g.img_height : g.img_height - band * g.wh;
     const unsigned long long* fb = mb.bits + (size_t)frame * mb.bits_stride;
@@ -797,11 +800,13 @@ __host__ __device__ inline Sws2Layout sws2_layout(const SearchGeom& g) {
 #define SWS2_REPORT
 #endif
 
+// The sliding-window search of the frame in slot `frame` (one workgroup): k_sws_fit2 runs it for blockIdx.x, k_search_list for
+// the slot of its item.
 template <int ND, bool BITS>   // ND dwords cover one window row of a u8 mask: 9 for widths <= 32, 17 for <= 64
-__global__ __launch_bounds__(NT) void k_sws_fit2(const uint8_t* __restrict__ masks, size_t mask_stride, MaskBits mb, SearchGeom g,
-                                                const uint32_t* __restrict__ band_sums, uint32_t* __restrict__ pix_all,
-                                                int32_t* __restrict__ cent_all, lt_lane_record* __restrict__ recs) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+__device__ __forceinline__ void sws_fit2_frame(unsigned char* smem, const int frame, const uint8_t* __restrict__ masks, size_t mask_stride,
+                                               const MaskBits& mb, const SearchGeom& g, const uint32_t* __restrict__ band_sums,
+                                               uint32_t* __restrict__ pix_all, int32_t* __restrict__ cent_all,
+                                               lt_lane_record* __restrict__ recs) {
     SWS2_DECL
     const Sws2Layout L = sws2_layout(g);
     unsigned* sum0 = reinterpret_cast<unsigned*>(smem + L.sum0);
@@ -811,7 +816,7 @@ __global__ __launch_bounds__(NT) void k_sws_fit2(const uint8_t* __restrict__ mas
     int* state = reinterpret_cast<int*>(smem + L.state);
     long long* s_mom = reinterpret_cast<long long*>(smem + L.mom);
 
-    const int frame = blockIdx.x, lane = lane_id(), wv = wave_id();
+    const int lane = lane_id(), wv = wave_id();
     const uint8_t* mask = masks + (size_t)frame * mask_stride;
     const uint32_t* fsums = band_sums + (size_t)frame * g.nbands * g.w;   // [band][w], band 0 = start slice
     int32_t* cent = cent_all + (size_t)frame * 2 * (g.maxlev + 2);
@@ -957,6 +962,14 @@ __global__ __launch_bounds__(NT) void k_sws_fit2(const uint8_t* __restrict__ mas
     reduce_and_fit(mom, distinct, s_mom, g.h, g.w, n_left, n_right, detected, 0, recs + frame, 1);
     SWS2_T(6)
     SWS2_REPORT
+}
+
+template <int ND, bool BITS>
+__global__ __launch_bounds__(NT) void k_sws_fit2(const uint8_t* __restrict__ masks, size_t mask_stride, MaskBits mb, SearchGeom g,
+                                                const uint32_t* __restrict__ band_sums, uint32_t* __restrict__ pix_all,
+                                                int32_t* __restrict__ cent_all, lt_lane_record* __restrict__ recs) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    sws_fit2_frame<ND, BITS>(smem, blockIdx.x, masks, mask_stride, mb, g, band_sums, pix_all, cent_all, recs);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -1183,6 +1196,24 @@ __global__ __launch_bounds__(NT) void k_band_fit2(const uint8_t* __restrict__ ma
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int frame = blockIdx.x;
     band_fit2_frame<BITS>(smem, frame, masks, mask_stride, mb, g, bp.by_value ? bp.c : prev + (size_t)frame * 6, pix_all, recs, nq, nullptr);
+}
+
+// k_search_list: the searches of frames of UNRELATED streams in one launch (LaneTrackerGroup: one frame per stream and tick).
+// Workgroup i runs item i -- a sliding-window search (mode 0, k_sws_fit2's body, geometry gs) or a band search around the item's
+// own coefficients (mode 1, k_band_fit2's body, geometry gb) -- over the item's slot, and leaves record, pixel block and (sliding
+// window) centroids in that slot, exactly where lt_sws_fit_run / lt_band_fit_run would.  The mode is uniform per workgroup, so
+// every __syncthreads and the two-wave recurrence of the sliding-window body see the whole workgroup.  Dynamic LDS: the larger
+// of the two layouts.  The band sums of the sliding-window items come from k_band_sums_bits over the same list.
+template <int ND, bool BITS>
+__global__ __launch_bounds__(NT) void k_search_list(const lt_search_item* __restrict__ items, const uint8_t* __restrict__ masks,
+                                                   size_t mask_stride, MaskBits mb, SearchGeom gs, SearchGeom gb,
+                                                   const uint32_t* __restrict__ band_sums, uint32_t* __restrict__ pix_all,
+                                                   int32_t* __restrict__ cent_all, lt_lane_record* __restrict__ recs, int nq) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const lt_search_item* it = items + blockIdx.x;
+    const int slot = __builtin_amdgcn_readfirstlane(it->slot), mode = __builtin_amdgcn_readfirstlane(it->mode);
+    if (mode == 0) sws_fit2_frame<ND, BITS>(smem, slot, masks, mask_stride, mb, gs, band_sums, pix_all, cent_all, recs);
+    else band_fit2_frame<BITS>(smem, slot, masks, mask_stride, mb, gb, it->prev_coeffs, pix_all, recs, nq, nullptr);
 }
 
 // k_band_chain2: the warm path of ONE stateful stream (lane_tracker.py:851-872 with last_detection <= n_reset on every
@@ -1513,7 +1544,8 @@ void launch_sws_fit(hipStream_t s, const uint8_t* masks, size_t mask_stride, Mas
         const size_t lds = (size_t)BSB_ROWS * mb.wpr * sizeof(unsigned long long);   // <= 128 KB at w = 4096
         static const bool big = allow_big_lds(k_band_sums_bits);
         (void)big;
-        hipLaunchKernelGGL(k_band_sums_bits, dim3(1, g.nbands, n), dim3(BSB_NT), lds, s, mb, g, band_sums);
+        hipLaunchKernelGGL(k_band_sums_bits, dim3(1, g.nbands, n), dim3(BSB_NT), lds, s, mb, g, band_sums,
+                           (const lt_search_item*)nullptr);
     } else {
         dim3 sgrid(((vec4 ? g.w / 4 : g.w) + 63) / 64, g.nbands, n);
         if (vec4) hipLaunchKernelGGL(k_band_sums<true>, sgrid, dim3(64, BS_RG), 0, s, masks, mask_stride, g, band_sums);
@@ -1561,6 +1593,37 @@ void launch_band_fit(hipStream_t s, const uint8_t* masks, size_t mask_stride, Ma
 }
 
 bool band_chain_supported(const SearchGeom& g, size_t mask_stride) { return band2_eligible(g, mask_stride); }
+
+bool search_list_supported(const SearchGeom* gs, const SearchGeom* gb, size_t mask_stride) {
+    return (!gs || sws_fit_takes_bits(*gs, mask_stride)) && (!gb || band_fit_takes_bits(*gb, mask_stride)) && (gs || gb);
+}
+
+void launch_search_list(hipStream_t s, const lt_search_item* items, int n, int n_sws, const uint8_t* masks, size_t mask_stride,
+                        MaskBits mb, const SearchGeom& gs,
+                        const SearchGeom& gb, uint32_t* band_sums, uint32_t* pix, int32_t* cent, lt_lane_record* rec) {
+    if (n <= 0) return;
+    size_t lds = 0;
+    if (n_sws > 0) {
+        const size_t bs_lds = (size_t)BSB_ROWS * mb.wpr * sizeof(unsigned long long);
+        static const bool big = allow_big_lds(k_band_sums_bits);
+        (void)big;
+        hipLaunchKernelGGL(k_band_sums_bits, dim3(1, gs.nbands, n_sws), dim3(BSB_NT), bs_lds, s, mb, gs, band_sums, items);
+        lds = (size_t)sws2_layout(gs).total;
+    }
+    int nq = 0;
+    if (n_sws < n) {
+        const int nrows = std::max(gb.band_bottom - gb.band_top, 0);
+        lds = std::max(lds, band2_mom_offset(nrows) + 16 * sizeof(long long));
+        nq = (int)((2LL * (long long)gb.bandwidth + 2 + 3 + 15) / 16);
+    }
+    static const bool big = allow_big_lds(k_search_list<9, true>) && allow_big_lds(k_search_list<17, true>);
+    (void)big;
+    // (gs is only read by sliding-window items: with none, its window width selects nothing that runs)
+    if (n_sws > 0 && 2 * gs.hw > 32)
+        hipLaunchKernelGGL((k_search_list<17, true>), dim3(n), dim3(NT), lds, s, items, masks, mask_stride, mb, gs, gb, band_sums, pix, cent, rec, nq);
+    else
+        hipLaunchKernelGGL((k_search_list<9, true>), dim3(n), dim3(NT), lds, s, items, masks, mask_stride, mb, gs, gb, band_sums, pix, cent, rec, nq);
+}
 
 // The band search of ONE frame around coefficients given by value, by the chain kernel with a chain of one: k_band_chain3 is
 // built around the latency of a single workgroup (8 us per frame against k_band_fit2's 22 for one frame; record and pixel

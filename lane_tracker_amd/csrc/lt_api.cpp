@@ -834,6 +834,8 @@ void lt_destroy(lt_ctx* c) {
     if (c->h_rec) (void)hipHostFree(c->h_rec);
     if (c->h_rec_stage) (void)hipHostFree(c->h_rec_stage);
     if (c->h_cancel) (void)hipHostFree(c->h_cancel);
+    if (c->h_items) (void)hipHostFree(c->h_items);
+    if (c->items_ev) (void)hipEventDestroy(c->items_ev);
     note("streams back to the pool: search, copy");
     stream_put(c->search);
     stream_put(c->copy);
@@ -860,6 +862,7 @@ void lt_destroy(lt_ctx* c) {
     dev_free(c->d_advance);
     dev_free(c->d_lines);
     dev_free(c->d_xpos);
+    dev_free(c->d_items);
     note("done");
     delete c;
 }
@@ -1852,6 +1855,172 @@ int lt_band_fit_run(lt_ctx* c, int first, int n, const lt_search_params* p, cons
     });
     if (rc) return rc;
     HIP_TRY(hipGetLastError());
+    return LT_OK;
+}
+
+// The searches of a list of frames of unrelated streams (LaneTrackerGroup): one k_search_list launch where its kernels take the
+// geometry, else the range forms' kernels slot by slot.  Ordering: the launch goes onto one stream that first waits for the tails of
+// every slot stream holding a listed slot (the masks may have been made on any of them) and for the chains touching the slots;
+// those slot streams then wait for it, so that whatever is enqueued over these slots later is ordered behind it.
+static_assert(sizeof(lt_search_item) == 64, "lt_search_item: 64 bytes, as the header says");
+int lt_search_fit_list(lt_ctx* c, int n, const lt_search_item* items, const lt_search_params* sws, const lt_search_params* band) {
+    if (!c) return fail(LT_ERR_INVALID, "null context");
+    if (n < 0 || (n > 0 && !items)) return fail(LT_ERR_INVALID, "lt_search_fit_list: n < 0 or a null item list");
+    int n_sws = 0;
+    {
+        std::vector<uint8_t> seen((size_t)std::max(c->capacity, 0), 0);
+        for (int i = 0; i < n; ++i) {
+            const int s = items[i].slot, m = items[i].mode;
+            if (s < 0 || s >= c->capacity) return fail(LT_ERR_INVALID, "lt_search_fit_list: item %d: slot %d outside capacity %d", i, s, c->capacity);
+            if (seen[(size_t)s]) return fail(LT_ERR_INVALID, "lt_search_fit_list: slot %d listed twice", s);
+            if (m != 0 && m != 1) return fail(LT_ERR_INVALID, "lt_search_fit_list: item %d: mode %d (0 sliding window, 1 band)", i, m);
+            seen[(size_t)s] = 1;
+            n_sws += m == 0;
+        }
+    }
+    if ((n_sws > 0 && !sws) || (n_sws < n && !band)) return fail(LT_ERR_INVALID, "lt_search_fit_list: a parameter set the items need is null");
+    if (n == 0) return LT_OK;
+    c->rec_mirror_slot = -1;                  // the records change: the page-locked mirror of a one-frame search is stale
+    int rc = set_device(c);
+    if (rc) return rc;
+    if (!c->have_mask) return fail(LT_ERR_STATE, "no mask in the slots: run lt_mask_run or lt_upload_masks first");
+    SearchGeom gs, gb;
+    std::memset(&gs, 0, sizeof gs);
+    std::memset(&gb, 0, sizeof gb);
+    if (n_sws > 0) {
+        if ((rc = make_search_geom(c, sws, false, gs))) return rc;
+        if ((rc = ensure_search_buffers(c, gs.maxpix, gs.maxlev))) return rc;
+        if ((rc = ensure_band_sums(c, gs.nbands))) return rc;
+    }
+    if (n_sws < n) {
+        if ((rc = make_search_geom(c, band, true, gb))) return rc;
+        if ((rc = ensure_search_buffers(c, gb.maxpix, 1))) return rc;
+    }
+    gs.maxpix = gb.maxpix = c->maxpix;
+    gs.maxlev = gb.maxlev = c->maxlev;
+    // sliding-window items first (k_band_sums_bits runs over the head of the list)
+    std::vector<lt_search_item> list(items, items + n);
+    std::stable_partition(list.begin(), list.end(), [](const lt_search_item& it) { return it.mode == 0; });
+    bool bits = true;
+    for (const auto& it : list) bits = bits && masks_have_bits(c, it.slot, 1);
+    const bool one_launch = bits && search_list_supported(n_sws > 0 ? &gs : nullptr, n_sws < n ? &gb : nullptr, c->plane_bytes);
+    if (!one_launch)
+        for (const auto& it : list)
+            if (!((it.mode == 0 ? sws_fit_takes_bits(gs, c->plane_bytes) : band_fit_takes_bits(gb, c->plane_bytes)) && masks_have_bits(c, it.slot, 1)) &&
+                (rc = ensure_u8_masks(c, it.slot, 1)))
+                return rc;
+    // the stream: the urgent one in urgent mode, else the stream of the first listed slot; the other slot streams in front of it
+    const int k = std::max(1, std::min(c->nstreams, c->capacity));
+    auto slice_of = [&](int s) {
+        for (int si = 0; si < k; ++si) {
+            const int b = si + 1 == k ? c->capacity : (int)((long long)c->capacity * (si + 1) / k) & ~1;
+            if (s < b) return si;
+        }
+        return k - 1;
+    };
+    std::vector<uint8_t> touched((size_t)k, 0);
+    for (const auto& it : list) touched[(size_t)slice_of(it.slot)] = 1;
+    hipStream_t st = c->urgent_on && c->urgent ? c->urgent : c->streams[(size_t)slice_of(list[0].slot)];
+    for (int si = 0; si < k; ++si) {
+        if (!touched[(size_t)si] || c->streams[(size_t)si] == st) continue;
+        hipEvent_t e = next_order_event(c);
+        if (!e) return fail(LT_ERR_HIP, "hipEventCreate failed");
+        HIP_TRY(hipEventRecord(e, c->streams[(size_t)si]));
+        HIP_TRY(hipStreamWaitEvent(st, e, 0));
+    }
+    for (const auto& it : list)
+        if ((rc = wait_chains(c, st, it.slot, it.slot + 1))) return rc;
+    const int wpr = (c->calib.warp_w + 63) / 64;
+    if (one_launch) {
+        if (n > c->items_cap) {
+            if (c->items_ev) HIP_TRY(hipEventSynchronize(c->items_ev));
+            dev_free(c->d_items);
+            if (c->h_items) { HIP_TRY(hipHostFree(c->h_items)); c->h_items = nullptr; }
+            c->items_cap = 0;
+            const int cap = std::max(n, c->capacity);
+            if ((rc = dev_alloc(&c->d_items, (size_t)cap))) return rc;
+            if (hipHostMalloc(reinterpret_cast<void**>(&c->h_items), (size_t)cap * sizeof(lt_search_item), hipHostMallocDefault) != hipSuccess) {
+                c->h_items = nullptr;
+                return fail(LT_ERR_HIP, "hipHostMalloc(%zu) failed", (size_t)cap * sizeof(lt_search_item));
+            }
+            c->items_cap = cap;
+        }
+        if (!c->items_ev && hipEventCreateWithFlags(&c->items_ev, hipEventDisableTiming) != hipSuccess) return fail(LT_ERR_HIP, "hipEventCreate failed");
+        // the previous list's kernels are done with it: items_ev is recorded behind them (below), so neither the staging nor the
+        // device copy is overwritten while a search of another call -- on another slot stream, perhaps -- still reads its items
+        HIP_TRY(hipEventSynchronize(c->items_ev));
+        std::memcpy(c->h_items, list.data(), (size_t)n * sizeof(lt_search_item));
+        HIP_TRY(hipMemcpyAsync(c->d_items, c->h_items, (size_t)n * sizeof(lt_search_item), hipMemcpyHostToDevice, st));
+        {
+            StageScope t(c, n_sws > 0 ? ST_SWS_FIT : ST_BAND_FIT, st);
+            const MaskBits mb{c->d_bits_open, c->bits_stride, wpr};
+            launch_search_list(st, c->d_items, n, n_sws, c->d_plane[P_MASK], c->plane_bytes, mb, gs, gb, c->d_band_sums, c->d_pix,
+                               c->d_cent, c->d_rec);
+        }
+        HIP_TRY(hipEventRecord(c->items_ev, st));         // behind the last kernel that reads d_items
+    } else {
+        for (const auto& it : list) {
+            const int s = it.slot;
+            const bool use_bits = masks_have_bits(c, s, 1) && (it.mode == 0 ? sws_fit_takes_bits(gs, c->plane_bytes) : band_fit_takes_bits(gb, c->plane_bytes));
+            const MaskBits mb{use_bits ? c->d_bits_open + (size_t)s * c->bits_stride : nullptr, c->bits_stride, wpr};
+            if (it.mode == 0) {
+                StageScope t(c, ST_SWS_FIT, st);
+                launch_sws_fit(st, c->d_plane[P_MASK] + (size_t)s * c->plane_bytes, c->plane_bytes, mb, gs,
+                               c->d_band_sums + (size_t)s * gs.nbands * c->calib.warp_w, c->d_pix + (size_t)s * 2 * c->maxpix,
+                               c->d_cent + (size_t)s * 2 * (c->maxlev + 2), c->d_rec + s, 1);
+            } else {
+                BandPrev bp;
+                std::memset(&bp, 0, sizeof bp);
+                std::memcpy(bp.c, it.prev_coeffs, sizeof bp.c);
+                bp.by_value = 1;
+                StageScope t(c, ST_BAND_FIT, st);
+                launch_band_fit(st, c->d_plane[P_MASK] + (size_t)s * c->plane_bytes, c->plane_bytes, mb, gb, c->d_prev + (size_t)s * 6, bp,
+                                c->d_pix + (size_t)s * 2 * c->maxpix, c->d_rec + s, 1);
+            }
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    {   // the writer of exactly the listed slots: one entry per run of consecutive slots
+        std::vector<int> slots;
+        slots.reserve(list.size());
+        for (const auto& it : list) slots.push_back(it.slot);
+        std::sort(slots.begin(), slots.end());
+        for (size_t a = 0; a < slots.size();) {
+            size_t b = a + 1;
+            while (b < slots.size() && slots[b] == slots[b - 1] + 1) ++b;
+            if ((rc = note_written(c, st, slots[a], slots[b - 1] + 1))) return rc;
+            a = b;
+        }
+    }
+    hipEvent_t done = next_order_event(c);
+    if (!done) return fail(LT_ERR_HIP, "hipEventCreate failed");
+    HIP_TRY(hipEventRecord(done, st));
+    for (int si = 0; si < k; ++si) {
+        if (!touched[(size_t)si] || c->streams[(size_t)si] == st) continue;
+        HIP_TRY(hipStreamWaitEvent(c->streams[(size_t)si], done, 0));
+    }
+    return LT_OK;
+}
+
+int lt_upload_frame_rows_list(lt_ctx* c, const uint8_t* const* frames, int first, int n) {
+    int rc = check_slots(c, first, n);
+    if (rc) return rc;
+    if (n > 0 && !frames) return fail(LT_ERR_INVALID, "null frame list");
+    for (int k = 0; k < n; ++k)
+        if (!frames[k]) return fail(LT_ERR_INVALID, "lt_upload_frame_rows_list: frame %d is null", k);
+    for (int k = 0; k < n; ++k)
+        if ((rc = upload_frame_rows_impl(c, frames[k], first + k, 1, true))) return rc;
+    return LT_OK;
+}
+
+int lt_upload_frame_rest_list(lt_ctx* c, const uint8_t* const* frames, int first, int n) {
+    int rc = check_slots(c, first, n);
+    if (rc) return rc;
+    if (n > 0 && !frames) return fail(LT_ERR_INVALID, "null frame list");
+    for (int k = 0; k < n; ++k)
+        if (!frames[k]) return fail(LT_ERR_INVALID, "lt_upload_frame_rest_list: frame %d is null", k);
+    for (int k = 0; k < n; ++k)
+        if ((rc = lt_upload_frame_rest(c, frames[k], first + k, 1))) return rc;
     return LT_OK;
 }
 

@@ -105,6 +105,12 @@ struct lt_ctx {
     uint32_t* d_pix = nullptr;
     int32_t* d_cent = nullptr;
     uint32_t* d_band_sums = nullptr;  // [slot][band][warp_w] column sums of the search bands
+    // lt_search_fit_list: the item list, staged in page-locked memory and copied to the device ahead of its search; items_ev is
+    // recorded behind the last kernel that reads the list (staging and device copy are written again only once it has fired)
+    lt_search_item* d_items = nullptr;
+    lt_search_item* h_items = nullptr;
+    int items_cap = 0;
+    hipEvent_t items_ev = nullptr;
     int maxpix = 0, maxlev = 0, maxbands = 0;
     bool have_mask = false;
     bool brute_tophat = false;

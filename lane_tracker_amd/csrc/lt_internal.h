@@ -220,6 +220,14 @@ bool launch_band_fit_one(hipStream_t s, MaskBits mb, SearchGeom g, const BandPre
 void launch_band_chain(hipStream_t s, const uint8_t* masks, size_t mask_stride, MaskBits mb, SearchGeom g, const lt_lane_record* seed_rec,
                        const BandPrev& seed, uint32_t* pix, lt_lane_record* rec, int n, const int* cancel_epoch, int my_epoch);
 
+// the searches of a list of (slot, mode, prev coefficients) items, one workgroup each (k_search_list), sliding-window items
+// first (n_sws of them; their band sums by k_band_sums_bits over the same list).  Bit-plane masks only; supported: both kernels
+// the list needs take bit planes for this geometry (null: no item of that mode).  `items` is device memory.
+bool search_list_supported(const SearchGeom* gs, const SearchGeom* gb, size_t mask_stride);
+void launch_search_list(hipStream_t s, const lt_search_item* items, int n, int n_sws, const uint8_t* masks, size_t mask_stride,
+                        MaskBits mb, const SearchGeom& gs, const SearchGeom& gb, uint32_t* band_sums, uint32_t* pix, int32_t* cent,
+                        lt_lane_record* rec);
+
 // fit of one explicit pixel list (packed (y<<16)|x); out: 3 doubles + 1 flag double (1.0 = rank deficient)
 void launch_fit_list(hipStream_t s, const uint32_t* pix, int n, int h, int w, double* out4);
 

@@ -1,0 +1,205 @@
+"""Many independent video streams, one frame each per call, on one device context: `LaneTrackerGroup`.
+
+A deployment with K cameras holds one tracker per camera and feeds each one frame at a time.  K `LaneTracker`s pay K upload +
+mask chain + search + record round trip + overlay + download per tick, each chain far too small to fill the chip.  A group
+runs the K frames of a tick as ONE batch: the camera rows of the active frames go into consecutive slots of one context
+(lt_upload_frame_rows_list, no gather on the host), one mask chain runs over them, one launch searches every frame in its own
+stream's mode around its own stream's prior fits (lt_search_fit_list), the records come back in one download, and each stream's
+state machine then runs on its record exactly as `LaneTracker.process()` runs it on its own.  Frames whose first try failed get
+the second parameter set together, in a spare slot range.  One overlay launch and one download return the annotated frames.
+
+Slots (K streams): [0, K) and [K, 2K) hold the first tries of alternate ticks, [2K, 3K) and [3K, 4K) their second tries -- the
+lane-pixel lists a stream has not read yet stay on the device until its slot comes round again (then they are fetched first), as
+`process()` alternates two slots for the same reason.
+"""
+import functools
+
+import numpy as np
+
+from . import _native
+from .lane_tracker import LaneTracker
+from .stream import StreamPipeline
+
+
+class _GroupMember(LaneTracker):
+    """One stream of a `LaneTrackerGroup`: every public attribute of `LaneTracker`, `get_state()` / `set_state()` and
+    `get_success_ratio()`, on the group's device context.  It owns no context, so it cannot process frames itself."""
+
+    _search_cus_set = True          # (the group's context never runs the chained stream pipeline: no CUs to reserve)
+
+    def __init__(self, group, *args, **kwargs):
+        self._group_ctx = group._ctx
+        super().__init__(*args, **kwargs)
+
+    def _make_context(self, device):
+        return self._group_ctx
+
+    def _not_owned(self, *args, **kwargs):
+        raise RuntimeError("a LaneTrackerGroup member does not own a device context: feed its frames through the group's process()")
+
+    # (wraps: process()'s signature stays LaneTracker.process's -- _batch_arguments reads the keywords and defaults from it)
+    process = functools.wraps(LaneTracker.process)(_not_owned)
+    process_batch = process_stream = warm = _not_owned
+    _owns_context = False           # close() leaves the group's context to LaneTrackerGroup.close
+
+
+class LaneTrackerGroup:
+    """`k` independent lane trackers -- one per video stream, same calibration and history lengths -- advanced one frame each
+    per `process()` call in one batch on one device context.
+
+    For every stream i, the annotated frame and the whole tracker state after every call equal, bit for bit, what a solo
+    `LaneTracker.process()` leaves when fed the same frames; a stream whose frame is None does not move.  `trackers[i]` is
+    stream i's tracker (read its attributes, `get_state()` / `set_state()` to hand a camera over).  Not thread-safe, like
+    `LaneTracker`; groups on different threads share nothing."""
+
+    def __init__(self, k, img_size, warped_size, cam_matrix, dist_coeffs, warp_matrices, mpp_conversion, n_fail=8, n_reset=4,
+                 n_average=2, print_frame_count=False, device=0):
+        k = int(k)
+        if k < 1:
+            raise ValueError("a group needs at least one stream")
+        self.k = k
+        self.img_size, self.warped_size = img_size, warped_size
+        self._ctx = _native.Context(img_size, warped_size, cam_matrix, dist_coeffs, warp_matrices[0], device=device, capacity=4 * k)
+        self._tick = 0
+        self.trackers = []
+        try:
+            for _ in range(k):
+                self.trackers.append(_GroupMember(self, img_size, warped_size, cam_matrix, dist_coeffs, warp_matrices, mpp_conversion,
+                                                  n_fail=n_fail, n_reset=n_reset, n_average=n_average,
+                                                  print_frame_count=print_frame_count, device=device))
+        except BaseException:
+            self.close()
+            raise
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def close(self):
+        for t in self.trackers:
+            t.close()
+        if self._ctx is not None:
+            self._ctx.close()
+            self._ctx = None
+
+    # ------------------------------------------------------------------------------------------------------------------------
+    def _free_slots(self, lo, hi):
+        """Fetch every stream's lists that still lie in slots [lo, hi) before those slots take new frames."""
+        for t in self.trackers:
+            p, q = t._pending, t._pending_cent
+            if (p is not None and lo <= p[1] < hi) or (q is not None and lo <= q[1] < hi):
+                t._materialise_pending()
+
+    def _search(self, ts, base, try_, diagnostics):
+        """Search the masks in slots base, base + 1, ... -- one per tracker of `ts`, each in its own mode -- in one launch and
+        collect the records into the trackers (what _search_uploaded leaves)."""
+        items = np.zeros(len(ts), _native.SEARCH_ITEM_DTYPE)
+        modes = []
+        for j, t in enumerate(ts):
+            items[j]["slot"] = base + j
+            if t.last_detection > t.n_reset:                                  # lane_tracker.py:851
+                modes.append('sws')
+            else:
+                modes.append('bs')
+                items[j]["mode"] = 1
+                items[j]["prev_coeffs"][:3] = np.asarray(t.last_left_coeffs, np.float64).reshape(3)
+                items[j]["prev_coeffs"][3:] = np.asarray(t.last_right_coeffs, np.float64).reshape(3)
+            if diagnostics:
+                print("Using sliding window search." if modes[-1] == 'sws' else "Using band search.")
+        q = try_
+        sws = _native.search_params(window_width=q[9], window_height=q[10], search_range=q[11], mu=q[12], no_success_limit=q[13],
+                                    start_slice=q[14], ignore_sides=q[15], ignore_bottom=q[16], partial=q[18])
+        band = _native.search_params(bandwidth=q[17], ignore_bottom=q[16], partial=q[18])
+        ctx = self._ctx
+        ctx.search_fit_list(items, sws, band)
+        recs = ctx.download_records(len(ts), first=base)
+        for j, t in enumerate(ts):
+            r = recs[j]
+            t._collect_record(ctx, (r["left_coeffs"].copy(), r["right_coeffs"].copy(), bool(r["detected"]), int(r["fit_flags"])),
+                              want_centroids=(modes[j] == 'sws'), slot=base + j, lazy=True)
+            if diagnostics:
+                print("Lane pixels found." if t.detected_pixels else "No lane pixels found.")
+
+    def process(self, frames, annotate=True, **kwargs):
+        """One frame per stream: `frames[i]` (RGB u8, img_size) for stream i, or None -- stream i skips this call.  `kwargs` are
+        `LaneTracker.process()`'s keywords (one set for the whole group; visualize_search / split_view are not available).
+        Returns a list of k entries: stream i's annotated frame (views of one block), or None for a skipped stream and for
+        every stream with `annotate=False` (the states are updated identically)."""
+        if self._ctx is None:
+            raise RuntimeError("the group is closed")
+        frames = list(frames)
+        if len(frames) != self.k:
+            raise ValueError("expected %d frames (None for a stream that skips this call), got %d" % (self.k, len(frames)))
+        kw, first_try, fp = self.trackers[0]._batch_arguments(kwargs)
+        n_tries, diagnostics = kw["n_tries"], kw["diagnostics"]
+        active = [i for i, f in enumerate(frames) if f is not None]
+        outs = [None] * self.k
+        if not active:
+            return outs
+        shape = (self._ctx.img_h, self._ctx.img_w, 3)
+        imgs = [np.ascontiguousarray(frames[i], np.uint8) for i in active]
+        for img in imgs:
+            if img.shape != shape:
+                raise ValueError("expected frames of shape %r, got %r" % (shape, img.shape))
+        ts = [self.trackers[i] for i in active]
+        m, k, ctx = len(active), self.k, self._ctx
+        r = self._tick & 1
+        self._tick += 1
+        base, spare = r * k, (2 + r) * k
+        self._free_slots(base, base + m)
+
+        # 1-3: camera rows of the m frames, one mask chain, one search launch
+        keep = ctx.upload_frame_rows_list(imgs, first=base)
+        ctx.mask_run(m, fp, first=base)
+        if annotate:
+            keep_rest = ctx.upload_frame_rest_list(imgs, first=base)     # (for the overlay, beside the mask chain)
+            ts[0]._configure_overlay()
+        for t in ts:                                                     # _step's opening
+            t._open_frame()
+            t._want_out = False
+            t._device_lane = None
+        self._search(ts, base, first_try, diagnostics)
+
+        # 4: each stream's verdict on its first try (_step's pieces, run per stream on the records of the one launch)
+        fits, partials, again = [None] * m, [first_try[-1]] * m, []
+        for j, t in enumerate(ts):
+            if t.detected_pixels:
+                fits[j] = t._fit_and_check(diagnostics, "first")
+            if t._needs_second_try(n_tries, diagnostics):
+                again.append(j)
+
+        # 5: the second parameter set over the frames that need it, in the spare slots (the first tries' slots stay untouched)
+        if again:
+            second = StreamPipeline._SECOND_TRY
+            self._free_slots(spare, spare + len(again))
+            keep_again = ctx.upload_frame_rows_list([imgs[j] for j in again], first=spare)
+            ctx.mask_run(len(again), _native.filter_params(second[4], *second[:4], *second[5:9]), first=spare)
+            self._search([ts[j] for j in again], spare, second, diagnostics)
+            for j in again:
+                t = ts[j]
+                partials[j] = 1.0
+                fits[j] = None
+                if t.detected_pixels:
+                    fits[j] = t._fit_and_check(diagnostics, "second")
+            del keep_again
+
+        # the outcomes (_step's ending, deferred pictures) ...
+        deferred = []
+        for j, t in enumerate(ts):
+            if not t.valid_lane_lines:
+                if diagnostics:
+                    print("No success after all attempts.")
+                t._record_failure()
+            else:
+                t._record_success(fits[j][0], fits[j][1], partials[j])
+            if annotate:
+                deferred.append(t._deferred_picture())
+        # 6: ... drawn by one overlay launch and one download
+        if annotate:
+            for i, out in zip(active, ts[0]._render_window(deferred, base)):
+                outs[i] = out
+            del keep_rest
+        del keep
+        return outs

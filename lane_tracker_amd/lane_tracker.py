@@ -106,7 +106,7 @@ class LaneTracker(StreamPipeline):
 
         # device side
         self.device = device
-        self._ctx = _native.Context(img_size, warped_size, cam_matrix, dist_coeffs, self.M, device=device, capacity=2)
+        self._ctx = self._make_context(device)
         global _live_trackers
         _live_trackers += 1
         self._closed = False
@@ -125,6 +125,11 @@ class LaneTracker(StreamPipeline):
         # rows the uploads bring by a row or two (so that the lane's rows need no upload of their own), and a frame uploaded before
         # that would lack them
         self._configure_overlay()
+
+    _owns_context = True        # False: the context is someone else's (a LaneTrackerGroup member) and close() leaves it open
+
+    def _make_context(self, device):
+        return _native.Context(self.img_size, self.warped_size, self.cam_matrix, self.dist_coeffs, self.M, device=device, capacity=2)
 
     # ------------------------------------------------------------------------------------------
     def get_success_ratio(self):
@@ -251,7 +256,8 @@ class LaneTracker(StreamPipeline):
                 self._group = None
         except Exception:
             pass
-        self._ctx.close()
+        if self._owns_context:
+            self._ctx.close()
         for c in self._aux_ctx.values():
             c.close()
         self._aux_ctx = {}
@@ -276,7 +282,11 @@ class LaneTracker(StreamPipeline):
         """Pull the lane record of `slot`.  The pixel lists (self.left_y/left_x/right_y/right_x) and
         window centroids are fetched right away, or -- in the stream pipeline, `lazy=True` -- only if
         somebody reads them before the slot is reused (the state machine itself needs the record only)."""
-        lf, rf, self.detected_pixels, flags = ctx.download_record(slot)
+        self._collect_record(ctx, ctx.download_record(slot), want_centroids, slot, lazy)
+
+    def _collect_record(self, ctx, record, want_centroids, slot, lazy):
+        """_collect_search with the record of `slot` already on the host: (left coeffs, right coeffs, detected, fit_flags)."""
+        lf, rf, self.detected_pixels, flags = record
         self._fit_flags = flags
         if not self.detected_pixels:
             self._fit = None        # like the reference, a failed search leaves the previous pixel lists in place
@@ -1140,9 +1150,7 @@ class LaneTracker(StreamPipeline):
         annotated frame is not produced here: ('lane', polygon, text) or ('fail', None, text) is appended
         and the caller renders all frames of the window in one overlay launch."""
         partial = first_try[-1]
-        self.counter += 1
-        self.detected_pixels = False
-        self.valid_lane_lines = False
+        self._open_frame()
         left_fit_coeffs = right_fit_coeffs = None
         used = first_try                      # the parameter set of the most recent attempt
         self._want_out = annotate and defer is None
@@ -1164,19 +1172,14 @@ class LaneTracker(StreamPipeline):
             if not self.valid_lane_lines:
                 spec = self._lane_in_flight = None      # drawn for nothing: whatever is presented later draws everything again
 
-        if ((not self.detected_pixels) or (not self.valid_lane_lines)) and ((n_tries >= 2) or (n_tries == -1)):
-            if diagnostics:
-                print("No success at first attempt, now trying second.")
+        if self._needs_second_try(n_tries, diagnostics):
             partial = 1.0                                               # the second parameter set (:1081-1099)
             second_try = self._SECOND_TRY
             used = second_try
             search_mode = self._find_lane_points_device(img, *second_try, diagnostics, reuse_frame=True, slot=slot,
                                                         lazy=lazy)
             if self.detected_pixels:
-                left_fit_coeffs, right_fit_coeffs = self.fit_poly()
-                self.check_validity(left_fit_coeffs, right_fit_coeffs, diagnostics)
-                if diagnostics and self.valid_lane_lines:
-                    print("Success at second attempt!")
+                left_fit_coeffs, right_fit_coeffs = self._fit_and_check(diagnostics, "second")
 
         search_visualization = warped_img = None
         if visualize_search or split_view:                              # :1130-1137
@@ -1208,11 +1211,10 @@ class LaneTracker(StreamPipeline):
             self._record_failure()
             if not annotate:
                 return None
-            redraw = (self.left_avg_y.size != 0) and (self.last_detection <= self.n_fail)
             if defer is not None:
-                defer.append(('lane', (self.left_avg_y, self.left_avg_x, self.right_avg_y, self.right_avg_x),
-                              self._lane_text()) if redraw else ('fail', None, self._failure_text()))
+                defer.append(self._deferred_picture())
                 return None
+            redraw = (self.left_avg_y.size != 0) and (self.last_detection <= self.n_fail)
             return present(self.draw_lane(img) if redraw else self.print_failure(img))
 
         # success (:1178-1209)
@@ -1226,10 +1228,38 @@ class LaneTracker(StreamPipeline):
         if not annotate:
             return None
         if defer is not None:
-            defer.append(('lane', (self.left_avg_y, self.left_avg_x, self.right_avg_y, self.right_avg_x),
-                          self._lane_text()))
+            defer.append(self._deferred_picture())
             return None
         return present(self.draw_lane(img))
+
+    # ---- pieces of _step that a caller running the searches itself reuses (LaneTrackerGroup) ------------------------------
+    def _open_frame(self):
+        self.counter += 1
+        self.detected_pixels = False
+        self.valid_lane_lines = False
+
+    def _needs_second_try(self, n_tries, diagnostics):
+        """After the first try: does this frame get the second parameter set (:1071-1080)?"""
+        if ((not self.detected_pixels) or (not self.valid_lane_lines)) and ((n_tries >= 2) or (n_tries == -1)):
+            if diagnostics:
+                print("No success at first attempt, now trying second.")
+            return True
+        return False
+
+    def _fit_and_check(self, diagnostics, attempt):
+        """fit_poly + check_validity of a try whose search found pixels -> the fit."""
+        left_fit_coeffs, right_fit_coeffs = self.fit_poly()
+        self.check_validity(left_fit_coeffs, right_fit_coeffs, diagnostics)
+        if diagnostics and self.valid_lane_lines:
+            print("Success at %s attempt!" % attempt)
+        return left_fit_coeffs, right_fit_coeffs
+
+    def _deferred_picture(self):
+        """The recorded frame's picture for a later overlay launch: ('lane', polygon, text) -- its lane, or the last averaged
+        lane redrawn for up to n_fail failures -- or ('fail', None, text) (what draw_lane / print_failure would draw)."""
+        if self.valid_lane_lines or ((self.left_avg_y.size != 0) and (self.last_detection <= self.n_fail)):
+            return ('lane', (self.left_avg_y, self.left_avg_x, self.right_avg_y, self.right_avg_x), self._lane_text())
+        return ('fail', None, self._failure_text())
 
 
 def _mean_of_rows(rows):
