@@ -1520,15 +1520,26 @@ bool sws2_eligible(const SearchGeom& g, size_t mask_stride) {
            (L.total <= 48 * 1024 || sws2_big_lds());
 }
 
+// launch sizes shared by every launcher of the band body (k_band_fit2, k_band_chain2, k_search_list)
+int band2_nq(const SearchGeom& g) { return (int)((2LL * (long long)g.bandwidth + 2 + 3 + 15) / 16); }   // 16-byte pieces covering a row's band from (a & ~3)
+size_t band2_lds(const SearchGeom& g) { return band2_mom_offset(std::max(g.band_bottom - g.band_top, 0)) + 16 * sizeof(long long); }
+
 // k_band_fit2: a band of at most 64 columns (2 * bandwidth + 2), dword rows, 32-bit row moments
 bool band2_eligible(const SearchGeom& g, size_t mask_stride) {
     static const bool v1 = env_flag("LT_BAND_V1");
     const bool vec4 = (g.w & 3) == 0 && (mask_stride & 3) == 0;
     const int nrows = std::max(g.band_bottom - g.band_top, 0);
     const long long width = 2LL * (long long)g.bandwidth + 2;
-    const size_t lds = band2_mom_offset(nrows) + 16 * sizeof(long long);
+    const size_t lds = band2_lds(g);
     return !v1 && vec4 && width <= 64 && g.h <= 8192 && g.w >= 16 && lds <= 150 * 1024 && band2_block_words(nrows) <= (long long)g.maxpix &&
            (lds <= 48 * 1024 || band2_big_lds());
+}
+
+// k_band_sums_bits: LDS of its BSB_ROWS bit rows, with the opt-in above 48 KB (<= 128 KB at w = 4096)
+size_t band_sums_bits_lds(const MaskBits& mb) {
+    static const bool big = allow_big_lds(k_band_sums_bits);
+    (void)big;
+    return (size_t)BSB_ROWS * mb.wpr * sizeof(unsigned long long);
 }
 
 }  // namespace
@@ -1541,10 +1552,7 @@ void launch_sws_fit(hipStream_t s, const uint8_t* masks, size_t mask_stride, Mas
     if (n <= 0) return;
     const bool vec4 = (g.w & 3) == 0 && (mask_stride & 3) == 0, v2 = sws2_eligible(g, mask_stride);
     if (mb.bits && v2) {
-        const size_t lds = (size_t)BSB_ROWS * mb.wpr * sizeof(unsigned long long);   // <= 128 KB at w = 4096
-        static const bool big = allow_big_lds(k_band_sums_bits);
-        (void)big;
-        hipLaunchKernelGGL(k_band_sums_bits, dim3(1, g.nbands, n), dim3(BSB_NT), lds, s, mb, g, band_sums,
+        hipLaunchKernelGGL(k_band_sums_bits, dim3(1, g.nbands, n), dim3(BSB_NT), band_sums_bits_lds(mb), s, mb, g, band_sums,
                            (const lt_search_item*)nullptr);
     } else {
         dim3 sgrid(((vec4 ? g.w / 4 : g.w) + 63) / 64, g.nbands, n);
@@ -1552,17 +1560,14 @@ void launch_sws_fit(hipStream_t s, const uint8_t* masks, size_t mask_stride, Mas
         else hipLaunchKernelGGL(k_band_sums<false>, sgrid, dim3(64, BS_RG), 0, s, masks, mask_stride, g, band_sums);
     }
     if (v2) {
-        const Sws2Layout L = sws2_layout(g);
-        {
-            const bool narrow = 2 * g.hw <= 32;
-            const size_t lds = (size_t)L.total;
+        const bool narrow = 2 * g.hw <= 32;
+        const size_t lds = (size_t)sws2_layout(g).total;
 #define LT_LAUNCH_SWS2(ND_, BITS_) \
     hipLaunchKernelGGL((k_sws_fit2<ND_, BITS_>), dim3(n), dim3(NT), lds, s, masks, mask_stride, mb, g, band_sums, pix, cent, rec)
-            if (mb.bits) { if (narrow) LT_LAUNCH_SWS2(9, true); else LT_LAUNCH_SWS2(17, true); }
-            else { if (narrow) LT_LAUNCH_SWS2(9, false); else LT_LAUNCH_SWS2(17, false); }
+        if (mb.bits) { if (narrow) LT_LAUNCH_SWS2(9, true); else LT_LAUNCH_SWS2(17, true); }
+        else { if (narrow) LT_LAUNCH_SWS2(9, false); else LT_LAUNCH_SWS2(17, false); }
 #undef LT_LAUNCH_SWS2
-            return;
-        }
+        return;
     }
     const size_t words = (size_t)(2 * g.w + 1 + 4 * g.wh + 2);
     const size_t lds = ((words * 4 + 15) & ~(size_t)15) + 16 * sizeof(long long);
@@ -1575,14 +1580,11 @@ void launch_band_fit(hipStream_t s, const uint8_t* masks, size_t mask_stride, Ma
     if (n <= 0) return;
     const bool vec4 = (g.w & 3) == 0 && (mask_stride & 3) == 0;
     if (band2_eligible(g, mask_stride)) {
-        const int nrows = std::max(g.band_bottom - g.band_top, 0);
-        const size_t lds2 = band2_mom_offset(nrows) + 16 * sizeof(long long);
-        {
-            const int nq = (int)((2LL * (long long)g.bandwidth + 2 + 3 + 15) / 16);   // 16-byte pieces covering a row's band from (a & ~3)
-            if (mb.bits) hipLaunchKernelGGL(k_band_fit2<true>, dim3(n), dim3(NT), lds2, s, masks, mask_stride, mb, g, prev, bp, pix, rec, nq);
-            else hipLaunchKernelGGL(k_band_fit2<false>, dim3(n), dim3(NT), lds2, s, masks, mask_stride, mb, g, prev, bp, pix, rec, nq);
-            return;
-        }
+        const size_t lds2 = band2_lds(g);
+        const int nq = band2_nq(g);
+        if (mb.bits) hipLaunchKernelGGL(k_band_fit2<true>, dim3(n), dim3(NT), lds2, s, masks, mask_stride, mb, g, prev, bp, pix, rec, nq);
+        else hipLaunchKernelGGL(k_band_fit2<false>, dim3(n), dim3(NT), lds2, s, masks, mask_stride, mb, g, prev, bp, pix, rec, nq);
+        return;
     }
     const size_t words = (size_t)(4 * g.h + 2) + 4;  // + 4 words for the distinct-row reduction
     const size_t lds = ((words * 4 + 15) & ~(size_t)15) + 16 * sizeof(long long);
@@ -1604,17 +1606,13 @@ void launch_search_list(hipStream_t s, const lt_search_item* items, int n, int n
     if (n <= 0) return;
     size_t lds = 0;
     if (n_sws > 0) {
-        const size_t bs_lds = (size_t)BSB_ROWS * mb.wpr * sizeof(unsigned long long);
-        static const bool big = allow_big_lds(k_band_sums_bits);
-        (void)big;
-        hipLaunchKernelGGL(k_band_sums_bits, dim3(1, gs.nbands, n_sws), dim3(BSB_NT), bs_lds, s, mb, gs, band_sums, items);
+        hipLaunchKernelGGL(k_band_sums_bits, dim3(1, gs.nbands, n_sws), dim3(BSB_NT), band_sums_bits_lds(mb), s, mb, gs, band_sums, items);
         lds = (size_t)sws2_layout(gs).total;
     }
     int nq = 0;
     if (n_sws < n) {
-        const int nrows = std::max(gb.band_bottom - gb.band_top, 0);
-        lds = std::max(lds, band2_mom_offset(nrows) + 16 * sizeof(long long));
-        nq = (int)((2LL * (long long)gb.bandwidth + 2 + 3 + 15) / 16);
+        lds = std::max(lds, band2_lds(gb));
+        nq = band2_nq(gb);
     }
     static const bool big = allow_big_lds(k_search_list<9, true>) && allow_big_lds(k_search_list<17, true>);
     (void)big;
@@ -1643,9 +1641,6 @@ bool launch_band_fit_one(hipStream_t s, MaskBits mb, SearchGeom g, const BandPre
 void launch_band_chain(hipStream_t s, const uint8_t* masks, size_t mask_stride, MaskBits mb, SearchGeom g, const lt_lane_record* seed_rec,
                        const BandPrev& seed, uint32_t* pix, lt_lane_record* rec, int n, const int* cancel_epoch, int my_epoch) {
     if (n <= 0) return;
-    const int nrows = std::max(g.band_bottom - g.band_top, 0);
-    const size_t lds2 = band2_mom_offset(nrows) + 16 * sizeof(long long);
-    const int nq = (int)((2LL * (long long)g.bandwidth + 2 + 3 + 15) / 16);
     static const bool v2 = env_flag("LT_CHAIN_V2");      // A/B: the first chained kernel (the body of k_band_fit2 in a loop)
     const size_t lds3 = (size_t)C3_VALUES * CT * sizeof(long long);
     static const bool big3 = allow_big_lds(k_band_chain3);
@@ -1660,6 +1655,8 @@ void launch_band_chain(hipStream_t s, const uint8_t* masks, size_t mask_stride, 
                            (lt_lane_record*)nullptr, 0u);
         return;
     }
+    const size_t lds2 = band2_lds(g);
+    const int nq = band2_nq(g);
     if (mb.bits) hipLaunchKernelGGL(k_band_chain2<true>, dim3(1), dim3(NT), lds2, s, masks, mask_stride, mb, g, seed_rec, seed, pix, rec, nq, n, cancel_epoch, my_epoch);
     else hipLaunchKernelGGL(k_band_chain2<false>, dim3(1), dim3(NT), lds2, s, masks, mask_stride, mb, g, seed_rec, seed, pix, rec, nq, n, cancel_epoch, my_epoch);
 }

@@ -145,6 +145,14 @@ int flush_stage_events(lt_ctx* c) {
     return LT_OK;
 }
 
+int wait_tail(lt_ctx* c, hipStream_t waiter, hipStream_t st) {
+    hipEvent_t e = next_order_event(c);
+    if (!e) return fail(LT_ERR_HIP, "hipEventCreate failed");
+    HIP_TRY(hipEventRecord(e, st));
+    HIP_TRY(hipStreamWaitEvent(waiter, e, 0));
+    return LT_OK;
+}
+
 hipEvent_t next_order_event(lt_ctx* c) {
     constexpr size_t RING = 64;
     if (c->order_events.size() < RING) {
@@ -320,7 +328,7 @@ int ensure_u8_masks(lt_ctx* c, int first, int n) {
         if (c->mask_u8_ok[(size_t)i]) { ++i; continue; }
         int j = i;
         while (j < first + n && !c->mask_u8_ok[(size_t)j]) ++j;
-        launch_bits_to_u8(c->stream, c->d_bits_open + (size_t)i * c->bits_stride, c->d_plane[P_MASK] + (size_t)i * c->plane_bytes,
+        launch_bits_to_u8(c->stream, slot_bits(c, i, true).bits, slot_mask(c, i),
                           c->calib.warp_h, c->calib.warp_w, c->plane_bytes, c->bits_stride, j - i);
         for (int k = i; k < j; ++k) c->mask_u8_ok[(size_t)k] = 1;
         i = j;
@@ -579,6 +587,24 @@ int make_search_geom(lt_ctx* c, const lt_search_params* p, bool band, SearchGeom
     g.maxlev = std::max(g.nlevels, 1) + 1;
     g.nbands = std::max(g.nlevels, 1);
     return LT_OK;
+}
+
+// The set-up every search entry point shares: the geometry of `p`, search buffers large enough for it (and, for the sliding
+// window, its band sums), and the buffers' actual row sizes in the geometry -- the kernels address slots by them.
+int prepare_search(lt_ctx* c, const lt_search_params* p, bool band, SearchGeom& g) {
+    int rc = make_search_geom(c, p, band, g);
+    if (rc) return rc;
+    if ((rc = ensure_search_buffers(c, g.maxpix, band ? 1 : g.maxlev))) return rc;
+    if (!band && (rc = ensure_band_sums(c, g.nbands))) return rc;
+    g.maxpix = c->maxpix;
+    g.maxlev = c->maxlev;
+    return LT_OK;
+}
+
+// The searches read the opened bit plane of slots [first, first + n) when all of them have one and the kernel that will run for
+// this geometry takes it (mode 0: sliding window, 1: band); else the u8 masks (ensure_u8_masks).
+bool slot_reads_bits(const lt_ctx* c, const SearchGeom& g, int mode, int first, int n) {
+    return masks_have_bits(c, first, n) && (mode == 0 ? sws_fit_takes_bits(g, c->plane_bytes) : band_fit_takes_bits(g, c->plane_bytes));
 }
 
 // The streams that carry the slot slices' kernels.  The HIP runtime multiplexes the streams of a process onto a
@@ -996,7 +1022,7 @@ int lt_upload_frames(lt_ctx* c, const uint8_t* frames, int first, int n) {
     if (!frames) return fail(LT_ERR_INVALID, "null frames");
     if ((rc = set_device(c))) return rc;
     if ((rc = sync_all(c))) return rc;
-    HIP_TRY(hipMemcpyAsync(c->d_frames + (size_t)first * c->frame_bytes, frames, (size_t)n * c->frame_bytes,
+    HIP_TRY(hipMemcpyAsync(slot_frame(c, first), frames, (size_t)n * c->frame_bytes,
                            hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     mark_frames(c, first, n, 1);
@@ -1012,6 +1038,23 @@ int lt_get_source_rows(lt_ctx* c, int* row0, int* row1) {
 }
 
 static int wait_reader_tails(lt_ctx* c, hipStream_t waiter);
+
+// The preamble of the uploads of camera rows into slots [first, first + n): slots and frames valid; the device current when there
+// is anything to copy.
+static int check_upload(lt_ctx* c, const uint8_t* frames, int first, int n) {
+    int rc = check_slots(c, first, n);
+    if (rc) return rc;
+    if (!frames) return fail(LT_ERR_INVALID, "null frames");
+    return n > 0 ? set_device(c) : LT_OK;
+}
+// A stream-ordered copy into the camera rows of slots [first, first + n) waits on `st` for the kernels that still read them (slot-range
+// events), or -- where the ring does not know them all -- for the tails of every stream such a kernel can be on.
+static int wait_camera_readers(lt_ctx* c, hipStream_t st, int first, int n) {
+    bool precise = true;
+    int rc = wait_range(c->readers, st, first, first + n, &precise);
+    if (!rc && !precise) rc = wait_reader_tails(c, st);
+    return rc;
+}
 
 // ---- one frame's rows through the PCIe aperture ----------------------------------------------------------------------------------
 // With a large BAR the whole device memory is mapped into the process, write-combining, at the addresses hipMalloc hands out: the
@@ -1116,11 +1159,8 @@ int lt_set_direct_upload(lt_ctx* c, int on) {
 unsigned long long lt_direct_upload_count(lt_ctx* c) { return c ? c->direct_uploads : 0; }
 
 static int upload_frame_rows_impl(lt_ctx* c, const uint8_t* frames, int first, int n, bool enqueue) {
-    int rc = check_slots(c, first, n);
-    if (rc) return rc;
-    if (!frames) return fail(LT_ERR_INVALID, "null frames");
-    if (n == 0 || c->cam_r1 <= c->cam_r0) return LT_OK;
-    if ((rc = set_device(c))) return rc;
+    int rc = check_upload(c, frames, first, n);
+    if (rc || n == 0 || c->cam_r1 <= c->cam_r0) return rc;
     // The enqueued form waits for nothing on the host: the copy goes onto the slots' own streams (behind everything launched over
     // these slots there) and, like lt_upload_frame_rows_async's, behind the kernels of OTHER streams that still read the slots'
     // camera rows -- overlays on the presentation stream (slot-range events).  LT_UPLOAD_SYNC=1: wait for the whole context first, as
@@ -1141,28 +1181,26 @@ static int upload_frame_rows_impl(lt_ctx* c, const uint8_t* frames, int first, i
         // a frame or two, and nothing left on the device that reads these slots' rows: by this thread's own stores (above); the
         // caller's array is free again when the call returns
         for (int k = 0; k < n; ++k)
-            store_through_aperture(c->d_frames + (size_t)(first + k) * c->frame_bytes + off, frames + (size_t)k * c->frame_bytes + off, bytes);
+            store_through_aperture(slot_frame(c, first + k) + off, frames + (size_t)k * c->frame_bytes + off, bytes);
         ++c->direct_uploads;
         return LT_OK;
     }
     if (enqueue)
         return for_each_slice(c, first, n, [&](hipStream_t st, int f0, int m) {
             if (!enqueue_syncs) {
-                bool precise = true;
-                int wrc = wait_range(c->readers, st, f0, f0 + m, &precise);
+                const int wrc = wait_camera_readers(c, st, f0, m);
                 if (wrc) return wrc;
-                if (!precise && (wrc = wait_reader_tails(c, st))) return wrc;
             }
             // (the rows in two to four pieces, so that the engine's copy of one runs under the runtime's staging of the next: measured
             // SLOWER, 195-218 against 183-186 us per 1280x720 frame -- every piece pays the call again; NOTES_r06 E.2)
-            HIP_TRY(hipMemcpy2DAsync(c->d_frames + (size_t)f0 * c->frame_bytes + off, c->frame_bytes, frames + off, c->frame_bytes,
+            HIP_TRY(hipMemcpy2DAsync(slot_frame(c, f0) + off, c->frame_bytes, frames + off, c->frame_bytes,
                                      bytes, (size_t)m, hipMemcpyHostToDevice, st));
             // (where a later small call could take the aperture, this copy counts as work on the slots' rows that the host has not
             // seen finished: stores from the host must not be overtaken by it)
             if (c->direct_upload == 1 && (size_t)m * bytes <= APERTURE_MAX_BYTES) return note_range_frame(c, c->readers, st, f0, f0 + m);
             return (int)LT_OK;
         });
-    HIP_TRY(hipMemcpy2DAsync(c->d_frames + (size_t)first * c->frame_bytes + off, c->frame_bytes, frames + off, c->frame_bytes,
+    HIP_TRY(hipMemcpy2DAsync(slot_frame(c, first) + off, c->frame_bytes, frames + off, c->frame_bytes,
                              bytes, (size_t)n, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return LT_OK;
@@ -1176,14 +1214,7 @@ int lt_upload_frame_rows_enqueue(lt_ctx* c, const uint8_t* frames, int first, in
 // and the urgent stream.
 static int wait_reader_tails(lt_ctx* c, hipStream_t waiter) {
     const bool slices_only = !c->readers.overflow;     // (only `lazy`: the unrecorded readers are on the slots' streams)
-    auto tail = [&](hipStream_t st) {
-        if (!st || st == waiter) return (int)LT_OK;
-        hipEvent_t e = next_order_event(c);
-        if (!e) return fail(LT_ERR_HIP, "hipEventCreate failed");
-        HIP_TRY(hipEventRecord(e, st));
-        HIP_TRY(hipStreamWaitEvent(waiter, e, 0));
-        return (int)LT_OK;
-    };
+    auto tail = [&](hipStream_t st) { return !st || st == waiter ? (int)LT_OK : wait_tail(c, waiter, st); };
     for (int i = 0; i < c->nstreams && i < (int)c->streams.size(); ++i) { const int rc = tail(c->streams[i]); if (rc) return rc; }
     if (slices_only) return LT_OK;
     int rc = tail(c->present);
@@ -1195,20 +1226,15 @@ static int wait_reader_tails(lt_ctx* c, hipStream_t waiter) {
 // enqueued on the streams that own these slots (their previous occupants), and those streams wait for it before
 // anything enqueued later -- so the upload of one slot range overlaps the chain of every other slot range.
 int lt_upload_frame_rows_async(lt_ctx* c, const uint8_t* frames, int first, int n) {
-    int rc = check_slots(c, first, n);
-    if (rc) return rc;
-    if (!frames) return fail(LT_ERR_INVALID, "null frames");
-    if (n == 0 || c->cam_r1 <= c->cam_r0) return LT_OK;
-    if ((rc = set_device(c))) return rc;
+    int rc = check_upload(c, frames, first, n);
+    if (rc || n == 0 || c->cam_r1 <= c->cam_r0) return rc;
     mark_frames(c, first, n, 0);
     front_stale(c, first, n);
     // the copy waits for the kernels that still read these slots' camera rows (the undistortion launches over these slots, the
     // overlay) -- not for the rest of their mask chains, and not for launches over other slots
-    bool precise = true;
-    if ((rc = wait_range(c->readers, c->copy, first, first + n, &precise))) return rc;
-    if (!precise && (rc = wait_reader_tails(c, c->copy))) return rc;
+    if ((rc = wait_camera_readers(c, c->copy, first, n))) return rc;
     const size_t row_bytes = (size_t)c->calib.img_w * 3, off = (size_t)c->cam_r0 * row_bytes;
-    HIP_TRY(hipMemcpy2DAsync(c->d_frames + (size_t)first * c->frame_bytes + off, c->frame_bytes, frames + off, c->frame_bytes,
+    HIP_TRY(hipMemcpy2DAsync(slot_frame(c, first) + off, c->frame_bytes, frames + off, c->frame_bytes,
                              (size_t)(c->cam_r1 - c->cam_r0) * row_bytes, (size_t)n, hipMemcpyHostToDevice, c->copy));
     hipEvent_t up = next_order_event(c);
     if (!up) return fail(LT_ERR_HIP, "hipEventCreate failed");
@@ -1230,23 +1256,17 @@ static int rest_mark(lt_ctx* c, int first, int n) {
 
 int lt_upload_frame_rest_rows(lt_ctx* c, const uint8_t* frames, int first, int n, const int32_t* rows4) {
     if (!rows4) return lt_upload_frame_rest(c, frames, first, n);
-    int rc = check_slots(c, first, n);
+    int rc = check_upload(c, frames, first, n);
     if (rc) return rc;
-    if (!frames) return fail(LT_ERR_INVALID, "null frames");
     const int H = c->calib.img_h;
     if (!(0 <= rows4[0] && rows4[0] <= rows4[1] && rows4[1] <= rows4[2] && rows4[2] <= rows4[3] && rows4[3] <= H))
         return fail(LT_ERR_INVALID, "row runs must be ordered and inside the frame");
     if (n == 0) return LT_OK;
-    if ((rc = set_device(c))) return rc;
-    {
-        bool precise = true;
-        if ((rc = wait_range(c->readers, c->copy, first, first + n, &precise))) return rc;
-        if (!precise && (rc = wait_reader_tails(c, c->copy))) return rc;
-    }
+    if ((rc = wait_camera_readers(c, c->copy, first, n))) return rc;
     // of the two runs, the rows lt_upload_frame_rows has not brought: below the window of rows the path reads, and above it
     const size_t row_bytes = (size_t)c->calib.img_w * 3;
     const int lo = c->cam_r1 > c->cam_r0 ? c->cam_r0 : 0, hi = c->cam_r1 > c->cam_r0 ? c->cam_r1 : 0;
-    uint8_t* dst = c->d_frames + (size_t)first * c->frame_bytes;
+    uint8_t* dst = slot_frame(c, first);
     for (int k = 0; k < 4; k += 2) {
         const int piece[2][2] = {{rows4[k], std::min(rows4[k + 1], lo)}, {std::max(rows4[k], hi), rows4[k + 1]}};
         for (const auto& pc : piece) {
@@ -1259,21 +1279,14 @@ int lt_upload_frame_rest_rows(lt_ctx* c, const uint8_t* frames, int first, int n
 }
 
 int lt_upload_frame_rest(lt_ctx* c, const uint8_t* frames, int first, int n) {
-    int rc = check_slots(c, first, n);
-    if (rc) return rc;
-    if (!frames) return fail(LT_ERR_INVALID, "null frames");
-    if (n == 0) return LT_OK;
-    if ((rc = set_device(c))) return rc;
+    int rc = check_upload(c, frames, first, n);
+    if (rc || n == 0) return rc;
     // these rows are read by nobody but the overlay: the copy waits for the overlays still reading the frames it replaces
     // (slot-range events; a stream of windows re-uses its slots), and the overlay of these slots waits for it
-    {
-        bool precise = true;
-        if ((rc = wait_range(c->readers, c->copy, first, first + n, &precise))) return rc;
-        if (!precise && (rc = wait_reader_tails(c, c->copy))) return rc;
-    }
+    if ((rc = wait_camera_readers(c, c->copy, first, n))) return rc;
     const size_t row_bytes = (size_t)c->calib.img_w * 3;
     const size_t head = (size_t)c->cam_r0 * row_bytes, tail0 = (size_t)c->cam_r1 * row_bytes;
-    uint8_t* dst = c->d_frames + (size_t)first * c->frame_bytes;
+    uint8_t* dst = slot_frame(c, first);
     if (c->cam_r1 <= c->cam_r0) {
         HIP_TRY(hipMemcpyAsync(dst, frames, (size_t)n * c->frame_bytes, hipMemcpyHostToDevice, c->copy));
         mark_frames(c, first, n, 1);
@@ -1295,7 +1308,7 @@ int lt_upload_masks(lt_ctx* c, const uint8_t* masks, int first, int n) {
     if ((rc = set_device(c))) return rc;
     if ((rc = sync_all(c))) return rc;
     if ((rc = ensure_plane(c, P_MASK))) return rc;
-    HIP_TRY(hipMemcpyAsync(c->d_plane[P_MASK] + (size_t)first * c->plane_bytes, masks, (size_t)n * c->plane_bytes,
+    HIP_TRY(hipMemcpyAsync(slot_mask(c, first), masks, (size_t)n * c->plane_bytes,
                            hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->have_mask = true;
@@ -1352,7 +1365,7 @@ int lt_download_masks(lt_ctx* c, int first, int n, uint8_t* masks) {
     if (rc) return rc;
     if ((rc = set_device(c))) return rc;
     if ((rc = ensure_u8_masks(c, first, n))) return rc;
-    return download(c, c->d_plane[P_MASK] + (size_t)first * c->plane_bytes, masks, (size_t)n * c->plane_bytes);
+    return download(c, slot_mask(c, first), masks, (size_t)n * c->plane_bytes);
 }
 
 int lt_download_plane(lt_ctx* c, int plane, int first, int n, uint8_t* out) {
@@ -1475,7 +1488,7 @@ static void mirror_record(lt_ctx* c, hipStream_t st, int slot) {
     static_assert(sizeof(lt_lane_record) == 64, "k_mirror_record copies 16 words and stores the ticket behind them");
     unsigned ticket = ++c->rec_ticket_counter;
     if (!ticket) ticket = ++c->rec_ticket_counter;          // 0 means "no ticket"
-    if (rec_mirror_device(c) && launch_mirror_record(st, c->h_rec, c->d_rec + slot, ticket)) {
+    if (rec_mirror_device(c) && launch_mirror_record(st, c->h_rec, slot_rec(c, slot), ticket)) {
         c->rec_mirror_slot = slot;
         c->rec_mirror_stream = st;
         c->rec_ticket = ticket;
@@ -1505,7 +1518,7 @@ int lt_download_records(lt_ctx* c, int first, int n, lt_lane_record* out) {
         std::memcpy(out, c->h_rec, sizeof(lt_lane_record));
         return LT_OK;
     }
-    return download(c, c->d_rec + first, out, (size_t)n * sizeof(lt_lane_record));
+    return download(c, slot_rec(c, first), out, (size_t)n * sizeof(lt_lane_record));
 }
 
 // The lane pixels of one side of a slot, expanded from the form the search kernels leave on the device (`region`: a host copy of the
@@ -1582,8 +1595,8 @@ int lt_download_pixels(lt_ctx* c, int slot, int side, int32_t* ys, int32_t* xs, 
     if (side < 0 || side > 1 || !count || cap < 0) return fail(LT_ERR_INVALID, "bad side/count/cap");
     if (!c->d_pix) return fail(LT_ERR_STATE, "no search has run yet");
     lt_lane_record r;
-    if ((rc = download(c, c->d_rec + slot, &r, sizeof r))) return rc;
-    const uint32_t* block = c->d_pix + (size_t)slot * 2 * c->maxpix;
+    if ((rc = download(c, slot_rec(c, slot), &r, sizeof r))) return rc;
+    const uint32_t* block = slot_pix(c, slot);
     size_t words = 0;
     if (r._pad == 1 || r._pad == 2) {
         uint32_t hdr[4];
@@ -1634,9 +1647,9 @@ int lt_download_lane_lists(lt_ctx* c, int slot, int32_t* ly, int32_t* lx, int32_
     if (c->urgent_on && c->urgent) st = c->urgent;      // as in download(): what is asked for was produced on the urgent stream (or is complete)
     else if ((rc = sync_all(c))) return rc;
     uint8_t* h = c->h_lists;
-    bool ok = launch_copy_words_to_pinned(st, h, c->d_rec + slot, sizeof(lt_lane_record)) &&
-              launch_copy_words_to_pinned(st, h + sizeof(lt_lane_record), c->d_pix + (size_t)slot * region_words, region_words * 4);
-    if (ok && cent_words) ok = launch_copy_words_to_pinned(st, h + sizeof(lt_lane_record) + region_words * 4, c->d_cent + (size_t)slot * cent_words, cent_words * 4);
+    bool ok = launch_copy_words_to_pinned(st, h, slot_rec(c, slot), sizeof(lt_lane_record)) &&
+              launch_copy_words_to_pinned(st, h + sizeof(lt_lane_record), slot_pix(c, slot), region_words * 4);
+    if (ok && cent_words) ok = launch_copy_words_to_pinned(st, h + sizeof(lt_lane_record) + region_words * 4, slot_cent(c, slot), cent_words * 4);
     if (!ok) return fail(LT_ERR_HIP, "lt_download_lane_lists: the copy launches were refused");
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));
@@ -1666,7 +1679,7 @@ int lt_download_centroids(lt_ctx* c, int slot, int side, int32_t* out, int cap, 
     if (side < 0 || side > 1 || !count || cap < 0 || (cap > 0 && !out)) return fail(LT_ERR_INVALID, "bad side/count/cap/out");
     if (!c->d_cent) return fail(LT_ERR_STATE, "no sliding-window search has run yet");
     std::vector<int32_t> tmp((size_t)c->maxlev + 2);
-    if ((rc = download(c, c->d_cent + ((size_t)slot * 2 + side) * (c->maxlev + 2), tmp.data(), tmp.size() * 4))) return rc;
+    if ((rc = download(c, slot_cent(c, slot) + (size_t)side * (c->maxlev + 2), tmp.data(), tmp.size() * 4))) return rc;
     int n = tmp[0];
     if (n < 0) n = 0;
     if (n > c->maxlev + 1) n = c->maxlev + 1;
@@ -1681,7 +1694,7 @@ int lt_copy_records_to_device(lt_ctx* c, int first, int n, void* dst) {
     if (!dst) return fail(LT_ERR_INVALID, "null destination");
     if ((rc = set_device(c))) return rc;
     if ((rc = sync_all(c))) return rc;
-    HIP_TRY(hipMemcpyAsync(dst, c->d_rec + first, (size_t)n * sizeof(lt_lane_record), hipMemcpyDeviceToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(dst, slot_rec(c, first), (size_t)n * sizeof(lt_lane_record), hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return LT_OK;
 }
@@ -1693,7 +1706,7 @@ int lt_enqueue_records_to_device(lt_ctx* c, int first, int n, void* dst) {
     if ((rc = set_device(c))) return rc;
     // stream-ordered behind the searches of each slot slice; no host synchronisation
     rc = for_each_slice(c, first, n, [&](hipStream_t st, int f0, int m) {
-        HIP_TRY(hipMemcpyAsync(static_cast<lt_lane_record*>(dst) + (f0 - first), c->d_rec + f0, (size_t)m * sizeof(lt_lane_record),
+        HIP_TRY(hipMemcpyAsync(static_cast<lt_lane_record*>(dst) + (f0 - first), slot_rec(c, f0), (size_t)m * sizeof(lt_lane_record),
                                hipMemcpyDeviceToDevice, st));
         return (int)LT_OK;
     });
@@ -1707,9 +1720,9 @@ int lt_set_frame_base(lt_ctx* c, int first, int n, int first_frame) {
     if ((rc = set_device(c))) return rc;
     std::vector<lt_lane_record> tmp((size_t)n);
     if (n == 0) return LT_OK;
-    if ((rc = download(c, c->d_rec + first, tmp.data(), tmp.size() * sizeof(lt_lane_record)))) return rc;
+    if ((rc = download(c, slot_rec(c, first), tmp.data(), tmp.size() * sizeof(lt_lane_record)))) return rc;
     for (int i = 0; i < n; ++i) tmp[i].frame = first_frame + i;
-    HIP_TRY(hipMemcpyAsync(c->d_rec + first, tmp.data(), tmp.size() * sizeof(lt_lane_record), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(slot_rec(c, first), tmp.data(), tmp.size() * sizeof(lt_lane_record), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return LT_OK;
 }
@@ -1729,7 +1742,7 @@ static int mask_run_impl(lt_ctx* c, int first, int n, const lt_filter_params* p,
         for (int i = f0; have_front && i < f0 + m; ++i) have_front = c->front_ok[(size_t)i] != 0;
         if (!have_front) {
             { StageScope t(c, ST_UNDISTORT, st);
-              launch_undistort_rows(st, c->d_frames + (size_t)f0 * c->frame_bytes, c->frame_bytes, c->d_uxy, c->d_ufrac,
+              launch_undistort_rows(st, slot_frame(c, f0), c->frame_bytes, c->d_uxy, c->d_ufrac,
                                     c->fe, c->d_und, c->und_px, f0, m); }
             { int mrc = n == 1 ? note_range_frame(c, c->readers, st, f0, f0 + m) : note_range(c->readers, st, f0, f0 + m); if (mrc) return mrc; }
             { StageScope t(c, ST_WARP_SPLIT, st);
@@ -1772,6 +1785,15 @@ int lt_filter_run(lt_ctx* c, int first, int n, const lt_filter_params* p) {
     return LT_OK;
 }
 
+// the range forms' kernels over slots [f0, f0 + m), by their slot addresses (the list form's fallback: one slot at a time)
+static void launch_sws_slots(lt_ctx* c, hipStream_t st, const SearchGeom& g, const MaskBits& mb, int f0, int m) {
+    launch_sws_fit(st, slot_mask(c, f0), c->plane_bytes, mb, g, slot_band_sums(c, f0, g.nbands), slot_pix(c, f0), slot_cent(c, f0),
+                   slot_rec(c, f0), m);
+}
+static void launch_band_slots(lt_ctx* c, hipStream_t st, const SearchGeom& g, const BandPrev& bp, const MaskBits& mb, int f0, int m) {
+    launch_band_fit(st, slot_mask(c, f0), c->plane_bytes, mb, g, slot_prev(c, f0), bp, slot_pix(c, f0), slot_rec(c, f0), m);
+}
+
 int lt_sws_fit_run(lt_ctx* c, int first, int n, const lt_search_params* p) {
     int rc = check_slots(c, first, n);
     if (rc) return rc;
@@ -1779,22 +1801,13 @@ int lt_sws_fit_run(lt_ctx* c, int first, int n, const lt_search_params* p) {
     if ((rc = set_device(c))) return rc;
     if (!c->have_mask) return fail(LT_ERR_STATE, "no mask in the slots: run lt_mask_run or lt_upload_masks first");
     SearchGeom g;
-    if ((rc = make_search_geom(c, p, false, g))) return rc;
-    if ((rc = ensure_search_buffers(c, g.maxpix, g.maxlev))) return rc;
-    if ((rc = ensure_band_sums(c, g.nbands))) return rc;
-    g.maxpix = c->maxpix;
-    g.maxlev = c->maxlev;
+    if ((rc = prepare_search(c, p, false, g))) return rc;
     if (n == 0) return LT_OK;
-    // the searches read the opened bit plane when the slots have one and the kernel that will run takes it
-    const bool use_bits = masks_have_bits(c, first, n) && sws_fit_takes_bits(g, c->plane_bytes);
+    const bool use_bits = slot_reads_bits(c, g, 0, first, n);
     if (!use_bits && (rc = ensure_u8_masks(c, first, n))) return rc;
-    const int wpr = (c->calib.warp_w + 63) / 64;
     rc = for_each_slice(c, first, n, [&](hipStream_t st, int f0, int m) {
         StageScope t(c, ST_SWS_FIT, st);
-        const MaskBits mb{use_bits ? c->d_bits_open + (size_t)f0 * c->bits_stride : nullptr, c->bits_stride, wpr};
-        launch_sws_fit(st, c->d_plane[P_MASK] + (size_t)f0 * c->plane_bytes, c->plane_bytes, mb, g,
-                       c->d_band_sums + (size_t)f0 * g.nbands * c->calib.warp_w, c->d_pix + (size_t)f0 * 2 * c->maxpix,
-                       c->d_cent + (size_t)f0 * 2 * (c->maxlev + 2), c->d_rec + f0, m);
+        launch_sws_slots(c, st, g, slot_bits(c, f0, use_bits), f0, m);
         if (n == 1) mirror_record(c, st, f0);
         return note_written_frame(c, st, f0, f0 + m, n);
     });
@@ -1811,9 +1824,7 @@ int lt_band_fit_run(lt_ctx* c, int first, int n, const lt_search_params* p, cons
     if ((rc = set_device(c))) return rc;
     if (!c->have_mask) return fail(LT_ERR_STATE, "no mask in the slots: run lt_mask_run or lt_upload_masks first");
     SearchGeom g;
-    if ((rc = make_search_geom(c, p, true, g))) return rc;
-    if ((rc = ensure_search_buffers(c, g.maxpix, 1))) return rc;
-    g.maxpix = c->maxpix;
+    if ((rc = prepare_search(c, p, true, g))) return rc;
     if (n == 0) return LT_OK;
     BandPrev bp;
     std::memset(&bp, 0, sizeof bp);
@@ -1824,31 +1835,29 @@ int lt_band_fit_run(lt_ctx* c, int first, int n, const lt_search_params* p, cons
         bp.by_value = 1;
     } else {
         if ((rc = sync_all(c))) return rc;
-        HIP_TRY(hipMemcpyAsync(c->d_prev + (size_t)first * 6, prev, (size_t)n * 6 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(slot_prev(c, first), prev, (size_t)n * 6 * sizeof(double), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));  // prev is caller memory: do not keep reading it after return
     }
-    const bool use_bits = masks_have_bits(c, first, n) && band_fit_takes_bits(g, c->plane_bytes);
+    const bool use_bits = slot_reads_bits(c, g, 1, first, n);
     if (!use_bits && (rc = ensure_u8_masks(c, first, n))) return rc;
-    const int wpr = (c->calib.warp_w + 63) / 64;
     rc = for_each_slice(c, first, n, [&](hipStream_t st, int f0, int m) {
         StageScope t(c, ST_BAND_FIT, st);
-        const MaskBits mb{use_bits ? c->d_bits_open + (size_t)f0 * c->bits_stride : nullptr, c->bits_stride, wpr};
+        const MaskBits mb = slot_bits(c, f0, use_bits);
         // one frame (process()): the chain kernel with a chain of one, a third of the latency (LT_BAND_ONE=0: k_band_fit2)
         const char* one_env = n == 1 ? LT_EXP_ENV("LT_BAND_ONE") : nullptr;
         lt_lane_record* mirror = n == 1 ? rec_mirror_device(c) : nullptr;
         unsigned ticket = ++c->rec_ticket_counter;
         if (!ticket) ticket = ++c->rec_ticket_counter;      // 0 means "no ticket"
         if (n == 1 && !(one_env && one_env[0] == '0') &&
-            launch_band_fit_one(st, mb, g, bp, c->d_pix + (size_t)f0 * 2 * c->maxpix, c->d_rec + f0, c->plane_bytes,
-                                reinterpret_cast<const int*>(c->d_prev), mirror, ticket)) {
+            launch_band_fit_one(st, mb, g, bp, slot_pix(c, f0), slot_rec(c, f0), c->plane_bytes, reinterpret_cast<const int*>(c->d_prev),
+                                mirror, ticket)) {
             if (mirror) {                    // the kernel itself leaves a copy of the record in page-locked memory, and its ticket
                 c->rec_mirror_slot = f0;
                 c->rec_mirror_stream = st;
                 c->rec_ticket = ticket;
             }
         } else {
-            launch_band_fit(st, c->d_plane[P_MASK] + (size_t)f0 * c->plane_bytes, c->plane_bytes, mb, g, c->d_prev + (size_t)f0 * 6, bp,
-                            c->d_pix + (size_t)f0 * 2 * c->maxpix, c->d_rec + f0, m);
+            launch_band_slots(c, st, g, bp, mb, f0, m);
             if (n == 1) mirror_record(c, st, f0);
         }
         return note_written_frame(c, st, f0, f0 + m, n);
@@ -1887,16 +1896,9 @@ int lt_search_fit_list(lt_ctx* c, int n, const lt_search_item* items, const lt_s
     SearchGeom gs, gb;
     std::memset(&gs, 0, sizeof gs);
     std::memset(&gb, 0, sizeof gb);
-    if (n_sws > 0) {
-        if ((rc = make_search_geom(c, sws, false, gs))) return rc;
-        if ((rc = ensure_search_buffers(c, gs.maxpix, gs.maxlev))) return rc;
-        if ((rc = ensure_band_sums(c, gs.nbands))) return rc;
-    }
-    if (n_sws < n) {
-        if ((rc = make_search_geom(c, band, true, gb))) return rc;
-        if ((rc = ensure_search_buffers(c, gb.maxpix, 1))) return rc;
-    }
-    gs.maxpix = gb.maxpix = c->maxpix;
+    if (n_sws > 0 && (rc = prepare_search(c, sws, false, gs))) return rc;
+    if (n_sws < n && (rc = prepare_search(c, band, true, gb))) return rc;
+    gs.maxpix = gb.maxpix = c->maxpix;        // (the second preparation may have grown the buffers further)
     gs.maxlev = gb.maxlev = c->maxlev;
     // sliding-window items first (k_band_sums_bits runs over the head of the list)
     std::vector<lt_search_item> list(items, items + n);
@@ -1904,33 +1906,20 @@ int lt_search_fit_list(lt_ctx* c, int n, const lt_search_item* items, const lt_s
     bool bits = true;
     for (const auto& it : list) bits = bits && masks_have_bits(c, it.slot, 1);
     const bool one_launch = bits && search_list_supported(n_sws > 0 ? &gs : nullptr, n_sws < n ? &gb : nullptr, c->plane_bytes);
+    auto geom = [&](const lt_search_item& it) -> const SearchGeom& { return it.mode == 0 ? gs : gb; };
     if (!one_launch)
         for (const auto& it : list)
-            if (!((it.mode == 0 ? sws_fit_takes_bits(gs, c->plane_bytes) : band_fit_takes_bits(gb, c->plane_bytes)) && masks_have_bits(c, it.slot, 1)) &&
-                (rc = ensure_u8_masks(c, it.slot, 1)))
-                return rc;
+            if (!slot_reads_bits(c, geom(it), it.mode, it.slot, 1) && (rc = ensure_u8_masks(c, it.slot, 1))) return rc;
     // the stream: the urgent one in urgent mode, else the stream of the first listed slot; the other slot streams in front of it
-    const int k = std::max(1, std::min(c->nstreams, c->capacity));
-    auto slice_of = [&](int s) {
-        for (int si = 0; si < k; ++si) {
-            const int b = si + 1 == k ? c->capacity : (int)((long long)c->capacity * (si + 1) / k) & ~1;
-            if (s < b) return si;
-        }
-        return k - 1;
-    };
+    const int k = slice_count(c);
     std::vector<uint8_t> touched((size_t)k, 0);
-    for (const auto& it : list) touched[(size_t)slice_of(it.slot)] = 1;
-    hipStream_t st = c->urgent_on && c->urgent ? c->urgent : c->streams[(size_t)slice_of(list[0].slot)];
+    for (const auto& it : list) touched[(size_t)slice_of(c, it.slot)] = 1;
+    hipStream_t st = c->urgent_on && c->urgent ? c->urgent : c->streams[(size_t)slice_of(c, list[0].slot)];
     for (int si = 0; si < k; ++si) {
-        if (!touched[(size_t)si] || c->streams[(size_t)si] == st) continue;
-        hipEvent_t e = next_order_event(c);
-        if (!e) return fail(LT_ERR_HIP, "hipEventCreate failed");
-        HIP_TRY(hipEventRecord(e, c->streams[(size_t)si]));
-        HIP_TRY(hipStreamWaitEvent(st, e, 0));
+        if (touched[(size_t)si] && c->streams[(size_t)si] != st && (rc = wait_tail(c, st, c->streams[(size_t)si]))) return rc;
     }
     for (const auto& it : list)
         if ((rc = wait_chains(c, st, it.slot, it.slot + 1))) return rc;
-    const int wpr = (c->calib.warp_w + 63) / 64;
     if (one_launch) {
         if (n > c->items_cap) {
             if (c->items_ev) HIP_TRY(hipEventSynchronize(c->items_ev));
@@ -1953,29 +1942,24 @@ int lt_search_fit_list(lt_ctx* c, int n, const lt_search_item* items, const lt_s
         HIP_TRY(hipMemcpyAsync(c->d_items, c->h_items, (size_t)n * sizeof(lt_search_item), hipMemcpyHostToDevice, st));
         {
             StageScope t(c, n_sws > 0 ? ST_SWS_FIT : ST_BAND_FIT, st);
-            const MaskBits mb{c->d_bits_open, c->bits_stride, wpr};
-            launch_search_list(st, c->d_items, n, n_sws, c->d_plane[P_MASK], c->plane_bytes, mb, gs, gb, c->d_band_sums, c->d_pix,
-                               c->d_cent, c->d_rec);
+            // (the whole buffers: the kernel addresses each item's slot itself)
+            launch_search_list(st, c->d_items, n, n_sws, c->d_plane[P_MASK], c->plane_bytes, slot_bits(c, 0, true), gs, gb, c->d_band_sums,
+                               c->d_pix, c->d_cent, c->d_rec);
         }
         HIP_TRY(hipEventRecord(c->items_ev, st));         // behind the last kernel that reads d_items
     } else {
         for (const auto& it : list) {
-            const int s = it.slot;
-            const bool use_bits = masks_have_bits(c, s, 1) && (it.mode == 0 ? sws_fit_takes_bits(gs, c->plane_bytes) : band_fit_takes_bits(gb, c->plane_bytes));
-            const MaskBits mb{use_bits ? c->d_bits_open + (size_t)s * c->bits_stride : nullptr, c->bits_stride, wpr};
+            const MaskBits mb = slot_bits(c, it.slot, slot_reads_bits(c, geom(it), it.mode, it.slot, 1));
             if (it.mode == 0) {
                 StageScope t(c, ST_SWS_FIT, st);
-                launch_sws_fit(st, c->d_plane[P_MASK] + (size_t)s * c->plane_bytes, c->plane_bytes, mb, gs,
-                               c->d_band_sums + (size_t)s * gs.nbands * c->calib.warp_w, c->d_pix + (size_t)s * 2 * c->maxpix,
-                               c->d_cent + (size_t)s * 2 * (c->maxlev + 2), c->d_rec + s, 1);
+                launch_sws_slots(c, st, gs, mb, it.slot, 1);
             } else {
                 BandPrev bp;
                 std::memset(&bp, 0, sizeof bp);
                 std::memcpy(bp.c, it.prev_coeffs, sizeof bp.c);
                 bp.by_value = 1;
                 StageScope t(c, ST_BAND_FIT, st);
-                launch_band_fit(st, c->d_plane[P_MASK] + (size_t)s * c->plane_bytes, c->plane_bytes, mb, gb, c->d_prev + (size_t)s * 6, bp,
-                                c->d_pix + (size_t)s * 2 * c->maxpix, c->d_rec + s, 1);
+                launch_band_slots(c, st, gb, bp, mb, it.slot, 1);
             }
         }
     }
@@ -2002,26 +1986,23 @@ int lt_search_fit_list(lt_ctx* c, int n, const lt_search_item* items, const lt_s
     return LT_OK;
 }
 
-int lt_upload_frame_rows_list(lt_ctx* c, const uint8_t* const* frames, int first, int n) {
+// the pointer-list forms: frames[k] into slot first + k by the one-frame form, once the whole list is checked
+static int upload_list(lt_ctx* c, const uint8_t* const* frames, int first, int n, const char* what,
+                       int (*one)(lt_ctx*, const uint8_t*, int, int)) {
     int rc = check_slots(c, first, n);
     if (rc) return rc;
     if (n > 0 && !frames) return fail(LT_ERR_INVALID, "null frame list");
     for (int k = 0; k < n; ++k)
-        if (!frames[k]) return fail(LT_ERR_INVALID, "lt_upload_frame_rows_list: frame %d is null", k);
+        if (!frames[k]) return fail(LT_ERR_INVALID, "%s: frame %d is null", what, k);
     for (int k = 0; k < n; ++k)
-        if ((rc = upload_frame_rows_impl(c, frames[k], first + k, 1, true))) return rc;
+        if ((rc = one(c, frames[k], first + k, 1))) return rc;
     return LT_OK;
 }
-
+int lt_upload_frame_rows_list(lt_ctx* c, const uint8_t* const* frames, int first, int n) {
+    return upload_list(c, frames, first, n, "lt_upload_frame_rows_list", lt_upload_frame_rows_enqueue);
+}
 int lt_upload_frame_rest_list(lt_ctx* c, const uint8_t* const* frames, int first, int n) {
-    int rc = check_slots(c, first, n);
-    if (rc) return rc;
-    if (n > 0 && !frames) return fail(LT_ERR_INVALID, "null frame list");
-    for (int k = 0; k < n; ++k)
-        if (!frames[k]) return fail(LT_ERR_INVALID, "lt_upload_frame_rest_list: frame %d is null", k);
-    for (int k = 0; k < n; ++k)
-        if ((rc = lt_upload_frame_rest(c, frames[k], first + k, 1))) return rc;
-    return LT_OK;
+    return upload_list(c, frames, first, n, "lt_upload_frame_rest_list", lt_upload_frame_rest);
 }
 
 int lt_set_urgent(lt_ctx* c, int on) {

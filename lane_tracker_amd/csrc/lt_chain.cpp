@@ -67,9 +67,7 @@ int lt_band_fit_chain_run(lt_ctx* c, int first, int n, const lt_search_params* p
     if ((rc = set_device(c))) return rc;
     if (!c->have_mask) return fail(LT_ERR_STATE, "no mask in the slots: run lt_mask_run or lt_upload_masks first");
     SearchGeom g;
-    if ((rc = make_search_geom(c, p, true, g))) return rc;
-    if ((rc = ensure_search_buffers(c, g.maxpix, 1))) return rc;
-    g.maxpix = c->maxpix;
+    if ((rc = prepare_search(c, p, true, g))) return rc;
     if (!band_chain_supported(g, c->plane_bytes))
         return fail(LT_ERR_STATE, "chained band search needs a band of at most 64 columns (2 * bandwidth + 2) and a mask width that is a multiple of 4");
     if (n == 0) return LT_OK;
@@ -79,7 +77,7 @@ int lt_band_fit_chain_run(lt_ctx* c, int first, int n, const lt_search_params* p
         std::memcpy(bp.c, seed, sizeof bp.c);
         bp.by_value = 1;
     }
-    const bool use_bits = masks_have_bits(c, first, n) && band_fit_takes_bits(g, c->plane_bytes);
+    const bool use_bits = slot_reads_bits(c, g, 1, first, n);
     if (!use_bits && (rc = ensure_u8_masks(c, first, n))) return rc;
     // The chain runs on the context's search stream, behind whatever the slots' streams hold so far (the masks of these
     // slots, the search that wrote the seed record); those streams do not wait for it -- the mask chains of later frames run
@@ -90,25 +88,16 @@ int lt_band_fit_chain_run(lt_ctx* c, int first, int n, const lt_search_params* p
     // everything the slots' streams wrote into these slots and may not have finished (their masks; the search that left the
     // seed record); a seed record left by an earlier chain is ordered by the search stream itself
     if ((rc = wait_range(c->writers, c->search, lo, lo + cnt, &precise))) return rc;
-    if (!precise) {
-        rc = for_each_slice(c, lo, cnt, [&](hipStream_t st, int, int) {      // the ring has overflowed: wait for the streams' tails
-            hipEvent_t e = next_order_event(c);
-            if (!e) return fail(LT_ERR_HIP, "hipEventCreate failed");
-            HIP_TRY(hipEventRecord(e, st));
-            HIP_TRY(hipStreamWaitEvent(c->search, e, 0));
-            return (int)LT_OK;
-        });
-        if (rc) return rc;
-    }
-    const int wpr = (c->calib.warp_w + 63) / 64;
+    if (!precise &&      // the ring has overflowed: wait for the streams' tails
+        (rc = for_each_slice(c, lo, cnt, [&](hipStream_t st, int, int) { return wait_tail(c, c->search, st); })))
+        return rc;
     {
         StageScope t(c, ST_BAND_FIT, c->search);
-        const MaskBits mb{use_bits ? c->d_bits_open + (size_t)first * c->bits_stride : nullptr, c->bits_stride, wpr};
-        launch_band_chain(c->search, c->d_plane[P_MASK] + (size_t)first * c->plane_bytes, c->plane_bytes, mb, g, seed ? nullptr : c->d_rec + first - 1,
-                          bp, c->d_pix + (size_t)first * 2 * c->maxpix, c->d_rec + first, n, c->d_cancel, *c->h_cancel);
+        launch_band_chain(c->search, slot_mask(c, first), c->plane_bytes, slot_bits(c, first, use_bits), g, seed ? nullptr : slot_rec(c, first - 1),
+                          bp, slot_pix(c, first), slot_rec(c, first), n, c->d_cancel, *c->h_cancel);
     }
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(c->h_rec_stage + lo, c->d_rec + lo, (size_t)cnt * sizeof(lt_lane_record), hipMemcpyDeviceToHost, c->search));
+    HIP_TRY(hipMemcpyAsync(c->h_rec_stage + lo, slot_rec(c, lo), (size_t)cnt * sizeof(lt_lane_record), hipMemcpyDeviceToHost, c->search));
     hipEvent_t done = nullptr;
     if (!c->chain_event_pool.empty()) { done = c->chain_event_pool.back(); c->chain_event_pool.pop_back(); }
     else if (hipEventCreateWithFlags(&done, hipEventDisableTiming) != hipSuccess) return fail(LT_ERR_HIP, "hipEventCreate failed");

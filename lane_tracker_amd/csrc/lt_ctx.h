@@ -235,6 +235,19 @@ struct lt_ctx {
 
 namespace lt {
 
+// ---- per-slot addresses in the context's buffers ------------------------------------------------------
+inline uint8_t* slot_frame(const lt_ctx* c, int s) { return c->d_frames + (size_t)s * c->frame_bytes; }
+inline uint8_t* slot_mask(const lt_ctx* c, int s) { return c->d_plane[P_MASK] + (size_t)s * c->plane_bytes; }
+// the opened bit plane of slot s as the searches take it; use_bits = false: none (they read slot_mask)
+inline MaskBits slot_bits(const lt_ctx* c, int s, bool use_bits) {
+    return MaskBits{use_bits ? c->d_bits_open + (size_t)s * c->bits_stride : nullptr, c->bits_stride, (c->calib.warp_w + 63) / 64};
+}
+inline lt_lane_record* slot_rec(const lt_ctx* c, int s) { return c->d_rec + s; }
+inline double* slot_prev(const lt_ctx* c, int s) { return c->d_prev + (size_t)s * 6; }
+inline uint32_t* slot_pix(const lt_ctx* c, int s) { return c->d_pix + (size_t)s * 2 * c->maxpix; }           // [side][maxpix]
+inline int32_t* slot_cent(const lt_ctx* c, int s) { return c->d_cent + (size_t)s * 2 * (c->maxlev + 2); }    // [side][maxlev + 2]
+inline uint32_t* slot_band_sums(const lt_ctx* c, int s, int nbands) { return c->d_band_sums + (size_t)s * nbands * c->calib.warp_w; }
+
 // ---- LT_TRACE_START=1 (lt_memory.cpp): one line per set-up phase on stderr -------------------------------
 //   lt_start <seconds on CLOCK_MONOTONIC, = Python's time.monotonic()> <what> <ms> [<bytes>]
 // What a first window of a stream or the first calls of process() spend outside the kernels: context growth (lt_reserve,
@@ -296,6 +309,7 @@ int note_range_frame(lt_ctx* c, lt_ctx::RangeEvents& r, hipStream_t st, int lo, 
 int wait_range(const lt_ctx::RangeEvents& r, hipStream_t waiter, int lo, int hi, bool* precise);
 int note_written(lt_ctx* c, hipStream_t st, int lo, int hi);
 hipEvent_t next_order_event(lt_ctx* c);
+int wait_tail(lt_ctx* c, hipStream_t waiter, hipStream_t st);   // `waiter` waits for what is enqueued on `st` so far (an order event)
 int wait_chains(lt_ctx* c, hipStream_t st, int lo, int hi);
 int flush_stage_events(lt_ctx* c);
 int check_slots(lt_ctx* c, int first, int n);
@@ -310,6 +324,8 @@ bool masks_have_bits(const lt_ctx* c, int first, int n);
 int ensure_u8_masks(lt_ctx* c, int first, int n);
 int make_search_geom(lt_ctx* c, const lt_search_params* p, bool band, SearchGeom& g);
 int ensure_band_sums(lt_ctx* c, int nbands);
+int prepare_search(lt_ctx* c, const lt_search_params* p, bool band, SearchGeom& g);
+bool slot_reads_bits(const lt_ctx* c, const SearchGeom& g, int mode, int first, int n);
 void mark_frames(lt_ctx* c, int first, int n, int full);
 void mark_annot(lt_ctx* c, int first, int n, int full);
 int first_partial(const std::vector<uint8_t>& v, int first, int n);
@@ -322,10 +338,27 @@ int warm_presentation(lt_ctx* c, bool strips);                // lt_present.cpp
 
 // Slot -> stream mapping is fixed (contiguous slices of the capacity), so consecutive stages of one
 // slot stay ordered on one stream while different slices overlap: the latency-bound search of one
-// slice runs under the mask chain of another.  Calls fn(stream, first, n) for every non-empty piece.
+// slice runs under the mask chain of another.  Slice si of k holds slots [lo, hi) and runs on streams[si].
+inline int slice_count(const lt_ctx* c) { return std::max(1, std::min(c->nstreams, c->capacity)); }
+inline void slice_bounds(const lt_ctx* c, int si, int k, int* lo, int* hi) {
+    // even boundaries: the undistorted rows of slots 2p and 2p+1 are interleaved, and the warp serves a pair with one load
+    *lo = (int)((long long)c->capacity * si / k) & ~1;
+    *hi = si + 1 == k ? c->capacity : (int)((long long)c->capacity * (si + 1) / k) & ~1;
+}
+inline int slice_of(const lt_ctx* c, int slot) {
+    const int k = slice_count(c);
+    for (int si = 0; si < k; ++si) {
+        int lo, hi;
+        slice_bounds(c, si, k, &lo, &hi);
+        if (slot < hi) return si;
+    }
+    return k - 1;
+}
+
+// Calls fn(stream, first, n) for every non-empty piece of slots [first, first + n).
 template <class F>
 int for_each_slice(lt_ctx* c, int first, int n, F fn) {
-    const int k = std::max(1, std::min(c->nstreams, c->capacity));
+    const int k = slice_count(c);
     if (c->urgent_on && c->urgent) {
         // one piece on the urgent stream: behind the kernels that wrote these slots (or, with the ring overflowed, the tails of
         // their streams) and a chain still touching them; the slots' own streams then wait for it, so that whatever is
@@ -336,21 +369,13 @@ int for_each_slice(lt_ctx* c, int first, int n, F fn) {
         if (rc) return rc;
         auto slices = [&](auto g) {
             for (int si = 0; si < k; ++si) {
-                const int lo = (int)((long long)c->capacity * si / k) & ~1, hi = si + 1 == k ? c->capacity : (int)((long long)c->capacity * (si + 1) / k) & ~1;
+                int lo, hi;
+                slice_bounds(c, si, k, &lo, &hi);
                 if (std::min(first + n, hi) > std::max(first, lo)) { int r = g(c->streams[si]); if (r) return r; }
             }
             return (int)LT_OK;
         };
-        if (!precise) {
-            rc = slices([&](hipStream_t st) {
-                hipEvent_t e = next_order_event(c);
-                if (!e) return fail(LT_ERR_HIP, "hipEventCreate failed");
-                HIP_TRY(hipEventRecord(e, st));
-                HIP_TRY(hipStreamWaitEvent(us, e, 0));
-                return (int)LT_OK;
-            });
-            if (rc) return rc;
-        }
+        if (!precise && (rc = slices([&](hipStream_t st) { return wait_tail(c, us, st); }))) return rc;
         if ((rc = wait_chains(c, us, first, first + n))) return rc;
         if ((rc = fn(us, first, n))) return rc;
         hipEvent_t done = next_order_event(c);
@@ -362,8 +387,8 @@ int for_each_slice(lt_ctx* c, int first, int n, F fn) {
         });
     }
     for (int si = 0; si < k; ++si) {
-        // even boundaries: the undistorted rows of slots 2p and 2p+1 are interleaved, and the warp serves a pair with one load
-        const int lo = (int)((long long)c->capacity * si / k) & ~1, hi = si + 1 == k ? c->capacity : (int)((long long)c->capacity * (si + 1) / k) & ~1;
+        int lo, hi;
+        slice_bounds(c, si, k, &lo, &hi);
         const int a = std::max(first, lo), b = std::min(first + n, hi);
         if (b <= a) continue;
         int rc = wait_chains(c, c->streams[si], a, b);                     // a chain in flight reads / writes these slots

@@ -431,23 +431,14 @@ static int overlay_run_impl(lt_ctx* c, int first, int n, const int32_t* left_n, 
     {   // the camera rows of these slots: behind the launches that wrote their masks (which waited for the rows' upload)
         bool precise = true;
         if ((rc = wait_range(c->writers, ps, first, first + n, &precise))) return rc;
-        if (!precise) {
-            rc = for_each_slice(c, first, n, [&](hipStream_t st, int, int) {
-                hipEvent_t e = next_order_event(c);
-                if (!e) return fail(LT_ERR_HIP, "hipEventCreate failed");
-                HIP_TRY(hipEventRecord(e, st));
-                HIP_TRY(hipStreamWaitEvent(ps, e, 0));
-                return (int)LT_OK;
-            });
-            if (rc) return rc;
-        }
+        if (!precise && (rc = for_each_slice(c, first, n, [&](hipStream_t st, int, int) { return wait_tail(c, ps, st); }))) return rc;
     }
     // an asynchronous download may still be reading the annotated frames this call overwrites
     if (c->annot_busy.hi > c->annot_busy.lo && first < c->annot_busy.hi && first + n > c->annot_busy.lo && c->annot_busy.done)
         HIP_TRY(hipStreamWaitEvent(ps, c->annot_busy.done, 0));
     if (one) {
         uint8_t* dst = direct_out ? direct_out : c->d_annot + (size_t)first * c->frame_bytes;
-        if (launch_overlay_lane_one(ps, c->d_frames + (size_t)first * c->frame_bytes, dst,
+        if (launch_overlay_lane_one(ps, slot_frame(c, first), dst,
                                     c->d_oxy, c->d_ofrac, hs, c->calib.img_h, c->calib.img_w, bh, c->calib.warp_w, (float)alpha, rows4)) {
             HIP_TRY(hipGetLastError());
             if (went_direct) *went_direct = direct_out != nullptr;
@@ -465,12 +456,12 @@ static int overlay_run_impl(lt_ctx* c, int first, int n, const int32_t* left_n, 
         return fail(LT_ERR_STATE, "lt_overlay_run_strip_coeffs: not available for this bird's-eye height");
     const auto t2 = std::chrono::steady_clock::now();
     if (strip) {
-        if (!launch_overlay_lane_strip(ps, c->d_frames + (size_t)first * c->frame_bytes, c->frame_bytes, c->d_strip + (size_t)first * c->strip_bytes,
+        if (!launch_overlay_lane_strip(ps, slot_frame(c, first), c->frame_bytes, c->d_strip + (size_t)first * c->strip_bytes,
                                        c->strip_bytes, c->d_oxy, c->d_ofrac, c->d_spans + (size_t)first * bh * 2, (size_t)bh, c->calib.img_w,
                                        c->ov_r0, c->ov_r1, bh, c->calib.warp_w, (float)alpha, n))
             return fail(LT_ERR_STATE, "strip overlay needs a frame width that is a multiple of 4");
     } else
-    launch_overlay_lane(ps, c->d_frames + (size_t)first * c->frame_bytes, c->d_annot + (size_t)first * c->frame_bytes,
+    launch_overlay_lane(ps, slot_frame(c, first), c->d_annot + (size_t)first * c->frame_bytes,
                         c->frame_bytes, c->d_oxy, c->d_ofrac, c->d_spans + (size_t)first * bh * 2, (size_t)bh,
                         c->calib.img_h, c->calib.img_w, bh, c->calib.warp_w, (float)alpha, n, rows4);
     HIP_TRY(hipGetLastError());
@@ -540,10 +531,7 @@ int lt_strip_download_async(lt_ctx* c, int first, int n, uint8_t* out, size_t ou
     if (n == 0 || c->strip_bytes == 0) return LT_OK;
     if ((rc = set_device(c))) return rc;
     if (!c->dl) HIP_TRY(stream_get(&c->dl, SK_PRIORITY, 0));
-    hipEvent_t e = next_order_event(c);
-    if (!e) return fail(LT_ERR_HIP, "hipEventCreate failed");
-    HIP_TRY(hipEventRecord(e, c->present));
-    HIP_TRY(hipStreamWaitEvent(c->dl, e, 0));
+    if ((rc = wait_tail(c, c->dl, c->present))) return rc;
     constexpr int STRIP_BLOCK = 32;
     const size_t sb = c->strip_bytes, block_bytes = (size_t)STRIP_BLOCK * sb;
     const size_t row_off = (size_t)c->ov_r0 * c->calib.img_w * 3;
@@ -828,9 +816,9 @@ int lt_present_lane_from_fit_async(lt_ctx* c, int slot, const double* prev_sum, 
             if (!precise) HIP_TRY(hipStreamWaitEvent(st, c->rest_done, 0));
         }
         int16_t* sp = c->d_spans + (size_t)f0 * bh * 2;
-        if (!launch_lane_spans_from_fit(st, c->d_rec + f0, prev_sum, count, c->d_ploty, c->d_ploty + n_rows, n_rows, bh, c->calib.warp_w, sp))
+        if (!launch_lane_spans_from_fit(st, slot_rec(c, f0), prev_sum, count, c->d_ploty, c->d_ploty + n_rows, n_rows, bh, c->calib.warp_w, sp))
             return fail(LT_ERR_STATE, "lt_present_lane_from_fit_async: too many rows for one workgroup's LDS");
-        launch_overlay_lane(st, c->d_frames + (size_t)f0 * c->frame_bytes, static_cast<uint8_t*>(dev), c->frame_bytes, c->d_oxy, c->d_ofrac, sp,
+        launch_overlay_lane(st, slot_frame(c, f0), static_cast<uint8_t*>(dev), c->frame_bytes, c->d_oxy, c->d_ofrac, sp,
                             (size_t)bh, c->calib.img_h, c->calib.img_w, bh, c->calib.warp_w, (float)alpha, 1, r);
         c->lane_spec_stream = st;
         c->lane_spec_ticket = 0;
@@ -955,10 +943,7 @@ static int download_overlay_async_impl(lt_ctx* c, int first, int n, uint8_t* out
         if (c->search_cus >= 2) HIP_TRY(stream_get(&c->dl, SK_CU_SET, -c->search_cus));
         else HIP_TRY(stream_get(&c->dl, SK_PRIORITY, 0));
     }
-    hipEvent_t e = next_order_event(c);
-    if (!e) return fail(LT_ERR_HIP, "hipEventCreate failed");
-    HIP_TRY(hipEventRecord(e, c->present ? c->present : c->stream));
-    HIP_TRY(hipStreamWaitEvent(c->dl, e, 0));
+    if ((rc = wait_tail(c, c->dl, c->present ? c->present : c->stream))) return rc;
     // engine or kernel: by measurement (choose_download); LT_DL_KERNEL=1 / 0 and lt_set_download_method pin one of them
     static const int env_method = [] { const char* e = LT_EXP_ENV("LT_DL_KERNEL"); return !e ? -1 : (e[0] == '0' ? 0 : 1); }();
     if (env_method >= 0 && c->dl_forced < 0) c->dl_forced = env_method;
