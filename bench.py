@@ -16,6 +16,11 @@ One step = one pass of the hot path over the rank's frames, resident in HBM befo
   --frames 4096  BASELINE config 4: a 4096-frame stream sharded over the GPUs          ("scaling": "strong")
 No data-path collective; every step's 64-byte lane records are staged device to device and the timed region ends
 with ONE RCCL all-gather of all of them.  Prints ONE JSON line on rank 0.
+
+A plain run does only what that line's headline needs: it renders the frames, sets up, warms up, times the steps, writes
+--dump-outputs and prints the line.  --full adds everything else: the overlapped figure over a second resident copy of the
+batch, the per-kernel hipEvent pass with the roofline, the host-fed uploads, the CPU baseline with the in-run parity check,
+the parameter sets, BASELINE config 1 and the stateful-stream leg (the --no-* options skip single legs of it).
 """
 import argparse
 import json
@@ -628,6 +633,88 @@ def write_outputs(out_dir, records, masks, mask_frames):
         np.save(os.path.join(out_dir, name + ".npy"), v)
 
 
+def serial_pass_figures(stages, KS, NL, info):
+    """--full: the figures of the serial pass (KS steps on one stream, a hipEvent pair around every kernel) -- roofline,
+    kernels_ms_per_step, search_fit -- and the sum of its kernels' ms per step, the un-overlapped step."""
+    mask_ms = sum(stages[s][0] for s in MASK_STAGES) / KS              # per launch of NL frames, serial pass
+    search_ms = stages["sws_fit"][0] / KS
+    alg = info.alg_bytes_mask * NL                                     # algorithmic bytes of the stage per launch
+    achieved = alg / (mask_ms * 1e-3) / 1e9 if mask_ms > 0 else 0.0
+    dom = max(MASK_STAGES, key=lambda s: stages[s][0])
+    # HBM-side traffic and VALU instruction counts come from a committed rocprofv3 --pmc run of this same command
+    # (profiles/<tag>_traffic.json); they are labelled as such and only attached when the launch shape matches.
+    from_profile = None
+    traffic = None
+    try:
+        tj = json.load(open(os.path.join(ROOT, "profiles", PROFILE_TAG + "_traffic.json")))
+        if tj["frames_per_launch"] == NL:
+            traffic = int(tj["mask_stage_traffic_bytes_per_launch"])
+            vi = json.load(open(os.path.join(ROOT, "profiles", CALIB_TAG + "_valu_issue.json")))
+            peak_rate = float(vi["peak_wave_insts_per_cycle_per_simd"])
+            lane_ops = float(tj["mask_stage_valu_wave_insts_per_launch"]) * 64.0
+            peak = info.cu_count * 4 * peak_rate * 64.0 * 2.4e9       # CUs x SIMDs x wave-insts/clk x 64 lanes x 2.4 GHz
+            # per kernel: the committed instruction / byte counts over THIS run's kernel times
+            stage_kernels = {"undistort_rows": ["k_undistort_rows"], "warp_split": ["k_warp_split4"],
+                             "erode_r29": ["SE29, false"], "tophat_r29": ["SE29, true"], "erode_b55": ["SE55, false"],
+                             "tophat_b55": ["SE55, true"], "threshold": ["k_bilateral_walk", "k_bilateral_tile"],
+                             "open5": ["k_merge_open5", "k_erode5_bits", "k_dilate5_bits", "k_or4_bits"]}
+            per_kernel = {}
+            for st, keys in stage_kernels.items():
+                ms = stages.get(st, (0.0, 0))[0] / KS
+                ks = [v for n, v in tj.get("per_kernel", {}).items() if any(k in n for k in keys)]
+                if ms <= 0 or not ks:
+                    continue
+                insts = sum(v["valu_wave_insts"] for v in ks)
+                byts = sum(v["fetch_bytes"] + v["write_bytes"] for v in ks)
+                per_kernel[st] = {"ms": round(ms, 4),
+                                  "valu_issue_frac": round(insts / (ms * 1e-3 * 2.4e9 * info.cu_count * 4 * peak_rate), 3),
+                                  "hbm_side_GBs": round(byts / (ms * 1e-3) / 1e9, 1)}
+            rocprof = None
+            try:
+                ks = json.load(open(os.path.join(ROOT, "profiles", PROFILE_TAG + "_kernel_stats_summary.json")))
+                rocprof = {"stage_ms": ks["mask_stage_ms"], "this_run_over_rocprof": round(mask_ms / ks["mask_stage_ms"], 3),
+                           "note": "sum of the rocprofv3 --kernel-trace average durations of the same kernels in the committed "
+                                   "profile run (kernels under the tracer run slower than between hipEvents)"}
+            except Exception:
+                pass
+            from_profile = {
+                "from_profile": PROFILE_TAG, "commit": tj.get("commit"), "rocprof_kernel_trace": rocprof,
+                "source": tj.get("source"), "per_kernel": per_kernel,
+                "traffic_bytes_per_launch": traffic, "traffic_over_algorithmic": round(traffic / float(alg), 2),
+                "fetch_write_calibration": tj.get("calibration"),
+                "traffic_over_compulsory": round(traffic / float(tj["mask_stage_compulsory_bytes_per_launch"]), 2) if tj.get("mask_stage_compulsory_bytes_per_launch") else None,
+                "lds_pipe": ({"busy_frac": round(float(tj["mask_stage_lds_idx_active_cycles_per_launch"]) / (mask_ms * 1e-3 * 2.4e9 * info.cu_count), 4),
+                              "what": "SQ_LDS_IDX_ACTIVE cycles of the stage's kernels (summed over the CUs) / (CUs x this run's stage time x 2.4 GHz)"}
+                             if tj.get("mask_stage_lds_idx_active_cycles_per_launch") else None),
+                "valu_issue": {"achieved": round(lane_ops / (mask_ms * 1e-3) / 1e12, 3), "peak": round(peak / 1e12, 3),
+                               "unit": "T lane-ops/s", "frac": round(lane_ops / (mask_ms * 1e-3) / peak, 4),
+                               "peak_from": "profiles/%s_valu_issue.json: %s wave64 instructions per cycle per SIMD measured for "
+                                            "the packed-16 / integer instructions of these kernels" % (CALIB_TAG, peak_rate)}}
+    except Exception:
+        pass
+    return {
+        "roofline": {"bound": "hbm", "binding_unit": "valu+lds",
+                     "binding_unit_fracs": ({"valu_issue_frac": from_profile["valu_issue"]["frac"],
+                                             "lds_pipe_busy_frac": (from_profile.get("lds_pipe") or {}).get("busy_frac"),
+                                             "from": "the counters of profile.from_profile over this run's stage time"} if from_profile else None),
+                     "kernel": "warp+threshold stage (%d kernels: %s)" % (len(MASK_STAGES), ",".join(MASK_STAGES)),
+                     "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic,
+                     "frac_of_copy_ceiling": round(achieved / HBM_COPY_CEILING_GBS, 6),
+                     "alg_bytes_per_frame": int(info.alg_bytes_mask), "frames_per_launch": NL,
+                     "stage_ms_per_launch": round(mask_ms, 4), "dominant_kernel": dom,
+                     "profile": from_profile,
+                     "note": "achieved = algorithmic bytes / hipEvent time of the stage's kernels, measured in this run; "
+                             "`traffic` and `profile` are NOT measured in this run: they are the PMC counters of the committed "
+                             "rocprofv3 run named in profile.from_profile (null when the launch shape differs). `bound` names the roofline "
+                             "the METRIC asks for (HBM); what binds the stage is binding_unit: the integer-VALU issue port and the CUs' "
+                             "LDS pipes together (binding_unit_fracs), see DESIGN.md"},
+        "kernels_ms_per_step": {k: round(v[0] / KS, 4) for k, v in stages.items() if v[1]},
+        "search_fit": {"ms_per_step": round(search_ms, 4),
+                       "achieved_GBs": round(info.alg_bytes_search * NL / (search_ms * 1e-3) / 1e9, 3) if search_ms > 0 else None},
+    }, mask_ms + search_ms
+
+
 def launcher(a):
     """--gpus N > 1 and no RANK in the environment: start the N ranks.  This process never touches the GPU."""
     from lane_tracker_amd import distributed
@@ -649,6 +736,9 @@ def main():
                     help="total frames of one stream, sharded over the GPUs (strong scaling; 4096 = BASELINE config 4)")
     ap.add_argument("--single-copy", action="store_true", help="do not keep a second resident copy of the batch (no overlapped_batches figure)")
     ap.add_argument("--streams", type=int, default=4, help="HIP streams per context (slot slices overlap each other's stages)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, every other leg: overlapped batches, per-kernel times and roofline, host-fed uploads, "
+                         "CPU baseline and parity, parameter sets, config 1, the stateful stream (the --no-* options skip single legs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-host-fed", action="store_true")
     ap.add_argument("--no-stream", action="store_true", help="skip the stateful-stream leg (process / process_batch frames/s)")
@@ -684,7 +774,7 @@ def main():
         indices = range(rank * a.batch, (rank + 1) * a.batch)
     NL = len(indices)                                   # frames this rank processes per step
     frames = render_frames(indices)                     # before anything initialises the GPU (forked workers)
-    streams = render_streams() if (world == 1 and not strong and not a.no_stream and not a.only_settings) else None
+    streams = render_streams() if (a.full and world == 1 and not strong and not a.no_stream) else None
 
     try:
         device = distributed.local_device(local_rank)   # LOCAL_RANK (LT_DEVICE_MODULO: test runs that share a GPU, labelled below)
@@ -694,7 +784,8 @@ def main():
     # `value`: every step over the SAME NL resident frames (slots [0, NL)); each step waits in order behind the previous one on
     # its slots.  A second resident copy of the batch (slots [NL, 2 NL)) serves one extra figure outside the timed region,
     # overlapped_batches_frames_per_s: steps alternating between the copies, so that the tail of step k and the head of step
-    # k+1 overlap the way consecutive batches of a stream do (rounds 1-3 reported that one as `value`).
+    # k+1 overlap the way consecutive batches of a stream do (rounds 1-3 reported that one as `value`).  Only --full fills the
+    # second copy; a plain run sizes the context the same, so that its timed steps run on the same layout either way.
     two_copies = NL <= 1024 and not a.single_copy
     ctx = _native.Context(cal["img_size"], cal["warped_size"], cal["cam_matrix"], cal["dist_coeffs"],
                           cal["warp_matrices"][0], device=device, capacity=2 * NL if two_copies else NL)
@@ -703,12 +794,13 @@ def main():
     for c0 in range(0, NL, 256):
         ctx.upload_frames(frames[c0:c0 + 256], first=c0)
     h2d_s = time.perf_counter() - t0
-    t0 = time.perf_counter()
-    for c0 in range(0, NL, 256):
-        ctx.upload_frame_rows(frames[c0:c0 + 256], first=c0)   # what a host-fed pipeline moves: the rows the path reads
-    h2d_rows_s = time.perf_counter() - t0
+    if a.full:
+        t0 = time.perf_counter()
+        for c0 in range(0, NL, 256):
+            ctx.upload_frame_rows(frames[c0:c0 + 256], first=c0)   # what a host-fed pipeline moves: the rows the path reads
+        h2d_rows_s = time.perf_counter() - t0
     ctx.set_frame_base(NL, indices[0])
-    if two_copies:
+    if a.full and two_copies:
         for c0 in range(0, NL, 256):
             ctx.upload_frames(frames[c0:c0 + 256], first=NL + c0)
         ctx.set_frame_base(NL, indices[0], first=NL)
@@ -762,8 +854,9 @@ def main():
             (marks["fenced"] - marks.get("gathered", marks["drained"])) * 1e3), file=sys.stderr)
 
     overlapped_fps = None
-    if two_copies and not in_rank:     # not part of the timed region: the same steps alternating between two resident copies of
-        for k in range(2):             # the batch, so that consecutive steps overlap the way consecutive batches of a stream do
+    if a.full and two_copies and not in_rank:   # not part of the timed region: the same steps alternating between two resident
+        # copies of the batch, so that consecutive steps overlap the way consecutive batches of a stream do
+        for k in range(2):
             step(k, True, False)
         ctx.sync()
         t1 = time.perf_counter()
@@ -775,16 +868,17 @@ def main():
     # Per-kernel durations for the roofline: the same steps again on ONE stream with a hipEvent pair
     # around every kernel (with several streams the kernels of different slices overlap, so their
     # individual durations are not separable).  These agree with the rocprofv3 --stats averages.
-    ctx.set_streams(1)
-    ctx.set_stage_timing(True)
-    ctx.stage_reset()
-    KS = max(1, min(a.steps, 5))
-    for _ in range(KS):
-        ctx.mask_run(NL, fp)
-        ctx.sws_fit_run(NL, sp)
-    ctx.sync()
-    stages = ctx.stage_ms()
-    ctx.set_stage_timing(False)
+    stages, KS = None, max(1, min(a.steps, 5))
+    if a.full:
+        ctx.set_streams(1)
+        ctx.set_stage_timing(True)
+        ctx.stage_reset()
+        for _ in range(KS):
+            ctx.mask_run(NL, fp)
+            ctx.sws_fit_run(NL, sp)
+        ctx.sync()
+        stages = ctx.stage_ms()
+        ctx.set_stage_timing(False)
 
     my_records = ctx.download_records(NL)
     if gather is not None:
@@ -807,62 +901,6 @@ def main():
         K = a.steps
         ms_step = dt / K * 1e3
         value = total_frames * K / dt
-        mask_ms = sum(stages[s][0] for s in MASK_STAGES) / KS              # per launch of NL frames, serial pass
-        search_ms = stages["sws_fit"][0] / KS
-        alg = info.alg_bytes_mask * NL                                     # algorithmic bytes of the stage per launch
-        achieved = alg / (mask_ms * 1e-3) / 1e9 if mask_ms > 0 else 0.0
-        dom = max(MASK_STAGES, key=lambda s: stages[s][0])
-        # HBM-side traffic and VALU instruction counts come from a committed rocprofv3 --pmc run of this same command
-        # (profiles/<tag>_traffic.json); they are labelled as such and only attached when the launch shape matches.
-        from_profile = None
-        traffic = None
-        try:
-            tj = json.load(open(os.path.join(ROOT, "profiles", PROFILE_TAG + "_traffic.json")))
-            if tj["frames_per_launch"] == NL:
-                traffic = int(tj["mask_stage_traffic_bytes_per_launch"])
-                vi = json.load(open(os.path.join(ROOT, "profiles", CALIB_TAG + "_valu_issue.json")))
-                peak_rate = float(vi["peak_wave_insts_per_cycle_per_simd"])
-                lane_ops = float(tj["mask_stage_valu_wave_insts_per_launch"]) * 64.0
-                peak = info.cu_count * 4 * peak_rate * 64.0 * 2.4e9       # CUs x SIMDs x wave-insts/clk x 64 lanes x 2.4 GHz
-                # per kernel: the committed instruction / byte counts over THIS run's kernel times
-                stage_kernels = {"undistort_rows": ["k_undistort_rows"], "warp_split": ["k_warp_split4"],
-                                 "erode_r29": ["SE29, false"], "tophat_r29": ["SE29, true"], "erode_b55": ["SE55, false"],
-                                 "tophat_b55": ["SE55, true"], "threshold": ["k_bilateral_walk", "k_bilateral_tile"],
-                                 "open5": ["k_merge_open5", "k_erode5_bits", "k_dilate5_bits", "k_or4_bits"]}
-                per_kernel = {}
-                for st, keys in stage_kernels.items():
-                    ms = stages.get(st, (0.0, 0))[0] / KS
-                    ks = [v for n, v in tj.get("per_kernel", {}).items() if any(k in n for k in keys)]
-                    if ms <= 0 or not ks:
-                        continue
-                    insts = sum(v["valu_wave_insts"] for v in ks)
-                    byts = sum(v["fetch_bytes"] + v["write_bytes"] for v in ks)
-                    per_kernel[st] = {"ms": round(ms, 4),
-                                      "valu_issue_frac": round(insts / (ms * 1e-3 * 2.4e9 * info.cu_count * 4 * peak_rate), 3),
-                                      "hbm_side_GBs": round(byts / (ms * 1e-3) / 1e9, 1)}
-                rocprof = None
-                try:
-                    ks = json.load(open(os.path.join(ROOT, "profiles", PROFILE_TAG + "_kernel_stats_summary.json")))
-                    rocprof = {"stage_ms": ks["mask_stage_ms"], "this_run_over_rocprof": round(mask_ms / ks["mask_stage_ms"], 3),
-                               "note": "sum of the rocprofv3 --kernel-trace average durations of the same kernels in the committed "
-                                       "profile run (kernels under the tracer run slower than between hipEvents)"}
-                except Exception:
-                    pass
-                from_profile = {
-                    "from_profile": PROFILE_TAG, "commit": tj.get("commit"), "rocprof_kernel_trace": rocprof,
-                    "source": tj.get("source"), "per_kernel": per_kernel,
-                    "traffic_bytes_per_launch": traffic, "traffic_over_algorithmic": round(traffic / float(alg), 2),
-                    "fetch_write_calibration": tj.get("calibration"),
-                    "traffic_over_compulsory": round(traffic / float(tj["mask_stage_compulsory_bytes_per_launch"]), 2) if tj.get("mask_stage_compulsory_bytes_per_launch") else None,
-                    "lds_pipe": ({"busy_frac": round(float(tj["mask_stage_lds_idx_active_cycles_per_launch"]) / (mask_ms * 1e-3 * 2.4e9 * info.cu_count), 4),
-                                  "what": "SQ_LDS_IDX_ACTIVE cycles of the stage's kernels (summed over the CUs) / (CUs x this run's stage time x 2.4 GHz)"}
-                                 if tj.get("mask_stage_lds_idx_active_cycles_per_launch") else None),
-                    "valu_issue": {"achieved": round(lane_ops / (mask_ms * 1e-3) / 1e12, 3), "peak": round(peak / 1e12, 3),
-                                   "unit": "T lane-ops/s", "frac": round(lane_ops / (mask_ms * 1e-3) / peak, 4),
-                                   "peak_from": "profiles/%s_valu_issue.json: %s wave64 instructions per cycle per SIMD measured for "
-                                                "the packed-16 / integer instructions of these kernels" % (CALIB_TAG, peak_rate)}}
-        except Exception:
-            pass
         workload = ("BASELINE config 4: %d-frame synthetic stream sharded over %d GPU(s) (%d frames on rank 0), HBM-resident"
                     % (a.frames, world, NL)) if strong else \
                    ("BASELINE config 3: batch of %d synthetic lane-like 1280x720 frames per GPU, HBM-resident" % NL)
@@ -881,39 +919,24 @@ def main():
                        "rank_environment": {distributed.IPC_ENV[0]: os.environ.get(distributed.IPC_ENV[0])} if world > 1 else None,
                        "streams_per_gpu": a.streams, "resident_copies_of_the_batch_in_the_timed_region": 1,
                        "detected_fraction": round(float(np.mean(rec_all["detected"])), 4)},
-            "roofline": {"bound": "hbm", "binding_unit": "valu+lds",
-                         "binding_unit_fracs": ({"valu_issue_frac": from_profile["valu_issue"]["frac"],
-                                                 "lds_pipe_busy_frac": (from_profile.get("lds_pipe") or {}).get("busy_frac"),
-                                                 "from": "the counters of profile.from_profile over this run's stage time"} if from_profile else None),
-                         "kernel": "warp+threshold stage (%d kernels: %s)" % (len(MASK_STAGES), ",".join(MASK_STAGES)),
-                         "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 6), "traffic": traffic,
-                         "frac_of_copy_ceiling": round(achieved / HBM_COPY_CEILING_GBS, 6),
-                         "alg_bytes_per_frame": int(info.alg_bytes_mask), "frames_per_launch": NL,
-                         "stage_ms_per_launch": round(mask_ms, 4), "dominant_kernel": dom,
-                         "profile": from_profile,
-                         "note": "achieved = algorithmic bytes / hipEvent time of the stage's kernels, measured in this run; "
-                                 "`traffic` and `profile` are NOT measured in this run: they are the PMC counters of the committed "
-                                 "rocprofv3 run named in profile.from_profile (null when the launch shape differs). `bound` names the roofline "
-                                 "the METRIC asks for (HBM); what binds the stage is binding_unit: the integer-VALU issue port and the CUs' "
-                                 "LDS pipes together (binding_unit_fracs), see DESIGN.md"},
-            "kernels_ms_per_step": {k: round(v[0] / KS, 4) for k, v in stages.items() if v[1]},
-            "timing_note": "value / ms_per_step: %d steps over the same resident frames on %d HIP streams per GPU (slot slices overlap: the "
-                           "latency-bound search of one slice hides under the mask chain of another)%s. kernels_ms_per_step, roofline and "
-                           "search_fit: %d further steps on one stream with hipEvents around every kernel; their sum (%.3f ms) "
-                           "is the un-overlapped step" % (a.steps, a.streams,
-                                                          "; overlapped_batches_frames_per_s: the same steps alternating between two resident copies "
-                                                          "of the batch (what rounds 1-3 reported as value)" if overlapped_fps else "", KS, mask_ms + search_ms),
-            "overlapped_batches_frames_per_s": round(overlapped_fps, 2) if overlapped_fps else None,
-            "search_fit": {"ms_per_step": round(search_ms, 4),
-                           "achieved_GBs": round(info.alg_bytes_search * NL / (search_ms * 1e-3) / 1e9, 3) if search_ms > 0 else None},
-            "host_fed": {"h2d_seconds_whole_frames": round(h2d_s, 4),
-                         "serial_frames_per_s_whole_frames": round(NL / (h2d_s + dt / K), 2),
-                         "h2d_seconds_source_rows_only": round(h2d_rows_s, 4), "source_rows": list(ctx.source_rows()),
-                         "serial_frames_per_s_source_rows_only": round(NL / (h2d_rows_s + dt / K), 2)},
-            "device": info.device_name.decode(errors="replace"),
         }
-        single = world == 1 and not strong
+        if a.full:
+            serial, unoverlapped_ms = serial_pass_figures(stages, KS, NL, info)
+            out.update(serial)
+        out["timing_note"] = ("value / ms_per_step: %d steps over the same resident frames on %d HIP streams per GPU (slot slices overlap: "
+                              "the latency-bound search of one slice hides under the mask chain of another)" % (a.steps, a.streams))
+        if a.full:
+            out["timing_note"] += ("%s. kernels_ms_per_step, roofline and search_fit: %d further steps on one stream with hipEvents around "
+                                   "every kernel; their sum (%.3f ms) is the un-overlapped step"
+                                   % ("; overlapped_batches_frames_per_s: the same steps alternating between two resident copies of the "
+                                      "batch (what rounds 1-3 reported as value)" if overlapped_fps else "", KS, unoverlapped_ms))
+            out["overlapped_batches_frames_per_s"] = round(overlapped_fps, 2) if overlapped_fps else None
+            out["host_fed"] = {"h2d_seconds_whole_frames": round(h2d_s, 4),
+                               "serial_frames_per_s_whole_frames": round(NL / (h2d_s + dt / K), 2),
+                               "h2d_seconds_source_rows_only": round(h2d_rows_s, 4), "source_rows": list(ctx.source_rows()),
+                               "serial_frames_per_s_source_rows_only": round(NL / (h2d_rows_s + dt / K), 2)}
+        out["device"] = info.device_name.decode(errors="replace")
+        single = a.full and world == 1 and not strong     # the legs after the headline: --full only
         if single and not a.no_cpu_baseline:
             masks_cache = {}
 

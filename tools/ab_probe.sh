@@ -4,7 +4,7 @@
 V=${1:-LT_XCD_REMAP}; k=${2:-20}
 for r in 0 1 0 1; do
   echo "$V=$r"
-  env $V=$r timeout 200 python bench.py --steps $k --warmup 3 --no-cpu-baseline 2>&1 | tail -1 | python -c "
+  env $V=$r timeout 200 python bench.py --full --steps $k --warmup 3 --no-cpu-baseline 2>&1 | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 print(d['value'], {k: round(v, 3) for k, v in d['kernels_ms_per_step'].items()})"

@@ -4,7 +4,7 @@
 import json, os, subprocess, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for i in range(int(sys.argv[1]) if len(sys.argv) > 1 else 2):
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--no-cpu-baseline", "--no-settings", "--no-host-fed"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--no-cpu-baseline", "--no-settings", "--no-host-fed"],
                        cwd=root, capture_output=True, text=True, timeout=600)
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     s = json.loads(line)["stream"]

@@ -14,7 +14,7 @@ for v in base WARP_NO_TAPS UND_NO_STORE; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -Wl,--version-script=exports.map -o /tmp/libfront_$v.so $OBJS /tmp/kf_$v.o || exit 1
   for r in 1 2; do
     echo "== $v"
-    (cd ../.. && LANE_TRACKER_AMD_LIB=/tmp/libfront_$v.so timeout 200 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-host-fed --no-stream --no-settings 2>/dev/null | tail -1 | python -c "
+    (cd ../.. && LANE_TRACKER_AMD_LIB=/tmp/libfront_$v.so timeout 200 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-host-fed --no-stream --no-settings 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 k = d['kernels_ms_per_step']

@@ -6,7 +6,7 @@ tag=${1:-r06}
 commit=${2:-unknown}
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 out=$root/gpurun_out/$tag; mkdir -p $out
-B="$root/bench.py --no-cpu-baseline --no-host-fed --no-stream --no-settings --streams 1"
+B="$root/bench.py --full --no-cpu-baseline --no-host-fed --no-stream --no-settings --streams 1"
 cd /tmp && export TMPDIR=/tmp
 timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o t -- python3 $B --steps 5 --warmup 2 > $out/trace.log 2>&1; echo "trace rc=$?"
 run() { name=$1; shift
@@ -32,7 +32,7 @@ print("rocprof mask stage %.4f ms" % stage)
 PY
 python3 tools/pmc_kernels.py $out k_ > $out/${tag}_pmc_kernels.txt
 python3 tools/make_traffic.py $out $out/${tag}_traffic.json 256 $commit
-python3 bench.py > $out/${tag}_bench.json 2> $out/${tag}_bench.err; tail -c 400 $out/${tag}_bench.json
+python3 bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err; tail -c 400 $out/${tag}_bench.json
 # the parameter sets of bench.py's settings leg (defaults, demo 1-3, second try), every dispatch 256 frames: the kernels only they use
 cd /tmp
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/strace -o t -- python3 $root/bench.py --only-settings --streams 1 > $out/strace.log 2>&1; echo "settings trace rc=$?"
