@@ -49,7 +49,8 @@ extern "C" {
  *    lt_host_text_now_group (a frame's text lines drawn at once, behind the group's copies), lt_frame_tail (validity, average,
  *    plot points, radius and eccentricity of a valid first try in one host call).  Later additions, still 5:
  *    lt_search_item + lt_search_fit_list (the searches of frames of unrelated streams in one launch), lt_upload_frame_rows_list +
- *    lt_upload_frame_rest_list (the uploads of frames that lie in separate host arrays).  Nothing removed or changed. */
+ *    lt_upload_frame_rest_list (the uploads of frames that lie in separate host arrays); lt_set_input_format + lt_get_input_format +
+ *    lt_yuv_to_rgb (camera frames in YUV 4:2:0, NV12 or I420, converted on the device).  Nothing removed or changed. */
 #define LT_ABI_VERSION 5
 
 typedef enum lt_status {
@@ -152,6 +153,29 @@ int  lt_sync(lt_ctx* ctx);
 int  lt_set_streams(lt_ctx* ctx, int nstreams);
 
 /* ---- frames in, results out ------------------------------------------------------------------ */
+/* The pixel format of the camera frames a context takes: RGB interleaved (the default), or YUV 4:2:0 as cameras and decoders hand
+ * it out -- NV12 (img_h rows of Y, then img_h / 2 rows of interleaved U,V pairs) or I420 (Y plane, U plane, V plane): one block
+ * of img_h * 3 / 2 rows of img_w bytes, img_h * img_w * 3 / 2 bytes a frame.  Such frames are converted on the device, with
+ * OpenCV's integer arithmetic (cv2.cvtColor(frame, COLOR_YUV2RGB_NV12 / _I420): one (U, V) pair per 2 x 2 block, 20-bit fixed point)
+ *     y = max(0, Y - 16) * CY;   r = clamp((y + 2^19 + CVR (V - 128)) >> 20),   g = clamp((y + 2^19 + CVG (V - 128) + CUG (U - 128)) >> 20),
+ *     b = clamp((y + 2^19 + CUB (U - 128)) >> 20)
+ * and coeffs = {CY, CVR, CVG, CUG, CUB} (LT_YUV_BT601: OpenCV's own; LT_YUV_BT709; any other matrix whose magnitudes stay below
+ * 2^23 and whose sums stay inside 32 bits).  lt_set_input_format is called once, before the context's first upload: LT_ERR_INVALID
+ * for an unknown layout, missing or oversized coefficients or an odd img_w / img_h, LT_ERR_STATE for a change after an upload
+ * (a context is one camera).  coeffs is not read for LT_INPUT_RGB.  In a 4:2:0 context every upload entry point below keeps its
+ * name and meaning and takes 4:2:0 frames where it says frames_rgb: the lt_upload_frame_rows family moves the rows
+ * [row0, row1) of the Y plane and the chroma rows under them (half the bytes of the RGB form), the undistortion converts the
+ * taps it reads, and lt_upload_frames / the lt_upload_frame_rest family also leave the RGB form of the rows they bring in the
+ * slot's camera frame, so that overlays, presentation and downloads find what they find in an RGB context.  Everything behind
+ * the undistortion is bit for bit what an RGB context computes from the converted frames.
+ * lt_get_input_format reads the setting back (coeffs may be NULL).
+ * lt_yuv_to_rgb converts one host frame of h x w (even, at most 16384 each) on the device: out_rgb = h * w * 3 bytes. */
+enum lt_input_layout { LT_INPUT_RGB = 0, LT_INPUT_NV12 = 1, LT_INPUT_I420 = 2 };
+#define LT_YUV_BT601 {1220542, 1673527, -852492, -409993, 2116026}   /* video range; OpenCV's constants */
+#define LT_YUV_BT709 {1220542, 1880097, -558891, -223347, 2214593}   /* video range */
+int  lt_set_input_format(lt_ctx* ctx, int layout, const int32_t coeffs[5]);
+int  lt_get_input_format(lt_ctx* ctx, int* layout, int32_t coeffs[5]);
+int  lt_yuv_to_rgb(lt_ctx* ctx, const uint8_t* frame, int h, int w, int layout, const int32_t coeffs[5], uint8_t* out_rgb);
 /* frames: n * img_h * img_w * 3 bytes, RGB interleaved, as LaneTracker.process() receives them (:876) */
 int  lt_upload_frames(lt_ctx* ctx, const uint8_t* frames_rgb, int first_slot, int n);
 /* Camera rows [row0, row1) that undistort + warp actually read (a third of a 720-row frame at the reference
@@ -171,7 +195,8 @@ int  lt_upload_frame_rows_enqueue(lt_ctx* ctx, const uint8_t* frames_rgb, int fi
  * copy + 6 us until the first kernel behind it.  The call then returns with the copy DONE (frames_rgb is the caller's again) after
  * waiting, on the host, for kernels that still read those slots' camera rows.  Same bytes, same results.
  * lt_set_direct_upload(ctx, on): 1 / 0 allows (the default) / forbids it, negative leaves the setting; returns 1 when such calls take
- * the aperture on this context, 0 when not (no large BAR, memory not mapped, forbidden).  lt_direct_upload_count: calls that did. */
+ * the aperture on this context, 0 when not (no large BAR, memory not mapped, forbidden; always 0 in a 4:2:0 context, whose rows
+ * the engine copies into staging).  lt_direct_upload_count: calls that did. */
 int  lt_set_direct_upload(lt_ctx* ctx, int on);
 unsigned long long lt_direct_upload_count(lt_ctx* ctx);
 /* The same rows without the host wait: the copy is enqueued on the context's copy stream behind the work already

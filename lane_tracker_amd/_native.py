@@ -195,7 +195,44 @@ _SIGNATURES = {
     "lt_download_stats": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "lt_last_threshold_path": (C.c_int, [_P]),
     "lt_last_adaptive_path": (C.c_int, [_P]),
+    "lt_set_input_format": (C.c_int, [_P, C.c_int, _P]),
+    "lt_get_input_format": (C.c_int, [_P, C.POINTER(C.c_int), _P]),
+    "lt_yuv_to_rgb": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
 }
+
+# camera-frame formats (lt_input_layout) and the conversion matrices {CY, CVR, CVG, CUG, CUB} of include/lane_tracker_amd.h
+PIXEL_FORMATS = {"rgb": 0, "nv12": 1, "i420": 2}
+YUV_MATRICES = {"bt601": (1220542, 1673527, -852492, -409993, 2116026),
+                "bt709": (1220542, 1880097, -558891, -223347, 2214593)}
+
+
+def pixel_format_id(pixel_format):
+    try:
+        return PIXEL_FORMATS[pixel_format]
+    except (KeyError, TypeError):
+        raise ValueError("pixel_format must be 'rgb', 'nv12' or 'i420', got %r" % (pixel_format,)) from None
+
+
+def yuv_coeffs(matrix):
+    """'bt601' / 'bt709', or five integers {CY, CVR, CVG, CUG, CUB} -> the int32 array the library takes."""
+    if isinstance(matrix, str):
+        if matrix not in YUV_MATRICES:
+            raise ValueError("yuv_matrix must be 'bt601' or 'bt709', got %r" % (matrix,))
+        matrix = YUV_MATRICES[matrix]
+    k = np.ascontiguousarray(matrix, dtype=np.int32)
+    if k.shape != (5,):
+        raise ValueError("a conversion matrix is five integers")
+    return k
+
+
+def frame_shape(img_size, pixel_format="rgb"):
+    """Shape of one camera frame of `img_size` = (width, height) in `pixel_format`: (H, W, 3), or (H * 3 // 2, W) for 4:2:0."""
+    w, h = int(img_size[0]), int(img_size[1])
+    if pixel_format_id(pixel_format) == 0:
+        return (h, w, 3)
+    if w % 2 or h % 2:
+        raise ValueError("4:2:0 frames need an even width and height, got %dx%d" % (w, h))
+    return (h * 3 // 2, w)
 
 _lib = None
 
@@ -579,6 +616,7 @@ class Context:
         self._h = h
         self.lib = lib
         self.img_w, self.img_h, self.warp_w, self.warp_h = cal.img_w, cal.img_h, cal.warp_w, cal.warp_h
+        self._frame_tail = (cal.img_h, cal.img_w, 3)     # shape of one camera frame as the uploads take it (set_input_format)
         self.reserve(capacity)
 
     def close(self):
@@ -610,6 +648,45 @@ class Context:
         _check(self.lib.lt_set_streams(self._h, int(n)))
 
     # -- data movement
+    def set_input_format(self, pixel_format="rgb", yuv_matrix="bt601"):
+        """The pixel format of the camera frames this context takes, once, before its first upload: 'rgb' (the default), or
+        'nv12' / 'i420' -- frames of shape (H * 3 // 2, W) as OpenCV holds them, converted on the device with `yuv_matrix`
+        ('bt601', 'bt709', or five integers).  Every upload method then takes such frames."""
+        layout = pixel_format_id(pixel_format)
+        tail = frame_shape((self.img_w, self.img_h), pixel_format)
+        k = yuv_coeffs(yuv_matrix) if layout else None
+        _check(self.lib.lt_set_input_format(self._h, layout, None if k is None else k.ctypes.data))
+        self._frame_tail = tail
+
+    def input_format(self):
+        """-> (pixel format name, the five conversion coefficients)."""
+        layout, k = C.c_int(0), np.zeros(5, np.int32)
+        _check(self.lib.lt_get_input_format(self._h, C.byref(layout), k.ctypes.data))
+        return {v: n for n, v in PIXEL_FORMATS.items()}[layout.value], tuple(int(v) for v in k)
+
+    def _frames(self, frames):
+        """`frames` as the C-contiguous u8 block (n,) + one frame's shape; ValueError for frames of another shape."""
+        f = _u8(frames)
+        tail = self._frame_tail
+        if f.shape[-len(tail):] != tail or f.ndim > len(tail) + 1:
+            if len(tail) == 3:
+                return f.reshape((-1,) + tail)           # (RGB: anything of the right size, as ever)
+            raise ValueError("expected camera frames of shape %r, got %r" % (tail, f.shape))
+        return f.reshape((-1,) + tail)
+
+    def yuv_to_rgb(self, frame, layout="nv12", matrix="bt601"):
+        """One 4:2:0 frame (H * 3 // 2, W) -> RGB (H, W, 3), on the device (lt_yuv_to_rgb)."""
+        a = _u8(frame)
+        if pixel_format_id(layout) == 0:
+            raise ValueError("layout must be 'nv12' or 'i420'")
+        if a.ndim != 2 or a.shape[0] % 3 or a.shape[1] % 2 or (a.shape[0] // 3 * 2) % 2:
+            raise ValueError("a 4:2:0 frame is a 2-D array of shape (H * 3 // 2, W) with H and W even, got %r" % (a.shape,))
+        h, w = a.shape[0] // 3 * 2, a.shape[1]
+        out = np.empty((h, w, 3), np.uint8)
+        k = yuv_coeffs(matrix)
+        _check(self.lib.lt_yuv_to_rgb(self._h, a.ctypes.data, h, w, pixel_format_id(layout), k.ctypes.data, out.ctypes.data))
+        return out
+
     def source_rows(self):
         """Camera rows [row0, row1) the path reads."""
         a, b = C.c_int(0), C.c_int(0)
@@ -620,7 +697,7 @@ class Context:
         """Like upload_frames, but only the camera rows the path reads cross the bus (not enough for the overlay).
         enqueue: no wait for the copy (lt_upload_frame_rows_enqueue) -- the array handed to the library is returned and must stay
         alive and unchanged until a call that waits for work launched over these slots afterwards (download_record, sync)."""
-        f = _u8(frames).reshape(-1, self.img_h, self.img_w, 3)
+        f = self._frames(frames)
         if enqueue:
             _check(self.lib.lt_upload_frame_rows_enqueue(self._h, f.ctypes.data, first, f.shape[0]))
             return f
@@ -632,7 +709,7 @@ class Context:
         f = np.asarray(frames)
         if f.dtype != np.uint8 or not f.flags["C_CONTIGUOUS"]:
             raise ValueError("upload_frame_rows_async needs a C-contiguous uint8 array (no hidden copy may be made)")
-        f = f.reshape(-1, self.img_h, self.img_w, 3)
+        f = self._frames(f)
         _check(self.lib.lt_upload_frame_rows_async(self._h, f.ctypes.data, first, f.shape[0]))
         return f
 
@@ -640,7 +717,7 @@ class Context:
         """The rows upload_frame_rows left out, on a copy stream beside the compute streams (for the overlay); with `rows` (the
         ADDRESS of four int32 {a0, a1, b0, b1}) only those of them inside the two runs -- what present_frame with the same runs
         reads.  Returns the array actually handed to the library: keep it alive until the next sync() / download."""
-        f = _u8(frames).reshape(-1, self.img_h, self.img_w, 3)
+        f = self._frames(frames)
         if rows is None:
             _check(self.lib.lt_upload_frame_rest(self._h, f.ctypes.data, first, f.shape[0]))
         else:
@@ -650,8 +727,8 @@ class Context:
     def _frame_list(self, frames):
         fs = [_u8(f) for f in frames]
         for f in fs:
-            if f.shape != (self.img_h, self.img_w, 3):
-                raise ValueError("expected frames of shape %r, got %r" % ((self.img_h, self.img_w, 3), f.shape))
+            if f.shape != self._frame_tail:
+                raise ValueError("expected frames of shape %r, got %r" % (self._frame_tail, f.shape))
         ptrs = (C.c_void_p * max(len(fs), 1))(*[f.ctypes.data for f in fs])
         return fs, ptrs
 
@@ -686,7 +763,7 @@ class Context:
         _check(self.lib.lt_search_fit_list(self._h, len(items), items.ctypes.data if len(items) else None, C.byref(sws), C.byref(band)))
 
     def upload_frames(self, frames, first=0):
-        f = _u8(frames).reshape(-1, self.img_h, self.img_w, 3)
+        f = self._frames(frames)
         _check(self.lib.lt_upload_frames(self._h, f.ctypes.data, first, f.shape[0]))
         return f.shape[0]
 

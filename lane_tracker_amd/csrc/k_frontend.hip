@@ -1,6 +1,8 @@
 // Geometric front end + colour split, gfx950.
 //
 //   k_undistort_rows   cv2.undistort            lane_tracker.py:832   (only the rows the warp reads)
+//   k_undistort_rows_yuv  the same over a 4:2:0 frame (NV12 / I420): cv2.cvtColor(YUV2RGB_*) of every tap, then the blend
+//   k_yuv_rows_to_rgb  cv2.cvtColor(YUV2RGB_NV12 / _I420) of a run of rows (for whoever shows the camera frame)
 //   k_warp_split       cv2.warpPerspective      lane_tracker.py:834
 //                      + img[:,:,0]             lane_tracker.py:207
 //                      + cvtColor(RGB2LAB)[:,:,2] lane_tracker.py:208
@@ -123,6 +125,215 @@ __global__ __launch_bounds__(256) void k_undistort_rows(const uint8_t* __restric
         __builtin_amdgcn_raw_buffer_store_b32(out, urs, (int)o * 8, __builtin_amdgcn_readfirstlane(((slot >> 1) - pair0) * pair_b + (slot & 1) * 4), 0);
         q0 = n0;
         q1 = n1;
+    }
+}
+
+// ---- YUV 4:2:0 input ------------------------------------------------------------------------------------------------------
+// OpenCV's 8-bit YUV -> RGB: 20-bit fixed point in int32, one (U, V) pair per 2 x 2 block, no chroma interpolation.  The
+// coefficients are below 2^23 in magnitude and the samples are 9-bit, so every product is a v_mul_i32_i24 / v_mad_i32_i24
+// whose low 32 bits are the exact product (the note on __mul24 above): no quarter-rate multiply and no table.
+struct Chroma { int r, g, b; };      // the three chroma terms of a (U, V) pair, rounding constant included
+__device__ __forceinline__ Chroma yuv_chroma(int u, int v, const YuvCoef& k) {
+    u -= 128;
+    v -= 128;
+    return Chroma{__mul24(k.cvr, v) + (1 << 19), __mul24(k.cvg, v) + __mul24(k.cug, u) + (1 << 19), __mul24(k.cub, u) + (1 << 19)};
+}
+__device__ __forceinline__ int clamp255(int v) { return min(max(v, 0), 255); }
+// -> R | G << 8 | B << 16
+__device__ __forceinline__ uint32_t yuv_pixel(int yy, const Chroma& c, const YuvCoef& k) {
+    // (cy is positive and below 2^23: the mask says so to the compiler, which otherwise widens this one to v_mul_lo_u32)
+    const int y = (int)__umul24((uint32_t)max(yy - 16, 0), (uint32_t)k.cy & 0x7fffffu);
+    return (uint32_t)clamp255((y + c.r) >> 20) | ((uint32_t)clamp255((y + c.g) >> 20) << 8) | ((uint32_t)clamp255((y + c.b) >> 20) << 16);
+}
+
+// k_undistort_rows over the slots' 4:2:0 staging frames.  LAYOUT 1: NV12 (Y plane, then rows of U,V pairs), 2: I420 (Y, U, V planes).
+// Conversion is not linear (the clamps, the shift), so each of the four taps is converted before the blend.  Per frame a thread
+// fetches, for each of the two tap rows, the 4-byte window that holds the two Y samples and the 4-byte window(s) that hold the
+// one or two chroma pairs under them -- 4 loads for NV12, 6 for I420 -- as the aligned dwordx2 around the window and one
+// v_alignbyte_b32: unconditional, on clamped addresses, through a buffer resource that covers the frames of this walk (what
+// a window reads beyond its samples is never used; beyond the last slot lies padding, and beyond that the resource returns 0).
+template <int LAYOUT>
+__global__ __launch_bounds__(256) void k_undistort_rows_yuv(const uint8_t* __restrict__ yuv, size_t yuv_stride, YuvCoef k,
+                                                           const int16_t* __restrict__ uxy,
+                                                           const uint16_t* __restrict__ ufrac, FrontEndGeom g,
+                                                           uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb,
+                                                           int remap) {
+    const uint32_t per_z = gridDim.x * gridDim.y;
+    const uint32_t id = xcd_block((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x, per_z * gridDim.z, remap);
+    const uint32_t bz = id / per_z, by = (id - bz * per_z) / gridDim.x, bx = id - bz * per_z - by * gridDim.x;
+    const int x = bx * blockDim.x + threadIdx.x;
+    const int row = by;  // relative to g.r0
+    if (x >= g.img_w) return;
+    const int z0 = bz * fpb, z1 = min(z0 + fpb, n);
+    const size_t o = (size_t)row * g.img_w + x;
+    const int sx = uxy[o * 2], sy = uxy[o * 2 + 1];
+    const int f = ufrac[o], fx = f & 31, fy = f >> 5;
+    const bool y0 = sy >= 0 && sy < g.img_h, y1 = sy + 1 >= 0 && sy + 1 < g.img_h;
+    const bool x0 = sx >= 0 && sx < g.img_w, x1 = sx + 1 >= 0 && sx + 1 < g.img_w;
+    const int cy0 = min(max(sy, 0), g.img_h - 1), cy1 = min(max(sy + 1, 0), g.img_h - 1);
+    const int cxl = min(max(sx, 0), g.img_w - 2);          // leftmost column of the windows (the width is even, so >= 2)
+    const int cx0 = min(max(sx, 0), g.img_w - 1), cx1 = min(max(sx + 1, 0), g.img_w - 1);   // both in {cxl, cxl + 1}
+    const int cb = cxl & ~1;                               // first column of the chroma pair under cxl; cxl + 1 is under cb or cb + 2
+    const int ysh0 = 8 * (cx0 - cxl), ysh1 = 8 * (cx1 - cxl);                  // the taps' Y samples inside the Y window
+    const int cs0 = (cx0 - cb) >> 1, cs1 = (cx1 - cb) >> 1;                    // the taps' pair (0 / 1) inside the chroma window
+    const uint32_t plane = (uint32_t)__mul24(g.img_h, g.img_w);
+    const uint32_t offy0 = (uint32_t)(__mul24(cy0, g.img_w) + cxl), offy1 = (uint32_t)(__mul24(cy1, g.img_w) + cxl);
+    uint32_t offc0, offc1, voff = 0;
+    if constexpr (LAYOUT == 1) {
+        offc0 = plane + (uint32_t)(__mul24(cy0 >> 1, g.img_w) + cb);
+        offc1 = plane + (uint32_t)(__mul24(cy1 >> 1, g.img_w) + cb);
+    } else {
+        const int hw = g.img_w >> 1;
+        offc0 = plane + (uint32_t)(__mul24(cy0 >> 1, hw) + (cb >> 1));
+        offc1 = plane + (uint32_t)(__mul24(cy1 >> 1, hw) + (cb >> 1));
+        voff = plane >> 2;                                 // the V plane lies (h / 2) (w / 2) bytes behind the U plane
+    }
+    const uint32_t m00 = (y0 && x0) ? 255u : 0u, m01 = (y0 && x1) ? 255u : 0u;
+    const uint32_t m10 = (y1 && x0) ? 255u : 0u, m11 = (y1 && x1) ? 255u : 0u;
+    const uint32_t gx = 32u - (uint32_t)fx, gy = 32u - (uint32_t)fy;
+    const uint32_t w00 = (gx * gy) & 0x7ffu, w01 = ((uint32_t)fx * gy) & 0x7ffu, w10 = (gx * (uint32_t)fy) & 0x7ffu, w11 = ((uint32_t)fx * (uint32_t)fy) & 0x7ffu;
+    constexpr int RSRC_RAW = 0x00027000;   // untyped 32-bit buffer, no swizzle
+    const int nz = z1 - z0, fstride = (int)yuv_stride;
+    const __amdgpu_buffer_rsrc_t frs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(yuv + (size_t)z0 * yuv_stride), 0, nz * fstride + 16, RSRC_RAW);
+    const int pair0 = (first_slot + z0) >> 1, pair1 = (first_slot + z1 - 1) >> 1, pair_b = (int)(und_px * 8);
+    const __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc(und + (size_t)pair0 * 2 * und_px, 0, (pair1 - pair0 + 1) * pair_b, RSRC_RAW);
+    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+    auto window = [&](uint32_t off, int frame_off) {       // the 4 bytes at `off` of the frame at `frame_off`
+        const u32x2 d = __builtin_amdgcn_raw_buffer_load_b64(frs, (int)(off & ~3u), frame_off, 0);
+        return __builtin_amdgcn_alignbyte(d.y, d.x, off & 3u);
+    };
+    struct Taps { uint32_t ya, yb, ca, cb, va, vb; };      // Y and chroma windows of the upper (a) and lower (b) tap row; va / vb: I420's V
+    auto fetch = [&](int frame_off) {
+        Taps t;
+        t.ya = window(offy0, frame_off);
+        t.yb = window(offy1, frame_off);
+        t.ca = window(offc0, frame_off);
+        t.cb = window(offc1, frame_off);
+        if constexpr (LAYOUT == 2) {
+            t.va = window(offc0 + voff, frame_off);
+            t.vb = window(offc1 + voff, frame_off);
+        } else {
+            t.va = t.vb = 0;
+        }
+        return t;
+    };
+    auto tap = [&](uint32_t yw, uint32_t cw, uint32_t vw, int ysh, int cs) {
+        int u, v;
+        if constexpr (LAYOUT == 1) {
+            u = (int)((cw >> (16 * cs)) & 255u);
+            v = (int)((cw >> (16 * cs + 8)) & 255u);
+        } else {
+            u = (int)((cw >> (8 * cs)) & 255u);
+            v = (int)((vw >> (8 * cs)) & 255u);
+        }
+        return yuv_pixel((int)((yw >> ysh) & 255u), yuv_chroma(u, v, k), k);
+    };
+    Taps q = fetch(0);
+    for (int z = z0; z < z1; ++z) {
+        // the next frame's taps are in flight while this one is converted and blended
+        const Taps nq = fetch((min(z + 1, z1 - 1) - z0) * fstride);
+        const uint32_t a0 = tap(q.ya, q.ca, q.va, ysh0, cs0), a1 = tap(q.ya, q.ca, q.va, ysh1, cs1);
+        const uint32_t b0 = tap(q.yb, q.cb, q.vb, ysh0, cs0), b1 = tap(q.yb, q.cb, q.vb, ysh1, cs1);
+        uint32_t out = 0;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const uint32_t v00 = (a0 >> (8 * ch)) & m00, v01 = (a1 >> (8 * ch)) & m01;
+            const uint32_t v10 = (b0 >> (8 * ch)) & m10, v11 = (b1 >> (8 * ch)) & m11;
+            out |= ((v00 * w00 + v01 * w01 + v10 * w10 + v11 * w11 + 512u) >> 10) << (8 * ch);   // k_undistort_rows' blend
+        }
+        const int slot = first_slot + z;   // wave-uniform: pair and parity go into the scalar offset of the store
+        __builtin_amdgcn_raw_buffer_store_b32(out, urs, (int)o * 8, __builtin_amdgcn_readfirstlane(((slot >> 1) - pair0) * pair_b + (slot & 1) * 4), 0);
+        q = nq;
+    }
+}
+
+// Rows [r0, r1) of 4:2:0 frames -> the same rows of RGB frames (3 B/px): a streaming kernel for whoever shows the camera frame.
+// One thread owns the two rows of a chroma row over 16 columns: 16 Y bytes per row and the 8 (U, V) pairs under them in
+// 16-byte loads, each pair's three chroma terms computed once for its four pixels, 48 bytes per row in three 16-byte stores.
+// Either row of the pair may lie outside [r0, r1) (block-uniform) and is then neither read nor written.
+template <int LAYOUT>
+__global__ __launch_bounds__(256) void k_yuv_rows_to_rgb(const uint8_t* __restrict__ yuv, size_t yuv_stride, YuvCoef k,
+                                                        uint8_t* __restrict__ rgb, size_t rgb_stride, int h, int w, int r0, int r1) {
+    const int x0 = (int)(blockIdx.x * blockDim.x + threadIdx.x) * 16;
+    if (x0 >= w) return;
+    const int cr = (r0 >> 1) + (int)blockIdx.y;            // chroma row
+    const uint8_t* src = yuv + (size_t)blockIdx.z * yuv_stride;
+    uint8_t* dst = rgb + (size_t)blockIdx.z * rgb_stride;
+    const size_t plane = (size_t)h * w;
+    uint32_t uv[4];                                        // NV12: 8 (U, V) pairs; I420: uv[0..1] 8 U, uv[2..3] 8 V
+    if constexpr (LAYOUT == 1) {
+        const uint4 c = *reinterpret_cast<const uint4*>(src + plane + (size_t)cr * w + x0);
+        uv[0] = c.x; uv[1] = c.y; uv[2] = c.z; uv[3] = c.w;
+    } else {
+        const size_t co = plane + (size_t)cr * (w >> 1) + (x0 >> 1);
+        const uint2 cu = *reinterpret_cast<const uint2*>(src + co), cv = *reinterpret_cast<const uint2*>(src + co + (plane >> 2));
+        uv[0] = cu.x; uv[1] = cu.y; uv[2] = cv.x; uv[3] = cv.y;
+    }
+    Chroma c[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        int u, v;
+        if constexpr (LAYOUT == 1) {
+            u = (int)((uv[i >> 1] >> (16 * (i & 1))) & 255u);
+            v = (int)((uv[i >> 1] >> (16 * (i & 1) + 8)) & 255u);
+        } else {
+            u = (int)((uv[i >> 2] >> (8 * (i & 3))) & 255u);
+            v = (int)((uv[2 + (i >> 2)] >> (8 * (i & 3))) & 255u);
+        }
+        c[i] = yuv_chroma(u, v, k);
+    }
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy) {
+        const int y = 2 * cr + dy;
+        if (y < r0 || y >= r1) continue;
+        const uint4 yq = *reinterpret_cast<const uint4*>(src + (size_t)y * w + x0);
+        const uint32_t yw[4] = {yq.x, yq.y, yq.z, yq.w};
+        uint32_t d[12];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {                      // four pixels (two chroma pairs) -> three dwords
+            uint32_t p[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) p[i] = yuv_pixel((int)((yw[j] >> (8 * i)) & 255u), c[2 * j + (i >> 1)], k);
+            d[3 * j] = p[0] | (p[1] << 24);
+            d[3 * j + 1] = (p[1] >> 8) | (p[2] << 16);
+            d[3 * j + 2] = (p[2] >> 16) | (p[3] << 8);
+        }
+        uint4* o = reinterpret_cast<uint4*>(dst + ((size_t)y * w + x0) * 3);
+        o[0] = make_uint4(d[0], d[1], d[2], d[3]);
+        o[1] = make_uint4(d[4], d[5], d[6], d[7]);
+        o[2] = make_uint4(d[8], d[9], d[10], d[11]);
+    }
+}
+
+// the same for any even width and any alignment: one thread per 2 x 2 block, byte accesses
+template <int LAYOUT>
+__global__ __launch_bounds__(256) void k_yuv_rows_to_rgb_any(const uint8_t* __restrict__ yuv, size_t yuv_stride, YuvCoef k,
+                                                            uint8_t* __restrict__ rgb, size_t rgb_stride, int h, int w, int r0, int r1) {
+    const int bx = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (2 * bx >= w) return;
+    const int cr = (r0 >> 1) + (int)blockIdx.y;
+    const uint8_t* src = yuv + (size_t)blockIdx.z * yuv_stride;
+    uint8_t* dst = rgb + (size_t)blockIdx.z * rgb_stride;
+    const size_t plane = (size_t)h * w;
+    int u, v;
+    if constexpr (LAYOUT == 1) {
+        u = src[plane + (size_t)cr * w + 2 * bx];
+        v = src[plane + (size_t)cr * w + 2 * bx + 1];
+    } else {
+        u = src[plane + (size_t)cr * (w >> 1) + bx];
+        v = src[plane + (plane >> 2) + (size_t)cr * (w >> 1) + bx];
+    }
+    const Chroma c = yuv_chroma(u, v, k);
+    for (int dy = 0; dy < 2; ++dy) {
+        const int y = 2 * cr + dy;
+        if (y < r0 || y >= r1) continue;
+        for (int dx = 0; dx < 2; ++dx) {
+            const size_t o = (size_t)y * w + 2 * bx + dx;
+            const uint32_t p = yuv_pixel(src[o], c, k);
+            dst[o * 3] = (uint8_t)p;
+            dst[o * 3 + 1] = (uint8_t)(p >> 8);
+            dst[o * 3 + 2] = (uint8_t)(p >> 16);
+        }
     }
 }
 
@@ -485,6 +696,34 @@ void launch_undistort_rows(hipStream_t s, const uint8_t* frames, size_t frame_st
         hipLaunchKernelGGL(k_undistort_rows<true>, grid, dim3(256), 0, s, frames, frame_stride, uxy, ufrac, g, und, und_px, first_slot, n, fpb, xcd_remap());
     else
         hipLaunchKernelGGL(k_undistort_rows<false>, grid, dim3(256), 0, s, frames, frame_stride, uxy, ufrac, g, und, und_px, first_slot, n, fpb, xcd_remap());
+}
+
+void launch_undistort_rows_yuv(hipStream_t s, int layout, const uint8_t* yuv, size_t yuv_stride, YuvCoef k, const int16_t* uxy,
+                               const uint16_t* ufrac, FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n) {
+    if (n <= 0 || g.nrows <= 0) return;
+    // (the frames of a walk are addressed by a 32-bit offset into one buffer resource)
+    const int fpb = (int)std::max<size_t>(1, std::min<size_t>((size_t)frames_per_thread(n), ((size_t)1 << 30) / yuv_stride));
+    dim3 grid((g.img_w + 255) / 256, g.nrows, (n + fpb - 1) / fpb);
+    if (layout == 1)
+        hipLaunchKernelGGL(k_undistort_rows_yuv<1>, grid, dim3(256), 0, s, yuv, yuv_stride, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, xcd_remap());
+    else
+        hipLaunchKernelGGL(k_undistort_rows_yuv<2>, grid, dim3(256), 0, s, yuv, yuv_stride, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, xcd_remap());
+}
+
+void launch_yuv_rows_to_rgb(hipStream_t s, int layout, const uint8_t* yuv, size_t yuv_stride, YuvCoef k, uint8_t* rgb,
+                            size_t rgb_stride, int h, int w, int r0, int r1, int n) {
+    if (n <= 0 || r1 <= r0) return;
+    const unsigned crows = (unsigned)(((r1 + 1) >> 1) - (r0 >> 1));
+    const bool wide = (w & 15) == 0 && ((yuv_stride | rgb_stride | (size_t)(uintptr_t)yuv | (size_t)(uintptr_t)rgb) & 15) == 0;
+    if (wide) {
+        dim3 grid((unsigned)((w / 16 + 63) / 64), crows, (unsigned)n);
+        if (layout == 1) hipLaunchKernelGGL(k_yuv_rows_to_rgb<1>, grid, dim3(64), 0, s, yuv, yuv_stride, k, rgb, rgb_stride, h, w, r0, r1);
+        else hipLaunchKernelGGL(k_yuv_rows_to_rgb<2>, grid, dim3(64), 0, s, yuv, yuv_stride, k, rgb, rgb_stride, h, w, r0, r1);
+    } else {
+        dim3 grid((unsigned)((w / 2 + 255) / 256), crows, (unsigned)n);
+        if (layout == 1) hipLaunchKernelGGL(k_yuv_rows_to_rgb_any<1>, grid, dim3(256), 0, s, yuv, yuv_stride, k, rgb, rgb_stride, h, w, r0, r1);
+        else hipLaunchKernelGGL(k_yuv_rows_to_rgb_any<2>, grid, dim3(256), 0, s, yuv, yuv_stride, k, rgb, rgb_stride, h, w, r0, r1);
+    }
 }
 
 void launch_warp_split(hipStream_t s, const uint32_t* und, size_t und_px, int first_slot, const int16_t* wxy,

@@ -64,6 +64,7 @@ int sync_all(lt_ctx* c) {
     c->readers.reset();                                 // every reader / writer enqueued so far is done
     c->writers.reset();
     c->rests.reset();
+    c->yuv_rows.reset();
     return LT_OK;
 }
 
@@ -180,6 +181,7 @@ int set_device(lt_ctx* c) {
 
 void free_slots(lt_ctx* c) {
     dev_free(c->d_frames);
+    dev_free(c->d_yuv);
     dev_free(c->d_und);
     dev_free(c->d_bev);
     for (auto& p : c->d_plane) dev_free(p);
@@ -801,6 +803,8 @@ int lt_create(const lt_calib* calib, int device, lt_ctx** out) {
 
     preload_kernels(device, c->stream);
     c->frame_bytes = (size_t)calib->img_h * calib->img_w * 3;
+    c->yuv_bytes = c->frame_bytes / 2;
+    c->yuv_stride = (c->yuv_bytes + 15) & ~(size_t)15;
     c->und_bytes = (size_t)c->fe.nrows * calib->img_w * 3;   // as returned by lt_download_undistorted (RGB)
     c->und_px = (size_t)c->fe.nrows * calib->img_w;
     c->plane_bytes = (size_t)calib->warp_h * calib->warp_w;
@@ -852,6 +856,7 @@ void lt_destroy(lt_ctx* c) {
     for (auto& w : c->readers.e) if (w.ev) (void)hipEventDestroy(w.ev);
     for (auto& w : c->writers.e) if (w.ev) (void)hipEventDestroy(w.ev);
     for (auto& w : c->rests.e) if (w.ev) (void)hipEventDestroy(w.ev);
+    for (auto& w : c->yuv_rows.e) if (w.ev) (void)hipEventDestroy(w.ev);
     for (auto& t : c->chains) (void)hipEventDestroy(t.done);
     for (auto e : c->chain_event_pool) (void)hipEventDestroy(e);
     note("hipHostFree(small, rec, rec_stage, cancel)");
@@ -913,6 +918,7 @@ int lt_reserve(lt_ctx* c, int capacity) {
     const size_t n = (size_t)capacity;
     if ((rc = dev_alloc(&c->d_frames, n * c->frame_bytes + 16))) { free_slots(c); return rc; }   // +16: k_undistort_rows reads 8-byte windows
     c->direct_upload = -1;               // a new frame buffer: whether the host can write it is found out by the first small upload
+    if (c->in_layout != LT_INPUT_RGB && (rc = dev_alloc(&c->d_yuv, n * c->yuv_stride + 16))) { free_slots(c); return rc; }
     if ((rc = dev_alloc(&c->d_und, (size_t)((n + 1) / 2) * 2 * c->und_px))) { free_slots(c); return rc; }
     for (int i : {(int)P_R, (int)P_B, (int)P_THR, (int)P_THB, (int)P_T0})     // the others when a path that uses them runs (ensure_plane)
         if ((rc = dev_alloc(&c->d_plane[i], n * c->plane_bytes))) { free_slots(c); return rc; }
@@ -1015,6 +1021,74 @@ int lt_set_streams(lt_ctx* c, int nstreams) {
     return LT_OK;
 }
 
+// ---- YUV 4:2:0 input ----------------------------------------------------------------------------------
+// OpenCV's 20-bit fixed-point conversion with the caller's five coefficients {CY, CVR, CVG, CUG, CUB}.  The kernels multiply with
+// 24-bit instructions and add in int32: CY positive, every magnitude below 2^23, and no intermediate beyond int32.
+static int check_yuv_format(int layout, const int32_t* k, int h, int w) {
+    if (layout != LT_INPUT_NV12 && layout != LT_INPUT_I420) return fail(LT_ERR_INVALID, "input layout must be RGB (0), NV12 (1) or I420 (2)");
+    if (!k) return fail(LT_ERR_INVALID, "a 4:2:0 layout needs its five conversion coefficients");
+    if (h < 2 || w < 2 || (h & 1) || (w & 1)) return fail(LT_ERR_INVALID, "4:2:0 frames need an even width and height, got %dx%d", w, h);
+    const long long lim = 1LL << 23;
+    if (k[0] <= 0 || k[0] >= lim) return fail(LT_ERR_INVALID, "the luma coefficient must be in (0, 2^23)");
+    for (int i = 1; i < 5; ++i)
+        if (k[i] <= -lim || k[i] >= lim) return fail(LT_ERR_INVALID, "conversion coefficients must be below 2^23 in magnitude");
+    const long long chroma = std::max({std::llabs((long long)k[1]), std::llabs((long long)k[2]) + std::llabs((long long)k[3]), std::llabs((long long)k[4])});
+    if (239LL * k[0] + (1LL << 19) + 128LL * chroma > 0x7fffffffLL) return fail(LT_ERR_INVALID, "conversion coefficients overflow 32 bits");
+    return LT_OK;
+}
+
+int lt_set_input_format(lt_ctx* c, int layout, const int32_t* coeffs) {
+    if (!c) return fail(LT_ERR_INVALID, "null context");
+    int rc;
+    if (layout != LT_INPUT_RGB && (rc = check_yuv_format(layout, coeffs, c->calib.img_h, c->calib.img_w))) return rc;
+    const bool same = layout == c->in_layout && (layout == LT_INPUT_RGB || std::memcmp(coeffs, c->yuv_coef, sizeof c->yuv_coef) == 0);
+    if (same) return LT_OK;
+    if (c->input_locked) return fail(LT_ERR_STATE, "the input format of a context cannot change after its first upload");
+    if ((rc = set_device(c))) return rc;
+    if ((rc = sync_all(c))) return rc;
+    if (layout == LT_INPUT_RGB) {
+        dev_free(c->d_yuv);
+    } else {
+        if (c->capacity > 0 && !c->d_yuv && (rc = dev_alloc(&c->d_yuv, (size_t)c->capacity * c->yuv_stride + 16))) return rc;
+        std::memcpy(c->yuv_coef, coeffs, sizeof c->yuv_coef);
+    }
+    c->in_layout = layout;
+    return LT_OK;
+}
+
+int lt_get_input_format(lt_ctx* c, int* layout, int32_t* coeffs) {
+    if (!c || !layout) return fail(LT_ERR_INVALID, "null argument");
+    *layout = c->in_layout;
+    if (coeffs) std::memcpy(coeffs, c->yuv_coef, sizeof c->yuv_coef);
+    return LT_OK;
+}
+
+// Rows [r0, r1) of the Y plane and rows [c0, c1) of the chroma plane(s) of n host frames (yuv_bytes apart) into the staging
+// frames of slots [first, first + n), on `st`: one pitched copy per plane piece.
+static int yuv_copy(lt_ctx* c, const uint8_t* frames, int first, int n, int r0, int r1, int c0, int c1, hipStream_t st) {
+    const size_t W = (size_t)c->calib.img_w, plane = (size_t)c->calib.img_h * W;
+    uint8_t* dst = slot_yuv(c, first);
+    auto piece = [&](size_t off, size_t bytes) {
+        HIP_TRY(hipMemcpy2DAsync(dst + off, c->yuv_stride, frames + off, c->yuv_bytes, bytes, (size_t)n, hipMemcpyHostToDevice, st));
+        return (int)LT_OK;
+    };
+    int rc = LT_OK;
+    if (r1 > r0 && c1 > c0 && r0 == 0 && r1 == c->calib.img_h && c0 == 0 && c1 == c->calib.img_h / 2) return piece(0, c->yuv_bytes);
+    if (r1 > r0 && (rc = piece((size_t)r0 * W, (size_t)(r1 - r0) * W))) return rc;
+    if (c1 <= c0) return rc;
+    if (c->in_layout == LT_INPUT_NV12) return piece(plane + (size_t)c0 * W, (size_t)(c1 - c0) * W);
+    if ((rc = piece(plane + (size_t)c0 * (W / 2), (size_t)(c1 - c0) * (W / 2)))) return rc;
+    return piece(plane + plane / 4 + (size_t)c0 * (W / 2), (size_t)(c1 - c0) * (W / 2));
+}
+// chroma rows under the Y rows [r0, r1)
+static inline int chroma_lo(int r0) { return r0 / 2; }
+static inline int chroma_hi(int r0, int r1) { return r1 > r0 ? (r1 - 1) / 2 + 1 : r0 / 2; }
+// rows [r0, r1) of the staging frames of slots [first, first + n) -> the same rows of their RGB camera frames, on `st`
+static void yuv_convert(lt_ctx* c, hipStream_t st, int first, int n, int r0, int r1) {
+    launch_yuv_rows_to_rgb(st, c->in_layout, slot_yuv(c, first), c->yuv_stride, yuv_coef_of(c), slot_frame(c, first), c->frame_bytes,
+                           c->calib.img_h, c->calib.img_w, r0, r1, n);
+}
+
 // ---- data movement -------------------------------------------------------------------------------
 int lt_upload_frames(lt_ctx* c, const uint8_t* frames, int first, int n) {
     int rc = check_slots(c, first, n);
@@ -1022,6 +1096,13 @@ int lt_upload_frames(lt_ctx* c, const uint8_t* frames, int first, int n) {
     if (!frames) return fail(LT_ERR_INVALID, "null frames");
     if ((rc = set_device(c))) return rc;
     if ((rc = sync_all(c))) return rc;
+    if (n > 0) c->input_locked = true;
+    if (c->in_layout != LT_INPUT_RGB) {
+        // 4:2:0: the frames into staging (what the undistortion reads), and their RGB form into the camera frames for whoever shows them
+        if (n > 0 && (rc = yuv_copy(c, frames, first, n, 0, c->calib.img_h, 0, c->calib.img_h / 2, c->stream))) return rc;
+        yuv_convert(c, c->stream, first, n, 0, c->calib.img_h);
+        HIP_TRY(hipGetLastError());
+    } else
     HIP_TRY(hipMemcpyAsync(slot_frame(c, first), frames, (size_t)n * c->frame_bytes,
                            hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1045,6 +1126,7 @@ static int check_upload(lt_ctx* c, const uint8_t* frames, int first, int n) {
     int rc = check_slots(c, first, n);
     if (rc) return rc;
     if (!frames) return fail(LT_ERR_INVALID, "null frames");
+    if (n > 0) c->input_locked = true;
     return n > 0 ? set_device(c) : LT_OK;
 }
 // A stream-ordered copy into the camera rows of slots [first, first + n) waits on `st` for the kernels that still read them (slot-range
@@ -1080,7 +1162,7 @@ static bool host_has_mapped(const void* p, size_t n) {
 static bool direct_upload_possible(lt_ctx* c) {
     if (c->direct_upload < 0)
         c->direct_upload = c->prop.isLargeBar && c->d_frames && host_has_mapped(c->d_frames, (size_t)c->capacity * c->frame_bytes) ? 1 : 0;
-    return c->direct_upload == 1 && c->direct_upload_wanted;
+    return c->direct_upload == 1 && c->direct_upload_wanted && c->in_layout == LT_INPUT_RGB;   // (4:2:0 frames take the engine)
 }
 __attribute__((target("avx2"))) static void store_stream_avx2(uint8_t* dst, const uint8_t* src, size_t n) {
     size_t head = (32 - ((uintptr_t)dst & 31)) & 31;
@@ -1169,6 +1251,20 @@ static int upload_frame_rows_impl(lt_ctx* c, const uint8_t* frames, int first, i
     if ((!enqueue || enqueue_syncs) && (rc = sync_all(c))) return rc;
     mark_frames(c, first, n, 0);         // a new frame's rows: the others are the previous occupant's until lt_upload_frame_rest
     front_stale(c, first, n);
+    if (c->in_layout != LT_INPUT_RGB) {
+        // 4:2:0: the same rows of the Y plane and the chroma rows under them, into staging; nothing is converted.  The enqueued
+        // copies are noted (yuv_rows): the conversion lt_upload_frame_rest puts on the copy stream reads these rows.
+        const int c0 = chroma_lo(c->cam_r0), c1 = chroma_hi(c->cam_r0, c->cam_r1);
+        if (enqueue)
+            return for_each_slice(c, first, n, [&](hipStream_t st, int f0, int m) {
+                int wrc = enqueue_syncs ? (int)LT_OK : wait_camera_readers(c, st, f0, m);
+                if (!wrc) wrc = yuv_copy(c, frames + (size_t)(f0 - first) * c->yuv_bytes, f0, m, c->cam_r0, c->cam_r1, c0, c1, st);
+                return wrc ? wrc : note_range(c->yuv_rows, st, f0, f0 + m);
+            });
+        if ((rc = yuv_copy(c, frames, first, n, c->cam_r0, c->cam_r1, c0, c1, c->stream))) return rc;
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return LT_OK;
+    }
     const size_t row_bytes = (size_t)c->calib.img_w * 3, off = (size_t)c->cam_r0 * row_bytes;
     const size_t bytes = (size_t)(c->cam_r1 - c->cam_r0) * row_bytes;
     // (one frame, measured in round 5 against this pitched copy, 279-286 us per frame of process(): a plain copy of the contiguous
@@ -1233,9 +1329,13 @@ int lt_upload_frame_rows_async(lt_ctx* c, const uint8_t* frames, int first, int 
     // the copy waits for the kernels that still read these slots' camera rows (the undistortion launches over these slots, the
     // overlay) -- not for the rest of their mask chains, and not for launches over other slots
     if ((rc = wait_camera_readers(c, c->copy, first, n))) return rc;
+    if (c->in_layout != LT_INPUT_RGB) {
+        if ((rc = yuv_copy(c, frames, first, n, c->cam_r0, c->cam_r1, chroma_lo(c->cam_r0), chroma_hi(c->cam_r0, c->cam_r1), c->copy))) return rc;
+    } else {
     const size_t row_bytes = (size_t)c->calib.img_w * 3, off = (size_t)c->cam_r0 * row_bytes;
     HIP_TRY(hipMemcpy2DAsync(slot_frame(c, first) + off, c->frame_bytes, frames + off, c->frame_bytes,
                              (size_t)(c->cam_r1 - c->cam_r0) * row_bytes, (size_t)n, hipMemcpyHostToDevice, c->copy));
+    }
     hipEvent_t up = next_order_event(c);
     if (!up) return fail(LT_ERR_HIP, "hipEventCreate failed");
     HIP_TRY(hipEventRecord(up, c->copy));
@@ -1243,6 +1343,15 @@ int lt_upload_frame_rows_async(lt_ctx* c, const uint8_t* frames, int first, int 
         HIP_TRY(hipStreamWaitEvent(st, up, 0));
         return (int)LT_OK;
     });
+}
+
+// 4:2:0: the copy stream waits for the enqueued uploads of source rows into the staging frames of slots [first, first + n) (the
+// synchronous form has finished, the stream-ordered one is on the copy stream itself)
+static int wait_yuv_rows(lt_ctx* c, int first, int n) {
+    bool precise = true;
+    int rc = wait_range(c->yuv_rows, c->copy, first, first + n, &precise);
+    if (!rc && !precise) rc = wait_reader_tails(c, c->copy);
+    return rc;
 }
 
 // the overlay (on the presentation stream) waits for the copies into its own slots before it reads the frames (or, when the
@@ -1266,6 +1375,22 @@ int lt_upload_frame_rest_rows(lt_ctx* c, const uint8_t* frames, int first, int n
     // of the two runs, the rows lt_upload_frame_rows has not brought: below the window of rows the path reads, and above it
     const size_t row_bytes = (size_t)c->calib.img_w * 3;
     const int lo = c->cam_r1 > c->cam_r0 ? c->cam_r0 : 0, hi = c->cam_r1 > c->cam_r0 ? c->cam_r1 : 0;
+    if (c->in_layout != LT_INPUT_RGB) {
+        // 4:2:0: those rows of the Y plane and the chroma rows under them that the source rows' upload has not brought either, into
+        // staging; then both runs whole -- the source rows they cover included, which lt_upload_frame_rows left in staging -- as RGB
+        // into the camera frame
+        const int c0 = chroma_lo(lo), c1 = chroma_hi(lo, hi);
+        for (int k = 0; k < 4; k += 2) {
+            const int a = rows4[k], b = std::min(rows4[k + 1], lo), d = std::max(rows4[k], hi), e = rows4[k + 1];
+            if (b > a && (rc = yuv_copy(c, frames, first, n, a, b, chroma_lo(a), std::min(chroma_hi(a, b), c0), c->copy))) return rc;
+            if (e > d && (rc = yuv_copy(c, frames, first, n, d, e, std::max(chroma_lo(d), c1), chroma_hi(d, e), c->copy))) return rc;
+        }
+        if ((rc = wait_yuv_rows(c, first, n))) return rc;
+        for (int k = 0; k < 4; k += 2) yuv_convert(c, c->copy, first, n, rows4[k], rows4[k + 1]);
+        HIP_TRY(hipGetLastError());
+        if ((rc = note_range(c->readers, c->copy, first, first + n))) return rc;     // the conversion reads staging: the next upload into it waits
+        return rest_mark(c, first, n);
+    }
     uint8_t* dst = slot_frame(c, first);
     for (int k = 0; k < 4; k += 2) {
         const int piece[2][2] = {{rows4[k], std::min(rows4[k + 1], lo)}, {std::max(rows4[k], hi), rows4[k + 1]}};
@@ -1284,6 +1409,23 @@ int lt_upload_frame_rest(lt_ctx* c, const uint8_t* frames, int first, int n) {
     // these rows are read by nobody but the overlay: the copy waits for the overlays still reading the frames it replaces
     // (slot-range events; a stream of windows re-uses its slots), and the overlay of these slots waits for it
     if ((rc = wait_camera_readers(c, c->copy, first, n))) return rc;
+    if (c->in_layout != LT_INPUT_RGB) {
+        // 4:2:0: the rows of the Y and chroma planes that lt_upload_frame_rows has not brought into staging, then the whole frame as
+        // RGB into the camera frame, behind both copies
+        const int H = c->calib.img_h, r0 = c->cam_r1 > c->cam_r0 ? c->cam_r0 : 0, r1 = c->cam_r1 > c->cam_r0 ? c->cam_r1 : 0;
+        if (r1 <= r0) {
+            if ((rc = yuv_copy(c, frames, first, n, 0, H, 0, H / 2, c->copy))) return rc;
+        } else {
+            if ((rc = yuv_copy(c, frames, first, n, 0, r0, 0, chroma_lo(r0), c->copy))) return rc;
+            if ((rc = yuv_copy(c, frames, first, n, r1, H, chroma_hi(r0, r1), H / 2, c->copy))) return rc;
+            if ((rc = wait_yuv_rows(c, first, n))) return rc;
+        }
+        yuv_convert(c, c->copy, first, n, 0, H);
+        HIP_TRY(hipGetLastError());
+        if ((rc = note_range(c->readers, c->copy, first, first + n))) return rc;     // the conversion reads staging: the next upload into it waits
+        mark_frames(c, first, n, 1);
+        return rest_mark(c, first, n);
+    }
     const size_t row_bytes = (size_t)c->calib.img_w * 3;
     const size_t head = (size_t)c->cam_r0 * row_bytes, tail0 = (size_t)c->cam_r1 * row_bytes;
     uint8_t* dst = slot_frame(c, first);
@@ -1742,6 +1884,10 @@ static int mask_run_impl(lt_ctx* c, int first, int n, const lt_filter_params* p,
         for (int i = f0; have_front && i < f0 + m; ++i) have_front = c->front_ok[(size_t)i] != 0;
         if (!have_front) {
             { StageScope t(c, ST_UNDISTORT, st);
+              if (c->in_layout != LT_INPUT_RGB)
+                  launch_undistort_rows_yuv(st, c->in_layout, slot_yuv(c, f0), c->yuv_stride, yuv_coef_of(c), c->d_uxy, c->d_ufrac,
+                                            c->fe, c->d_und, c->und_px, f0, m);
+              else
               launch_undistort_rows(st, slot_frame(c, f0), c->frame_bytes, c->d_uxy, c->d_ufrac,
                                     c->fe, c->d_und, c->und_px, f0, m); }
             { int mrc = n == 1 ? note_range_frame(c, c->readers, st, f0, f0 + m) : note_range(c->readers, st, f0, f0 + m); if (mrc) return mrc; }
@@ -2105,6 +2251,31 @@ int lt_bilateral_adaptive_threshold(lt_ctx* c, const uint8_t* img, int h, int w,
     dev_free(d_in);
     dev_free(d_out);
     if (e != hipSuccess) return fail(LT_ERR_HIP, "bilateral threshold failed: %s", hipGetErrorString(e));
+    return LT_OK;
+}
+
+// one 4:2:0 host frame of any even size -> RGB, on the device (cv2.cvtColor(frame, COLOR_YUV2RGB_NV12 / _I420) with the given matrix)
+int lt_yuv_to_rgb(lt_ctx* c, const uint8_t* frame, int h, int w, int layout, const int32_t* coeffs, uint8_t* out_rgb) {
+    if (!c || !frame || !out_rgb) return fail(LT_ERR_INVALID, "null argument");
+    int rc = check_yuv_format(layout, coeffs, h, w);
+    if (rc) return rc;
+    if (h > 16384 || w > 16384) return fail(LT_ERR_INVALID, "bad image size (at most 16384 x 16384)");
+    if ((rc = set_device(c))) return rc;
+    const size_t px = (size_t)h * w;
+    uint8_t *d_in = nullptr, *d_out = nullptr;
+    if ((rc = dev_alloc(&d_in, px * 3 / 2))) return rc;
+    if ((rc = dev_alloc(&d_out, px * 3))) { dev_free(d_in); return rc; }
+    hipError_t e = hipMemcpyAsync(d_in, frame, px * 3 / 2, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        launch_yuv_rows_to_rgb(c->stream, layout, d_in, px * 3 / 2, YuvCoef{coeffs[0], coeffs[1], coeffs[2], coeffs[3], coeffs[4]}, d_out,
+                               px * 3, h, w, 0, h, 1);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out_rgb, d_out, px * 3, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    dev_free(d_in);
+    dev_free(d_out);
+    if (e != hipSuccess) return fail(LT_ERR_HIP, "YUV conversion failed: %s", hipGetErrorString(e));
     return LT_OK;
 }
 

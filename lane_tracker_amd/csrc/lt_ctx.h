@@ -61,6 +61,15 @@ struct lt_ctx {
     int capacity = 0;
     size_t frame_bytes = 0, und_bytes = 0, plane_bytes = 0, bev_bytes = 0;
     uint8_t *d_frames = nullptr, *d_bev = nullptr;
+    // YUV 4:2:0 input (lt_set_input_format): the caller's layout, the five conversion coefficients, and per slot a staging frame
+    // of yuv_bytes = h * w * 3 / 2 bytes in that layout, yuv_stride (a multiple of 16) apart, 16 bytes of padding behind the last
+    // one (k_undistort_rows_yuv reads aligned 8-byte windows).  The undistortion reads the staging frame; the RGB camera frame
+    // of a slot is written by k_yuv_rows_to_rgb behind the uploads that would have brought RGB rows for whoever shows the frame.
+    int in_layout = 0;                        // LT_INPUT_RGB
+    int32_t yuv_coef[5] = {0, 0, 0, 0, 0};
+    bool input_locked = false;                // an upload has happened: the format stays
+    uint8_t* d_yuv = nullptr;
+    size_t yuv_bytes = 0, yuv_stride = 0;
     uint32_t* d_und = nullptr;        // undistorted camera rows [r0, r0+nrows), one RGBX dword per pixel, slots 2p / 2p+1 interleaved (und_slot_base)
     size_t und_px = 0;                // pixels per slot of d_und
     uint8_t* d_plane[P_COUNT] = {};   // P_R, P_B, P_THR, P_THB, P_T0 with the slots; the others on first use (ensure_plane)
@@ -198,6 +207,7 @@ struct lt_ctx {
         void reset() { head = count = 0; overflow = false; lazy = false; lazy_seen = lazy_seq; }
     };
     RangeEvents readers, writers;
+    RangeEvents yuv_rows;                     // 4:2:0 context: the enqueued copies of source rows into staging (slots' streams): the conversion of a slot's rows waits for them
     RangeEvents rests;                        // lt_upload_frame_rest copies (copy stream): the overlay of a slot waits for ITS rows only
     // The chained band search of a stream (lt_band_fit_chain_run) is one workgroup walking many frames: it runs on a stream
     // of its own, beside the mask chains of later frames on the slots' streams.  A chain leaves its records in page-locked
@@ -237,6 +247,8 @@ namespace lt {
 
 // ---- per-slot addresses in the context's buffers ------------------------------------------------------
 inline uint8_t* slot_frame(const lt_ctx* c, int s) { return c->d_frames + (size_t)s * c->frame_bytes; }
+inline uint8_t* slot_yuv(const lt_ctx* c, int s) { return c->d_yuv + (size_t)s * c->yuv_stride; }
+inline YuvCoef yuv_coef_of(const lt_ctx* c) { return YuvCoef{c->yuv_coef[0], c->yuv_coef[1], c->yuv_coef[2], c->yuv_coef[3], c->yuv_coef[4]}; }
 inline uint8_t* slot_mask(const lt_ctx* c, int s) { return c->d_plane[P_MASK] + (size_t)s * c->plane_bytes; }
 // the opened bit plane of slot s as the searches take it; use_bits = false: none (they read slot_mask)
 inline MaskBits slot_bits(const lt_ctx* c, int s, bool use_bits) {

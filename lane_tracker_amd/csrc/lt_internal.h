@@ -58,6 +58,18 @@ void launch_undistort_rows(hipStream_t s, const uint8_t* frames, size_t frame_st
 void launch_warp_split(hipStream_t s, const uint32_t* und, size_t und_px, int first_slot, const int16_t* wxy,
                        const uint16_t* wfrac, FrontEndGeom g, const uint16_t* gamma_tab, const uint16_t* cbrt_tab,
                        const int32_t* coeffs, uint8_t* planeR, uint8_t* planeB, size_t plane_stride, int n);
+// YUV 4:2:0 input (lt_set_input_format): the five 20-bit fixed-point coefficients of the conversion, each below 2^23 in
+// magnitude (checked where they enter), so that every product with a 9-bit sample is one 24-bit multiply
+struct YuvCoef {
+    int32_t cy, cvr, cvg, cug, cub;
+};
+// launch_undistort_rows reading the slots' 4:2:0 staging frames (layout 1 = NV12, 2 = I420; `yuv_stride` bytes per slot, a
+// multiple of 16, 16 bytes of padding behind the last slot) instead of their RGB camera frames: every tap converted, then the same blend
+void launch_undistort_rows_yuv(hipStream_t s, int layout, const uint8_t* yuv, size_t yuv_stride, YuvCoef k, const int16_t* uxy,
+                               const uint16_t* ufrac, FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n);
+// rows [r0, r1) of n 4:2:0 frames of h x w (h, w even) -> the same rows of n RGB frames
+void launch_yuv_rows_to_rgb(hipStream_t s, int layout, const uint8_t* yuv, size_t yuv_stride, YuvCoef k, uint8_t* rgb,
+                            size_t rgb_stride, int h, int w, int r0, int r1, int n);
 void launch_split_bev(hipStream_t s, const uint8_t* bev, size_t bev_stride, int npix, const uint16_t* gamma_tab,
                       const uint16_t* cbrt_tab, const int32_t* coeffs, uint8_t* planeR, uint8_t* planeB,
                       size_t plane_stride, int n);

@@ -53,20 +53,25 @@ class LaneTrackerGroup:
     `LaneTracker`; groups on different threads share nothing."""
 
     def __init__(self, k, img_size, warped_size, cam_matrix, dist_coeffs, warp_matrices, mpp_conversion, n_fail=8, n_reset=4,
-                 n_average=2, print_frame_count=False, device=0):
+                 n_average=2, print_frame_count=False, device=0, *, pixel_format='rgb', yuv_matrix='bt601'):
         k = int(k)
         if k < 1:
             raise ValueError("a group needs at least one stream")
         self.k = k
         self.img_size, self.warped_size = img_size, warped_size
+        self.pixel_format, self.yuv_matrix = pixel_format, yuv_matrix
+        self._frame_shape = _native.frame_shape(img_size, pixel_format)
         self._ctx = _native.Context(img_size, warped_size, cam_matrix, dist_coeffs, warp_matrices[0], device=device, capacity=4 * k)
         self._tick = 0
         self.trackers = []
         try:
+            if pixel_format != 'rgb':        # every stream of a group is a camera of the same kind
+                self._ctx.set_input_format(pixel_format, yuv_matrix)
             for _ in range(k):
                 self.trackers.append(_GroupMember(self, img_size, warped_size, cam_matrix, dist_coeffs, warp_matrices, mpp_conversion,
                                                   n_fail=n_fail, n_reset=n_reset, n_average=n_average,
-                                                  print_frame_count=print_frame_count, device=device))
+                                                  print_frame_count=print_frame_count, device=device,
+                                                  pixel_format=pixel_format, yuv_matrix=yuv_matrix))
         except BaseException:
             self.close()
             raise
@@ -138,7 +143,7 @@ class LaneTrackerGroup:
         outs = [None] * self.k
         if not active:
             return outs
-        shape = (self._ctx.img_h, self._ctx.img_w, 3)
+        shape = self._frame_shape
         imgs = [np.ascontiguousarray(frames[i], np.uint8) for i in active]
         for img in imgs:
             if img.shape != shape:

@@ -64,7 +64,13 @@ class LaneTracker(StreamPipeline):
     """
 
     def __init__(self, img_size, warped_size, cam_matrix, dist_coeffs, warp_matrices, mpp_conversion,
-                 n_fail=8, n_reset=4, n_average=2, print_frame_count=False, device=0):
+                 n_fail=8, n_reset=4, n_average=2, print_frame_count=False, device=0, *, pixel_format='rgb', yuv_matrix='bt601'):
+        # the camera's pixel format: 'rgb' frames (H, W, 3), or YUV 4:2:0 as cameras and decoders hand it out -- 'nv12' / 'i420'
+        # frames (H * 3 // 2, W), converted on the device with `yuv_matrix` ('bt601', 'bt709'); everything that comes back is RGB
+        self.pixel_format, self.yuv_matrix = pixel_format, yuv_matrix
+        self._frame_shape = _native.frame_shape(img_size, pixel_format)      # (ValueError: unknown format, odd 4:2:0 size)
+        if pixel_format != 'rgb':
+            _native.yuv_coeffs(yuv_matrix)
         self.img_size = img_size
         self.warped_size = warped_size
         self.cam_matrix = cam_matrix
@@ -129,7 +135,24 @@ class LaneTracker(StreamPipeline):
     _owns_context = True        # False: the context is someone else's (a LaneTrackerGroup member) and close() leaves it open
 
     def _make_context(self, device):
-        return _native.Context(self.img_size, self.warped_size, self.cam_matrix, self.dist_coeffs, self.M, device=device, capacity=2)
+        ctx = _native.Context(self.img_size, self.warped_size, self.cam_matrix, self.dist_coeffs, self.M, device=device, capacity=2)
+        if self.pixel_format != 'rgb':
+            try:
+                ctx.set_input_format(self.pixel_format, self.yuv_matrix)
+            except BaseException:
+                ctx.close()
+                raise
+        return ctx
+
+    def _check_frame(self, img, window=False):
+        """A 4:2:0 tracker takes frames of its own shape only (nothing is uploaded before this has been looked at); an RGB tracker
+        takes what it always took."""
+        if self.pixel_format == 'rgb':
+            return
+        shape = getattr(img, "shape", None)
+        want = self._frame_shape
+        if shape is None or tuple(shape[1:] if window else shape) != want or (window and len(shape) != 3):
+            raise ValueError("a %r tracker takes frames of shape %s%r, got %r" % (self.pixel_format, "(n,) + " if window else "", want, shape))
 
     # ------------------------------------------------------------------------------------------
     def get_success_ratio(self):
@@ -199,6 +222,9 @@ class LaneTracker(StreamPipeline):
         f = self._fit                        # the fit of the last search that found pixels (fit_poly() hands it out)
         st["last_search_fit"] = None if f is None else [arr(f[2]), arr(f[3])]
         st["outage_group"] = int(self._outage_group)
+        if self.pixel_format != 'rgb':       # (an RGB tracker's state is what it always was; a state without these keys means RGB)
+            st["pixel_format"] = self.pixel_format
+            st["yuv_matrix"] = self.yuv_matrix if isinstance(self.yuv_matrix, str) else [int(v) for v in self.yuv_matrix]
         st["avg_partial"] = None             # the `partial` the plot points of the averages (left_avg_x, ...) were formed with
         if self._avg_packed is not None:
             for (partial, _), b in self.__dict__.get("_packed", {}).items():
@@ -218,6 +244,11 @@ class LaneTracker(StreamPipeline):
                 raise ValueError("state was taken with %s=%r, this tracker has %r" % (k, state[k], getattr(self, k)))
         if list(state["img_size"]) != [int(v) for v in self.img_size] or list(state["warped_size"]) != [int(v) for v in self.warped_size]:
             raise ValueError("state was taken from a tracker of another geometry")
+        theirs = (state.get("pixel_format", "rgb"), state.get("yuv_matrix", "bt601") if state.get("pixel_format", "rgb") != "rgb" else None)
+        mine = (self.pixel_format, (self.yuv_matrix if isinstance(self.yuv_matrix, str) else [int(v) for v in self.yuv_matrix])
+                if self.pixel_format != "rgb" else None)
+        if theirs != mine:
+            raise ValueError("state was taken from a %r tracker (matrix %r), this one takes %r (%r)" % (theirs + mine))
         self._all_copies_done()
         self._pending = self._pending_cent = None
         for k in self._STATE_SCALARS:
@@ -1133,6 +1164,7 @@ class LaneTracker(StreamPipeline):
         # nothing (upstream keeps the old lists in that case).
         if self._in_stream:
             raise RuntimeError("process() inside an active process_stream() would overwrite its frames")
+        self._check_frame(img)
         self._slot ^= 1
         try:
             return self._step(img, first_try, n_tries, diagnostics, slot=self._slot, have_mask=False, lazy=True, annotate=True,

@@ -581,9 +581,13 @@ class StreamPipeline:
                      _native.search_params(bandwidth=q[17], ignore_bottom=q[16], partial=q[18]), mode)
         return time.perf_counter() - t0
 
-    @staticmethod
-    def _as_window(frames):
+    def _as_window(self, frames):
         frames = np.ascontiguousarray(frames, np.uint8)
+        if self.pixel_format != 'rgb':
+            if self._annotate_inplace:
+                raise ValueError("annotate='inplace' draws into RGB frames: a %r tracker has none on the host" % (self.pixel_format,))
+            self._check_frame(frames, window=True)
+            return frames
         if frames.ndim != 4:
             raise ValueError("expected frames of shape (n, H, W, 3)")
         return frames

@@ -85,3 +85,12 @@ def create_split_view(target_size, images, positions, sizes, captions=[]):
             img = img[:, :, None]
         canvas[y:min(y + h, y_max), x:min(x + w, x_max), :] = img[:min(h, y_max - y), :min(w, x_max - x)]
     return canvas
+
+
+def yuv_to_rgb(frame, layout='nv12', matrix='bt601'):
+    """A YUV 4:2:0 frame as OpenCV holds it -- a u8 array (H * 3 // 2, W): the Y plane, then interleaved U,V rows ('nv12') or the
+    U plane and the V plane ('i420') -- to RGB (H, W, 3), on the device: `cv2.cvtColor(frame, cv2.COLOR_YUV2RGB_NV12)` /
+    `_I420` bit for bit with matrix='bt601' (OpenCV's constants, video range); 'bt709' or five integers {CY, CVR, CVG, CUG, CUB}
+    (20-bit fixed point) for another matrix.  What a `LaneTracker(..., pixel_format=layout, yuv_matrix=matrix)` sees of the frame."""
+    from .lane_tracker import _context_for_module_functions
+    return _context_for_module_functions().yuv_to_rgb(frame, layout, matrix)

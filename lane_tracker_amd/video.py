@@ -7,7 +7,10 @@ frames out.  Supported on both sides:
 
   * a directory of images (PNG/JPEG/BMP/PPM, sorted by name; Pillow),
   * a `.npy` array of shape (n, H, W, 3) (memory-mapped, so a long clip never has to fit in RAM),
-  * a headerless raw RGB24 file (`.rgb` / `.raw`; what `ffmpeg -pix_fmt rgb24 -f rawvideo` writes and reads).
+  * a headerless raw RGB24 file (`.rgb` / `.raw`; what `ffmpeg -pix_fmt rgb24 -f rawvideo` writes and reads),
+  * on the input side, a headerless raw YUV 4:2:0 file as cameras and decoders produce it: `.nv12`, or `.i420` / `.yuv` (I420;
+    `ffmpeg -pix_fmt nv12 | yuv420p -f rawvideo`).  Its frames are (H * 3 // 2, W) arrays for a tracker built with the same
+    `pixel_format`, which converts them on the device; what comes out, and every sink, is RGB.
 
 `process_frames()` feeds the tracker in windows through `LaneTracker.process_stream` (the stream pipeline:
 masks of the whole window batched ahead on the GPU, state machine trailing), which gives exactly the
@@ -33,6 +36,12 @@ def _is_raw(path):
     return str(path).lower().endswith((".rgb", ".raw"))
 
 
+def _yuv_layout(path):
+    """'nv12' / 'i420' for a raw 4:2:0 file name, else None."""
+    p = str(path).lower()
+    return "nv12" if p.endswith(".nv12") else "i420" if p.endswith((".i420", ".yuv")) else None
+
+
 def resolve_clip_path(path, must_exist=True):
     """A video file name as process_video.py spells it ('clip.mp4') -> the frame sequence standing in for
     it: 'clip.mp4' itself if it is a directory, else 'clip/' , 'clip.npy' or 'clip.rgb' next to it.  For
@@ -51,12 +60,16 @@ def resolve_clip_path(path, must_exist=True):
 
 
 class FrameSource:
-    """Ordered RGB u8 frames.  `size` = (width, height) is required for raw files only."""
+    """Ordered u8 frames: RGB (n, H, W, 3), or -- `pixel_format` 'nv12' / 'i420', raw 4:2:0 files -- (n, H * 3 // 2, W).
+    `size` = (width, height) is required for raw files only."""
+
+    pixel_format = "rgb"
 
     def __init__(self, path, size=None):
         self.path = str(path)
         self._files = None
         self._array = None
+        self._tail = None                # shape of one frame
         if os.path.isdir(self.path):
             self._files = sorted(os.path.join(self.path, f) for f in os.listdir(self.path)
                                  if f.lower().endswith(_IMAGE_EXT))
@@ -81,8 +94,25 @@ class FrameSource:
             self._n = nbytes // fb
             self._array = np.memmap(self.path, np.uint8, "r", shape=(self._n, self.height, self.width, 3)) if self._n \
                 else np.zeros((0, self.height, self.width, 3), np.uint8)
+        elif _yuv_layout(self.path):
+            if size is None:
+                raise ValueError("raw 4:2:0 input needs size=(width, height)")
+            self.pixel_format = _yuv_layout(self.path)
+            self.width, self.height = int(size[0]), int(size[1])
+            if self.width % 2 or self.height % 2 or self.width < 2 or self.height < 2:
+                raise ValueError(f"4:2:0 frames need an even width and height, got {self.width}x{self.height}")
+            self._tail = (self.height * 3 // 2, self.width)
+            fb = self.width * self.height * 3 // 2
+            nbytes = os.path.getsize(self.path)
+            if nbytes % fb:
+                raise ValueError(f"{self.path}: {nbytes} bytes is not a whole number of {self.width}x{self.height} 4:2:0 frames")
+            self._n = nbytes // fb
+            self._array = np.memmap(self.path, np.uint8, "r", shape=(self._n,) + self._tail) if self._n \
+                else np.zeros((0,) + self._tail, np.uint8)
         else:
-            raise ValueError(f"unsupported frame source {self.path!r} (directory of images, .npy, .rgb/.raw)")
+            raise ValueError(f"unsupported frame source {self.path!r} (directory of images, .npy, .rgb/.raw, .nv12, .i420/.yuv)")
+        if self._tail is None:
+            self._tail = (self.height, self.width, 3)
         if size is not None and (self.width, self.height) != (int(size[0]), int(size[1])):
             raise ValueError(f"frames are {self.width}x{self.height}, expected {size[0]}x{size[1]}")
 
@@ -110,9 +140,9 @@ class FrameSource:
         return (self.width, self.height)
 
     def read(self, start, stop):
-        """Frames [start, stop) as one contiguous (n, H, W, 3) array."""
+        """Frames [start, stop) as one contiguous array (n, H, W, 3) -- 4:2:0: (n, H * 3 // 2, W)."""
         start, stop = max(0, start), min(self._n, stop)
-        out = self._buffer((max(stop - start, 0), self.height, self.width, 3))
+        out = self._buffer((max(stop - start, 0),) + self._tail)
         if self._files is None:
             out[...] = self._array[start:stop]
             return out
@@ -182,6 +212,9 @@ def process_frames(tracker, source, sink=None, window=64, **process_kwargs):
     annotated frames to `sink` if there is one.  Returns (frames, seconds)."""
     t0 = time.perf_counter()
     n = len(source)
+    want, have = getattr(source, "pixel_format", "rgb"), getattr(tracker, "pixel_format", "rgb")
+    if want != have:
+        raise ValueError("the source delivers %r frames, the tracker was built with pixel_format=%r" % (want, have))
     windows = (source.read(start, start + window) for start in range(0, n, window))
     # process_stream: the uploads and masks of window k+1 run while the searches of window k drain
     for out in tracker.process_stream(windows, annotate=sink is not None, **process_kwargs):
@@ -202,6 +235,7 @@ class VideoFileClip:
         self._source = _source if _source is not None else FrameSource(resolve_clip_path(filename), size)
         self._fn = _fn
         self.size = self._source.size
+        self.pixel_format = self._source.pixel_format     # what a tracker for this clip is built with
 
     def fl_image(self, image_func):
         return VideoFileClip(self.filename, fps=self.fps, _fn=image_func, _source=self._source)
@@ -231,12 +265,15 @@ def _parse_size(text):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Lane tracking over a frame sequence (process_video.py without moviepy)")
-    ap.add_argument("input", help="directory of images, .npy (n,H,W,3) or raw .rgb")
+    ap.add_argument("input", help="directory of images, .npy (n,H,W,3), raw .rgb, or raw 4:2:0 (.nv12, .i420 / .yuv)")
     ap.add_argument("output", help="directory (PNG), .npy or raw .rgb; '-' to discard the frames")
     ap.add_argument("--cam", default="cam_calib.p", help="camera calibration (.p pickle or .npz)")
     ap.add_argument("--warp", default="warp_params.p", help="warp parameters (.p pickle or .npz)")
     ap.add_argument("--size", type=_parse_size, default=None, help="WxH of raw input frames")
     ap.add_argument("--window", type=int, default=64, help="frames per GPU batch")
+    ap.add_argument("--pixel-format", choices=("rgb", "nv12", "i420"), default=None,
+                    help="pixel format of the input frames (default: by the input's name); must match a raw input's extension")
+    ap.add_argument("--yuv-matrix", choices=("bt601", "bt709"), default="bt601", help="conversion matrix of 4:2:0 input")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--frame-count", action="store_true", help="print the frame number onto each image")
     ap.add_argument("--settings", choices=("default", "demo1", "demo2", "demo3"), default="default",
@@ -247,9 +284,11 @@ def main(argv=None):
     cam_matrix, dist_coeffs = load_camera_calib(a.cam)
     M, Minv, image_wh, warped_wh, mppv, mpph = load_warp_params(a.warp)
     src = FrameSource(a.input, a.size or image_wh)
+    if a.pixel_format is not None and a.pixel_format != src.pixel_format:
+        ap.error("--pixel-format %s, but %s holds %s frames" % (a.pixel_format, a.input, src.pixel_format))
     lt = LaneTracker(img_size=image_wh, warped_size=warped_wh, cam_matrix=cam_matrix, dist_coeffs=dist_coeffs,
                      warp_matrices=(M, Minv), mpp_conversion=(mppv, mpph), n_fail=8, n_reset=4, n_average=2,
-                     print_frame_count=a.frame_count, device=a.device)
+                     print_frame_count=a.frame_count, device=a.device, pixel_format=src.pixel_format, yuv_matrix=a.yuv_matrix)
     try:
         sink = None if a.output == "-" else FrameSink(a.output, src.size, n=len(src))
         kw = {}
