@@ -50,7 +50,9 @@ extern "C" {
  *    plot points, radius and eccentricity of a valid first try in one host call).  Later additions, still 5:
  *    lt_search_item + lt_search_fit_list (the searches of frames of unrelated streams in one launch), lt_upload_frame_rows_list +
  *    lt_upload_frame_rest_list (the uploads of frames that lie in separate host arrays); lt_set_input_format + lt_get_input_format +
- *    lt_yuv_to_rgb (camera frames in YUV 4:2:0, NV12 or I420, converted on the device).  Nothing removed or changed. */
+ *    lt_yuv_to_rgb (camera frames in YUV 4:2:0, NV12 or I420, converted on the device); lt_device_surface + lt_attach_device_frames +
+ *    lt_device_frames_rest (camera frames that already lie in device memory, read where they lie), lt_device_alloc / _free /
+ *    _write / _read (device blocks for callers without a HIP binding of their own), lt_device_stream_wait.  Nothing removed or changed. */
 #define LT_ABI_VERSION 5
 
 typedef enum lt_status {
@@ -220,6 +222,50 @@ int  lt_upload_frame_rest_rows(lt_ctx* ctx, const uint8_t* frames_rgb, int first
  * call returns. */
 int  lt_upload_frame_rows_list(lt_ctx* ctx, const uint8_t* const* frames_rgb, int first_slot, int n);
 int  lt_upload_frame_rest_list(lt_ctx* ctx, const uint8_t* const* frames_rgb, int first_slot, int n);
+/* ---- camera frames that are already in device memory --------------------------------------------------------------------------
+ * A decoder or a capture pipeline hands its surfaces out in device memory, usually with a row pitch above the width and the
+ * chroma plane somewhere else.  Such frames are not copied: the undistortion -- the only kernel that reads camera pixels on the
+ * way to a lane record -- fetches its taps from the surfaces themselves.  One lt_device_surface per frame, in the layout of the
+ * context's input format: plane[0] the RGB rows (3 bytes a pixel) or the Y plane, `pitch` bytes from row to row; NV12: plane[1]
+ * the rows of (U, V) pairs; I420: plane[1] the U and plane[2] the V plane; `chroma_pitch` bytes between chroma rows.  Any byte
+ * alignment of pointers and pitches is taken (a column crop of an RGB frame starts at 3 * x0).  Results are bit for bit those of
+ * the same bytes uploaded from the host.
+ *
+ * lt_attach_device_frames: from now on the front end of slots [first_slot, first_slot + n) reads surfaces[0 .. n).  Ordered like
+ * lt_upload_frame_rows_enqueue -- behind everything launched over these slots so far, ahead of whatever is launched over them
+ * next -- and with its contract for the caller's memory: the surfaces hold their final content when the call is made (wait for
+ * the producer first) and stay valid and unchanged until a call that waits for work launched over these slots afterwards has
+ * returned (lt_download_records of a search, lt_sync).  The list itself is read before the call returns.  Any lt_upload_* of
+ * camera rows into a slot detaches it; lt_mask_run takes ranges that mix attached and plain slots, lt_mask_rerun reuses the
+ * front end of an attached slot like any other.
+ * Every plane is checked on the host BEFORE anything is launched: device memory of the context's device, known to the HIP
+ * runtime this library is linked against, its whole extent -- pitch * (rows - 1) + row bytes -- inside one allocation; pitches at
+ * least a row wide and below 2^23.  Anything else is LT_ERR_INVALID with a message, nothing is launched and the context is as it
+ * was.  (A pointer of another runtime in the same process -- a framework that bundles its own copy of the HIP runtime -- is
+ * unknown to this one and refused.)  The verdict is not remembered: every call checks again.
+ *
+ * lt_device_frames_rest: the counterpart of lt_upload_frame_rest / _rest_rows for attached slots -- the rows a SHOWN frame needs
+ * (rows4 = {a0, a1, b0, b1}: those two runs, whole; NULL: the whole frame) are brought from the surfaces into the slots' RGB
+ * camera frames on the device, converted where the context is 4:2:0, on the copy stream beside the mask chain; lt_overlay_run
+ * waits for it.  LT_ERR_STATE for a slot that is not attached.  A search-only caller never needs it: nothing is copied then. */
+typedef struct lt_device_surface {
+    const void* plane[3];
+    int32_t pitch;               /* bytes between rows of plane[0] */
+    int32_t chroma_pitch;        /* bytes between rows of plane[1] (and plane[2]); not read in an RGB context */
+} lt_device_surface;
+int  lt_attach_device_frames(lt_ctx* ctx, const lt_device_surface* surfaces, int first_slot, int n);
+int  lt_device_frames_rest(lt_ctx* ctx, int first_slot, int n, const int32_t* rows4);
+/* Device blocks out of the library's own cache (lt_device_cache_stats counts them as live), with plain synchronous copies
+ * from and to host memory: for callers that have no HIP binding of their own -- the Python package, tools, tests -- and want to
+ * hold frames on the device in the runtime the library lives in.  lt_device_write / lt_device_read refuse ranges that do not lie
+ * inside such a block; lt_device_free waits for the device first, as hipFree does. */
+int  lt_device_alloc(int device, size_t bytes, void** out);
+int  lt_device_free(void* block);
+int  lt_device_write(void* dst_device, const void* src_host, size_t bytes);
+int  lt_device_read(void* dst_host, const void* src_device, size_t bytes);
+/* The host waits for a producer's stream of this runtime before its frames are attached: 1 the legacy default stream, 2 the
+ * per-thread default stream (the numbers of __cuda_array_interface__), anything else a hipStream_t; 0 is LT_ERR_INVALID. */
+int  lt_device_stream_wait(int device, uintptr_t stream);
 /* masks: n * warp_h * warp_w bytes; lets the search stages run on caller-supplied binary images */
 int  lt_upload_masks(lt_ctx* ctx, const uint8_t* masks, int first_slot, int n);
 int  lt_download_masks(lt_ctx* ctx, int first_slot, int n, uint8_t* masks);

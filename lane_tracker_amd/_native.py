@@ -63,6 +63,15 @@ SEARCH_ITEM_DTYPE = np.dtype([("slot", "<i4"), ("mode", "<i4"), ("_pad", "<i4", 
 assert SEARCH_ITEM_DTYPE.itemsize == 64 and C.sizeof(SearchItem) == 64
 
 
+class DeviceSurface(C.Structure):
+    """lt_device_surface: one camera frame in device memory (plane pointers, luma / RGB pitch, chroma pitch)."""
+    _fields_ = [("plane", C.c_void_p * 3), ("pitch", C.c_int32), ("chroma_pitch", C.c_int32)]
+
+
+SURFACE_DTYPE = np.dtype([("plane", "<u8", 3), ("pitch", "<i4"), ("chroma_pitch", "<i4")])
+assert SURFACE_DTYPE.itemsize == 32 and C.sizeof(DeviceSurface) == 32
+
+
 class Info(C.Structure):
     _fields_ = [("abi_version", C.c_int32), ("device", C.c_int32), ("capacity", C.c_int32),
                 ("cu_count", C.c_int32), ("src_row0", C.c_int32), ("src_row1", C.c_int32),
@@ -198,6 +207,13 @@ _SIGNATURES = {
     "lt_set_input_format": (C.c_int, [_P, C.c_int, _P]),
     "lt_get_input_format": (C.c_int, [_P, C.POINTER(C.c_int), _P]),
     "lt_yuv_to_rgb": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "lt_attach_device_frames": (C.c_int, [_P, _P, C.c_int, C.c_int]),
+    "lt_device_frames_rest": (C.c_int, [_P, C.c_int, C.c_int, _P]),
+    "lt_device_alloc": (C.c_int, [C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]),
+    "lt_device_free": (C.c_int, [_P]),
+    "lt_device_write": (C.c_int, [_P, _P, C.c_size_t]),
+    "lt_device_read": (C.c_int, [_P, _P, C.c_size_t]),
+    "lt_device_stream_wait": (C.c_int, [C.c_int, C.c_size_t]),
 }
 
 # camera-frame formats (lt_input_layout) and the conversion matrices {CY, CVR, CVG, CUG, CUB} of include/lane_tracker_amd.h
@@ -723,6 +739,21 @@ class Context:
         else:
             _check(self.lib.lt_upload_frame_rest_rows(self._h, f.ctypes.data, first, f.shape[0], rows))
         return f
+
+    def attach_device_frames(self, frames, first=0):
+        """The front end of slots first, first + 1, ... reads `frames` (a device.DeviceFrames) where they lie in device memory
+        (lt_attach_device_frames); nothing is copied.  Returns `frames`: keep it -- and the memory it describes -- alive and
+        unchanged until a call that waits for work launched over these slots afterwards (download_record, sync)."""
+        frames.check_for((self.img_w, self.img_h), {3: "rgb"}.get(len(self._frame_tail)) or self.input_format()[0])
+        frames.wait_for_producer()
+        s = np.ascontiguousarray(frames.surfaces)
+        _check(self.lib.lt_attach_device_frames(self._h, s.ctypes.data, first, s.shape[0]))
+        return frames
+
+    def device_frames_rest(self, n, first=0, rows=None):
+        """The rows a shown frame needs, from the attached surfaces into the slots' RGB camera frames, on the device beside the mask
+        chain (lt_device_frames_rest); `rows`: the ADDRESS of four int32 {a0, a1, b0, b1}, or None for the whole frame."""
+        _check(self.lib.lt_device_frames_rest(self._h, first, int(n), rows))
 
     def _frame_list(self, frames):
         fs = [_u8(f) for f in frames]

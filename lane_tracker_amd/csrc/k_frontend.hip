@@ -337,6 +337,287 @@ __global__ __launch_bounds__(256) void k_yuv_rows_to_rgb_any(const uint8_t* __re
     }
 }
 
+// ---- frames that lie in the caller's device memory (lt_attach_device_frames) ---------------------------------------------------
+// The same two walks with the taps fetched from the caller's surfaces: entry first_slot + z of the surface table (device memory,
+// SurfEntry per slot) holds the plane pointers and pitches of frame z.  z is wave-uniform, so an entry arrives by scalar loads and
+// every plane gets a buffer resource of its own in SGPRs, based at ptr & ~3 -- the remainder goes into the windows' offsets, which
+// are split into an aligned load and a v_alignbyte_b32 anyway -- and covering exactly the plane's bytes, rounded up to the end of
+// the aligned dword that holds its last byte: pitch * (rows - 1) + row bytes.  A window that overruns the plane comes back as
+// zeros from the resource's range check (raw buffers are checked dword by dword) and those bytes are never used; nothing is read
+// outside the dwords the plane occupies, so a surface may end on the last byte of its allocation.  The entry of frame z + 2 is
+// requested while the windows of frame z + 1 are in flight and frame z is blended.
+constexpr int SURF_RSRC_RAW = 0x00027000;   // untyped 32-bit buffer, no swizzle
+struct SurfPlane { __amdgpu_buffer_rsrc_t rs; int rem; };
+__device__ __forceinline__ SurfPlane surf_plane(uint64_t ptr, int pitch, int rows, int row_bytes) {
+    const int rem = (int)(ptr & 3u);
+    return SurfPlane{__builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(ptr & ~(uint64_t)3), 0,
+                                                       (rem + __mul24(pitch, rows - 1) + row_bytes + 3) & ~3, SURF_RSRC_RAW), rem};
+}
+
+__global__ __launch_bounds__(256) void k_undistort_rows_surf(const SurfEntry* __restrict__ tab,
+                                                            const int16_t* __restrict__ uxy,
+                                                            const uint16_t* __restrict__ ufrac, FrontEndGeom g,
+                                                            uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb,
+                                                            int remap) {
+    const uint32_t per_z = gridDim.x * gridDim.y;
+    const uint32_t id = xcd_block((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x, per_z * gridDim.z, remap);
+    const uint32_t bz = id / per_z, by = (id - bz * per_z) / gridDim.x, bx = id - bz * per_z - by * gridDim.x;
+    const int x = bx * blockDim.x + threadIdx.x;
+    const int row = by;  // relative to g.r0
+    if (x >= g.img_w) return;
+    const int z0 = bz * fpb, z1 = min(z0 + fpb, n);
+    const size_t o = (size_t)row * g.img_w + x;
+    const int sx = uxy[o * 2], sy = uxy[o * 2 + 1];
+    const int f = ufrac[o], fx = f & 31, fy = f >> 5;
+    const bool y0 = sy >= 0 && sy < g.img_h, y1 = sy + 1 >= 0 && sy + 1 < g.img_h;
+    const bool x0 = sx >= 0 && sx < g.img_w, x1 = sx + 1 >= 0 && sx + 1 < g.img_w;
+    const int cy0 = min(max(sy, 0), g.img_h - 1), cy1 = min(max(sy + 1, 0), g.img_h - 1);
+    const int cxl = min(max(sx, 0), g.img_w - 2);          // leftmost column of the 6-byte window we fetch
+    const int cx3 = cxl * 3;
+    const int sh0 = 24 * (min(max(sx, 0), g.img_w - 1) - cxl), sh1 = 24 * (min(max(sx + 1, 0), g.img_w - 1) - cxl);
+    const uint32_t m00 = (y0 && x0) ? 255u : 0u, m01 = (y0 && x1) ? 255u : 0u;
+    const uint32_t m10 = (y1 && x0) ? 255u : 0u, m11 = (y1 && x1) ? 255u : 0u;
+    const uint32_t gx = 32u - (uint32_t)fx, gy = 32u - (uint32_t)fy;
+    const uint32_t w00 = (gx * gy) & 0x7ffu, w01 = ((uint32_t)fx * gy) & 0x7ffu, w10 = (gx * (uint32_t)fy) & 0x7ffu, w11 = ((uint32_t)fx * (uint32_t)fy) & 0x7ffu;
+    const int pair0 = (first_slot + z0) >> 1, pair1 = (first_slot + z1 - 1) >> 1, pair_b = (int)(und_px * 8);
+    const __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc(und + (size_t)pair0 * 2 * und_px, 0, (pair1 - pair0 + 1) * pair_b, SURF_RSRC_RAW);
+    typedef unsigned u32x3 __attribute__((ext_vector_type(3)));
+    const int row_bytes = g.img_w * 3;
+    // the 8 bytes at (row cy, column cxl) of the frame of entry e: pitch and remainder are the frame's, so the offset is too
+    auto window = [&](const SurfEntry& e, int cy) {
+        const SurfPlane p = surf_plane(e.plane[0], e.pitch, g.img_h, row_bytes);
+        const uint32_t off = (uint32_t)(__mul24(cy, e.pitch) + cx3 + p.rem);
+        const u32x3 d = __builtin_amdgcn_raw_buffer_load_b96(p.rs, (int)(off & ~3u), 0, 0);
+        const uint32_t lo = __builtin_amdgcn_alignbyte(d.y, d.x, off & 3u), hi = __builtin_amdgcn_alignbyte(d.z, d.y, off & 3u);
+        return (uint64_t)lo | ((uint64_t)hi << 32);
+    };
+    const SurfEntry* ent = tab + first_slot;
+    SurfEntry e1 = ent[z0];
+    uint64_t q0 = window(e1, cy0), q1 = window(e1, cy1);
+    e1 = ent[min(z0 + 1, z1 - 1)];
+    for (int z = z0; z < z1; ++z) {
+        // the next frame's taps are in flight while this one is blended, and the entry of the frame after it is on its way
+        const uint64_t n0 = window(e1, cy0), n1 = window(e1, cy1);
+        e1 = ent[min(z + 2, z1 - 1)];
+        const uint32_t a0 = (uint32_t)(q0 >> sh0), a1 = (uint32_t)(q0 >> sh1);
+        const uint32_t b0 = (uint32_t)(q1 >> sh0), b1 = (uint32_t)(q1 >> sh1);
+        uint32_t out = 0;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const uint32_t v00 = (a0 >> (8 * ch)) & m00, v01 = (a1 >> (8 * ch)) & m01;
+            const uint32_t v10 = (b0 >> (8 * ch)) & m10, v11 = (b1 >> (8 * ch)) & m11;
+            out |= ((v00 * w00 + v01 * w01 + v10 * w10 + v11 * w11 + 512u) >> 10) << (8 * ch);   // k_undistort_rows' blend
+        }
+        const int slot = first_slot + z;   // wave-uniform: pair and parity go into the scalar offset of the store
+        __builtin_amdgcn_raw_buffer_store_b32(out, urs, (int)o * 8, __builtin_amdgcn_readfirstlane(((slot >> 1) - pair0) * pair_b + (slot & 1) * 4), 0);
+        q0 = n0;
+        q1 = n1;
+    }
+}
+
+template <int LAYOUT>
+__global__ __launch_bounds__(256) void k_undistort_rows_yuv_surf(const SurfEntry* __restrict__ tab, YuvCoef k,
+                                                                const int16_t* __restrict__ uxy,
+                                                                const uint16_t* __restrict__ ufrac, FrontEndGeom g,
+                                                                uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb,
+                                                                int remap) {
+    const uint32_t per_z = gridDim.x * gridDim.y;
+    const uint32_t id = xcd_block((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x, per_z * gridDim.z, remap);
+    const uint32_t bz = id / per_z, by = (id - bz * per_z) / gridDim.x, bx = id - bz * per_z - by * gridDim.x;
+    const int x = bx * blockDim.x + threadIdx.x;
+    const int row = by;  // relative to g.r0
+    if (x >= g.img_w) return;
+    const int z0 = bz * fpb, z1 = min(z0 + fpb, n);
+    const size_t o = (size_t)row * g.img_w + x;
+    const int sx = uxy[o * 2], sy = uxy[o * 2 + 1];
+    const int f = ufrac[o], fx = f & 31, fy = f >> 5;
+    const bool y0 = sy >= 0 && sy < g.img_h, y1 = sy + 1 >= 0 && sy + 1 < g.img_h;
+    const bool x0 = sx >= 0 && sx < g.img_w, x1 = sx + 1 >= 0 && sx + 1 < g.img_w;
+    const int cy0 = min(max(sy, 0), g.img_h - 1), cy1 = min(max(sy + 1, 0), g.img_h - 1);
+    const int cxl = min(max(sx, 0), g.img_w - 2);          // leftmost column of the windows (the width is even, so >= 2)
+    const int cx0 = min(max(sx, 0), g.img_w - 1), cx1 = min(max(sx + 1, 0), g.img_w - 1);   // both in {cxl, cxl + 1}
+    const int cb = cxl & ~1;                               // first column of the chroma pair under cxl; cxl + 1 is under cb or cb + 2
+    const int ysh0 = 8 * (cx0 - cxl), ysh1 = 8 * (cx1 - cxl);                  // the taps' Y samples inside the Y window
+    const int cs0 = (cx0 - cb) >> 1, cs1 = (cx1 - cb) >> 1;                    // the taps' pair (0 / 1) inside the chroma window
+    const int ccol = LAYOUT == 1 ? cb : cb >> 1;           // byte column of the chroma window in its plane
+    const uint32_t m00 = (y0 && x0) ? 255u : 0u, m01 = (y0 && x1) ? 255u : 0u;
+    const uint32_t m10 = (y1 && x0) ? 255u : 0u, m11 = (y1 && x1) ? 255u : 0u;
+    const uint32_t gx = 32u - (uint32_t)fx, gy = 32u - (uint32_t)fy;
+    const uint32_t w00 = (gx * gy) & 0x7ffu, w01 = ((uint32_t)fx * gy) & 0x7ffu, w10 = (gx * (uint32_t)fy) & 0x7ffu, w11 = ((uint32_t)fx * (uint32_t)fy) & 0x7ffu;
+    const int pair0 = (first_slot + z0) >> 1, pair1 = (first_slot + z1 - 1) >> 1, pair_b = (int)(und_px * 8);
+    const __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc(und + (size_t)pair0 * 2 * und_px, 0, (pair1 - pair0 + 1) * pair_b, SURF_RSRC_RAW);
+    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+    auto window = [&](const SurfPlane& p, int off) {       // the 4 bytes at `off` of the plane (+ its remainder)
+        const uint32_t a = (uint32_t)(off + p.rem);
+        const u32x2 d = __builtin_amdgcn_raw_buffer_load_b64(p.rs, (int)(a & ~3u), 0, 0);
+        return __builtin_amdgcn_alignbyte(d.y, d.x, a & 3u);
+    };
+    struct Taps { uint32_t ya, yb, ca, cb, va, vb; };      // Y and chroma windows of the upper (a) and lower (b) tap row; va / vb: I420's V
+    const int crows = g.img_h >> 1, cbytes = LAYOUT == 1 ? g.img_w : g.img_w >> 1;
+    auto fetch = [&](const SurfEntry& e) {
+        Taps t;
+        const SurfPlane py = surf_plane(e.plane[0], e.pitch, g.img_h, g.img_w);
+        const SurfPlane pc = surf_plane(e.plane[1], e.cpitch, crows, cbytes);
+        const int oc0 = __mul24(cy0 >> 1, e.cpitch) + ccol, oc1 = __mul24(cy1 >> 1, e.cpitch) + ccol;
+        t.ya = window(py, __mul24(cy0, e.pitch) + cxl);
+        t.yb = window(py, __mul24(cy1, e.pitch) + cxl);
+        t.ca = window(pc, oc0);
+        t.cb = window(pc, oc1);
+        if constexpr (LAYOUT == 2) {
+            const SurfPlane pv = surf_plane(e.plane[2], e.cpitch, crows, cbytes);
+            t.va = window(pv, oc0);
+            t.vb = window(pv, oc1);
+        } else {
+            t.va = t.vb = 0;
+        }
+        return t;
+    };
+    auto tap = [&](uint32_t yw, uint32_t cw, uint32_t vw, int ysh, int cs) {
+        int u, v;
+        if constexpr (LAYOUT == 1) {
+            u = (int)((cw >> (16 * cs)) & 255u);
+            v = (int)((cw >> (16 * cs + 8)) & 255u);
+        } else {
+            u = (int)((cw >> (8 * cs)) & 255u);
+            v = (int)((vw >> (8 * cs)) & 255u);
+        }
+        return yuv_pixel((int)((yw >> ysh) & 255u), yuv_chroma(u, v, k), k);
+    };
+    const SurfEntry* ent = tab + first_slot;
+    SurfEntry e1 = ent[z0];
+    Taps q = fetch(e1);
+    e1 = ent[min(z0 + 1, z1 - 1)];
+    for (int z = z0; z < z1; ++z) {
+        // the next frame's taps are in flight while this one is converted and blended, and the entry of the frame after it is on its way
+        const Taps nq = fetch(e1);
+        e1 = ent[min(z + 2, z1 - 1)];
+        const uint32_t a0 = tap(q.ya, q.ca, q.va, ysh0, cs0), a1 = tap(q.ya, q.ca, q.va, ysh1, cs1);
+        const uint32_t b0 = tap(q.yb, q.cb, q.vb, ysh0, cs0), b1 = tap(q.yb, q.cb, q.vb, ysh1, cs1);
+        uint32_t out = 0;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch) {
+            const uint32_t v00 = (a0 >> (8 * ch)) & m00, v01 = (a1 >> (8 * ch)) & m01;
+            const uint32_t v10 = (b0 >> (8 * ch)) & m10, v11 = (b1 >> (8 * ch)) & m11;
+            out |= ((v00 * w00 + v01 * w01 + v10 * w10 + v11 * w11 + 512u) >> 10) << (8 * ch);   // k_undistort_rows' blend
+        }
+        const int slot = first_slot + z;   // wave-uniform: pair and parity go into the scalar offset of the store
+        __builtin_amdgcn_raw_buffer_store_b32(out, urs, (int)o * 8, __builtin_amdgcn_readfirstlane(((slot >> 1) - pair0) * pair_b + (slot & 1) * 4), 0);
+        q = nq;
+    }
+}
+
+// Entries into the surface table, as a kernel argument (no host memory has to outlive the call): entry i -> tab[first + i].
+__global__ __launch_bounds__(64) void k_write_surf_entries(SurfEntry* __restrict__ tab, int first, int n, SurfChunk ch) {
+    const int i = (int)threadIdx.x;
+    if (i >= n) return;
+    const SurfEntry e = ch.e[i];
+    tab[first + i] = e;
+}
+
+// Rows [r0, r1) of 4:2:0 surfaces -> the same rows of the slots' RGB camera frames: k_yuv_rows_to_rgb with plane pointers and pitches.
+// The surfaces of the launch travel as a kernel argument (frame blockIdx.z is entry blockIdx.z of the chunk).
+template <int LAYOUT>
+__global__ __launch_bounds__(256) void k_surf_rows_to_rgb(SurfChunk ch, YuvCoef k, uint8_t* __restrict__ rgb, size_t rgb_stride, int w, int r0, int r1) {
+    const int x0 = (int)(blockIdx.x * blockDim.x + threadIdx.x) * 16;
+    if (x0 >= w) return;
+    const int cr = (r0 >> 1) + (int)blockIdx.y;            // chroma row
+    const SurfEntry& e = ch.e[blockIdx.z];
+    const uint8_t* py = reinterpret_cast<const uint8_t*>(e.plane[0]);
+    const uint8_t* pu = reinterpret_cast<const uint8_t*>(e.plane[1]);
+    uint8_t* dst = rgb + (size_t)blockIdx.z * rgb_stride;
+    uint32_t uv[4];                                        // NV12: 8 (U, V) pairs; I420: uv[0..1] 8 U, uv[2..3] 8 V
+    if constexpr (LAYOUT == 1) {
+        const uint4 c = *reinterpret_cast<const uint4*>(pu + (size_t)cr * e.cpitch + x0);
+        uv[0] = c.x; uv[1] = c.y; uv[2] = c.z; uv[3] = c.w;
+    } else {
+        const uint8_t* pv = reinterpret_cast<const uint8_t*>(e.plane[2]);
+        const size_t co = (size_t)cr * e.cpitch + (x0 >> 1);
+        const uint2 cu = *reinterpret_cast<const uint2*>(pu + co), cv = *reinterpret_cast<const uint2*>(pv + co);
+        uv[0] = cu.x; uv[1] = cu.y; uv[2] = cv.x; uv[3] = cv.y;
+    }
+    Chroma c[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        int u, v;
+        if constexpr (LAYOUT == 1) {
+            u = (int)((uv[i >> 1] >> (16 * (i & 1))) & 255u);
+            v = (int)((uv[i >> 1] >> (16 * (i & 1) + 8)) & 255u);
+        } else {
+            u = (int)((uv[i >> 2] >> (8 * (i & 3))) & 255u);
+            v = (int)((uv[2 + (i >> 2)] >> (8 * (i & 3))) & 255u);
+        }
+        c[i] = yuv_chroma(u, v, k);
+    }
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy) {
+        const int y = 2 * cr + dy;
+        if (y < r0 || y >= r1) continue;
+        const uint4 yq = *reinterpret_cast<const uint4*>(py + (size_t)y * e.pitch + x0);
+        const uint32_t yw[4] = {yq.x, yq.y, yq.z, yq.w};
+        uint32_t d[12];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {                      // four pixels (two chroma pairs) -> three dwords
+            uint32_t p[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) p[i] = yuv_pixel((int)((yw[j] >> (8 * i)) & 255u), c[2 * j + (i >> 1)], k);
+            d[3 * j] = p[0] | (p[1] << 24);
+            d[3 * j + 1] = (p[1] >> 8) | (p[2] << 16);
+            d[3 * j + 2] = (p[2] >> 16) | (p[3] << 8);
+        }
+        uint4* o = reinterpret_cast<uint4*>(dst + ((size_t)y * w + x0) * 3);
+        o[0] = make_uint4(d[0], d[1], d[2], d[3]);
+        o[1] = make_uint4(d[4], d[5], d[6], d[7]);
+        o[2] = make_uint4(d[8], d[9], d[10], d[11]);
+    }
+}
+
+// the same for any even width, any pitch and any alignment: one thread per 2 x 2 block, byte accesses
+template <int LAYOUT>
+__global__ __launch_bounds__(256) void k_surf_rows_to_rgb_any(SurfChunk ch, YuvCoef k, uint8_t* __restrict__ rgb, size_t rgb_stride, int w, int r0, int r1) {
+    const int bx = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (2 * bx >= w) return;
+    const int cr = (r0 >> 1) + (int)blockIdx.y;
+    const SurfEntry& e = ch.e[blockIdx.z];
+    const uint8_t* py = reinterpret_cast<const uint8_t*>(e.plane[0]);
+    const uint8_t* pu = reinterpret_cast<const uint8_t*>(e.plane[1]);
+    uint8_t* dst = rgb + (size_t)blockIdx.z * rgb_stride;
+    int u, v;
+    if constexpr (LAYOUT == 1) {
+        u = pu[(size_t)cr * e.cpitch + 2 * bx];
+        v = pu[(size_t)cr * e.cpitch + 2 * bx + 1];
+    } else {
+        u = pu[(size_t)cr * e.cpitch + bx];
+        v = reinterpret_cast<const uint8_t*>(e.plane[2])[(size_t)cr * e.cpitch + bx];
+    }
+    const Chroma c = yuv_chroma(u, v, k);
+    for (int dy = 0; dy < 2; ++dy) {
+        const int y = 2 * cr + dy;
+        if (y < r0 || y >= r1) continue;
+        for (int dx = 0; dx < 2; ++dx) {
+            const uint32_t p = yuv_pixel(py[(size_t)y * e.pitch + 2 * bx + dx], c, k);
+            const size_t o = (size_t)y * w + 2 * bx + dx;
+            dst[o * 3] = (uint8_t)p;
+            dst[o * 3 + 1] = (uint8_t)(p >> 8);
+            dst[o * 3 + 2] = (uint8_t)(p >> 16);
+        }
+    }
+}
+
+// Rows [r0, r1) of RGB surfaces -> the same rows of the slots' camera frames (row_bytes = 3 w, dense): a pitched row copy, one
+// thread per 16 bytes (WIDE: every base and pitch of the launch a multiple of 16) or per byte.
+template <bool WIDE>
+__global__ __launch_bounds__(256) void k_surf_copy_rows(SurfChunk ch, uint8_t* __restrict__ rgb, size_t rgb_stride, int row_bytes, int r0) {
+    constexpr int V = WIDE ? 16 : 1;
+    const int xb = (int)(blockIdx.x * blockDim.x + threadIdx.x) * V;
+    if (xb >= row_bytes) return;
+    const int y = r0 + (int)blockIdx.y;
+    const SurfEntry& e = ch.e[blockIdx.z];
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(e.plane[0]) + (size_t)y * e.pitch + xb;
+    uint8_t* dst = rgb + (size_t)blockIdx.z * rgb_stride + (size_t)y * row_bytes + xb;
+    if constexpr (WIDE) *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(src);
+    else *dst = *src;
+}
+
 struct LabLut {
     const uint16_t* gamma_tab;
     const uint16_t* cbrt_tab;
@@ -723,6 +1004,64 @@ void launch_yuv_rows_to_rgb(hipStream_t s, int layout, const uint8_t* yuv, size_
         dim3 grid((unsigned)((w / 2 + 255) / 256), crows, (unsigned)n);
         if (layout == 1) hipLaunchKernelGGL(k_yuv_rows_to_rgb_any<1>, grid, dim3(256), 0, s, yuv, yuv_stride, k, rgb, rgb_stride, h, w, r0, r1);
         else hipLaunchKernelGGL(k_yuv_rows_to_rgb_any<2>, grid, dim3(256), 0, s, yuv, yuv_stride, k, rgb, rgb_stride, h, w, r0, r1);
+    }
+}
+
+void launch_undistort_rows_surf(hipStream_t s, int layout, const SurfEntry* tab, YuvCoef k, const int16_t* uxy, const uint16_t* ufrac,
+                                FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n) {
+    if (n <= 0 || g.nrows <= 0) return;
+    const int fpb = frames_per_thread(n);
+    dim3 grid((g.img_w + 255) / 256, g.nrows, (n + fpb - 1) / fpb);
+    if (layout == 0)
+        hipLaunchKernelGGL(k_undistort_rows_surf, grid, dim3(256), 0, s, tab, uxy, ufrac, g, und, und_px, first_slot, n, fpb, xcd_remap());
+    else if (layout == 1)
+        hipLaunchKernelGGL(k_undistort_rows_yuv_surf<1>, grid, dim3(256), 0, s, tab, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, xcd_remap());
+    else
+        hipLaunchKernelGGL(k_undistort_rows_yuv_surf<2>, grid, dim3(256), 0, s, tab, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, xcd_remap());
+}
+
+void launch_write_surf_entries(hipStream_t s, SurfEntry* tab, int first, const SurfEntry* entries, int n) {
+    for (int i = 0; i < n; i += SurfChunk::N) {
+        const int m = std::min(n - i, (int)SurfChunk::N);
+        SurfChunk ch{};
+        std::copy(entries + i, entries + i + m, ch.e);
+        hipLaunchKernelGGL(k_write_surf_entries, dim3(1), dim3(64), 0, s, tab, first + i, m, ch);
+    }
+}
+
+void launch_surf_rows_to_rgb(hipStream_t s, int layout, const SurfEntry* entries, YuvCoef k, uint8_t* rgb, size_t rgb_stride, int h, int w,
+                             int r0, int r1, int n) {
+    (void)h;
+    if (n <= 0 || r1 <= r0) return;
+    for (int i = 0; i < n; i += SurfChunk::N) {
+        const int m = std::min(n - i, (int)SurfChunk::N);
+        SurfChunk ch{};
+        std::copy(entries + i, entries + i + m, ch.e);
+        uint8_t* dst = rgb + (size_t)i * rgb_stride;
+        size_t bits = rgb_stride | (size_t)(uintptr_t)dst;   // every base and pitch of the launch a multiple of 16?
+        for (int j = 0; j < m; ++j) {
+            bits |= (size_t)ch.e[j].plane[0] | (size_t)ch.e[j].pitch;
+            if (layout != 0) bits |= (size_t)ch.e[j].plane[1] | (size_t)ch.e[j].cpitch;
+            if (layout == 2) bits |= (size_t)ch.e[j].plane[2];
+        }
+        if (layout == 0) {
+            const int row_bytes = w * 3;
+            if ((bits & 15) == 0 && (row_bytes & 15) == 0)
+                hipLaunchKernelGGL(k_surf_copy_rows<true>, dim3((unsigned)((row_bytes / 16 + 255) / 256), (unsigned)(r1 - r0), (unsigned)m), dim3(256), 0, s, ch, dst, rgb_stride, row_bytes, r0);
+            else
+                hipLaunchKernelGGL(k_surf_copy_rows<false>, dim3((unsigned)((row_bytes + 255) / 256), (unsigned)(r1 - r0), (unsigned)m), dim3(256), 0, s, ch, dst, rgb_stride, row_bytes, r0);
+            continue;
+        }
+        const unsigned crows = (unsigned)(((r1 + 1) >> 1) - (r0 >> 1));
+        if ((w & 15) == 0 && (bits & 15) == 0) {
+            dim3 grid((unsigned)((w / 16 + 63) / 64), crows, (unsigned)m);
+            if (layout == 1) hipLaunchKernelGGL(k_surf_rows_to_rgb<1>, grid, dim3(64), 0, s, ch, k, dst, rgb_stride, w, r0, r1);
+            else hipLaunchKernelGGL(k_surf_rows_to_rgb<2>, grid, dim3(64), 0, s, ch, k, dst, rgb_stride, w, r0, r1);
+        } else {
+            dim3 grid((unsigned)((w / 2 + 255) / 256), crows, (unsigned)m);
+            if (layout == 1) hipLaunchKernelGGL(k_surf_rows_to_rgb_any<1>, grid, dim3(256), 0, s, ch, k, dst, rgb_stride, w, r0, r1);
+            else hipLaunchKernelGGL(k_surf_rows_to_rgb_any<2>, grid, dim3(256), 0, s, ch, k, dst, rgb_stride, w, r0, r1);
+        }
     }
 }
 

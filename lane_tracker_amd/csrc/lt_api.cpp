@@ -183,6 +183,9 @@ void free_slots(lt_ctx* c) {
     dev_free(c->d_frames);
     dev_free(c->d_yuv);
     dev_free(c->d_und);
+    dev_free(c->d_surf);
+    c->surf.clear();
+    c->attached.clear();
     dev_free(c->d_bev);
     for (auto& p : c->d_plane) dev_free(p);
     dev_free(c->d_bits_merged);
@@ -261,6 +264,10 @@ void mark_frames(lt_ctx* c, int first, int n, int full) {
 }
 static void front_stale(lt_ctx* c, int first, int n) {      // new camera rows in these slots: their planes are the old frames'
     for (int i = first; i < first + n && i < (int)c->front_ok.size(); ++i) c->front_ok[(size_t)i] = 0;
+}
+// an upload of camera rows into these slots: their front end reads the slots' own frames again (lt_attach_device_frames)
+static void detach_slots(lt_ctx* c, int first, int n) {
+    for (int i = first; i < first + n && i < (int)c->attached.size(); ++i) c->attached[(size_t)i] = 0;
 }
 void mark_annot(lt_ctx* c, int first, int n, int full) {
     for (int i = first; i < first + n && i < (int)c->annot_full.size(); ++i) c->annot_full[(size_t)i] = (uint8_t)full;
@@ -1097,6 +1104,7 @@ int lt_upload_frames(lt_ctx* c, const uint8_t* frames, int first, int n) {
     if ((rc = set_device(c))) return rc;
     if ((rc = sync_all(c))) return rc;
     if (n > 0) c->input_locked = true;
+    detach_slots(c, first, n);
     if (c->in_layout != LT_INPUT_RGB) {
         // 4:2:0: the frames into staging (what the undistortion reads), and their RGB form into the camera frames for whoever shows them
         if (n > 0 && (rc = yuv_copy(c, frames, first, n, 0, c->calib.img_h, 0, c->calib.img_h / 2, c->stream))) return rc;
@@ -1127,6 +1135,7 @@ static int check_upload(lt_ctx* c, const uint8_t* frames, int first, int n) {
     if (rc) return rc;
     if (!frames) return fail(LT_ERR_INVALID, "null frames");
     if (n > 0) c->input_locked = true;
+    detach_slots(c, first, n);
     return n > 0 ? set_device(c) : LT_OK;
 }
 // A stream-ordered copy into the camera rows of slots [first, first + n) waits on `st` for the kernels that still read them (slot-range
@@ -1440,6 +1449,129 @@ int lt_upload_frame_rest(lt_ctx* c, const uint8_t* frames, int first, int n) {
         HIP_TRY(hipMemcpy2DAsync(dst + tail0, c->frame_bytes, frames + tail0, c->frame_bytes, c->frame_bytes - tail0, (size_t)n,
                                  hipMemcpyHostToDevice, c->copy));
     mark_frames(c, first, n, 1);
+    return rest_mark(c, first, n);
+}
+
+// ---- frames that are already in device memory ------------------------------------------------------------------------------------
+// Every plane of every surface is checked on the host before anything is launched: device memory of this context's device, its
+// whole extent inside one allocation.  Blocks of lt_device_alloc are known to the library (no query); for anything else the
+// runtime is asked -- per allocation once within a call, and never remembered beyond it (the caller may free it afterwards).
+namespace {
+struct KnownRange { uintptr_t base = 0; size_t size = 0; };
+int check_plane(lt_ctx* c, const void* p, size_t extent, int k, int i, KnownRange& memo) {
+    if (!p) return fail(LT_ERR_INVALID, "surface %d: plane %d is a null pointer", k, i);
+    const uintptr_t a = (uintptr_t)p;
+    const void* base = nullptr;
+    size_t size = 0;
+    int dev = 0;
+    if (cached_block_find(p, &base, &size, &dev)) {
+        if (dev != c->device) return fail(LT_ERR_INVALID, "surface %d: plane %d lies on device %d, the context on device %d", k, i, dev, c->device);
+        if (a + extent > (uintptr_t)base + size)
+            return fail(LT_ERR_INVALID, "surface %d: plane %d runs past the end of its allocation (%zu bytes from the pointer, %zu left)", k, i, extent,
+                        (size_t)((uintptr_t)base + size - a));
+        return LT_OK;
+    }
+    if (memo.size && a >= memo.base && a + extent <= memo.base + memo.size) return LT_OK;
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(LT_ERR_INVALID, "surface %d: plane %d (%p) is not device memory of this process's HIP runtime (a host pointer, or memory of another runtime)", k, i, p);
+    }
+    if (at.type != hipMemoryTypeDevice) return fail(LT_ERR_INVALID, "surface %d: plane %d (%p) is not device memory", k, i, p);
+    if (at.device != c->device) return fail(LT_ERR_INVALID, "surface %d: plane %d lies on device %d, the context on device %d", k, i, at.device, c->device);
+    hipDeviceptr_t rb = nullptr;
+    size_t rs = 0;
+    if (hipMemGetAddressRange(&rb, &rs, (hipDeviceptr_t)const_cast<void*>(p)) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(LT_ERR_INVALID, "surface %d: plane %d (%p): the runtime does not know its allocation", k, i, p);
+    }
+    if (a < (uintptr_t)rb || a + extent > (uintptr_t)rb + rs)
+        return fail(LT_ERR_INVALID, "surface %d: plane %d runs past the end of its allocation (%zu bytes from the pointer, %zu left)", k, i, extent,
+                    a >= (uintptr_t)rb && a < (uintptr_t)rb + rs ? (size_t)((uintptr_t)rb + rs - a) : (size_t)0);
+    memo.base = (uintptr_t)rb;
+    memo.size = rs;
+    return LT_OK;
+}
+int check_surfaces(lt_ctx* c, const lt_device_surface* s, int n, SurfEntry* out) {
+    const int H = c->calib.img_h, W = c->calib.img_w, layout = c->in_layout;
+    const int row = layout == LT_INPUT_RGB ? 3 * W : W, crow = layout == LT_INPUT_NV12 ? W : W / 2;
+    constexpr int PITCH_MAX = (1 << 23) - 1;             // the kernels multiply rows and pitches with 24-bit instructions
+    KnownRange memo;
+    for (int k = 0; k < n; ++k) {
+        const lt_device_surface& f = s[k];
+        if (f.pitch < row) return fail(LT_ERR_INVALID, "surface %d: pitch %d is below the row's %d bytes", k, (int)f.pitch, row);
+        if (f.pitch > PITCH_MAX) return fail(LT_ERR_INVALID, "surface %d: pitch %d is too large", k, (int)f.pitch);
+        const size_t ext = (size_t)f.pitch * (size_t)(H - 1) + (size_t)row;
+        if (ext >= ((size_t)1 << 31) - 8) return fail(LT_ERR_INVALID, "surface %d: a plane of %zu bytes is too large", k, ext);
+        int rc = check_plane(c, f.plane[0], ext, k, 0, memo);
+        if (rc) return rc;
+        out[k] = SurfEntry{{(uint64_t)(uintptr_t)f.plane[0], 0, 0}, f.pitch, 0};
+        if (layout == LT_INPUT_RGB) continue;
+        if (f.chroma_pitch < crow) return fail(LT_ERR_INVALID, "surface %d: chroma pitch %d is below the row's %d bytes", k, (int)f.chroma_pitch, crow);
+        if (f.chroma_pitch > PITCH_MAX) return fail(LT_ERR_INVALID, "surface %d: chroma pitch %d is too large", k, (int)f.chroma_pitch);
+        const size_t cext = (size_t)f.chroma_pitch * (size_t)(H / 2 - 1) + (size_t)crow;
+        if (cext >= ((size_t)1 << 31) - 8) return fail(LT_ERR_INVALID, "surface %d: a plane of %zu bytes is too large", k, cext);
+        for (int i = 1; i <= (layout == LT_INPUT_I420 ? 2 : 1); ++i) {
+            if ((rc = check_plane(c, f.plane[i], cext, k, i, memo))) return rc;
+            out[k].plane[i] = (uint64_t)(uintptr_t)f.plane[i];
+        }
+        out[k].cpitch = f.chroma_pitch;
+    }
+    return LT_OK;
+}
+}  // namespace
+
+int lt_attach_device_frames(lt_ctx* c, const lt_device_surface* surfaces, int first, int n) {
+    int rc = check_slots(c, first, n);
+    if (rc) return rc;
+    if (!surfaces) return fail(LT_ERR_INVALID, "null surfaces");
+    if (n == 0) return LT_OK;
+    if ((rc = set_device(c))) return rc;
+    std::vector<SurfEntry> ent((size_t)n);
+    if ((rc = check_surfaces(c, surfaces, n, ent.data()))) return rc;     // nothing has been launched or changed
+    if (!c->d_surf) {
+        if ((rc = dev_alloc(&c->d_surf, (size_t)c->capacity))) return rc;
+        c->surf.assign((size_t)c->capacity, SurfEntry{});
+        c->attached.assign((size_t)c->capacity, 0);
+    }
+    c->input_locked = true;
+    mark_frames(c, first, n, 0);         // the slots' own camera frames are the previous occupants' until lt_device_frames_rest
+    front_stale(c, first, n);
+    for (int i = 0; i < n; ++i) {
+        c->surf[(size_t)(first + i)] = ent[(size_t)i];
+        c->attached[(size_t)(first + i)] = 1;
+    }
+    // The entries go into the table on the slots' own streams: behind everything launched over these slots there (the front end
+    // that reads their previous entries) and ahead of whatever is launched next -- and behind readers on other streams.
+    return for_each_slice(c, first, n, [&](hipStream_t st, int f0, int m) {
+        const int wrc = wait_camera_readers(c, st, f0, m);
+        if (wrc) return wrc;
+        launch_write_surf_entries(st, c->d_surf, f0, ent.data() + (f0 - first), m);
+        HIP_TRY(hipGetLastError());
+        return (int)LT_OK;
+    });
+}
+
+int lt_device_frames_rest(lt_ctx* c, int first, int n, const int32_t* rows4) {
+    int rc = check_slots(c, first, n);
+    if (rc) return rc;
+    for (int i = first; i < first + n; ++i)
+        if (i >= (int)c->attached.size() || !c->attached[(size_t)i]) return fail(LT_ERR_STATE, "slot %d has no device frame attached", i);
+    const int H = c->calib.img_h;
+    if (rows4 && !(0 <= rows4[0] && rows4[0] <= rows4[1] && rows4[1] <= rows4[2] && rows4[2] <= rows4[3] && rows4[3] <= H))
+        return fail(LT_ERR_INVALID, "row runs must be ordered and inside the frame");
+    if (n == 0) return LT_OK;
+    if ((rc = set_device(c))) return rc;
+    // as lt_upload_frame_rest: on the copy stream, behind the overlays that still read the camera frames these rows replace
+    if ((rc = wait_camera_readers(c, c->copy, first, n))) return rc;
+    const int32_t whole[4] = {0, H, H, H};
+    const int32_t* r = rows4 ? rows4 : whole;
+    for (int k = 0; k < 4; k += 2)
+        launch_surf_rows_to_rgb(c->copy, c->in_layout, &c->surf[(size_t)first], yuv_coef_of(c), slot_frame(c, first), c->frame_bytes, H,
+                                c->calib.img_w, r[k], r[k + 1], n);
+    HIP_TRY(hipGetLastError());
+    if ((rc = note_range(c->readers, c->copy, first, first + n))) return rc;      // it reads the surfaces and writes the camera frames: the next upload waits
+    if (!rows4) mark_frames(c, first, n, 1);
     return rest_mark(c, first, n);
 }
 
@@ -1884,12 +2016,20 @@ static int mask_run_impl(lt_ctx* c, int first, int n, const lt_filter_params* p,
         for (int i = f0; have_front && i < f0 + m; ++i) have_front = c->front_ok[(size_t)i] != 0;
         if (!have_front) {
             { StageScope t(c, ST_UNDISTORT, st);
-              if (c->in_layout != LT_INPUT_RGB)
-                  launch_undistort_rows_yuv(st, c->in_layout, slot_yuv(c, f0), c->yuv_stride, yuv_coef_of(c), c->d_uxy, c->d_ufrac,
-                                            c->fe, c->d_und, c->und_px, f0, m);
-              else
-              launch_undistort_rows(st, slot_frame(c, f0), c->frame_bytes, c->d_uxy, c->d_ufrac,
-                                    c->fe, c->d_und, c->und_px, f0, m); }
+              // runs of slots whose frames lie in the caller's device memory (the table form) and of slots that hold their own
+              auto is_attached = [&](int i) { return i < (int)c->attached.size() && c->attached[(size_t)i] != 0; };
+              for (int a = f0, b; a < f0 + m; a = b) {
+                  const bool att = is_attached(a);
+                  for (b = a + 1; b < f0 + m && is_attached(b) == att; ++b) {}
+                  if (att)
+                      launch_undistort_rows_surf(st, c->in_layout, c->d_surf, yuv_coef_of(c), c->d_uxy, c->d_ufrac, c->fe, c->d_und, c->und_px, a, b - a);
+                  else if (c->in_layout != LT_INPUT_RGB)
+                      launch_undistort_rows_yuv(st, c->in_layout, slot_yuv(c, a), c->yuv_stride, yuv_coef_of(c), c->d_uxy, c->d_ufrac,
+                                                c->fe, c->d_und, c->und_px, a, b - a);
+                  else
+                      launch_undistort_rows(st, slot_frame(c, a), c->frame_bytes, c->d_uxy, c->d_ufrac,
+                                            c->fe, c->d_und, c->und_px, a, b - a);
+              } }
             { int mrc = n == 1 ? note_range_frame(c, c->readers, st, f0, f0 + m) : note_range(c->readers, st, f0, f0 + m); if (mrc) return mrc; }
             { StageScope t(c, ST_WARP_SPLIT, st);
               launch_warp_split(st, c->d_und, c->und_px, f0, c->d_wxy, c->d_wfrac, c->fe, c->d_gamma,

@@ -70,6 +70,12 @@ struct lt_ctx {
     bool input_locked = false;                // an upload has happened: the format stays
     uint8_t* d_yuv = nullptr;
     size_t yuv_bytes = 0, yuv_stride = 0;
+    // Frames in the caller's device memory (lt_attach_device_frames): the surface table -- one entry per slot, read by the table form
+    // of the undistortion (k_frontend.hip) -- its host mirror (what lt_device_frames_rest passes on as kernel arguments) and which
+    // slots are attached.  Allocated by the first attach; any upload of camera rows into a slot detaches it.
+    lt::SurfEntry* d_surf = nullptr;
+    std::vector<lt::SurfEntry> surf;
+    std::vector<uint8_t> attached;
     uint32_t* d_und = nullptr;        // undistorted camera rows [r0, r0+nrows), one RGBX dword per pixel, slots 2p / 2p+1 interleaved (und_slot_base)
     size_t und_px = 0;                // pixels per slot of d_und
     uint8_t* d_plane[P_COUNT] = {};   // P_R, P_B, P_THR, P_THB, P_T0 with the slots; the others on first use (ensure_plane)
@@ -292,6 +298,8 @@ void pooled_event_release(hipEvent_t e);
 // ---- device memory (lt_memory.cpp): a cache in front of hipMalloc / hipFree ------------------------------
 void* cached_alloc(size_t bytes);
 void cached_free(void* p);
+// the block the cache has handed out that holds address p (lt_device_alloc's blocks, the contexts' own buffers): its base, size and device
+bool cached_block_find(const void* p, const void** base, size_t* bytes, int* device);
 // Frees of one thread bracketed by this wait for `device` ONCE and enter the cache together when the scope closes -- behind
 // the allocations made inside it (lt_reserve: the larger blocks first, then the old ones into the cache; lt_destroy).
 struct FreeScope {

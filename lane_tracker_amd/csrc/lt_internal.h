@@ -70,6 +70,27 @@ void launch_undistort_rows_yuv(hipStream_t s, int layout, const uint8_t* yuv, si
 // rows [r0, r1) of n 4:2:0 frames of h x w (h, w even) -> the same rows of n RGB frames
 void launch_yuv_rows_to_rgb(hipStream_t s, int layout, const uint8_t* yuv, size_t yuv_stride, YuvCoef k, uint8_t* rgb,
                             size_t rgb_stride, int h, int w, int r0, int r1, int n);
+// Frames in the caller's device memory (lt_attach_device_frames): one entry per slot of the context's surface table -- the plane
+// pointers (RGB: [0]; NV12: Y, UV; I420: Y, U, V) and the row pitches of the luma / RGB plane and of the chroma plane(s), in bytes.
+// Checked on the host before they reach a kernel: pitches at least a row and below 2^23 (24-bit multiplies), planes below 2^31 bytes.
+struct SurfEntry {
+    uint64_t plane[3];
+    int32_t pitch, cpitch;
+};
+static_assert(sizeof(SurfEntry) == 32, "SurfEntry: 32 bytes, two scalar loads");
+struct SurfChunk {               // the entries of one launch, by value
+    static constexpr int N = 32;
+    SurfEntry e[N];
+};
+// launch_undistort_rows / _yuv (layout 0 = RGB, 1 = NV12, 2 = I420) with the taps read from the surfaces of entries
+// [first_slot, first_slot + n) of `tab` (device memory)
+void launch_undistort_rows_surf(hipStream_t s, int layout, const SurfEntry* tab, YuvCoef k, const int16_t* uxy, const uint16_t* ufrac,
+                                FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n);
+// entries[0, n) (host memory, consumed before the call returns) -> tab[first, first + n), stream-ordered
+void launch_write_surf_entries(hipStream_t s, SurfEntry* tab, int first, const SurfEntry* entries, int n);
+// rows [r0, r1) of the n surfaces of entries[] (host memory) -> the same rows of n RGB frames: a conversion (4:2:0) or a pitched copy (RGB)
+void launch_surf_rows_to_rgb(hipStream_t s, int layout, const SurfEntry* entries, YuvCoef k, uint8_t* rgb, size_t rgb_stride, int h, int w,
+                             int r0, int r1, int n);
 void launch_split_bev(hipStream_t s, const uint8_t* bev, size_t bev_stride, int npix, const uint16_t* gamma_tab,
                       const uint16_t* cbrt_tab, const int32_t* coeffs, uint8_t* planeR, uint8_t* planeB,
                       size_t plane_stride, int n);

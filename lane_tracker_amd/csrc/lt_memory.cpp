@@ -239,6 +239,19 @@ void cached_free(void* p) {
     release_blocks(out);
 }
 
+bool cached_block_find(const void* p, const void** base, size_t* bytes, int* device) {
+    DevCache& dc = dev_cache();
+    std::lock_guard<std::mutex> g(dc.m);
+    auto it = dc.live.upper_bound(const_cast<void*>(p));
+    if (it == dc.live.begin()) return false;
+    --it;
+    if ((uintptr_t)p >= (uintptr_t)it->first + it->second.second) return false;
+    *base = it->first;
+    *bytes = it->second.second;
+    *device = it->second.first;
+    return true;
+}
+
 void cache_take(size_t keep_bytes, std::vector<std::pair<int, void*>>& out) {
     DevCache& dc = dev_cache();
     std::lock_guard<std::mutex> g(dc.m);
@@ -270,6 +283,63 @@ int lt_host_alloc(size_t bytes, void** out) {
         *out = nullptr;
         return fail(LT_ERR_HIP, "hipHostMalloc(%zu) failed", bytes);
     }
+    return LT_OK;
+}
+
+// Device blocks for callers without a HIP binding of their own (the Python package, tools, tests): out of the cache the contexts'
+// buffers come from, so that the frames they hold live in the library's runtime, with plain synchronous copies.
+int lt_device_alloc(int device, size_t bytes, void** out) {
+    if (!out || bytes == 0) return fail(LT_ERR_INVALID, "lt_device_alloc: null output or zero size");
+    *out = nullptr;
+    int cur = 0;
+    HIP_TRY(hipGetDevice(&cur));
+    if (cur != device) HIP_TRY(hipSetDevice(device));
+    *out = cached_alloc(bytes);
+    if (cur != device) (void)hipSetDevice(cur);
+    if (!*out) return fail(LT_ERR_NOMEM, "hipMalloc(%zu bytes) failed", bytes);
+    return LT_OK;
+}
+
+int lt_device_free(void* p) {
+    if (!p) return LT_OK;
+    const void* base = nullptr;
+    size_t bytes = 0;
+    int dev = 0;
+    if (!cached_block_find(p, &base, &bytes, &dev) || base != p) return fail(LT_ERR_INVALID, "lt_device_free: not a block of lt_device_alloc");
+    cached_free(p);                      // waits for the block's device first, as hipFree would
+    return LT_OK;
+}
+
+static int device_copy(void* dst, const void* src, size_t bytes, const void* dev_ptr, hipMemcpyKind kind, const char* what) {
+    if (bytes == 0) return LT_OK;
+    if (!dst || !src) return fail(LT_ERR_INVALID, "%s: null pointer", what);
+    const void* base = nullptr;
+    size_t size = 0;
+    int dev = 0;
+    if (!cached_block_find(dev_ptr, &base, &size, &dev) || (uintptr_t)dev_ptr + bytes > (uintptr_t)base + size)
+        return fail(LT_ERR_INVALID, "%s: %zu bytes at %p do not lie inside a block of lt_device_alloc", what, bytes, dev_ptr);
+    int cur = 0;
+    HIP_TRY(hipGetDevice(&cur));
+    if (cur != dev) HIP_TRY(hipSetDevice(dev));
+    const hipError_t e = hipMemcpy(dst, src, bytes, kind);
+    if (cur != dev) (void)hipSetDevice(cur);
+    if (e != hipSuccess) return fail(LT_ERR_HIP, "%s: hipMemcpy failed: %s", what, hipGetErrorString(e));
+    return LT_OK;
+}
+int lt_device_write(void* dst_device, const void* src_host, size_t bytes) { return device_copy(dst_device, src_host, bytes, dst_device, hipMemcpyHostToDevice, "lt_device_write"); }
+int lt_device_read(void* dst_host, const void* src_device, size_t bytes) { return device_copy(dst_host, src_device, bytes, src_device, hipMemcpyDeviceToHost, "lt_device_read"); }
+
+// The host waits for a producer's stream (the `stream` entry of __cuda_array_interface__: 1 the legacy default stream, 2 the
+// per-thread default stream, anything else a hipStream_t of this runtime) before its frames are attached.
+int lt_device_stream_wait(int device, uintptr_t stream) {
+    if (stream == 0) return fail(LT_ERR_INVALID, "lt_device_stream_wait: 0 is not a stream (1: legacy default, 2: per-thread default)");
+    int cur = 0;
+    HIP_TRY(hipGetDevice(&cur));
+    if (cur != device) HIP_TRY(hipSetDevice(device));
+    const hipStream_t st = stream == 1 ? (hipStream_t) nullptr : stream == 2 ? hipStreamPerThread : reinterpret_cast<hipStream_t>(stream);
+    const hipError_t e = hipStreamSynchronize(st);
+    if (cur != device) (void)hipSetDevice(cur);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(LT_ERR_HIP, "hipStreamSynchronize failed: %s", hipGetErrorString(e)); }
     return LT_OK;
 }
 

@@ -17,6 +17,7 @@ import functools
 import numpy as np
 
 from . import _native
+from .device import DeviceFrames, feed_rest_list, feed_rows_list
 from .lane_tracker import LaneTracker
 from .stream import StreamPipeline
 
@@ -144,9 +145,13 @@ class LaneTrackerGroup:
         if not active:
             return outs
         shape = self._frame_shape
-        imgs = [np.ascontiguousarray(frames[i], np.uint8) for i in active]
+        imgs = [frames[i] if isinstance(frames[i], DeviceFrames) else np.ascontiguousarray(frames[i], np.uint8) for i in active]
         for img in imgs:
-            if img.shape != shape:
+            if isinstance(img, DeviceFrames):        # a stream whose frame is already in device memory: attached, not uploaded
+                img.check_for(self.img_size, self.pixel_format)
+                if len(img) != 1:
+                    raise ValueError("expected one frame per stream, got DeviceFrames of %d" % len(img))
+            elif img.shape != shape:
                 raise ValueError("expected frames of shape %r, got %r" % (shape, img.shape))
         ts = [self.trackers[i] for i in active]
         m, k, ctx = len(active), self.k, self._ctx
@@ -156,10 +161,10 @@ class LaneTrackerGroup:
         self._free_slots(base, base + m)
 
         # 1-3: camera rows of the m frames, one mask chain, one search launch
-        keep = ctx.upload_frame_rows_list(imgs, first=base)
+        keep = feed_rows_list(ctx, imgs, base)
         ctx.mask_run(m, fp, first=base)
         if annotate:
-            keep_rest = ctx.upload_frame_rest_list(imgs, first=base)     # (for the overlay, beside the mask chain)
+            keep_rest = feed_rest_list(ctx, imgs, base)                  # (for the overlay, beside the mask chain)
             ts[0]._configure_overlay()
         for t in ts:                                                     # _step's opening
             t._open_frame()
@@ -179,7 +184,7 @@ class LaneTrackerGroup:
         if again:
             second = StreamPipeline._SECOND_TRY
             self._free_slots(spare, spare + len(again))
-            keep_again = ctx.upload_frame_rows_list([imgs[j] for j in again], first=spare)
+            keep_again = feed_rows_list(ctx, [imgs[j] for j in again], spare)
             ctx.mask_run(len(again), _native.filter_params(second[4], *second[:4], *second[5:9]), first=spare)
             self._search([ts[j] for j in again], spare, second, diagnostics)
             for j in again:

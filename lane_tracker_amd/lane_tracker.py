@@ -21,6 +21,7 @@ from . import hostcpu as _hostcpu
 from . import _native
 from . import overlay as _overlay
 from . import utils as _utils
+from .device import DeviceFrames
 from .stream import StreamPipeline, _PackedPoly, _pack_deferred      # noqa: F401  (the window / stream pipeline: a mix-in)
 
 __all__ = ["LaneTracker", "bilateral_adaptive_threshold"]
@@ -126,6 +127,7 @@ class LaneTracker(StreamPipeline):
         self._overlay_ready = False
         self._have_font = False
         self._resident = None       # (frame array, slot) of the camera frame last uploaded to the main context
+        self._device_keepalive = {}  # first slot -> the DeviceFrames the stream pipeline attached there, until their work has been waited for
         self._in_stream = False     # a process_stream() generator is active: its windows own the context's slots
         # the presentation stage's tables now, not at the first annotated frame: lt_overlay_configure may widen the run of camera
         # rows the uploads bring by a row or two (so that the lane's rows need no upload of their own), and a frame uploaded before
@@ -146,7 +148,12 @@ class LaneTracker(StreamPipeline):
 
     def _check_frame(self, img, window=False):
         """A 4:2:0 tracker takes frames of its own shape only (nothing is uploaded before this has been looked at); an RGB tracker
-        takes what it always took."""
+        takes what it always took.  Frames in device memory (device.DeviceFrames) must be the tracker's size and pixel format."""
+        if isinstance(img, DeviceFrames):
+            img.check_for(self.img_size, self.pixel_format)
+            if not window and len(img) != 1:
+                raise ValueError("process() takes one frame, got DeviceFrames of %d" % len(img))
+            return
         if self.pixel_format == 'rgb':
             return
         shape = getattr(img, "shape", None)
@@ -646,6 +653,12 @@ class LaneTracker(StreamPipeline):
         self._configure_overlay()
         if self._resident is not None and self._resident[0] is img:
             return self._resident[1]
+        if isinstance(img, DeviceFrames):    # shown where it lies: attached, and the whole frame brought into the slot on the device
+            self._check_frame(img)
+            self._rows_keepalive = self._ctx.attach_device_frames(img, first=0)
+            self._ctx.device_frames_rest(1, first=0)
+            self._resident, self._resident_partial = (img, 0), False
+            return 0
         self._ctx.upload_frames(img, first=0)
         self._resident, self._resident_partial = (img, 0), False
         return 0
@@ -743,6 +756,27 @@ class LaneTracker(StreamPipeline):
             return None
         return self._present_rows()
 
+    def _feed_rows(self, frames, first):
+        """The camera rows the path reads of a window's frames into slots first ..: stream-ordered, nobody waits.  Frames in
+        device memory are attached instead -- nothing crosses the bus, nothing is copied."""
+        if isinstance(frames, DeviceFrames):
+            self._device_keepalive[first] = self._ctx.attach_device_frames(frames, first=first)
+            return frames
+        return self._ctx.upload_frame_rows_async(frames, first=first)
+
+    def _feed_rest(self, frames, first, rows=None):
+        """The rows a shown frame needs besides (upload_frame_rest); from attached frames on the device (device_frames_rest)."""
+        if isinstance(frames, DeviceFrames):
+            self._ctx.device_frames_rest(len(frames), first=first, rows=rows)
+            return frames
+        return self._ctx.upload_frame_rest(frames, first=first, rows=rows)
+
+    def _device_frames_done(self):
+        """The windows attached by the stream pipeline may go: everything launched over them has been waited for."""
+        if self._device_keepalive:
+            self._ctx.sync()
+            self._device_keepalive.clear()
+
     _copying = False            # the library's copy thread may still be filling rows of _out (or of the frame just handed out)
 
     _copy_keepalive = None      # the arrays the copy threads read and write, until they are done
@@ -775,7 +809,7 @@ class LaneTracker(StreamPipeline):
 
     def _rows_for_window(self, frames):
         """_present_rows() when the annotated frames of this window can travel as row runs, else None."""
-        if not self.host_copies_rows or frames.dtype != np.uint8 or not frames.flags["C_CONTIGUOUS"] or \
+        if isinstance(frames, DeviceFrames) or not self.host_copies_rows or frames.dtype != np.uint8 or not frames.flags["C_CONTIGUOUS"] or \
                 frames.shape[1:] != (self.img_size[1], self.img_size[0], 3):
             return None
         return self._present_rows()
@@ -796,7 +830,7 @@ class LaneTracker(StreamPipeline):
             raise ValueError("at most three text lines")
         if rows is None and self._resident_partial and self._resident is not None:
             # the whole frame is wanted after all (draw_lane() by hand on the frame process() has just seen): bring the rest
-            self._upload_keepalive = self._ctx.upload_frame_rest(self._resident[0], first=slot)
+            self._upload_keepalive = self._feed_rest(self._resident[0], slot)
             self._resident_partial = False
         def packed():        # the lines as the library takes them (only where somebody still has to draw them)
             return b"".join(t.encode("ascii", "replace")[:line_len].ljust(line_len, b"\0") for t in lines) \
@@ -910,7 +944,10 @@ class LaneTracker(StreamPipeline):
             # (not waited for: the engine's copy runs under the mask chain's launches; `img` -- or the contiguous copy the binding
             # made of it -- stays alive until the frame's record is on the host, and process() waits for the device on its way out
             # of an exception)
-            self._rows_keepalive = ctx.upload_frame_rows(img, first=slot, enqueue=self.enqueues_upload)
+            if isinstance(img, DeviceFrames):    # already on the device: read where it lies, nothing is copied
+                self._rows_keepalive = ctx.attach_device_frames(img, first=slot)
+            else:
+                self._rows_keepalive = ctx.upload_frame_rows(img, first=slot, enqueue=self.enqueues_upload)
         try:
             self._resident = (img, slot)
             if not have_mask:
@@ -932,9 +969,9 @@ class LaneTracker(StreamPipeline):
                     rows = self._rows_for(img) if self._want_out else None
                     if rows is not None and rows[4] is not None:
                         if rows[4][4]:           # (rows of the lane's run the mask chain does not read: none with the reference calibration)
-                            self._upload_keepalive = ctx.upload_frame_rest(img, first=slot, rows=rows[4][1])
+                            self._upload_keepalive = self._feed_rest(img, slot, rows[4][1])
                     else:
-                        self._upload_keepalive = ctx.upload_frame_rest(img, first=slot, rows=None if rows is None else rows[1])
+                        self._upload_keepalive = self._feed_rest(img, slot, None if rows is None else rows[1])
                     self._resident_partial = rows is not None
                 if self._want_out and self._out is None:
                     self._prepare_out()          # (a frame whose output array could not be prepared ahead of the search)

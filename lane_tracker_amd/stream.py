@@ -9,6 +9,7 @@ import numpy as np
 
 from . import _native
 from . import overlay as _overlay
+from .device import DeviceFrames
 
 
 class StreamPipeline:
@@ -364,10 +365,10 @@ class StreamPipeline:
             while masked < min(total, upto):
                 if masked < n:
                     m = min(span(masked), n - masked)
-                    ctx.upload_frame_rows_async(frames[masked:masked + m], first=base + masked)
+                    self._feed_rows(frames[masked:masked + m], base + masked)
                     ctx.mask_run(m, fp, first=base + masked)
                     if rest_needed:      # the rest of these frames, for the overlay: behind their rows on the copy stream
-                        ctx.upload_frame_rest(frames[masked:masked + m], first=base + masked, rows=rest_rows)
+                        self._feed_rest(frames[masked:masked + m], base + masked, rest_rows)
                 else:
                     q = masked - n
                     for a in ahead:                       # the window position `masked` falls into
@@ -375,10 +376,10 @@ class StreamPipeline:
                             break
                         q -= len(a[0])
                     m = min(chunk, len(a[0]) - q)
-                    ctx.upload_frame_rows_async(a[0][q:q + m], first=a[1] + q)
+                    self._feed_rows(a[0][q:q + m], a[1] + q)
                     ctx.mask_run(m, fp, first=a[1] + q)
                     if rest_needed:
-                        ctx.upload_frame_rest(a[0][q:q + m], first=a[1] + q, rows=rest_rows)
+                        self._feed_rest(a[0][q:q + m], a[1] + q, rest_rows)
                     a[2] = q + m
                 masked += m
         feed(2 * chunk)
@@ -582,6 +583,11 @@ class StreamPipeline:
         return time.perf_counter() - t0
 
     def _as_window(self, frames):
+        if isinstance(frames, DeviceFrames):     # frames in device memory: attached where they lie, shown through the device
+            if self._annotate_inplace:
+                raise ValueError("annotate='inplace' draws into RGB frames on the host: DeviceFrames have none there")
+            self._check_frame(frames, window=True)
+            return frames[0:1] if frames.single else frames
         frames = np.ascontiguousarray(frames, np.uint8)
         if self.pixel_format != 'rgb':
             if self._annotate_inplace:
@@ -763,16 +769,23 @@ class StreamPipeline:
             finally:
                 self._all_copies_done()
                 self._window_rows = None
+                self._device_frames_done()
         else:
-            ctx.upload_frame_rows(frames)        # the camera rows the path reads; the rest only if frames are annotated
+            if isinstance(frames, DeviceFrames):
+                self._feed_rows(frames, 0)
+            else:
+                ctx.upload_frame_rows(frames)    # the camera rows the path reads; the rest only if frames are annotated
             ctx.mask_run(n, fp)
             if annotate:
-                self._upload_keepalive = ctx.upload_frame_rest(frames)     # beside the mask chain, for the overlay
+                self._upload_keepalive = self._feed_rest(frames, 0)        # beside the mask chain, for the overlay
             for i in range(n):
                 self._step(frames[i], first_try, k["n_tries"], k["diagnostics"], slot=i, have_mask=True, lazy=True,
                            annotate=annotate, defer=deferred)
         self._materialise_pending()      # the attributes describe the last frame, as after process()
-        return self._render_window(deferred, 0) if annotate else [None] * n
+        try:
+            return self._render_window(deferred, 0) if annotate else [None] * n
+        finally:
+            self._device_frames_done()
 
     def process_stream(self, windows, annotate=True, **kwargs):
         """Generator over consecutive windows of ONE video: `windows` yields arrays (n, H, W, 3); for each, what
@@ -795,6 +808,13 @@ class StreamPipeline:
         if self._in_stream:
             raise RuntimeError("this tracker already runs a process_stream()")
         cur = self._as_window(cur)
+        device_fed = isinstance(cur, DeviceFrames)
+
+        def as_next_window(w):               # (how annotated frames travel is decided once per stream, by its first window)
+            w = self._as_window(w)
+            if isinstance(w, DeviceFrames) != device_fed:
+                raise ValueError("the windows of one stream are either all arrays or all DeviceFrames")
+            return w
         ctx = self._ctx
         look = max(1, int(self.stream_lookahead))
         # windows resident side by side: the one being searched and `look` being fed -- and, with annotation, the one before,
@@ -823,7 +843,7 @@ class StreamPipeline:
                     w = next(it, None)
                     if w is None:
                         break
-                    queue.append([self._as_window(w), None, 0])
+                    queue.append([as_next_window(w), None, 0])
                 n = cur[0].shape[0]
                 if cur[1] is None:                   # first window, or one that did not fit the regions: (re)size the context
                     if landing is not None:
@@ -866,6 +886,10 @@ class StreamPipeline:
         finally:
             self._in_stream = False
             self._window_rows = None
+            try:
+                self._device_frames_done()   # (waits for the device: the attached windows may go)
+            except Exception:
+                pass
             if annotate:                 # a generator closed early: no copy may still be writing into page-locked arrays
                 try:                     # that go back to the pool with their last reference
                     ctx.band_fit_chain_cancel()
