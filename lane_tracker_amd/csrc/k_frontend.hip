@@ -2,7 +2,10 @@
 //
 //   k_undistort_rows   cv2.undistort            lane_tracker.py:832   (only the rows the warp reads)
 //   k_undistort_rows_yuv  the same over a 4:2:0 frame (NV12 / I420): cv2.cvtColor(YUV2RGB_*) of every tap, then the blend
-//   k_yuv_rows_to_rgb  cv2.cvtColor(YUV2RGB_NV12 / _I420) of a run of rows (for whoever shows the camera frame)
+//   k_undistort_rows_surf, k_undistort_rows_yuv_surf  the same two over frames in the caller's device memory (surface table)
+//                      -- all of them entry points of one walk, undistort_walk<source, pixel format>
+//   k_yuv_rows_to_rgb, k_surf_rows_to_rgb  cv2.cvtColor(YUV2RGB_NV12 / _I420) of a run of rows (for whoever shows the camera
+//                      frame), from a slot's staging frame / from a surface: one 16-column and one byte-wise body
 //   k_warp_split       cv2.warpPerspective      lane_tracker.py:834
 //                      + img[:,:,0]             lane_tracker.py:207
 //                      + cvtColor(RGB2LAB)[:,:,2] lane_tracker.py:208
@@ -47,87 +50,6 @@ __device__ __forceinline__ uint32_t xcd_block(uint32_t lid, uint32_t total, int 
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + k;
 }
 
-// One thread per undistorted pixel.  Frames are RGB interleaved (3 B/px); the output is one RGBX
-// dword per pixel, so that the warp fetches a whole tap with a single aligned load.  All loads are
-// unconditional on clamped addresses and masked afterwards (a guarded load serialises on its own
-// s_waitcnt).
-
-// ALIGNED4 (frames are 4-byte aligned and so is their stride): the 8-byte window is fetched as the three aligned dwords
-// that hold it and shifted into place with two v_alignbyte_b32 -- an unaligned dwordx2 at 3-byte pitch occupies the
-// memory pipe for ~32 cycles, an aligned dwordx3 for ~20.
-template <bool ALIGNED4>
-__global__ __launch_bounds__(256) void k_undistort_rows(const uint8_t* __restrict__ frames, size_t frame_stride,
-                                                       const int16_t* __restrict__ uxy,
-                                                       const uint16_t* __restrict__ ufrac, FrontEndGeom g,
-                                                       uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb,
-                                                       int remap) {
-    const uint32_t per_z = gridDim.x * gridDim.y;
-    const uint32_t id = xcd_block((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x, per_z * gridDim.z, remap);
-    const uint32_t bz = id / per_z, by = (id - bz * per_z) / gridDim.x, bx = id - bz * per_z - by * gridDim.x;
-    const int x = bx * blockDim.x + threadIdx.x;
-    const int row = by;  // relative to g.r0
-    if (x >= g.img_w) return;
-    const int z0 = bz * fpb, z1 = min(z0 + fpb, n);   // fpb frames per thread: table entry and offsets are frame-independent
-    const size_t o = (size_t)row * g.img_w + x;
-    const int sx = uxy[o * 2], sy = uxy[o * 2 + 1];
-    const int f = ufrac[o], fx = f & 31, fy = f >> 5;
-    const bool y0 = sy >= 0 && sy < g.img_h, y1 = sy + 1 >= 0 && sy + 1 < g.img_h;
-    const bool x0 = sx >= 0 && sx < g.img_w, x1 = sx + 1 >= 0 && sx + 1 < g.img_w;
-    const int cy0 = min(max(sy, 0), g.img_h - 1), cy1 = min(max(sy + 1, 0), g.img_h - 1);
-    // The two taps of a row are 6 consecutive bytes (RGB RGB) at byte offset 3*sx: one 8-byte window per row instead
-    // of six byte loads (the frame buffer is padded by 8 bytes for the overrun).  When sx or sx+1 is outside the
-    // frame the row is fetched from the clamped column and the taps are masked.
-    struct __attribute__((packed, aligned(1))) Row8 { uint64_t v; };
-    const int cxl = min(max(sx, 0), g.img_w - 2);          // leftmost column of the 6-byte window we fetch
-    // 32-bit offsets (a frame is far below 2^31 bytes) keep the address math on full-rate 24-bit multiplies
-    const uint32_t off0 = (uint32_t)((__mul24(cy0, g.img_w) + cxl) * 3), off1 = (uint32_t)((__mul24(cy1, g.img_w) + cxl) * 3);
-    // column sx sits at byte 3*(sx-cxl) of the window when it is inside the frame; sx+1 three bytes later
-    const int sh0 = 24 * (min(max(sx, 0), g.img_w - 1) - cxl), sh1 = 24 * (min(max(sx + 1, 0), g.img_w - 1) - cxl);
-    const uint32_t m00 = (y0 && x0) ? 255u : 0u, m01 = (y0 && x1) ? 255u : 0u;
-    const uint32_t m10 = (y1 && x0) ? 255u : 0u, m11 = (y1 && x1) ? 255u : 0u;
-    const uint32_t gx = 32u - (uint32_t)fx, gy = 32u - (uint32_t)fy;
-    const uint32_t w00 = (gx * gy) & 0x7ffu, w01 = ((uint32_t)fx * gy) & 0x7ffu, w10 = (gx * (uint32_t)fy) & 0x7ffu, w11 = ((uint32_t)fx * (uint32_t)fy) & 0x7ffu;
-    const uint8_t* src = frames + (size_t)z0 * frame_stride;
-    constexpr int RSRC_RAW = 0x00027000;   // untyped 32-bit buffer, no swizzle
-    const int nz = z1 - z0, fstride = (int)frame_stride;
-    // +8: the window of the frame's last pixel ends in the padding behind it
-    const __amdgpu_buffer_rsrc_t frs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(src), 0, nz * fstride + 8, RSRC_RAW);
-    // the slots this thread writes: pairs [pair0, pair1] of the interleaved buffer
-    const int pair0 = (first_slot + z0) >> 1, pair1 = (first_slot + z1 - 1) >> 1, pair_b = (int)(und_px * 8);
-    const __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc(und + (size_t)pair0 * 2 * und_px, 0, (pair1 - pair0 + 1) * pair_b, RSRC_RAW);
-    typedef unsigned u32x3 __attribute__((ext_vector_type(3)));
-    auto window = [&](uint32_t off, int frame_off) {
-        if constexpr (ALIGNED4) {
-            const u32x3 d = __builtin_amdgcn_raw_buffer_load_b96(frs, (int)(off & ~3u), frame_off, 0);
-            const uint32_t lo = __builtin_amdgcn_alignbyte(d.y, d.x, off & 3u), hi = __builtin_amdgcn_alignbyte(d.z, d.y, off & 3u);
-            return (uint64_t)lo | ((uint64_t)hi << 32);
-        } else {
-            return reinterpret_cast<const Row8*>(src + (size_t)(unsigned)frame_off + off)->v;
-        }
-    };
-    uint64_t q0 = window(off0, 0), q1 = window(off1, 0);
-    for (int z = z0; z < z1; ++z) {
-        // the next frame's taps are in flight while this one is blended
-        const int nfo = (min(z + 1, z1 - 1) - z0) * fstride;
-        const uint64_t n0 = window(off0, nfo), n1 = window(off1, nfo);
-        const uint32_t a0 = (uint32_t)(q0 >> sh0), a1 = (uint32_t)(q0 >> sh1);
-        const uint32_t b0 = (uint32_t)(q1 >> sh0), b1 = (uint32_t)(q1 >> sh1);
-        uint32_t out = 0;
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-            const uint32_t v00 = (a0 >> (8 * ch)) & m00, v01 = (a1 >> (8 * ch)) & m01;
-            const uint32_t v10 = (b0 >> (8 * ch)) & m10, v11 = (b1 >> (8 * ch)) & m11;
-            // (sum_i w_i p_i + 2^9) >> 10: the same integer as bilerp(); with the 11-bit weights visible every product is a
-            // v_mul_u32_u24 / v_mad_u32_u24 (the two-stage form was re-associated into quarter-rate 32- and 64-bit multiplies)
-            out |= ((v00 * w00 + v01 * w01 + v10 * w10 + v11 * w11 + 512u) >> 10) << (8 * ch);
-        }
-        const int slot = first_slot + z;   // wave-uniform: pair and parity go into the scalar offset of the store
-        __builtin_amdgcn_raw_buffer_store_b32(out, urs, (int)o * 8, __builtin_amdgcn_readfirstlane(((slot >> 1) - pair0) * pair_b + (slot & 1) * 4), 0);
-        q0 = n0;
-        q1 = n1;
-    }
-}
-
 // ---- YUV 4:2:0 input ------------------------------------------------------------------------------------------------------
 // OpenCV's 8-bit YUV -> RGB: 20-bit fixed point in int32, one (U, V) pair per 2 x 2 block, no chroma interpolation.  The
 // coefficients are below 2^23 in magnitude and the samples are 9-bit, so every product is a v_mul_i32_i24 / v_mad_i32_i24
@@ -138,86 +60,111 @@ __device__ __forceinline__ Chroma yuv_chroma(int u, int v, const YuvCoef& k) {
     v -= 128;
     return Chroma{__mul24(k.cvr, v) + (1 << 19), __mul24(k.cvg, v) + __mul24(k.cug, u) + (1 << 19), __mul24(k.cub, u) + (1 << 19)};
 }
-__device__ __forceinline__ int clamp255(int v) { return min(max(v, 0), 255); }
+// clamp(v >> 20, 0, 255), written clamp first: "shift right, clamp to 0..255" of two values packed into one word is what hipcc
+// turns into v_ashr_pk_u8_i32 (DESIGN.md "Toolchain cases"; tests/test_isa_guards.py), and it did in the row conversion
+__device__ __forceinline__ int clamp_sh20(int v) { return min(max(v, 0), (256 << 20) - 1) >> 20; }
 // -> R | G << 8 | B << 16
 __device__ __forceinline__ uint32_t yuv_pixel(int yy, const Chroma& c, const YuvCoef& k) {
     // (cy is positive and below 2^23: the mask says so to the compiler, which otherwise widens this one to v_mul_lo_u32)
     const int y = (int)__umul24((uint32_t)max(yy - 16, 0), (uint32_t)k.cy & 0x7fffffu);
-    return (uint32_t)clamp255((y + c.r) >> 20) | ((uint32_t)clamp255((y + c.g) >> 20) << 8) | ((uint32_t)clamp255((y + c.b) >> 20) << 16);
+    return (uint32_t)clamp_sh20(y + c.r) | ((uint32_t)clamp_sh20(y + c.g) << 8) | ((uint32_t)clamp_sh20(y + c.b) << 16);
 }
 
-// k_undistort_rows over the slots' 4:2:0 staging frames.  LAYOUT 1: NV12 (Y plane, then rows of U,V pairs), 2: I420 (Y, U, V planes).
-// Conversion is not linear (the clamps, the shift), so each of the four taps is converted before the blend.  Per frame a thread
-// fetches, for each of the two tap rows, the 4-byte window that holds the two Y samples and the 4-byte window(s) that hold the
-// one or two chroma pairs under them -- 4 loads for NV12, 6 for I420 -- as the aligned dwordx2 around the window and one
-// v_alignbyte_b32: unconditional, on clamped addresses, through a buffer resource that covers the frames of this walk (what
-// a window reads beyond its samples is never used; beyond the last slot lies padding, and beyond that the resource returns 0).
-template <int LAYOUT>
-__global__ __launch_bounds__(256) void k_undistort_rows_yuv(const uint8_t* __restrict__ yuv, size_t yuv_stride, YuvCoef k,
-                                                           const int16_t* __restrict__ uxy,
-                                                           const uint16_t* __restrict__ ufrac, FrontEndGeom g,
-                                                           uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb,
-                                                           int remap) {
-    const uint32_t per_z = gridDim.x * gridDim.y;
-    const uint32_t id = xcd_block((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x, per_z * gridDim.z, remap);
-    const uint32_t bz = id / per_z, by = (id - bz * per_z) / gridDim.x, bx = id - bz * per_z - by * gridDim.x;
-    const int x = bx * blockDim.x + threadIdx.x;
-    const int row = by;  // relative to g.r0
-    if (x >= g.img_w) return;
-    const int z0 = bz * fpb, z1 = min(z0 + fpb, n);
-    const size_t o = (size_t)row * g.img_w + x;
-    const int sx = uxy[o * 2], sy = uxy[o * 2 + 1];
-    const int f = ufrac[o], fx = f & 31, fy = f >> 5;
-    const bool y0 = sy >= 0 && sy < g.img_h, y1 = sy + 1 >= 0 && sy + 1 < g.img_h;
-    const bool x0 = sx >= 0 && sx < g.img_w, x1 = sx + 1 >= 0 && sx + 1 < g.img_w;
-    const int cy0 = min(max(sy, 0), g.img_h - 1), cy1 = min(max(sy + 1, 0), g.img_h - 1);
-    const int cxl = min(max(sx, 0), g.img_w - 2);          // leftmost column of the windows (the width is even, so >= 2)
-    const int cx0 = min(max(sx, 0), g.img_w - 1), cx1 = min(max(sx + 1, 0), g.img_w - 1);   // both in {cxl, cxl + 1}
-    const int cb = cxl & ~1;                               // first column of the chroma pair under cxl; cxl + 1 is under cb or cb + 2
-    const int ysh0 = 8 * (cx0 - cxl), ysh1 = 8 * (cx1 - cxl);                  // the taps' Y samples inside the Y window
-    const int cs0 = (cx0 - cb) >> 1, cs1 = (cx1 - cb) >> 1;                    // the taps' pair (0 / 1) inside the chroma window
-    const uint32_t plane = (uint32_t)__mul24(g.img_h, g.img_w);
-    const uint32_t offy0 = (uint32_t)(__mul24(cy0, g.img_w) + cxl), offy1 = (uint32_t)(__mul24(cy1, g.img_w) + cxl);
-    uint32_t offc0, offc1, voff = 0;
-    if constexpr (LAYOUT == 1) {
-        offc0 = plane + (uint32_t)(__mul24(cy0 >> 1, g.img_w) + cb);
-        offc1 = plane + (uint32_t)(__mul24(cy1 >> 1, g.img_w) + cb);
+// ---- the undistortion walk --------------------------------------------------------------------------------------------------
+// One thread per undistorted pixel, walking the frames of its launch slice with one remap-table entry; the output is one RGBX
+// dword per pixel, so that the warp fetches a whole tap with a single aligned load.  undistort_walk below is the only walk: a
+// pixel FORMAT says which windows of bytes a sample needs (plane, row, byte column) and turns them into the four RGB taps, a
+// SOURCE says where the planes of frame z lie and fetches a window.  Every window is fetched unconditionally from a clamped
+// address and the taps are masked afterwards (a guarded load serialises on its own s_waitcnt).
+constexpr int RSRC_RAW = 0x00027000;   // untyped 32-bit buffer, no swizzle
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x3 __attribute__((ext_vector_type(3)));
+
+// The sizeof(W) = 4 / 8 bytes at byte `off` (+ the scalar `soff`) of a buffer: the two / three aligned dwords that hold them,
+// shifted into place with v_alignbyte_b32 -- an unaligned dwordx2 at 3-byte pitch occupies the memory pipe for ~32 cycles, an
+// aligned dwordx3 for ~20.  What a window holds beyond the samples it was fetched for is never used.
+template <class W>
+__device__ __forceinline__ W window_at(__amdgpu_buffer_rsrc_t rs, uint32_t off, int soff) {
+    if constexpr (sizeof(W) == 8) {
+        const u32x3 d = __builtin_amdgcn_raw_buffer_load_b96(rs, (int)(off & ~3u), soff, 0);
+        const uint32_t lo = __builtin_amdgcn_alignbyte(d.y, d.x, off & 3u), hi = __builtin_amdgcn_alignbyte(d.z, d.y, off & 3u);
+        return (uint64_t)lo | ((uint64_t)hi << 32);
     } else {
-        const int hw = g.img_w >> 1;
-        offc0 = plane + (uint32_t)(__mul24(cy0 >> 1, hw) + (cb >> 1));
-        offc1 = plane + (uint32_t)(__mul24(cy1 >> 1, hw) + (cb >> 1));
-        voff = plane >> 2;                                 // the V plane lies (h / 2) (w / 2) bytes behind the U plane
-    }
-    const uint32_t m00 = (y0 && x0) ? 255u : 0u, m01 = (y0 && x1) ? 255u : 0u;
-    const uint32_t m10 = (y1 && x0) ? 255u : 0u, m11 = (y1 && x1) ? 255u : 0u;
-    const uint32_t gx = 32u - (uint32_t)fx, gy = 32u - (uint32_t)fy;
-    const uint32_t w00 = (gx * gy) & 0x7ffu, w01 = ((uint32_t)fx * gy) & 0x7ffu, w10 = (gx * (uint32_t)fy) & 0x7ffu, w11 = ((uint32_t)fx * (uint32_t)fy) & 0x7ffu;
-    constexpr int RSRC_RAW = 0x00027000;   // untyped 32-bit buffer, no swizzle
-    const int nz = z1 - z0, fstride = (int)yuv_stride;
-    const __amdgpu_buffer_rsrc_t frs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(yuv + (size_t)z0 * yuv_stride), 0, nz * fstride + 16, RSRC_RAW);
-    const int pair0 = (first_slot + z0) >> 1, pair1 = (first_slot + z1 - 1) >> 1, pair_b = (int)(und_px * 8);
-    const __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc(und + (size_t)pair0 * 2 * und_px, 0, (pair1 - pair0 + 1) * pair_b, RSRC_RAW);
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-    auto window = [&](uint32_t off, int frame_off) {       // the 4 bytes at `off` of the frame at `frame_off`
-        const u32x2 d = __builtin_amdgcn_raw_buffer_load_b64(frs, (int)(off & ~3u), frame_off, 0);
+        const u32x2 d = __builtin_amdgcn_raw_buffer_load_b64(rs, (int)(off & ~3u), soff, 0);
         return __builtin_amdgcn_alignbyte(d.y, d.x, off & 3u);
-    };
+    }
+}
+
+// A plane of a frame as its format defines it; `dense` = where it starts in a slot's own (unpitched) frame.
+struct PlaneGeom { int rows, row_bytes; uint32_t dense; };
+// The clamped columns of a sample's two taps: cx0, cx1 (both in {cxl, cxl + 1}) and the leftmost column cxl of what is fetched.
+struct TapCols { int cxl, cx0, cx1; };
+
+// RGB interleaved, 3 B/px.  The two taps of a row are 6 consecutive bytes (RGB RGB) at byte 3 * cxl: one 8-byte window per tap
+// row instead of six byte loads.  When sx or sx + 1 is outside the frame the row is fetched from the clamped column and the
+// taps are masked.
+struct Rgb24 {
+    typedef uint64_t Window;
+    static constexpr int DENSE_PAD = 8;     // a slot's frame buffer is padded by 8 bytes: the window of its last pixel ends there
+    struct Taps { uint64_t a, b; };          // the windows of the upper (a) and the lower (b) tap row
+    int col, sh0, sh1;
+    __device__ __forceinline__ void place(const TapCols& c) {
+        col = c.cxl * 3;
+        sh0 = 24 * (c.cx0 - c.cxl), sh1 = 24 * (c.cx1 - c.cxl);   // column cx sits at byte 3 * (cx - cxl) of the window
+    }
+    __device__ __forceinline__ static PlaneGeom plane(const FrontEndGeom& g, int) { return PlaneGeom{g.img_h, g.img_w * 3, 0u}; }
+    template <class Source>
+    __device__ __forceinline__ Taps fetch(const Source& src, const typename Source::Frame& f, const FrontEndGeom& g, int cy0, int cy1) const {
+        const auto p0 = src.plane(f, plane(g, 0), 0);
+        return Taps{src.template window<Window>(p0, cy0, col), src.template window<Window>(p0, cy1, col)};
+    }
+    __device__ __forceinline__ void decode(const Taps& t, uint32_t& a0, uint32_t& a1, uint32_t& b0, uint32_t& b1) const {
+        a0 = (uint32_t)(t.a >> sh0), a1 = (uint32_t)(t.a >> sh1);
+        b0 = (uint32_t)(t.b >> sh0), b1 = (uint32_t)(t.b >> sh1);
+    }
+};
+
+// 4:2:0.  LAYOUT 1: NV12 (Y plane, then rows of U,V pairs), 2: I420 (Y, U, V planes).  Conversion is not linear (the clamps, the
+// shift), so each of the four taps is converted before the blend.  Per tap row: the 4-byte window that holds the two Y samples
+// and the 4-byte window(s) that hold the one or two chroma pairs under them -- 4 loads per frame for NV12, 6 for I420.
+template <int LAYOUT>
+struct Yuv420 {
+    typedef uint32_t Window;
+    static constexpr int DENSE_PAD = 16;    // a slot's staging frame: 16 bytes of padding behind the last slot
     struct Taps { uint32_t ya, yb, ca, cb, va, vb; };      // Y and chroma windows of the upper (a) and lower (b) tap row; va / vb: I420's V
-    auto fetch = [&](int frame_off) {
+    YuvCoef k;
+    int cxl, ccol, ysh0, ysh1, cs0, cs1;
+    __device__ __forceinline__ void place(const TapCols& c) {
+        cxl = c.cxl;                                       // (the width is even, so cxl >= 0)
+        const int cb = c.cxl & ~1;                         // first column of the chroma pair under cxl; cxl + 1 is under cb or cb + 2
+        ccol = LAYOUT == 1 ? cb : cb >> 1;                 // byte column of the chroma window in its plane
+        ysh0 = 8 * (c.cx0 - c.cxl), ysh1 = 8 * (c.cx1 - c.cxl);                // the taps' Y samples inside the Y window
+        cs0 = (c.cx0 - cb) >> 1, cs1 = (c.cx1 - cb) >> 1;                      // the taps' pair (0 / 1) inside the chroma window
+    }
+    __device__ __forceinline__ static PlaneGeom plane(const FrontEndGeom& g, int p) {
+        const uint32_t luma = (uint32_t)__mul24(g.img_h, g.img_w);
+        if (p == 0) return PlaneGeom{g.img_h, g.img_w, 0u};
+        // I420's V plane lies (h / 2) (w / 2) bytes behind the U plane
+        return PlaneGeom{g.img_h >> 1, LAYOUT == 1 ? g.img_w : g.img_w >> 1, p == 1 ? luma : luma + (luma >> 2)};
+    }
+    template <class Source>
+    __device__ __forceinline__ Taps fetch(const Source& src, const typename Source::Frame& f, const FrontEndGeom& g, int cy0, int cy1) const {
         Taps t;
-        t.ya = window(offy0, frame_off);
-        t.yb = window(offy1, frame_off);
-        t.ca = window(offc0, frame_off);
-        t.cb = window(offc1, frame_off);
+        const auto py = src.plane(f, plane(g, 0), 0), pc = src.plane(f, plane(g, 1), 1);
+        t.ya = src.template window<Window>(py, cy0, cxl);
+        t.yb = src.template window<Window>(py, cy1, cxl);
+        t.ca = src.template window<Window>(pc, cy0 >> 1, ccol);
+        t.cb = src.template window<Window>(pc, cy1 >> 1, ccol);
         if constexpr (LAYOUT == 2) {
-            t.va = window(offc0 + voff, frame_off);
-            t.vb = window(offc1 + voff, frame_off);
+            const auto pv = src.plane(f, plane(g, 2), 2);
+            t.va = src.template window<Window>(pv, cy0 >> 1, ccol);
+            t.vb = src.template window<Window>(pv, cy1 >> 1, ccol);
         } else {
             t.va = t.vb = 0;
         }
         return t;
-    };
-    auto tap = [&](uint32_t yw, uint32_t cw, uint32_t vw, int ysh, int cs) {
+    }
+    __device__ __forceinline__ uint32_t tap(uint32_t yw, uint32_t cw, uint32_t vw, int ysh, int cs) const {
         int u, v;
         if constexpr (LAYOUT == 1) {
             u = (int)((cw >> (16 * cs)) & 255u);
@@ -227,46 +174,213 @@ __global__ __launch_bounds__(256) void k_undistort_rows_yuv(const uint8_t* __res
             v = (int)((vw >> (8 * cs)) & 255u);
         }
         return yuv_pixel((int)((yw >> ysh) & 255u), yuv_chroma(u, v, k), k);
-    };
-    Taps q = fetch(0);
+    }
+    __device__ __forceinline__ void decode(const Taps& t, uint32_t& a0, uint32_t& a1, uint32_t& b0, uint32_t& b1) const {
+        a0 = tap(t.ya, t.ca, t.va, ysh0, cs0), a1 = tap(t.ya, t.ca, t.va, ysh1, cs1);
+        b0 = tap(t.yb, t.cb, t.vb, ysh0, cs0), b1 = tap(t.yb, t.cb, t.vb, ysh1, cs1);
+    }
+};
+
+// The slots' own frames: `stride` bytes apart, planes dense.  One buffer resource covers the frames [z0, z1) of the walk (a frame
+// is selected by the scalar offset of the load) plus the format's padding behind them; beyond that the resource returns 0.
+// 32-bit offsets (a walk stays below 2^30 bytes: launch_undistort_rows) keep the address math on full-rate 24-bit multiplies.
+// ALIGNED4 = false, for frames or strides that are not 4-byte aligned: a plain unaligned load of the window (8-byte windows only).
+template <bool ALIGNED4>
+struct SlotSource {
+    typedef int Frame;                       // byte offset of a frame behind the first of the walk
+    const uint8_t* frames;                   // frame 0 of the launch
+    size_t stride;
+    const uint8_t* base;                     // frame z0
+    int z0;
+    __amdgpu_buffer_rsrc_t rs;
+    __device__ __forceinline__ void begin(int, int z0_, int z1, int pad) {
+        base = frames + (size_t)z0_ * stride;
+        z0 = z0_;
+        rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(base), 0, (z1 - z0_) * (int)stride + pad, RSRC_RAW);
+    }
+    __device__ __forceinline__ Frame frame(int z) const { return (z - z0) * (int)stride; }
+    struct Plane { uint32_t first; int pitch; Frame f; };
+    __device__ __forceinline__ Plane plane(const Frame& f, const PlaneGeom& pg, int) const { return Plane{pg.dense, pg.row_bytes, f}; }
+    template <class W>
+    __device__ __forceinline__ W window(const Plane& pl, int row, int col) const {
+        const uint32_t off = pl.first + (uint32_t)(__mul24(row, pl.pitch) + col);
+        if constexpr (ALIGNED4) {
+            return window_at<W>(rs, off, pl.f);
+        } else {
+            struct __attribute__((packed, aligned(1))) Unaligned { W v; };
+            return reinterpret_cast<const Unaligned*>(base + (size_t)(unsigned)pl.f + off)->v;
+        }
+    }
+};
+
+// Frames that lie in the caller's device memory (lt_attach_device_frames): entry first_slot + z of the surface table (device
+// memory, SurfEntry per slot) holds the plane pointers and pitches of frame z.  z is wave-uniform, so an entry arrives by scalar
+// loads and every plane gets a buffer resource of its own in SGPRs, based at ptr & ~3 -- the remainder goes into the windows'
+// offsets, which are split into an aligned load and a v_alignbyte_b32 anyway -- and covering exactly the plane's bytes, rounded up
+// to the end of the aligned dword that holds its last byte: pitch * (rows - 1) + row bytes.  A window that overruns the plane
+// comes back as zeros from the resource's range check (raw buffers are checked dword by dword) and those bytes are never used;
+// nothing is read outside the dwords the plane occupies, so a surface may end on the last byte of its allocation.
+struct SurfPlane { __amdgpu_buffer_rsrc_t rs; int rem, pitch; };
+__device__ __forceinline__ SurfPlane surf_plane(uint64_t ptr, int pitch, int rows, int row_bytes) {
+    const int rem = (int)(ptr & 3u);
+    return SurfPlane{__builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(ptr & ~(uint64_t)3), 0,
+                                                       (rem + __mul24(pitch, rows - 1) + row_bytes + 3) & ~3, RSRC_RAW), rem, pitch};
+}
+struct SurfSource {
+    typedef SurfEntry Frame;
+    const SurfEntry* tab;
+    const SurfEntry* ent;                    // entry of frame 0 of the launch
+    __device__ __forceinline__ void begin(int first_slot, int, int, int) { ent = tab + first_slot; }
+    __device__ __forceinline__ Frame frame(int z) const { return ent[z]; }
+    typedef SurfPlane Plane;
+    __device__ __forceinline__ Plane plane(const Frame& e, const PlaneGeom& pg, int p) const {
+        return surf_plane(e.plane[p], p == 0 ? e.pitch : e.cpitch, pg.rows, pg.row_bytes);
+    }
+    // pitch and remainder are the frame's, so the offset is too
+    template <class W>
+    __device__ __forceinline__ W window(const Plane& pl, int row, int col) const {
+        return window_at<W>(pl.rs, (uint32_t)(__mul24(row, pl.pitch) + col + pl.rem), 0);
+    }
+};
+
+// What the kernels below hand to the walk besides their source and format.
+struct WalkArgs {
+    const int16_t* uxy;
+    const uint16_t* ufrac;
+    FrontEndGeom g;
+    uint32_t* und;
+    size_t und_px;
+    int first_slot, n, fpb, remap;
+};
+
+template <class Source, class Format>
+__device__ __forceinline__ void undistort_walk(const WalkArgs& a, Source src, Format fmt) {
+    const FrontEndGeom& g = a.g;
+    const uint32_t per_z = gridDim.x * gridDim.y;
+    const uint32_t id = xcd_block((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x, per_z * gridDim.z, a.remap);
+    const uint32_t bz = id / per_z, by = (id - bz * per_z) / gridDim.x, bx = id - bz * per_z - by * gridDim.x;
+    // (blockDim.x of a __global__ function: written as blockDim.x here, in a device function, it is lowered through the generic
+    // work-group-size path -- a third v_mul_lo_u32 and a global_load_ushort in the prologue)
+    const int x = bx * __builtin_amdgcn_workgroup_size_x() + threadIdx.x;
+    const int row = by;  // relative to g.r0
+    if (x >= g.img_w) return;
+    const int z0 = bz * a.fpb, z1 = min(z0 + a.fpb, a.n);   // fpb frames per thread: table entry and offsets are frame-independent
+    const size_t o = (size_t)row * g.img_w + x;
+    const int sx = a.uxy[o * 2], sy = a.uxy[o * 2 + 1];
+    const int f = a.ufrac[o], fx = f & 31, fy = f >> 5;
+    const bool y0 = sy >= 0 && sy < g.img_h, y1 = sy + 1 >= 0 && sy + 1 < g.img_h;
+    const bool x0 = sx >= 0 && sx < g.img_w, x1 = sx + 1 >= 0 && sx + 1 < g.img_w;
+    const int cy0 = min(max(sy, 0), g.img_h - 1), cy1 = min(max(sy + 1, 0), g.img_h - 1);
+    const TapCols cols{min(max(sx, 0), g.img_w - 2), min(max(sx, 0), g.img_w - 1), min(max(sx + 1, 0), g.img_w - 1)};
+    fmt.place(cols);
+    const uint32_t m00 = (y0 && x0) ? 255u : 0u, m01 = (y0 && x1) ? 255u : 0u;
+    const uint32_t m10 = (y1 && x0) ? 255u : 0u, m11 = (y1 && x1) ? 255u : 0u;
+    const uint32_t gx = 32u - (uint32_t)fx, gy = 32u - (uint32_t)fy;
+    const uint32_t w00 = (gx * gy) & 0x7ffu, w01 = ((uint32_t)fx * gy) & 0x7ffu, w10 = (gx * (uint32_t)fy) & 0x7ffu, w11 = ((uint32_t)fx * (uint32_t)fy) & 0x7ffu;
+    // the slots this thread writes: pairs [pair0, pair1] of the interleaved buffer
+    const int pair0 = (a.first_slot + z0) >> 1, pair1 = (a.first_slot + z1 - 1) >> 1, pair_b = (int)(a.und_px * 8);
+    const __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc(a.und + (size_t)pair0 * 2 * a.und_px, 0, (pair1 - pair0 + 1) * pair_b, RSRC_RAW);
+    src.begin(a.first_slot, z0, z1, Format::DENSE_PAD);
+    auto fr = src.frame(z0);
+    auto q = fmt.fetch(src, fr, g, cy0, cy1);
+    fr = src.frame(min(z0 + 1, z1 - 1));
     for (int z = z0; z < z1; ++z) {
-        // the next frame's taps are in flight while this one is converted and blended
-        const Taps nq = fetch((min(z + 1, z1 - 1) - z0) * fstride);
-        const uint32_t a0 = tap(q.ya, q.ca, q.va, ysh0, cs0), a1 = tap(q.ya, q.ca, q.va, ysh1, cs1);
-        const uint32_t b0 = tap(q.yb, q.cb, q.vb, ysh0, cs0), b1 = tap(q.yb, q.cb, q.vb, ysh1, cs1);
+        // the next frame's windows are in flight while this one is (converted and) blended, and the frame after it is being located
+        // (surfaces: its entry is on its way)
+        const auto nq = fmt.fetch(src, fr, g, cy0, cy1);
+        fr = src.frame(min(z + 2, z1 - 1));
+        uint32_t a0, a1, b0, b1;
+        fmt.decode(q, a0, a1, b0, b1);
         uint32_t out = 0;
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
             const uint32_t v00 = (a0 >> (8 * ch)) & m00, v01 = (a1 >> (8 * ch)) & m01;
             const uint32_t v10 = (b0 >> (8 * ch)) & m10, v11 = (b1 >> (8 * ch)) & m11;
-            out |= ((v00 * w00 + v01 * w01 + v10 * w10 + v11 * w11 + 512u) >> 10) << (8 * ch);   // k_undistort_rows' blend
+            // (sum_i w_i p_i + 2^9) >> 10: the same integer as bilerp(); with the 11-bit weights visible every product is a
+            // v_mul_u32_u24 / v_mad_u32_u24 (the two-stage form was re-associated into quarter-rate 32- and 64-bit multiplies)
+            out |= ((v00 * w00 + v01 * w01 + v10 * w10 + v11 * w11 + 512u) >> 10) << (8 * ch);
+            // Opaque to the optimiser, free at run time: it keeps the third channel from being re-associated into the OR of the
+            // first two (which happens once this unrolled loop is inlined into a kernel), after which the two v_and_or_b32 of the
+            // packing are selected as two v_and_b32 + a v_or3_b32 -- one VALU instruction more per frame, two more VGPRs in the
+            // 4:2:0 surface walks.
+            if (ch == 1) asm("" : "+v"(out));
         }
-        const int slot = first_slot + z;   // wave-uniform: pair and parity go into the scalar offset of the store
+        const int slot = a.first_slot + z;   // wave-uniform: pair and parity go into the scalar offset of the store
         __builtin_amdgcn_raw_buffer_store_b32(out, urs, (int)o * 8, __builtin_amdgcn_readfirstlane(((slot >> 1) - pair0) * pair_b + (slot & 1) * 4), 0);
         q = nq;
     }
 }
 
-// Rows [r0, r1) of 4:2:0 frames -> the same rows of RGB frames (3 B/px): a streaming kernel for whoever shows the camera frame.
-// One thread owns the two rows of a chroma row over 16 columns: 16 Y bytes per row and the 8 (U, V) pairs under them in
-// 16-byte loads, each pair's three chroma terms computed once for its four pixels, 48 bytes per row in three 16-byte stores.
-// Either row of the pair may lie outside [r0, r1) (block-uniform) and is then neither read nor written.
+// The entry points: source x format.  (Their names and parameter lists are what the profiles and tools know them by.)
+template <bool ALIGNED4>
+__global__ __launch_bounds__(256) void k_undistort_rows(const uint8_t* __restrict__ frames, size_t frame_stride,
+                                                       const int16_t* __restrict__ uxy,
+                                                       const uint16_t* __restrict__ ufrac, FrontEndGeom g,
+                                                       uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb,
+                                                       int remap) {
+    undistort_walk(WalkArgs{uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap},
+                   SlotSource<ALIGNED4>{frames, frame_stride}, Rgb24{});
+}
+
 template <int LAYOUT>
-__global__ __launch_bounds__(256) void k_yuv_rows_to_rgb(const uint8_t* __restrict__ yuv, size_t yuv_stride, YuvCoef k,
-                                                        uint8_t* __restrict__ rgb, size_t rgb_stride, int h, int w, int r0, int r1) {
-    const int x0 = (int)(blockIdx.x * blockDim.x + threadIdx.x) * 16;
-    if (x0 >= w) return;
-    const int cr = (r0 >> 1) + (int)blockIdx.y;            // chroma row
-    const uint8_t* src = yuv + (size_t)blockIdx.z * yuv_stride;
-    uint8_t* dst = rgb + (size_t)blockIdx.z * rgb_stride;
+__global__ __launch_bounds__(256) void k_undistort_rows_yuv(const uint8_t* __restrict__ yuv, size_t yuv_stride, YuvCoef k,
+                                                           const int16_t* __restrict__ uxy,
+                                                           const uint16_t* __restrict__ ufrac, FrontEndGeom g,
+                                                           uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb,
+                                                           int remap) {
+    undistort_walk(WalkArgs{uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap},
+                   SlotSource<true>{yuv, yuv_stride}, Yuv420<LAYOUT>{k});
+}
+
+__global__ __launch_bounds__(256) void k_undistort_rows_surf(const SurfEntry* __restrict__ tab,
+                                                            const int16_t* __restrict__ uxy,
+                                                            const uint16_t* __restrict__ ufrac, FrontEndGeom g,
+                                                            uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb,
+                                                            int remap) {
+    undistort_walk(WalkArgs{uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap},
+                   SurfSource{tab}, Rgb24{});
+}
+
+template <int LAYOUT>
+__global__ __launch_bounds__(256) void k_undistort_rows_yuv_surf(const SurfEntry* __restrict__ tab, YuvCoef k,
+                                                                const int16_t* __restrict__ uxy,
+                                                                const uint16_t* __restrict__ ufrac, FrontEndGeom g,
+                                                                uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb,
+                                                                int remap) {
+    undistort_walk(WalkArgs{uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap},
+                   SurfSource{tab}, Yuv420<LAYOUT>{k});
+}
+
+// ---- 4:2:0 rows -> RGB rows ---------------------------------------------------------------------------------------------------
+// Rows [r0, r1) of 4:2:0 frames -> the same rows of RGB frames (3 B/px): a streaming kernel for whoever shows the camera frame.
+// The planes of one frame: the dense entry points compute them from the frame's base, the surface ones read them from the entry.
+struct YuvPlanes {
+    const uint8_t *y, *u, *v;                // u: NV12's plane of (U, V) pairs; v: I420 only
+    int pitch, cpitch;
+};
+template <int LAYOUT>
+__device__ __forceinline__ YuvPlanes dense_planes(const uint8_t* frame, int h, int w) {
     const size_t plane = (size_t)h * w;
+    return YuvPlanes{frame, frame + plane, frame + plane + (plane >> 2), w, LAYOUT == 1 ? w : w >> 1};
+}
+__device__ __forceinline__ YuvPlanes surf_planes(const SurfEntry& e) {
+    return YuvPlanes{reinterpret_cast<const uint8_t*>(e.plane[0]), reinterpret_cast<const uint8_t*>(e.plane[1]),
+                     reinterpret_cast<const uint8_t*>(e.plane[2]), e.pitch, e.cpitch};
+}
+
+// One thread owns the two rows of chroma row `cr` over the 16 columns from x0: 16 Y bytes per row and the 8 (U, V) pairs under
+// them in 16-byte loads, each pair's three chroma terms computed once for its four pixels, 48 bytes per row in three 16-byte
+// stores.  Either row of the pair may lie outside [r0, r1) (block-uniform) and is then neither read nor written.
+template <int LAYOUT>
+__device__ __forceinline__ void yuv_rows16(const YuvPlanes& p, YuvCoef k, uint8_t* dst, int w, int r0, int r1, int x0, int cr) {
+    if (x0 >= w) return;
     uint32_t uv[4];                                        // NV12: 8 (U, V) pairs; I420: uv[0..1] 8 U, uv[2..3] 8 V
     if constexpr (LAYOUT == 1) {
-        const uint4 c = *reinterpret_cast<const uint4*>(src + plane + (size_t)cr * w + x0);
+        const uint4 c = *reinterpret_cast<const uint4*>(p.u + (size_t)cr * p.cpitch + x0);
         uv[0] = c.x; uv[1] = c.y; uv[2] = c.z; uv[3] = c.w;
     } else {
-        const size_t co = plane + (size_t)cr * (w >> 1) + (x0 >> 1);
-        const uint2 cu = *reinterpret_cast<const uint2*>(src + co), cv = *reinterpret_cast<const uint2*>(src + co + (plane >> 2));
+        const size_t co = (size_t)cr * p.cpitch + (x0 >> 1);
+        const uint2 cu = *reinterpret_cast<const uint2*>(p.u + co), cv = *reinterpret_cast<const uint2*>(p.v + co);
         uv[0] = cu.x; uv[1] = cu.y; uv[2] = cv.x; uv[3] = cv.y;
     }
     Chroma c[8];
@@ -286,17 +400,17 @@ __global__ __launch_bounds__(256) void k_yuv_rows_to_rgb(const uint8_t* __restri
     for (int dy = 0; dy < 2; ++dy) {
         const int y = 2 * cr + dy;
         if (y < r0 || y >= r1) continue;
-        const uint4 yq = *reinterpret_cast<const uint4*>(src + (size_t)y * w + x0);
+        const uint4 yq = *reinterpret_cast<const uint4*>(p.y + (size_t)y * p.pitch + x0);
         const uint32_t yw[4] = {yq.x, yq.y, yq.z, yq.w};
         uint32_t d[12];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {                      // four pixels (two chroma pairs) -> three dwords
-            uint32_t p[4];
+            uint32_t px[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) p[i] = yuv_pixel((int)((yw[j] >> (8 * i)) & 255u), c[2 * j + (i >> 1)], k);
-            d[3 * j] = p[0] | (p[1] << 24);
-            d[3 * j + 1] = (p[1] >> 8) | (p[2] << 16);
-            d[3 * j + 2] = (p[2] >> 16) | (p[3] << 8);
+            for (int i = 0; i < 4; ++i) px[i] = yuv_pixel((int)((yw[j] >> (8 * i)) & 255u), c[2 * j + (i >> 1)], k);
+            d[3 * j] = px[0] | (px[1] << 24);
+            d[3 * j + 1] = (px[1] >> 8) | (px[2] << 16);
+            d[3 * j + 2] = (px[2] >> 16) | (px[3] << 8);
         }
         uint4* o = reinterpret_cast<uint4*>(dst + ((size_t)y * w + x0) * 3);
         o[0] = make_uint4(d[0], d[1], d[2], d[3]);
@@ -305,205 +419,44 @@ __global__ __launch_bounds__(256) void k_yuv_rows_to_rgb(const uint8_t* __restri
     }
 }
 
-// the same for any even width and any alignment: one thread per 2 x 2 block, byte accesses
+// the same for any even width, any pitch and any alignment: one thread per 2 x 2 block (block column bx), byte accesses
 template <int LAYOUT>
-__global__ __launch_bounds__(256) void k_yuv_rows_to_rgb_any(const uint8_t* __restrict__ yuv, size_t yuv_stride, YuvCoef k,
-                                                            uint8_t* __restrict__ rgb, size_t rgb_stride, int h, int w, int r0, int r1) {
-    const int bx = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+__device__ __forceinline__ void yuv_rows2x2(const YuvPlanes& p, YuvCoef k, uint8_t* dst, int w, int r0, int r1, int bx, int cr) {
     if (2 * bx >= w) return;
-    const int cr = (r0 >> 1) + (int)blockIdx.y;
-    const uint8_t* src = yuv + (size_t)blockIdx.z * yuv_stride;
-    uint8_t* dst = rgb + (size_t)blockIdx.z * rgb_stride;
-    const size_t plane = (size_t)h * w;
     int u, v;
     if constexpr (LAYOUT == 1) {
-        u = src[plane + (size_t)cr * w + 2 * bx];
-        v = src[plane + (size_t)cr * w + 2 * bx + 1];
+        u = p.u[(size_t)cr * p.cpitch + 2 * bx];
+        v = p.u[(size_t)cr * p.cpitch + 2 * bx + 1];
     } else {
-        u = src[plane + (size_t)cr * (w >> 1) + bx];
-        v = src[plane + (plane >> 2) + (size_t)cr * (w >> 1) + bx];
+        u = p.u[(size_t)cr * p.cpitch + bx];
+        v = p.v[(size_t)cr * p.cpitch + bx];
     }
     const Chroma c = yuv_chroma(u, v, k);
     for (int dy = 0; dy < 2; ++dy) {
         const int y = 2 * cr + dy;
         if (y < r0 || y >= r1) continue;
         for (int dx = 0; dx < 2; ++dx) {
+            const uint32_t px = yuv_pixel(p.y[(size_t)y * p.pitch + 2 * bx + dx], c, k);
             const size_t o = (size_t)y * w + 2 * bx + dx;
-            const uint32_t p = yuv_pixel(src[o], c, k);
-            dst[o * 3] = (uint8_t)p;
-            dst[o * 3 + 1] = (uint8_t)(p >> 8);
-            dst[o * 3 + 2] = (uint8_t)(p >> 16);
+            dst[o * 3] = (uint8_t)px;
+            dst[o * 3 + 1] = (uint8_t)(px >> 8);
+            dst[o * 3 + 2] = (uint8_t)(px >> 16);
         }
     }
 }
 
-// ---- frames that lie in the caller's device memory (lt_attach_device_frames) ---------------------------------------------------
-// The same two walks with the taps fetched from the caller's surfaces: entry first_slot + z of the surface table (device memory,
-// SurfEntry per slot) holds the plane pointers and pitches of frame z.  z is wave-uniform, so an entry arrives by scalar loads and
-// every plane gets a buffer resource of its own in SGPRs, based at ptr & ~3 -- the remainder goes into the windows' offsets, which
-// are split into an aligned load and a v_alignbyte_b32 anyway -- and covering exactly the plane's bytes, rounded up to the end of
-// the aligned dword that holds its last byte: pitch * (rows - 1) + row bytes.  A window that overruns the plane comes back as
-// zeros from the resource's range check (raw buffers are checked dword by dword) and those bytes are never used; nothing is read
-// outside the dwords the plane occupies, so a surface may end on the last byte of its allocation.  The entry of frame z + 2 is
-// requested while the windows of frame z + 1 are in flight and frame z is blended.
-constexpr int SURF_RSRC_RAW = 0x00027000;   // untyped 32-bit buffer, no swizzle
-struct SurfPlane { __amdgpu_buffer_rsrc_t rs; int rem; };
-__device__ __forceinline__ SurfPlane surf_plane(uint64_t ptr, int pitch, int rows, int row_bytes) {
-    const int rem = (int)(ptr & 3u);
-    return SurfPlane{__builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(ptr & ~(uint64_t)3), 0,
-                                                       (rem + __mul24(pitch, rows - 1) + row_bytes + 3) & ~3, SURF_RSRC_RAW), rem};
-}
-
-__global__ __launch_bounds__(256) void k_undistort_rows_surf(const SurfEntry* __restrict__ tab,
-                                                            const int16_t* __restrict__ uxy,
-                                                            const uint16_t* __restrict__ ufrac, FrontEndGeom g,
-                                                            uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb,
-                                                            int remap) {
-    const uint32_t per_z = gridDim.x * gridDim.y;
-    const uint32_t id = xcd_block((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x, per_z * gridDim.z, remap);
-    const uint32_t bz = id / per_z, by = (id - bz * per_z) / gridDim.x, bx = id - bz * per_z - by * gridDim.x;
-    const int x = bx * blockDim.x + threadIdx.x;
-    const int row = by;  // relative to g.r0
-    if (x >= g.img_w) return;
-    const int z0 = bz * fpb, z1 = min(z0 + fpb, n);
-    const size_t o = (size_t)row * g.img_w + x;
-    const int sx = uxy[o * 2], sy = uxy[o * 2 + 1];
-    const int f = ufrac[o], fx = f & 31, fy = f >> 5;
-    const bool y0 = sy >= 0 && sy < g.img_h, y1 = sy + 1 >= 0 && sy + 1 < g.img_h;
-    const bool x0 = sx >= 0 && sx < g.img_w, x1 = sx + 1 >= 0 && sx + 1 < g.img_w;
-    const int cy0 = min(max(sy, 0), g.img_h - 1), cy1 = min(max(sy + 1, 0), g.img_h - 1);
-    const int cxl = min(max(sx, 0), g.img_w - 2);          // leftmost column of the 6-byte window we fetch
-    const int cx3 = cxl * 3;
-    const int sh0 = 24 * (min(max(sx, 0), g.img_w - 1) - cxl), sh1 = 24 * (min(max(sx + 1, 0), g.img_w - 1) - cxl);
-    const uint32_t m00 = (y0 && x0) ? 255u : 0u, m01 = (y0 && x1) ? 255u : 0u;
-    const uint32_t m10 = (y1 && x0) ? 255u : 0u, m11 = (y1 && x1) ? 255u : 0u;
-    const uint32_t gx = 32u - (uint32_t)fx, gy = 32u - (uint32_t)fy;
-    const uint32_t w00 = (gx * gy) & 0x7ffu, w01 = ((uint32_t)fx * gy) & 0x7ffu, w10 = (gx * (uint32_t)fy) & 0x7ffu, w11 = ((uint32_t)fx * (uint32_t)fy) & 0x7ffu;
-    const int pair0 = (first_slot + z0) >> 1, pair1 = (first_slot + z1 - 1) >> 1, pair_b = (int)(und_px * 8);
-    const __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc(und + (size_t)pair0 * 2 * und_px, 0, (pair1 - pair0 + 1) * pair_b, SURF_RSRC_RAW);
-    typedef unsigned u32x3 __attribute__((ext_vector_type(3)));
-    const int row_bytes = g.img_w * 3;
-    // the 8 bytes at (row cy, column cxl) of the frame of entry e: pitch and remainder are the frame's, so the offset is too
-    auto window = [&](const SurfEntry& e, int cy) {
-        const SurfPlane p = surf_plane(e.plane[0], e.pitch, g.img_h, row_bytes);
-        const uint32_t off = (uint32_t)(__mul24(cy, e.pitch) + cx3 + p.rem);
-        const u32x3 d = __builtin_amdgcn_raw_buffer_load_b96(p.rs, (int)(off & ~3u), 0, 0);
-        const uint32_t lo = __builtin_amdgcn_alignbyte(d.y, d.x, off & 3u), hi = __builtin_amdgcn_alignbyte(d.z, d.y, off & 3u);
-        return (uint64_t)lo | ((uint64_t)hi << 32);
-    };
-    const SurfEntry* ent = tab + first_slot;
-    SurfEntry e1 = ent[z0];
-    uint64_t q0 = window(e1, cy0), q1 = window(e1, cy1);
-    e1 = ent[min(z0 + 1, z1 - 1)];
-    for (int z = z0; z < z1; ++z) {
-        // the next frame's taps are in flight while this one is blended, and the entry of the frame after it is on its way
-        const uint64_t n0 = window(e1, cy0), n1 = window(e1, cy1);
-        e1 = ent[min(z + 2, z1 - 1)];
-        const uint32_t a0 = (uint32_t)(q0 >> sh0), a1 = (uint32_t)(q0 >> sh1);
-        const uint32_t b0 = (uint32_t)(q1 >> sh0), b1 = (uint32_t)(q1 >> sh1);
-        uint32_t out = 0;
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-            const uint32_t v00 = (a0 >> (8 * ch)) & m00, v01 = (a1 >> (8 * ch)) & m01;
-            const uint32_t v10 = (b0 >> (8 * ch)) & m10, v11 = (b1 >> (8 * ch)) & m11;
-            out |= ((v00 * w00 + v01 * w01 + v10 * w10 + v11 * w11 + 512u) >> 10) << (8 * ch);   // k_undistort_rows' blend
-        }
-        const int slot = first_slot + z;   // wave-uniform: pair and parity go into the scalar offset of the store
-        __builtin_amdgcn_raw_buffer_store_b32(out, urs, (int)o * 8, __builtin_amdgcn_readfirstlane(((slot >> 1) - pair0) * pair_b + (slot & 1) * 4), 0);
-        q0 = n0;
-        q1 = n1;
-    }
-}
-
+// The slots' dense staging frames (frame blockIdx.z at yuv + blockIdx.z * yuv_stride) ...
 template <int LAYOUT>
-__global__ __launch_bounds__(256) void k_undistort_rows_yuv_surf(const SurfEntry* __restrict__ tab, YuvCoef k,
-                                                                const int16_t* __restrict__ uxy,
-                                                                const uint16_t* __restrict__ ufrac, FrontEndGeom g,
-                                                                uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb,
-                                                                int remap) {
-    const uint32_t per_z = gridDim.x * gridDim.y;
-    const uint32_t id = xcd_block((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x, per_z * gridDim.z, remap);
-    const uint32_t bz = id / per_z, by = (id - bz * per_z) / gridDim.x, bx = id - bz * per_z - by * gridDim.x;
-    const int x = bx * blockDim.x + threadIdx.x;
-    const int row = by;  // relative to g.r0
-    if (x >= g.img_w) return;
-    const int z0 = bz * fpb, z1 = min(z0 + fpb, n);
-    const size_t o = (size_t)row * g.img_w + x;
-    const int sx = uxy[o * 2], sy = uxy[o * 2 + 1];
-    const int f = ufrac[o], fx = f & 31, fy = f >> 5;
-    const bool y0 = sy >= 0 && sy < g.img_h, y1 = sy + 1 >= 0 && sy + 1 < g.img_h;
-    const bool x0 = sx >= 0 && sx < g.img_w, x1 = sx + 1 >= 0 && sx + 1 < g.img_w;
-    const int cy0 = min(max(sy, 0), g.img_h - 1), cy1 = min(max(sy + 1, 0), g.img_h - 1);
-    const int cxl = min(max(sx, 0), g.img_w - 2);          // leftmost column of the windows (the width is even, so >= 2)
-    const int cx0 = min(max(sx, 0), g.img_w - 1), cx1 = min(max(sx + 1, 0), g.img_w - 1);   // both in {cxl, cxl + 1}
-    const int cb = cxl & ~1;                               // first column of the chroma pair under cxl; cxl + 1 is under cb or cb + 2
-    const int ysh0 = 8 * (cx0 - cxl), ysh1 = 8 * (cx1 - cxl);                  // the taps' Y samples inside the Y window
-    const int cs0 = (cx0 - cb) >> 1, cs1 = (cx1 - cb) >> 1;                    // the taps' pair (0 / 1) inside the chroma window
-    const int ccol = LAYOUT == 1 ? cb : cb >> 1;           // byte column of the chroma window in its plane
-    const uint32_t m00 = (y0 && x0) ? 255u : 0u, m01 = (y0 && x1) ? 255u : 0u;
-    const uint32_t m10 = (y1 && x0) ? 255u : 0u, m11 = (y1 && x1) ? 255u : 0u;
-    const uint32_t gx = 32u - (uint32_t)fx, gy = 32u - (uint32_t)fy;
-    const uint32_t w00 = (gx * gy) & 0x7ffu, w01 = ((uint32_t)fx * gy) & 0x7ffu, w10 = (gx * (uint32_t)fy) & 0x7ffu, w11 = ((uint32_t)fx * (uint32_t)fy) & 0x7ffu;
-    const int pair0 = (first_slot + z0) >> 1, pair1 = (first_slot + z1 - 1) >> 1, pair_b = (int)(und_px * 8);
-    const __amdgpu_buffer_rsrc_t urs = __builtin_amdgcn_make_buffer_rsrc(und + (size_t)pair0 * 2 * und_px, 0, (pair1 - pair0 + 1) * pair_b, SURF_RSRC_RAW);
-    typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-    auto window = [&](const SurfPlane& p, int off) {       // the 4 bytes at `off` of the plane (+ its remainder)
-        const uint32_t a = (uint32_t)(off + p.rem);
-        const u32x2 d = __builtin_amdgcn_raw_buffer_load_b64(p.rs, (int)(a & ~3u), 0, 0);
-        return __builtin_amdgcn_alignbyte(d.y, d.x, a & 3u);
-    };
-    struct Taps { uint32_t ya, yb, ca, cb, va, vb; };      // Y and chroma windows of the upper (a) and lower (b) tap row; va / vb: I420's V
-    const int crows = g.img_h >> 1, cbytes = LAYOUT == 1 ? g.img_w : g.img_w >> 1;
-    auto fetch = [&](const SurfEntry& e) {
-        Taps t;
-        const SurfPlane py = surf_plane(e.plane[0], e.pitch, g.img_h, g.img_w);
-        const SurfPlane pc = surf_plane(e.plane[1], e.cpitch, crows, cbytes);
-        const int oc0 = __mul24(cy0 >> 1, e.cpitch) + ccol, oc1 = __mul24(cy1 >> 1, e.cpitch) + ccol;
-        t.ya = window(py, __mul24(cy0, e.pitch) + cxl);
-        t.yb = window(py, __mul24(cy1, e.pitch) + cxl);
-        t.ca = window(pc, oc0);
-        t.cb = window(pc, oc1);
-        if constexpr (LAYOUT == 2) {
-            const SurfPlane pv = surf_plane(e.plane[2], e.cpitch, crows, cbytes);
-            t.va = window(pv, oc0);
-            t.vb = window(pv, oc1);
-        } else {
-            t.va = t.vb = 0;
-        }
-        return t;
-    };
-    auto tap = [&](uint32_t yw, uint32_t cw, uint32_t vw, int ysh, int cs) {
-        int u, v;
-        if constexpr (LAYOUT == 1) {
-            u = (int)((cw >> (16 * cs)) & 255u);
-            v = (int)((cw >> (16 * cs + 8)) & 255u);
-        } else {
-            u = (int)((cw >> (8 * cs)) & 255u);
-            v = (int)((vw >> (8 * cs)) & 255u);
-        }
-        return yuv_pixel((int)((yw >> ysh) & 255u), yuv_chroma(u, v, k), k);
-    };
-    const SurfEntry* ent = tab + first_slot;
-    SurfEntry e1 = ent[z0];
-    Taps q = fetch(e1);
-    e1 = ent[min(z0 + 1, z1 - 1)];
-    for (int z = z0; z < z1; ++z) {
-        // the next frame's taps are in flight while this one is converted and blended, and the entry of the frame after it is on its way
-        const Taps nq = fetch(e1);
-        e1 = ent[min(z + 2, z1 - 1)];
-        const uint32_t a0 = tap(q.ya, q.ca, q.va, ysh0, cs0), a1 = tap(q.ya, q.ca, q.va, ysh1, cs1);
-        const uint32_t b0 = tap(q.yb, q.cb, q.vb, ysh0, cs0), b1 = tap(q.yb, q.cb, q.vb, ysh1, cs1);
-        uint32_t out = 0;
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) {
-            const uint32_t v00 = (a0 >> (8 * ch)) & m00, v01 = (a1 >> (8 * ch)) & m01;
-            const uint32_t v10 = (b0 >> (8 * ch)) & m10, v11 = (b1 >> (8 * ch)) & m11;
-            out |= ((v00 * w00 + v01 * w01 + v10 * w10 + v11 * w11 + 512u) >> 10) << (8 * ch);   // k_undistort_rows' blend
-        }
-        const int slot = first_slot + z;   // wave-uniform: pair and parity go into the scalar offset of the store
-        __builtin_amdgcn_raw_buffer_store_b32(out, urs, (int)o * 8, __builtin_amdgcn_readfirstlane(((slot >> 1) - pair0) * pair_b + (slot & 1) * 4), 0);
-        q = nq;
-    }
+__global__ __launch_bounds__(256) void k_yuv_rows_to_rgb(const uint8_t* __restrict__ yuv, size_t yuv_stride, YuvCoef k,
+                                                        uint8_t* __restrict__ rgb, size_t rgb_stride, int h, int w, int r0, int r1) {
+    yuv_rows16<LAYOUT>(dense_planes<LAYOUT>(yuv + (size_t)blockIdx.z * yuv_stride, h, w), k, rgb + (size_t)blockIdx.z * rgb_stride, w, r0, r1,
+                       (int)(blockIdx.x * blockDim.x + threadIdx.x) * 16, (r0 >> 1) + (int)blockIdx.y);
+}
+template <int LAYOUT>
+__global__ __launch_bounds__(256) void k_yuv_rows_to_rgb_any(const uint8_t* __restrict__ yuv, size_t yuv_stride, YuvCoef k,
+                                                            uint8_t* __restrict__ rgb, size_t rgb_stride, int h, int w, int r0, int r1) {
+    yuv_rows2x2<LAYOUT>(dense_planes<LAYOUT>(yuv + (size_t)blockIdx.z * yuv_stride, h, w), k, rgb + (size_t)blockIdx.z * rgb_stride, w, r0, r1,
+                        (int)(blockIdx.x * blockDim.x + threadIdx.x), (r0 >> 1) + (int)blockIdx.y);
 }
 
 // Entries into the surface table, as a kernel argument (no host memory has to outlive the call): entry i -> tab[first + i].
@@ -514,93 +467,17 @@ __global__ __launch_bounds__(64) void k_write_surf_entries(SurfEntry* __restrict
     tab[first + i] = e;
 }
 
-// Rows [r0, r1) of 4:2:0 surfaces -> the same rows of the slots' RGB camera frames: k_yuv_rows_to_rgb with plane pointers and pitches.
-// The surfaces of the launch travel as a kernel argument (frame blockIdx.z is entry blockIdx.z of the chunk).
+// ... and 4:2:0 surfaces -> the slots' RGB camera frames.  The surfaces of the launch travel as a kernel argument (frame blockIdx.z
+// is entry blockIdx.z of the chunk).
 template <int LAYOUT>
 __global__ __launch_bounds__(256) void k_surf_rows_to_rgb(SurfChunk ch, YuvCoef k, uint8_t* __restrict__ rgb, size_t rgb_stride, int w, int r0, int r1) {
-    const int x0 = (int)(blockIdx.x * blockDim.x + threadIdx.x) * 16;
-    if (x0 >= w) return;
-    const int cr = (r0 >> 1) + (int)blockIdx.y;            // chroma row
-    const SurfEntry& e = ch.e[blockIdx.z];
-    const uint8_t* py = reinterpret_cast<const uint8_t*>(e.plane[0]);
-    const uint8_t* pu = reinterpret_cast<const uint8_t*>(e.plane[1]);
-    uint8_t* dst = rgb + (size_t)blockIdx.z * rgb_stride;
-    uint32_t uv[4];                                        // NV12: 8 (U, V) pairs; I420: uv[0..1] 8 U, uv[2..3] 8 V
-    if constexpr (LAYOUT == 1) {
-        const uint4 c = *reinterpret_cast<const uint4*>(pu + (size_t)cr * e.cpitch + x0);
-        uv[0] = c.x; uv[1] = c.y; uv[2] = c.z; uv[3] = c.w;
-    } else {
-        const uint8_t* pv = reinterpret_cast<const uint8_t*>(e.plane[2]);
-        const size_t co = (size_t)cr * e.cpitch + (x0 >> 1);
-        const uint2 cu = *reinterpret_cast<const uint2*>(pu + co), cv = *reinterpret_cast<const uint2*>(pv + co);
-        uv[0] = cu.x; uv[1] = cu.y; uv[2] = cv.x; uv[3] = cv.y;
-    }
-    Chroma c[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        int u, v;
-        if constexpr (LAYOUT == 1) {
-            u = (int)((uv[i >> 1] >> (16 * (i & 1))) & 255u);
-            v = (int)((uv[i >> 1] >> (16 * (i & 1) + 8)) & 255u);
-        } else {
-            u = (int)((uv[i >> 2] >> (8 * (i & 3))) & 255u);
-            v = (int)((uv[2 + (i >> 2)] >> (8 * (i & 3))) & 255u);
-        }
-        c[i] = yuv_chroma(u, v, k);
-    }
-#pragma unroll
-    for (int dy = 0; dy < 2; ++dy) {
-        const int y = 2 * cr + dy;
-        if (y < r0 || y >= r1) continue;
-        const uint4 yq = *reinterpret_cast<const uint4*>(py + (size_t)y * e.pitch + x0);
-        const uint32_t yw[4] = {yq.x, yq.y, yq.z, yq.w};
-        uint32_t d[12];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {                      // four pixels (two chroma pairs) -> three dwords
-            uint32_t p[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) p[i] = yuv_pixel((int)((yw[j] >> (8 * i)) & 255u), c[2 * j + (i >> 1)], k);
-            d[3 * j] = p[0] | (p[1] << 24);
-            d[3 * j + 1] = (p[1] >> 8) | (p[2] << 16);
-            d[3 * j + 2] = (p[2] >> 16) | (p[3] << 8);
-        }
-        uint4* o = reinterpret_cast<uint4*>(dst + ((size_t)y * w + x0) * 3);
-        o[0] = make_uint4(d[0], d[1], d[2], d[3]);
-        o[1] = make_uint4(d[4], d[5], d[6], d[7]);
-        o[2] = make_uint4(d[8], d[9], d[10], d[11]);
-    }
+    yuv_rows16<LAYOUT>(surf_planes(ch.e[blockIdx.z]), k, rgb + (size_t)blockIdx.z * rgb_stride, w, r0, r1,
+                       (int)(blockIdx.x * blockDim.x + threadIdx.x) * 16, (r0 >> 1) + (int)blockIdx.y);
 }
-
-// the same for any even width, any pitch and any alignment: one thread per 2 x 2 block, byte accesses
 template <int LAYOUT>
 __global__ __launch_bounds__(256) void k_surf_rows_to_rgb_any(SurfChunk ch, YuvCoef k, uint8_t* __restrict__ rgb, size_t rgb_stride, int w, int r0, int r1) {
-    const int bx = (int)(blockIdx.x * blockDim.x + threadIdx.x);
-    if (2 * bx >= w) return;
-    const int cr = (r0 >> 1) + (int)blockIdx.y;
-    const SurfEntry& e = ch.e[blockIdx.z];
-    const uint8_t* py = reinterpret_cast<const uint8_t*>(e.plane[0]);
-    const uint8_t* pu = reinterpret_cast<const uint8_t*>(e.plane[1]);
-    uint8_t* dst = rgb + (size_t)blockIdx.z * rgb_stride;
-    int u, v;
-    if constexpr (LAYOUT == 1) {
-        u = pu[(size_t)cr * e.cpitch + 2 * bx];
-        v = pu[(size_t)cr * e.cpitch + 2 * bx + 1];
-    } else {
-        u = pu[(size_t)cr * e.cpitch + bx];
-        v = reinterpret_cast<const uint8_t*>(e.plane[2])[(size_t)cr * e.cpitch + bx];
-    }
-    const Chroma c = yuv_chroma(u, v, k);
-    for (int dy = 0; dy < 2; ++dy) {
-        const int y = 2 * cr + dy;
-        if (y < r0 || y >= r1) continue;
-        for (int dx = 0; dx < 2; ++dx) {
-            const uint32_t p = yuv_pixel(py[(size_t)y * e.pitch + 2 * bx + dx], c, k);
-            const size_t o = (size_t)y * w + 2 * bx + dx;
-            dst[o * 3] = (uint8_t)p;
-            dst[o * 3 + 1] = (uint8_t)(p >> 8);
-            dst[o * 3 + 2] = (uint8_t)(p >> 16);
-        }
-    }
+    yuv_rows2x2<LAYOUT>(surf_planes(ch.e[blockIdx.z]), k, rgb + (size_t)blockIdx.z * rgb_stride, w, r0, r1,
+                        (int)(blockIdx.x * blockDim.x + threadIdx.x), (r0 >> 1) + (int)blockIdx.y);
 }
 
 // Rows [r0, r1) of RGB surfaces -> the same rows of the slots' camera frames (row_bytes = 3 w, dense): a pitched row copy, one
@@ -967,57 +844,49 @@ static int frames_per_thread(int n) {
     return fpb < 1 ? 1 : (fpb > cap ? cap : fpb);
 }
 
-void launch_undistort_rows(hipStream_t s, const uint8_t* frames, size_t frame_stride, const int16_t* uxy,
-                           const uint16_t* ufrac, FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n) {
+void launch_undistort_rows(hipStream_t s, FrameSource src, int layout, YuvCoef k, const int16_t* uxy, const uint16_t* ufrac,
+                           FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n) {
     if (n <= 0 || g.nrows <= 0) return;
-    const int fpb = frames_per_thread(n);
-    dim3 grid((g.img_w + 255) / 256, g.nrows, (n + fpb - 1) / fpb);
-    static const bool unaligned = [] { const char* e = LT_EXP_ENV("LT_UNDISTORT_UNALIGNED"); return e && e[0] == '1'; }();   // A/B
-    if (!unaligned && ((uintptr_t)frames & 3) == 0 && (frame_stride & 3) == 0 && (size_t)fpb * frame_stride < (1u << 30))
-        hipLaunchKernelGGL(k_undistort_rows<true>, grid, dim3(256), 0, s, frames, frame_stride, uxy, ufrac, g, und, und_px, first_slot, n, fpb, xcd_remap());
-    else
-        hipLaunchKernelGGL(k_undistort_rows<false>, grid, dim3(256), 0, s, frames, frame_stride, uxy, ufrac, g, und, und_px, first_slot, n, fpb, xcd_remap());
+    int fpb = frames_per_thread(n);
+    // the slots of a walk are addressed by a 32-bit offset into one buffer resource: a walk stays below 2^30 bytes (one frame
+    // per thread where a single frame is larger)
+    if (!src.tab) fpb = (int)std::max<size_t>(1, std::min<size_t>((size_t)fpb, (((size_t)1 << 30) - 1) / src.stride));
+    const dim3 grid((g.img_w + 255) / 256, g.nrows, (n + fpb - 1) / fpb), block(256);
+    const int remap = xcd_remap();
+    if (src.tab) {
+        if (layout == 0) hipLaunchKernelGGL(k_undistort_rows_surf, grid, block, 0, s, src.tab, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
+        else if (layout == 1) hipLaunchKernelGGL(k_undistort_rows_yuv_surf<1>, grid, block, 0, s, src.tab, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
+        else hipLaunchKernelGGL(k_undistort_rows_yuv_surf<2>, grid, block, 0, s, src.tab, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
+    } else if (layout == 0) {
+        static const bool unaligned = [] { const char* e = LT_EXP_ENV("LT_UNDISTORT_UNALIGNED"); return e && e[0] == '1'; }();   // A/B
+        if (!unaligned && ((uintptr_t)src.frames & 3) == 0 && (src.stride & 3) == 0 && src.stride < (1u << 30))   // (a larger frame: 64-bit addresses)
+            hipLaunchKernelGGL(k_undistort_rows<true>, grid, block, 0, s, src.frames, src.stride, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
+        else
+            hipLaunchKernelGGL(k_undistort_rows<false>, grid, block, 0, s, src.frames, src.stride, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
+    } else if (layout == 1) {
+        hipLaunchKernelGGL(k_undistort_rows_yuv<1>, grid, block, 0, s, src.frames, src.stride, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
+    } else {
+        hipLaunchKernelGGL(k_undistort_rows_yuv<2>, grid, block, 0, s, src.frames, src.stride, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
+    }
 }
 
-void launch_undistort_rows_yuv(hipStream_t s, int layout, const uint8_t* yuv, size_t yuv_stride, YuvCoef k, const int16_t* uxy,
-                               const uint16_t* ufrac, FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n) {
-    if (n <= 0 || g.nrows <= 0) return;
-    // (the frames of a walk are addressed by a 32-bit offset into one buffer resource)
-    const int fpb = (int)std::max<size_t>(1, std::min<size_t>((size_t)frames_per_thread(n), ((size_t)1 << 30) / yuv_stride));
-    dim3 grid((g.img_w + 255) / 256, g.nrows, (n + fpb - 1) / fpb);
-    if (layout == 1)
-        hipLaunchKernelGGL(k_undistort_rows_yuv<1>, grid, dim3(256), 0, s, yuv, yuv_stride, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, xcd_remap());
+// The 4:2:0 row conversion of n frames, dense or from surfaces: the 16-column kernels where the width and every base and pitch of
+// the launch (`bits`: all of them ORed) are multiples of 16, the byte-wise ones otherwise.  wide / any: the <NV12>, <I420> forms.
+template <class K, class... Args>
+static void launch_rows_to_rgb(hipStream_t s, int layout, K wide1, K wide2, K any1, K any2, size_t bits, int w, int r0, int r1, int n, Args... args) {
+    const unsigned crows = (unsigned)(((r1 + 1) >> 1) - (r0 >> 1));
+    if ((w & 15) == 0 && (bits & 15) == 0)
+        hipLaunchKernelGGL(layout == 1 ? wide1 : wide2, dim3((unsigned)((w / 16 + 63) / 64), crows, (unsigned)n), dim3(64), 0, s, args...);
     else
-        hipLaunchKernelGGL(k_undistort_rows_yuv<2>, grid, dim3(256), 0, s, yuv, yuv_stride, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, xcd_remap());
+        hipLaunchKernelGGL(layout == 1 ? any1 : any2, dim3((unsigned)((w / 2 + 255) / 256), crows, (unsigned)n), dim3(256), 0, s, args...);
 }
 
 void launch_yuv_rows_to_rgb(hipStream_t s, int layout, const uint8_t* yuv, size_t yuv_stride, YuvCoef k, uint8_t* rgb,
                             size_t rgb_stride, int h, int w, int r0, int r1, int n) {
     if (n <= 0 || r1 <= r0) return;
-    const unsigned crows = (unsigned)(((r1 + 1) >> 1) - (r0 >> 1));
-    const bool wide = (w & 15) == 0 && ((yuv_stride | rgb_stride | (size_t)(uintptr_t)yuv | (size_t)(uintptr_t)rgb) & 15) == 0;
-    if (wide) {
-        dim3 grid((unsigned)((w / 16 + 63) / 64), crows, (unsigned)n);
-        if (layout == 1) hipLaunchKernelGGL(k_yuv_rows_to_rgb<1>, grid, dim3(64), 0, s, yuv, yuv_stride, k, rgb, rgb_stride, h, w, r0, r1);
-        else hipLaunchKernelGGL(k_yuv_rows_to_rgb<2>, grid, dim3(64), 0, s, yuv, yuv_stride, k, rgb, rgb_stride, h, w, r0, r1);
-    } else {
-        dim3 grid((unsigned)((w / 2 + 255) / 256), crows, (unsigned)n);
-        if (layout == 1) hipLaunchKernelGGL(k_yuv_rows_to_rgb_any<1>, grid, dim3(256), 0, s, yuv, yuv_stride, k, rgb, rgb_stride, h, w, r0, r1);
-        else hipLaunchKernelGGL(k_yuv_rows_to_rgb_any<2>, grid, dim3(256), 0, s, yuv, yuv_stride, k, rgb, rgb_stride, h, w, r0, r1);
-    }
-}
-
-void launch_undistort_rows_surf(hipStream_t s, int layout, const SurfEntry* tab, YuvCoef k, const int16_t* uxy, const uint16_t* ufrac,
-                                FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n) {
-    if (n <= 0 || g.nrows <= 0) return;
-    const int fpb = frames_per_thread(n);
-    dim3 grid((g.img_w + 255) / 256, g.nrows, (n + fpb - 1) / fpb);
-    if (layout == 0)
-        hipLaunchKernelGGL(k_undistort_rows_surf, grid, dim3(256), 0, s, tab, uxy, ufrac, g, und, und_px, first_slot, n, fpb, xcd_remap());
-    else if (layout == 1)
-        hipLaunchKernelGGL(k_undistort_rows_yuv_surf<1>, grid, dim3(256), 0, s, tab, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, xcd_remap());
-    else
-        hipLaunchKernelGGL(k_undistort_rows_yuv_surf<2>, grid, dim3(256), 0, s, tab, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, xcd_remap());
+    launch_rows_to_rgb(s, layout, k_yuv_rows_to_rgb<1>, k_yuv_rows_to_rgb<2>, k_yuv_rows_to_rgb_any<1>, k_yuv_rows_to_rgb_any<2>,
+                       yuv_stride | rgb_stride | (size_t)(uintptr_t)yuv | (size_t)(uintptr_t)rgb, w, r0, r1, n,
+                       yuv, yuv_stride, k, rgb, rgb_stride, h, w, r0, r1);
 }
 
 void launch_write_surf_entries(hipStream_t s, SurfEntry* tab, int first, const SurfEntry* entries, int n) {
@@ -1029,9 +898,8 @@ void launch_write_surf_entries(hipStream_t s, SurfEntry* tab, int first, const S
     }
 }
 
-void launch_surf_rows_to_rgb(hipStream_t s, int layout, const SurfEntry* entries, YuvCoef k, uint8_t* rgb, size_t rgb_stride, int h, int w,
+void launch_surf_rows_to_rgb(hipStream_t s, int layout, const SurfEntry* entries, YuvCoef k, uint8_t* rgb, size_t rgb_stride, int w,
                              int r0, int r1, int n) {
-    (void)h;
     if (n <= 0 || r1 <= r0) return;
     for (int i = 0; i < n; i += SurfChunk::N) {
         const int m = std::min(n - i, (int)SurfChunk::N);
@@ -1050,17 +918,9 @@ void launch_surf_rows_to_rgb(hipStream_t s, int layout, const SurfEntry* entries
                 hipLaunchKernelGGL(k_surf_copy_rows<true>, dim3((unsigned)((row_bytes / 16 + 255) / 256), (unsigned)(r1 - r0), (unsigned)m), dim3(256), 0, s, ch, dst, rgb_stride, row_bytes, r0);
             else
                 hipLaunchKernelGGL(k_surf_copy_rows<false>, dim3((unsigned)((row_bytes + 255) / 256), (unsigned)(r1 - r0), (unsigned)m), dim3(256), 0, s, ch, dst, rgb_stride, row_bytes, r0);
-            continue;
-        }
-        const unsigned crows = (unsigned)(((r1 + 1) >> 1) - (r0 >> 1));
-        if ((w & 15) == 0 && (bits & 15) == 0) {
-            dim3 grid((unsigned)((w / 16 + 63) / 64), crows, (unsigned)m);
-            if (layout == 1) hipLaunchKernelGGL(k_surf_rows_to_rgb<1>, grid, dim3(64), 0, s, ch, k, dst, rgb_stride, w, r0, r1);
-            else hipLaunchKernelGGL(k_surf_rows_to_rgb<2>, grid, dim3(64), 0, s, ch, k, dst, rgb_stride, w, r0, r1);
         } else {
-            dim3 grid((unsigned)((w / 2 + 255) / 256), crows, (unsigned)m);
-            if (layout == 1) hipLaunchKernelGGL(k_surf_rows_to_rgb_any<1>, grid, dim3(256), 0, s, ch, k, dst, rgb_stride, w, r0, r1);
-            else hipLaunchKernelGGL(k_surf_rows_to_rgb_any<2>, grid, dim3(256), 0, s, ch, k, dst, rgb_stride, w, r0, r1);
+            launch_rows_to_rgb(s, layout, k_surf_rows_to_rgb<1>, k_surf_rows_to_rgb<2>, k_surf_rows_to_rgb_any<1>, k_surf_rows_to_rgb_any<2>,
+                               bits, w, r0, r1, m, ch, k, dst, rgb_stride, w, r0, r1);
         }
     }
 }

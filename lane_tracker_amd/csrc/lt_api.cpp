@@ -1567,7 +1567,7 @@ int lt_device_frames_rest(lt_ctx* c, int first, int n, const int32_t* rows4) {
     const int32_t whole[4] = {0, H, H, H};
     const int32_t* r = rows4 ? rows4 : whole;
     for (int k = 0; k < 4; k += 2)
-        launch_surf_rows_to_rgb(c->copy, c->in_layout, &c->surf[(size_t)first], yuv_coef_of(c), slot_frame(c, first), c->frame_bytes, H,
+        launch_surf_rows_to_rgb(c->copy, c->in_layout, &c->surf[(size_t)first], yuv_coef_of(c), slot_frame(c, first), c->frame_bytes,
                                 c->calib.img_w, r[k], r[k + 1], n);
     HIP_TRY(hipGetLastError());
     if ((rc = note_range(c->readers, c->copy, first, first + n))) return rc;      // it reads the surfaces and writes the camera frames: the next upload waits
@@ -2021,14 +2021,10 @@ static int mask_run_impl(lt_ctx* c, int first, int n, const lt_filter_params* p,
               for (int a = f0, b; a < f0 + m; a = b) {
                   const bool att = is_attached(a);
                   for (b = a + 1; b < f0 + m && is_attached(b) == att; ++b) {}
-                  if (att)
-                      launch_undistort_rows_surf(st, c->in_layout, c->d_surf, yuv_coef_of(c), c->d_uxy, c->d_ufrac, c->fe, c->d_und, c->und_px, a, b - a);
-                  else if (c->in_layout != LT_INPUT_RGB)
-                      launch_undistort_rows_yuv(st, c->in_layout, slot_yuv(c, a), c->yuv_stride, yuv_coef_of(c), c->d_uxy, c->d_ufrac,
-                                                c->fe, c->d_und, c->und_px, a, b - a);
-                  else
-                      launch_undistort_rows(st, slot_frame(c, a), c->frame_bytes, c->d_uxy, c->d_ufrac,
-                                            c->fe, c->d_und, c->und_px, a, b - a);
+                  const FrameSource src = att ? FrameSource::surfaces(c->d_surf)
+                                          : c->in_layout != LT_INPUT_RGB ? FrameSource::slots(slot_yuv(c, a), c->yuv_stride)
+                                                                         : FrameSource::slots(slot_frame(c, a), c->frame_bytes);
+                  launch_undistort_rows(st, src, c->in_layout, yuv_coef_of(c), c->d_uxy, c->d_ufrac, c->fe, c->d_und, c->und_px, a, b - a);
               } }
             { int mrc = n == 1 ? note_range_frame(c, c->readers, st, f0, f0 + m) : note_range(c->readers, st, f0, f0 + m); if (mrc) return mrc; }
             { StageScope t(c, ST_WARP_SPLIT, st);

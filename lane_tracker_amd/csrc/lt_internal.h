@@ -51,10 +51,7 @@ struct FrontEndGeom {
 __host__ __device__
 #endif
 inline size_t und_slot_base(size_t und_px, int slot) { return (size_t)(slot >> 1) * 2 * und_px + (size_t)(slot & 1); }
-// `und` is the base of the whole buffer, `first_slot` the absolute slot of frame 0 of the call; frames / planes point at
-// that slot's data
-void launch_undistort_rows(hipStream_t s, const uint8_t* frames, size_t frame_stride, const int16_t* uxy,
-                           const uint16_t* ufrac, FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n);
+// `und` is the base of the whole buffer, `first_slot` the absolute slot of frame 0 of the call; planes point at that slot's data
 void launch_warp_split(hipStream_t s, const uint32_t* und, size_t und_px, int first_slot, const int16_t* wxy,
                        const uint16_t* wfrac, FrontEndGeom g, const uint16_t* gamma_tab, const uint16_t* cbrt_tab,
                        const int32_t* coeffs, uint8_t* planeR, uint8_t* planeB, size_t plane_stride, int n);
@@ -63,10 +60,6 @@ void launch_warp_split(hipStream_t s, const uint32_t* und, size_t und_px, int fi
 struct YuvCoef {
     int32_t cy, cvr, cvg, cug, cub;
 };
-// launch_undistort_rows reading the slots' 4:2:0 staging frames (layout 1 = NV12, 2 = I420; `yuv_stride` bytes per slot, a
-// multiple of 16, 16 bytes of padding behind the last slot) instead of their RGB camera frames: every tap converted, then the same blend
-void launch_undistort_rows_yuv(hipStream_t s, int layout, const uint8_t* yuv, size_t yuv_stride, YuvCoef k, const int16_t* uxy,
-                               const uint16_t* ufrac, FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n);
 // rows [r0, r1) of n 4:2:0 frames of h x w (h, w even) -> the same rows of n RGB frames
 void launch_yuv_rows_to_rgb(hipStream_t s, int layout, const uint8_t* yuv, size_t yuv_stride, YuvCoef k, uint8_t* rgb,
                             size_t rgb_stride, int h, int w, int r0, int r1, int n);
@@ -82,14 +75,25 @@ struct SurfChunk {               // the entries of one launch, by value
     static constexpr int N = 32;
     SurfEntry e[N];
 };
-// launch_undistort_rows / _yuv (layout 0 = RGB, 1 = NV12, 2 = I420) with the taps read from the surfaces of entries
-// [first_slot, first_slot + n) of `tab` (device memory)
-void launch_undistort_rows_surf(hipStream_t s, int layout, const SurfEntry* tab, YuvCoef k, const int16_t* uxy, const uint16_t* ufrac,
-                                FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n);
+// Where the undistortion finds the frames of slots [first_slot, first_slot + n): in the slots themselves -- `frames` = the frame
+// of first_slot, `stride` bytes per slot: the RGB camera frames (8 bytes of padding behind each) or the 4:2:0 staging frames (a
+// multiple of 16 apart, 16 bytes of padding behind the last) -- or on the caller's surfaces, entries [first_slot, first_slot + n)
+// of `tab` (device memory).
+struct FrameSource {
+    const SurfEntry* tab;        // not null: surfaces
+    const uint8_t* frames;
+    size_t stride;
+    static FrameSource slots(const uint8_t* frames, size_t stride) { return FrameSource{nullptr, frames, stride}; }
+    static FrameSource surfaces(const SurfEntry* tab) { return FrameSource{tab, nullptr, 0}; }
+};
+// the undistorted rows of n frames (layout 0 = RGB, 1 = NV12, 2 = I420; `k` is read for 4:2:0 only: every tap converted, then the
+// same blend); `und` is the base of the whole buffer, `first_slot` the absolute slot of frame 0 of the call
+void launch_undistort_rows(hipStream_t s, FrameSource src, int layout, YuvCoef k, const int16_t* uxy, const uint16_t* ufrac,
+                           FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n);
 // entries[0, n) (host memory, consumed before the call returns) -> tab[first, first + n), stream-ordered
 void launch_write_surf_entries(hipStream_t s, SurfEntry* tab, int first, const SurfEntry* entries, int n);
 // rows [r0, r1) of the n surfaces of entries[] (host memory) -> the same rows of n RGB frames: a conversion (4:2:0) or a pitched copy (RGB)
-void launch_surf_rows_to_rgb(hipStream_t s, int layout, const SurfEntry* entries, YuvCoef k, uint8_t* rgb, size_t rgb_stride, int h, int w,
+void launch_surf_rows_to_rgb(hipStream_t s, int layout, const SurfEntry* entries, YuvCoef k, uint8_t* rgb, size_t rgb_stride, int w,
                              int r0, int r1, int n);
 void launch_split_bev(hipStream_t s, const uint8_t* bev, size_t bev_stride, int npix, const uint16_t* gamma_tab,
                       const uint16_t* cbrt_tab, const int32_t* coeffs, uint8_t* planeR, uint8_t* planeB,
