@@ -4,7 +4,6 @@
 //   k_morph_ellipse   morphologyEx TOPHAT / OPEN building block   lane_tracker.py:210-211, 238
 //   k_bilateral       bilateral_adaptive_threshold                lane_tracker.py:14-83, 214-215, 224
 //   k_adaptive_mean   cv2.adaptiveThreshold(MEAN_C)               lane_tracker.py:217-218
-//   k_merge           OR / noise-mask merge                       lane_tracker.py:221-235
 #include "lt_internal.h"
 
 namespace lt {
@@ -146,22 +145,6 @@ __global__ __launch_bounds__(256) void k_adaptive_mean(const uint8_t* __restrict
     }
 }
 
-// ---- merge ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_merge(const uint8_t* __restrict__ tr, const uint8_t* __restrict__ tb,
-                                              const uint8_t* __restrict__ labb, const uint8_t* __restrict__ noise_bil,
-                                              int noise_thresh, int use_noise, uint8_t* __restrict__ merged,
-                                              size_t npix, size_t plane_stride) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= npix) return;
-    const size_t o = (size_t)blockIdx.z * plane_stride + i;
-    bool v = tr[o] || tb[o];
-    if (use_noise) {
-        const bool part1 = labb[o] >= noise_thresh;  // inRange(b, thresh, 255)
-        v = v && (!part1 || noise_bil[o]);
-    }
-    merged[o] = v ? 255 : 0;
-}
-
 }  // namespace
 
 void launch_morph_ellipse(hipStream_t s, const uint8_t* src, uint8_t* dst, const uint8_t* minuend, int h, int w,
@@ -192,14 +175,6 @@ void launch_adaptive_mean(hipStream_t s, const uint8_t* src, uint8_t* dst, int h
     const size_t lds = (size_t)((th * tw + 15) & ~15) + (size_t)th * AT_W * sizeof(int32_t);
     dim3 grid((w + AT_W - 1) / AT_W, (h + AT_H - 1) / AT_H, n);
     hipLaunchKernelGGL(k_adaptive_mean, grid, dim3(256), lds, s, src, dst, h, w, bs, C, plane_stride);
-}
-
-void launch_merge(hipStream_t s, const uint8_t* tr, const uint8_t* tb, const uint8_t* labb, const uint8_t* noise_bil,
-                  int noise_thresh, int use_noise, uint8_t* merged, size_t npix, size_t plane_stride, int n) {
-    if (n <= 0 || npix == 0) return;
-    dim3 grid((unsigned)((npix + 255) / 256), 1, n);
-    hipLaunchKernelGGL(k_merge, grid, dim3(256), 0, s, tr, tb, labb, noise_bil, noise_thresh, use_noise, merged, npix,
-                       plane_stride);
 }
 
 // Code objects load on the first launch of one of their kernels (a few ms each, once per process and device): lt_create launches

@@ -894,16 +894,21 @@ void launch_open5_to_bits(hipStream_t s, const unsigned long long* merged, unsig
                        bits_stride);
 }
 
-// merged (or the first of four partial planes, OR-ed in place) -> opened, both bit planes; false when the row does not
-// fit a wave (w > 4096): the caller runs the separate kernels
-bool launch_merge_open5(hipStream_t s, unsigned long long* p0, const unsigned long long* p1, const unsigned long long* p2,
-                        const unsigned long long* p3, unsigned long long* opened, int h, int w, size_t bits_stride, int n,
-                        const unsigned long long* n0, const unsigned long long* n1) {
+// The merged plane of `in` -> opened, both bit planes, the merge in place on the way; false when the row does not fit a wave
+// (w > 4096): the caller runs the separate kernels.  with_np: f(NP as a constant) for the planes `in` makes the kernel read.
+template <class F>
+static void with_np(const MergeInputs& in, F f) {
+    switch (merge_planes(in)) {
+        case 6: f(std::integral_constant<int, 6>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        default: f(std::integral_constant<int, 1>{}); break;
+    }
+}
+bool launch_merge_open5(hipStream_t s, const MergeInputs& in, unsigned long long* opened, int h, int w, size_t bits_stride, int n) {
     const int wpr = (w + 63) / 64;
-    if ((n0 || n1) && !(n0 && n1 && p1 && p2 && p3)) return false;
-    if ((p2 != nullptr) != (p3 != nullptr) || (p2 && !p1)) return false;
     static const bool off = [] { const char* e = LT_EXP_ENV("LT_OPEN5_SEPARATE"); return e && e[0] == '1'; }();   // A/B
-    if (off || n <= 0 || h <= 0 || wpr > 64 || opened == p0) return false;
+    if (off || !merge_planes(in) || n <= 0 || h <= 0 || wpr > 64 || opened == in.dst) return false;
     const int G = 64 / wpr;
     static const int rows_env = [] { const char* e = LT_EXP_ENV("LT_OPEN5_BAND_ROWS"); return e ? std::atoi(e) : 0; }();
     // enough bands to give every SIMD a few waves, none shorter than 24 rows (8 halo rows per band are recomputed)
@@ -911,28 +916,22 @@ bool launch_merge_open5(hipStream_t s, unsigned long long* p0, const unsigned lo
     int nbands = std::max(1, std::min(h / 24, (4096 + groups - 1) / groups));
     int band_rows = rows_env > 0 ? rows_env : (h + nbands - 1) / nbands;
     nbands = (h + band_rows - 1) / band_rows;
-    dim3 grid(groups, nbands);
-    if (n0) hipLaunchKernelGGL(k_merge_open5<6>, grid, dim3(64), 0, s, p0, p1, p2, p3, n0, n1, opened, h, w, wpr, bits_stride, band_rows, G, n);
-    else if (p1 && !p2) hipLaunchKernelGGL(k_merge_open5<2>, grid, dim3(64), 0, s, p0, p1, p2, p3, n0, n1, opened, h, w, wpr, bits_stride, band_rows, G, n);
-    else if (p1) hipLaunchKernelGGL(k_merge_open5<4>, grid, dim3(64), 0, s, p0, p1, p2, p3, n0, n1, opened, h, w, wpr, bits_stride, band_rows, G, n);
-    else hipLaunchKernelGGL(k_merge_open5<1>, grid, dim3(64), 0, s, p0, p1, p2, p3, n0, n1, opened, h, w, wpr, bits_stride, band_rows, G, n);
+    with_np(in, [&](auto np) {
+        hipLaunchKernelGGL(k_merge_open5<decltype(np)::value>, dim3(groups, nbands), dim3(64), 0, s, in.dst, in.more[0], in.more[1], in.more[2],
+                           in.and0, in.and1, opened, h, w, wpr, bits_stride, band_rows, G, n);
+    });
     return true;
 }
 
 // the same for a few frames (k_or_open5_small); false: not launched (a row wider than 64 words, LT_OPEN_SMALL=0)
-bool launch_or_open5_small(hipStream_t s, unsigned long long* p0, const unsigned long long* p1, const unsigned long long* p2,
-                           const unsigned long long* p3, unsigned long long* opened, int h, int w, size_t bits_stride, int n,
-                           const unsigned long long* n0, const unsigned long long* n1) {
+bool launch_or_open5_small(hipStream_t s, const MergeInputs& in, unsigned long long* opened, int h, int w, size_t bits_stride, int n) {
     const int wpr = (w + 63) / 64;
-    if ((n0 || n1) && !(n0 && n1 && p1 && p2 && p3)) return false;
-    if ((p2 != nullptr) != (p3 != nullptr) || (p2 && !p1)) return false;
     static const bool off = [] { const char* e = LT_EXP_ENV("LT_OPEN_SMALL"); return e && e[0] == '0'; }();   // A/B
-    if (off || n <= 0 || h <= 0 || wpr > 64 || opened == p0) return false;
-    const dim3 grid((h + OS_RB - 1) / OS_RB, n);
-    if (n0) hipLaunchKernelGGL(k_or_open5_small<6>, grid, dim3(256), 0, s, p0, p1, p2, p3, n0, n1, opened, h, w, wpr, bits_stride);
-    else if (p1 && !p2) hipLaunchKernelGGL(k_or_open5_small<2>, grid, dim3(256), 0, s, p0, p1, p2, p3, n0, n1, opened, h, w, wpr, bits_stride);
-    else if (p1) hipLaunchKernelGGL(k_or_open5_small<4>, grid, dim3(256), 0, s, p0, p1, p2, p3, n0, n1, opened, h, w, wpr, bits_stride);
-    else hipLaunchKernelGGL(k_or_open5_small<1>, grid, dim3(256), 0, s, p0, p1, p2, p3, n0, n1, opened, h, w, wpr, bits_stride);
+    if (off || !merge_planes(in) || n <= 0 || h <= 0 || wpr > 64 || opened == in.dst) return false;
+    with_np(in, [&](auto np) {
+        hipLaunchKernelGGL(k_or_open5_small<decltype(np)::value>, dim3((h + OS_RB - 1) / OS_RB, n), dim3(256), 0, s, in.dst, in.more[0],
+                           in.more[1], in.more[2], in.and0, in.and1, opened, h, w, wpr, bits_stride);
+    });
     return true;
 }
 

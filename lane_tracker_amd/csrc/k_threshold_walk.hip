@@ -572,49 +572,47 @@ void dispatch_walk(int k, hipStream_t s, const uint8_t* src, int C, unsigned lon
 
 }  // namespace
 
-bool bilateral_walk_supported(int k_r, int C_r, int k_b, int C_b, int h, int w, int pitch) {
+bool bilateral_walk_supported(int k_r, int C_r, int k_b, int C_b, int h, int w, int pitch, size_t plane_stride) {
     static const bool off = [] { const char* e = LT_EXP_ENV("LT_BILATERAL_TILES"); return e && e[0] == '1'; }();
     if (off || !walk_supports(k_r) || !walk_supports(k_b) || C_r < 0 || C_b < 0) return false;
-    if ((w & 3) || (pitch & 63) || pitch < w || w < 8 || h < 1) return false;
+    if ((w & 3) || (pitch & 63) || (plane_stride & 63) || pitch < w || w < 8 || h < 1) return false;
     return (long long)k_r * (255 + C_r) < 32768 && (long long)k_b * (255 + C_b) < 32768;
 }
 
-// Both bilateral thresholds through the walking kernels: four partial bit planes (merged, s1, s2, s3), OR-ed into `merged`
-// here when `merge` is set -- otherwise the caller merges them (launch_merge_open5 does it on the way into the 5x5 open).
-// Returns 0 when it ran, -1 when the parameters are outside its limits.
+// Both bilateral thresholds through the walking kernels: four partial bit planes (merged, s1, s2, s3) the caller merges
+// (launch_merge_open5 does it on the way into the 5x5 open).  Returns 0 when it ran, -1 when the predicate above says no.
 int launch_bilateral_walk(hipStream_t s, const uint8_t* thr, int k_r, int C_r, const uint8_t* thb, int k_b, int C_b,
                           unsigned long long* merged, unsigned long long* s1, unsigned long long* s2, unsigned long long* s3,
-                          int h, int w, int pitch, size_t plane_stride, size_t bits_stride, int n, bool merge) {
-    if (n <= 0 || !bilateral_walk_supported(k_r, C_r, k_b, C_b, h, w, pitch) || (plane_stride & 63)) return -1;
+                          int h, int w, int pitch, size_t plane_stride, size_t bits_stride, int n) {
+    if (n <= 0 || !bilateral_walk_supported(k_r, C_r, k_b, C_b, h, w, pitch, plane_stride)) return -1;
     static const int passes = [] { const char* e = LT_EXP_ENV("LT_WALK_PASSES"); return e ? std::atoi(e) : 15; }();
     dispatch_walk(k_r, s, thr, C_r, merged, s1, h, w, pitch, plane_stride, bits_stride, n, passes & 3);
     dispatch_walk(k_b, s, thb, C_b, s2, s3, h, w, pitch, plane_stride, bits_stride, n, (passes >> 2) & 3);
-    if (merge) launch_or4_bits(s, merged, s1, s2, s3, h, w, bits_stride, n);
     return 0;
 }
 
-bool noise_walk_supported(int k_n, int C_n, int h, int w, int pitch) {
+bool noise_walk_supported(int k_n, int C_n, int h, int w, int pitch, size_t plane_stride) {
     static const bool off = [] { const char* e = LT_EXP_ENV("LT_BILATERAL_TILES"); return e && e[0] == '1'; }();
     if (off || k_n != K_NOISE || C_n < 0 || (long long)k_n * (255 + C_n) >= 32768) return false;
-    return !((w & 3) || (pitch & 63) || pitch < w || w < 8 || h < 1);
+    return !((w & 3) || (pitch & 63) || (plane_stride & 63) || pitch < w || w < 8 || h < 1);
 }
 
 // noise_h | noise_v = the greenery mask  !inRange(b, noise_thresh, 255) | bilateral(b, 65, C_n)  of lane_tracker.py:223-225;
 // `braw` is the RAW Lab-b plane with the padded pitch.  0 = ran, -1 = outside its limits.
 int launch_noise_walk(hipStream_t s, const uint8_t* braw, int k_n, int C_n, int noise_thresh, unsigned long long* noise_h,
                       unsigned long long* noise_v, int h, int w, int pitch, size_t plane_stride, size_t bits_stride, int n) {
-    if (n <= 0 || !noise_walk_supported(k_n, C_n, h, w, pitch) || (plane_stride & 63)) return -1;
+    if (n <= 0 || !noise_walk_supported(k_n, C_n, h, w, pitch, plane_stride)) return -1;
     launch_walk_noise(s, braw, C_n, noise_thresh, noise_h, noise_v, h, w, pitch, plane_stride, bits_stride, n);
     return 0;
 }
 
-void launch_or4_bits(hipStream_t s, unsigned long long* merged, const unsigned long long* s1, const unsigned long long* s2,
-                     const unsigned long long* s3, int h, int w, size_t bits_stride, int n, const unsigned long long* n0,
-                     const unsigned long long* n1) {
-    if (n <= 0) return;
+void launch_or4_bits(hipStream_t s, const MergeInputs& in, int h, int w, size_t bits_stride, int n) {
+    const int np = merge_planes(in);
+    if (n <= 0 || np < 2) return;
     const size_t words = (size_t)(n - 1) * bits_stride + (size_t)h * ((w + 63) / 64);
-    if (!n0 || !n1) n0 = n1 = nullptr;
-    hipLaunchKernelGGL(k_or4_bits, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, merged, s1, s2, s3, n0, n1, merged, words);
+    // the kernel ORs four planes: two are made four by naming the second one three times
+    const unsigned long long *p2 = np == 2 ? in.more[0] : in.more[1], *p3 = np == 2 ? in.more[0] : in.more[2];
+    hipLaunchKernelGGL(k_or4_bits, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, in.dst, in.more[0], p2, p3, in.and0, in.and1, in.dst, words);
 }
 
 // Code objects load on the first launch of one of their kernels (a few ms each, once per process and device): lt_create launches

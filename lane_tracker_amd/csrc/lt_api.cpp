@@ -1,6 +1,6 @@
 // C-ABI layer of liblane_tracker_amd.so (see include/lane_tracker_amd.h).
 // Owns the context: HIP stream, calibration tables, frame slots; sequences the kernel chain of
-// LaneTracker.find_lane_points() (lane_tracker.py:795-874) for a batch of independent frames.
+// LaneTracker.find_lane_points() (lane_tracker.py:795-874) for a batch of independent frames (the mask stage: lt_mask_chain.cpp).
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -187,18 +187,7 @@ void free_slots(lt_ctx* c) {
     c->surf.clear();
     c->attached.clear();
     dev_free(c->d_bev);
-    for (auto& p : c->d_plane) dev_free(p);
-    dev_free(c->d_bits_merged);
-    dev_free(c->d_bits_eroded);
-    dev_free(c->d_bits_open);
-    dev_free(c->d_bits_tmp);
-    dev_free(c->d_bits_tmp2);
-    dev_free(c->d_th_pad[0]);
-    dev_free(c->d_th_pad[1]);
-    dev_free(c->d_b_pad);
-    dev_free(c->d_bits_n1);
-    dev_free(c->d_bits_n2);
-    c->th_padded.clear();
+    c->masks.release();
     c->mask_bits_ok.clear();
     c->mask_u8_ok.clear();
     c->frame_full.clear();
@@ -214,7 +203,6 @@ void free_slots(lt_ctx* c) {
     c->h_ploty.clear();
     dev_free(c->d_annot);
     dev_free(c->d_strip);
-    dev_free(c->d_side_scratch);
     c->maxbands = 0;
     c->capacity = 0;
     c->maxpix = 0;
@@ -325,11 +313,25 @@ bool masks_have_bits(const lt_ctx* c, int first, int n) {
         if (!c->mask_bits_ok[(size_t)i]) return false;
     return true;
 }
+// the u8 mask plane of the slots; slots nobody has written a mask to read as zeros
+static int ensure_mask_plane(lt_ctx* c) {
+    if (c->masks.d_plane[P_MASK]) return LT_OK;
+    const int rc = c->masks.ensure_plane(P_MASK);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(c->masks.d_plane[P_MASK], 0, (size_t)c->capacity * c->masks.plane_bytes, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return LT_OK;
+}
+// what the mask chain takes from the context besides the arena (lt_mask_chain.cpp)
+static ChainEnv chain_env(lt_ctx* c) {
+    return ChainEnv{&c->se29, &c->se55, c->brute_tophat, c->walk_min_pixels, &c->streams, c->stage_timing ? c : nullptr,
+                    &c->last_threshold_path, &c->last_adaptive_path};
+}
 // make d_plane[P_MASK] current for the slots (expands the bit plane where only that exists)
 int ensure_u8_masks(lt_ctx* c, int first, int n) {
     bool any = false;
     for (int i = first; i < first + n; ++i) any = any || !c->mask_u8_ok[(size_t)i];
-    int rc = ensure_plane(c, P_MASK);
+    int rc = ensure_mask_plane(c);
     if (rc) return rc;
     if (!any) return LT_OK;
     if ((rc = sync_all(c))) return rc;
@@ -338,219 +340,12 @@ int ensure_u8_masks(lt_ctx* c, int first, int n) {
         int j = i;
         while (j < first + n && !c->mask_u8_ok[(size_t)j]) ++j;
         launch_bits_to_u8(c->stream, slot_bits(c, i, true).bits, slot_mask(c, i),
-                          c->calib.warp_h, c->calib.warp_w, c->plane_bytes, c->bits_stride, j - i);
+                          c->calib.warp_h, c->calib.warp_w, c->masks.plane_bytes, c->masks.bits_stride, j - i);
         for (int k = i; k < j; ++k) c->mask_u8_ok[(size_t)k] = 1;
         i = j;
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(c->stream));
-    return LT_OK;
-}
-
-int ensure_noise_buffers(lt_ctx* c) {
-    if (c->d_b_pad && c->d_bits_n1 && c->d_bits_n2) return LT_OK;
-    const size_t n = (size_t)c->capacity;
-    int rc;
-    if (!c->d_b_pad && (rc = dev_alloc(&c->d_b_pad, n * c->th_pad_bytes))) return rc;
-    if (!c->d_bits_n1 && (rc = dev_alloc(&c->d_bits_n1, n * c->bits_stride))) return rc;
-    if (!c->d_bits_n2 && (rc = dev_alloc(&c->d_bits_n2, n * c->bits_stride))) return rc;
-    return LT_OK;
-}
-
-int validate_filter(const lt_filter_params* p) {
-    if (!p) return fail(LT_ERR_INVALID, "null filter params");
-    if (p->filter_type != 0 && p->filter_type != 1)
-        return fail(LT_ERR_INVALID, "Unexpected filter mode. Expected modes are 'bilateral' or 'neighborhood'.");
-    if (p->ksize_r < 1 || p->ksize_b < 1 || (p->mask_noise && p->ksize_noise < 1))
-        return fail(LT_ERR_INVALID, "filter sizes must be >= 1");
-    if (p->filter_type == 1 && ((p->ksize_r & 1) == 0 || (p->ksize_b & 1) == 0))
-        return fail(LT_ERR_INVALID, "'neighborhood' block sizes must be odd (cv2.adaptiveThreshold requirement)");
-    if (p->ksize_r > 128 || p->ksize_b > 128 || p->ksize_noise > 128)
-        return fail(LT_ERR_INVALID, "filter size too large (max 128)");
-    return LT_OK;
-}
-
-// Planes only some paths use are allocated when one of those paths runs first (the whole capacity at once): the u8 mask
-// (d_plane[P_MASK]: lt_upload_masks, lt_download_masks, searches outside the bit-plane kernels' limits), the expanded merged
-// plane (lt_download_plane), the scratch planes of the older threshold kernels (P_T1 .. P_T3).  A 768-slot context is 10.4 GB
-// instead of 14.6 -- and device memory that has been used before costs ~16 ms per GB to allocate (the driver clears it: NOTES D.2).
-int ensure_plane(lt_ctx* c, int idx) {
-    if (c->d_plane[idx]) return LT_OK;
-    int rc = dev_alloc(&c->d_plane[idx], (size_t)c->capacity * c->plane_bytes);
-    if (rc) return rc;
-    if (idx == P_MASK) {             // slots nobody has written a mask to read as zeros
-        HIP_TRY(hipMemsetAsync(c->d_plane[idx], 0, (size_t)c->capacity * c->plane_bytes, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    return LT_OK;
-}
-
-constexpr int SIDE_LANES = 10;   // eroded-R scratch of the one- and two-frame chain: one per slice stream (up to 8), one for every other stream
-
-// filter_lane_points() on planes P_R / P_B of the given slots (lane_tracker.py:210-238)
-int run_filter_chain(lt_ctx* c, hipStream_t s, int first, int n, const lt_filter_params* p, int h, int w, int call_frames,
-                     bool u8_mask = false) {
-    const size_t ps = c->plane_bytes, off = (size_t)first * ps;
-    uint8_t* R = c->d_plane[P_R] + off;
-    uint8_t* B = c->d_plane[P_B] + off;
-    uint8_t* thR = c->d_plane[P_THR] + off;
-    uint8_t* thB = c->d_plane[P_THB] + off;
-    uint8_t* t0 = c->d_plane[P_T0] + off;
-    uint8_t *t1 = nullptr, *t2 = nullptr, *t3 = nullptr;      // allocated by the paths that use them (ensure_plane)
-    auto scratch = [&](int idx, uint8_t*& q) -> int {
-        const int rc = ensure_plane(c, idx);
-        if (!rc) q = c->d_plane[idx] + off;
-        return rc;
-    };
-    uint8_t* mask = nullptr;
-    if (u8_mask) { const int rc = scratch(P_MASK, mask); if (rc) return rc; }
-    // the walking threshold kernels read the top-hat planes with a padded row pitch: the dilate launches write them so
-    // (the greenery mask, mask_noise, rides along: a third walk with window 65 over the raw Lab-b plane)
-    const bool walk = p->filter_type == 0 && !c->brute_tophat && c->d_th_pad[0] && c->d_bits_tmp && c->d_bits_tmp2 &&
-                      first + n <= (int)c->th_padded.size() && (long long)call_frames * h * w >= c->walk_min_pixels &&
-                      bilateral_walk_supported(p->ksize_r, p->C_r, p->ksize_b, p->C_b, h, w, c->th_pitch) &&
-                      (!p->mask_noise || noise_walk_supported(p->ksize_noise, p->C_noise, h, w, c->th_pitch));
-    const bool walk_noise = walk && p->mask_noise;
-    if (walk_noise) {
-        const int rc = ensure_noise_buffers(c);
-        if (rc) return rc;
-    }
-    uint8_t* bpad = walk_noise ? c->d_b_pad + (size_t)first * c->th_pad_bytes : nullptr;
-    if (p->filter_type == 0) c->last_threshold_path = walk ? 1 : 0;
-    const int dpitch = walk ? c->th_pitch : 0;
-    uint8_t* thRd = walk ? c->d_th_pad[0] + (size_t)first * c->th_pad_bytes : thR;
-    uint8_t* thBd = walk ? c->d_th_pad[1] + (size_t)first * c->th_pad_bytes : thB;
-    // the 55x55 top-hat of the Lab-b plane; with the greenery mask it also leaves the raw plane in the padded layout
-    auto tophat_b = [&](hipStream_t st) -> int {
-        if (bpad && launch_morph_runs(st, t0, thBd, B, h, w, 55, true, ps, n, dpitch, c->th_pad_bytes, bpad)) return LT_OK;
-        launch_morph_runs(st, t0, thBd, B, h, w, 55, true, ps, n, dpitch, c->th_pad_bytes);
-        if (bpad)   // that kernel form does not exist for this geometry / A-B switch: plain strided copies
-            for (int i = 0; i < n; ++i)
-                HIP_TRY(hipMemcpy2DAsync(bpad + (size_t)i * c->th_pad_bytes, (size_t)c->th_pitch, B + (size_t)i * ps, (size_t)w, (size_t)w,
-                                         (size_t)h, hipMemcpyDeviceToDevice, st));
-        return LT_OK;
-    };
-    if (p->filter_type == 0 && first + n <= (int)c->th_padded.size())
-        for (int i = first; i < first + n; ++i) c->th_padded[(size_t)i] = walk ? 1 : 0;
-    unsigned long long* mbits = c->d_bits_merged + (size_t)first * c->bits_stride;
-    unsigned long long* ebits = c->d_bits_eroded + (size_t)first * c->bits_stride;
-    unsigned long long* tbits = c->d_bits_tmp ? c->d_bits_tmp + (size_t)first * c->bits_stride : nullptr;
-    unsigned long long* ubits = c->d_bits_tmp2 ? c->d_bits_tmp2 + (size_t)first * c->bits_stride : nullptr;
-    // One or two frames (process()): both planes' thresholds in ONE launch with the H and the V phases of a tile in workgroups of
-    // their own (one frame: 81 tiles on 256 CUs) -- H verdicts of both planes into mbits, V verdicts into ebits; the open ORs them
-    bool both_split = false;
-    if (p->filter_type == 0) {
-        if (c->brute_tophat) {   // debugging aid of the experiments build (LT_TOPHAT_BRUTE=1): direct footprint evaluation, still on the GPU
-            { StageScope t(c, ST_ERODE_R, s);  launch_morph_ellipse(s, R, t0, nullptr, h, w, c->se29, false, ps, n); }
-            { StageScope t(c, ST_TOPHAT_R, s); launch_morph_ellipse(s, t0, thR, R, h, w, c->se29, true, ps, n); }
-            { StageScope t(c, ST_ERODE_B, s);  launch_morph_ellipse(s, B, t0, nullptr, h, w, c->se55, false, ps, n); }
-            { StageScope t(c, ST_TOPHAT_B, s); launch_morph_ellipse(s, t0, thB, B, h, w, c->se55, true, ps, n); }
-        } else if (n <= 2 && !c->stage_timing && !walk) {
-            // One or two frames cannot fill the chip (a few hundred waves per top-hat kernel), and the two planes' top-hats do not
-            // depend on each other: the 55x55 erode of the Lab-b plane and the 29x29 erode of the R plane are ONE launch, the two
-            // top-hats the next (k_morph_one_pair).  (Round 5 ran the R plane's chain on a side stream: a fork, a join that cost the
-            // frame 11-12 us of signalling, and three more launches.)  The eroded R plane has a scratch of its own, two planes per context.
-            // (per STREAM, not per slot: a context of a thousand slots runs these one- and two-frame calls on a handful of streams --
-            // the slices' streams and the urgent one -- and calls on one stream are ordered)
-            if (!c->d_side_scratch) { const int rc = dev_alloc(&c->d_side_scratch, (size_t)SIDE_LANES * 2 * ps); if (rc) return rc; }
-            int lane_of_stream = SIDE_LANES - 1;
-            for (int i = 0; i < (int)c->streams.size() && i < SIDE_LANES - 1; ++i)
-                if (c->streams[(size_t)i] == s) { lane_of_stream = i; break; }
-            uint8_t* ts = c->d_side_scratch + (size_t)lane_of_stream * 2 * ps;
-            if (launch_morph_one_pair(s, B, t0, nullptr, R, ts, nullptr, h, w, false, ps, n, 0, 0)) {
-                if (!launch_morph_one_pair(s, t0, thB, B, ts, thR, R, h, w, true, ps, n, 0, 0)) {
-                    launch_morph_runs(s, t0, thB, B, h, w, 55, true, ps, n);
-                    launch_morph_runs(s, ts, thR, R, h, w, 29, true, ps, n);
-                }
-            } else {             // (a geometry the one-frame kernel does not take: an image width that is not a multiple of four)
-                launch_morph_runs(s, R, t0, nullptr, h, w, 29, false, ps, n);
-                launch_morph_runs(s, t0, thR, R, h, w, 29, true, ps, n);
-                launch_morph_runs(s, B, t0, nullptr, h, w, 55, false, ps, n);
-                launch_morph_runs(s, t0, thB, B, h, w, 55, true, ps, n);
-            }
-            both_split = !p->mask_noise;
-        } else {
-            { StageScope t(c, ST_ERODE_R, s);  launch_morph_runs(s, R, t0, nullptr, h, w, 29, false, ps, n); }
-            { StageScope t(c, ST_TOPHAT_R, s); launch_morph_runs(s, t0, thRd, R, h, w, 29, true, ps, n, dpitch, c->th_pad_bytes); }
-            { StageScope t(c, ST_ERODE_B, s);  launch_morph_runs(s, B, t0, nullptr, h, w, 55, false, ps, n); }
-            { StageScope t(c, ST_TOPHAT_B, s); const int rc = tophat_b(s); if (rc) return rc; }
-        }
-    }
-    bool merged_done = false, partials = false;   // partials: mbits, ebits, tmp, tmp2 still wait for their OR
-    bool two_partials = false;                    // ... only mbits and ebits (the 'neighborhood' walk)
-    unsigned long long *nbits1 = nullptr, *nbits2 = nullptr;   // the greenery mask of the walking kernels: n1 | n2
-    if (p->filter_type == 0) {
-        StageScope t(c, ST_THRESHOLD, s);   // both bilateral thresholds, the greenery mask and the OR-merge
-        // long-walk kernels for the supported window sizes; their four partial planes are merged on the way into the open
-        if (walk) {
-            merged_done = launch_bilateral_walk(s, thRd, p->ksize_r, p->C_r, thBd, p->ksize_b, p->C_b, mbits, ebits, tbits, ubits,
-                                                h, w, c->th_pitch, c->th_pad_bytes, c->bits_stride, n, false) == 0;
-            partials = merged_done;
-            if (merged_done && walk_noise) {
-                nbits1 = c->d_bits_n1 + (size_t)first * c->bits_stride;
-                nbits2 = c->d_bits_n2 + (size_t)first * c->bits_stride;
-                if (launch_noise_walk(s, bpad, p->ksize_noise, p->C_noise, p->noise_thresh, nbits1, nbits2, h, w, c->th_pitch,
-                                      c->th_pad_bytes, c->bits_stride, n))
-                    return fail(LT_ERR_STATE, "the greenery-mask walk refused parameters its own predicate accepted");
-            }
-        }
-        if (!merged_done && both_split) {        // (refused when the packed arithmetic does not fit the parameters: one workgroup per tile below)
-            merged_done = launch_bilateral_bits(s, thR, p->ksize_r, p->C_r, thB, p->ksize_b, p->C_b, B, p->ksize_noise, p->C_noise,
-                                                p->noise_thresh, 0, mbits, h, w, ps, c->bits_stride, n, ebits) == 0;
-            partials = two_partials = merged_done;
-        }
-        if (!merged_done)
-          merged_done = launch_bilateral_bits(s, thR, p->ksize_r, p->C_r, thB, p->ksize_b, p->C_b, B, p->ksize_noise,
-                                            p->C_noise, p->noise_thresh, p->mask_noise ? 1 : 0, mbits, h, w, ps,
-                                            c->bits_stride, n) == 0;
-        if (!merged_done) {              // tile + halo exceeds the LDS: one plane at a time
-            { int rc = scratch(P_T1, t1); if (!rc) rc = scratch(P_T2, t2); if (rc) return rc; }
-            launch_bilateral(s, thR, t1, h, w, p->ksize_r, p->C_r, 0, 255, 0, ps, n);
-            launch_bilateral(s, thB, t2, h, w, p->ksize_b, p->C_b, 0, 255, 0, ps, n);
-        }
-    } else {
-        StageScope t(c, ST_THRESHOLD, s);
-        // running box sums, both planes in one launch, bit planes out (merged on the way into the open); the per-pixel
-        // window kernel for what that does not take (window > 63, a width that is not a multiple of 4, the greenery mask)
-        if (!p->mask_noise && launch_adaptive_walk(s, R, p->ksize_r, p->C_r, mbits, B, p->ksize_b, p->C_b, ebits, h, w, ps, c->bits_stride, n)) {
-            merged_done = true;
-            partials = true;
-            two_partials = true;
-        } else {
-            { int rc = scratch(P_T1, t1); if (!rc) rc = scratch(P_T2, t2); if (rc) return rc; }
-            launch_adaptive_mean(s, R, t1, h, w, p->ksize_r, p->C_r, ps, n);
-            launch_adaptive_mean(s, B, t2, h, w, p->ksize_b, p->C_b, ps, n);
-        }
-        c->last_adaptive_path = two_partials ? 1 : 0;
-    }
-    if (!merged_done) {
-        { const int rc = scratch(P_T3, t3); if (rc) return rc; }
-        if (p->mask_noise) {
-            StageScope t(c, ST_THRESHOLD, s);
-            launch_bilateral(s, B, t3, h, w, p->ksize_noise, p->C_noise, 0, 255, 0, ps, n);
-        }
-        StageScope t(c, ST_MERGE, s);
-        launch_pack_merge(s, t1, t2, B, t3, p->noise_thresh, p->mask_noise ? 1 : 0, mbits, h, w, ps, c->bits_stride, n);
-    }
-    { StageScope t(c, ST_OPEN, s);
-      unsigned long long* obits = c->d_bits_open + (size_t)first * c->bits_stride;
-      bool opened = false;
-      // one pass over the words; a handful of frames is latency-bound and better off with the wide, shallow kernels
-      if (!u8_mask && n >= 16)
-          opened = launch_merge_open5(s, mbits, partials ? ebits : nullptr, two_partials ? nullptr : tbits, two_partials ? nullptr : ubits, obits,
-                                      h, w, c->bits_stride, n, nbits1, nbits2);
-      // a few frames: the OR and the open in one launch of small workgroups (the one-frame chain is made of launch gaps: three
-      // kernels of 5 us here; LT_OPEN_SMALL=0 restores them)
-      if (!opened && !u8_mask && n <= 4)
-          opened = launch_or_open5_small(s, mbits, partials ? ebits : nullptr, (!partials || two_partials) ? nullptr : tbits,
-                                         (!partials || two_partials) ? nullptr : ubits, obits, h, w, c->bits_stride, n, nbits1, nbits2);
-      if (!opened) {
-          if (partials) launch_or4_bits(s, mbits, ebits, two_partials ? ebits : tbits, two_partials ? ebits : ubits, h, w, c->bits_stride, n, nbits1, nbits2);
-          if (u8_mask) launch_open5_bits(s, mbits, ebits, mask, h, w, ps, c->bits_stride, n);
-          else launch_open5_to_bits(s, mbits, ebits, obits, h, w, c->bits_stride, n);
-      } }
-    (void)t0;
-    HIP_TRY(hipGetLastError());
     return LT_OK;
 }
 
@@ -613,7 +408,7 @@ int prepare_search(lt_ctx* c, const lt_search_params* p, bool band, SearchGeom& 
 // The searches read the opened bit plane of slots [first, first + n) when all of them have one and the kernel that will run for
 // this geometry takes it (mode 0: sliding window, 1: band); else the u8 masks (ensure_u8_masks).
 bool slot_reads_bits(const lt_ctx* c, const SearchGeom& g, int mode, int first, int n) {
-    return masks_have_bits(c, first, n) && (mode == 0 ? sws_fit_takes_bits(g, c->plane_bytes) : band_fit_takes_bits(g, c->plane_bytes));
+    return masks_have_bits(c, first, n) && (mode == 0 ? sws_fit_takes_bits(g, c->masks.plane_bytes) : band_fit_takes_bits(g, c->masks.plane_bytes));
 }
 
 // The streams that carry the slot slices' kernels.  The HIP runtime multiplexes the streams of a process onto a
@@ -814,8 +609,8 @@ int lt_create(const lt_calib* calib, int device, lt_ctx** out) {
     c->yuv_stride = (c->yuv_bytes + 15) & ~(size_t)15;
     c->und_bytes = (size_t)c->fe.nrows * calib->img_w * 3;   // as returned by lt_download_undistorted (RGB)
     c->und_px = (size_t)c->fe.nrows * calib->img_w;
-    c->plane_bytes = (size_t)calib->warp_h * calib->warp_w;
-    c->bev_bytes = c->plane_bytes * 3;
+    c->masks.set_geometry(calib->warp_h, calib->warp_w);
+    c->bev_bytes = c->masks.plane_bytes * 3;
     *out = c;
     return LT_OK;
 }
@@ -927,19 +722,7 @@ int lt_reserve(lt_ctx* c, int capacity) {
     c->direct_upload = -1;               // a new frame buffer: whether the host can write it is found out by the first small upload
     if (c->in_layout != LT_INPUT_RGB && (rc = dev_alloc(&c->d_yuv, n * c->yuv_stride + 16))) { free_slots(c); return rc; }
     if ((rc = dev_alloc(&c->d_und, (size_t)((n + 1) / 2) * 2 * c->und_px))) { free_slots(c); return rc; }
-    for (int i : {(int)P_R, (int)P_B, (int)P_THR, (int)P_THB, (int)P_T0})     // the others when a path that uses them runs (ensure_plane)
-        if ((rc = dev_alloc(&c->d_plane[i], n * c->plane_bytes))) { free_slots(c); return rc; }
-    c->bits_stride = (size_t)c->calib.warp_h * ((c->calib.warp_w + 63) / 64);
-    if ((rc = dev_alloc(&c->d_bits_merged, n * c->bits_stride))) { free_slots(c); return rc; }
-    if ((rc = dev_alloc(&c->d_bits_eroded, n * c->bits_stride))) { free_slots(c); return rc; }
-    if ((rc = dev_alloc(&c->d_bits_open, n * c->bits_stride))) { free_slots(c); return rc; }
-    if ((rc = dev_alloc(&c->d_bits_tmp, n * c->bits_stride))) { free_slots(c); return rc; }
-    if ((rc = dev_alloc(&c->d_bits_tmp2, n * c->bits_stride))) { free_slots(c); return rc; }
-    c->th_pitch = (c->calib.warp_w + 63) & ~63;
-    c->th_pad_bytes = (size_t)c->calib.warp_h * c->th_pitch;
-    for (auto& q : c->d_th_pad)
-        if ((rc = dev_alloc(&q, n * c->th_pad_bytes))) { free_slots(c); return rc; }
-    c->th_padded.assign(n, 0);
+    if ((rc = c->masks.reserve(capacity, true))) { free_slots(c); return rc; }
     c->mask_bits_ok.assign(n, 0);
     c->mask_u8_ok.assign(n, 1);          // zero-filled below
     c->frame_full.assign(n, 0);
@@ -1001,8 +784,8 @@ int lt_get_info(lt_ctx* c, lt_info* out) {
     out->max_pixels_per_side = c->maxpix;
     out->max_levels = c->maxlev;
     // compulsory input rows (full width, 3 B/px) + the mask written once
-    out->alg_bytes_mask = (int64_t)c->fe.nrows * c->calib.img_w * 3 + (int64_t)c->plane_bytes;
-    out->alg_bytes_search = (int64_t)c->plane_bytes + (int64_t)sizeof(lt_lane_record);
+    out->alg_bytes_mask = (int64_t)c->fe.nrows * c->calib.img_w * 3 + (int64_t)c->masks.plane_bytes;
+    out->alg_bytes_search = (int64_t)c->masks.plane_bytes + (int64_t)sizeof(lt_lane_record);
     std::snprintf(out->device_name, sizeof out->device_name, "%s", c->prop.name[0] ? c->prop.name : c->prop.gcnArchName);
     return LT_OK;
 }
@@ -1581,8 +1364,8 @@ int lt_upload_masks(lt_ctx* c, const uint8_t* masks, int first, int n) {
     if (!masks) return fail(LT_ERR_INVALID, "null masks");
     if ((rc = set_device(c))) return rc;
     if ((rc = sync_all(c))) return rc;
-    if ((rc = ensure_plane(c, P_MASK))) return rc;
-    HIP_TRY(hipMemcpyAsync(slot_mask(c, first), masks, (size_t)n * c->plane_bytes,
+    if ((rc = ensure_mask_plane(c))) return rc;
+    HIP_TRY(hipMemcpyAsync(slot_mask(c, first), masks, (size_t)n * c->masks.plane_bytes,
                            hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->have_mask = true;
@@ -1639,7 +1422,7 @@ int lt_download_masks(lt_ctx* c, int first, int n, uint8_t* masks) {
     if (rc) return rc;
     if ((rc = set_device(c))) return rc;
     if ((rc = ensure_u8_masks(c, first, n))) return rc;
-    return download(c, slot_mask(c, first), masks, (size_t)n * c->plane_bytes);
+    return download(c, slot_mask(c, first), masks, (size_t)n * c->masks.plane_bytes);
 }
 
 int lt_download_plane(lt_ctx* c, int plane, int first, int n, uint8_t* out) {
@@ -1654,10 +1437,10 @@ int lt_download_plane(lt_ctx* c, int plane, int first, int n, uint8_t* out) {
     if (plane == LT_PLANE_MERGED) {   // kept bit-packed on the device; expand on demand
         if ((rc = set_device(c))) return rc;
         if ((rc = sync_all(c))) return rc;
-        if ((rc = ensure_plane(c, P_MERGED))) return rc;
-        launch_bits_to_u8(c->stream, c->d_bits_merged + (size_t)first * c->bits_stride,
-                          c->d_plane[P_MERGED] + (size_t)first * c->plane_bytes, c->calib.warp_h, c->calib.warp_w,
-                          c->plane_bytes, c->bits_stride, n);
+        if ((rc = c->masks.ensure_plane(P_MERGED))) return rc;
+        launch_bits_to_u8(c->stream, c->masks.d_bits_merged + (size_t)first * c->masks.bits_stride,
+                          c->masks.d_plane[P_MERGED] + (size_t)first * c->masks.plane_bytes, c->calib.warp_h, c->calib.warp_w,
+                          c->masks.plane_bytes, c->masks.bits_stride, n);
     }
     if (plane == LT_PLANE_TOPHAT_R || plane == LT_PLANE_TOPHAT_B) {   // slot by slot: the current copy may be the padded one
         if (!out) return fail(LT_ERR_INVALID, "null output buffer");
@@ -1665,18 +1448,18 @@ int lt_download_plane(lt_ctx* c, int plane, int first, int n, uint8_t* out) {
         if ((rc = sync_all(c))) return rc;
         const int w = c->calib.warp_w, h = c->calib.warp_h, q = plane == LT_PLANE_TOPHAT_R ? 0 : 1;
         for (int i = first; i < first + n; ++i) {
-            uint8_t* dst = out + (size_t)(i - first) * c->plane_bytes;
-            if (i < (int)c->th_padded.size() && c->th_padded[(size_t)i])
-                HIP_TRY(hipMemcpy2DAsync(dst, (size_t)w, c->d_th_pad[q] + (size_t)i * c->th_pad_bytes, (size_t)c->th_pitch, (size_t)w,
+            uint8_t* dst = out + (size_t)(i - first) * c->masks.plane_bytes;
+            if (i < (int)c->masks.th_padded.size() && c->masks.th_padded[(size_t)i])
+                HIP_TRY(hipMemcpy2DAsync(dst, (size_t)w, c->masks.d_th_pad[q] + (size_t)i * c->masks.th_pad_bytes, (size_t)c->masks.th_pitch, (size_t)w,
                                          (size_t)h, hipMemcpyDeviceToHost, c->stream));
             else
-                HIP_TRY(hipMemcpyAsync(dst, c->d_plane[map[plane]] + (size_t)i * c->plane_bytes, c->plane_bytes,
+                HIP_TRY(hipMemcpyAsync(dst, c->masks.d_plane[map[plane]] + (size_t)i * c->masks.plane_bytes, c->masks.plane_bytes,
                                        hipMemcpyDeviceToHost, c->stream));
         }
         HIP_TRY(hipStreamSynchronize(c->stream));
         return LT_OK;
     }
-    return download(c, c->d_plane[map[plane]] + (size_t)first * c->plane_bytes, out, (size_t)n * c->plane_bytes);
+    return download(c, c->masks.d_plane[map[plane]] + (size_t)first * c->masks.plane_bytes, out, (size_t)n * c->masks.plane_bytes);
 }
 
 int lt_download_undistorted(lt_ctx* c, int first, int n, uint8_t* out) {
@@ -2008,7 +1791,8 @@ static int mask_run_impl(lt_ctx* c, int first, int n, const lt_filter_params* p,
     if ((rc = validate_filter(p))) return rc;
     if ((rc = set_device(c))) return rc;
     if (n == 0) return LT_OK;
-    const size_t ps = c->plane_bytes;
+    const size_t ps = c->masks.plane_bytes;
+    const ChainEnv env = chain_env(c);
     rc = for_each_slice(c, first, n, [&](hipStream_t st, int f0, int m) {
         // the front end -- unless the caller asked for a RE-run (lt_mask_rerun: the second try of a frame, other filter parameters
         // over the same bird's-eye planes) and these slots' planes are those of the frames they hold
@@ -2029,11 +1813,11 @@ static int mask_run_impl(lt_ctx* c, int first, int n, const lt_filter_params* p,
             { int mrc = n == 1 ? note_range_frame(c, c->readers, st, f0, f0 + m) : note_range(c->readers, st, f0, f0 + m); if (mrc) return mrc; }
             { StageScope t(c, ST_WARP_SPLIT, st);
               launch_warp_split(st, c->d_und, c->und_px, f0, c->d_wxy, c->d_wfrac, c->fe, c->d_gamma,
-                                c->d_cbrt, c->d_coef, c->d_plane[P_R] + (size_t)f0 * ps, c->d_plane[P_B] + (size_t)f0 * ps,
+                                c->d_cbrt, c->d_coef, c->masks.d_plane[P_R] + (size_t)f0 * ps, c->masks.d_plane[P_B] + (size_t)f0 * ps,
                                 ps, m); }
             for (int i = f0; i < f0 + m && i < (int)c->front_ok.size(); ++i) c->front_ok[(size_t)i] = 1;
         }
-        int frc = run_filter_chain(c, st, f0, m, p, c->calib.warp_h, c->calib.warp_w, n);
+        int frc = run_mask_chain(c->masks, env, st, f0, m, p, c->calib.warp_h, c->calib.warp_w, n);
         return frc ? frc : note_written_frame(c, st, f0, f0 + m, n);
     });
     if (rc) return rc;
@@ -2052,13 +1836,14 @@ int lt_filter_run(lt_ctx* c, int first, int n, const lt_filter_params* p) {
     if ((rc = set_device(c))) return rc;
     if (!c->d_bev) return fail(LT_ERR_STATE, "lt_upload_bev has not been called");
     if (n == 0) return LT_OK;
-    const size_t ps = c->plane_bytes;
+    const size_t ps = c->masks.plane_bytes;
+    const ChainEnv env = chain_env(c);
     front_stale(c, first, n);            // the planes become the uploaded bird's-eye image's
     rc = for_each_slice(c, first, n, [&](hipStream_t st, int f0, int m) {
         { StageScope t(c, ST_SPLIT_BEV, st);
           launch_split_bev(st, c->d_bev + (size_t)f0 * c->bev_bytes, c->bev_bytes, (int)ps, c->d_gamma, c->d_cbrt,
-                           c->d_coef, c->d_plane[P_R] + (size_t)f0 * ps, c->d_plane[P_B] + (size_t)f0 * ps, ps, m); }
-        int frc = run_filter_chain(c, st, f0, m, p, c->calib.warp_h, c->calib.warp_w, n);
+                           c->d_coef, c->masks.d_plane[P_R] + (size_t)f0 * ps, c->masks.d_plane[P_B] + (size_t)f0 * ps, ps, m); }
+        int frc = run_mask_chain(c->masks, env, st, f0, m, p, c->calib.warp_h, c->calib.warp_w, n);
         return frc ? frc : note_written(c, st, f0, f0 + m);
     });
     if (rc) return rc;
@@ -2069,11 +1854,11 @@ int lt_filter_run(lt_ctx* c, int first, int n, const lt_filter_params* p) {
 
 // the range forms' kernels over slots [f0, f0 + m), by their slot addresses (the list form's fallback: one slot at a time)
 static void launch_sws_slots(lt_ctx* c, hipStream_t st, const SearchGeom& g, const MaskBits& mb, int f0, int m) {
-    launch_sws_fit(st, slot_mask(c, f0), c->plane_bytes, mb, g, slot_band_sums(c, f0, g.nbands), slot_pix(c, f0), slot_cent(c, f0),
+    launch_sws_fit(st, slot_mask(c, f0), c->masks.plane_bytes, mb, g, slot_band_sums(c, f0, g.nbands), slot_pix(c, f0), slot_cent(c, f0),
                    slot_rec(c, f0), m);
 }
 static void launch_band_slots(lt_ctx* c, hipStream_t st, const SearchGeom& g, const BandPrev& bp, const MaskBits& mb, int f0, int m) {
-    launch_band_fit(st, slot_mask(c, f0), c->plane_bytes, mb, g, slot_prev(c, f0), bp, slot_pix(c, f0), slot_rec(c, f0), m);
+    launch_band_fit(st, slot_mask(c, f0), c->masks.plane_bytes, mb, g, slot_prev(c, f0), bp, slot_pix(c, f0), slot_rec(c, f0), m);
 }
 
 int lt_sws_fit_run(lt_ctx* c, int first, int n, const lt_search_params* p) {
@@ -2131,7 +1916,7 @@ int lt_band_fit_run(lt_ctx* c, int first, int n, const lt_search_params* p, cons
         unsigned ticket = ++c->rec_ticket_counter;
         if (!ticket) ticket = ++c->rec_ticket_counter;      // 0 means "no ticket"
         if (n == 1 && !(one_env && one_env[0] == '0') &&
-            launch_band_fit_one(st, mb, g, bp, slot_pix(c, f0), slot_rec(c, f0), c->plane_bytes, reinterpret_cast<const int*>(c->d_prev),
+            launch_band_fit_one(st, mb, g, bp, slot_pix(c, f0), slot_rec(c, f0), c->masks.plane_bytes, reinterpret_cast<const int*>(c->d_prev),
                                 mirror, ticket)) {
             if (mirror) {                    // the kernel itself leaves a copy of the record in page-locked memory, and its ticket
                 c->rec_mirror_slot = f0;
@@ -2187,7 +1972,7 @@ int lt_search_fit_list(lt_ctx* c, int n, const lt_search_item* items, const lt_s
     std::stable_partition(list.begin(), list.end(), [](const lt_search_item& it) { return it.mode == 0; });
     bool bits = true;
     for (const auto& it : list) bits = bits && masks_have_bits(c, it.slot, 1);
-    const bool one_launch = bits && search_list_supported(n_sws > 0 ? &gs : nullptr, n_sws < n ? &gb : nullptr, c->plane_bytes);
+    const bool one_launch = bits && search_list_supported(n_sws > 0 ? &gs : nullptr, n_sws < n ? &gb : nullptr, c->masks.plane_bytes);
     auto geom = [&](const lt_search_item& it) -> const SearchGeom& { return it.mode == 0 ? gs : gb; };
     if (!one_launch)
         for (const auto& it : list)
@@ -2225,7 +2010,7 @@ int lt_search_fit_list(lt_ctx* c, int n, const lt_search_item* items, const lt_s
         {
             StageScope t(c, n_sws > 0 ? ST_SWS_FIT : ST_BAND_FIT, st);
             // (the whole buffers: the kernel addresses each item's slot itself)
-            launch_search_list(st, c->d_items, n, n_sws, c->d_plane[P_MASK], c->plane_bytes, slot_bits(c, 0, true), gs, gb, c->d_band_sums,
+            launch_search_list(st, c->d_items, n, n_sws, c->masks.d_plane[P_MASK], c->masks.plane_bytes, slot_bits(c, 0, true), gs, gb, c->d_band_sums,
                                c->d_pix, c->d_cent, c->d_rec);
         }
         HIP_TRY(hipEventRecord(c->items_ev, st));         // behind the last kernel that reads d_items
@@ -2421,37 +2206,22 @@ int lt_filter_lane_points(lt_ctx* c, const uint8_t* bev, int h, int w, const lt_
     if (rc) return rc;
     if (h < 1 || w < 1 || h > 16384 || w > 4096) return fail(LT_ERR_INVALID, "bad image size (width <= 4096, height <= 16384)");
     if ((rc = set_device(c))) return rc;
-    // a private one-slot arena of the requested size (the image may differ from the calibration's BEV size)
-    lt_ctx tmp;
-    tmp.device = c->device;
-    tmp.stream = c->stream;
-    tmp.se5 = c->se5; tmp.se29 = c->se29; tmp.se55 = c->se55;
-    tmp.brute_tophat = c->brute_tophat;
-    tmp.plane_bytes = (size_t)h * w;
-    tmp.bits_stride = (size_t)h * ((w + 63) / 64);
-    tmp.capacity = 1;
+    // a private one-slot arena of the requested size (the image may differ from the calibration's BEV size): whatever the chain
+    // allocates in it is freed with it, when this call returns
+    MaskArena arena;
+    arena.set_geometry(h, w);
+    const size_t ps = arena.plane_bytes;
     uint8_t* d_bev = nullptr;
-    auto cleanup = [&]() {
-        for (auto& q : tmp.d_plane) dev_free(q);
-        dev_free(tmp.d_bits_merged);
-        dev_free(tmp.d_bits_eroded);
-        dev_free(d_bev);
-        tmp.stream = nullptr;
-    };
-    for (int i = 0; i < P_COUNT; ++i)
-        if ((rc = dev_alloc(&tmp.d_plane[i], tmp.plane_bytes))) { cleanup(); return rc; }
-    if ((rc = dev_alloc(&d_bev, tmp.plane_bytes * 3))) { cleanup(); return rc; }
-    if ((rc = dev_alloc(&tmp.d_bits_merged, tmp.bits_stride))) { cleanup(); return rc; }
-    if ((rc = dev_alloc(&tmp.d_bits_eroded, tmp.bits_stride))) { cleanup(); return rc; }
-    hipError_t e = hipMemcpyAsync(d_bev, bev, tmp.plane_bytes * 3, hipMemcpyHostToDevice, c->stream);
+    if ((rc = arena.reserve(1, false)) || (rc = dev_alloc(&d_bev, ps * 3))) return rc;
+    const ChainEnv env{&c->se29, &c->se55, c->brute_tophat};   // no batch kernels, no stage timing, nobody asks for the route
+    hipError_t e = hipMemcpyAsync(d_bev, bev, ps * 3, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
-        launch_split_bev(c->stream, d_bev, tmp.plane_bytes * 3, (int)tmp.plane_bytes, c->d_gamma, c->d_cbrt, c->d_coef,
-                         tmp.d_plane[P_R], tmp.d_plane[P_B], tmp.plane_bytes, 1);
-        rc = run_filter_chain(&tmp, c->stream, 0, 1, p, h, w, 1, true);
-        if (rc == LT_OK) e = hipMemcpyAsync(mask, tmp.d_plane[P_MASK], tmp.plane_bytes, hipMemcpyDeviceToHost, c->stream);
+        launch_split_bev(c->stream, d_bev, ps * 3, (int)ps, c->d_gamma, c->d_cbrt, c->d_coef, arena.d_plane[P_R], arena.d_plane[P_B], ps, 1);
+        rc = run_mask_chain(arena, env, c->stream, 0, 1, p, h, w, 1, true);
+        if (rc == LT_OK) e = hipMemcpyAsync(mask, arena.d_plane[P_MASK], ps, hipMemcpyDeviceToHost, c->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    cleanup();
+    dev_free(d_bev);
     if (rc) return rc;
     if (e != hipSuccess) return fail(LT_ERR_HIP, "filter_lane_points failed: %s", hipGetErrorString(e));
     return LT_OK;

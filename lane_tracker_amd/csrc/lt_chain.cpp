@@ -68,7 +68,7 @@ int lt_band_fit_chain_run(lt_ctx* c, int first, int n, const lt_search_params* p
     if (!c->have_mask) return fail(LT_ERR_STATE, "no mask in the slots: run lt_mask_run or lt_upload_masks first");
     SearchGeom g;
     if ((rc = prepare_search(c, p, true, g))) return rc;
-    if (!band_chain_supported(g, c->plane_bytes))
+    if (!band_chain_supported(g, c->masks.plane_bytes))
         return fail(LT_ERR_STATE, "chained band search needs a band of at most 64 columns (2 * bandwidth + 2) and a mask width that is a multiple of 4");
     if (n == 0) return LT_OK;
     BandPrev bp;
@@ -93,7 +93,7 @@ int lt_band_fit_chain_run(lt_ctx* c, int first, int n, const lt_search_params* p
         return rc;
     {
         StageScope t(c, ST_BAND_FIT, c->search);
-        launch_band_chain(c->search, slot_mask(c, first), c->plane_bytes, slot_bits(c, first, use_bits), g, seed ? nullptr : slot_rec(c, first - 1),
+        launch_band_chain(c->search, slot_mask(c, first), c->masks.plane_bytes, slot_bits(c, first, use_bits), g, seed ? nullptr : slot_rec(c, first - 1),
                           bp, slot_pix(c, first), slot_rec(c, first), n, c->d_cancel, *c->h_cancel);
     }
     HIP_TRY(hipGetLastError());

@@ -1,5 +1,6 @@
 // The context behind the C ABI (struct lt_ctx) and the helpers its translation units share:
-//   lt_api.cpp     -- create / destroy / reserve, uploads, downloads, the mask chain, the searches, measurement
+//   lt_api.cpp     -- create / destroy / reserve, uploads, downloads, the searches, measurement
+//   lt_mask_chain.cpp -- the mask chain (top-hats, thresholds, merge + 5x5 open) and the arena that owns its device memory
 //   lt_memory.cpp  -- device-memory cache, page-locked host memory, the host copy threads
 //   lt_present.cpp -- presentation stage: lane overlay, text, annotated frames on their way back
 //   lt_chain.cpp   -- the chained band search of a stream (tickets, cancel, collect)
@@ -31,6 +32,47 @@ enum Stage {
 
 enum Plane { P_R = 0, P_B, P_THR, P_THB, P_MERGED, P_MASK, P_T0, P_T1, P_T2, P_T3, P_COUNT };
 
+// The device memory the mask chain (lt_mask_chain.cpp) reads and writes, for `capacity` slots of h x w pixels: a context holds
+// one for its slots, lt_filter_lane_points a one-slot one for the length of a call.  Whatever the chain allocates on the way
+// lands here, and release() is the only place that frees any of it.
+struct MaskArena {
+    int capacity = 0;
+    size_t plane_bytes = 0;           // h * w
+    size_t bits_stride = 0;           // u64 words per slot of a bit plane: 1 bit / pixel, wpr words per row
+    uint8_t* d_plane[P_COUNT] = {};   // P_R, P_B, P_THR, P_THB, P_T0 from reserve(); the others on first use (ensure_plane)
+    unsigned long long *d_bits_merged = nullptr, *d_bits_eroded = nullptr;
+    unsigned long long* d_bits_open = nullptr;    // the opened mask as the chain leaves it (what the searches read)
+    unsigned long long* d_bits_tmp = nullptr;     // third and fourth partial plane of the walking threshold kernels
+    unsigned long long* d_bits_tmp2 = nullptr;
+    // Top-hat planes with a 64-byte-multiple row pitch: what the walking threshold kernels read (every 64-byte piece of
+    // a row is one aligned sector; with the image width as pitch the horizontal pass fetched every sector twice).
+    // th_padded[slot] says which copy of the slot's top-hat planes is current (lt_download_plane).
+    uint8_t* d_th_pad[2] = {nullptr, nullptr};
+    size_t th_pad_bytes = 0;
+    int th_pitch = 0;
+    std::vector<uint8_t> th_padded;
+    // mask_noise through the walking kernels (allocated by the first such call, ensure_noise_buffers): the raw Lab-b plane
+    // in the padded layout (the 55x55 top-hat launch stores its minuend there) and the two greenery-mask bit planes
+    uint8_t* d_b_pad = nullptr;
+    unsigned long long *d_bits_n1 = nullptr, *d_bits_n2 = nullptr;
+    // the eroded R plane of a one- or two-frame chain: two planes per stream that can run one (ensure_side_scratch)
+    static constexpr int SIDE_LANES = 10;         // one per slice stream (up to 8), one for every other stream
+    uint8_t* d_side_scratch = nullptr;
+
+    MaskArena() = default;
+    MaskArena(const MaskArena&) = delete;
+    MaskArena& operator=(const MaskArena&) = delete;
+    ~MaskArena() { release(); }
+    void set_geometry(int h, int w);              // the sizes above; allocates nothing
+    // the planes every call needs; batch: also the opened bit plane and what the walking kernels of large calls read and write
+    int reserve(int slots, bool batch);
+    void release();                               // frees everything; the geometry stays
+    bool walk_planes() const { return d_th_pad[0] && d_th_pad[1] && d_bits_tmp && d_bits_tmp2; }
+    int ensure_plane(int idx);
+    int ensure_noise_buffers();
+    int ensure_side_scratch();
+};
+
 }  // namespace lt
 
 using lt::P_COUNT;
@@ -59,7 +101,7 @@ struct lt_ctx {
     int32_t* d_coef = nullptr;
     // slots
     int capacity = 0;
-    size_t frame_bytes = 0, und_bytes = 0, plane_bytes = 0, bev_bytes = 0;
+    size_t frame_bytes = 0, und_bytes = 0, bev_bytes = 0;
     uint8_t *d_frames = nullptr, *d_bev = nullptr;
     // YUV 4:2:0 input (lt_set_input_format): the caller's layout, the five conversion coefficients, and per slot a staging frame
     // of yuv_bytes = h * w * 3 / 2 bytes in that layout, yuv_stride (a multiple of 16) apart, 16 bytes of padding behind the last
@@ -78,23 +120,7 @@ struct lt_ctx {
     std::vector<uint8_t> attached;
     uint32_t* d_und = nullptr;        // undistorted camera rows [r0, r0+nrows), one RGBX dword per pixel, slots 2p / 2p+1 interleaved (und_slot_base)
     size_t und_px = 0;                // pixels per slot of d_und
-    uint8_t* d_plane[P_COUNT] = {};   // P_R, P_B, P_THR, P_THB, P_T0 with the slots; the others on first use (ensure_plane)
-    uint8_t* d_side_scratch = nullptr;     // the eroded R plane of a one- or two-frame chain: two planes per stream that can run one (run_filter_chain)
-    unsigned long long *d_bits_merged = nullptr, *d_bits_eroded = nullptr;   // 1 bit / pixel, wpr words per row
-    unsigned long long* d_bits_open = nullptr;    // the opened mask as the mask chain leaves it (what the searches read)
-    unsigned long long* d_bits_tmp = nullptr;     // third and fourth partial plane of the walking threshold kernels
-    unsigned long long* d_bits_tmp2 = nullptr;
-    // Top-hat planes with a 64-byte-multiple row pitch: what the walking threshold kernels read (every 64-byte piece of
-    // a row is one aligned sector; with the image width as pitch the horizontal pass fetched every sector twice).
-    // th_padded[slot] says which copy of the slot's top-hat planes is current (lt_download_plane).
-    uint8_t* d_th_pad[2] = {nullptr, nullptr};
-    size_t th_pad_bytes = 0;
-    int th_pitch = 0;
-    std::vector<uint8_t> th_padded;
-    // mask_noise through the walking kernels (allocated by the first such call, ensure_noise_buffers): the raw Lab-b plane
-    // in the padded layout (the 55x55 top-hat launch stores its minuend there) and the two greenery-mask bit planes
-    uint8_t* d_b_pad = nullptr;
-    unsigned long long *d_bits_n1 = nullptr, *d_bits_n2 = nullptr;
+    lt::MaskArena masks;              // the mask chain's device memory, one block of each kind for the whole capacity
     int last_threshold_path = -1;                 // lt_last_threshold_path
     int last_adaptive_path = -1;                  // 'neighborhood' calls: 1 = running box sums (k_adaptive_walk.hip), 0 = per-pixel windows
     // The walking threshold kernels are long serial walks (a wave covers half an image row or column): they win once a
@@ -114,7 +140,6 @@ struct lt_ctx {
     // front end, cleared by every upload of camera rows and by lt_filter_run.  A second lt_mask_run over such slots with other
     // filter parameters (the second try of a frame, lane_tracker.py:1081-1101) skips the undistortion and the warp: same planes.
     std::vector<uint8_t> front_ok;
-    size_t bits_stride = 0;                                                  // u64 words per slot
     lt_lane_record* d_rec = nullptr;
     double* d_prev = nullptr;
     uint32_t* d_pix = nullptr;
@@ -255,10 +280,10 @@ namespace lt {
 inline uint8_t* slot_frame(const lt_ctx* c, int s) { return c->d_frames + (size_t)s * c->frame_bytes; }
 inline uint8_t* slot_yuv(const lt_ctx* c, int s) { return c->d_yuv + (size_t)s * c->yuv_stride; }
 inline YuvCoef yuv_coef_of(const lt_ctx* c) { return YuvCoef{c->yuv_coef[0], c->yuv_coef[1], c->yuv_coef[2], c->yuv_coef[3], c->yuv_coef[4]}; }
-inline uint8_t* slot_mask(const lt_ctx* c, int s) { return c->d_plane[P_MASK] + (size_t)s * c->plane_bytes; }
+inline uint8_t* slot_mask(const lt_ctx* c, int s) { return c->masks.d_plane[P_MASK] + (size_t)s * c->masks.plane_bytes; }
 // the opened bit plane of slot s as the searches take it; use_bits = false: none (they read slot_mask)
 inline MaskBits slot_bits(const lt_ctx* c, int s, bool use_bits) {
-    return MaskBits{use_bits ? c->d_bits_open + (size_t)s * c->bits_stride : nullptr, c->bits_stride, (c->calib.warp_w + 63) / 64};
+    return MaskBits{use_bits ? c->masks.d_bits_open + (size_t)s * c->masks.bits_stride : nullptr, c->masks.bits_stride, (c->calib.warp_w + 63) / 64};
 }
 inline lt_lane_record* slot_rec(const lt_ctx* c, int s) { return c->d_rec + s; }
 inline double* slot_prev(const lt_ctx* c, int s) { return c->d_prev + (size_t)s * 6; }
@@ -322,6 +347,63 @@ void dev_free(T*& p) {
     p = nullptr;
 }
 
+// ---- the mask chain's arena (MaskArena, above) ----------------------------------------------------------------
+inline void MaskArena::set_geometry(int h, int w) {
+    plane_bytes = (size_t)h * w;
+    bits_stride = (size_t)h * ((w + 63) / 64);
+    th_pitch = (w + 63) & ~63;
+    th_pad_bytes = (size_t)h * th_pitch;
+}
+
+inline int MaskArena::reserve(int slots, bool batch) {
+    release();
+    capacity = slots;
+    const size_t n = (size_t)slots;
+    int rc;
+    for (int i : {(int)P_R, (int)P_B, (int)P_THR, (int)P_THB, (int)P_T0})
+        if ((rc = dev_alloc(&d_plane[i], n * plane_bytes))) return rc;
+    for (auto q : {&d_bits_merged, &d_bits_eroded})
+        if ((rc = dev_alloc(q, n * bits_stride))) return rc;
+    if (!batch) return LT_OK;
+    for (auto q : {&d_bits_open, &d_bits_tmp, &d_bits_tmp2})
+        if ((rc = dev_alloc(q, n * bits_stride))) return rc;
+    for (auto& q : d_th_pad)
+        if ((rc = dev_alloc(&q, n * th_pad_bytes))) return rc;
+    th_padded.assign(n, 0);
+    return LT_OK;
+}
+
+inline void MaskArena::release() {
+    for (auto& q : d_plane) dev_free(q);
+    for (auto q : {&d_bits_merged, &d_bits_eroded, &d_bits_open, &d_bits_tmp, &d_bits_tmp2, &d_bits_n1, &d_bits_n2}) dev_free(*q);
+    for (auto q : {&d_th_pad[0], &d_th_pad[1], &d_b_pad, &d_side_scratch}) dev_free(*q);
+    th_padded.clear();
+    capacity = 0;
+}
+
+// Planes only some paths use are allocated when one of those paths runs first (the whole capacity at once): the u8 mask
+// (d_plane[P_MASK]: lt_upload_masks, lt_download_masks, searches outside the bit-plane kernels' limits), the expanded merged
+// plane (lt_download_plane), the scratch planes of the older threshold kernels (P_T1 .. P_T3).  A 768-slot context is 10.4 GB
+// instead of 14.6 -- and device memory that has been used before costs ~16 ms per GB to allocate (the driver clears it: NOTES D.2).
+inline int MaskArena::ensure_plane(int idx) {
+    return d_plane[idx] ? (int)LT_OK : dev_alloc(&d_plane[idx], (size_t)capacity * plane_bytes);
+}
+
+inline int MaskArena::ensure_noise_buffers() {
+    const size_t n = (size_t)capacity;
+    int rc;
+    if (!d_b_pad && (rc = dev_alloc(&d_b_pad, n * th_pad_bytes))) return rc;
+    if (!d_bits_n1 && (rc = dev_alloc(&d_bits_n1, n * bits_stride))) return rc;
+    if (!d_bits_n2 && (rc = dev_alloc(&d_bits_n2, n * bits_stride))) return rc;
+    return LT_OK;
+}
+
+// (per STREAM, not per slot: a context of a thousand slots runs its one- and two-frame calls on a handful of streams -- the
+// slices' streams and the urgent one -- and calls on one stream are ordered)
+inline int MaskArena::ensure_side_scratch() {
+    return d_side_scratch ? (int)LT_OK : dev_alloc(&d_side_scratch, (size_t)SIDE_LANES * 2 * plane_bytes);
+}
+
 // ---- streams, slot ranges, ordering (lt_api.cpp) ---------------------------------------------------------
 int sync_all(lt_ctx* c);
 int note_range(lt_ctx::RangeEvents& r, hipStream_t st, int lo, int hi);
@@ -338,7 +420,6 @@ hipError_t create_compute_stream(hipStream_t* st, int reserved = 0);
 // (stream_get / stream_put -- the per-process stream pool -- are declared in lt_internal.h)
 int download(lt_ctx* c, const void* src, void* dst, size_t bytes);
 int ensure_bev(lt_ctx* c);
-int ensure_plane(lt_ctx* c, int idx);
 int ensure_search_buffers(lt_ctx* c, int maxpix, int maxlev);
 bool masks_have_bits(const lt_ctx* c, int first, int n);
 int ensure_u8_masks(lt_ctx* c, int first, int n);
@@ -419,14 +500,14 @@ int for_each_slice(lt_ctx* c, int first, int n, F fn) {
     return LT_OK;
 }
 
-// RAII-free helper pair: bracket one kernel launch with events when stage timing is on
+// RAII-free helper pair: bracket one kernel launch with events when stage timing is on (c = nullptr: no timing sink, does nothing)
 struct StageScope {
     lt_ctx* c;
     int stage;
     hipStream_t st;
     hipEvent_t a = nullptr, b = nullptr;
-    StageScope(lt_ctx* c_, int stage_, hipStream_t st_ = nullptr) : c(c_), stage(stage_), st(st_ ? st_ : c_->stream) {
-        if (!c->stage_timing) return;
+    StageScope(lt_ctx* c_, int stage_, hipStream_t st_ = nullptr) : c(c_), stage(stage_), st(st_ || !c_ ? st_ : c_->stream) {
+        if (!c || !c->stage_timing) return;
         if (c->ev_used + 2 > c->ev_pool.size()) {
             if (flush_stage_events(c) != LT_OK) return;
             while (c->ev_pool.size() < 256) {
@@ -446,5 +527,22 @@ struct StageScope {
         c->pending.push_back({stage, a, b});
     }
 };
+
+// ---- the mask chain (lt_mask_chain.cpp) -------------------------------------------------------------------
+int validate_filter(const lt_filter_params* p);
+// what the chain takes from a context besides the arena
+struct ChainEnv {
+    const EllipseSE *se29 = nullptr, *se55 = nullptr;   // the brute-force top-hats' footprints
+    bool brute_tophat = false;
+    long long walk_min_pixels = 0;                      // calls of fewer pixels take the tile kernels (lt_ctx::walk_min_pixels)
+    const std::vector<hipStream_t>* streams = nullptr;  // whose position picks a stream's lane of the side scratch; null: the spare lane
+    lt_ctx* timing = nullptr;                           // the context whose stage timers take the launches (StageScope); null: untimed
+    int *threshold_path = nullptr, *adaptive_path = nullptr;   // lt_last_threshold_path / lt_last_adaptive_path; null: nobody asks
+};
+// filter_lane_points() (lane_tracker.py:210-238) on planes P_R / P_B of slots [first, first + n) of the arena, h x w pixels each, on
+// stream s; call_frames: the frames of the whole call this piece belongs to.  The opened mask lands in d_bits_open, or with
+// u8_mask in d_plane[P_MASK] (allocated here if need be).
+int run_mask_chain(MaskArena& a, const ChainEnv& env, hipStream_t s, int first, int n, const lt_filter_params* p, int h, int w,
+                   int call_frames, bool u8_mask = false);
 
 }  // namespace lt

@@ -1,4 +1,4 @@
-// Internal declarations shared by the C-ABI layer (lt_api.cpp), the host table builders
+// Internal declarations shared by the C-ABI layer (lt_api.cpp, lt_mask_chain.cpp), the host table builders
 // (lt_tables.cpp) and the kernel launchers (*.hip).  Not installed; the public ABI is
 // include/lane_tracker_amd.h.
 #pragma once
@@ -164,9 +164,6 @@ void launch_adaptive_mean(hipStream_t s, const uint8_t* src, uint8_t* dst, int h
 bool adaptive_walk_supported(int bs_r, int bs_b, int h, int w, size_t plane_stride);
 bool launch_adaptive_walk(hipStream_t s, const uint8_t* R, int bs_r, int C_r, unsigned long long* out_r, const uint8_t* B, int bs_b,
                           int C_b, unsigned long long* out_b, int h, int w, size_t plane_stride, size_t bits_stride, int n);
-// merged = ((tr | tb) & (use_noise ? (!(labb >= thresh) | noise_bil) : 1)) ? 255 : 0
-void launch_merge(hipStream_t s, const uint8_t* tr, const uint8_t* tb, const uint8_t* labb, const uint8_t* noise_bil,
-                  int noise_thresh, int use_noise, uint8_t* merged, size_t npix, size_t plane_stride, int n);
 
 // bit-plane path (k_threshold.hip): fused bilateral thresholds + merge, u8->bits merge, 5x5 open on bits
 int launch_bilateral_bits(hipStream_t s, const uint8_t* thr, int k_r, int C_r, const uint8_t* thb, int k_b, int C_b,
@@ -178,29 +175,43 @@ void launch_pack_merge(hipStream_t s, const uint8_t* tr, const uint8_t* tb, cons
                        size_t bits_stride, int n);
 void launch_open5_bits(hipStream_t s, const unsigned long long* merged, unsigned long long* eroded, uint8_t* mask, int h,
                        int w, size_t plane_stride, size_t bits_stride, int n);
-// both bilateral thresholds + merge through the long-walk kernels (k_threshold_walk.hip).  The top-hat planes have the row
-// pitch `pitch` (a multiple of 64) and `plane_stride` bytes per frame.  0 = ran, -1 = outside its limits.
-bool bilateral_walk_supported(int k_r, int C_r, int k_b, int C_b, int h, int w, int pitch);
+// What the merged plane of the mask chain is on its way into the 5x5 open (host only):
+//     (dst | more[0] | .. | more[n_more - 1]) & (and0 | and1)        -- the AND term only where the pair is given.
+// dst already holds the first term, and the merged plane is written over it (lt_download_plane(4) reads it there).
+struct MergeInputs {
+    unsigned long long* dst = nullptr;
+    const unsigned long long* more[3] = {nullptr, nullptr, nullptr};
+    int n_more = 0;                                               // 0 (dst is the merged plane), 1 or 3
+    const unsigned long long *and0 = nullptr, *and1 = nullptr;    // both or neither, and with n_more == 3 only (the greenery mask)
+};
+// the planes the kernels read for it -- their NP: 1, 2, 4 or 6 -- or 0 for a value that breaks the rules above (the one place they are checked)
+inline int merge_planes(const MergeInputs& in) {
+    if (!in.dst || (in.n_more != 0 && in.n_more != 1 && in.n_more != 3)) return 0;
+    for (int i = 0; i < 3; ++i)
+        if ((in.more[i] != nullptr) != (i < in.n_more)) return 0;
+    if ((in.and0 != nullptr) != (in.and1 != nullptr) || (in.and0 && in.n_more != 3)) return 0;
+    return in.and0 ? 6 : in.n_more + 1;
+}
+// both bilateral thresholds through the long-walk kernels (k_threshold_walk.hip): four partial bit planes, merged on the way into
+// the open.  The top-hat planes have the row pitch `pitch` (a multiple of 64) and `plane_stride` bytes (a multiple of 64) per
+// frame.  0 = ran, -1 = outside its limits: exactly where bilateral_walk_supported says no.
+bool bilateral_walk_supported(int k_r, int C_r, int k_b, int C_b, int h, int w, int pitch, size_t plane_stride);
 int launch_bilateral_walk(hipStream_t s, const uint8_t* thr, int k_r, int C_r, const uint8_t* thb, int k_b, int C_b,
                           unsigned long long* merged, unsigned long long* s1, unsigned long long* s2, unsigned long long* s3,
-                          int h, int w, int pitch, size_t plane_stride, size_t bits_stride, int n, bool merge);
-void launch_or4_bits(hipStream_t s, unsigned long long* merged, const unsigned long long* s1, const unsigned long long* s2,
-                     const unsigned long long* s3, int h, int w, size_t bits_stride, int n, const unsigned long long* n0 = nullptr,
-                     const unsigned long long* n1 = nullptr);
+                          int h, int w, int pitch, size_t plane_stride, size_t bits_stride, int n);
+// the merge alone, in place (k_or4_bits); nothing to do for a plane that is merged already
+void launch_or4_bits(hipStream_t s, const MergeInputs& in, int h, int w, size_t bits_stride, int n);
 // the greenery mask (lane_tracker.py:223-225) through the walking kernels: noise_h | noise_v = !inRange(b, thresh, 255) |
 // bilateral(b, 65, C_n); `braw` = the raw Lab-b plane with the padded pitch.  0 = ran, -1 = outside its limits.
-bool noise_walk_supported(int k_n, int C_n, int h, int w, int pitch);
+bool noise_walk_supported(int k_n, int C_n, int h, int w, int pitch, size_t plane_stride);
 int launch_noise_walk(hipStream_t s, const uint8_t* braw, int k_n, int C_n, int noise_thresh, unsigned long long* noise_h,
                       unsigned long long* noise_v, int h, int w, int pitch, size_t plane_stride, size_t bits_stride, int n);
-// erode + dilate with the 5x5 ellipse, bit plane in, bit plane out
-// p1 alone: two partial planes.  n0 / n1 (both or neither; with p1..p3 only): the merged plane is (p0 | p1 | p2 | p3) & (n0 | n1)
-bool launch_merge_open5(hipStream_t s, unsigned long long* p0, const unsigned long long* p1, const unsigned long long* p2,
-                        const unsigned long long* p3, unsigned long long* opened, int h, int w, size_t bits_stride, int n,
-                        const unsigned long long* n0 = nullptr, const unsigned long long* n1 = nullptr);
-// ... for a few frames: one launch of small workgroups (k_or_open5_small)
-bool launch_or_open5_small(hipStream_t s, unsigned long long* p0, const unsigned long long* p1, const unsigned long long* p2,
-                        const unsigned long long* p3, unsigned long long* opened, int h, int w, size_t bits_stride, int n,
-                        const unsigned long long* n0 = nullptr, const unsigned long long* n1 = nullptr);
+// merge + erode + dilate with the 5x5 ellipse in one launch, bit planes in, bit plane out (k_merge_open5<NP>: a wave walks down
+// the rows); false: not launched (a row wider than 64 words, a value merge_planes refuses, LT_OPEN5_SEPARATE=1)
+bool launch_merge_open5(hipStream_t s, const MergeInputs& in, unsigned long long* opened, int h, int w, size_t bits_stride, int n);
+// ... for a few frames: one launch of small workgroups (k_or_open5_small<NP>); false: as above, or LT_OPEN_SMALL=0
+bool launch_or_open5_small(hipStream_t s, const MergeInputs& in, unsigned long long* opened, int h, int w, size_t bits_stride, int n);
+// erode + dilate of a merged plane as two launches, bit plane out
 void launch_open5_to_bits(hipStream_t s, const unsigned long long* merged, unsigned long long* eroded,
                           unsigned long long* opened, int h, int w, size_t bits_stride, int n);
 void launch_bits_to_u8(hipStream_t s, const unsigned long long* bits, uint8_t* out, int h, int w, size_t plane_stride,

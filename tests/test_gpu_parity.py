@@ -325,6 +325,25 @@ def test_filter_lane_points_any_size(ctx, nat, oracle, shape):
         assert_same(got, oracle.filter_lane_points(bev, oracle.filter_params(**kw)), f"{shape} {kw}")
 
 
+@pytest.mark.parametrize("kw", [dict(), dict(mask_noise=True), dict(filter_type="neighborhood", C_r=5)],
+                         ids=["bilateral", "bilateral_mask_noise", "neighborhood"])
+def test_filter_lane_points_gives_back_the_device_memory_it_takes(ctx, nat, oracle, kw):
+    """filter_lane_points on a single bird's-eye image runs the mask chain in a one-slot arena of its own: whatever the chain
+    allocates on the way (the 20 planes of eroded-R scratch of the one-frame top-hats, the scratch planes of the per-plane
+    thresholds) is freed with it.  The library's live device bytes after the second and every later call equal those after the
+    first, and the masks stay the oracle's."""
+    rng = np.random.default_rng(5)
+    bev = rng.integers(0, 256, (132, 184, 3), dtype=np.uint8)
+    fp, want = nat.filter_params(**kw), oracle.filter_lane_points(bev, oracle.filter_params(**kw))
+    assert_same(ctx.filter_lane_points(bev, fp), want, f"first call, {kw}")
+    live = nat.device_cache_stats()["live_bytes"]
+    for k in range(2, 6):
+        assert_same(ctx.filter_lane_points(bev, fp), want, f"call {k}, {kw}")
+        now = nat.device_cache_stats()["live_bytes"]
+        print(f"filter_lane_points {kw}: live bytes after call 1: {live}, after call {k}: {now}")
+        assert now == live, f"call {k} left {now - live} more live device bytes than the first, {kw}"
+
+
 BATCH_SETS = {
     "process_defaults": (dict(), dict()),
     # the author's Demo 1 / Demo 3 filter (tracker_settings.md:10-13, 86-89: the greenery mask) with Demo 3's half look-ahead
@@ -638,8 +657,9 @@ def test_fallback_kernel_paths_keep_parity_at_the_reference_geometry(switch):
 
 def test_odd_slot_ranges_and_the_batch_paths_of_the_open_stage(nat, cal, oracle, ref_calib):
     """Slot pairs share the interleaved undistorted rows and the front-end kernels walk pairs: ranges that start or end on
-    an odd slot, and a batch large enough (>= 16 frames) for the fused merge + open pass on an already merged plane
-    (tile threshold kernel: a window size the walking kernels do not have) must give the oracle's planes slot by slot."""
+    an odd slot, and a batch of 21 frames over three streams (slices of 6, 8 and 7) through the tile threshold kernel (a window size
+    the walking kernels do not have) and the separate open kernels a merged plane of more than four frames takes (DESIGN.md
+    section 4, the route table) must give the oracle's planes slot by slot."""
     from lane_tracker_amd import synth
     r = synth.SceneRenderer(cal)
     n = 21
@@ -649,7 +669,7 @@ def test_odd_slot_ranges_and_the_batch_paths_of_the_open_stage(nat, cal, oracle,
     try:
         c.set_streams(3)                                   # slices 0-6, 6-14, 14-21: even boundaries inside an odd capacity
         c.upload_frames(batch)
-        kw = dict(ksize_r=25, C_r=6, ksize_b=31, C_b=4)    # not 15 / 20 / 35: tile kernel, then the fused open of 21 frames
+        kw = dict(ksize_r=25, C_r=6, ksize_b=31, C_b=4)    # not 15 / 20 / 35: tile kernel, then k_erode5_bits + k_dilate5_bits
         c.mask_run(n, nat.filter_params(**kw))
         assert c.last_threshold_path() == 0
         masks, merged = c.download_masks(n), c.download_plane(4, n)

@@ -331,11 +331,10 @@ def test_release_library_reads_the_deployment_switches_and_no_others():
             assert "LT_PROBE_" not in text, f + " carries a timing probe (they live in tools/probes/*.patch)"
             direct = set(re.findall(r"getenv\(\"(LT_[A-Z0-9_]+)\"\)", re.sub(r"LT_EXP_ENV\([^)]*\)", "", text)))
             assert direct <= DEPLOYMENT_SWITCHES, (f, sorted(direct - DEPLOYMENT_SWITCHES))
-    # run_filter_chain reads no switch at all, in either build (its alternatives are gone or are arguments)
-    api = open(os.path.join(ROOT, "lane_tracker_amd", "csrc", "lt_api.cpp")).read()
-    a = api.index("int run_filter_chain(")
-    body = api[a:api.index("\n}\n", a)]
-    assert "getenv" not in body and "LT_EXP_ENV" not in body
+    # the mask chain reads no switch at all, in either build (its alternatives are gone or are arguments): the whole of its file
+    chain = open(os.path.join(ROOT, "lane_tracker_amd", "csrc", "lt_mask_chain.cpp")).read()
+    assert "int run_mask_chain(" in chain
+    assert "getenv" not in chain and "LT_EXP_ENV" not in chain
 
 
 def test_copy_groups_survive_a_fork_and_two_submitters_do_not_starve_each_other():
