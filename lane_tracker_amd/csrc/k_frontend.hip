@@ -25,6 +25,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "front_arith.h"
 #include "lt_internal.h"
 
 namespace lt {
@@ -515,8 +516,15 @@ __device__ __forceinline__ int lab_b_of(int r, int g, int b, const uint16_t* gt,
 __device__ __forceinline__ void stage_lab_tables(uint16_t* s_gamma, uint16_t* s_cbrt, int32_t* s_coef,
                                                  const uint16_t* gamma_tab, const uint16_t* cbrt_tab,
                                                  const int32_t* coeffs) {
-    for (int i = threadIdx.x; i < 256; i += blockDim.x) s_gamma[i] = gamma_tab[i];
-    for (int i = threadIdx.x; i < 3072; i += blockDim.x) s_cbrt[i] = cbrt_tab[i];
+    // 16 bytes per load where the tables allow it (the context's are hipMalloc'ed): 2 loads per thread instead of 13 -- a block
+    // of k_warp_split4 walks a few slot pairs only, and these loads were a third of its vector-memory instructions
+    if (((reinterpret_cast<uintptr_t>(gamma_tab) | reinterpret_cast<uintptr_t>(cbrt_tab)) & 15u) == 0) {
+        for (int i = threadIdx.x; i < 256 / 8; i += blockDim.x) reinterpret_cast<uint4*>(s_gamma)[i] = reinterpret_cast<const uint4*>(gamma_tab)[i];
+        for (int i = threadIdx.x; i < 3072 / 8; i += blockDim.x) reinterpret_cast<uint4*>(s_cbrt)[i] = reinterpret_cast<const uint4*>(cbrt_tab)[i];
+    } else {
+        for (int i = threadIdx.x; i < 256; i += blockDim.x) s_gamma[i] = gamma_tab[i];
+        for (int i = threadIdx.x; i < 3072; i += blockDim.x) s_cbrt[i] = cbrt_tab[i];
+    }
     if (threadIdx.x < 9) s_coef[threadIdx.x] = coeffs[threadIdx.x];
     __syncthreads();
 }
@@ -575,9 +583,12 @@ __device__ __forceinline__ void warp_pixel(const uint32_t* __restrict__ src, con
 #ifndef LT_WARP_WAVES
 #define LT_WARP_WAVES 8
 #endif
-#ifndef LT_WARP_DOT
-#define LT_WARP_DOT 0   // measured: 11 % fewer VALU instructions (324 -> 288 per 8 pixels), the same 0.537 ms per 256 frames -- the kernel is co-bound by the vector-memory pipe
+// LAB_CLAMP: the cube-root table index keeps its clamp to 3071 (false where launch_warp_split's caller has shown it dead for the
+// tables of this context: front_arith.h, lab_clamp_is_dead).
+#ifndef LT_WARP_F32
+#define LT_WARP_F32 0   // the blend as an fp32 fma chain (front_arith.h; exact): measured 0.733 ms against 0.540 -- the byte -> float conversions are 4-cycle instructions and the packed fma form spills; kept for the A/B
 #endif
+template <bool LAB_CLAMP>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LT_WARP_WAVES, LT_WARP_WAVES))) void k_warp_split4(const uint32_t* __restrict__ und, size_t und_px, int first_slot,
                                                     const int16_t* __restrict__ wxy,
                                                     const uint16_t* __restrict__ wfrac, FrontEndGeom g,
@@ -586,13 +597,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LT_WARP_WAV
                                                     const int32_t* __restrict__ coeffs, uint8_t* __restrict__ planeR,
                                                     uint8_t* __restrict__ planeB, size_t plane_stride, int n, int ppb,
                                                     int remap) {
-    __shared__ uint16_t s_gamma[256];
-    __shared__ uint16_t s_cbrt[3072];
+    __shared__ alignas(16) uint16_t s_gamma[256];
+    __shared__ alignas(16) uint16_t s_cbrt[3072];
     __shared__ int32_t s_coef[9];
     // gamma LUT and the Y / Z rows of the matrix folded into one table per channel: s_yz[ch][v] = gamma[v] * (C[3+ch], C[6+ch]),
     // the rounding constant of DESCALE(., 12) added to the red entries -- one 8-byte LDS read per channel replaces a 16-bit
     // read, two multiplies / multiply-adds and the rounding add (the kernel is at 80 % of the VALU issue ceiling)
-    __shared__ uint2 s_yz[3][256];
+    __shared__ fa::YZ s_yz[3][256];
     const size_t quads = ((size_t)g.warp_h * g.warp_w) >> 2;
     const uint32_t id = xcd_block(blockIdx.z * gridDim.x + blockIdx.x, gridDim.x * gridDim.z, remap);
     const uint32_t bz = id / gridDim.x, bx = id - bz * gridDim.x;
@@ -606,7 +617,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LT_WARP_WAV
         const uint32_t gv = gamma_tab[v];
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch)
-            s_yz[ch][v] = make_uint2(gv * (uint32_t)coeffs[3 + ch] + (ch == 0 ? 2048u : 0u), gv * (uint32_t)coeffs[6 + ch] + (ch == 0 ? 2048u : 0u));
+            s_yz[ch][v] = fa::yz_row(gv, coeffs, ch);
     }
     stage_lab_tables(s_gamma, s_cbrt, s_coef, gamma_tab, cbrt_tab, coeffs);
     if (qi >= quads) return;
@@ -627,30 +638,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LT_WARP_WAV
         inside = inside && sx >= 0 && sx + 1 < g.img_w && sy >= g.r0 && sy + 1 < g.r0 + g.nrows && sy + 1 < g.img_h;
     }
     if (inside) {
-        // The four tap weights of a pixel (products of the 5-bit fractions, <= 1024) are frame-independent.  They
-        // are masked to 11 bits on purpose: the compiler folds (a gx + b fx) gy into a (gx gy) + b (fx gy) anyway,
-        // and unless it can see that the weight products are small it multiplies with v_mul_lo_u32 (quarter rate)
-        // instead of v_mul_u32_u24 -- six of them per pixel in the previous version of this loop.
-        uint32_t w00[4], w01[4], w10[4], w11[4];
-        // LT_WARP_DOT: the two-stage form of the same integer, two rows at a time in packed 16-bit lanes --
-        //   (h0, h1) = (top.left, bottom.left) * gx + (top.right, bottom.right) * fx      v_pk_mul_lo_u16 + v_pk_mad_u16  (<= 8160)
-        //   value    = (h0 * gy + h1 * fy + 512) >> 10                                       v_dot2_u32_u16 + shift
-        // with one v_perm_b32 per tap pair to put a channel of the top and the bottom tap into the two lanes: 6 instructions per
-        // channel instead of 4 field extracts + 4 multiply-adds + add + shift.  gx2 / fx2 hold the weight in both lanes.
-        uint32_t gx2[4], fx2[4], gyfy[4];
+        // The four tap weights of a pixel (products of the 5-bit fractions) are frame-independent: floats, scaled so that the
+        // blend is an fma chain of the 2-cycle class that ends in 8 x the value (front_arith.h; exact, the same integer as
+        // (sum_i w_i p_i + 2^9) >> 10).
+#if LT_WARP_F32
+        fa::Weights wt[4];
+#else
+        fa::WeightsI wt[4];
+#endif
         int toff[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int sx = (int16_t)(xyv[i] & 0xffffu), sy = (int16_t)(xyv[i] >> 16);
             toff[i] = (__mul24(sy - g.r0, g.img_w) + sx) * 8;            // byte offset of the left tap inside a pair
-            const uint32_t fx = frv[i] & 31u, fy = frv[i] >> 5, gx = 32u - fx, gy = 32u - fy;
-            w00[i] = (gx * gy) & 0x7ffu;
-            w01[i] = (fx * gy) & 0x7ffu;
-            w10[i] = (gx * fy) & 0x7ffu;
-            w11[i] = (fx * fy) & 0x7ffu;
-            gx2[i] = gx | (gx << 16);
-            fx2[i] = fx | (fx << 16);
-            gyfy[i] = gy | (fy << 16);
+#if LT_WARP_F32
+            wt[i] = fa::weights8((int)(frv[i] & 31u), (int)(frv[i] >> 5));
+#else
+            wt[i] = fa::weights_i((int)(frv[i] & 31u), (int)(frv[i] >> 5));
+#endif
         }
         // Taps and outputs go through buffer descriptors of this walk: descriptor + 32-bit lane offset + scalar
         // pair / frame offset, so no access pays a 64-bit VALU address add.
@@ -679,41 +684,30 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LT_WARP_WAV
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const uint32_t ta = t[i][f], tb = t[i][2 + f], ba = t[4 + i][f], bb = t[4 + i][2 + f];
-                    int rgb[3];
-#if LT_WARP_DOT
-                    typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
-#pragma unroll
-                    for (int ch = 0; ch < 3; ++ch) {
-                        // lanes (top, bottom) of channel ch: bytes ch of the top tap and of the bottom tap, zero-extended
-                        const uint32_t selc = 0x0c000c00u | (uint32_t)ch | ((uint32_t)(4 + ch) << 16);
-                        const u16x2 L = __builtin_bit_cast(u16x2, __builtin_amdgcn_perm(ba, ta, selc));
-                        const u16x2 Rr = __builtin_bit_cast(u16x2, __builtin_amdgcn_perm(bb, tb, selc));
-                        const u16x2 H = L * __builtin_bit_cast(u16x2, gx2[i]) + Rr * __builtin_bit_cast(u16x2, fx2[i]);
-                        rgb[ch] = (int)(__builtin_amdgcn_udot2(H, __builtin_bit_cast(u16x2, gyfy[i]), 512u, false) >> 10);
-                    }
+#if !LT_WARP_F32
+                    // The packed weights stay packed across the loop (8 registers, not 16: with 16 the kernel kept two values in
+                    // scratch and reloaded them for every slot pair, through the memory pipe it is co-bound by): opaque here, so
+                    // the halves are selected inside the loop, by the multiply's own operand select.
+                    fa::WeightsI wq = wt[i];
+                    asm volatile("" : "+v"(wq.top), "+v"(wq.bot));
 #else
-#pragma unroll
-                    for (int ch = 0; ch < 3; ++ch)     // (sum_i w_i p_i + 2^9) >> 10: the same integer as the two-stage blend
-                        rgb[ch] = (int)((((ta >> (8 * ch)) & 255u) * w00[i] + ((tb >> (8 * ch)) & 255u) * w01[i] +
-                                         ((ba >> (8 * ch)) & 255u) * w10[i] + ((bb >> (8 * ch)) & 255u) * w11[i] + 512u) >> 10);
+                    const fa::Weights wq = wt[i];
 #endif
-                    int r = rgb[0], b;
-                    {
-                        const uint2 yr = s_yz[0][rgb[0]], yg = s_yz[1][rgb[1]], yb = s_yz[2][rgb[2]];
-                        int iy = (int)((yr.x + yg.x + yb.x) >> 12), iz = (int)((yr.y + yg.y + yb.y) >> 12);   // sums < 2^24
-                        iy = iy > 3071 ? 3071 : iy;
-                        iz = iz > 3071 ? 3071 : iz;
-                        const int fY = s_cbrt[iy], fZ = s_cbrt[iz];
-                        const int v = (__mul24(200, fY - fZ) + 128 * (1 << 15) + (1 << 14)) >> 15;
-                        b = v < 0 ? 0 : (v > 255 ? 255 : v);
-                    }
+                    // 8 x the blended channel = the byte offset of its row in s_yz[ch]: no shift between blend and table
+                    uint32_t r8 = fa::blend8<0>(ta, tb, ba, bb, wq) & fa::ROW8_MASK;
+                    const uint32_t g8 = fa::blend8<1>(ta, tb, ba, bb, wq) & fa::ROW8_MASK;
+                    const uint32_t b8 = fa::blend8<2>(ta, tb, ba, bb, wq) & fa::ROW8_MASK;
+                    auto row = [&](int ch, uint32_t off) __attribute__((always_inline)) {
+                        return *reinterpret_cast<const fa::YZ*>(reinterpret_cast<const char*>(s_yz[ch]) + off);
+                    };
+                    int b = fa::lab_b_rows<LAB_CLAMP>(row(0, r8), row(1, g8), row(2, b8), s_cbrt);
                     // Opaque to the optimiser on purpose: with the value ranges visible, hipcc (ROCm 7.2) folded the
                     // four byte inserts into a 16-bit combine that leaked bits 16+ of an unshifted Lab value into the
                     // third pixel (caught by the parity test); the barrier costs nothing at run time.
 #ifndef LT_CASE_WARP_NO_BARRIER   // tools/toolchain_cases.sh builds the kernel without it to check whether the case still exists
-                    asm volatile("" : "+v"(r), "+v"(b));
+                    asm volatile("" : "+v"(r8), "+v"(b));
 #endif
-                    oR |= ((uint32_t)r & 255u) << (8 * i);
+                    oR |= i == 0 ? r8 >> 3 : r8 << (8 * i - 3);      // r8 = 8 x red, bits 3..10
                     oB |= ((uint32_t)b & 255u) << (8 * i);
                 }
                 __builtin_amdgcn_raw_buffer_store_b32(oR, rrs, out_off, (slot - s_lo) * (int)plane_stride, 0);
@@ -784,8 +778,8 @@ __global__ __launch_bounds__(256) void k_warp_split1(const uint32_t* __restrict_
                                                     const uint16_t* __restrict__ cbrt_tab,
                                                     const int32_t* __restrict__ coeffs, uint8_t* __restrict__ planeR,
                                                     uint8_t* __restrict__ planeB, size_t plane_stride) {
-    __shared__ uint16_t s_gamma[256];
-    __shared__ uint16_t s_cbrt[3072];
+    __shared__ alignas(16) uint16_t s_gamma[256];
+    __shared__ alignas(16) uint16_t s_cbrt[3072];
     __shared__ int32_t s_coef[9];
     stage_lab_tables(s_gamma, s_cbrt, s_coef, gamma_tab, cbrt_tab, coeffs);
     const size_t npix = (size_t)g.warp_h * g.warp_w;
@@ -804,8 +798,8 @@ __global__ __launch_bounds__(256) void k_split_bev(const uint8_t* __restrict__ b
                                                   const uint16_t* __restrict__ cbrt_tab,
                                                   const int32_t* __restrict__ coeffs, uint8_t* __restrict__ planeR,
                                                   uint8_t* __restrict__ planeB, size_t plane_stride) {
-    __shared__ uint16_t s_gamma[256];
-    __shared__ uint16_t s_cbrt[3072];
+    __shared__ alignas(16) uint16_t s_gamma[256];
+    __shared__ alignas(16) uint16_t s_cbrt[3072];
     __shared__ int32_t s_coef[9];
     stage_lab_tables(s_gamma, s_cbrt, s_coef, gamma_tab, cbrt_tab, coeffs);
     const size_t o = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -927,15 +921,15 @@ void launch_surf_rows_to_rgb(hipStream_t s, int layout, const SurfEntry* entries
 
 void launch_warp_split(hipStream_t s, const uint32_t* und, size_t und_px, int first_slot, const int16_t* wxy,
                        const uint16_t* wfrac, FrontEndGeom g, const uint16_t* gamma_tab, const uint16_t* cbrt_tab,
-                       const int32_t* coeffs, uint8_t* planeR, uint8_t* planeB, size_t plane_stride, int n) {
+                       const int32_t* coeffs, bool lab_clamp_dead, uint8_t* planeR, uint8_t* planeB, size_t plane_stride, int n) {
     if (n <= 0 || g.nrows <= 0) return;
     const size_t npix = (size_t)g.warp_h * g.warp_w;
     if ((g.warp_w & 3) == 0 && (plane_stride & 3) == 0) {
         const int pairs = ((first_slot + n + 1) >> 1) - (first_slot >> 1);
         const int ppb = std::max(1, frames_per_thread(n) / 2);
         dim3 grid((unsigned)(((npix >> 2) + 255) / 256), 1, (pairs + ppb - 1) / ppb);
-        hipLaunchKernelGGL(k_warp_split4, grid, dim3(256), 0, s, und, und_px, first_slot, wxy, wfrac, g, gamma_tab, cbrt_tab,
-                           coeffs, planeR, planeB, plane_stride, n, ppb, xcd_remap());
+        hipLaunchKernelGGL(lab_clamp_dead ? k_warp_split4<false> : k_warp_split4<true>, grid, dim3(256), 0, s, und, und_px, first_slot, wxy,
+                           wfrac, g, gamma_tab, cbrt_tab, coeffs, planeR, planeB, plane_stride, n, ppb, xcd_remap());
     } else {
         dim3 grid((unsigned)((npix + 255) / 256), 1, n);
         hipLaunchKernelGGL(k_warp_split1, grid, dim3(256), 0, s, und, und_px, first_slot, wxy, wfrac, g, gamma_tab, cbrt_tab,

@@ -24,6 +24,7 @@
 
 #include <hip/hip_ext.h>
 
+#include "front_arith.h"
 #include "lt_ctx.h"
 
 using namespace lt;
@@ -564,6 +565,7 @@ int lt_create(const lt_calib* calib, int device, lt_ctx** out) {
     uint16_t gamma_tab[256], cbrt_tab[3072];
     int32_t coef[9];
     build_lab_tables(gamma_tab, cbrt_tab, coef);
+    c->lab_clamp_dead = fa::lab_clamp_is_dead(*std::max_element(gamma_tab, gamma_tab + 256), coef);
     auto make_se = [](int k, EllipseSE& se) {
         int dx[64];
         ellipse_halfwidths(k, dx);
@@ -1813,7 +1815,7 @@ static int mask_run_impl(lt_ctx* c, int first, int n, const lt_filter_params* p,
             { int mrc = n == 1 ? note_range_frame(c, c->readers, st, f0, f0 + m) : note_range(c->readers, st, f0, f0 + m); if (mrc) return mrc; }
             { StageScope t(c, ST_WARP_SPLIT, st);
               launch_warp_split(st, c->d_und, c->und_px, f0, c->d_wxy, c->d_wfrac, c->fe, c->d_gamma,
-                                c->d_cbrt, c->d_coef, c->masks.d_plane[P_R] + (size_t)f0 * ps, c->masks.d_plane[P_B] + (size_t)f0 * ps,
+                                c->d_cbrt, c->d_coef, c->lab_clamp_dead, c->masks.d_plane[P_R] + (size_t)f0 * ps, c->masks.d_plane[P_B] + (size_t)f0 * ps,
                                 ps, m); }
             for (int i = f0; i < f0 + m && i < (int)c->front_ok.size(); ++i) c->front_ok[(size_t)i] = 1;
         }

@@ -99,6 +99,7 @@ struct lt_ctx {
     int16_t *d_uxy = nullptr, *d_wxy = nullptr;
     uint16_t *d_ufrac = nullptr, *d_wfrac = nullptr, *d_gamma = nullptr, *d_cbrt = nullptr;
     int32_t* d_coef = nullptr;
+    bool lab_clamp_dead = false;   // no pixel reaches the clamp of the cube-root table index with these tables (front_arith.h)
     // slots
     int capacity = 0;
     size_t frame_bytes = 0, und_bytes = 0, bev_bytes = 0;

@@ -54,7 +54,7 @@ inline size_t und_slot_base(size_t und_px, int slot) { return (size_t)(slot >> 1
 // `und` is the base of the whole buffer, `first_slot` the absolute slot of frame 0 of the call; planes point at that slot's data
 void launch_warp_split(hipStream_t s, const uint32_t* und, size_t und_px, int first_slot, const int16_t* wxy,
                        const uint16_t* wfrac, FrontEndGeom g, const uint16_t* gamma_tab, const uint16_t* cbrt_tab,
-                       const int32_t* coeffs, uint8_t* planeR, uint8_t* planeB, size_t plane_stride, int n);
+                       const int32_t* coeffs, bool lab_clamp_dead, uint8_t* planeR, uint8_t* planeB, size_t plane_stride, int n);
 // YUV 4:2:0 input (lt_set_input_format): the five 20-bit fixed-point coefficients of the conversion, each below 2^23 in
 // magnitude (checked where they enter), so that every product with a 9-bit sample is one 24-bit multiply
 struct YuvCoef {

@@ -1,8 +1,10 @@
 // VALU issue-rate calibration for gfx950: wave-instructions per cycle per SIMD for the integer / packed-16 /
-// DPP / permute instructions the mask-stage kernels are made of, as independent and dependent chains at
+// DPP / permute instructions the mask-stage kernels are made of, and for the fp32 / conversion forms the front end chose its
+// blend and Lab tail from (profiles/front_f32_valu_issue.txt), as independent and dependent chains at
 // 1..8 waves per SIMD.  Prints one JSON document; tools/microbench/run.sh stores it under profiles/.
 //
 //   build: hipcc -O2 --offload-arch=gfx950 valu_issue.hip -o valu_issue
+//   run:   valu_issue [iters [row,row,...]]      (a list of row names: time these rows only)
 //
 // Method: a 256-thread workgroup = one wave per SIMD; `W` workgroups per CU are forced by a dynamic-LDS request of
 // floor(160 KiB / W) per workgroup, grid = CUs x W (all resident at once).  Each wave executes ITERS x 64 copies of
@@ -79,6 +81,31 @@
 #define I_CNDS(i)    "v_cndmask_b32 %" #i ", %" #i ", %8, s[20:21]\n\t"
 #define I_PERMADD(i) "v_perm_b32 %" #i ", %" #i ", %8, %9\n\tv_add_u32 %" #i ", %" #i ", %8\n\t"
 #define I_READLANE(i) "v_readlane_b32 s20, %" #i ", 3\n\t"
+// the fp32 / conversion forms the front end's blend and Lab tail choose from (profiles/front_f32_valu_issue.txt)
+#define I_CVTUB0(i)  "v_cvt_f32_ubyte0_e32 %" #i ", %" #i "\n\t"
+#define I_CVTUB1(i)  "v_cvt_f32_ubyte1_e32 %" #i ", %" #i "\n\t"
+#define I_CVTUB2(i)  "v_cvt_f32_ubyte2_e32 %" #i ", %" #i "\n\t"
+#define I_CVTUB3(i)  "v_cvt_f32_ubyte3_e32 %" #i ", %" #i "\n\t"
+#define I_CVTFU(i)   "v_cvt_f32_u32_e32 %" #i ", %" #i "\n\t"
+#define I_CVTUF(i)   "v_cvt_u32_f32_e32 %" #i ", %" #i "\n\t"
+#define I_FLOOR(i)   "v_floor_f32_e32 %" #i ", %" #i "\n\t"
+#define I_FMAC(i)    "v_fmac_f32_e32 %" #i ", %8, %9\n\t"
+#define I_MULF(i)    "v_mul_f32_e32 %" #i ", %" #i ", %8\n\t"
+#define I_MINF(i)    "v_min_f32_e32 %" #i ", %" #i ", %8\n\t"
+#define I_MAXF(i)    "v_max_f32_e32 %" #i ", %" #i ", %8\n\t"
+#define I_MED3F(i)   "v_med3_f32 %" #i ", %" #i ", %8, %9\n\t"
+#define I_MINU16(i)  "v_min_u16_e32 %" #i ", %" #i ", %8\n\t"
+#define I_MINI16(i)  "v_min_i16_e32 %" #i ", %" #i ", %8\n\t"
+#define I_MAXU16(i)  "v_max_u16_e32 %" #i ", %" #i ", %8\n\t"
+#define I_CVTPKU8(i) "v_cvt_pk_u8_f32 %" #i ", %" #i ", %8, %9\n\t"
+#define I_DOT2U16(i) "v_dot2_u32_u16 %" #i ", %" #i ", %8, %9\n\t"
+#define I_LSHL_E32(i) "v_lshlrev_b32_e32 %" #i ", 1, %" #i "\n\t"
+#define I_LSHL_E64(i) "v_lshlrev_b32_e64 %" #i ", 1, %" #i "\n\t"
+#define I_LSHR_E64(i) "v_lshrrev_b32_e64 %" #i ", 1, %" #i "\n\t"
+// packed fp32: every operand is a 64-bit register pair (OPS64)
+#define I_PKFMAF32(i) "v_pk_fma_f32 %" #i ", %" #i ", %8, %9\n\t"
+#define I_PKMULF32(i) "v_pk_mul_f32 %" #i ", %" #i ", %8\n\t"
+#define I_PKADDF32(i) "v_pk_add_f32 %" #i ", %" #i ", %8\n\t"
 
 #define OPS(F) \
     F(pk_minimum3_f16, I_PKMIN3) F(pk_maximum3_f16, I_PKMAX3) F(pk_mad_u16, I_PKMAD) F(pk_add_u16, I_PKADD) \
@@ -92,17 +119,25 @@
     F(max_i16, I_MAXI16) F(add_u16, I_ADD16) F(mul_u32_u24, I_MUL24) F(lshrrev_b32, I_LSHR) F(ashrrev_i32, I_ASHR) \
     F(add_u32_sdwa_byte, I_ADDSDWA) F(add_co_u32, I_ADDCO) F(add_f32, I_ADDF) F(pk_add_f16, I_PKADDF16) \
     F(pk_mul_lo_u16, I_PKMULLO) F(mad_u16, I_MADU16) F(bfrev_b32, I_BFREV) F(cndmask_then_3_adds_x4insts, I_CNDADD) \
-    F(cndmask_sgpr_mask, I_CNDS) F(perm_then_add_x2insts, I_PERMADD) F(readlane_b32, I_READLANE)
+    F(cndmask_sgpr_mask, I_CNDS) F(perm_then_add_x2insts, I_PERMADD) F(readlane_b32, I_READLANE) \
+    F(cvt_f32_ubyte0, I_CVTUB0) F(cvt_f32_ubyte1, I_CVTUB1) F(cvt_f32_ubyte2, I_CVTUB2) F(cvt_f32_ubyte3, I_CVTUB3) \
+    F(cvt_f32_u32, I_CVTFU) F(cvt_u32_f32, I_CVTUF) F(floor_f32, I_FLOOR) F(fmac_f32_e32, I_FMAC) F(mul_f32, I_MULF) \
+    F(min_f32, I_MINF) F(max_f32, I_MAXF) F(med3_f32, I_MED3F) F(min_u16_e32, I_MINU16) F(min_i16_e32, I_MINI16) \
+    F(max_u16_e32, I_MAXU16) F(cvt_pk_u8_f32, I_CVTPKU8) F(dot2_u32_u16, I_DOT2U16) F(lshlrev_b32_e32, I_LSHL_E32) \
+    F(lshlrev_b32_e64, I_LSHL_E64) F(lshrrev_b32_e64, I_LSHR_E64)
+#define OPS64(F) F(pk_fma_f32, I_PKFMAF32) F(pk_mul_f32, I_PKMULF32) F(pk_add_f32, I_PKADDF32)
 
 extern "C" __global__ void k_dummy() {}
 
-#define DEFINE_KERNEL(NAME, INS)                                                                                     \
+#define DEFINE_KERNEL(NAME, INS) DEFINE_KERNEL_T(NAME, INS, unsigned)
+#define DEFINE_KERNEL64(NAME, INS) DEFINE_KERNEL_T(NAME, INS, unsigned long long)
+#define DEFINE_KERNEL_T(NAME, INS, T)                                                                                   \
     template <bool DEP>                                                                                              \
     __global__ __launch_bounds__(256) void k_##NAME(int iters, unsigned long long* cycles, unsigned* sink) {         \
         extern __shared__ unsigned char smem_[];                                                                     \
-        unsigned a0 = threadIdx.x, a1 = a0 + 1, a2 = a0 + 2, a3 = a0 + 3, a4 = a0 + 4, a5 = a0 + 5, a6 = a0 + 6,    \
-                 a7 = a0 + 7;                                                                                        \
-        const unsigned b = 0x00030005u + (threadIdx.x & 1), c = 0x04020400u;                                         \
+        T a0 = threadIdx.x, a1 = a0 + 1, a2 = a0 + 2, a3 = a0 + 3, a4 = a0 + 4, a5 = a0 + 5, a6 = a0 + 6,           \
+          a7 = a0 + 7;                                                                                               \
+        const T b = 0x00030005u + (threadIdx.x & 1), c = 0x04020400u;                                                \
         __syncthreads();                                                                                             \
         const unsigned long long t0 = __builtin_readcyclecounter();                                                  \
         for (int it = 0; it < iters; ++it) {                                                                         \
@@ -122,6 +157,7 @@ extern "C" __global__ void k_dummy() {}
         if ((a0 ^ a1 ^ a2 ^ a3 ^ a4 ^ a5 ^ a6 ^ a7) == 0x12345u) sink[0] = smem_[0];                                 \
     }
 OPS(DEFINE_KERNEL)
+OPS64(DEFINE_KERNEL64)
 
 struct Op {
     const char* name;
@@ -129,7 +165,7 @@ struct Op {
     void (*dep)(int, unsigned long long*, unsigned*);
 };
 #define OP_ENTRY(NAME, INS) {#NAME, k_##NAME<false>, k_##NAME<true>},
-static const Op g_ops[] = {OPS(OP_ENTRY)};
+static const Op g_ops[] = {OPS(OP_ENTRY) OPS64(OP_ENTRY)};
 
 int main(int argc, char** argv) {
     int dev = 0;
@@ -140,6 +176,7 @@ int main(int argc, char** argv) {
     int clock_khz = 0;
     CHECK(hipDeviceGetAttribute(&clock_khz, hipDeviceAttributeClockRate, dev));
     const int iters = argc > 1 ? std::atoi(argv[1]) : 2000;
+    const char* only = argc > 2 ? argv[2] : nullptr;   // a comma-separated list of row names: time these rows only
     unsigned long long* d_cycles;
     unsigned* d_sink;
     CHECK(hipMalloc(&d_cycles, sizeof(unsigned long long) * cus * 8 * 4));
@@ -156,6 +193,10 @@ int main(int argc, char** argv) {
                 "ghz = insts*W*4*cus/(rate*... ) see wall_ms\",\n \"ops\": {\n");
     bool first = true;
     for (const Op& op : g_ops) {
+        if (only) {
+            const std::string list = std::string(",") + only + ",", key = std::string(",") + op.name + ",";
+            if (list.find(key) == std::string::npos) continue;
+        }
         for (int dep = 0; dep < 2; ++dep) {
             auto fn = dep ? op.dep : op.indep;
             std::printf("%s  \"%s/%s\": {", first ? "" : ",\n", op.name, dep ? "dep" : "indep");
