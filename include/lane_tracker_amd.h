@@ -52,7 +52,9 @@ extern "C" {
  *    lt_upload_frame_rest_list (the uploads of frames that lie in separate host arrays); lt_set_input_format + lt_get_input_format +
  *    lt_yuv_to_rgb (camera frames in YUV 4:2:0, NV12 or I420, converted on the device); lt_device_surface + lt_attach_device_frames +
  *    lt_device_frames_rest (camera frames that already lie in device memory, read where they lie), lt_device_alloc / _free /
- *    _write / _read (device blocks for callers without a HIP binding of their own), lt_device_stream_wait.  Nothing removed or changed. */
+ *    _write / _read (device blocks for callers without a HIP binding of their own), lt_device_stream_wait; lt_viz_item +
+ *    lt_search_viz_run + lt_split_panes_run + lt_split_panes_size + lt_search_viz_wait (the search visualisations and split-view
+ *    panes of listed frames, painted on the device), lt_calib_split_panes_size, lt_resize_linear_u8.  Nothing removed or changed. */
 #define LT_ABI_VERSION 5
 
 typedef enum lt_status {
@@ -110,6 +112,18 @@ typedef struct lt_search_item {
     double  prev_coeffs[6];
 } lt_search_item;
 
+/* One frame of a visualisation list (lt_search_viz_run, lt_split_panes_run), 48 bytes: the slot whose mask, lane pixels and window
+ * centroids are shown, which picture (lane_tracker.py:1130-1137) and the parameters of the search that is shown. */
+typedef struct lt_viz_item {
+    int32_t slot;
+    int32_t kind;                      /* 0 the bare mask (nothing detected), 1 sliding-window search, 2 band search */
+    int32_t window_width, window_height, ignore_bottom;   /* kind 1 */
+    int32_t bandwidth;                                    /* kind 2 */
+    int32_t n_fit_left, n_fit_right;   /* plot points of the new fit (kinds 1, 2) */
+    int32_t n_band_left, n_band_right; /* kind 2: plot points of the curves the band was searched around */
+    int32_t _pad[2];
+} lt_viz_item;
+
 typedef struct lt_info {
     int32_t abi_version, device, capacity, cu_count;
     int32_t src_row0, src_row1;  /* camera rows [row0,row1) that influence the bird's-eye view */
@@ -145,7 +159,8 @@ int  lt_reserve(lt_ctx* ctx, int capacity);
  * the first searches / the first chained search / the first overlay would otherwise create on the way (20-35 ms of the first
  * window of a stream).  sws / band: the search parameters to size the result buffers for (either may be NULL); annotate: 0 = no
  * presentation stage, 1 = whole annotated frames (lt_overlay_run), 2 = strips (lt_overlay_run_strip); needs lt_overlay_configure
- * for 1 and 2.  Optional: every entry point still sets up what it finds missing. */
+ * for 1 and 2; + 4: the staging ring of lt_search_viz_run, + 8: that of lt_split_panes_run as well.  Optional: every entry point
+ * still sets up what it finds missing. */
 int  lt_warm(lt_ctx* ctx, const lt_search_params* sws, const lt_search_params* band, int annotate);
 int  lt_get_info(lt_ctx* ctx, lt_info* out);
 int  lt_sync(lt_ctx* ctx);
@@ -380,6 +395,9 @@ int  lt_filter_lane_points(lt_ctx* ctx, const uint8_t* bev_rgb, int h, int w, co
  * morphologyEx (:210-211, :238).  k in {5, 29, 55}; op 0 erode, 1 dilate, 2 top-hat, 3 open.
  * direct != 0 evaluates the footprint tap by tap instead of using the run decomposition (k = 5 always does). */
 int  lt_morph_ellipse(lt_ctx* ctx, const uint8_t* img, int h, int w, int k, int op, int direct, uint8_t* out);
+/* cv2.resize(img, (dw, dh)) with the default INTER_LINEAR on a u8 image of 1 or 3 interleaved channels (host memory in and
+ * out): half-pixel centres, 11-bit coefficients, OpenCV's two-stage fixed-point rounding. */
+int  lt_resize_linear_u8(lt_ctx* ctx, const uint8_t* img, int h, int w, int channels, int dh, int dw, uint8_t* out);
 
 /* LaneTracker.fit_poly() on explicit pixel lists (np.polyfit(ys, xs, 2), :506-507): n (y,x) pairs with
  * coordinates in [0, 65535].  *rank_deficient is set when fewer than 3 distinct y exist (coef = 0). */
@@ -593,6 +611,28 @@ int  lt_device_cache_counters(unsigned long long* hits, unsigned long long* miss
 /* the bird's-eye RGB image of the slots' frames (lane_tracker.py:834, :1035): n * warp_h * warp_w * 3;
  * needs lt_mask_run on those slots first (it reuses their undistorted rows) */
 int  lt_download_bev(lt_ctx* ctx, int first_slot, int n, uint8_t* out);
+/* The search visualisations of listed frames (visualize_sliding_window_search / visualize_band_search, lane_tracker.py:687-771),
+ * painted on the device from what the slots hold -- the opened mask, the lane pixels in whatever form the search left them, the
+ * window centroids -- and sent to out_host: n pictures of warp_h * warp_w * 3 bytes, in item order.  The point lists are int32
+ * (y, x) pairs, the items' points back to back: the plot points of the new left / right fit (yellow), and for kind 2 those of the
+ * curves the band was searched around (lt_poly_points produces all four).  A kind-0 picture is the mask in all three channels.
+ * Enqueued behind everything launched so far over each listed slot; work launched over those slots later is ordered behind the
+ * reads.  `items` and the lists are read before the call returns.  The copies run on the download stream: out_host holds the
+ * pictures after lt_search_viz_wait, lt_sync or an lt_download_* call (page-locked memory preferred, pageable taken).  The
+ * pictures pass through a staging ring of 32 frames, allocated by the first call and freed by lt_reserve / lt_destroy: nothing
+ * grows with the capacity, and a longer list goes through the ring in pieces.  LT_ERR_INVALID: n < 0, a NULL list that is
+ * needed, a slot outside the capacity, an unknown kind, a negative count, window_height <= 0 (kind 1); LT_ERR_STATE: a slot
+ * without a mask, kinds 1 / 2 before any search has run.  Nothing is launched after a refusal. */
+int  lt_search_viz_run(lt_ctx* ctx, int n, const lt_viz_item* items, const int32_t* fit_left_yx, const int32_t* fit_right_yx,
+                       const int32_t* band_left_yx, const int32_t* band_right_yx, uint8_t* out_host);
+/* The same pictures as the lower part of triple_split_view (lane_tracker.py:773-793): per item one strip of scaled_h * img_w * 3
+ * bytes -- the bird's-eye RGB image (as lt_download_bev) scaled to (scaled_w, scaled_h) at column 0, the visualisation scaled
+ * likewise at column second_x, both cropped at the right edge, bytes no pane covers 0 (lt_split_panes_size gives the three
+ * numbers; cv2.resize INTER_LINEAR arithmetic).  Same contract as lt_search_viz_run; the slots need lt_mask_run first. */
+int  lt_split_panes_run(lt_ctx* ctx, int n, const lt_viz_item* items, const int32_t* fit_left_yx, const int32_t* fit_right_yx,
+                        const int32_t* band_left_yx, const int32_t* band_right_yx, uint8_t* out_host);
+int  lt_split_panes_size(lt_ctx* ctx, int* scaled_w, int* scaled_h, int* second_x);   /* no GPU work; any pointer may be NULL */
+int  lt_search_viz_wait(lt_ctx* ctx);  /* waits for the copies of the two calls above, and for nothing else */
 
 /* ---- host-only views of the calibration tables (no GPU needed) --------------------------------------- */
 /* What lt_create derives from the calibration, exposed so that it can be checked against independent
@@ -601,6 +641,8 @@ int  lt_download_bev(lt_ctx* ctx, int first_slot, int n, uint8_t* out);
  * [row0,row1) x img_w entries), the camera rows the warp reads, the RGB2LAB tables (:208) and the half-widths
  * of getStructuringElement(MORPH_ELLIPSE, (k,k)) (:203-205). */
 int  lt_calib_source_rows(const lt_calib* calib, int* row0, int* row1);
+/* lt_split_panes_size for a calibration (only the four sizes are read): triple_split_view's arithmetic (:781-787) */
+int  lt_calib_split_panes_size(const lt_calib* calib, int* scaled_w, int* scaled_h, int* second_x);
 int  lt_calib_warp_table(const lt_calib* calib, int16_t* xy, uint16_t* frac);
 int  lt_calib_undistort_table(const lt_calib* calib, int row0, int row1, int16_t* xy, uint16_t* frac);
 int  lt_calib_lab_tables(uint16_t* gamma256, uint16_t* cbrt3072, int32_t* coeffs9);

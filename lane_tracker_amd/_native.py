@@ -63,6 +63,21 @@ SEARCH_ITEM_DTYPE = np.dtype([("slot", "<i4"), ("mode", "<i4"), ("_pad", "<i4", 
 assert SEARCH_ITEM_DTYPE.itemsize == 64 and C.sizeof(SearchItem) == 64
 
 
+class VizItem(C.Structure):
+    """lt_viz_item: one frame of lt_search_viz_run / lt_split_panes_run (slot, 0 bare mask / 1 sliding window / 2 band, the shown
+    search's parameters, the lengths of the frame's stretches of the four point lists)."""
+    _fields_ = [("slot", C.c_int32), ("kind", C.c_int32), ("window_width", C.c_int32), ("window_height", C.c_int32),
+                ("ignore_bottom", C.c_int32), ("bandwidth", C.c_int32), ("n_fit_left", C.c_int32), ("n_fit_right", C.c_int32),
+                ("n_band_left", C.c_int32), ("n_band_right", C.c_int32), ("_pad", C.c_int32 * 2)]
+
+
+VIZ_ITEM_DTYPE = np.dtype([("slot", "<i4"), ("kind", "<i4"), ("window_width", "<i4"), ("window_height", "<i4"), ("ignore_bottom", "<i4"),
+                           ("bandwidth", "<i4"), ("n_fit_left", "<i4"), ("n_fit_right", "<i4"), ("n_band_left", "<i4"),
+                           ("n_band_right", "<i4"), ("_pad", "<i4", 2)])
+assert VIZ_ITEM_DTYPE.itemsize == 48 and C.sizeof(VizItem) == 48
+VIZ_MASK, VIZ_SWS, VIZ_BAND = 0, 1, 2
+
+
 class DeviceSurface(C.Structure):
     """lt_device_surface: one camera frame in device memory (plane pointers, luma / RGB pitch, chroma pitch)."""
     _fields_ = [("plane", C.c_void_p * 3), ("pitch", C.c_int32), ("chroma_pitch", C.c_int32)]
@@ -124,6 +139,12 @@ _SIGNATURES = {
     "lt_download_overlay": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "lt_download_overlay_async": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "lt_download_bev": (C.c_int, [_P, C.c_int, C.c_int, _P]),
+    "lt_search_viz_run": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "lt_split_panes_run": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P]),
+    "lt_split_panes_size": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "lt_search_viz_wait": (C.c_int, [_P]),
+    "lt_calib_split_panes_size": (C.c_int, [C.POINTER(Calib), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "lt_resize_linear_u8": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "lt_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(C.c_void_p)]),
     "lt_host_free": (C.c_int, [_P]),
     "lt_host_copy_async": (C.c_int, [_P, _P, C.c_size_t]),
@@ -606,6 +627,16 @@ def pack_polygons(polygons):
     return ln, rn, pairs([p[0] for p in polygons], [p[1] for p in polygons], ln), pairs([p[2] for p in polygons], [p[3] for p in polygons], rn)
 
 
+def split_panes_size(img_size, warped_size):
+    """(scaled_w, scaled_h, second_x) of triple_split_view (reference :781-787) for a camera / bird's-eye size pair (width, height):
+    the panes' size and the second pane's column.  Host-only (lt_calib_split_panes_size)."""
+    cal = Calib()
+    cal.img_w, cal.img_h, cal.warp_w, cal.warp_h = int(img_size[0]), int(img_size[1]), int(warped_size[0]), int(warped_size[1])
+    a, b, c_ = C.c_int(0), C.c_int(0), C.c_int(0)
+    _check(load().lt_calib_split_panes_size(C.byref(cal), C.byref(a), C.byref(b), C.byref(c_)))
+    return a.value, b.value, c_.value
+
+
 def poly_points(warped_size, coeffs, ploty, ploty2):
     """get_poly_points (reference :511-528) for many pairs of parabolas at once, packed for overlay_run_packed: coeffs (n, 6)
     = left a, b, c, right a, b, c; ploty / ploty2 as LaneTracker._plot_rows gives them.  Host-only (lt_poly_points)."""
@@ -878,7 +909,7 @@ class Context:
 
     def warm(self, sws=None, band=None, annotate=0):
         """Set up now what the first searches / chains / overlays would set up on the way (lt_warm); annotate: 0 none, 1 whole
-        annotated frames, 2 strips."""
+        annotated frames, 2 strips; + 4 the staging ring of search_viz_run, + 8 that of split_panes_run as well."""
         _check(self.lib.lt_warm(self._h, None if sws is None else C.byref(sws), None if band is None else C.byref(band), int(annotate)))
 
     def overlay_set_font(self, atlas, advance, first_char=32):
@@ -930,6 +961,57 @@ class Context:
     def download_bev(self, n, first=0):
         out = pinned_empty((n, self.warp_h, self.warp_w, 3))
         _check(self.lib.lt_download_bev(self._h, first, n, out.ctypes.data))
+        return out
+
+    # -- search visualisations, split-view panes (lt_search_viz_run & co.)
+    def _viz_call(self, fn, items, fit_left, fit_right, band_left, band_right, out, shape):
+        items = np.ascontiguousarray(items, VIZ_ITEM_DTYPE)
+        n = int(items.shape[0])
+        lists = [None if a is None else np.ascontiguousarray(a, np.int32).reshape(-1, 2) for a in (fit_left, fit_right, band_left, band_right)]
+        fit, band = items["kind"] != 0, items["kind"] == 2          # (the library reads exactly these many points of each list)
+        wants = (items["n_fit_left"][fit].sum(), items["n_fit_right"][fit].sum(), items["n_band_left"][band].sum(), items["n_band_right"][band].sum())
+        for a, want in zip(lists, wants):
+            if a is not None and a.shape[0] < int(want):
+                raise ValueError("a point list is shorter than the items' counts")
+        wait = out is None
+        if wait:
+            out = pinned_empty((n,) + shape)
+        elif out.shape != (n,) + shape or out.dtype != np.uint8 or not out.flags.c_contiguous:
+            raise ValueError("out must be a C-contiguous uint8 array of shape %r" % ((n,) + shape,))
+        _check(fn(self._h, n, items.ctypes.data, *[None if a is None else a.ctypes.data for a in lists], out.ctypes.data))
+        if wait:
+            self.search_viz_wait()
+        return out
+
+    def search_viz_run(self, items, fit_left=None, fit_right=None, band_left=None, band_right=None, out=None):
+        """The search visualisations of the listed frames (`items`: VIZ_ITEM_DTYPE; the lists: int32 (y, x) pairs, the items' points
+        back to back) -> (n, warp_h, warp_w, 3).  With `out` the call only enqueues: `out` is complete after search_viz_wait()."""
+        return self._viz_call(self.lib.lt_search_viz_run, items, fit_left, fit_right, band_left, band_right, out, (self.warp_h, self.warp_w, 3))
+
+    def split_panes_run(self, items, fit_left=None, fit_right=None, band_left=None, band_right=None, out=None):
+        """The lower part of the split view of the listed frames -> (n, scaled_h, img_w, 3); otherwise as search_viz_run."""
+        return self._viz_call(self.lib.lt_split_panes_run, items, fit_left, fit_right, band_left, band_right, out,
+                              (self.split_panes_size()[1], self.img_w, 3))
+
+    def split_panes_size(self):
+        """(scaled_w, scaled_h, second_x) of triple_split_view for this context's camera and bird's-eye sizes."""
+        a, b, c_ = C.c_int(0), C.c_int(0), C.c_int(0)
+        _check(self.lib.lt_split_panes_size(self._h, C.byref(a), C.byref(b), C.byref(c_)))
+        return a.value, b.value, c_.value
+
+    def search_viz_wait(self):
+        """Block until the pictures of every search_viz_run / split_panes_run have landed (nothing else is waited for)."""
+        _check(self.lib.lt_search_viz_wait(self._h))
+
+    def resize_linear(self, img, dsize):
+        """cv2.resize(img, dsize=(w, h)), INTER_LINEAR, on a u8 image of one or three channels (utils.resize_linear on the device)."""
+        a = _u8(img)
+        if a.ndim not in (2, 3) or (a.ndim == 3 and a.shape[2] not in (1, 3)):
+            raise ValueError("resize_linear expects an (h, w) or (h, w, 3) image")
+        ch = 1 if a.ndim == 2 else a.shape[2]
+        dw, dh = int(dsize[0]), int(dsize[1])
+        out = np.empty((dh, dw) if a.ndim == 2 else (dh, dw, ch), np.uint8)
+        _check(self.lib.lt_resize_linear_u8(self._h, a.ctypes.data, a.shape[0], a.shape[1], ch, dh, dw, out.ctypes.data))
         return out
 
     def download_records(self, n, first=0):

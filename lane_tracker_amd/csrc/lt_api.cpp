@@ -204,6 +204,7 @@ void free_slots(lt_ctx* c) {
     c->h_ploty.clear();
     dev_free(c->d_annot);
     dev_free(c->d_strip);
+    viz_free_device(c);
     c->maxbands = 0;
     c->capacity = 0;
     c->maxpix = 0;
@@ -294,6 +295,7 @@ static void preload_kernels(int device, hipStream_t s) {
     preload_k_adaptive_walk(s);
     preload_k_search(s);
     preload_k_overlay(s);
+    preload_k_search_viz(s);
     (void)hipStreamSynchronize(s);
     (void)hipGetLastError();
 }
@@ -643,6 +645,7 @@ void lt_destroy(lt_ctx* c) {
     if (c->spans_busy.done) (void)hipEventDestroy(c->spans_busy.done);
     if (c->text_busy.done) (void)hipEventDestroy(c->text_busy.done);
     if (c->annot_busy.done) (void)hipEventDestroy(c->annot_busy.done);
+    viz_free_host(c);
     note("streams back to the pool: dl");
     stream_put(c->dl);
     note("events: download timing");
@@ -770,7 +773,8 @@ int lt_warm(lt_ctx* c, const lt_search_params* sws, const lt_search_params* band
         maxlev = std::max(maxlev, 1);
     }
     if (maxpix && (rc = ensure_search_buffers(c, maxpix, maxlev))) return rc;
-    if (annotate && (rc = warm_presentation(c, annotate == 2))) return rc;
+    if ((annotate & 3) && (rc = warm_presentation(c, (annotate & 3) == 2))) return rc;
+    if ((annotate & 12) && (rc = warm_search_viz(c, (annotate & 8) != 0))) return rc;
     return sync_all(c);
 }
 

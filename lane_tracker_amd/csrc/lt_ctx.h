@@ -4,6 +4,7 @@
 //   lt_memory.cpp  -- device-memory cache, page-locked host memory, the host copy threads
 //   lt_present.cpp -- presentation stage: lane overlay, text, annotated frames on their way back
 //   lt_chain.cpp   -- the chained band search of a stream (tickets, cancel, collect)
+//   lt_search_viz.cpp -- search visualisations and split-view panes of listed frames, lt_resize_linear_u8
 // Not installed; the public ABI is include/lane_tracker_amd.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -73,6 +74,24 @@ struct MaskArena {
     int ensure_side_scratch();
 };
 
+// The staging ring of lt_search_viz_run / lt_split_panes_run (lt_search_viz.cpp): FRAMES pictures (and, for split views, as many
+// bird's-eye images and pane strips) in two halves that take turns -- one is painted while the other crosses the bus.  Allocated
+// by the first call that needs a part; nothing here grows with the context's capacity.
+struct VizRing {
+    static constexpr int FRAMES = 32, HALF = FRAMES / 2;
+    uint8_t *d_pics = nullptr, *d_bev = nullptr, *d_panes = nullptr;
+    int32_t *d_xt = nullptr, *d_yt = nullptr;      // resize taps bird's-eye size -> pane size (four int32 per column / row)
+    struct Half {
+        uint8_t *h_stage = nullptr, *d_stage = nullptr;   // band intervals and plot points of the half's pictures: page-locked, device
+        size_t h_bytes = 0, d_bytes = 0;
+        hipEvent_t staged = nullptr;     // behind the kernels that read the staging and paint the half
+        hipEvent_t copied = nullptr;     // behind the copy of the half's pictures to the host
+        bool staged_set = false, copied_set = false;
+    } half[2];
+    int next = 0;
+    hipEvent_t last = nullptr;           // the `copied` event of the most recent piece (lt_search_viz_wait); null: nothing in flight
+};
+
 }  // namespace lt
 
 using lt::P_COUNT;
@@ -122,6 +141,7 @@ struct lt_ctx {
     uint32_t* d_und = nullptr;        // undistorted camera rows [r0, r0+nrows), one RGBX dword per pixel, slots 2p / 2p+1 interleaved (und_slot_base)
     size_t und_px = 0;                // pixels per slot of d_und
     lt::MaskArena masks;              // the mask chain's device memory, one block of each kind for the whole capacity
+    lt::VizRing viz;                  // lt_search_viz_run / lt_split_panes_run: pictures on their way to the host
     int last_threshold_path = -1;                 // lt_last_threshold_path
     int last_adaptive_path = -1;                  // 'neighborhood' calls: 1 = running box sums (k_adaptive_walk.hip), 0 = per-pixel windows
     // The walking threshold kernels are long serial walks (a wave covers half an image row or column): they win once a
@@ -434,6 +454,9 @@ int first_partial(const std::vector<uint8_t>& v, int first, int n);
 int ensure_search_stream(lt_ctx* c);                          // lt_chain.cpp
 int ensure_chain_buffers(lt_ctx* c);                          // lt_chain.cpp
 int warm_presentation(lt_ctx* c, bool strips);                // lt_present.cpp
+int warm_search_viz(lt_ctx* c, bool panes);                   // lt_search_viz.cpp: the staging ring (lt_warm)
+void viz_free_device(lt_ctx* c);                              // lt_search_viz.cpp: the ring's device memory (free_slots)
+void viz_free_host(lt_ctx* c);                                // ... its events and page-locked staging (lt_destroy)
 
 
 

@@ -279,6 +279,33 @@ void launch_search_list(hipStream_t s, const lt_search_item* items, int n, int n
 // fit of one explicit pixel list (packed (y<<16)|x); out: 3 doubles + 1 flag double (1.0 = rank deficient)
 void launch_fit_list(hipStream_t s, const uint32_t* pix, int n, int h, int w, double* out4);
 
+// ---- search visualisation, cv2.resize(INTER_LINEAR) on u8 (k_search_viz.hip) ---------------------------------
+// One picture of a k_search_viz launch: where the slot keeps what the picture is made of, and what the host adds.
+struct VizFrame {
+    const unsigned long long* bits;  // the slot's opened bit plane, or null: `mask`, its u8 plane (an uploaded mask)
+    const uint8_t* mask;
+    const uint32_t* pix;             // the slot's lane-pixel region, in the form rec->_pad names
+    const int32_t* cent;             // the slot's window centroids [side][maxlev + 2] (kind 1)
+    const lt_lane_record* rec;
+    const int16_t* band;             // kind 2: [side][h] (lo, hi), the band polygons' row intervals clipped to the image (lo > hi: none)
+    const int32_t* pts;              // (y, x) pairs of the new fit's plot points, left then right
+    uint8_t* out;                    // h x w x 3
+    int32_t kind, ww, wh, H1;        // lt_viz_item: kind, window_width, window_height, warp_h - ignore_bottom
+    int32_t n_fit_left, n_fit_right;
+};
+constexpr int LT_VIZ_BATCH = 16;     // pictures per launch: their descriptors travel as a kernel argument
+struct VizBatch {
+    VizFrame f[LT_VIZ_BATCH];
+};
+// the first n pictures of the batch: the gather pass, then the lists (packed lane pixels, curves) on the same stream
+void launch_search_viz(hipStream_t s, const VizBatch& b, int n, int h, int w, int wpr, int maxpix, int maxlev);
+// n images of `ch` interleaved channels, rows of sw pixels, src_stride bytes apart -> columns [0, dcols) and all dh rows of the scaled
+// images into columns dcol0 .. of destination rows of dpitch bytes; xt / yt: four int32 per destination column / row (tap 0, tap 1,
+// coefficient 0, coefficient 1: utils._resize_taps), device memory
+void launch_resize_linear_u8(hipStream_t s, const uint8_t* src, size_t src_stride, int sw, int ch, uint8_t* dst, size_t dst_stride,
+                             int dpitch, int dcol0, int dcols, int dh, const int32_t* xt, const int32_t* yt, int n);
+void preload_k_search_viz(hipStream_t s);
+
 // ---- internal view of a context for lt_gather.cpp (defined in lt_api.cpp) ----------------------------
 int set_error(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));   // fills lt_last_error(), returns code
 int ctx_device(lt_ctx* c);

@@ -139,6 +139,9 @@ class LaneTrackerGroup:
         if len(frames) != self.k:
             raise ValueError("expected %d frames (None for a stream that skips this call), got %d" % (self.k, len(frames)))
         kw, first_try, fp = self.trackers[0]._batch_arguments(kwargs)
+        if kw["visualize_search"] or kw["split_view"]:
+            raise NotImplementedError("search visualisation / split view are not available for a group: use the streams' own trackers "
+                                      "(process, process_batch, process_stream)")
         n_tries, diagnostics = kw["n_tries"], kw["diagnostics"]
         active = [i for i, f in enumerate(frames) if f is not None]
         outs = [None] * self.k

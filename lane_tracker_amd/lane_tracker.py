@@ -1214,10 +1214,13 @@ class LaneTracker(StreamPipeline):
             self._want_out, self._out, self._out_rows, self._text_in_flight = False, None, None, None
 
     def _step(self, img, first_try, n_tries, diagnostics, slot, have_mask, lazy, annotate, visualize_search=False,
-              split_view=False, defer=None):
+              split_view=False, defer=None, viz=None):
         """One frame of the per-stream state machine (reference :1026-1209).  With `defer` (a list) the
         annotated frame is not produced here: ('lane', polygon, text) or ('fail', None, text) is appended
-        and the caller renders all frames of the window in one overlay launch."""
+        and the caller renders all frames of the window in one overlay launch.  `viz` (the stream pipeline's, with
+        `defer`): the frame's search visualisation is not returned either -- a list takes (picture, bird's-eye image or
+        None) painted here on the host, a `stream._VizWindow` takes the descriptor the device paints it from and enqueues
+        it at once, while the slot still holds the mask and the lists of the attempt shown."""
         partial = first_try[-1]
         self._open_frame()
         left_fit_coeffs = right_fit_coeffs = None
@@ -1251,7 +1254,15 @@ class LaneTracker(StreamPipeline):
                 left_fit_coeffs, right_fit_coeffs = self._fit_and_check(diagnostics, "second")
 
         search_visualization = warped_img = None
-        if visualize_search or split_view:                              # :1130-1137
+        if viz is not None and not isinstance(viz, list):
+            if not self.detected_pixels:
+                viz.add(slot, 0, used)
+            elif search_mode == 'sws':
+                viz.add(slot, 1, used, fit=(left_fit_coeffs, right_fit_coeffs))
+            else:
+                viz.add(slot, 2, used, fit=(left_fit_coeffs, right_fit_coeffs), band=(self.last_left_coeffs, self.last_right_coeffs))
+            viz.flush()
+        elif visualize_search or split_view:                            # :1130-1137
             binary_img = self._ctx.download_masks(1, first=slot)[0]
             if self.detected_pixels:
                 if search_mode == 'sws':
@@ -1266,6 +1277,8 @@ class LaneTracker(StreamPipeline):
             if split_view:
                 # the bird's-eye image the detector saw (upstream warps the raw, still distorted frame here, :1035)
                 warped_img = self._ctx.download_bev(1, first=slot)[0]
+            if isinstance(viz, list):
+                viz.append((search_visualization, warped_img))
 
         def present(annotated):
             if visualize_search:

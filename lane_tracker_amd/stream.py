@@ -177,7 +177,7 @@ class StreamPipeline:
 
     _SECOND_TRY = (15, 5, 35, 5, 'neighborhood', False, 140, 65, 10, 30, 40, 20, 0.1, 50, 0.25, 360, 30, 30, 1.0)   # :1081-1099
 
-    def _fail_group(self, frames, base, i, k, first_try, fp, n_tries, annotate, deferred, speculate=None):
+    def _fail_group(self, frames, base, i, k, first_try, fp, n_tries, annotate, deferred, speculate=None, viz=None):
         """Frames i .. i+k-1 of a window (slots base+i ..; first-try masks computed), the first of which is known or
         expected to fail its first try: all of them at once, speculating that every one fails both tries.  While frames
         fail, nothing a frame needs depends on the frame before it except the count of misses: its search mode (sliding
@@ -189,6 +189,8 @@ class StreamPipeline:
         frames behind it are chained from its record at once (`speculate(position)`, the caller's launcher), beside the second
         tries still to run in front of it: those usually fail too, and the chain has then done its work under them.
         Returns (frames committed >= 1, ended with a success, that chain or None).
+        `viz` (a `_VizWindow`): the committed frames' search visualisations are enqueued here, before a first-try mask or
+        search is run again over one of their slots.
         State after every frame = `_step` frame by frame (tests/test_stream_driver_cpu.py, tests/fuzz_chain.py)."""
         ctx = self._ctx
         tries = [first_try] + ([self._SECOND_TRY] if (n_tries >= 2 or n_tries == -1) else [])
@@ -233,7 +235,7 @@ class StreamPipeline:
 
         rec1 = search(0, 0, k) if k else None
         if rec1 is None:
-            self._step(frames[i], first_try, n_tries, False, slot=base + i, have_mask=True, lazy=True, annotate=annotate, defer=deferred)
+            self._step(frames[i], first_try, n_tries, False, slot=base + i, have_mask=True, lazy=True, annotate=annotate, defer=deferred, viz=viz)
             return 1, bool(self.valid_lane_lines), None
         v1 = verdicts(rec1)
         end = first_where(v1 != 0, k)                              # frames [0, end) failed their first try for certain
@@ -249,7 +251,7 @@ class StreamPipeline:
                 if spec is not None:
                     ctx.band_fit_chain_cancel()
                 ctx.mask_run(e2, fp, first=base + i, reuse_front=True)
-                self._step(frames[i], first_try, n_tries, False, slot=base + i, have_mask=True, lazy=True, annotate=annotate, defer=deferred)
+                self._step(frames[i], first_try, n_tries, False, slot=base + i, have_mask=True, lazy=True, annotate=annotate, defer=deferred, viz=viz)
                 return 1, bool(self.valid_lane_lines), None
             v2 = verdicts(rec2)
             end = min(end, first_where(v2 != 0, e2))
@@ -264,6 +266,18 @@ class StreamPipeline:
         if spec is not None and not (win is not None and win[0] == 0 and i + committed == spec[0]):
             ctx.band_fit_chain_cancel()  # a second try succeeded in front of it (or a frame needs care): its seed is not the stream's state
             spec = None
+        if viz is not None and committed:
+            # what `_step` would have drawn each committed frame from: its last attempt -- the slots still hold that attempt's
+            # mask, lists and centroids; the first-try search run again below for the tracker's lists would replace them
+            for j in range(committed):
+                t, r = win if j == end else ((1, rec2[j]) if rec2 is not None else (0, rec1[j]))
+                if not r["detected"]:
+                    viz.add(base + i + j, 0, tries[t])
+                elif j < n_bs:
+                    viz.add(base + i + j, 2, tries[t], fit=(r["left_coeffs"], r["right_coeffs"]), band=(seed[:3], seed[3:]))
+                else:
+                    viz.add(base + i + j, 1, tries[t], fit=(r["left_coeffs"], r["right_coeffs"]))
+            viz.flush()
         last = None                      # the most recent search of the committed frames that found pixels: (frame, try, record)
         for j in range(end):
             final = rec2[j] if rec2 is not None else rec1[j]
@@ -313,11 +327,11 @@ class StreamPipeline:
         if e2 > committed:               # frames behind the last committed one still carry second-try masks
             ctx.mask_run(e2 - committed, fp, first=base + i + committed, reuse_front=True)
         if not committed:                # frame i itself needs the frame-by-frame route (a rank-deficient fit)
-            self._step(frames[i], first_try, n_tries, False, slot=base + i, have_mask=True, lazy=True, annotate=annotate, defer=deferred)
+            self._step(frames[i], first_try, n_tries, False, slot=base + i, have_mask=True, lazy=True, annotate=annotate, defer=deferred, viz=viz)
             return 1, bool(self.valid_lane_lines), None
         return committed, win is not None, spec
 
-    def _run_window_chained(self, frames, first_try, fp, n_tries, annotate, deferred, base=0, prefed=0, ahead=None, flush=None):
+    def _run_window_chained(self, frames, first_try, fp, n_tries, annotate, deferred, base=0, prefed=0, ahead=None, flush=None, viz=None):
         """The frame loop of a window with the searches chained on the device.  State after every frame, and every
         attribute at the end, equal those of `_step` frame by frame (tests/test_gpu_chain.py, tests/fuzz_chain.py).
         The window's frames live in slots base .. base+n-1; the first `prefed` of them already have their upload and
@@ -434,7 +448,7 @@ class StreamPipeline:
                         started = True
                         yield
                     self._step(frames[i], first_try, n_tries, False, slot=base + i, have_mask=True, lazy=True, annotate=annotate,
-                               defer=deferred)
+                               defer=deferred, viz=viz)
                     i += 1
                     continue
                 flight.append(first_chain)
@@ -475,7 +489,15 @@ class StreamPipeline:
                 if annotate:
                     deferred.append(('lane', (self.left_avg_y, self.left_avg_x, self.right_avg_y, self.right_avg_x),
                                      self._lane_text()))
+            if viz is not None and g:
+                # the band of frame j of a chain was drawn around frame j - 1's fit, the first one's around the state's (`launch`,
+                # `launch_behind`: the record the chain before left is that state by now)
+                around = None if mode == 'sws' else np.concatenate([np.asarray(self.last_left_coeffs, np.float64).reshape(1, 3),
+                                                                    np.asarray(self.last_right_coeffs, np.float64).reshape(1, 3)], 1)
+                viz.add_chain(base + first, mode, first_try, np.asarray(LF[:g], np.float64), np.asarray(RF[:g], np.float64), around)
             self._commit_valid_run(LF, RF, g, skip, annotate, partial, deferred, commit)
+            if viz is not None:
+                viz.flush()
             i = first + g
             if flush is not None:
                 flush(False)             # render and download what has been committed so far, under the searches still running
@@ -500,7 +522,7 @@ class StreamPipeline:
                         return at, L, 'bs'
                     with ctx.urgent():   # not behind the masks of later frames queued on the slots' streams
                         done, recovered, spec = self._fail_group(frames, base, i, k, first_try, fp, n_tries, annotate, deferred,
-                                                                 speculate if self.outage_groups else None)
+                                                                 speculate if self.outage_groups else None, viz=viz)
                     i += done
                     if flush is not None:
                         flush(False)
@@ -540,8 +562,6 @@ class StreamPipeline:
         if unknown:
             raise TypeError("unexpected keyword(s): " + ", ".join(sorted(unknown)))
         k.update(kwargs)
-        if k["visualize_search"] or k["split_view"]:
-            raise NotImplementedError("search visualisation / split view are not available in the stream pipeline")
         first_try = (k["ksize_r"], k["C_r"], k["ksize_b"], k["C_b"], k["filter_type"], k["mask_noise"], k["noise_thresh"],
                      k["ksize_noise"], k["C_noise"], k["window_width"], k["window_height"], k["search_range"], k["mu"],
                      k["no_success_limit"], k["start_slice"], k["ignore_sides"], k["ignore_bottom"], k["bandwidth"],
@@ -556,7 +576,8 @@ class StreamPipeline:
         (`stream_lookahead` + 1 windows, one more with annotation) sized once, the search and chain buffers for both parameter
         sets, the presentation stage's buffers, the glyph atlas and -- `output_pool` -- the memory the annotated frames of the first
         windows will be returned in, every page touched (first touch of fresh memory runs at ~10 GB/s: 70 ms per window of 256
-        1280x720 frames, which a stream that was not warmed pays inside its first three or four windows).  Optional -- a stream
+        1280x720 frames, which a stream that was not warmed pays inside its first three or four windows); with `visualize_search` /
+        `split_view` among the keywords also the staging ring their pictures pass through.  Optional -- a stream
         that was not warmed does the same work on the way -- and repeatable (a no-op the second time).  Returns the seconds it took."""
         import time
         t0 = time.perf_counter()
@@ -576,6 +597,10 @@ class StreamPipeline:
             mode = 2 if (rows is not None and rows[4] is not None) else 1
         if mode == 2 and output_pool and annotate != "inplace":   # the pool of output frames: a window being filled, one landing, one with the caller, one to spare
             _native.frames_prefault((int(window), ctx.img_h, ctx.img_w, 3), regions)
+        if k["visualize_search"]:        # the staging ring of the search visualisations / split-view panes (lt_warm: + 4 / + 8)
+            mode += 4
+        elif k["split_view"]:
+            mode += 8
         for q in (first_try, self._SECOND_TRY):
             ctx.warm(_native.search_params(window_width=q[9], window_height=q[10], search_range=q[11], mu=q[12], no_success_limit=q[13],
                                            start_slice=q[14], ignore_sides=q[15], ignore_bottom=q[16], partial=q[18]),
@@ -742,11 +767,15 @@ class StreamPipeline:
         `kwargs` are `process()`'s keywords.  Returns the list of annotated frames, or None for every
         frame when `annotate=False` (state and attributes are updated identically).  `annotate="inplace"` (not in the
         reference: its draw_lane returns a new image) draws into `frames` itself where the frames travel as strips -- a
-        C-contiguous, writeable uint8 window -- and returns its frames; otherwise it behaves like `annotate=True`.  For
+        C-contiguous, writeable uint8 window -- and returns its frames; otherwise it behaves like `annotate=True`.
+        `visualize_search=True` / `split_view=True` return per frame what `process()` returns with them -- (annotated frame or
+        None, picture), or the split view (needs `annotate=True`) -- painted by the device from what the frame's slot holds at its
+        commit (`_VizWindow`, lt_search_viz_run / lt_split_panes_run).  For
         consecutive windows of one video prefer `process_stream`, which keeps the device busy across window boundaries."""
         if self._in_stream:
             raise RuntimeError("process_batch() inside an active process_stream() would overwrite its frames")
         k, first_try, fp = self._batch_arguments(kwargs)
+        mode = self._viz_mode(k, annotate)
         self._annotate_inplace = isinstance(annotate, str) and annotate == "inplace"   # (a window _as_window had to copy: into the copy)
         frames = self._as_window(frames)
         n = frames.shape[0]
@@ -758,14 +787,15 @@ class StreamPipeline:
             self._window_rows = self._rows_for_window(frames) if annotate else None
             try:
                 flush, out = self._window_renderer(deferred, 0, n, frames=frames) if (annotate and n) else (None, None)
-                for _ in self._run_window_chained(frames, first_try, fp, k["n_tries"], annotate, deferred, flush=flush):
+                viz = _VizWindow(self, n, mode == 'split') if mode else None
+                for _ in self._run_window_chained(frames, first_try, fp, k["n_tries"], annotate, deferred, flush=flush, viz=viz):
                     pass
                 self._materialise_pending()  # the attributes describe the last frame, as after process() (also waits for `out`)
-                if out is not None:
+                if out is not None or viz is not None:
                     ctx.sync()
+                if out is not None:
                     self._copies_done(flush.group)
-                    return list(out)
-                return [None] * n
+                return self._with_viz(list(out) if out is not None else [None] * n, viz)
             finally:
                 self._all_copies_done()
                 self._window_rows = None
@@ -778,14 +808,49 @@ class StreamPipeline:
             ctx.mask_run(n, fp)
             if annotate:
                 self._upload_keepalive = self._feed_rest(frames, 0)        # beside the mask chain, for the overlay
+            painted = [] if mode else None       # this route paints on the host, as process() does
             for i in range(n):
                 self._step(frames[i], first_try, k["n_tries"], k["diagnostics"], slot=i, have_mask=True, lazy=True,
-                           annotate=annotate, defer=deferred)
+                           annotate=annotate, visualize_search=mode == 'vis', split_view=mode == 'split', defer=deferred, viz=painted)
         self._materialise_pending()      # the attributes describe the last frame, as after process()
         try:
-            return self._render_window(deferred, 0) if annotate else [None] * n
+            annotated = self._render_window(deferred, 0) if annotate else [None] * n
+            if mode == 'vis':
+                return [(a, p[0]) for a, p in zip(annotated, painted)]
+            if mode == 'split':
+                return [self.triple_split_view([a, p[1], p[0]]) for a, p in zip(annotated, painted)]
+            return annotated
         finally:
             self._device_frames_done()
+
+    @staticmethod
+    def _viz_mode(k, annotate):
+        """'vis' (`visualize_search`; it wins when both are set, as in `_step`'s `present`), 'split' (`split_view`) or None."""
+        if k["visualize_search"]:
+            return 'vis'
+        if not k["split_view"]:
+            return None
+        if not annotate:
+            raise ValueError("split_view shows the annotated frame: it needs annotate=True")
+        if isinstance(annotate, str) and annotate == "inplace":
+            raise ValueError("split_view returns a new, larger image: it cannot be drawn in place")
+        return 'split'
+
+    def _with_viz(self, annotated, viz):
+        """A window's annotated frames (or Nones) and its `_VizWindow`, both landed -> what `process()` returns per frame with the
+        same keywords: (annotated, picture), or the split view -- the annotated frame on top, the pane strip below."""
+        if viz is None:
+            return annotated
+        if not viz.split:
+            return list(zip(annotated, viz.pictures()))
+        H = self._ctx.img_h
+        views = []
+        for a, panes in zip(annotated, viz.out if viz.out is not None else []):
+            v = np.empty((H + panes.shape[0],) + panes.shape[1:], np.uint8)
+            v[:H] = a
+            v[H:] = panes
+            views.append(v)
+        return views
 
     def process_stream(self, windows, annotate=True, **kwargs):
         """Generator over consecutive windows of ONE video: `windows` yields arrays (n, H, W, 3); for each, what
@@ -796,6 +861,7 @@ class StreamPipeline:
         tracker until the generator is exhausted or closed.  `annotate="inplace"`: see `process_batch` (every window must be a
         C-contiguous, writeable uint8 array; a window that is not comes back as new frames)."""
         k, first_try, fp = self._batch_arguments(kwargs)
+        mode = self._viz_mode(k, annotate)
         self._annotate_inplace = isinstance(annotate, str) and annotate == "inplace"
         if not (self.chain_searches and not k["diagnostics"]):
             for w in windows:            # the frame-by-frame route has nothing to overlap
@@ -828,13 +894,15 @@ class StreamPipeline:
 
         def landed():
             nonlocal landing
-            arrays, region, group = landing
+            arrays, region, group, viz = landing
             landing = None
             if not (self._window_rows is not None and self._window_rows[4] is not None):
                 ctx.download_overlay_wait()  # these frames have landed; the uploads, masks and searches of the next windows run on
             self._copies_done(group)     # ... and so have the rows the host copies itself and -- strips -- the rows from the device (this window's group only)
+            if viz is not None:
+                ctx.search_viz_wait()    # (the pictures of every window so far: the next window's are not enqueued yet)
             free.append(region)
-            return list(arrays)
+            return self._with_viz(list(arrays), viz)
         self._in_stream = True
         self._window_rows = self._rows_for_window(cur[0]) if annotate else None
         try:
@@ -866,20 +934,23 @@ class StreamPipeline:
                     ahead.append(q)
                 deferred = []
                 flush, frames_out = self._window_renderer(deferred, cur[1], n, frames=cur[0]) if (annotate and n) else (None, None)
+                viz = _VizWindow(self, n, mode == 'split') if mode else None
                 if n:
                     for _ in self._run_window_chained(cur[0], first_try, fp, k["n_tries"], annotate, deferred, base=cur[1],
-                                                      prefed=cur[2], ahead=ahead, flush=flush):
+                                                      prefed=cur[2], ahead=ahead, flush=flush, viz=viz):
                         if landing is not None:      # this window's first searches are in flight: now wait for the frames of the one before
                             yield landed()
                 if landing is not None:
                     yield landed()
                 if frames_out is not None:
-                    landing = (frames_out, cur[1], flush.group)   # handed out when the next window is under way (or the stream ends)
+                    landing = (frames_out, cur[1], flush.group, viz)   # handed out when the next window is under way (or the stream ends)
                     cur = queue.pop(0) if queue else None
                 else:
+                    if viz is not None:
+                        ctx.search_viz_wait()    # (enqueued behind the searches; the region's next window is ordered behind the reads)
                     free.append(cur[1])  # its frames, masks and records are not needed any more
                     cur = queue.pop(0) if queue else None
-                    yield [None] * n
+                    yield self._with_viz([None] * n, viz)
             if landing is not None:
                 yield landed()
             self._materialise_pending()  # the attributes describe the last frame, as after process()
@@ -890,7 +961,7 @@ class StreamPipeline:
                 self._device_frames_done()   # (waits for the device: the attached windows may go)
             except Exception:
                 pass
-            if annotate:                 # a generator closed early: no copy may still be writing into page-locked arrays
+            if annotate or mode:         # a generator closed early: no copy may still be writing into page-locked arrays
                 try:                     # that go back to the pool with their last reference
                     ctx.band_fit_chain_cancel()
                     ctx.sync()
@@ -898,6 +969,70 @@ class StreamPipeline:
                 except Exception:
                     pass
 
+
+
+class _VizWindow:
+    """The search visualisations (`visualize_search=True`) or split-view panes (`split_view=True`) of a window's frames, painted by
+    the device: one descriptor per committed frame, in frame order -- what `_step` would have drawn that frame from: the kind of
+    picture (the search of its last attempt, or the bare mask when that found nothing), the parameter set of that attempt, the plot
+    points of its fit and, for a band, of the curves the band was searched around -- and `flush()`, which enqueues the pictures of
+    the descriptors gathered since the last call (lt_search_viz_run / lt_split_panes_run) while their slots still hold the mask,
+    lists and centroids of those attempts.  `out` is complete after `Context.search_viz_wait()`."""
+
+    def __init__(self, tracker, n, split):
+        self.tracker, self.ctx, self.split = tracker, tracker._ctx, split
+        self.descs, self.done = [], 0
+        self.out = None
+        if n:
+            shape = (self.ctx.split_panes_size()[1], self.ctx.img_w, 3) if split else (self.ctx.warp_h, self.ctx.warp_w, 3)
+            self.out = _native.pinned_empty((n,) + shape)
+
+    def _points(self, left, right, partial):
+        ploty, ploty2 = self.tracker._plot_rows(partial)
+        co = np.concatenate([np.asarray(left, np.float64).reshape(-1, 3), np.asarray(right, np.float64).reshape(-1, 3)], 1)
+        ln, rn, lyx, ryx = _native.poly_points(self.tracker.warped_size, co, ploty, ploty2)
+        le, re = np.cumsum(ln), np.cumsum(rn)
+        return [(lyx[le[q] - ln[q]:le[q]], ryx[re[q] - rn[q]:re[q]]) for q in range(len(co))]
+
+    def add(self, slot, kind, used, fit=None, band=None):
+        """One frame: `used` is the parameter tuple of the attempt shown (`first_try` or `_SECOND_TRY`), `fit` its (left, right)
+        coefficients, `band` the (left, right) coefficients its band was searched around."""
+        f = self._points(fit[0], fit[1], 1)[0] if kind else (_NO_POINTS, _NO_POINTS)
+        b = self._points(band[0], band[1], used[18])[0] if kind == 2 else (_NO_POINTS, _NO_POINTS)
+        self.descs.append((slot, kind, used[9], used[10], used[16], used[17], f[0], f[1], b[0], b[1]))
+
+    def add_chain(self, slot0, mode, used, LF, RF, around):
+        """The frames of a chain whose first tries were valid, slots slot0 ..: a sliding-window search first when `mode` says so, bands
+        behind it, each around the fit of the frame before (`around`, (1, 6): the curves of the first band)."""
+        g = len(LF)
+        fits = self._points(LF, RF, 1)
+        prev = np.concatenate([LF, RF], 1)[:-1]
+        prev = np.concatenate([around if around is not None else np.zeros((1, 6)), prev], 0)
+        bands = self._points(prev[:, :3], prev[:, 3:], used[18])
+        for j in range(g):
+            sws = mode == 'sws' and j == 0
+            b = (_NO_POINTS, _NO_POINTS) if sws else bands[j]
+            self.descs.append((slot0 + j, 1 if sws else 2, used[9], used[10], used[16], used[17], fits[j][0], fits[j][1], b[0], b[1]))
+
+    def flush(self):
+        lo, hi = self.done, len(self.descs)
+        if hi <= lo:
+            return
+        part = self.descs[lo:hi]
+        items = np.zeros(len(part), _native.VIZ_ITEM_DTYPE)
+        for q, d in enumerate(part):
+            items[q] = (d[0], d[1], d[2], d[3], d[4], d[5], len(d[6]), len(d[7]), len(d[8]), len(d[9]), (0, 0))
+        lists = [np.concatenate([d[c] for d in part]) for c in (6, 7, 8, 9)]
+        run = self.ctx.split_panes_run if self.split else self.ctx.search_viz_run
+        run(items, *lists, out=self.out[lo:hi])
+        self.done = hi
+
+    def kinds(self):
+        return [d[1] for d in self.descs]
+
+    def pictures(self):
+        """The window's pictures as `process()` returns them (a bare mask is two-dimensional); call after search_viz_wait()."""
+        return [np.ascontiguousarray(self.out[q][:, :, 0]) if d[1] == 0 else self.out[q] for q, d in enumerate(self.descs)]
 
 
 class _PackedPoly:

@@ -207,9 +207,11 @@ class FrameSink:
         self.close()
 
 
-def process_frames(tracker, source, sink=None, window=64, **process_kwargs):
+def process_frames(tracker, source, sink=None, window=64, viz_sink=None, **process_kwargs):
     """Run every frame of `source` through the tracker, in order, `window` frames per GPU batch; write the
-    annotated frames to `sink` if there is one.  Returns (frames, seconds)."""
+    annotated frames to `sink` if there is one -- the split views with `split_view=True` among the keywords, for a sink of
+    that size -- and the search visualisations (bird's-eye size; `visualize_search=True` is set) to `viz_sink` if there
+    is one.  Returns (frames, seconds)."""
     t0 = time.perf_counter()
     n = len(source)
     want, have = getattr(source, "pixel_format", "rgb"), getattr(tracker, "pixel_format", "rgb")
@@ -217,7 +219,14 @@ def process_frames(tracker, source, sink=None, window=64, **process_kwargs):
         raise ValueError("the source delivers %r frames, the tracker was built with pixel_format=%r" % (want, have))
     windows = (source.read(start, start + window) for start in range(0, n, window))
     # process_stream: the uploads and masks of window k+1 run while the searches of window k drain
+    if viz_sink is not None:
+        process_kwargs = dict(process_kwargs, visualize_search=True)
     for out in tracker.process_stream(windows, annotate=sink is not None, **process_kwargs):
+        if process_kwargs.get("visualize_search"):        # (annotated frame or None, picture) per frame
+            pictures = [p if p.ndim == 3 else np.repeat(p[:, :, None], 3, axis=2) for _, p in out]
+            out = [a for a, _ in out]
+            if viz_sink is not None:
+                viz_sink.write(np.stack(pictures, 0))
         if sink is not None:
             sink.write(np.stack(out, 0))
     return n, time.perf_counter() - t0
@@ -278,7 +287,16 @@ def main(argv=None):
     ap.add_argument("--frame-count", action="store_true", help="print the frame number onto each image")
     ap.add_argument("--settings", choices=("default", "demo1", "demo2", "demo3"), default="default",
                     help="parameter set of tracker_settings.md (process() keywords + validity limits)")
+    ap.add_argument("--split-view", action="store_true",
+                    help="write split views: the annotated frame above the bird's-eye image and the search visualisation")
+    ap.add_argument("--visualize-search", metavar="DIR", default=None,
+                    help="a second sink (directory, .npy or raw .rgb) for the search visualisations, bird's-eye size")
     a = ap.parse_args(argv)
+    if a.split_view and a.output == "-":
+        ap.error("--split-view shows the annotated frames: it needs an output")
+    if a.split_view and a.visualize_search:
+        ap.error("--split-view and --visualize-search are two runs: process() returns one or the other")
+    from . import _native
     from .lane_tracker import LaneTracker
     from .utils import load_camera_calib, load_warp_params
     cam_matrix, dist_coeffs = load_camera_calib(a.cam)
@@ -290,14 +308,21 @@ def main(argv=None):
                      warp_matrices=(M, Minv), mpp_conversion=(mppv, mpph), n_fail=8, n_reset=4, n_average=2,
                      print_frame_count=a.frame_count, device=a.device, pixel_format=src.pixel_format, yuv_matrix=a.yuv_matrix)
     try:
-        sink = None if a.output == "-" else FrameSink(a.output, src.size, n=len(src))
+        out_size = src.size
+        if a.split_view:                 # the annotated frame on top, the pane strip below it
+            out_size = (src.size[0], src.size[1] + _native.split_panes_size(src.size, warped_wh)[1])
+        sink = None if a.output == "-" else FrameSink(a.output, out_size, n=len(src))
+        viz_sink = FrameSink(a.visualize_search, warped_wh, n=len(src)) if a.visualize_search else None
         kw = {}
         if a.settings != "default":
             from . import settings
             kw = settings.apply(lt, settings.DEMOS[a.settings])
-        n, dt = process_frames(lt, src, sink, window=a.window, **kw)
-        if sink is not None:
-            sink.close()
+        if a.split_view:
+            kw["split_view"] = True
+        n, dt = process_frames(lt, src, sink, window=a.window, viz_sink=viz_sink, **kw)
+        for s_ in (sink, viz_sink):
+            if s_ is not None:
+                s_.close()
         ratio, success, total = lt.get_success_ratio() if lt.counter else (0.0, 0, 0)
         print("Frames: {}  ({:.1f} frames/s including I/O)".format(n, n / dt if dt > 0 else 0.0))
         print("Success ratio: ", ratio)
