@@ -54,7 +54,8 @@ extern "C" {
  *    lt_device_frames_rest (camera frames that already lie in device memory, read where they lie), lt_device_alloc / _free /
  *    _write / _read (device blocks for callers without a HIP binding of their own), lt_device_stream_wait; lt_viz_item +
  *    lt_search_viz_run + lt_split_panes_run + lt_split_panes_size + lt_search_viz_wait (the search visualisations and split-view
- *    panes of listed frames, painted on the device), lt_calib_split_panes_size, lt_resize_linear_u8.  Nothing removed or changed. */
+ *    panes of listed frames, painted on the device), lt_calib_split_panes_size, lt_resize_linear_u8; lt_rgb_to_surfaces + lt_overlay_store_device +
+ *    lt_overlay_store_wait (annotated frames written into the caller's device surfaces, RGB, NV12 or I420).  Nothing removed or changed. */
 #define LT_ABI_VERSION 5
 
 typedef enum lt_status {
@@ -504,6 +505,41 @@ int  lt_download_overlay_rows_async(lt_ctx* ctx, int first_slot, int n, uint8_t*
 /* Wait until every copy enqueued by lt_download_overlay_async has landed -- and for nothing else: uploads and masks of
  * later frames keep running (lt_sync would drain them too). */
 int  lt_download_overlay_wait(lt_ctx* ctx);
+/* ---- device sinks: annotated frames into surfaces the caller owns ------------------------------------------------------------
+ * The way out that mirrors lt_attach_device_frames: the whole annotated frames of slots -- RGB, dense, in the context's own
+ * memory -- are written by a kernel into lt_device_surface destinations in device memory: RGB rows at the caller's pitch, or
+ * YUV 4:2:0 as an encoder takes it, NV12 or I420, planes anywhere, any pitch, any byte alignment (16-byte aligned bases and
+ * pitches and a width that is a multiple of 16 take the wide kernels).  `layout` is an lt_input_layout and has nothing to do with
+ * the context's input format: an RGB camera may feed an NV12 encoder.  RGB -> YUV is OpenCV's integer arithmetic
+ * (cv2.cvtColor(img, COLOR_RGB2YUV_I420), 20-bit fixed point, no chroma averaging):
+ *     Y = clamp((CRY r + CGY g + CBY b + 2^19 + (16  << 20)) >> 20)     every pixel
+ *     U = clamp((CRU r + CGU g + CBU b + 2^19 + (128 << 20)) >> 20)     of the pixel at (even row, even column) of each 2 x 2 block
+ *     V = clamp((CBU r + CGV g + CBV b + 2^19 + (128 << 20)) >> 20)     of the same pixel; its R coefficient IS CBU
+ * with coeffs = {CRY, CGY, CBY, CRU, CGU, CBU, CGV, CBV} (LT_RGB2YUV_BT601: OpenCV's own; LT_RGB2YUV_BT709; any other matrix
+ * whose magnitudes stay below 2^23 and whose rows keep sum |c| * 255 + 2^19 + (128 << 20) inside 32 bits).  coeffs is not read
+ * for LT_INPUT_RGB.
+ * Every destination plane is checked on the host BEFORE anything is launched, by the rules of lt_attach_device_frames: device
+ * memory of that device, known to this runtime, its whole extent -- pitch * (rows - 1) + row bytes -- inside one allocation,
+ * pitches at least a row wide and below 2^23; width and height even for 4:2:0; no two planes of a call sharing a byte; and for a
+ * context no destination sharing a byte with a camera surface attached to any of its slots (annotating a decoder's surface in place
+ * is not supported; a slot stays attached until an upload of camera rows detaches it).  Anything else is LT_ERR_INVALID with a
+ * message; a slot that holds only row runs of its annotated frame is LT_ERR_STATE (as for lt_download_overlay); nothing is launched
+ * and the context is as it was.  Only bytes inside a row of a plane are ever written: what lies between rows and around planes
+ * stays the caller's.
+ *   lt_rgb_to_surfaces       n dense RGB frames of h x w (at most 16384 each), frame_stride bytes apart, in a block of
+ *                            lt_device_alloc -> dst[0 .. n); synchronous.  For callers without a context, tools, tests.
+ *   lt_overlay_store_device  the whole annotated frames of slots [first_slot, first_slot + n) -> dst[0 .. n), enqueued on the
+ *                            presentation stream behind the lt_overlay_run / lt_overlay_text that wrote them; returns without
+ *                            waiting.  dst[] itself is read before the call returns; the memory it names must stay valid until
+ *                            lt_overlay_store_wait, or an lt_sync, has returned -- its content is final then.  A later
+ *                            lt_overlay_run over the same slots is ordered behind the store by the stream.
+ *   lt_overlay_store_wait    the host waits until every store enqueued so far has landed -- and for nothing else. */
+#define LT_RGB2YUV_BT601 {269484, 528482, 102760, -155188, -305135, 460324, -385875, -74448}   /* video range; OpenCV's constants */
+#define LT_RGB2YUV_BT709 {191455, 644067, 65019, -105533, -355018, 460551, -418321, -42230}    /* video range; round(c * 2^20) */
+int  lt_rgb_to_surfaces(int device, const void* rgb, size_t frame_stride, int h, int w, int n, const lt_device_surface* dst, int layout,
+                        const int32_t coeffs[8]);
+int  lt_overlay_store_device(lt_ctx* ctx, int first_slot, int n, const lt_device_surface* dst, int layout, const int32_t coeffs[8]);
+int  lt_overlay_store_wait(lt_ctx* ctx);
 /* How lt_download_overlay_async moves the frames: 0 = the copy engine, 1 = a kernel storing into the (page-locked, 16-byte
  * aligned) destination, -1 (default) = chosen by measurement: every copy is timed, the engine is used while its copies
  * reach ~42 GB/s, otherwise whichever of the two measures faster (the engine's rate depends on how the process's memory

@@ -235,12 +235,42 @@ _SIGNATURES = {
     "lt_device_write": (C.c_int, [_P, _P, C.c_size_t]),
     "lt_device_read": (C.c_int, [_P, _P, C.c_size_t]),
     "lt_device_stream_wait": (C.c_int, [C.c_int, C.c_size_t]),
+    "lt_rgb_to_surfaces": (C.c_int, [C.c_int, _P, C.c_size_t, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),
+    "lt_overlay_store_device": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P]),
+    "lt_overlay_store_wait": (C.c_int, [_P]),
 }
 
 # camera-frame formats (lt_input_layout) and the conversion matrices {CY, CVR, CVG, CUG, CUB} of include/lane_tracker_amd.h
 PIXEL_FORMATS = {"rgb": 0, "nv12": 1, "i420": 2}
 YUV_MATRICES = {"bt601": (1220542, 1673527, -852492, -409993, 2116026),
                 "bt709": (1220542, 1880097, -558891, -223347, 2214593)}
+
+
+# ... and the way out, RGB -> YUV 4:2:0 {CRY, CGY, CBY, CRU, CGU, CBU, CGV, CBV} (LT_RGB2YUV_BT601 / _BT709)
+RGB2YUV_MATRICES = {"bt601": (269484, 528482, 102760, -155188, -305135, 460324, -385875, -74448),
+                    "bt709": (191455, 644067, 65019, -105533, -355018, 460551, -418321, -42230)}
+
+
+def rgb2yuv_coeffs(matrix):
+    """'bt601' / 'bt709', or eight integers {CRY, CGY, CBY, CRU, CGU, CBU, CGV, CBV} -> the int32 array the library takes."""
+    if isinstance(matrix, str):
+        if matrix not in RGB2YUV_MATRICES:
+            raise ValueError("matrix must be 'bt601' or 'bt709', got %r" % (matrix,))
+        matrix = RGB2YUV_MATRICES[matrix]
+    k = np.ascontiguousarray(matrix, dtype=np.int32)
+    if k.shape != (8,):
+        raise ValueError("an RGB -> YUV matrix is eight integers")
+    return k
+
+
+def rgb_to_surfaces(rgb_ptr, frame_stride, img_size, sink, matrix="bt601", device=0):
+    """len(sink) dense RGB frames of `img_size` at device address `rgb_ptr` (a block of lt_device_alloc), `frame_stride` bytes
+    apart -> the surfaces of `sink` (a device.DeviceFrames), in its pixel format (lt_rgb_to_surfaces); synchronous."""
+    layout = pixel_format_id(sink.pixel_format)
+    k = rgb2yuv_coeffs(matrix) if layout else None
+    s = np.ascontiguousarray(sink.surfaces)
+    _check(load().lt_rgb_to_surfaces(int(device), C.c_void_p(int(rgb_ptr)), int(frame_stride), int(img_size[1]), int(img_size[0]), s.shape[0],
+                                     s.ctypes.data, layout, None if k is None else k.ctypes.data))
 
 
 def pixel_format_id(pixel_format):
@@ -953,6 +983,23 @@ class Context:
         _check(self.lib.lt_download_stats(self._h, C.byref(eg), C.byref(ec), C.byref(kg), C.byref(kc), C.byref(m)))
         return {"engine_GBs": round(eg.value, 1), "engine_copies": ec.value, "kernel_GBs": round(kg.value, 1), "kernel_copies": kc.value,
                 "method": "kernel" if m.value == 1 else "engine"}
+
+    def store_overlay_device(self, sink, first=0, matrix="bt601"):
+        """Enqueue the whole annotated frames of slots first .. first + len(sink) - 1 into `sink`, a device.DeviceFrames of this
+        context's image size in any pixel format -- RGB at its pitch, or NV12 / I420 converted with `matrix` ('bt601', 'bt709' or
+        eight integers) -- behind the overlay_run / overlay_text that wrote them (lt_overlay_store_device).  Nothing crosses the
+        bus.  The sink's memory is final after store_wait() or sync(); keep it alive until then."""
+        if sink.img_size != (self.img_w, self.img_h):
+            raise ValueError("expected a sink of %dx%d frames, got %dx%d" % ((self.img_w, self.img_h) + sink.img_size))
+        layout = pixel_format_id(sink.pixel_format)
+        k = rgb2yuv_coeffs(matrix) if layout else None
+        s = np.ascontiguousarray(sink.surfaces)
+        _check(self.lib.lt_overlay_store_device(self._h, int(first), s.shape[0], s.ctypes.data, layout, None if k is None else k.ctypes.data))
+        return sink
+
+    def store_wait(self):
+        """Block until every store_overlay_device so far has landed -- and for nothing else."""
+        _check(self.lib.lt_overlay_store_wait(self._h))
 
     def download_overlay_wait(self):
         """Block until the frames of every download_overlay_async have landed (later uploads / masks keep running)."""

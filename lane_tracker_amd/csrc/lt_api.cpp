@@ -655,6 +655,7 @@ void lt_destroy(lt_ctx* c) {
     stream_put(c->present);
     stream_put(c->urgent);
     if (c->rest_done) (void)hipEventDestroy(c->rest_done);
+    if (c->store_done) (void)hipEventDestroy(c->store_done);
     note("hipHostFree(spans, lines, xpos)");
     if (c->h_spans) (void)hipHostFree(c->h_spans);
     if (c->h_lines) (void)hipHostFree(c->h_lines);
@@ -1245,16 +1246,16 @@ int lt_upload_frame_rest(lt_ctx* c, const uint8_t* frames, int first, int n) {
 // Every plane of every surface is checked on the host before anything is launched: device memory of this context's device, its
 // whole extent inside one allocation.  Blocks of lt_device_alloc are known to the library (no query); for anything else the
 // runtime is asked -- per allocation once within a call, and never remembered beyond it (the caller may free it afterwards).
-namespace {
-struct KnownRange { uintptr_t base = 0; size_t size = 0; };
-int check_plane(lt_ctx* c, const void* p, size_t extent, int k, int i, KnownRange& memo) {
+}  // extern "C"
+namespace lt {
+int check_plane(int device, const void* p, size_t extent, int k, int i, KnownRange& memo) {
     if (!p) return fail(LT_ERR_INVALID, "surface %d: plane %d is a null pointer", k, i);
     const uintptr_t a = (uintptr_t)p;
     const void* base = nullptr;
     size_t size = 0;
     int dev = 0;
     if (cached_block_find(p, &base, &size, &dev)) {
-        if (dev != c->device) return fail(LT_ERR_INVALID, "surface %d: plane %d lies on device %d, the context on device %d", k, i, dev, c->device);
+        if (dev != device) return fail(LT_ERR_INVALID, "surface %d: plane %d lies on device %d, not on device %d", k, i, dev, device);
         if (a + extent > (uintptr_t)base + size)
             return fail(LT_ERR_INVALID, "surface %d: plane %d runs past the end of its allocation (%zu bytes from the pointer, %zu left)", k, i, extent,
                         (size_t)((uintptr_t)base + size - a));
@@ -1267,7 +1268,7 @@ int check_plane(lt_ctx* c, const void* p, size_t extent, int k, int i, KnownRang
         return fail(LT_ERR_INVALID, "surface %d: plane %d (%p) is not device memory of this process's HIP runtime (a host pointer, or memory of another runtime)", k, i, p);
     }
     if (at.type != hipMemoryTypeDevice) return fail(LT_ERR_INVALID, "surface %d: plane %d (%p) is not device memory", k, i, p);
-    if (at.device != c->device) return fail(LT_ERR_INVALID, "surface %d: plane %d lies on device %d, the context on device %d", k, i, at.device, c->device);
+    if (at.device != device) return fail(LT_ERR_INVALID, "surface %d: plane %d lies on device %d, not on device %d", k, i, at.device, device);
     hipDeviceptr_t rb = nullptr;
     size_t rs = 0;
     if (hipMemGetAddressRange(&rb, &rs, (hipDeviceptr_t)const_cast<void*>(p)) != hipSuccess) {
@@ -1281,6 +1282,9 @@ int check_plane(lt_ctx* c, const void* p, size_t extent, int k, int i, KnownRang
     memo.size = rs;
     return LT_OK;
 }
+}  // namespace lt
+extern "C" {
+namespace {
 int check_surfaces(lt_ctx* c, const lt_device_surface* s, int n, SurfEntry* out) {
     const int H = c->calib.img_h, W = c->calib.img_w, layout = c->in_layout;
     const int row = layout == LT_INPUT_RGB ? 3 * W : W, crow = layout == LT_INPUT_NV12 ? W : W / 2;
@@ -1292,7 +1296,7 @@ int check_surfaces(lt_ctx* c, const lt_device_surface* s, int n, SurfEntry* out)
         if (f.pitch > PITCH_MAX) return fail(LT_ERR_INVALID, "surface %d: pitch %d is too large", k, (int)f.pitch);
         const size_t ext = (size_t)f.pitch * (size_t)(H - 1) + (size_t)row;
         if (ext >= ((size_t)1 << 31) - 8) return fail(LT_ERR_INVALID, "surface %d: a plane of %zu bytes is too large", k, ext);
-        int rc = check_plane(c, f.plane[0], ext, k, 0, memo);
+        int rc = check_plane(c->device, f.plane[0], ext, k, 0, memo);
         if (rc) return rc;
         out[k] = SurfEntry{{(uint64_t)(uintptr_t)f.plane[0], 0, 0}, f.pitch, 0};
         if (layout == LT_INPUT_RGB) continue;
@@ -1301,7 +1305,7 @@ int check_surfaces(lt_ctx* c, const lt_device_surface* s, int n, SurfEntry* out)
         const size_t cext = (size_t)f.chroma_pitch * (size_t)(H / 2 - 1) + (size_t)crow;
         if (cext >= ((size_t)1 << 31) - 8) return fail(LT_ERR_INVALID, "surface %d: a plane of %zu bytes is too large", k, cext);
         for (int i = 1; i <= (layout == LT_INPUT_I420 ? 2 : 1); ++i) {
-            if ((rc = check_plane(c, f.plane[i], cext, k, i, memo))) return rc;
+            if ((rc = check_plane(c->device, f.plane[i], cext, k, i, memo))) return rc;
             out[k].plane[i] = (uint64_t)(uintptr_t)f.plane[i];
         }
         out[k].cpitch = f.chroma_pitch;

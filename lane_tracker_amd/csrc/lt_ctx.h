@@ -5,6 +5,7 @@
 //   lt_present.cpp -- presentation stage: lane overlay, text, annotated frames on their way back
 //   lt_chain.cpp   -- the chained band search of a stream (tickets, cancel, collect)
 //   lt_search_viz.cpp -- search visualisations and split-view panes of listed frames, lt_resize_linear_u8
+//   lt_sink.cpp    -- device sinks: annotated frames (or any RGB frames) into the caller's RGB / NV12 / I420 surfaces
 // Not installed; the public ABI is include/lane_tracker_amd.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -219,6 +220,8 @@ struct lt_ctx {
     int dl_since_probe = 0;           // copies since the other method was last tried
     int dl_forced = -1;               // LT_DL_KERNEL=0 / 1, lt_set_download_method: -1 = choose by measurement
     hipEvent_t rest_done = nullptr;   // end of the most recent lt_upload_frame_rest on the copy stream
+    hipEvent_t store_done = nullptr;  // behind the most recent lt_overlay_store_device on the presentation stream (lt_overlay_store_wait)
+    bool store_pending = false;
     bool rest_pending = false;
     // text: glyph atlas (set once) and the per-slot lines of the current call
     uint8_t *d_atlas = nullptr, *d_advance = nullptr, *d_lines = nullptr;
@@ -451,6 +454,11 @@ bool slot_reads_bits(const lt_ctx* c, const SearchGeom& g, int mode, int first, 
 void mark_frames(lt_ctx* c, int first, int n, int full);
 void mark_annot(lt_ctx* c, int first, int n, int full);
 int first_partial(const std::vector<uint8_t>& v, int first, int n);
+// A plane of a caller's surface, checked on the host before anything is launched (lt_attach_device_frames, the device sinks): device
+// memory of `device`, known to this runtime, its whole extent inside one allocation.  `memo`: the allocation the runtime was last
+// asked about, within one call.
+struct KnownRange { uintptr_t base = 0; size_t size = 0; };
+int check_plane(int device, const void* p, size_t extent, int k, int i, KnownRange& memo);
 int ensure_search_stream(lt_ctx* c);                          // lt_chain.cpp
 int ensure_chain_buffers(lt_ctx* c);                          // lt_chain.cpp
 int warm_presentation(lt_ctx* c, bool strips);                // lt_present.cpp

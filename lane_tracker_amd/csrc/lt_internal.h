@@ -95,6 +95,10 @@ void launch_write_surf_entries(hipStream_t s, SurfEntry* tab, int first, const S
 // rows [r0, r1) of the n surfaces of entries[] (host memory) -> the same rows of n RGB frames: a conversion (4:2:0) or a pitched copy (RGB)
 void launch_surf_rows_to_rgb(hipStream_t s, int layout, const SurfEntry* entries, YuvCoef k, uint8_t* rgb, size_t rgb_stride, int w,
                              int r0, int r1, int n);
+// device sinks (k_sink.hip): n dense RGB frames of h x w, rgb_stride bytes apart -> the n surfaces of entries[] (host memory) in
+// `layout`: a pitched copy (RGB) or a conversion with coeffs[8] (4:2:0; h and w even; sink_arith.h), 32 surfaces per launch
+void launch_rgb_to_surfaces(hipStream_t s, int layout, const uint8_t* rgb, size_t rgb_stride, int h, int w, const SurfEntry* entries,
+                            int n, const int32_t* coeffs);
 void launch_split_bev(hipStream_t s, const uint8_t* bev, size_t bev_stride, int npix, const uint16_t* gamma_tab,
                       const uint16_t* cbrt_tab, const int32_t* coeffs, uint8_t* planeR, uint8_t* planeB,
                       size_t plane_stride, int n);

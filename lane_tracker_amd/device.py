@@ -90,6 +90,38 @@ def _extent(rows, row_bytes, pitch):
     return pitch * (rows - 1) + row_bytes
 
 
+def _layout_block(n, img_size, pixel_format, pitch, chroma_pitch, offset):
+    """n frames of `img_size` as pitched surfaces in one block: frame after frame, plane after plane, every row `pitch` (chroma
+    rows: `chroma_pitch`) bytes after the one before, the first at `offset`; the block ends with the last byte of the last plane.
+    -> (bytes of the block, surfaces with plane OFFSETS into it, [(rows, row bytes, pitch) per plane])."""
+    layout = pixel_format_id(pixel_format)
+    (rows, rb), chroma, nplanes = _plane_rows(img_size, pixel_format)
+    pitch = rb if pitch is None else int(pitch)
+    if pitch < rb:
+        raise ValueError("pitch %d is below the row's %d bytes" % (pitch, rb))
+    sizes = [(rows, rb, pitch)]
+    if chroma:
+        default = pitch if layout == 1 else (pitch // 2 if pitch % 2 == 0 else chroma[1])
+        cp = default if chroma_pitch is None else int(chroma_pitch)
+        if cp < chroma[1]:
+            raise ValueError("chroma pitch %d is below the row's %d bytes" % (cp, chroma[1]))
+        sizes += [(chroma[0], chroma[1], cp)] * (nplanes - 1)
+    offset = int(offset)
+    if offset < 0:
+        raise ValueError("offset must not be negative")
+    frame_stride = sum(r * p for r, _, p in sizes)
+    total = offset + n * frame_stride - (sizes[-1][2] - sizes[-1][1])
+    surf = np.zeros(n, SURFACE_DTYPE)
+    surf["pitch"] = pitch
+    surf["chroma_pitch"] = sizes[1][2] if chroma else 0
+    for k in range(n):
+        at = offset + k * frame_stride
+        for i, (r, _, p) in enumerate(sizes):
+            surf["plane"][k, i] = at
+            at += r * p
+    return total, surf, sizes
+
+
 def pack_host_frames(frames, pixel_format="rgb", pitch=None, chroma_pitch=None, offset=0, fill=0):
     """Host frames -- (n, H, W, 3) / (H, W, 3), or (n, H * 3 // 2, W) / (H * 3 // 2, W) for 4:2:0 -- laid out as pitched surfaces in
     one block: frame after frame, plane after plane, every row `pitch` (chroma rows: `chroma_pitch`) bytes after the one before,
@@ -110,35 +142,15 @@ def pack_host_frames(frames, pixel_format="rgb", pitch=None, chroma_pitch=None, 
         if f.shape[1] % 3:
             raise ValueError("a 4:2:0 frame is a 2-D array of shape (H * 3 // 2, W) with H and W even, got %r" % (f.shape[1:],))
         h, w = f.shape[1] // 3 * 2, f.shape[2]
-    (rows, rb), chroma, nplanes = _plane_rows((w, h), pixel_format)
-    pitch = rb if pitch is None else int(pitch)
-    if pitch < rb:
-        raise ValueError("pitch %d is below the row's %d bytes" % (pitch, rb))
-    sizes = [(rows, rb, pitch)]
-    if chroma:
-        default = pitch if layout == 1 else (pitch // 2 if pitch % 2 == 0 else chroma[1])
-        cp = default if chroma_pitch is None else int(chroma_pitch)
-        if cp < chroma[1]:
-            raise ValueError("chroma pitch %d is below the row's %d bytes" % (cp, chroma[1]))
-        sizes += [(chroma[0], chroma[1], cp)] * (nplanes - 1)
-    offset = int(offset)
-    if offset < 0:
-        raise ValueError("offset must not be negative")
     n = f.shape[0]
-    frame_stride = sum(r * p for r, _, p in sizes)
-    total = offset + n * frame_stride - (sizes[-1][2] - sizes[-1][1])
+    total, surf, sizes = _layout_block(n, (w, h), pixel_format, pitch, chroma_pitch, offset)
     block = np.full(total, fill, np.uint8)
-    surf = np.zeros(n, SURFACE_DTYPE)
-    surf["pitch"] = pitch
-    surf["chroma_pitch"] = sizes[1][2] if chroma else 0
     flat = f.reshape(n, -1)
     for k in range(n):
-        at, src = offset + k * frame_stride, 0
+        src = 0
         for i, (r, b, p) in enumerate(sizes):
-            surf["plane"][k, i] = at
-            dst = np.lib.stride_tricks.as_strided(block[at:], shape=(r, b), strides=(p, 1))
+            dst = np.lib.stride_tricks.as_strided(block[int(surf["plane"][k, i]):], shape=(r, b), strides=(p, 1))
             dst[...] = flat[k, src:src + r * b].reshape(r, b)
-            at += r * p
             src += r * b
     return block, surf, (w, h), single
 
@@ -257,6 +269,26 @@ class DeviceFrames:
         nplanes = _plane_rows(size, pixel_format)[2]
         surf["plane"][:, :nplanes] += np.uint64(buf.ptr)
         return cls(surf, size, pixel_format, owner=buf, single=single, device=device)
+
+    @classmethod
+    def empty(cls, n, img_size, pixel_format="rgb", pitch=None, chroma_pitch=None, offset=0, fill=None, device=0):
+        """A sink: n surfaces of `img_size` in `pixel_format` in a fresh DeviceBuffer it owns, laid out as pack_host_frames lays
+        frames out (the block ends on the last byte of the last plane) -- what `Context.store_overlay_device`, `process_batch(...,
+        out=)` and `utils.rgb_to_yuv` write into and `to_host()` reads back.  `fill`: a byte value the whole block is set to first
+        (None: whatever the memory held)."""
+        n = int(n)
+        if n < 0:
+            raise ValueError("a sink holds zero or more frames, got %d" % n)
+        size = (int(img_size[0]), int(img_size[1]))
+        total, surf, _ = _layout_block(n, size, pixel_format, pitch, chroma_pitch, offset)
+        nplanes = _plane_rows(size, pixel_format)[2]
+        buf = None
+        if n:
+            buf = DeviceBuffer(total, device)
+            if fill is not None:
+                buf.copy_from_host(np.full(total, int(fill), np.uint8))
+            surf["plane"][:, :nplanes] += np.uint64(buf.ptr)
+        return cls(surf, size, pixel_format, owner=buf, device=device)
 
     # -- a sequence of frames
     def __len__(self):

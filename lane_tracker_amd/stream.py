@@ -593,7 +593,7 @@ class StreamPipeline:
             ctx.reserve(regions * size)
         mode = 0
         if annotate:
-            rows = self._present_rows() if self.host_copies_rows else None
+            rows = self._present_rows() if (self.host_copies_rows and not self._to_sink) else None
             mode = 2 if (rows is not None and rows[4] is not None) else 1
         if mode == 2 and output_pool and annotate != "inplace":   # the pool of output frames: a window being filled, one landing, one with the caller, one to spare
             _native.frames_prefault((int(window), ctx.img_h, ctx.img_w, 3), regions)
@@ -626,8 +626,32 @@ class StreamPipeline:
     _window_rows = None         # _present_rows() while an annotated window / stream sends its frames back as row runs
     strip_piece = 32            # frames per overlay launch + strip download of a committed run
     _annotate_inplace = False   # annotate="inplace": annotated frames are the caller's own arrays, drawn over (strips only)
+    _to_sink = False            # the annotated frames of the current call go into device sinks (`out=`): whole frames, drawn on the device
 
-    def _window_renderer(self, deferred, base, n, piece=32, frames=None):
+    def _sink_keywords(self, out, annotate, k):
+        """ValueError for the keywords a device sink (`out=`) does not combine with."""
+        if out is None:
+            return
+        if not annotate:
+            raise ValueError("out= receives the annotated frames: it needs annotate=True")
+        if isinstance(annotate, str) and annotate == "inplace":
+            raise ValueError("out= and annotate='inplace' are two destinations for the annotated frames: choose one")
+        if k["visualize_search"] or k["split_view"]:
+            raise ValueError("out= receives annotated frames only: visualize_search / split_view return pictures on the host")
+
+    def _check_sink(self, sink, n):
+        """`sink` as the destination of a window of n frames: a DeviceFrames of the tracker's image size, n surfaces, on its device."""
+        if not isinstance(sink, DeviceFrames):
+            raise ValueError("out= takes a DeviceFrames (DeviceFrames.empty(n, img_size, pixel_format)), got %r" % (type(sink).__name__,))
+        if sink.img_size != (int(self.img_size[0]), int(self.img_size[1])):
+            raise ValueError("out= holds frames of %dx%d, the tracker's are %dx%d" % (sink.img_size + (int(self.img_size[0]), int(self.img_size[1]))))
+        if len(sink) != n:
+            raise ValueError("out= holds %d surfaces for a window of %d frames" % (len(sink), n))
+        if sink.device != self.device:
+            raise ValueError("out= lies on device %d, the tracker on device %d" % (sink.device, self.device))
+        return sink
+
+    def _window_renderer(self, deferred, base, n, piece=32, frames=None, sink=None, matrix='bt601'):
         """(flush, out) for a window of n frames in slots base..: `flush(force)` renders the frames committed to `deferred`
         since the last call -- overlay kernels, then the copy towards `out`, all only enqueued -- once at least `piece` of them
         have gathered (or `force`); `out` is complete after `_copies_done(flush.group)` (strips) / the next sync and
@@ -638,7 +662,10 @@ class StreamPipeline:
         by the library's copy threads, which also draw the text lines (lt_host_text_async_group).  One completion group per window.
         Row runs (`_window_rows` without strips: `host_text = False`) and whole frames (`host_copies_rows = False`): round 4's ways, `out` page-locked.
         In place (`annotate="inplace"`, strips only): `out` IS `frames` -- the strips land in the caller's own window and the text is
-        drawn over it; no row is copied on the host (0.9 instead of 2.8 MB per 1280x720 frame through the copy threads)."""
+        drawn over it; no row is copied on the host (0.9 instead of 2.8 MB per 1280x720 frame through the copy threads).
+        Device sink (`sink`, a DeviceFrames; `_window_rows` is None then): whole frames, lane and text drawn on the device, and `out`
+        IS the sink -- every piece is written into its surfaces by a kernel (lt_overlay_store_device), in the sink's pixel format;
+        complete after `Context.store_wait()`.  No frame touches the host."""
         self._configure_overlay()
         ctx = self._ctx
         empty = np.zeros(0, np.int64)
@@ -706,7 +733,7 @@ class StreamPipeline:
                 done[0] = hi
             flush.group = group
             return flush, out
-        out = _native.pinned_empty((n, ctx.img_h, ctx.img_w, 3))
+        out = sink if sink is not None else _native.pinned_empty((n, ctx.img_h, ctx.img_w, 3))
         rows = wr[1] if wr is not None else None
         group = None
         if rows is not None:
@@ -734,21 +761,31 @@ class StreamPipeline:
             ctx.overlay_run_packed(*_pack_deferred(part), first=base + lo, rows=rows)
             if self._have_font:
                 ctx.overlay_text([d[2] for d in part], first=base + lo)
-            ctx.download_overlay_async(out[lo:hi], first=base + lo, rows=rows)
+            if sink is not None:
+                ctx.store_overlay_device(sink[lo:hi], first=base + lo, matrix=matrix)
+            else:
+                ctx.download_overlay_async(out[lo:hi], first=base + lo, rows=rows)
             done[0] = hi
         flush.group = group
         return flush, out
 
-    def _render_window(self, deferred, base):
-        """One overlay launch and one download for a whole window; a failed frame has no polygon (plain copy)."""
+    def _render_window(self, deferred, base, sink=None, matrix='bt601'):
+        """One overlay launch and one download -- or, with `sink`, one store into its surfaces -- for a whole window; a failed frame
+        has no polygon (plain copy)."""
         self._configure_overlay()
         ctx = self._ctx
+        if sink is not None and not deferred:
+            return []
         ctx.overlay_run_packed(*_pack_deferred(deferred), first=base)
         if self._have_font:
             ctx.overlay_text([d[2] for d in deferred], first=base)
+        if sink is not None:
+            ctx.store_overlay_device(sink, first=base, matrix=matrix)
+            ctx.store_wait()
+            return list(sink)
         return list(ctx.download_overlay(len(deferred), first=base))
 
-    def process_batch(self, frames, annotate=True, **kwargs):
+    def process_batch(self, frames, annotate=True, out=None, out_yuv_matrix='bt601', **kwargs):
         """The same result as calling `process()` on each frame of `frames` in order (one stateful
         stream), arranged for throughput:
 
@@ -771,34 +808,48 @@ class StreamPipeline:
         `visualize_search=True` / `split_view=True` return per frame what `process()` returns with them -- (annotated frame or
         None, picture), or the split view (needs `annotate=True`) -- painted by the device from what the frame's slot holds at its
         commit (`_VizWindow`, lt_search_viz_run / lt_split_panes_run).  For
-        consecutive windows of one video prefer `process_stream`, which keeps the device busy across window boundaries."""
+        consecutive windows of one video prefer `process_stream`, which keeps the device busy across window boundaries.
+        `out`: a device sink -- a `DeviceFrames` of the tracker's `img_size` with one surface per frame, in any pixel format
+        (`DeviceFrames.empty`, or an encoder's surfaces through `from_planes`).  The annotated frames are then drawn whole on the
+        device and written into its surfaces by a kernel (RGB at its pitch, or NV12 / I420 converted with `out_yuv_matrix`:
+        'bt601', 'bt709' or eight integers; `utils.rgb_to_yuv` is the same conversion), whatever `frames` are -- host arrays or
+        `DeviceFrames`, in the tracker's input format -- and no frame crosses the bus on the way out.  Returns `[out[i] for i in
+        range(n)]`, final when the call returns; state and attributes are those of the same call with `annotate=True`.  Needs
+        `annotate=True`, and neither `visualize_search` nor `split_view`."""
         if self._in_stream:
             raise RuntimeError("process_batch() inside an active process_stream() would overwrite its frames")
         k, first_try, fp = self._batch_arguments(kwargs)
         mode = self._viz_mode(k, annotate)
+        self._sink_keywords(out, annotate, k)
         self._annotate_inplace = isinstance(annotate, str) and annotate == "inplace"   # (a window _as_window had to copy: into the copy)
         frames = self._as_window(frames)
         n = frames.shape[0]
+        sink = self._check_sink(out, n) if out is not None else None
         ctx = self._ctx
         self._materialise_pending()      # growing the context below drops what is still on the device
         ctx.reserve(max(n, 1))
         deferred = []
         if self.chain_searches and not k["diagnostics"]:
-            self._window_rows = self._rows_for_window(frames) if annotate else None
+            self._window_rows = self._rows_for_window(frames) if (annotate and sink is None) else None
+            self._to_sink = sink is not None
             try:
-                flush, out = self._window_renderer(deferred, 0, n, frames=frames) if (annotate and n) else (None, None)
+                flush, out = self._window_renderer(deferred, 0, n, frames=frames, sink=sink, matrix=out_yuv_matrix) if (annotate and n) else (None, None)
                 viz = _VizWindow(self, n, mode == 'split') if mode else None
                 for _ in self._run_window_chained(frames, first_try, fp, k["n_tries"], annotate, deferred, flush=flush, viz=viz):
                     pass
                 self._materialise_pending()  # the attributes describe the last frame, as after process() (also waits for `out`)
                 if out is not None or viz is not None:
                     ctx.sync()
+                if sink is not None:
+                    ctx.store_wait()
+                    return list(sink)
                 if out is not None:
                     self._copies_done(flush.group)
                 return self._with_viz(list(out) if out is not None else [None] * n, viz)
             finally:
                 self._all_copies_done()
                 self._window_rows = None
+                self._to_sink = False
                 self._device_frames_done()
         else:
             if isinstance(frames, DeviceFrames):
@@ -814,7 +865,7 @@ class StreamPipeline:
                            annotate=annotate, visualize_search=mode == 'vis', split_view=mode == 'split', defer=deferred, viz=painted)
         self._materialise_pending()      # the attributes describe the last frame, as after process()
         try:
-            annotated = self._render_window(deferred, 0) if annotate else [None] * n
+            annotated = self._render_window(deferred, 0, sink, out_yuv_matrix) if annotate else [None] * n
             if mode == 'vis':
                 return [(a, p[0]) for a, p in zip(annotated, painted)]
             if mode == 'split':
@@ -852,20 +903,37 @@ class StreamPipeline:
             views.append(v)
         return views
 
-    def process_stream(self, windows, annotate=True, **kwargs):
+    def process_stream(self, windows, annotate=True, out=None, out_yuv_matrix='bt601', **kwargs):
         """Generator over consecutive windows of ONE video: `windows` yields arrays (n, H, W, 3); for each, what
         `process_batch` would return is yielded, and the tracker's state after it is what `process()` frame by frame
         leaves.  The context holds `stream_lookahead + 1` windows side by side: while the searches of one window drain, the
         uploads and masks of the next ones are already running, so neither the bus nor the device idles at window boundaries
         (a window's head and tail cost about a quarter of a 256-frame `process_batch` call).  Do not call `process()` / `process_batch()` on this
         tracker until the generator is exhausted or closed.  `annotate="inplace"`: see `process_batch` (every window must be a
-        C-contiguous, writeable uint8 array; a window that is not comes back as new frames)."""
+        C-contiguous, writeable uint8 array; a window that is not comes back as new frames).  `out`: device sinks, an iterable
+        that yields one `DeviceFrames` per window (see `process_batch`); a window is yielded, as the list of its sink's frames, once
+        its stores have landed (`Context.store_wait`), and its sink may be reused from then on."""
         k, first_try, fp = self._batch_arguments(kwargs)
         mode = self._viz_mode(k, annotate)
+        self._sink_keywords(out, annotate, k)
         self._annotate_inplace = isinstance(annotate, str) and annotate == "inplace"
+        sinks = iter(out) if out is not None else None
+
+        def sink_for(w):                     # the sink of the window just taken from `windows`
+            if sinks is None:
+                return None
+            try:
+                s = next(sinks)
+            except StopIteration:
+                raise ValueError("out= yielded fewer sinks than there are windows") from None
+            return self._check_sink(s, w.shape[0])
         if not (self.chain_searches and not k["diagnostics"]):
             for w in windows:            # the frame-by-frame route has nothing to overlap
-                yield self.process_batch(w, annotate=annotate, **kwargs)
+                if sinks is None:
+                    yield self.process_batch(w, annotate=annotate, **kwargs)
+                else:
+                    w = self._as_window(w)
+                    yield self.process_batch(w, annotate=annotate, out=sink_for(w), out_yuv_matrix=out_yuv_matrix, **kwargs)
             return
         it = iter(windows)
         cur = next(it, None)
@@ -875,6 +943,7 @@ class StreamPipeline:
             raise RuntimeError("this tracker already runs a process_stream()")
         cur = self._as_window(cur)
         device_fed = isinstance(cur, DeviceFrames)
+        cur_sink = sink_for(cur)
 
         def as_next_window(w):               # (how annotated frames travel is decided once per stream, by its first window)
             w = self._as_window(w)
@@ -889,14 +958,16 @@ class StreamPipeline:
         size = 0                         # slots per region
         free = []                        # first slots of the regions nobody lives in
         queue = []                       # windows ahead of `cur`, in order: [frames, first slot, frames fed]; [.., None, 0]: not placed
-        cur = [cur, None, 0]
+        cur = [cur, None, 0, cur_sink]   # (and the window's device sink, or None)
         landing = None                   # (page-locked frames, first slot) of the window before `cur`, annotated frames being copied back
 
         def landed():
             nonlocal landing
             arrays, region, group, viz = landing
             landing = None
-            if not (self._window_rows is not None and self._window_rows[4] is not None):
+            if isinstance(arrays, DeviceFrames):
+                ctx.store_wait()             # a device sink: its stores have landed
+            elif not (self._window_rows is not None and self._window_rows[4] is not None):
                 ctx.download_overlay_wait()  # these frames have landed; the uploads, masks and searches of the next windows run on
             self._copies_done(group)     # ... and so have the rows the host copies itself and -- strips -- the rows from the device (this window's group only)
             if viz is not None:
@@ -904,14 +975,16 @@ class StreamPipeline:
             free.append(region)
             return self._with_viz(list(arrays), viz)
         self._in_stream = True
-        self._window_rows = self._rows_for_window(cur[0]) if annotate else None
+        self._window_rows = self._rows_for_window(cur[0]) if (annotate and sinks is None) else None
+        self._to_sink = sinks is not None
         try:
             while cur is not None:
                 while len(queue) < look:             # know the next windows
                     w = next(it, None)
                     if w is None:
                         break
-                    queue.append([as_next_window(w), None, 0])
+                    w = as_next_window(w)
+                    queue.append([w, None, 0, sink_for(w)])
                 n = cur[0].shape[0]
                 if cur[1] is None:                   # first window, or one that did not fit the regions: (re)size the context
                     if landing is not None:
@@ -933,7 +1006,8 @@ class StreamPipeline:
                         q[1] = free.pop(0)
                     ahead.append(q)
                 deferred = []
-                flush, frames_out = self._window_renderer(deferred, cur[1], n, frames=cur[0]) if (annotate and n) else (None, None)
+                flush, frames_out = (self._window_renderer(deferred, cur[1], n, frames=cur[0], sink=cur[3], matrix=out_yuv_matrix)
+                                     if (annotate and n) else (None, None))
                 viz = _VizWindow(self, n, mode == 'split') if mode else None
                 if n:
                     for _ in self._run_window_chained(cur[0], first_try, fp, k["n_tries"], annotate, deferred, base=cur[1],
@@ -950,13 +1024,14 @@ class StreamPipeline:
                         ctx.search_viz_wait()    # (enqueued behind the searches; the region's next window is ordered behind the reads)
                     free.append(cur[1])  # its frames, masks and records are not needed any more
                     cur = queue.pop(0) if queue else None
-                    yield self._with_viz([None] * n, viz)
+                    yield self._with_viz([None] * n if sinks is None else [], viz)
             if landing is not None:
                 yield landed()
             self._materialise_pending()  # the attributes describe the last frame, as after process()
         finally:
             self._in_stream = False
             self._window_rows = None
+            self._to_sink = False
             try:
                 self._device_frames_done()   # (waits for the device: the attached windows may go)
             except Exception:

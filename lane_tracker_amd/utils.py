@@ -94,3 +94,29 @@ def yuv_to_rgb(frame, layout='nv12', matrix='bt601'):
     (20-bit fixed point) for another matrix.  What a `LaneTracker(..., pixel_format=layout, yuv_matrix=matrix)` sees of the frame."""
     from .lane_tracker import _context_for_module_functions
     return _context_for_module_functions().yuv_to_rgb(frame, layout, matrix)
+
+
+def rgb_to_yuv(frame, layout='nv12', matrix='bt601'):
+    """The counterpart of `yuv_to_rgb`: an RGB frame (H, W, 3), H and W even, to YUV 4:2:0 as OpenCV holds it -- a u8 array
+    (H * 3 // 2, W): the Y plane, then interleaved U,V rows ('nv12') or the U plane and the V plane ('i420') -- on the device,
+    with OpenCV's integer arithmetic (`cv2.cvtColor(frame, cv2.COLOR_RGB2YUV_I420)`: chroma of the top-left pixel of each 2 x 2
+    block, 20-bit fixed point; matrix='bt601': OpenCV's constants, video range; 'bt709' or eight integers {CRY, CGY, CBY, CRU, CGU,
+    CBU, CGV, CBV} for another matrix).  What a device sink in that layout receives of an annotated frame."""
+    from . import _native
+    from .device import DeviceBuffer, DeviceFrames
+    a = np.ascontiguousarray(frame, np.uint8)
+    if _native.pixel_format_id(layout) == 0:
+        raise ValueError("layout must be 'nv12' or 'i420'")
+    if a.ndim != 3 or a.shape[2] != 3 or a.shape[0] % 2 or a.shape[1] % 2 or 0 in a.shape:
+        raise ValueError("an RGB frame is an array (H, W, 3) with H and W even, got %r" % (a.shape,))
+    size = (a.shape[1], a.shape[0])
+    k = _native.rgb2yuv_coeffs(matrix)
+    with DeviceBuffer(a.nbytes) as src:
+        src.copy_from_host(a)
+        sink = DeviceFrames.empty(1, size, layout)
+        try:
+            _native.rgb_to_surfaces(src.ptr, a.nbytes, size, sink, k)
+            return sink.to_host()[0]
+        finally:
+            sink.owner.close()
+

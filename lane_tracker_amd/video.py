@@ -10,7 +10,9 @@ frames out.  Supported on both sides:
   * a headerless raw RGB24 file (`.rgb` / `.raw`; what `ffmpeg -pix_fmt rgb24 -f rawvideo` writes and reads),
   * on the input side, a headerless raw YUV 4:2:0 file as cameras and decoders produce it: `.nv12`, or `.i420` / `.yuv` (I420;
     `ffmpeg -pix_fmt nv12 | yuv420p -f rawvideo`).  Its frames are (H * 3 // 2, W) arrays for a tracker built with the same
-    `pixel_format`, which converts them on the device; what comes out, and every sink, is RGB.
+    `pixel_format`, which converts them on the device; what comes out, and every sink, is RGB -- unless
+  * `--out-format nv12 | i420` (or `rgb`) asks for the annotated frames through a device sink (`process_stream(..., out=)`): they
+    are converted on the device and written as a raw `.nv12` / `.i420` (`.rgb`) file, which this module also reads.
 
 `process_frames()` feeds the tracker in windows through `LaneTracker.process_stream` (the stream pipeline:
 masks of the whole window batched ahead on the GPU, state machine trailing), which gives exactly the
@@ -159,15 +161,22 @@ class FrameSource:
 
 
 class FrameSink:
-    """Where processed frames go.  Directories get `frame_000000.png`, ...; `.npy` needs `n` up front."""
+    """Where processed frames go.  Directories get `frame_000000.png`, ...; `.npy` needs `n` up front.  `pixel_format` 'nv12' /
+    'i420': frames of shape (H * 3 // 2, W) into a raw 4:2:0 file (`.nv12`, `.i420` / `.yuv`)."""
 
-    def __init__(self, path, size, n=None):
+    def __init__(self, path, size, n=None, pixel_format="rgb"):
         self.path = str(path)
         self.width, self.height = int(size[0]), int(size[1])
         self.count = 0
         self._raw = None
         self._array = None
-        if self.path.lower().endswith(".npy"):
+        self._tail = (self.height, self.width, 3)
+        if pixel_format != "rgb":
+            if _yuv_layout(self.path) != pixel_format:
+                raise ValueError("%s frames go into a raw file named *.%s, got %s" % (pixel_format, pixel_format, self.path))
+            self._tail = (self.height * 3 // 2, self.width)
+            self._raw = open(self.path, "wb")
+        elif self.path.lower().endswith(".npy"):
             if n is None:
                 raise ValueError(".npy output needs the number of frames")
             self._array = np.lib.format.open_memmap(self.path, "w+", np.uint8, (int(n), self.height, self.width, 3))
@@ -178,10 +187,10 @@ class FrameSink:
 
     def write(self, frames):
         frames = np.asarray(frames, np.uint8)
-        if frames.ndim == 3:
+        if frames.ndim == len(self._tail):
             frames = frames[None]
-        if frames.shape[1:] != (self.height, self.width, 3):
-            raise ValueError(f"sink takes {self.width}x{self.height} RGB frames, got {frames.shape[1:]}")
+        if frames.shape[1:] != self._tail:
+            raise ValueError(f"sink takes frames of shape {self._tail}, got {frames.shape[1:]}")
         if self._array is not None:
             self._array[self.count:self.count + len(frames)] = frames
         elif self._raw is not None:
@@ -207,11 +216,13 @@ class FrameSink:
         self.close()
 
 
-def process_frames(tracker, source, sink=None, window=64, viz_sink=None, **process_kwargs):
+def process_frames(tracker, source, sink=None, window=64, viz_sink=None, out_format=None, out_yuv_matrix="bt601", **process_kwargs):
     """Run every frame of `source` through the tracker, in order, `window` frames per GPU batch; write the
     annotated frames to `sink` if there is one -- the split views with `split_view=True` among the keywords, for a sink of
     that size -- and the search visualisations (bird's-eye size; `visualize_search=True` is set) to `viz_sink` if there
-    is one.  Returns (frames, seconds)."""
+    is one.  `out_format` ('rgb', 'nv12', 'i420'): the annotated frames leave through device sinks in that pixel format
+    (`process_stream(..., out=)`; 4:2:0 converted on the device with `out_yuv_matrix`) and `sink` receives what the sinks hold.
+    Returns (frames, seconds)."""
     t0 = time.perf_counter()
     n = len(source)
     want, have = getattr(source, "pixel_format", "rgb"), getattr(tracker, "pixel_format", "rgb")
@@ -221,6 +232,17 @@ def process_frames(tracker, source, sink=None, window=64, viz_sink=None, **proce
     # process_stream: the uploads and masks of window k+1 run while the searches of window k drain
     if viz_sink is not None:
         process_kwargs = dict(process_kwargs, visualize_search=True)
+    if out_format is not None:
+        if sink is None or viz_sink is not None:
+            raise ValueError("out_format writes the annotated frames: it needs a sink, and no visualisation sink")
+        from .device import DeviceFrames
+        sinks = (DeviceFrames.empty(min(window, n - start), source.size, out_format, device=tracker.device) for start in range(0, n, window))
+        for out in tracker.process_stream(windows, annotate=True, out=sinks, out_yuv_matrix=out_yuv_matrix, **process_kwargs):
+            for f in out:                # one-frame DeviceFrames of the window's sink
+                sink.write(f.to_host())
+            if out:
+                out[0].owner.close()
+        return n, time.perf_counter() - t0
     for out in tracker.process_stream(windows, annotate=sink is not None, **process_kwargs):
         if process_kwargs.get("visualize_search"):        # (annotated frame or None, picture) per frame
             pictures = [p if p.ndim == 3 else np.repeat(p[:, :, None], 3, axis=2) for _, p in out]
@@ -283,6 +305,10 @@ def main(argv=None):
     ap.add_argument("--pixel-format", choices=("rgb", "nv12", "i420"), default=None,
                     help="pixel format of the input frames (default: by the input's name); must match a raw input's extension")
     ap.add_argument("--yuv-matrix", choices=("bt601", "bt709"), default="bt601", help="conversion matrix of 4:2:0 input")
+    ap.add_argument("--out-format", choices=("rgb", "nv12", "i420"), default=None,
+                    help="write the annotated frames through a device sink in this pixel format: a raw .rgb / .nv12 / .i420 file for "
+                         "4:2:0 (converted on the device, --out-yuv-matrix); default: RGB frames brought back by the host")
+    ap.add_argument("--out-yuv-matrix", choices=("bt601", "bt709"), default="bt601", help="conversion matrix of 4:2:0 output")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--frame-count", action="store_true", help="print the frame number onto each image")
     ap.add_argument("--settings", choices=("default", "demo1", "demo2", "demo3"), default="default",
@@ -296,6 +322,10 @@ def main(argv=None):
         ap.error("--split-view shows the annotated frames: it needs an output")
     if a.split_view and a.visualize_search:
         ap.error("--split-view and --visualize-search are two runs: process() returns one or the other")
+    if a.out_format is not None and (a.split_view or a.visualize_search or a.output == "-"):
+        ap.error("--out-format writes the annotated frames through a device sink: it needs an output, and neither --split-view nor --visualize-search")
+    if a.out_format in ("nv12", "i420") and _yuv_layout(a.output) != a.out_format:
+        ap.error("--out-format %s needs an output file named *.%s" % (a.out_format, a.out_format))
     from . import _native
     from .lane_tracker import LaneTracker
     from .utils import load_camera_calib, load_warp_params
@@ -311,7 +341,7 @@ def main(argv=None):
         out_size = src.size
         if a.split_view:                 # the annotated frame on top, the pane strip below it
             out_size = (src.size[0], src.size[1] + _native.split_panes_size(src.size, warped_wh)[1])
-        sink = None if a.output == "-" else FrameSink(a.output, out_size, n=len(src))
+        sink = None if a.output == "-" else FrameSink(a.output, out_size, n=len(src), pixel_format=a.out_format or "rgb")
         viz_sink = FrameSink(a.visualize_search, warped_wh, n=len(src)) if a.visualize_search else None
         kw = {}
         if a.settings != "default":
@@ -319,7 +349,7 @@ def main(argv=None):
             kw = settings.apply(lt, settings.DEMOS[a.settings])
         if a.split_view:
             kw["split_view"] = True
-        n, dt = process_frames(lt, src, sink, window=a.window, viz_sink=viz_sink, **kw)
+        n, dt = process_frames(lt, src, sink, window=a.window, viz_sink=viz_sink, out_format=a.out_format, out_yuv_matrix=a.out_yuv_matrix, **kw)
         for s_ in (sink, viz_sink):
             if s_ is not None:
                 s_.close()
