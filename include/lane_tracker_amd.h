@@ -55,7 +55,9 @@ extern "C" {
  *    _write / _read (device blocks for callers without a HIP binding of their own), lt_device_stream_wait; lt_viz_item +
  *    lt_search_viz_run + lt_split_panes_run + lt_split_panes_size + lt_search_viz_wait (the search visualisations and split-view
  *    panes of listed frames, painted on the device), lt_calib_split_panes_size, lt_resize_linear_u8; lt_rgb_to_surfaces + lt_overlay_store_device +
- *    lt_overlay_store_wait (annotated frames written into the caller's device surfaces, RGB, NV12 or I420).  Nothing removed or changed. */
+ *    lt_overlay_store_wait (annotated frames written into the caller's device surfaces, RGB, NV12 or I420); lt_add_calibration +
+ *    lt_calibration_count + lt_set_slot_calibrations + lt_get_slot_calibrations + lt_overlay_configure_set (several calibrations in
+ *    one context, one per slot: the cameras of a LaneTrackerGroup).  Nothing removed or changed. */
 #define LT_ABI_VERSION 5
 
 typedef enum lt_status {
@@ -271,6 +273,39 @@ typedef struct lt_device_surface {
 } lt_device_surface;
 int  lt_attach_device_frames(lt_ctx* ctx, const lt_device_surface* surfaces, int first_slot, int n);
 int  lt_device_frames_rest(lt_ctx* ctx, int first_slot, int n, const int32_t* rows4);
+/* ---- calibration sets: one context, cameras of different calibrations ------------------------------------------------------------
+ * A context holds one or more calibration SETS -- the remap tables of one camera: its intrinsics, its distortion, its bird's-eye
+ * homography -- and every slot has one of them.  Set 0 is the calibration lt_create was given, and every slot starts with it: a
+ * context that never adds a set is what it always was, launch for launch.
+ *
+ * lt_add_calibration: a further set from `calib`; *id is its number (1, 2, ...; at most 256 sets).  img_w, img_h, warp_w and warp_h
+ * must equal the context's (LT_ERR_INVALID).  Like lt_set_input_format it belongs in front of the context's first upload or
+ * attach: LT_ERR_STATE afterwards.  The GEOMETRY stays one per context: the rows of the undistorted image the front end fills, the
+ * camera rows the uploads bring (lt_get_source_rows) and the rows a lane can reach (lt_overlay_rows) become the UNIONS over the
+ * sets of what each set needs, and every set's undistortion table is built for that union.  Rows a set's own warp never
+ * references are computed and never read: a slot's planes, mask and record are bit for bit those of a context created with its
+ * set alone.  (lt_get_info's src_row0 / src_row1 and lt_download_undistorted follow the union.)
+ * lt_calibration_count: the sets the context holds, set 0 included.
+ * lt_set_slot_calibrations: slot first_slot + i gets set ids[i] (LT_ERR_INVALID for an id the context does not hold).  Cheap -- a
+ * host table; the launches carry the ids by value, so nothing has to be ordered on the device and an assignment may change every
+ * tick.  A slot whose set changes has a stale front end: lt_mask_rerun over it runs the front end again.  lt_reserve, when it
+ * grows the context, puts every slot back to set 0.  lt_get_slot_calibrations reads the assignment back.
+ * lt_overlay_configure_set: lt_overlay_configure for one set (lt_overlay_configure is set 0's).
+ *
+ * lt_mask_run / lt_mask_rerun over slots of ONE set -- whichever -- launch the kernels they always launched, with that set's tables;
+ * a stream slice that MIXES sets takes table-per-slot forms of the undistortion and of the warp (one launch each, whatever the
+ * number of sets; frames in slots or attached, RGB / NV12 / I420).  lt_overlay_run / lt_overlay_run_rows draw every slot through
+ * the inverse-warp table of its own set (LT_ERR_STATE if that set's overlay is not configured), run by run over consecutive
+ * slots of one set; lt_overlay_text and the downloads do not depend on the set; lt_download_bev warps every slot with its own.
+ * Everything else that reads calibration tables knows set 0 only and REFUSES a slot that has another set with LT_ERR_STATE,
+ * nothing launched and the context as it was: lt_present_frame, lt_present_lane_async, lt_present_lane_from_fit_async,
+ * lt_present_finish, lt_overlay_run_strip, lt_overlay_run_strip_coeffs, lt_search_viz_run, lt_split_panes_run -- and
+ * lt_lane_spans_from_fit, which names no slot, while ANY slot of the context has another set. */
+int  lt_add_calibration(lt_ctx* ctx, const lt_calib* calib, int* id);
+int  lt_calibration_count(lt_ctx* ctx, int* count);
+int  lt_set_slot_calibrations(lt_ctx* ctx, int first_slot, int n, const int32_t* ids);
+int  lt_get_slot_calibrations(lt_ctx* ctx, int first_slot, int n, int32_t* ids);
+int  lt_overlay_configure_set(lt_ctx* ctx, int set, const double* Minv /* 9 */);
 /* Device blocks out of the library's own cache (lt_device_cache_stats counts them as live), with plain synchronous copies
  * from and to host memory: for callers that have no HIP binding of their own -- the Python package, tools, tests -- and want to
  * hold frames on the device in the runtime the library lives in.  lt_device_write / lt_device_read refuse ranges that do not lie
@@ -410,7 +445,8 @@ int  lt_fit_poly2(lt_ctx* ctx, const int32_t* ys, const int32_t* xs, int n, int 
  * (lane_tracker.py:648); builds the camera-sized remap table once.  Call it BEFORE uploading frames whose annotated form will be
  * asked for: when the rows the lane can reach (lt_overlay_rows) stick out of the rows lt_upload_frame_rows brings by a few rows
  * (458-696 against 457-695 of 720 with the reference calibration), that run is widened to cover them (lt_get_source_rows reports
- * the new run), so that an annotated frame's lane rows need no upload of their own; a frame uploaded before lacks those rows. */
+ * the new run), so that an annotated frame's lane rows need no upload of their own; a frame uploaded before lacks those rows.
+ * The run only ever widens: another lt_overlay_configure, or a further calibration set, never takes rows away. */
 int  lt_overlay_configure(lt_ctx* ctx, const double* Minv /* 9 */);
 /* draw_lane() without the text (lane_tracker.py:637-662) for the frames in slots [first, first+n):
  * fillPoly of the polygon left points + reversed right points in (0,255,0), warpPerspective with Minv,

@@ -238,6 +238,11 @@ _SIGNATURES = {
     "lt_rgb_to_surfaces": (C.c_int, [C.c_int, _P, C.c_size_t, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),
     "lt_overlay_store_device": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P]),
     "lt_overlay_store_wait": (C.c_int, [_P]),
+    "lt_add_calibration": (C.c_int, [_P, C.POINTER(Calib), C.POINTER(C.c_int)]),
+    "lt_calibration_count": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "lt_set_slot_calibrations": (C.c_int, [_P, C.c_int, C.c_int, _P]),
+    "lt_get_slot_calibrations": (C.c_int, [_P, C.c_int, C.c_int, _P]),
+    "lt_overlay_configure_set": (C.c_int, [_P, C.c_int, _P]),
 }
 
 # camera-frame formats (lt_input_layout) and the conversion matrices {CY, CVR, CVG, CUG, CUB} of include/lane_tracker_amd.h
@@ -764,6 +769,32 @@ class Context:
         _check(self.lib.lt_yuv_to_rgb(self._h, a.ctypes.data, h, w, pixel_format_id(layout), k.ctypes.data, out.ctypes.data))
         return out
 
+    # -- calibration sets: cameras of different calibrations in one context, one per slot
+    def add_calibration(self, cam_matrix, dist_coeffs, M):
+        """A further calibration set of the context's image and bird's-eye sizes, before the first upload (lt_add_calibration);
+        returns its id.  Set 0 is the calibration the context was created with."""
+        cal = make_calib((self.img_w, self.img_h), (self.warp_w, self.warp_h), cam_matrix, dist_coeffs, M)
+        i = C.c_int(0)
+        _check(self.lib.lt_add_calibration(self._h, C.byref(cal), C.byref(i)))
+        return i.value
+
+    def calibration_count(self):
+        n = C.c_int(0)
+        _check(self.lib.lt_calibration_count(self._h, C.byref(n)))
+        return n.value
+
+    def set_slot_calibrations(self, ids, first=0):
+        """Slot first + i takes calibration set ids[i] (lt_set_slot_calibrations)."""
+        a = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        _check(self.lib.lt_set_slot_calibrations(self._h, int(first), a.shape[0], a.ctypes.data if a.shape[0] else None))
+
+    def slot_calibrations(self, n=None, first=0):
+        """The calibration sets of slots first, first + 1, ... (n of them; None: up to the capacity)."""
+        n = self.capacity - first if n is None else int(n)
+        a = np.zeros(max(n, 0), np.int32)
+        _check(self.lib.lt_get_slot_calibrations(self._h, int(first), n, a.ctypes.data if n > 0 else None))
+        return a
+
     def source_rows(self):
         """Camera rows [row0, row1) the path reads."""
         a, b = C.c_int(0), C.c_int(0)
@@ -886,9 +917,12 @@ class Context:
         return out
 
     # ---- presentation stage (draw_lane overlay, bird's-eye image) ----
-    def overlay_configure(self, Minv):
+    def overlay_configure(self, Minv, calibration=0):
         m = np.ascontiguousarray(Minv, np.float64).reshape(9)
-        _check(self.lib.lt_overlay_configure(self._h, m.ctypes.data))
+        if calibration:
+            _check(self.lib.lt_overlay_configure_set(self._h, int(calibration), m.ctypes.data))
+        else:
+            _check(self.lib.lt_overlay_configure(self._h, m.ctypes.data))
 
     def overlay_run(self, polygons, first=0, alpha=0.3, rows=None):
         """polygons: one (left_y, left_x, right_y, right_x) tuple per slot (empty arrays: plain copy); rows: None or the

@@ -4,6 +4,8 @@
 //   k_undistort_rows_yuv  the same over a 4:2:0 frame (NV12 / I420): cv2.cvtColor(YUV2RGB_*) of every tap, then the blend
 //   k_undistort_rows_surf, k_undistort_rows_yuv_surf  the same two over frames in the caller's device memory (surface table)
 //                      -- all of them entry points of one walk, undistort_walk<source, pixel format>
+//   k_undistort_cal*, k_warp_cal  the table-per-slot forms of the walk's seven entry points and of the warp: every slot of a launch with
+//                      the remap tables of its own calibration set (lt_add_calibration), for slices that mix sets
 //   k_yuv_rows_to_rgb, k_surf_rows_to_rgb  cv2.cvtColor(YUV2RGB_NV12 / _I420) of a run of rows (for whoever shows the camera
 //                      frame), from a slot's staging frame / from a surface: one 16-column and one byte-wise body
 //   k_warp_split       cv2.warpPerspective      lane_tracker.py:834
@@ -254,8 +256,19 @@ struct WalkArgs {
     int first_slot, n, fpb, remap;
 };
 
-template <class Source, class Format>
-__device__ __forceinline__ void undistort_walk(const WalkArgs& a, Source src, Format fmt) {
+// Whose remap table a walk reads: the launch's one table (a.uxy, a.ufrac), or -- the table-per-slot form, one frame per walk --
+// that of the calibration set of the walk's slot.  The slot is wave-uniform, so its set's id (a byte of the kernel argument) and the
+// set's entry of the set table (device memory) arrive by scalar loads, as a surface's entry does.
+struct OneTable { static constexpr bool PER_SLOT = false; };
+struct SlotTables {
+    static constexpr bool PER_SLOT = true;
+    const CalTables* sets;
+    const CalIds* ids;
+    __device__ __forceinline__ const CalTables& of(int z) const { return sets[(ids->w[z >> 2] >> (8 * (z & 3))) & 255u]; }
+};
+
+template <class Source, class Format, class Tables = OneTable>
+__device__ __forceinline__ void undistort_walk(const WalkArgs& a, Source src, Format fmt, Tables tabs = Tables{}) {
     const FrontEndGeom& g = a.g;
     const uint32_t per_z = gridDim.x * gridDim.y;
     const uint32_t id = xcd_block((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x, per_z * gridDim.z, a.remap);
@@ -267,8 +280,15 @@ __device__ __forceinline__ void undistort_walk(const WalkArgs& a, Source src, Fo
     if (x >= g.img_w) return;
     const int z0 = bz * a.fpb, z1 = min(z0 + a.fpb, a.n);   // fpb frames per thread: table entry and offsets are frame-independent
     const size_t o = (size_t)row * g.img_w + x;
-    const int sx = a.uxy[o * 2], sy = a.uxy[o * 2 + 1];
-    const int f = a.ufrac[o], fx = f & 31, fy = f >> 5;
+    const int16_t* uxy = a.uxy;
+    const uint16_t* ufrac = a.ufrac;
+    if constexpr (Tables::PER_SLOT) {        // (fpb == 1: the walk is slot first_slot + z0's)
+        const CalTables& t = tabs.of(z0);
+        uxy = t.uxy;
+        ufrac = t.ufrac;
+    }
+    const int sx = uxy[o * 2], sy = uxy[o * 2 + 1];
+    const int f = ufrac[o], fx = f & 31, fy = f >> 5;
     const bool y0 = sy >= 0 && sy < g.img_h, y1 = sy + 1 >= 0 && sy + 1 < g.img_h;
     const bool x0 = sx >= 0 && sx < g.img_w, x1 = sx + 1 >= 0 && sx + 1 < g.img_w;
     const int cy0 = min(max(sy, 0), g.img_h - 1), cy1 = min(max(sy + 1, 0), g.img_h - 1);
@@ -350,6 +370,39 @@ __global__ __launch_bounds__(256) void k_undistort_rows_yuv_surf(const SurfEntry
                                                                 int remap) {
     undistort_walk(WalkArgs{uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap},
                    SurfSource{tab}, Yuv420<LAYOUT>{k});
+}
+
+// ... and the table-per-slot forms of the same seven (a context whose slots hold cameras of different calibrations: a slice that
+// mixes sets).  One frame per walk; `ids`: the sets of slots first_slot, first_slot + 1, ...
+template <bool ALIGNED4>
+__global__ __launch_bounds__(256) void k_undistort_cal(const uint8_t* __restrict__ frames, size_t frame_stride,
+                                                      const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
+                                                      uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int remap) {
+    undistort_walk(WalkArgs{nullptr, nullptr, g, und, und_px, first_slot, n, 1, remap},
+                   SlotSource<ALIGNED4>{frames, frame_stride}, Rgb24{}, SlotTables{sets, &ids});
+}
+
+template <int LAYOUT>
+__global__ __launch_bounds__(256) void k_undistort_cal_yuv(const uint8_t* __restrict__ yuv, size_t yuv_stride, YuvCoef k,
+                                                          const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
+                                                          uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int remap) {
+    undistort_walk(WalkArgs{nullptr, nullptr, g, und, und_px, first_slot, n, 1, remap},
+                   SlotSource<true>{yuv, yuv_stride}, Yuv420<LAYOUT>{k}, SlotTables{sets, &ids});
+}
+
+__global__ __launch_bounds__(256) void k_undistort_cal_surf(const SurfEntry* __restrict__ tab,
+                                                           const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
+                                                           uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int remap) {
+    undistort_walk(WalkArgs{nullptr, nullptr, g, und, und_px, first_slot, n, 1, remap},
+                   SurfSource{tab}, Rgb24{}, SlotTables{sets, &ids});
+}
+
+template <int LAYOUT>
+__global__ __launch_bounds__(256) void k_undistort_cal_yuv_surf(const SurfEntry* __restrict__ tab, YuvCoef k,
+                                                               const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
+                                                               uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int remap) {
+    undistort_walk(WalkArgs{nullptr, nullptr, g, und, und_px, first_slot, n, 1, remap},
+                   SurfSource{tab}, Yuv420<LAYOUT>{k}, SlotTables{sets, &ids});
 }
 
 // ---- 4:2:0 rows -> RGB rows ---------------------------------------------------------------------------------------------------
@@ -792,6 +845,60 @@ __global__ __launch_bounds__(256) void k_warp_split1(const uint32_t* __restrict_
     planeB[(size_t)blockIdx.z * plane_stride + o] = (uint8_t)b;
 }
 
+// The table-per-slot form of the warp: PX adjacent bird's-eye pixels of ONE slot per thread (4 where the width is a multiple of 4:
+// one dword store per plane; else 1), the table entry from the slot's calibration set (SlotTables: scalar loads, the slot is
+// blockIdx.z).  Slots 2p and 2p + 1 may belong to different sets, so nothing here is shared between the partners of a pair: every
+// tap is the slot's own dword of the pair-interleaved rows (warp_pixel over und_slot_base), blended and split by warp_pixel with
+// the staged Lab tables, as k_warp_split1 and the border path of k_warp_split4 do.
+template <int PX>
+__global__ __launch_bounds__(256) void k_warp_cal(const uint32_t* __restrict__ und, size_t und_px, int first_slot,
+                                                 const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
+                                                 const uint16_t* __restrict__ gamma_tab, const uint16_t* __restrict__ cbrt_tab,
+                                                 const int32_t* __restrict__ coeffs, uint8_t* __restrict__ planeR,
+                                                 uint8_t* __restrict__ planeB, size_t plane_stride) {
+    __shared__ alignas(16) uint16_t s_gamma[256];
+    __shared__ alignas(16) uint16_t s_cbrt[3072];
+    __shared__ int32_t s_coef[9];
+    const int z = (int)blockIdx.z;
+    const CalTables& t = SlotTables{sets, &ids}.of(z);
+    const int16_t* wxy = t.wxy;
+    const uint16_t* wfrac = t.wfrac;
+    const size_t units = ((size_t)g.warp_h * g.warp_w) / PX;
+    const size_t u = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t uc = u < units ? u : units - 1;
+    uint32_t xyv[PX], frv[PX];
+    // the table entry is requested before the Lab tables are staged: both latencies overlap
+    if constexpr (PX == 4) {
+        const uint4 xy = reinterpret_cast<const uint4*>(wxy)[uc];        // 4 x (sx, sy) int16 pairs
+        const uint2 fr = reinterpret_cast<const uint2*>(wfrac)[uc];      // 4 x u16
+        xyv[0] = xy.x, xyv[1] = xy.y, xyv[2] = xy.z, xyv[3] = xy.w;
+        frv[0] = fr.x & 0xffffu, frv[1] = fr.x >> 16, frv[2] = fr.y & 0xffffu, frv[3] = fr.y >> 16;
+    } else {
+        xyv[0] = reinterpret_cast<const uint32_t*>(wxy)[uc];
+        frv[0] = wfrac[uc];
+    }
+    stage_lab_tables(s_gamma, s_cbrt, s_coef, gamma_tab, cbrt_tab, coeffs);
+    if (u >= units) return;
+    const uint32_t* src = und + und_slot_base(und_px, first_slot + z);
+    uint32_t oR = 0, oB = 0;
+#pragma unroll
+    for (int i = 0; i < PX; ++i) {
+        const int sx = (int16_t)(xyv[i] & 0xffffu), sy = (int16_t)(xyv[i] >> 16);
+        int r, b;
+        warp_pixel(src, g, sx, sy, (int)frv[i], s_gamma, s_cbrt, s_coef, r, b);
+        asm volatile("" : "+v"(r), "+v"(b));     // (the byte inserts stay byte inserts: the note in k_warp_split4)
+        oR |= ((uint32_t)r & 255u) << (8 * i);
+        oB |= ((uint32_t)b & 255u) << (8 * i);
+    }
+    if constexpr (PX == 4) {
+        reinterpret_cast<uint32_t*>(planeR + (size_t)z * plane_stride)[u] = oR;
+        reinterpret_cast<uint32_t*>(planeB + (size_t)z * plane_stride)[u] = oB;
+    } else {
+        planeR[(size_t)z * plane_stride + u] = (uint8_t)oR;
+        planeB[(size_t)z * plane_stride + u] = (uint8_t)oB;
+    }
+}
+
 // filter_lane_points() entry on an already-warped RGB image (lane_tracker.py:207-208)
 __global__ __launch_bounds__(256) void k_split_bev(const uint8_t* __restrict__ bev, size_t bev_stride, int npix,
                                                   const uint16_t* __restrict__ gamma_tab,
@@ -934,6 +1041,57 @@ void launch_warp_split(hipStream_t s, const uint32_t* und, size_t und_px, int fi
         dim3 grid((unsigned)((npix + 255) / 256), 1, n);
         hipLaunchKernelGGL(k_warp_split1, grid, dim3(256), 0, s, und, und_px, first_slot, wxy, wfrac, g, gamma_tab, cbrt_tab,
                            coeffs, planeR, planeB, plane_stride);
+    }
+}
+
+static CalIds pack_ids(const uint8_t* ids, int m) {
+    CalIds c{};
+    for (int i = 0; i < m; ++i) c.w[i >> 2] |= (uint32_t)ids[i] << (8 * (i & 3));
+    return c;
+}
+
+void launch_undistort_cal(hipStream_t s, FrameSource src, int layout, YuvCoef k, const CalTables* sets, const uint8_t* ids,
+                          FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n) {
+    if (n <= 0 || g.nrows <= 0) return;
+    const int remap = xcd_remap();
+    for (int i = 0; i < n; i += CalIds::N) {
+        const int m = std::min(n - i, (int)CalIds::N), fs = first_slot + i;
+        const CalIds ci = pack_ids(ids + i, m);
+        const dim3 grid((g.img_w + 255) / 256, g.nrows, m), block(256);
+        const uint8_t* frames = src.tab ? nullptr : src.frames + (size_t)i * src.stride;
+        if (src.tab) {
+            if (layout == 0) hipLaunchKernelGGL(k_undistort_cal_surf, grid, block, 0, s, src.tab, sets, ci, g, und, und_px, fs, m, remap);
+            else if (layout == 1) hipLaunchKernelGGL(k_undistort_cal_yuv_surf<1>, grid, block, 0, s, src.tab, k, sets, ci, g, und, und_px, fs, m, remap);
+            else hipLaunchKernelGGL(k_undistort_cal_yuv_surf<2>, grid, block, 0, s, src.tab, k, sets, ci, g, und, und_px, fs, m, remap);
+        } else if (layout == 0) {
+            if (((uintptr_t)frames & 3) == 0 && (src.stride & 3) == 0 && src.stride < (1u << 30))
+                hipLaunchKernelGGL(k_undistort_cal<true>, grid, block, 0, s, frames, src.stride, sets, ci, g, und, und_px, fs, m, remap);
+            else
+                hipLaunchKernelGGL(k_undistort_cal<false>, grid, block, 0, s, frames, src.stride, sets, ci, g, und, und_px, fs, m, remap);
+        } else if (layout == 1) {
+            hipLaunchKernelGGL(k_undistort_cal_yuv<1>, grid, block, 0, s, frames, src.stride, k, sets, ci, g, und, und_px, fs, m, remap);
+        } else {
+            hipLaunchKernelGGL(k_undistort_cal_yuv<2>, grid, block, 0, s, frames, src.stride, k, sets, ci, g, und, und_px, fs, m, remap);
+        }
+    }
+}
+
+void launch_warp_cal(hipStream_t s, const uint32_t* und, size_t und_px, int first_slot, const CalTables* sets, const uint8_t* ids,
+                     FrontEndGeom g, const uint16_t* gamma_tab, const uint16_t* cbrt_tab, const int32_t* coeffs, uint8_t* planeR,
+                     uint8_t* planeB, size_t plane_stride, int n) {
+    if (n <= 0 || g.nrows <= 0) return;
+    const size_t npix = (size_t)g.warp_h * g.warp_w;
+    const bool four = (g.warp_w & 3) == 0 && (plane_stride & 3) == 0;
+    for (int i = 0; i < n; i += CalIds::N) {
+        const int m = std::min(n - i, (int)CalIds::N);
+        const CalIds ci = pack_ids(ids + i, m);
+        uint8_t *pr = planeR + (size_t)i * plane_stride, *pb = planeB + (size_t)i * plane_stride;
+        if (four)
+            hipLaunchKernelGGL(k_warp_cal<4>, dim3((unsigned)(((npix >> 2) + 255) / 256), 1, m), dim3(256), 0, s, und, und_px, first_slot + i,
+                               sets, ci, g, gamma_tab, cbrt_tab, coeffs, pr, pb, plane_stride);
+        else
+            hipLaunchKernelGGL(k_warp_cal<1>, dim3((unsigned)((npix + 255) / 256), 1, m), dim3(256), 0, s, und, und_px, first_slot + i,
+                               sets, ci, g, gamma_tab, cbrt_tab, coeffs, pr, pb, plane_stride);
     }
 }
 

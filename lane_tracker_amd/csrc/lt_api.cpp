@@ -194,6 +194,7 @@ void free_slots(lt_ctx* c) {
     c->frame_full.clear();
     c->annot_full.clear();
     c->front_ok.clear();
+    c->slot_cal.clear();
     dev_free(c->d_rec);
     dev_free(c->d_prev);
     dev_free(c->d_pix);
@@ -615,6 +616,13 @@ int lt_create(const lt_calib* calib, int device, lt_ctx** out) {
     c->und_px = (size_t)c->fe.nrows * calib->img_w;
     c->masks.set_geometry(calib->warp_h, calib->warp_w);
     c->bev_bytes = c->masks.plane_bytes * 3;
+    c->cal.resize(1);                    // set 0: this calibration
+    c->cal[0].calib = *calib;
+    c->cal[0].r0 = r0;
+    c->cal[0].r1 = r1;
+    c->cal[0].need0 = c->cam_r0;
+    c->cal[0].need1 = c->cam_r1;
+    refresh_cal0(c);
     *out = c;
     return LT_OK;
 }
@@ -697,6 +705,11 @@ void lt_destroy(lt_ctx* c) {
     dev_free(c->d_coef);
     dev_free(c->d_oxy);
     dev_free(c->d_ofrac);
+    for (size_t i = 1; i < c->cal.size(); ++i) {     // (set 0's tables are the ones above)
+        lt_ctx::CalSet& q = c->cal[i];
+        dev_free(q.d_uxy); dev_free(q.d_ufrac); dev_free(q.d_wxy); dev_free(q.d_wfrac); dev_free(q.d_oxy); dev_free(q.d_ofrac);
+    }
+    dev_free(c->d_cal);
     dev_free(c->d_atlas);
     dev_free(c->d_advance);
     dev_free(c->d_lines);
@@ -734,6 +747,7 @@ int lt_reserve(lt_ctx* c, int capacity) {
     c->frame_full.assign(n, 0);
     c->annot_full.assign(n, 0);
     c->front_ok.assign(n, 0);
+    c->slot_cal.assign(n, 0);            // every slot starts with set 0
     if ((rc = dev_alloc(&c->d_rec, n))) { free_slots(c); return rc; }
     if ((rc = dev_alloc(&c->d_prev, n * 6))) { free_slots(c); return rc; }
     c->capacity = capacity;
@@ -1794,6 +1808,210 @@ int lt_set_frame_base(lt_ctx* c, int first, int n, int first_frame) {
     return LT_OK;
 }
 
+// ---- calibration sets -----------------------------------------------------------------------------------
+}  // extern "C"
+namespace lt {
+void refresh_cal0(lt_ctx* c) {
+    if (c->cal.empty()) return;
+    lt_ctx::CalSet& q = c->cal[0];
+    q.d_uxy = c->d_uxy; q.d_ufrac = c->d_ufrac; q.d_wxy = c->d_wxy; q.d_wfrac = c->d_wfrac; q.d_oxy = c->d_oxy; q.d_ofrac = c->d_ofrac;
+    q.have_overlay = c->have_overlay;
+}
+int refuse_foreign(lt_ctx* c, int first, int n, const char* who) {
+    const int bad = first_foreign(c, first, n);
+    if (bad < 0) return LT_OK;
+    return fail(LT_ERR_STATE, "%s knows the context's own calibration only: slot %d has calibration set %d", who, bad, slot_set(c, bad));
+}
+// The rows every set shares, from what each set needs: the rows of the undistorted image (fe.r0, fe.nrows), the camera rows the
+// uploads bring (cam_r0, cam_r1: widened by the lane's rows where those are the same run, as lt_overlay_configure says, and never
+// narrowed) and the rows a lane can reach (ov_r0, ov_r1).  Returns whether the rows of the undistorted image changed.
+bool union_rows(lt_ctx* c) {
+    auto join = [](int& lo, int& hi, int a, int b) {
+        if (b <= a) return;
+        if (hi <= lo) { lo = a; hi = b; }
+        else { lo = std::min(lo, a); hi = std::max(hi, b); }
+    };
+    int r0 = 0, r1 = 0, n0 = 0, n1 = 0, o0 = 0, o1 = 0;
+    for (const auto& q : c->cal) {
+        join(r0, r1, q.r0, q.r1);
+        join(n0, n1, q.need0, q.need1);
+        if (q.have_overlay) join(o0, o1, q.ov_r0, q.ov_r1);
+    }
+    if (n1 > n0 && o1 > o0 && o0 >= n0 - 32 && o1 <= n1 + 32) { n0 = std::min(n0, o0); n1 = std::max(n1, o1); }
+    join(n0, n1, c->cam_r0, c->cam_r1);   // the rows the uploads bring only ever widen (a second lt_overlay_configure: as it always did)
+    c->cam_r0 = n0; c->cam_r1 = n1;
+    c->ov_r0 = o0; c->ov_r1 = o1;
+    const bool changed = r0 != c->fe.r0 || r1 - r0 != c->fe.nrows;
+    c->fe.r0 = r0;
+    c->fe.nrows = r1 - r0;
+    return changed;
+}
+// The undistortion table of calibration `k` for the rows [U0, U1) of the undistorted image, built and uploaded into fresh device
+// blocks; need0 / need1: the camera rows it reads for the rows [r0, r1) the set's own warp reads.  Nothing of the context changes.
+struct UndTables {
+    int16_t* d_uxy = nullptr;
+    uint16_t* d_ufrac = nullptr;
+    int need0 = 0, need1 = 0;
+    void release() { dev_free(d_uxy); dev_free(d_ufrac); }
+};
+static int build_undistortion(const lt_calib& k, int r0, int r1, int U0, int U1, UndTables& out) {
+    RemapTable und;
+    build_undistort_table(k, U0, U1, und);
+    int lo = k.img_h, hi = 0;
+    for (int row = std::max(r0, U0); row < std::min(r1, U1); ++row)
+        for (int x = 0; x < und.cols; ++x) {
+            const size_t o = (size_t)(row - U0) * und.cols + x;
+            const int sx = und.xy[o * 2], sy = und.xy[o * 2 + 1];
+            if (sy < -1 || sy >= k.img_h || sx < -1 || sx >= k.img_w) continue;   // every tap outside: reads as 0
+            lo = std::min(lo, std::max(sy, 0));
+            hi = std::max(hi, std::min(sy + 2, k.img_h));
+        }
+    out.need0 = hi > lo ? lo : 0;
+    out.need1 = hi > lo ? hi : 0;
+    int rc;
+    if ((rc = dev_alloc(&out.d_uxy, und.xy.size())) || (rc = dev_alloc(&out.d_ufrac, und.frac.size()))) { out.release(); return rc; }
+    if (hipMemcpy(out.d_uxy, und.xy.data(), und.xy.size() * 2, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(out.d_ufrac, und.frac.data(), und.frac.size() * 2, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError();
+        out.release();
+        return fail(LT_ERR_HIP, "table upload failed");
+    }
+    return LT_OK;
+}
+}  // namespace lt
+extern "C" {
+
+// Everything that can fail -- the new set's tables, the other sets' tables where the rows grow, the buffer of undistorted rows, the
+// set table -- is built beside the context first; only then is the set committed, by steps that cannot fail.  An error leaves the
+// context exactly as it was.
+int lt_add_calibration(lt_ctx* c, const lt_calib* calib, int* id) {
+    if (!c || !calib || !id) return fail(LT_ERR_INVALID, "null argument");
+    if (calib->img_w != c->calib.img_w || calib->img_h != c->calib.img_h || calib->warp_w != c->calib.warp_w || calib->warp_h != c->calib.warp_h)
+        return fail(LT_ERR_INVALID, "a calibration set must have the context's sizes (camera %dx%d, bird's-eye %dx%d), got %dx%d and %dx%d",
+                    c->calib.img_w, c->calib.img_h, c->calib.warp_w, c->calib.warp_h, calib->img_w, calib->img_h, calib->warp_w, calib->warp_h);
+    if (c->input_locked) return fail(LT_ERR_STATE, "calibration sets are added before a context's first upload");
+    if ((int)c->cal.size() >= LT_MAX_CALIBRATIONS) return fail(LT_ERR_CAPACITY, "a context holds at most %d calibration sets", LT_MAX_CALIBRATIONS);
+    int rc = set_device(c);
+    if (rc) return rc;
+    if ((rc = sync_all(c))) return rc;
+    TraceScope ts_all("lt_add_calibration");
+    refresh_cal0(c);
+    lt_ctx::CalSet q;
+    q.calib = *calib;
+    RemapTable warp;
+    build_warp_table(*calib, warp);
+    warp_source_rows(*calib, warp, q.r0, q.r1);
+    // the rows of the undistorted image with this set: do they grow?
+    int U0 = c->fe.r0, U1 = c->fe.r0 + c->fe.nrows;
+    if (q.r1 > q.r0) {
+        if (U1 <= U0) { U0 = q.r0; U1 = q.r1; }
+        else { U0 = std::min(U0, q.r0); U1 = std::max(U1, q.r1); }
+    }
+    const bool grow = U0 != c->fe.r0 || U1 - U0 != c->fe.nrows;
+    const size_t n_old = c->cal.size(), und_px = (size_t)(U1 - U0) * c->calib.img_w;
+    std::vector<UndTables> fresh(grow ? n_old + 1 : 1);      // [i]: set i's table for the new rows (grow), last: the new set's
+    uint32_t* d_und = nullptr;
+    CalTables* d_cal = nullptr;
+    auto drop = [&](int code) {
+        dev_free(q.d_wxy); dev_free(q.d_wfrac);
+        for (auto& f : fresh) f.release();
+        dev_free(d_und);
+        dev_free(d_cal);
+        return code;
+    };
+    if ((rc = dev_alloc(&q.d_wxy, warp.xy.size()))) return drop(rc);
+    if ((rc = dev_alloc(&q.d_wfrac, warp.frac.size()))) return drop(rc);
+    if (hipMemcpy(q.d_wxy, warp.xy.data(), warp.xy.size() * 2, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(q.d_wfrac, warp.frac.data(), warp.frac.size() * 2, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipGetLastError();
+        return drop(fail(LT_ERR_HIP, "table upload failed"));
+    }
+    if (grow)        // every earlier set's table again, for the union
+        for (size_t i = 0; i < n_old; ++i)
+            if ((rc = build_undistortion(c->cal[i].calib, c->cal[i].r0, c->cal[i].r1, U0, U1, fresh[i]))) return drop(rc);
+    if ((rc = build_undistortion(q.calib, q.r0, q.r1, U0, U1, fresh.back()))) return drop(rc);
+    if (grow && c->capacity > 0 && (rc = dev_alloc(&d_und, (size_t)((c->capacity + 1) / 2) * 2 * und_px))) return drop(rc);
+    if (!c->d_cal && (rc = dev_alloc(&d_cal, (size_t)LT_MAX_CALIBRATIONS))) return drop(rc);
+    {   // the set table as it will be
+        std::vector<CalTables> tabs(n_old + 1);
+        for (size_t i = 0; i < n_old; ++i)
+            tabs[i] = CalTables{grow ? fresh[i].d_uxy : c->cal[i].d_uxy, grow ? fresh[i].d_ufrac : c->cal[i].d_ufrac, c->cal[i].d_wxy, c->cal[i].d_wfrac};
+        tabs[n_old] = CalTables{fresh.back().d_uxy, fresh.back().d_ufrac, q.d_wxy, q.d_wfrac};
+        if (hipMemcpy(c->d_cal ? c->d_cal : d_cal, tabs.data(), tabs.size() * sizeof(CalTables), hipMemcpyHostToDevice) != hipSuccess) {
+            // (an existing table may now name tables that are about to be dropped: written again below)
+            (void)hipGetLastError();
+            if (c->d_cal) {
+                for (size_t i = 0; i < n_old; ++i) tabs[i] = CalTables{c->cal[i].d_uxy, c->cal[i].d_ufrac, c->cal[i].d_wxy, c->cal[i].d_wfrac};
+                (void)hipMemcpy(c->d_cal, tabs.data(), n_old * sizeof(CalTables), hipMemcpyHostToDevice);
+                (void)hipGetLastError();
+            }
+            return drop(fail(LT_ERR_HIP, "table upload failed"));
+        }
+    }
+    // ---- commit: nothing below can fail ----
+    if (d_cal) c->d_cal = d_cal;
+    if (grow) {
+        for (size_t i = 0; i < n_old; ++i) {
+            lt_ctx::CalSet& e = c->cal[i];
+            dev_free(e.d_uxy);
+            dev_free(e.d_ufrac);
+            e.d_uxy = fresh[i].d_uxy;
+            e.d_ufrac = fresh[i].d_ufrac;
+            e.need0 = fresh[i].need0;
+            e.need1 = fresh[i].need1;
+        }
+        c->d_uxy = c->cal[0].d_uxy;          // (set 0's tables are the context's own)
+        c->d_ufrac = c->cal[0].d_ufrac;
+        c->und_px = und_px;
+        c->und_bytes = und_px * 3;           // as returned by lt_download_undistorted (RGB)
+        if (c->capacity > 0) {
+            dev_free(c->d_und);
+            c->d_und = d_und;
+        }
+        std::fill(c->front_ok.begin(), c->front_ok.end(), 0);
+    }
+    q.d_uxy = fresh.back().d_uxy;
+    q.d_ufrac = fresh.back().d_ufrac;
+    q.need0 = fresh.back().need0;
+    q.need1 = fresh.back().need1;
+    c->cal.push_back(q);
+    union_rows(c);
+    *id = (int)c->cal.size() - 1;
+    return LT_OK;
+}
+
+int lt_calibration_count(lt_ctx* c, int* count) {
+    if (!c || !count) return fail(LT_ERR_INVALID, "null argument");
+    *count = (int)c->cal.size();
+    return LT_OK;
+}
+
+int lt_set_slot_calibrations(lt_ctx* c, int first, int n, const int32_t* ids) {
+    int rc = check_slots(c, first, n);
+    if (rc) return rc;
+    if (n > 0 && !ids) return fail(LT_ERR_INVALID, "null ids");
+    for (int i = 0; i < n; ++i)
+        if (ids[i] < 0 || ids[i] >= (int)c->cal.size())
+            return fail(LT_ERR_INVALID, "slot %d: calibration set %d out of range (the context has %d)", first + i, ids[i], (int)c->cal.size());
+    // Nothing to order on the device: a launch carries the sets of its slots by value.  A slot that changes set has planes made with
+    // another set's tables: its front end is stale (lt_mask_rerun).
+    for (int i = 0; i < n; ++i) {
+        const size_t s = (size_t)(first + i);
+        if (c->slot_cal[s] == (uint8_t)ids[i]) continue;
+        c->slot_cal[s] = (uint8_t)ids[i];
+        front_stale(c, first + i, 1);
+    }
+    return LT_OK;
+}
+
+int lt_get_slot_calibrations(lt_ctx* c, int first, int n, int32_t* ids) {
+    int rc = check_slots(c, first, n);
+    if (rc) return rc;
+    if (n > 0 && !ids) return fail(LT_ERR_INVALID, "null ids");
+    for (int i = 0; i < n; ++i) ids[i] = slot_set(c, first + i);
+    return LT_OK;
+}
+
 // ---- compute ------------------------------------------------------------------------------------------
 static int mask_run_impl(lt_ctx* c, int first, int n, const lt_filter_params* p, bool reuse_front) {
     int rc = check_slots(c, first, n);
@@ -1809,6 +2027,11 @@ static int mask_run_impl(lt_ctx* c, int first, int n, const lt_filter_params* p,
         bool have_front = reuse_front && !c->stage_timing && f0 + m <= (int)c->front_ok.size();
         for (int i = f0; have_front && i < f0 + m; ++i) have_front = c->front_ok[(size_t)i] != 0;
         if (!have_front) {
+            // A slice whose slots all have one calibration set -- whichever -- takes the kernels that read one table, with that set's
+            // tables; only a slice that mixes sets takes the table-per-slot forms.
+            const lt_ctx::CalSet& cs = c->cal[(size_t)slot_set(c, f0)];
+            bool mixed = false;
+            for (int i = f0 + 1; i < f0 + m && !mixed; ++i) mixed = slot_set(c, i) != slot_set(c, f0);
             { StageScope t(c, ST_UNDISTORT, st);
               // runs of slots whose frames lie in the caller's device memory (the table form) and of slots that hold their own
               auto is_attached = [&](int i) { return i < (int)c->attached.size() && c->attached[(size_t)i] != 0; };
@@ -1818,13 +2041,15 @@ static int mask_run_impl(lt_ctx* c, int first, int n, const lt_filter_params* p,
                   const FrameSource src = att ? FrameSource::surfaces(c->d_surf)
                                           : c->in_layout != LT_INPUT_RGB ? FrameSource::slots(slot_yuv(c, a), c->yuv_stride)
                                                                          : FrameSource::slots(slot_frame(c, a), c->frame_bytes);
-                  launch_undistort_rows(st, src, c->in_layout, yuv_coef_of(c), c->d_uxy, c->d_ufrac, c->fe, c->d_und, c->und_px, a, b - a);
+                  if (mixed) launch_undistort_cal(st, src, c->in_layout, yuv_coef_of(c), c->d_cal, &c->slot_cal[(size_t)a], c->fe, c->d_und, c->und_px, a, b - a);
+                  else launch_undistort_rows(st, src, c->in_layout, yuv_coef_of(c), cs.d_uxy, cs.d_ufrac, c->fe, c->d_und, c->und_px, a, b - a);
               } }
             { int mrc = n == 1 ? note_range_frame(c, c->readers, st, f0, f0 + m) : note_range(c->readers, st, f0, f0 + m); if (mrc) return mrc; }
             { StageScope t(c, ST_WARP_SPLIT, st);
-              launch_warp_split(st, c->d_und, c->und_px, f0, c->d_wxy, c->d_wfrac, c->fe, c->d_gamma,
-                                c->d_cbrt, c->d_coef, c->lab_clamp_dead, c->masks.d_plane[P_R] + (size_t)f0 * ps, c->masks.d_plane[P_B] + (size_t)f0 * ps,
-                                ps, m); }
+              uint8_t *pr = c->masks.d_plane[P_R] + (size_t)f0 * ps, *pb = c->masks.d_plane[P_B] + (size_t)f0 * ps;
+              if (mixed) launch_warp_cal(st, c->d_und, c->und_px, f0, c->d_cal, &c->slot_cal[(size_t)f0], c->fe, c->d_gamma, c->d_cbrt, c->d_coef, pr, pb, ps, m);
+              else launch_warp_split(st, c->d_und, c->und_px, f0, cs.d_wxy, cs.d_wfrac, c->fe, c->d_gamma,
+                                     c->d_cbrt, c->d_coef, c->lab_clamp_dead, pr, pb, ps, m); }
             for (int i = f0; i < f0 + m && i < (int)c->front_ok.size(); ++i) c->front_ok[(size_t)i] = 1;
         }
         int frc = run_mask_chain(c->masks, env, st, f0, m, p, c->calib.warp_h, c->calib.warp_w, n);

@@ -119,6 +119,23 @@ struct lt_ctx {
     int16_t *d_uxy = nullptr, *d_wxy = nullptr;
     uint16_t *d_ufrac = nullptr, *d_wfrac = nullptr, *d_gamma = nullptr, *d_cbrt = nullptr;
     int32_t* d_coef = nullptr;
+    // Calibration sets (lt_add_calibration).  Set 0 is the context's own: `calib` and the tables above.  `cal[id]` holds what set
+    // id brings: its calibration, its remap tables and its overlay table; cal[0] mirrors the pointers above (refresh_cal0).  The
+    // geometry is ONE for all sets: fe.r0 / fe.nrows, cam_r0 / cam_r1 and ov_r0 / ov_r1 are the unions over the sets, and every
+    // set's undistortion table is built for the union rows.  d_cal: the sets' tables as the table-per-slot kernels read them
+    // (allocated with the second set); slot_cal: the set of every slot.
+    struct CalSet {
+        lt_calib calib{};
+        int16_t *d_uxy = nullptr, *d_wxy = nullptr, *d_oxy = nullptr;
+        uint16_t *d_ufrac = nullptr, *d_wfrac = nullptr, *d_ofrac = nullptr;
+        int r0 = 0, r1 = 0;                   // the rows of the undistorted image its warp reads
+        int need0 = 0, need1 = 0;             // the camera rows its undistortion reads for them
+        int ov_r0 = 0, ov_r1 = 0;             // the camera rows its lane overlay can change
+        bool have_overlay = false;
+    };
+    std::vector<CalSet> cal;
+    lt::CalTables* d_cal = nullptr;
+    std::vector<uint8_t> slot_cal;
     bool lab_clamp_dead = false;   // no pixel reaches the clamp of the cube-root table index with these tables (front_arith.h)
     // slots
     int capacity = 0;
@@ -314,6 +331,18 @@ inline double* slot_prev(const lt_ctx* c, int s) { return c->d_prev + (size_t)s 
 inline uint32_t* slot_pix(const lt_ctx* c, int s) { return c->d_pix + (size_t)s * 2 * c->maxpix; }           // [side][maxpix]
 inline int32_t* slot_cent(const lt_ctx* c, int s) { return c->d_cent + (size_t)s * 2 * (c->maxlev + 2); }    // [side][maxlev + 2]
 inline uint32_t* slot_band_sums(const lt_ctx* c, int s, int nbands) { return c->d_band_sums + (size_t)s * nbands * c->calib.warp_w; }
+
+// ---- calibration sets (lt_api.cpp) ------------------------------------------------------------------------------
+inline int slot_set(const lt_ctx* c, int s) { return s >= 0 && s < (int)c->slot_cal.size() ? c->slot_cal[(size_t)s] : 0; }
+// the first slot of [first, first + n) whose set is not 0, or -1: what the entry points that know set 0's tables only ask
+inline int first_foreign(const lt_ctx* c, int first, int n) {
+    for (int i = first; i < first + n; ++i)
+        if (slot_set(c, i) != 0) return i;
+    return -1;
+}
+int refuse_foreign(lt_ctx* c, int first, int n, const char* who);   // LT_ERR_STATE if one of the slots has another set than 0
+bool union_rows(lt_ctx* c);                                         // fe.r0 / fe.nrows, cam_r0 / cam_r1, ov_r0 / ov_r1 := the unions over the sets
+void refresh_cal0(lt_ctx* c);                                       // cal[0] := the context's own tables and rows
 
 // ---- LT_TRACE_START=1 (lt_memory.cpp): one line per set-up phase on stderr -------------------------------
 //   lt_start <seconds on CLOCK_MONOTONIC, = Python's time.monotonic()> <what> <ms> [<bytes>]

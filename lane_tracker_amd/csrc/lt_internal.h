@@ -90,6 +90,29 @@ struct FrameSource {
 // same blend); `und` is the base of the whole buffer, `first_slot` the absolute slot of frame 0 of the call
 void launch_undistort_rows(hipStream_t s, FrameSource src, int layout, YuvCoef k, const int16_t* uxy, const uint16_t* ufrac,
                            FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n);
+// Calibration sets (lt_add_calibration): the remap tables of one set as the table-per-slot front end finds them -- entry `id` of the
+// context's set table (device memory, written when a set is added or rebuilt: before the context's first upload, with nothing in
+// flight).  Which set a slot of a launch has travels BY VALUE, one byte per slot of the launch (id of slot first_slot + z: byte z):
+// an assignment changes every tick of a group, and an argument cannot be rewritten under a launch still queued on another stream.
+struct CalTables {
+    const int16_t* uxy;
+    const uint16_t* ufrac;
+    const int16_t* wxy;
+    const uint16_t* wfrac;
+};
+static_assert(sizeof(CalTables) == 32, "CalTables: 32 bytes, two scalar loads");
+constexpr int LT_MAX_CALIBRATIONS = 256;   // an id is a byte
+struct CalIds {                  // the sets of the slots of one launch
+    static constexpr int N = 64;
+    uint32_t w[N / 4];
+};
+// The table-per-slot forms of the two launches above, for slots [first_slot, first_slot + n) whose sets are ids[0, n) (host memory):
+// every slot with the tables of its own set, one frame per walk; launches of up to CalIds::N slots.
+void launch_undistort_cal(hipStream_t s, FrameSource src, int layout, YuvCoef k, const CalTables* sets, const uint8_t* ids,
+                          FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n);
+void launch_warp_cal(hipStream_t s, const uint32_t* und, size_t und_px, int first_slot, const CalTables* sets, const uint8_t* ids,
+                     FrontEndGeom g, const uint16_t* gamma_tab, const uint16_t* cbrt_tab, const int32_t* coeffs, uint8_t* planeR,
+                     uint8_t* planeB, size_t plane_stride, int n);
 // entries[0, n) (host memory, consumed before the call returns) -> tab[first, first + n), stream-ordered
 void launch_write_surf_entries(hipStream_t s, SurfEntry* tab, int first, const SurfEntry* entries, int n);
 // rows [r0, r1) of the n surfaces of entries[] (host memory) -> the same rows of n RGB frames: a conversion (4:2:0) or a pitched copy (RGB)

@@ -95,8 +95,9 @@ int lt_lane_polygon_spans(int warp_h, const int32_t* left_yx, int n_left, const 
     return LT_OK;
 }
 
-int lt_overlay_configure(lt_ctx* c, const double* Minv) {
+int lt_overlay_configure_set(lt_ctx* c, int set, const double* Minv) {
     if (!c || !Minv) return fail(LT_ERR_INVALID, "null argument");
+    if (set < 0 || set >= (int)c->cal.size()) return fail(LT_ERR_INVALID, "calibration set %d out of range (the context has %d)", set, (int)c->cal.size());
     int rc = set_device(c);
     if (rc) return rc;
     TraceScope ts_all("lt_overlay_configure");
@@ -109,17 +110,27 @@ int lt_overlay_configure(lt_ctx* c, const double* Minv) {
     u.warp_h = c->calib.img_h;
     RemapTable t;
     build_warp_table(u, t);
-    dev_free(c->d_oxy);
-    dev_free(c->d_ofrac);
-    c->have_overlay = false;
-    if ((rc = dev_alloc(&c->d_oxy, t.xy.size()))) return rc;
-    if ((rc = dev_alloc(&c->d_ofrac, t.frac.size()))) return rc;
-    HIP_TRY(hipMemcpy(c->d_oxy, t.xy.data(), t.xy.size() * 2, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c->d_ofrac, t.frac.data(), t.frac.size() * 2, hipMemcpyHostToDevice));
+    lt_ctx::CalSet& q = c->cal[(size_t)set];
+    dev_free(q.d_oxy);
+    dev_free(q.d_ofrac);
+    q.have_overlay = false;
+    if (set == 0) {                      // (set 0's tables are the context's own)
+        c->d_oxy = nullptr;
+        c->d_ofrac = nullptr;
+        c->have_overlay = false;
+    }
+    if ((rc = dev_alloc(&q.d_oxy, t.xy.size()))) return rc;
+    if ((rc = dev_alloc(&q.d_ofrac, t.frac.size()))) return rc;
+    if (set == 0) {
+        c->d_oxy = q.d_oxy;
+        c->d_ofrac = q.d_ofrac;
+    }
+    HIP_TRY(hipMemcpy(q.d_oxy, t.xy.data(), t.xy.size() * 2, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(q.d_ofrac, t.frac.data(), t.frac.size() * 2, hipMemcpyHostToDevice));
     // Camera rows the lane can reach at all: a pixel's four taps are (sx, sy) .. (sx + 1, sy + 1), so only pixels with
     // -1 <= sx <= bw - 1 and -1 <= sy <= bh - 1 can see the bird's-eye image; every other pixel of the annotated frame is the
     // camera pixel whatever the polygon (lt_overlay_rows, lt_present_frame).
-    c->ov_r0 = c->ov_r1 = 0;
+    q.ov_r0 = q.ov_r1 = 0;
     for (int y = 0; y < t.rows; ++y) {
         bool any = false;
         for (int x = 0; x < t.cols && !any; ++x) {
@@ -127,22 +138,23 @@ int lt_overlay_configure(lt_ctx* c, const double* Minv) {
             any = sx >= -1 && sx <= c->calib.warp_w - 1 && sy >= -1 && sy <= c->calib.warp_h - 1;
         }
         if (any) {
-            if (c->ov_r1 == 0) c->ov_r0 = y;
-            c->ov_r1 = y + 1;
+            if (q.ov_r1 == 0) q.ov_r0 = y;
+            q.ov_r1 = y + 1;
         }
     }
+    q.have_overlay = true;
+    if (set == 0) c->have_overlay = true;
     // The rows the mask chain uploads (lt_upload_frame_rows: what the undistortion reads) and the rows the lane can reach are
     // nearly the same run (457-695 and 458-696 of 720 with the reference calibration): a row or two more in the former, and an
     // annotated frame needs no second upload for the lane's run (lt_upload_frame_rest_rows: 12 us per frame of process()).
     // (a 1920x1080 camera scaled from the reference calibration: 685-1042 against a lane run that ends a dozen rows lower -- the
     // second upload was 26-29 us of every process() frame there: tools/process_trace.py x; up to 32 rows either side are taken along)
-    if (c->cam_r1 > c->cam_r0 && c->ov_r1 > c->ov_r0 && c->ov_r0 >= c->cam_r0 - 32 && c->ov_r1 <= c->cam_r1 + 32) {
-        c->cam_r0 = std::min(c->cam_r0, c->ov_r0);
-        c->cam_r1 = std::max(c->cam_r1, c->ov_r1);
-    }
-    c->have_overlay = true;
+    // With several calibration sets both runs are the unions over the sets (union_rows).
+    union_rows(c);
     return LT_OK;
 }
+
+int lt_overlay_configure(lt_ctx* c, const double* Minv) { return lt_overlay_configure_set(c, 0, Minv); }
 
 // A call is about to overwrite the page-locked staging regions of slots [first, first + n): if a copy out of those regions
 // may still be in flight (an earlier call of the same kind over the same slots), wait for it; then widen the busy range.
@@ -354,7 +366,11 @@ static int overlay_run_impl(lt_ctx* c, int first, int n, const int32_t* left_n, 
                             bool* went_direct = nullptr, const CoeffInput* ci = nullptr) {
     int rc = check_slots(c, first, n);
     if (rc) return rc;
-    if (!c->have_overlay) return fail(LT_ERR_STATE, "lt_overlay_run before lt_overlay_configure");
+    if (!c->have_overlay && first_foreign(c, first, n) < 0) return fail(LT_ERR_STATE, "lt_overlay_run before lt_overlay_configure");
+    if (strip && (rc = refuse_foreign(c, first, n, "a strip overlay"))) return rc;
+    for (int i = first; i < first + n; ++i)           // every slot is drawn with the inverse-warp table of its own calibration set
+        if (!c->cal[(size_t)slot_set(c, i)].have_overlay)
+            return fail(LT_ERR_STATE, "lt_overlay_run before lt_overlay_configure: slot %d has calibration set %d, whose overlay is not configured", i, slot_set(c, i));
     if (n == 0) return LT_OK;
     if (!ci) {
         if (!left_n || !right_n) return fail(LT_ERR_INVALID, "null point counts");
@@ -438,8 +454,9 @@ static int overlay_run_impl(lt_ctx* c, int first, int n, const int32_t* left_n, 
         HIP_TRY(hipStreamWaitEvent(ps, c->annot_busy.done, 0));
     if (one) {
         uint8_t* dst = direct_out ? direct_out : c->d_annot + (size_t)first * c->frame_bytes;
+        const lt_ctx::CalSet& q = c->cal[(size_t)slot_set(c, first)];
         if (launch_overlay_lane_one(ps, slot_frame(c, first), dst,
-                                    c->d_oxy, c->d_ofrac, hs, c->calib.img_h, c->calib.img_w, bh, c->calib.warp_w, (float)alpha, rows4)) {
+                                    q.d_oxy, q.d_ofrac, hs, c->calib.img_h, c->calib.img_w, bh, c->calib.warp_w, (float)alpha, rows4)) {
             HIP_TRY(hipGetLastError());
             if (went_direct) *went_direct = direct_out != nullptr;
             if (!direct_out) mark_annot(c, first, n, rows4 ? 0 : 1);
@@ -460,10 +477,16 @@ static int overlay_run_impl(lt_ctx* c, int first, int n, const int32_t* left_n, 
                                        c->strip_bytes, c->d_oxy, c->d_ofrac, c->d_spans + (size_t)first * bh * 2, (size_t)bh, c->calib.img_w,
                                        c->ov_r0, c->ov_r1, bh, c->calib.warp_w, (float)alpha, n))
             return fail(LT_ERR_STATE, "strip overlay needs a frame width that is a multiple of 4");
-    } else
-    launch_overlay_lane(ps, slot_frame(c, first), c->d_annot + (size_t)first * c->frame_bytes,
-                        c->frame_bytes, c->d_oxy, c->d_ofrac, c->d_spans + (size_t)first * bh * 2, (size_t)bh,
-                        c->calib.img_h, c->calib.img_w, bh, c->calib.warp_w, (float)alpha, n, rows4);
+    } else {
+        // run by run over consecutive slots of one calibration set (one launch where the range has one set)
+        for (int a = first, b; a < first + n; a = b) {
+            for (b = a + 1; b < first + n && slot_set(c, b) == slot_set(c, a); ++b) {}
+            const lt_ctx::CalSet& q = c->cal[(size_t)slot_set(c, a)];
+            launch_overlay_lane(ps, slot_frame(c, a), c->d_annot + (size_t)a * c->frame_bytes,
+                                c->frame_bytes, q.d_oxy, q.d_ofrac, c->d_spans + (size_t)a * bh * 2, (size_t)bh,
+                                c->calib.img_h, c->calib.img_w, bh, c->calib.warp_w, (float)alpha, b - a, rows4);
+        }
+    }
     HIP_TRY(hipGetLastError());
     if (!strip) mark_annot(c, first, n, rows4 ? 0 : 1);
     if ((rc = staging_mark(c->spans_busy, ps))) return rc;
@@ -741,6 +764,7 @@ int lt_present_frame(lt_ctx* c, int slot, const int32_t* left_n, const int32_t* 
     if (rc) return rc;
     if (!out) return fail(LT_ERR_INVALID, "null output buffer");
     if (!left_n || !right_n) return fail(LT_ERR_INVALID, "null point counts");
+    if ((rc = refuse_foreign(c, slot, 1, "lt_present_frame"))) return rc;
     if (!c->have_overlay) return fail(LT_ERR_STATE, "lt_present_frame before lt_overlay_configure");
     const bool text = lines && n_lines > 0 && line_len > 0 && c->font_glyphs > 0;
     int r[4];
@@ -764,6 +788,7 @@ int lt_present_lane_async(lt_ctx* c, int slot, const int32_t* left_n, const int3
     if (rc) return rc;
     if (!out) return fail(LT_ERR_INVALID, "null output buffer");
     if (!left_n || !right_n) return fail(LT_ERR_INVALID, "null point counts");
+    if ((rc = refuse_foreign(c, slot, 1, "lt_present_lane_async"))) return rc;
     if (!c->have_overlay) return fail(LT_ERR_STATE, "lt_present_lane_async before lt_overlay_configure");
     int r[4];
     if ((rc = present_rows(c, rows4, false, 0, 0, 0, true, true, r))) return rc;
@@ -796,6 +821,7 @@ int lt_present_lane_from_fit_async(lt_ctx* c, int slot, const double* prev_sum, 
     int rc = check_slots(c, slot, 1);
     if (rc) return rc;
     if (!out || !ploty || !ploty2 || n_rows < 1 || count < 1 || (count > 1 && !prev_sum)) return fail(LT_ERR_INVALID, "lt_present_lane_from_fit_async: bad arguments");
+    if ((rc = refuse_foreign(c, slot, 1, "lt_present_lane_from_fit_async"))) return rc;
     if (!c->have_overlay) return fail(LT_ERR_STATE, "lt_present_lane_from_fit_async before lt_overlay_configure");
     int r[4];
     if ((rc = present_rows(c, rows4, false, 0, 0, 0, true, true, r))) return rc;
@@ -845,8 +871,9 @@ int lt_present_lane_from_fit_async(lt_ctx* c, int slot, const double* prev_sum, 
 int lt_lane_spans_from_fit(lt_ctx* c, const double* fit6, int detected, int fit_flags, const double* prev_sum, int count, const double* ploty,
                            const double* ploty2, int n_rows, int16_t* spans_out) {
     if (!c || !fit6 || !ploty || !ploty2 || !spans_out || n_rows < 1 || count < 1) return fail(LT_ERR_INVALID, "lt_lane_spans_from_fit: bad arguments");
-    int rc = set_device(c);
+    int rc = refuse_foreign(c, 0, c->capacity, "lt_lane_spans_from_fit");      // (it names no slot: refused while ANY slot has another set)
     if (rc) return rc;
+    if ((rc = set_device(c))) return rc;
     if ((rc = sync_all(c))) return rc;
     const int bh = c->calib.warp_h;
     lt_lane_record rec;
@@ -882,6 +909,7 @@ int lt_present_finish(lt_ctx* c, int slot, const char* lines, int n_lines, int l
     int rc = check_slots(c, slot, 1);
     if (rc) return rc;
     if (!out) return fail(LT_ERR_INVALID, "null output buffer");
+    if ((rc = refuse_foreign(c, slot, 1, "lt_present_finish"))) return rc;
     const bool text = lines && n_lines > 0 && line_len > 0 && c->font_glyphs > 0;
     if ((!c->d_annot || !c->present) && (!c->lane_spec_stream || text || (rows4 && rows4[1] > rows4[0])))
         return fail(LT_ERR_STATE, "lt_present_finish before lt_present_lane_async");
@@ -1088,7 +1116,11 @@ int lt_download_bev(lt_ctx* c, int first, int n, uint8_t* out) {
     uint8_t* dst = c->d_bev + (size_t)first * c->bev_bytes;
     if (c->fe.nrows <= 0) HIP_TRY(hipMemsetAsync(dst, 0, (size_t)n * c->bev_bytes, c->stream));
     else
-        launch_warp_rgb(c->stream, c->d_und, c->und_px, first, c->d_wxy, c->d_wfrac, c->fe, dst, c->bev_bytes, n);
+        for (int a = first, b; a < first + n; a = b) {       // run by run over consecutive slots of one calibration set
+            for (b = a + 1; b < first + n && slot_set(c, b) == slot_set(c, a); ++b) {}
+            const lt_ctx::CalSet& q = c->cal[(size_t)slot_set(c, a)];
+            launch_warp_rgb(c->stream, c->d_und, c->und_px, a, q.d_wxy, q.d_wfrac, c->fe, dst + (size_t)(a - first) * c->bev_bytes, c->bev_bytes, b - a);
+        }
     HIP_TRY(hipGetLastError());
     return download(c, dst, out, (size_t)n * c->bev_bytes);
 }

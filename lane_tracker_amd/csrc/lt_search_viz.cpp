@@ -135,6 +135,10 @@ static int viz_run(lt_ctx* c, int n, const lt_viz_item* items, const int32_t* fl
     }
     if ((tfl && !fl) || (tfr && !fr) || (tbl && !bl) || (tbr && !br)) return fail(LT_ERR_INVALID, "%s: a point list the items need is null", who);
     if (n == 0) return LT_OK;
+    for (int i = 0; i < n; ++i) {        // (the bird's-eye images of the split view are warped with the context's own table)
+        const int rrc = refuse_foreign(c, items[i].slot, 1, who);
+        if (rrc) return rrc;
+    }
     if (!c->have_mask) return fail(LT_ERR_STATE, "%s: no mask in the slots: run lt_mask_run or lt_upload_masks first", who);
     for (int i = 0; i < n; ++i)
         if (!c->mask_bits_ok[(size_t)items[i].slot] && !c->masks.d_plane[P_MASK])

@@ -28,9 +28,20 @@ class _GroupMember(LaneTracker):
 
     _search_cus_set = True          # (the group's context never runs the chained stream pipeline: no CUs to reserve)
 
-    def __init__(self, group, *args, **kwargs):
-        self._group_ctx = group._ctx
+    def __init__(self, group, cal_id, *args, **kwargs):
+        self._group, self._group_ctx = group, group._ctx
+        self._cal_id = cal_id           # the calibration set of the group's context this stream's slots take
         super().__init__(*args, **kwargs)
+
+    def _overlay_tables(self):
+        """The table of this stream's calibration set, once per set of the group."""
+        done = self._group._overlay_sets
+        if self._cal_id not in done:
+            if self._cal_id:
+                self._ctx.overlay_configure(self.Minv, calibration=self._cal_id)
+            else:
+                self._ctx.overlay_configure(self.Minv)
+            done.add(self._cal_id)
 
     def _make_context(self, device):
         return self._group_ctx
@@ -44,9 +55,49 @@ class _GroupMember(LaneTracker):
     _owns_context = False           # close() leaves the group's context to LaneTrackerGroup.close
 
 
+_CALIBRATION_KEYS = ("cam_matrix", "dist_coeffs", "warp_matrices", "mpp_conversion")
+
+
+def _stream_calibrations(calibrations, k, own):
+    """`calibrations` of LaneTrackerGroup -> one complete mapping per stream (missing keys: the group's own).  ValueError /
+    TypeError for a list of another length, an entry that is no mapping, unknown keys.  Touches no device."""
+    if calibrations is None:
+        return [dict(own) for _ in range(k)]
+    cals = list(calibrations)
+    if len(cals) != k:
+        raise ValueError("calibrations: expected %d entries (None for the group's own calibration), got %d" % (k, len(cals)))
+    out = []
+    for i, c in enumerate(cals):
+        full = dict(own)
+        if c is not None:
+            if not hasattr(c, "keys"):
+                raise TypeError("calibrations[%d]: expected None or a mapping with any of %s" % (i, ", ".join(_CALIBRATION_KEYS)))
+            unknown = sorted(set(c.keys()) - set(_CALIBRATION_KEYS))
+            if unknown:
+                raise ValueError("calibrations[%d]: unknown keys %s (known: %s)" % (i, ", ".join(map(repr, unknown)), ", ".join(_CALIBRATION_KEYS)))
+            full.update(c)
+        if len(full["warp_matrices"]) != 2 or len(full["mpp_conversion"]) != 2:
+            raise ValueError("calibrations[%d]: warp_matrices is (M, Minv) and mpp_conversion is (vertical, horizontal)" % i)
+        out.append(full)
+    return out
+
+
+def _table_key(c):
+    """What a calibration set of the context is made of, byte for byte: entries with equal keys share a set."""
+    d = np.asarray(c["dist_coeffs"], np.float64).reshape(-1)
+    parts = [np.asarray(c["cam_matrix"], np.float64).reshape(9), np.concatenate([d[:5], np.zeros(max(0, 5 - d.size))]),
+             np.asarray(c["warp_matrices"][0], np.float64).reshape(9), np.asarray(c["warp_matrices"][1], np.float64).reshape(9)]
+    return b"".join(np.ascontiguousarray(p).tobytes() for p in parts)
+
+
 class LaneTrackerGroup:
-    """`k` independent lane trackers -- one per video stream, same calibration and history lengths -- advanced one frame each
+    """`k` independent lane trackers -- one per video stream, same image sizes and history lengths -- advanced one frame each
     per `process()` call in one batch on one device context.
+
+    `calibrations` (keyword only): one entry per stream -- None for the group's own calibration, or a mapping with any of
+    `cam_matrix`, `dist_coeffs`, `warp_matrices`, `mpp_conversion` (missing keys: the group's) -- for cameras that differ in
+    intrinsics, distortion or mounting.  `img_size` / `warped_size` are the group's.  Entries whose arrays are equal byte for byte
+    share one calibration set of the context (`calibration_count()`).
 
     For every stream i, the annotated frame and the whole tracker state after every call equal, bit for bit, what a solo
     `LaneTracker.process()` leaves when fed the same frames; a stream whose frame is None does not move.  `trackers[i]` is
@@ -54,23 +105,36 @@ class LaneTrackerGroup:
     `LaneTracker`; groups on different threads share nothing."""
 
     def __init__(self, k, img_size, warped_size, cam_matrix, dist_coeffs, warp_matrices, mpp_conversion, n_fail=8, n_reset=4,
-                 n_average=2, print_frame_count=False, device=0, *, pixel_format='rgb', yuv_matrix='bt601'):
+                 n_average=2, print_frame_count=False, device=0, *, pixel_format='rgb', yuv_matrix='bt601', calibrations=None):
         k = int(k)
         if k < 1:
             raise ValueError("a group needs at least one stream")
+        self._ctx = None
+        self.trackers = []
+        cals = _stream_calibrations(calibrations, k, dict(cam_matrix=cam_matrix, dist_coeffs=dist_coeffs, warp_matrices=warp_matrices,
+                                                          mpp_conversion=mpp_conversion))
         self.k = k
         self.img_size, self.warped_size = img_size, warped_size
         self.pixel_format, self.yuv_matrix = pixel_format, yuv_matrix
         self._frame_shape = _native.frame_shape(img_size, pixel_format)
         self._ctx = _native.Context(img_size, warped_size, cam_matrix, dist_coeffs, warp_matrices[0], device=device, capacity=4 * k)
         self._tick = 0
-        self.trackers = []
+        self._overlay_sets = set()           # the calibration sets whose overlay a member has configured
         try:
             if pixel_format != 'rgb':        # every stream of a group is a camera of the same kind
                 self._ctx.set_input_format(pixel_format, yuv_matrix)
-            for _ in range(k):
-                self.trackers.append(_GroupMember(self, img_size, warped_size, cam_matrix, dist_coeffs, warp_matrices, mpp_conversion,
-                                                  n_fail=n_fail, n_reset=n_reset, n_average=n_average,
+            # the calibration sets of the context: 0 is the group's own, one more for every distinct calibration among the streams
+            sets = {_table_key(dict(cam_matrix=cam_matrix, dist_coeffs=dist_coeffs, warp_matrices=warp_matrices)): 0}
+            self._cal_ids = []
+            for c in cals:
+                key = _table_key(c)
+                if key not in sets:
+                    sets[key] = self._ctx.add_calibration(c["cam_matrix"], c["dist_coeffs"], c["warp_matrices"][0])
+                self._cal_ids.append(sets[key])
+            self._many_sets = len(sets) > 1
+            for c, cal_id in zip(cals, self._cal_ids):
+                self.trackers.append(_GroupMember(self, cal_id, img_size, warped_size, c["cam_matrix"], c["dist_coeffs"], c["warp_matrices"],
+                                                  c["mpp_conversion"], n_fail=n_fail, n_reset=n_reset, n_average=n_average,
                                                   print_frame_count=print_frame_count, device=device,
                                                   pixel_format=pixel_format, yuv_matrix=yuv_matrix))
         except BaseException:
@@ -82,6 +146,10 @@ class LaneTrackerGroup:
 
     def __exit__(self, *exc):
         self.close()
+
+    def calibration_count(self):
+        """The calibration sets the group's context holds (1: every stream has the group's own calibration)."""
+        return self._ctx.calibration_count() if self._many_sets else 1
 
     def close(self):
         for t in self.trackers:
@@ -165,10 +233,12 @@ class LaneTrackerGroup:
 
         # 1-3: camera rows of the m frames, one mask chain, one search launch
         keep = feed_rows_list(ctx, imgs, base)
+        if self._many_sets:                                              # every slot with its stream's calibration set
+            ctx.set_slot_calibrations([self._cal_ids[i] for i in active], first=base)
         ctx.mask_run(m, fp, first=base)
         if annotate:
             keep_rest = feed_rest_list(ctx, imgs, base)                  # (for the overlay, beside the mask chain)
-            ts[0]._configure_overlay()
+            ts[0]._configure_overlay()                                   # (every member configured its set's overlay when it was built)
         for t in ts:                                                     # _step's opening
             t._open_frame()
             t._want_out = False
@@ -188,6 +258,8 @@ class LaneTrackerGroup:
             second = StreamPipeline._SECOND_TRY
             self._free_slots(spare, spare + len(again))
             keep_again = feed_rows_list(ctx, [imgs[j] for j in again], spare)
+            if self._many_sets:
+                ctx.set_slot_calibrations([self._cal_ids[active[j]] for j in again], first=spare)
             ctx.mask_run(len(again), _native.filter_params(second[4], *second[:4], *second[5:9]), first=spare)
             self._search([ts[j] for j in again], spare, second, diagnostics)
             for j in again:

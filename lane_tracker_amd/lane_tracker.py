@@ -630,9 +630,13 @@ class LaneTracker(StreamPipeline):
             lines.append("Frame: {}".format(self.counter - 1))
         return lines
 
+    def _overlay_tables(self):
+        """The presentation stage's inverse-warp table of this tracker's calibration, into its context."""
+        self._ctx.overlay_configure(self.Minv)
+
     def _configure_overlay(self):
         if not self._overlay_ready:
-            self._ctx.overlay_configure(self.Minv)
+            self._overlay_tables()
             font = _overlay.font_atlas()
             self._have_font = font is not None
             if font is not None:

@@ -10,6 +10,13 @@ pool of frames), annotated, process()'s default keywords:
   vs_one_solo      group_fps / the K = 1 solo rate of the same size (the rate of ONE LaneTracker.process() stream)
 
   python tools/group_throughput.py [--ticks 60] [--warmup 8] [--out profiles/group_throughput.jsonl] [--no-solo]
+                                   [--distinct-calibrations] [--front-end-times]
+
+--distinct-calibrations: every stream a camera of its own (stream i: the distortion coefficients x (1 + 0.002 i)), so that the
+group's context holds K calibration sets and every slice of a tick mixes them (the table-per-slot front end); `calibrations` in
+the line says how many sets the group holds.  --front-end-times: a second, separate pass over the same ticks with the context's
+stage timers on (hipEvent pairs around every launch, which also serialise the slices: not for the tick times) -- undistort_ms /
+warp_ms per tick, the two front-end launches summed over a tick's slices and tries.
 """
 import argparse
 import json
@@ -45,8 +52,15 @@ def tick_frames(pool, k, t):
     return [pool[(t + 11 * i) % POOL] for i in range(k)]
 
 
-def run_group(cal, pool, k, ticks, warmup):
-    with LaneTrackerGroup(k, **cal) as g:
+def distinct_calibrations(cal, k):
+    return [None] + [dict(dist_coeffs=np.asarray(cal["dist_coeffs"], np.float64) * (1.0 + 0.002 * i)) for i in range(1, k)]
+
+
+def run_group(cal, pool, k, ticks, warmup, distinct=False, stages=None):
+    kw = dict(calibrations=distinct_calibrations(cal, k)) if distinct else {}
+    with LaneTrackerGroup(k, **cal, **kw) as g:
+        if stages is not None:
+            stages["calibrations"] = g.calibration_count() if hasattr(g, "calibration_count") else 1
         for t in range(warmup):
             g.process(tick_frames(pool, k, t))
         times = []
@@ -56,6 +70,19 @@ def run_group(cal, pool, k, ticks, warmup):
             g.process(tick_frames(pool, k, t))
             times.append(time.perf_counter() - a)
         wall, cpu = time.perf_counter() - t0, cpu_s() - c0
+        if stages is not None and stages.get("front_end"):
+            ctx = g._ctx
+            ctx.sync()
+            ctx.set_stage_timing(True)
+            ctx.stage_reset()
+            for t in range(warmup + ticks, warmup + 2 * ticks):
+                g.process(tick_frames(pool, k, t))
+            ctx.sync()
+            ms = ctx.stage_ms()
+            ctx.set_stage_timing(False)
+            stages["undistort_ms"] = round(ms["undistort_rows"][0] / ticks, 4)
+            stages["warp_ms"] = round(ms["warp_split"][0] / ticks, 4)
+            stages["front_end_launches_per_tick"] = round((ms["undistort_rows"][1] + ms["warp_split"][1]) / ticks, 2)
     return wall, cpu, np.array(times)
 
 
@@ -83,6 +110,8 @@ def main():
     ap.add_argument("--ks-1080p", default="1,8")
     ap.add_argument("--out", default=None, help="also append the lines to this file")
     ap.add_argument("--no-solo", action="store_true", help="the group only (a kernel trace of the group's ticks)")
+    ap.add_argument("--distinct-calibrations", action="store_true", help="every stream a camera of its own calibration")
+    ap.add_argument("--front-end-times", action="store_true", help="a second pass with stage timers: undistortion and warp per tick")
     a = ap.parse_args()
     plan = [("1280x720", calib.reference_calibration(), [int(v) for v in a.ks.split(",") if v]),
             ("1920x1080", calib.scaled_calibration(1.5), [int(v) for v in a.ks_1080p.split(",") if v])]
@@ -91,7 +120,9 @@ def main():
         pool = pool_frames(cal)
         one_solo = None
         for k in ks:
-            gw, gc, times = run_group(cal, pool, k, a.ticks, a.warmup)
+            stages = dict(front_end=a.front_end_times)
+            gw, gc, times = run_group(cal, pool, k, a.ticks, a.warmup, a.distinct_calibrations, stages)
+            stages.pop("front_end")
             n = k * a.ticks
             sw, sc = run_solo(cal, pool, k, a.ticks, a.warmup) if not a.no_solo else (float("nan"), float("nan"))
             solo_fps = n / sw
@@ -100,7 +131,7 @@ def main():
             line = dict(tool="group_throughput", size=size, k=k, ticks=a.ticks, group_fps=round(n / gw, 1),
                         tick_ms_median=round(float(np.median(times)) * 1e3, 3), tick_ms_p99=round(float(np.percentile(times, 99)) * 1e3, 3),
                         solo_fps=round(solo_fps, 1), group_cpu_s_per_frame=round(gc / n, 6), solo_cpu_s_per_frame=round(sc / n, 6),
-                        vs_one_solo=None if one_solo is None else round(n / gw / one_solo, 2))
+                        vs_one_solo=None if one_solo is None else round(n / gw / one_solo, 2), **stages)
             s = json.dumps(line)
             print(s, flush=True)
             if out:
