@@ -57,7 +57,8 @@ extern "C" {
  *    panes of listed frames, painted on the device), lt_calib_split_panes_size, lt_resize_linear_u8; lt_rgb_to_surfaces + lt_overlay_store_device +
  *    lt_overlay_store_wait (annotated frames written into the caller's device surfaces, RGB, NV12 or I420); lt_add_calibration +
  *    lt_calibration_count + lt_set_slot_calibrations + lt_get_slot_calibrations + lt_overlay_configure_set (several calibrations in
- *    one context, one per slot: the cameras of a LaneTrackerGroup).  Nothing removed or changed. */
+ *    one context, one per slot: the cameras of a LaneTrackerGroup); lt_inplace_text + lt_overlay_run_inplace +
+ *    lt_overlay_run_inplace_coeffs (lane and text drawn into the attached camera surfaces themselves).  Nothing removed or changed. */
 #define LT_ABI_VERSION 5
 
 typedef enum lt_status {
@@ -557,8 +558,8 @@ int  lt_download_overlay_wait(lt_ctx* ctx);
  * Every destination plane is checked on the host BEFORE anything is launched, by the rules of lt_attach_device_frames: device
  * memory of that device, known to this runtime, its whole extent -- pitch * (rows - 1) + row bytes -- inside one allocation,
  * pitches at least a row wide and below 2^23; width and height even for 4:2:0; no two planes of a call sharing a byte; and for a
- * context no destination sharing a byte with a camera surface attached to any of its slots (annotating a decoder's surface in place
- * is not supported; a slot stays attached until an upload of camera rows detaches it).  Anything else is LT_ERR_INVALID with a
+ * context no destination sharing a byte with a camera surface attached to any of its slots (a sink is never the input: drawing in
+ * place is lt_overlay_run_inplace's; a slot stays attached until an upload of camera rows or an in-place draw detaches it).  Anything else is LT_ERR_INVALID with a
  * message; a slot that holds only row runs of its annotated frame is LT_ERR_STATE (as for lt_download_overlay); nothing is launched
  * and the context is as it was.  Only bytes inside a row of a plane are ever written: what lies between rows and around planes
  * stays the caller's.
@@ -576,6 +577,43 @@ int  lt_rgb_to_surfaces(int device, const void* rgb, size_t frame_stride, int h,
                         const int32_t coeffs[8]);
 int  lt_overlay_store_device(lt_ctx* ctx, int first_slot, int n, const lt_device_surface* dst, int layout, const int32_t coeffs[8]);
 int  lt_overlay_store_wait(lt_ctx* ctx);
+/* ---- annotated frames IN the caller's camera surfaces ------------------------------------------------------------------------
+ * The third destination: the surfaces attached to the slots (lt_attach_device_frames) themselves.  An annotated frame differs from
+ * its camera frame only where the lane polygon lands -- rows lt_overlay_rows, the green byte -- and under the text lines; the
+ * kernels visit those rows only, read the surface where it lies and store only what changed.  There is no destination argument: in
+ * place means the input.  RGB, NV12 and I420 contexts, by lt_attach_device_frames' rules (any pitch, any alignment, planes anywhere;
+ * 4-byte aligned RGB / 8-byte aligned 4:2:0 geometry takes the wide kernels).
+ *   RGB surface    every pixel becomes what lt_overlay_run + lt_overlay_text would have drawn; only bytes of pixels that change
+ *                  are written; nothing between rows or around the plane.
+ *   4:2:0 surface  with C = the camera frame as RGB (the context's input matrix) and A = C with lane and text drawn: Y of pixel p
+ *                  becomes luma(A(p)) where A(p) != C(p); the (U, V) of a 2 x 2 block become chroma(A(top-left pixel)) where that
+ *                  pixel changed -- the bytes lt_overlay_store_device would write there (rgb2yuv[8] as its coeffs; not read by an RGB
+ *                  context).  Every other byte keeps what the decoder wrote: YUV -> RGB -> YUV is not the identity, and it is
+ *                  applied to nothing that was not drawn on.  A block under both the lane and the text is converted once, drawn on
+ *                  twice, converted back once.
+ * text: NULL or n_lines <= 0 for none; else n_lines * line_len bytes per slot (NUL-padded) as for lt_overlay_text, the first line's
+ * top left at (x0, y0), `step` rows between lines -- at least the glyph height (LT_ERR_INVALID); characters behind a line's first
+ * NUL are not drawn.  Needs lt_overlay_set_font.
+ *   lt_overlay_run_inplace         the lanes as plot points (lt_overlay_run's arguments)
+ *   lt_overlay_run_inplace_coeffs  the lanes as averaged coefficients (lt_overlay_run_strip_coeffs' arguments; LT_ERR_STATE where
+ *                                  that form does not exist)
+ * Refusals, all before anything is staged or launched (the context and the surfaces are as they were): LT_ERR_STATE for a slot
+ * that is not attached or whose calibration set's overlay is not configured; LT_ERR_INVALID for bad point lists, missing or
+ * oversized rgb2yuv (4:2:0), a NULL text or overlapping lines.
+ * Enqueued on the presentation stream, behind the front end of exactly these slots: the undistortion lt_mask_run enqueued for a
+ * frame has read the surface before a byte of it changes.  Returns without waiting; lt_overlay_store_wait and lt_sync cover these
+ * draws as they cover lt_overlay_store_device's stores -- the surfaces are final, and the caller's again, when one has returned.
+ * Afterwards the slots are DETACHED and marked: their surfaces hold no camera frame any more.  lt_mask_rerun still works (the
+ * planes of the front end came from the original pixels); lt_mask_run and lt_device_frames_rest over such a slot are LT_ERR_STATE
+ * until an attach or an upload brings a new frame; a later lt_overlay_store_device may write into the surface. */
+typedef struct lt_inplace_text {
+    const char* lines;
+    int32_t n_lines, line_len, x0, y0, step;
+} lt_inplace_text;
+int  lt_overlay_run_inplace(lt_ctx* ctx, int first_slot, int n, const int32_t* left_n, const int32_t* right_n, const int32_t* left_yx,
+                            const int32_t* right_yx, double alpha, const lt_inplace_text* text, const int32_t rgb2yuv[8]);
+int  lt_overlay_run_inplace_coeffs(lt_ctx* ctx, int first_slot, int n, const double* coeffs, const uint8_t* draw, const double* ploty,
+                                   const double* ploty2, int n_rows, double alpha, const lt_inplace_text* text, const int32_t rgb2yuv[8]);
 /* How lt_download_overlay_async moves the frames: 0 = the copy engine, 1 = a kernel storing into the (page-locked, 16-byte
  * aligned) destination, -1 (default) = chosen by measurement: every copy is timed, the engine is used while its copies
  * reach ~42 GB/s, otherwise whichever of the two measures faster (the engine's rate depends on how the process's memory

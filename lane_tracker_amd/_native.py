@@ -238,6 +238,8 @@ _SIGNATURES = {
     "lt_rgb_to_surfaces": (C.c_int, [C.c_int, _P, C.c_size_t, C.c_int, C.c_int, C.c_int, _P, C.c_int, _P]),
     "lt_overlay_store_device": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P]),
     "lt_overlay_store_wait": (C.c_int, [_P]),
+    "lt_overlay_run_inplace": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_double, _P, _P]),
+    "lt_overlay_run_inplace_coeffs": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.c_double, _P, _P]),
     "lt_add_calibration": (C.c_int, [_P, C.POINTER(Calib), C.POINTER(C.c_int)]),
     "lt_calibration_count": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "lt_set_slot_calibrations": (C.c_int, [_P, C.c_int, C.c_int, _P]),
@@ -254,6 +256,11 @@ YUV_MATRICES = {"bt601": (1220542, 1673527, -852492, -409993, 2116026),
 # ... and the way out, RGB -> YUV 4:2:0 {CRY, CGY, CBY, CRU, CGU, CBU, CGV, CBV} (LT_RGB2YUV_BT601 / _BT709)
 RGB2YUV_MATRICES = {"bt601": (269484, 528482, 102760, -155188, -305135, 460324, -385875, -74448),
                     "bt709": (191455, 644067, 65019, -105533, -355018, 460551, -418321, -42230)}
+
+
+class InplaceText(C.Structure):
+    """lt_inplace_text: the text lines of an in-place draw."""
+    _fields_ = [("lines", C.c_char_p), ("n_lines", C.c_int32), ("line_len", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("step", C.c_int32)]
 
 
 def rgb2yuv_coeffs(matrix):
@@ -1031,8 +1038,62 @@ class Context:
         _check(self.lib.lt_overlay_store_device(self._h, int(first), s.shape[0], s.ctypes.data, layout, None if k is None else k.ctypes.data))
         return sink
 
+    def _inplace_tail(self, n, lines_per_slot, origin, step, line_len, matrix):
+        """-> (what keeps the arguments alive, the address of the lt_inplace_text or None, the address of the eight integers or None)."""
+        text, keep = None, []
+        if lines_per_slot is not None:
+            if len(lines_per_slot) != n:
+                raise ValueError("one list of text lines per slot")
+            buf, nl = text_bytes(lines_per_slot, line_len)
+            if nl:
+                t = InplaceText(buf, nl, int(line_len), int(origin[0]), int(origin[1]), int(step))
+                keep += [buf, t]
+                text = C.addressof(t)
+        k = None
+        if pixel_format_id(self.input_format()[0]):
+            if matrix is None:
+                raise ValueError("drawing into 4:2:0 surfaces needs an RGB -> YUV matrix ('bt601', 'bt709' or eight integers)")
+            k = rgb2yuv_coeffs(matrix)
+            keep.append(k)
+        return keep, text, None if k is None else k.ctypes.data
+
+    def overlay_run_inplace_packed(self, ln, rn, lyx, ryx, first=0, alpha=0.3, lines=None, origin=(20, 8), step=35, line_len=40,
+                                   matrix="bt601"):
+        """Lane and text drawn INTO the surfaces attached to slots first .. (lt_overlay_run_inplace): the polygons packed as for
+        overlay_run_packed, `lines` None or one list of strings per slot, `matrix` the RGB -> YUV matrix of a 4:2:0 context (not
+        read by an RGB one).  Only enqueued: the surfaces are final after store_wait() or sync().  The slots are detached."""
+        ln, rn = np.ascontiguousarray(ln, np.int32), np.ascontiguousarray(rn, np.int32)
+        lyx, ryx = np.ascontiguousarray(lyx, np.int32), np.ascontiguousarray(ryx, np.int32)
+        if len(rn) != len(ln) or lyx.size != 2 * int(ln.sum()) or ryx.size != 2 * int(rn.sum()):
+            raise ValueError("point lists do not match their counts")
+        keep, text, k = self._inplace_tail(len(ln), lines, origin, step, line_len, matrix)
+        _check(self.lib.lt_overlay_run_inplace(self._h, int(first), len(ln), ln.ctypes.data, rn.ctypes.data, lyx.ctypes.data if lyx.size else None,
+                                               ryx.ctypes.data if ryx.size else None, float(alpha), text, k))
+
+    def overlay_run_inplace(self, polygons, first=0, **kw):
+        """overlay_run_inplace_packed for one (left_y, left_x, right_y, right_x) tuple per slot (empty arrays: no lane)."""
+        self.overlay_run_inplace_packed(*pack_polygons(polygons), first=first, **kw)
+
+    def inplace_coeffs_available(self, n_rows):
+        """Does overlay_run_inplace_coeffs exist for this context and this many plot rows (the limits of lt_overlay_run_strip_coeffs)?"""
+        bh = self.warp_h
+        return n_rows >= 1 and bh % 2 == 0 and bh * 4 >= 56 and (2 * bh + 2 * int(n_rows)) * 4 <= 60 * 1024
+
+    def overlay_run_inplace_coeffs(self, coeffs, draw, ploty, ploty2, first=0, alpha=0.3, lines=None, origin=(20, 8), step=35, line_len=40,
+                                   matrix="bt601"):
+        """overlay_run_inplace_packed from the lanes' averaged coefficients (lt_overlay_run_inplace_coeffs): coeffs (n, 6) f64, draw
+        (n,) u8 (0: no lane in that frame); plot points and polygon intervals are formed on the device."""
+        coeffs = np.ascontiguousarray(coeffs, np.float64).reshape(-1, 6)
+        draw = np.ascontiguousarray(draw, np.uint8)
+        if len(draw) != len(coeffs):
+            raise ValueError("one draw byte per frame")
+        ploty, ploty2 = np.ascontiguousarray(ploty, np.float64), np.ascontiguousarray(ploty2, np.float64)
+        keep, text, k = self._inplace_tail(len(coeffs), lines, origin, step, line_len, matrix)
+        _check(self.lib.lt_overlay_run_inplace_coeffs(self._h, int(first), len(coeffs), coeffs.ctypes.data, draw.ctypes.data, ploty.ctypes.data,
+                                                      ploty2.ctypes.data, len(ploty), float(alpha), text, k))
+
     def store_wait(self):
-        """Block until every store_overlay_device so far has landed -- and for nothing else."""
+        """Block until every store_overlay_device and every overlay_run_inplace so far has landed -- and for nothing else."""
         _check(self.lib.lt_overlay_store_wait(self._h))
 
     def download_overlay_wait(self):

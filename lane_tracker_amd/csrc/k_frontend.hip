@@ -29,6 +29,7 @@
 
 #include "front_arith.h"
 #include "lt_internal.h"
+#include "yuv_arith.h"
 
 namespace lt {
 namespace {
@@ -54,24 +55,11 @@ __device__ __forceinline__ uint32_t xcd_block(uint32_t lid, uint32_t total, int 
 }
 
 // ---- YUV 4:2:0 input ------------------------------------------------------------------------------------------------------
-// OpenCV's 8-bit YUV -> RGB: 20-bit fixed point in int32, one (U, V) pair per 2 x 2 block, no chroma interpolation.  The
-// coefficients are below 2^23 in magnitude and the samples are 9-bit, so every product is a v_mul_i32_i24 / v_mad_i32_i24
-// whose low 32 bits are the exact product (the note on __mul24 above): no quarter-rate multiply and no table.
-struct Chroma { int r, g, b; };      // the three chroma terms of a (U, V) pair, rounding constant included
-__device__ __forceinline__ Chroma yuv_chroma(int u, int v, const YuvCoef& k) {
-    u -= 128;
-    v -= 128;
-    return Chroma{__mul24(k.cvr, v) + (1 << 19), __mul24(k.cvg, v) + __mul24(k.cug, u) + (1 << 19), __mul24(k.cub, u) + (1 << 19)};
-}
-// clamp(v >> 20, 0, 255), written clamp first: "shift right, clamp to 0..255" of two values packed into one word is what hipcc
-// turns into v_ashr_pk_u8_i32 (DESIGN.md "Toolchain cases"; tests/test_isa_guards.py), and it did in the row conversion
-__device__ __forceinline__ int clamp_sh20(int v) { return min(max(v, 0), (256 << 20) - 1) >> 20; }
-// -> R | G << 8 | B << 16
-__device__ __forceinline__ uint32_t yuv_pixel(int yy, const Chroma& c, const YuvCoef& k) {
-    // (cy is positive and below 2^23: the mask says so to the compiler, which otherwise widens this one to v_mul_lo_u32)
-    const int y = (int)__umul24((uint32_t)max(yy - 16, 0), (uint32_t)k.cy & 0x7fffffu);
-    return (uint32_t)clamp_sh20(y + c.r) | ((uint32_t)clamp_sh20(y + c.g) << 8) | ((uint32_t)clamp_sh20(y + c.b) << 16);
-}
+// OpenCV's 8-bit YUV -> RGB, one (U, V) pair per 2 x 2 block, no chroma interpolation: yuv_arith.h (shared with k_inplace.hip and
+// compiled for the host by the CPU tests).
+using ya::Chroma;
+using ya::yuv_chroma;
+using ya::yuv_pixel;
 
 // ---- the undistortion walk --------------------------------------------------------------------------------------------------
 // One thread per undistorted pixel, walking the frames of its launch slice with one remap-table entry; the output is one RGBX

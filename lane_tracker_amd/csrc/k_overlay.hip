@@ -13,28 +13,12 @@
 #include <algorithm>
 #include <cstring>
 #include "lt_internal.h"
+#include "overlay_lane.h"
 
 namespace lt {
 namespace {
 
-__device__ __forceinline__ int tap_in(const short2* __restrict__ spans, int bh, int bw, int x, int y) {
-    const short2 s = spans[min(max(y, 0), bh - 1)];
-    return (y >= 0 && y < bh && x >= 0 && x < bw && x >= s.x && x <= s.y) ? 255 : 0;
-}
-
-__device__ __forceinline__ int lane_value(const short2* __restrict__ spans, int bh, int bw, int sx, int sy, int f) {
-    const int fx = f & 31, fy = f >> 5, gx = 32 - fx, gy = 32 - fy;
-    const int v00 = tap_in(spans, bh, bw, sx, sy), v01 = tap_in(spans, bh, bw, sx + 1, sy);
-    const int v10 = tap_in(spans, bh, bw, sx, sy + 1), v11 = tap_in(spans, bh, bw, sx + 1, sy + 1);
-    const int h0 = __mul24(v00, gx) + __mul24(v01, fx), h1 = __mul24(v10, gx) + __mul24(v11, fx);
-    return (__mul24(h0, gy) + __mul24(h1, fy) + 512) >> 10;      // == (sum w_i v_i + 2^14) >> 15
-}
-
-__device__ __forceinline__ uint32_t blend_green(uint32_t g, int lane, float alpha) {
-    const float t = __fadd_rn((float)g, __fmul_rn((float)lane, alpha));   // no fma: cv::addWeighted rounds the product
-    const int r = (int)rintf(t);
-    return (uint32_t)min(max(r, 0), 255);
-}
+// tap_in, lane_value, blend_green: overlay_lane.h (shared with k_inplace.hip)
 
 // One thread per camera pixel; `spans` = (lo, hi) int16 per bird's-eye row of this slot.
 __global__ __launch_bounds__(256) void k_overlay_lane(const uint8_t* __restrict__ frames, uint8_t* __restrict__ out,

@@ -187,6 +187,7 @@ void free_slots(lt_ctx* c) {
     dev_free(c->d_surf);
     c->surf.clear();
     c->attached.clear();
+    c->drawn.clear();
     dev_free(c->d_bev);
     c->masks.release();
     c->mask_bits_ok.clear();
@@ -259,6 +260,7 @@ static void front_stale(lt_ctx* c, int first, int n) {      // new camera rows i
 // an upload of camera rows into these slots: their front end reads the slots' own frames again (lt_attach_device_frames)
 static void detach_slots(lt_ctx* c, int first, int n) {
     for (int i = first; i < first + n && i < (int)c->attached.size(); ++i) c->attached[(size_t)i] = 0;
+    for (int i = first; i < first + n && i < (int)c->drawn.size(); ++i) c->drawn[(size_t)i] = 0;
 }
 void mark_annot(lt_ctx* c, int first, int n, int full) {
     for (int i = first; i < first + n && i < (int)c->annot_full.size(); ++i) c->annot_full[(size_t)i] = (uint8_t)full;
@@ -1347,6 +1349,7 @@ int lt_attach_device_frames(lt_ctx* c, const lt_device_surface* surfaces, int fi
     for (int i = 0; i < n; ++i) {
         c->surf[(size_t)(first + i)] = ent[(size_t)i];
         c->attached[(size_t)(first + i)] = 1;
+        if ((size_t)(first + i) < c->drawn.size()) c->drawn[(size_t)(first + i)] = 0;
     }
     // The entries go into the table on the slots' own streams: behind everything launched over these slots there (the front end
     // that reads their previous entries) and ahead of whatever is launched next -- and behind readers on other streams.
@@ -1363,7 +1366,9 @@ int lt_device_frames_rest(lt_ctx* c, int first, int n, const int32_t* rows4) {
     int rc = check_slots(c, first, n);
     if (rc) return rc;
     for (int i = first; i < first + n; ++i)
-        if (i >= (int)c->attached.size() || !c->attached[(size_t)i]) return fail(LT_ERR_STATE, "slot %d has no device frame attached", i);
+        if (i >= (int)c->attached.size() || !c->attached[(size_t)i])
+            return fail(LT_ERR_STATE, i < (int)c->drawn.size() && c->drawn[(size_t)i] ? "slot %d: its surface was drawn into in place (lt_overlay_run_inplace) and holds no camera frame any more"
+                                                                                      : "slot %d has no device frame attached", i);
     const int H = c->calib.img_h;
     if (rows4 && !(0 <= rows4[0] && rows4[0] <= rows4[1] && rows4[1] <= rows4[2] && rows4[2] <= rows4[3] && rows4[3] <= H))
         return fail(LT_ERR_INVALID, "row runs must be ordered and inside the frame");
@@ -2019,6 +2024,16 @@ static int mask_run_impl(lt_ctx* c, int first, int n, const lt_filter_params* p,
     if ((rc = validate_filter(p))) return rc;
     if ((rc = set_device(c))) return rc;
     if (n == 0) return LT_OK;
+    // A slot whose surface lt_overlay_run_inplace has drawn into holds no camera frame: only a re-run over planes that are all
+    // there is possible (a front end would read the slot's own, stale frame).
+    for (int i = first; i < first + n && i < (int)c->drawn.size(); ++i) {
+        if (!c->drawn[(size_t)i]) continue;
+        bool planes = reuse_front && !c->stage_timing && first + n <= (int)c->front_ok.size();
+        for (int j = first; planes && j < first + n; ++j) planes = c->front_ok[(size_t)j] != 0;
+        if (!planes)
+            return fail(LT_ERR_STATE, "slot %d: its surface was drawn into in place (lt_overlay_run_inplace) and holds no camera frame any more: attach or upload one first", i);
+        break;
+    }
     const size_t ps = c->masks.plane_bytes;
     const ChainEnv env = chain_env(c);
     rc = for_each_slice(c, first, n, [&](hipStream_t st, int f0, int m) {

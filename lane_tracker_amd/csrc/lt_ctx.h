@@ -156,6 +156,10 @@ struct lt_ctx {
     lt::SurfEntry* d_surf = nullptr;
     std::vector<lt::SurfEntry> surf;
     std::vector<uint8_t> attached;
+    // per slot: lt_overlay_run_inplace has drawn into the surface that was attached -- it holds no camera frame any more, and the slot
+    // none of its own.  The planes of its front end are still the original pixels' (lt_mask_rerun works); a front end over it is
+    // refused until an attach or an upload brings a frame.
+    std::vector<uint8_t> drawn;
     uint32_t* d_und = nullptr;        // undistorted camera rows [r0, r0+nrows), one RGBX dword per pixel, slots 2p / 2p+1 interleaved (und_slot_base)
     size_t und_px = 0;                // pixels per slot of d_und
     lt::MaskArena masks;              // the mask chain's device memory, one block of each kind for the whole capacity

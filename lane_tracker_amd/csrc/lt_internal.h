@@ -10,6 +10,7 @@
 #include <cstdlib>
 
 #include "../../include/lane_tracker_amd.h"
+#include "yuv_arith.h"
 
 // Measurement switches -- alternative kernels and launch shapes for A/B runs, each held bit-exact by the parity suite -- exist in
 // the EXPERIMENTS build only (`make EXPERIMENTS=1` -> liblane_tracker_amd_exp.so, -DLT_EXPERIMENTS; tools/* and
@@ -55,11 +56,7 @@ inline size_t und_slot_base(size_t und_px, int slot) { return (size_t)(slot >> 1
 void launch_warp_split(hipStream_t s, const uint32_t* und, size_t und_px, int first_slot, const int16_t* wxy,
                        const uint16_t* wfrac, FrontEndGeom g, const uint16_t* gamma_tab, const uint16_t* cbrt_tab,
                        const int32_t* coeffs, bool lab_clamp_dead, uint8_t* planeR, uint8_t* planeB, size_t plane_stride, int n);
-// YUV 4:2:0 input (lt_set_input_format): the five 20-bit fixed-point coefficients of the conversion, each below 2^23 in
-// magnitude (checked where they enter), so that every product with a 9-bit sample is one 24-bit multiply
-struct YuvCoef {
-    int32_t cy, cvr, cvg, cug, cub;
-};
+// (YuvCoef, the five coefficients of the YUV 4:2:0 input's conversion: yuv_arith.h)
 // rows [r0, r1) of n 4:2:0 frames of h x w (h, w even) -> the same rows of n RGB frames
 void launch_yuv_rows_to_rgb(hipStream_t s, int layout, const uint8_t* yuv, size_t yuv_stride, YuvCoef k, uint8_t* rgb,
                             size_t rgb_stride, int h, int w, int r0, int r1, int n);
@@ -122,6 +119,28 @@ void launch_surf_rows_to_rgb(hipStream_t s, int layout, const SurfEntry* entries
 // `layout`: a pitched copy (RGB) or a conversion with coeffs[8] (4:2:0; h and w even; sink_arith.h), 32 surfaces per launch
 void launch_rgb_to_surfaces(hipStream_t s, int layout, const uint8_t* rgb, size_t rgb_stride, int h, int w, const SurfEntry* entries,
                             int n, const int32_t* coeffs);
+// drawing into attached surfaces (k_inplace.hip).  The lane: the inverse-warp tables of the launch's calibration set and the row
+// intervals of its first slot (span_stride_rows rows of (lo, hi) per slot); the text (nl == 0: none): glyph atlas, and the lines
+// and character positions of the launch's first slot (slot_chars per slot); the rows: two disjoint runs [a0, a0 + an), [b0, b0 + bn).
+struct InplaceLane {
+    const int16_t* oxy;
+    const uint16_t* ofrac;
+    const int16_t* spans;
+    size_t span_stride_rows;
+    int bh, bw;
+    float alpha;
+};
+struct InplaceText {
+    const uint8_t *atlas, *advance, *lines;
+    const int16_t* xpos;
+    int first_char, n_glyphs, gw, gh, nl, len, slot_chars, y0, step;
+};
+struct InplaceRows { int a0, an, b0, bn; };
+// Lane and text into n surfaces in `layout`: tab[0, n) (device memory: the context's table from the launch's first slot), whose host
+// mirror entries[0, n) decides the kernel (alignment).  rows4 = two runs of camera rows {a0, a1, b0, b1} outside which nothing can
+// change (they may overlap or be empty).  kin / rgb2yuv[8]: 4:2:0 only.
+void launch_inplace(hipStream_t s, int layout, const SurfEntry* tab, const SurfEntry* entries, int n, int h, int w, const int rows4[4],
+                    InplaceLane l, InplaceText t, YuvCoef kin, const int32_t* rgb2yuv);
 void launch_split_bev(hipStream_t s, const uint8_t* bev, size_t bev_stride, int npix, const uint16_t* gamma_tab,
                       const uint16_t* cbrt_tab, const int32_t* coeffs, uint8_t* planeR, uint8_t* planeB,
                       size_t plane_stride, int n);

@@ -19,6 +19,7 @@
 #include <hip/hip_ext.h>
 
 #include "lt_ctx.h"
+#include "sink_arith.h"
 
 using namespace lt;
 
@@ -361,6 +362,38 @@ static int ensure_ploty(lt_ctx* c, const double* ploty, const double* ploty2, in
 // averaged coefficients instead of points (lt_overlay_run_strip_coeffs): the device forms plot points and row intervals itself
 struct CoeffInput { const double* coeffs; const uint8_t* draw; const double* ploty; const double* ploty2; int n_rows; };
 
+// What the overlay's kernels find in a piece's interval regions (hs: n regions of bh (lo, hi) pairs, page-locked staging or the
+// caller's): the polygons' row intervals, or -- coefficients form -- six doubles and a draw byte at the start of every region.
+static void fill_span_staging(int16_t* hs, int bh, int n, const int32_t* left_n, const int32_t* right_n, const int32_t* left_yx,
+                              const int32_t* right_yx, const CoeffInput* ci) {
+    // ~18 us of edge walking per polygon: a window's piece of 32 .. 128 polygons is shared among a few threads (the caller is
+    // the one thread that feeds the device)
+    const int workers = std::max(1, std::min({n / 8, 8, (int)std::thread::hardware_concurrency()}));
+    auto some = [&](int w) {
+        size_t ol = 0, orr = 0;
+        for (int i = 0; i < n; ++i) {
+            if (i * (long long)workers / n == w)
+                lane_polygon_spans(hs + (size_t)i * bh * 2, bh, left_yx ? left_yx + 2 * ol : nullptr, left_n[i],
+                                   right_yx ? right_yx + 2 * orr : nullptr, right_n[i]);
+            ol += (size_t)left_n[i];
+            orr += (size_t)right_n[i];
+        }
+    };
+    if (ci) {                                  // six doubles and a draw byte at the start of every slot's interval region
+        for (int i = 0; i < n; ++i) {
+            uint8_t* reg = reinterpret_cast<uint8_t*>(hs + (size_t)i * bh * 2);
+            std::memcpy(reg, ci->coeffs + (size_t)6 * i, 6 * sizeof(double));
+            reg[48] = ci->draw ? ci->draw[i] : 1;
+        }
+    } else if (workers == 1) some(0);
+    else {
+        std::vector<std::thread> pool;
+        for (int w = 1; w < workers; ++w) pool.emplace_back(some, w);
+        some(0);
+        for (auto& t : pool) t.join();
+    }
+}
+
 static int overlay_run_impl(lt_ctx* c, int first, int n, const int32_t* left_n, const int32_t* right_n, const int32_t* left_yx,
                             const int32_t* right_yx, double alpha, const int* rows4, bool strip = false, uint8_t* direct_out = nullptr,
                             bool* went_direct = nullptr, const CoeffInput* ci = nullptr) {
@@ -409,32 +442,7 @@ static int overlay_run_impl(lt_ctx* c, int first, int n, const int32_t* left_n, 
     int16_t* hs = one ? one_spans : c->h_spans + (size_t)first * bh * 2;
     static const bool timing = LT_EXP_ENV("LT_OVERLAY_TIMING") != nullptr;
     const auto t0 = std::chrono::steady_clock::now();
-    // ~18 us of edge walking per polygon: a window's piece of 32 .. 128 polygons is shared among a few threads (the caller is
-    // the one thread that feeds the device)
-    const int workers = std::max(1, std::min({n / 8, 8, (int)std::thread::hardware_concurrency()}));
-    auto some = [&](int w) {
-        size_t ol = 0, orr = 0;
-        for (int i = 0; i < n; ++i) {
-            if (i * (long long)workers / n == w)
-                lane_polygon_spans(hs + (size_t)i * bh * 2, bh, left_yx ? left_yx + 2 * ol : nullptr, left_n[i],
-                                   right_yx ? right_yx + 2 * orr : nullptr, right_n[i]);
-            ol += (size_t)left_n[i];
-            orr += (size_t)right_n[i];
-        }
-    };
-    if (ci) {                                  // six doubles and a draw byte at the start of every slot's interval region
-        for (int i = 0; i < n; ++i) {
-            uint8_t* reg = reinterpret_cast<uint8_t*>(hs + (size_t)i * bh * 2);
-            std::memcpy(reg, ci->coeffs + (size_t)6 * i, 6 * sizeof(double));
-            reg[48] = ci->draw ? ci->draw[i] : 1;
-        }
-    } else if (workers == 1) some(0);
-    else {
-        std::vector<std::thread> pool;
-        for (int w = 1; w < workers; ++w) pool.emplace_back(some, w);
-        some(0);
-        for (auto& t : pool) t.join();
-    }
+    fill_span_staging(hs, bh, n, left_n, right_n, left_yx, right_yx, ci);
     // the rows of the frame the path does not read came on the copy stream (lt_upload_frame_rest): the overlay is their reader
     const auto t1 = std::chrono::steady_clock::now();
     if ((rc = present_stream(c))) return rc;
@@ -621,14 +629,12 @@ int lt_overlay_set_font(lt_ctx* c, const uint8_t* atlas, const uint8_t* advance,
     return LT_OK;
 }
 
-int lt_overlay_text(lt_ctx* c, int first, int n, const char* lines, int n_lines, int line_len, int x0, int y0, int step) {
-    int rc = check_slots(c, first, n);
-    if (rc) return rc;
-    if (!c->font_glyphs) return fail(LT_ERR_STATE, "lt_overlay_text before lt_overlay_set_font");
-    if (!c->d_annot) return fail(LT_ERR_STATE, "lt_overlay_text before lt_overlay_run");
-    if (n == 0 || n_lines <= 0 || line_len <= 0) return LT_OK;
-    if (!lines) return fail(LT_ERR_INVALID, "null text");
-    if ((rc = set_device(c))) return rc;
+// The text lines of slots [first, first + n) into the per-slot text buffers, and where a kernel on the presentation stream finds
+// them: *kl / *kx = the lines and the left edges of their characters of slot `first`, `*stride` characters per slot.  The caller
+// launches its kernel and then marks the staging busy (staging_mark(c->text_busy, c->present)).
+static int stage_text(lt_ctx* c, int first, int n, const char* lines, int n_lines, int line_len, int x0, const uint8_t** kl_out,
+                      const int16_t** kx_out, size_t* stride_out, bool may_read_host = true) {
+    int rc;
     const size_t per = (size_t)n_lines * line_len;
     if (per > c->text_per_slot || c->text_slots < c->capacity) {      // (re)size the per-slot text buffers: rare, synchronises
         if ((rc = sync_all(c))) return rc;
@@ -680,7 +686,7 @@ int lt_overlay_text(lt_ctx* c, int first, int n, const char* lines, int n_lines,
     const int16_t* kx = dx;
     void *pl = nullptr, *px = nullptr;
     static const bool direct_ok = [] { const char* e = LT_EXP_ENV("LT_TEXT_DIRECT"); return !(e && e[0] == '0'); }();
-    if (direct_ok && n <= 2 && hipHostGetDevicePointer(&pl, hl, 0) == hipSuccess && hipHostGetDevicePointer(&px, hx, 0) == hipSuccess &&
+    if (direct_ok && may_read_host && n <= 2 && hipHostGetDevicePointer(&pl, hl, 0) == hipSuccess && hipHostGetDevicePointer(&px, hx, 0) == hipSuccess &&
         pl && px) {
         kl = static_cast<const uint8_t*>(pl);
         kx = static_cast<const int16_t*>(px);
@@ -689,11 +695,149 @@ int lt_overlay_text(lt_ctx* c, int first, int n, const char* lines, int n_lines,
         launch_copy_from_pinned(c->present, dl, hl, (size_t)n * stride);
         launch_copy_from_pinned(c->present, dx, hx, (size_t)n * stride * sizeof(int16_t));
     }
+    *kl_out = kl;
+    *kx_out = kx;
+    *stride_out = stride;
+    return LT_OK;
+}
+
+int lt_overlay_text(lt_ctx* c, int first, int n, const char* lines, int n_lines, int line_len, int x0, int y0, int step) {
+    int rc = check_slots(c, first, n);
+    if (rc) return rc;
+    if (!c->font_glyphs) return fail(LT_ERR_STATE, "lt_overlay_text before lt_overlay_set_font");
+    if (!c->d_annot) return fail(LT_ERR_STATE, "lt_overlay_text before lt_overlay_run");
+    if (n == 0 || n_lines <= 0 || line_len <= 0) return LT_OK;
+    if (!lines) return fail(LT_ERR_INVALID, "null text");
+    if ((rc = set_device(c))) return rc;
+    const uint8_t* kl = nullptr;
+    const int16_t* kx = nullptr;
+    size_t stride = 0;
+    if ((rc = stage_text(c, first, n, lines, n_lines, line_len, x0, &kl, &kx, &stride))) return rc;
     launch_overlay_text(c->present, c->d_annot + (size_t)first * c->frame_bytes, c->frame_bytes, c->calib.img_h, c->calib.img_w,
                         c->d_atlas, c->d_advance, c->font_first, c->font_glyphs, c->font_gw, c->font_gh, kl, kx,
                         n_lines, line_len, (int)stride, y0, step, n);
     HIP_TRY(hipGetLastError());
     return staging_mark(c->text_busy, c->present);
+}
+
+// ---- lane and text drawn into the attached surfaces themselves (k_inplace.hip) ---------------------------------------------------
+// The third destination of annotated frames, beside the host and a device sink: the camera surfaces the caller attached.  Only the
+// rows a lane can reach and the text's rows are visited, and only what changes is stored.  Everything is checked before anything
+// is allocated, staged or launched: a refused call leaves the context and the surfaces as they were.
+static int inplace_impl(lt_ctx* c, int first, int n, const int32_t* left_n, const int32_t* right_n, const int32_t* left_yx,
+                        const int32_t* right_yx, const CoeffInput* ci, double alpha, const lt_inplace_text* text, const int32_t* rgb2yuv) {
+    int rc = check_slots(c, first, n);
+    if (rc) return rc;
+    for (int i = first; i < first + n; ++i)
+        if (i >= (int)c->attached.size() || !c->attached[(size_t)i])
+            return fail(LT_ERR_STATE, "lt_overlay_run_inplace: slot %d has no device frame attached (in place means the surface the slot reads)", i);
+    for (int i = first; i < first + n; ++i)
+        if (!c->cal[(size_t)slot_set(c, i)].have_overlay)
+            return fail(LT_ERR_STATE, "lt_overlay_run_inplace before lt_overlay_configure: slot %d has calibration set %d, whose overlay is not configured", i, slot_set(c, i));
+    if (!ci) {
+        if (n > 0 && (!left_n || !right_n)) return fail(LT_ERR_INVALID, "null point counts");
+        long long tl = 0, tr = 0;
+        for (int i = 0; i < n; ++i) {
+            if (left_n[i] < 0 || right_n[i] < 0) return fail(LT_ERR_INVALID, "negative point count");
+            tl += left_n[i];
+            tr += right_n[i];
+        }
+        if ((tl && !left_yx) || (tr && !right_yx)) return fail(LT_ERR_INVALID, "null point list");
+    }
+    if (c->in_layout != LT_INPUT_RGB) {
+        if (!rgb2yuv) return fail(LT_ERR_INVALID, "drawing into a 4:2:0 surface needs the eight RGB -> YUV coefficients");
+        if (!sa::coeffs_ok(rgb2yuv))
+            return fail(LT_ERR_INVALID, "conversion coefficients must be below 2^23 in magnitude and keep every row's sum inside 32 bits");
+    }
+    const bool have_text = text && text->n_lines > 0 && text->line_len > 0;
+    if (have_text) {
+        if (!c->font_glyphs) return fail(LT_ERR_STATE, "lt_overlay_run_inplace with text before lt_overlay_set_font");
+        if (!text->lines) return fail(LT_ERR_INVALID, "null text");
+        if (text->step < c->font_gh) return fail(LT_ERR_INVALID, "text lines %d rows apart would overlap (the glyphs are %d rows high)", text->step, c->font_gh);
+    }
+    if (n == 0) return LT_OK;
+    if ((rc = set_device(c))) return rc;
+    const int bh = c->calib.warp_h, H = c->calib.img_h, W = c->calib.img_w;
+    if (!c->d_spans && (rc = dev_alloc(&c->d_spans, (size_t)c->capacity * bh * 2))) return rc;
+    if (ci && (rc = ensure_ploty(c, ci->ploty, ci->ploty2, ci->n_rows))) return rc;
+    if (!c->store_done && hipEventCreateWithFlags(&c->store_done, hipEventDisableTiming) != hipSuccess) return fail(LT_ERR_HIP, "hipEventCreate failed");
+    if ((rc = staging_claim(c->spans_busy, first, n))) return rc;
+    if ((rc = ensure_span_staging(c))) return rc;
+    int16_t* hs = c->h_spans + (size_t)first * bh * 2;
+    fill_span_staging(hs, bh, n, left_n, right_n, left_yx, right_yx, ci);
+    if ((rc = present_stream(c))) return rc;
+    hipStream_t ps = c->present;
+    InplaceText t{};
+    if (have_text) {
+        const uint8_t* kl = nullptr;
+        const int16_t* kx = nullptr;
+        size_t stride = 0;
+        // (to the device whatever n: every pixel of the text's rows searches the positions)
+        if ((rc = stage_text(c, first, n, text->lines, text->n_lines, text->line_len, text->x0, &kl, &kx, &stride, false))) return rc;
+        t = InplaceText{c->d_atlas, c->d_advance, kl, kx, c->font_first, c->font_glyphs, c->font_gw, c->font_gh, text->n_lines, text->line_len,
+                        (int)stride, text->y0, text->step};
+    }
+    // The draw changes bytes the front end of these slots reads: it waits for exactly those reads -- the undistortion of a slot's
+    // current frame was noted among the readers when lt_mask_run enqueued it (behind the write of the slot's table entry, which
+    // the kernels here read too).  A slot whose front end has not run since its attach has only that write in flight, which
+    // carries no event: the tails of the slots' streams then.
+    {
+        bool precise = true;
+        if ((rc = wait_range(c->readers, ps, first, first + n, &precise))) return rc;
+        for (int i = first; precise && i < first + n; ++i) precise = i < (int)c->front_ok.size() && c->front_ok[(size_t)i] != 0;
+        if (!precise && (rc = for_each_slice(c, first, n, [&](hipStream_t st, int, int) { return wait_tail(c, ps, st); }))) return rc;
+        if (c->rest_pending) {          // lt_device_frames_rest reads the surfaces on the copy stream
+            bool p2 = true;
+            if ((rc = wait_range(c->rests, ps, first, first + n, &p2))) return rc;
+            if (!p2) HIP_TRY(hipStreamWaitEvent(ps, c->rest_done, 0));
+        }
+    }
+    launch_copy_from_pinned(ps, c->d_spans + (size_t)first * bh * 2, hs, (size_t)n * bh * 2 * sizeof(int16_t));
+    if (ci && !launch_lane_spans_from_regions(ps, c->d_ploty, c->d_ploty + ci->n_rows, ci->n_rows, bh, c->calib.warp_w, c->d_spans + (size_t)first * bh * 2, n))
+        return fail(LT_ERR_STATE, "lt_overlay_run_inplace_coeffs: not available for this bird's-eye height");
+    // run by run over consecutive slots of one calibration set
+    for (int a = first, b; a < first + n; a = b) {
+        for (b = a + 1; b < first + n && slot_set(c, b) == slot_set(c, a); ++b) {}
+        const lt_ctx::CalSet& q = c->cal[(size_t)slot_set(c, a)];
+        const int t0 = have_text ? text->y0 : 0, t1 = have_text ? text->y0 + (text->n_lines - 1) * text->step + c->font_gh : 0;
+        const int rows4[4] = {t0, t1, q.ov_r0, q.ov_r1};
+        InplaceLane l{q.d_oxy, q.d_ofrac, c->d_spans + (size_t)a * bh * 2, (size_t)bh, bh, c->calib.warp_w, (float)alpha};
+        InplaceText ta = t;
+        if (have_text) {
+            ta.lines = t.lines + (size_t)(a - first) * t.slot_chars;
+            ta.xpos = t.xpos + (size_t)(a - first) * t.slot_chars;
+        }
+        launch_inplace(ps, c->in_layout, c->d_surf + a, &c->surf[(size_t)a], b - a, H, W, rows4, l, ta, yuv_coef_of(c), rgb2yuv);
+    }
+    HIP_TRY(hipGetLastError());
+    if ((rc = staging_mark(c->spans_busy, ps))) return rc;
+    if (have_text && (rc = staging_mark(c->text_busy, ps))) return rc;
+    if ((rc = note_range(c->readers, ps, first, first + n))) return rc;       // it reads the slots' table entries: the next attach waits
+    HIP_TRY(hipEventRecord(c->store_done, ps));
+    c->store_pending = true;
+    // The surfaces no longer hold camera frames: the slots are detached -- nothing of the library reads them again, and a later
+    // sink is not refused for overlapping them -- and marked, so that a front end over them is refused until new frames come.
+    if (c->drawn.size() < (size_t)c->capacity) c->drawn.resize((size_t)c->capacity, 0);
+    for (int i = first; i < first + n; ++i) {
+        c->attached[(size_t)i] = 0;
+        c->drawn[(size_t)i] = 1;
+    }
+    return LT_OK;
+}
+
+int lt_overlay_run_inplace(lt_ctx* c, int first, int n, const int32_t* left_n, const int32_t* right_n, const int32_t* left_yx,
+                           const int32_t* right_yx, double alpha, const lt_inplace_text* text, const int32_t* rgb2yuv) {
+    return inplace_impl(c, first, n, left_n, right_n, left_yx, right_yx, nullptr, alpha, text, rgb2yuv);
+}
+
+int lt_overlay_run_inplace_coeffs(lt_ctx* c, int first, int n, const double* coeffs, const uint8_t* draw, const double* ploty,
+                                  const double* ploty2, int n_rows, double alpha, const lt_inplace_text* text, const int32_t* rgb2yuv) {
+    if (!c || (n > 0 && !coeffs) || !ploty || !ploty2 || n_rows < 1) return fail(LT_ERR_INVALID, "lt_overlay_run_inplace_coeffs: bad arguments");
+    const int bh = c->calib.warp_h;
+    if ((bh & 1) || bh * 4 < 56 || ((size_t)2 * bh + (size_t)2 * n_rows) * sizeof(int) > 60 * 1024)
+        return fail(LT_ERR_STATE, "lt_overlay_run_inplace_coeffs: not available for this bird's-eye height");
+    const CoeffInput ci{coeffs, draw, ploty, ploty2, n_rows};
+    return inplace_impl(c, first, n, nullptr, nullptr, nullptr, nullptr, &ci, alpha, text, rgb2yuv);
 }
 
 int lt_download_overlay(lt_ctx* c, int first, int n, uint8_t* out) {

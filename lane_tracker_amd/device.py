@@ -159,13 +159,15 @@ class DeviceFrames:
     """n camera frames of `img_size` = (width, height) in `pixel_format` somewhere in device memory: a description, not an owner
     (`owner` is whatever keeps the memory alive; it is only referenced).  `surfaces` is a SURFACE_DTYPE array, one entry per
     frame: plane pointers (RGB: one; NV12: Y, UV; I420: Y, U, V), the pitch of plane 0 and the chroma pitch, in bytes.
-    `single`: made from one frame (what process() takes); `stream`: the producer's stream to wait for before the frames are read."""
+    `single`: made from one frame (what process() takes); `stream`: the producer's stream to wait for before the frames are read;
+    `readonly`: the producer said so (`__cuda_array_interface__`'s data[1]) -- such frames are never drawn into (`out="inplace"`)."""
 
-    def __init__(self, surfaces, img_size, pixel_format, owner=None, single=False, stream=None, device=0):
+    def __init__(self, surfaces, img_size, pixel_format, owner=None, single=False, stream=None, device=0, readonly=False):
         self.surfaces = surfaces
         self.img_size = (int(img_size[0]), int(img_size[1]))
         self.pixel_format = pixel_format
         self.owner, self.single, self.stream, self.device = owner, bool(single), stream, int(device)
+        self.readonly = bool(readonly)
 
     # -- construction
     @classmethod
@@ -259,7 +261,8 @@ class DeviceFrames:
             surf["plane"][:, 1] = base + np.uint64(h * w)
             surf["plane"][:, 2] = base + np.uint64(h * w + (h // 2) * (w // 2))
             surf["chroma_pitch"] = w // 2
-        return cls(surf, (w, h), pixel_format, owner=obj, single=single, stream=ai.get("stream"), device=device)
+        return cls(surf, (w, h), pixel_format, owner=obj, single=single, stream=ai.get("stream"), device=device,
+                   readonly=len(data) > 1 and bool(data[1]))
 
     @classmethod
     def from_host(cls, frames, pixel_format="rgb", pitch=None, chroma_pitch=None, offset=0, device=0):
@@ -304,7 +307,8 @@ class DeviceFrames:
             s, single = self.surfaces[idx], False
         else:
             raise TypeError("DeviceFrames take an integer or a slice, got %r" % (idx,))
-        return DeviceFrames(s, self.img_size, self.pixel_format, owner=self.owner, single=single, stream=self.stream, device=self.device)
+        return DeviceFrames(s, self.img_size, self.pixel_format, owner=self.owner, single=single, stream=self.stream, device=self.device,
+                            readonly=self.readonly)
 
     @property
     def shape(self):

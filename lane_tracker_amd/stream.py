@@ -370,7 +370,7 @@ class StreamPipeline:
                                          # under the copy of the piece before
 
         rest_rows = self._window_rows[1] if self._window_rows is not None else None   # annotated frames travel as row runs
-        rest_needed = annotate
+        rest_needed = annotate and not self._draw_inplace    # (in place: the surface is read where it lies, never copied into the slot)
         if self._window_rows is not None and self._window_rows[4] is not None:         # ... as strips: the lane's run of rows alone,
             rest_rows, rest_needed = self._window_rows[4][1], annotate and self._window_rows[4][4]   # which the mask chain has uploaded
 
@@ -592,7 +592,7 @@ class StreamPipeline:
             self._materialise_pending()      # growing the context drops what is still on the device
             ctx.reserve(regions * size)
         mode = 0
-        if annotate:
+        if annotate and not self._draw_inplace:      # (drawing into the caller's surfaces needs neither annotated frames nor strips)
             rows = self._present_rows() if (self.host_copies_rows and not self._to_sink) else None
             mode = 2 if (rows is not None and rows[4] is not None) else 1
         if mode == 2 and output_pool and annotate != "inplace":   # the pool of output frames: a window being filled, one landing, one with the caller, one to spare
@@ -627,6 +627,62 @@ class StreamPipeline:
     strip_piece = 32            # frames per overlay launch + strip download of a committed run
     _annotate_inplace = False   # annotate="inplace": annotated frames are the caller's own arrays, drawn over (strips only)
     _to_sink = False            # the annotated frames of the current call go into device sinks (`out=`): whole frames, drawn on the device
+
+    _draw_inplace = False       # the annotated frames of the current call are the DeviceFrames handed in, drawn into (`out="inplace"`)
+
+    def _inplace_matrix(self, out, out_yuv_matrix):
+        """`out` is a string: it must be "inplace".  -> the RGB -> YUV matrix the draw converts back with: `out_yuv_matrix`, or the
+        tracker's own `yuv_matrix` when that is a preset name (a custom input matrix names no matrix for the way back)."""
+        if out != "inplace":
+            raise ValueError("out= takes a DeviceFrames or 'inplace', got %r" % (out,))
+        if out_yuv_matrix is not None:
+            _native.rgb2yuv_coeffs(out_yuv_matrix)
+            return out_yuv_matrix
+        if self.pixel_format == 'rgb':
+            return 'bt601'               # (not read)
+        if not isinstance(self.yuv_matrix, str):
+            raise ValueError("out='inplace' converts back with the matrix that matches the tracker's yuv_matrix: a custom one has no "
+                             "preset counterpart, pass out_yuv_matrix (eight integers)")
+        return self.yuv_matrix
+
+    def _check_inplace_source(self, frames):
+        """`frames` (what `_as_window` made of a window) as the destination of its own annotated frames."""
+        if not isinstance(frames, DeviceFrames):
+            raise ValueError("out='inplace' draws into DeviceFrames; host arrays are drawn over with annotate='inplace'")
+        if frames.readonly:
+            raise ValueError("out='inplace' writes into the frames handed in: these DeviceFrames are read-only")
+        return frames
+
+    def _draw_in_place(self, part, first, matrix):
+        """The deferred pictures `part` into the surfaces attached to slots first ..: one call per run of one kind -- averaged
+        coefficients (`_CoeffPoly`: plot points and polygons on the device) or points -- as the strip route splits them, lane and text
+        of a frame in one pass (lt_overlay_run_inplace)."""
+        ctx = self._ctx
+        g0 = 0
+        while g0 < len(part):
+            kind, g1 = None, g0
+            while g1 < len(part):
+                d = part[g1]
+                kd = None if d[0] != 'lane' else ('c' if isinstance(d[1], _CoeffPoly) and ctx.inplace_coeffs_available(len(d[1].plot[0])) else 'p')
+                if kd is not None and kind is not None and kd != kind:
+                    break
+                kind = kind or kd
+                g1 += 1
+            run = part[g0:g1]
+            lines = [d[2] for d in run] if self._have_font else None
+            kw = dict(first=first + g0, lines=lines, origin=self._TEXT_ORIGIN, step=self._TEXT_STEP, matrix=matrix)
+            if kind == 'c':
+                first_poly = next(d[1] for d in run if d[0] == 'lane')
+                co = np.zeros((len(run), 6), np.float64)
+                dr = np.zeros(len(run), np.uint8)
+                for i, d in enumerate(run):
+                    if d[0] == 'lane':
+                        co[i] = d[1].coeffs
+                        dr[i] = 1
+                ctx.overlay_run_inplace_coeffs(co, dr, first_poly.plot[0], first_poly.plot[1], **kw)
+            else:
+                ctx.overlay_run_inplace_packed(*_pack_deferred(run), **kw)
+            g0 = g1
 
     def _sink_keywords(self, out, annotate, k):
         """ValueError for the keywords a device sink (`out=`) does not combine with."""
@@ -670,6 +726,19 @@ class StreamPipeline:
         ctx = self._ctx
         empty = np.zeros(0, np.int64)
         done = [0]
+        if self._draw_inplace:
+            # In place (`out="inplace"`): `out` IS the window, DeviceFrames -- every committed piece is drawn into the surfaces its
+            # slots are attached to (lt_overlay_run_inplace); no rest rows, no annotated frames, no store.  A frame is drawn only
+            # after it is committed, and nothing reads a committed frame's surface again: second tries and re-runs of speculative
+            # groups come before the commit and reuse the front end's planes.
+            def flush(force):
+                lo, hi = done[0], len(deferred)
+                if hi <= lo or (hi - lo < piece and not force):
+                    return
+                self._draw_in_place(deferred[lo:hi], base + lo, matrix)
+                done[0] = hi
+            flush.group = None
+            return flush, sink
         wr = self._window_rows if (frames is not None and n) else None
         H, rb, fb = ctx.img_h, ctx.img_w * 3, ctx.img_h * ctx.img_w * 3
         if wr is not None and wr[4] is not None:
@@ -776,6 +845,10 @@ class StreamPipeline:
         ctx = self._ctx
         if sink is not None and not deferred:
             return []
+        if self._draw_inplace:
+            self._draw_in_place(deferred, base, matrix)
+            ctx.store_wait()
+            return list(sink)
         ctx.overlay_run_packed(*_pack_deferred(deferred), first=base)
         if self._have_font:
             ctx.overlay_text([d[2] for d in deferred], first=base)
@@ -785,7 +858,7 @@ class StreamPipeline:
             return list(sink)
         return list(ctx.download_overlay(len(deferred), first=base))
 
-    def process_batch(self, frames, annotate=True, out=None, out_yuv_matrix='bt601', **kwargs):
+    def process_batch(self, frames, annotate=True, out=None, out_yuv_matrix=None, **kwargs):
         """The same result as calling `process()` on each frame of `frames` in order (one stateful
         stream), arranged for throughput:
 
@@ -815,16 +888,35 @@ class StreamPipeline:
         'bt601', 'bt709' or eight integers; `utils.rgb_to_yuv` is the same conversion), whatever `frames` are -- host arrays or
         `DeviceFrames`, in the tracker's input format -- and no frame crosses the bus on the way out.  Returns `[out[i] for i in
         range(n)]`, final when the call returns; state and attributes are those of the same call with `annotate=True`.  Needs
-        `annotate=True`, and neither `visualize_search` nor `split_view`."""
+        `annotate=True`, and neither `visualize_search` nor `split_view`.  `out_yuv_matrix=None` is 'bt601'.
+        `out="inplace"`: `frames` are `DeviceFrames` (writeable) and lane and text are drawn INTO them, by kernels that touch only the
+        pixels that change -- an RGB surface becomes the annotated frame; of a 4:2:0 surface only the bytes under a changed pixel are
+        replaced (with what a sink would hold there) and every other byte stays the decoder's.  Returns `[frames[i] for i in
+        range(n)]`, final when the call returns; the same keyword rules as for a sink.  `out_yuv_matrix=None` is then the
+        tracker's own `yuv_matrix` (a tracker with a custom input matrix must name one)."""
         if self._in_stream:
             raise RuntimeError("process_batch() inside an active process_stream() would overwrite its frames")
         k, first_try, fp = self._batch_arguments(kwargs)
         mode = self._viz_mode(k, annotate)
         self._sink_keywords(out, annotate, k)
+        in_place = isinstance(out, str)
+        out_yuv_matrix = self._inplace_matrix(out, out_yuv_matrix) if in_place else ('bt601' if out_yuv_matrix is None else out_yuv_matrix)
+        if in_place and not isinstance(frames, DeviceFrames):
+            self._check_inplace_source(frames)
         self._annotate_inplace = isinstance(annotate, str) and annotate == "inplace"   # (a window _as_window had to copy: into the copy)
         frames = self._as_window(frames)
         n = frames.shape[0]
-        sink = self._check_sink(out, n) if out is not None else None
+        sink = self._check_inplace_source(frames) if in_place else (self._check_sink(out, n) if out is not None else None)
+        self._draw_inplace = in_place
+        try:
+            return self._process_window(frames, n, sink, annotate, out_yuv_matrix, k, first_try, fp, mode)
+        finally:
+            self._draw_inplace = False
+            if in_place:
+                self._resident = None    # (no slot holds the last frame's camera rows: its surface is the annotated frame now)
+
+    def _process_window(self, frames, n, sink, annotate, out_yuv_matrix, k, first_try, fp, mode):
+        """process_batch behind its argument checks."""
         ctx = self._ctx
         self._materialise_pending()      # growing the context below drops what is still on the device
         ctx.reserve(max(n, 1))
@@ -857,7 +949,7 @@ class StreamPipeline:
             else:
                 ctx.upload_frame_rows(frames)    # the camera rows the path reads; the rest only if frames are annotated
             ctx.mask_run(n, fp)
-            if annotate:
+            if annotate and not self._draw_inplace:
                 self._upload_keepalive = self._feed_rest(frames, 0)        # beside the mask chain, for the overlay
             painted = [] if mode else None       # this route paints on the host, as process() does
             for i in range(n):
@@ -903,7 +995,7 @@ class StreamPipeline:
             views.append(v)
         return views
 
-    def process_stream(self, windows, annotate=True, out=None, out_yuv_matrix='bt601', **kwargs):
+    def process_stream(self, windows, annotate=True, out=None, out_yuv_matrix=None, **kwargs):
         """Generator over consecutive windows of ONE video: `windows` yields arrays (n, H, W, 3); for each, what
         `process_batch` would return is yielded, and the tracker's state after it is what `process()` frame by frame
         leaves.  The context holds `stream_lookahead + 1` windows side by side: while the searches of one window drain, the
@@ -912,16 +1004,22 @@ class StreamPipeline:
         tracker until the generator is exhausted or closed.  `annotate="inplace"`: see `process_batch` (every window must be a
         C-contiguous, writeable uint8 array; a window that is not comes back as new frames).  `out`: device sinks, an iterable
         that yields one `DeviceFrames` per window (see `process_batch`); a window is yielded, as the list of its sink's frames, once
-        its stores have landed (`Context.store_wait`), and its sink may be reused from then on."""
+        its stores have landed (`Context.store_wait`), and its sink may be reused from then on.  `out="inplace"`: every window is a
+        `DeviceFrames` and is drawn into (see `process_batch`); a window is yielded, as the list of its own frames, once its draws
+        have landed."""
         k, first_try, fp = self._batch_arguments(kwargs)
         mode = self._viz_mode(k, annotate)
         self._sink_keywords(out, annotate, k)
+        in_place = isinstance(out, str)
+        out_yuv_matrix = self._inplace_matrix(out, out_yuv_matrix) if in_place else ('bt601' if out_yuv_matrix is None else out_yuv_matrix)
         self._annotate_inplace = isinstance(annotate, str) and annotate == "inplace"
-        sinks = iter(out) if out is not None else None
+        sinks = (True if in_place else iter(out)) if out is not None else None
 
         def sink_for(w):                     # the sink of the window just taken from `windows`
             if sinks is None:
                 return None
+            if in_place:
+                return self._check_inplace_source(w)
             try:
                 s = next(sinks)
             except StopIteration:
@@ -931,6 +1029,8 @@ class StreamPipeline:
             for w in windows:            # the frame-by-frame route has nothing to overlap
                 if sinks is None:
                     yield self.process_batch(w, annotate=annotate, **kwargs)
+                elif in_place:
+                    yield self.process_batch(w, annotate=annotate, out=out, out_yuv_matrix=out_yuv_matrix, **kwargs)
                 else:
                     w = self._as_window(w)
                     yield self.process_batch(w, annotate=annotate, out=sink_for(w), out_yuv_matrix=out_yuv_matrix, **kwargs)
@@ -941,6 +1041,8 @@ class StreamPipeline:
             return
         if self._in_stream:
             raise RuntimeError("this tracker already runs a process_stream()")
+        if in_place and not isinstance(cur, DeviceFrames):
+            self._check_inplace_source(cur)
         cur = self._as_window(cur)
         device_fed = isinstance(cur, DeviceFrames)
         cur_sink = sink_for(cur)
@@ -977,6 +1079,7 @@ class StreamPipeline:
         self._in_stream = True
         self._window_rows = self._rows_for_window(cur[0]) if (annotate and sinks is None) else None
         self._to_sink = sinks is not None
+        self._draw_inplace = in_place
         try:
             while cur is not None:
                 while len(queue) < look:             # know the next windows
@@ -1032,6 +1135,9 @@ class StreamPipeline:
             self._in_stream = False
             self._window_rows = None
             self._to_sink = False
+            self._draw_inplace = False
+            if in_place:
+                self._resident = None        # (no slot holds the last frame's camera rows: its surface is the annotated frame now)
             try:
                 self._device_frames_done()   # (waits for the device: the attached windows may go)
             except Exception:

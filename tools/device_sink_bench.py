@@ -11,7 +11,8 @@ median and the range, and the commit):
   --stream    process_stream, windows of 128 frames with a short outage, at 1280x720 and 1920x1080, frames/s behind the first
               window: DeviceFrames in and sink out (RGB -> RGB, NV12 -> NV12); host arrays in and annotated frames out through
               the host (annotate=True: the copy threads place them); annotate='inplace'; and search only (annotate=False,
-              DeviceFrames in) -- the stream whose spread the device-out form should share.
+              DeviceFrames in) -- the stream whose spread the device-out form should share; and DeviceFrames in, drawn into in
+              place (out="inplace": RGB, NV12, I420) -- every window a fresh copy of the frames, made ahead of the clock.
 
   python tools/device_sink_bench.py [--kernels | --stream] [--runs 3] [--out profiles/device_sink.json] [--commit HASH]
 """
@@ -96,13 +97,19 @@ def frames_for(cal, fmt):
     if key not in _pools:
         pool = synth.stream_lanes(POOL, seed=5, cal=cal).copy()
         pool[20:23] = 0                  # a short outage: second tries, failure pictures
-        _pools[key] = np.stack([rgb_to_nv12(f) for f in pool]) if fmt == "nv12" else pool
+        if fmt != "rgb":
+            pool = np.stack([rgb_to_nv12(f) for f in pool])
+            if fmt == "i420":            # the same samples, U and V in planes of their own
+                h = pool.shape[1] * 2 // 3
+                uv = pool[:, h:].reshape(len(pool), -1, 2)
+                pool = np.concatenate([pool[:, :h].reshape(len(pool), -1), uv[..., 0], uv[..., 1]], 1).reshape(pool.shape)
+        _pools[key] = pool
     return np.ascontiguousarray(_pools[key][np.arange(128) % POOL])
 
 
 def leg_stream(cal, form, windows=6, size=128):
     """frames/s of `windows` windows behind the first one (which pays the set-up)."""
-    fmt = "nv12" if form == "device_nv12_to_nv12_sink" else "rgb"
+    fmt = "nv12" if "nv12" in form else ("i420" if "i420" in form else "rgb")
     frames = frames_for(cal, fmt)
     t = LaneTracker(**cal) if fmt == "rgb" else LaneTracker(**cal, pixel_format=fmt)
     keep = []
@@ -114,6 +121,8 @@ def leg_stream(cal, form, windows=6, size=128):
             keep.append(win)
             if form == "device_search_only":
                 kw = dict(annotate=False)
+            elif form.endswith("_inplace"):
+                kw = dict(out="inplace")
             else:
                 sinks = [DeviceFrames.empty(size, cal["img_size"], fmt) for _ in range(4)]     # one being filled, one landing, one with the caller, one to spare
                 keep += sinks
@@ -121,6 +130,9 @@ def leg_stream(cal, form, windows=6, size=128):
         elif form == "host_inplace":
             kw = dict(annotate="inplace")
         feed = ([win.copy() for _ in range(windows + 1)] if form == "host_inplace" else [win] * (windows + 1))
+        if form.startswith("device_") and form.endswith("_inplace"):     # a drawn window is no camera window any more: fresh ones
+            feed = [win] + [DeviceFrames.from_host(frames, fmt) for _ in range(windows)]
+            keep += feed[1:]
         n, t0 = 0, None
         for k, out in enumerate(t.process_stream(feed, **kw)):
             if k == 0:
@@ -136,7 +148,8 @@ def leg_stream(cal, form, windows=6, size=128):
 
 def stream_legs(runs, sizes, note):
     cals = {"1280x720": calib.reference_calibration, "1920x1080": lambda: calib.scaled_calibration(1.5)}
-    forms = ("device_rgb_to_rgb_sink", "device_nv12_to_nv12_sink", "host_annotated", "host_inplace", "device_search_only")
+    forms = ("device_rgb_to_rgb_sink", "device_nv12_to_nv12_sink", "device_rgb_inplace", "device_nv12_inplace", "device_i420_inplace",
+             "host_annotated", "host_inplace", "device_search_only")
     for size in sizes:
         cal = cals[size]()
         got = {f: [] for f in forms}
