@@ -802,6 +802,15 @@ const char* lt_stage_name(int stage);
  * one they have exercised. */
 #define LT_NO_CONTEXT (-2147483647 - 1)
 int  lt_last_threshold_path(lt_ctx* ctx);
+/* Which form of the batch top-hat walks the context's last lt_mask_run / lt_filter_run piece launched: bit 0 = the 29x29 pair
+ * of launches, bit 1 = the 55x55 pair took the split-band form (every band walks its own rows only and boundary rows are
+ * merged from the two neighbours' partial results); 0 = the bands walked their halos, or another top-hat route ran (one or two
+ * frames, brute force); -1 = none yet.  Both forms give identical planes. */
+int  lt_last_tophat_path(lt_ctx* ctx);
+/* The host's rule behind it, callable without a device: 1 if an h x w plane cut into `nbands` bands takes the split-band form
+ * of the k x k walk (k = 29 or 55): rows 4-byte aligned, at most four bands, every band -- the last, shorter one included --
+ * at least one boundary zone (28 / 56 rows) long. */
+int  lt_tophat_split_form(int h, int w, int k, int nbands);
 /* The same for the last 'neighborhood' call (cv2.adaptiveThreshold, lane_tracker.py:217-218): 1 = running box sums
  * (odd windows up to 63, width a multiple of 4, no greenery mask), 0 = the per-pixel window kernel, -1 = none yet. */
 int  lt_last_adaptive_path(lt_ctx* ctx);

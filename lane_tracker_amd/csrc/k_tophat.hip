@@ -147,6 +147,9 @@ struct SE29 {
     }
 };
 
+// Split-band form: the rows of a band boundary that both neighbours contribute to, 2R rounded up to the walk's rows per trip
+template <class SE> struct SplitZone { static constexpr int ROWS = SE::K == 55 ? (LT_FUSED55 ? 56 : 54) : 28; };
+
 struct RunsGeom {
     int h, w, nstrips, nbands, band_rows, ntasks;
     size_t plane_stride;
@@ -157,6 +160,8 @@ struct RunsGeom {
     int n_normal;                // tasks of those strips: nframes * nstrips_normal * nbands; the tasks behind them are pair tasks
     int xcd;                     // 1: workgroups are renumbered so that each XCD (= each L2) owns one contiguous range of tasks
     uint8_t* copy_dst;           // COPYM kernels: the minuend is also stored here, with the destination's pitch and stride
+    uint32_t* zone;              // split-band form: the partial rows of the band boundaries, (frame, strip, boundary, row, lane) dwords
+    size_t zone_stride;          // ... dwords per frame
 };
 
 // Per-lane column bookkeeping, loop invariant: clamped byte offsets of the (up to) four pixels a
@@ -617,10 +622,11 @@ __device__ __forceinline__ void row_windows2(uint2* s, int lane, uint2 e_pa, uin
 // with the destination's pitch -- the raw Lab-b plane in the layout the threshold walks read (the greenery mask of
 // filter_lane_points, lane_tracker.py:224, is a bilateral threshold of the RAW plane).  One more store per row pair in a
 // kernel whose memory pipe idles.
-template <class SE, bool DIL, bool WIDE, bool TH, bool PAIR, bool COPYM = false>
+template <class SE, bool DIL, bool WIDE, bool TH, bool PAIR, bool COPYM = false, bool SPLIT = false>
 __device__ __forceinline__ void morph_task(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, const uint8_t* __restrict__ minuend,
                                            const RunsGeom& g, uint2* chain, uint8_t* s_out_w, int lane, int strip, int band, int frame) {
     static_assert(WIDE || !PAIR, "pair strips exist for the WIDE kernels only");
+    static_assert(WIDE || !SPLIT, "the split-band form exists for the WIDE kernels only");
     static_assert(!COPYM || (WIDE && TH), "the minuend copy rides on the dword store of the WIDE top-hat");
     constexpr int K = SE::K, R = SE::R, NH = SE::NH;
     constexpr uint32_t NEUTRAL = (DIL ? 0u : 0x00ff00ffu) | BIAS2;
@@ -630,7 +636,14 @@ __device__ __forceinline__ void morph_task(const uint8_t* __restrict__ src, uint
     const bool has_b = PAIR && frame + 1 < g.nframes;                                    // wave-uniform
     const bool lane_b = PAIR && (lane & 16);                                             // this lane stores frame f + 1
     const int x0 = strip * 128;
-    const int yb0 = band * g.band_rows, yb1 = min(yb0 + g.band_rows, g.h);
+    // 55x55: two row pairs per loop iteration (see the loop below)
+    constexpr int PAIRS = (LT_FUSED55 && K == 55) ? 2 : 1, STEP = 2 * PAIRS, ZONE = SplitZone<SE>::ROWS;
+    // [yb0, yb1): the band.  SPLIT: the INPUT rows this wave accumulates, with band starts rounded down to the loop's row step
+    // (every band but the last is then a whole number of trips, and the last one is no shorter than its nominal length);
+    // [lo, hi): the output rows it stores -- from behind its upper zone to the end of its lower one (see k_morph_split).
+    const int yb0 = SPLIT ? (band * g.band_rows) & ~(STEP - 1) : band * g.band_rows;
+    const int yb1 = SPLIT ? (band + 1 < g.nbands ? ((band + 1) * g.band_rows) & ~(STEP - 1) : g.h) : min(yb0 + g.band_rows, g.h);
+    const int lo = SPLIT && band > 0 ? yb0 - R + ZONE : yb0, hi = SPLIT && band + 1 < g.nbands ? yb1 - R + ZONE : yb1;
     const int xa = x0 + lane, xb = xa + 64;
     const bool va = xa < g.w, vb = xb < g.w;
     const int oa = min(xa, g.w - 1), ob = min(xb, g.w - 1);
@@ -640,9 +653,11 @@ __device__ __forceinline__ void morph_task(const uint8_t* __restrict__ src, uint
 
     uint32_t A[K];
 #pragma unroll
-    for (int j = 0; j < K; ++j) A[j] = NEUTRAL;   // flushed out of the pipeline before the band's first row
+    for (int j = 0; j < K; ++j) A[j] = NEUTRAL;   // flushed out of the pipeline before the band's first row (SPLIT: rows of other bands, or none)
 
-    const int y_first = yb0 - R, y_last = yb1 - 1 + R;
+    const int y_first = SPLIT ? yb0 : yb0 - R, y_last = SPLIT ? yb1 - 1 : yb1 - 1 + R;
+    // the output row of the first pair that goes through the store path (SPLIT: behind the pairs of the upper zone)
+    const int y_start = SPLIT ? (band > 0 ? lo : -R) : yb0 - 2 * R;
     // the three source columns of a lane (entry 0 = columns (a, b), entry 1 = (b, c)), clamped into the image
     const int c0 = x0 - R + lane;
     const uint32_t col_a = (uint32_t)min(max(c0, 0), g.w - 1), col_b = (uint32_t)min(max(c0 + 64, 0), g.w - 1), col_c = (uint32_t)min(max(c0 + 128, 0), g.w - 1);
@@ -652,10 +667,10 @@ __device__ __forceinline__ void morph_task(const uint8_t* __restrict__ src, uint
     const __amdgpu_buffer_rsrc_t src_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(s), 0, plane_bytes + b_src, RSRC_RAW);
     // the destination descriptor covers the band's rows only: whatever a lane computes above or below them is dropped
     // (PAIR: the band of frame f through the band of frame f + 1; rows are tested explicitly there)
-    const __amdgpu_buffer_rsrc_t dst_rs = __builtin_amdgcn_make_buffer_rsrc(d + (size_t)yb0 * g.dpitch, 0, (yb1 - yb0) * g.dpitch + (has_b ? (int)g.dst_stride : 0), RSRC_RAW);
+    const __amdgpu_buffer_rsrc_t dst_rs = __builtin_amdgcn_make_buffer_rsrc(d + (size_t)lo * g.dpitch, 0, (hi - lo) * g.dpitch + (has_b ? (int)g.dst_stride : 0), RSRC_RAW);
     const __amdgpu_buffer_rsrc_t min_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(TH ? m : s), 0, plane_bytes + b_src, RSRC_RAW);
     const __amdgpu_buffer_rsrc_t cp_rs = __builtin_amdgcn_make_buffer_rsrc(
-        (COPYM ? g.copy_dst + (size_t)frame * g.dst_stride : d) + (size_t)yb0 * g.dpitch, 0, (yb1 - yb0) * g.dpitch + (has_b ? (int)g.dst_stride : 0), RSRC_RAW);
+        (COPYM ? g.copy_dst + (size_t)frame * g.dst_stride : d) + (size_t)lo * g.dpitch, 0, (hi - lo) * g.dpitch + (has_b ? (int)g.dst_stride : 0), RSRC_RAW);
     auto row_ptr = [&](int y) { return __mul24(min(max(y, 0), g.h - 1), g.w); };   // byte offset of the (clamped) row: wave-uniform
     // Software prefetch: the three pixels (a, b, c) of each row of the NEXT pair are requested at the top of a pair, and
     // combined into its two entries (a | b << 16, b | c << 16) by the LAST statements of the pair.  The combine is a
@@ -708,9 +723,14 @@ __device__ __forceinline__ void morph_task(const uint8_t* __restrict__ src, uint
     uint32_t ma0 = 0, mb0 = 0, ma1 = 0, mb1 = 0;   // !WIDE: minuend (xa, xb) of output rows y and y+1
     // WIDE: running byte offsets of this lane's dword -- row y + (lane >> 5) of the minuend, row y - 2 + (lane >> 5) of the
     // band (relative to its first row), for the output row y of the current iteration; lanes right of the image stay out of range
-    uint32_t m_off = (uint32_t)(__mul24(yb0 - 2 * R + (lane >> 5), g.w) + wcol_c + (lane_b ? b_src : 0));
-    uint32_t st_off = wcol < g.w && (!lane_b || has_b) ? (uint32_t)(__mul24(-2 * R - 2 + (lane >> 5), g.dpitch) + wcol + (lane_b ? (int)g.dst_stride : 0))
+    uint32_t m_off = (uint32_t)(__mul24(y_start + (lane >> 5), g.w) + wcol_c + (lane_b ? b_src : 0));
+    uint32_t st_off = wcol < g.w && (!lane_b || has_b) ? (uint32_t)(__mul24(y_start - lo - 2 + (lane >> 5), g.dpitch) + wcol + (lane_b ? (int)g.dst_stride : 0))
                                                       : 0x80000000u;
+    // SPLIT: this task's boundary zones; the one above the band takes the partial rows of the walk's first ZONE rows (dword
+    // stores, running offset, whatever falls outside the zone is dropped), the one below is read back after the last row
+    uint32_t* const zone = SPLIT ? g.zone + (size_t)frame * g.zone_stride + (size_t)strip * (3 * SplitZone<SE>::ROWS * 64) : nullptr;
+    const __amdgpu_buffer_rsrc_t zup_rs = __builtin_amdgcn_make_buffer_rsrc(zone + (size_t)max(band - 1, 0) * (ZONE * 64), 0, SPLIT && band > 0 ? ZONE * 256 : 0, RSRC_RAW);
+    uint32_t z_off = 4u * (uint32_t)lane;
     uint32_t mcur = 0;
     const uint32_t s0_rd = (uint32_t)(uintptr_t)(chain + MARGIN + ((R + lane) & 63));
     const uint32_t out_wr = (uint32_t)(uintptr_t)(s_out_w + (WIDE ? 2 * lane : 0));         // LDS offsets
@@ -722,7 +742,7 @@ __device__ __forceinline__ void morph_task(const uint8_t* __restrict__ src, uint
         if (TH) v = mp - v;   // TOPHAT: src - open(src) >= 0 in every byte
         if (PAIR) {           // two frames behind one descriptor: the band is tested per lane
             const int row = yp + (lane >> 5);
-            if (row >= yb0 && row < yb1) {
+            if (row >= lo && row < hi) {
                 __builtin_amdgcn_raw_buffer_store_b32(v, dst_rs, (int)st_off, 0, 0);
                 if (COPYM) __builtin_amdgcn_raw_buffer_store_b32(mp, cp_rs, (int)st_off, 0, 0);
             }
@@ -731,7 +751,9 @@ __device__ __forceinline__ void morph_task(const uint8_t* __restrict__ src, uint
             if (COPYM) __builtin_amdgcn_raw_buffer_store_b32(mp, cp_rs, (int)st_off, 0, 0);
         }
     };
-    auto row_pair = [&](int yy) __attribute__((always_inline)) {
+    // zp (SPLIT): a pair of the upper zone -- its two output rows are partial, and go to the zone as the packed dwords they are
+    auto row_pair = [&](int yy, auto zp) __attribute__((always_inline)) {
+        constexpr bool ZP = decltype(zp)::value;
         const uint2 e_pa = make_uint2(ea0, eb0);
         const uint2 e_pb = make_uint2(ea1, eb1);
         chain[MARGIN + lane] = lane < R ? e_pb : e_pa;   // entry (lane < R ? lane + 64 : lane): what lane (lane - R) mod 64 owns
@@ -740,7 +762,7 @@ __device__ __forceinline__ void morph_task(const uint8_t* __restrict__ src, uint
         const int y = yy - R;                       // output rows y and y+1 complete in this iteration
         const uint32_t ca0 = ma0, cb0 = mb0, ca1 = ma1, cb1 = mb1;
         const uint32_t mprev = mcur;    // WIDE: minuend of rows y-2, y-1 (stored in this iteration)
-        if (TH) {
+        if (TH && !ZP) {
             if (WIDE) {   // lane <-> row y + (lane >> 5), columns x0 + 4 (lane & 31) .. + 3: the layout of the dword store
                 mcur = __builtin_amdgcn_raw_buffer_load_b32(min_rs, (int)m_off, 0, 0);
             } else {
@@ -755,7 +777,7 @@ __device__ __forceinline__ void morph_task(const uint8_t* __restrict__ src, uint
         uint32_t out_ab[2];
         row_windows2<SE, DIL, FUSE>(chain, lane, e_pa, e_pb, s0_rd, Ha, Hb, A, out_ab);
         wave_lds_fence();   // the chain planes are rewritten by the next iteration
-        const bool prev_out = WIDE && y - 1 >= yb0 && y - 2 < yb1;   // rows y-2, y-1 wait regrouped in s_out
+        const bool prev_out = WIDE && !ZP && y - 1 >= lo && y - 2 < hi;   // rows y-2, y-1 wait regrouped in s_out
         unsigned long long q = 0;
         if (prev_out) out_issue(q);
         if (WIDE) __builtin_amdgcn_sched_barrier(0);
@@ -768,12 +790,16 @@ __device__ __forceinline__ void morph_task(const uint8_t* __restrict__ src, uint
             out_ab[1] = A[0];                                                         // row y + 1
         }
         const uint32_t out_a = out_ab[0], out_b = out_ab[1];
-        if (WIDE) {
+        if (ZP) {
+            __builtin_amdgcn_raw_buffer_store_b32(out_a, zup_rs, (int)z_off, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(out_b, zup_rs, (int)z_off, 256, 0);
+            z_off += 512u;
+        } else if (WIDE) {
             __builtin_amdgcn_sched_barrier(0);   // the window update above stays between the read-back and its use
             // unconditional: outside the band the store falls outside dst_rs.  Under a branch the compiler cannot count
             // it, and the wait for the next pair's bytes at the loop top becomes vmcnt(0) -- a wait for this store
             out_finish(q, mprev, y - 2);
-            if (y + 1 >= yb0 && y < yb1) {       // wave-uniform; read back and stored while the next row pair computes
+            if (y + 1 >= lo && y < hi) {         // wave-uniform; read back and stored while the next row pair computes
                 const uint32_t W = __builtin_amdgcn_perm(out_b, out_a, 0x06020400u);   // [row y: xa, row y+1: xa, y: xb, y+1: xb]
                 asm volatile("ds_write_b16 %0, %1\n\tds_write_b16_d16_hi %0, %1 offset:128" :: "v"(out_wr), "v"(W) : "memory");
             }
@@ -803,10 +829,19 @@ __device__ __forceinline__ void morph_task(const uint8_t* __restrict__ src, uint
     // pair per iteration the staged update order (outer rows first) left 11 register copies at the loop's back edge,
     // with two the second pair lands in the first one's registers.  An odd pair count runs one pair past the band
     // (loads are clamped, stores fall outside the band's descriptor).
-    constexpr int PAIRS = (LT_FUSED55 && K == 55) ? 2 : 1;
-    for (int yy = y_first; yy <= y_last; yy += 2 * PAIRS) {
-        row_pair(yy);
-        if (PAIRS == 2) row_pair(yy + 2);
+    int yy = y_first;
+    if constexpr (SPLIT) {
+        // The pairs of the upper zone in an instance of the loop of their own (stores under a branch in ONE loop would cost it a
+        // vmcnt(0) wait, see above).
+        const int zone_end = band > 0 ? y_first + ZONE : y_first;
+        for (; yy < zone_end; yy += STEP) {
+            row_pair(yy, std::true_type{});
+            if (PAIRS == 2) row_pair(yy + 2, std::true_type{});
+        }
+    }
+    for (; yy <= y_last; yy += STEP) {
+        row_pair(yy, std::false_type{});
+        if (PAIRS == 2) row_pair(yy + 2, std::false_type{});
     }
     if (WIDE) {   // the last row pair is still in s_out (outside the band if the loop ran past it: dropped by the descriptor)
         const int npairs = (y_last - y_first) / 2 + 1, pairs_run = (npairs + PAIRS - 1) / PAIRS * PAIRS;
@@ -814,6 +849,63 @@ __device__ __forceinline__ void morph_task(const uint8_t* __restrict__ src, uint
         unsigned long long q;
         out_issue(q);
         out_finish(q, mcur, y_tail);
+        if constexpr (SPLIT) {
+            // The one barrier of the task, here and not behind the zone pairs: every band has walked the same number of trips by
+            // now (the top band has no zone pairs but as many rows), so nobody waits long; behind it every zone of the task is
+            // written.  Every wave of the workgroup is a band of the task and gets here.
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            // The accumulators still in flight are the partial rows T0 .. T0 + 2R - 1 (T0 = the row behind the last one the loop
+            // completed): A[1 + t] is row T0 + t as far as this band's input goes.  A band with a neighbour below merges each with the
+            // neighbour's partial row from the zone (rows past this band's reach are the neighbour's alone) and sends it down the
+            // usual path: regroup, subtract, dword store.  The bottom band stores what is left of the image.  Seven row pairs at a
+            // time: their zone and minuend loads are in flight together, and they are regrouped side by side in the wave's chain
+            // planes (idle now) behind ONE wait -- pair by pair this tail is a string of memory round trips.
+            constexpr int TB = 7;
+            static_assert(ZONE % (2 * TB) == 0, "whole batches");
+            const int T0 = y_tail + 2;
+            const bool below = band + 1 < g.nbands;        // wave-uniform
+            const __amdgpu_buffer_rsrc_t zdn_rs = __builtin_amdgcn_make_buffer_rsrc(zone + (size_t)band * (ZONE * 64), 0, below ? ZONE * 256 : 0, RSRC_RAW);
+            st_off += 2u * (uint32_t)g.dpitch;
+            const uint32_t tb_wr = (uint32_t)(uintptr_t)chain + 2u * (uint32_t)lane, tb_rd = (uint32_t)(uintptr_t)chain + 8u * (uint32_t)(lane & 31);
+#pragma unroll
+            for (int t = 0; t < ZONE; t += 2 * TB) {
+                if (below || T0 + t < g.h) {
+                    uint32_t z[2 * TB], mm[TB];
+#pragma unroll
+                    for (int r = 0; r < 2 * TB; ++r) z[r] = below ? __builtin_amdgcn_raw_buffer_load_b32(zdn_rs, 4 * lane, (t + r) * 256, 0) : NEUTRAL;
+#pragma unroll
+                    for (int i = 0; i < TB; ++i) mm[i] = TH ? __builtin_amdgcn_raw_buffer_load_b32(min_rs, (int)(m_off + 2u * i * (uint32_t)g.w), 0, 0) : 0u;
+#pragma unroll
+                    for (int i = 0; i < TB; ++i) {
+                        const int ta = t + 2 * i, tb = ta + 1;
+                        const uint32_t pa = op2<DIL>(ta < 2 * R ? A[ta + 1 < K ? ta + 1 : K - 1] : NEUTRAL, z[2 * i]);
+                        const uint32_t pb = op2<DIL>(tb < 2 * R ? A[tb + 1 < K ? tb + 1 : K - 1] : NEUTRAL, z[2 * i + 1]);
+                        const uint32_t W = __builtin_amdgcn_perm(pb, pa, 0x06020400u);
+                        asm volatile("ds_write_b16 %0, %1\n\tds_write_b16_d16_hi %0, %1 offset:128" :: "v"(tb_wr + 256u * i), "v"(W) : "memory");
+                    }
+                    unsigned long long qq[TB];
+#pragma unroll
+                    for (int i = 0; i < TB; ++i) asm volatile("ds_read_b64 %0, %1" : "=v"(qq[i]) : "v"(tb_rd + 256u * i) : "memory");
+                    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(qq[0]), "+v"(qq[1]), "+v"(qq[2]), "+v"(qq[3]), "+v"(qq[4]), "+v"(qq[5]), "+v"(qq[6]) :: "memory");
+#pragma unroll
+                    for (int i = 0; i < TB; ++i) {
+                        uint32_t v = __builtin_amdgcn_perm((uint32_t)(qq[i] >> 32), (uint32_t)qq[i], row_sel);
+                        if (TH) v = mm[i] - v;
+                        const int row = T0 + t + 2 * i + (lane >> 5);
+                        // the row offset goes into the LANE offset: a scalar offset is not part of the descriptor's range check
+                        const int so = (int)(st_off + 2u * i * (uint32_t)g.dpitch);
+                        if (!PAIR || (row >= lo && row < hi)) {   // (PAIR: two frames behind one descriptor, as in out_finish)
+                            __builtin_amdgcn_raw_buffer_store_b32(v, dst_rs, so, 0, 0);
+                            if (COPYM) __builtin_amdgcn_raw_buffer_store_b32(mm[i], cp_rs, so, 0, 0);
+                        }
+                    }
+                }
+                m_off += 2u * TB * (uint32_t)g.w;
+                st_off += 2u * TB * (uint32_t)g.dpitch;
+            }
+        }
     }
 }
 
@@ -859,6 +951,41 @@ __global__ __launch_bounds__(64 * LT_MORPH_WPB) LT_MORPH_WAVES_ATTR void k_morph
         morph_task<SE, DIL, WIDE, TH, false, COPYM>(src, dst, minuend, g, s_chain[wv], s_out[wv], lane, strip, band, frame);
     } else if constexpr (WIDE) {
         morph_task<SE, DIL, WIDE, TH, true, COPYM>(src, dst, minuend, g, s_chain[wv], s_out[wv], lane, g.nstrips_normal, task % g.nbands, 2 * (task / g.nbands));
+    }
+}
+
+// ================================================================================================
+// Split-band form: a band accumulates ITS OWN input rows only.
+//
+// k_morph_runs2's task walks band_rows + 2R input rows: the 2R halo rows are the neighbouring bands' rows, loaded, chained,
+// windowed and accumulated a second time (16 % of a 55x55 walk at 4 bands of 275 rows, 9 % of a 29x29 one).  min and max are
+// associative and idempotent and taps outside the image are neutral, so a band that starts from A[] = NEUTRAL and walks only the
+// rows [yb0, yb1) delivers
+//   * first the rows [yb0 - R, yb0 - R + ZONE): PARTIAL -- the band above holds the rest of them;
+//   * then final rows, up to yb1 - R;
+//   * and, behind its last input row, in the accumulators still in flight, the partial rows [yb1 - R, yb1 + R).
+// A boundary row is op(partial from above, partial from below).  The waves of a workgroup are the bands of ONE (frame, strip) task
+// (of one pair task for the PAIR strip): the lower band stores its first ZONE partial rows into a scratch zone as the packed
+// dwords its lanes hold, ONE workgroup barrier follows, and the upper band, done with its rows, reads them back, merges and
+// stores rows [yb1 - R, yb1 - R + ZONE) itself; the lower band's own stores start behind them.  ZONE is 2R rounded up to the
+// walk's rows per trip; rows of it beyond the upper band's reach are the lower band's alone.  The top band starts at row 0 and
+// the bottom band ends at row h - 1 (its last trip may read up to three clamped rows, harmless as in k_morph_runs2).
+// Band starts are rounded down to the rows per trip inside morph_task, so that every band but the last is whole trips.
+// split_form_ok() is the host's predicate; k_morph_runs2 takes every geometry it refuses.
+template <class SE, bool DIL, bool TH, bool COPYM = false>
+__global__ __launch_bounds__(256) LT_MORPH_WAVES_ATTR void k_morph_split(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst,
+                                                                     const uint8_t* __restrict__ minuend, RunsGeom g) {
+    __shared__ uint2 s_chain[4][4 * PLANE];   // S0, S1, S4, S13 per wave
+    __shared__ __attribute__((aligned(8))) uint8_t s_out[4][256];
+    const int lane = threadIdx.x & 63, band = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // blockDim.x = 64 * nbands
+    const int task = (int)blockIdx.x;         // the grid is exactly the tasks: a workgroup is valid as a whole (one barrier inside)
+    if (!LT_MORPH_BIAS) __builtin_amdgcn_s_setreg(1 | (6 << 6) | (1 << 11), 3);   // f16 denormals kept (see k_morph_runs2)
+    const int n_pair = g.ntasks - g.n_normal; // pair tasks first, as in k_morph_runs2 (workgroup-uniform branch)
+    if (task >= n_pair) {
+        const int t = task - n_pair;
+        morph_task<SE, DIL, true, TH, false, COPYM, true>(src, dst, minuend, g, s_chain[band], s_out[band], lane, t % g.nstrips_normal, band, t / g.nstrips_normal);
+    } else {
+        morph_task<SE, DIL, true, TH, true, COPYM, true>(src, dst, minuend, g, s_chain[band], s_out[band], lane, g.nstrips_normal, band, 2 * task);
     }
 }
 
@@ -1068,8 +1195,11 @@ bool table_matches(const EllipseSE& se) {
 
 template <class SE>
 bool launch_runs(hipStream_t s, const uint8_t* src, uint8_t* dst, const uint8_t* minuend, int h, int w, bool dilate,
-                 size_t plane_stride, int n, int dpitch, size_t dst_stride, uint8_t* copy_dst) {
+                 size_t plane_stride, int n, int dpitch, size_t dst_stride, uint8_t* copy_dst, const MorphZone& zone, int* form) {
     RunsGeom g;
+    if (form) *form = 0;
+    g.zone = nullptr;
+    g.zone_stride = 0;
     g.copy_dst = copy_dst;
     g.h = h;
     g.w = w;
@@ -1092,9 +1222,19 @@ bool launch_runs(hipStream_t s, const uint8_t* src, uint8_t* dst, const uint8_t*
         else launch_one<SE, 4>(s, src, dst, minuend, dilate, g);
         return true;
     }
-    // Band count: every task walks band_rows + 2R rows, and the chip holds `slots` waves at once, so
-    // the makespan is ~ ceil(tasks / slots) * (band_rows + 2R).  Pick the band count that minimises
-    // it (a grid of 2.25 rounds costs 3 rounds); bands no shorter than 2R keep the halo overhead sane.
+    // The split-band form (k_morph_split) for a cut into nb bands of `rows` rows: what the geometry rule accepts, with a zone scratch
+    // at hand.  Not with LT_MORPH_XCD (k_morph_split does not renumber its workgroups: the switch would measure nothing).
+    static const bool no_split = [] { const char* e = LT_EXP_ENV("LT_MORPH_SPLIT"); return e && e[0] == '0'; }();   // A/B
+    static const bool want_xcd = [] { const char* e = LT_EXP_ENV("LT_MORPH_XCD"); return e && e[0] == '1'; }();
+    const bool split_cand = !one_row && !no_split && !want_xcd && zone.base && ((uintptr_t)src & 3) == 0 &&
+                            (!copy_dst || (SE::K == 55 && dilate && minuend && ((uintptr_t)copy_dst & 3) == 0)) &&
+                            zone.stride_dwords >= (size_t)g.nstrips * tophat_split_zone_dwords(SE::K);
+    auto splits = [&](int rows, int nb) { return split_cand && tophat_split_form(h, w, SE::K, rows, nb, wide); };
+    // Band count: a task walks band_rows + 2R rows -- band_rows where the split-band form runs, whose bands walk no halo -- and
+    // the chip holds `slots` waves at once, so the makespan is ~ ceil(tasks / slots) * (rows walked).  Pick the band count that
+    // minimises it (a grid of 2.25 rounds costs 3 rounds); bands no shorter than 2R keep the halo overhead sane (the split form
+    // needs them a zone long anyway).  The occupancy figure is k_morph_runs2's: k_morph_split is held to the same VGPR step
+    // (tests/test_tophat_split_guards.py), and a workgroup of either is four waves at the bands this rule ends up with.
     int dev = 0, cus = 256, blocks_per_cu = 3;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
@@ -1123,10 +1263,12 @@ bool launch_runs(hipStream_t s, const uint8_t* src, uint8_t* dst, const uint8_t*
         if (nb > 1 && rows < (tasks <= simds ? 4 : tasks <= slots ? (SE::R + 1) / 2 : 2 * SE::R)) break;
         const double rounds = (double)((tasks + slots - 1) / slots);
         // small grids cannot fill the chip: prefer more, shorter tasks there
-        const double cost = tasks <= simds ? (double)(rows + 2 * SE::R) : tasks < slots ? 1.15 * (rows + 2 * SE::R) : rounds * (rows + 2 * SE::R);
+        const int walk = rows + (splits(rows, real_nb) ? 0 : 2 * SE::R);
+        const double cost = tasks <= simds ? (double)walk : tasks < slots ? 1.15 * walk : rounds * walk;
         if (cost < best_cost - 1e-9) { best_cost = cost; best_nb = nb; }
     }
-    // Measured on the full 256-frame grid (tools/nb_sweep.sh, tools/nb55_sweep.sh): all four kernels are fastest with
+    // Measured on the full 256-frame grid (tools/nb_sweep.sh, tools/nb55_sweep.sh; again on the split-band form, which runs here:
+    // profiles/NOTES_split_bands.md, 3 bands against 4): all four kernels are fastest with
     // 4 bands of 275 rows (the model above picks 5 and 2 for 29x29 and 5 for 55x55: it trusts an occupancy figure
     // whose extra waves add no throughput -- the kernels are bound by VALU issue and the LDS pipe, not by latency).
     if ((long long)n * g.nstrips * 4 >= slots && h / 4 >= 2 * SE::R) best_nb = 4;
@@ -1154,8 +1296,23 @@ bool launch_runs(hipStream_t s, const uint8_t* src, uint8_t* dst, const uint8_t*
     g.ntasks = g.n_normal + (pair_strip ? (n + 1) / 2 * g.nbands : 0);
     // measured (tools/ab_fetch.sh LT_MORPH_XCD): the renumbering makes all four launches 1-5 % SLOWER (0.295 -> 0.311 ms
     // erode 29x29, 0.493 -> 0.508 ms erode 55x55 per 256 frames), so it is off unless asked for
-    static const bool want_xcd = [] { const char* e = LT_EXP_ENV("LT_MORPH_XCD"); return e && e[0] == '1'; }();
     g.xcd = want_xcd ? 1 : 0;
+    // The split-band form: the waves of a workgroup are the bands of one (frame, strip) or pair task.
+    if (splits(g.band_rows, g.nbands)) {
+        g.zone = zone.base;
+        g.zone_stride = zone.stride_dwords;
+        g.n_normal = n * g.nstrips_normal;
+        g.ntasks = g.n_normal + (pair_strip ? (n + 1) / 2 : 0);
+        const dim3 grid_s(g.ntasks), block_s(64 * g.nbands);
+        const bool th = dilate && minuend != nullptr;
+        if (copy_dst) {
+            if constexpr (SE::K == 55) hipLaunchKernelGGL((k_morph_split<SE, true, true, true>), grid_s, block_s, 0, s, src, dst, minuend, g);
+        } else if (th) hipLaunchKernelGGL((k_morph_split<SE, true, true>), grid_s, block_s, 0, s, src, dst, minuend, g);
+        else if (dilate) hipLaunchKernelGGL((k_morph_split<SE, true, false>), grid_s, block_s, 0, s, src, dst, minuend, g);
+        else hipLaunchKernelGGL((k_morph_split<SE, false, false>), grid_s, block_s, 0, s, src, dst, minuend, g);
+        if (form) *form = 1;
+        return true;
+    }
     dim3 grid((g.ntasks + 3) / 4);
     const dim3 grid2((g.ntasks + LT_MORPH_WPB - 1) / LT_MORPH_WPB), block2(64 * LT_MORPH_WPB);
     if (copy_dst && one_row) return false;
@@ -1196,11 +1353,23 @@ bool tophat_tables_match(const EllipseSE& se29, const EllipseSE& se55) {
 }
 
 bool launch_morph_runs(hipStream_t s, const uint8_t* src, uint8_t* dst, const uint8_t* minuend, int h, int w, int k,
-                       bool dilate, size_t plane_stride, int n, int dpitch, size_t dst_stride, uint8_t* copy_dst) {
+                       bool dilate, size_t plane_stride, int n, int dpitch, size_t dst_stride, uint8_t* copy_dst, const MorphZone& zone, int* form) {
+    if (form) *form = 0;
     if (n <= 0 || h <= 0 || w <= 0) return true;
     if (k == 55)
-        return launch_runs<SE55>(s, src, dst, minuend, h, w, dilate, plane_stride, n, dpitch, dst_stride, copy_dst);
-    return launch_runs<SE29>(s, src, dst, minuend, h, w, dilate, plane_stride, n, dpitch, dst_stride, copy_dst);
+        return launch_runs<SE55>(s, src, dst, minuend, h, w, dilate, plane_stride, n, dpitch, dst_stride, copy_dst, zone, form);
+    return launch_runs<SE29>(s, src, dst, minuend, h, w, dilate, plane_stride, n, dpitch, dst_stride, copy_dst, zone, form);
+}
+
+// The split-band form's precondition (k_morph_split): rows 4-byte aligned (`wide`), at most four bands -- the waves of one
+// workgroup -- and every band, the last one included, at least one zone long.
+int tophat_split_zone_rows(int k) { return k == 55 ? SplitZone<SE55>::ROWS : SplitZone<SE29>::ROWS; }
+size_t tophat_split_zone_dwords(int k) { return (size_t)3 * tophat_split_zone_rows(k) * 64; }   // per strip: three boundaries
+bool tophat_split_form(int h, int w, int k, int band_rows, int nbands, bool wide) {
+    if (!wide || (k != 55 && k != 29) || h <= 0 || w < 4 || band_rows <= 0) return false;
+    if (nbands < 1 || nbands > 4 || nbands != (h + band_rows - 1) / band_rows) return false;
+    const int zone = tophat_split_zone_rows(k), last = h - (nbands - 1) * band_rows;
+    return band_rows >= zone && last >= zone;
 }
 
 // One or two frames: the same step (erode, or dilate / top-hat) of the 55x55 chain of one plane and of the 29x29 chain of another

@@ -331,7 +331,7 @@ static int ensure_mask_plane(lt_ctx* c) {
 // what the mask chain takes from the context besides the arena (lt_mask_chain.cpp)
 static ChainEnv chain_env(lt_ctx* c) {
     return ChainEnv{&c->se29, &c->se55, c->brute_tophat, c->walk_min_pixels, &c->streams, c->stage_timing ? c : nullptr,
-                    &c->last_threshold_path, &c->last_adaptive_path};
+                    &c->last_threshold_path, &c->last_adaptive_path, &c->last_tophat_path};
 }
 // make d_plane[P_MASK] current for the slots (expands the bit plane where only that exists)
 int ensure_u8_masks(lt_ctx* c, int first, int n) {
@@ -2559,6 +2559,17 @@ int lt_timer_stop(lt_ctx* c, float* ms) {
 int lt_last_threshold_path(lt_ctx* c) {
     if (!c) { (void)fail(LT_ERR_INVALID, "null context"); return LT_NO_CONTEXT; }
     return c->last_threshold_path;
+}
+
+int lt_last_tophat_path(lt_ctx* c) {
+    if (!c) { (void)fail(LT_ERR_INVALID, "null context"); return LT_NO_CONTEXT; }
+    return c->last_tophat_path;
+}
+
+int lt_tophat_split_form(int h, int w, int k, int nbands) {
+    if (h <= 0 || w <= 0 || nbands <= 0) return 0;
+    const int band_rows = (h + nbands - 1) / nbands;
+    return lt::tophat_split_form(h, w, k, band_rows, (h + band_rows - 1) / band_rows, (w & 3) == 0 && w >= 4) ? 1 : 0;
 }
 
 int lt_last_adaptive_path(lt_ctx* c) {

@@ -60,6 +60,10 @@ struct MaskArena {
     // the eroded R plane of a one- or two-frame chain: two planes per stream that can run one (ensure_side_scratch)
     static constexpr int SIDE_LANES = 10;         // one per slice stream (up to 8), one for every other stream
     uint8_t* d_side_scratch = nullptr;
+    // the boundary zones of the split-band top-hat walks (k_tophat.hip: k_morph_split): per slot and 128-column strip three zones
+    // of 56 rows x 64 dwords; the four launches of a slot's chain run one behind the other and share them (ensure_zone_scratch)
+    uint32_t* d_zone = nullptr;
+    size_t zone_stride = 0;                       // dwords per slot
 
     MaskArena() = default;
     MaskArena(const MaskArena&) = delete;
@@ -73,6 +77,7 @@ struct MaskArena {
     int ensure_plane(int idx);
     int ensure_noise_buffers();
     int ensure_side_scratch();
+    int ensure_zone_scratch();
 };
 
 // The staging ring of lt_search_viz_run / lt_split_panes_run (lt_search_viz.cpp): FRAMES pictures (and, for split views, as many
@@ -165,6 +170,7 @@ struct lt_ctx {
     lt::MaskArena masks;              // the mask chain's device memory, one block of each kind for the whole capacity
     lt::VizRing viz;                  // lt_search_viz_run / lt_split_panes_run: pictures on their way to the host
     int last_threshold_path = -1;                 // lt_last_threshold_path
+    int last_tophat_path = -1;                    // lt_last_tophat_path
     int last_adaptive_path = -1;                  // 'neighborhood' calls: 1 = running box sums (k_adaptive_walk.hip), 0 = per-pixel windows
     // The walking threshold kernels are long serial walks (a wave covers half an image row or column): they win once a
     // call brings enough frames to fill the chip -- measured crossover 70-80 frames of 1100 x 1080 per call
@@ -410,6 +416,7 @@ inline void MaskArena::set_geometry(int h, int w) {
     bits_stride = (size_t)h * ((w + 63) / 64);
     th_pitch = (w + 63) & ~63;
     th_pad_bytes = (size_t)h * th_pitch;
+    zone_stride = (size_t)((w + 127) / 128) * tophat_split_zone_dwords(55);
 }
 
 inline int MaskArena::reserve(int slots, bool batch) {
@@ -434,6 +441,7 @@ inline void MaskArena::release() {
     for (auto& q : d_plane) dev_free(q);
     for (auto q : {&d_bits_merged, &d_bits_eroded, &d_bits_open, &d_bits_tmp, &d_bits_tmp2, &d_bits_n1, &d_bits_n2}) dev_free(*q);
     for (auto q : {&d_th_pad[0], &d_th_pad[1], &d_b_pad, &d_side_scratch}) dev_free(*q);
+    dev_free(d_zone);
     th_padded.clear();
     capacity = 0;
 }
@@ -459,6 +467,12 @@ inline int MaskArena::ensure_noise_buffers() {
 // slices' streams and the urgent one -- and calls on one stream are ordered)
 inline int MaskArena::ensure_side_scratch() {
     return d_side_scratch ? (int)LT_OK : dev_alloc(&d_side_scratch, (size_t)SIDE_LANES * 2 * plane_bytes);
+}
+
+// (per SLOT, like the scratch plane P_T0: slots of different slices are in flight at once.  Never written by the host and never
+// read before the same launch wrote it, so it is not cleared.)
+inline int MaskArena::ensure_zone_scratch() {
+    return d_zone ? (int)LT_OK : dev_alloc(&d_zone, (size_t)capacity * zone_stride * sizeof(uint32_t));
 }
 
 // ---- streams, slot ranges, ordering (lt_api.cpp) ---------------------------------------------------------
@@ -603,6 +617,7 @@ struct ChainEnv {
     const std::vector<hipStream_t>* streams = nullptr;  // whose position picks a stream's lane of the side scratch; null: the spare lane
     lt_ctx* timing = nullptr;                           // the context whose stage timers take the launches (StageScope); null: untimed
     int *threshold_path = nullptr, *adaptive_path = nullptr;   // lt_last_threshold_path / lt_last_adaptive_path; null: nobody asks
+    int* tophat_path = nullptr;                         // lt_last_tophat_path; null: nobody asks
 };
 // filter_lane_points() (lane_tracker.py:210-238) on planes P_R / P_B of slots [first, first + n) of the arena, h x w pixels each, on
 // stream s; call_frames: the frames of the whole call this piece belongs to.  The opened mask lands in d_bits_open, or with

@@ -195,8 +195,16 @@ void launch_morph_ellipse(hipStream_t s, const uint8_t* src, uint8_t* dst, const
 // dpitch > 0: the destination has its own row pitch and per-frame stride (the padded top-hat planes the threshold walks read)
 // copy_dst (55x55 top-hat with dpitch > 0 only): the minuend is stored there as well, in the destination's layout; false
 // when that form is not available for the geometry (nothing was launched)
+// zone: scratch of the split-band form (k_tophat.hip: k_morph_split), `stride_dwords` per frame of the launch; without one, or for
+// a geometry tophat_split_form() refuses, the bands walk their halos (k_morph_runs2).  *form: 1 if the split-band form ran, else 0
+struct MorphZone { uint32_t* base = nullptr; size_t stride_dwords = 0; };
 bool launch_morph_runs(hipStream_t s, const uint8_t* src, uint8_t* dst, const uint8_t* minuend, int h, int w, int k,
-                       bool dilate, size_t plane_stride, int n, int dpitch = 0, size_t dst_stride = 0, uint8_t* copy_dst = nullptr);
+                       bool dilate, size_t plane_stride, int n, int dpitch = 0, size_t dst_stride = 0, uint8_t* copy_dst = nullptr,
+                       const MorphZone& zone = MorphZone(), int* form = nullptr);
+// geometry -> form: true where the split-band form takes (h, w) cut into `nbands` bands of `band_rows` rows (the last one shorter)
+bool tophat_split_form(int h, int w, int k, int band_rows, int nbands, bool wide);
+int tophat_split_zone_rows(int k);          // rows of a boundary zone: 56 (55x55), 28 (29x29)
+size_t tophat_split_zone_dwords(int k);     // scratch dwords per strip of a frame
 // one or two frames: the same step of the 55x55 chain of one plane and of the 29x29 chain of another in one launch; false: not launched
 bool launch_morph_one_pair(hipStream_t s, const uint8_t* src55, uint8_t* dst55, const uint8_t* min55, const uint8_t* src29, uint8_t* dst29,
                            const uint8_t* min29, int h, int w, bool dilate, size_t plane_stride, int n, int dpitch, size_t dst_stride);

@@ -44,6 +44,7 @@ struct Chain {
     // padded row pitch: the dilate launches write them so.  The greenery mask, mask_noise, rides along: a third walk with
     // window 65 over the raw Lab-b plane, which the 55x55 top-hat launch leaves in the padded layout (bpad).
     bool walk = false;
+    int tophat_path = 0;
     uint8_t *thRd = thR, *thBd = thB, *bpad = nullptr;
     int dpitch = 0;
 
@@ -73,9 +74,9 @@ struct Chain {
     }
 
     // the 55x55 top-hat of the Lab-b plane; with the greenery mask it also leaves the raw plane in the padded layout
-    int tophat_b() {
-        if (bpad && launch_morph_runs(s, t0, thBd, B, h, w, 55, true, ps, n, dpitch, a.th_pad_bytes, bpad)) return LT_OK;
-        launch_morph_runs(s, t0, thBd, B, h, w, 55, true, ps, n, dpitch, a.th_pad_bytes);
+    int tophat_b(const MorphZone& zone, int* form) {
+        if (bpad && launch_morph_runs(s, t0, thBd, B, h, w, 55, true, ps, n, dpitch, a.th_pad_bytes, bpad, zone, form)) return LT_OK;
+        launch_morph_runs(s, t0, thBd, B, h, w, 55, true, ps, n, dpitch, a.th_pad_bytes, nullptr, zone, form);
         if (bpad)   // that kernel form does not exist for this geometry / A-B switch: plain strided copies
             for (int i = 0; i < n; ++i)
                 HIP_TRY(hipMemcpy2DAsync(bpad + (size_t)i * a.th_pad_bytes, (size_t)a.th_pitch, B + (size_t)i * ps, (size_t)w, (size_t)w,
@@ -113,11 +114,22 @@ struct Chain {
                 launch_morph_runs(s, t0, thB, B, h, w, 55, true, ps, n);
             }
         } else if (form == TH_BATCH) {
-            { StageScope t(tm, ST_ERODE_R, s);  launch_morph_runs(s, R, t0, nullptr, h, w, 29, false, ps, n); }
-            { StageScope t(tm, ST_TOPHAT_R, s); launch_morph_runs(s, t0, thRd, R, h, w, 29, true, ps, n, dpitch, a.th_pad_bytes); }
-            { StageScope t(tm, ST_ERODE_B, s);  launch_morph_runs(s, B, t0, nullptr, h, w, 55, false, ps, n); }
-            { StageScope t(tm, ST_TOPHAT_B, s); const int rc = tophat_b(); if (rc) return rc; }
+            // the split-band walks' boundary zones, per slot: the four launches run one behind the other on s and share them
+            MorphZone zone;
+            if (n > 2) {   // (one or two frames: launch_morph_runs takes k_morph_one, which needs none)
+                const int rc = a.ensure_zone_scratch();
+                if (rc) return rc;
+                zone.base = a.d_zone + (size_t)first * a.zone_stride;
+                zone.stride_dwords = a.zone_stride;
+            }
+            int f29e = 0, f29d = 0, f55e = 0, f55d = 0;
+            { StageScope t(tm, ST_ERODE_R, s);  launch_morph_runs(s, R, t0, nullptr, h, w, 29, false, ps, n, 0, 0, nullptr, zone, &f29e); }
+            { StageScope t(tm, ST_TOPHAT_R, s); launch_morph_runs(s, t0, thRd, R, h, w, 29, true, ps, n, dpitch, a.th_pad_bytes, nullptr, zone, &f29d); }
+            { StageScope t(tm, ST_ERODE_B, s);  launch_morph_runs(s, B, t0, nullptr, h, w, 55, false, ps, n, 0, 0, nullptr, zone, &f55e); }
+            { StageScope t(tm, ST_TOPHAT_B, s); const int rc = tophat_b(zone, &f55d); if (rc) return rc; }
+            tophat_path = (f29e && f29d ? 1 : 0) | (f55e && f55d ? 2 : 0);
         }
+        if (env.tophat_path && p->filter_type == 0) *env.tophat_path = tophat_path;
         return LT_OK;
     }
 
