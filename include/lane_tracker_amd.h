@@ -50,7 +50,7 @@ extern "C" {
  *    plot points, radius and eccentricity of a valid first try in one host call).  Later additions, still 5:
  *    lt_search_item + lt_search_fit_list (the searches of frames of unrelated streams in one launch), lt_upload_frame_rows_list +
  *    lt_upload_frame_rest_list (the uploads of frames that lie in separate host arrays); lt_set_input_format + lt_get_input_format +
- *    lt_yuv_to_rgb (camera frames in YUV 4:2:0, NV12 or I420, converted on the device); lt_device_surface + lt_attach_device_frames +
+ *    lt_yuv_to_rgb (camera frames in YUV 4:2:0, NV12 or I420, or packed 4:2:2, YUY2 or UYVY, converted on the device); lt_device_surface + lt_attach_device_frames +
  *    lt_device_frames_rest (camera frames that already lie in device memory, read where they lie), lt_device_alloc / _free /
  *    _write / _read (device blocks for callers without a HIP binding of their own), lt_device_stream_wait; lt_viz_item +
  *    lt_search_viz_run + lt_split_panes_run + lt_split_panes_size + lt_search_viz_wait (the search visualisations and split-view
@@ -190,8 +190,17 @@ int  lt_set_streams(lt_ctx* ctx, int nstreams);
  * slot's camera frame, so that overlays, presentation and downloads find what they find in an RGB context.  Everything behind
  * the undistortion is bit for bit what an RGB context computes from the converted frames.
  * lt_get_input_format reads the setting back (coeffs may be NULL).
- * lt_yuv_to_rgb converts one host frame of h x w (even, at most 16384 each) on the device: out_rgb = h * w * 3 bytes. */
-enum lt_input_layout { LT_INPUT_RGB = 0, LT_INPUT_NV12 = 1, LT_INPUT_I420 = 2 };
+ * lt_yuv_to_rgb converts one host frame of h x w (even, at most 16384 each) on the device: out_rgb = h * w * 3 bytes.
+ *
+ * Packed YUV 4:2:2 as cameras and capture cards hand it out -- LT_INPUT_YUY2 (bytes Y0 U Y1 V; UVC webcams, SDI / HDMI capture) and
+ * LT_INPUT_UYVY (U Y0 V Y1; GMSL / FPD-Link cameras): one plane of img_h rows of 2 * img_w bytes, img_h * img_w * 2 bytes a frame,
+ * OpenCV's CV_8UC2.  The same arithmetic and coefficients with one (U, V) pair per horizontal pixel pair
+ * (cv2.cvtColor(frame, COLOR_YUV2RGB_YUY2 / _UYVY)); img_w even and at least 4, img_h any.  Everything said above for 4:2:0 holds
+ * with "rows [row0, row1) of the one plane" for the rows that are moved (2 / 3 of the bytes of the RGB form); lt_yuv_to_rgb takes a
+ * frame of h * w * 2 bytes (w even, at least 4; any h).  4:2:2 is an INPUT format only: lt_rgb_to_surfaces and
+ * lt_overlay_store_device return LT_ERR_INVALID for these two layouts, and lt_overlay_run_inplace* on a 4:2:2 context returns
+ * LT_ERR_STATE before anything is staged (a 4:2:2 context writes its annotated frames into RGB, NV12 or I420 sinks like any other). */
+enum lt_input_layout { LT_INPUT_RGB = 0, LT_INPUT_NV12 = 1, LT_INPUT_I420 = 2, LT_INPUT_YUY2 = 3, LT_INPUT_UYVY = 4 };
 #define LT_YUV_BT601 {1220542, 1673527, -852492, -409993, 2116026}   /* video range; OpenCV's constants */
 #define LT_YUV_BT709 {1220542, 1880097, -558891, -223347, 2214593}   /* video range */
 int  lt_set_input_format(lt_ctx* ctx, int layout, const int32_t coeffs[5]);
@@ -246,7 +255,8 @@ int  lt_upload_frame_rest_list(lt_ctx* ctx, const uint8_t* const* frames_rgb, in
  * chroma plane somewhere else.  Such frames are not copied: the undistortion -- the only kernel that reads camera pixels on the
  * way to a lane record -- fetches its taps from the surfaces themselves.  One lt_device_surface per frame, in the layout of the
  * context's input format: plane[0] the RGB rows (3 bytes a pixel) or the Y plane, `pitch` bytes from row to row; NV12: plane[1]
- * the rows of (U, V) pairs; I420: plane[1] the U and plane[2] the V plane; `chroma_pitch` bytes between chroma rows.  Any byte
+ * the rows of (U, V) pairs; I420: plane[1] the U and plane[2] the V plane; `chroma_pitch` bytes between chroma rows.  YUY2 / UYVY:
+ * plane[0] the one plane, `pitch` >= 2 * img_w; chroma_pitch is not read.  Any byte
  * alignment of pointers and pitches is taken (a column crop of an RGB frame starts at 3 * x0).  Results are bit for bit those of
  * the same bytes uploaded from the host.
  *
@@ -270,7 +280,7 @@ int  lt_upload_frame_rest_list(lt_ctx* ctx, const uint8_t* const* frames_rgb, in
 typedef struct lt_device_surface {
     const void* plane[3];
     int32_t pitch;               /* bytes between rows of plane[0] */
-    int32_t chroma_pitch;        /* bytes between rows of plane[1] (and plane[2]); not read in an RGB context */
+    int32_t chroma_pitch;        /* bytes between rows of plane[1] (and plane[2]); not read in an RGB or a 4:2:2 context */
 } lt_device_surface;
 int  lt_attach_device_frames(lt_ctx* ctx, const lt_device_surface* surfaces, int first_slot, int n);
 int  lt_device_frames_rest(lt_ctx* ctx, int first_slot, int n, const int32_t* rows4);
@@ -546,7 +556,8 @@ int  lt_download_overlay_wait(lt_ctx* ctx);
  * The way out that mirrors lt_attach_device_frames: the whole annotated frames of slots -- RGB, dense, in the context's own
  * memory -- are written by a kernel into lt_device_surface destinations in device memory: RGB rows at the caller's pitch, or
  * YUV 4:2:0 as an encoder takes it, NV12 or I420, planes anywhere, any pitch, any byte alignment (16-byte aligned bases and
- * pitches and a width that is a multiple of 16 take the wide kernels).  `layout` is an lt_input_layout and has nothing to do with
+ * pitches and a width that is a multiple of 16 take the wide kernels).  `layout` is an lt_input_layout -- RGB, NV12 or I420: packed
+ * 4:2:2 is an input format only, LT_ERR_INVALID here -- and has nothing to do with
  * the context's input format: an RGB camera may feed an NV12 encoder.  RGB -> YUV is OpenCV's integer arithmetic
  * (cv2.cvtColor(img, COLOR_RGB2YUV_I420), 20-bit fixed point, no chroma averaging):
  *     Y = clamp((CRY r + CGY g + CBY b + 2^19 + (16  << 20)) >> 20)     every pixel

@@ -250,7 +250,11 @@ _SIGNATURES = {
 }
 
 # camera-frame formats (lt_input_layout) and the conversion matrices {CY, CVR, CVG, CUG, CUB} of include/lane_tracker_amd.h
+# PIXEL_FORMATS is the SINK-CAPABLE SUBSET -- what a camera frame and a destination of annotated frames can both be -- and not the list
+# of formats a camera can have: that is INPUT_FORMATS, which adds packed 4:2:2 (one plane of (H, W, 2) bytes; camera frames only).
 PIXEL_FORMATS = {"rgb": 0, "nv12": 1, "i420": 2}
+INPUT_FORMATS = dict(PIXEL_FORMATS, yuy2=3, uyvy=4)                # every format a camera frame can have (pixel_format_id)
+PACKED_422 = ("yuy2", "uyvy")                                      # the names INPUT_FORMATS adds
 YUV_MATRICES = {"bt601": (1220542, 1673527, -852492, -409993, 2116026),
                 "bt709": (1220542, 1880097, -558891, -223347, 2214593)}
 
@@ -280,7 +284,7 @@ def rgb2yuv_coeffs(matrix):
 def rgb_to_surfaces(rgb_ptr, frame_stride, img_size, sink, matrix="bt601", device=0):
     """len(sink) dense RGB frames of `img_size` at device address `rgb_ptr` (a block of lt_device_alloc), `frame_stride` bytes
     apart -> the surfaces of `sink` (a device.DeviceFrames), in its pixel format (lt_rgb_to_surfaces); synchronous."""
-    layout = pixel_format_id(sink.pixel_format)
+    layout = sink_format_id(sink.pixel_format)
     k = rgb2yuv_coeffs(matrix) if layout else None
     s = np.ascontiguousarray(sink.surfaces)
     _check(load().lt_rgb_to_surfaces(int(device), C.c_void_p(int(rgb_ptr)), int(frame_stride), int(img_size[1]), int(img_size[0]), s.shape[0],
@@ -289,9 +293,16 @@ def rgb_to_surfaces(rgb_ptr, frame_stride, img_size, sink, matrix="bt601", devic
 
 def pixel_format_id(pixel_format):
     try:
-        return PIXEL_FORMATS[pixel_format]
+        return INPUT_FORMATS[pixel_format]
     except (KeyError, TypeError):
-        raise ValueError("pixel_format must be 'rgb', 'nv12' or 'i420', got %r" % (pixel_format,)) from None
+        raise ValueError("pixel_format must be 'rgb', 'nv12', 'i420', 'yuy2' or 'uyvy', got %r" % (pixel_format,)) from None
+
+
+def sink_format_id(pixel_format):
+    """pixel_format_id for a destination of annotated frames: packed 4:2:2 is an input format only."""
+    if pixel_format in PACKED_422:
+        raise ValueError("%r is an input format only: annotated frames go into 'rgb', 'nv12' or 'i420' surfaces" % (pixel_format,))
+    return pixel_format_id(pixel_format)
 
 
 def yuv_coeffs(matrix):
@@ -307,10 +318,15 @@ def yuv_coeffs(matrix):
 
 
 def frame_shape(img_size, pixel_format="rgb"):
-    """Shape of one camera frame of `img_size` = (width, height) in `pixel_format`: (H, W, 3), or (H * 3 // 2, W) for 4:2:0."""
+    """Shape of one camera frame of `img_size` = (width, height) in `pixel_format`: (H, W, 3), (H * 3 // 2, W) for 4:2:0, or
+    (H, W, 2) for packed 4:2:2 (OpenCV's CV_8UC2)."""
     w, h = int(img_size[0]), int(img_size[1])
     if pixel_format_id(pixel_format) == 0:
         return (h, w, 3)
+    if pixel_format in PACKED_422:
+        if w % 2 or w < 4 or h < 1:
+            raise ValueError("4:2:2 frames need an even width of at least 4, got %dx%d" % (w, h))
+        return (h, w, 2)
     if w % 2 or h % 2:
         raise ValueError("4:2:0 frames need an even width and height, got %dx%d" % (w, h))
     return (h * 3 // 2, w)
@@ -741,8 +757,9 @@ class Context:
     # -- data movement
     def set_input_format(self, pixel_format="rgb", yuv_matrix="bt601"):
         """The pixel format of the camera frames this context takes, once, before its first upload: 'rgb' (the default), or
-        'nv12' / 'i420' -- frames of shape (H * 3 // 2, W) as OpenCV holds them, converted on the device with `yuv_matrix`
-        ('bt601', 'bt709', or five integers).  Every upload method then takes such frames."""
+        'nv12' / 'i420' -- frames of shape (H * 3 // 2, W) as OpenCV holds them -- or packed 4:2:2, 'yuy2' / 'uyvy' -- frames of shape
+        (H, W, 2) -- converted on the device with `yuv_matrix` ('bt601', 'bt709', or five integers).  Every upload method then takes
+        such frames."""
         layout = pixel_format_id(pixel_format)
         tail = frame_shape((self.img_w, self.img_h), pixel_format)
         k = yuv_coeffs(yuv_matrix) if layout else None
@@ -753,23 +770,30 @@ class Context:
         """-> (pixel format name, the five conversion coefficients)."""
         layout, k = C.c_int(0), np.zeros(5, np.int32)
         _check(self.lib.lt_get_input_format(self._h, C.byref(layout), k.ctypes.data))
-        return {v: n for n, v in PIXEL_FORMATS.items()}[layout.value], tuple(int(v) for v in k)
+        return {v: n for n, v in INPUT_FORMATS.items()}[layout.value], tuple(int(v) for v in k)
 
     def _frames(self, frames):
         """`frames` as the C-contiguous u8 block (n,) + one frame's shape; ValueError for frames of another shape."""
         f = _u8(frames)
         tail = self._frame_tail
         if f.shape[-len(tail):] != tail or f.ndim > len(tail) + 1:
-            if len(tail) == 3:
+            if tail[-1] == 3 and len(tail) == 3:
                 return f.reshape((-1,) + tail)           # (RGB: anything of the right size, as ever)
             raise ValueError("expected camera frames of shape %r, got %r" % (tail, f.shape))
         return f.reshape((-1,) + tail)
 
     def yuv_to_rgb(self, frame, layout="nv12", matrix="bt601"):
-        """One 4:2:0 frame (H * 3 // 2, W) -> RGB (H, W, 3), on the device (lt_yuv_to_rgb)."""
+        """One 4:2:0 frame (H * 3 // 2, W), or one packed 4:2:2 frame (H, W, 2), -> RGB (H, W, 3), on the device (lt_yuv_to_rgb)."""
         a = _u8(frame)
         if pixel_format_id(layout) == 0:
-            raise ValueError("layout must be 'nv12' or 'i420'")
+            raise ValueError("layout must be 'nv12', 'i420', 'yuy2' or 'uyvy'")
+        if layout in PACKED_422:
+            if a.ndim != 3 or a.shape[2] != 2 or a.shape[1] % 2 or a.shape[1] < 4 or a.shape[0] < 1:
+                raise ValueError("a 4:2:2 frame is an array of shape (H, W, 2) with W even and at least 4, got %r" % (a.shape,))
+            out = np.empty((a.shape[0], a.shape[1], 3), np.uint8)
+            k = yuv_coeffs(matrix)
+            _check(self.lib.lt_yuv_to_rgb(self._h, a.ctypes.data, a.shape[0], a.shape[1], pixel_format_id(layout), k.ctypes.data, out.ctypes.data))
+            return out
         if a.ndim != 2 or a.shape[0] % 3 or a.shape[1] % 2 or (a.shape[0] // 3 * 2) % 2:
             raise ValueError("a 4:2:0 frame is a 2-D array of shape (H * 3 // 2, W) with H and W even, got %r" % (a.shape,))
         h, w = a.shape[0] // 3 * 2, a.shape[1]
@@ -845,7 +869,7 @@ class Context:
         """The front end of slots first, first + 1, ... reads `frames` (a device.DeviceFrames) where they lie in device memory
         (lt_attach_device_frames); nothing is copied.  Returns `frames`: keep it -- and the memory it describes -- alive and
         unchanged until a call that waits for work launched over these slots afterwards (download_record, sync)."""
-        frames.check_for((self.img_w, self.img_h), {3: "rgb"}.get(len(self._frame_tail)) or self.input_format()[0])
+        frames.check_for((self.img_w, self.img_h), "rgb" if self._frame_tail[-1] == 3 and len(self._frame_tail) == 3 else self.input_format()[0])
         frames.wait_for_producer()
         s = np.ascontiguousarray(frames.surfaces)
         _check(self.lib.lt_attach_device_frames(self._h, s.ctypes.data, first, s.shape[0]))
@@ -1034,7 +1058,7 @@ class Context:
         bus.  The sink's memory is final after store_wait() or sync(); keep it alive until then."""
         if sink.img_size != (self.img_w, self.img_h):
             raise ValueError("expected a sink of %dx%d frames, got %dx%d" % ((self.img_w, self.img_h) + sink.img_size))
-        layout = pixel_format_id(sink.pixel_format)
+        layout = sink_format_id(sink.pixel_format)
         k = rgb2yuv_coeffs(matrix) if layout else None
         s = np.ascontiguousarray(sink.surfaces)
         _check(self.lib.lt_overlay_store_device(self._h, int(first), s.shape[0], s.ctypes.data, layout, None if k is None else k.ctypes.data))
@@ -1052,6 +1076,8 @@ class Context:
                 keep += [buf, t]
                 text = C.addressof(t)
         k = None
+        if self.input_format()[0] in PACKED_422:
+            raise ValueError("packed 4:2:2 is an input format only: nothing is drawn into such surfaces")
         if pixel_format_id(self.input_format()[0]):
             if matrix is None:
                 raise ValueError("drawing into 4:2:0 surfaces needs an RGB -> YUV matrix ('bt601', 'bt709' or eight integers)")

@@ -4,6 +4,9 @@
 //   k_undistort_rows_yuv  the same over a 4:2:0 frame (NV12 / I420): cv2.cvtColor(YUV2RGB_*) of every tap, then the blend
 //   k_undistort_rows_surf, k_undistort_rows_yuv_surf  the same two over frames in the caller's device memory (surface table)
 //                      -- all of them entry points of one walk, undistort_walk<source, pixel format>
+//   k_undistort422, k_undistort422_surf, k_undistort422_cal, k_undistort422_cal_surf  the walk over packed 4:2:2 frames (YUY2 / UYVY):
+//                      slots, surfaces, and the table-per-slot forms of both; k_yuv422_rows_to_rgb, k_surf422_rows_to_rgb: their rows
+//                      as RGB (cv2.cvtColor(YUV2RGB_YUY2 / _UYVY)) for whoever shows the camera frame
 //   k_undistort_cal*, k_warp_cal  the table-per-slot forms of the walk's seven entry points and of the warp: every slot of a launch with
 //                      the remap tables of its own calibration set (lt_add_calibration), for slices that mix sets
 //   k_yuv_rows_to_rgb, k_surf_rows_to_rgb  cv2.cvtColor(YUV2RGB_NV12 / _I420) of a run of rows (for whoever shows the camera
@@ -169,6 +172,40 @@ struct Yuv420 {
     __device__ __forceinline__ void decode(const Taps& t, uint32_t& a0, uint32_t& a1, uint32_t& b0, uint32_t& b1) const {
         a0 = tap(t.ya, t.ca, t.va, ysh0, cs0), a1 = tap(t.ya, t.ca, t.va, ysh1, cs1);
         b0 = tap(t.yb, t.cb, t.vb, ysh0, cs0), b1 = tap(t.yb, t.cb, t.vb, ysh1, cs1);
+    }
+};
+
+// Packed 4:2:2, one plane of 2 W bytes per row.  ORDER 0: YUY2 (Y0 U Y1 V), 1: UYVY (U Y0 V Y1).  The two taps of a tap row lie inside
+// two consecutive macropixels: one 8-byte window per tap row, as for RGB -- 2 loads per frame.  The window starts at macropixel
+// min(cxl >> 1, W / 2 - 2) (yuv_arith.h: the position arithmetic, which the CPU tests compile for the host), so it never leaves its
+// row.  Each tap picks the dword of its macropixel (a select; no 64-bit shift) and is converted before the blend, as for 4:2:0; the
+// two taps of a row may or may not share a macropixel, so both are converted.
+template <int ORDER>
+struct Yuv422 {
+    typedef uint64_t Window;
+    static constexpr int DENSE_PAD = 16;    // a slot's staging frame: 16 bytes of padding behind the last slot (the third dword of the last window's aligned load)
+    struct Taps { uint64_t a, b; };          // the windows of the upper (a) and the lower (b) tap row
+    YuvCoef k;
+    int last_mp;                             // W / 2 - 2
+    int col, hi0, hi1, ysh0, ysh1;
+    __device__ __forceinline__ void place(const TapCols& c) {
+        const int mp = ya::win422_mp(c.cxl, last_mp);
+        col = ya::win422_col(mp);
+        hi0 = ya::win422_dword(c.cx0, mp), hi1 = ya::win422_dword(c.cx1, mp);
+        ysh0 = ya::ysh422(ORDER, c.cx0), ysh1 = ya::ysh422(ORDER, c.cx1);
+    }
+    __device__ __forceinline__ static PlaneGeom plane(const FrontEndGeom& g, int) { return PlaneGeom{g.img_h, 2 * g.img_w, 0u}; }
+    template <class Source>
+    __device__ __forceinline__ Taps fetch(const Source& src, const typename Source::Frame& f, const FrontEndGeom& g, int cy0, int cy1) const {
+        const auto p0 = src.plane(f, plane(g, 0), 0);
+        return Taps{src.template window<Window>(p0, cy0, col), src.template window<Window>(p0, cy1, col)};
+    }
+    __device__ __forceinline__ uint32_t tap(uint64_t w, int hi, int ysh) const {
+        return ya::yuv422_pixel(hi ? (uint32_t)(w >> 32) : (uint32_t)w, ORDER, ysh, k);
+    }
+    __device__ __forceinline__ void decode(const Taps& t, uint32_t& a0, uint32_t& a1, uint32_t& b0, uint32_t& b1) const {
+        a0 = tap(t.a, hi0, ysh0), a1 = tap(t.a, hi1, ysh1);
+        b0 = tap(t.b, hi0, ysh0), b1 = tap(t.b, hi1, ysh1);
     }
 };
 
@@ -393,6 +430,44 @@ __global__ __launch_bounds__(256) void k_undistort_cal_yuv_surf(const SurfEntry*
                    SurfSource{tab}, Yuv420<LAYOUT>{k}, SlotTables{sets, &ids});
 }
 
+// ... and the eight entry points of the packed 4:2:2 formats (ORDER 0: YUY2, 1: UYVY): slots, surfaces, and the table-per-slot forms
+// of both.
+template <int ORDER>
+__global__ __launch_bounds__(256) void k_undistort422(const uint8_t* __restrict__ yuv, size_t yuv_stride, YuvCoef k,
+                                                     const int16_t* __restrict__ uxy,
+                                                     const uint16_t* __restrict__ ufrac, FrontEndGeom g,
+                                                     uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb,
+                                                     int remap) {
+    undistort_walk(WalkArgs{uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap},
+                   SlotSource<true>{yuv, yuv_stride}, Yuv422<ORDER>{k, (g.img_w >> 1) - 2});
+}
+
+template <int ORDER>
+__global__ __launch_bounds__(256) void k_undistort422_surf(const SurfEntry* __restrict__ tab, YuvCoef k,
+                                                          const int16_t* __restrict__ uxy,
+                                                          const uint16_t* __restrict__ ufrac, FrontEndGeom g,
+                                                          uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb,
+                                                          int remap) {
+    undistort_walk(WalkArgs{uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap},
+                   SurfSource{tab}, Yuv422<ORDER>{k, (g.img_w >> 1) - 2});
+}
+
+template <int ORDER>
+__global__ __launch_bounds__(256) void k_undistort422_cal(const uint8_t* __restrict__ yuv, size_t yuv_stride, YuvCoef k,
+                                                         const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
+                                                         uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int remap) {
+    undistort_walk(WalkArgs{nullptr, nullptr, g, und, und_px, first_slot, n, 1, remap},
+                   SlotSource<true>{yuv, yuv_stride}, Yuv422<ORDER>{k, (g.img_w >> 1) - 2}, SlotTables{sets, &ids});
+}
+
+template <int ORDER>
+__global__ __launch_bounds__(256) void k_undistort422_cal_surf(const SurfEntry* __restrict__ tab, YuvCoef k,
+                                                              const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
+                                                              uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int remap) {
+    undistort_walk(WalkArgs{nullptr, nullptr, g, und, und_px, first_slot, n, 1, remap},
+                   SurfSource{tab}, Yuv422<ORDER>{k, (g.img_w >> 1) - 2}, SlotTables{sets, &ids});
+}
+
 // ---- 4:2:0 rows -> RGB rows ---------------------------------------------------------------------------------------------------
 // Rows [r0, r1) of 4:2:0 frames -> the same rows of RGB frames (3 B/px): a streaming kernel for whoever shows the camera frame.
 // The planes of one frame: the dense entry points compute them from the frame's base, the surface ones read them from the entry.
@@ -520,6 +595,80 @@ template <int LAYOUT>
 __global__ __launch_bounds__(256) void k_surf_rows_to_rgb_any(SurfChunk ch, YuvCoef k, uint8_t* __restrict__ rgb, size_t rgb_stride, int w, int r0, int r1) {
     yuv_rows2x2<LAYOUT>(surf_planes(ch.e[blockIdx.z]), k, rgb + (size_t)blockIdx.z * rgb_stride, w, r0, r1,
                         (int)(blockIdx.x * blockDim.x + threadIdx.x), (r0 >> 1) + (int)blockIdx.y);
+}
+
+// ---- packed 4:2:2 rows -> RGB rows ---------------------------------------------------------------------------------------------
+// The same role for YUY2 / UYVY frames: row y of the one plane -> row y of the RGB frame.  Both bodies take the plane pointer and
+// pitch of a frame: the dense entry points pass a slot's staging frame (pitch 2 w), the surface ones an entry of the chunk.
+struct Plane422 { const uint8_t* p; int pitch; };
+
+// One thread owns the 16 columns from x0 of row y: 8 macropixels in two 16-byte loads, each macropixel's three chroma terms computed
+// once for its two pixels, 48 bytes in three 16-byte stores.
+template <int ORDER>
+__device__ __forceinline__ void yuv422_row16(const Plane422& s, YuvCoef k, uint8_t* dst, int w, int y, int x0) {
+    if (x0 >= w) return;
+    const uint4* in = reinterpret_cast<const uint4*>(s.p + (size_t)y * s.pitch + 2 * x0);
+    const uint4 q0 = in[0], q1 = in[1];
+    const uint32_t m[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+    uint32_t d[12];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {                          // two macropixels (four pixels) -> three dwords
+        uint32_t px[4];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const uint32_t mp = m[2 * j + i];
+            const Chroma c = yuv_chroma((int)((mp >> ya::ush422(ORDER)) & 255u), (int)((mp >> ya::vsh422(ORDER)) & 255u), k);
+            px[2 * i] = yuv_pixel((int)((mp >> ya::ysh422(ORDER, 0)) & 255u), c, k);
+            px[2 * i + 1] = yuv_pixel((int)((mp >> ya::ysh422(ORDER, 1)) & 255u), c, k);
+        }
+        d[3 * j] = px[0] | (px[1] << 24);
+        d[3 * j + 1] = (px[1] >> 8) | (px[2] << 16);
+        d[3 * j + 2] = (px[2] >> 16) | (px[3] << 8);
+    }
+    uint4* o = reinterpret_cast<uint4*>(dst + ((size_t)y * w + x0) * 3);
+    o[0] = make_uint4(d[0], d[1], d[2], d[3]);
+    o[1] = make_uint4(d[4], d[5], d[6], d[7]);
+    o[2] = make_uint4(d[8], d[9], d[10], d[11]);
+}
+
+// the same for any even width, any pitch and any alignment: one thread per macropixel (index mx of row y), byte accesses
+template <int ORDER>
+__device__ __forceinline__ void yuv422_row_mp(const Plane422& s, YuvCoef k, uint8_t* dst, int w, int y, int mx) {
+    if (2 * mx >= w) return;
+    const uint8_t* b = s.p + (size_t)y * s.pitch + 4 * mx;
+    const Chroma c = yuv_chroma(b[ya::ush422(ORDER) >> 3], b[ya::vsh422(ORDER) >> 3], k);
+    uint8_t* o = dst + ((size_t)y * w + 2 * mx) * 3;
+    for (int dx = 0; dx < 2; ++dx) {
+        const uint32_t px = yuv_pixel(b[ya::ysh422(ORDER, dx) >> 3], c, k);
+        o[3 * dx] = (uint8_t)px;
+        o[3 * dx + 1] = (uint8_t)(px >> 8);
+        o[3 * dx + 2] = (uint8_t)(px >> 16);
+    }
+}
+
+// rows [r0, r0 + gridDim.y) of the slots' dense staging frames (frame blockIdx.z at yuv + blockIdx.z * yuv_stride) ...
+template <int ORDER>
+__global__ __launch_bounds__(256) void k_yuv422_rows_to_rgb(const uint8_t* __restrict__ yuv, size_t yuv_stride, YuvCoef k,
+                                                           uint8_t* __restrict__ rgb, size_t rgb_stride, int w, int r0) {
+    yuv422_row16<ORDER>(Plane422{yuv + (size_t)blockIdx.z * yuv_stride, 2 * w}, k, rgb + (size_t)blockIdx.z * rgb_stride, w,
+                        r0 + (int)blockIdx.y, (int)(blockIdx.x * blockDim.x + threadIdx.x) * 16);
+}
+template <int ORDER>
+__global__ __launch_bounds__(256) void k_yuv422_rows_to_rgb_any(const uint8_t* __restrict__ yuv, size_t yuv_stride, YuvCoef k,
+                                                               uint8_t* __restrict__ rgb, size_t rgb_stride, int w, int r0) {
+    yuv422_row_mp<ORDER>(Plane422{yuv + (size_t)blockIdx.z * yuv_stride, 2 * w}, k, rgb + (size_t)blockIdx.z * rgb_stride, w,
+                         r0 + (int)blockIdx.y, (int)(blockIdx.x * blockDim.x + threadIdx.x));
+}
+// ... and of surfaces (frame blockIdx.z is entry blockIdx.z of the chunk)
+template <int ORDER>
+__global__ __launch_bounds__(256) void k_surf422_rows_to_rgb(SurfChunk ch, YuvCoef k, uint8_t* __restrict__ rgb, size_t rgb_stride, int w, int r0) {
+    yuv422_row16<ORDER>(Plane422{reinterpret_cast<const uint8_t*>(ch.e[blockIdx.z].plane[0]), ch.e[blockIdx.z].pitch}, k,
+                        rgb + (size_t)blockIdx.z * rgb_stride, w, r0 + (int)blockIdx.y, (int)(blockIdx.x * blockDim.x + threadIdx.x) * 16);
+}
+template <int ORDER>
+__global__ __launch_bounds__(256) void k_surf422_rows_to_rgb_any(SurfChunk ch, YuvCoef k, uint8_t* __restrict__ rgb, size_t rgb_stride, int w, int r0) {
+    yuv422_row_mp<ORDER>(Plane422{reinterpret_cast<const uint8_t*>(ch.e[blockIdx.z].plane[0]), ch.e[blockIdx.z].pitch}, k,
+                         rgb + (size_t)blockIdx.z * rgb_stride, w, r0 + (int)blockIdx.y, (int)(blockIdx.x * blockDim.x + threadIdx.x));
 }
 
 // Rows [r0, r1) of RGB surfaces -> the same rows of the slots' camera frames (row_bytes = 3 w, dense): a pitched row copy, one
@@ -945,7 +1094,9 @@ void launch_undistort_rows(hipStream_t s, FrameSource src, int layout, YuvCoef k
     if (src.tab) {
         if (layout == 0) hipLaunchKernelGGL(k_undistort_rows_surf, grid, block, 0, s, src.tab, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
         else if (layout == 1) hipLaunchKernelGGL(k_undistort_rows_yuv_surf<1>, grid, block, 0, s, src.tab, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
-        else hipLaunchKernelGGL(k_undistort_rows_yuv_surf<2>, grid, block, 0, s, src.tab, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
+        else if (layout == 2) hipLaunchKernelGGL(k_undistort_rows_yuv_surf<2>, grid, block, 0, s, src.tab, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
+        else if (layout == 3) hipLaunchKernelGGL(k_undistort422_surf<0>, grid, block, 0, s, src.tab, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
+        else hipLaunchKernelGGL(k_undistort422_surf<1>, grid, block, 0, s, src.tab, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
     } else if (layout == 0) {
         static const bool unaligned = [] { const char* e = LT_EXP_ENV("LT_UNDISTORT_UNALIGNED"); return e && e[0] == '1'; }();   // A/B
         if (!unaligned && ((uintptr_t)src.frames & 3) == 0 && (src.stride & 3) == 0 && src.stride < (1u << 30))   // (a larger frame: 64-bit addresses)
@@ -954,8 +1105,12 @@ void launch_undistort_rows(hipStream_t s, FrameSource src, int layout, YuvCoef k
             hipLaunchKernelGGL(k_undistort_rows<false>, grid, block, 0, s, src.frames, src.stride, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
     } else if (layout == 1) {
         hipLaunchKernelGGL(k_undistort_rows_yuv<1>, grid, block, 0, s, src.frames, src.stride, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
-    } else {
+    } else if (layout == 2) {
         hipLaunchKernelGGL(k_undistort_rows_yuv<2>, grid, block, 0, s, src.frames, src.stride, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
+    } else if (layout == 3) {
+        hipLaunchKernelGGL(k_undistort422<0>, grid, block, 0, s, src.frames, src.stride, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
+    } else {
+        hipLaunchKernelGGL(k_undistort422<1>, grid, block, 0, s, src.frames, src.stride, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
     }
 }
 
@@ -970,9 +1125,25 @@ static void launch_rows_to_rgb(hipStream_t s, int layout, K wide1, K wide2, K an
         hipLaunchKernelGGL(layout == 1 ? any1 : any2, dim3((unsigned)((w / 2 + 255) / 256), crows, (unsigned)n), dim3(256), 0, s, args...);
 }
 
+// The packed 4:2:2 row conversion of n frames: one launch row per frame row; wide / any as above, [0]: YUY2, [1]: UYVY.
+template <class K, class... Args>
+static void launch_rows422_to_rgb(hipStream_t s, int layout, K wide0, K wide1, K any0, K any1, size_t bits, int w, int r0, int r1, int n, Args... args) {
+    const unsigned rows = (unsigned)(r1 - r0);
+    if ((w & 15) == 0 && (bits & 15) == 0)
+        hipLaunchKernelGGL(layout == 3 ? wide0 : wide1, dim3((unsigned)((w / 16 + 63) / 64), rows, (unsigned)n), dim3(64), 0, s, args...);
+    else
+        hipLaunchKernelGGL(layout == 3 ? any0 : any1, dim3((unsigned)((w / 2 + 255) / 256), rows, (unsigned)n), dim3(256), 0, s, args...);
+}
+
 void launch_yuv_rows_to_rgb(hipStream_t s, int layout, const uint8_t* yuv, size_t yuv_stride, YuvCoef k, uint8_t* rgb,
                             size_t rgb_stride, int h, int w, int r0, int r1, int n) {
     if (n <= 0 || r1 <= r0) return;
+    if (layout >= 3) {
+        launch_rows422_to_rgb(s, layout, k_yuv422_rows_to_rgb<0>, k_yuv422_rows_to_rgb<1>, k_yuv422_rows_to_rgb_any<0>, k_yuv422_rows_to_rgb_any<1>,
+                              yuv_stride | rgb_stride | (size_t)(uintptr_t)yuv | (size_t)(uintptr_t)rgb, w, r0, r1, n,
+                              yuv, yuv_stride, k, rgb, rgb_stride, w, r0);
+        return;
+    }
     launch_rows_to_rgb(s, layout, k_yuv_rows_to_rgb<1>, k_yuv_rows_to_rgb<2>, k_yuv_rows_to_rgb_any<1>, k_yuv_rows_to_rgb_any<2>,
                        yuv_stride | rgb_stride | (size_t)(uintptr_t)yuv | (size_t)(uintptr_t)rgb, w, r0, r1, n,
                        yuv, yuv_stride, k, rgb, rgb_stride, h, w, r0, r1);
@@ -998,7 +1169,7 @@ void launch_surf_rows_to_rgb(hipStream_t s, int layout, const SurfEntry* entries
         size_t bits = rgb_stride | (size_t)(uintptr_t)dst;   // every base and pitch of the launch a multiple of 16?
         for (int j = 0; j < m; ++j) {
             bits |= (size_t)ch.e[j].plane[0] | (size_t)ch.e[j].pitch;
-            if (layout != 0) bits |= (size_t)ch.e[j].plane[1] | (size_t)ch.e[j].cpitch;
+            if (layout == 1 || layout == 2) bits |= (size_t)ch.e[j].plane[1] | (size_t)ch.e[j].cpitch;
             if (layout == 2) bits |= (size_t)ch.e[j].plane[2];
         }
         if (layout == 0) {
@@ -1007,6 +1178,9 @@ void launch_surf_rows_to_rgb(hipStream_t s, int layout, const SurfEntry* entries
                 hipLaunchKernelGGL(k_surf_copy_rows<true>, dim3((unsigned)((row_bytes / 16 + 255) / 256), (unsigned)(r1 - r0), (unsigned)m), dim3(256), 0, s, ch, dst, rgb_stride, row_bytes, r0);
             else
                 hipLaunchKernelGGL(k_surf_copy_rows<false>, dim3((unsigned)((row_bytes + 255) / 256), (unsigned)(r1 - r0), (unsigned)m), dim3(256), 0, s, ch, dst, rgb_stride, row_bytes, r0);
+        } else if (layout >= 3) {
+            launch_rows422_to_rgb(s, layout, k_surf422_rows_to_rgb<0>, k_surf422_rows_to_rgb<1>, k_surf422_rows_to_rgb_any<0>, k_surf422_rows_to_rgb_any<1>,
+                                  bits, w, r0, r1, m, ch, k, dst, rgb_stride, w, r0);
         } else {
             launch_rows_to_rgb(s, layout, k_surf_rows_to_rgb<1>, k_surf_rows_to_rgb<2>, k_surf_rows_to_rgb_any<1>, k_surf_rows_to_rgb_any<2>,
                                bits, w, r0, r1, m, ch, k, dst, rgb_stride, w, r0, r1);
@@ -1050,7 +1224,9 @@ void launch_undistort_cal(hipStream_t s, FrameSource src, int layout, YuvCoef k,
         if (src.tab) {
             if (layout == 0) hipLaunchKernelGGL(k_undistort_cal_surf, grid, block, 0, s, src.tab, sets, ci, g, und, und_px, fs, m, remap);
             else if (layout == 1) hipLaunchKernelGGL(k_undistort_cal_yuv_surf<1>, grid, block, 0, s, src.tab, k, sets, ci, g, und, und_px, fs, m, remap);
-            else hipLaunchKernelGGL(k_undistort_cal_yuv_surf<2>, grid, block, 0, s, src.tab, k, sets, ci, g, und, und_px, fs, m, remap);
+            else if (layout == 2) hipLaunchKernelGGL(k_undistort_cal_yuv_surf<2>, grid, block, 0, s, src.tab, k, sets, ci, g, und, und_px, fs, m, remap);
+            else if (layout == 3) hipLaunchKernelGGL(k_undistort422_cal_surf<0>, grid, block, 0, s, src.tab, k, sets, ci, g, und, und_px, fs, m, remap);
+            else hipLaunchKernelGGL(k_undistort422_cal_surf<1>, grid, block, 0, s, src.tab, k, sets, ci, g, und, und_px, fs, m, remap);
         } else if (layout == 0) {
             if (((uintptr_t)frames & 3) == 0 && (src.stride & 3) == 0 && src.stride < (1u << 30))
                 hipLaunchKernelGGL(k_undistort_cal<true>, grid, block, 0, s, frames, src.stride, sets, ci, g, und, und_px, fs, m, remap);
@@ -1058,8 +1234,12 @@ void launch_undistort_cal(hipStream_t s, FrameSource src, int layout, YuvCoef k,
                 hipLaunchKernelGGL(k_undistort_cal<false>, grid, block, 0, s, frames, src.stride, sets, ci, g, und, und_px, fs, m, remap);
         } else if (layout == 1) {
             hipLaunchKernelGGL(k_undistort_cal_yuv<1>, grid, block, 0, s, frames, src.stride, k, sets, ci, g, und, und_px, fs, m, remap);
-        } else {
+        } else if (layout == 2) {
             hipLaunchKernelGGL(k_undistort_cal_yuv<2>, grid, block, 0, s, frames, src.stride, k, sets, ci, g, und, und_px, fs, m, remap);
+        } else if (layout == 3) {
+            hipLaunchKernelGGL(k_undistort422_cal<0>, grid, block, 0, s, frames, src.stride, k, sets, ci, g, und, und_px, fs, m, remap);
+        } else {
+            hipLaunchKernelGGL(k_undistort422_cal<1>, grid, block, 0, s, frames, src.stride, k, sets, ci, g, und, und_px, fs, m, remap);
         }
     }
 }

@@ -834,13 +834,18 @@ int lt_set_streams(lt_ctx* c, int nstreams) {
     return LT_OK;
 }
 
-// ---- YUV 4:2:0 input ----------------------------------------------------------------------------------
+// ---- YUV input: 4:2:0 (NV12 / I420) and packed 4:2:2 (YUY2 / UYVY) ---------------------------------------
 // OpenCV's 20-bit fixed-point conversion with the caller's five coefficients {CY, CVR, CVG, CUG, CUB}.  The kernels multiply with
 // 24-bit instructions and add in int32: CY positive, every magnitude below 2^23, and no intermediate beyond int32.
+static inline bool is_422(int layout) { return layout == LT_INPUT_YUY2 || layout == LT_INPUT_UYVY; }
 static int check_yuv_format(int layout, const int32_t* k, int h, int w) {
-    if (layout != LT_INPUT_NV12 && layout != LT_INPUT_I420) return fail(LT_ERR_INVALID, "input layout must be RGB (0), NV12 (1) or I420 (2)");
-    if (!k) return fail(LT_ERR_INVALID, "a 4:2:0 layout needs its five conversion coefficients");
-    if (h < 2 || w < 2 || (h & 1) || (w & 1)) return fail(LT_ERR_INVALID, "4:2:0 frames need an even width and height, got %dx%d", w, h);
+    if (layout != LT_INPUT_NV12 && layout != LT_INPUT_I420 && !is_422(layout))
+        return fail(LT_ERR_INVALID, "input layout must be RGB (0), NV12 (1), I420 (2), YUY2 (3) or UYVY (4)");
+    if (!k) return fail(LT_ERR_INVALID, "a YUV layout needs its five conversion coefficients");
+    if (is_422(layout)) {
+        // (two macropixels a row at the least: the 8-byte window of a tap row lies inside its row)
+        if (h < 1 || w < 4 || (w & 1)) return fail(LT_ERR_INVALID, "4:2:2 frames need an even width of at least 4, got %dx%d", w, h);
+    } else if (h < 2 || w < 2 || (h & 1) || (w & 1)) return fail(LT_ERR_INVALID, "4:2:0 frames need an even width and height, got %dx%d", w, h);
     const long long lim = 1LL << 23;
     if (k[0] <= 0 || k[0] >= lim) return fail(LT_ERR_INVALID, "the luma coefficient must be in (0, 2^23)");
     for (int i = 1; i < 5; ++i)
@@ -862,7 +867,15 @@ int lt_set_input_format(lt_ctx* c, int layout, const int32_t* coeffs) {
     if (layout == LT_INPUT_RGB) {
         dev_free(c->d_yuv);
     } else {
-        if (c->capacity > 0 && !c->d_yuv && (rc = dev_alloc(&c->d_yuv, (size_t)c->capacity * c->yuv_stride + 16))) return rc;
+        // the staging frame of a slot: h w 3 / 2 bytes (4:2:0) or h w 2 (4:2:2), slots a multiple of 16 apart
+        const size_t bytes = is_422(layout) ? c->frame_bytes / 3 * 2 : c->frame_bytes / 2, stride = (bytes + 15) & ~(size_t)15;
+        if (stride != c->yuv_stride) dev_free(c->d_yuv);
+        c->yuv_bytes = bytes;
+        c->yuv_stride = stride;
+        if (c->capacity > 0 && !c->d_yuv && (rc = dev_alloc(&c->d_yuv, (size_t)c->capacity * c->yuv_stride + 16))) {
+            c->in_layout = LT_INPUT_RGB;     // (no staging: the context falls back to what needs none)
+            return rc;
+        }
         std::memcpy(c->yuv_coef, coeffs, sizeof c->yuv_coef);
     }
     c->in_layout = layout;
@@ -886,6 +899,8 @@ static int yuv_copy(lt_ctx* c, const uint8_t* frames, int first, int n, int r0, 
         return (int)LT_OK;
     };
     int rc = LT_OK;
+    if (is_422(c->in_layout))            // one plane of 2 W bytes a row: its rows [r0, r1); no chroma rows
+        return r1 > r0 ? piece((size_t)r0 * 2 * W, (size_t)(r1 - r0) * 2 * W) : rc;
     if (r1 > r0 && c1 > c0 && r0 == 0 && r1 == c->calib.img_h && c0 == 0 && c1 == c->calib.img_h / 2) return piece(0, c->yuv_bytes);
     if (r1 > r0 && (rc = piece((size_t)r0 * W, (size_t)(r1 - r0) * W))) return rc;
     if (c1 <= c0) return rc;
@@ -1303,7 +1318,7 @@ extern "C" {
 namespace {
 int check_surfaces(lt_ctx* c, const lt_device_surface* s, int n, SurfEntry* out) {
     const int H = c->calib.img_h, W = c->calib.img_w, layout = c->in_layout;
-    const int row = layout == LT_INPUT_RGB ? 3 * W : W, crow = layout == LT_INPUT_NV12 ? W : W / 2;
+    const int row = layout == LT_INPUT_RGB ? 3 * W : is_422(layout) ? 2 * W : W, crow = layout == LT_INPUT_NV12 ? W : W / 2;
     constexpr int PITCH_MAX = (1 << 23) - 1;             // the kernels multiply rows and pitches with 24-bit instructions
     KnownRange memo;
     for (int k = 0; k < n; ++k) {
@@ -1315,7 +1330,7 @@ int check_surfaces(lt_ctx* c, const lt_device_surface* s, int n, SurfEntry* out)
         int rc = check_plane(c->device, f.plane[0], ext, k, 0, memo);
         if (rc) return rc;
         out[k] = SurfEntry{{(uint64_t)(uintptr_t)f.plane[0], 0, 0}, f.pitch, 0};
-        if (layout == LT_INPUT_RGB) continue;
+        if (layout == LT_INPUT_RGB || is_422(layout)) continue;      // one plane; chroma_pitch is not read
         if (f.chroma_pitch < crow) return fail(LT_ERR_INVALID, "surface %d: chroma pitch %d is below the row's %d bytes", k, (int)f.chroma_pitch, crow);
         if (f.chroma_pitch > PITCH_MAX) return fail(LT_ERR_INVALID, "surface %d: chroma pitch %d is too large", k, (int)f.chroma_pitch);
         const size_t cext = (size_t)f.chroma_pitch * (size_t)(H / 2 - 1) + (size_t)crow;
@@ -2425,20 +2440,21 @@ int lt_bilateral_adaptive_threshold(lt_ctx* c, const uint8_t* img, int h, int w,
     return LT_OK;
 }
 
-// one 4:2:0 host frame of any even size -> RGB, on the device (cv2.cvtColor(frame, COLOR_YUV2RGB_NV12 / _I420) with the given matrix)
+// one 4:2:0 host frame of any even size (h w 3 / 2 bytes), or one packed 4:2:2 frame of any even width (h w 2 bytes) -> RGB, on the
+// device (cv2.cvtColor(frame, COLOR_YUV2RGB_NV12 / _I420 / _YUY2 / _UYVY) with the given matrix)
 int lt_yuv_to_rgb(lt_ctx* c, const uint8_t* frame, int h, int w, int layout, const int32_t* coeffs, uint8_t* out_rgb) {
     if (!c || !frame || !out_rgb) return fail(LT_ERR_INVALID, "null argument");
     int rc = check_yuv_format(layout, coeffs, h, w);
     if (rc) return rc;
     if (h > 16384 || w > 16384) return fail(LT_ERR_INVALID, "bad image size (at most 16384 x 16384)");
     if ((rc = set_device(c))) return rc;
-    const size_t px = (size_t)h * w;
+    const size_t px = (size_t)h * w, in_bytes = is_422(layout) ? px * 2 : px * 3 / 2;
     uint8_t *d_in = nullptr, *d_out = nullptr;
-    if ((rc = dev_alloc(&d_in, px * 3 / 2))) return rc;
+    if ((rc = dev_alloc(&d_in, in_bytes))) return rc;
     if ((rc = dev_alloc(&d_out, px * 3))) { dev_free(d_in); return rc; }
-    hipError_t e = hipMemcpyAsync(d_in, frame, px * 3 / 2, hipMemcpyHostToDevice, c->stream);
+    hipError_t e = hipMemcpyAsync(d_in, frame, in_bytes, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
-        launch_yuv_rows_to_rgb(c->stream, layout, d_in, px * 3 / 2, YuvCoef{coeffs[0], coeffs[1], coeffs[2], coeffs[3], coeffs[4]}, d_out,
+        launch_yuv_rows_to_rgb(c->stream, layout, d_in, in_bytes, YuvCoef{coeffs[0], coeffs[1], coeffs[2], coeffs[3], coeffs[4]}, d_out,
                                px * 3, h, w, 0, h, 1);
         e = hipGetLastError();
     }

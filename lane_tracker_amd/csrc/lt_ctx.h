@@ -146,8 +146,8 @@ struct lt_ctx {
     int capacity = 0;
     size_t frame_bytes = 0, und_bytes = 0, bev_bytes = 0;
     uint8_t *d_frames = nullptr, *d_bev = nullptr;
-    // YUV 4:2:0 input (lt_set_input_format): the caller's layout, the five conversion coefficients, and per slot a staging frame
-    // of yuv_bytes = h * w * 3 / 2 bytes in that layout, yuv_stride (a multiple of 16) apart, 16 bytes of padding behind the last
+    // YUV input (lt_set_input_format): the caller's layout, the five conversion coefficients, and per slot a staging frame
+    // of yuv_bytes = h * w * 3 / 2 (4:2:0) or h * w * 2 (packed 4:2:2) bytes in that layout, yuv_stride (a multiple of 16) apart, 16 bytes of padding behind the last
     // one (k_undistort_rows_yuv reads aligned 8-byte windows).  The undistortion reads the staging frame; the RGB camera frame
     // of a slot is written by k_yuv_rows_to_rgb behind the uploads that would have brought RGB rows for whoever shows the frame.
     int in_layout = 0;                        // LT_INPUT_RGB

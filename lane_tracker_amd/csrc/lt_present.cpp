@@ -728,6 +728,8 @@ static int inplace_impl(lt_ctx* c, int first, int n, const int32_t* left_n, cons
                         const int32_t* right_yx, const CoeffInput* ci, double alpha, const lt_inplace_text* text, const int32_t* rgb2yuv) {
     int rc = check_slots(c, first, n);
     if (rc) return rc;
+    if (c->in_layout == LT_INPUT_YUY2 || c->in_layout == LT_INPUT_UYVY)
+        return fail(LT_ERR_STATE, "lt_overlay_run_inplace: packed 4:2:2 (YUY2 / UYVY) is an input format only, nothing is drawn into such surfaces");
     for (int i = first; i < first + n; ++i)
         if (i >= (int)c->attached.size() || !c->attached[(size_t)i])
             return fail(LT_ERR_STATE, "lt_overlay_run_inplace: slot %d has no device frame attached (in place means the surface the slot reads)", i);

@@ -83,7 +83,17 @@ def _plane_rows(img_size, pixel_format):
     frame_shape((w, h), pixel_format)                    # (ValueError for odd 4:2:0 sizes)
     if layout == 0:
         return (h, 3 * w), None, 1
+    if layout >= 3:                                      # packed 4:2:2: one plane of 2 W bytes a row
+        return (h, 2 * w), None, 1
     return (h, w), ((h // 2, w) if layout == 1 else (h // 2, w // 2)), layout + 1
+
+
+def _frame_dims(layout):
+    """-> (dimensions of one frame's array, its last axis or 0): RGB (H, W, 3), packed 4:2:2 (H, W, 2), 4:2:0 (H * 3 // 2, W)."""
+    return (3, 3) if layout == 0 else (3, 2) if layout >= 3 else (2, 0)
+
+
+_SHAPE_NAMES = {3: "(H, W, 3)", 2: "(H, W, 2)", 0: "(H * 3 // 2, W)"}
 
 
 def _extent(rows, row_bytes, pitch):
@@ -123,7 +133,8 @@ def _layout_block(n, img_size, pixel_format, pitch, chroma_pitch, offset):
 
 
 def pack_host_frames(frames, pixel_format="rgb", pitch=None, chroma_pitch=None, offset=0, fill=0):
-    """Host frames -- (n, H, W, 3) / (H, W, 3), or (n, H * 3 // 2, W) / (H * 3 // 2, W) for 4:2:0 -- laid out as pitched surfaces in
+    """Host frames -- (n, H, W, 3) / (H, W, 3), (n, H * 3 // 2, W) / (H * 3 // 2, W) for 4:2:0, or (n, H, W, 2) / (H, W, 2) for
+    packed 4:2:2 -- laid out as pitched surfaces in
     one block: frame after frame, plane after plane, every row `pitch` (chroma rows: `chroma_pitch`) bytes after the one before,
     the first at `offset`; bytes between and around the rows are `fill`.  The block ends with the last byte of the last plane.
     -> (the block as a u8 array, surfaces with plane OFFSETS into it, img_size, whether `frames` was one frame)."""
@@ -131,12 +142,12 @@ def pack_host_frames(frames, pixel_format="rgb", pitch=None, chroma_pitch=None, 
     if f.dtype != np.uint8:
         raise ValueError("camera frames are uint8, got %s" % f.dtype)
     layout = pixel_format_id(pixel_format)
-    nd = 3 if layout == 0 else 2
-    if f.ndim not in (nd, nd + 1) or (layout == 0 and f.shape[-1] != 3):
-        raise ValueError("expected camera frames of shape %s, got %r" % ("(H, W, 3)" if layout == 0 else "(H * 3 // 2, W)", f.shape))
+    nd, last = _frame_dims(layout)
+    if f.ndim not in (nd, nd + 1) or (last and f.shape[-1] != last):
+        raise ValueError("expected camera frames of shape %s, got %r" % (_SHAPE_NAMES[last], f.shape))
     single = f.ndim == nd
     f = f[None] if single else f
-    if layout == 0:
+    if last:
         h, w = f.shape[1], f.shape[2]
     else:
         if f.shape[1] % 3:
@@ -158,7 +169,7 @@ def pack_host_frames(frames, pixel_format="rgb", pitch=None, chroma_pitch=None, 
 class DeviceFrames:
     """n camera frames of `img_size` = (width, height) in `pixel_format` somewhere in device memory: a description, not an owner
     (`owner` is whatever keeps the memory alive; it is only referenced).  `surfaces` is a SURFACE_DTYPE array, one entry per
-    frame: plane pointers (RGB: one; NV12: Y, UV; I420: Y, U, V), the pitch of plane 0 and the chroma pitch, in bytes.
+    frame: plane pointers (RGB, YUY2, UYVY: one; NV12: Y, UV; I420: Y, U, V), the pitch of plane 0 and the chroma pitch, in bytes.
     `single`: made from one frame (what process() takes); `stream`: the producer's stream to wait for before the frames are read;
     `readonly`: the producer said so (`__cuda_array_interface__`'s data[1]) -- such frames are never drawn into (`out="inplace"`)."""
 
@@ -172,7 +183,8 @@ class DeviceFrames:
     # -- construction
     @classmethod
     def from_planes(cls, planes, img_size, pixel_format, pitch, chroma_pitch=None, owner=None, stream=None, device=0):
-        """Explicit pointers: `planes` is one tuple of plane addresses per frame (RGB: (rgb,); NV12: (y, uv); I420: (y, u, v)) --
+        """Explicit pointers: `planes` is one tuple of plane addresses per frame (RGB: (rgb,); NV12: (y, uv); I420: (y, u, v); YUY2 /
+        UYVY: (plane,), pitch >= 2 W) --
         or a single such tuple for one frame -- `pitch` / `chroma_pitch` the bytes between rows (one value, or one per frame)."""
         (rows, rb), chroma, nplanes = _plane_rows(img_size, pixel_format)
         single = len(planes) > 0 and not hasattr(planes[0], "__len__")
@@ -199,7 +211,8 @@ class DeviceFrames:
     @classmethod
     def from_cuda_array(cls, obj, pixel_format="rgb", device=0):
         """Anything with `__cuda_array_interface__` (or the dict itself): '|u1', shape (n, H, W, 3) / (H, W, 3) for RGB and
-        (n, H * 3 // 2, W) / (H * 3 // 2, W) for NV12 / I420 with dense planes; row and frame strides come from `strides`."""
+        (n, H * 3 // 2, W) / (H * 3 // 2, W) for NV12 / I420 with dense planes, (n, H, W, 2) / (H, W, 2) for YUY2 / UYVY (strides
+        (frame, pitch, 2, 1), pitch >= 2 W); row and frame strides come from `strides`."""
         ai = obj if isinstance(obj, dict) else getattr(obj, "__cuda_array_interface__", None)
         if not isinstance(ai, dict):
             raise ValueError("the object has no __cuda_array_interface__")
@@ -211,9 +224,9 @@ class DeviceFrames:
             raise ValueError("masked arrays are not supported")
         shape = tuple(int(v) for v in ai["shape"])
         layout = pixel_format_id(pixel_format)
-        nd = 3 if layout == 0 else 2
-        if len(shape) not in (nd, nd + 1) or (layout == 0 and shape[-1] != 3):
-            raise ValueError("expected camera frames of shape %s, got %r" % ("(H, W, 3)" if layout == 0 else "(H * 3 // 2, W)", shape))
+        nd, last = _frame_dims(layout)
+        if len(shape) not in (nd, nd + 1) or (last and shape[-1] != last):
+            raise ValueError("expected camera frames of shape %s, got %r" % (_SHAPE_NAMES[last], shape))
         if any(v <= 0 for v in shape[-nd:]):
             raise ValueError("empty camera frames: shape %r" % (shape,))
         strides = ai.get("strides")
@@ -235,6 +248,11 @@ class DeviceFrames:
             h, w = shape[-3], shape[-2]
             if strides[-1] != 1 or strides[-2] != 3:
                 raise ValueError("RGB frames are interleaved: a pixel stride of 3 and a channel stride of 1, got %r" % (strides[-2:],))
+            pitch = strides[-3]
+        elif last == 2:
+            h, w = shape[-3], shape[-2]
+            if strides[-1] != 1 or strides[-2] != 2:
+                raise ValueError("4:2:2 frames are packed: a pixel stride of 2 and a sample stride of 1, got %r" % (strides[-2:],))
             pitch = strides[-3]
         else:
             if shape[-2] % 3:
@@ -275,7 +293,7 @@ class DeviceFrames:
 
     @classmethod
     def empty(cls, n, img_size, pixel_format="rgb", pitch=None, chroma_pitch=None, offset=0, fill=None, device=0):
-        """A sink: n surfaces of `img_size` in `pixel_format` in a fresh DeviceBuffer it owns, laid out as pack_host_frames lays
+        """A sink (packed 4:2:2: a container for input frames only, refused as a sink): n surfaces of `img_size` in `pixel_format` in a fresh DeviceBuffer it owns, laid out as pack_host_frames lays
         frames out (the block ends on the last byte of the last plane) -- what `Context.store_overlay_device`, `process_batch(...,
         out=)` and `utils.rgb_to_yuv` write into and `to_host()` reads back.  `fill`: a byte value the whole block is set to first
         (None: whatever the memory held)."""

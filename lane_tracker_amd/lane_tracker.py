@@ -66,10 +66,11 @@ class LaneTracker(StreamPipeline):
 
     def __init__(self, img_size, warped_size, cam_matrix, dist_coeffs, warp_matrices, mpp_conversion,
                  n_fail=8, n_reset=4, n_average=2, print_frame_count=False, device=0, *, pixel_format='rgb', yuv_matrix='bt601'):
-        # the camera's pixel format: 'rgb' frames (H, W, 3), or YUV 4:2:0 as cameras and decoders hand it out -- 'nv12' / 'i420'
-        # frames (H * 3 // 2, W), converted on the device with `yuv_matrix` ('bt601', 'bt709'); everything that comes back is RGB
+        # the camera's pixel format: 'rgb' frames (H, W, 3), YUV 4:2:0 as decoders hand it out -- 'nv12' / 'i420' frames
+        # (H * 3 // 2, W) -- or packed 4:2:2 as cameras and capture cards do -- 'yuy2' / 'uyvy' frames (H, W, 2) -- converted on the
+        # device with `yuv_matrix` ('bt601', 'bt709'); everything that comes back is RGB
         self.pixel_format, self.yuv_matrix = pixel_format, yuv_matrix
-        self._frame_shape = _native.frame_shape(img_size, pixel_format)      # (ValueError: unknown format, odd 4:2:0 size)
+        self._frame_shape = _native.frame_shape(img_size, pixel_format)      # (ValueError: unknown format, odd 4:2:0 size, odd 4:2:2 width)
         if pixel_format != 'rgb':
             _native.yuv_coeffs(yuv_matrix)
         self.img_size = img_size
@@ -147,7 +148,7 @@ class LaneTracker(StreamPipeline):
         return ctx
 
     def _check_frame(self, img, window=False):
-        """A 4:2:0 tracker takes frames of its own shape only (nothing is uploaded before this has been looked at); an RGB tracker
+        """A 4:2:0 / 4:2:2 tracker takes frames of its own shape only (nothing is uploaded before this has been looked at); an RGB tracker
         takes what it always took.  Frames in device memory (device.DeviceFrames) must be the tracker's size and pixel format."""
         if isinstance(img, DeviceFrames):
             img.check_for(self.img_size, self.pixel_format)
@@ -158,7 +159,7 @@ class LaneTracker(StreamPipeline):
             return
         shape = getattr(img, "shape", None)
         want = self._frame_shape
-        if shape is None or tuple(shape[1:] if window else shape) != want or (window and len(shape) != 3):
+        if shape is None or tuple(shape[1:] if window else shape) != want or (window and len(shape) != len(want) + 1):
             raise ValueError("a %r tracker takes frames of shape %s%r, got %r" % (self.pixel_format, "(n,) + " if window else "", want, shape))
 
     # ------------------------------------------------------------------------------------------

@@ -635,6 +635,8 @@ class StreamPipeline:
         tracker's own `yuv_matrix` when that is a preset name (a custom input matrix names no matrix for the way back)."""
         if out != "inplace":
             raise ValueError("out= takes a DeviceFrames or 'inplace', got %r" % (out,))
+        if self.pixel_format in _native.PACKED_422:
+            raise ValueError("out='inplace' draws into RGB, NV12 or I420 surfaces: %r is an input format only" % (self.pixel_format,))
         if out_yuv_matrix is not None:
             _native.rgb2yuv_coeffs(out_yuv_matrix)
             return out_yuv_matrix
@@ -699,6 +701,7 @@ class StreamPipeline:
         """`sink` as the destination of a window of n frames: a DeviceFrames of the tracker's image size, n surfaces, on its device."""
         if not isinstance(sink, DeviceFrames):
             raise ValueError("out= takes a DeviceFrames (DeviceFrames.empty(n, img_size, pixel_format)), got %r" % (type(sink).__name__,))
+        _native.sink_format_id(sink.pixel_format)       # (packed 4:2:2 is an input format only)
         if sink.img_size != (int(self.img_size[0]), int(self.img_size[1])):
             raise ValueError("out= holds frames of %dx%d, the tracker's are %dx%d" % (sink.img_size + (int(self.img_size[0]), int(self.img_size[1]))))
         if len(sink) != n:

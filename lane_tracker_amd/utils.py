@@ -91,7 +91,9 @@ def yuv_to_rgb(frame, layout='nv12', matrix='bt601'):
     """A YUV 4:2:0 frame as OpenCV holds it -- a u8 array (H * 3 // 2, W): the Y plane, then interleaved U,V rows ('nv12') or the
     U plane and the V plane ('i420') -- to RGB (H, W, 3), on the device: `cv2.cvtColor(frame, cv2.COLOR_YUV2RGB_NV12)` /
     `_I420` bit for bit with matrix='bt601' (OpenCV's constants, video range); 'bt709' or five integers {CY, CVR, CVG, CUG, CUB}
-    (20-bit fixed point) for another matrix.  What a `LaneTracker(..., pixel_format=layout, yuv_matrix=matrix)` sees of the frame."""
+    (20-bit fixed point) for another matrix.  Or a packed 4:2:2 frame as OpenCV holds it -- a u8 array (H, W, 2), W even: 'yuy2'
+    (bytes Y0 U Y1 V) / 'uyvy' (U Y0 V Y1) -- `cv2.cvtColor(frame, cv2.COLOR_YUV2RGB_YUY2)` / `_UYVY`, the same arithmetic with one
+    (U, V) pair per horizontal pixel pair.  What a `LaneTracker(..., pixel_format=layout, yuv_matrix=matrix)` sees of the frame."""
     from .lane_tracker import _context_for_module_functions
     return _context_for_module_functions().yuv_to_rgb(frame, layout, matrix)
 
@@ -105,7 +107,7 @@ def rgb_to_yuv(frame, layout='nv12', matrix='bt601'):
     from . import _native
     from .device import DeviceBuffer, DeviceFrames
     a = np.ascontiguousarray(frame, np.uint8)
-    if _native.pixel_format_id(layout) == 0:
+    if _native.sink_format_id(layout) == 0:              # (packed 4:2:2 is an input format only: ValueError)
         raise ValueError("layout must be 'nv12' or 'i420'")
     if a.ndim != 3 or a.shape[2] != 3 or a.shape[0] % 2 or a.shape[1] % 2 or 0 in a.shape:
         raise ValueError("an RGB frame is an array (H, W, 3) with H and W even, got %r" % (a.shape,))

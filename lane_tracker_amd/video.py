@@ -11,6 +11,9 @@ frames out.  Supported on both sides:
   * on the input side, a headerless raw YUV 4:2:0 file as cameras and decoders produce it: `.nv12`, or `.i420` / `.yuv` (I420;
     `ffmpeg -pix_fmt nv12 | yuv420p -f rawvideo`).  Its frames are (H * 3 // 2, W) arrays for a tracker built with the same
     `pixel_format`, which converts them on the device; what comes out, and every sink, is RGB -- unless
+  * or a headerless raw packed 4:2:2 file as cameras and capture cards produce it: `.yuy2` (Y0 U Y1 V) or `.uyvy` (U Y0 V Y1),
+    H * W * 2 bytes a frame (`ffmpeg -pix_fmt yuyv422 | uyvy422 -f rawvideo`); its frames are (H, W, 2) arrays.  A `FrameSink`
+    with such a `pixel_format` writes the same files (the bytes as given; the tracker itself has no 4:2:2 output)
   * `--out-format nv12 | i420` (or `rgb`) asks for the annotated frames through a device sink (`process_stream(..., out=)`): they
     are converted on the device and written as a raw `.nv12` / `.i420` (`.rgb`) file, which this module also reads.
 
@@ -39,9 +42,21 @@ def _is_raw(path):
 
 
 def _yuv_layout(path):
-    """'nv12' / 'i420' for a raw 4:2:0 file name, else None."""
+    """'nv12' / 'i420' for a raw 4:2:0 file name, 'yuy2' / 'uyvy' for a raw packed 4:2:2 one, else None."""
     p = str(path).lower()
-    return "nv12" if p.endswith(".nv12") else "i420" if p.endswith((".i420", ".yuv")) else None
+    return ("nv12" if p.endswith(".nv12") else "i420" if p.endswith((".i420", ".yuv")) else "yuy2" if p.endswith(".yuy2")
+            else "uyvy" if p.endswith(".uyvy") else None)
+
+
+def _yuv_tail(pixel_format, width, height):
+    """(shape of one frame, the format's family name); ValueError for a size the format does not take."""
+    if pixel_format in ("yuy2", "uyvy"):
+        if width % 2 or width < 4 or height < 1:
+            raise ValueError(f"4:2:2 frames need an even width of at least 4, got {width}x{height}")
+        return (height, width, 2), "4:2:2"
+    if width % 2 or height % 2 or width < 2 or height < 2:
+        raise ValueError(f"4:2:0 frames need an even width and height, got {width}x{height}")
+    return (height * 3 // 2, width), "4:2:0"
 
 
 def resolve_clip_path(path, must_exist=True):
@@ -62,7 +77,8 @@ def resolve_clip_path(path, must_exist=True):
 
 
 class FrameSource:
-    """Ordered u8 frames: RGB (n, H, W, 3), or -- `pixel_format` 'nv12' / 'i420', raw 4:2:0 files -- (n, H * 3 // 2, W).
+    """Ordered u8 frames: RGB (n, H, W, 3), or -- `pixel_format` 'nv12' / 'i420', raw 4:2:0 files -- (n, H * 3 // 2, W), or --
+    'yuy2' / 'uyvy', raw packed 4:2:2 files -- (n, H, W, 2).
     `size` = (width, height) is required for raw files only."""
 
     pixel_format = "rgb"
@@ -98,21 +114,20 @@ class FrameSource:
                 else np.zeros((0, self.height, self.width, 3), np.uint8)
         elif _yuv_layout(self.path):
             if size is None:
-                raise ValueError("raw 4:2:0 input needs size=(width, height)")
+                raise ValueError("raw 4:2:0 input needs size=(width, height)" if _yuv_layout(self.path) in ("nv12", "i420")
+                                 else "raw 4:2:2 input needs size=(width, height)")
             self.pixel_format = _yuv_layout(self.path)
             self.width, self.height = int(size[0]), int(size[1])
-            if self.width % 2 or self.height % 2 or self.width < 2 or self.height < 2:
-                raise ValueError(f"4:2:0 frames need an even width and height, got {self.width}x{self.height}")
-            self._tail = (self.height * 3 // 2, self.width)
-            fb = self.width * self.height * 3 // 2
+            self._tail, family = _yuv_tail(self.pixel_format, self.width, self.height)
+            fb = int(np.prod(self._tail))
             nbytes = os.path.getsize(self.path)
             if nbytes % fb:
-                raise ValueError(f"{self.path}: {nbytes} bytes is not a whole number of {self.width}x{self.height} 4:2:0 frames")
+                raise ValueError(f"{self.path}: {nbytes} bytes is not a whole number of {self.width}x{self.height} {family} frames")
             self._n = nbytes // fb
             self._array = np.memmap(self.path, np.uint8, "r", shape=(self._n,) + self._tail) if self._n \
                 else np.zeros((0,) + self._tail, np.uint8)
         else:
-            raise ValueError(f"unsupported frame source {self.path!r} (directory of images, .npy, .rgb/.raw, .nv12, .i420/.yuv)")
+            raise ValueError(f"unsupported frame source {self.path!r} (directory of images, .npy, .rgb/.raw, .nv12, .i420/.yuv, .yuy2, .uyvy)")
         if self._tail is None:
             self._tail = (self.height, self.width, 3)
         if size is not None and (self.width, self.height) != (int(size[0]), int(size[1])):
@@ -142,7 +157,7 @@ class FrameSource:
         return (self.width, self.height)
 
     def read(self, start, stop):
-        """Frames [start, stop) as one contiguous array (n, H, W, 3) -- 4:2:0: (n, H * 3 // 2, W)."""
+        """Frames [start, stop) as one contiguous array (n, H, W, 3) -- 4:2:0: (n, H * 3 // 2, W); 4:2:2: (n, H, W, 2)."""
         start, stop = max(0, start), min(self._n, stop)
         out = self._buffer((max(stop - start, 0),) + self._tail)
         if self._files is None:
@@ -162,7 +177,8 @@ class FrameSource:
 
 class FrameSink:
     """Where processed frames go.  Directories get `frame_000000.png`, ...; `.npy` needs `n` up front.  `pixel_format` 'nv12' /
-    'i420': frames of shape (H * 3 // 2, W) into a raw 4:2:0 file (`.nv12`, `.i420` / `.yuv`)."""
+    'i420': frames of shape (H * 3 // 2, W) into a raw 4:2:0 file (`.nv12`, `.i420` / `.yuv`); 'yuy2' / 'uyvy': frames of shape
+    (H, W, 2) into a raw packed 4:2:2 file (`.yuy2`, `.uyvy`)."""
 
     def __init__(self, path, size, n=None, pixel_format="rgb"):
         self.path = str(path)
@@ -174,7 +190,7 @@ class FrameSink:
         if pixel_format != "rgb":
             if _yuv_layout(self.path) != pixel_format:
                 raise ValueError("%s frames go into a raw file named *.%s, got %s" % (pixel_format, pixel_format, self.path))
-            self._tail = (self.height * 3 // 2, self.width)
+            self._tail = _yuv_tail(pixel_format, self.width, self.height)[0]
             self._raw = open(self.path, "wb")
         elif self.path.lower().endswith(".npy"):
             if n is None:
@@ -296,15 +312,15 @@ def _parse_size(text):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Lane tracking over a frame sequence (process_video.py without moviepy)")
-    ap.add_argument("input", help="directory of images, .npy (n,H,W,3), raw .rgb, or raw 4:2:0 (.nv12, .i420 / .yuv)")
+    ap.add_argument("input", help="directory of images, .npy (n,H,W,3), raw .rgb, raw 4:2:0 (.nv12, .i420 / .yuv) or raw packed 4:2:2 (.yuy2, .uyvy)")
     ap.add_argument("output", help="directory (PNG), .npy or raw .rgb; '-' to discard the frames")
     ap.add_argument("--cam", default="cam_calib.p", help="camera calibration (.p pickle or .npz)")
     ap.add_argument("--warp", default="warp_params.p", help="warp parameters (.p pickle or .npz)")
     ap.add_argument("--size", type=_parse_size, default=None, help="WxH of raw input frames")
     ap.add_argument("--window", type=int, default=64, help="frames per GPU batch")
-    ap.add_argument("--pixel-format", choices=("rgb", "nv12", "i420"), default=None,
+    ap.add_argument("--pixel-format", choices=("rgb", "nv12", "i420", "yuy2", "uyvy"), default=None,
                     help="pixel format of the input frames (default: by the input's name); must match a raw input's extension")
-    ap.add_argument("--yuv-matrix", choices=("bt601", "bt709"), default="bt601", help="conversion matrix of 4:2:0 input")
+    ap.add_argument("--yuv-matrix", choices=("bt601", "bt709"), default="bt601", help="conversion matrix of 4:2:0 / 4:2:2 input")
     ap.add_argument("--out-format", choices=("rgb", "nv12", "i420"), default=None,
                     help="write the annotated frames through a device sink in this pixel format: a raw .rgb / .nv12 / .i420 file for "
                          "4:2:0 (converted on the device, --out-yuv-matrix); default: RGB frames brought back by the host")

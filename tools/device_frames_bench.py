@@ -12,6 +12,12 @@ Modes (one per invocation; every leg runs `--runs` times, the file holds each ru
                LaneTrackerGroup of 8 -- each fed DeviceFrames and, beside it, host arrays.
   --host-fed   the host-fed halves of --trackers alone (what an older checkout can run: its figures are the yardstick).
 
+`--pixel-format yuy2|uyvy` (repeatable) adds packed 4:2:2 legs to `--formats`; with --resident / --attached every leg also records
+the `undistort_rows` stage time per 256 frames (lt_set_stage_timing: one timed mask run behind the measured steps).
+
+The `--runs` repetitions of a leg run back to back, one format after the other.  For runs that ALTERNATE between the formats (what
+profiles/yuv422_frontend.json holds) call the tool once per round with `--runs 1` and a file of its own, and put the rounds together.
+
   python tools/device_frames_bench.py --attached [--runs 3] [--steps 10] [--warmup 2] [--out profiles/device_frames.json] [--commit HASH]
 """
 import argparse
@@ -51,6 +57,20 @@ def rgb_to_nv12(rgb):
     return np.concatenate([q(y), np.stack([q(mean(u)), q(mean(v))], -1).reshape(h // 2, w)])
 
 
+def rgb_to_422(rgb, fmt):
+    """BT.601 video range, chroma the mean of each pixel pair; 'yuy2': Y0 U Y1 V, 'uyvy': U Y0 V Y1 (only makes inputs)."""
+    f = rgb.astype(np.float32)
+    h, w = f.shape[:2]
+    r, g, b = f[..., 0], f[..., 1], f[..., 2]
+    q = lambda p: np.clip(np.rint(p), 0, 255).astype(np.uint8)
+    y = q(0.257 * r + 0.504 * g + 0.098 * b + 16)
+    u = q((-0.148 * r - 0.291 * g + 0.439 * b + 128).reshape(h, w // 2, 2).mean(2))
+    v = q((0.439 * r - 0.368 * g - 0.071 * b + 128).reshape(h, w // 2, 2).mean(2))
+    m = np.stack([y[:, 0::2], u, y[:, 1::2], v] if fmt == "yuy2" else [u, y[:, 0::2], v, y[:, 1::2]], -1)
+    return m.reshape(h, w, 2)
+
+
+PACKED = ("yuy2", "uyvy")
 _pools = {}
 
 
@@ -60,7 +80,8 @@ def frames_for(cal, fmt, n, outage=False):
         pool = synth.stream_lanes(POOL, seed=5, cal=cal).copy()
         if outage:
             pool[20:23] = 0             # a short outage: second tries, failure pictures
-        _pools[key] = np.stack([rgb_to_nv12(f) for f in pool]) if fmt == "nv12" else pool
+        _pools[key] = (np.stack([rgb_to_nv12(f) for f in pool]) if fmt == "nv12" else
+                       np.stack([rgb_to_422(f, fmt) for f in pool]) if fmt in PACKED else pool)
     return np.ascontiguousarray(_pools[key][np.arange(n) % POOL])
 
 
@@ -70,7 +91,8 @@ def summary(values):
 
 # ---- the batch step ------------------------------------------------------------------------------------------------------------
 def batch_step(cal, fmt, mode, steps, warmup, streams, pitch_extra=0):
-    """frames/s of `steps` steps (mask chain + sliding-window search + fit over 256 frames) behind `warmup`."""
+    """frames/s of `steps` steps (mask chain + sliding-window search + fit over 256 frames) behind `warmup`; lanes detected; ms of
+    the undistort_rows stage of one more mask run over the 256 frames, timed stage by stage (None where the library cannot)."""
     frames = frames_for(cal, fmt, NL)
     ctx = _native.Context(cal["img_size"], cal["warped_size"], cal["cam_matrix"], cal["dist_coeffs"], cal["warp_matrices"][0], capacity=2 * NL)
     keep = None
@@ -80,7 +102,7 @@ def batch_step(cal, fmt, mode, steps, warmup, streams, pitch_extra=0):
         if mode == "resident":
             ctx.upload_frames(frames)
         else:
-            row = cal["img_size"][0] * (3 if fmt == "rgb" else 1)
+            row = cal["img_size"][0] * (3 if fmt == "rgb" else 2 if fmt in PACKED else 1)
             keep = ctx.attach_device_frames(DeviceFrames.from_host(frames, fmt, pitch=row + pitch_extra))
         fp, sp = _native.filter_params(), _native.search_params()
         ctx.set_streams(streams)
@@ -97,7 +119,17 @@ def batch_step(cal, fmt, mode, steps, warmup, streams, pitch_extra=0):
         ctx.sync()
         dt = time.perf_counter() - t0
         rec = ctx.download_records(NL)
-        return NL * steps / dt, int((rec["detected"] != 0).sum())
+        stage = None
+        if hasattr(ctx, "set_stage_timing"):
+            ctx.set_stage_timing(True)
+            ctx.mask_run(NL, fp)            # (the first timed run pays for the events)
+            ctx.sync()
+            ctx.stage_reset()
+            ctx.mask_run(NL, fp)
+            ctx.sync()
+            stage = float(ctx.stage_ms()["undistort_rows"][0])
+            ctx.set_stage_timing(False)
+        return NL * steps / dt, int((rec["detected"] != 0).sum()), stage
     finally:
         ctx.close()
         del keep
@@ -167,6 +199,7 @@ def main():
     ap.add_argument("--streams", type=int, default=4)
     ap.add_argument("--sizes", default="1280x720,1920x1080")
     ap.add_argument("--formats", default="rgb,nv12")
+    ap.add_argument("--pixel-format", action="append", choices=PACKED, default=[], help="a packed 4:2:2 format to measure beside --formats (repeatable)")
     ap.add_argument("--out", default="-")
     ap.add_argument("--commit", default=None, help="the commit hash to record (default: git rev-parse HEAD of this checkout)")
     a = ap.parse_args()
@@ -184,14 +217,19 @@ def main():
     def note(line):
         result["legs"].append(line)
         print(json.dumps(line), flush=True)
-    formats = [f for f in a.formats.split(",") if f == "rgb" or HAS_YUV]
+    formats = [f for f in a.formats.split(",") + a.pixel_format if f == "rgb" or HAS_YUV]
+    if any(f in PACKED for f in formats) and "yuy2" not in getattr(_native, "INPUT_FORMATS", {}):
+        sys.exit("this checkout has no packed 4:2:2 input")
     if mode in ("resident", "attached"):
         cal = calib.reference_calibration()
         for fmt in formats:
             for extra in ([0] if (mode == "resident" or fmt == "rgb") else [0, 64]):
                 got = [batch_step(cal, fmt, mode, a.steps, a.warmup, a.streams, extra) for _ in range(a.runs)]
-                note(dict(leg="batch_step", frames=mode, pixel_format=fmt, pitch_extra=extra, steps=a.steps, detected=got[0][1],
-                          **summary([g[0] for g in got])))
+                line = dict(leg="batch_step", frames=mode, pixel_format=fmt, pitch_extra=extra, steps=a.steps, detected=got[0][1],
+                            **summary([g[0] for g in got]))
+                if got[0][2] is not None:
+                    line["undistort_rows_ms_per_256"] = [round(g[2], 4) for g in got]
+                note(line)
     else:
         cals = {"1280x720": calib.reference_calibration, "1920x1080": lambda: calib.scaled_calibration(1.5)}
         feeds = [False] if mode == "host_fed" else [True, False]
