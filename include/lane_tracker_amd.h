@@ -58,7 +58,9 @@ extern "C" {
  *    lt_overlay_store_wait (annotated frames written into the caller's device surfaces, RGB, NV12 or I420); lt_add_calibration +
  *    lt_calibration_count + lt_set_slot_calibrations + lt_get_slot_calibrations + lt_overlay_configure_set (several calibrations in
  *    one context, one per slot: the cameras of a LaneTrackerGroup); lt_inplace_text + lt_overlay_run_inplace +
- *    lt_overlay_run_inplace_coeffs (lane and text drawn into the attached camera surfaces themselves).  Nothing removed or changed. */
+ *    lt_overlay_run_inplace_coeffs (lane and text drawn into the attached camera surfaces themselves); lt_overlay_run_to_surfaces +
+ *    lt_last_overlay_launches (lane and text drawn on the way into device sinks, one launch whatever the slots' calibration sets).
+ *    Nothing removed or changed. */
 #define LT_ABI_VERSION 5
 
 typedef enum lt_status {
@@ -625,6 +627,22 @@ int  lt_overlay_run_inplace(lt_ctx* ctx, int first_slot, int n, const int32_t* l
                             const int32_t* right_yx, double alpha, const lt_inplace_text* text, const int32_t rgb2yuv[8]);
 int  lt_overlay_run_inplace_coeffs(lt_ctx* ctx, int first_slot, int n, const double* coeffs, const uint8_t* draw, const double* ploty,
                                    const double* ploty2, int n_rows, double alpha, const lt_inplace_text* text, const int32_t rgb2yuv[8]);
+/* ---- annotated frames drawn on their way INTO device sinks -----------------------------------------------------------------------
+ * lt_overlay_run + lt_overlay_text + lt_overlay_store_device as one pass: every pixel of the camera frames of slots [first_slot,
+ * first_slot + n) is read once, drawn on -- the lane with the inverse-warp table of the slot's OWN calibration set, then the text --
+ * and written straight into dst[0 .. n) in `layout` (RGB at its pitch; NV12 / I420 with coeffs[8], chroma from the pixel at the even
+ * row and even column): byte for byte what the three calls leave in the sinks.  No annotated frame is kept in the context
+ * (lt_download_overlay and lt_overlay_store_device do not see these frames), and one kernel launch serves up to 32 slots whatever
+ * their sets.  `text` as for lt_overlay_run_inplace (NULL: none).
+ * Preconditions, refusals and ordering are those of lt_overlay_run followed by lt_overlay_store_device: whole camera frames in the
+ * slots and every slot's set configured (LT_ERR_STATE), the sinks' rules above -- layout, even sizes and coefficients for 4:2:0,
+ * pitches, disjoint planes, no byte shared with an attached camera surface (LT_ERR_INVALID) -- all checked before anything is
+ * staged or launched: a refused call leaves the context and the surfaces as they were.  Enqueued on the presentation stream behind
+ * the slots' writers and pending lt_upload_frame_rest / lt_device_frames_rest copies; returns without waiting; the surfaces are
+ * final after lt_overlay_store_wait or lt_sync. */
+int  lt_overlay_run_to_surfaces(lt_ctx* ctx, int first_slot, int n, const int32_t* left_n, const int32_t* right_n, const int32_t* left_yx,
+                                const int32_t* right_yx, double alpha, const lt_inplace_text* text, const lt_device_surface* dst, int layout,
+                                const int32_t coeffs[8]);
 /* How lt_download_overlay_async moves the frames: 0 = the copy engine, 1 = a kernel storing into the (page-locked, 16-byte
  * aligned) destination, -1 (default) = chosen by measurement: every copy is timed, the engine is used while its copies
  * reach ~42 GB/s, otherwise whichever of the two measures faster (the engine's rate depends on how the process's memory
@@ -825,6 +843,12 @@ int  lt_tophat_split_form(int h, int w, int k, int nbands);
 /* The same for the last 'neighborhood' call (cv2.adaptiveThreshold, lane_tracker.py:217-218): 1 = running box sums
  * (odd windows up to 63, width a multiple of 4, no greenery mask), 0 = the per-pixel window kernel, -1 = none yet. */
 int  lt_last_adaptive_path(lt_ctx* ctx);
+/* The lane-drawing kernel launches the most recent lt_overlay_run, lt_overlay_run_rows, lt_overlay_run_inplace,
+ * lt_overlay_run_inplace_coeffs or lt_overlay_run_to_surfaces of the context enqueued (text and store launches are not counted):
+ * 1 for a range of up to 64 slots (32 for lt_overlay_run_to_surfaces) whatever the slots' calibration sets -- a range that mixes
+ * sets is drawn by table-per-slot kernels, not run by run.  -1 = none yet; a refused call does not change it; LT_NO_CONTEXT for a
+ * null context. */
+int  lt_last_overlay_launches(lt_ctx* ctx);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

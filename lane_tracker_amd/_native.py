@@ -241,6 +241,8 @@ _SIGNATURES = {
     "lt_overlay_store_device": (C.c_int, [_P, C.c_int, C.c_int, _P, C.c_int, _P]),
     "lt_overlay_store_wait": (C.c_int, [_P]),
     "lt_overlay_run_inplace": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_double, _P, _P]),
+    "lt_overlay_run_to_surfaces": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_double, _P, _P, C.c_int, _P]),
+    "lt_last_overlay_launches": (C.c_int, [_P]),
     "lt_overlay_run_inplace_coeffs": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int, C.c_double, _P, _P]),
     "lt_add_calibration": (C.c_int, [_P, C.POINTER(Calib), C.POINTER(C.c_int)]),
     "lt_calibration_count": (C.c_int, [_P, C.POINTER(C.c_int)]),
@@ -1064,8 +1066,9 @@ class Context:
         _check(self.lib.lt_overlay_store_device(self._h, int(first), s.shape[0], s.ctypes.data, layout, None if k is None else k.ctypes.data))
         return sink
 
-    def _inplace_tail(self, n, lines_per_slot, origin, step, line_len, matrix):
-        """-> (what keeps the arguments alive, the address of the lt_inplace_text or None, the address of the eight integers or None)."""
+    @staticmethod
+    def _text_argument(n, lines_per_slot, origin, step, line_len):
+        """-> (what keeps it alive, the address of the lt_inplace_text or None)."""
         text, keep = None, []
         if lines_per_slot is not None:
             if len(lines_per_slot) != n:
@@ -1075,6 +1078,43 @@ class Context:
                 t = InplaceText(buf, nl, int(line_len), int(origin[0]), int(origin[1]), int(step))
                 keep += [buf, t]
                 text = C.addressof(t)
+        return keep, text
+
+    def overlay_run_to_surfaces_packed(self, ln, rn, lyx, ryx, sink, first=0, alpha=0.3, lines=None, origin=(20, 8), step=35, line_len=40,
+                                       matrix="bt601"):
+        """Lane and text drawn on the way from the camera frames of slots first .. first + len(sink) - 1 into `sink`, a
+        device.DeviceFrames of this context's image size in 'rgb', 'nv12' or 'i420' (lt_overlay_run_to_surfaces): what overlay_run_packed
+        + overlay_text + store_overlay_device leave there, in one pass and one launch per 32 slots whatever the slots' calibration sets.
+        Only enqueued: the sink is final after store_wait() or sync(); keep it alive until then."""
+        ln, rn = np.ascontiguousarray(ln, np.int32), np.ascontiguousarray(rn, np.int32)
+        lyx, ryx = np.ascontiguousarray(lyx, np.int32), np.ascontiguousarray(ryx, np.int32)
+        if len(rn) != len(ln) or lyx.size != 2 * int(ln.sum()) or ryx.size != 2 * int(rn.sum()):
+            raise ValueError("point lists do not match their counts")
+        if sink.img_size != (self.img_w, self.img_h):
+            raise ValueError("expected a sink of %dx%d frames, got %dx%d" % ((self.img_w, self.img_h) + sink.img_size))
+        if len(sink) != len(ln):
+            raise ValueError("one surface per slot: %d surfaces for %d slots" % (len(sink), len(ln)))
+        layout = sink_format_id(sink.pixel_format)
+        k = rgb2yuv_coeffs(matrix) if layout else None
+        s = np.ascontiguousarray(sink.surfaces)
+        keep, text = self._text_argument(len(ln), lines, origin, step, line_len)
+        _check(self.lib.lt_overlay_run_to_surfaces(self._h, int(first), len(ln), ln.ctypes.data, rn.ctypes.data, lyx.ctypes.data if lyx.size else None,
+                                                   ryx.ctypes.data if ryx.size else None, float(alpha), text, s.ctypes.data, layout,
+                                                   None if k is None else k.ctypes.data))
+        del keep
+        return sink
+
+    def overlay_run_to_surfaces(self, polygons, sink, first=0, **kw):
+        """overlay_run_to_surfaces_packed for one (left_y, left_x, right_y, right_x) tuple per slot (empty arrays: no lane)."""
+        return self.overlay_run_to_surfaces_packed(*pack_polygons(polygons), sink, first=first, **kw)
+
+    def last_overlay_launches(self):
+        """Lane-drawing kernel launches of the most recent overlay_run* / overlay_run_inplace* / overlay_run_to_surfaces*; -1: none yet."""
+        return int(self.lib.lt_last_overlay_launches(self._h))
+
+    def _inplace_tail(self, n, lines_per_slot, origin, step, line_len, matrix):
+        """-> (what keeps the arguments alive, the address of the lt_inplace_text or None, the address of the eight integers or None)."""
+        keep, text = self._text_argument(n, lines_per_slot, origin, step, line_len)
         k = None
         if self.input_format()[0] in PACKED_422:
             raise ValueError("packed 4:2:2 is an input format only: nothing is drawn into such surfaces")

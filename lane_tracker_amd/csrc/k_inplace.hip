@@ -8,6 +8,8 @@
 //   k_inplace_rgb     RGB surfaces of any geometry, one pixel per thread, byte accesses
 //   k_inplace_420     NV12 / I420, one thread per 2 x 2 block (byte accesses) or per four blocks side by side (8-byte luma rows;
 //                     width, luma bases and pitches multiples of 8, chroma of 8 (NV12) / 4 (I420))
+//   k_inplace_*_cal   the same bodies for a launch whose slots mix calibration sets: frame blockIdx.z with the inverse-warp tables
+//                     of its own set (overlay_lane.h: SlotOv), CalIds::N slots per launch
 //
 // Lane and text of a pixel are found FIRST (overlay_lane.h: the four taps against the polygon's row intervals; the glyph under the
 // pixel from the slot's list of character positions); a thread none of whose pixels is reached loads and stores nothing.  A 4:2:0
@@ -34,33 +36,8 @@ __device__ __forceinline__ int lane_at(const InplaceLane& l, const short2* __res
     return lane_value(sp, l.bh, l.bw, l.oxy[2 * o], l.oxy[2 * o + 1], l.ofrac[o]);
 }
 
-// The alpha of the glyph over pixel (x, y) of frame z, 0 where there is none.  The line comes from y0 / step / gh (lines do not
-// overlap: step >= gh, checked on the host), the character from the slot's positions: xpos[] never decreases along a line (a
-// running sum of advances), cells are disjoint, so the last character that starts at or before x is the only candidate.
-__device__ __forceinline__ int text_alpha(const InplaceText& t, int z, int x, int y) {
-    const int dy = y - t.y0;
-    if (t.nl <= 0 || dy < 0) return 0;
-    const int line = dy / t.step, gy = dy - line * t.step;
-    if (line >= t.nl || gy >= t.gh) return 0;
-    const size_t base = (size_t)z * t.slot_chars + (size_t)line * t.len;
-    const int16_t* __restrict__ xp = t.xpos + base;
-    int lo = 0, hi = t.len;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (xp[mid] <= x) lo = mid + 1;
-        else hi = mid;
-    }
-    if (lo == 0) return 0;
-    const int k = lo - 1;
-    const int ch = (int)t.lines[base + k] - t.first_char;
-    if (ch < 0 || ch >= t.n_glyphs) return 0;
-    const int gx = x - xp[k];
-    if (gx >= t.advance[ch] || gx >= t.gw) return 0;
-    return t.atlas[((size_t)ch * t.gh + gy) * t.gw + gx];
-}
-
-__global__ __launch_bounds__(256) void k_inplace_rgb(const SurfEntry* __restrict__ tab, InplaceRows rows, InplaceLane l, InplaceText t,
-                                                    int w, int items) {
+__device__ __forceinline__ void inplace_rgb_body(const SurfEntry* __restrict__ tab, const InplaceRows& rows, const InplaceLane& l,
+                                                 const InplaceText& t, int w, int items) {
     const int i = (int)(blockIdx.x * 256u + threadIdx.x);
     if (i >= items) return;
     const int ri = i / w, x = i - ri * w, y = row_of(rows, ri), z = (int)blockIdx.z;
@@ -76,9 +53,26 @@ __global__ __launch_bounds__(256) void k_inplace_rgb(const SurfEntry* __restrict
         if (((q ^ px) >> (8 * c)) & 255u) p[c] = (uint8_t)(q >> (8 * c));
 }
 
+// The kernels: one calibration set for the launch (the tables in `l`), or -- _cal -- frame blockIdx.z with the tables of its own set.
+// A pixel outside its own set's lane rows has lane value 0 (all four taps miss the bird's-eye image), so the union rows serve all.
+__device__ __forceinline__ InplaceLane lane_of_slot(InplaceLane l, const OvTables* __restrict__ sets, const CalIds& ids) {
+    const OvTables& o = SlotOv{sets, &ids}.of((int)blockIdx.z);
+    l.oxy = o.oxy;
+    l.ofrac = o.ofrac;
+    return l;
+}
+__global__ __launch_bounds__(256) void k_inplace_rgb(const SurfEntry* __restrict__ tab, InplaceRows rows, InplaceLane l, InplaceText t,
+                                                    int w, int items) {
+    inplace_rgb_body(tab, rows, l, t, w, items);
+}
+__global__ __launch_bounds__(256) void k_inplace_rgb_cal(const SurfEntry* __restrict__ tab, InplaceRows rows, InplaceLane l, InplaceText t,
+                                                        int w, int items, const OvTables* __restrict__ sets, CalIds ids) {
+    inplace_rgb_body(tab, rows, lane_of_slot(l, sets, ids), t, w, items);
+}
+
 // byte layout of a quad's three dwords: R0 G0 B0 R1 | G1 B1 R2 G2 | B2 R3 G3 B3
-__global__ __launch_bounds__(256) void k_inplace_rgb4(const SurfEntry* __restrict__ tab, InplaceRows rows, InplaceLane l, InplaceText t,
-                                                     int w, int items) {
+__device__ __forceinline__ void inplace_rgb4_body(const SurfEntry* __restrict__ tab, const InplaceRows& rows, const InplaceLane& l,
+                                                  const InplaceText& t, int w, int items) {
     const int i = (int)(blockIdx.x * 256u + threadIdx.x);
     if (i >= items) return;
     const int qrow = w >> 2, ri = i / qrow, xq = i - ri * qrow, y = row_of(rows, ri), z = (int)blockIdx.z;
@@ -109,10 +103,19 @@ __global__ __launch_bounds__(256) void k_inplace_rgb4(const SurfEntry* __restric
     if (n2 != d2) p[2] = n2;
 }
 
+__global__ __launch_bounds__(256) void k_inplace_rgb4(const SurfEntry* __restrict__ tab, InplaceRows rows, InplaceLane l, InplaceText t,
+                                                     int w, int items) {
+    inplace_rgb4_body(tab, rows, l, t, w, items);
+}
+__global__ __launch_bounds__(256) void k_inplace_rgb4_cal(const SurfEntry* __restrict__ tab, InplaceRows rows, InplaceLane l, InplaceText t,
+                                                         int w, int items, const OvTables* __restrict__ sets, CalIds ids) {
+    inplace_rgb4_body(tab, rows, lane_of_slot(l, sets, ids), t, w, items);
+}
+
 // LAYOUT 1: NV12 (rows of U, V pairs), 2: I420 (a U and a V plane).  `rows` are runs of CHROMA rows: a thread owns whole blocks.
 template <int LAYOUT, bool WIDE>
-__global__ __launch_bounds__(256) void k_inplace_420(const SurfEntry* __restrict__ tab, InplaceRows rows, InplaceLane l, InplaceText t,
-                                                    YuvCoef kin, sa::Rgb2Yuv kout, int w, int groups, int items) {
+__device__ __forceinline__ void inplace_420_body(const SurfEntry* __restrict__ tab, const InplaceRows& rows, const InplaceLane& l,
+                                                 const InplaceText& t, const YuvCoef& kin, const sa::Rgb2Yuv& kout, int w, int groups, int items) {
     constexpr int NB = WIDE ? 4 : 1;                 // blocks per thread, side by side
     const int i = (int)(blockIdx.x * 256u + threadIdx.x);
     if (i >= items) return;
@@ -216,6 +219,18 @@ __global__ __launch_bounds__(256) void k_inplace_420(const SurfEntry* __restrict
     }
 }
 
+template <int LAYOUT, bool WIDE>
+__global__ __launch_bounds__(256) void k_inplace_420(const SurfEntry* __restrict__ tab, InplaceRows rows, InplaceLane l, InplaceText t,
+                                                    YuvCoef kin, sa::Rgb2Yuv kout, int w, int groups, int items) {
+    inplace_420_body<LAYOUT, WIDE>(tab, rows, l, t, kin, kout, w, groups, items);
+}
+template <int LAYOUT, bool WIDE>
+__global__ __launch_bounds__(256) void k_inplace_420_cal(const SurfEntry* __restrict__ tab, InplaceRows rows, InplaceLane l, InplaceText t,
+                                                        YuvCoef kin, sa::Rgb2Yuv kout, int w, int groups, int items,
+                                                        const OvTables* __restrict__ sets, CalIds ids) {
+    inplace_420_body<LAYOUT, WIDE>(tab, rows, lane_of_slot(l, sets, ids), t, kin, kout, w, groups, items);
+}
+
 // two runs of rows -> disjoint, ordered runs (one where they meet); unit = 1: pixel rows, 2: chroma rows (a run covers every chroma
 // row one of its pixel rows belongs to)
 InplaceRows merge_runs(const int r[4], int unit, int h) {
@@ -231,10 +246,12 @@ InplaceRows merge_runs(const int r[4], int unit, int h) {
 }  // namespace
 
 // slots of one launch: entries[0, n) are the host's mirror of tab[0, n) (device), read here for the launch's alignment only
-void launch_inplace(hipStream_t s, int layout, const SurfEntry* tab, const SurfEntry* entries, int n, int h, int w, const int rows4[4],
-                    InplaceLane l, InplaceText t, YuvCoef kin, const int32_t* rgb2yuv) {
-    if (n <= 0 || h <= 0 || w <= 0) return;
-    constexpr int Z = 32768;
+int launch_inplace(hipStream_t s, int layout, const SurfEntry* tab, const SurfEntry* entries, int n, int h, int w, const int rows4[4],
+                   InplaceLane l, InplaceText t, YuvCoef kin, const int32_t* rgb2yuv, OvSets per_slot) {
+    if (n <= 0 || h <= 0 || w <= 0) return 0;
+    const bool cal = per_slot.sets != nullptr;
+    const int Z = cal ? (int)CalIds::N : 32768;
+    int launches = 0;
     for (int at = 0; at < n; at += Z) {
         const int m = std::min(n - at, Z);
         size_t ybits = 0, cbits = 0;
@@ -250,17 +267,17 @@ void launch_inplace(hipStream_t s, int layout, const SurfEntry* tab, const SurfE
             tz.lines = t.lines + (size_t)at * t.slot_chars;
             tz.xpos = t.xpos + (size_t)at * t.slot_chars;
         }
+        const CalIds ids = cal ? pack_cal_ids(per_slot.ids + at, m) : CalIds{};
         if (layout == 0) {
             const InplaceRows rows = merge_runs(rows4, 1, h);
             const int nrows = rows.an + rows.bn;
             if (nrows <= 0) continue;
-            if ((w & 3) == 0 && (ybits & 3) == 0) {
-                const int items = nrows * (w >> 2);
-                hipLaunchKernelGGL(k_inplace_rgb4, dim3((unsigned)((items + 255) / 256), 1, (unsigned)m), dim3(256), 0, s, tab + at, rows, lz, tz, w, items);
-            } else {
-                const int items = nrows * w;
-                hipLaunchKernelGGL(k_inplace_rgb, dim3((unsigned)((items + 255) / 256), 1, (unsigned)m), dim3(256), 0, s, tab + at, rows, lz, tz, w, items);
-            }
+            const bool four = (w & 3) == 0 && (ybits & 3) == 0;
+            const int items = four ? nrows * (w >> 2) : nrows * w;
+            const dim3 grid((unsigned)((items + 255) / 256), 1, (unsigned)m);
+            if (cal) hipLaunchKernelGGL(four ? k_inplace_rgb4_cal : k_inplace_rgb_cal, grid, dim3(256), 0, s, tab + at, rows, lz, tz, w, items, per_slot.sets, ids);
+            else hipLaunchKernelGGL(four ? k_inplace_rgb4 : k_inplace_rgb, grid, dim3(256), 0, s, tab + at, rows, lz, tz, w, items);
+            ++launches;
             continue;
         }
         const InplaceRows rows = merge_runs(rows4, 2, h);
@@ -270,14 +287,16 @@ void launch_inplace(hipStream_t s, int layout, const SurfEntry* tab, const SurfE
         const bool wide = (w & 7) == 0 && (ybits & 7) == 0 && (cbits & (layout == 1 ? 7 : 3)) == 0;
         const int groups = wide ? w / 8 : w / 2, items = nrows * groups;
         const dim3 grid((unsigned)((items + 255) / 256), 1, (unsigned)m);
-        if (layout == 1) {
-            if (wide) hipLaunchKernelGGL((k_inplace_420<1, true>), grid, dim3(256), 0, s, tab + at, rows, lz, tz, kin, kout, w, groups, items);
-            else hipLaunchKernelGGL((k_inplace_420<1, false>), grid, dim3(256), 0, s, tab + at, rows, lz, tz, kin, kout, w, groups, items);
+        if (cal) {
+            auto k = layout == 1 ? (wide ? k_inplace_420_cal<1, true> : k_inplace_420_cal<1, false>) : (wide ? k_inplace_420_cal<2, true> : k_inplace_420_cal<2, false>);
+            hipLaunchKernelGGL(k, grid, dim3(256), 0, s, tab + at, rows, lz, tz, kin, kout, w, groups, items, per_slot.sets, ids);
         } else {
-            if (wide) hipLaunchKernelGGL((k_inplace_420<2, true>), grid, dim3(256), 0, s, tab + at, rows, lz, tz, kin, kout, w, groups, items);
-            else hipLaunchKernelGGL((k_inplace_420<2, false>), grid, dim3(256), 0, s, tab + at, rows, lz, tz, kin, kout, w, groups, items);
+            auto k = layout == 1 ? (wide ? k_inplace_420<1, true> : k_inplace_420<1, false>) : (wide ? k_inplace_420<2, true> : k_inplace_420<2, false>);
+            hipLaunchKernelGGL(k, grid, dim3(256), 0, s, tab + at, rows, lz, tz, kin, kout, w, groups, items);
         }
+        ++launches;
     }
+    return launches;
 }
 
 }  // namespace lt

@@ -21,11 +21,11 @@ namespace {
 // tap_in, lane_value, blend_green: overlay_lane.h (shared with k_inplace.hip)
 
 // One thread per camera pixel; `spans` = (lo, hi) int16 per bird's-eye row of this slot.
-__global__ __launch_bounds__(256) void k_overlay_lane(const uint8_t* __restrict__ frames, uint8_t* __restrict__ out,
-                                                     size_t frame_stride, const int16_t* __restrict__ oxy,
-                                                     const uint16_t* __restrict__ ofrac,
-                                                     const short2* __restrict__ spans, size_t span_stride, int npix,
-                                                     int bh, int bw, float alpha) {
+__device__ __forceinline__ void overlay_lane_body(const uint8_t* __restrict__ frames, uint8_t* __restrict__ out,
+                                                  size_t frame_stride, const int16_t* __restrict__ oxy,
+                                                  const uint16_t* __restrict__ ofrac,
+                                                  const short2* __restrict__ spans, size_t span_stride, int npix,
+                                                  int bh, int bw, float alpha) {
     const int o = blockIdx.x * blockDim.x + threadIdx.x;
     if (o >= npix) return;
     const uint8_t* src = frames + (size_t)blockIdx.z * frame_stride + (size_t)o * 3;
@@ -36,6 +36,23 @@ __global__ __launch_bounds__(256) void k_overlay_lane(const uint8_t* __restrict_
     dst[0] = (uint8_t)r;
     dst[1] = (uint8_t)(v ? blend_green(g, v, alpha) : g);
     dst[2] = (uint8_t)b;
+}
+
+__global__ __launch_bounds__(256) void k_overlay_lane(const uint8_t* __restrict__ frames, uint8_t* __restrict__ out,
+                                                     size_t frame_stride, const int16_t* __restrict__ oxy,
+                                                     const uint16_t* __restrict__ ofrac,
+                                                     const short2* __restrict__ spans, size_t span_stride, int npix,
+                                                     int bh, int bw, float alpha) {
+    overlay_lane_body(frames, out, frame_stride, oxy, ofrac, spans, span_stride, npix, bh, bw, alpha);
+}
+// The table-per-slot forms (_cal, here and below): frame blockIdx.z with the inverse-warp tables of its own calibration set (SlotOv).
+// A pixel outside its own set's lane rows has lane value 0 -- all four taps miss the bird's-eye image -- and stays the camera pixel.
+__global__ __launch_bounds__(256) void k_overlay_lane_cal(const uint8_t* __restrict__ frames, uint8_t* __restrict__ out,
+                                                         size_t frame_stride, const OvTables* __restrict__ sets, CalIds ids,
+                                                         const short2* __restrict__ spans, size_t span_stride, int npix,
+                                                         int bh, int bw, float alpha) {
+    const OvTables& t = SlotOv{sets, &ids}.of((int)blockIdx.z);
+    overlay_lane_body(frames, out, frame_stride, t.oxy, t.ofrac, spans, span_stride, npix, bh, bw, alpha);
 }
 
 // Four pixels (12 bytes = three dwords) per thread when the row length allows it.
@@ -80,6 +97,14 @@ __global__ __launch_bounds__(256) void k_overlay_lane4(const uint32_t* __restric
                                                       const short2* __restrict__ spans, size_t span_stride, int qa, int na,
                                                       int qb, int nb, int bh, int bw, float alpha) {
     overlay_lane4_body(frames, out, frame_stride_dw, out_stride_dw, out_q0, oxy, ofrac, spans, span_stride, qa, na, qb, nb, bh, bw, alpha);
+}
+
+__global__ __launch_bounds__(256) void k_overlay_lane4_cal(const uint32_t* __restrict__ frames, uint32_t* __restrict__ out,
+                                                          size_t frame_stride_dw, const OvTables* __restrict__ sets, CalIds ids,
+                                                          const short2* __restrict__ spans, size_t span_stride, int qa, int na,
+                                                          int qb, int nb, int bh, int bw, float alpha) {
+    const OvTables& t = SlotOv{sets, &ids}.of((int)blockIdx.z);
+    overlay_lane4_body(frames, out, frame_stride_dw, frame_stride_dw, 0, t.oxy, t.ofrac, spans, span_stride, qa, na, qb, nb, bh, bw, alpha);
 }
 
 // k_overlay_lane4 for ONE frame with the row intervals as a kernel ARGUMENT (up to LT_SPAN_ARG_ROWS bird's-eye rows; should the
@@ -452,17 +477,35 @@ bool launch_overlay_lane_strip(hipStream_t s, const uint8_t* frames, size_t fram
     return true;
 }
 
-void launch_overlay_lane(hipStream_t s, const uint8_t* frames, uint8_t* out, size_t frame_stride, const int16_t* oxy,
-                         const uint16_t* ofrac, const int16_t* spans, size_t span_stride_rows, int img_h, int img_w,
-                         int bh, int bw, float alpha, int n, const int* rows4) {
-    if (n <= 0) return;
+int launch_overlay_lane(hipStream_t s, const uint8_t* frames, uint8_t* out, size_t frame_stride, const int16_t* oxy,
+                        const uint16_t* ofrac, const int16_t* spans, size_t span_stride_rows, int img_h, int img_w,
+                        int bh, int bw, float alpha, int n, const int* rows4, OvSets per_slot) {
+    if (n <= 0) return 0;
     const int npix = img_h * img_w;
     const short2* sp = reinterpret_cast<const short2*>(spans);
-    if ((img_w & 3) == 0 && (frame_stride & 3) == 0) {
-        const int qrow = img_w >> 2;
-        int qa = 0, na = npix >> 2, qb = 0, nb = 0;
-        if (rows4) { qa = rows4[0] * qrow; na = (rows4[1] - rows4[0]) * qrow; qb = rows4[2] * qrow; nb = (rows4[3] - rows4[2]) * qrow; }
-        if (na + nb <= 0) return;
+    const bool four = (img_w & 3) == 0 && (frame_stride & 3) == 0;
+    const int qrow = img_w >> 2;
+    int qa = 0, na = npix >> 2, qb = 0, nb = 0;
+    if (four && rows4) { qa = rows4[0] * qrow; na = (rows4[1] - rows4[0]) * qrow; qb = rows4[2] * qrow; nb = (rows4[3] - rows4[2]) * qrow; }
+    if (four && na + nb <= 0) return 0;
+    if (per_slot.sets) {         // every slot with the tables of its own set: CalIds::N slots per launch
+        int launches = 0;
+        for (int at = 0; at < n; at += CalIds::N, ++launches) {
+            const int m = std::min(n - at, (int)CalIds::N);
+            const CalIds ids = pack_cal_ids(per_slot.ids + at, m);
+            const uint8_t* f = frames + (size_t)at * frame_stride;
+            uint8_t* o = out + (size_t)at * frame_stride;
+            const short2* spz = sp + (size_t)at * span_stride_rows;
+            if (four)
+                hipLaunchKernelGGL(k_overlay_lane4_cal, dim3((na + nb + 255) / 256, 1, m), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(f),
+                                   reinterpret_cast<uint32_t*>(o), frame_stride >> 2, per_slot.sets, ids, spz, span_stride_rows, qa, na, qb, nb, bh, bw, alpha);
+            else
+                hipLaunchKernelGGL(k_overlay_lane_cal, dim3((npix + 255) / 256, 1, m), dim3(256), 0, s, f, o, frame_stride, per_slot.sets, ids, spz,
+                                   span_stride_rows, npix, bh, bw, alpha);
+        }
+        return launches;
+    }
+    if (four) {
         hipLaunchKernelGGL(k_overlay_lane4, dim3((na + nb + 255) / 256, 1, n), dim3(256), 0, s,
                            reinterpret_cast<const uint32_t*>(frames), reinterpret_cast<uint32_t*>(out), frame_stride >> 2, frame_stride >> 2, 0,
                            oxy, ofrac, sp, span_stride_rows, qa, na, qb, nb, bh, bw, alpha);
@@ -470,6 +513,7 @@ void launch_overlay_lane(hipStream_t s, const uint8_t* frames, uint8_t* out, siz
         hipLaunchKernelGGL(k_overlay_lane, dim3((npix + 255) / 256, 1, n), dim3(256), 0, s, frames, out, frame_stride, oxy,
                            ofrac, sp, span_stride_rows, npix, bh, bw, alpha);
     }
+    return 1;
 }
 
 bool launch_overlay_lane_one(hipStream_t s, const uint8_t* frame, uint8_t* out, const int16_t* oxy, const uint16_t* ofrac,

@@ -712,6 +712,7 @@ void lt_destroy(lt_ctx* c) {
         dev_free(q.d_uxy); dev_free(q.d_ufrac); dev_free(q.d_wxy); dev_free(q.d_wfrac); dev_free(q.d_oxy); dev_free(q.d_ofrac);
     }
     dev_free(c->d_cal);
+    dev_free(c->d_ov);
     dev_free(c->d_atlas);
     dev_free(c->d_advance);
     dev_free(c->d_lines);
@@ -2580,6 +2581,11 @@ int lt_last_threshold_path(lt_ctx* c) {
 int lt_last_tophat_path(lt_ctx* c) {
     if (!c) { (void)fail(LT_ERR_INVALID, "null context"); return LT_NO_CONTEXT; }
     return c->last_tophat_path;
+}
+
+int lt_last_overlay_launches(lt_ctx* c) {
+    if (!c) { (void)fail(LT_ERR_INVALID, "null context"); return LT_NO_CONTEXT; }
+    return c->last_overlay_launches;
 }
 
 int lt_tophat_split_form(int h, int w, int k, int nbands) {

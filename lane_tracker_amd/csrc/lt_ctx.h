@@ -5,7 +5,8 @@
 //   lt_present.cpp -- presentation stage: lane overlay, text, annotated frames on their way back
 //   lt_chain.cpp   -- the chained band search of a stream (tickets, cancel, collect)
 //   lt_search_viz.cpp -- search visualisations and split-view panes of listed frames, lt_resize_linear_u8
-//   lt_sink.cpp    -- device sinks: annotated frames (or any RGB frames) into the caller's RGB / NV12 / I420 surfaces
+//   lt_sink.cpp    -- device sinks: annotated frames (or any RGB frames) into the caller's RGB / NV12 / I420 surfaces; the checks of
+//                     a call's destinations (shared with lt_overlay_run_to_surfaces, lt_present.cpp)
 // Not installed; the public ABI is include/lane_tracker_amd.h.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -141,6 +142,10 @@ struct lt_ctx {
     std::vector<CalSet> cal;
     lt::CalTables* d_cal = nullptr;
     std::vector<uint8_t> slot_cal;
+    // the sets' inverse-warp tables as the table-per-slot presentation kernels read them: entry id written when lt_overlay_configure_set
+    // builds set id's tables (allocated by the first such call)
+    lt::OvTables* d_ov = nullptr;
+    int last_overlay_launches = -1;               // lt_last_overlay_launches
     bool lab_clamp_dead = false;   // no pixel reaches the clamp of the cube-root table index with these tables (front_arith.h)
     // slots
     int capacity = 0;
@@ -506,6 +511,11 @@ int first_partial(const std::vector<uint8_t>& v, int first, int n);
 // asked about, within one call.
 struct KnownRange { uintptr_t base = 0; size_t size = 0; };
 int check_plane(int device, const void* p, size_t extent, int k, int i, KnownRange& memo);
+// device sinks (lt_sink.cpp), shared with lt_overlay_run_to_surfaces: the layout, size and coefficients of a sink; then every plane
+// of the n destinations through check_plane's rules, no two planes sharing a byte, none sharing a byte with a camera surface attached
+// to a slot of the context -> the kernels' entries
+int check_sink_format(int layout, int h, int w, const int32_t* coeffs);
+int check_ctx_sinks(lt_ctx* c, const lt_device_surface* dst, int n, int layout, std::vector<SurfEntry>& ent);
 int ensure_search_stream(lt_ctx* c);                          // lt_chain.cpp
 int ensure_chain_buffers(lt_ctx* c);                          // lt_chain.cpp
 int warm_presentation(lt_ctx* c, bool strips);                // lt_present.cpp

@@ -136,11 +136,34 @@ struct InplaceText {
     int first_char, n_glyphs, gw, gh, nl, len, slot_chars, y0, step;
 };
 struct InplaceRows { int a0, an, b0, bn; };
+// The inverse-warp tables of the calibration sets as the table-per-slot presentation kernels find them: entry `id` of the context's
+// table of overlay tables (device memory, written when lt_overlay_configure_set builds a set's tables: with nothing in flight).  The
+// sets of a launch's slots travel by value, as for the front end (CalIds).
+struct OvTables {
+    const int16_t* oxy;
+    const uint16_t* ofrac;
+};
+static_assert(sizeof(OvTables) == 16, "OvTables: 16 bytes, one scalar load");
+// Which tables a presentation launch over slots [first, first + n) uses: those of one set (sets == nullptr: the launcher's oxy /
+// ofrac arguments, the kernels and arguments of a context with one set) or every slot's own -- ids[0, n), host memory, one launch
+// per CalIds::N slots.
+struct OvSets {
+    const OvTables* sets = nullptr;
+    const uint8_t* ids = nullptr;
+};
 // Lane and text into n surfaces in `layout`: tab[0, n) (device memory: the context's table from the launch's first slot), whose host
 // mirror entries[0, n) decides the kernel (alignment).  rows4 = two runs of camera rows {a0, a1, b0, b1} outside which nothing can
 // change (they may overlap or be empty).  kin / rgb2yuv[8]: 4:2:0 only.
-void launch_inplace(hipStream_t s, int layout, const SurfEntry* tab, const SurfEntry* entries, int n, int h, int w, const int rows4[4],
-                    InplaceLane l, InplaceText t, YuvCoef kin, const int32_t* rgb2yuv);
+// -> the launches enqueued
+int launch_inplace(hipStream_t s, int layout, const SurfEntry* tab, const SurfEntry* entries, int n, int h, int w, const int rows4[4],
+                   InplaceLane l, InplaceText t, YuvCoef kin, const int32_t* rgb2yuv, OvSets per_slot = OvSets());
+// Lane and text drawn on the way from the slots' dense RGB camera frames into the caller's surfaces (k_draw_sink.hip): frame z of
+// `rgb` (rgb_stride bytes apart) -> entries[z] (host memory) in `layout`, with the tables sets[ids[z]] and the row intervals and
+// text of slot z from l.spans / t (l.oxy / l.ofrac are not read).  Lane lookups in camera rows [lane_r0, lane_r1) only, the glyph
+// search in the text's rows only; every other row is a plain conversion.  SurfChunk::N surfaces per launch.  -> the launches enqueued
+int launch_draw_to_surfaces(hipStream_t s, int layout, const uint8_t* rgb, size_t rgb_stride, int h, int w, const SurfEntry* entries,
+                            int n, const OvTables* sets, const uint8_t* ids, InplaceLane l, InplaceText t, int lane_r0, int lane_r1,
+                            const int32_t* coeffs);
 void launch_split_bev(hipStream_t s, const uint8_t* bev, size_t bev_stride, int npix, const uint16_t* gamma_tab,
                       const uint16_t* cbrt_tab, const int32_t* coeffs, uint8_t* planeR, uint8_t* planeB,
                       size_t plane_stride, int n);
@@ -163,9 +186,10 @@ void preload_k_overlay(hipStream_t s);
 bool launch_overlay_lane_strip(hipStream_t s, const uint8_t* frames, size_t frame_stride, uint8_t* strips, size_t strip_stride,
                                const int16_t* oxy, const uint16_t* ofrac, const int16_t* spans, size_t span_stride_rows, int img_w,
                                int row0, int row1, int bh, int bw, float alpha, int n);
-void launch_overlay_lane(hipStream_t s, const uint8_t* frames, uint8_t* out, size_t frame_stride, const int16_t* oxy,
-                         const uint16_t* ofrac, const int16_t* spans, size_t span_stride_rows, int img_h, int img_w,
-                         int bh, int bw, float alpha, int n, const int* rows4 = nullptr);
+// (-> the launches enqueued; per_slot: every slot with the tables of its own set, oxy / ofrac are not read then)
+int launch_overlay_lane(hipStream_t s, const uint8_t* frames, uint8_t* out, size_t frame_stride, const int16_t* oxy,
+                        const uint16_t* ofrac, const int16_t* spans, size_t span_stride_rows, int img_h, int img_w,
+                        int bh, int bw, float alpha, int n, const int* rows4 = nullptr, OvSets per_slot = OvSets());
 // one frame, the row intervals (host memory, bh pairs) passed as a kernel argument; rows4 = nullptr: the whole frame, else two
 // runs of camera rows {a0, a1, b0, b1} (the others are not written); false: not launched (bh above LT_SPAN_ARG_ROWS, a row
 // length that is no multiple of 4, or the runtime refused the argument block)

@@ -128,6 +128,12 @@ int lt_overlay_configure_set(lt_ctx* c, int set, const double* Minv) {
     }
     HIP_TRY(hipMemcpy(q.d_oxy, t.xy.data(), t.xy.size() * 2, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(q.d_ofrac, t.frac.data(), t.frac.size() * 2, hipMemcpyHostToDevice));
+    // the set's entry of the table of overlay tables (the table-per-slot presentation kernels; nothing is in flight here)
+    if (!c->d_ov && (rc = dev_alloc(&c->d_ov, (size_t)LT_MAX_CALIBRATIONS))) return rc;
+    {
+        const OvTables entry{q.d_oxy, q.d_ofrac};
+        HIP_TRY(hipMemcpy(c->d_ov + set, &entry, sizeof entry, hipMemcpyHostToDevice));
+    }
     // Camera rows the lane can reach at all: a pixel's four taps are (sx, sy) .. (sx + 1, sy + 1), so only pixels with
     // -1 <= sx <= bw - 1 and -1 <= sy <= bh - 1 can see the bird's-eye image; every other pixel of the annotated frame is the
     // camera pixel whatever the polygon (lt_overlay_rows, lt_present_frame).
@@ -394,6 +400,13 @@ static void fill_span_staging(int16_t* hs, int bh, int n, const int32_t* left_n,
     }
 }
 
+// the tables of a presentation launch over slots [first, first + n): per slot where the range mixes calibration sets
+static OvSets slot_tables(const lt_ctx* c, int first, int n) {
+    for (int i = first + 1; i < first + n; ++i)
+        if (slot_set(c, i) != slot_set(c, first)) return OvSets{c->d_ov, &c->slot_cal[(size_t)first]};
+    return OvSets{};
+}
+
 static int overlay_run_impl(lt_ctx* c, int first, int n, const int32_t* left_n, const int32_t* right_n, const int32_t* left_yx,
                             const int32_t* right_yx, double alpha, const int* rows4, bool strip = false, uint8_t* direct_out = nullptr,
                             bool* went_direct = nullptr, const CoeffInput* ci = nullptr) {
@@ -466,6 +479,7 @@ static int overlay_run_impl(lt_ctx* c, int first, int n, const int32_t* left_n, 
         if (launch_overlay_lane_one(ps, slot_frame(c, first), dst,
                                     q.d_oxy, q.d_ofrac, hs, c->calib.img_h, c->calib.img_w, bh, c->calib.warp_w, (float)alpha, rows4)) {
             HIP_TRY(hipGetLastError());
+            c->last_overlay_launches = 1;
             if (went_direct) *went_direct = direct_out != nullptr;
             if (!direct_out) mark_annot(c, first, n, rows4 ? 0 : 1);
             return note_range(c->readers, ps, first, first + n);
@@ -480,23 +494,25 @@ static int overlay_run_impl(lt_ctx* c, int first, int n, const int32_t* left_n, 
     if (ci && !launch_lane_spans_from_regions(ps, c->d_ploty, c->d_ploty + ci->n_rows, ci->n_rows, bh, c->calib.warp_w, c->d_spans + (size_t)first * bh * 2, n))
         return fail(LT_ERR_STATE, "lt_overlay_run_strip_coeffs: not available for this bird's-eye height");
     const auto t2 = std::chrono::steady_clock::now();
+    int launches = 0;
     if (strip) {
         if (!launch_overlay_lane_strip(ps, slot_frame(c, first), c->frame_bytes, c->d_strip + (size_t)first * c->strip_bytes,
                                        c->strip_bytes, c->d_oxy, c->d_ofrac, c->d_spans + (size_t)first * bh * 2, (size_t)bh, c->calib.img_w,
                                        c->ov_r0, c->ov_r1, bh, c->calib.warp_w, (float)alpha, n))
             return fail(LT_ERR_STATE, "strip overlay needs a frame width that is a multiple of 4");
     } else {
-        // run by run over consecutive slots of one calibration set (one launch where the range has one set)
-        for (int a = first, b; a < first + n; a = b) {
-            for (b = a + 1; b < first + n && slot_set(c, b) == slot_set(c, a); ++b) {}
-            const lt_ctx::CalSet& q = c->cal[(size_t)slot_set(c, a)];
-            launch_overlay_lane(ps, slot_frame(c, a), c->d_annot + (size_t)a * c->frame_bytes,
-                                c->frame_bytes, q.d_oxy, q.d_ofrac, c->d_spans + (size_t)a * bh * 2, (size_t)bh,
-                                c->calib.img_h, c->calib.img_w, bh, c->calib.warp_w, (float)alpha, b - a, rows4);
-        }
+        // one set in the range: its tables, today's kernels; several: every slot with the tables of its own set (CalIds::N slots per
+        // launch) -- a pixel outside its own set's lane rows has lane value 0, so whole frames and the caller's row runs serve all
+        const lt_ctx::CalSet& q = c->cal[(size_t)slot_set(c, first)];
+        launches = launch_overlay_lane(ps, slot_frame(c, first), c->d_annot + (size_t)first * c->frame_bytes,
+                                       c->frame_bytes, q.d_oxy, q.d_ofrac, c->d_spans + (size_t)first * bh * 2, (size_t)bh,
+                                       c->calib.img_h, c->calib.img_w, bh, c->calib.warp_w, (float)alpha, n, rows4, slot_tables(c, first, n));
     }
     HIP_TRY(hipGetLastError());
-    if (!strip) mark_annot(c, first, n, rows4 ? 0 : 1);
+    if (!strip) {
+        mark_annot(c, first, n, rows4 ? 0 : 1);
+        c->last_overlay_launches = launches;
+    }
     if ((rc = staging_mark(c->spans_busy, ps))) return rc;
     rc = note_range(c->readers, ps, first, first + n);
     if (timing) {
@@ -794,22 +810,38 @@ static int inplace_impl(lt_ctx* c, int first, int n, const int32_t* left_n, cons
             if (!p2) HIP_TRY(hipStreamWaitEvent(ps, c->rest_done, 0));
         }
     }
+    // Slots outside the range that are attached to one of these surfaces as well (a group's second try attaches a stream's frame to
+    // a spare slot): their front end reads the bytes the draw changes, so the draw waits for them too, and they are detached with
+    // the range below -- no slot stays attached to a surface that holds no camera frame any more.
+    std::vector<int> aliases;
+    {
+        std::vector<uint64_t> drawn_planes;
+        for (int i = first; i < first + n; ++i) drawn_planes.push_back(c->surf[(size_t)i].plane[0]);
+        std::sort(drawn_planes.begin(), drawn_planes.end());
+        for (int s = 0; s < (int)c->attached.size(); ++s)
+            if (c->attached[(size_t)s] && (s < first || s >= first + n) &&
+                std::binary_search(drawn_planes.begin(), drawn_planes.end(), c->surf[(size_t)s].plane[0]))
+                aliases.push_back(s);
+        for (int s : aliases) {
+            bool precise = true;
+            if ((rc = wait_range(c->readers, ps, s, s + 1, &precise))) return rc;
+            precise = precise && s < (int)c->front_ok.size() && c->front_ok[(size_t)s] != 0;
+            if (!precise && (rc = for_each_slice(c, s, 1, [&](hipStream_t st, int, int) { return wait_tail(c, ps, st); }))) return rc;
+        }
+    }
     launch_copy_from_pinned(ps, c->d_spans + (size_t)first * bh * 2, hs, (size_t)n * bh * 2 * sizeof(int16_t));
     if (ci && !launch_lane_spans_from_regions(ps, c->d_ploty, c->d_ploty + ci->n_rows, ci->n_rows, bh, c->calib.warp_w, c->d_spans + (size_t)first * bh * 2, n))
         return fail(LT_ERR_STATE, "lt_overlay_run_inplace_coeffs: not available for this bird's-eye height");
-    // run by run over consecutive slots of one calibration set
-    for (int a = first, b; a < first + n; a = b) {
-        for (b = a + 1; b < first + n && slot_set(c, b) == slot_set(c, a); ++b) {}
-        const lt_ctx::CalSet& q = c->cal[(size_t)slot_set(c, a)];
+    // One set in the range: its tables and its lane rows, today's kernels.  Several: every slot with the tables of its own set over
+    // the union of the sets' lane rows (a pixel outside its own set's rows has lane value 0 and stores nothing), CalIds::N per launch.
+    int launches;
+    {
+        const OvSets per_slot = slot_tables(c, first, n);
+        const lt_ctx::CalSet& q = c->cal[(size_t)slot_set(c, first)];
         const int t0 = have_text ? text->y0 : 0, t1 = have_text ? text->y0 + (text->n_lines - 1) * text->step + c->font_gh : 0;
-        const int rows4[4] = {t0, t1, q.ov_r0, q.ov_r1};
-        InplaceLane l{q.d_oxy, q.d_ofrac, c->d_spans + (size_t)a * bh * 2, (size_t)bh, bh, c->calib.warp_w, (float)alpha};
-        InplaceText ta = t;
-        if (have_text) {
-            ta.lines = t.lines + (size_t)(a - first) * t.slot_chars;
-            ta.xpos = t.xpos + (size_t)(a - first) * t.slot_chars;
-        }
-        launch_inplace(ps, c->in_layout, c->d_surf + a, &c->surf[(size_t)a], b - a, H, W, rows4, l, ta, yuv_coef_of(c), rgb2yuv);
+        const int rows4[4] = {t0, t1, per_slot.sets ? c->ov_r0 : q.ov_r0, per_slot.sets ? c->ov_r1 : q.ov_r1};
+        InplaceLane l{q.d_oxy, q.d_ofrac, c->d_spans + (size_t)first * bh * 2, (size_t)bh, bh, c->calib.warp_w, (float)alpha};
+        launches = launch_inplace(ps, c->in_layout, c->d_surf + first, &c->surf[(size_t)first], n, H, W, rows4, l, t, yuv_coef_of(c), rgb2yuv, per_slot);
     }
     HIP_TRY(hipGetLastError());
     if ((rc = staging_mark(c->spans_busy, ps))) return rc;
@@ -817,12 +849,17 @@ static int inplace_impl(lt_ctx* c, int first, int n, const int32_t* left_n, cons
     if ((rc = note_range(c->readers, ps, first, first + n))) return rc;       // it reads the slots' table entries: the next attach waits
     HIP_TRY(hipEventRecord(c->store_done, ps));
     c->store_pending = true;
+    c->last_overlay_launches = launches;
     // The surfaces no longer hold camera frames: the slots are detached -- nothing of the library reads them again, and a later
     // sink is not refused for overlapping them -- and marked, so that a front end over them is refused until new frames come.
     if (c->drawn.size() < (size_t)c->capacity) c->drawn.resize((size_t)c->capacity, 0);
     for (int i = first; i < first + n; ++i) {
         c->attached[(size_t)i] = 0;
         c->drawn[(size_t)i] = 1;
+    }
+    for (int s : aliases) {
+        c->attached[(size_t)s] = 0;
+        c->drawn[(size_t)s] = 1;
     }
     return LT_OK;
 }
@@ -840,6 +877,91 @@ int lt_overlay_run_inplace_coeffs(lt_ctx* c, int first, int n, const double* coe
         return fail(LT_ERR_STATE, "lt_overlay_run_inplace_coeffs: not available for this bird's-eye height");
     const CoeffInput ci{coeffs, draw, ploty, ploty2, n_rows};
     return inplace_impl(c, first, n, nullptr, nullptr, nullptr, nullptr, &ci, alpha, text, rgb2yuv);
+}
+
+// ---- lane and text drawn on the way into the caller's surfaces (k_draw_sink.hip) ---------------------------------------------------
+// lt_overlay_run + lt_overlay_text + lt_overlay_store_device in one pass and one launch per SurfChunk::N slots, whatever the slots'
+// calibration sets: no annotated frame is kept (lt_download_overlay / lt_overlay_store_device over these slots see what was there
+// before).  Everything is checked before anything is allocated, staged or launched.
+int lt_overlay_run_to_surfaces(lt_ctx* c, int first, int n, const int32_t* left_n, const int32_t* right_n, const int32_t* left_yx,
+                               const int32_t* right_yx, double alpha, const lt_inplace_text* text, const lt_device_surface* dst, int layout,
+                               const int32_t* coeffs) {
+    int rc = check_slots(c, first, n);
+    if (rc) return rc;
+    if (!c->have_overlay && first_foreign(c, first, n) < 0) return fail(LT_ERR_STATE, "lt_overlay_run_to_surfaces before lt_overlay_configure");
+    for (int i = first; i < first + n; ++i)
+        if (!c->cal[(size_t)slot_set(c, i)].have_overlay)
+            return fail(LT_ERR_STATE, "lt_overlay_run_to_surfaces before lt_overlay_configure: slot %d has calibration set %d, whose overlay is not configured", i, slot_set(c, i));
+    const int bh = c->calib.warp_h, H = c->calib.img_h, W = c->calib.img_w;
+    if ((rc = check_sink_format(layout, H, W, coeffs))) return rc;
+    if (n == 0) return LT_OK;
+    if (!left_n || !right_n) return fail(LT_ERR_INVALID, "null point counts");
+    {
+        long long tl = 0, tr = 0;
+        for (int i = 0; i < n; ++i) {
+            if (left_n[i] < 0 || right_n[i] < 0) return fail(LT_ERR_INVALID, "negative point count");
+            tl += left_n[i];
+            tr += right_n[i];
+        }
+        if ((tl && !left_yx) || (tr && !right_yx)) return fail(LT_ERR_INVALID, "null point list");
+    }
+    if (!dst) return fail(LT_ERR_INVALID, "null surfaces");
+    const bool have_text = text && text->n_lines > 0 && text->line_len > 0;
+    if (have_text) {
+        if (!c->font_glyphs) return fail(LT_ERR_STATE, "lt_overlay_run_to_surfaces with text before lt_overlay_set_font");
+        if (!text->lines) return fail(LT_ERR_INVALID, "null text");
+        if (text->step < c->font_gh) return fail(LT_ERR_INVALID, "text lines %d rows apart would overlap (the glyphs are %d rows high)", text->step, c->font_gh);
+    }
+    {
+        const int bad = first_partial(c->frame_full, first, n);
+        if (bad >= 0)
+            return fail(LT_ERR_STATE, "slot %d holds only part of its camera frame (lt_upload_frame_rows without lt_upload_frame_rest): a whole-frame "
+                                      "overlay would show rows of the block's previous occupant", bad);
+    }
+    if ((rc = set_device(c))) return rc;
+    std::vector<SurfEntry> ent;
+    if ((rc = check_ctx_sinks(c, dst, n, layout, ent))) return rc;
+    if (!c->d_spans && (rc = dev_alloc(&c->d_spans, (size_t)c->capacity * bh * 2))) return rc;
+    if (!c->store_done && hipEventCreateWithFlags(&c->store_done, hipEventDisableTiming) != hipSuccess) return fail(LT_ERR_HIP, "hipEventCreate failed");
+    if ((rc = staging_claim(c->spans_busy, first, n))) return rc;
+    if ((rc = ensure_span_staging(c))) return rc;
+    int16_t* hs = c->h_spans + (size_t)first * bh * 2;
+    fill_span_staging(hs, bh, n, left_n, right_n, left_yx, right_yx, nullptr);
+    if ((rc = present_stream(c))) return rc;
+    hipStream_t ps = c->present;
+    InplaceText t{};
+    if (have_text) {
+        const uint8_t* kl = nullptr;
+        const int16_t* kx = nullptr;
+        size_t stride = 0;
+        // (to the device whatever n: every pixel of the text's rows searches the positions)
+        if ((rc = stage_text(c, first, n, text->lines, text->n_lines, text->line_len, text->x0, &kl, &kx, &stride, false))) return rc;
+        t = InplaceText{c->d_atlas, c->d_advance, kl, kx, c->font_first, c->font_glyphs, c->font_gw, c->font_gh, text->n_lines, text->line_len,
+                        (int)stride, text->y0, text->step};
+    }
+    // as lt_overlay_run: behind the copies of the rows the path does not read, and behind the launches that wrote the slots' masks
+    if (c->rest_pending) {
+        bool precise = true;
+        if ((rc = wait_range(c->rests, ps, first, first + n, &precise))) return rc;
+        if (!precise) HIP_TRY(hipStreamWaitEvent(ps, c->rest_done, 0));
+    }
+    {
+        bool precise = true;
+        if ((rc = wait_range(c->writers, ps, first, first + n, &precise))) return rc;
+        if (!precise && (rc = for_each_slice(c, first, n, [&](hipStream_t st, int, int) { return wait_tail(c, ps, st); }))) return rc;
+    }
+    launch_copy_from_pinned(ps, c->d_spans + (size_t)first * bh * 2, hs, (size_t)n * bh * 2 * sizeof(int16_t));
+    InplaceLane l{nullptr, nullptr, c->d_spans + (size_t)first * bh * 2, (size_t)bh, bh, c->calib.warp_w, (float)alpha};
+    const int launches = launch_draw_to_surfaces(ps, layout, slot_frame(c, first), c->frame_bytes, H, W, ent.data(), n, c->d_ov,
+                                                 &c->slot_cal[(size_t)first], l, t, c->ov_r0, c->ov_r1, coeffs);
+    HIP_TRY(hipGetLastError());
+    if ((rc = staging_mark(c->spans_busy, ps))) return rc;
+    if (have_text && (rc = staging_mark(c->text_busy, ps))) return rc;
+    if ((rc = note_range(c->readers, ps, first, first + n))) return rc;
+    HIP_TRY(hipEventRecord(c->store_done, ps));
+    c->store_pending = true;
+    c->last_overlay_launches = launches;
+    return LT_OK;
 }
 
 int lt_download_overlay(lt_ctx* c, int first, int n, uint8_t* out) {

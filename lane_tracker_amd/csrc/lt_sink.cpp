@@ -77,6 +77,35 @@ const ByteRange* overlapping(const std::vector<ByteRange>& ranges, uintptr_t lo,
 
 }  // namespace
 
+namespace lt {
+
+int check_sink_format(int layout, int h, int w, const int32_t* coeffs) { return check_format(layout, h, w, coeffs); }
+
+int check_ctx_sinks(lt_ctx* c, const lt_device_surface* dst, int n, int layout, std::vector<SurfEntry>& ent) {
+    const int H = c->calib.img_h, W = c->calib.img_w;
+    std::vector<ByteRange> ranges;
+    int rc = check_sinks(c->device, dst, n, layout, H, W, ent, ranges);
+    if (rc) return rc;
+    // The front end of an attached slot reads its surface whenever its next lt_mask_run / lt_device_frames_rest comes: a sink
+    // may not share a byte with any of them (the host mirror of the surface table says where they are).
+    const int in_planes = plane_count(c->in_layout);
+    for (size_t s = 0; s < c->attached.size(); ++s) {
+        if (!c->attached[s]) continue;
+        const SurfEntry& a = c->surf[s];
+        for (int i = 0; i < in_planes; ++i) {
+            int rows, rb;
+            plane_geom(c->in_layout, H, W, i, &rows, &rb);
+            const uintptr_t lo = (uintptr_t)a.plane[i], hi = lo + (size_t)(i == 0 ? a.pitch : a.cpitch) * (size_t)(rows - 1) + (size_t)rb;
+            if (const ByteRange* r = overlapping(ranges, lo, hi))
+                return fail(LT_ERR_INVALID, "surface %d plane %d overlaps the camera surface attached to slot %d: annotating a surface in place is not supported",
+                            r->surface, r->plane, (int)s);
+        }
+    }
+    return LT_OK;
+}
+
+}  // namespace lt
+
 extern "C" {
 
 int lt_rgb_to_surfaces(int device, const void* rgb, size_t frame_stride, int h, int w, int n, const lt_device_surface* dst, int layout,
@@ -131,23 +160,7 @@ int lt_overlay_store_device(lt_ctx* c, int first, int n, const lt_device_surface
     }
     if ((rc = set_device(c))) return rc;
     std::vector<SurfEntry> ent;
-    std::vector<ByteRange> ranges;
-    if ((rc = check_sinks(c->device, dst, n, layout, H, W, ent, ranges))) return rc;
-    // The front end of an attached slot reads its surface whenever its next lt_mask_run / lt_device_frames_rest comes: a sink
-    // may not share a byte with any of them (the host mirror of the surface table says where they are).
-    const int in_planes = plane_count(c->in_layout);
-    for (size_t s = 0; s < c->attached.size(); ++s) {
-        if (!c->attached[s]) continue;
-        const SurfEntry& a = c->surf[s];
-        for (int i = 0; i < in_planes; ++i) {
-            int rows, rb;
-            plane_geom(c->in_layout, H, W, i, &rows, &rb);
-            const uintptr_t lo = (uintptr_t)a.plane[i], hi = lo + (size_t)(i == 0 ? a.pitch : a.cpitch) * (size_t)(rows - 1) + (size_t)rb;
-            if (const ByteRange* r = overlapping(ranges, lo, hi))
-                return fail(LT_ERR_INVALID, "surface %d plane %d overlaps the camera surface attached to slot %d: annotating a surface in place is not supported",
-                            r->surface, r->plane, (int)s);
-        }
-    }
+    if ((rc = check_ctx_sinks(c, dst, n, layout, ent))) return rc;
     if (!c->store_done && hipEventCreateWithFlags(&c->store_done, hipEventDisableTiming) != hipSuccess) return fail(LT_ERR_HIP, "hipEventCreate failed");
     // On the presentation stream: behind the lt_overlay_run / lt_overlay_text that wrote these frames, ahead of the next ones over
     // the same slots.  The store only reads the annotated frames, so a download in flight on the download stream is no hazard.

@@ -1,4 +1,4 @@
-// The lane polygon as a camera pixel sees it (device code shared by k_overlay.hip and k_inplace.hip).
+// The lane polygon and the text as a camera pixel sees them (device code shared by k_overlay.hip, k_inplace.hip and k_draw_sink.hip).
 //
 // The filled polygon is never rasterised: it is y-monotone (both lane curves are functions of y), so it is described by one
 // column interval [lo, hi] per bird's-eye row (`spans`).  The inverse warp is OpenCV's fixed-point bilinear remap of that 0/255
@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include "inplace_arith.h"
+#include "lt_internal.h"
 
 namespace lt {
 
@@ -25,5 +26,43 @@ __device__ __forceinline__ int lane_value(const short2* __restrict__ spans, int 
 }
 
 using ia::blend_green;
+
+// The alpha of the glyph over pixel (x, y) of frame z, 0 where there is none.  The line comes from y0 / step / gh (lines do not
+// overlap: step >= gh, checked on the host), the character from the slot's positions: xpos[] never decreases along a line (a
+// running sum of advances), cells are disjoint, so the last character that starts at or before x is the only candidate.
+__device__ __forceinline__ int text_alpha(const InplaceText& t, int z, int x, int y) {
+    const int dy = y - t.y0;
+    if (t.nl <= 0 || dy < 0) return 0;
+    const int line = dy / t.step, gy = dy - line * t.step;
+    if (line >= t.nl || gy >= t.gh) return 0;
+    const size_t base = (size_t)z * t.slot_chars + (size_t)line * t.len;
+    const int16_t* __restrict__ xp = t.xpos + base;
+    int lo = 0, hi = t.len;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (xp[mid] <= x) lo = mid + 1;
+        else hi = mid;
+    }
+    if (lo == 0) return 0;
+    const int k = lo - 1;
+    const int ch = (int)t.lines[base + k] - t.first_char;
+    if (ch < 0 || ch >= t.n_glyphs) return 0;
+    const int gx = x - xp[k];
+    if (gx >= t.advance[ch] || gx >= t.gw) return 0;
+    return t.atlas[((size_t)ch * t.gh + gy) * t.gw + gx];
+}
+
+// The tables policy of the table-per-slot presentation kernels, as the front end's SlotTables: frame z of a launch takes the
+// inverse-warp tables of its own calibration set -- uniform per workgroup (z is blockIdx.z), so the pair arrives by scalar loads.
+struct SlotOv {
+    const OvTables* sets;
+    const CalIds* ids;
+    __device__ __forceinline__ const OvTables& of(int z) const { return sets[(ids->w[z >> 2] >> (8 * (z & 3))) & 255u]; }
+};
+inline CalIds pack_cal_ids(const uint8_t* ids, int m) {
+    CalIds c{};
+    for (int i = 0; i < m; ++i) c.w[i >> 2] |= (uint32_t)ids[i] << (8 * (i & 3));
+    return c;
+}
 
 }  // namespace lt

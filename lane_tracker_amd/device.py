@@ -328,6 +328,16 @@ class DeviceFrames:
         return DeviceFrames(s, self.img_size, self.pixel_format, owner=self.owner, single=single, stream=self.stream, device=self.device,
                             readonly=self.readonly)
 
+    def select(self, indices):
+        """The frames at `indices` (any order, as a list), as a window: what `frames[a:b]` is for a slice."""
+        n = len(self.surfaces)
+        idx = [int(i) for i in indices]
+        for i in idx:
+            if not -n <= i < n:
+                raise IndexError("frame %d of %d" % (i, n))
+        return DeviceFrames(self.surfaces[np.asarray(idx, np.intp)], self.img_size, self.pixel_format, owner=self.owner, single=False,
+                            stream=self.stream, device=self.device, readonly=self.readonly)
+
     @property
     def shape(self):
         """The shape of the host array these frames would be."""

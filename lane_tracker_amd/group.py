@@ -19,7 +19,7 @@ import numpy as np
 from . import _native
 from .device import DeviceFrames, feed_rest_list, feed_rows_list
 from .lane_tracker import LaneTracker
-from .stream import StreamPipeline
+from .stream import StreamPipeline, _pack_deferred
 
 
 class _GroupMember(LaneTracker):
@@ -196,22 +196,44 @@ class LaneTrackerGroup:
             if diagnostics:
                 print("Lane pixels found." if t.detected_pixels else "No lane pixels found.")
 
-    def process(self, frames, annotate=True, **kwargs):
-        """One frame per stream: `frames[i]` (RGB u8, img_size) for stream i, or None -- stream i skips this call.  `kwargs` are
+    def process(self, frames, annotate=True, out=None, out_yuv_matrix=None, **kwargs):
+        """One frame per stream: `frames[i]` (a host array or a one-frame `DeviceFrames` of img_size in the group's pixel format) for
+        stream i, or None -- stream i skips this call.  `kwargs` are
         `LaneTracker.process()`'s keywords (one set for the whole group; visualize_search / split_view are not available).
         Returns a list of k entries: stream i's annotated frame (views of one block), or None for a skipped stream and for
-        every stream with `annotate=False` (the states are updated identically)."""
+        every stream with `annotate=False` (the states are updated identically).
+        `out`: a device sink -- a `DeviceFrames` of the group's `img_size` with k surfaces on the group's device, 'rgb', 'nv12' or
+        'i420' at any pitch; surface i is stream i's.  The annotated frames of the active streams are drawn on their way into their
+        surfaces by one kernel launch, whatever the streams' calibrations (lt_overlay_run_to_surfaces; 4:2:0 converted with
+        `out_yuv_matrix`, None: 'bt601'), and no frame crosses the bus on the way out; the surfaces of skipped streams are not touched.
+        Returns `out[i]` for active streams and None for skipped ones, final when the call returns.
+        `out="inplace"`: every active frame is a writeable one-frame `DeviceFrames`, and lane and text are drawn INTO them by one
+        launch (lt_overlay_run_inplace; `out_yuv_matrix=None`: the group's own `yuv_matrix`, which must then be a preset's name).
+        Returns the frames handed in.  Both need `annotate=True`; states and attributes are those of the same call without `out`."""
         if self._ctx is None:
             raise RuntimeError("the group is closed")
         frames = list(frames)
         if len(frames) != self.k:
             raise ValueError("expected %d frames (None for a stream that skips this call), got %d" % (self.k, len(frames)))
-        kw, first_try, fp = self.trackers[0]._batch_arguments(kwargs)
+        t0 = self.trackers[0]
+        kw, first_try, fp = t0._batch_arguments(kwargs)
         if kw["visualize_search"] or kw["split_view"]:
             raise NotImplementedError("search visualisation / split view are not available for a group: use the streams' own trackers "
                                       "(process, process_batch, process_stream)")
         n_tries, diagnostics = kw["n_tries"], kw["diagnostics"]
         active = [i for i, f in enumerate(frames) if f is not None]
+        # the destination of the annotated frames, checked before anything reaches the device
+        t0._sink_keywords(out, annotate, kw)
+        in_place = isinstance(out, str)
+        sink = None
+        if in_place:
+            out_yuv_matrix = t0._inplace_matrix(out, out_yuv_matrix)
+            for i in active:
+                t0._check_inplace_source(frames[i])
+        elif out is not None:
+            sink = t0._check_sink(out, self.k)
+            out_yuv_matrix = 'bt601' if out_yuv_matrix is None else out_yuv_matrix
+            _native.rgb2yuv_coeffs(out_yuv_matrix)
         outs = [None] * self.k
         if not active:
             return outs
@@ -236,8 +258,10 @@ class LaneTrackerGroup:
         if self._many_sets:                                              # every slot with its stream's calibration set
             ctx.set_slot_calibrations([self._cal_ids[i] for i in active], first=base)
         ctx.mask_run(m, fp, first=base)
+        keep_rest = None
         if annotate:
-            keep_rest = feed_rest_list(ctx, imgs, base)                  # (for the overlay, beside the mask chain)
+            if not in_place:                                             # (an in-place draw reads the surfaces themselves)
+                keep_rest = feed_rest_list(ctx, imgs, base)              # (for the overlay, beside the mask chain)
             ts[0]._configure_overlay()                                   # (every member configured its set's overlay when it was built)
         for t in ts:                                                     # _step's opening
             t._open_frame()
@@ -281,10 +305,23 @@ class LaneTrackerGroup:
                 t._record_success(fits[j][0], fits[j][1], partials[j])
             if annotate:
                 deferred.append(t._deferred_picture())
-        # 6: ... drawn by one overlay launch and one download
-        if annotate:
-            for i, out in zip(active, ts[0]._render_window(deferred, base)):
-                outs[i] = out
-            del keep_rest
+        # 6: ... drawn by one overlay launch and one download -- or, with `out`, by one launch into the sink's surfaces / into the
+        # frames themselves (a second try attached its surface to a spare slot as well: the draw detaches every slot of a surface)
+        if in_place:
+            ts[0]._draw_in_place(deferred, base, out_yuv_matrix)
+            ctx.store_wait()
+            for i in active:
+                outs[i] = frames[i]
+        elif sink is not None:
+            lines = [d[2] for d in deferred] if ts[0]._have_font else None
+            ctx.overlay_run_to_surfaces_packed(*_pack_deferred(deferred), sink.select(active), first=base, lines=lines,
+                                               origin=ts[0]._TEXT_ORIGIN, step=ts[0]._TEXT_STEP, matrix=out_yuv_matrix)
+            ctx.store_wait()
+            for i in active:
+                outs[i] = sink[i]
+        elif annotate:
+            for i, picture in zip(active, ts[0]._render_window(deferred, base)):
+                outs[i] = picture
+        del keep_rest
         del keep
         return outs

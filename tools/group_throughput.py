@@ -11,6 +11,13 @@ pool of frames), annotated, process()'s default keywords:
 
   python tools/group_throughput.py [--ticks 60] [--warmup 8] [--out profiles/group_throughput.jsonl] [--no-solo]
                                    [--distinct-calibrations] [--front-end-times]
+                                   [--frames-out host|sink|inplace] [--sink-format rgb|nv12|i420] [--device-frames]
+
+--frames-out: where a tick's annotated frames go -- `host` (the default: one download), `sink` (process(out=) a DeviceFrames of K
+surfaces in --sink-format: one lt_overlay_run_to_surfaces per tick) or `inplace` (process(out="inplace"): drawn into the frames
+handed in, which must be in device memory).  --device-frames: the inputs of a tick are one-frame DeviceFrames (RGB), refreshed from
+the pool before the tick OUTSIDE the timed region; the rates are then K * ticks over the sum of the tick times.  Lines of these
+routes carry `frames_out`, `device_frames` and `overlay_launches` (lt_last_overlay_launches after the last tick).
 
 --distinct-calibrations: every stream a camera of its own (stream i: the distortion coefficients x (1 + 0.002 i)), so that the
 group's context holds K calibration sets and every slice of a tick mixes them (the table-per-slot front end); `calibrations` in
@@ -56,33 +63,71 @@ def distinct_calibrations(cal, k):
     return [None] + [dict(dist_coeffs=np.asarray(cal["dist_coeffs"], np.float64) * (1.0 + 0.002 * i)) for i in range(1, k)]
 
 
-def run_group(cal, pool, k, ticks, warmup, distinct=False, stages=None):
+class DeviceFeed:
+    """The frames of a tick as one-frame DeviceFrames: two sets of K RGB surfaces that take turns (a tick's slots stay attached to
+    its surfaces until the tick after the next), filled from the pool before the tick."""
+
+    def __init__(self, cal, k):
+        from lane_tracker_amd.device import DeviceFrames
+        self.sets = [[DeviceFrames.from_host(np.zeros((cal["img_size"][1], cal["img_size"][0], 3), np.uint8)) for _ in range(k)] for _ in range(2)]
+
+    def tick(self, pool, k, t):
+        frames = self.sets[t & 1]
+        for f, host in zip(frames, tick_frames(pool, k, t)):
+            f.owner.copy_from_host(np.ascontiguousarray(host).reshape(-1))
+        return frames
+
+    def close(self):
+        for s in self.sets:
+            for f in s:
+                f.owner.close()
+
+
+def run_group(cal, pool, k, ticks, warmup, distinct=False, stages=None, frames_out="host", sink_format="nv12", device_frames=False):
     kw = dict(calibrations=distinct_calibrations(cal, k)) if distinct else {}
+    feed = DeviceFeed(cal, k) if device_frames else None
+    sink = None
+    if frames_out == "sink":
+        from lane_tracker_amd.device import DeviceFrames
+        sink = DeviceFrames.empty(k, cal["img_size"], sink_format)
+    pkw = {} if frames_out == "host" else dict(out=sink if frames_out == "sink" else "inplace")
+    frames_of = (lambda t: feed.tick(pool, k, t)) if feed else (lambda t: tick_frames(pool, k, t))
     with LaneTrackerGroup(k, **cal, **kw) as g:
         if stages is not None:
             stages["calibrations"] = g.calibration_count() if hasattr(g, "calibration_count") else 1
         for t in range(warmup):
-            g.process(tick_frames(pool, k, t))
+            g.process(frames_of(t), **pkw)
         times = []
         c0, t0 = cpu_s(), time.perf_counter()
         for t in range(warmup, warmup + ticks):
+            frames = frames_of(t)
             a = time.perf_counter()
-            g.process(tick_frames(pool, k, t))
+            g.process(frames, **pkw)
             times.append(time.perf_counter() - a)
         wall, cpu = time.perf_counter() - t0, cpu_s() - c0
+        if feed:                        # (the refresh of the device frames is not the group's work)
+            wall = float(np.sum(times))
+        if stages is not None and (pkw or feed):
+            stages.update(frames_out=frames_out, device_frames=bool(feed), overlay_launches=g._ctx.last_overlay_launches())
+            if sink is not None:
+                stages["sink_format"] = sink_format
         if stages is not None and stages.get("front_end"):
             ctx = g._ctx
             ctx.sync()
             ctx.set_stage_timing(True)
             ctx.stage_reset()
             for t in range(warmup + ticks, warmup + 2 * ticks):
-                g.process(tick_frames(pool, k, t))
+                g.process(frames_of(t), **pkw)
             ctx.sync()
             ms = ctx.stage_ms()
             ctx.set_stage_timing(False)
             stages["undistort_ms"] = round(ms["undistort_rows"][0] / ticks, 4)
             stages["warp_ms"] = round(ms["warp_split"][0] / ticks, 4)
             stages["front_end_launches_per_tick"] = round((ms["undistort_rows"][1] + ms["warp_split"][1]) / ticks, 2)
+    if feed:
+        feed.close()
+    if sink is not None and sink.owner is not None:
+        sink.owner.close()
     return wall, cpu, np.array(times)
 
 
@@ -112,7 +157,12 @@ def main():
     ap.add_argument("--no-solo", action="store_true", help="the group only (a kernel trace of the group's ticks)")
     ap.add_argument("--distinct-calibrations", action="store_true", help="every stream a camera of its own calibration")
     ap.add_argument("--front-end-times", action="store_true", help="a second pass with stage timers: undistortion and warp per tick")
+    ap.add_argument("--frames-out", choices=("host", "sink", "inplace"), default="host", help="where the annotated frames of a tick go")
+    ap.add_argument("--sink-format", choices=("rgb", "nv12", "i420"), default="nv12", help="the pixel format of --frames-out sink")
+    ap.add_argument("--device-frames", action="store_true", help="the inputs are DeviceFrames (what --frames-out inplace needs)")
     a = ap.parse_args()
+    if a.frames_out == "inplace" and not a.device_frames:
+        ap.error("--frames-out inplace draws into the frames handed in: it needs --device-frames")
     plan = [("1280x720", calib.reference_calibration(), [int(v) for v in a.ks.split(",") if v]),
             ("1920x1080", calib.scaled_calibration(1.5), [int(v) for v in a.ks_1080p.split(",") if v])]
     out = open(a.out, "a") if a.out else None
@@ -121,7 +171,7 @@ def main():
         one_solo = None
         for k in ks:
             stages = dict(front_end=a.front_end_times)
-            gw, gc, times = run_group(cal, pool, k, a.ticks, a.warmup, a.distinct_calibrations, stages)
+            gw, gc, times = run_group(cal, pool, k, a.ticks, a.warmup, a.distinct_calibrations, stages, a.frames_out, a.sink_format, a.device_frames)
             stages.pop("front_end")
             n = k * a.ticks
             sw, sc = run_solo(cal, pool, k, a.ticks, a.warmup) if not a.no_solo else (float("nan"), float("nan"))
