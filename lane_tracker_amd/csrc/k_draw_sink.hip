@@ -204,13 +204,7 @@ int launch_draw_to_surfaces(hipStream_t s, int layout, const uint8_t* rgb, size_
         std::copy(entries + at, entries + at + m, ch.e);
         const CalIds ci = pack_cal_ids(ids + at, m);
         const uint8_t* src = rgb + (size_t)at * rgb_stride;
-        InplaceLane lz = l;
-        lz.spans = l.spans + (size_t)at * l.span_stride_rows * 2;
-        InplaceText tz = t;
-        if (t.nl > 0) {
-            tz.lines = t.lines + (size_t)at * t.slot_chars;
-            tz.xpos = t.xpos + (size_t)at * t.slot_chars;
-        }
+        const InplaceDraw d = advanced(l, t, at);
         size_t bits = rgb_stride | (size_t)(uintptr_t)src, cbits = 0;   // every base and pitch of the launch a multiple of 16 (I420 chroma: 8)?
         for (int j = 0; j < m; ++j) {
             bits |= (size_t)ch.e[j].plane[0] | (size_t)ch.e[j].pitch;
@@ -220,12 +214,12 @@ int launch_draw_to_surfaces(hipStream_t s, int layout, const uint8_t* rgb, size_
         if ((w & 15) == 0 && (bits & 15) == 0 && (cbits & 7) == 0) {
             const int groups = w / 16, items = ((h + 1) / 2) * groups;
             auto kern = layout == 0 ? k_draw_rows_to_surf<0> : layout == 1 ? k_draw_rows_to_surf<1> : k_draw_rows_to_surf<2>;
-            hipLaunchKernelGGL(kern, dim3((unsigned)((items + 255) / 256), 1, (unsigned)m), dim3(256), 0, s, src, rgb_stride, ch, sets, ci, lz, tz,
+            hipLaunchKernelGGL(kern, dim3((unsigned)((items + 255) / 256), 1, (unsigned)m), dim3(256), 0, s, src, rgb_stride, ch, sets, ci, d.l, d.t,
                                rows, k, h, w, groups, items);
         } else {
             const int groups = layout == 0 ? w : w / 2, items = (layout == 0 ? h : h / 2) * groups;
             auto kern = layout == 0 ? k_draw_rows_to_surf_any<0> : layout == 1 ? k_draw_rows_to_surf_any<1> : k_draw_rows_to_surf_any<2>;
-            hipLaunchKernelGGL(kern, dim3((unsigned)((items + 255) / 256), 1, (unsigned)m), dim3(256), 0, s, src, rgb_stride, ch, sets, ci, lz, tz,
+            hipLaunchKernelGGL(kern, dim3((unsigned)((items + 255) / 256), 1, (unsigned)m), dim3(256), 0, s, src, rgb_stride, ch, sets, ci, d.l, d.t,
                                rows, k, h, w, groups, items);
         }
     }

@@ -260,13 +260,7 @@ int launch_inplace(hipStream_t s, int layout, const SurfEntry* tab, const SurfEn
             if (layout != 0) cbits |= (size_t)entries[j].plane[1] | (size_t)entries[j].cpitch;
             if (layout == 2) cbits |= (size_t)entries[j].plane[2];
         }
-        InplaceLane lz = l;
-        lz.spans = l.spans + (size_t)at * l.span_stride_rows * 2;
-        InplaceText tz = t;
-        if (t.nl > 0) {
-            tz.lines = t.lines + (size_t)at * t.slot_chars;
-            tz.xpos = t.xpos + (size_t)at * t.slot_chars;
-        }
+        const InplaceDraw d = advanced(l, t, at);
         const CalIds ids = cal ? pack_cal_ids(per_slot.ids + at, m) : CalIds{};
         if (layout == 0) {
             const InplaceRows rows = merge_runs(rows4, 1, h);
@@ -275,8 +269,8 @@ int launch_inplace(hipStream_t s, int layout, const SurfEntry* tab, const SurfEn
             const bool four = (w & 3) == 0 && (ybits & 3) == 0;
             const int items = four ? nrows * (w >> 2) : nrows * w;
             const dim3 grid((unsigned)((items + 255) / 256), 1, (unsigned)m);
-            if (cal) hipLaunchKernelGGL(four ? k_inplace_rgb4_cal : k_inplace_rgb_cal, grid, dim3(256), 0, s, tab + at, rows, lz, tz, w, items, per_slot.sets, ids);
-            else hipLaunchKernelGGL(four ? k_inplace_rgb4 : k_inplace_rgb, grid, dim3(256), 0, s, tab + at, rows, lz, tz, w, items);
+            if (cal) hipLaunchKernelGGL(four ? k_inplace_rgb4_cal : k_inplace_rgb_cal, grid, dim3(256), 0, s, tab + at, rows, d.l, d.t, w, items, per_slot.sets, ids);
+            else hipLaunchKernelGGL(four ? k_inplace_rgb4 : k_inplace_rgb, grid, dim3(256), 0, s, tab + at, rows, d.l, d.t, w, items);
             ++launches;
             continue;
         }
@@ -289,10 +283,10 @@ int launch_inplace(hipStream_t s, int layout, const SurfEntry* tab, const SurfEn
         const dim3 grid((unsigned)((items + 255) / 256), 1, (unsigned)m);
         if (cal) {
             auto k = layout == 1 ? (wide ? k_inplace_420_cal<1, true> : k_inplace_420_cal<1, false>) : (wide ? k_inplace_420_cal<2, true> : k_inplace_420_cal<2, false>);
-            hipLaunchKernelGGL(k, grid, dim3(256), 0, s, tab + at, rows, lz, tz, kin, kout, w, groups, items, per_slot.sets, ids);
+            hipLaunchKernelGGL(k, grid, dim3(256), 0, s, tab + at, rows, d.l, d.t, kin, kout, w, groups, items, per_slot.sets, ids);
         } else {
             auto k = layout == 1 ? (wide ? k_inplace_420<1, true> : k_inplace_420<1, false>) : (wide ? k_inplace_420<2, true> : k_inplace_420<2, false>);
-            hipLaunchKernelGGL(k, grid, dim3(256), 0, s, tab + at, rows, lz, tz, kin, kout, w, groups, items);
+            hipLaunchKernelGGL(k, grid, dim3(256), 0, s, tab + at, rows, d.l, d.t, kin, kout, w, groups, items);
         }
         ++launches;
     }

@@ -477,6 +477,13 @@ bool launch_overlay_lane_strip(hipStream_t s, const uint8_t* frames, size_t fram
     return true;
 }
 
+// two runs of camera rows r = {a0, a1, b0, b1} (nullptr: the whole frame) as runs of pixel quads [qa, qa + na), [qb, qb + nb)
+struct QuadRuns { int qa, na, qb, nb; };
+static QuadRuns quad_runs(const int* r, int img_h, int img_w) {
+    const int q = img_w >> 2;
+    return r ? QuadRuns{r[0] * q, (r[1] - r[0]) * q, r[2] * q, (r[3] - r[2]) * q} : QuadRuns{0, img_h * q, 0, 0};
+}
+
 int launch_overlay_lane(hipStream_t s, const uint8_t* frames, uint8_t* out, size_t frame_stride, const int16_t* oxy,
                         const uint16_t* ofrac, const int16_t* spans, size_t span_stride_rows, int img_h, int img_w,
                         int bh, int bw, float alpha, int n, const int* rows4, OvSets per_slot) {
@@ -484,9 +491,7 @@ int launch_overlay_lane(hipStream_t s, const uint8_t* frames, uint8_t* out, size
     const int npix = img_h * img_w;
     const short2* sp = reinterpret_cast<const short2*>(spans);
     const bool four = (img_w & 3) == 0 && (frame_stride & 3) == 0;
-    const int qrow = img_w >> 2;
-    int qa = 0, na = npix >> 2, qb = 0, nb = 0;
-    if (four && rows4) { qa = rows4[0] * qrow; na = (rows4[1] - rows4[0]) * qrow; qb = rows4[2] * qrow; nb = (rows4[3] - rows4[2]) * qrow; }
+    const auto [qa, na, qb, nb] = quad_runs(rows4, img_h, img_w);
     if (four && na + nb <= 0) return 0;
     if (per_slot.sets) {         // every slot with the tables of its own set: CalIds::N slots per launch
         int launches = 0;
@@ -522,9 +527,7 @@ bool launch_overlay_lane_one(hipStream_t s, const uint8_t* frame, uint8_t* out, 
     if (refused || bh > SPAN_ARG_ROWS || (img_w & 3) || (((size_t)(uintptr_t)frame | (size_t)(uintptr_t)out) & 3)) return false;
     SpanArg arg;
     std::memcpy(arg.s, spans_host, (size_t)bh * sizeof(short2));
-    const int qrow = img_w >> 2;
-    int qa = 0, na = img_h * qrow, qb = 0, nb = 0;
-    if (rows4) { qa = rows4[0] * qrow; na = (rows4[1] - rows4[0]) * qrow; qb = rows4[2] * qrow; nb = (rows4[3] - rows4[2]) * qrow; }
+    const auto [qa, na, qb, nb] = quad_runs(rows4, img_h, img_w);
     if (na + nb <= 0) return true;
     (void)hipGetLastError();
     hipLaunchKernelGGL(k_overlay_lane4_arg, dim3((na + nb + 255) / 256), dim3(256), 0, s, reinterpret_cast<const uint32_t*>(frame),
@@ -542,10 +545,14 @@ void launch_store_word(hipStream_t s, unsigned* dev_word, unsigned value) {
 
 // row intervals of the averaged lane of the frame whose record is *rec (k_lane_spans_from_fit); false: too many rows for the LDS
 // the same for n frames whose averaged coefficients (6 doubles) and draw byte (offset 48) stand at the start of their interval regions
+static size_t lane_spans_lds(int bh, int n_rows) { return ((size_t)2 * bh + (size_t)2 * std::max(n_rows, 1)) * sizeof(int); }
+bool lane_spans_from_regions_available(int bh, int n_rows) {
+    return n_rows >= 0 && (bh & 1) == 0 && bh * 4 >= 56 && lane_spans_lds(bh, n_rows) <= 60 * 1024;   // (regions of 4 bh bytes: 8-byte aligned, >= 56 bytes)
+}
 bool launch_lane_spans_from_regions(hipStream_t s, const double* ploty, const double* ploty2, int n_rows, int bh, int bw, int16_t* spans,
                                     int n) {
-    const size_t lds = ((size_t)2 * bh + (size_t)2 * std::max(n_rows, 1)) * sizeof(int);
-    if (lds > 60 * 1024 || n_rows < 0 || n < 1 || (bh & 1) || bh * 4 < 56) return false;       // (regions of 4 bh bytes: 8-byte aligned, >= 56 bytes)
+    if (n < 1 || !lane_spans_from_regions_available(bh, n_rows)) return false;
+    const size_t lds = lane_spans_lds(bh, n_rows);
     LaneFromFit p;
     for (int k = 0; k < 6; ++k) p.prev_sum[k] = 0.0;
     p.count = 1;
@@ -559,7 +566,7 @@ bool launch_lane_spans_from_regions(hipStream_t s, const double* ploty, const do
 
 bool launch_lane_spans_from_fit(hipStream_t s, const lt_lane_record* rec, const double* prev_sum, int count, const double* ploty,
                                 const double* ploty2, int n_rows, int bh, int bw, int16_t* spans) {
-    const size_t lds = ((size_t)2 * bh + (size_t)2 * std::max(n_rows, 1)) * sizeof(int);
+    const size_t lds = lane_spans_lds(bh, n_rows);
     if (lds > 60 * 1024 || count < 1 || n_rows < 0) return false;
     LaneFromFit p;
     for (int k = 0; k < 6; ++k) p.prev_sum[k] = prev_sum ? prev_sum[k] : 0.0;

@@ -136,6 +136,13 @@ struct InplaceText {
     int first_char, n_glyphs, gw, gh, nl, len, slot_chars, y0, step;
 };
 struct InplaceRows { int a0, an, b0, bn; };
+// the lane and the text of a launch whose first slot lies `at` slots behind the first slot of l and t
+struct InplaceDraw { InplaceLane l; InplaceText t; };
+inline InplaceDraw advanced(InplaceLane l, InplaceText t, int at) {
+    l.spans += (size_t)at * l.span_stride_rows * 2;
+    if (t.nl > 0) { t.lines += (size_t)at * t.slot_chars; t.xpos += (size_t)at * t.slot_chars; }
+    return InplaceDraw{l, t};
+}
 // The inverse-warp tables of the calibration sets as the table-per-slot presentation kernels find them: entry `id` of the context's
 // table of overlay tables (device memory, written when lt_overlay_configure_set builds a set's tables: with nothing in flight).  The
 // sets of a launch's slots travel by value, as for the front end (CalIds).
@@ -195,6 +202,8 @@ int launch_overlay_lane(hipStream_t s, const uint8_t* frames, uint8_t* out, size
 // length that is no multiple of 4, or the runtime refused the argument block)
 constexpr int LT_SPAN_ARG_ROWS = 1104;
 void launch_store_word(hipStream_t s, unsigned* dev_word, unsigned value);
+// (averaged coefficients at the start of every slot's interval region -> intervals: does that form exist for this height and these plot rows?)
+bool lane_spans_from_regions_available(int bh, int n_rows);
 bool launch_lane_spans_from_regions(hipStream_t s, const double* ploty, const double* ploty2, int n_rows, int bh, int bw, int16_t* spans, int n);
 bool launch_lane_spans_from_fit(hipStream_t s, const lt_lane_record* rec, const double* prev_sum, int count, const double* ploty,
                                 const double* ploty2, int n_rows, int bh, int bw, int16_t* spans);

@@ -51,11 +51,7 @@ static void span_line(int16_t* spans, int bh, int xa, int ya, int xb, int yb) {
     const int len = tall ? ady : adx, across = tall ? adx : ady;
     int err = len - 2 * across;
     for (int i = 0, x = xa, y = ya; i <= len; ++i) {
-        if (y >= 0 && y < bh) {
-            const int16_t xc = (int16_t)std::min(std::max(x, -32768), 32767);
-            if (xc < spans[2 * y]) spans[2 * y] = xc;
-            if (xc > spans[2 * y + 1]) spans[2 * y + 1] = xc;
-        }
+        span_point(spans, bh, x, y);
         const bool turn = err < 0;
         err -= 2 * across;
         if (turn) err += 2 * len;
@@ -165,13 +161,16 @@ int lt_overlay_configure(lt_ctx* c, const double* Minv) { return lt_overlay_conf
 
 // A call is about to overwrite the page-locked staging regions of slots [first, first + n): if a copy out of those regions
 // may still be in flight (an earlier call of the same kind over the same slots), wait for it; then widen the busy range.
+static void widen_busy(lt_ctx::StagingBusy& b, int first, int n) {
+    if (b.hi <= b.lo) { b.lo = first; b.hi = first + n; }
+    else { b.lo = std::min(b.lo, first); b.hi = std::max(b.hi, first + n); }
+}
 static int staging_claim(lt_ctx::StagingBusy& b, int first, int n) {
     if (b.hi > b.lo && first < b.hi && first + n > b.lo && b.done) {
         HIP_TRY(hipEventSynchronize(b.done));
         b.lo = b.hi = 0;
     }
-    if (b.hi <= b.lo) { b.lo = first; b.hi = first + n; }
-    else { b.lo = std::min(b.lo, first); b.hi = std::max(b.hi, first + n); }
+    widen_busy(b, first, n);
     return LT_OK;
 }
 static int staging_mark(lt_ctx::StagingBusy& b, hipStream_t st) {
@@ -185,6 +184,7 @@ static int present_stream(lt_ctx* c) {
     return LT_OK;
 }
 static int ensure_strips(lt_ctx* c);
+static int ensure_spans(lt_ctx* c) { return c->d_spans ? (int)LT_OK : dev_alloc(&c->d_spans, (size_t)c->capacity * c->calib.warp_h * 2); }
 static int ensure_span_staging(lt_ctx* c) {
     const int bh = c->calib.warp_h;
     if (c->h_spans_cap >= c->capacity) return LT_OK;
@@ -205,8 +205,7 @@ int warm_presentation(lt_ctx* c, bool strips) {
     if (!c->have_overlay) return LT_OK;
     int rc = present_stream(c);
     if (rc) return rc;
-    const int bh = c->calib.warp_h;
-    if (!c->d_spans && (rc = dev_alloc(&c->d_spans, (size_t)c->capacity * bh * 2))) return rc;
+    if ((rc = ensure_spans(c))) return rc;
     if ((rc = ensure_span_staging(c))) return rc;
     if (strips) {
         if ((rc = ensure_strips(c))) return rc;
@@ -330,9 +329,6 @@ int lt_frame_tail(int warp_w, int warp_h, const double* in, const double* ploty_
     return LT_OK;
 }
 
-// lt_overlay_run; rows4: two runs of camera rows {a0, a1, b0, b1} outside which the annotated frames are not needed
-// (lt_present_frame, lt_overlay_run_rows), nullptr = all of them
-// strip mode: the rows the lane can reach (lt_overlay_rows) of every slot, packed, into the context's strip buffer
 static int ensure_strips(lt_ctx* c) {
     const size_t sb = (size_t)std::max(c->ov_r1 - c->ov_r0, 0) * c->calib.img_w * 3;
     if (c->d_strip && c->strip_bytes == sb) return LT_OK;
@@ -343,8 +339,6 @@ static int ensure_strips(lt_ctx* c) {
     return dev_alloc(&c->d_strip, (size_t)c->capacity * std::max<size_t>(sb, 4));
 }
 
-// direct_out (one frame, row runs): the device-visible address of a page-locked frame in HOST memory the kernel stores the drawn
-// rows into itself, instead of the context's annotated-frame buffer and a copy kernel behind it (lt_present_lane_async)
 // the plot rows (ploty, ploty ** 2 of get_poly_points) on the device: sent when they change (they depend on `partial` and the image
 // height only); waits for the whole context when they do
 static int ensure_ploty(lt_ctx* c, const double* ploty, const double* ploty2, int n_rows) {
@@ -365,13 +359,54 @@ static int ensure_ploty(lt_ctx* c, const double* ploty, const double* ploty2, in
     return LT_OK;
 }
 
-// averaged coefficients instead of points (lt_overlay_run_strip_coeffs): the device forms plot points and row intervals itself
+// ---- the steps every lane-drawing entry point is made of ---------------------------------------------------------------------------
+// lt_overlay_run* (annotated frames kept in the context), lt_overlay_run_inplace* (into the attached surfaces) and
+// lt_overlay_run_to_surfaces (into the caller's sinks) are sequences of these: the checks, the row intervals into page-locked staging
+// (the host's work, before the stream waits) and on to the device (behind the waits), the waits themselves, the close.
+
+// The lanes of n slots as the caller gave them: polygons (counts per slot, the (y, x) pairs of all slots back to back) or -- `ci` --
+// their averaged coefficients, from which the device forms plot points and row intervals itself (lt_overlay_run_strip_coeffs)
 struct CoeffInput { const double* coeffs; const uint8_t* draw; const double* ploty; const double* ploty2; int n_rows; };
+struct LaneInput { const int32_t *left_n, *right_n, *left_yx, *right_yx; const CoeffInput* ci; };
+
+static int check_lane_input(const LaneInput& in, int n) {
+    if (in.ci) return LT_OK;
+    if (!in.left_n || !in.right_n) return fail(LT_ERR_INVALID, "null point counts");
+    long long tl = 0, tr = 0;
+    for (int i = 0; i < n; ++i) {
+        if (in.left_n[i] < 0 || in.right_n[i] < 0) return fail(LT_ERR_INVALID, "negative point count");
+        tl += in.left_n[i];
+        tr += in.right_n[i];
+    }
+    return (tl && !in.left_yx) || (tr && !in.right_yx) ? fail(LT_ERR_INVALID, "null point list") : (int)LT_OK;
+}
+// the arguments of a coefficient entry point `who`, and whether that form exists for this context at all
+static int check_coeff_input(lt_ctx* c, const char* who, int n, const CoeffInput& ci) {
+    if (!c || (n > 0 && !ci.coeffs) || !ci.ploty || !ci.ploty2 || ci.n_rows < 1) return fail(LT_ERR_INVALID, "%s: bad arguments", who);
+    if (!lane_spans_from_regions_available(c->calib.warp_h, ci.n_rows)) return fail(LT_ERR_STATE, "%s: not available for this bird's-eye height", who);
+    return LT_OK;
+}
+// a context whose own calibration has no overlay serves only ranges with a slot of another set ...
+static int check_overlay_configured(const lt_ctx* c, const char* who, int first, int n) {
+    return c->have_overlay || first_foreign(c, first, n) >= 0 ? (int)LT_OK : fail(LT_ERR_STATE, "%s before lt_overlay_configure", who);
+}
+// ... and every slot is drawn with the inverse-warp table of its own calibration set
+static int check_overlay_sets(const lt_ctx* c, const char* who, int first, int n) {
+    for (int i = first; i < first + n; ++i)
+        if (!c->cal[(size_t)slot_set(c, i)].have_overlay)
+            return fail(LT_ERR_STATE, "%s before lt_overlay_configure: slot %d has calibration set %d, whose overlay is not configured", who, i, slot_set(c, i));
+    return LT_OK;
+}
+static int refuse_partial_frames(const lt_ctx* c, int first, int n) {
+    const int bad = first_partial(c->frame_full, first, n);
+    return bad < 0 ? (int)LT_OK
+                   : fail(LT_ERR_STATE, "slot %d holds only part of its camera frame (lt_upload_frame_rows without lt_upload_frame_rest): a whole-frame "
+                                        "overlay would show rows of the block's previous occupant", bad);
+}
 
 // What the overlay's kernels find in a piece's interval regions (hs: n regions of bh (lo, hi) pairs, page-locked staging or the
 // caller's): the polygons' row intervals, or -- coefficients form -- six doubles and a draw byte at the start of every region.
-static void fill_span_staging(int16_t* hs, int bh, int n, const int32_t* left_n, const int32_t* right_n, const int32_t* left_yx,
-                              const int32_t* right_yx, const CoeffInput* ci) {
+static void fill_span_staging(int16_t* hs, int bh, int n, const LaneInput& in) {
     // ~18 us of edge walking per polygon: a window's piece of 32 .. 128 polygons is shared among a few threads (the caller is
     // the one thread that feeds the device)
     const int workers = std::max(1, std::min({n / 8, 8, (int)std::thread::hardware_concurrency()}));
@@ -379,17 +414,17 @@ static void fill_span_staging(int16_t* hs, int bh, int n, const int32_t* left_n,
         size_t ol = 0, orr = 0;
         for (int i = 0; i < n; ++i) {
             if (i * (long long)workers / n == w)
-                lane_polygon_spans(hs + (size_t)i * bh * 2, bh, left_yx ? left_yx + 2 * ol : nullptr, left_n[i],
-                                   right_yx ? right_yx + 2 * orr : nullptr, right_n[i]);
-            ol += (size_t)left_n[i];
-            orr += (size_t)right_n[i];
+                lane_polygon_spans(hs + (size_t)i * bh * 2, bh, in.left_yx ? in.left_yx + 2 * ol : nullptr, in.left_n[i],
+                                   in.right_yx ? in.right_yx + 2 * orr : nullptr, in.right_n[i]);
+            ol += (size_t)in.left_n[i];
+            orr += (size_t)in.right_n[i];
         }
     };
-    if (ci) {                                  // six doubles and a draw byte at the start of every slot's interval region
+    if (in.ci) {                               // six doubles and a draw byte at the start of every slot's interval region
         for (int i = 0; i < n; ++i) {
             uint8_t* reg = reinterpret_cast<uint8_t*>(hs + (size_t)i * bh * 2);
-            std::memcpy(reg, ci->coeffs + (size_t)6 * i, 6 * sizeof(double));
-            reg[48] = ci->draw ? ci->draw[i] : 1;
+            std::memcpy(reg, in.ci->coeffs + (size_t)6 * i, 6 * sizeof(double));
+            reg[48] = in.ci->draw ? in.ci->draw[i] : 1;
         }
     } else if (workers == 1) some(0);
     else {
@@ -400,6 +435,78 @@ static void fill_span_staging(int16_t* hs, int bh, int n, const int32_t* left_n,
     }
 }
 
+// Row intervals, step 1 -- the host's work, before the presentation stream is made to wait for anything: the slots' page-locked
+// regions claimed from the copy that may still read them, and filled ...
+static int claim_span_staging(lt_ctx* c, int first, int n, int16_t** hs) {
+    int rc = staging_claim(c->spans_busy, first, n);
+    if (rc || (rc = ensure_span_staging(c))) return rc;
+    *hs = c->h_spans + (size_t)first * c->calib.warp_h * 2;
+    return LT_OK;
+}
+static int prepare_spans(lt_ctx* c, int first, int n, const LaneInput& in, int16_t** hs) {
+    int rc = ensure_spans(c);
+    if (rc || (in.ci && (rc = ensure_ploty(c, in.ci->ploty, in.ci->ploty2, in.ci->n_rows))) || (rc = claim_span_staging(c, first, n, hs))) return rc;
+    fill_span_staging(*hs, c->calib.warp_h, n, in);
+    return LT_OK;
+}
+// ... step 2, behind the waits: staging -> device, where the coefficient form (entry point `who`) turns the regions into intervals.
+// The staging stays claimed until the caller's kernel has run (close_draw).
+static int enqueue_spans(lt_ctx* c, hipStream_t ps, int first, int n, const int16_t* hs, const CoeffInput* ci, const char* who) {
+    const int bh = c->calib.warp_h;
+    int16_t* ds = c->d_spans + (size_t)first * bh * 2;
+    launch_copy_from_pinned(ps, ds, hs, (size_t)n * bh * 2 * sizeof(int16_t));
+    if (ci && !launch_lane_spans_from_regions(ps, c->d_ploty, c->d_ploty + ci->n_rows, ci->n_rows, bh, c->calib.warp_w, ds, n))
+        return fail(LT_ERR_STATE, "%s: not available for this bird's-eye height", who);
+    return LT_OK;
+}
+
+// What a stream `st` waits for before it reads or changes slots [first, first + n).  The rows of the camera frames the path does not
+// read come on the copy stream (lt_upload_frame_rest, lt_device_frames_rest): a draw is their reader.
+static int wait_rests(lt_ctx* c, hipStream_t st, int first, int n) {
+    if (!c->rest_pending) return LT_OK;
+    bool precise = true;
+    const int rc = wait_range(c->rests, st, first, first + n, &precise);
+    if (!rc && !precise) HIP_TRY(hipStreamWaitEvent(st, c->rest_done, 0));
+    return rc;
+}
+// the range's events, or -- the ring has overflowed, `all_known` is false -- the tails of the slots' streams
+static int wait_range_or_tails(lt_ctx* c, hipStream_t st, const lt_ctx::RangeEvents& r, int first, int n, bool all_known = true) {
+    bool precise = true;
+    const int rc = wait_range(r, st, first, first + n, &precise);
+    if (rc || (precise && all_known)) return rc;
+    return for_each_slice(c, first, n, [&](hipStream_t s, int, int) { return wait_tail(c, st, s); });
+}
+// Reading the slots' camera rows: behind the launches that wrote their masks (which waited for the rows' upload).
+static int wait_writers_or_tails(lt_ctx* c, hipStream_t st, int first, int n) { return wait_range_or_tails(c, st, c->writers, first, n); }
+// CHANGING the slots' attached surfaces: behind exactly the reads of their front end -- the undistortion of a slot's current frame was
+// noted among the readers when lt_mask_run enqueued it (behind the write of the slot's table entry, which the in-place kernels read
+// too).  A slot whose front end has not run since its attach has only that write in flight, which carries no event: the tails then.
+static int wait_front_readers(lt_ctx* c, hipStream_t st, int first, int n) {
+    bool front_ok = true;
+    for (int i = first; front_ok && i < first + n; ++i) front_ok = i < (int)c->front_ok.size() && c->front_ok[(size_t)i] != 0;
+    return wait_range_or_tails(c, st, c->readers, first, n, front_ok);
+}
+
+// The close of a draw enqueued on `ps`: the staging it read stays claimed until it has run, and it is a reader of the slots (their
+// camera rows or, in place, their table entries) -- the next upload or attach waits for it.
+static int close_draw(lt_ctx* c, hipStream_t ps, int first, int n, bool text) {
+    int rc = staging_mark(c->spans_busy, ps);
+    if (rc || (text && (rc = staging_mark(c->text_busy, ps)))) return rc;
+    return note_range(c->readers, ps, first, first + n);
+}
+// ... of one into the caller's device memory as well: what lt_overlay_store_wait waits for (the event exists before anything is staged)
+static int ensure_store_event(lt_ctx* c) {
+    return c->store_done || hipEventCreateWithFlags(&c->store_done, hipEventDisableTiming) == hipSuccess ? (int)LT_OK : fail(LT_ERR_HIP, "hipEventCreate failed");
+}
+static int close_store(lt_ctx* c, hipStream_t ps, int first, int n, bool text, int launches) {
+    const int rc = close_draw(c, ps, first, n, text);
+    if (rc) return rc;
+    HIP_TRY(hipEventRecord(c->store_done, ps));
+    c->store_pending = true;
+    c->last_overlay_launches = launches;
+    return LT_OK;
+}
+
 // the tables of a presentation launch over slots [first, first + n): per slot where the range mixes calibration sets
 static OvSets slot_tables(const lt_ctx* c, int first, int n) {
     for (int i = first + 1; i < first + n; ++i)
@@ -407,114 +514,83 @@ static OvSets slot_tables(const lt_ctx* c, int first, int n) {
     return OvSets{};
 }
 
-static int overlay_run_impl(lt_ctx* c, int first, int n, const int32_t* left_n, const int32_t* right_n, const int32_t* left_yx,
-                            const int32_t* right_yx, double alpha, const int* rows4, bool strip = false, uint8_t* direct_out = nullptr,
-                            bool* went_direct = nullptr, const CoeffInput* ci = nullptr) {
+// ---- annotated frames kept in the context: lt_overlay_run and its forms -----------------------------------------------------------
+// Where the frames go: whole frames, or (rows4) two runs of camera rows {a0, a1, b0, b1} outside which the annotated frames are not
+// needed (lt_present_frame, lt_overlay_run_rows), into the context's annotated-frame buffer; or (strip) the rows the lane can
+// reach (lt_overlay_rows) of every slot, packed, into the context's strip buffer.  direct_out (one frame, row runs): the
+// device-visible address of a page-locked frame in HOST memory the kernel stores the drawn rows into itself, instead of the
+// annotated-frame buffer and a copy kernel behind it (lt_present_lane_async); *went_direct: it did.
+struct HostDest { const int* rows4; bool strip; uint8_t* direct_out; bool* went_direct; };
+
+static int overlay_run_impl(lt_ctx* c, int first, int n, const LaneInput& in, double alpha, const HostDest& to = HostDest{}) {
+    static const char who[] = "lt_overlay_run";
+    const int* const rows4 = to.rows4; const bool strip = to.strip;
     int rc = check_slots(c, first, n);
     if (rc) return rc;
-    if (!c->have_overlay && first_foreign(c, first, n) < 0) return fail(LT_ERR_STATE, "lt_overlay_run before lt_overlay_configure");
+    if ((rc = check_overlay_configured(c, who, first, n))) return rc;
     if (strip && (rc = refuse_foreign(c, first, n, "a strip overlay"))) return rc;
-    for (int i = first; i < first + n; ++i)           // every slot is drawn with the inverse-warp table of its own calibration set
-        if (!c->cal[(size_t)slot_set(c, i)].have_overlay)
-            return fail(LT_ERR_STATE, "lt_overlay_run before lt_overlay_configure: slot %d has calibration set %d, whose overlay is not configured", i, slot_set(c, i));
+    if ((rc = check_overlay_sets(c, who, first, n))) return rc;
     if (n == 0) return LT_OK;
-    if (!ci) {
-        if (!left_n || !right_n) return fail(LT_ERR_INVALID, "null point counts");
-        long long tl = 0, tr = 0;
-        for (int i = 0; i < n; ++i) {
-            if (left_n[i] < 0 || right_n[i] < 0) return fail(LT_ERR_INVALID, "negative point count");
-            tl += left_n[i];
-            tr += right_n[i];
-        }
-        if ((tl && !left_yx) || (tr && !right_yx)) return fail(LT_ERR_INVALID, "null point list");
-    }
-    if (!rows4 && !strip) {
-        const int bad = first_partial(c->frame_full, first, n);
-        if (bad >= 0)
-            return fail(LT_ERR_STATE, "slot %d holds only part of its camera frame (lt_upload_frame_rows without lt_upload_frame_rest): a whole-frame "
-                                      "overlay would show rows of the block's previous occupant", bad);
-    }
+    if ((rc = check_lane_input(in, n))) return rc;
+    if (!rows4 && !strip && (rc = refuse_partial_frames(c, first, n))) return rc;
     if ((rc = set_device(c))) return rc;
     const int bh = c->calib.warp_h;
-    if (!c->d_spans && (rc = dev_alloc(&c->d_spans, (size_t)c->capacity * bh * 2))) return rc;
+    if ((rc = ensure_spans(c))) return rc;
     if (strip) {
         if ((rc = ensure_strips(c))) return rc;
     } else if (!c->d_annot && (rc = dev_alloc(&c->d_annot, (size_t)c->capacity * c->frame_bytes))) return rc;
     // One frame (process()): the intervals travel as a kernel argument -- no staging buffer, no copy launch, no events
     static const bool arg_ok = [] { const char* e = LT_EXP_ENV("LT_SPANS_ARG"); return !(e && e[0] == '0'); }();
-    bool one = arg_ok && !strip && !ci && n == 1 && bh <= LT_SPAN_ARG_ROWS && (c->calib.img_w & 3) == 0;
-    if (ci && (rc = ensure_ploty(c, ci->ploty, ci->ploty2, ci->n_rows))) return rc;
+    const bool one = arg_ok && !strip && !in.ci && n == 1 && bh <= LT_SPAN_ARG_ROWS && (c->calib.img_w & 3) == 0;
     int16_t one_spans[2 * LT_SPAN_ARG_ROWS];
-    auto claim_staging = [&]() -> int {
-        int r = staging_claim(c->spans_busy, first, n);
-        if (r) return r;
-        if ((r = ensure_span_staging(c))) return r;
-        return (int)LT_OK;
-    };
-    if (!one && (rc = claim_staging())) return rc;
-    int16_t* hs = one ? one_spans : c->h_spans + (size_t)first * bh * 2;
+    int16_t* hs = one_spans;
     static const bool timing = LT_EXP_ENV("LT_OVERLAY_TIMING") != nullptr;
     const auto t0 = std::chrono::steady_clock::now();
-    fill_span_staging(hs, bh, n, left_n, right_n, left_yx, right_yx, ci);
-    // the rows of the frame the path does not read came on the copy stream (lt_upload_frame_rest): the overlay is their reader
+    if (one) fill_span_staging(hs, bh, 1, in);
+    else if ((rc = prepare_spans(c, first, n, in, &hs))) return rc;
     const auto t1 = std::chrono::steady_clock::now();
     if ((rc = present_stream(c))) return rc;
     hipStream_t ps = c->present;
-    if (c->rest_pending) {
-        bool precise = true;
-        if ((rc = wait_range(c->rests, ps, first, first + n, &precise))) return rc;
-        if (!precise) HIP_TRY(hipStreamWaitEvent(ps, c->rest_done, 0));
-    }
-    {   // the camera rows of these slots: behind the launches that wrote their masks (which waited for the rows' upload)
-        bool precise = true;
-        if ((rc = wait_range(c->writers, ps, first, first + n, &precise))) return rc;
-        if (!precise && (rc = for_each_slice(c, first, n, [&](hipStream_t st, int, int) { return wait_tail(c, ps, st); }))) return rc;
-    }
+    if ((rc = wait_rests(c, ps, first, n))) return rc;
+    if ((rc = wait_writers_or_tails(c, ps, first, n))) return rc;
     // an asynchronous download may still be reading the annotated frames this call overwrites
     if (c->annot_busy.hi > c->annot_busy.lo && first < c->annot_busy.hi && first + n > c->annot_busy.lo && c->annot_busy.done)
         HIP_TRY(hipStreamWaitEvent(ps, c->annot_busy.done, 0));
     if (one) {
-        uint8_t* dst = direct_out ? direct_out : c->d_annot + (size_t)first * c->frame_bytes;
+        uint8_t* dst = to.direct_out ? to.direct_out : c->d_annot + (size_t)first * c->frame_bytes;
         const lt_ctx::CalSet& q = c->cal[(size_t)slot_set(c, first)];
-        if (launch_overlay_lane_one(ps, slot_frame(c, first), dst,
-                                    q.d_oxy, q.d_ofrac, hs, c->calib.img_h, c->calib.img_w, bh, c->calib.warp_w, (float)alpha, rows4)) {
+        if (launch_overlay_lane_one(ps, slot_frame(c, first), dst, q.d_oxy, q.d_ofrac, hs, c->calib.img_h, c->calib.img_w, bh, c->calib.warp_w, (float)alpha, rows4)) {
             HIP_TRY(hipGetLastError());
             c->last_overlay_launches = 1;
-            if (went_direct) *went_direct = direct_out != nullptr;
-            if (!direct_out) mark_annot(c, first, n, rows4 ? 0 : 1);
+            if (to.went_direct) *to.went_direct = to.direct_out != nullptr;
+            if (!to.direct_out) mark_annot(c, first, n, rows4 ? 0 : 1);
             return note_range(c->readers, ps, first, first + n);
         }
         // not launched (the runtime refused the argument block): the staged way after all, with the intervals already built
-        one = false;
-        if ((rc = claim_staging())) return rc;
-        std::memcpy(c->h_spans + (size_t)first * bh * 2, one_spans, (size_t)bh * 2 * sizeof(int16_t));
-        hs = c->h_spans + (size_t)first * bh * 2;
+        if ((rc = claim_span_staging(c, first, n, &hs))) return rc;
+        std::memcpy(hs, one_spans, (size_t)bh * 2 * sizeof(int16_t));
     }
-    launch_copy_from_pinned(ps, c->d_spans + (size_t)first * bh * 2, hs, (size_t)n * bh * 2 * sizeof(int16_t));
-    if (ci && !launch_lane_spans_from_regions(ps, c->d_ploty, c->d_ploty + ci->n_rows, ci->n_rows, bh, c->calib.warp_w, c->d_spans + (size_t)first * bh * 2, n))
-        return fail(LT_ERR_STATE, "lt_overlay_run_strip_coeffs: not available for this bird's-eye height");
+    if ((rc = enqueue_spans(c, ps, first, n, hs, in.ci, "lt_overlay_run_strip_coeffs"))) return rc;
     const auto t2 = std::chrono::steady_clock::now();
+    const int16_t* ds = c->d_spans + (size_t)first * bh * 2;
     int launches = 0;
     if (strip) {
-        if (!launch_overlay_lane_strip(ps, slot_frame(c, first), c->frame_bytes, c->d_strip + (size_t)first * c->strip_bytes,
-                                       c->strip_bytes, c->d_oxy, c->d_ofrac, c->d_spans + (size_t)first * bh * 2, (size_t)bh, c->calib.img_w,
-                                       c->ov_r0, c->ov_r1, bh, c->calib.warp_w, (float)alpha, n))
+        if (!launch_overlay_lane_strip(ps, slot_frame(c, first), c->frame_bytes, c->d_strip + (size_t)first * c->strip_bytes, c->strip_bytes, c->d_oxy,
+                                       c->d_ofrac, ds, (size_t)bh, c->calib.img_w, c->ov_r0, c->ov_r1, bh, c->calib.warp_w, (float)alpha, n))
             return fail(LT_ERR_STATE, "strip overlay needs a frame width that is a multiple of 4");
     } else {
         // one set in the range: its tables, today's kernels; several: every slot with the tables of its own set (CalIds::N slots per
         // launch) -- a pixel outside its own set's lane rows has lane value 0, so whole frames and the caller's row runs serve all
         const lt_ctx::CalSet& q = c->cal[(size_t)slot_set(c, first)];
-        launches = launch_overlay_lane(ps, slot_frame(c, first), c->d_annot + (size_t)first * c->frame_bytes,
-                                       c->frame_bytes, q.d_oxy, q.d_ofrac, c->d_spans + (size_t)first * bh * 2, (size_t)bh,
-                                       c->calib.img_h, c->calib.img_w, bh, c->calib.warp_w, (float)alpha, n, rows4, slot_tables(c, first, n));
+        launches = launch_overlay_lane(ps, slot_frame(c, first), c->d_annot + (size_t)first * c->frame_bytes, c->frame_bytes, q.d_oxy, q.d_ofrac, ds,
+                                       (size_t)bh, c->calib.img_h, c->calib.img_w, bh, c->calib.warp_w, (float)alpha, n, rows4, slot_tables(c, first, n));
     }
     HIP_TRY(hipGetLastError());
-    if (!strip) {
+    if (!strip) {                 // (strips leave the annotated frames and the launch count as they are)
         mark_annot(c, first, n, rows4 ? 0 : 1);
         c->last_overlay_launches = launches;
     }
-    if ((rc = staging_mark(c->spans_busy, ps))) return rc;
-    rc = note_range(c->readers, ps, first, first + n);
+    rc = close_draw(c, ps, first, n, false);
     if (timing) {
         const auto t3 = std::chrono::steady_clock::now();
         auto us = [](auto a, auto b) { return (long)std::chrono::duration_cast<std::chrono::microseconds>(b - a).count(); };
@@ -525,7 +601,7 @@ static int overlay_run_impl(lt_ctx* c, int first, int n, const int32_t* left_n, 
 
 int lt_overlay_run(lt_ctx* c, int first, int n, const int32_t* left_n, const int32_t* right_n, const int32_t* left_yx,
                    const int32_t* right_yx, double alpha) {
-    return overlay_run_impl(c, first, n, left_n, right_n, left_yx, right_yx, alpha, nullptr);
+    return overlay_run_impl(c, first, n, LaneInput{left_n, right_n, left_yx, right_yx, nullptr}, alpha);
 }
 
 static int ordered_rows(lt_ctx* c, const int32_t* rows4, int r[4]) {
@@ -537,17 +613,18 @@ static int ordered_rows(lt_ctx* c, const int32_t* rows4, int r[4]) {
 
 int lt_overlay_run_rows(lt_ctx* c, int first, int n, const int32_t* left_n, const int32_t* right_n, const int32_t* left_yx,
                         const int32_t* right_yx, double alpha, const int32_t* rows4) {
-    if (!rows4) return overlay_run_impl(c, first, n, left_n, right_n, left_yx, right_yx, alpha, nullptr);
+    const LaneInput in{left_n, right_n, left_yx, right_yx, nullptr};
+    if (!rows4) return overlay_run_impl(c, first, n, in, alpha);
     if (!c) return fail(LT_ERR_INVALID, "null context");
     int r[4];
     const int rc = ordered_rows(c, rows4, r);
     if (rc) return rc;
-    return overlay_run_impl(c, first, n, left_n, right_n, left_yx, right_yx, alpha, r);
+    return overlay_run_impl(c, first, n, in, alpha, HostDest{r});
 }
 
 int lt_overlay_run_strip(lt_ctx* c, int first, int n, const int32_t* left_n, const int32_t* right_n, const int32_t* left_yx,
                          const int32_t* right_yx, double alpha) {
-    return overlay_run_impl(c, first, n, left_n, right_n, left_yx, right_yx, alpha, nullptr, true);
+    return overlay_run_impl(c, first, n, LaneInput{left_n, right_n, left_yx, right_yx, nullptr}, alpha, HostDest{nullptr, true});
 }
 
 // lt_overlay_run_strip from the lanes' AVERAGED coefficients (n x 6 doubles: left a, b, c, right a, b, c) instead of their plot points:
@@ -556,12 +633,10 @@ int lt_overlay_run_strip(lt_ctx* c, int first, int n, const int32_t* left_n, con
 // draw: n bytes, 0 = no lane in that frame (plain copy); nullptr: all drawn.
 int lt_overlay_run_strip_coeffs(lt_ctx* c, int first, int n, const double* coeffs, const uint8_t* draw, const double* ploty, const double* ploty2,
                                 int n_rows, double alpha) {
-    if (!c || (n > 0 && !coeffs) || !ploty || !ploty2 || n_rows < 1) return fail(LT_ERR_INVALID, "lt_overlay_run_strip_coeffs: bad arguments");
-    const int bh = c->calib.warp_h;
-    if ((bh & 1) || bh * 4 < 56 || ((size_t)2 * bh + (size_t)2 * n_rows) * sizeof(int) > 60 * 1024)
-        return fail(LT_ERR_STATE, "lt_overlay_run_strip_coeffs: not available for this bird's-eye height");
     const CoeffInput ci{coeffs, draw, ploty, ploty2, n_rows};
-    return overlay_run_impl(c, first, n, nullptr, nullptr, nullptr, nullptr, alpha, nullptr, true, nullptr, nullptr, &ci);
+    const int rc = check_coeff_input(c, "lt_overlay_run_strip_coeffs", n, ci);
+    if (rc) return rc;
+    return overlay_run_impl(c, first, n, LaneInput{nullptr, nullptr, nullptr, nullptr, &ci}, alpha, HostDest{nullptr, true});
 }
 
 // The strips of slots [first, first + n) on their way into the caller's frames: one contiguous copy per block of STRIP_BLOCK slots
@@ -608,8 +683,7 @@ int lt_strip_download_async(lt_ctx* c, int first, int n, uint8_t* out, size_t ou
             host_unreserve(group);           // the scatter pieces are queued: the group now waits for those
         });
     }
-    if (c->annot_busy.hi <= c->annot_busy.lo) { c->annot_busy.lo = first; c->annot_busy.hi = first + n; }
-    else { c->annot_busy.lo = std::min(c->annot_busy.lo, first); c->annot_busy.hi = std::max(c->annot_busy.hi, first + n); }
+    widen_busy(c->annot_busy, first, n);
     return staging_mark(c->annot_busy, c->dl);
 }
 
@@ -736,12 +810,39 @@ int lt_overlay_text(lt_ctx* c, int first, int n, const char* lines, int n_lines,
     return staging_mark(c->text_busy, c->present);
 }
 
+// ---- lane and text in one pass: into the attached surfaces, or on the way into the caller's sinks ---------------------------------
+// the text of such a draw (entry point `who`): checked ...
+static bool has_text(const lt_inplace_text* text) { return text && text->n_lines > 0 && text->line_len > 0; }
+static int check_text(const lt_ctx* c, const char* who, const lt_inplace_text* text) {
+    if (!has_text(text)) return LT_OK;
+    if (!c->font_glyphs) return fail(LT_ERR_STATE, "%s with text before lt_overlay_set_font", who);
+    if (!text->lines) return fail(LT_ERR_INVALID, "null text");
+    if (text->step < c->font_gh) return fail(LT_ERR_INVALID, "text lines %d rows apart would overlap (the glyphs are %d rows high)", text->step, c->font_gh);
+    return LT_OK;
+}
+// ... and staged -> what the kernels take (*t untouched, nl == 0: no text).  To the device whatever n: every pixel of the text's rows
+// searches the positions.
+static int stage_inplace_text(lt_ctx* c, int first, int n, const lt_inplace_text* text, InplaceText* t) {
+    if (!has_text(text)) return LT_OK;
+    const uint8_t* kl = nullptr;
+    const int16_t* kx = nullptr;
+    size_t stride = 0;
+    const int rc = stage_text(c, first, n, text->lines, text->n_lines, text->line_len, text->x0, &kl, &kx, &stride, false);
+    if (rc) return rc;
+    *t = InplaceText{c->d_atlas, c->d_advance, kl, kx, c->font_first, c->font_glyphs, c->font_gw, c->font_gh, text->n_lines, text->line_len,
+                     (int)stride, text->y0, text->step};
+    return LT_OK;
+}
+
 // ---- lane and text drawn into the attached surfaces themselves (k_inplace.hip) ---------------------------------------------------
 // The third destination of annotated frames, beside the host and a device sink: the camera surfaces the caller attached.  Only the
 // rows a lane can reach and the text's rows are visited, and only what changes is stored.  Everything is checked before anything
 // is allocated, staged or launched: a refused call leaves the context and the surfaces as they were.
-static int inplace_impl(lt_ctx* c, int first, int n, const int32_t* left_n, const int32_t* right_n, const int32_t* left_yx,
-                        const int32_t* right_yx, const CoeffInput* ci, double alpha, const lt_inplace_text* text, const int32_t* rgb2yuv) {
+// Beside the shared steps: every slot must be attached (the context's own overlay is not asked for: a slot's set decides), packed
+// 4:2:2 is refused, the draw waits for the surfaces' READERS -- those of the range and of every other slot attached to one of its
+// surfaces -- and all of them are detached behind it.
+static int inplace_impl(lt_ctx* c, int first, int n, const LaneInput& in, double alpha, const lt_inplace_text* text, const int32_t* rgb2yuv) {
+    static const char who[] = "lt_overlay_run_inplace";
     int rc = check_slots(c, first, n);
     if (rc) return rc;
     if (c->in_layout == LT_INPUT_YUY2 || c->in_layout == LT_INPUT_UYVY)
@@ -749,67 +850,26 @@ static int inplace_impl(lt_ctx* c, int first, int n, const int32_t* left_n, cons
     for (int i = first; i < first + n; ++i)
         if (i >= (int)c->attached.size() || !c->attached[(size_t)i])
             return fail(LT_ERR_STATE, "lt_overlay_run_inplace: slot %d has no device frame attached (in place means the surface the slot reads)", i);
-    for (int i = first; i < first + n; ++i)
-        if (!c->cal[(size_t)slot_set(c, i)].have_overlay)
-            return fail(LT_ERR_STATE, "lt_overlay_run_inplace before lt_overlay_configure: slot %d has calibration set %d, whose overlay is not configured", i, slot_set(c, i));
-    if (!ci) {
-        if (n > 0 && (!left_n || !right_n)) return fail(LT_ERR_INVALID, "null point counts");
-        long long tl = 0, tr = 0;
-        for (int i = 0; i < n; ++i) {
-            if (left_n[i] < 0 || right_n[i] < 0) return fail(LT_ERR_INVALID, "negative point count");
-            tl += left_n[i];
-            tr += right_n[i];
-        }
-        if ((tl && !left_yx) || (tr && !right_yx)) return fail(LT_ERR_INVALID, "null point list");
-    }
+    if ((rc = check_overlay_sets(c, who, first, n))) return rc;
+    if (n > 0 && (rc = check_lane_input(in, n))) return rc;
     if (c->in_layout != LT_INPUT_RGB) {
         if (!rgb2yuv) return fail(LT_ERR_INVALID, "drawing into a 4:2:0 surface needs the eight RGB -> YUV coefficients");
         if (!sa::coeffs_ok(rgb2yuv))
             return fail(LT_ERR_INVALID, "conversion coefficients must be below 2^23 in magnitude and keep every row's sum inside 32 bits");
     }
-    const bool have_text = text && text->n_lines > 0 && text->line_len > 0;
-    if (have_text) {
-        if (!c->font_glyphs) return fail(LT_ERR_STATE, "lt_overlay_run_inplace with text before lt_overlay_set_font");
-        if (!text->lines) return fail(LT_ERR_INVALID, "null text");
-        if (text->step < c->font_gh) return fail(LT_ERR_INVALID, "text lines %d rows apart would overlap (the glyphs are %d rows high)", text->step, c->font_gh);
-    }
+    if ((rc = check_text(c, who, text))) return rc;
     if (n == 0) return LT_OK;
     if ((rc = set_device(c))) return rc;
-    const int bh = c->calib.warp_h, H = c->calib.img_h, W = c->calib.img_w;
-    if (!c->d_spans && (rc = dev_alloc(&c->d_spans, (size_t)c->capacity * bh * 2))) return rc;
-    if (ci && (rc = ensure_ploty(c, ci->ploty, ci->ploty2, ci->n_rows))) return rc;
-    if (!c->store_done && hipEventCreateWithFlags(&c->store_done, hipEventDisableTiming) != hipSuccess) return fail(LT_ERR_HIP, "hipEventCreate failed");
-    if ((rc = staging_claim(c->spans_busy, first, n))) return rc;
-    if ((rc = ensure_span_staging(c))) return rc;
-    int16_t* hs = c->h_spans + (size_t)first * bh * 2;
-    fill_span_staging(hs, bh, n, left_n, right_n, left_yx, right_yx, ci);
+    if ((rc = ensure_store_event(c))) return rc;
+    int16_t* hs = nullptr;
+    if ((rc = prepare_spans(c, first, n, in, &hs))) return rc;
     if ((rc = present_stream(c))) return rc;
     hipStream_t ps = c->present;
     InplaceText t{};
-    if (have_text) {
-        const uint8_t* kl = nullptr;
-        const int16_t* kx = nullptr;
-        size_t stride = 0;
-        // (to the device whatever n: every pixel of the text's rows searches the positions)
-        if ((rc = stage_text(c, first, n, text->lines, text->n_lines, text->line_len, text->x0, &kl, &kx, &stride, false))) return rc;
-        t = InplaceText{c->d_atlas, c->d_advance, kl, kx, c->font_first, c->font_glyphs, c->font_gw, c->font_gh, text->n_lines, text->line_len,
-                        (int)stride, text->y0, text->step};
-    }
-    // The draw changes bytes the front end of these slots reads: it waits for exactly those reads -- the undistortion of a slot's
-    // current frame was noted among the readers when lt_mask_run enqueued it (behind the write of the slot's table entry, which
-    // the kernels here read too).  A slot whose front end has not run since its attach has only that write in flight, which
-    // carries no event: the tails of the slots' streams then.
-    {
-        bool precise = true;
-        if ((rc = wait_range(c->readers, ps, first, first + n, &precise))) return rc;
-        for (int i = first; precise && i < first + n; ++i) precise = i < (int)c->front_ok.size() && c->front_ok[(size_t)i] != 0;
-        if (!precise && (rc = for_each_slice(c, first, n, [&](hipStream_t st, int, int) { return wait_tail(c, ps, st); }))) return rc;
-        if (c->rest_pending) {          // lt_device_frames_rest reads the surfaces on the copy stream
-            bool p2 = true;
-            if ((rc = wait_range(c->rests, ps, first, first + n, &p2))) return rc;
-            if (!p2) HIP_TRY(hipStreamWaitEvent(ps, c->rest_done, 0));
-        }
-    }
+    if ((rc = stage_inplace_text(c, first, n, text, &t))) return rc;
+    // The draw changes bytes the front end of these slots reads, and lt_device_frames_rest reads the surfaces on the copy stream
+    if ((rc = wait_front_readers(c, ps, first, n))) return rc;
+    if ((rc = wait_rests(c, ps, first, n))) return rc;
     // Slots outside the range that are attached to one of these surfaces as well (a group's second try attaches a stream's frame to
     // a spare slot): their front end reads the bytes the draw changes, so the draw waits for them too, and they are detached with
     // the range below -- no slot stays attached to a surface that holds no camera frame any more.
@@ -822,146 +882,82 @@ static int inplace_impl(lt_ctx* c, int first, int n, const int32_t* left_n, cons
             if (c->attached[(size_t)s] && (s < first || s >= first + n) &&
                 std::binary_search(drawn_planes.begin(), drawn_planes.end(), c->surf[(size_t)s].plane[0]))
                 aliases.push_back(s);
-        for (int s : aliases) {
-            bool precise = true;
-            if ((rc = wait_range(c->readers, ps, s, s + 1, &precise))) return rc;
-            precise = precise && s < (int)c->front_ok.size() && c->front_ok[(size_t)s] != 0;
-            if (!precise && (rc = for_each_slice(c, s, 1, [&](hipStream_t st, int, int) { return wait_tail(c, ps, st); }))) return rc;
-        }
+        for (int s : aliases)
+            if ((rc = wait_front_readers(c, ps, s, 1))) return rc;
     }
-    launch_copy_from_pinned(ps, c->d_spans + (size_t)first * bh * 2, hs, (size_t)n * bh * 2 * sizeof(int16_t));
-    if (ci && !launch_lane_spans_from_regions(ps, c->d_ploty, c->d_ploty + ci->n_rows, ci->n_rows, bh, c->calib.warp_w, c->d_spans + (size_t)first * bh * 2, n))
-        return fail(LT_ERR_STATE, "lt_overlay_run_inplace_coeffs: not available for this bird's-eye height");
+    if ((rc = enqueue_spans(c, ps, first, n, hs, in.ci, "lt_overlay_run_inplace_coeffs"))) return rc;
     // One set in the range: its tables and its lane rows, today's kernels.  Several: every slot with the tables of its own set over
     // the union of the sets' lane rows (a pixel outside its own set's rows has lane value 0 and stores nothing), CalIds::N per launch.
-    int launches;
-    {
-        const OvSets per_slot = slot_tables(c, first, n);
-        const lt_ctx::CalSet& q = c->cal[(size_t)slot_set(c, first)];
-        const int t0 = have_text ? text->y0 : 0, t1 = have_text ? text->y0 + (text->n_lines - 1) * text->step + c->font_gh : 0;
-        const int rows4[4] = {t0, t1, per_slot.sets ? c->ov_r0 : q.ov_r0, per_slot.sets ? c->ov_r1 : q.ov_r1};
-        InplaceLane l{q.d_oxy, q.d_ofrac, c->d_spans + (size_t)first * bh * 2, (size_t)bh, bh, c->calib.warp_w, (float)alpha};
-        launches = launch_inplace(ps, c->in_layout, c->d_surf + first, &c->surf[(size_t)first], n, H, W, rows4, l, t, yuv_coef_of(c), rgb2yuv, per_slot);
-    }
+    const int bh = c->calib.warp_h;
+    const OvSets per_slot = slot_tables(c, first, n);
+    const lt_ctx::CalSet& q = c->cal[(size_t)slot_set(c, first)];
+    const int rows4[4] = {t.nl ? t.y0 : 0, t.nl ? t.y0 + (t.nl - 1) * t.step + t.gh : 0, per_slot.sets ? c->ov_r0 : q.ov_r0, per_slot.sets ? c->ov_r1 : q.ov_r1};
+    const InplaceLane l{q.d_oxy, q.d_ofrac, c->d_spans + (size_t)first * bh * 2, (size_t)bh, bh, c->calib.warp_w, (float)alpha};
+    const int launches = launch_inplace(ps, c->in_layout, c->d_surf + first, &c->surf[(size_t)first], n, c->calib.img_h, c->calib.img_w, rows4, l, t,
+                                        yuv_coef_of(c), rgb2yuv, per_slot);
     HIP_TRY(hipGetLastError());
-    if ((rc = staging_mark(c->spans_busy, ps))) return rc;
-    if (have_text && (rc = staging_mark(c->text_busy, ps))) return rc;
-    if ((rc = note_range(c->readers, ps, first, first + n))) return rc;       // it reads the slots' table entries: the next attach waits
-    HIP_TRY(hipEventRecord(c->store_done, ps));
-    c->store_pending = true;
-    c->last_overlay_launches = launches;
+    if ((rc = close_store(c, ps, first, n, t.nl > 0, launches))) return rc;       // (it reads the slots' table entries: the next attach waits)
     // The surfaces no longer hold camera frames: the slots are detached -- nothing of the library reads them again, and a later
     // sink is not refused for overlapping them -- and marked, so that a front end over them is refused until new frames come.
     if (c->drawn.size() < (size_t)c->capacity) c->drawn.resize((size_t)c->capacity, 0);
-    for (int i = first; i < first + n; ++i) {
-        c->attached[(size_t)i] = 0;
-        c->drawn[(size_t)i] = 1;
-    }
-    for (int s : aliases) {
-        c->attached[(size_t)s] = 0;
-        c->drawn[(size_t)s] = 1;
-    }
+    for (int i = first; i < first + n; ++i) aliases.push_back(i);
+    for (int s : aliases) { c->attached[(size_t)s] = 0; c->drawn[(size_t)s] = 1; }
     return LT_OK;
 }
 
 int lt_overlay_run_inplace(lt_ctx* c, int first, int n, const int32_t* left_n, const int32_t* right_n, const int32_t* left_yx,
                            const int32_t* right_yx, double alpha, const lt_inplace_text* text, const int32_t* rgb2yuv) {
-    return inplace_impl(c, first, n, left_n, right_n, left_yx, right_yx, nullptr, alpha, text, rgb2yuv);
+    return inplace_impl(c, first, n, LaneInput{left_n, right_n, left_yx, right_yx, nullptr}, alpha, text, rgb2yuv);
 }
 
 int lt_overlay_run_inplace_coeffs(lt_ctx* c, int first, int n, const double* coeffs, const uint8_t* draw, const double* ploty,
                                   const double* ploty2, int n_rows, double alpha, const lt_inplace_text* text, const int32_t* rgb2yuv) {
-    if (!c || (n > 0 && !coeffs) || !ploty || !ploty2 || n_rows < 1) return fail(LT_ERR_INVALID, "lt_overlay_run_inplace_coeffs: bad arguments");
-    const int bh = c->calib.warp_h;
-    if ((bh & 1) || bh * 4 < 56 || ((size_t)2 * bh + (size_t)2 * n_rows) * sizeof(int) > 60 * 1024)
-        return fail(LT_ERR_STATE, "lt_overlay_run_inplace_coeffs: not available for this bird's-eye height");
     const CoeffInput ci{coeffs, draw, ploty, ploty2, n_rows};
-    return inplace_impl(c, first, n, nullptr, nullptr, nullptr, nullptr, &ci, alpha, text, rgb2yuv);
+    const int rc = check_coeff_input(c, "lt_overlay_run_inplace_coeffs", n, ci);
+    if (rc) return rc;
+    return inplace_impl(c, first, n, LaneInput{nullptr, nullptr, nullptr, nullptr, &ci}, alpha, text, rgb2yuv);
 }
 
 // ---- lane and text drawn on the way into the caller's surfaces (k_draw_sink.hip) ---------------------------------------------------
 // lt_overlay_run + lt_overlay_text + lt_overlay_store_device in one pass and one launch per SurfChunk::N slots, whatever the slots'
 // calibration sets: no annotated frame is kept (lt_download_overlay / lt_overlay_store_device over these slots see what was there
 // before).  Everything is checked before anything is allocated, staged or launched.
+// Beside the shared steps: the sink's format is checked before an empty range returns, its surfaces once the device is set; the
+// draw reads the slots' camera frames, so it waits as lt_overlay_run does.
 int lt_overlay_run_to_surfaces(lt_ctx* c, int first, int n, const int32_t* left_n, const int32_t* right_n, const int32_t* left_yx,
                                const int32_t* right_yx, double alpha, const lt_inplace_text* text, const lt_device_surface* dst, int layout,
                                const int32_t* coeffs) {
+    static const char who[] = "lt_overlay_run_to_surfaces";
+    const LaneInput in{left_n, right_n, left_yx, right_yx, nullptr};
     int rc = check_slots(c, first, n);
     if (rc) return rc;
-    if (!c->have_overlay && first_foreign(c, first, n) < 0) return fail(LT_ERR_STATE, "lt_overlay_run_to_surfaces before lt_overlay_configure");
-    for (int i = first; i < first + n; ++i)
-        if (!c->cal[(size_t)slot_set(c, i)].have_overlay)
-            return fail(LT_ERR_STATE, "lt_overlay_run_to_surfaces before lt_overlay_configure: slot %d has calibration set %d, whose overlay is not configured", i, slot_set(c, i));
+    if ((rc = check_overlay_configured(c, who, first, n))) return rc;
+    if ((rc = check_overlay_sets(c, who, first, n))) return rc;
     const int bh = c->calib.warp_h, H = c->calib.img_h, W = c->calib.img_w;
     if ((rc = check_sink_format(layout, H, W, coeffs))) return rc;
     if (n == 0) return LT_OK;
-    if (!left_n || !right_n) return fail(LT_ERR_INVALID, "null point counts");
-    {
-        long long tl = 0, tr = 0;
-        for (int i = 0; i < n; ++i) {
-            if (left_n[i] < 0 || right_n[i] < 0) return fail(LT_ERR_INVALID, "negative point count");
-            tl += left_n[i];
-            tr += right_n[i];
-        }
-        if ((tl && !left_yx) || (tr && !right_yx)) return fail(LT_ERR_INVALID, "null point list");
-    }
+    if ((rc = check_lane_input(in, n))) return rc;
     if (!dst) return fail(LT_ERR_INVALID, "null surfaces");
-    const bool have_text = text && text->n_lines > 0 && text->line_len > 0;
-    if (have_text) {
-        if (!c->font_glyphs) return fail(LT_ERR_STATE, "lt_overlay_run_to_surfaces with text before lt_overlay_set_font");
-        if (!text->lines) return fail(LT_ERR_INVALID, "null text");
-        if (text->step < c->font_gh) return fail(LT_ERR_INVALID, "text lines %d rows apart would overlap (the glyphs are %d rows high)", text->step, c->font_gh);
-    }
-    {
-        const int bad = first_partial(c->frame_full, first, n);
-        if (bad >= 0)
-            return fail(LT_ERR_STATE, "slot %d holds only part of its camera frame (lt_upload_frame_rows without lt_upload_frame_rest): a whole-frame "
-                                      "overlay would show rows of the block's previous occupant", bad);
-    }
+    if ((rc = check_text(c, who, text))) return rc;
+    if ((rc = refuse_partial_frames(c, first, n))) return rc;
     if ((rc = set_device(c))) return rc;
     std::vector<SurfEntry> ent;
     if ((rc = check_ctx_sinks(c, dst, n, layout, ent))) return rc;
-    if (!c->d_spans && (rc = dev_alloc(&c->d_spans, (size_t)c->capacity * bh * 2))) return rc;
-    if (!c->store_done && hipEventCreateWithFlags(&c->store_done, hipEventDisableTiming) != hipSuccess) return fail(LT_ERR_HIP, "hipEventCreate failed");
-    if ((rc = staging_claim(c->spans_busy, first, n))) return rc;
-    if ((rc = ensure_span_staging(c))) return rc;
-    int16_t* hs = c->h_spans + (size_t)first * bh * 2;
-    fill_span_staging(hs, bh, n, left_n, right_n, left_yx, right_yx, nullptr);
+    if ((rc = ensure_store_event(c))) return rc;
+    int16_t* hs = nullptr;
+    if ((rc = prepare_spans(c, first, n, in, &hs))) return rc;
     if ((rc = present_stream(c))) return rc;
     hipStream_t ps = c->present;
     InplaceText t{};
-    if (have_text) {
-        const uint8_t* kl = nullptr;
-        const int16_t* kx = nullptr;
-        size_t stride = 0;
-        // (to the device whatever n: every pixel of the text's rows searches the positions)
-        if ((rc = stage_text(c, first, n, text->lines, text->n_lines, text->line_len, text->x0, &kl, &kx, &stride, false))) return rc;
-        t = InplaceText{c->d_atlas, c->d_advance, kl, kx, c->font_first, c->font_glyphs, c->font_gw, c->font_gh, text->n_lines, text->line_len,
-                        (int)stride, text->y0, text->step};
-    }
-    // as lt_overlay_run: behind the copies of the rows the path does not read, and behind the launches that wrote the slots' masks
-    if (c->rest_pending) {
-        bool precise = true;
-        if ((rc = wait_range(c->rests, ps, first, first + n, &precise))) return rc;
-        if (!precise) HIP_TRY(hipStreamWaitEvent(ps, c->rest_done, 0));
-    }
-    {
-        bool precise = true;
-        if ((rc = wait_range(c->writers, ps, first, first + n, &precise))) return rc;
-        if (!precise && (rc = for_each_slice(c, first, n, [&](hipStream_t st, int, int) { return wait_tail(c, ps, st); }))) return rc;
-    }
-    launch_copy_from_pinned(ps, c->d_spans + (size_t)first * bh * 2, hs, (size_t)n * bh * 2 * sizeof(int16_t));
-    InplaceLane l{nullptr, nullptr, c->d_spans + (size_t)first * bh * 2, (size_t)bh, bh, c->calib.warp_w, (float)alpha};
+    if ((rc = stage_inplace_text(c, first, n, text, &t))) return rc;
+    if ((rc = wait_rests(c, ps, first, n))) return rc;
+    if ((rc = wait_writers_or_tails(c, ps, first, n))) return rc;
+    if ((rc = enqueue_spans(c, ps, first, n, hs, nullptr, who))) return rc;
+    const InplaceLane l{nullptr, nullptr, c->d_spans + (size_t)first * bh * 2, (size_t)bh, bh, c->calib.warp_w, (float)alpha};
     const int launches = launch_draw_to_surfaces(ps, layout, slot_frame(c, first), c->frame_bytes, H, W, ent.data(), n, c->d_ov,
                                                  &c->slot_cal[(size_t)first], l, t, c->ov_r0, c->ov_r1, coeffs);
     HIP_TRY(hipGetLastError());
-    if ((rc = staging_mark(c->spans_busy, ps))) return rc;
-    if (have_text && (rc = staging_mark(c->text_busy, ps))) return rc;
-    if ((rc = note_range(c->readers, ps, first, first + n))) return rc;
-    HIP_TRY(hipEventRecord(c->store_done, ps));
-    c->store_pending = true;
-    c->last_overlay_launches = launches;
-    return LT_OK;
+    return close_store(c, ps, first, n, t.nl > 0, launches);
 }
 
 int lt_download_overlay(lt_ctx* c, int first, int n, uint8_t* out) {
@@ -1009,9 +1005,8 @@ static int present_rows(lt_ctx* c, const int32_t* rows4, bool text, int n_lines,
     const int H = c->calib.img_h;
     r[0] = 0; r[1] = H; r[2] = H; r[3] = H;
     if (!rows4) return split ? fail(LT_ERR_INVALID, "two row runs are needed") : (int)LT_OK;
-    for (int k = 0; k < 4; ++k) r[k] = rows4[k];
-    if (!(0 <= r[0] && r[0] <= r[1] && r[1] <= r[2] && r[2] <= r[3] && r[3] <= H))
-        return fail(LT_ERR_INVALID, "row runs must be ordered and inside the frame");
+    const int rc = ordered_rows(c, rows4, r);
+    if (rc) return rc;
     auto within = [&](int lo, int hi, int a, int b) { lo = std::max(lo, 0); hi = std::min(hi, H); return lo >= hi || (a <= lo && hi <= b); };
     const int t0 = y0, t1 = y0 + (n_lines - 1) * step + c->font_gh;
     if (split) {
@@ -1037,7 +1032,7 @@ int lt_present_frame(lt_ctx* c, int slot, const int32_t* left_n, const int32_t* 
     const bool text = lines && n_lines > 0 && line_len > 0 && c->font_glyphs > 0;
     int r[4];
     if ((rc = present_rows(c, rows4, text, n_lines, y0, step, left_n[0] > 0 || right_n[0] > 0, false, r))) return rc;
-    if ((rc = overlay_run_impl(c, slot, 1, left_n, right_n, left_yx, right_yx, alpha, rows4 ? r : nullptr))) return rc;
+    if ((rc = overlay_run_impl(c, slot, 1, LaneInput{left_n, right_n, left_yx, right_yx, nullptr}, alpha, HostDest{rows4 ? r : nullptr}))) return rc;
     if (text && (rc = lt_overlay_text(c, slot, 1, lines, n_lines, line_len, x0, y0, step))) return rc;
     if ((rc = present_copy_rows(c, slot, out, r[0], r[1]))) return rc;
     if ((rc = present_copy_rows(c, slot, out, r[2], r[3]))) return rc;
@@ -1064,15 +1059,16 @@ int lt_present_lane_async(lt_ctx* c, int slot, const int32_t* left_n, const int3
     // overlay kernel stores what it draws into the page-locked frame itself -- one launch instead of two, the rows cross the bus as
     // they are drawn (-13 us per frame of process(); LT_OVERLAY_DIRECT=0: draw into the context's buffer, then the copy kernel).
     static const bool direct_ok = [] { const char* e = LT_EXP_ENV("LT_OVERLAY_DIRECT"); return !(e && e[0] == '0'); }();
+    const LaneInput in{left_n, right_n, left_yx, right_yx, nullptr};
     void* dev = nullptr;
     bool direct = false;
     if (direct_ok && r[1] <= r[0] && ((uintptr_t)out & 15) == 0 && hipHostGetDevicePointer(&dev, out, 0) == hipSuccess && dev) {
-        if ((rc = overlay_run_impl(c, slot, 1, left_n, right_n, left_yx, right_yx, alpha, r, false, static_cast<uint8_t*>(dev), &direct))) return rc;
+        if ((rc = overlay_run_impl(c, slot, 1, in, alpha, HostDest{r, false, static_cast<uint8_t*>(dev), &direct}))) return rc;
         if (direct) return LT_OK;
         return present_copy_rows(c, slot, out, r[2], r[3]);      // (the staged path ran: the rows are in the context's buffer)
     }
     (void)hipGetLastError();
-    if ((rc = overlay_run_impl(c, slot, 1, left_n, right_n, left_yx, right_yx, alpha, r))) return rc;
+    if ((rc = overlay_run_impl(c, slot, 1, in, alpha, HostDest{r}))) return rc;
     return present_copy_rows(c, slot, out, r[2], r[3]);
 }
 
@@ -1100,15 +1096,11 @@ int lt_present_lane_from_fit_async(lt_ctx* c, int slot, const double* prev_sum, 
         return fail(LT_ERR_STATE, "lt_present_lane_from_fit_async: needs the lane's run alone and a page-locked, 16-byte aligned frame");
     }
     const int bh = c->calib.warp_h;
-    if (!c->d_spans && (rc = dev_alloc(&c->d_spans, (size_t)c->capacity * bh * 2))) return rc;
+    if ((rc = ensure_spans(c))) return rc;
     if ((rc = ensure_ploty(c, ploty, ploty2, n_rows))) return rc;
     return for_each_slice(c, slot, 1, [&](hipStream_t st, int f0, int) {
-        if (c->rest_pending) {       // rows of the frame the mask chain's upload did not bring (lt_upload_frame_rest): the overlay reads them
-            bool precise = true;
-            int wrc = wait_range(c->rests, st, f0, f0 + 1, &precise);
-            if (wrc) return wrc;
-            if (!precise) HIP_TRY(hipStreamWaitEvent(st, c->rest_done, 0));
-        }
+        const int wrc = wait_rests(c, st, f0, 1);
+        if (wrc) return wrc;
         int16_t* sp = c->d_spans + (size_t)f0 * bh * 2;
         if (!launch_lane_spans_from_fit(st, slot_rec(c, f0), prev_sum, count, c->d_ploty, c->d_ploty + n_rows, n_rows, bh, c->calib.warp_w, sp))
             return fail(LT_ERR_STATE, "lt_present_lane_from_fit_async: too many rows for one workgroup's LDS");
@@ -1292,8 +1284,7 @@ static int download_overlay_async_impl(lt_ctx* c, int first, int n, uint8_t* out
         if (ta) c->dl_event_pool.push_back(ta);
         if (tb) c->dl_event_pool.push_back(tb);
     }
-    if (c->annot_busy.hi <= c->annot_busy.lo) { c->annot_busy.lo = first; c->annot_busy.hi = first + n; }
-    else { c->annot_busy.lo = std::min(c->annot_busy.lo, first); c->annot_busy.hi = std::max(c->annot_busy.hi, first + n); }
+    widen_busy(c->annot_busy, first, n);
     return staging_mark(c->annot_busy, c->dl);
 }
 
