@@ -166,7 +166,8 @@ int  lt_reserve(lt_ctx* ctx, int capacity);
  * window of a stream).  sws / band: the search parameters to size the result buffers for (either may be NULL); annotate: 0 = no
  * presentation stage, 1 = whole annotated frames (lt_overlay_run), 2 = strips (lt_overlay_run_strip); needs lt_overlay_configure
  * for 1 and 2; + 4: the staging ring of lt_search_viz_run, + 8: that of lt_split_panes_run as well.  Optional: every entry point
- * still sets up what it finds missing. */
+ * still sets up what it finds missing.  LT_ERR_INVALID for search parameters the search calls themselves refuse (the size limits
+ * at lt_sws_fit_run). */
 int  lt_warm(lt_ctx* ctx, const lt_search_params* sws, const lt_search_params* band, int annotate);
 int  lt_get_info(lt_ctx* ctx, lt_info* out);
 int  lt_sync(lt_ctx* ctx);
@@ -365,6 +366,14 @@ int  lt_mask_rerun(lt_ctx* ctx, int first_slot, int n, const lt_filter_params* p
 /* filter_lane_points() only, on bird's-eye RGB images already uploaded with lt_upload_bev (:183-240) */
 int  lt_upload_bev(lt_ctx* ctx, const uint8_t* bev_rgb, int first_slot, int n);
 int  lt_filter_run(lt_ctx* ctx, int first_slot, int n, const lt_filter_params* p);
+/* The fit of every search below (and of lt_fit_poly2): integer moments, moved exactly to the pixels' own mean row, 3 x 3 Cholesky in
+ * f64 -- within the BASELINE tolerance (1e-4 relative) of exact rational least squares for a dash of three adjacent rows at the image's
+ * edge as for a full-height lane of 16384 rows (sum dy^4 is kept in 128 bits).  fit_flags bit 0 / 1: the left / right lane has
+ * fewer than 3 distinct rows, its coefficients are 0.
+ * Size limits, refused with LT_ERR_INVALID before anything is launched: a search that only the first-formulation kernels take
+ * keeps its row counters in LDS, 150 KB at most -- a band search with bandwidth > 31 (a band wider than 64 columns), a width that
+ * is no multiple of 4 or more than 4795 band rows, and any band search on an image taller than 8192 rows: at most 9590 image rows;
+ * a sliding-window search outside k_sws_fit2's geometry: 16 * window_height + 8 * width bytes. */
 /* sliding_window_search() + fit_poly() (:242-447, :502-509) on the slots' masks */
 int  lt_sws_fit_run(lt_ctx* ctx, int first_slot, int n, const lt_search_params* p);
 /* band_search() + fit_poly() (:449-509); prev_coeffs: n * 6 doubles (last_left_coeffs, last_right_coeffs) */
@@ -449,7 +458,9 @@ int  lt_morph_ellipse(lt_ctx* ctx, const uint8_t* img, int h, int w, int k, int 
 int  lt_resize_linear_u8(lt_ctx* ctx, const uint8_t* img, int h, int w, int channels, int dh, int dw, uint8_t* out);
 
 /* LaneTracker.fit_poly() on explicit pixel lists (np.polyfit(ys, xs, 2), :506-507): n (y,x) pairs with
- * coordinates in [0, 65535].  *rank_deficient is set when fewer than 3 distinct y exist (coef = 0). */
+ * coordinates in [0, 65535], for any h, w >= 1: they only name the point the moments are taken about, (h / 2, w / 2) kept inside
+ * [0, 65535]; the sums that can pass 64 bits are kept in 128, so any list an int counts is solved.  *rank_deficient is set when
+ * fewer than 3 distinct y exist (coef = 0). */
 int  lt_fit_poly2(lt_ctx* ctx, const int32_t* ys, const int32_t* xs, int n, int h, int w, double coef[3],
                   int* rank_deficient);
 

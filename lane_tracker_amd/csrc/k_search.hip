@@ -5,7 +5,8 @@
 //
 // Column histograms are LDS atomics, the first/last-argmax of the box-filtered histogram and the
 // per-row stream compaction are wavefront ballots/shuffles (64 lanes), and the 2nd-degree fit is a
-// per-lane 3x3 normal-equations solve on exact int64 moments taken about the image centre.
+// per-lane 3x3 normal-equations solve on exact integer moments, accumulated about the image centre and moved to
+// the pixels' own mean row before the solve (solve_poly2).
 // Lane pixels are emitted in the reference's order (level-major, then row-major inside a window;
 // row-major for the band search) as packed (y << 16) | x.
 #include <algorithm>
@@ -49,16 +50,22 @@ __device__ __forceinline__ unsigned wave_inclusive_sum_dpp(unsigned v) {
     return v;
 }
 
-// sum of a 64-bit value over the wave (wave-uniform result, two's complement): three limbs of 22/22/20
-// bits, so that each limb's 64-lane sum fits 32 bits and can use the DPP scan
-__device__ __forceinline__ long long wave_sum_i64(long long v) {
-    const unsigned long long u = (unsigned long long)v;
+// sum of an unsigned 64-bit value over the wave (wave-uniform result): three limbs of 22/22/20 bits, so that each limb's 64-lane
+// sum fits 32 bits and can use the DPP scan.  Returns the low word of the total, its bits 64 and up in hi.
+__device__ __forceinline__ unsigned long long wave_sum_u64_wide(unsigned long long u, unsigned long long& hi) {
     const unsigned s0 = wave_inclusive_sum_dpp((unsigned)(u & 0x3fffffu));
     const unsigned s1 = wave_inclusive_sum_dpp((unsigned)((u >> 22) & 0x3fffffu));
     const unsigned s2 = wave_inclusive_sum_dpp((unsigned)(u >> 44));
     const unsigned long long t0 = (unsigned)__builtin_amdgcn_readlane((int)s0, 63), t1 = (unsigned)__builtin_amdgcn_readlane((int)s1, 63),
                              t2 = (unsigned)__builtin_amdgcn_readlane((int)s2, 63);
-    return (long long)(t0 + (t1 << 22) + (t2 << 44));
+    const unsigned long long low = t0 + (t1 << 22), top = t2 << 44, sum = low + top;   // t2 < 2^26: t2 << 44 is a 70-bit number
+    hi = (t2 >> 20) + (sum < top ? 1u : 0u);
+    return sum;
+}
+// ... of a signed value whose total fits 64 bits (two's complement: the low word is the total)
+__device__ __forceinline__ long long wave_sum_i64(long long v) {
+    unsigned long long ignored;
+    return (long long)wave_sum_u64_wide((unsigned long long)v, ignored);
 }
 __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
 #pragma unroll
@@ -76,33 +83,73 @@ __device__ __forceinline__ int wave_max_i32(int v) {
     return v;
 }
 
-// Moments of the lane pixels about (y0, x0), exact in int64:
+// Moments of the lane pixels about (y0, x0), exact integers:
 //   m[0..4] = sum (y-y0)^k, k = 0..4 ;  m[5..7] = sum (x-x0) (y-y0)^k, k = 0..2
+// Sums are taken modulo 2^64 (two's complement), so only the TOTALS have to fit: with w <= 4096 and h <= 16384 every one does
+// (|m[3]| <= 2^62 with every pixel of one half of the image set) except m[4] = sum dy^4, which passes 2^63 for a full-height lane
+// 20 pixels wide at h = 8192.  m4h holds its bits 64 and up.  The closed-form row moments of the *2 kernels and k_band_chain3
+// (h <= 8192, at most 64 pixels per row, at most 64 rows per thread) stay below 2^60 per thread and leave m4h alone: their
+// m[4] only grows past 64 bits in the reduction over the threads.
 struct Moments {
     long long m[8];
+    unsigned long long m4h;
     __device__ void clear() {
 #pragma unroll
         for (int i = 0; i < 8; ++i) m[i] = 0;
+        m4h = 0;
     }
     __device__ void add(int y, int x, int y0, int x0) {
         const long long dy = y - y0, dx = x - x0, dy2 = dy * dy;
-        m[0] += 1; m[1] += dy; m[2] += dy2; m[3] += dy2 * dy; m[4] += dy2 * dy2;
+        const unsigned long long dy4 = (unsigned long long)dy2 * (unsigned long long)dy2, lo = (unsigned long long)m[4] + dy4;
+        m[0] += 1; m[1] += dy; m[2] += dy2; m[3] += dy2 * dy; m[4] = (long long)lo; m4h += lo < dy4 ? 1u : 0u;
         m[5] += dx; m[6] += dx * dy; m[7] += dx * dy2;
     }
 };
 
+// The eight moments as the solve takes them: the three that can pass 64 bits in some caller (m3, m4 and m7 in k_fit_list, whose
+// rows go to 65535 and whose list may hold 2^31 pixels; m4 alone in the searches) as 128-bit integers.
+struct WideMoments {
+    long long m0, m1, m2, m5, m6;
+    __int128 m3, m4, m7;
+};
+__device__ __forceinline__ double i128_to_double(__int128 v) {
+    const bool neg = v < 0;
+    const unsigned __int128 u = neg ? (unsigned __int128)0 - (unsigned __int128)v : (unsigned __int128)v;
+    const double d = (double)(unsigned long long)(u >> 64) * 18446744073709551616.0 + (double)(unsigned long long)u;
+    return neg ? -d : d;
+}
+
 // Least-squares parabola x = a y^2 + b y + c from the centred moments (np.polyfit(y, x, 2)).
-// The normal equations are solved in f64 on variables scaled to O(1); returns false when the
-// system is rank deficient (fewer than 3 distinct y), which the host then handles like NumPy.
-__device__ bool solve_poly2(const long long* m, int distinct_rows, double y0, double x0, double sy, double* out) {
+// The moments arrive about the image centre; a short dash at the top or bottom edge lies hundreds of rows from it, and the
+// normal equations about the centre then cancel to a few digits.  So the moments are first moved, in exact integer arithmetic,
+// to the data's own mean row t (rounded: any integer does, the shift is exact), and the rows are scaled by the power of two next
+// to their standard deviation (exact as well).  The 3x3 system is then O(1) and as well conditioned as the rows allow; it is
+// solved in f64 by Cholesky.  Returns false when the system is rank deficient (fewer than 3 distinct y), which the host then
+// handles like NumPy.
+__device__ bool solve_poly2(const WideMoments& w, int distinct_rows, double y0, double x0, double* out) {
     out[0] = out[1] = out[2] = 0.0;
-    if (m[0] <= 0) return false;
+    if (w.m0 <= 0) return false;
     if (distinct_rows < 3) return false;
-    const double is = 1.0 / sy, is2 = is * is, is3 = is2 * is, is4 = is2 * is2;
-    // u = (y - y0)/sy ; x' = x - x0 ;  [S4 S3 S2; S3 S2 S1; S2 S1 S0] [A B C]' = [T2 T1 T0]'
-    const double S0 = (double)m[0], S1 = (double)m[1] * is, S2 = (double)m[2] * is2, S3 = (double)m[3] * is3,
-                 S4 = (double)m[4] * is4;
-    const double T0 = (double)m[5], T1 = (double)m[6] * is, T2 = (double)m[7] * is2;
+    // sum (dy - t)^k by Horner in t; every product below stays inside 128 bits (|t| < 2^16, m0 < 2^31, m4 < 2^95)
+    const long long t = (long long)rint((double)w.m1 / (double)w.m0);
+    // (64-bit steps wrap like the sums themselves: only their results have to fit)
+    auto less = [](long long a, long long f, long long b) { return (long long)((unsigned long long)a - (unsigned long long)f * (unsigned long long)b); };
+    const long long n1 = less(w.m1, t, w.m0);                                     // sum d
+    const long long n2 = less(w.m2, t, w.m1 + n1);                                // sum d^2 = m2 - 2 t m1 + t^2 m0
+    const __int128 b3 = 3 * (__int128)w.m2 - (__int128)t * (3 * w.m1 - t * w.m0);
+    const __int128 n3 = w.m3 - t * b3;                                            // m3 - 3 t m2 + 3 t^2 m1 - t^3 m0
+    const __int128 d4 = 6 * (__int128)w.m2 - (__int128)t * (4 * w.m1 - t * w.m0);
+    const __int128 n4 = w.m4 - t * (4 * w.m3 - t * d4);                           // m4 - 4 t m3 + 6 t^2 m2 - 4 t^3 m1 + t^4 m0
+    const long long n6 = less(w.m6, t, w.m5);                                        // sum dx d
+    const __int128 n7 = w.m7 - (__int128)t * ((__int128)w.m6 + n6);               // sum dx d^2 = m7 - 2 t m6 + t^2 m5
+    if (n2 <= 0) return false;
+    // u = (y - y0 - t) / 2^k with 4^k next to the rows' variance n2 / m0
+    const int k = (ilogb((double)n2) - ilogb((double)w.m0)) >> 1;
+    const double is = scalbn(1.0, -k), is2 = is * is, is3 = is2 * is, is4 = is2 * is2;
+    // x' = x - x0 ;  [S4 S3 S2; S3 S2 S1; S2 S1 S0] [A B C]' = [T2 T1 T0]'
+    const double S0 = (double)w.m0, S1 = (double)n1 * is, S2 = (double)n2 * is2, S3 = i128_to_double(n3) * is3,
+                 S4 = i128_to_double(n4) * is4;
+    const double T0 = (double)w.m5, T1 = (double)n6 * is, T2 = i128_to_double(n7) * is2;
     // symmetric positive definite: Cholesky  G = L L'
     const double l00 = sqrt(S4);
     if (!(l00 > 0.0)) return false;
@@ -116,12 +163,20 @@ __device__ bool solve_poly2(const long long* m, int distinct_rows, double y0, do
     const double l22 = sqrt(d2);
     const double z0 = T2 / l00, z1 = (T1 - l10 * z0) / l11, z2 = (T0 - l20 * z0 - l21 * z1) / l22;
     const double C = z2 / l22, B = (z1 - l21 * C) / l11, A = (z0 - l10 * B - l20 * C) / l00;
-    // x - x0 = A u^2 + B u + C with u = (y - y0)/sy
-    const double a = A * is2, b = B * is;
+    // x - x0 = A u^2 + B u + C with u = (y - yc) / 2^k, yc = y0 + t
+    const double a = A * is2, b = B * is, yc = y0 + (double)t;
     out[0] = a;
-    out[1] = b - 2.0 * a * y0;
-    out[2] = a * y0 * y0 - b * y0 + C + x0;
+    out[1] = b - 2.0 * a * yc;
+    out[2] = a * yc * yc - b * yc + C + x0;
     return true;
+}
+// the searches' form: eight 64-bit totals and m[4]'s high word
+__device__ bool solve_poly2(const long long* m, unsigned long long m4h, int distinct_rows, double y0, double x0, double* out) {
+    WideMoments w;
+    w.m0 = m[0]; w.m1 = m[1]; w.m2 = m[2]; w.m5 = m[5]; w.m6 = m[6];
+    w.m3 = m[3]; w.m7 = m[7];
+    w.m4 = (__int128)(((unsigned __int128)m4h << 64) | (unsigned long long)m[4]);
+    return solve_poly2(w, distinct_rows, y0, x0, out);
 }
 
 // exclusive prefix of an LDS int array of n entries into out[0..n] (out[n] = total), by wave 0
@@ -368,27 +423,41 @@ __device__ void extract_windows(const uint8_t* mask, int w, int r0, int r1, cons
 
 // carry (LDS, 8 doubles, optional): the six coefficients of this fit and, in [6], 1.0 when the next frame of a chained band
 // search may build on them (both lanes found, both fits regular) -- k_band_chain2
+// WIDE: the threads' m4h words count (per-pixel accumulation, k_sws_fit and k_band_fit); else they are zero and left out
+template <bool WIDE = false>
 __device__ void reduce_and_fit(Moments* mom, const int* distinct, long long* s_mom, int h, int w, int n_left,
                                int n_right, bool detected, int mode, lt_lane_record* rec, int pix_format = 0,
                                double* carry = nullptr) {
     // block-reduce the per-thread moments: wave shuffle, then LDS atomics
+    __shared__ unsigned long long s_m4h[2];      // bits 64 and up of the two m[4] totals
     for (int i = threadIdx.x; i < 16; i += NT) s_mom[i] = 0;
+    if (threadIdx.x < 2) s_m4h[threadIdx.x] = 0;
     __syncthreads();
-    for (int s = 0; s < 2; ++s)
+    for (int s = 0; s < 2; ++s) {
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
+            if (k == 4) continue;
             const long long v = wave_sum_i64(mom[s].m[k]);
             if (lane_id() == 0 && v != 0) atomicAdd(reinterpret_cast<unsigned long long*>(&s_mom[s * 8 + k]), (unsigned long long)v);
         }
+        unsigned long long hi;
+        const unsigned long long lo = wave_sum_u64_wide((unsigned long long)mom[s].m[4], hi);
+        if (WIDE) hi += (unsigned long long)wave_sum_i64((long long)mom[s].m4h);
+        if (lane_id() == 0) {
+            const unsigned long long before = atomicAdd(reinterpret_cast<unsigned long long*>(&s_mom[s * 8 + 4]), lo);
+            hi += before + lo < lo ? 1u : 0u;        // the carry out of the low word
+            if (hi) atomicAdd(&s_m4h[s], hi);
+        }
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
         lt_lane_record r;
-        const double y0 = (double)(h / 2), x0 = (double)(w / 2), sy = (double)(h > 1 ? h : 2) * 0.5;
+        const double y0 = (double)(h / 2), x0 = (double)(w / 2);
         unsigned flags = 0;
         for (int k = 0; k < 3; ++k) r.left_coeffs[k] = r.right_coeffs[k] = 0.0;
         if (detected) {
-            if (!solve_poly2(s_mom, distinct[0], y0, x0, sy, r.left_coeffs)) flags |= 1u;
-            if (!solve_poly2(s_mom + 8, distinct[1], y0, x0, sy, r.right_coeffs)) flags |= 2u;
+            if (!solve_poly2(s_mom, s_m4h[0], distinct[0], y0, x0, r.left_coeffs)) flags |= 1u;
+            if (!solve_poly2(s_mom + 8, s_m4h[1], distinct[1], y0, x0, r.right_coeffs)) flags |= 2u;
         }
         r.n_left = n_left;
         r.n_right = n_right;
@@ -518,7 +587,7 @@ __global__ __launch_bounds__(NT) void k_sws_fit(const uint8_t* __restrict__ mask
         cent[g.maxlev + 2] = ncent[1];
     }
     const bool detected = nroi[0] > 0 && nroi[1] > 0 && n_out[0] > 0 && n_out[1] > 0;   // :432-447
-    reduce_and_fit(mom, distinct, s_mom, g.h, g.w, n_out[0], n_out[1], detected, 0, recs + frame);
+    reduce_and_fit<true>(mom, distinct, s_mom, g.h, g.w, n_out[0], n_out[1], detected, 0, recs + frame);
 }
 
 // ===================================================================================================
@@ -1062,7 +1131,7 @@ __global__ __launch_bounds__(NT) void k_band_fit(const uint8_t* __restrict__ mas
     const int nl = (int)rowoff[nrows], nr = (int)rowoff[(g.h + 1) + nrows];
     const bool detected = nl != 0 && nr != 0;                        // :491
     __syncthreads();
-    reduce_and_fit(mom, distinct, s_mom, g.h, g.w, nl, nr, detected, 1, recs + frame);
+    reduce_and_fit<true>(mom, distinct, s_mom, g.h, g.w, nl, nr, detected, 1, recs + frame);
 }
 
 // k_band_fit2: the band search with the same row-mask scheme as k_sws_fit2.  Every (side, row) has a column
@@ -1300,6 +1369,7 @@ __global__ __launch_bounds__(CT) void k_band_chain3(MaskBits mb, SearchGeom g, c
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     long long* part = reinterpret_cast<long long*>(smem);                  // [C3_VALUES][CT]
     __shared__ long long s_tot[C3_VALUES];
+    __shared__ unsigned long long s_tot4h[2];                              // bits 64 and up of the two m[4] totals
     __shared__ double carry[8], pc[6], s_fit[6];
     __shared__ int s_stop, s_ok[2];
     const int lane = lane_id(), wv = threadIdx.x >> 6;
@@ -1389,6 +1459,12 @@ __global__ __launch_bounds__(CT) void k_band_chain3(MaskBits mb, SearchGeom g, c
             long long acc = 0;
 #pragma unroll
             for (int i = 0; i < CT / 64; ++i) acc += part[v * CT + i * 64 + lane];
+            if (v == 4 || v == 13) {   // m[4]: at most 2^62 per lane here (32 rows per thread, 64 pixels per row, |dy| <= 4096), wider in total
+                unsigned long long hi;
+                const unsigned long long lo = wave_sum_u64_wide((unsigned long long)acc, hi);
+                if (lane == 0) { s_tot[v] = (long long)lo; s_tot4h[v == 13] = hi; }
+                continue;
+            }
             const long long tot = wave_sum_i64(acc);
             if (lane == 0) s_tot[v] = tot;
         }
@@ -1397,10 +1473,10 @@ __global__ __launch_bounds__(CT) void k_band_chain3(MaskBits mb, SearchGeom g, c
         const int nl = (int)(unsigned)(s_tot[8] & 0xffffffffll), nr = (int)(unsigned)(s_tot[17] & 0xffffffffll);
         const bool detected = nl != 0 && nr != 0;                            // :491
         if (lane == 0 && wv < 2) {
-            const double y0 = (double)(g.h / 2), x0 = (double)(g.w / 2), sy = (double)(g.h > 1 ? g.h : 2) * 0.5;
+            const double y0 = (double)(g.h / 2), x0 = (double)(g.w / 2);
             double c[3] = {0.0, 0.0, 0.0};
             bool ok = true;
-            if (detected && !(ablate & 8)) ok = solve_poly2(s_tot + wv * 9, (int)(s_tot[wv * 9 + 8] >> 32), y0, x0, sy, c);
+            if (detected && !(ablate & 8)) ok = solve_poly2(s_tot + wv * 9, s_tot4h[wv], (int)(s_tot[wv * 9 + 8] >> 32), y0, x0, c);
             if (ablate & 8) { c[0] = pc[wv * 3]; c[1] = pc[wv * 3 + 1]; c[2] = pc[wv * 3 + 2]; }
             s_fit[wv * 3] = c[0]; s_fit[wv * 3 + 1] = c[1]; s_fit[wv * 3 + 2] = c[2];
             s_ok[wv] = ok ? 1 : 0;
@@ -1441,32 +1517,42 @@ __global__ __launch_bounds__(CT) void k_band_chain3(MaskBits mb, SearchGeom g, c
     }
 }
 
-// fit_poly() on an explicit pixel list: moments by all threads, one Cholesky solve
+// fit_poly() on an explicit pixel list: moments by all threads, one Cholesky solve.  Rows and columns go to 65535 whatever h and
+// w are, and the list may be long: sum dy^3, sum dy^4 and sum dx dy^2 are kept in 128 bits per thread (a thread's other sums fit
+// 64 bits for any list an int counts), and thread 0 adds the 256 partial sums of each.
 __global__ __launch_bounds__(NT) void k_fit_list(const uint32_t* __restrict__ pix, int n, int h, int w,
                                                 double* __restrict__ out4) {
     __shared__ long long s_mom[8];
+    __shared__ __int128 s_wide[3][NT];
     __shared__ int s_ymin, s_ymax, s_mid;
     if (threadIdx.x < 8) s_mom[threadIdx.x] = 0;
     if (threadIdx.x == 0) { s_ymin = 0x7fffffff; s_ymax = -1; s_mid = 0; }
     __syncthreads();
-    Moments m;
-    m.clear();
+    long long m0 = 0, m1 = 0, m2 = 0, m5 = 0, m6 = 0;
+    __int128 m3 = 0, m4 = 0, m7 = 0;
+    // the point the sums are taken about: the image centre, kept inside the coordinate range so that |dy|, |dx| <= 65535 whatever
+    // h and w say (the solve moves the moments to the pixels' mean row anyway, and the column offset is added back exactly)
+    const int y0 = min(h / 2, 65535), x0 = min(w / 2, 65535);
     int ymin = 0x7fffffff, ymax = -1;
     for (int i = threadIdx.x; i < n; i += NT) {
         const uint32_t p = pix[i];
         const int y = (int)(p >> 16), x = (int)(p & 0xffffu);
-        m.add(y, x, h / 2, w / 2);
+        const long long dy = y - y0, dx = x - x0, dy2 = dy * dy;      // |dy|, |dx| <= 65535
+        m0 += 1; m1 += dy; m2 += dy2; m3 += dy2 * dy; m4 += (unsigned long long)dy2 * (unsigned long long)dy2;
+        m5 += dx; m6 += dx * dy; m7 += dx * dy2;
         ymin = min(ymin, y);
         ymax = max(ymax, y);
     }
     ymin = wave_min_i32(ymin);
     ymax = wave_max_i32(ymax);
     if (lane_id() == 0) { atomicMin(&s_ymin, ymin); atomicMax(&s_ymax, ymax); }
+    const long long narrow[5] = {m0, m1, m2, m5, m6};
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        const long long v = wave_sum_i64(m.m[k]);
+    for (int k = 0; k < 5; ++k) {
+        const long long v = wave_sum_i64(narrow[k]);
         if (lane_id() == 0 && v != 0) atomicAdd(reinterpret_cast<unsigned long long*>(&s_mom[k]), (unsigned long long)v);
     }
+    s_wide[0][threadIdx.x] = m3; s_wide[1][threadIdx.x] = m4; s_wide[2][threadIdx.x] = m7;
     __syncthreads();
     // a third distinct y exists iff some y is strictly between the extremes
     int mid = 0;
@@ -1478,8 +1564,12 @@ __global__ __launch_bounds__(NT) void k_fit_list(const uint32_t* __restrict__ pi
     __syncthreads();
     if (threadIdx.x == 0) {
         const int distinct = n <= 0 ? 0 : (s_ymin == s_ymax ? 1 : (s_mid ? 3 : 2));
+        WideMoments wm;
+        wm.m0 = s_mom[0]; wm.m1 = s_mom[1]; wm.m2 = s_mom[2]; wm.m5 = s_mom[3]; wm.m6 = s_mom[4];
+        wm.m3 = wm.m4 = wm.m7 = 0;
+        for (int i = 0; i < NT; ++i) { wm.m3 += s_wide[0][i]; wm.m4 += s_wide[1][i]; wm.m7 += s_wide[2][i]; }
         double c[3];
-        const bool ok = solve_poly2(s_mom, distinct, (double)(h / 2), (double)(w / 2), (double)(h > 1 ? h : 2) * 0.5, c);
+        const bool ok = solve_poly2(wm, distinct, (double)y0, (double)x0, c);
         out4[0] = c[0]; out4[1] = c[1]; out4[2] = c[2];
         out4[3] = ok ? 0.0 : 1.0;
     }
@@ -1542,7 +1632,26 @@ size_t band_sums_bits_lds(const MaskBits& mb) {
     return (size_t)BSB_ROWS * mb.wpr * sizeof(unsigned long long);
 }
 
+// dynamic LDS of the first-formulation kernels: k_sws_fit holds a level's sums and its windows' row counts, k_band_fit two
+// counters per (side, row) of the WHOLE image -- 16 bytes per image row
+size_t sws1_lds(const SearchGeom& g) { return (((size_t)(2 * g.w + 1 + 4 * g.wh + 2) * 4 + 15) & ~(size_t)15) + 16 * sizeof(long long); }
+size_t band1_lds(const SearchGeom& g) { return (((size_t)(4 * g.h + 2 + 4) * 4 + 15) & ~(size_t)15) + 16 * sizeof(long long); }   // + 4 words for the distinct-row reduction
+bool first_big_lds() {
+    static const bool ok = allow_big_lds(k_sws_fit<false>) && allow_big_lds(k_sws_fit<true>) && allow_big_lds(k_band_fit<false>) &&
+                           allow_big_lds(k_band_fit<true>);
+    return ok;
+}
+
 }  // namespace
+
+// Whether the kernel that would run for this geometry can be launched at all: the *2 kernels check their LDS in *_eligible; the
+// first-formulation kernels they fall back to take more LDS the taller the window (k_sws_fit) or the image (k_band_fit: above 9590
+// rows it passes the 150 KB a workgroup may ask for).  The host refuses such a search instead of issuing a launch that fails.
+bool search_launchable(const SearchGeom& g, bool band, size_t mask_stride) {
+    if (band ? band2_eligible(g, mask_stride) : sws2_eligible(g, mask_stride)) return true;
+    const size_t lds = band ? band1_lds(g) : sws1_lds(g);
+    return lds <= 48 * 1024 || (lds <= 150 * 1024 && first_big_lds());
+}
 
 bool sws_fit_takes_bits(const SearchGeom& g, size_t mask_stride) { return sws2_eligible(g, mask_stride) && !env_flag("LT_SEARCH_U8"); }
 bool band_fit_takes_bits(const SearchGeom& g, size_t mask_stride) { return band2_eligible(g, mask_stride) && !env_flag("LT_SEARCH_U8"); }
@@ -1569,8 +1678,7 @@ void launch_sws_fit(hipStream_t s, const uint8_t* masks, size_t mask_stride, Mas
 #undef LT_LAUNCH_SWS2
         return;
     }
-    const size_t words = (size_t)(2 * g.w + 1 + 4 * g.wh + 2);
-    const size_t lds = ((words * 4 + 15) & ~(size_t)15) + 16 * sizeof(long long);
+    const size_t lds = sws1_lds(g);               // (within the limit: search_launchable, checked by prepare_search)
     if (vec4) hipLaunchKernelGGL(k_sws_fit<true>, dim3(n), dim3(NT), lds, s, masks, mask_stride, g, band_sums, pix, cent, rec);
     else hipLaunchKernelGGL(k_sws_fit<false>, dim3(n), dim3(NT), lds, s, masks, mask_stride, g, band_sums, pix, cent, rec);
 }
@@ -1586,8 +1694,7 @@ void launch_band_fit(hipStream_t s, const uint8_t* masks, size_t mask_stride, Ma
         else hipLaunchKernelGGL(k_band_fit2<false>, dim3(n), dim3(NT), lds2, s, masks, mask_stride, mb, g, prev, bp, pix, rec, nq);
         return;
     }
-    const size_t words = (size_t)(4 * g.h + 2) + 4;  // + 4 words for the distinct-row reduction
-    const size_t lds = ((words * 4 + 15) & ~(size_t)15) + 16 * sizeof(long long);
+    const size_t lds = band1_lds(g);              // (within the limit: search_launchable, checked by prepare_search)
     if (vec4)
         hipLaunchKernelGGL(k_band_fit<true>, dim3(n), dim3(NT), lds, s, masks, mask_stride, g, prev, bp, pix, rec);
     else

@@ -408,6 +408,11 @@ int prepare_search(lt_ctx* c, const lt_search_params* p, bool band, SearchGeom& 
     if (!band && (rc = ensure_band_sums(c, g.nbands))) return rc;
     g.maxpix = c->maxpix;
     g.maxlev = c->maxlev;
+    if (!search_launchable(g, band, c->masks.plane_bytes))
+        return band ? fail(LT_ERR_INVALID, "a band search wider than 64 columns (bandwidth > 31), or any on an image taller than 8192 rows, "
+                                           "keeps 16 bytes of LDS per image row: at most 9590 rows, this image has %d", g.h)
+                    : fail(LT_ERR_INVALID, "this sliding-window search keeps 16 bytes of LDS per window row and 8 per image column: "
+                                           "window_height %d is too tall for width %d (150 KB in all)", g.wh, g.w);
     return LT_OK;
 }
 
@@ -791,6 +796,10 @@ int lt_warm(lt_ctx* c, const lt_search_params* sws, const lt_search_params* band
         maxlev = std::max(maxlev, 1);
     }
     if (maxpix && (rc = ensure_search_buffers(c, maxpix, maxlev))) return rc;
+    // ... and the same refusal the run calls give (prepare_search), with the buffers as they now are
+    SearchGeom g;
+    if (sws && (rc = prepare_search(c, sws, false, g))) return rc;
+    if (band && (rc = prepare_search(c, band, true, g))) return rc;
     if ((annotate & 3) && (rc = warm_presentation(c, (annotate & 3) == 2))) return rc;
     if ((annotate & 12) && (rc = warm_search_viz(c, (annotate & 8) != 0))) return rc;
     return sync_all(c);

@@ -335,6 +335,9 @@ struct MaskBits {
     int wpr;
 };
 bool sws_fit_takes_bits(const SearchGeom& g, size_t mask_stride);
+// false: the kernel this geometry selects needs more LDS than a workgroup can have (tall windows or bands wider than 64 columns
+// on tall images, see k_search.hip) -- the entry points refuse the search with LT_ERR_INVALID
+bool search_launchable(const SearchGeom& g, bool band, size_t mask_stride);
 bool band_fit_takes_bits(const SearchGeom& g, size_t mask_stride);
 void launch_sws_fit(hipStream_t s, const uint8_t* masks, size_t mask_stride, MaskBits mb, SearchGeom g, uint32_t* band_sums,
                     uint32_t* pix, int32_t* cent, lt_lane_record* rec, int n);
