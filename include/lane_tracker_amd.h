@@ -59,8 +59,9 @@ extern "C" {
  *    lt_calibration_count + lt_set_slot_calibrations + lt_get_slot_calibrations + lt_overlay_configure_set (several calibrations in
  *    one context, one per slot: the cameras of a LaneTrackerGroup); lt_inplace_text + lt_overlay_run_inplace +
  *    lt_overlay_run_inplace_coeffs (lane and text drawn into the attached camera surfaces themselves); lt_overlay_run_to_surfaces +
- *    lt_last_overlay_launches (lane and text drawn on the way into device sinks, one launch whatever the slots' calibration sets).
- *    Nothing removed or changed. */
+ *    lt_last_overlay_launches (lane and text drawn on the way into device sinks, one launch whatever the slots' calibration sets);
+ *    lt_set_input_size + lt_get_input_size + lt_get_input_rows (RGB camera frames of another size than the calibration's, resized on
+ *    the device).  Nothing removed or changed. */
 #define LT_ABI_VERSION 5
 
 typedef enum lt_status {
@@ -209,6 +210,24 @@ enum lt_input_layout { LT_INPUT_RGB = 0, LT_INPUT_NV12 = 1, LT_INPUT_I420 = 2, L
 int  lt_set_input_format(lt_ctx* ctx, int layout, const int32_t coeffs[5]);
 int  lt_get_input_format(lt_ctx* ctx, int* layout, int32_t coeffs[5]);
 int  lt_yuv_to_rgb(lt_ctx* ctx, const uint8_t* frame, int h, int w, int layout, const int32_t coeffs[5], uint8_t* out_rgb);
+/* Frames of another SIZE than the calibration's: a context with an input size of src_w x src_h takes RGB frames of src_h * src_w * 3
+ * bytes and resizes them on the device to img_w x img_h -- cv2.resize(frame, (img_w, img_h)) with the default INTER_LINEAR, bit for bit:
+ * half-pixel centres, 11-bit coefficients, OpenCV's two-stage rounding.  Everything the context computes, keeps and hands out is what a
+ * plain context gives for the resized frames; annotated frames are img_w x img_h.  lt_set_input_size is called once, before the
+ * context's first upload or attach, like lt_set_input_format: LT_ERR_INVALID for a width or height outside 1 .. 16384, LT_ERR_STATE
+ * after an upload or in a context whose input format is not RGB (lt_set_input_format with a YUV layout on a context with an input size
+ * is LT_ERR_STATE likewise); (img_w, img_h) clears the setting.  lt_get_input_size reads it back (the calibration's size without one).
+ * In such a context every upload entry point below keeps its name and takes frames of the input size where it says frames_rgb.  Each
+ * slot has a staging frame of the input size: the lt_upload_frame_rows family copies the source rows [s0, s1) that camera rows
+ * [row0, row1) read -- lt_get_input_rows; lt_get_source_rows keeps its meaning, rows of the img_w x img_h frame -- and resizes
+ * [row0, row1) into the slot's camera frame right behind the copy, ahead of whatever is launched over the slots next;
+ * lt_upload_frames and the lt_upload_frame_rest family bring the source rows their rows read and leave the resized rows in the
+ * camera frame (rows4 of lt_upload_frame_rest_rows are rows of the img_w x img_h frame).  The undistortion and everything behind
+ * it read the camera frame as in a plain context.  lt_set_direct_upload returns 0 on such a context (its rows go to staging), and
+ * lt_attach_device_frames returns LT_ERR_STATE: frames in device memory are not resized. */
+int  lt_set_input_size(lt_ctx* ctx, int src_w, int src_h);
+int  lt_get_input_size(lt_ctx* ctx, int* src_w, int* src_h);
+int  lt_get_input_rows(lt_ctx* ctx, int* row0, int* row1);
 /* frames: n * img_h * img_w * 3 bytes, RGB interleaved, as LaneTracker.process() receives them (:876) */
 int  lt_upload_frames(lt_ctx* ctx, const uint8_t* frames_rgb, int first_slot, int n);
 /* Camera rows [row0, row1) that undistort + warp actually read (a third of a 720-row frame at the reference

@@ -229,6 +229,9 @@ _SIGNATURES = {
     "lt_last_adaptive_path": (C.c_int, [_P]),
     "lt_set_input_format": (C.c_int, [_P, C.c_int, _P]),
     "lt_get_input_format": (C.c_int, [_P, C.POINTER(C.c_int), _P]),
+    "lt_set_input_size": (C.c_int, [_P, C.c_int, C.c_int]),
+    "lt_get_input_size": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "lt_get_input_rows": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "lt_yuv_to_rgb": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "lt_attach_device_frames": (C.c_int, [_P, _P, C.c_int, C.c_int]),
     "lt_device_frames_rest": (C.c_int, [_P, C.c_int, C.c_int, _P]),
@@ -317,6 +320,24 @@ def yuv_coeffs(matrix):
     if k.shape != (5,):
         raise ValueError("a conversion matrix is five integers")
     return k
+
+
+def checked_input_size(input_size, img_size, pixel_format="rgb"):
+    """`input_size` = (width, height) of the frames a tracker is fed when that is not its calibration's `img_size`, as a tuple of two
+    ints, or None (no input size, or the calibration's own); ValueError for a size outside 1 .. 16384 and for YUV frames."""
+    if input_size is None:
+        return None
+    try:
+        w, h = (int(v) for v in input_size)
+    except (TypeError, ValueError):
+        raise ValueError("input_size is (width, height), got %r" % (input_size,)) from None
+    if not (1 <= w <= 16384 and 1 <= h <= 16384):
+        raise ValueError("input_size must be 1 .. 16384 pixels wide and high, got %dx%d" % (w, h))
+    if (w, h) == (int(img_size[0]), int(img_size[1])):
+        return None
+    if pixel_format != "rgb":
+        raise ValueError("input_size resizes RGB frames only: pixel_format=%r frames must come in the calibration's size" % (pixel_format,))
+    return w, h
 
 
 def frame_shape(img_size, pixel_format="rgb"):
@@ -725,7 +746,8 @@ class Context:
         self._h = h
         self.lib = lib
         self.img_w, self.img_h, self.warp_w, self.warp_h = cal.img_w, cal.img_h, cal.warp_w, cal.warp_h
-        self._frame_tail = (cal.img_h, cal.img_w, 3)     # shape of one camera frame as the uploads take it (set_input_format)
+        self._frame_tail = (cal.img_h, cal.img_w, 3)     # shape of one camera frame as the uploads take it (set_input_format, set_input_size)
+        self._input_size = None                          # (width, height) of the frames the uploads take when it is not the calibration's
         self.reserve(capacity)
 
     def close(self):
@@ -765,8 +787,33 @@ class Context:
         layout = pixel_format_id(pixel_format)
         tail = frame_shape((self.img_w, self.img_h), pixel_format)
         k = yuv_coeffs(yuv_matrix) if layout else None
+        if layout and self._input_size is not None:
+            raise ValueError("a context with an input size takes RGB frames only: %r frames are not resized" % (pixel_format,))
         _check(self.lib.lt_set_input_format(self._h, layout, None if k is None else k.ctypes.data))
         self._frame_tail = tail
+
+    def set_input_size(self, size):
+        """Frames of another size: the uploads take RGB frames (Hi, Wi, 3) of `size` = (Wi, Hi) and resize them on the device to the
+        calibration's size -- `cv2.resize(frame, img_size)`, INTER_LINEAR, bit for bit (lt_set_input_size).  Once, before the first
+        upload, RGB contexts only; None or the calibration's own size clears the setting."""
+        w, h = (self.img_w, self.img_h) if size is None else (int(size[0]), int(size[1]))
+        _check(self.lib.lt_set_input_size(self._h, w, h))
+        plain = (w, h) == (self.img_w, self.img_h)
+        self._input_size = None if plain else (w, h)
+        self._frame_tail = (h, w, 3)
+
+    def input_size(self):
+        """-> (width, height) of the frames the uploads take (lt_get_input_size)."""
+        w, h = C.c_int(0), C.c_int(0)
+        _check(self.lib.lt_get_input_size(self._h, C.byref(w), C.byref(h)))
+        return w.value, h.value
+
+    def input_rows(self):
+        """Rows [row0, row1) of a frame of the input size that upload_frame_rows moves (lt_get_input_rows): source_rows() without an
+        input size."""
+        a, b = C.c_int(0), C.c_int(0)
+        _check(self.lib.lt_get_input_rows(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def input_format(self):
         """-> (pixel format name, the five conversion coefficients)."""
@@ -779,7 +826,7 @@ class Context:
         f = _u8(frames)
         tail = self._frame_tail
         if f.shape[-len(tail):] != tail or f.ndim > len(tail) + 1:
-            if tail[-1] == 3 and len(tail) == 3:
+            if tail[-1] == 3 and len(tail) == 3 and self._input_size is None:
                 return f.reshape((-1,) + tail)           # (RGB: anything of the right size, as ever)
             raise ValueError("expected camera frames of shape %r, got %r" % (tail, f.shape))
         return f.reshape((-1,) + tail)
@@ -871,6 +918,8 @@ class Context:
         """The front end of slots first, first + 1, ... reads `frames` (a device.DeviceFrames) where they lie in device memory
         (lt_attach_device_frames); nothing is copied.  Returns `frames`: keep it -- and the memory it describes -- alive and
         unchanged until a call that waits for work launched over these slots afterwards (download_record, sync)."""
+        if self._input_size is not None:
+            raise ValueError("a context with an input size takes host frames only: frames in device memory are not resized")
         frames.check_for((self.img_w, self.img_h), "rgb" if self._frame_tail[-1] == 3 and len(self._frame_tail) == 3 else self.input_format()[0])
         frames.wait_for_producer()
         s = np.ascontiguousarray(frames.surfaces)

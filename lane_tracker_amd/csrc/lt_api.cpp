@@ -26,6 +26,7 @@
 
 #include "front_arith.h"
 #include "lt_ctx.h"
+#include "resize_arith.h"
 
 using namespace lt;
 
@@ -183,6 +184,7 @@ int set_device(lt_ctx* c) {
 void free_slots(lt_ctx* c) {
     dev_free(c->d_frames);
     dev_free(c->d_yuv);
+    dev_free(c->d_src);
     dev_free(c->d_und);
     dev_free(c->d_surf);
     c->surf.clear();
@@ -710,6 +712,8 @@ void lt_destroy(lt_ctx* c) {
     dev_free(c->d_gamma);
     dev_free(c->d_cbrt);
     dev_free(c->d_coef);
+    dev_free(c->d_rs_xt);
+    dev_free(c->d_rs_yt);
     dev_free(c->d_oxy);
     dev_free(c->d_ofrac);
     for (size_t i = 1; i < c->cal.size(); ++i) {     // (set 0's tables are the ones above)
@@ -748,6 +752,7 @@ int lt_reserve(lt_ctx* c, int capacity) {
     if ((rc = dev_alloc(&c->d_frames, n * c->frame_bytes + 16))) { free_slots(c); return rc; }   // +16: k_undistort_rows reads 8-byte windows
     c->direct_upload = -1;               // a new frame buffer: whether the host can write it is found out by the first small upload
     if (c->in_layout != LT_INPUT_RGB && (rc = dev_alloc(&c->d_yuv, n * c->yuv_stride + 16))) { free_slots(c); return rc; }
+    if (c->src_w > 0 && (rc = dev_alloc(&c->d_src, n * c->src_stride))) { free_slots(c); return rc; }
     if ((rc = dev_alloc(&c->d_und, (size_t)((n + 1) / 2) * 2 * c->und_px))) { free_slots(c); return rc; }
     if ((rc = c->masks.reserve(capacity, true))) { free_slots(c); return rc; }
     c->mask_bits_ok.assign(n, 0);
@@ -872,6 +877,8 @@ int lt_set_input_format(lt_ctx* c, int layout, const int32_t* coeffs) {
     const bool same = layout == c->in_layout && (layout == LT_INPUT_RGB || std::memcmp(coeffs, c->yuv_coef, sizeof c->yuv_coef) == 0);
     if (same) return LT_OK;
     if (c->input_locked) return fail(LT_ERR_STATE, "the input format of a context cannot change after its first upload");
+    if (layout != LT_INPUT_RGB && c->src_w > 0)
+        return fail(LT_ERR_STATE, "a context with an input size (lt_set_input_size) takes RGB frames only: YUV frames are not resized");
     if ((rc = set_device(c))) return rc;
     if ((rc = sync_all(c))) return rc;
     if (layout == LT_INPUT_RGB) {
@@ -927,6 +934,109 @@ static void yuv_convert(lt_ctx* c, hipStream_t st, int first, int n, int r0, int
                            c->calib.img_h, c->calib.img_w, r0, r1, n);
 }
 
+// ---- input frames of another size (lt_set_input_size) ------------------------------------------------------------------------
+// The slots' staging frames hold the caller's src_w x src_h RGB frames (or the rows of them that have been uploaded); k_resize_rows
+// fills rows of the slots' RGB camera frames from them.  Which source rows a run of camera rows reads follows from the vertical tap
+// table (resize_arith.h: input_run).
+static inline bool resizes(const lt_ctx* c) { return c->src_w > 0; }
+static void rs_input_rows(const lt_ctx* c, int a, int b, int* s0, int* s1) {
+    if (b <= a) { *s0 = *s1 = 0; return; }
+    *s0 = c->rs_yt[4 * (size_t)a];
+    *s1 = c->rs_yt[4 * (size_t)(b - 1) + 1] + 1;
+}
+// source rows [s0, s1) of n host frames (src_bytes apart) into the staging frames of slots [first, first + n), on `st`
+static int rs_copy(lt_ctx* c, const uint8_t* frames, int first, int n, int s0, int s1, hipStream_t st) {
+    if (s1 <= s0) return LT_OK;
+    const size_t rb = (size_t)c->src_w * 3, off = (size_t)s0 * rb;
+    HIP_TRY(hipMemcpy2DAsync(slot_src(c, first) + off, c->src_stride, frames + off, c->src_bytes, (size_t)(s1 - s0) * rb, (size_t)n,
+                             hipMemcpyHostToDevice, st));
+    return LT_OK;
+}
+// ... those that camera rows [a, b) read and that the upload of the rows the path reads does not bring
+static int rs_copy_for(lt_ctx* c, const uint8_t* frames, int first, int n, int a, int b, hipStream_t st) {
+    int A, B, s0, s1;
+    rs_input_rows(c, a, b, &A, &B);
+    rs_input_rows(c, c->cam_r0, c->cam_r1, &s0, &s1);
+    if (s1 <= s0) return rs_copy(c, frames, first, n, A, B, st);
+    int rc = rs_copy(c, frames, first, n, A, std::min(B, s0), st);
+    return rc ? rc : rs_copy(c, frames, first, n, std::max(A, s1), B, st);
+}
+// rows [a, b) of the RGB camera frames of slots [first, first + n) := the resized rows of their staging frames, on `st`
+static int rs_resize(lt_ctx* c, hipStream_t st, int first, int n, int a, int b) {
+    launch_resize_rows(st, slot_src(c, first), c->src_stride, c->src_bytes, c->src_w, slot_frame(c, first), c->frame_bytes, c->calib.img_w,
+                       a, b, c->d_rs_xt, c->d_rs_yt, n);
+    HIP_TRY(hipGetLastError());
+    return LT_OK;
+}
+
+int lt_set_input_size(lt_ctx* c, int src_w, int src_h) {
+    if (!c) return fail(LT_ERR_INVALID, "null context");
+    if (src_w < 1 || src_w > rz::SIZE_MAX_AXIS || src_h < 1 || src_h > rz::SIZE_MAX_AXIS)
+        return fail(LT_ERR_INVALID, "an input size is 1 .. %d pixels wide and high, got %dx%d", rz::SIZE_MAX_AXIS, src_w, src_h);
+    const int W = c->calib.img_w, H = c->calib.img_h;
+    const bool plain = src_w == W && src_h == H;
+    if (plain ? !resizes(c) : (src_w == c->src_w && src_h == c->src_h)) return LT_OK;
+    if (c->input_locked) return fail(LT_ERR_STATE, "the input size of a context cannot change after its first upload");
+    if (c->in_layout != LT_INPUT_RGB) return fail(LT_ERR_STATE, "an input size needs RGB frames: this context's input format is a YUV layout");
+    int rc = set_device(c);
+    if (rc) return rc;
+    if ((rc = sync_all(c))) return rc;
+    if (plain) {
+        dev_free(c->d_src);
+        dev_free(c->d_rs_xt);
+        dev_free(c->d_rs_yt);
+        c->rs_yt.clear();
+        c->src_w = c->src_h = 0;
+        c->src_bytes = c->src_stride = 0;
+        return LT_OK;
+    }
+    // the tap tables: columns as the kernel reads them (padded to whole groups of four with entries that read column 0), rows as taps
+    std::vector<uint32_t> xt((size_t)((W + 3) & ~3) * 2, 0u);
+    for (int x = 0; x < W; ++x) rz::pack_column(rz::resize_tap(src_w, W, x), src_w, &xt[2 * (size_t)x]);
+    std::vector<int32_t> yt((size_t)H * 4);
+    for (int y = 0; y < H; ++y) {
+        const rz::Tap t = rz::resize_tap(src_h, H, y);
+        yt[4 * (size_t)y] = t.tap0; yt[4 * (size_t)y + 1] = t.tap1; yt[4 * (size_t)y + 2] = t.c0; yt[4 * (size_t)y + 3] = t.c1;
+    }
+    dev_free(c->d_rs_xt);
+    dev_free(c->d_rs_yt);
+    if ((rc = dev_alloc(&c->d_rs_xt, xt.size()))) return rc;
+    if ((rc = dev_alloc(&c->d_rs_yt, yt.size()))) return rc;
+    HIP_TRY(hipMemcpy(c->d_rs_xt, xt.data(), xt.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->d_rs_yt, yt.data(), yt.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    // the staging frame of a slot: src_h src_w 3 bytes, slots a multiple of 16 apart with at least 16 bytes between two frames
+    const size_t bytes = (size_t)src_h * src_w * 3, stride = ((bytes + 15) & ~(size_t)15) + 16;
+    if (stride != c->src_stride) dev_free(c->d_src);
+    if (c->capacity > 0 && !c->d_src && (rc = dev_alloc(&c->d_src, (size_t)c->capacity * stride))) {
+        dev_free(c->d_rs_xt);
+        dev_free(c->d_rs_yt);
+        c->rs_yt.clear();
+        c->src_w = c->src_h = 0;             // (no staging: the context falls back to what needs none)
+        c->src_bytes = c->src_stride = 0;
+        return rc;
+    }
+    c->rs_yt.swap(yt);
+    c->src_w = src_w;
+    c->src_h = src_h;
+    c->src_bytes = bytes;
+    c->src_stride = stride;
+    return LT_OK;
+}
+
+int lt_get_input_size(lt_ctx* c, int* src_w, int* src_h) {
+    if (!c || !src_w || !src_h) return fail(LT_ERR_INVALID, "null argument");
+    *src_w = resizes(c) ? c->src_w : c->calib.img_w;
+    *src_h = resizes(c) ? c->src_h : c->calib.img_h;
+    return LT_OK;
+}
+
+int lt_get_input_rows(lt_ctx* c, int* row0, int* row1) {
+    if (!c || !row0 || !row1) return fail(LT_ERR_INVALID, "null argument");
+    if (resizes(c)) rs_input_rows(c, c->cam_r0, c->cam_r1, row0, row1);
+    else { *row0 = c->cam_r0; *row1 = c->cam_r1; }
+    return LT_OK;
+}
+
 // ---- data movement -------------------------------------------------------------------------------
 int lt_upload_frames(lt_ctx* c, const uint8_t* frames, int first, int n) {
     int rc = check_slots(c, first, n);
@@ -941,6 +1051,10 @@ int lt_upload_frames(lt_ctx* c, const uint8_t* frames, int first, int n) {
         if (n > 0 && (rc = yuv_copy(c, frames, first, n, 0, c->calib.img_h, 0, c->calib.img_h / 2, c->stream))) return rc;
         yuv_convert(c, c->stream, first, n, 0, c->calib.img_h);
         HIP_TRY(hipGetLastError());
+    } else if (resizes(c)) {
+        // another size: the frames into staging, and their resized form into the camera frames (what everything else reads)
+        if (n > 0 && (rc = rs_copy(c, frames, first, n, 0, c->src_h, c->stream))) return rc;
+        if ((rc = rs_resize(c, c->stream, first, n, 0, c->calib.img_h))) return rc;
     } else
     HIP_TRY(hipMemcpyAsync(slot_frame(c, first), frames, (size_t)n * c->frame_bytes,
                            hipMemcpyHostToDevice, c->stream));
@@ -1002,7 +1116,7 @@ static bool host_has_mapped(const void* p, size_t n) {
 static bool direct_upload_possible(lt_ctx* c) {
     if (c->direct_upload < 0)
         c->direct_upload = c->prop.isLargeBar && c->d_frames && host_has_mapped(c->d_frames, (size_t)c->capacity * c->frame_bytes) ? 1 : 0;
-    return c->direct_upload == 1 && c->direct_upload_wanted && c->in_layout == LT_INPUT_RGB;   // (4:2:0 frames take the engine)
+    return c->direct_upload == 1 && c->direct_upload_wanted && c->in_layout == LT_INPUT_RGB && !resizes(c);   // (4:2:0 frames take the engine; so do frames of another size: their rows go to staging)
 }
 __attribute__((target("avx2"))) static void store_stream_avx2(uint8_t* dst, const uint8_t* src, size_t n) {
     size_t head = (32 - ((uintptr_t)dst & 31)) & 31;
@@ -1105,6 +1219,25 @@ static int upload_frame_rows_impl(lt_ctx* c, const uint8_t* frames, int first, i
         HIP_TRY(hipStreamSynchronize(c->stream));
         return LT_OK;
     }
+    if (resizes(c)) {
+        // another size: the source rows the path's rows read, into staging, and k_resize_rows over the path's rows right behind the copy
+        // on the same stream -- ahead of whatever is launched over the slots next.  Both are noted: the resize reads staging (the next
+        // upload into it waits), and the rest's resize on the copy stream reads rows this copy brings (yuv_rows).
+        int s0, s1;
+        rs_input_rows(c, c->cam_r0, c->cam_r1, &s0, &s1);
+        if (enqueue)
+            return for_each_slice(c, first, n, [&](hipStream_t st, int f0, int m) {
+                int wrc = enqueue_syncs ? (int)LT_OK : wait_camera_readers(c, st, f0, m);
+                if (!wrc) wrc = rs_copy(c, frames + (size_t)(f0 - first) * c->src_bytes, f0, m, s0, s1, st);
+                if (!wrc) wrc = rs_resize(c, st, f0, m, c->cam_r0, c->cam_r1);
+                if (!wrc) wrc = note_range_frame(c, c->readers, st, f0, f0 + m);
+                return wrc ? wrc : note_range_frame(c, c->yuv_rows, st, f0, f0 + m);
+            });
+        if ((rc = rs_copy(c, frames, first, n, s0, s1, c->stream))) return rc;
+        if ((rc = rs_resize(c, c->stream, first, n, c->cam_r0, c->cam_r1))) return rc;
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return LT_OK;
+    }
     const size_t row_bytes = (size_t)c->calib.img_w * 3, off = (size_t)c->cam_r0 * row_bytes;
     const size_t bytes = (size_t)(c->cam_r1 - c->cam_r0) * row_bytes;
     // (one frame, measured in round 5 against this pitched copy, 279-286 us per frame of process(): a plain copy of the contiguous
@@ -1171,6 +1304,12 @@ int lt_upload_frame_rows_async(lt_ctx* c, const uint8_t* frames, int first, int 
     if ((rc = wait_camera_readers(c, c->copy, first, n))) return rc;
     if (c->in_layout != LT_INPUT_RGB) {
         if ((rc = yuv_copy(c, frames, first, n, c->cam_r0, c->cam_r1, chroma_lo(c->cam_r0), chroma_hi(c->cam_r0, c->cam_r1), c->copy))) return rc;
+    } else if (resizes(c)) {
+        // another size: copy and resize both on the copy stream, the slots' streams wait for the resize
+        int s0, s1;
+        rs_input_rows(c, c->cam_r0, c->cam_r1, &s0, &s1);
+        if ((rc = rs_copy(c, frames, first, n, s0, s1, c->copy))) return rc;
+        if ((rc = rs_resize(c, c->copy, first, n, c->cam_r0, c->cam_r1))) return rc;
     } else {
     const size_t row_bytes = (size_t)c->calib.img_w * 3, off = (size_t)c->cam_r0 * row_bytes;
     HIP_TRY(hipMemcpy2DAsync(slot_frame(c, first) + off, c->frame_bytes, frames + off, c->frame_bytes,
@@ -1231,6 +1370,23 @@ int lt_upload_frame_rest_rows(lt_ctx* c, const uint8_t* frames, int first, int n
         if ((rc = note_range(c->readers, c->copy, first, first + n))) return rc;     // the conversion reads staging: the next upload into it waits
         return rest_mark(c, first, n);
     }
+    if (resizes(c)) {
+        // another size: for those rows of the two runs, the source rows they read that staging does not hold yet; then, behind the
+        // enqueued uploads of the path's source rows (the rows next to the window read some of them), their resize
+        int pieces[4][2], np = 0;
+        for (int k = 0; k < 4; k += 2) {
+            const int piece[2][2] = {{rows4[k], std::min(rows4[k + 1], lo)}, {std::max(rows4[k], hi), rows4[k + 1]}};
+            for (const auto& pc : piece)
+                if (pc[1] > pc[0]) { pieces[np][0] = pc[0]; pieces[np][1] = pc[1]; ++np; }
+        }
+        for (int i = 0; i < np; ++i)
+            if ((rc = rs_copy_for(c, frames, first, n, pieces[i][0], pieces[i][1], c->copy))) return rc;
+        if ((rc = wait_yuv_rows(c, first, n))) return rc;
+        for (int i = 0; i < np; ++i)
+            if ((rc = rs_resize(c, c->copy, first, n, pieces[i][0], pieces[i][1]))) return rc;
+        if ((rc = note_range(c->readers, c->copy, first, first + n))) return rc;     // the resize reads staging: the next upload into it waits
+        return rest_mark(c, first, n);
+    }
     uint8_t* dst = slot_frame(c, first);
     for (int k = 0; k < 4; k += 2) {
         const int piece[2][2] = {{rows4[k], std::min(rows4[k + 1], lo)}, {std::max(rows4[k], hi), rows4[k + 1]}};
@@ -1263,6 +1419,24 @@ int lt_upload_frame_rest(lt_ctx* c, const uint8_t* frames, int first, int n) {
         yuv_convert(c, c->copy, first, n, 0, H);
         HIP_TRY(hipGetLastError());
         if ((rc = note_range(c->readers, c->copy, first, first + n))) return rc;     // the conversion reads staging: the next upload into it waits
+        mark_frames(c, first, n, 1);
+        return rest_mark(c, first, n);
+    }
+    if (resizes(c)) {
+        // another size: the source rows the rows above and below the path's window read and staging does not hold yet, then those rows
+        // resized into the camera frame, behind both copies
+        const int H = c->calib.img_h, r0 = c->cam_r1 > c->cam_r0 ? c->cam_r0 : 0, r1 = c->cam_r1 > c->cam_r0 ? c->cam_r1 : 0;
+        if (r1 <= r0) {
+            if ((rc = rs_copy(c, frames, first, n, 0, c->src_h, c->copy))) return rc;
+            if ((rc = rs_resize(c, c->copy, first, n, 0, H))) return rc;
+        } else {
+            if ((rc = rs_copy_for(c, frames, first, n, 0, r0, c->copy))) return rc;
+            if ((rc = rs_copy_for(c, frames, first, n, r1, H, c->copy))) return rc;
+            if ((rc = wait_yuv_rows(c, first, n))) return rc;
+            if ((rc = rs_resize(c, c->copy, first, n, 0, r0))) return rc;
+            if ((rc = rs_resize(c, c->copy, first, n, r1, H))) return rc;
+        }
+        if ((rc = note_range(c->readers, c->copy, first, first + n))) return rc;     // the resize reads staging: the next upload into it waits
         mark_frames(c, first, n, 1);
         return rest_mark(c, first, n);
     }
@@ -1359,6 +1533,8 @@ int lt_attach_device_frames(lt_ctx* c, const lt_device_surface* surfaces, int fi
     int rc = check_slots(c, first, n);
     if (rc) return rc;
     if (!surfaces) return fail(LT_ERR_INVALID, "null surfaces");
+    if (c->src_w > 0)
+        return fail(LT_ERR_STATE, "a context with an input size (lt_set_input_size) takes host frames only: frames in device memory are not resized");
     if (n == 0) return LT_OK;
     if ((rc = set_device(c))) return rc;
     std::vector<SurfEntry> ent((size_t)n);

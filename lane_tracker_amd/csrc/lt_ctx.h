@@ -160,6 +160,17 @@ struct lt_ctx {
     bool input_locked = false;                // an upload has happened: the format stays
     uint8_t* d_yuv = nullptr;
     size_t yuv_bytes = 0, yuv_stride = 0;
+    // Input frames of another size (lt_set_input_size): src_w x src_h RGB frames, resized on the device to the calibration's size
+    // (cv2.resize, INTER_LINEAR).  Per slot a staging frame of src_bytes = src_h * src_w * 3 bytes, src_stride apart (a multiple of 16
+    // with at least 16 bytes of padding behind every frame: k_resize_rows reads aligned dwords); the uploads copy source rows into it
+    // and k_resize_rows fills the rows of the slot's RGB camera frame, which everything else reads as in a plain context.  The tap
+    // tables are built when the size is set: rs_yt on the host too (which source rows a run of rows reads).
+    int src_w = 0, src_h = 0;                 // 0: frames of the calibration's size
+    uint8_t* d_src = nullptr;
+    size_t src_bytes = 0, src_stride = 0;
+    uint32_t* d_rs_xt = nullptr;              // [img_w rounded up to 4][2] (resize_arith.h: pack_column)
+    int32_t* d_rs_yt = nullptr;               // [img_h][4]
+    std::vector<int32_t> rs_yt;
     // Frames in the caller's device memory (lt_attach_device_frames): the surface table -- one entry per slot, read by the table form
     // of the undistortion (k_frontend.hip) -- its host mirror (what lt_device_frames_rest passes on as kernel arguments) and which
     // slots are attached.  Allocated by the first attach; any upload of camera rows into a slot detaches it.
@@ -294,7 +305,7 @@ struct lt_ctx {
         void reset() { head = count = 0; overflow = false; lazy = false; lazy_seen = lazy_seq; }
     };
     RangeEvents readers, writers;
-    RangeEvents yuv_rows;                     // 4:2:0 context: the enqueued copies of source rows into staging (slots' streams): the conversion of a slot's rows waits for them
+    RangeEvents yuv_rows;                     // 4:2:0 / input-size context: the enqueued copies of source rows into staging (slots' streams): the conversion / resize of a slot's other rows waits for them
     RangeEvents rests;                        // lt_upload_frame_rest copies (copy stream): the overlay of a slot waits for ITS rows only
     // The chained band search of a stream (lt_band_fit_chain_run) is one workgroup walking many frames: it runs on a stream
     // of its own, beside the mask chains of later frames on the slots' streams.  A chain leaves its records in page-locked
@@ -335,6 +346,7 @@ namespace lt {
 // ---- per-slot addresses in the context's buffers ------------------------------------------------------
 inline uint8_t* slot_frame(const lt_ctx* c, int s) { return c->d_frames + (size_t)s * c->frame_bytes; }
 inline uint8_t* slot_yuv(const lt_ctx* c, int s) { return c->d_yuv + (size_t)s * c->yuv_stride; }
+inline uint8_t* slot_src(const lt_ctx* c, int s) { return c->d_src + (size_t)s * c->src_stride; }
 inline YuvCoef yuv_coef_of(const lt_ctx* c) { return YuvCoef{c->yuv_coef[0], c->yuv_coef[1], c->yuv_coef[2], c->yuv_coef[3], c->yuv_coef[4]}; }
 inline uint8_t* slot_mask(const lt_ctx* c, int s) { return c->masks.d_plane[P_MASK] + (size_t)s * c->masks.plane_bytes; }
 // the opened bit plane of slot s as the searches take it; use_bits = false: none (they read slot_mask)

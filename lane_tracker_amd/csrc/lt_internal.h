@@ -60,6 +60,11 @@ void launch_warp_split(hipStream_t s, const uint32_t* und, size_t und_px, int fi
 // rows [r0, r1) of n 4:2:0 frames of h x w (h, w even) -> the same rows of n RGB frames
 void launch_yuv_rows_to_rgb(hipStream_t s, int layout, const uint8_t* yuv, size_t yuv_stride, YuvCoef k, uint8_t* rgb,
                             size_t rgb_stride, int h, int w, int r0, int r1, int n);
+// Input frames of another size (lt_set_input_size; k_resize.hip): destination rows [a, b) of n RGB frames of width w, dst_stride apart, :=
+// cv2.resize(INTER_LINEAR) of n RGB staging frames of src_bytes (rows of src_w pixels), src_stride apart.  xt: two words per destination
+// column (resize_arith.h: pack_column), padded to a multiple of four columns; yt: (tap0, tap1, c0, c1) per destination row; device memory.
+void launch_resize_rows(hipStream_t s, const uint8_t* src, size_t src_stride, size_t src_bytes, int src_w, uint8_t* dst, size_t dst_stride,
+                        int w, int a, int b, const uint32_t* xt, const int32_t* yt, int n);
 // Frames in the caller's device memory (lt_attach_device_frames): one entry per slot of the context's surface table -- the plane
 // pointers (RGB: [0]; NV12: Y, UV; I420: Y, U, V) and the row pitches of the luma / RGB plane and of the chroma plane(s), in bytes.
 // Checked on the host before they reach a kernel: pitches at least a row and below 2^23 (24-bit multiplies), planes below 2^31 bytes.

@@ -105,7 +105,8 @@ class LaneTrackerGroup:
     `LaneTracker`; groups on different threads share nothing."""
 
     def __init__(self, k, img_size, warped_size, cam_matrix, dist_coeffs, warp_matrices, mpp_conversion, n_fail=8, n_reset=4,
-                 n_average=2, print_frame_count=False, device=0, *, pixel_format='rgb', yuv_matrix='bt601', calibrations=None):
+                 n_average=2, print_frame_count=False, device=0, *, pixel_format='rgb', yuv_matrix='bt601', calibrations=None,
+                 input_size=None):
         k = int(k)
         if k < 1:
             raise ValueError("a group needs at least one stream")
@@ -117,12 +118,19 @@ class LaneTrackerGroup:
         self.img_size, self.warped_size = img_size, warped_size
         self.pixel_format, self.yuv_matrix = pixel_format, yuv_matrix
         self._frame_shape = _native.frame_shape(img_size, pixel_format)
+        # one input size for all streams (LaneTracker's input_size): RGB frames of that size, resized on the device to img_size
+        self.input_size = None if input_size is None else tuple(int(v) for v in input_size)
+        self._resize_from = _native.checked_input_size(input_size, img_size, pixel_format)
+        if self._resize_from is not None:
+            self._frame_shape = (self._resize_from[1], self._resize_from[0], 3)
         self._ctx = _native.Context(img_size, warped_size, cam_matrix, dist_coeffs, warp_matrices[0], device=device, capacity=4 * k)
         self._tick = 0
         self._overlay_sets = set()           # the calibration sets whose overlay a member has configured
         try:
             if pixel_format != 'rgb':        # every stream of a group is a camera of the same kind
                 self._ctx.set_input_format(pixel_format, yuv_matrix)
+            if self._resize_from is not None:
+                self._ctx.set_input_size(self._resize_from)
             # the calibration sets of the context: 0 is the group's own, one more for every distinct calibration among the streams
             sets = {_table_key(dict(cam_matrix=cam_matrix, dist_coeffs=dist_coeffs, warp_matrices=warp_matrices)): 0}
             self._cal_ids = []
@@ -136,7 +144,7 @@ class LaneTrackerGroup:
                 self.trackers.append(_GroupMember(self, cal_id, img_size, warped_size, c["cam_matrix"], c["dist_coeffs"], c["warp_matrices"],
                                                   c["mpp_conversion"], n_fail=n_fail, n_reset=n_reset, n_average=n_average,
                                                   print_frame_count=print_frame_count, device=device,
-                                                  pixel_format=pixel_format, yuv_matrix=yuv_matrix))
+                                                  pixel_format=pixel_format, yuv_matrix=yuv_matrix, input_size=input_size))
         except BaseException:
             self.close()
             raise
@@ -240,6 +248,8 @@ class LaneTrackerGroup:
         shape = self._frame_shape
         imgs = [frames[i] if isinstance(frames[i], DeviceFrames) else np.ascontiguousarray(frames[i], np.uint8) for i in active]
         for img in imgs:
+            if isinstance(img, DeviceFrames) and self._resize_from is not None:
+                raise ValueError("a group with input_size takes host frames only: frames in device memory are not resized")
             if isinstance(img, DeviceFrames):        # a stream whose frame is already in device memory: attached, not uploaded
                 img.check_for(self.img_size, self.pixel_format)
                 if len(img) != 1:

@@ -65,7 +65,8 @@ class LaneTracker(StreamPipeline):
     """
 
     def __init__(self, img_size, warped_size, cam_matrix, dist_coeffs, warp_matrices, mpp_conversion,
-                 n_fail=8, n_reset=4, n_average=2, print_frame_count=False, device=0, *, pixel_format='rgb', yuv_matrix='bt601'):
+                 n_fail=8, n_reset=4, n_average=2, print_frame_count=False, device=0, *, pixel_format='rgb', yuv_matrix='bt601',
+                 input_size=None):
         # the camera's pixel format: 'rgb' frames (H, W, 3), YUV 4:2:0 as decoders hand it out -- 'nv12' / 'i420' frames
         # (H * 3 // 2, W) -- or packed 4:2:2 as cameras and capture cards do -- 'yuy2' / 'uyvy' frames (H, W, 2) -- converted on the
         # device with `yuv_matrix` ('bt601', 'bt709'); everything that comes back is RGB
@@ -73,6 +74,12 @@ class LaneTracker(StreamPipeline):
         self._frame_shape = _native.frame_shape(img_size, pixel_format)      # (ValueError: unknown format, odd 4:2:0 size, odd 4:2:2 width)
         if pixel_format != 'rgb':
             _native.yuv_coeffs(yuv_matrix)
+        # frames of another size than the calibration's: RGB frames (Hi, Wi, 3) of input_size = (Wi, Hi), resized on the device to
+        # img_size as cv2.resize(frame, img_size) does; everything that comes back -- annotated frames too -- is img_size
+        self.input_size = None if input_size is None else tuple(int(v) for v in input_size)
+        self._resize_from = _native.checked_input_size(input_size, img_size, pixel_format)     # None: frames come in img_size
+        if self._resize_from is not None:
+            self._frame_shape = (self._resize_from[1], self._resize_from[0], 3)
         self.img_size = img_size
         self.warped_size = warped_size
         self.cam_matrix = cam_matrix
@@ -139,17 +146,27 @@ class LaneTracker(StreamPipeline):
 
     def _make_context(self, device):
         ctx = _native.Context(self.img_size, self.warped_size, self.cam_matrix, self.dist_coeffs, self.M, device=device, capacity=2)
-        if self.pixel_format != 'rgb':
-            try:
+        try:
+            if self.pixel_format != 'rgb':
                 ctx.set_input_format(self.pixel_format, self.yuv_matrix)
-            except BaseException:
-                ctx.close()
-                raise
+            if self._resize_from is not None:
+                ctx.set_input_size(self._resize_from)
+        except BaseException:
+            ctx.close()
+            raise
         return ctx
 
     def _check_frame(self, img, window=False):
         """A 4:2:0 / 4:2:2 tracker takes frames of its own shape only (nothing is uploaded before this has been looked at); an RGB tracker
         takes what it always took.  Frames in device memory (device.DeviceFrames) must be the tracker's size and pixel format."""
+        if self._resize_from is not None:
+            if isinstance(img, DeviceFrames):
+                raise ValueError("a tracker with input_size takes host frames only: frames in device memory are not resized")
+            shape, want = getattr(img, "shape", None), self._frame_shape
+            if shape is None or tuple(shape[1:] if window else shape) != want or (window and len(shape) != len(want) + 1):
+                raise ValueError("a tracker with input_size=%r takes frames of shape %s%r, got %r"
+                                 % (self._resize_from, "(n,) + " if window else "", want, shape))
+            return
         if isinstance(img, DeviceFrames):
             img.check_for(self.img_size, self.pixel_format)
             if not window and len(img) != 1:

@@ -593,7 +593,7 @@ class StreamPipeline:
             ctx.reserve(regions * size)
         mode = 0
         if annotate and not self._draw_inplace:      # (drawing into the caller's surfaces needs neither annotated frames nor strips)
-            rows = self._present_rows() if (self.host_copies_rows and not self._to_sink) else None
+            rows = self._present_rows() if (self.host_copies_rows and not self._to_sink and self._resize_from is None) else None
             mode = 2 if (rows is not None and rows[4] is not None) else 1
         if mode == 2 and output_pool and annotate != "inplace":   # the pool of output frames: a window being filled, one landing, one with the caller, one to spare
             _native.frames_prefault((int(window), ctx.img_h, ctx.img_w, 3), regions)
@@ -608,6 +608,13 @@ class StreamPipeline:
         return time.perf_counter() - t0
 
     def _as_window(self, frames):
+        if self._resize_from is not None:        # frames of another size: host arrays of that size, resized on the device
+            if self._annotate_inplace:
+                raise ValueError("annotate='inplace' draws into the caller's frames: a tracker with input_size returns frames of img_size")
+            if not isinstance(frames, DeviceFrames):
+                frames = np.ascontiguousarray(frames, np.uint8)
+            self._check_frame(frames, window=True)
+            return frames
         if isinstance(frames, DeviceFrames):     # frames in device memory: attached where they lie, shown through the device
             if self._annotate_inplace:
                 raise ValueError("annotate='inplace' draws into RGB frames on the host: DeviceFrames have none there")
@@ -635,6 +642,8 @@ class StreamPipeline:
         tracker's own `yuv_matrix` when that is a preset name (a custom input matrix names no matrix for the way back)."""
         if out != "inplace":
             raise ValueError("out= takes a DeviceFrames or 'inplace', got %r" % (out,))
+        if self._resize_from is not None:
+            raise ValueError("out='inplace' draws into the frames handed in: a tracker with input_size returns frames of img_size")
         if self.pixel_format in _native.PACKED_422:
             raise ValueError("out='inplace' draws into RGB, NV12 or I420 surfaces: %r is an input format only" % (self.pixel_format,))
         if out_yuv_matrix is not None:

@@ -252,7 +252,9 @@ def process_frames(tracker, source, sink=None, window=64, viz_sink=None, out_for
         if sink is None or viz_sink is not None:
             raise ValueError("out_format writes the annotated frames: it needs a sink, and no visualisation sink")
         from .device import DeviceFrames
-        sinks = (DeviceFrames.empty(min(window, n - start), source.size, out_format, device=tracker.device) for start in range(0, n, window))
+        # (a tracker with an input size hands out frames of its own img_size, not of the source's)
+        out_size = tuple(int(v) for v in tracker.img_size) if getattr(tracker, "input_size", None) is not None else source.size
+        sinks = (DeviceFrames.empty(min(window, n - start), out_size, out_format, device=tracker.device) for start in range(0, n, window))
         for out in tracker.process_stream(windows, annotate=True, out=sinks, out_yuv_matrix=out_yuv_matrix, **process_kwargs):
             for f in out:                # one-frame DeviceFrames of the window's sink
                 sink.write(f.to_host())
@@ -317,6 +319,9 @@ def main(argv=None):
     ap.add_argument("--cam", default="cam_calib.p", help="camera calibration (.p pickle or .npz)")
     ap.add_argument("--warp", default="warp_params.p", help="warp parameters (.p pickle or .npz)")
     ap.add_argument("--size", type=_parse_size, default=None, help="WxH of raw input frames")
+    ap.add_argument("--input-size", type=_parse_size, default=None,
+                    help="WxH of the input frames when that is not the calibration's size: raw RGB input is read in this size and the "
+                         "tracker resizes the frames on the device (cv2.resize, INTER_LINEAR); what is written has the calibration's size")
     ap.add_argument("--window", type=int, default=64, help="frames per GPU batch")
     ap.add_argument("--pixel-format", choices=("rgb", "nv12", "i420", "yuy2", "uyvy"), default=None,
                     help="pixel format of the input frames (default: by the input's name); must match a raw input's extension")
@@ -347,16 +352,19 @@ def main(argv=None):
     from .utils import load_camera_calib, load_warp_params
     cam_matrix, dist_coeffs = load_camera_calib(a.cam)
     M, Minv, image_wh, warped_wh, mppv, mpph = load_warp_params(a.warp)
-    src = FrameSource(a.input, a.size or image_wh)
+    if a.input_size is not None and a.size is not None and tuple(a.size) != tuple(a.input_size):
+        ap.error("--size %dx%d and --input-size %dx%d name two sizes for the input frames" % (tuple(a.size) + tuple(a.input_size)))
+    src = FrameSource(a.input, a.input_size or a.size or image_wh)
     if a.pixel_format is not None and a.pixel_format != src.pixel_format:
         ap.error("--pixel-format %s, but %s holds %s frames" % (a.pixel_format, a.input, src.pixel_format))
     lt = LaneTracker(img_size=image_wh, warped_size=warped_wh, cam_matrix=cam_matrix, dist_coeffs=dist_coeffs,
                      warp_matrices=(M, Minv), mpp_conversion=(mppv, mpph), n_fail=8, n_reset=4, n_average=2,
-                     print_frame_count=a.frame_count, device=a.device, pixel_format=src.pixel_format, yuv_matrix=a.yuv_matrix)
+                     print_frame_count=a.frame_count, device=a.device, pixel_format=src.pixel_format, yuv_matrix=a.yuv_matrix,
+                     input_size=a.input_size)
     try:
-        out_size = src.size
+        out_size = src.size if a.input_size is None else tuple(int(v) for v in image_wh)
         if a.split_view:                 # the annotated frame on top, the pane strip below it
-            out_size = (src.size[0], src.size[1] + _native.split_panes_size(src.size, warped_wh)[1])
+            out_size = (out_size[0], out_size[1] + _native.split_panes_size(out_size, warped_wh)[1])
         sink = None if a.output == "-" else FrameSink(a.output, out_size, n=len(src), pixel_format=a.out_format or "rgb")
         viz_sink = FrameSink(a.visualize_search, warped_wh, n=len(src)) if a.visualize_search else None
         kw = {}
