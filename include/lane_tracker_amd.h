@@ -203,8 +203,20 @@ int  lt_set_streams(lt_ctx* ctx, int nstreams);
  * with "rows [row0, row1) of the one plane" for the rows that are moved (2 / 3 of the bytes of the RGB form); lt_yuv_to_rgb takes a
  * frame of h * w * 2 bytes (w even, at least 4; any h).  4:2:2 is an INPUT format only: lt_rgb_to_surfaces and
  * lt_overlay_store_device return LT_ERR_INVALID for these two layouts, and lt_overlay_run_inplace* on a 4:2:2 context returns
- * LT_ERR_STATE before anything is staged (a 4:2:2 context writes its annotated frames into RGB, NV12 or I420 sinks like any other). */
-enum lt_input_layout { LT_INPUT_RGB = 0, LT_INPUT_NV12 = 1, LT_INPUT_I420 = 2, LT_INPUT_YUY2 = 3, LT_INPUT_UYVY = 4 };
+ * LT_ERR_STATE before anything is staged (a 4:2:2 context writes its annotated frames into RGB, NV12 or I420 sinks like any other).
+ *
+ * The other members of the RGB family, as users' own software holds frames -- LT_INPUT_BGR (bytes B G R; OpenCV's cv2.imread /
+ * VideoCapture: img_h rows of 3 * img_w bytes, numpy (H, W, 3)), LT_INPUT_RGBA (R G B A) and LT_INPUT_BGRA (B G R A; GStreamer / V4L2
+ * RGBx / BGRx, capture and compositor surfaces: img_h rows of 4 * img_w bytes, numpy (H, W, 4)).  A channel permutation, folded
+ * into the constant shifts the undistortion takes its channels out with: no conversion, `coeffs` is not read (NULL), the alpha
+ * byte is never read, and everything is bit for bit what an RGB context computes from the permuted frames.  img_w at least 2, no
+ * parity requirement.  Uploads and attached surfaces work as said above with one plane of 3 / 4 bytes a pixel (pitch >= 3 / 4 *
+ * img_w; chroma_pitch is not read); lt_set_direct_upload returns 0 (rows go to staging).  These three are SINKS too:
+ * lt_rgb_to_surfaces and lt_overlay_store_device write them (alpha = 255, bytes between a row's end and the pitch untouched, any
+ * byte alignment).  Not supported: lt_overlay_run_inplace* on such a context and lt_set_input_size with such a format return
+ * LT_ERR_STATE, lt_overlay_run_to_surfaces with such a sink layout LT_ERR_INVALID; lt_yuv_to_rgb does not take them. */
+enum lt_input_layout { LT_INPUT_RGB = 0, LT_INPUT_NV12 = 1, LT_INPUT_I420 = 2, LT_INPUT_YUY2 = 3, LT_INPUT_UYVY = 4,
+                       LT_INPUT_BGR = 5, LT_INPUT_RGBA = 6, LT_INPUT_BGRA = 7 };
 #define LT_YUV_BT601 {1220542, 1673527, -852492, -409993, 2116026}   /* video range; OpenCV's constants */
 #define LT_YUV_BT709 {1220542, 1880097, -558891, -223347, 2214593}   /* video range */
 int  lt_set_input_format(lt_ctx* ctx, int layout, const int32_t coeffs[5]);
@@ -278,7 +290,7 @@ int  lt_upload_frame_rest_list(lt_ctx* ctx, const uint8_t* const* frames_rgb, in
  * way to a lane record -- fetches its taps from the surfaces themselves.  One lt_device_surface per frame, in the layout of the
  * context's input format: plane[0] the RGB rows (3 bytes a pixel) or the Y plane, `pitch` bytes from row to row; NV12: plane[1]
  * the rows of (U, V) pairs; I420: plane[1] the U and plane[2] the V plane; `chroma_pitch` bytes between chroma rows.  YUY2 / UYVY:
- * plane[0] the one plane, `pitch` >= 2 * img_w; chroma_pitch is not read.  Any byte
+ * plane[0] the one plane, `pitch` >= 2 * img_w; BGR: >= 3 * img_w; RGBA / BGRA: >= 4 * img_w; chroma_pitch is not read.  Any byte
  * alignment of pointers and pitches is taken (a column crop of an RGB frame starts at 3 * x0).  Results are bit for bit those of
  * the same bytes uploaded from the host.
  *
@@ -588,7 +600,8 @@ int  lt_download_overlay_wait(lt_ctx* ctx);
  * The way out that mirrors lt_attach_device_frames: the whole annotated frames of slots -- RGB, dense, in the context's own
  * memory -- are written by a kernel into lt_device_surface destinations in device memory: RGB rows at the caller's pitch, or
  * YUV 4:2:0 as an encoder takes it, NV12 or I420, planes anywhere, any pitch, any byte alignment (16-byte aligned bases and
- * pitches and a width that is a multiple of 16 take the wide kernels).  `layout` is an lt_input_layout -- RGB, NV12 or I420: packed
+ * pitches and a width that is a multiple of 16 take the wide kernels).  `layout` is an lt_input_layout -- RGB, NV12, I420, or BGR /
+ * RGBA / BGRA (the RGB copy with permuted channels, alpha 255): packed
  * 4:2:2 is an input format only, LT_ERR_INVALID here -- and has nothing to do with
  * the context's input format: an RGB camera may feed an NV12 encoder.  RGB -> YUV is OpenCV's integer arithmetic
  * (cv2.cvtColor(img, COLOR_RGB2YUV_I420), 20-bit fixed point, no chroma averaging):

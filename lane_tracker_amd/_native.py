@@ -260,6 +260,10 @@ _SIGNATURES = {
 PIXEL_FORMATS = {"rgb": 0, "nv12": 1, "i420": 2}
 INPUT_FORMATS = dict(PIXEL_FORMATS, yuy2=3, uyvy=4)                # every format a camera frame can have (pixel_format_id)
 PACKED_422 = ("yuy2", "uyvy")                                      # the names INPUT_FORMATS adds
+# ... and the RGB family's other members, as users' own software holds frames: 'bgr' (H, W, 3) -- OpenCV's order --, 'rgba' / 'bgra'
+# (H, W, 4), alpha never read.  A channel permutation, no conversion; camera frames AND sinks (alpha written as 255).  A table of
+# its own: the three above keep their contents.
+RGB_FAMILY = {"bgr": 5, "rgba": 6, "bgra": 7}
 YUV_MATRICES = {"bt601": (1220542, 1673527, -852492, -409993, 2116026),
                 "bt709": (1220542, 1880097, -558891, -223347, 2214593)}
 
@@ -290,7 +294,7 @@ def rgb_to_surfaces(rgb_ptr, frame_stride, img_size, sink, matrix="bt601", devic
     """len(sink) dense RGB frames of `img_size` at device address `rgb_ptr` (a block of lt_device_alloc), `frame_stride` bytes
     apart -> the surfaces of `sink` (a device.DeviceFrames), in its pixel format (lt_rgb_to_surfaces); synchronous."""
     layout = sink_format_id(sink.pixel_format)
-    k = rgb2yuv_coeffs(matrix) if layout else None
+    k = rgb2yuv_coeffs(matrix) if is_yuv(layout) else None
     s = np.ascontiguousarray(sink.surfaces)
     _check(load().lt_rgb_to_surfaces(int(device), C.c_void_p(int(rgb_ptr)), int(frame_stride), int(img_size[1]), int(img_size[0]), s.shape[0],
                                      s.ctypes.data, layout, None if k is None else k.ctypes.data))
@@ -298,16 +302,34 @@ def rgb_to_surfaces(rgb_ptr, frame_stride, img_size, sink, matrix="bt601", devic
 
 def pixel_format_id(pixel_format):
     try:
-        return INPUT_FORMATS[pixel_format]
+        return INPUT_FORMATS[pixel_format] if pixel_format in INPUT_FORMATS else RGB_FAMILY[pixel_format]
     except (KeyError, TypeError):
-        raise ValueError("pixel_format must be 'rgb', 'nv12', 'i420', 'yuy2' or 'uyvy', got %r" % (pixel_format,)) from None
+        raise ValueError("pixel_format must be 'rgb', 'nv12', 'i420', 'yuy2', 'uyvy', 'bgr', 'rgba' or 'bgra', got %r" % (pixel_format,)) from None
+
+
+def format_name(layout):
+    """The name of an lt_input_layout value."""
+    return {v: n for n, v in list(INPUT_FORMATS.items()) + list(RGB_FAMILY.items())}[int(layout)]
+
+
+def is_yuv(layout):
+    """Does an lt_input_layout value name a YUV format (one that is converted with a matrix)?"""
+    return 1 <= int(layout) <= 4
 
 
 def sink_format_id(pixel_format):
     """pixel_format_id for a destination of annotated frames: packed 4:2:2 is an input format only."""
     if pixel_format in PACKED_422:
-        raise ValueError("%r is an input format only: annotated frames go into 'rgb', 'nv12' or 'i420' surfaces" % (pixel_format,))
+        raise ValueError("%r is an input format only: annotated frames go into 'rgb', 'bgr', 'rgba', 'bgra', 'nv12' or 'i420' surfaces" % (pixel_format,))
     return pixel_format_id(pixel_format)
+
+
+def draw_sink_format_id(pixel_format):
+    """sink_format_id for the one-launch draw into sinks (lt_overlay_run_to_surfaces, a LaneTrackerGroup's `out=`): 'rgb', 'nv12' or
+    'i420' only."""
+    if pixel_format in RGB_FAMILY:
+        raise ValueError("a group's out= sink is 'rgb', 'nv12' or 'i420': %r sinks are written by a tracker's process_batch / process_stream" % (pixel_format,))
+    return sink_format_id(pixel_format)
 
 
 def yuv_coeffs(matrix):
@@ -335,6 +357,7 @@ def checked_input_size(input_size, img_size, pixel_format="rgb"):
         raise ValueError("input_size must be 1 .. 16384 pixels wide and high, got %dx%d" % (w, h))
     if (w, h) == (int(img_size[0]), int(img_size[1])):
         return None
+    pixel_format_id(pixel_format)
     if pixel_format != "rgb":
         raise ValueError("input_size resizes RGB frames only: pixel_format=%r frames must come in the calibration's size" % (pixel_format,))
     return w, h
@@ -342,10 +365,14 @@ def checked_input_size(input_size, img_size, pixel_format="rgb"):
 
 def frame_shape(img_size, pixel_format="rgb"):
     """Shape of one camera frame of `img_size` = (width, height) in `pixel_format`: (H, W, 3), (H * 3 // 2, W) for 4:2:0, or
-    (H, W, 2) for packed 4:2:2 (OpenCV's CV_8UC2)."""
+    (H, W, 2) for packed 4:2:2 (OpenCV's CV_8UC2); 'bgr': (H, W, 3), 'rgba' / 'bgra': (H, W, 4)."""
     w, h = int(img_size[0]), int(img_size[1])
     if pixel_format_id(pixel_format) == 0:
         return (h, w, 3)
+    if pixel_format in RGB_FAMILY:
+        if w < 1 or h < 1:
+            raise ValueError("empty %r frames: %dx%d" % (pixel_format, w, h))
+        return (h, w, 3 if pixel_format == "bgr" else 4)
     if pixel_format in PACKED_422:
         if w % 2 or w < 4 or h < 1:
             raise ValueError("4:2:2 frames need an even width of at least 4, got %dx%d" % (w, h))
@@ -353,6 +380,17 @@ def frame_shape(img_size, pixel_format="rgb"):
     if w % 2 or h % 2:
         raise ValueError("4:2:0 frames need an even width and height, got %dx%d" % (w, h))
     return (h * 3 // 2, w)
+
+
+
+def input_frame_shape(img_size, pixel_format="rgb"):
+    """frame_shape for CAMERA frames: a 'bgr' / 'rgba' / 'bgra' camera frame is at least 2 pixels wide (the undistortion fetches the
+    two taps of a row as one window); a sink may be narrower."""
+    tail = frame_shape(img_size, pixel_format)
+    if pixel_format in RGB_FAMILY and int(img_size[0]) < 2:
+        raise ValueError("%r camera frames need a width of at least 2, got %dx%d" % (pixel_format, int(img_size[0]), int(img_size[1])))
+    return tail
+
 
 _lib = None
 
@@ -746,6 +784,7 @@ class Context:
         self._h = h
         self.lib = lib
         self.img_w, self.img_h, self.warp_w, self.warp_h = cal.img_w, cal.img_h, cal.warp_w, cal.warp_h
+        self._pixel_format = "rgb"                       # the camera frames' pixel format (set_input_format)
         self._frame_tail = (cal.img_h, cal.img_w, 3)     # shape of one camera frame as the uploads take it (set_input_format, set_input_size)
         self._input_size = None                          # (width, height) of the frames the uploads take when it is not the calibration's
         self.reserve(capacity)
@@ -782,15 +821,17 @@ class Context:
     def set_input_format(self, pixel_format="rgb", yuv_matrix="bt601"):
         """The pixel format of the camera frames this context takes, once, before its first upload: 'rgb' (the default), or
         'nv12' / 'i420' -- frames of shape (H * 3 // 2, W) as OpenCV holds them -- or packed 4:2:2, 'yuy2' / 'uyvy' -- frames of shape
-        (H, W, 2) -- converted on the device with `yuv_matrix` ('bt601', 'bt709', or five integers).  Every upload method then takes
-        such frames."""
+        (H, W, 2) -- converted on the device with `yuv_matrix` ('bt601', 'bt709', or five integers); or another member of the RGB
+        family, 'bgr' -- (H, W, 3), OpenCV's order -- / 'rgba' / 'bgra' -- (H, W, 4), alpha not read --, a channel permutation
+        (`yuv_matrix` is ignored as for 'rgb').  Every upload method then takes such frames."""
         layout = pixel_format_id(pixel_format)
-        tail = frame_shape((self.img_w, self.img_h), pixel_format)
-        k = yuv_coeffs(yuv_matrix) if layout else None
+        tail = input_frame_shape((self.img_w, self.img_h), pixel_format)
+        k = yuv_coeffs(yuv_matrix) if is_yuv(layout) else None
         if layout and self._input_size is not None:
             raise ValueError("a context with an input size takes RGB frames only: %r frames are not resized" % (pixel_format,))
         _check(self.lib.lt_set_input_format(self._h, layout, None if k is None else k.ctypes.data))
         self._frame_tail = tail
+        self._pixel_format = pixel_format
 
     def set_input_size(self, size):
         """Frames of another size: the uploads take RGB frames (Hi, Wi, 3) of `size` = (Wi, Hi) and resize them on the device to the
@@ -819,14 +860,14 @@ class Context:
         """-> (pixel format name, the five conversion coefficients)."""
         layout, k = C.c_int(0), np.zeros(5, np.int32)
         _check(self.lib.lt_get_input_format(self._h, C.byref(layout), k.ctypes.data))
-        return {v: n for n, v in INPUT_FORMATS.items()}[layout.value], tuple(int(v) for v in k)
+        return format_name(layout.value), tuple(int(v) for v in k)
 
     def _frames(self, frames):
         """`frames` as the C-contiguous u8 block (n,) + one frame's shape; ValueError for frames of another shape."""
         f = _u8(frames)
         tail = self._frame_tail
         if f.shape[-len(tail):] != tail or f.ndim > len(tail) + 1:
-            if tail[-1] == 3 and len(tail) == 3 and self._input_size is None:
+            if self._pixel_format == "rgb" and self._input_size is None:
                 return f.reshape((-1,) + tail)           # (RGB: anything of the right size, as ever)
             raise ValueError("expected camera frames of shape %r, got %r" % (tail, f.shape))
         return f.reshape((-1,) + tail)
@@ -834,7 +875,7 @@ class Context:
     def yuv_to_rgb(self, frame, layout="nv12", matrix="bt601"):
         """One 4:2:0 frame (H * 3 // 2, W), or one packed 4:2:2 frame (H, W, 2), -> RGB (H, W, 3), on the device (lt_yuv_to_rgb)."""
         a = _u8(frame)
-        if pixel_format_id(layout) == 0:
+        if not is_yuv(pixel_format_id(layout)):
             raise ValueError("layout must be 'nv12', 'i420', 'yuy2' or 'uyvy'")
         if layout in PACKED_422:
             if a.ndim != 3 or a.shape[2] != 2 or a.shape[1] % 2 or a.shape[1] < 4 or a.shape[0] < 1:
@@ -920,7 +961,7 @@ class Context:
         unchanged until a call that waits for work launched over these slots afterwards (download_record, sync)."""
         if self._input_size is not None:
             raise ValueError("a context with an input size takes host frames only: frames in device memory are not resized")
-        frames.check_for((self.img_w, self.img_h), "rgb" if self._frame_tail[-1] == 3 and len(self._frame_tail) == 3 else self.input_format()[0])
+        frames.check_for((self.img_w, self.img_h), self._pixel_format)
         frames.wait_for_producer()
         s = np.ascontiguousarray(frames.surfaces)
         _check(self.lib.lt_attach_device_frames(self._h, s.ctypes.data, first, s.shape[0]))
@@ -1104,13 +1145,13 @@ class Context:
 
     def store_overlay_device(self, sink, first=0, matrix="bt601"):
         """Enqueue the whole annotated frames of slots first .. first + len(sink) - 1 into `sink`, a device.DeviceFrames of this
-        context's image size in any pixel format -- RGB at its pitch, or NV12 / I420 converted with `matrix` ('bt601', 'bt709' or
-        eight integers) -- behind the overlay_run / overlay_text that wrote them (lt_overlay_store_device).  Nothing crosses the
+        context's image size in any sink format -- RGB at its pitch, BGR / RGBA / BGRA (permuted, alpha 255), or NV12 / I420 converted
+        with `matrix` ('bt601', 'bt709' or eight integers) -- behind the overlay_run / overlay_text that wrote them (lt_overlay_store_device).  Nothing crosses the
         bus.  The sink's memory is final after store_wait() or sync(); keep it alive until then."""
         if sink.img_size != (self.img_w, self.img_h):
             raise ValueError("expected a sink of %dx%d frames, got %dx%d" % ((self.img_w, self.img_h) + sink.img_size))
         layout = sink_format_id(sink.pixel_format)
-        k = rgb2yuv_coeffs(matrix) if layout else None
+        k = rgb2yuv_coeffs(matrix) if is_yuv(layout) else None
         s = np.ascontiguousarray(sink.surfaces)
         _check(self.lib.lt_overlay_store_device(self._h, int(first), s.shape[0], s.ctypes.data, layout, None if k is None else k.ctypes.data))
         return sink
@@ -1143,7 +1184,7 @@ class Context:
             raise ValueError("expected a sink of %dx%d frames, got %dx%d" % ((self.img_w, self.img_h) + sink.img_size))
         if len(sink) != len(ln):
             raise ValueError("one surface per slot: %d surfaces for %d slots" % (len(sink), len(ln)))
-        layout = sink_format_id(sink.pixel_format)
+        layout = draw_sink_format_id(sink.pixel_format)
         k = rgb2yuv_coeffs(matrix) if layout else None
         s = np.ascontiguousarray(sink.surfaces)
         keep, text = self._text_argument(len(ln), lines, origin, step, line_len)
@@ -1167,6 +1208,8 @@ class Context:
         k = None
         if self.input_format()[0] in PACKED_422:
             raise ValueError("packed 4:2:2 is an input format only: nothing is drawn into such surfaces")
+        if self.input_format()[0] in RGB_FAMILY:
+            raise ValueError("nothing is drawn into 'bgr' / 'rgba' / 'bgra' surfaces in place: such sinks are written by store_overlay_device")
         if pixel_format_id(self.input_format()[0]):
             if matrix is None:
                 raise ValueError("drawing into 4:2:0 surfaces needs an RGB -> YUV matrix ('bt601', 'bt709' or eight integers)")

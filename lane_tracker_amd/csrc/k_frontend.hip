@@ -7,6 +7,9 @@
 //   k_undistort422, k_undistort422_surf, k_undistort422_cal, k_undistort422_cal_surf  the walk over packed 4:2:2 frames (YUY2 / UYVY):
 //                      slots, surfaces, and the table-per-slot forms of both; k_yuv422_rows_to_rgb, k_surf422_rows_to_rgb: their rows
 //                      as RGB (cv2.cvtColor(YUV2RGB_YUY2 / _UYVY)) for whoever shows the camera frame
+//   k_undistort_px, k_undistort_px_surf, k_undistort_px_cal, k_undistort_px_cal_surf  the walk over the RGB family's other members
+//                      (<5> BGR, <6> RGBA, <7> BGRA: a channel permutation, folded into the shifts the walk takes its channels out with);
+//                      k_px_rows_to_rgb, k_surfpx_rows_to_rgb: their rows as RGB for whoever shows the camera frame
 //   k_undistort_cal*, k_warp_cal  the table-per-slot forms of the walk's seven entry points and of the warp: every slot of a launch with
 //                      the remap tables of its own calibration set (lt_add_calibration), for slices that mix sets
 //   k_yuv_rows_to_rgb, k_surf_rows_to_rgb  cv2.cvtColor(YUV2RGB_NV12 / _I420) of a run of rows (for whoever shows the camera
@@ -29,6 +32,7 @@
 // hold them for two frames: one dwordx4 load instead of two dwordx2 loads.
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "front_arith.h"
 #include "lt_internal.h"
@@ -96,10 +100,13 @@ struct TapCols { int cxl, cx0, cx1; };
 
 // RGB interleaved, 3 B/px.  The two taps of a row are 6 consecutive bytes (RGB RGB) at byte 3 * cxl: one 8-byte window per tap
 // row instead of six byte loads.  When sx or sx + 1 is outside the frame the row is fetched from the clamped column and the
-// taps are masked.
-struct Rgb24 {
+// taps are masked.  A format also says at which bit of a decoded tap channel ch (0: R, 1: G, 2: B) lies -- chan(ch), 8 * ch for
+// R G B order; REVERSED: bytes B G R (OpenCV's BGR), chan(ch) = 16 - 8 * ch: another constant in the same shift, no instruction.
+template <bool REVERSED>
+struct Rgb24T {
     typedef uint64_t Window;
     static constexpr int DENSE_PAD = 8;     // a slot's frame buffer is padded by 8 bytes: the window of its last pixel ends there
+    static constexpr int chan(int ch) { return REVERSED ? 16 - 8 * ch : 8 * ch; }
     struct Taps { uint64_t a, b; };          // the windows of the upper (a) and the lower (b) tap row
     int col, sh0, sh1;
     __device__ __forceinline__ void place(const TapCols& c) {
@@ -117,6 +124,37 @@ struct Rgb24 {
         b0 = (uint32_t)(t.b >> sh0), b1 = (uint32_t)(t.b >> sh1);
     }
 };
+typedef Rgb24T<false> Rgb24;
+typedef Rgb24T<true> Bgr24;
+
+// Four bytes a pixel, the fourth (alpha, or padding: RGBx / BGRx) never used.  ORDER 0: R G B A, 1: B G R A.  The two taps of a tap
+// row are the two dwords at byte 4 * cxl (cxl <= W - 2: the window never leaves its row); a tap is the dword of its column, a select.
+// From a slot's staging frame the window is dword-aligned: a plain two-dword fetch.
+template <int ORDER>
+struct Rgb32 {
+    typedef uint64_t Window;
+    static constexpr int DENSE_PAD = 8;
+    static constexpr int chan(int ch) { return ORDER ? 16 - 8 * ch : 8 * ch; }
+    struct Taps { uint64_t a, b; };
+    int col, hi0, hi1;
+    __device__ __forceinline__ void place(const TapCols& c) {
+        col = c.cxl * 4;
+        hi0 = c.cx0 - c.cxl, hi1 = c.cx1 - c.cxl;           // column cx is dword cx - cxl (0 / 1) of the window
+    }
+    __device__ __forceinline__ static PlaneGeom plane(const FrontEndGeom& g, int) { return PlaneGeom{g.img_h, g.img_w * 4, 0u}; }
+    template <class Source>
+    __device__ __forceinline__ Taps fetch(const Source& src, const typename Source::Frame& f, const FrontEndGeom& g, int cy0, int cy1) const {
+        const auto p0 = src.plane(f, plane(g, 0), 0);
+        return Taps{src.dwords2(p0, cy0, col), src.dwords2(p0, cy1, col)};
+    }
+    __device__ __forceinline__ static uint32_t pick(uint64_t w, int hi) { return hi ? (uint32_t)(w >> 32) : (uint32_t)w; }
+    __device__ __forceinline__ void decode(const Taps& t, uint32_t& a0, uint32_t& a1, uint32_t& b0, uint32_t& b1) const {
+        a0 = pick(t.a, hi0), a1 = pick(t.a, hi1);
+        b0 = pick(t.b, hi0), b1 = pick(t.b, hi1);
+    }
+};
+// the formats of layouts 5 (BGR), 6 (RGBA), 7 (BGRA)
+template <int F> using PxFormat = std::conditional_t<F == 5, Bgr24, Rgb32<F == 7 ? 1 : 0>>;
 
 // 4:2:0.  LAYOUT 1: NV12 (Y plane, then rows of U,V pairs), 2: I420 (Y, U, V planes).  Conversion is not linear (the clamps, the
 // shift), so each of the four taps is converted before the blend.  Per tap row: the 4-byte window that holds the two Y samples
@@ -125,6 +163,7 @@ template <int LAYOUT>
 struct Yuv420 {
     typedef uint32_t Window;
     static constexpr int DENSE_PAD = 16;    // a slot's staging frame: 16 bytes of padding behind the last slot
+    static constexpr int chan(int ch) { return 8 * ch; }   // (yuv_pixel: R | G << 8 | B << 16)
     struct Taps { uint32_t ya, yb, ca, cb, va, vb; };      // Y and chroma windows of the upper (a) and lower (b) tap row; va / vb: I420's V
     YuvCoef k;
     int cxl, ccol, ysh0, ysh1, cs0, cs1;
@@ -184,6 +223,7 @@ template <int ORDER>
 struct Yuv422 {
     typedef uint64_t Window;
     static constexpr int DENSE_PAD = 16;    // a slot's staging frame: 16 bytes of padding behind the last slot (the third dword of the last window's aligned load)
+    static constexpr int chan(int ch) { return 8 * ch; }
     struct Taps { uint64_t a, b; };          // the windows of the upper (a) and the lower (b) tap row
     YuvCoef k;
     int last_mp;                             // W / 2 - 2
@@ -239,6 +279,15 @@ struct SlotSource {
             return reinterpret_cast<const Unaligned*>(base + (size_t)(unsigned)pl.f + off)->v;
         }
     }
+    // an 8-byte window at a column that is a multiple of 4 in a plane whose pitch is one too: the two dwords as they lie
+    __device__ __forceinline__ uint64_t dwords2(const Plane& pl, int row, int col) const {
+        if constexpr (ALIGNED4) {
+            const u32x2 d = __builtin_amdgcn_raw_buffer_load_b64(rs, (int)(pl.first + (uint32_t)(__mul24(row, pl.pitch) + col)), pl.f, 0);
+            return (uint64_t)d.x | ((uint64_t)d.y << 32);
+        } else {
+            return window<uint64_t>(pl, row, col);
+        }
+    }
 };
 
 // Frames that lie in the caller's device memory (lt_attach_device_frames): entry first_slot + z of the surface table (device
@@ -269,6 +318,8 @@ struct SurfSource {
     __device__ __forceinline__ W window(const Plane& pl, int row, int col) const {
         return window_at<W>(pl.rs, (uint32_t)(__mul24(row, pl.pitch) + col + pl.rem), 0);
     }
+    // (a surface lies at any byte: nothing is known of the window's alignment)
+    __device__ __forceinline__ uint64_t dwords2(const Plane& pl, int row, int col) const { return window<uint64_t>(pl, row, col); }
 };
 
 // What the kernels below hand to the walk besides their source and format.
@@ -340,8 +391,8 @@ __device__ __forceinline__ void undistort_walk(const WalkArgs& a, Source src, Fo
         uint32_t out = 0;
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
-            const uint32_t v00 = (a0 >> (8 * ch)) & m00, v01 = (a1 >> (8 * ch)) & m01;
-            const uint32_t v10 = (b0 >> (8 * ch)) & m10, v11 = (b1 >> (8 * ch)) & m11;
+            const uint32_t v00 = (a0 >> Format::chan(ch)) & m00, v01 = (a1 >> Format::chan(ch)) & m01;
+            const uint32_t v10 = (b0 >> Format::chan(ch)) & m10, v11 = (b1 >> Format::chan(ch)) & m11;
             // (sum_i w_i p_i + 2^9) >> 10: the same integer as bilerp(); with the 11-bit weights visible every product is a
             // v_mul_u32_u24 / v_mad_u32_u24 (the two-stage form was re-associated into quarter-rate 32- and 64-bit multiplies)
             out |= ((v00 * w00 + v01 * w01 + v10 * w10 + v11 * w11 + 512u) >> 10) << (8 * ch);
@@ -466,6 +517,44 @@ __global__ __launch_bounds__(256) void k_undistort422_cal_surf(const SurfEntry* 
                                                               uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int remap) {
     undistort_walk(WalkArgs{nullptr, nullptr, g, und, und_px, first_slot, n, 1, remap},
                    SurfSource{tab}, Yuv422<ORDER>{k, (g.img_w >> 1) - 2}, SlotTables{sets, &ids});
+}
+
+// ... and those of the RGB family's other members, F = the layout: 5 BGR, 6 RGBA, 7 BGRA.  A slot's staging frame is dword-aligned
+// (lt_set_input_format), so the slot forms are SlotSource<true>'s.
+template <int F>
+__global__ __launch_bounds__(256) void k_undistort_px(const uint8_t* __restrict__ frames, size_t frame_stride,
+                                                     const int16_t* __restrict__ uxy,
+                                                     const uint16_t* __restrict__ ufrac, FrontEndGeom g,
+                                                     uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb,
+                                                     int remap) {
+    undistort_walk(WalkArgs{uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap},
+                   SlotSource<true>{frames, frame_stride}, PxFormat<F>{});
+}
+
+template <int F>
+__global__ __launch_bounds__(256) void k_undistort_px_surf(const SurfEntry* __restrict__ tab,
+                                                          const int16_t* __restrict__ uxy,
+                                                          const uint16_t* __restrict__ ufrac, FrontEndGeom g,
+                                                          uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb,
+                                                          int remap) {
+    undistort_walk(WalkArgs{uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap},
+                   SurfSource{tab}, PxFormat<F>{});
+}
+
+template <int F>
+__global__ __launch_bounds__(256) void k_undistort_px_cal(const uint8_t* __restrict__ frames, size_t frame_stride,
+                                                         const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
+                                                         uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int remap) {
+    undistort_walk(WalkArgs{nullptr, nullptr, g, und, und_px, first_slot, n, 1, remap},
+                   SlotSource<true>{frames, frame_stride}, PxFormat<F>{}, SlotTables{sets, &ids});
+}
+
+template <int F>
+__global__ __launch_bounds__(256) void k_undistort_px_cal_surf(const SurfEntry* __restrict__ tab,
+                                                              const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
+                                                              uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int remap) {
+    undistort_walk(WalkArgs{nullptr, nullptr, g, und, und_px, first_slot, n, 1, remap},
+                   SurfSource{tab}, PxFormat<F>{}, SlotTables{sets, &ids});
 }
 
 // ---- 4:2:0 rows -> RGB rows ---------------------------------------------------------------------------------------------------
@@ -669,6 +758,82 @@ template <int ORDER>
 __global__ __launch_bounds__(256) void k_surf422_rows_to_rgb_any(SurfChunk ch, YuvCoef k, uint8_t* __restrict__ rgb, size_t rgb_stride, int w, int r0) {
     yuv422_row_mp<ORDER>(Plane422{reinterpret_cast<const uint8_t*>(ch.e[blockIdx.z].plane[0]), ch.e[blockIdx.z].pitch}, k,
                          rgb + (size_t)blockIdx.z * rgb_stride, w, r0 + (int)blockIdx.y, (int)(blockIdx.x * blockDim.x + threadIdx.x));
+}
+
+// ---- BGR / RGBA / BGRA rows -> RGB rows ------------------------------------------------------------------------------------------
+// The same role for the RGB family (F = the layout: 5 BGR, 6 RGBA, 7 BGRA): row y of the one plane -> row y of the RGB frame, a
+// permutation of bytes; alpha is not read.
+template <int F>
+struct PxBytes {
+    static constexpr int BPP = F == 5 ? 3 : 4;             // bytes a pixel
+    static constexpr int R = F == 6 ? 0 : 2, B = 2 - R;    // where R and B lie in it (G: byte 1)
+};
+
+// One thread owns the 16 columns from x0 of row y: 48 / 64 bytes in three / four 16-byte loads, 48 bytes in three 16-byte stores.
+template <int F>
+__device__ __forceinline__ void px_row16(const Plane422& s, uint8_t* dst, int w, int y, int x0) {
+    typedef PxBytes<F> P;
+    if (x0 >= w) return;
+    const uint4* in = reinterpret_cast<const uint4*>(s.p + (size_t)y * s.pitch + P::BPP * x0);
+    uint32_t m[4 * P::BPP];
+#pragma unroll
+    for (int i = 0; i < P::BPP; ++i) {
+        const uint4 q = in[i];
+        m[4 * i] = q.x; m[4 * i + 1] = q.y; m[4 * i + 2] = q.z; m[4 * i + 3] = q.w;
+    }
+    auto byte_at = [&](int j) { return (m[j >> 2] >> (8 * (j & 3))) & 255u; };
+    uint32_t d[12];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {                          // four pixels -> three dwords
+        uint32_t px[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int b0 = P::BPP * (4 * j + i);
+            px[i] = byte_at(b0 + P::R) | (byte_at(b0 + 1) << 8) | (byte_at(b0 + P::B) << 16);
+        }
+        d[3 * j] = px[0] | (px[1] << 24);
+        d[3 * j + 1] = (px[1] >> 8) | (px[2] << 16);
+        d[3 * j + 2] = (px[2] >> 16) | (px[3] << 8);
+    }
+    uint4* o = reinterpret_cast<uint4*>(dst + ((size_t)y * w + x0) * 3);
+    o[0] = make_uint4(d[0], d[1], d[2], d[3]);
+    o[1] = make_uint4(d[4], d[5], d[6], d[7]);
+    o[2] = make_uint4(d[8], d[9], d[10], d[11]);
+}
+
+// the same for any width, any pitch and any alignment: one thread per pixel (column x of row y), byte accesses
+template <int F>
+__device__ __forceinline__ void px_row1(const Plane422& s, uint8_t* dst, int w, int y, int x) {
+    typedef PxBytes<F> P;
+    if (x >= w) return;
+    const uint8_t* b = s.p + (size_t)y * s.pitch + (size_t)P::BPP * x;
+    uint8_t* o = dst + ((size_t)y * w + x) * 3;
+    o[0] = b[P::R];
+    o[1] = b[1];
+    o[2] = b[P::B];
+}
+
+// rows [r0, r0 + gridDim.y) of the slots' dense staging frames (frame blockIdx.z at px + blockIdx.z * px_stride) ...
+template <int F>
+__global__ __launch_bounds__(256) void k_px_rows_to_rgb(const uint8_t* __restrict__ px, size_t px_stride, uint8_t* __restrict__ rgb, size_t rgb_stride, int w, int r0) {
+    px_row16<F>(Plane422{px + (size_t)blockIdx.z * px_stride, PxBytes<F>::BPP * w}, rgb + (size_t)blockIdx.z * rgb_stride, w,
+                r0 + (int)blockIdx.y, (int)(blockIdx.x * blockDim.x + threadIdx.x) * 16);
+}
+template <int F>
+__global__ __launch_bounds__(256) void k_px_rows_to_rgb_any(const uint8_t* __restrict__ px, size_t px_stride, uint8_t* __restrict__ rgb, size_t rgb_stride, int w, int r0) {
+    px_row1<F>(Plane422{px + (size_t)blockIdx.z * px_stride, PxBytes<F>::BPP * w}, rgb + (size_t)blockIdx.z * rgb_stride, w,
+               r0 + (int)blockIdx.y, (int)(blockIdx.x * blockDim.x + threadIdx.x));
+}
+// ... and of surfaces (frame blockIdx.z is entry blockIdx.z of the chunk)
+template <int F>
+__global__ __launch_bounds__(256) void k_surfpx_rows_to_rgb(SurfChunk ch, uint8_t* __restrict__ rgb, size_t rgb_stride, int w, int r0) {
+    px_row16<F>(Plane422{reinterpret_cast<const uint8_t*>(ch.e[blockIdx.z].plane[0]), ch.e[blockIdx.z].pitch},
+                rgb + (size_t)blockIdx.z * rgb_stride, w, r0 + (int)blockIdx.y, (int)(blockIdx.x * blockDim.x + threadIdx.x) * 16);
+}
+template <int F>
+__global__ __launch_bounds__(256) void k_surfpx_rows_to_rgb_any(SurfChunk ch, uint8_t* __restrict__ rgb, size_t rgb_stride, int w, int r0) {
+    px_row1<F>(Plane422{reinterpret_cast<const uint8_t*>(ch.e[blockIdx.z].plane[0]), ch.e[blockIdx.z].pitch},
+               rgb + (size_t)blockIdx.z * rgb_stride, w, r0 + (int)blockIdx.y, (int)(blockIdx.x * blockDim.x + threadIdx.x));
 }
 
 // Rows [r0, r1) of RGB surfaces -> the same rows of the slots' camera frames (row_bytes = 3 w, dense): a pitched row copy, one
@@ -1096,7 +1261,10 @@ void launch_undistort_rows(hipStream_t s, FrameSource src, int layout, YuvCoef k
         else if (layout == 1) hipLaunchKernelGGL(k_undistort_rows_yuv_surf<1>, grid, block, 0, s, src.tab, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
         else if (layout == 2) hipLaunchKernelGGL(k_undistort_rows_yuv_surf<2>, grid, block, 0, s, src.tab, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
         else if (layout == 3) hipLaunchKernelGGL(k_undistort422_surf<0>, grid, block, 0, s, src.tab, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
-        else hipLaunchKernelGGL(k_undistort422_surf<1>, grid, block, 0, s, src.tab, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
+        else if (layout == 4) hipLaunchKernelGGL(k_undistort422_surf<1>, grid, block, 0, s, src.tab, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
+        else if (layout == 5) hipLaunchKernelGGL(k_undistort_px_surf<5>, grid, block, 0, s, src.tab, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
+        else if (layout == 6) hipLaunchKernelGGL(k_undistort_px_surf<6>, grid, block, 0, s, src.tab, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
+        else hipLaunchKernelGGL(k_undistort_px_surf<7>, grid, block, 0, s, src.tab, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
     } else if (layout == 0) {
         static const bool unaligned = [] { const char* e = LT_EXP_ENV("LT_UNDISTORT_UNALIGNED"); return e && e[0] == '1'; }();   // A/B
         if (!unaligned && ((uintptr_t)src.frames & 3) == 0 && (src.stride & 3) == 0 && src.stride < (1u << 30))   // (a larger frame: 64-bit addresses)
@@ -1109,8 +1277,14 @@ void launch_undistort_rows(hipStream_t s, FrameSource src, int layout, YuvCoef k
         hipLaunchKernelGGL(k_undistort_rows_yuv<2>, grid, block, 0, s, src.frames, src.stride, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
     } else if (layout == 3) {
         hipLaunchKernelGGL(k_undistort422<0>, grid, block, 0, s, src.frames, src.stride, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
-    } else {
+    } else if (layout == 4) {
         hipLaunchKernelGGL(k_undistort422<1>, grid, block, 0, s, src.frames, src.stride, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
+    } else if (layout == 5) {
+        hipLaunchKernelGGL(k_undistort_px<5>, grid, block, 0, s, src.frames, src.stride, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
+    } else if (layout == 6) {
+        hipLaunchKernelGGL(k_undistort_px<6>, grid, block, 0, s, src.frames, src.stride, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
+    } else {
+        hipLaunchKernelGGL(k_undistort_px<7>, grid, block, 0, s, src.frames, src.stride, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
     }
 }
 
@@ -1135,9 +1309,28 @@ static void launch_rows422_to_rgb(hipStream_t s, int layout, K wide0, K wide1, K
         hipLaunchKernelGGL(layout == 3 ? any0 : any1, dim3((unsigned)((w / 2 + 255) / 256), rows, (unsigned)n), dim3(256), 0, s, args...);
 }
 
+// The RGB family's row conversion of n frames (layout 5 BGR, 6 RGBA, 7 BGRA): one launch row per frame row; wide[] / any[]: the
+// 16-column and the byte-wise kernels of the three layouts.
+template <class K, class... Args>
+static void launch_rows_px_to_rgb(hipStream_t s, int layout, const K (&wide)[3], const K (&any)[3], size_t bits, int w, int r0, int r1, int n, Args... args) {
+    const unsigned rows = (unsigned)(r1 - r0);
+    if ((w & 15) == 0 && (bits & 15) == 0)
+        hipLaunchKernelGGL(wide[layout - 5], dim3((unsigned)((w / 16 + 63) / 64), rows, (unsigned)n), dim3(64), 0, s, args...);
+    else
+        hipLaunchKernelGGL(any[layout - 5], dim3((unsigned)((w + 255) / 256), rows, (unsigned)n), dim3(256), 0, s, args...);
+}
+
 void launch_yuv_rows_to_rgb(hipStream_t s, int layout, const uint8_t* yuv, size_t yuv_stride, YuvCoef k, uint8_t* rgb,
                             size_t rgb_stride, int h, int w, int r0, int r1, int n) {
     if (n <= 0 || r1 <= r0) return;
+    if (layout >= 5) {
+        typedef void (*K)(const uint8_t*, size_t, uint8_t*, size_t, int, int);
+        static const K wide[3] = {k_px_rows_to_rgb<5>, k_px_rows_to_rgb<6>, k_px_rows_to_rgb<7>};
+        static const K any[3] = {k_px_rows_to_rgb_any<5>, k_px_rows_to_rgb_any<6>, k_px_rows_to_rgb_any<7>};
+        launch_rows_px_to_rgb(s, layout, wide, any, yuv_stride | rgb_stride | (size_t)(uintptr_t)yuv | (size_t)(uintptr_t)rgb, w, r0, r1, n,
+                              yuv, yuv_stride, rgb, rgb_stride, w, r0);
+        return;
+    }
     if (layout >= 3) {
         launch_rows422_to_rgb(s, layout, k_yuv422_rows_to_rgb<0>, k_yuv422_rows_to_rgb<1>, k_yuv422_rows_to_rgb_any<0>, k_yuv422_rows_to_rgb_any<1>,
                               yuv_stride | rgb_stride | (size_t)(uintptr_t)yuv | (size_t)(uintptr_t)rgb, w, r0, r1, n,
@@ -1178,6 +1371,11 @@ void launch_surf_rows_to_rgb(hipStream_t s, int layout, const SurfEntry* entries
                 hipLaunchKernelGGL(k_surf_copy_rows<true>, dim3((unsigned)((row_bytes / 16 + 255) / 256), (unsigned)(r1 - r0), (unsigned)m), dim3(256), 0, s, ch, dst, rgb_stride, row_bytes, r0);
             else
                 hipLaunchKernelGGL(k_surf_copy_rows<false>, dim3((unsigned)((row_bytes + 255) / 256), (unsigned)(r1 - r0), (unsigned)m), dim3(256), 0, s, ch, dst, rgb_stride, row_bytes, r0);
+        } else if (layout >= 5) {
+            typedef void (*K)(SurfChunk, uint8_t*, size_t, int, int);
+            static const K wide[3] = {k_surfpx_rows_to_rgb<5>, k_surfpx_rows_to_rgb<6>, k_surfpx_rows_to_rgb<7>};
+            static const K any[3] = {k_surfpx_rows_to_rgb_any<5>, k_surfpx_rows_to_rgb_any<6>, k_surfpx_rows_to_rgb_any<7>};
+            launch_rows_px_to_rgb(s, layout, wide, any, bits, w, r0, r1, m, ch, dst, rgb_stride, w, r0);
         } else if (layout >= 3) {
             launch_rows422_to_rgb(s, layout, k_surf422_rows_to_rgb<0>, k_surf422_rows_to_rgb<1>, k_surf422_rows_to_rgb_any<0>, k_surf422_rows_to_rgb_any<1>,
                                   bits, w, r0, r1, m, ch, k, dst, rgb_stride, w, r0);
@@ -1226,7 +1424,10 @@ void launch_undistort_cal(hipStream_t s, FrameSource src, int layout, YuvCoef k,
             else if (layout == 1) hipLaunchKernelGGL(k_undistort_cal_yuv_surf<1>, grid, block, 0, s, src.tab, k, sets, ci, g, und, und_px, fs, m, remap);
             else if (layout == 2) hipLaunchKernelGGL(k_undistort_cal_yuv_surf<2>, grid, block, 0, s, src.tab, k, sets, ci, g, und, und_px, fs, m, remap);
             else if (layout == 3) hipLaunchKernelGGL(k_undistort422_cal_surf<0>, grid, block, 0, s, src.tab, k, sets, ci, g, und, und_px, fs, m, remap);
-            else hipLaunchKernelGGL(k_undistort422_cal_surf<1>, grid, block, 0, s, src.tab, k, sets, ci, g, und, und_px, fs, m, remap);
+            else if (layout == 4) hipLaunchKernelGGL(k_undistort422_cal_surf<1>, grid, block, 0, s, src.tab, k, sets, ci, g, und, und_px, fs, m, remap);
+            else if (layout == 5) hipLaunchKernelGGL(k_undistort_px_cal_surf<5>, grid, block, 0, s, src.tab, sets, ci, g, und, und_px, fs, m, remap);
+            else if (layout == 6) hipLaunchKernelGGL(k_undistort_px_cal_surf<6>, grid, block, 0, s, src.tab, sets, ci, g, und, und_px, fs, m, remap);
+            else hipLaunchKernelGGL(k_undistort_px_cal_surf<7>, grid, block, 0, s, src.tab, sets, ci, g, und, und_px, fs, m, remap);
         } else if (layout == 0) {
             if (((uintptr_t)frames & 3) == 0 && (src.stride & 3) == 0 && src.stride < (1u << 30))
                 hipLaunchKernelGGL(k_undistort_cal<true>, grid, block, 0, s, frames, src.stride, sets, ci, g, und, und_px, fs, m, remap);
@@ -1238,8 +1439,14 @@ void launch_undistort_cal(hipStream_t s, FrameSource src, int layout, YuvCoef k,
             hipLaunchKernelGGL(k_undistort_cal_yuv<2>, grid, block, 0, s, frames, src.stride, k, sets, ci, g, und, und_px, fs, m, remap);
         } else if (layout == 3) {
             hipLaunchKernelGGL(k_undistort422_cal<0>, grid, block, 0, s, frames, src.stride, k, sets, ci, g, und, und_px, fs, m, remap);
-        } else {
+        } else if (layout == 4) {
             hipLaunchKernelGGL(k_undistort422_cal<1>, grid, block, 0, s, frames, src.stride, k, sets, ci, g, und, und_px, fs, m, remap);
+        } else if (layout == 5) {
+            hipLaunchKernelGGL(k_undistort_px_cal<5>, grid, block, 0, s, frames, src.stride, sets, ci, g, und, und_px, fs, m, remap);
+        } else if (layout == 6) {
+            hipLaunchKernelGGL(k_undistort_px_cal<6>, grid, block, 0, s, frames, src.stride, sets, ci, g, und, und_px, fs, m, remap);
+        } else {
+            hipLaunchKernelGGL(k_undistort_px_cal<7>, grid, block, 0, s, frames, src.stride, sets, ci, g, und, und_px, fs, m, remap);
         }
     }
 }

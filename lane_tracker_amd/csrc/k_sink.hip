@@ -1,5 +1,6 @@
 // Device sinks: dense RGB frames of the library (the annotated frames of a context, d_annot) -> surfaces the caller owns, in the
-// caller's pixel format and pitches -- RGB (a pitched row copy), NV12 or I420 (sink_arith.h: OpenCV's RGB2YUV_I420 arithmetic,
+// caller's pixel format and pitches -- RGB (a pitched row copy), BGR / RGBA / BGRA (the same copy with permuted channels, alpha
+// written as 255), NV12 or I420 (sink_arith.h: OpenCV's RGB2YUV_I420 arithmetic,
 // chroma from the pixel at the even row and even column of each 2 x 2 block).  The mirror image of k_surf_rows_to_rgb /
 // k_surf_copy_rows (k_frontend.hip).  The destinations of a launch travel as a SurfChunk kernel argument (frame blockIdx.z is
 // entry blockIdx.z).
@@ -116,11 +117,57 @@ __global__ __launch_bounds__(256) void k_rgb_copy_rows_to_surf(const uint8_t* __
     else *dst = *src;
 }
 
+// The RGB family's other members (F = the layout: 5 BGR, 6 RGBA, 7 BGRA): the pitched copy above with the channels permuted and,
+// for the 4-byte pixels, alpha = 255.  WIDE (w a multiple of 16, every base and pitch of the launch one too): one thread per 16
+// pixels, 48 bytes in three 16-byte loads, 48 / 64 bytes in three / four 16-byte stores; else one thread per pixel, byte stores.
+template <int F, bool WIDE>
+__global__ __launch_bounds__(256) void k_rgb_rows_to_px(const uint8_t* __restrict__ rgb, size_t rgb_stride, SurfChunk ch, int w) {
+    constexpr int BPP = F == 5 ? 3 : 4, R = F == 6 ? 0 : 2, B = 2 - R;
+    const int x = (int)(blockIdx.x * 256u + threadIdx.x) * (WIDE ? 16 : 1);
+    if (x >= w) return;
+    const int y = (int)blockIdx.y;
+    const SurfEntry& e = ch.e[blockIdx.z];
+    const uint8_t* src = rgb + (size_t)blockIdx.z * rgb_stride + ((size_t)y * w + x) * 3;
+    uint8_t* dst = reinterpret_cast<uint8_t*>(e.plane[0]) + (size_t)y * e.pitch + (size_t)x * BPP;
+    if constexpr (WIDE) {
+        const uint4* s = reinterpret_cast<const uint4*>(src);
+        const uint4 q0 = s[0], q1 = s[1], q2 = s[2];
+        const uint32_t d[12] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w};
+        uint32_t o[4 * BPP] = {};
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const uint32_t c[3] = {(d[(3 * i) >> 2] >> (8 * ((3 * i) & 3))) & 255u, (d[(3 * i + 1) >> 2] >> (8 * ((3 * i + 1) & 3))) & 255u,
+                                   (d[(3 * i + 2) >> 2] >> (8 * ((3 * i + 2) & 3))) & 255u};
+            const int b0 = BPP * i;
+            o[(b0 + R) >> 2] |= c[0] << (8 * ((b0 + R) & 3));
+            o[(b0 + 1) >> 2] |= c[1] << (8 * ((b0 + 1) & 3));
+            o[(b0 + B) >> 2] |= c[2] << (8 * ((b0 + B) & 3));
+            if constexpr (BPP == 4) o[i] |= 255u << 24;
+        }
+        uint4* out = reinterpret_cast<uint4*>(dst);
+#pragma unroll
+        for (int i = 0; i < BPP; ++i) out[i] = make_uint4(o[4 * i], o[4 * i + 1], o[4 * i + 2], o[4 * i + 3]);
+    } else {
+        dst[R] = src[0];
+        dst[1] = src[1];
+        dst[B] = src[2];
+        if constexpr (BPP == 4) dst[3] = 255;
+    }
+}
+
+template <int F>
+static void launch_rgb_rows_to_px(hipStream_t s, bool wide, const uint8_t* src, size_t rgb_stride, const SurfChunk& ch, int h, int w, int m) {
+    if (wide)
+        hipLaunchKernelGGL((k_rgb_rows_to_px<F, true>), dim3((unsigned)((w / 16 + 255) / 256), (unsigned)h, (unsigned)m), dim3(256), 0, s, src, rgb_stride, ch, w);
+    else
+        hipLaunchKernelGGL((k_rgb_rows_to_px<F, false>), dim3((unsigned)((w + 255) / 256), (unsigned)h, (unsigned)m), dim3(256), 0, s, src, rgb_stride, ch, w);
+}
+
 // n frames -> entries[0, n) (host memory, consumed before the call returns); the wide kernels where a launch's geometry allows them
 void launch_rgb_to_surfaces(hipStream_t s, int layout, const uint8_t* rgb, size_t rgb_stride, int h, int w, const SurfEntry* entries,
                             int n, const int32_t* coeffs) {
     if (n <= 0 || h <= 0 || w <= 0) return;
-    const Rgb2Yuv k = layout != 0 ? sa::coef_of(coeffs) : Rgb2Yuv{};
+    const Rgb2Yuv k = layout == 1 || layout == 2 ? sa::coef_of(coeffs) : Rgb2Yuv{};
     for (int i = 0; i < n; i += SurfChunk::N) {
         const int m = std::min(n - i, (int)SurfChunk::N);
         SurfChunk ch{};
@@ -138,6 +185,11 @@ void launch_rgb_to_surfaces(hipStream_t s, int layout, const uint8_t* rgb, size_
                 hipLaunchKernelGGL(k_rgb_copy_rows_to_surf<true>, dim3((unsigned)((row_bytes / 16 + 255) / 256), (unsigned)h, (unsigned)m), dim3(256), 0, s, src, rgb_stride, ch, row_bytes);
             else
                 hipLaunchKernelGGL(k_rgb_copy_rows_to_surf<false>, dim3((unsigned)((row_bytes + 255) / 256), (unsigned)h, (unsigned)m), dim3(256), 0, s, src, rgb_stride, ch, row_bytes);
+        } else if (layout >= 5) {
+            const bool wide = (w & 15) == 0 && (bits & 15) == 0;
+            if (layout == 5) launch_rgb_rows_to_px<5>(s, wide, src, rgb_stride, ch, h, w, m);
+            else if (layout == 6) launch_rgb_rows_to_px<6>(s, wide, src, rgb_stride, ch, h, w, m);
+            else launch_rgb_rows_to_px<7>(s, wide, src, rgb_stride, ch, h, w, m);
         } else if ((w & 15) == 0 && (bits & 15) == 0 && (cbits & 7) == 0) {
             const int groups = w / 16, items = (h / 2) * groups;
             hipLaunchKernelGGL(layout == 1 ? k_rgb_rows_to_surf<1> : k_rgb_rows_to_surf<2>, dim3((unsigned)((items + 255) / 256), 1, (unsigned)m), dim3(256), 0, s,

@@ -855,7 +855,7 @@ int lt_set_streams(lt_ctx* c, int nstreams) {
 static inline bool is_422(int layout) { return layout == LT_INPUT_YUY2 || layout == LT_INPUT_UYVY; }
 static int check_yuv_format(int layout, const int32_t* k, int h, int w) {
     if (layout != LT_INPUT_NV12 && layout != LT_INPUT_I420 && !is_422(layout))
-        return fail(LT_ERR_INVALID, "input layout must be RGB (0), NV12 (1), I420 (2), YUY2 (3) or UYVY (4)");
+        return fail(LT_ERR_INVALID, "input layout must be RGB (0), NV12 (1), I420 (2), YUY2 (3), UYVY (4), BGR (5), RGBA (6) or BGRA (7)");
     if (!k) return fail(LT_ERR_INVALID, "a YUV layout needs its five conversion coefficients");
     if (is_422(layout)) {
         // (two macropixels a row at the least: the 8-byte window of a tap row lies inside its row)
@@ -873,19 +873,24 @@ static int check_yuv_format(int layout, const int32_t* k, int h, int w) {
 int lt_set_input_format(lt_ctx* c, int layout, const int32_t* coeffs) {
     if (!c) return fail(LT_ERR_INVALID, "null context");
     int rc;
-    if (layout != LT_INPUT_RGB && (rc = check_yuv_format(layout, coeffs, c->calib.img_h, c->calib.img_w))) return rc;
-    const bool same = layout == c->in_layout && (layout == LT_INPUT_RGB || std::memcmp(coeffs, c->yuv_coef, sizeof c->yuv_coef) == 0);
+    const bool plain = layout == LT_INPUT_RGB || is_rgb_family(layout);      // no conversion: `coeffs` is not read
+    if (is_rgb_family(layout)) {
+        // (the 8-byte window of a tap row starts at column min(x, W - 2): two pixels a row at the least)
+        if (c->calib.img_w < 2) return fail(LT_ERR_INVALID, "BGR / RGBA / BGRA frames need a width of at least 2, got %dx%d", c->calib.img_w, c->calib.img_h);
+    } else if (layout != LT_INPUT_RGB && (rc = check_yuv_format(layout, coeffs, c->calib.img_h, c->calib.img_w))) return rc;
+    const bool same = layout == c->in_layout && (plain || std::memcmp(coeffs, c->yuv_coef, sizeof c->yuv_coef) == 0);
     if (same) return LT_OK;
     if (c->input_locked) return fail(LT_ERR_STATE, "the input format of a context cannot change after its first upload");
     if (layout != LT_INPUT_RGB && c->src_w > 0)
-        return fail(LT_ERR_STATE, "a context with an input size (lt_set_input_size) takes RGB frames only: YUV frames are not resized");
+        return fail(LT_ERR_STATE, "a context with an input size (lt_set_input_size) takes RGB frames only: frames of another format are not resized");
     if ((rc = set_device(c))) return rc;
     if ((rc = sync_all(c))) return rc;
     if (layout == LT_INPUT_RGB) {
         dev_free(c->d_yuv);
     } else {
-        // the staging frame of a slot: h w 3 / 2 bytes (4:2:0) or h w 2 (4:2:2), slots a multiple of 16 apart
-        const size_t bytes = is_422(layout) ? c->frame_bytes / 3 * 2 : c->frame_bytes / 2, stride = (bytes + 15) & ~(size_t)15;
+        // the staging frame of a slot: h w 3 / 2 bytes (4:2:0), h w 2 (4:2:2), h w 3 (BGR) or h w 4 (RGBA / BGRA), slots a multiple of
+        // 16 apart
+        const size_t bytes = packed_bpp(layout) ? c->frame_bytes / 3 * (size_t)packed_bpp(layout) : c->frame_bytes / 2, stride = (bytes + 15) & ~(size_t)15;
         if (stride != c->yuv_stride) dev_free(c->d_yuv);
         c->yuv_bytes = bytes;
         c->yuv_stride = stride;
@@ -893,7 +898,7 @@ int lt_set_input_format(lt_ctx* c, int layout, const int32_t* coeffs) {
             c->in_layout = LT_INPUT_RGB;     // (no staging: the context falls back to what needs none)
             return rc;
         }
-        std::memcpy(c->yuv_coef, coeffs, sizeof c->yuv_coef);
+        if (!plain) std::memcpy(c->yuv_coef, coeffs, sizeof c->yuv_coef);
     }
     c->in_layout = layout;
     return LT_OK;
@@ -916,8 +921,8 @@ static int yuv_copy(lt_ctx* c, const uint8_t* frames, int first, int n, int r0, 
         return (int)LT_OK;
     };
     int rc = LT_OK;
-    if (is_422(c->in_layout))            // one plane of 2 W bytes a row: its rows [r0, r1); no chroma rows
-        return r1 > r0 ? piece((size_t)r0 * 2 * W, (size_t)(r1 - r0) * 2 * W) : rc;
+    if (const size_t bpp = (size_t)packed_bpp(c->in_layout))   // one plane of 2 W (4:2:2), 3 W (BGR) or 4 W (RGBA / BGRA) bytes a row: its rows [r0, r1); no chroma rows
+        return r1 > r0 ? piece((size_t)r0 * bpp * W, (size_t)(r1 - r0) * bpp * W) : rc;
     if (r1 > r0 && c1 > c0 && r0 == 0 && r1 == c->calib.img_h && c0 == 0 && c1 == c->calib.img_h / 2) return piece(0, c->yuv_bytes);
     if (r1 > r0 && (rc = piece((size_t)r0 * W, (size_t)(r1 - r0) * W))) return rc;
     if (c1 <= c0) return rc;
@@ -977,7 +982,7 @@ int lt_set_input_size(lt_ctx* c, int src_w, int src_h) {
     const bool plain = src_w == W && src_h == H;
     if (plain ? !resizes(c) : (src_w == c->src_w && src_h == c->src_h)) return LT_OK;
     if (c->input_locked) return fail(LT_ERR_STATE, "the input size of a context cannot change after its first upload");
-    if (c->in_layout != LT_INPUT_RGB) return fail(LT_ERR_STATE, "an input size needs RGB frames: this context's input format is a YUV layout");
+    if (c->in_layout != LT_INPUT_RGB) return fail(LT_ERR_STATE, "an input size needs RGB frames: this context's input format is another layout");
     int rc = set_device(c);
     if (rc) return rc;
     if ((rc = sync_all(c))) return rc;
@@ -1502,7 +1507,7 @@ extern "C" {
 namespace {
 int check_surfaces(lt_ctx* c, const lt_device_surface* s, int n, SurfEntry* out) {
     const int H = c->calib.img_h, W = c->calib.img_w, layout = c->in_layout;
-    const int row = layout == LT_INPUT_RGB ? 3 * W : is_422(layout) ? 2 * W : W, crow = layout == LT_INPUT_NV12 ? W : W / 2;
+    const int row = packed_bpp(layout) ? packed_bpp(layout) * W : W, crow = layout == LT_INPUT_NV12 ? W : W / 2;
     constexpr int PITCH_MAX = (1 << 23) - 1;             // the kernels multiply rows and pitches with 24-bit instructions
     KnownRange memo;
     for (int k = 0; k < n; ++k) {
@@ -1514,7 +1519,7 @@ int check_surfaces(lt_ctx* c, const lt_device_surface* s, int n, SurfEntry* out)
         int rc = check_plane(c->device, f.plane[0], ext, k, 0, memo);
         if (rc) return rc;
         out[k] = SurfEntry{{(uint64_t)(uintptr_t)f.plane[0], 0, 0}, f.pitch, 0};
-        if (layout == LT_INPUT_RGB || is_422(layout)) continue;      // one plane; chroma_pitch is not read
+        if (packed_bpp(layout)) continue;                            // one plane; chroma_pitch is not read
         if (f.chroma_pitch < crow) return fail(LT_ERR_INVALID, "surface %d: chroma pitch %d is below the row's %d bytes", k, (int)f.chroma_pitch, crow);
         if (f.chroma_pitch > PITCH_MAX) return fail(LT_ERR_INVALID, "surface %d: chroma pitch %d is too large", k, (int)f.chroma_pitch);
         const size_t cext = (size_t)f.chroma_pitch * (size_t)(H / 2 - 1) + (size_t)crow;

@@ -88,7 +88,7 @@ struct FrameSource {
     static FrameSource slots(const uint8_t* frames, size_t stride) { return FrameSource{nullptr, frames, stride}; }
     static FrameSource surfaces(const SurfEntry* tab) { return FrameSource{tab, nullptr, 0}; }
 };
-// the undistorted rows of n frames (layout 0 = RGB, 1 = NV12, 2 = I420, 3 = YUY2, 4 = UYVY; `k` is read for the YUV layouts only: every tap converted, then the
+// the undistorted rows of n frames (layout 0 = RGB, 1 = NV12, 2 = I420, 3 = YUY2, 4 = UYVY, 5 = BGR, 6 = RGBA, 7 = BGRA; `k` is read for the YUV layouts only: every tap converted, then the
 // same blend); `und` is the base of the whole buffer, `first_slot` the absolute slot of frame 0 of the call
 void launch_undistort_rows(hipStream_t s, FrameSource src, int layout, YuvCoef k, const int16_t* uxy, const uint16_t* ufrac,
                            FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n);

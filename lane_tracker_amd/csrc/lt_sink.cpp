@@ -1,5 +1,5 @@
 // Device sinks of liblane_tracker_amd.so: dense RGB frames of the library -- the annotated frames of a context, or any block of
-// lt_device_alloc -- written into surfaces the caller owns, RGB, NV12 or I420 at the caller's pitches (k_sink.hip).  The way out
+// lt_device_alloc -- written into surfaces the caller owns, RGB, BGR, RGBA, BGRA, NV12 or I420 at the caller's pitches (k_sink.hip).  The way out
 // that mirrors lt_attach_device_frames: a pipeline of decoder, lane tracker and encoder never crosses the bus with a frame.
 // Everything is checked on the host before anything is launched; a refused call leaves the context as it was.
 #include <algorithm>
@@ -17,16 +17,16 @@ struct ByteRange { uintptr_t lo, hi; int surface, plane; };   // [lo, hi)
 
 // (rows, row bytes) of plane i of an h x w frame in `layout`
 inline void plane_geom(int layout, int h, int w, int i, int* rows, int* row_bytes) {
-    if (i == 0) { *rows = h; *row_bytes = layout == LT_INPUT_RGB ? 3 * w : layout >= LT_INPUT_YUY2 ? 2 * w : w; }   // (4:2:2: an attached camera surface only)
+    if (i == 0) { *rows = h; *row_bytes = packed_bpp(layout) ? packed_bpp(layout) * w : w; }   // (4:2:2: an attached camera surface only)
     else { *rows = h / 2; *row_bytes = layout == LT_INPUT_NV12 ? w : w / 2; }
 }
-inline int plane_count(int layout) { return layout == LT_INPUT_RGB || layout >= LT_INPUT_YUY2 ? 1 : layout + 1; }
+inline int plane_count(int layout) { return packed_bpp(layout) ? 1 : layout + 1; }
 
 int check_format(int layout, int h, int w, const int32_t* coeffs) {
-    if (layout != LT_INPUT_RGB && layout != LT_INPUT_NV12 && layout != LT_INPUT_I420)
-        return fail(LT_ERR_INVALID, "sink layout must be RGB (0), NV12 (1) or I420 (2): packed 4:2:2 is an input format only");
+    if (layout != LT_INPUT_RGB && layout != LT_INPUT_NV12 && layout != LT_INPUT_I420 && !is_rgb_family(layout))
+        return fail(LT_ERR_INVALID, "sink layout must be RGB (0), NV12 (1), I420 (2), BGR (5), RGBA (6) or BGRA (7): packed 4:2:2 is an input format only");
     if (h < 1 || w < 1 || h > 16384 || w > 16384) return fail(LT_ERR_INVALID, "bad image size %dx%d (at most 16384 x 16384)", w, h);
-    if (layout == LT_INPUT_RGB) return LT_OK;
+    if (layout == LT_INPUT_RGB || is_rgb_family(layout)) return LT_OK;
     if ((h & 1) || (w & 1)) return fail(LT_ERR_INVALID, "4:2:0 surfaces need an even width and height, got %dx%d", w, h);
     if (!coeffs) return fail(LT_ERR_INVALID, "a 4:2:0 sink needs its eight conversion coefficients");
     if (!sa::coeffs_ok(coeffs))
@@ -59,7 +59,7 @@ int check_sinks(int device, const lt_device_surface* dst, int n, int layout, int
             ranges.push_back(ByteRange{(uintptr_t)f.plane[i], (uintptr_t)f.plane[i] + ext, k, i});
         }
         ent[(size_t)k].pitch = f.pitch;
-        ent[(size_t)k].cpitch = layout == LT_INPUT_RGB ? 0 : f.chroma_pitch;
+        ent[(size_t)k].cpitch = planes == 1 ? 0 : f.chroma_pitch;
     }
     std::sort(ranges.begin(), ranges.end(), [](const ByteRange& a, const ByteRange& b) { return a.lo < b.lo; });
     for (size_t j = 1; j < ranges.size(); ++j)
@@ -79,7 +79,11 @@ const ByteRange* overlapping(const std::vector<ByteRange>& ranges, uintptr_t lo,
 
 namespace lt {
 
-int check_sink_format(int layout, int h, int w, const int32_t* coeffs) { return check_format(layout, h, w, coeffs); }
+// (the one-launch draw of lt_overlay_run_to_surfaces, k_draw_sink.hip: RGB, NV12 and I420 only)
+int check_sink_format(int layout, int h, int w, const int32_t* coeffs) {
+    if (is_rgb_family(layout)) return fail(LT_ERR_INVALID, "lt_overlay_run_to_surfaces draws into RGB (0), NV12 (1) or I420 (2) surfaces: BGR / RGBA / BGRA sinks take lt_overlay_store_device");
+    return check_format(layout, h, w, coeffs);
+}
 
 int check_ctx_sinks(lt_ctx* c, const lt_device_surface* dst, int n, int layout, std::vector<SurfEntry>& ent) {
     const int H = c->calib.img_h, W = c->calib.img_w;

@@ -81,19 +81,22 @@ def _plane_rows(img_size, pixel_format):
     w, h = int(img_size[0]), int(img_size[1])
     layout = pixel_format_id(pixel_format)
     frame_shape((w, h), pixel_format)                    # (ValueError for odd 4:2:0 sizes)
-    if layout == 0:
-        return (h, 3 * w), None, 1
-    if layout >= 3:                                      # packed 4:2:2: one plane of 2 W bytes a row
-        return (h, 2 * w), None, 1
+    bpp = _PIXEL_BYTES.get(layout)
+    if bpp:                                              # one plane of whole pixels: 3 W (RGB, BGR), 2 W (packed 4:2:2) or 4 W (RGBA, BGRA) bytes a row
+        return (h, bpp * w), None, 1
     return (h, w), ((h // 2, w) if layout == 1 else (h // 2, w // 2)), layout + 1
 
 
+_PIXEL_BYTES = {0: 3, 3: 2, 4: 2, 5: 3, 6: 4, 7: 4}       # bytes a pixel of the layouts that are one plane of whole pixels
+
+
 def _frame_dims(layout):
-    """-> (dimensions of one frame's array, its last axis or 0): RGB (H, W, 3), packed 4:2:2 (H, W, 2), 4:2:0 (H * 3 // 2, W)."""
-    return (3, 3) if layout == 0 else (3, 2) if layout >= 3 else (2, 0)
+    """-> (dimensions of one frame's array, its last axis or 0): RGB / BGR (H, W, 3), RGBA / BGRA (H, W, 4), packed 4:2:2 (H, W, 2),
+    4:2:0 (H * 3 // 2, W)."""
+    return (3, _PIXEL_BYTES[layout]) if layout in _PIXEL_BYTES else (2, 0)
 
 
-_SHAPE_NAMES = {3: "(H, W, 3)", 2: "(H, W, 2)", 0: "(H * 3 // 2, W)"}
+_SHAPE_NAMES = {3: "(H, W, 3)", 4: "(H, W, 4)", 2: "(H, W, 2)", 0: "(H * 3 // 2, W)"}
 
 
 def _extent(rows, row_bytes, pitch):
@@ -133,8 +136,8 @@ def _layout_block(n, img_size, pixel_format, pitch, chroma_pitch, offset):
 
 
 def pack_host_frames(frames, pixel_format="rgb", pitch=None, chroma_pitch=None, offset=0, fill=0):
-    """Host frames -- (n, H, W, 3) / (H, W, 3), (n, H * 3 // 2, W) / (H * 3 // 2, W) for 4:2:0, or (n, H, W, 2) / (H, W, 2) for
-    packed 4:2:2 -- laid out as pitched surfaces in
+    """Host frames -- (n, H, W, 3) / (H, W, 3) ('rgb', 'bgr'), (n, H, W, 4) / (H, W, 4) ('rgba', 'bgra'), (n, H * 3 // 2, W) /
+    (H * 3 // 2, W) for 4:2:0, or (n, H, W, 2) / (H, W, 2) for packed 4:2:2 -- laid out as pitched surfaces in
     one block: frame after frame, plane after plane, every row `pitch` (chroma rows: `chroma_pitch`) bytes after the one before,
     the first at `offset`; bytes between and around the rows are `fill`.  The block ends with the last byte of the last plane.
     -> (the block as a u8 array, surfaces with plane OFFSETS into it, img_size, whether `frames` was one frame)."""
@@ -169,7 +172,7 @@ def pack_host_frames(frames, pixel_format="rgb", pitch=None, chroma_pitch=None, 
 class DeviceFrames:
     """n camera frames of `img_size` = (width, height) in `pixel_format` somewhere in device memory: a description, not an owner
     (`owner` is whatever keeps the memory alive; it is only referenced).  `surfaces` is a SURFACE_DTYPE array, one entry per
-    frame: plane pointers (RGB, YUY2, UYVY: one; NV12: Y, UV; I420: Y, U, V), the pitch of plane 0 and the chroma pitch, in bytes.
+    frame: plane pointers (RGB, BGR, RGBA, BGRA, YUY2, UYVY: one; NV12: Y, UV; I420: Y, U, V), the pitch of plane 0 and the chroma pitch, in bytes.
     `single`: made from one frame (what process() takes); `stream`: the producer's stream to wait for before the frames are read;
     `readonly`: the producer said so (`__cuda_array_interface__`'s data[1]) -- such frames are never drawn into (`out="inplace"`)."""
 
@@ -184,7 +187,7 @@ class DeviceFrames:
     @classmethod
     def from_planes(cls, planes, img_size, pixel_format, pitch, chroma_pitch=None, owner=None, stream=None, device=0):
         """Explicit pointers: `planes` is one tuple of plane addresses per frame (RGB: (rgb,); NV12: (y, uv); I420: (y, u, v); YUY2 /
-        UYVY: (plane,), pitch >= 2 W) --
+        UYVY: (plane,), pitch >= 2 W; BGR: (plane,), pitch >= 3 W; RGBA / BGRA: (plane,), pitch >= 4 W) --
         or a single such tuple for one frame -- `pitch` / `chroma_pitch` the bytes between rows (one value, or one per frame)."""
         (rows, rb), chroma, nplanes = _plane_rows(img_size, pixel_format)
         single = len(planes) > 0 and not hasattr(planes[0], "__len__")
@@ -212,7 +215,8 @@ class DeviceFrames:
     def from_cuda_array(cls, obj, pixel_format="rgb", device=0):
         """Anything with `__cuda_array_interface__` (or the dict itself): '|u1', shape (n, H, W, 3) / (H, W, 3) for RGB and
         (n, H * 3 // 2, W) / (H * 3 // 2, W) for NV12 / I420 with dense planes, (n, H, W, 2) / (H, W, 2) for YUY2 / UYVY (strides
-        (frame, pitch, 2, 1), pitch >= 2 W); row and frame strides come from `strides`."""
+        (frame, pitch, 2, 1), pitch >= 2 W), (n, H, W, 3) / (H, W, 3) for BGR as for RGB, (n, H, W, 4) / (H, W, 4) for RGBA / BGRA
+        (a pixel stride of 4: a `uint8` (H, W, 4) tensor); row and frame strides come from `strides`."""
         ai = obj if isinstance(obj, dict) else getattr(obj, "__cuda_array_interface__", None)
         if not isinstance(ai, dict):
             raise ValueError("the object has no __cuda_array_interface__")
@@ -244,10 +248,11 @@ class DeviceFrames:
             raise ValueError("the data pointer is null")
         single = len(shape) == nd
         n, fstride = (1, 0) if single else (shape[0], strides[0])
-        if layout == 0:
+        if last in (3, 4):
             h, w = shape[-3], shape[-2]
-            if strides[-1] != 1 or strides[-2] != 3:
-                raise ValueError("RGB frames are interleaved: a pixel stride of 3 and a channel stride of 1, got %r" % (strides[-2:],))
+            if strides[-1] != 1 or strides[-2] != last:
+                raise ValueError("%s frames are interleaved: a pixel stride of %d and a channel stride of 1, got %r"
+                                 % ("RGB" if layout == 0 else pixel_format.upper(), last, strides[-2:]))
             pitch = strides[-3]
         elif last == 2:
             h, w = shape[-3], shape[-2]

@@ -117,7 +117,7 @@ class LaneTrackerGroup:
         self.k = k
         self.img_size, self.warped_size = img_size, warped_size
         self.pixel_format, self.yuv_matrix = pixel_format, yuv_matrix
-        self._frame_shape = _native.frame_shape(img_size, pixel_format)
+        self._frame_shape = _native.input_frame_shape(img_size, pixel_format)
         # one input size for all streams (LaneTracker's input_size): RGB frames of that size, resized on the device to img_size
         self.input_size = None if input_size is None else tuple(int(v) for v in input_size)
         self._resize_from = _native.checked_input_size(input_size, img_size, pixel_format)
@@ -239,7 +239,7 @@ class LaneTrackerGroup:
             for i in active:
                 t0._check_inplace_source(frames[i])
         elif out is not None:
-            sink = t0._check_sink(out, self.k)
+            sink = t0._check_sink(out, self.k, one_launch=True)
             out_yuv_matrix = 'bt601' if out_yuv_matrix is None else out_yuv_matrix
             _native.rgb2yuv_coeffs(out_yuv_matrix)
         outs = [None] * self.k

@@ -69,10 +69,12 @@ class LaneTracker(StreamPipeline):
                  input_size=None):
         # the camera's pixel format: 'rgb' frames (H, W, 3), YUV 4:2:0 as decoders hand it out -- 'nv12' / 'i420' frames
         # (H * 3 // 2, W) -- or packed 4:2:2 as cameras and capture cards do -- 'yuy2' / 'uyvy' frames (H, W, 2) -- converted on the
-        # device with `yuv_matrix` ('bt601', 'bt709'); everything that comes back is RGB
+        # device with `yuv_matrix` ('bt601', 'bt709') -- or what users' own software holds: 'bgr' frames (H, W, 3) (OpenCV's order),
+        # 'rgba' / 'bgra' frames (H, W, 4), alpha never read: a channel permutation, `yuv_matrix` ignored as for 'rgb';
+        # everything that comes back is RGB
         self.pixel_format, self.yuv_matrix = pixel_format, yuv_matrix
-        self._frame_shape = _native.frame_shape(img_size, pixel_format)      # (ValueError: unknown format, odd 4:2:0 size, odd 4:2:2 width)
-        if pixel_format != 'rgb':
+        self._frame_shape = _native.input_frame_shape(img_size, pixel_format)      # (ValueError: unknown format, odd 4:2:0 size, odd 4:2:2 width)
+        if _native.is_yuv(_native.pixel_format_id(pixel_format)):
             _native.yuv_coeffs(yuv_matrix)
         # frames of another size than the calibration's: RGB frames (Hi, Wi, 3) of input_size = (Wi, Hi), resized on the device to
         # img_size as cv2.resize(frame, img_size) does; everything that comes back -- annotated frames too -- is img_size
@@ -773,8 +775,8 @@ class LaneTracker(StreamPipeline):
 
     def _rows_for(self, img):
         """_present_rows() when `img` is a frame whose rows the host can copy as they are, else None."""
-        if not self.host_copies_rows or not (isinstance(img, np.ndarray) and img.dtype == np.uint8 and img.flags["C_CONTIGUOUS"]
-                                             and img.shape == (self.img_size[1], self.img_size[0], 3)):
+        if not self.host_copies_rows or self.pixel_format != 'rgb' or not (isinstance(img, np.ndarray) and img.dtype == np.uint8 and img.flags["C_CONTIGUOUS"]
+                                                                           and img.shape == (self.img_size[1], self.img_size[0], 3)):
             return None
         return self._present_rows()
 
@@ -831,7 +833,7 @@ class LaneTracker(StreamPipeline):
 
     def _rows_for_window(self, frames):
         """_present_rows() when the annotated frames of this window can travel as row runs, else None."""
-        if isinstance(frames, DeviceFrames) or not self.host_copies_rows or frames.dtype != np.uint8 or not frames.flags["C_CONTIGUOUS"] or \
+        if isinstance(frames, DeviceFrames) or not self.host_copies_rows or self.pixel_format != 'rgb' or frames.dtype != np.uint8 or not frames.flags["C_CONTIGUOUS"] or \
                 frames.shape[1:] != (self.img_size[1], self.img_size[0], 3):
             return None
         return self._present_rows()

@@ -646,6 +646,8 @@ class StreamPipeline:
             raise ValueError("out='inplace' draws into the frames handed in: a tracker with input_size returns frames of img_size")
         if self.pixel_format in _native.PACKED_422:
             raise ValueError("out='inplace' draws into RGB, NV12 or I420 surfaces: %r is an input format only" % (self.pixel_format,))
+        if self.pixel_format in _native.RGB_FAMILY:
+            raise ValueError("out='inplace' draws into RGB, NV12 or I420 surfaces: %r frames go into an out= sink" % (self.pixel_format,))
         if out_yuv_matrix is not None:
             _native.rgb2yuv_coeffs(out_yuv_matrix)
             return out_yuv_matrix
@@ -706,11 +708,12 @@ class StreamPipeline:
         if k["visualize_search"] or k["split_view"]:
             raise ValueError("out= receives annotated frames only: visualize_search / split_view return pictures on the host")
 
-    def _check_sink(self, sink, n):
-        """`sink` as the destination of a window of n frames: a DeviceFrames of the tracker's image size, n surfaces, on its device."""
+    def _check_sink(self, sink, n, one_launch=False):
+        """`sink` as the destination of a window of n frames: a DeviceFrames of the tracker's image size, n surfaces, on its device.
+        one_launch: a group's sink, drawn into by lt_overlay_run_to_surfaces ('rgb', 'nv12', 'i420' only)."""
         if not isinstance(sink, DeviceFrames):
             raise ValueError("out= takes a DeviceFrames (DeviceFrames.empty(n, img_size, pixel_format)), got %r" % (type(sink).__name__,))
-        _native.sink_format_id(sink.pixel_format)       # (packed 4:2:2 is an input format only)
+        (_native.draw_sink_format_id if one_launch else _native.sink_format_id)(sink.pixel_format)       # (packed 4:2:2 is an input format only)
         if sink.img_size != (int(self.img_size[0]), int(self.img_size[1])):
             raise ValueError("out= holds frames of %dx%d, the tracker's are %dx%d" % (sink.img_size + (int(self.img_size[0]), int(self.img_size[1]))))
         if len(sink) != n:

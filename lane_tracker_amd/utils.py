@@ -94,7 +94,10 @@ def yuv_to_rgb(frame, layout='nv12', matrix='bt601'):
     (20-bit fixed point) for another matrix.  Or a packed 4:2:2 frame as OpenCV holds it -- a u8 array (H, W, 2), W even: 'yuy2'
     (bytes Y0 U Y1 V) / 'uyvy' (U Y0 V Y1) -- `cv2.cvtColor(frame, cv2.COLOR_YUV2RGB_YUY2)` / `_UYVY`, the same arithmetic with one
     (U, V) pair per horizontal pixel pair.  What a `LaneTracker(..., pixel_format=layout, yuv_matrix=matrix)` sees of the frame."""
+    from . import _native
     from .lane_tracker import _context_for_module_functions
+    if not _native.is_yuv(_native.pixel_format_id(layout)):          # (before a context is made: 'rgb', 'bgr', 'rgba', 'bgra' hold no YUV)
+        raise ValueError("layout must be 'nv12', 'i420', 'yuy2' or 'uyvy'")
     return _context_for_module_functions().yuv_to_rgb(frame, layout, matrix)
 
 
@@ -107,7 +110,7 @@ def rgb_to_yuv(frame, layout='nv12', matrix='bt601'):
     from . import _native
     from .device import DeviceBuffer, DeviceFrames
     a = np.ascontiguousarray(frame, np.uint8)
-    if _native.sink_format_id(layout) == 0:              # (packed 4:2:2 is an input format only: ValueError)
+    if _native.sink_format_id(layout) not in (1, 2):     # (packed 4:2:2 is an input format only: ValueError)
         raise ValueError("layout must be 'nv12' or 'i420'")
     if a.ndim != 3 or a.shape[2] != 3 or a.shape[0] % 2 or a.shape[1] % 2 or 0 in a.shape:
         raise ValueError("an RGB frame is an array (H, W, 3) with H and W even, got %r" % (a.shape,))
@@ -122,3 +125,36 @@ def rgb_to_yuv(frame, layout='nv12', matrix='bt601'):
         finally:
             sink.owner.close()
 
+
+
+_RGB_ORDER = {"rgb": (0, 1, 2), "bgr": (2, 1, 0), "rgba": (0, 1, 2), "bgra": (2, 1, 0)}
+
+
+def packed_to_rgb(frame, pixel_format):
+    """A frame (or frames) of the RGB family -- 'bgr' (..., H, W, 3), 'rgba' / 'bgra' (..., H, W, 4); 'rgb' as it is -- as RGB
+    (..., H, W, 3): a channel permutation, the alpha byte dropped.  NumPy only; what a `LaneTracker(..., pixel_format=...)` sees of
+    the frame, bit for bit."""
+    if pixel_format not in _RGB_ORDER:
+        raise ValueError("pixel_format must be 'rgb', 'bgr', 'rgba' or 'bgra', got %r" % (pixel_format,))
+    a = np.asarray(frame)
+    want = 4 if pixel_format in ("rgba", "bgra") else 3
+    if a.dtype != np.uint8 or a.ndim < 3 or a.shape[-1] != want:
+        raise ValueError("a %r frame is a uint8 array (..., H, W, %d), got %s %r" % (pixel_format, want, a.dtype, a.shape))
+    return np.ascontiguousarray(a[..., list(_RGB_ORDER[pixel_format])])
+
+
+def rgb_to_packed(rgb, pixel_format, alpha=255):
+    """The way back: RGB frames (..., H, W, 3) in `pixel_format` -- 'bgr', or 'rgba' / 'bgra' with every alpha byte `alpha` (what a
+    device sink in that format receives: 255).  NumPy only."""
+    if pixel_format not in _RGB_ORDER:
+        raise ValueError("pixel_format must be 'rgb', 'bgr', 'rgba' or 'bgra', got %r" % (pixel_format,))
+    a = np.asarray(rgb)
+    if a.dtype != np.uint8 or a.ndim < 3 or a.shape[-1] != 3:
+        raise ValueError("an RGB frame is a uint8 array (..., H, W, 3), got %s %r" % (a.dtype, a.shape))
+    nch = 4 if pixel_format in ("rgba", "bgra") else 3
+    out = np.empty(a.shape[:-1] + (nch,), np.uint8)
+    for ch, at in enumerate(_RGB_ORDER[pixel_format]):
+        out[..., at] = a[..., ch]
+    if nch == 4:
+        out[..., 3] = alpha
+    return out

@@ -14,6 +14,9 @@ frames out.  Supported on both sides:
   * or a headerless raw packed 4:2:2 file as cameras and capture cards produce it: `.yuy2` (Y0 U Y1 V) or `.uyvy` (U Y0 V Y1),
     H * W * 2 bytes a frame (`ffmpeg -pix_fmt yuyv422 | uyvy422 -f rawvideo`); its frames are (H, W, 2) arrays.  A `FrameSink`
     with such a `pixel_format` writes the same files (the bytes as given; the tracker itself has no 4:2:2 output)
+  * or a headerless raw file of another member of the RGB family, as users' own software holds frames: `.bgr` (B G R, H * W * 3
+    bytes a frame; OpenCV's order), `.rgba` / `.bgra` (H * W * 4; `ffmpeg -pix_fmt bgr24 | rgba | bgra -f rawvideo`); frames of
+    shape (H, W, 3) / (H, W, 4), alpha not read.  These three are output formats too (`--out-format`, alpha written as 255)
   * `--out-format nv12 | i420` (or `rgb`) asks for the annotated frames through a device sink (`process_stream(..., out=)`): they
     are converted on the device and written as a raw `.nv12` / `.i420` (`.rgb`) file, which this module also reads.
 
@@ -42,14 +45,25 @@ def _is_raw(path):
 
 
 def _yuv_layout(path):
-    """'nv12' / 'i420' for a raw 4:2:0 file name, 'yuy2' / 'uyvy' for a raw packed 4:2:2 one, else None."""
+    """'nv12' / 'i420' for a raw 4:2:0 file name, 'yuy2' / 'uyvy' for a raw packed 4:2:2 one, 'bgr' / 'rgba' / 'bgra' for a raw
+    file of the RGB family's other members, else None."""
     p = str(path).lower()
+    for name in _RGB_FAMILY:
+        if p.endswith("." + name):
+            return name
     return ("nv12" if p.endswith(".nv12") else "i420" if p.endswith((".i420", ".yuv")) else "yuy2" if p.endswith(".yuy2")
             else "uyvy" if p.endswith(".uyvy") else None)
 
 
+_RGB_FAMILY = ("bgr", "rgba", "bgra")
+
+
 def _yuv_tail(pixel_format, width, height):
     """(shape of one frame, the format's family name); ValueError for a size the format does not take."""
+    if pixel_format in _RGB_FAMILY:
+        if width < 2 or height < 1:
+            raise ValueError(f"{pixel_format} frames need a width of at least 2, got {width}x{height}")
+        return (height, width, 3 if pixel_format == "bgr" else 4), pixel_format.upper()
     if pixel_format in ("yuy2", "uyvy"):
         if width % 2 or width < 4 or height < 1:
             raise ValueError(f"4:2:2 frames need an even width of at least 4, got {width}x{height}")
@@ -78,7 +92,7 @@ def resolve_clip_path(path, must_exist=True):
 
 class FrameSource:
     """Ordered u8 frames: RGB (n, H, W, 3), or -- `pixel_format` 'nv12' / 'i420', raw 4:2:0 files -- (n, H * 3 // 2, W), or --
-    'yuy2' / 'uyvy', raw packed 4:2:2 files -- (n, H, W, 2).
+    'yuy2' / 'uyvy', raw packed 4:2:2 files -- (n, H, W, 2), or -- 'bgr' / 'rgba' / 'bgra', raw files -- (n, H, W, 3) / (n, H, W, 4).
     `size` = (width, height) is required for raw files only."""
 
     pixel_format = "rgb"
@@ -115,6 +129,7 @@ class FrameSource:
         elif _yuv_layout(self.path):
             if size is None:
                 raise ValueError("raw 4:2:0 input needs size=(width, height)" if _yuv_layout(self.path) in ("nv12", "i420")
+                                 else "raw %s input needs size=(width, height)" % _yuv_layout(self.path).upper() if _yuv_layout(self.path) in _RGB_FAMILY
                                  else "raw 4:2:2 input needs size=(width, height)")
             self.pixel_format = _yuv_layout(self.path)
             self.width, self.height = int(size[0]), int(size[1])
@@ -127,7 +142,7 @@ class FrameSource:
             self._array = np.memmap(self.path, np.uint8, "r", shape=(self._n,) + self._tail) if self._n \
                 else np.zeros((0,) + self._tail, np.uint8)
         else:
-            raise ValueError(f"unsupported frame source {self.path!r} (directory of images, .npy, .rgb/.raw, .nv12, .i420/.yuv, .yuy2, .uyvy)")
+            raise ValueError(f"unsupported frame source {self.path!r} (directory of images, .npy, .rgb/.raw, .bgr, .rgba, .bgra, .nv12, .i420/.yuv, .yuy2, .uyvy)")
         if self._tail is None:
             self._tail = (self.height, self.width, 3)
         if size is not None and (self.width, self.height) != (int(size[0]), int(size[1])):
@@ -178,7 +193,8 @@ class FrameSource:
 class FrameSink:
     """Where processed frames go.  Directories get `frame_000000.png`, ...; `.npy` needs `n` up front.  `pixel_format` 'nv12' /
     'i420': frames of shape (H * 3 // 2, W) into a raw 4:2:0 file (`.nv12`, `.i420` / `.yuv`); 'yuy2' / 'uyvy': frames of shape
-    (H, W, 2) into a raw packed 4:2:2 file (`.yuy2`, `.uyvy`)."""
+    (H, W, 2) into a raw packed 4:2:2 file (`.yuy2`, `.uyvy`); 'bgr' / 'rgba' / 'bgra': frames of shape (H, W, 3) / (H, W, 4) into
+    a raw file of that name (`.bgr`, `.rgba`, `.bgra`)."""
 
     def __init__(self, path, size, n=None, pixel_format="rgb"):
         self.path = str(path)
@@ -236,7 +252,7 @@ def process_frames(tracker, source, sink=None, window=64, viz_sink=None, out_for
     """Run every frame of `source` through the tracker, in order, `window` frames per GPU batch; write the
     annotated frames to `sink` if there is one -- the split views with `split_view=True` among the keywords, for a sink of
     that size -- and the search visualisations (bird's-eye size; `visualize_search=True` is set) to `viz_sink` if there
-    is one.  `out_format` ('rgb', 'nv12', 'i420'): the annotated frames leave through device sinks in that pixel format
+    is one.  `out_format` ('rgb', 'bgr', 'rgba', 'bgra', 'nv12', 'i420'): the annotated frames leave through device sinks in that pixel format
     (`process_stream(..., out=)`; 4:2:0 converted on the device with `out_yuv_matrix`) and `sink` receives what the sinks hold.
     Returns (frames, seconds)."""
     t0 = time.perf_counter()
@@ -314,7 +330,7 @@ def _parse_size(text):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Lane tracking over a frame sequence (process_video.py without moviepy)")
-    ap.add_argument("input", help="directory of images, .npy (n,H,W,3), raw .rgb, raw 4:2:0 (.nv12, .i420 / .yuv) or raw packed 4:2:2 (.yuy2, .uyvy)")
+    ap.add_argument("input", help="directory of images, .npy (n,H,W,3), raw .rgb / .bgr / .rgba / .bgra, raw 4:2:0 (.nv12, .i420 / .yuv) or raw packed 4:2:2 (.yuy2, .uyvy)")
     ap.add_argument("output", help="directory (PNG), .npy or raw .rgb; '-' to discard the frames")
     ap.add_argument("--cam", default="cam_calib.p", help="camera calibration (.p pickle or .npz)")
     ap.add_argument("--warp", default="warp_params.p", help="warp parameters (.p pickle or .npz)")
@@ -323,12 +339,13 @@ def main(argv=None):
                     help="WxH of the input frames when that is not the calibration's size: raw RGB input is read in this size and the "
                          "tracker resizes the frames on the device (cv2.resize, INTER_LINEAR); what is written has the calibration's size")
     ap.add_argument("--window", type=int, default=64, help="frames per GPU batch")
-    ap.add_argument("--pixel-format", choices=("rgb", "nv12", "i420", "yuy2", "uyvy"), default=None,
+    ap.add_argument("--pixel-format", choices=("rgb", "nv12", "i420", "yuy2", "uyvy") + _RGB_FAMILY, default=None,
                     help="pixel format of the input frames (default: by the input's name); must match a raw input's extension")
     ap.add_argument("--yuv-matrix", choices=("bt601", "bt709"), default="bt601", help="conversion matrix of 4:2:0 / 4:2:2 input")
-    ap.add_argument("--out-format", choices=("rgb", "nv12", "i420"), default=None,
+    ap.add_argument("--out-format", choices=("rgb", "nv12", "i420") + _RGB_FAMILY, default=None,
                     help="write the annotated frames through a device sink in this pixel format: a raw .rgb / .nv12 / .i420 file for "
-                         "4:2:0 (converted on the device, --out-yuv-matrix); default: RGB frames brought back by the host")
+                         "4:2:0 (converted on the device, --out-yuv-matrix), a raw .bgr / .rgba / .bgra file (permuted on the device, "
+                         "alpha 255); default: RGB frames brought back by the host")
     ap.add_argument("--out-yuv-matrix", choices=("bt601", "bt709"), default="bt601", help="conversion matrix of 4:2:0 output")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--frame-count", action="store_true", help="print the frame number onto each image")
@@ -345,7 +362,7 @@ def main(argv=None):
         ap.error("--split-view and --visualize-search are two runs: process() returns one or the other")
     if a.out_format is not None and (a.split_view or a.visualize_search or a.output == "-"):
         ap.error("--out-format writes the annotated frames through a device sink: it needs an output, and neither --split-view nor --visualize-search")
-    if a.out_format in ("nv12", "i420") and _yuv_layout(a.output) != a.out_format:
+    if a.out_format in ("nv12", "i420") + _RGB_FAMILY and _yuv_layout(a.output) != a.out_format:
         ap.error("--out-format %s needs an output file named *.%s" % (a.out_format, a.out_format))
     from . import _native
     from .lane_tracker import LaneTracker

@@ -12,7 +12,7 @@ Modes (one per invocation; every leg runs `--runs` times, the file holds each ru
                LaneTrackerGroup of 8 -- each fed DeviceFrames and, beside it, host arrays.
   --host-fed   the host-fed halves of --trackers alone (what an older checkout can run: its figures are the yardstick).
 
-`--pixel-format yuy2|uyvy` (repeatable) adds packed 4:2:2 legs to `--formats`; with --resident / --attached every leg also records
+`--pixel-format yuy2|uyvy|bgr|rgba|bgra` (repeatable) adds packed 4:2:2 legs, or legs in the RGB family's other members, to `--formats`; with --resident / --attached every leg also records
 the `undistort_rows` stage time per 256 frames (lt_set_stage_timing: one timed mask run behind the measured steps).
 
 The `--runs` repetitions of a leg run back to back, one format after the other.  For runs that ALTERNATE between the formats (what
@@ -71,6 +71,13 @@ def rgb_to_422(rgb, fmt):
 
 
 PACKED = ("yuy2", "uyvy")
+RGB_FAMILY = ("bgr", "rgba", "bgra")
+ROW_BYTES = dict(rgb=3, yuy2=2, uyvy=2, bgr=3, rgba=4, bgra=4)          # bytes a pixel of plane 0 (1: the 4:2:0 formats)
+
+
+def rgb_to_family(rgb, fmt):
+    from lane_tracker_amd.utils import rgb_to_packed
+    return rgb_to_packed(rgb, fmt, alpha=0x5a)
 _pools = {}
 
 
@@ -81,7 +88,8 @@ def frames_for(cal, fmt, n, outage=False):
         if outage:
             pool[20:23] = 0             # a short outage: second tries, failure pictures
         _pools[key] = (np.stack([rgb_to_nv12(f) for f in pool]) if fmt == "nv12" else
-                       np.stack([rgb_to_422(f, fmt) for f in pool]) if fmt in PACKED else pool)
+                       np.stack([rgb_to_422(f, fmt) for f in pool]) if fmt in PACKED else
+                       rgb_to_family(pool, fmt) if fmt in RGB_FAMILY else pool)
     return np.ascontiguousarray(_pools[key][np.arange(n) % POOL])
 
 
@@ -102,7 +110,7 @@ def batch_step(cal, fmt, mode, steps, warmup, streams, pitch_extra=0):
         if mode == "resident":
             ctx.upload_frames(frames)
         else:
-            row = cal["img_size"][0] * (3 if fmt == "rgb" else 2 if fmt in PACKED else 1)
+            row = cal["img_size"][0] * ROW_BYTES.get(fmt, 1)
             keep = ctx.attach_device_frames(DeviceFrames.from_host(frames, fmt, pitch=row + pitch_extra))
         fp, sp = _native.filter_params(), _native.search_params()
         ctx.set_streams(streams)
@@ -199,7 +207,8 @@ def main():
     ap.add_argument("--streams", type=int, default=4)
     ap.add_argument("--sizes", default="1280x720,1920x1080")
     ap.add_argument("--formats", default="rgb,nv12")
-    ap.add_argument("--pixel-format", action="append", choices=PACKED, default=[], help="a packed 4:2:2 format to measure beside --formats (repeatable)")
+    ap.add_argument("--pixel-format", action="append", choices=PACKED + RGB_FAMILY, default=[],
+                    help="a packed 4:2:2 format, or another member of the RGB family, to measure beside --formats (repeatable)")
     ap.add_argument("--out", default="-")
     ap.add_argument("--commit", default=None, help="the commit hash to record (default: git rev-parse HEAD of this checkout)")
     a = ap.parse_args()
@@ -220,6 +229,8 @@ def main():
     formats = [f for f in a.formats.split(",") + a.pixel_format if f == "rgb" or HAS_YUV]
     if any(f in PACKED for f in formats) and "yuy2" not in getattr(_native, "INPUT_FORMATS", {}):
         sys.exit("this checkout has no packed 4:2:2 input")
+    if any(f in RGB_FAMILY for f in formats) and "bgr" not in getattr(_native, "RGB_FAMILY", {}):
+        sys.exit("this checkout has no BGR / RGBA / BGRA input")
     if mode in ("resident", "attached"):
         cal = calib.reference_calibration()
         for fmt in formats:
