@@ -50,7 +50,7 @@ extern "C" {
  *    plot points, radius and eccentricity of a valid first try in one host call).  Later additions, still 5:
  *    lt_search_item + lt_search_fit_list (the searches of frames of unrelated streams in one launch), lt_upload_frame_rows_list +
  *    lt_upload_frame_rest_list (the uploads of frames that lie in separate host arrays); lt_set_input_format + lt_get_input_format +
- *    lt_yuv_to_rgb (camera frames in YUV 4:2:0, NV12 or I420, or packed 4:2:2, YUY2 or UYVY, converted on the device); lt_device_surface + lt_attach_device_frames +
+ *    lt_yuv_to_rgb (camera frames in YUV 4:2:0, NV12 or I420, or packed 4:2:2, YUY2 or UYVY, converted on the device), lt_bayer_to_rgb (8-bit raw Bayer, layouts 16 .. 19, demosaiced on the device); lt_device_surface + lt_attach_device_frames +
  *    lt_device_frames_rest (camera frames that already lie in device memory, read where they lie), lt_device_alloc / _free /
  *    _write / _read (device blocks for callers without a HIP binding of their own), lt_device_stream_wait; lt_viz_item +
  *    lt_search_viz_run + lt_split_panes_run + lt_split_panes_size + lt_search_viz_wait (the search visualisations and split-view
@@ -214,14 +214,37 @@ int  lt_set_streams(lt_ctx* ctx, int nstreams);
  * img_w; chroma_pitch is not read); lt_set_direct_upload returns 0 (rows go to staging).  These three are SINKS too:
  * lt_rgb_to_surfaces and lt_overlay_store_device write them (alpha = 255, bytes between a row's end and the pitch untouched, any
  * byte alignment).  Not supported: lt_overlay_run_inplace* on such a context and lt_set_input_size with such a format return
- * LT_ERR_STATE, lt_overlay_run_to_surfaces with such a sink layout LT_ERR_INVALID; lt_yuv_to_rgb does not take them. */
+ * LT_ERR_STATE, lt_overlay_run_to_surfaces with such a sink layout LT_ERR_INVALID; lt_yuv_to_rgb does not take them.
+ *
+ * 8-bit raw Bayer, as a sensor delivers it before any image signal processor has run (machine-vision and GMSL cameras in raw mode,
+ * raw sensor logs) -- LT_INPUT_BAYER_RGGB, _GRBG, _GBRG, _BGGR, named by the sensor's top-left 2 x 2 block: one plane of img_h rows
+ * of img_w bytes, img_h * img_w bytes a frame (a third of the RGB form), numpy (H, W); img_w and img_h even and at least 4.  The
+ * pixel at (y, x) carries the colour at position 2 * (y & 1) + (x & 1) of the pattern's name.  Demosaiced on the device, bilinear, in
+ * integers -- at an interior pixel (1 <= y <= img_h - 2, 1 <= x <= img_w - 2) of the mosaic m:
+ *     red / blue site:  own colour m[y,x];  G = (m[y-1,x] + m[y+1,x] + m[y,x-1] + m[y,x+1] + 2) >> 2;
+ *                       the opposite colour = (m[y-1,x-1] + m[y-1,x+1] + m[y+1,x-1] + m[y+1,x+1] + 2) >> 2
+ *     green site:       G = m[y,x];  the horizontal neighbours' colour = (m[y,x-1] + m[y,x+1] + 1) >> 1;
+ *                       the vertical neighbours' colour = (m[y-1,x] + m[y+1,x] + 1) >> 1
+ * and a border pixel takes the value of the interior pixel at (clamp(y, 1, img_h - 2), clamp(x, 1, img_w - 2)).  This is what
+ * cv2.cvtColor(frame, COLOR_BayerRGGB2RGB / GRBG / GBRG / BGGR) is understood to compute; that was not checked against OpenCV, the
+ * definition here is the contract.  `coeffs` is not read (NULL).  The undistortion demosaics the taps it reads, and everything
+ * behind it is bit for bit what an RGB context computes from the demosaiced frames.  Uploads and attached surfaces work as said
+ * above with one plane of one byte a pixel (pitch >= img_w; chroma_pitch is not read); the lt_upload_frame_rows family moves the
+ * source rows that the windows of the path's camera rows touch (lt_get_input_rows: the run widened by a row on either side, four
+ * rows at the least); lt_set_direct_upload returns 0.  lt_bayer_to_rgb is the conversion alone, of one host frame of h x w (even,
+ * 4 .. 16384 each) on the device: out_rgb = h * w * 3 bytes.  Raw Bayer is an INPUT format only: lt_rgb_to_surfaces,
+ * lt_overlay_store_device and lt_overlay_run_to_surfaces return LT_ERR_INVALID for these layouts, lt_overlay_run_inplace* on such a
+ * context and lt_set_input_size with such a format return LT_ERR_STATE; lt_yuv_to_rgb does not take them.  Not built: 10 / 12 / 16-bit
+ * or companded raw, other demosaics, white balance or any other step of an image signal processor. */
 enum lt_input_layout { LT_INPUT_RGB = 0, LT_INPUT_NV12 = 1, LT_INPUT_I420 = 2, LT_INPUT_YUY2 = 3, LT_INPUT_UYVY = 4,
-                       LT_INPUT_BGR = 5, LT_INPUT_RGBA = 6, LT_INPUT_BGRA = 7 };
+                       LT_INPUT_BGR = 5, LT_INPUT_RGBA = 6, LT_INPUT_BGRA = 7,
+                       LT_INPUT_BAYER_RGGB = 16, LT_INPUT_BAYER_GRBG = 17, LT_INPUT_BAYER_GBRG = 18, LT_INPUT_BAYER_BGGR = 19 };
 #define LT_YUV_BT601 {1220542, 1673527, -852492, -409993, 2116026}   /* video range; OpenCV's constants */
 #define LT_YUV_BT709 {1220542, 1880097, -558891, -223347, 2214593}   /* video range */
 int  lt_set_input_format(lt_ctx* ctx, int layout, const int32_t coeffs[5]);
 int  lt_get_input_format(lt_ctx* ctx, int* layout, int32_t coeffs[5]);
 int  lt_yuv_to_rgb(lt_ctx* ctx, const uint8_t* frame, int h, int w, int layout, const int32_t coeffs[5], uint8_t* out_rgb);
+int  lt_bayer_to_rgb(lt_ctx* ctx, const uint8_t* frame, int h, int w, int layout, uint8_t* out_rgb);
 /* Frames of another SIZE than the calibration's: a context with an input size of src_w x src_h takes RGB frames of src_h * src_w * 3
  * bytes and resizes them on the device to img_w x img_h -- cv2.resize(frame, (img_w, img_h)) with the default INTER_LINEAR, bit for bit:
  * half-pixel centres, 11-bit coefficients, OpenCV's two-stage rounding.  Everything the context computes, keeps and hands out is what a

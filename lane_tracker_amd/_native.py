@@ -233,6 +233,7 @@ _SIGNATURES = {
     "lt_get_input_size": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "lt_get_input_rows": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "lt_yuv_to_rgb": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "lt_bayer_to_rgb": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "lt_attach_device_frames": (C.c_int, [_P, _P, C.c_int, C.c_int]),
     "lt_device_frames_rest": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "lt_device_alloc": (C.c_int, [C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]),
@@ -264,6 +265,9 @@ PACKED_422 = ("yuy2", "uyvy")                                      # the names I
 # (H, W, 4), alpha never read.  A channel permutation, no conversion; camera frames AND sinks (alpha written as 255).  A table of
 # its own: the three above keep their contents.
 RGB_FAMILY = {"bgr": 5, "rgba": 6, "bgra": 7}
+# ... and 8-bit raw Bayer, as a sensor delivers it before any image signal processor: one plane of (H, W) bytes, named by the
+# sensor's top-left 2 x 2 block; demosaiced (bilinear) on the device.  Camera frames only.  Again a table of its own.
+BAYER_FORMATS = {"bayer_rggb": 16, "bayer_grbg": 17, "bayer_gbrg": 18, "bayer_bggr": 19}
 YUV_MATRICES = {"bt601": (1220542, 1673527, -852492, -409993, 2116026),
                 "bt709": (1220542, 1880097, -558891, -223347, 2214593)}
 
@@ -302,14 +306,17 @@ def rgb_to_surfaces(rgb_ptr, frame_stride, img_size, sink, matrix="bt601", devic
 
 def pixel_format_id(pixel_format):
     try:
-        return INPUT_FORMATS[pixel_format] if pixel_format in INPUT_FORMATS else RGB_FAMILY[pixel_format]
+        if pixel_format in INPUT_FORMATS:
+            return INPUT_FORMATS[pixel_format]
+        return RGB_FAMILY[pixel_format] if pixel_format in RGB_FAMILY else BAYER_FORMATS[pixel_format]
     except (KeyError, TypeError):
-        raise ValueError("pixel_format must be 'rgb', 'nv12', 'i420', 'yuy2', 'uyvy', 'bgr', 'rgba' or 'bgra', got %r" % (pixel_format,)) from None
+        raise ValueError("pixel_format must be 'rgb', 'nv12', 'i420', 'yuy2', 'uyvy', 'bgr', 'rgba', 'bgra' or 'bayer_rggb' / '_grbg' / '_gbrg' / "
+                         "'_bggr', got %r" % (pixel_format,)) from None
 
 
 def format_name(layout):
     """The name of an lt_input_layout value."""
-    return {v: n for n, v in list(INPUT_FORMATS.items()) + list(RGB_FAMILY.items())}[int(layout)]
+    return {v: n for n, v in list(INPUT_FORMATS.items()) + list(RGB_FAMILY.items()) + list(BAYER_FORMATS.items())}[int(layout)]
 
 
 def is_yuv(layout):
@@ -318,8 +325,8 @@ def is_yuv(layout):
 
 
 def sink_format_id(pixel_format):
-    """pixel_format_id for a destination of annotated frames: packed 4:2:2 is an input format only."""
-    if pixel_format in PACKED_422:
+    """pixel_format_id for a destination of annotated frames: packed 4:2:2 and raw Bayer are input formats only."""
+    if pixel_format in PACKED_422 or pixel_format in BAYER_FORMATS:
         raise ValueError("%r is an input format only: annotated frames go into 'rgb', 'bgr', 'rgba', 'bgra', 'nv12' or 'i420' surfaces" % (pixel_format,))
     return pixel_format_id(pixel_format)
 
@@ -365,7 +372,7 @@ def checked_input_size(input_size, img_size, pixel_format="rgb"):
 
 def frame_shape(img_size, pixel_format="rgb"):
     """Shape of one camera frame of `img_size` = (width, height) in `pixel_format`: (H, W, 3), (H * 3 // 2, W) for 4:2:0, or
-    (H, W, 2) for packed 4:2:2 (OpenCV's CV_8UC2); 'bgr': (H, W, 3), 'rgba' / 'bgra': (H, W, 4)."""
+    (H, W, 2) for packed 4:2:2 (OpenCV's CV_8UC2); 'bgr': (H, W, 3), 'rgba' / 'bgra': (H, W, 4); raw Bayer: (H, W)."""
     w, h = int(img_size[0]), int(img_size[1])
     if pixel_format_id(pixel_format) == 0:
         return (h, w, 3)
@@ -373,6 +380,10 @@ def frame_shape(img_size, pixel_format="rgb"):
         if w < 1 or h < 1:
             raise ValueError("empty %r frames: %dx%d" % (pixel_format, w, h))
         return (h, w, 3 if pixel_format == "bgr" else 4)
+    if pixel_format in BAYER_FORMATS:
+        if w % 2 or h % 2 or w < 4 or h < 4:
+            raise ValueError("raw Bayer frames need an even width and height of at least 4, got %dx%d" % (w, h))
+        return (h, w)
     if pixel_format in PACKED_422:
         if w % 2 or w < 4 or h < 1:
             raise ValueError("4:2:2 frames need an even width of at least 4, got %dx%d" % (w, h))
@@ -823,7 +834,9 @@ class Context:
         'nv12' / 'i420' -- frames of shape (H * 3 // 2, W) as OpenCV holds them -- or packed 4:2:2, 'yuy2' / 'uyvy' -- frames of shape
         (H, W, 2) -- converted on the device with `yuv_matrix` ('bt601', 'bt709', or five integers); or another member of the RGB
         family, 'bgr' -- (H, W, 3), OpenCV's order -- / 'rgba' / 'bgra' -- (H, W, 4), alpha not read --, a channel permutation
-        (`yuv_matrix` is ignored as for 'rgb').  Every upload method then takes such frames."""
+        (`yuv_matrix` is ignored as for 'rgb'); or 8-bit raw Bayer, 'bayer_rggb' / 'bayer_grbg' / 'bayer_gbrg' / 'bayer_bggr' -- frames of
+        shape (H, W), H and W even and at least 4, demosaiced on the device (`yuv_matrix` ignored).  Every upload method then takes
+        such frames."""
         layout = pixel_format_id(pixel_format)
         tail = input_frame_shape((self.img_w, self.img_h), pixel_format)
         k = yuv_coeffs(yuv_matrix) if is_yuv(layout) else None
@@ -890,6 +903,18 @@ class Context:
         out = np.empty((h, w, 3), np.uint8)
         k = yuv_coeffs(matrix)
         _check(self.lib.lt_yuv_to_rgb(self._h, a.ctypes.data, h, w, pixel_format_id(layout), k.ctypes.data, out.ctypes.data))
+        return out
+
+    def bayer_to_rgb(self, frame, pattern="bayer_rggb"):
+        """One 8-bit raw Bayer frame (H, W), H and W even and at least 4, -> RGB (H, W, 3): the bilinear demosaic, on the device
+        (lt_bayer_to_rgb)."""
+        a = _u8(frame)
+        if pattern not in BAYER_FORMATS:
+            raise ValueError("pattern must be one of %s, got %r" % (", ".join(repr(n) for n in BAYER_FORMATS), pattern))
+        if a.ndim != 2 or a.shape[0] % 2 or a.shape[1] % 2 or a.shape[0] < 4 or a.shape[1] < 4:
+            raise ValueError("a raw Bayer frame is a 2-D array of shape (H, W) with H and W even and at least 4, got %r" % (a.shape,))
+        out = np.empty((a.shape[0], a.shape[1], 3), np.uint8)
+        _check(self.lib.lt_bayer_to_rgb(self._h, a.ctypes.data, a.shape[0], a.shape[1], BAYER_FORMATS[pattern], out.ctypes.data))
         return out
 
     # -- calibration sets: cameras of different calibrations in one context, one per slot
@@ -1208,6 +1233,8 @@ class Context:
         k = None
         if self.input_format()[0] in PACKED_422:
             raise ValueError("packed 4:2:2 is an input format only: nothing is drawn into such surfaces")
+        if self.input_format()[0] in BAYER_FORMATS:
+            raise ValueError("raw Bayer is an input format only: nothing is drawn into such surfaces")
         if self.input_format()[0] in RGB_FAMILY:
             raise ValueError("nothing is drawn into 'bgr' / 'rgba' / 'bgra' surfaces in place: such sinks are written by store_overlay_device")
         if pixel_format_id(self.input_format()[0]):

@@ -10,6 +10,9 @@
 //   k_undistort_px, k_undistort_px_surf, k_undistort_px_cal, k_undistort_px_cal_surf  the walk over the RGB family's other members
 //                      (<5> BGR, <6> RGBA, <7> BGRA: a channel permutation, folded into the shifts the walk takes its channels out with);
 //                      k_px_rows_to_rgb, k_surfpx_rows_to_rgb: their rows as RGB for whoever shows the camera frame
+//   k_undistort_bayer, k_undistort_bayer_surf, k_undistort_bayer_cal, k_undistort_bayer_cal_surf  the walk over 8-bit raw Bayer frames
+//                      (<0> RGGB, <1> GRBG, <2> GBRG, <3> BGGR): every tap demosaiced (bilinear, bayer_arith.h) from one 4 x 4 byte window,
+//                      then the blend; k_bayer_rows_to_rgb, k_surfbayer_rows_to_rgb: their rows as RGB for whoever shows the camera frame
 //   k_undistort_cal*, k_warp_cal  the table-per-slot forms of the walk's seven entry points and of the warp: every slot of a launch with
 //                      the remap tables of its own calibration set (lt_add_calibration), for slices that mix sets
 //   k_yuv_rows_to_rgb, k_surf_rows_to_rgb  cv2.cvtColor(YUV2RGB_NV12 / _I420) of a run of rows (for whoever shows the camera
@@ -34,6 +37,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "bayer_arith.h"
 #include "front_arith.h"
 #include "lt_internal.h"
 #include "yuv_arith.h"
@@ -249,6 +253,46 @@ struct Yuv422 {
     }
 };
 
+// 8-bit raw Bayer, one plane of W bytes per row.  PATTERN 0: RGGB, 1: GRBG, 2: GBRG, 3: BGGR (bayer_arith.h).  Demosaicing is not
+// linear in the samples (the rounding shifts), so each of the four taps is demosaiced before the blend, at its position clamped to
+// the interior.  The four 3 x 3 neighbourhoods lie inside one 4 x 4 byte window -- rows by .. by + 3 from byte column bx, by =
+// clamp(sy - 1, 0, H - 4), bx = clamp(sx - 1, 0, W - 4) -- so a frame costs four 4-byte windows, as NV12 does, and no window leaves
+// its row or the plane.  Each clamped tap sits at offset 1 or 2 inside the window in both directions; its colour phase follows from
+// the parities of its clamped position and the pattern, a compile-time constant.
+template <int PATTERN>
+struct Bayer8 {
+    typedef uint32_t Window;
+    static constexpr int DENSE_PAD = 16;    // a slot's staging frame: 16 bytes of padding behind the last slot (the second dword of the last window's aligned load)
+    static constexpr int chan(int ch) { return 8 * ch; }   // (ba::demosaic: R | G << 8 | B << 16)
+    struct Taps { uint32_t r0, r1, r2, r3; };               // the window's four rows
+    int w, h;
+    int bx, ox0, ox1, px0, px1, by, oy0, oy1, py0, py1;
+    __device__ __forceinline__ void place(const TapCols& c) {
+        const ba::Axis a = ba::place_axis(c.cx0, c.cx1, w);
+        bx = a.origin, ox0 = a.o0, ox1 = a.o1, px0 = a.par0, px1 = a.par1;
+    }
+    __device__ __forceinline__ void place_rows(int cy0, int cy1) {
+        const ba::Axis a = ba::place_axis(cy0, cy1, h);
+        by = a.origin, oy0 = a.o0, oy1 = a.o1, py0 = a.par0, py1 = a.par1;
+    }
+    __device__ __forceinline__ static PlaneGeom plane(const FrontEndGeom& g, int) { return PlaneGeom{g.img_h, g.img_w, 0u}; }
+    template <class Source>
+    __device__ __forceinline__ Taps fetch(const Source& src, const typename Source::Frame& f, const FrontEndGeom& g, int, int) const {
+        const auto p0 = src.plane(f, plane(g, 0), 0);
+        return Taps{src.template window<Window>(p0, by, bx), src.template window<Window>(p0, by + 1, bx),
+                    src.template window<Window>(p0, by + 2, bx), src.template window<Window>(p0, by + 3, bx)};
+    }
+    __device__ __forceinline__ void decode(const Taps& t, uint32_t& a0, uint32_t& a1, uint32_t& b0, uint32_t& b1) const {
+        a0 = ba::window_tap(t.r0, t.r1, t.r2, t.r3, oy0, ox0, ba::phase_of(PATTERN, py0, px0));
+        a1 = ba::window_tap(t.r0, t.r1, t.r2, t.r3, oy0, ox1, ba::phase_of(PATTERN, py0, px1));
+        b0 = ba::window_tap(t.r0, t.r1, t.r2, t.r3, oy1, ox0, ba::phase_of(PATTERN, py1, px0));
+        b1 = ba::window_tap(t.r0, t.r1, t.r2, t.r3, oy1, ox1, ba::phase_of(PATTERN, py1, px1));
+    }
+};
+// a format whose windows depend on the sample's rows beyond cy0 / cy1 as they are says so, and is told them once per walk
+template <class F> struct PlacesRows : std::false_type {};
+template <int PATTERN> struct PlacesRows<Bayer8<PATTERN>> : std::true_type {};
+
 // The slots' own frames: `stride` bytes apart, planes dense.  One buffer resource covers the frames [z0, z1) of the walk (a frame
 // is selected by the scalar offset of the load) plus the format's padding behind them; beyond that the resource returns 0.
 // 32-bit offsets (a walk stays below 2^30 bytes: launch_undistort_rows) keep the address math on full-rate 24-bit multiplies.
@@ -370,6 +414,7 @@ __device__ __forceinline__ void undistort_walk(const WalkArgs& a, Source src, Fo
     const int cy0 = min(max(sy, 0), g.img_h - 1), cy1 = min(max(sy + 1, 0), g.img_h - 1);
     const TapCols cols{min(max(sx, 0), g.img_w - 2), min(max(sx, 0), g.img_w - 1), min(max(sx + 1, 0), g.img_w - 1)};
     fmt.place(cols);
+    if constexpr (PlacesRows<Format>::value) fmt.place_rows(cy0, cy1);
     const uint32_t m00 = (y0 && x0) ? 255u : 0u, m01 = (y0 && x1) ? 255u : 0u;
     const uint32_t m10 = (y1 && x0) ? 255u : 0u, m11 = (y1 && x1) ? 255u : 0u;
     const uint32_t gx = 32u - (uint32_t)fx, gy = 32u - (uint32_t)fy;
@@ -555,6 +600,43 @@ __global__ __launch_bounds__(256) void k_undistort_px_cal_surf(const SurfEntry* 
                                                               uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int remap) {
     undistort_walk(WalkArgs{nullptr, nullptr, g, und, und_px, first_slot, n, 1, remap},
                    SurfSource{tab}, PxFormat<F>{}, SlotTables{sets, &ids});
+}
+
+// ... and those of 8-bit raw Bayer, P = the pattern (layout - 16): 0 RGGB, 1 GRBG, 2 GBRG, 3 BGGR.
+template <int P>
+__global__ __launch_bounds__(256) void k_undistort_bayer(const uint8_t* __restrict__ frames, size_t frame_stride,
+                                                        const int16_t* __restrict__ uxy,
+                                                        const uint16_t* __restrict__ ufrac, FrontEndGeom g,
+                                                        uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb,
+                                                        int remap) {
+    undistort_walk(WalkArgs{uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap},
+                   SlotSource<true>{frames, frame_stride}, Bayer8<P>{g.img_w, g.img_h});
+}
+
+template <int P>
+__global__ __launch_bounds__(256) void k_undistort_bayer_surf(const SurfEntry* __restrict__ tab,
+                                                             const int16_t* __restrict__ uxy,
+                                                             const uint16_t* __restrict__ ufrac, FrontEndGeom g,
+                                                             uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb,
+                                                             int remap) {
+    undistort_walk(WalkArgs{uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap},
+                   SurfSource{tab}, Bayer8<P>{g.img_w, g.img_h});
+}
+
+template <int P>
+__global__ __launch_bounds__(256) void k_undistort_bayer_cal(const uint8_t* __restrict__ frames, size_t frame_stride,
+                                                            const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
+                                                            uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int remap) {
+    undistort_walk(WalkArgs{nullptr, nullptr, g, und, und_px, first_slot, n, 1, remap},
+                   SlotSource<true>{frames, frame_stride}, Bayer8<P>{g.img_w, g.img_h}, SlotTables{sets, &ids});
+}
+
+template <int P>
+__global__ __launch_bounds__(256) void k_undistort_bayer_cal_surf(const SurfEntry* __restrict__ tab,
+                                                                 const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
+                                                                 uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int remap) {
+    undistort_walk(WalkArgs{nullptr, nullptr, g, und, und_px, first_slot, n, 1, remap},
+                   SurfSource{tab}, Bayer8<P>{g.img_w, g.img_h}, SlotTables{sets, &ids});
 }
 
 // ---- 4:2:0 rows -> RGB rows ---------------------------------------------------------------------------------------------------
@@ -834,6 +916,84 @@ template <int F>
 __global__ __launch_bounds__(256) void k_surfpx_rows_to_rgb_any(SurfChunk ch, uint8_t* __restrict__ rgb, size_t rgb_stride, int w, int r0) {
     px_row1<F>(Plane422{reinterpret_cast<const uint8_t*>(ch.e[blockIdx.z].plane[0]), ch.e[blockIdx.z].pitch},
                rgb + (size_t)blockIdx.z * rgb_stride, w, r0 + (int)blockIdx.y, (int)(blockIdx.x * blockDim.x + threadIdx.x));
+}
+
+// ---- raw Bayer rows -> RGB rows ---------------------------------------------------------------------------------------------------
+// The same role for 8-bit raw Bayer (P = the pattern): row y of the RGB frame is the demosaic of row clamp(y, 1, h - 2) of the one
+// plane, column x that of column clamp(x, 1, w - 2) (bayer_arith.h).
+
+// One thread owns the 16 columns from x0 of row y (w a multiple of 16): 16 bytes of each of the three rows around the clamped row in
+// 16-byte loads and the byte on either side of them, 48 bytes in three 16-byte stores.
+template <int P>
+__device__ __forceinline__ void bayer_row16(const Plane422& s, uint8_t* dst, int h, int w, int y, int x0) {
+    if (x0 >= w) return;
+    const int cy = ba::tap_pos(y, h), xl = max(x0 - 1, 0), xr = min(x0 + 16, w - 1);
+    uint32_t m[3][4], left[3], right[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const uint8_t* row = s.p + (size_t)(cy - 1 + r) * s.pitch;
+        const uint4 q = *reinterpret_cast<const uint4*>(row + x0);
+        m[r][0] = q.x; m[r][1] = q.y; m[r][2] = q.z; m[r][3] = q.w;
+        left[r] = row[xl];
+        right[r] = row[xr];
+    }
+    // column x0 + j of row r of the three, j = -1 .. 16
+    auto at = [&](int r, int j) { return j < 0 ? left[r] : j > 15 ? right[r] : (m[r][j >> 2] >> (8 * (j & 3))) & 255u; };
+    uint32_t px[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j)             // (x0 is even: the column's parity is j's)
+        px[j] = ba::demosaic(at(1, j), at(1, j - 1) + at(1, j + 1), at(0, j) + at(2, j),
+                             at(0, j - 1) + at(0, j + 1) + at(2, j - 1) + at(2, j + 1), ba::phase(P, cy, j));
+    if (x0 == 0) px[0] = px[1];              // the frame's first and last column: their neighbours'
+    if (x0 + 16 == w) px[15] = px[14];
+    uint32_t d[12];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        d[3 * j] = px[4 * j] | (px[4 * j + 1] << 24);
+        d[3 * j + 1] = (px[4 * j + 1] >> 8) | (px[4 * j + 2] << 16);
+        d[3 * j + 2] = (px[4 * j + 2] >> 16) | (px[4 * j + 3] << 8);
+    }
+    uint4* o = reinterpret_cast<uint4*>(dst + ((size_t)y * w + x0) * 3);
+    o[0] = make_uint4(d[0], d[1], d[2], d[3]);
+    o[1] = make_uint4(d[4], d[5], d[6], d[7]);
+    o[2] = make_uint4(d[8], d[9], d[10], d[11]);
+}
+
+// the same for any width, any pitch and any alignment: one thread per pixel (column x of row y), byte accesses
+template <int P>
+__device__ __forceinline__ void bayer_row1(const Plane422& s, uint8_t* dst, int h, int w, int y, int x) {
+    if (x >= w) return;
+    const int cy = ba::tap_pos(y, h), cx = ba::tap_pos(x, w);
+    const uint8_t *up = s.p + (size_t)(cy - 1) * s.pitch + cx, *mid = up + s.pitch, *dn = mid + s.pitch;
+    const uint32_t v = ba::demosaic(mid[0], (uint32_t)mid[-1] + mid[1], (uint32_t)up[0] + dn[0], (uint32_t)up[-1] + up[1] + dn[-1] + dn[1],
+                                    ba::phase(P, cy, cx));
+    uint8_t* o = dst + ((size_t)y * w + x) * 3;
+    o[0] = (uint8_t)v;
+    o[1] = (uint8_t)(v >> 8);
+    o[2] = (uint8_t)(v >> 16);
+}
+
+// rows [r0, r0 + gridDim.y) of the slots' dense staging frames (frame blockIdx.z at raw + blockIdx.z * raw_stride) ...
+template <int P>
+__global__ __launch_bounds__(256) void k_bayer_rows_to_rgb(const uint8_t* __restrict__ raw, size_t raw_stride, uint8_t* __restrict__ rgb, size_t rgb_stride, int h, int w, int r0) {
+    bayer_row16<P>(Plane422{raw + (size_t)blockIdx.z * raw_stride, w}, rgb + (size_t)blockIdx.z * rgb_stride, h, w,
+                   r0 + (int)blockIdx.y, (int)(blockIdx.x * blockDim.x + threadIdx.x) * 16);
+}
+template <int P>
+__global__ __launch_bounds__(256) void k_bayer_rows_to_rgb_any(const uint8_t* __restrict__ raw, size_t raw_stride, uint8_t* __restrict__ rgb, size_t rgb_stride, int h, int w, int r0) {
+    bayer_row1<P>(Plane422{raw + (size_t)blockIdx.z * raw_stride, w}, rgb + (size_t)blockIdx.z * rgb_stride, h, w,
+                  r0 + (int)blockIdx.y, (int)(blockIdx.x * blockDim.x + threadIdx.x));
+}
+// ... and of surfaces (frame blockIdx.z is entry blockIdx.z of the chunk)
+template <int P>
+__global__ __launch_bounds__(256) void k_surfbayer_rows_to_rgb(SurfChunk ch, uint8_t* __restrict__ rgb, size_t rgb_stride, int h, int w, int r0) {
+    bayer_row16<P>(Plane422{reinterpret_cast<const uint8_t*>(ch.e[blockIdx.z].plane[0]), ch.e[blockIdx.z].pitch},
+                   rgb + (size_t)blockIdx.z * rgb_stride, h, w, r0 + (int)blockIdx.y, (int)(blockIdx.x * blockDim.x + threadIdx.x) * 16);
+}
+template <int P>
+__global__ __launch_bounds__(256) void k_surfbayer_rows_to_rgb_any(SurfChunk ch, uint8_t* __restrict__ rgb, size_t rgb_stride, int h, int w, int r0) {
+    bayer_row1<P>(Plane422{reinterpret_cast<const uint8_t*>(ch.e[blockIdx.z].plane[0]), ch.e[blockIdx.z].pitch},
+                  rgb + (size_t)blockIdx.z * rgb_stride, h, w, r0 + (int)blockIdx.y, (int)(blockIdx.x * blockDim.x + threadIdx.x));
 }
 
 // Rows [r0, r1) of RGB surfaces -> the same rows of the slots' camera frames (row_bytes = 3 w, dense): a pitched row copy, one
@@ -1256,6 +1416,15 @@ void launch_undistort_rows(hipStream_t s, FrameSource src, int layout, YuvCoef k
     if (!src.tab) fpb = (int)std::max<size_t>(1, std::min<size_t>((size_t)fpb, (((size_t)1 << 30) - 1) / src.stride));
     const dim3 grid((g.img_w + 255) / 256, g.nrows, (n + fpb - 1) / fpb), block(256);
     const int remap = xcd_remap();
+    if (layout >= 16) {                      // raw Bayer, pattern layout - 16
+        typedef void (*KS)(const SurfEntry*, const int16_t*, const uint16_t*, FrontEndGeom, uint32_t*, size_t, int, int, int, int);
+        typedef void (*KD)(const uint8_t*, size_t, const int16_t*, const uint16_t*, FrontEndGeom, uint32_t*, size_t, int, int, int, int);
+        static const KS surf[4] = {k_undistort_bayer_surf<0>, k_undistort_bayer_surf<1>, k_undistort_bayer_surf<2>, k_undistort_bayer_surf<3>};
+        static const KD dense[4] = {k_undistort_bayer<0>, k_undistort_bayer<1>, k_undistort_bayer<2>, k_undistort_bayer<3>};
+        if (src.tab) hipLaunchKernelGGL(surf[layout - 16], grid, block, 0, s, src.tab, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
+        else hipLaunchKernelGGL(dense[layout - 16], grid, block, 0, s, src.frames, src.stride, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
+        return;
+    }
     if (src.tab) {
         if (layout == 0) hipLaunchKernelGGL(k_undistort_rows_surf, grid, block, 0, s, src.tab, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
         else if (layout == 1) hipLaunchKernelGGL(k_undistort_rows_yuv_surf<1>, grid, block, 0, s, src.tab, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
@@ -1320,9 +1489,28 @@ static void launch_rows_px_to_rgb(hipStream_t s, int layout, const K (&wide)[3],
         hipLaunchKernelGGL(any[layout - 5], dim3((unsigned)((w + 255) / 256), rows, (unsigned)n), dim3(256), 0, s, args...);
 }
 
+// The raw Bayer row conversion of n frames (layout 16 + pattern): one launch row per frame row; wide[] / any[]: the 16-column and the
+// byte-wise kernels of the four patterns.
+template <class K, class... Args>
+static void launch_rows_bayer_to_rgb(hipStream_t s, int layout, const K (&wide)[4], const K (&any)[4], size_t bits, int w, int r0, int r1, int n, Args... args) {
+    const unsigned rows = (unsigned)(r1 - r0);
+    if ((w & 15) == 0 && (bits & 15) == 0)
+        hipLaunchKernelGGL(wide[layout - 16], dim3((unsigned)((w / 16 + 63) / 64), rows, (unsigned)n), dim3(64), 0, s, args...);
+    else
+        hipLaunchKernelGGL(any[layout - 16], dim3((unsigned)((w + 255) / 256), rows, (unsigned)n), dim3(256), 0, s, args...);
+}
+
 void launch_yuv_rows_to_rgb(hipStream_t s, int layout, const uint8_t* yuv, size_t yuv_stride, YuvCoef k, uint8_t* rgb,
                             size_t rgb_stride, int h, int w, int r0, int r1, int n) {
     if (n <= 0 || r1 <= r0) return;
+    if (layout >= 16) {
+        typedef void (*K)(const uint8_t*, size_t, uint8_t*, size_t, int, int, int);
+        static const K wide[4] = {k_bayer_rows_to_rgb<0>, k_bayer_rows_to_rgb<1>, k_bayer_rows_to_rgb<2>, k_bayer_rows_to_rgb<3>};
+        static const K any[4] = {k_bayer_rows_to_rgb_any<0>, k_bayer_rows_to_rgb_any<1>, k_bayer_rows_to_rgb_any<2>, k_bayer_rows_to_rgb_any<3>};
+        launch_rows_bayer_to_rgb(s, layout, wide, any, yuv_stride | rgb_stride | (size_t)(uintptr_t)yuv | (size_t)(uintptr_t)rgb, w, r0, r1, n,
+                                 yuv, yuv_stride, rgb, rgb_stride, h, w, r0);
+        return;
+    }
     if (layout >= 5) {
         typedef void (*K)(const uint8_t*, size_t, uint8_t*, size_t, int, int);
         static const K wide[3] = {k_px_rows_to_rgb<5>, k_px_rows_to_rgb<6>, k_px_rows_to_rgb<7>};
@@ -1351,7 +1539,7 @@ void launch_write_surf_entries(hipStream_t s, SurfEntry* tab, int first, const S
     }
 }
 
-void launch_surf_rows_to_rgb(hipStream_t s, int layout, const SurfEntry* entries, YuvCoef k, uint8_t* rgb, size_t rgb_stride, int w,
+void launch_surf_rows_to_rgb(hipStream_t s, int layout, const SurfEntry* entries, YuvCoef k, uint8_t* rgb, size_t rgb_stride, int h, int w,
                              int r0, int r1, int n) {
     if (n <= 0 || r1 <= r0) return;
     for (int i = 0; i < n; i += SurfChunk::N) {
@@ -1371,6 +1559,11 @@ void launch_surf_rows_to_rgb(hipStream_t s, int layout, const SurfEntry* entries
                 hipLaunchKernelGGL(k_surf_copy_rows<true>, dim3((unsigned)((row_bytes / 16 + 255) / 256), (unsigned)(r1 - r0), (unsigned)m), dim3(256), 0, s, ch, dst, rgb_stride, row_bytes, r0);
             else
                 hipLaunchKernelGGL(k_surf_copy_rows<false>, dim3((unsigned)((row_bytes + 255) / 256), (unsigned)(r1 - r0), (unsigned)m), dim3(256), 0, s, ch, dst, rgb_stride, row_bytes, r0);
+        } else if (layout >= 16) {
+            typedef void (*K)(SurfChunk, uint8_t*, size_t, int, int, int);
+            static const K wide[4] = {k_surfbayer_rows_to_rgb<0>, k_surfbayer_rows_to_rgb<1>, k_surfbayer_rows_to_rgb<2>, k_surfbayer_rows_to_rgb<3>};
+            static const K any[4] = {k_surfbayer_rows_to_rgb_any<0>, k_surfbayer_rows_to_rgb_any<1>, k_surfbayer_rows_to_rgb_any<2>, k_surfbayer_rows_to_rgb_any<3>};
+            launch_rows_bayer_to_rgb(s, layout, wide, any, bits, w, r0, r1, m, ch, dst, rgb_stride, h, w, r0);
         } else if (layout >= 5) {
             typedef void (*K)(SurfChunk, uint8_t*, size_t, int, int);
             static const K wide[3] = {k_surfpx_rows_to_rgb<5>, k_surfpx_rows_to_rgb<6>, k_surfpx_rows_to_rgb<7>};
@@ -1419,6 +1612,15 @@ void launch_undistort_cal(hipStream_t s, FrameSource src, int layout, YuvCoef k,
         const CalIds ci = pack_ids(ids + i, m);
         const dim3 grid((g.img_w + 255) / 256, g.nrows, m), block(256);
         const uint8_t* frames = src.tab ? nullptr : src.frames + (size_t)i * src.stride;
+        if (layout >= 16) {                  // raw Bayer, pattern layout - 16
+            typedef void (*KS)(const SurfEntry*, const CalTables*, CalIds, FrontEndGeom, uint32_t*, size_t, int, int, int);
+            typedef void (*KD)(const uint8_t*, size_t, const CalTables*, CalIds, FrontEndGeom, uint32_t*, size_t, int, int, int);
+            static const KS surf[4] = {k_undistort_bayer_cal_surf<0>, k_undistort_bayer_cal_surf<1>, k_undistort_bayer_cal_surf<2>, k_undistort_bayer_cal_surf<3>};
+            static const KD dense[4] = {k_undistort_bayer_cal<0>, k_undistort_bayer_cal<1>, k_undistort_bayer_cal<2>, k_undistort_bayer_cal<3>};
+            if (src.tab) hipLaunchKernelGGL(surf[layout - 16], grid, block, 0, s, src.tab, sets, ci, g, und, und_px, fs, m, remap);
+            else hipLaunchKernelGGL(dense[layout - 16], grid, block, 0, s, frames, src.stride, sets, ci, g, und, und_px, fs, m, remap);
+            continue;
+        }
         if (src.tab) {
             if (layout == 0) hipLaunchKernelGGL(k_undistort_cal_surf, grid, block, 0, s, src.tab, sets, ci, g, und, und_px, fs, m, remap);
             else if (layout == 1) hipLaunchKernelGGL(k_undistort_cal_yuv_surf<1>, grid, block, 0, s, src.tab, k, sets, ci, g, und, und_px, fs, m, remap);

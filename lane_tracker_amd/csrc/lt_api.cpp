@@ -24,6 +24,7 @@
 
 #include <hip/hip_ext.h>
 
+#include "bayer_arith.h"
 #include "front_arith.h"
 #include "lt_ctx.h"
 #include "resize_arith.h"
@@ -855,7 +856,7 @@ int lt_set_streams(lt_ctx* c, int nstreams) {
 static inline bool is_422(int layout) { return layout == LT_INPUT_YUY2 || layout == LT_INPUT_UYVY; }
 static int check_yuv_format(int layout, const int32_t* k, int h, int w) {
     if (layout != LT_INPUT_NV12 && layout != LT_INPUT_I420 && !is_422(layout))
-        return fail(LT_ERR_INVALID, "input layout must be RGB (0), NV12 (1), I420 (2), YUY2 (3), UYVY (4), BGR (5), RGBA (6) or BGRA (7)");
+        return fail(LT_ERR_INVALID, "input layout must be RGB (0), NV12 (1), I420 (2), YUY2 (3), UYVY (4), BGR (5), RGBA (6), BGRA (7) or raw Bayer (16 .. 19)");
     if (!k) return fail(LT_ERR_INVALID, "a YUV layout needs its five conversion coefficients");
     if (is_422(layout)) {
         // (two macropixels a row at the least: the 8-byte window of a tap row lies inside its row)
@@ -870,11 +871,26 @@ static int check_yuv_format(int layout, const int32_t* k, int h, int w) {
     return LT_OK;
 }
 
+// 8-bit raw Bayer: whole 2 x 2 blocks, and a 4 x 4 window of bytes (the neighbourhoods of a sample's four taps) inside the plane
+static int check_bayer_size(int h, int w) {
+    if (h < 4 || w < 4 || (h & 1) || (w & 1)) return fail(LT_ERR_INVALID, "raw Bayer frames need an even width and height of at least 4, got %dx%d", w, h);
+    return LT_OK;
+}
+// The rows of a slot's staging frame that the lt_upload_frame_rows family brings for the path's camera rows [cam_r0, cam_r1): those
+// rows themselves, or -- raw Bayer -- the rows that their taps' windows touch (bayer_arith.h: input_run).
+static void staged_run(const lt_ctx* c, int* r0, int* r1) {
+    *r0 = c->cam_r0;
+    *r1 = c->cam_r1;
+    if (is_bayer(c->in_layout) && c->cam_r1 > c->cam_r0) ba::input_run(c->cam_r0, c->cam_r1, c->calib.img_h, r0, r1);
+}
+
 int lt_set_input_format(lt_ctx* c, int layout, const int32_t* coeffs) {
     if (!c) return fail(LT_ERR_INVALID, "null context");
     int rc;
-    const bool plain = layout == LT_INPUT_RGB || is_rgb_family(layout);      // no conversion: `coeffs` is not read
-    if (is_rgb_family(layout)) {
+    const bool plain = layout == LT_INPUT_RGB || is_rgb_family(layout) || is_bayer(layout);      // no coefficients: `coeffs` is not read
+    if (is_bayer(layout)) {
+        if ((rc = check_bayer_size(c->calib.img_h, c->calib.img_w))) return rc;
+    } else if (is_rgb_family(layout)) {
         // (the 8-byte window of a tap row starts at column min(x, W - 2): two pixels a row at the least)
         if (c->calib.img_w < 2) return fail(LT_ERR_INVALID, "BGR / RGBA / BGRA frames need a width of at least 2, got %dx%d", c->calib.img_w, c->calib.img_h);
     } else if (layout != LT_INPUT_RGB && (rc = check_yuv_format(layout, coeffs, c->calib.img_h, c->calib.img_w))) return rc;
@@ -888,8 +904,8 @@ int lt_set_input_format(lt_ctx* c, int layout, const int32_t* coeffs) {
     if (layout == LT_INPUT_RGB) {
         dev_free(c->d_yuv);
     } else {
-        // the staging frame of a slot: h w 3 / 2 bytes (4:2:0), h w 2 (4:2:2), h w 3 (BGR) or h w 4 (RGBA / BGRA), slots a multiple of
-        // 16 apart
+        // the staging frame of a slot: h w 3 / 2 bytes (4:2:0), h w 2 (4:2:2), h w 3 (BGR), h w 4 (RGBA / BGRA) or h w (raw Bayer), slots a
+        // multiple of 16 apart
         const size_t bytes = packed_bpp(layout) ? c->frame_bytes / 3 * (size_t)packed_bpp(layout) : c->frame_bytes / 2, stride = (bytes + 15) & ~(size_t)15;
         if (stride != c->yuv_stride) dev_free(c->d_yuv);
         c->yuv_bytes = bytes;
@@ -1038,7 +1054,7 @@ int lt_get_input_size(lt_ctx* c, int* src_w, int* src_h) {
 int lt_get_input_rows(lt_ctx* c, int* row0, int* row1) {
     if (!c || !row0 || !row1) return fail(LT_ERR_INVALID, "null argument");
     if (resizes(c)) rs_input_rows(c, c->cam_r0, c->cam_r1, row0, row1);
-    else { *row0 = c->cam_r0; *row1 = c->cam_r1; }
+    else staged_run(c, row0, row1);
     return LT_OK;
 }
 
@@ -1213,14 +1229,17 @@ static int upload_frame_rows_impl(lt_ctx* c, const uint8_t* frames, int first, i
     if (c->in_layout != LT_INPUT_RGB) {
         // 4:2:0: the same rows of the Y plane and the chroma rows under them, into staging; nothing is converted.  The enqueued
         // copies are noted (yuv_rows): the conversion lt_upload_frame_rest puts on the copy stream reads these rows.
-        const int c0 = chroma_lo(c->cam_r0), c1 = chroma_hi(c->cam_r0, c->cam_r1);
+        // (raw Bayer: the rows the taps' windows touch)
+        int sr0, sr1;
+        staged_run(c, &sr0, &sr1);
+        const int c0 = chroma_lo(sr0), c1 = chroma_hi(sr0, sr1);
         if (enqueue)
             return for_each_slice(c, first, n, [&](hipStream_t st, int f0, int m) {
                 int wrc = enqueue_syncs ? (int)LT_OK : wait_camera_readers(c, st, f0, m);
-                if (!wrc) wrc = yuv_copy(c, frames + (size_t)(f0 - first) * c->yuv_bytes, f0, m, c->cam_r0, c->cam_r1, c0, c1, st);
+                if (!wrc) wrc = yuv_copy(c, frames + (size_t)(f0 - first) * c->yuv_bytes, f0, m, sr0, sr1, c0, c1, st);
                 return wrc ? wrc : note_range(c->yuv_rows, st, f0, f0 + m);
             });
-        if ((rc = yuv_copy(c, frames, first, n, c->cam_r0, c->cam_r1, c0, c1, c->stream))) return rc;
+        if ((rc = yuv_copy(c, frames, first, n, sr0, sr1, c0, c1, c->stream))) return rc;
         HIP_TRY(hipStreamSynchronize(c->stream));
         return LT_OK;
     }
@@ -1308,7 +1327,9 @@ int lt_upload_frame_rows_async(lt_ctx* c, const uint8_t* frames, int first, int 
     // overlay) -- not for the rest of their mask chains, and not for launches over other slots
     if ((rc = wait_camera_readers(c, c->copy, first, n))) return rc;
     if (c->in_layout != LT_INPUT_RGB) {
-        if ((rc = yuv_copy(c, frames, first, n, c->cam_r0, c->cam_r1, chroma_lo(c->cam_r0), chroma_hi(c->cam_r0, c->cam_r1), c->copy))) return rc;
+        int sr0, sr1;
+        staged_run(c, &sr0, &sr1);
+        if ((rc = yuv_copy(c, frames, first, n, sr0, sr1, chroma_lo(sr0), chroma_hi(sr0, sr1), c->copy))) return rc;
     } else if (resizes(c)) {
         // another size: copy and resize both on the copy stream, the slots' streams wait for the resize
         int s0, s1;
@@ -1358,14 +1379,18 @@ int lt_upload_frame_rest_rows(lt_ctx* c, const uint8_t* frames, int first, int n
     if ((rc = wait_camera_readers(c, c->copy, first, n))) return rc;
     // of the two runs, the rows lt_upload_frame_rows has not brought: below the window of rows the path reads, and above it
     const size_t row_bytes = (size_t)c->calib.img_w * 3;
-    const int lo = c->cam_r1 > c->cam_r0 ? c->cam_r0 : 0, hi = c->cam_r1 > c->cam_r0 ? c->cam_r1 : 0;
+    int lo, hi;
+    staged_run(c, &lo, &hi);
+    if (hi <= lo) lo = hi = 0;
     if (c->in_layout != LT_INPUT_RGB) {
         // 4:2:0: those rows of the Y plane and the chroma rows under them that the source rows' upload has not brought either, into
         // staging; then both runs whole -- the source rows they cover included, which lt_upload_frame_rows left in staging -- as RGB
         // into the camera frame
         const int c0 = chroma_lo(lo), c1 = chroma_hi(lo, hi);
         for (int k = 0; k < 4; k += 2) {
-            const int a = rows4[k], b = std::min(rows4[k + 1], lo), d = std::max(rows4[k], hi), e = rows4[k + 1];
+            int ra = rows4[k], re = rows4[k + 1];
+            if (is_bayer(c->in_layout) && re > ra) ba::support_run(ra, re, H, &ra, &re);     // the rows the demosaic of the run reads
+            const int a = ra, b = std::min(re, lo), d = std::max(ra, hi), e = re;
             if (b > a && (rc = yuv_copy(c, frames, first, n, a, b, chroma_lo(a), std::min(chroma_hi(a, b), c0), c->copy))) return rc;
             if (e > d && (rc = yuv_copy(c, frames, first, n, d, e, std::max(chroma_lo(d), c1), chroma_hi(d, e), c->copy))) return rc;
         }
@@ -1413,7 +1438,9 @@ int lt_upload_frame_rest(lt_ctx* c, const uint8_t* frames, int first, int n) {
     if (c->in_layout != LT_INPUT_RGB) {
         // 4:2:0: the rows of the Y and chroma planes that lt_upload_frame_rows has not brought into staging, then the whole frame as
         // RGB into the camera frame, behind both copies
-        const int H = c->calib.img_h, r0 = c->cam_r1 > c->cam_r0 ? c->cam_r0 : 0, r1 = c->cam_r1 > c->cam_r0 ? c->cam_r1 : 0;
+        const int H = c->calib.img_h;
+        int r0, r1;
+        staged_run(c, &r0, &r1);
         if (r1 <= r0) {
             if ((rc = yuv_copy(c, frames, first, n, 0, H, 0, H / 2, c->copy))) return rc;
         } else {
@@ -1586,7 +1613,7 @@ int lt_device_frames_rest(lt_ctx* c, int first, int n, const int32_t* rows4) {
     const int32_t* r = rows4 ? rows4 : whole;
     for (int k = 0; k < 4; k += 2)
         launch_surf_rows_to_rgb(c->copy, c->in_layout, &c->surf[(size_t)first], yuv_coef_of(c), slot_frame(c, first), c->frame_bytes,
-                                c->calib.img_w, r[k], r[k + 1], n);
+                                c->calib.img_h, c->calib.img_w, r[k], r[k + 1], n);
     HIP_TRY(hipGetLastError());
     if ((rc = note_range(c->readers, c->copy, first, first + n))) return rc;      // it reads the surfaces and writes the camera frames: the next upload waits
     if (!rows4) mark_frames(c, first, n, 1);
@@ -2654,6 +2681,31 @@ int lt_yuv_to_rgb(lt_ctx* c, const uint8_t* frame, int h, int w, int layout, con
     dev_free(d_in);
     dev_free(d_out);
     if (e != hipSuccess) return fail(LT_ERR_HIP, "YUV conversion failed: %s", hipGetErrorString(e));
+    return LT_OK;
+}
+
+// one 8-bit raw Bayer host frame of any even size from 4 x 4 (h w bytes) -> RGB, on the device: the bilinear demosaic of bayer_arith.h
+int lt_bayer_to_rgb(lt_ctx* c, const uint8_t* frame, int h, int w, int layout, uint8_t* out_rgb) {
+    if (!c || !frame || !out_rgb) return fail(LT_ERR_INVALID, "null argument");
+    if (!is_bayer(layout)) return fail(LT_ERR_INVALID, "lt_bayer_to_rgb takes the raw Bayer layouts (16 .. 19)");
+    int rc = check_bayer_size(h, w);
+    if (rc) return rc;
+    if (h > 16384 || w > 16384) return fail(LT_ERR_INVALID, "bad image size (at most 16384 x 16384)");
+    if ((rc = set_device(c))) return rc;
+    const size_t px = (size_t)h * w;
+    uint8_t *d_in = nullptr, *d_out = nullptr;
+    if ((rc = dev_alloc(&d_in, px))) return rc;
+    if ((rc = dev_alloc(&d_out, px * 3))) { dev_free(d_in); return rc; }
+    hipError_t e = hipMemcpyAsync(d_in, frame, px, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        launch_yuv_rows_to_rgb(c->stream, layout, d_in, px, YuvCoef{}, d_out, px * 3, h, w, 0, h, 1);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out_rgb, d_out, px * 3, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    dev_free(d_in);
+    dev_free(d_out);
+    if (e != hipSuccess) return fail(LT_ERR_HIP, "raw Bayer conversion failed: %s", hipGetErrorString(e));
     return LT_OK;
 }
 

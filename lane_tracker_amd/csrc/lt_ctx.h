@@ -152,7 +152,7 @@ struct lt_ctx {
     size_t frame_bytes = 0, und_bytes = 0, bev_bytes = 0;
     uint8_t *d_frames = nullptr, *d_bev = nullptr;
     // Input that is not RGB (lt_set_input_format): the caller's layout, the five conversion coefficients (YUV), and per slot a staging frame
-    // of yuv_bytes = h * w * 3 / 2 (4:2:0), h * w * 2 (packed 4:2:2), h * w * 3 (BGR) or h * w * 4 (RGBA / BGRA) bytes in that layout, yuv_stride (a multiple of 16) apart, 16 bytes of padding behind the last
+    // of yuv_bytes = h * w * 3 / 2 (4:2:0), h * w * 2 (packed 4:2:2), h * w * 3 (BGR), h * w * 4 (RGBA / BGRA) or h * w (raw Bayer) bytes in that layout, yuv_stride (a multiple of 16) apart, 16 bytes of padding behind the last
     // one (k_undistort_rows_yuv reads aligned 8-byte windows).  The undistortion reads the staging frame; the RGB camera frame
     // of a slot is written by k_yuv_rows_to_rgb behind the uploads that would have brought RGB rows for whoever shows the frame.
     int in_layout = 0;                        // LT_INPUT_RGB
@@ -348,9 +348,11 @@ inline uint8_t* slot_frame(const lt_ctx* c, int s) { return c->d_frames + (size_
 // What a layout is, by name and never by comparison of its number: the RGB family's other members (BGR, RGBA, BGRA: a channel
 // permutation of RGB, no coefficients), and the bytes a pixel of the layouts that are ONE plane of whole pixels (0 for 4:2:0).
 inline bool is_rgb_family(int layout) { return layout == LT_INPUT_BGR || layout == LT_INPUT_RGBA || layout == LT_INPUT_BGRA; }
+// 8-bit raw Bayer (RGGB, GRBG, GBRG, BGGR): one plane of one byte a pixel, an input format only
+inline bool is_bayer(int layout) { return layout >= LT_INPUT_BAYER_RGGB && layout <= LT_INPUT_BAYER_BGGR; }
 inline int packed_bpp(int layout) {
     return layout == LT_INPUT_RGB || layout == LT_INPUT_BGR ? 3 : layout == LT_INPUT_RGBA || layout == LT_INPUT_BGRA ? 4
-           : layout == LT_INPUT_YUY2 || layout == LT_INPUT_UYVY ? 2 : 0;
+           : layout == LT_INPUT_YUY2 || layout == LT_INPUT_UYVY ? 2 : is_bayer(layout) ? 1 : 0;
 }
 inline uint8_t* slot_yuv(const lt_ctx* c, int s) { return c->d_yuv + (size_t)s * c->yuv_stride; }
 inline uint8_t* slot_src(const lt_ctx* c, int s) { return c->d_src + (size_t)s * c->src_stride; }

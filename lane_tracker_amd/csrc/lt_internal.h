@@ -88,7 +88,7 @@ struct FrameSource {
     static FrameSource slots(const uint8_t* frames, size_t stride) { return FrameSource{nullptr, frames, stride}; }
     static FrameSource surfaces(const SurfEntry* tab) { return FrameSource{tab, nullptr, 0}; }
 };
-// the undistorted rows of n frames (layout 0 = RGB, 1 = NV12, 2 = I420, 3 = YUY2, 4 = UYVY, 5 = BGR, 6 = RGBA, 7 = BGRA; `k` is read for the YUV layouts only: every tap converted, then the
+// the undistorted rows of n frames (layout 0 = RGB, 1 = NV12, 2 = I420, 3 = YUY2, 4 = UYVY, 5 = BGR, 6 = RGBA, 7 = BGRA, 16 .. 19 = raw Bayer RGGB / GRBG / GBRG / BGGR; `k` is read for the YUV layouts only: every tap converted, then the
 // same blend); `und` is the base of the whole buffer, `first_slot` the absolute slot of frame 0 of the call
 void launch_undistort_rows(hipStream_t s, FrameSource src, int layout, YuvCoef k, const int16_t* uxy, const uint16_t* ufrac,
                            FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n);
@@ -117,8 +117,9 @@ void launch_warp_cal(hipStream_t s, const uint32_t* und, size_t und_px, int firs
                      uint8_t* planeB, size_t plane_stride, int n);
 // entries[0, n) (host memory, consumed before the call returns) -> tab[first, first + n), stream-ordered
 void launch_write_surf_entries(hipStream_t s, SurfEntry* tab, int first, const SurfEntry* entries, int n);
-// rows [r0, r1) of the n surfaces of entries[] (host memory) -> the same rows of n RGB frames: a conversion (4:2:0) or a pitched copy (RGB)
-void launch_surf_rows_to_rgb(hipStream_t s, int layout, const SurfEntry* entries, YuvCoef k, uint8_t* rgb, size_t rgb_stride, int w,
+// rows [r0, r1) of the n surfaces of entries[] (host memory) -> the same rows of n RGB frames of h x w: a conversion (YUV, raw Bayer), a
+// permutation (BGR, RGBA, BGRA) or a pitched copy (RGB)
+void launch_surf_rows_to_rgb(hipStream_t s, int layout, const SurfEntry* entries, YuvCoef k, uint8_t* rgb, size_t rgb_stride, int h, int w,
                              int r0, int r1, int n);
 // device sinks (k_sink.hip): n dense RGB frames of h x w, rgb_stride bytes apart -> the n surfaces of entries[] (host memory) in
 // `layout`: a pitched copy (RGB) or a conversion with coeffs[8] (4:2:0; h and w even; sink_arith.h), 32 surfaces per launch

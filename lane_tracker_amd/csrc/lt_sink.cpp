@@ -17,14 +17,14 @@ struct ByteRange { uintptr_t lo, hi; int surface, plane; };   // [lo, hi)
 
 // (rows, row bytes) of plane i of an h x w frame in `layout`
 inline void plane_geom(int layout, int h, int w, int i, int* rows, int* row_bytes) {
-    if (i == 0) { *rows = h; *row_bytes = packed_bpp(layout) ? packed_bpp(layout) * w : w; }   // (4:2:2: an attached camera surface only)
+    if (i == 0) { *rows = h; *row_bytes = packed_bpp(layout) ? packed_bpp(layout) * w : w; }   // (4:2:2, raw Bayer: an attached camera surface only)
     else { *rows = h / 2; *row_bytes = layout == LT_INPUT_NV12 ? w : w / 2; }
 }
 inline int plane_count(int layout) { return packed_bpp(layout) ? 1 : layout + 1; }
 
 int check_format(int layout, int h, int w, const int32_t* coeffs) {
     if (layout != LT_INPUT_RGB && layout != LT_INPUT_NV12 && layout != LT_INPUT_I420 && !is_rgb_family(layout))
-        return fail(LT_ERR_INVALID, "sink layout must be RGB (0), NV12 (1), I420 (2), BGR (5), RGBA (6) or BGRA (7): packed 4:2:2 is an input format only");
+        return fail(LT_ERR_INVALID, "sink layout must be RGB (0), NV12 (1), I420 (2), BGR (5), RGBA (6) or BGRA (7): packed 4:2:2 is an input format only, and so is raw Bayer");
     if (h < 1 || w < 1 || h > 16384 || w > 16384) return fail(LT_ERR_INVALID, "bad image size %dx%d (at most 16384 x 16384)", w, h);
     if (layout == LT_INPUT_RGB || is_rgb_family(layout)) return LT_OK;
     if ((h & 1) || (w & 1)) return fail(LT_ERR_INVALID, "4:2:0 surfaces need an even width and height, got %dx%d", w, h);

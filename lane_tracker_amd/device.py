@@ -12,7 +12,7 @@ refuses what its runtime does not know.  No framework is imported here.
 import numpy as np
 
 from . import _native
-from ._native import SURFACE_DTYPE, frame_shape, pixel_format_id
+from ._native import BAYER_FORMATS, SURFACE_DTYPE, frame_shape, pixel_format_id
 
 __all__ = ["DeviceBuffer", "DeviceFrames", "pack_host_frames", "feed_rows_list", "feed_rest_list"]
 
@@ -82,21 +82,23 @@ def _plane_rows(img_size, pixel_format):
     layout = pixel_format_id(pixel_format)
     frame_shape((w, h), pixel_format)                    # (ValueError for odd 4:2:0 sizes)
     bpp = _PIXEL_BYTES.get(layout)
-    if bpp:                                              # one plane of whole pixels: 3 W (RGB, BGR), 2 W (packed 4:2:2) or 4 W (RGBA, BGRA) bytes a row
+    if bpp:                                              # one plane of whole pixels: 3 W (RGB, BGR), 2 W (packed 4:2:2), 4 W (RGBA, BGRA) or W (raw Bayer) bytes a row
         return (h, bpp * w), None, 1
     return (h, w), ((h // 2, w) if layout == 1 else (h // 2, w // 2)), layout + 1
 
 
-_PIXEL_BYTES = {0: 3, 3: 2, 4: 2, 5: 3, 6: 4, 7: 4}       # bytes a pixel of the layouts that are one plane of whole pixels
+_PIXEL_BYTES = {0: 3, 3: 2, 4: 2, 5: 3, 6: 4, 7: 4, 16: 1, 17: 1, 18: 1, 19: 1}       # bytes a pixel of the layouts that are one plane of whole pixels
 
 
 def _frame_dims(layout):
     """-> (dimensions of one frame's array, its last axis or 0): RGB / BGR (H, W, 3), RGBA / BGRA (H, W, 4), packed 4:2:2 (H, W, 2),
-    4:2:0 (H * 3 // 2, W)."""
+    4:2:0 (H * 3 // 2, W); raw Bayer (H, W): no last axis, 1 stands for it."""
+    if _PIXEL_BYTES.get(layout) == 1:
+        return 2, 1
     return (3, _PIXEL_BYTES[layout]) if layout in _PIXEL_BYTES else (2, 0)
 
 
-_SHAPE_NAMES = {3: "(H, W, 3)", 4: "(H, W, 4)", 2: "(H, W, 2)", 0: "(H * 3 // 2, W)"}
+_SHAPE_NAMES = {3: "(H, W, 3)", 4: "(H, W, 4)", 2: "(H, W, 2)", 1: "(H, W)", 0: "(H * 3 // 2, W)"}
 
 
 def _extent(rows, row_bytes, pitch):
@@ -137,7 +139,7 @@ def _layout_block(n, img_size, pixel_format, pitch, chroma_pitch, offset):
 
 def pack_host_frames(frames, pixel_format="rgb", pitch=None, chroma_pitch=None, offset=0, fill=0):
     """Host frames -- (n, H, W, 3) / (H, W, 3) ('rgb', 'bgr'), (n, H, W, 4) / (H, W, 4) ('rgba', 'bgra'), (n, H * 3 // 2, W) /
-    (H * 3 // 2, W) for 4:2:0, or (n, H, W, 2) / (H, W, 2) for packed 4:2:2 -- laid out as pitched surfaces in
+    (H * 3 // 2, W) for 4:2:0, (n, H, W, 2) / (H, W, 2) for packed 4:2:2, or (n, H, W) / (H, W) for raw Bayer -- laid out as pitched surfaces in
     one block: frame after frame, plane after plane, every row `pitch` (chroma rows: `chroma_pitch`) bytes after the one before,
     the first at `offset`; bytes between and around the rows are `fill`.  The block ends with the last byte of the last plane.
     -> (the block as a u8 array, surfaces with plane OFFSETS into it, img_size, whether `frames` was one frame)."""
@@ -146,7 +148,7 @@ def pack_host_frames(frames, pixel_format="rgb", pitch=None, chroma_pitch=None, 
         raise ValueError("camera frames are uint8, got %s" % f.dtype)
     layout = pixel_format_id(pixel_format)
     nd, last = _frame_dims(layout)
-    if f.ndim not in (nd, nd + 1) or (last and f.shape[-1] != last):
+    if f.ndim not in (nd, nd + 1) or (last > 1 and f.shape[-1] != last):
         raise ValueError("expected camera frames of shape %s, got %r" % (_SHAPE_NAMES[last], f.shape))
     single = f.ndim == nd
     f = f[None] if single else f
@@ -172,7 +174,7 @@ def pack_host_frames(frames, pixel_format="rgb", pitch=None, chroma_pitch=None, 
 class DeviceFrames:
     """n camera frames of `img_size` = (width, height) in `pixel_format` somewhere in device memory: a description, not an owner
     (`owner` is whatever keeps the memory alive; it is only referenced).  `surfaces` is a SURFACE_DTYPE array, one entry per
-    frame: plane pointers (RGB, BGR, RGBA, BGRA, YUY2, UYVY: one; NV12: Y, UV; I420: Y, U, V), the pitch of plane 0 and the chroma pitch, in bytes.
+    frame: plane pointers (RGB, BGR, RGBA, BGRA, YUY2, UYVY, raw Bayer: one; NV12: Y, UV; I420: Y, U, V), the pitch of plane 0 and the chroma pitch, in bytes.
     `single`: made from one frame (what process() takes); `stream`: the producer's stream to wait for before the frames are read;
     `readonly`: the producer said so (`__cuda_array_interface__`'s data[1]) -- such frames are never drawn into (`out="inplace"`)."""
 
@@ -187,7 +189,7 @@ class DeviceFrames:
     @classmethod
     def from_planes(cls, planes, img_size, pixel_format, pitch, chroma_pitch=None, owner=None, stream=None, device=0):
         """Explicit pointers: `planes` is one tuple of plane addresses per frame (RGB: (rgb,); NV12: (y, uv); I420: (y, u, v); YUY2 /
-        UYVY: (plane,), pitch >= 2 W; BGR: (plane,), pitch >= 3 W; RGBA / BGRA: (plane,), pitch >= 4 W) --
+        UYVY: (plane,), pitch >= 2 W; BGR: (plane,), pitch >= 3 W; RGBA / BGRA: (plane,), pitch >= 4 W; raw Bayer: (plane,), pitch >= W) --
         or a single such tuple for one frame -- `pitch` / `chroma_pitch` the bytes between rows (one value, or one per frame)."""
         (rows, rb), chroma, nplanes = _plane_rows(img_size, pixel_format)
         single = len(planes) > 0 and not hasattr(planes[0], "__len__")
@@ -216,7 +218,8 @@ class DeviceFrames:
         """Anything with `__cuda_array_interface__` (or the dict itself): '|u1', shape (n, H, W, 3) / (H, W, 3) for RGB and
         (n, H * 3 // 2, W) / (H * 3 // 2, W) for NV12 / I420 with dense planes, (n, H, W, 2) / (H, W, 2) for YUY2 / UYVY (strides
         (frame, pitch, 2, 1), pitch >= 2 W), (n, H, W, 3) / (H, W, 3) for BGR as for RGB, (n, H, W, 4) / (H, W, 4) for RGBA / BGRA
-        (a pixel stride of 4: a `uint8` (H, W, 4) tensor); row and frame strides come from `strides`."""
+        (a pixel stride of 4: a `uint8` (H, W, 4) tensor), (n, H, W) / (H, W) for raw Bayer (strides (frame, pitch, 1), pitch >= W);
+        row and frame strides come from `strides`."""
         ai = obj if isinstance(obj, dict) else getattr(obj, "__cuda_array_interface__", None)
         if not isinstance(ai, dict):
             raise ValueError("the object has no __cuda_array_interface__")
@@ -229,7 +232,7 @@ class DeviceFrames:
         shape = tuple(int(v) for v in ai["shape"])
         layout = pixel_format_id(pixel_format)
         nd, last = _frame_dims(layout)
-        if len(shape) not in (nd, nd + 1) or (last and shape[-1] != last):
+        if len(shape) not in (nd, nd + 1) or (last > 1 and shape[-1] != last):
             raise ValueError("expected camera frames of shape %s, got %r" % (_SHAPE_NAMES[last], shape))
         if any(v <= 0 for v in shape[-nd:]):
             raise ValueError("empty camera frames: shape %r" % (shape,))
@@ -259,6 +262,11 @@ class DeviceFrames:
             if strides[-1] != 1 or strides[-2] != 2:
                 raise ValueError("4:2:2 frames are packed: a pixel stride of 2 and a sample stride of 1, got %r" % (strides[-2:],))
             pitch = strides[-3]
+        elif last == 1:
+            h, w = shape[-2], shape[-1]
+            if strides[-1] != 1:
+                raise ValueError("a raw Bayer plane holds one byte per pixel: a pixel stride of 1, got %d" % strides[-1])
+            pitch = strides[-2]
         else:
             if shape[-2] % 3:
                 raise ValueError("a 4:2:0 frame is a 2-D array of shape (H * 3 // 2, W) with H and W even, got %r" % (shape[-2:],))
@@ -303,6 +311,8 @@ class DeviceFrames:
         out=)` and `utils.rgb_to_yuv` write into and `to_host()` reads back.  `fill`: a byte value the whole block is set to first
         (None: whatever the memory held)."""
         n = int(n)
+        if pixel_format in BAYER_FORMATS:
+            raise ValueError("%r is an input format only: annotated frames go into 'rgb', 'bgr', 'rgba', 'bgra', 'nv12' or 'i420' surfaces" % (pixel_format,))
         if n < 0:
             raise ValueError("a sink holds zero or more frames, got %d" % n)
         size = (int(img_size[0]), int(img_size[1]))

@@ -70,7 +70,9 @@ class LaneTracker(StreamPipeline):
         # the camera's pixel format: 'rgb' frames (H, W, 3), YUV 4:2:0 as decoders hand it out -- 'nv12' / 'i420' frames
         # (H * 3 // 2, W) -- or packed 4:2:2 as cameras and capture cards do -- 'yuy2' / 'uyvy' frames (H, W, 2) -- converted on the
         # device with `yuv_matrix` ('bt601', 'bt709') -- or what users' own software holds: 'bgr' frames (H, W, 3) (OpenCV's order),
-        # 'rgba' / 'bgra' frames (H, W, 4), alpha never read: a channel permutation, `yuv_matrix` ignored as for 'rgb';
+        # 'rgba' / 'bgra' frames (H, W, 4), alpha never read: a channel permutation, `yuv_matrix` ignored as for 'rgb'; or what the
+        # sensor delivers before any image signal processor: 8-bit raw Bayer, 'bayer_rggb' / 'bayer_grbg' / 'bayer_gbrg' / 'bayer_bggr'
+        # frames (H, W), H and W even, demosaiced (bilinear) on the device, `yuv_matrix` ignored;
         # everything that comes back is RGB
         self.pixel_format, self.yuv_matrix = pixel_format, yuv_matrix
         self._frame_shape = _native.input_frame_shape(img_size, pixel_format)      # (ValueError: unknown format, odd 4:2:0 size, odd 4:2:2 width)

@@ -646,6 +646,8 @@ class StreamPipeline:
             raise ValueError("out='inplace' draws into the frames handed in: a tracker with input_size returns frames of img_size")
         if self.pixel_format in _native.PACKED_422:
             raise ValueError("out='inplace' draws into RGB, NV12 or I420 surfaces: %r is an input format only" % (self.pixel_format,))
+        if self.pixel_format in _native.BAYER_FORMATS:
+            raise ValueError("out='inplace' draws into RGB, NV12 or I420 surfaces: %r is an input format only" % (self.pixel_format,))
         if self.pixel_format in _native.RGB_FAMILY:
             raise ValueError("out='inplace' draws into RGB, NV12 or I420 surfaces: %r frames go into an out= sink" % (self.pixel_format,))
         if out_yuv_matrix is not None:

@@ -101,6 +101,28 @@ def yuv_to_rgb(frame, layout='nv12', matrix='bt601'):
     return _context_for_module_functions().yuv_to_rgb(frame, layout, matrix)
 
 
+def bayer_to_rgb(frame, pattern='bayer_rggb'):
+    """An 8-bit raw Bayer frame -- a u8 array (H, W), H and W even and at least 4, the sensor's mosaic with `pattern` ('bayer_rggb',
+    'bayer_grbg', 'bayer_gbrg', 'bayer_bggr': its top-left 2 x 2 block) -- or a stack (n, H, W) of them, to RGB (H, W, 3) /
+    (n, H, W, 3), on the device: the bilinear demosaic in integers, border pixels taking their interior neighbours' values.  This is
+    what `cv2.cvtColor(frame, cv2.COLOR_BayerRGGB2RGB)` (GRBG / GBRG / BGGR) is understood to compute, which was not checked against
+    OpenCV.  What a `LaneTracker(..., pixel_format=pattern)` sees of the frame."""
+    from . import _native
+    from .lane_tracker import _context_for_module_functions
+    if pattern not in _native.BAYER_FORMATS:
+        raise ValueError("pattern must be one of %s, got %r" % (", ".join(repr(n) for n in _native.BAYER_FORMATS), pattern))
+    a = np.ascontiguousarray(frame, np.uint8)
+    if a.ndim == 2:
+        return _context_for_module_functions().bayer_to_rgb(a, pattern)
+    if a.ndim != 3:
+        raise ValueError("a raw Bayer frame is an array (H, W), a stack of them (n, H, W); got %r" % (a.shape,))
+    ctx = _context_for_module_functions()
+    out = np.empty(a.shape + (3,), np.uint8)
+    for k in range(a.shape[0]):
+        out[k] = ctx.bayer_to_rgb(a[k], pattern)
+    return out
+
+
 def rgb_to_yuv(frame, layout='nv12', matrix='bt601'):
     """The counterpart of `yuv_to_rgb`: an RGB frame (H, W, 3), H and W even, to YUV 4:2:0 as OpenCV holds it -- a u8 array
     (H * 3 // 2, W): the Y plane, then interleaved U,V rows ('nv12') or the U plane and the V plane ('i420') -- on the device,

@@ -56,6 +56,12 @@ def _yuv_layout(path):
 
 
 _RGB_FAMILY = ("bgr", "rgba", "bgra")
+# 8-bit raw Bayer: headerless `.bayer` files; the suffix cannot name the pattern, the caller does (FrameSource's pixel_format)
+_BAYER = ("bayer_rggb", "bayer_grbg", "bayer_gbrg", "bayer_bggr")
+
+
+def _is_bayer_file(path):
+    return str(path).lower().endswith(".bayer")
 
 
 def _yuv_tail(pixel_format, width, height):
@@ -64,6 +70,10 @@ def _yuv_tail(pixel_format, width, height):
         if width < 2 or height < 1:
             raise ValueError(f"{pixel_format} frames need a width of at least 2, got {width}x{height}")
         return (height, width, 3 if pixel_format == "bgr" else 4), pixel_format.upper()
+    if pixel_format in _BAYER:
+        if width % 2 or height % 2 or width < 4 or height < 4:
+            raise ValueError(f"raw Bayer frames need an even width and height of at least 4, got {width}x{height}")
+        return (height, width), "raw Bayer"
     if pixel_format in ("yuy2", "uyvy"):
         if width % 2 or width < 4 or height < 1:
             raise ValueError(f"4:2:2 frames need an even width of at least 4, got {width}x{height}")
@@ -93,12 +103,15 @@ def resolve_clip_path(path, must_exist=True):
 class FrameSource:
     """Ordered u8 frames: RGB (n, H, W, 3), or -- `pixel_format` 'nv12' / 'i420', raw 4:2:0 files -- (n, H * 3 // 2, W), or --
     'yuy2' / 'uyvy', raw packed 4:2:2 files -- (n, H, W, 2), or -- 'bgr' / 'rgba' / 'bgra', raw files -- (n, H, W, 3) / (n, H, W, 4).
-    `size` = (width, height) is required for raw files only."""
+    Headerless 8-bit raw Bayer files (`.bayer`) hold frames (n, H, W); their suffix cannot name the pattern, so `pixel_format` must
+    ('bayer_rggb', 'bayer_grbg', 'bayer_gbrg', 'bayer_bggr').  `size` = (width, height) is required for raw files only."""
 
     pixel_format = "rgb"
 
-    def __init__(self, path, size=None):
+    def __init__(self, path, size=None, pixel_format=None):
         self.path = str(path)
+        if pixel_format in _BAYER and not _is_bayer_file(self.path):
+            raise ValueError(f"pixel_format={pixel_format!r} names the pattern of a raw .bayer file; {self.path!r} is none")
         self._files = None
         self._array = None
         self._tail = None                # shape of one frame
@@ -126,6 +139,22 @@ class FrameSource:
             self._n = nbytes // fb
             self._array = np.memmap(self.path, np.uint8, "r", shape=(self._n, self.height, self.width, 3)) if self._n \
                 else np.zeros((0, self.height, self.width, 3), np.uint8)
+        elif _is_bayer_file(self.path):
+            if pixel_format not in _BAYER:
+                raise ValueError(f"{self.path}: a .bayer file holds raw Bayer frames and its suffix cannot name the pattern: say which with "
+                                 "--pixel-format bayer_rggb / bayer_grbg / bayer_gbrg / bayer_bggr (FrameSource's pixel_format=)")
+            if size is None:
+                raise ValueError("raw Bayer input needs size=(width, height)")
+            self.pixel_format = pixel_format
+            self.width, self.height = int(size[0]), int(size[1])
+            self._tail, family = _yuv_tail(self.pixel_format, self.width, self.height)
+            fb = int(np.prod(self._tail))
+            nbytes = os.path.getsize(self.path)
+            if nbytes % fb:
+                raise ValueError(f"{self.path}: {nbytes} bytes is not a whole number of {self.width}x{self.height} {family} frames")
+            self._n = nbytes // fb
+            self._array = np.memmap(self.path, np.uint8, "r", shape=(self._n,) + self._tail) if self._n \
+                else np.zeros((0,) + self._tail, np.uint8)
         elif _yuv_layout(self.path):
             if size is None:
                 raise ValueError("raw 4:2:0 input needs size=(width, height)" if _yuv_layout(self.path) in ("nv12", "i420")
@@ -142,7 +171,7 @@ class FrameSource:
             self._array = np.memmap(self.path, np.uint8, "r", shape=(self._n,) + self._tail) if self._n \
                 else np.zeros((0,) + self._tail, np.uint8)
         else:
-            raise ValueError(f"unsupported frame source {self.path!r} (directory of images, .npy, .rgb/.raw, .bgr, .rgba, .bgra, .nv12, .i420/.yuv, .yuy2, .uyvy)")
+            raise ValueError(f"unsupported frame source {self.path!r} (directory of images, .npy, .rgb/.raw, .bgr, .rgba, .bgra, .nv12, .i420/.yuv, .yuy2, .uyvy, .bayer)")
         if self._tail is None:
             self._tail = (self.height, self.width, 3)
         if size is not None and (self.width, self.height) != (int(size[0]), int(size[1])):
@@ -339,8 +368,9 @@ def main(argv=None):
                     help="WxH of the input frames when that is not the calibration's size: raw RGB input is read in this size and the "
                          "tracker resizes the frames on the device (cv2.resize, INTER_LINEAR); what is written has the calibration's size")
     ap.add_argument("--window", type=int, default=64, help="frames per GPU batch")
-    ap.add_argument("--pixel-format", choices=("rgb", "nv12", "i420", "yuy2", "uyvy") + _RGB_FAMILY, default=None,
-                    help="pixel format of the input frames (default: by the input's name); must match a raw input's extension")
+    ap.add_argument("--pixel-format", choices=("rgb", "nv12", "i420", "yuy2", "uyvy") + _RGB_FAMILY + _BAYER, default=None,
+                    help="pixel format of the input frames (default: by the input's name); must match a raw input's extension; a raw "
+                         ".bayer input needs it: bayer_rggb / bayer_grbg / bayer_gbrg / bayer_bggr, the sensor's pattern")
     ap.add_argument("--yuv-matrix", choices=("bt601", "bt709"), default="bt601", help="conversion matrix of 4:2:0 / 4:2:2 input")
     ap.add_argument("--out-format", choices=("rgb", "nv12", "i420") + _RGB_FAMILY, default=None,
                     help="write the annotated frames through a device sink in this pixel format: a raw .rgb / .nv12 / .i420 file for "
@@ -371,7 +401,12 @@ def main(argv=None):
     M, Minv, image_wh, warped_wh, mppv, mpph = load_warp_params(a.warp)
     if a.input_size is not None and a.size is not None and tuple(a.size) != tuple(a.input_size):
         ap.error("--size %dx%d and --input-size %dx%d name two sizes for the input frames" % (tuple(a.size) + tuple(a.input_size)))
-    src = FrameSource(a.input, a.input_size or a.size or image_wh)
+    try:
+        src = FrameSource(a.input, a.input_size or a.size or image_wh, pixel_format=a.pixel_format if a.pixel_format in _BAYER else None)
+    except ValueError as e:
+        if not (_is_bayer_file(a.input) or a.pixel_format in _BAYER):
+            raise
+        ap.error(str(e))
     if a.pixel_format is not None and a.pixel_format != src.pixel_format:
         ap.error("--pixel-format %s, but %s holds %s frames" % (a.pixel_format, a.input, src.pixel_format))
     lt = LaneTracker(img_size=image_wh, warped_size=warped_wh, cam_matrix=cam_matrix, dist_coeffs=dist_coeffs,

@@ -12,7 +12,8 @@ Modes (one per invocation; every leg runs `--runs` times, the file holds each ru
                LaneTrackerGroup of 8 -- each fed DeviceFrames and, beside it, host arrays.
   --host-fed   the host-fed halves of --trackers alone (what an older checkout can run: its figures are the yardstick).
 
-`--pixel-format yuy2|uyvy|bgr|rgba|bgra` (repeatable) adds packed 4:2:2 legs, or legs in the RGB family's other members, to `--formats`; with --resident / --attached every leg also records
+`--pixel-format yuy2|uyvy|bgr|rgba|bgra|bayer_rggb|bayer_grbg|bayer_gbrg|bayer_bggr` (repeatable) adds packed 4:2:2 legs, legs in the RGB
+family's other members, or 8-bit raw Bayer legs to `--formats`; `--legs stream` keeps the process_stream leg alone of --trackers / --host-fed; with --resident / --attached every leg also records
 the `undistort_rows` stage time per 256 frames (lt_set_stage_timing: one timed mask run behind the measured steps).
 
 The `--runs` repetitions of a leg run back to back, one format after the other.  For runs that ALTERNATE between the formats (what
@@ -72,7 +73,17 @@ def rgb_to_422(rgb, fmt):
 
 PACKED = ("yuy2", "uyvy")
 RGB_FAMILY = ("bgr", "rgba", "bgra")
-ROW_BYTES = dict(rgb=3, yuy2=2, uyvy=2, bgr=3, rgba=4, bgra=4)          # bytes a pixel of plane 0 (1: the 4:2:0 formats)
+BAYER = ("bayer_rggb", "bayer_grbg", "bayer_gbrg", "bayer_bggr")
+ROW_BYTES = dict(rgb=3, yuy2=2, uyvy=2, bgr=3, rgba=4, bgra=4)          # bytes a pixel of plane 0 (1: the 4:2:0 formats and raw Bayer)
+
+
+def rgb_to_bayer(rgb, fmt):
+    """The mosaic of RGB frames (n, H, W, 3): every site keeps the channel the pattern's name gives it (only makes inputs)."""
+    ch = ["rgb".index(c) for c in fmt[len("bayer_"):]]
+    out = np.empty(rgb.shape[:-1], np.uint8)
+    for i, c in enumerate(ch):
+        out[:, i >> 1::2, i & 1::2] = rgb[:, i >> 1::2, i & 1::2, c]
+    return out
 
 
 def rgb_to_family(rgb, fmt):
@@ -89,7 +100,7 @@ def frames_for(cal, fmt, n, outage=False):
             pool[20:23] = 0             # a short outage: second tries, failure pictures
         _pools[key] = (np.stack([rgb_to_nv12(f) for f in pool]) if fmt == "nv12" else
                        np.stack([rgb_to_422(f, fmt) for f in pool]) if fmt in PACKED else
-                       rgb_to_family(pool, fmt) if fmt in RGB_FAMILY else pool)
+                       rgb_to_family(pool, fmt) if fmt in RGB_FAMILY else rgb_to_bayer(pool, fmt) if fmt in BAYER else pool)
     return np.ascontiguousarray(_pools[key][np.arange(n) % POOL])
 
 
@@ -207,8 +218,9 @@ def main():
     ap.add_argument("--streams", type=int, default=4)
     ap.add_argument("--sizes", default="1280x720,1920x1080")
     ap.add_argument("--formats", default="rgb,nv12")
-    ap.add_argument("--pixel-format", action="append", choices=PACKED + RGB_FAMILY, default=[],
-                    help="a packed 4:2:2 format, or another member of the RGB family, to measure beside --formats (repeatable)")
+    ap.add_argument("--pixel-format", action="append", choices=PACKED + RGB_FAMILY + BAYER, default=[],
+                    help="a packed 4:2:2 format, another member of the RGB family, or an 8-bit raw Bayer pattern, to measure beside --formats (repeatable)")
+    ap.add_argument("--legs", choices=("all", "stream"), default="all", help="--trackers / --host-fed: every leg, or process_stream alone")
     ap.add_argument("--out", default="-")
     ap.add_argument("--commit", default=None, help="the commit hash to record (default: git rev-parse HEAD of this checkout)")
     a = ap.parse_args()
@@ -231,6 +243,8 @@ def main():
         sys.exit("this checkout has no packed 4:2:2 input")
     if any(f in RGB_FAMILY for f in formats) and "bgr" not in getattr(_native, "RGB_FAMILY", {}):
         sys.exit("this checkout has no BGR / RGBA / BGRA input")
+    if any(f in BAYER for f in formats) and not hasattr(_native, "BAYER_FORMATS"):
+        sys.exit("this checkout has no raw Bayer input")
     if mode in ("resident", "attached"):
         cal = calib.reference_calibration()
         for fmt in formats:
@@ -251,7 +265,7 @@ def main():
                 for device in feeds:
                     note(dict(leg="process_stream", size=size, pixel_format=fmt, fed="device" if device else "host",
                               **summary([leg_stream(cal, fmt, frames, device) for _ in range(a.runs)])))
-                if size != "1280x720":
+                if size != "1280x720" or a.legs == "stream":
                     continue
                 for device in feeds:
                     note(dict(leg="process_annotated", size=size, pixel_format=fmt, fed="device" if device else "host",
