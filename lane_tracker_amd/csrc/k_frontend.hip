@@ -1,22 +1,16 @@
 // Geometric front end + colour split, gfx950.
 //
-//   k_undistort_rows   cv2.undistort            lane_tracker.py:832   (only the rows the warp reads)
-//   k_undistort_rows_yuv  the same over a 4:2:0 frame (NV12 / I420): cv2.cvtColor(YUV2RGB_*) of every tap, then the blend
-//   k_undistort_rows_surf, k_undistort_rows_yuv_surf  the same two over frames in the caller's device memory (surface table)
-//                      -- all of them entry points of one walk, undistort_walk<source, pixel format>
-//   k_undistort422, k_undistort422_surf, k_undistort422_cal, k_undistort422_cal_surf  the walk over packed 4:2:2 frames (YUY2 / UYVY):
-//                      slots, surfaces, and the table-per-slot forms of both; k_yuv422_rows_to_rgb, k_surf422_rows_to_rgb: their rows
-//                      as RGB (cv2.cvtColor(YUV2RGB_YUY2 / _UYVY)) for whoever shows the camera frame
-//   k_undistort_px, k_undistort_px_surf, k_undistort_px_cal, k_undistort_px_cal_surf  the walk over the RGB family's other members
-//                      (<5> BGR, <6> RGBA, <7> BGRA: a channel permutation, folded into the shifts the walk takes its channels out with);
-//                      k_px_rows_to_rgb, k_surfpx_rows_to_rgb: their rows as RGB for whoever shows the camera frame
-//   k_undistort_bayer, k_undistort_bayer_surf, k_undistort_bayer_cal, k_undistort_bayer_cal_surf  the walk over 8-bit raw Bayer frames
-//                      (<0> RGGB, <1> GRBG, <2> GBRG, <3> BGGR): every tap demosaiced (bilinear, bayer_arith.h) from one 4 x 4 byte window,
-//                      then the blend; k_bayer_rows_to_rgb, k_surfbayer_rows_to_rgb: their rows as RGB for whoever shows the camera frame
-//   k_undistort_cal*, k_warp_cal  the table-per-slot forms of the walk's seven entry points and of the warp: every slot of a launch with
-//                      the remap tables of its own calibration set (lt_add_calibration), for slices that mix sets
-//   k_yuv_rows_to_rgb, k_surf_rows_to_rgb  cv2.cvtColor(YUV2RGB_NV12 / _I420) of a run of rows (for whoever shows the camera
-//                      frame), from a slot's staging frame / from a surface: one 16-column and one byte-wise body
+//   k_undistort_rows<LAYOUT, SRC, PER_SLOT>  cv2.undistort  lane_tracker.py:832   (only the rows the warp reads): the one entry point of
+//                      the one walk, undistort_walk<source, pixel format>.  LAYOUT, the frames' pixel format: 0 RGB; 1 NV12, 2 I420
+//                      (cv2.cvtColor(YUV2RGB_*) of every tap, then the blend); 3 YUY2, 4 UYVY (packed 4:2:2); 5 BGR, 6 RGBA, 7 BGRA (a
+//                      channel permutation, folded into the shifts the walk takes its channels out with); 16 .. 19 8-bit raw Bayer RGGB /
+//                      GRBG / GBRG / BGGR (every tap demosaiced -- bilinear, bayer_arith.h -- from one 4 x 4 byte window).  SRC: 0 frames
+//                      in the caller's device memory (surface table), 1 / 2 the slots' own frames, dword-aligned / at any byte (RGB).
+//                      PER_SLOT: every slot of a launch with the remap tables of its own calibration set (lt_add_calibration), for
+//                      slices that mix sets; k_warp_cal: the same form of the warp
+//   k_rows_to_rgb<LAYOUT, SURF, WIDE>  a run of rows of frames in LAYOUT (not 0) as RGB, for whoever shows the camera frame
+//                      (cv2.cvtColor(YUV2RGB_NV12 / _I420 / _YUY2 / _UYVY), a permutation, the demosaic), from a slot's staging frame / from
+//                      a surface (SURF): one 16-column (WIDE) and one byte-wise body per family of layouts; k_surf_copy_rows: RGB surfaces
 //   k_warp_split       cv2.warpPerspective      lane_tracker.py:834
 //                      + img[:,:,0]             lane_tracker.py:207
 //                      + cvtColor(RGB2LAB)[:,:,2] lane_tracker.py:208
@@ -366,29 +360,28 @@ struct SurfSource {
     __device__ __forceinline__ uint64_t dwords2(const Plane& pl, int row, int col) const { return window<uint64_t>(pl, row, col); }
 };
 
+// Whose remap table a walk reads: the launch's one table (a.uxy, a.ufrac), or -- PER_SLOT, the table-per-slot form, one frame per
+// walk -- that of the calibration set of the walk's slot (a.tabs).  The slot is wave-uniform, so its set's id (a byte of the
+// kernel argument) and the set's entry of the set table (device memory) arrive by scalar loads, as a surface's entry does.
+struct SlotTables {
+    const CalTables* sets;
+    const CalIds* ids;
+    __device__ __forceinline__ const CalTables& of(int z) const { return sets[(ids->w[z >> 2] >> (8 * (z & 3))) & 255u]; }
+};
+
 // What the kernels below hand to the walk besides their source and format.
 struct WalkArgs {
     const int16_t* uxy;
     const uint16_t* ufrac;
+    SlotTables tabs;
     FrontEndGeom g;
     uint32_t* und;
     size_t und_px;
     int first_slot, n, fpb, remap;
 };
 
-// Whose remap table a walk reads: the launch's one table (a.uxy, a.ufrac), or -- the table-per-slot form, one frame per walk --
-// that of the calibration set of the walk's slot.  The slot is wave-uniform, so its set's id (a byte of the kernel argument) and the
-// set's entry of the set table (device memory) arrive by scalar loads, as a surface's entry does.
-struct OneTable { static constexpr bool PER_SLOT = false; };
-struct SlotTables {
-    static constexpr bool PER_SLOT = true;
-    const CalTables* sets;
-    const CalIds* ids;
-    __device__ __forceinline__ const CalTables& of(int z) const { return sets[(ids->w[z >> 2] >> (8 * (z & 3))) & 255u]; }
-};
-
-template <class Source, class Format, class Tables = OneTable>
-__device__ __forceinline__ void undistort_walk(const WalkArgs& a, Source src, Format fmt, Tables tabs = Tables{}) {
+template <bool PER_SLOT, class Source, class Format>
+__device__ __forceinline__ void undistort_walk(const WalkArgs& a, Source src, Format fmt) {
     const FrontEndGeom& g = a.g;
     const uint32_t per_z = gridDim.x * gridDim.y;
     const uint32_t id = xcd_block((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x, per_z * gridDim.z, a.remap);
@@ -402,8 +395,8 @@ __device__ __forceinline__ void undistort_walk(const WalkArgs& a, Source src, Fo
     const size_t o = (size_t)row * g.img_w + x;
     const int16_t* uxy = a.uxy;
     const uint16_t* ufrac = a.ufrac;
-    if constexpr (Tables::PER_SLOT) {        // (fpb == 1: the walk is slot first_slot + z0's)
-        const CalTables& t = tabs.of(z0);
+    if constexpr (PER_SLOT) {                // (fpb == 1: the walk is slot first_slot + z0's)
+        const CalTables& t = a.tabs.of(z0);
         uxy = t.uxy;
         ufrac = t.ufrac;
     }
@@ -453,299 +446,273 @@ __device__ __forceinline__ void undistort_walk(const WalkArgs& a, Source src, Fo
     }
 }
 
-// The entry points: source x format.  (Their names and parameter lists are what the profiles and tools know them by.)
-template <bool ALIGNED4>
-__global__ __launch_bounds__(256) void k_undistort_rows(const uint8_t* __restrict__ frames, size_t frame_stride,
-                                                       const int16_t* __restrict__ uxy,
-                                                       const uint16_t* __restrict__ ufrac, FrontEndGeom g,
-                                                       uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb,
-                                                       int remap) {
-    undistort_walk(WalkArgs{uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap},
-                   SlotSource<ALIGNED4>{frames, frame_stride}, Rgb24{});
-}
-
+// The layout of a frame (lt_internal.h: launch_undistort_rows) as the walk's pixel format -- the one place where the number becomes a type.
 template <int LAYOUT>
-__global__ __launch_bounds__(256) void k_undistort_rows_yuv(const uint8_t* __restrict__ yuv, size_t yuv_stride, YuvCoef k,
-                                                           const int16_t* __restrict__ uxy,
-                                                           const uint16_t* __restrict__ ufrac, FrontEndGeom g,
-                                                           uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb,
-                                                           int remap) {
-    undistort_walk(WalkArgs{uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap},
-                   SlotSource<true>{yuv, yuv_stride}, Yuv420<LAYOUT>{k});
+__device__ __forceinline__ auto format_of(const FrontEndGeom& g, const YuvCoef& k) {
+    if constexpr (LAYOUT == 0) return Rgb24{};
+    else if constexpr (LAYOUT <= 2) return Yuv420<LAYOUT>{k};
+    else if constexpr (LAYOUT <= 4) return Yuv422<LAYOUT - 3>{k, (g.img_w >> 1) - 2};
+    else if constexpr (LAYOUT <= 7) return PxFormat<LAYOUT>{};
+    else return Bayer8<LAYOUT - 16>{g.img_w, g.img_h};
 }
 
-__global__ __launch_bounds__(256) void k_undistort_rows_surf(const SurfEntry* __restrict__ tab,
-                                                            const int16_t* __restrict__ uxy,
-                                                            const uint16_t* __restrict__ ufrac, FrontEndGeom g,
-                                                            uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb,
-                                                            int remap) {
-    undistort_walk(WalkArgs{uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap},
-                   SurfSource{tab}, Rgb24{});
+// The walk's one entry point: layout x source x table form.  SRC: where the frames lie -- the caller's surfaces (`tab`), or the slots'
+// own frames (`frames`, `stride`) at a dword-aligned base and stride or at any byte (plain RGB only; a staging frame of every other
+// layout is dword-aligned: lt_set_input_format).  PER_SLOT: the table-per-slot form (a context whose slots hold cameras of different
+// calibrations: a slice that mixes sets) -- one frame per walk, with the tables sets[id] of its slot, `ids`: the sets of slots
+// first_slot, first_slot + 1, ...; else the launch's one table uxy / ufrac and fpb frames per walk.  Every form has the same parameter
+// list and reads what it needs: `k` the YUV layouts.  (The name is what the profiles and tools know the walks by.)
+constexpr int SRC_SURFACES = 0, SRC_SLOTS = 1, SRC_SLOTS_ANY_BYTE = 2;
+template <int LAYOUT, int SRC, bool PER_SLOT>
+__global__ __launch_bounds__(256) void k_undistort_rows(const SurfEntry* __restrict__ tab, const uint8_t* __restrict__ frames, size_t stride,
+                                                       YuvCoef k, const int16_t* __restrict__ uxy, const uint16_t* __restrict__ ufrac,
+                                                       const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
+                                                       uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb, int remap) {
+    static_assert(SRC != SRC_SLOTS_ANY_BYTE || LAYOUT == 0, "only plain RGB frames lie at any byte");
+    const WalkArgs a{uxy, ufrac, SlotTables{sets, &ids}, g, und, und_px, first_slot, n, PER_SLOT ? 1 : fpb, remap};
+    if constexpr (SRC == SRC_SURFACES) undistort_walk<PER_SLOT>(a, SurfSource{tab}, format_of<LAYOUT>(g, k));
+    else undistort_walk<PER_SLOT>(a, SlotSource<SRC == SRC_SLOTS>{frames, stride}, format_of<LAYOUT>(g, k));
 }
 
-template <int LAYOUT>
-__global__ __launch_bounds__(256) void k_undistort_rows_yuv_surf(const SurfEntry* __restrict__ tab, YuvCoef k,
-                                                                const int16_t* __restrict__ uxy,
-                                                                const uint16_t* __restrict__ ufrac, FrontEndGeom g,
-                                                                uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb,
-                                                                int remap) {
-    undistort_walk(WalkArgs{uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap},
-                   SurfSource{tab}, Yuv420<LAYOUT>{k});
-}
-
-// ... and the table-per-slot forms of the same seven (a context whose slots hold cameras of different calibrations: a slice that
-// mixes sets).  One frame per walk; `ids`: the sets of slots first_slot, first_slot + 1, ...
-template <bool ALIGNED4>
-__global__ __launch_bounds__(256) void k_undistort_cal(const uint8_t* __restrict__ frames, size_t frame_stride,
-                                                      const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
-                                                      uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int remap) {
-    undistort_walk(WalkArgs{nullptr, nullptr, g, und, und_px, first_slot, n, 1, remap},
-                   SlotSource<ALIGNED4>{frames, frame_stride}, Rgb24{}, SlotTables{sets, &ids});
-}
-
-template <int LAYOUT>
-__global__ __launch_bounds__(256) void k_undistort_cal_yuv(const uint8_t* __restrict__ yuv, size_t yuv_stride, YuvCoef k,
-                                                          const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
-                                                          uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int remap) {
-    undistort_walk(WalkArgs{nullptr, nullptr, g, und, und_px, first_slot, n, 1, remap},
-                   SlotSource<true>{yuv, yuv_stride}, Yuv420<LAYOUT>{k}, SlotTables{sets, &ids});
-}
-
-__global__ __launch_bounds__(256) void k_undistort_cal_surf(const SurfEntry* __restrict__ tab,
-                                                           const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
-                                                           uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int remap) {
-    undistort_walk(WalkArgs{nullptr, nullptr, g, und, und_px, first_slot, n, 1, remap},
-                   SurfSource{tab}, Rgb24{}, SlotTables{sets, &ids});
-}
-
-template <int LAYOUT>
-__global__ __launch_bounds__(256) void k_undistort_cal_yuv_surf(const SurfEntry* __restrict__ tab, YuvCoef k,
-                                                               const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
-                                                               uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int remap) {
-    undistort_walk(WalkArgs{nullptr, nullptr, g, und, und_px, first_slot, n, 1, remap},
-                   SurfSource{tab}, Yuv420<LAYOUT>{k}, SlotTables{sets, &ids});
-}
-
-// ... and the eight entry points of the packed 4:2:2 formats (ORDER 0: YUY2, 1: UYVY): slots, surfaces, and the table-per-slot forms
-// of both.
-template <int ORDER>
-__global__ __launch_bounds__(256) void k_undistort422(const uint8_t* __restrict__ yuv, size_t yuv_stride, YuvCoef k,
-                                                     const int16_t* __restrict__ uxy,
-                                                     const uint16_t* __restrict__ ufrac, FrontEndGeom g,
-                                                     uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb,
-                                                     int remap) {
-    undistort_walk(WalkArgs{uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap},
-                   SlotSource<true>{yuv, yuv_stride}, Yuv422<ORDER>{k, (g.img_w >> 1) - 2});
-}
-
-template <int ORDER>
-__global__ __launch_bounds__(256) void k_undistort422_surf(const SurfEntry* __restrict__ tab, YuvCoef k,
-                                                          const int16_t* __restrict__ uxy,
-                                                          const uint16_t* __restrict__ ufrac, FrontEndGeom g,
-                                                          uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb,
-                                                          int remap) {
-    undistort_walk(WalkArgs{uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap},
-                   SurfSource{tab}, Yuv422<ORDER>{k, (g.img_w >> 1) - 2});
-}
-
-template <int ORDER>
-__global__ __launch_bounds__(256) void k_undistort422_cal(const uint8_t* __restrict__ yuv, size_t yuv_stride, YuvCoef k,
-                                                         const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
-                                                         uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int remap) {
-    undistort_walk(WalkArgs{nullptr, nullptr, g, und, und_px, first_slot, n, 1, remap},
-                   SlotSource<true>{yuv, yuv_stride}, Yuv422<ORDER>{k, (g.img_w >> 1) - 2}, SlotTables{sets, &ids});
-}
-
-template <int ORDER>
-__global__ __launch_bounds__(256) void k_undistort422_cal_surf(const SurfEntry* __restrict__ tab, YuvCoef k,
-                                                              const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
-                                                              uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int remap) {
-    undistort_walk(WalkArgs{nullptr, nullptr, g, und, und_px, first_slot, n, 1, remap},
-                   SurfSource{tab}, Yuv422<ORDER>{k, (g.img_w >> 1) - 2}, SlotTables{sets, &ids});
-}
-
-// ... and those of the RGB family's other members, F = the layout: 5 BGR, 6 RGBA, 7 BGRA.  A slot's staging frame is dword-aligned
-// (lt_set_input_format), so the slot forms are SlotSource<true>'s.
-template <int F>
-__global__ __launch_bounds__(256) void k_undistort_px(const uint8_t* __restrict__ frames, size_t frame_stride,
-                                                     const int16_t* __restrict__ uxy,
-                                                     const uint16_t* __restrict__ ufrac, FrontEndGeom g,
-                                                     uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb,
-                                                     int remap) {
-    undistort_walk(WalkArgs{uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap},
-                   SlotSource<true>{frames, frame_stride}, PxFormat<F>{});
-}
-
-template <int F>
-__global__ __launch_bounds__(256) void k_undistort_px_surf(const SurfEntry* __restrict__ tab,
-                                                          const int16_t* __restrict__ uxy,
-                                                          const uint16_t* __restrict__ ufrac, FrontEndGeom g,
-                                                          uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb,
-                                                          int remap) {
-    undistort_walk(WalkArgs{uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap},
-                   SurfSource{tab}, PxFormat<F>{});
-}
-
-template <int F>
-__global__ __launch_bounds__(256) void k_undistort_px_cal(const uint8_t* __restrict__ frames, size_t frame_stride,
-                                                         const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
-                                                         uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int remap) {
-    undistort_walk(WalkArgs{nullptr, nullptr, g, und, und_px, first_slot, n, 1, remap},
-                   SlotSource<true>{frames, frame_stride}, PxFormat<F>{}, SlotTables{sets, &ids});
-}
-
-template <int F>
-__global__ __launch_bounds__(256) void k_undistort_px_cal_surf(const SurfEntry* __restrict__ tab,
-                                                              const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
-                                                              uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int remap) {
-    undistort_walk(WalkArgs{nullptr, nullptr, g, und, und_px, first_slot, n, 1, remap},
-                   SurfSource{tab}, PxFormat<F>{}, SlotTables{sets, &ids});
-}
-
-// ... and those of 8-bit raw Bayer, P = the pattern (layout - 16): 0 RGGB, 1 GRBG, 2 GBRG, 3 BGGR.
-template <int P>
-__global__ __launch_bounds__(256) void k_undistort_bayer(const uint8_t* __restrict__ frames, size_t frame_stride,
-                                                        const int16_t* __restrict__ uxy,
-                                                        const uint16_t* __restrict__ ufrac, FrontEndGeom g,
-                                                        uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb,
-                                                        int remap) {
-    undistort_walk(WalkArgs{uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap},
-                   SlotSource<true>{frames, frame_stride}, Bayer8<P>{g.img_w, g.img_h});
-}
-
-template <int P>
-__global__ __launch_bounds__(256) void k_undistort_bayer_surf(const SurfEntry* __restrict__ tab,
-                                                             const int16_t* __restrict__ uxy,
-                                                             const uint16_t* __restrict__ ufrac, FrontEndGeom g,
-                                                             uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb,
-                                                             int remap) {
-    undistort_walk(WalkArgs{uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap},
-                   SurfSource{tab}, Bayer8<P>{g.img_w, g.img_h});
-}
-
-template <int P>
-__global__ __launch_bounds__(256) void k_undistort_bayer_cal(const uint8_t* __restrict__ frames, size_t frame_stride,
-                                                            const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
-                                                            uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int remap) {
-    undistort_walk(WalkArgs{nullptr, nullptr, g, und, und_px, first_slot, n, 1, remap},
-                   SlotSource<true>{frames, frame_stride}, Bayer8<P>{g.img_w, g.img_h}, SlotTables{sets, &ids});
-}
-
-template <int P>
-__global__ __launch_bounds__(256) void k_undistort_bayer_cal_surf(const SurfEntry* __restrict__ tab,
-                                                                 const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
-                                                                 uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int remap) {
-    undistort_walk(WalkArgs{nullptr, nullptr, g, und, und_px, first_slot, n, 1, remap},
-                   SurfSource{tab}, Bayer8<P>{g.img_w, g.img_h}, SlotTables{sets, &ids});
-}
-
-// ---- 4:2:0 rows -> RGB rows ---------------------------------------------------------------------------------------------------
-// Rows [r0, r1) of 4:2:0 frames -> the same rows of RGB frames (3 B/px): a streaming kernel for whoever shows the camera frame.
-// The planes of one frame: the dense entry points compute them from the frame's base, the surface ones read them from the entry.
-struct YuvPlanes {
-    const uint8_t *y, *u, *v;                // u: NV12's plane of (U, V) pairs; v: I420 only
+// ---- camera rows -> RGB rows ---------------------------------------------------------------------------------------------------
+// Rows [r0, r1) of frames in another layout -> the same rows of RGB frames (3 B/px): a streaming kernel for whoever shows the camera
+// frame.  Per family of layouts a description (Rows420, Rows422, RowsPx, RowsBayer) holds what its conversion is made of:
+//   wide         the body of a thread that owns the 16 columns from x0: 16-byte loads, 48 bytes per row in three 16-byte stores (for a
+//                width and every base and pitch that are multiples of 16)
+//   any          the body for any width, any pitch and any alignment, byte accesses: thread i owns the ANY_COLS columns from ANY_COLS * i
+//   CHROMA_ROWS  a launch row `row` is a chroma row, the frame rows 2 row and 2 row + 1 (4:2:0); else the frame row itself
+//   dense        the planes of a slot's dense staging frame (a surface's planes and pitches: its entry)
+// Both bodies take (planes, k, dst frame, h, w, r0, r1, row, x0 or i).
+struct Planes {
+    const uint8_t *y, *u, *v;                // y: the one plane of a single-plane layout; u: NV12's plane of (U, V) pairs; v: I420 only
     int pitch, cpitch;
 };
-template <int LAYOUT>
-__device__ __forceinline__ YuvPlanes dense_planes(const uint8_t* frame, int h, int w) {
-    const size_t plane = (size_t)h * w;
-    return YuvPlanes{frame, frame + plane, frame + plane + (plane >> 2), w, LAYOUT == 1 ? w : w >> 1};
-}
-__device__ __forceinline__ YuvPlanes surf_planes(const SurfEntry& e) {
-    return YuvPlanes{reinterpret_cast<const uint8_t*>(e.plane[0]), reinterpret_cast<const uint8_t*>(e.plane[1]),
-                     reinterpret_cast<const uint8_t*>(e.plane[2]), e.pitch, e.cpitch};
+__device__ __forceinline__ Planes surf_planes(const SurfEntry& e) {
+    return Planes{reinterpret_cast<const uint8_t*>(e.plane[0]), reinterpret_cast<const uint8_t*>(e.plane[1]),
+                  reinterpret_cast<const uint8_t*>(e.plane[2]), e.pitch, e.cpitch};
 }
 
-// One thread owns the two rows of chroma row `cr` over the 16 columns from x0: 16 Y bytes per row and the 8 (U, V) pairs under
-// them in 16-byte loads, each pair's three chroma terms computed once for its four pixels, 48 bytes per row in three 16-byte
-// stores.  Either row of the pair may lie outside [r0, r1) (block-uniform) and is then neither read nor written.
+// The tail of the wide bodies: four pixels (R | G << 8 | B << 16) -> the three dwords of their 12 bytes, and the twelve dwords of 16
+// pixels -> 48 bytes at `at` in three 16-byte stores
+__device__ __forceinline__ void pack_rgb4(const uint32_t* px, uint32_t* d) {
+    d[0] = px[0] | (px[1] << 24);
+    d[1] = (px[1] >> 8) | (px[2] << 16);
+    d[2] = (px[2] >> 16) | (px[3] << 8);
+}
+__device__ __forceinline__ void store_rgb16(uint8_t* at, const uint32_t (&d)[12]) {
+    uint4* o = reinterpret_cast<uint4*>(at);
+    o[0] = make_uint4(d[0], d[1], d[2], d[3]);
+    o[1] = make_uint4(d[4], d[5], d[6], d[7]);
+    o[2] = make_uint4(d[8], d[9], d[10], d[11]);
+}
+__device__ __forceinline__ void store_rgb1(uint8_t* at, uint32_t px) {
+    at[0] = (uint8_t)px;
+    at[1] = (uint8_t)(px >> 8);
+    at[2] = (uint8_t)(px >> 16);
+}
+
+// 4:2:0 (LAYOUT 1: NV12, 2: I420).
 template <int LAYOUT>
-__device__ __forceinline__ void yuv_rows16(const YuvPlanes& p, YuvCoef k, uint8_t* dst, int w, int r0, int r1, int x0, int cr) {
-    if (x0 >= w) return;
-    uint32_t uv[4];                                        // NV12: 8 (U, V) pairs; I420: uv[0..1] 8 U, uv[2..3] 8 V
-    if constexpr (LAYOUT == 1) {
-        const uint4 c = *reinterpret_cast<const uint4*>(p.u + (size_t)cr * p.cpitch + x0);
-        uv[0] = c.x; uv[1] = c.y; uv[2] = c.z; uv[3] = c.w;
-    } else {
-        const size_t co = (size_t)cr * p.cpitch + (x0 >> 1);
-        const uint2 cu = *reinterpret_cast<const uint2*>(p.u + co), cv = *reinterpret_cast<const uint2*>(p.v + co);
-        uv[0] = cu.x; uv[1] = cu.y; uv[2] = cv.x; uv[3] = cv.y;
+struct Rows420 {
+    static constexpr bool CHROMA_ROWS = true;
+    static constexpr int ANY_COLS = 2;
+    __device__ __forceinline__ static Planes dense(const uint8_t* frame, int h, int w) {
+        const size_t plane = (size_t)h * w;
+        return Planes{frame, frame + plane, frame + plane + (plane >> 2), w, LAYOUT == 1 ? w : w >> 1};
     }
-    Chroma c[8];
+    // The two rows of chroma row `cr`: 16 Y bytes per row and the 8 (U, V) pairs under them in 16-byte loads, each pair's three chroma
+    // terms computed once for its four pixels.  Either row of the pair may lie outside [r0, r1) (block-uniform) and is then neither
+    // read nor written.
+    __device__ __forceinline__ static void wide(const Planes& p, YuvCoef k, uint8_t* dst, int, int w, int r0, int r1, int cr, int x0) {
+        if (x0 >= w) return;
+        uint32_t uv[4];                                    // NV12: 8 (U, V) pairs; I420: uv[0..1] 8 U, uv[2..3] 8 V
+        if constexpr (LAYOUT == 1) {
+            const uint4 c = *reinterpret_cast<const uint4*>(p.u + (size_t)cr * p.cpitch + x0);
+            uv[0] = c.x; uv[1] = c.y; uv[2] = c.z; uv[3] = c.w;
+        } else {
+            const size_t co = (size_t)cr * p.cpitch + (x0 >> 1);
+            const uint2 cu = *reinterpret_cast<const uint2*>(p.u + co), cv = *reinterpret_cast<const uint2*>(p.v + co);
+            uv[0] = cu.x; uv[1] = cu.y; uv[2] = cv.x; uv[3] = cv.y;
+        }
+        Chroma c[8];
 #pragma unroll
-    for (int i = 0; i < 8; ++i) {
+        for (int i = 0; i < 8; ++i) {
+            int u, v;
+            if constexpr (LAYOUT == 1) {
+                u = (int)((uv[i >> 1] >> (16 * (i & 1))) & 255u);
+                v = (int)((uv[i >> 1] >> (16 * (i & 1) + 8)) & 255u);
+            } else {
+                u = (int)((uv[i >> 2] >> (8 * (i & 3))) & 255u);
+                v = (int)((uv[2 + (i >> 2)] >> (8 * (i & 3))) & 255u);
+            }
+            c[i] = yuv_chroma(u, v, k);
+        }
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy) {
+            const int y = 2 * cr + dy;
+            if (y < r0 || y >= r1) continue;
+            const uint4 yq = *reinterpret_cast<const uint4*>(p.y + (size_t)y * p.pitch + x0);
+            const uint32_t yw[4] = {yq.x, yq.y, yq.z, yq.w};
+            uint32_t d[12];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {                  // four pixels (two chroma pairs) -> three dwords
+                uint32_t px[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) px[i] = yuv_pixel((int)((yw[j] >> (8 * i)) & 255u), c[2 * j + (i >> 1)], k);
+                pack_rgb4(px, d + 3 * j);
+            }
+            store_rgb16(dst + ((size_t)y * w + x0) * 3, d);
+        }
+    }
+    // one thread per 2 x 2 block (block column bx)
+    __device__ __forceinline__ static void any(const Planes& p, YuvCoef k, uint8_t* dst, int, int w, int r0, int r1, int cr, int bx) {
+        if (2 * bx >= w) return;
         int u, v;
         if constexpr (LAYOUT == 1) {
-            u = (int)((uv[i >> 1] >> (16 * (i & 1))) & 255u);
-            v = (int)((uv[i >> 1] >> (16 * (i & 1) + 8)) & 255u);
+            u = p.u[(size_t)cr * p.cpitch + 2 * bx];
+            v = p.u[(size_t)cr * p.cpitch + 2 * bx + 1];
         } else {
-            u = (int)((uv[i >> 2] >> (8 * (i & 3))) & 255u);
-            v = (int)((uv[2 + (i >> 2)] >> (8 * (i & 3))) & 255u);
+            u = p.u[(size_t)cr * p.cpitch + bx];
+            v = p.v[(size_t)cr * p.cpitch + bx];
         }
-        c[i] = yuv_chroma(u, v, k);
+        const Chroma c = yuv_chroma(u, v, k);
+        for (int dy = 0; dy < 2; ++dy) {
+            const int y = 2 * cr + dy;
+            if (y < r0 || y >= r1) continue;
+            for (int dx = 0; dx < 2; ++dx)
+                store_rgb1(dst + ((size_t)y * w + 2 * bx + dx) * 3, yuv_pixel(p.y[(size_t)y * p.pitch + 2 * bx + dx], c, k));
+        }
     }
-#pragma unroll
-    for (int dy = 0; dy < 2; ++dy) {
-        const int y = 2 * cr + dy;
-        if (y < r0 || y >= r1) continue;
-        const uint4 yq = *reinterpret_cast<const uint4*>(p.y + (size_t)y * p.pitch + x0);
-        const uint32_t yw[4] = {yq.x, yq.y, yq.z, yq.w};
+};
+
+// Packed 4:2:2 (ORDER 0: YUY2, 1: UYVY): row y of the one plane -> row y of the RGB frame.
+template <int ORDER>
+struct Rows422 {
+    static constexpr bool CHROMA_ROWS = false;
+    static constexpr int ANY_COLS = 2;
+    __device__ __forceinline__ static Planes dense(const uint8_t* frame, int, int w) { return Planes{frame, nullptr, nullptr, 2 * w, 0}; }
+    // 8 macropixels in two 16-byte loads, each macropixel's three chroma terms computed once for its two pixels
+    __device__ __forceinline__ static void wide(const Planes& s, YuvCoef k, uint8_t* dst, int, int w, int, int, int y, int x0) {
+        if (x0 >= w) return;
+        const uint4* in = reinterpret_cast<const uint4*>(s.y + (size_t)y * s.pitch + 2 * x0);
+        const uint4 q0 = in[0], q1 = in[1];
+        const uint32_t m[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
         uint32_t d[12];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {                      // four pixels (two chroma pairs) -> three dwords
+        for (int j = 0; j < 4; ++j) {                      // two macropixels (four pixels) -> three dwords
             uint32_t px[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) px[i] = yuv_pixel((int)((yw[j] >> (8 * i)) & 255u), c[2 * j + (i >> 1)], k);
-            d[3 * j] = px[0] | (px[1] << 24);
-            d[3 * j + 1] = (px[1] >> 8) | (px[2] << 16);
-            d[3 * j + 2] = (px[2] >> 16) | (px[3] << 8);
+            for (int i = 0; i < 2; ++i) {
+                const uint32_t mp = m[2 * j + i];
+                const Chroma c = yuv_chroma((int)((mp >> ya::ush422(ORDER)) & 255u), (int)((mp >> ya::vsh422(ORDER)) & 255u), k);
+                px[2 * i] = yuv_pixel((int)((mp >> ya::ysh422(ORDER, 0)) & 255u), c, k);
+                px[2 * i + 1] = yuv_pixel((int)((mp >> ya::ysh422(ORDER, 1)) & 255u), c, k);
+            }
+            pack_rgb4(px, d + 3 * j);
         }
-        uint4* o = reinterpret_cast<uint4*>(dst + ((size_t)y * w + x0) * 3);
-        o[0] = make_uint4(d[0], d[1], d[2], d[3]);
-        o[1] = make_uint4(d[4], d[5], d[6], d[7]);
-        o[2] = make_uint4(d[8], d[9], d[10], d[11]);
+        store_rgb16(dst + ((size_t)y * w + x0) * 3, d);
     }
-}
+    // one thread per macropixel (index mx of row y)
+    __device__ __forceinline__ static void any(const Planes& s, YuvCoef k, uint8_t* dst, int, int w, int, int, int y, int mx) {
+        if (2 * mx >= w) return;
+        const uint8_t* b = s.y + (size_t)y * s.pitch + 4 * mx;
+        const Chroma c = yuv_chroma(b[ya::ush422(ORDER) >> 3], b[ya::vsh422(ORDER) >> 3], k);
+        uint8_t* o = dst + ((size_t)y * w + 2 * mx) * 3;
+        for (int dx = 0; dx < 2; ++dx) store_rgb1(o + 3 * dx, yuv_pixel(b[ya::ysh422(ORDER, dx) >> 3], c, k));
+    }
+};
 
-// the same for any even width, any pitch and any alignment: one thread per 2 x 2 block (block column bx), byte accesses
-template <int LAYOUT>
-__device__ __forceinline__ void yuv_rows2x2(const YuvPlanes& p, YuvCoef k, uint8_t* dst, int w, int r0, int r1, int bx, int cr) {
-    if (2 * bx >= w) return;
-    int u, v;
-    if constexpr (LAYOUT == 1) {
-        u = p.u[(size_t)cr * p.cpitch + 2 * bx];
-        v = p.u[(size_t)cr * p.cpitch + 2 * bx + 1];
-    } else {
-        u = p.u[(size_t)cr * p.cpitch + bx];
-        v = p.v[(size_t)cr * p.cpitch + bx];
-    }
-    const Chroma c = yuv_chroma(u, v, k);
-    for (int dy = 0; dy < 2; ++dy) {
-        const int y = 2 * cr + dy;
-        if (y < r0 || y >= r1) continue;
-        for (int dx = 0; dx < 2; ++dx) {
-            const uint32_t px = yuv_pixel(p.y[(size_t)y * p.pitch + 2 * bx + dx], c, k);
-            const size_t o = (size_t)y * w + 2 * bx + dx;
-            dst[o * 3] = (uint8_t)px;
-            dst[o * 3 + 1] = (uint8_t)(px >> 8);
-            dst[o * 3 + 2] = (uint8_t)(px >> 16);
+// The RGB family (F = the layout: 5 BGR, 6 RGBA, 7 BGRA): row y of the one plane -> row y of the RGB frame, a permutation of bytes;
+// alpha is not read.
+template <int F>
+struct RowsPx {
+    static constexpr bool CHROMA_ROWS = false;
+    static constexpr int ANY_COLS = 1;
+    static constexpr int BPP = F == 5 ? 3 : 4;             // bytes a pixel
+    static constexpr int R = F == 6 ? 0 : 2, B = 2 - R;    // where R and B lie in it (G: byte 1)
+    __device__ __forceinline__ static Planes dense(const uint8_t* frame, int, int w) { return Planes{frame, nullptr, nullptr, BPP * w, 0}; }
+    // 48 / 64 bytes in three / four 16-byte loads
+    __device__ __forceinline__ static void wide(const Planes& s, YuvCoef, uint8_t* dst, int, int w, int, int, int y, int x0) {
+        if (x0 >= w) return;
+        const uint4* in = reinterpret_cast<const uint4*>(s.y + (size_t)y * s.pitch + BPP * x0);
+        uint32_t m[4 * BPP];
+#pragma unroll
+        for (int i = 0; i < BPP; ++i) {
+            const uint4 q = in[i];
+            m[4 * i] = q.x; m[4 * i + 1] = q.y; m[4 * i + 2] = q.z; m[4 * i + 3] = q.w;
         }
+        auto byte_at = [&](int j) { return (m[j >> 2] >> (8 * (j & 3))) & 255u; };
+        uint32_t d[12];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {                      // four pixels -> three dwords
+            uint32_t px[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int b0 = BPP * (4 * j + i);
+                px[i] = byte_at(b0 + R) | (byte_at(b0 + 1) << 8) | (byte_at(b0 + B) << 16);
+            }
+            pack_rgb4(px, d + 3 * j);
+        }
+        store_rgb16(dst + ((size_t)y * w + x0) * 3, d);
     }
-}
+    // one thread per pixel (column x of row y)
+    __device__ __forceinline__ static void any(const Planes& s, YuvCoef, uint8_t* dst, int, int w, int, int, int y, int x) {
+        if (x >= w) return;
+        const uint8_t* b = s.y + (size_t)y * s.pitch + (size_t)BPP * x;
+        uint8_t* o = dst + ((size_t)y * w + x) * 3;
+        o[0] = b[R];
+        o[1] = b[1];
+        o[2] = b[B];
+    }
+};
 
-// The slots' dense staging frames (frame blockIdx.z at yuv + blockIdx.z * yuv_stride) ...
-template <int LAYOUT>
-__global__ __launch_bounds__(256) void k_yuv_rows_to_rgb(const uint8_t* __restrict__ yuv, size_t yuv_stride, YuvCoef k,
-                                                        uint8_t* __restrict__ rgb, size_t rgb_stride, int h, int w, int r0, int r1) {
-    yuv_rows16<LAYOUT>(dense_planes<LAYOUT>(yuv + (size_t)blockIdx.z * yuv_stride, h, w), k, rgb + (size_t)blockIdx.z * rgb_stride, w, r0, r1,
-                       (int)(blockIdx.x * blockDim.x + threadIdx.x) * 16, (r0 >> 1) + (int)blockIdx.y);
-}
-template <int LAYOUT>
-__global__ __launch_bounds__(256) void k_yuv_rows_to_rgb_any(const uint8_t* __restrict__ yuv, size_t yuv_stride, YuvCoef k,
-                                                            uint8_t* __restrict__ rgb, size_t rgb_stride, int h, int w, int r0, int r1) {
-    yuv_rows2x2<LAYOUT>(dense_planes<LAYOUT>(yuv + (size_t)blockIdx.z * yuv_stride, h, w), k, rgb + (size_t)blockIdx.z * rgb_stride, w, r0, r1,
-                        (int)(blockIdx.x * blockDim.x + threadIdx.x), (r0 >> 1) + (int)blockIdx.y);
-}
+// 8-bit raw Bayer (P = the pattern): row y of the RGB frame is the demosaic of row clamp(y, 1, h - 2) of the one plane, column x that
+// of column clamp(x, 1, w - 2) (bayer_arith.h).
+template <int P>
+struct RowsBayer {
+    static constexpr bool CHROMA_ROWS = false;
+    static constexpr int ANY_COLS = 1;
+    __device__ __forceinline__ static Planes dense(const uint8_t* frame, int, int w) { return Planes{frame, nullptr, nullptr, w, 0}; }
+    // 16 bytes of each of the three rows around the clamped row in 16-byte loads and the byte on either side of them
+    __device__ __forceinline__ static void wide(const Planes& s, YuvCoef, uint8_t* dst, int h, int w, int, int, int y, int x0) {
+        if (x0 >= w) return;
+        const int cy = ba::tap_pos(y, h), xl = max(x0 - 1, 0), xr = min(x0 + 16, w - 1);
+        uint32_t m[3][4], left[3], right[3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const uint8_t* row = s.y + (size_t)(cy - 1 + r) * s.pitch;
+            const uint4 q = *reinterpret_cast<const uint4*>(row + x0);
+            m[r][0] = q.x; m[r][1] = q.y; m[r][2] = q.z; m[r][3] = q.w;
+            left[r] = row[xl];
+            right[r] = row[xr];
+        }
+        // column x0 + j of row r of the three, j = -1 .. 16
+        auto at = [&](int r, int j) { return j < 0 ? left[r] : j > 15 ? right[r] : (m[r][j >> 2] >> (8 * (j & 3))) & 255u; };
+        uint32_t px[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j)         // (x0 is even: the column's parity is j's)
+            px[j] = ba::demosaic(at(1, j), at(1, j - 1) + at(1, j + 1), at(0, j) + at(2, j),
+                                 at(0, j - 1) + at(0, j + 1) + at(2, j - 1) + at(2, j + 1), ba::phase(P, cy, j));
+        if (x0 == 0) px[0] = px[1];          // the frame's first and last column: their neighbours'
+        if (x0 + 16 == w) px[15] = px[14];
+        uint32_t d[12];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) pack_rgb4(px + 4 * j, d + 3 * j);
+        store_rgb16(dst + ((size_t)y * w + x0) * 3, d);
+    }
+    // one thread per pixel (column x of row y)
+    __device__ __forceinline__ static void any(const Planes& s, YuvCoef, uint8_t* dst, int h, int w, int, int, int y, int x) {
+        if (x >= w) return;
+        const int cy = ba::tap_pos(y, h), cx = ba::tap_pos(x, w);
+        const uint8_t *up = s.y + (size_t)(cy - 1) * s.pitch + cx, *mid = up + s.pitch, *dn = mid + s.pitch;
+        const uint32_t v = ba::demosaic(mid[0], (uint32_t)mid[-1] + mid[1], (uint32_t)up[0] + dn[0], (uint32_t)up[-1] + up[1] + dn[-1] + dn[1],
+                                        ba::phase(P, cy, cx));
+        store_rgb1(dst + ((size_t)y * w + x) * 3, v);
+    }
+};
+// the description of a layout (none for 0, plain RGB: its rows are shown as they are)
+template <int L>
+using RowsOf = std::conditional_t<L <= 2, Rows420<L>, std::conditional_t<L <= 4, Rows422<L - 3>, std::conditional_t<L <= 7, RowsPx<L>, RowsBayer<L - 16>>>>;
 
 // Entries into the surface table, as a kernel argument (no host memory has to outlive the call): entry i -> tab[first + i].
 __global__ __launch_bounds__(64) void k_write_surf_entries(SurfEntry* __restrict__ tab, int first, int n, SurfChunk ch) {
@@ -755,245 +722,22 @@ __global__ __launch_bounds__(64) void k_write_surf_entries(SurfEntry* __restrict
     tab[first + i] = e;
 }
 
-// ... and 4:2:0 surfaces -> the slots' RGB camera frames.  The surfaces of the launch travel as a kernel argument (frame blockIdx.z
-// is entry blockIdx.z of the chunk).
-template <int LAYOUT>
-__global__ __launch_bounds__(256) void k_surf_rows_to_rgb(SurfChunk ch, YuvCoef k, uint8_t* __restrict__ rgb, size_t rgb_stride, int w, int r0, int r1) {
-    yuv_rows16<LAYOUT>(surf_planes(ch.e[blockIdx.z]), k, rgb + (size_t)blockIdx.z * rgb_stride, w, r0, r1,
-                       (int)(blockIdx.x * blockDim.x + threadIdx.x) * 16, (r0 >> 1) + (int)blockIdx.y);
-}
-template <int LAYOUT>
-__global__ __launch_bounds__(256) void k_surf_rows_to_rgb_any(SurfChunk ch, YuvCoef k, uint8_t* __restrict__ rgb, size_t rgb_stride, int w, int r0, int r1) {
-    yuv_rows2x2<LAYOUT>(surf_planes(ch.e[blockIdx.z]), k, rgb + (size_t)blockIdx.z * rgb_stride, w, r0, r1,
-                        (int)(blockIdx.x * blockDim.x + threadIdx.x), (r0 >> 1) + (int)blockIdx.y);
-}
-
-// ---- packed 4:2:2 rows -> RGB rows ---------------------------------------------------------------------------------------------
-// The same role for YUY2 / UYVY frames: row y of the one plane -> row y of the RGB frame.  Both bodies take the plane pointer and
-// pitch of a frame: the dense entry points pass a slot's staging frame (pitch 2 w), the surface ones an entry of the chunk.
-struct Plane422 { const uint8_t* p; int pitch; };
-
-// One thread owns the 16 columns from x0 of row y: 8 macropixels in two 16-byte loads, each macropixel's three chroma terms computed
-// once for its two pixels, 48 bytes in three 16-byte stores.
-template <int ORDER>
-__device__ __forceinline__ void yuv422_row16(const Plane422& s, YuvCoef k, uint8_t* dst, int w, int y, int x0) {
-    if (x0 >= w) return;
-    const uint4* in = reinterpret_cast<const uint4*>(s.p + (size_t)y * s.pitch + 2 * x0);
-    const uint4 q0 = in[0], q1 = in[1];
-    const uint32_t m[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
-    uint32_t d[12];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {                          // two macropixels (four pixels) -> three dwords
-        uint32_t px[4];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const uint32_t mp = m[2 * j + i];
-            const Chroma c = yuv_chroma((int)((mp >> ya::ush422(ORDER)) & 255u), (int)((mp >> ya::vsh422(ORDER)) & 255u), k);
-            px[2 * i] = yuv_pixel((int)((mp >> ya::ysh422(ORDER, 0)) & 255u), c, k);
-            px[2 * i + 1] = yuv_pixel((int)((mp >> ya::ysh422(ORDER, 1)) & 255u), c, k);
-        }
-        d[3 * j] = px[0] | (px[1] << 24);
-        d[3 * j + 1] = (px[1] >> 8) | (px[2] << 16);
-        d[3 * j + 2] = (px[2] >> 16) | (px[3] << 8);
-    }
-    uint4* o = reinterpret_cast<uint4*>(dst + ((size_t)y * w + x0) * 3);
-    o[0] = make_uint4(d[0], d[1], d[2], d[3]);
-    o[1] = make_uint4(d[4], d[5], d[6], d[7]);
-    o[2] = make_uint4(d[8], d[9], d[10], d[11]);
-}
-
-// the same for any even width, any pitch and any alignment: one thread per macropixel (index mx of row y), byte accesses
-template <int ORDER>
-__device__ __forceinline__ void yuv422_row_mp(const Plane422& s, YuvCoef k, uint8_t* dst, int w, int y, int mx) {
-    if (2 * mx >= w) return;
-    const uint8_t* b = s.p + (size_t)y * s.pitch + 4 * mx;
-    const Chroma c = yuv_chroma(b[ya::ush422(ORDER) >> 3], b[ya::vsh422(ORDER) >> 3], k);
-    uint8_t* o = dst + ((size_t)y * w + 2 * mx) * 3;
-    for (int dx = 0; dx < 2; ++dx) {
-        const uint32_t px = yuv_pixel(b[ya::ysh422(ORDER, dx) >> 3], c, k);
-        o[3 * dx] = (uint8_t)px;
-        o[3 * dx + 1] = (uint8_t)(px >> 8);
-        o[3 * dx + 2] = (uint8_t)(px >> 16);
-    }
-}
-
-// rows [r0, r0 + gridDim.y) of the slots' dense staging frames (frame blockIdx.z at yuv + blockIdx.z * yuv_stride) ...
-template <int ORDER>
-__global__ __launch_bounds__(256) void k_yuv422_rows_to_rgb(const uint8_t* __restrict__ yuv, size_t yuv_stride, YuvCoef k,
-                                                           uint8_t* __restrict__ rgb, size_t rgb_stride, int w, int r0) {
-    yuv422_row16<ORDER>(Plane422{yuv + (size_t)blockIdx.z * yuv_stride, 2 * w}, k, rgb + (size_t)blockIdx.z * rgb_stride, w,
-                        r0 + (int)blockIdx.y, (int)(blockIdx.x * blockDim.x + threadIdx.x) * 16);
-}
-template <int ORDER>
-__global__ __launch_bounds__(256) void k_yuv422_rows_to_rgb_any(const uint8_t* __restrict__ yuv, size_t yuv_stride, YuvCoef k,
-                                                               uint8_t* __restrict__ rgb, size_t rgb_stride, int w, int r0) {
-    yuv422_row_mp<ORDER>(Plane422{yuv + (size_t)blockIdx.z * yuv_stride, 2 * w}, k, rgb + (size_t)blockIdx.z * rgb_stride, w,
-                         r0 + (int)blockIdx.y, (int)(blockIdx.x * blockDim.x + threadIdx.x));
-}
-// ... and of surfaces (frame blockIdx.z is entry blockIdx.z of the chunk)
-template <int ORDER>
-__global__ __launch_bounds__(256) void k_surf422_rows_to_rgb(SurfChunk ch, YuvCoef k, uint8_t* __restrict__ rgb, size_t rgb_stride, int w, int r0) {
-    yuv422_row16<ORDER>(Plane422{reinterpret_cast<const uint8_t*>(ch.e[blockIdx.z].plane[0]), ch.e[blockIdx.z].pitch}, k,
-                        rgb + (size_t)blockIdx.z * rgb_stride, w, r0 + (int)blockIdx.y, (int)(blockIdx.x * blockDim.x + threadIdx.x) * 16);
-}
-template <int ORDER>
-__global__ __launch_bounds__(256) void k_surf422_rows_to_rgb_any(SurfChunk ch, YuvCoef k, uint8_t* __restrict__ rgb, size_t rgb_stride, int w, int r0) {
-    yuv422_row_mp<ORDER>(Plane422{reinterpret_cast<const uint8_t*>(ch.e[blockIdx.z].plane[0]), ch.e[blockIdx.z].pitch}, k,
-                         rgb + (size_t)blockIdx.z * rgb_stride, w, r0 + (int)blockIdx.y, (int)(blockIdx.x * blockDim.x + threadIdx.x));
-}
-
-// ---- BGR / RGBA / BGRA rows -> RGB rows ------------------------------------------------------------------------------------------
-// The same role for the RGB family (F = the layout: 5 BGR, 6 RGBA, 7 BGRA): row y of the one plane -> row y of the RGB frame, a
-// permutation of bytes; alpha is not read.
-template <int F>
-struct PxBytes {
-    static constexpr int BPP = F == 5 ? 3 : 4;             // bytes a pixel
-    static constexpr int R = F == 6 ? 0 : 2, B = 2 - R;    // where R and B lie in it (G: byte 1)
-};
-
-// One thread owns the 16 columns from x0 of row y: 48 / 64 bytes in three / four 16-byte loads, 48 bytes in three 16-byte stores.
-template <int F>
-__device__ __forceinline__ void px_row16(const Plane422& s, uint8_t* dst, int w, int y, int x0) {
-    typedef PxBytes<F> P;
-    if (x0 >= w) return;
-    const uint4* in = reinterpret_cast<const uint4*>(s.p + (size_t)y * s.pitch + P::BPP * x0);
-    uint32_t m[4 * P::BPP];
-#pragma unroll
-    for (int i = 0; i < P::BPP; ++i) {
-        const uint4 q = in[i];
-        m[4 * i] = q.x; m[4 * i + 1] = q.y; m[4 * i + 2] = q.z; m[4 * i + 3] = q.w;
-    }
-    auto byte_at = [&](int j) { return (m[j >> 2] >> (8 * (j & 3))) & 255u; };
-    uint32_t d[12];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {                          // four pixels -> three dwords
-        uint32_t px[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int b0 = P::BPP * (4 * j + i);
-            px[i] = byte_at(b0 + P::R) | (byte_at(b0 + 1) << 8) | (byte_at(b0 + P::B) << 16);
-        }
-        d[3 * j] = px[0] | (px[1] << 24);
-        d[3 * j + 1] = (px[1] >> 8) | (px[2] << 16);
-        d[3 * j + 2] = (px[2] >> 16) | (px[3] << 8);
-    }
-    uint4* o = reinterpret_cast<uint4*>(dst + ((size_t)y * w + x0) * 3);
-    o[0] = make_uint4(d[0], d[1], d[2], d[3]);
-    o[1] = make_uint4(d[4], d[5], d[6], d[7]);
-    o[2] = make_uint4(d[8], d[9], d[10], d[11]);
-}
-
-// the same for any width, any pitch and any alignment: one thread per pixel (column x of row y), byte accesses
-template <int F>
-__device__ __forceinline__ void px_row1(const Plane422& s, uint8_t* dst, int w, int y, int x) {
-    typedef PxBytes<F> P;
-    if (x >= w) return;
-    const uint8_t* b = s.p + (size_t)y * s.pitch + (size_t)P::BPP * x;
-    uint8_t* o = dst + ((size_t)y * w + x) * 3;
-    o[0] = b[P::R];
-    o[1] = b[1];
-    o[2] = b[P::B];
-}
-
-// rows [r0, r0 + gridDim.y) of the slots' dense staging frames (frame blockIdx.z at px + blockIdx.z * px_stride) ...
-template <int F>
-__global__ __launch_bounds__(256) void k_px_rows_to_rgb(const uint8_t* __restrict__ px, size_t px_stride, uint8_t* __restrict__ rgb, size_t rgb_stride, int w, int r0) {
-    px_row16<F>(Plane422{px + (size_t)blockIdx.z * px_stride, PxBytes<F>::BPP * w}, rgb + (size_t)blockIdx.z * rgb_stride, w,
-                r0 + (int)blockIdx.y, (int)(blockIdx.x * blockDim.x + threadIdx.x) * 16);
-}
-template <int F>
-__global__ __launch_bounds__(256) void k_px_rows_to_rgb_any(const uint8_t* __restrict__ px, size_t px_stride, uint8_t* __restrict__ rgb, size_t rgb_stride, int w, int r0) {
-    px_row1<F>(Plane422{px + (size_t)blockIdx.z * px_stride, PxBytes<F>::BPP * w}, rgb + (size_t)blockIdx.z * rgb_stride, w,
-               r0 + (int)blockIdx.y, (int)(blockIdx.x * blockDim.x + threadIdx.x));
-}
-// ... and of surfaces (frame blockIdx.z is entry blockIdx.z of the chunk)
-template <int F>
-__global__ __launch_bounds__(256) void k_surfpx_rows_to_rgb(SurfChunk ch, uint8_t* __restrict__ rgb, size_t rgb_stride, int w, int r0) {
-    px_row16<F>(Plane422{reinterpret_cast<const uint8_t*>(ch.e[blockIdx.z].plane[0]), ch.e[blockIdx.z].pitch},
-                rgb + (size_t)blockIdx.z * rgb_stride, w, r0 + (int)blockIdx.y, (int)(blockIdx.x * blockDim.x + threadIdx.x) * 16);
-}
-template <int F>
-__global__ __launch_bounds__(256) void k_surfpx_rows_to_rgb_any(SurfChunk ch, uint8_t* __restrict__ rgb, size_t rgb_stride, int w, int r0) {
-    px_row1<F>(Plane422{reinterpret_cast<const uint8_t*>(ch.e[blockIdx.z].plane[0]), ch.e[blockIdx.z].pitch},
-               rgb + (size_t)blockIdx.z * rgb_stride, w, r0 + (int)blockIdx.y, (int)(blockIdx.x * blockDim.x + threadIdx.x));
-}
-
-// ---- raw Bayer rows -> RGB rows ---------------------------------------------------------------------------------------------------
-// The same role for 8-bit raw Bayer (P = the pattern): row y of the RGB frame is the demosaic of row clamp(y, 1, h - 2) of the one
-// plane, column x that of column clamp(x, 1, w - 2) (bayer_arith.h).
-
-// One thread owns the 16 columns from x0 of row y (w a multiple of 16): 16 bytes of each of the three rows around the clamped row in
-// 16-byte loads and the byte on either side of them, 48 bytes in three 16-byte stores.
-template <int P>
-__device__ __forceinline__ void bayer_row16(const Plane422& s, uint8_t* dst, int h, int w, int y, int x0) {
-    if (x0 >= w) return;
-    const int cy = ba::tap_pos(y, h), xl = max(x0 - 1, 0), xr = min(x0 + 16, w - 1);
-    uint32_t m[3][4], left[3], right[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        const uint8_t* row = s.p + (size_t)(cy - 1 + r) * s.pitch;
-        const uint4 q = *reinterpret_cast<const uint4*>(row + x0);
-        m[r][0] = q.x; m[r][1] = q.y; m[r][2] = q.z; m[r][3] = q.w;
-        left[r] = row[xl];
-        right[r] = row[xr];
-    }
-    // column x0 + j of row r of the three, j = -1 .. 16
-    auto at = [&](int r, int j) { return j < 0 ? left[r] : j > 15 ? right[r] : (m[r][j >> 2] >> (8 * (j & 3))) & 255u; };
-    uint32_t px[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j)             // (x0 is even: the column's parity is j's)
-        px[j] = ba::demosaic(at(1, j), at(1, j - 1) + at(1, j + 1), at(0, j) + at(2, j),
-                             at(0, j - 1) + at(0, j + 1) + at(2, j - 1) + at(2, j + 1), ba::phase(P, cy, j));
-    if (x0 == 0) px[0] = px[1];              // the frame's first and last column: their neighbours'
-    if (x0 + 16 == w) px[15] = px[14];
-    uint32_t d[12];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        d[3 * j] = px[4 * j] | (px[4 * j + 1] << 24);
-        d[3 * j + 1] = (px[4 * j + 1] >> 8) | (px[4 * j + 2] << 16);
-        d[3 * j + 2] = (px[4 * j + 2] >> 16) | (px[4 * j + 3] << 8);
-    }
-    uint4* o = reinterpret_cast<uint4*>(dst + ((size_t)y * w + x0) * 3);
-    o[0] = make_uint4(d[0], d[1], d[2], d[3]);
-    o[1] = make_uint4(d[4], d[5], d[6], d[7]);
-    o[2] = make_uint4(d[8], d[9], d[10], d[11]);
-}
-
-// the same for any width, any pitch and any alignment: one thread per pixel (column x of row y), byte accesses
-template <int P>
-__device__ __forceinline__ void bayer_row1(const Plane422& s, uint8_t* dst, int h, int w, int y, int x) {
-    if (x >= w) return;
-    const int cy = ba::tap_pos(y, h), cx = ba::tap_pos(x, w);
-    const uint8_t *up = s.p + (size_t)(cy - 1) * s.pitch + cx, *mid = up + s.pitch, *dn = mid + s.pitch;
-    const uint32_t v = ba::demosaic(mid[0], (uint32_t)mid[-1] + mid[1], (uint32_t)up[0] + dn[0], (uint32_t)up[-1] + up[1] + dn[-1] + dn[1],
-                                    ba::phase(P, cy, cx));
-    uint8_t* o = dst + ((size_t)y * w + x) * 3;
-    o[0] = (uint8_t)v;
-    o[1] = (uint8_t)(v >> 8);
-    o[2] = (uint8_t)(v >> 16);
-}
-
-// rows [r0, r0 + gridDim.y) of the slots' dense staging frames (frame blockIdx.z at raw + blockIdx.z * raw_stride) ...
-template <int P>
-__global__ __launch_bounds__(256) void k_bayer_rows_to_rgb(const uint8_t* __restrict__ raw, size_t raw_stride, uint8_t* __restrict__ rgb, size_t rgb_stride, int h, int w, int r0) {
-    bayer_row16<P>(Plane422{raw + (size_t)blockIdx.z * raw_stride, w}, rgb + (size_t)blockIdx.z * rgb_stride, h, w,
-                   r0 + (int)blockIdx.y, (int)(blockIdx.x * blockDim.x + threadIdx.x) * 16);
-}
-template <int P>
-__global__ __launch_bounds__(256) void k_bayer_rows_to_rgb_any(const uint8_t* __restrict__ raw, size_t raw_stride, uint8_t* __restrict__ rgb, size_t rgb_stride, int h, int w, int r0) {
-    bayer_row1<P>(Plane422{raw + (size_t)blockIdx.z * raw_stride, w}, rgb + (size_t)blockIdx.z * rgb_stride, h, w,
-                  r0 + (int)blockIdx.y, (int)(blockIdx.x * blockDim.x + threadIdx.x));
-}
-// ... and of surfaces (frame blockIdx.z is entry blockIdx.z of the chunk)
-template <int P>
-__global__ __launch_bounds__(256) void k_surfbayer_rows_to_rgb(SurfChunk ch, uint8_t* __restrict__ rgb, size_t rgb_stride, int h, int w, int r0) {
-    bayer_row16<P>(Plane422{reinterpret_cast<const uint8_t*>(ch.e[blockIdx.z].plane[0]), ch.e[blockIdx.z].pitch},
-                   rgb + (size_t)blockIdx.z * rgb_stride, h, w, r0 + (int)blockIdx.y, (int)(blockIdx.x * blockDim.x + threadIdx.x) * 16);
-}
-template <int P>
-__global__ __launch_bounds__(256) void k_surfbayer_rows_to_rgb_any(SurfChunk ch, uint8_t* __restrict__ rgb, size_t rgb_stride, int h, int w, int r0) {
-    bayer_row1<P>(Plane422{reinterpret_cast<const uint8_t*>(ch.e[blockIdx.z].plane[0]), ch.e[blockIdx.z].pitch},
-                  rgb + (size_t)blockIdx.z * rgb_stride, h, w, r0 + (int)blockIdx.y, (int)(blockIdx.x * blockDim.x + threadIdx.x));
+// The one entry point: layout x source x body.  Frame blockIdx.z of the launch is the slot's dense staging frame at src.p + blockIdx.z *
+// src.stride, or (SURF) the surface of entry blockIdx.z of the chunk, which travels as the kernel argument; launch row blockIdx.y
+// counts from r0 (CHROMA_ROWS: from chroma row r0 / 2).  (What every layout reads comes first in the parameter list, so that a form that
+// reads nothing else fetches its arguments in one piece.)
+struct DenseFrames { const uint8_t* p; size_t stride; };
+template <int LAYOUT, bool SURF, bool WIDE>
+__global__ __launch_bounds__(256) void k_rows_to_rgb(std::conditional_t<SURF, SurfChunk, DenseFrames> src, uint8_t* __restrict__ rgb,
+                                                    size_t rgb_stride, int w, int r0, int r1, int h, YuvCoef k) {
+    typedef RowsOf<LAYOUT> D;
+    Planes p;
+    if constexpr (SURF) p = surf_planes(src.e[blockIdx.z]);
+    else p = D::dense(src.p + (size_t)blockIdx.z * src.stride, h, w);
+    uint8_t* dst = rgb + (size_t)blockIdx.z * rgb_stride;
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x), row = (D::CHROMA_ROWS ? r0 >> 1 : r0) + (int)blockIdx.y;
+    if constexpr (WIDE) D::wide(p, k, dst, h, w, r0, r1, row, i * 16);
+    else D::any(p, k, dst, h, w, r0, r1, row, i);
 }
 
 // Rows [r0, r1) of RGB surfaces -> the same rows of the slots' camera frames (row_bytes = 3 w, dense): a pitched row copy, one
@@ -1407,6 +1151,44 @@ static int frames_per_thread(int n) {
     return fpb < 1 ? 1 : (fpb > cap ? cap : fpb);
 }
 
+// layout -> f(std::integral_constant<int, layout>{}): the one place where the host turns the number into a template argument
+template <class F>
+static void with_layout(int layout, F&& f) {
+    switch (layout) {
+        case 0: return f(std::integral_constant<int, 0>{});
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 5: return f(std::integral_constant<int, 5>{});
+        case 6: return f(std::integral_constant<int, 6>{});
+        case 7: return f(std::integral_constant<int, 7>{});
+        case 16: return f(std::integral_constant<int, 16>{});
+        case 17: return f(std::integral_constant<int, 17>{});
+        case 18: return f(std::integral_constant<int, 18>{});
+        case 19: return f(std::integral_constant<int, 19>{});
+    }
+}
+
+// One launch of the walk over the n frames of `src`.  Plain RGB frames of the slots that are not dword-aligned, dword-strided and below
+// 2^30 bytes (a larger frame: 64-bit addresses) -- or all of them, any_byte -- take the form that fetches at any byte.
+template <bool PER_SLOT>
+static void launch_walk(hipStream_t s, dim3 grid, FrameSource src, int layout, YuvCoef k, const int16_t* uxy, const uint16_t* ufrac,
+                        const CalTables* sets, const CalIds& ids, FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n, int fpb,
+                        bool any_byte) {
+    const bool aligned = !any_byte && ((uintptr_t)src.frames & 3) == 0 && (src.stride & 3) == 0 && src.stride < (1u << 30);
+    const int remap = xcd_remap();
+    with_layout(layout, [&](auto l) {
+        constexpr int L = decltype(l)::value;
+        auto launch = [&](auto k_walk) {
+            hipLaunchKernelGGL(k_walk, grid, dim3(256), 0, s, src.tab, src.frames, src.stride, k, uxy, ufrac, sets, ids, g, und, und_px, first_slot, n, fpb, remap);
+        };
+        if (src.tab) launch(k_undistort_rows<L, SRC_SURFACES, PER_SLOT>);
+        else if (L != 0 || aligned) launch(k_undistort_rows<L, SRC_SLOTS, PER_SLOT>);
+        else launch(k_undistort_rows<0, SRC_SLOTS_ANY_BYTE, PER_SLOT>);
+    });
+}
+
 void launch_undistort_rows(hipStream_t s, FrameSource src, int layout, YuvCoef k, const int16_t* uxy, const uint16_t* ufrac,
                            FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n) {
     if (n <= 0 || g.nrows <= 0) return;
@@ -1414,120 +1196,36 @@ void launch_undistort_rows(hipStream_t s, FrameSource src, int layout, YuvCoef k
     // the slots of a walk are addressed by a 32-bit offset into one buffer resource: a walk stays below 2^30 bytes (one frame
     // per thread where a single frame is larger)
     if (!src.tab) fpb = (int)std::max<size_t>(1, std::min<size_t>((size_t)fpb, (((size_t)1 << 30) - 1) / src.stride));
-    const dim3 grid((g.img_w + 255) / 256, g.nrows, (n + fpb - 1) / fpb), block(256);
-    const int remap = xcd_remap();
-    if (layout >= 16) {                      // raw Bayer, pattern layout - 16
-        typedef void (*KS)(const SurfEntry*, const int16_t*, const uint16_t*, FrontEndGeom, uint32_t*, size_t, int, int, int, int);
-        typedef void (*KD)(const uint8_t*, size_t, const int16_t*, const uint16_t*, FrontEndGeom, uint32_t*, size_t, int, int, int, int);
-        static const KS surf[4] = {k_undistort_bayer_surf<0>, k_undistort_bayer_surf<1>, k_undistort_bayer_surf<2>, k_undistort_bayer_surf<3>};
-        static const KD dense[4] = {k_undistort_bayer<0>, k_undistort_bayer<1>, k_undistort_bayer<2>, k_undistort_bayer<3>};
-        if (src.tab) hipLaunchKernelGGL(surf[layout - 16], grid, block, 0, s, src.tab, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
-        else hipLaunchKernelGGL(dense[layout - 16], grid, block, 0, s, src.frames, src.stride, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
-        return;
-    }
-    if (src.tab) {
-        if (layout == 0) hipLaunchKernelGGL(k_undistort_rows_surf, grid, block, 0, s, src.tab, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
-        else if (layout == 1) hipLaunchKernelGGL(k_undistort_rows_yuv_surf<1>, grid, block, 0, s, src.tab, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
-        else if (layout == 2) hipLaunchKernelGGL(k_undistort_rows_yuv_surf<2>, grid, block, 0, s, src.tab, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
-        else if (layout == 3) hipLaunchKernelGGL(k_undistort422_surf<0>, grid, block, 0, s, src.tab, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
-        else if (layout == 4) hipLaunchKernelGGL(k_undistort422_surf<1>, grid, block, 0, s, src.tab, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
-        else if (layout == 5) hipLaunchKernelGGL(k_undistort_px_surf<5>, grid, block, 0, s, src.tab, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
-        else if (layout == 6) hipLaunchKernelGGL(k_undistort_px_surf<6>, grid, block, 0, s, src.tab, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
-        else hipLaunchKernelGGL(k_undistort_px_surf<7>, grid, block, 0, s, src.tab, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
-    } else if (layout == 0) {
-        static const bool unaligned = [] { const char* e = LT_EXP_ENV("LT_UNDISTORT_UNALIGNED"); return e && e[0] == '1'; }();   // A/B
-        if (!unaligned && ((uintptr_t)src.frames & 3) == 0 && (src.stride & 3) == 0 && src.stride < (1u << 30))   // (a larger frame: 64-bit addresses)
-            hipLaunchKernelGGL(k_undistort_rows<true>, grid, block, 0, s, src.frames, src.stride, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
-        else
-            hipLaunchKernelGGL(k_undistort_rows<false>, grid, block, 0, s, src.frames, src.stride, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
-    } else if (layout == 1) {
-        hipLaunchKernelGGL(k_undistort_rows_yuv<1>, grid, block, 0, s, src.frames, src.stride, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
-    } else if (layout == 2) {
-        hipLaunchKernelGGL(k_undistort_rows_yuv<2>, grid, block, 0, s, src.frames, src.stride, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
-    } else if (layout == 3) {
-        hipLaunchKernelGGL(k_undistort422<0>, grid, block, 0, s, src.frames, src.stride, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
-    } else if (layout == 4) {
-        hipLaunchKernelGGL(k_undistort422<1>, grid, block, 0, s, src.frames, src.stride, k, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
-    } else if (layout == 5) {
-        hipLaunchKernelGGL(k_undistort_px<5>, grid, block, 0, s, src.frames, src.stride, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
-    } else if (layout == 6) {
-        hipLaunchKernelGGL(k_undistort_px<6>, grid, block, 0, s, src.frames, src.stride, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
-    } else {
-        hipLaunchKernelGGL(k_undistort_px<7>, grid, block, 0, s, src.frames, src.stride, uxy, ufrac, g, und, und_px, first_slot, n, fpb, remap);
-    }
+    const dim3 grid((g.img_w + 255) / 256, g.nrows, (n + fpb - 1) / fpb);
+    static const bool unaligned = [] { const char* e = LT_EXP_ENV("LT_UNDISTORT_UNALIGNED"); return e && e[0] == '1'; }();   // A/B
+    launch_walk<false>(s, grid, src, layout, k, uxy, ufrac, nullptr, CalIds{}, g, und, und_px, first_slot, n, fpb, unaligned);
 }
 
-// The 4:2:0 row conversion of n frames, dense or from surfaces: the 16-column kernels where the width and every base and pitch of
-// the launch (`bits`: all of them ORed) are multiples of 16, the byte-wise ones otherwise.  wide / any: the <NV12>, <I420> forms.
-template <class K, class... Args>
-static void launch_rows_to_rgb(hipStream_t s, int layout, K wide1, K wide2, K any1, K any2, size_t bits, int w, int r0, int r1, int n, Args... args) {
-    const unsigned crows = (unsigned)(((r1 + 1) >> 1) - (r0 >> 1));
-    if ((w & 15) == 0 && (bits & 15) == 0)
-        hipLaunchKernelGGL(layout == 1 ? wide1 : wide2, dim3((unsigned)((w / 16 + 63) / 64), crows, (unsigned)n), dim3(64), 0, s, args...);
-    else
-        hipLaunchKernelGGL(layout == 1 ? any1 : any2, dim3((unsigned)((w / 2 + 255) / 256), crows, (unsigned)n), dim3(256), 0, s, args...);
-}
-
-// The packed 4:2:2 row conversion of n frames: one launch row per frame row; wide / any as above, [0]: YUY2, [1]: UYVY.
-template <class K, class... Args>
-static void launch_rows422_to_rgb(hipStream_t s, int layout, K wide0, K wide1, K any0, K any1, size_t bits, int w, int r0, int r1, int n, Args... args) {
-    const unsigned rows = (unsigned)(r1 - r0);
-    if ((w & 15) == 0 && (bits & 15) == 0)
-        hipLaunchKernelGGL(layout == 3 ? wide0 : wide1, dim3((unsigned)((w / 16 + 63) / 64), rows, (unsigned)n), dim3(64), 0, s, args...);
-    else
-        hipLaunchKernelGGL(layout == 3 ? any0 : any1, dim3((unsigned)((w / 2 + 255) / 256), rows, (unsigned)n), dim3(256), 0, s, args...);
-}
-
-// The RGB family's row conversion of n frames (layout 5 BGR, 6 RGBA, 7 BGRA): one launch row per frame row; wide[] / any[]: the
-// 16-column and the byte-wise kernels of the three layouts.
-template <class K, class... Args>
-static void launch_rows_px_to_rgb(hipStream_t s, int layout, const K (&wide)[3], const K (&any)[3], size_t bits, int w, int r0, int r1, int n, Args... args) {
-    const unsigned rows = (unsigned)(r1 - r0);
-    if ((w & 15) == 0 && (bits & 15) == 0)
-        hipLaunchKernelGGL(wide[layout - 5], dim3((unsigned)((w / 16 + 63) / 64), rows, (unsigned)n), dim3(64), 0, s, args...);
-    else
-        hipLaunchKernelGGL(any[layout - 5], dim3((unsigned)((w + 255) / 256), rows, (unsigned)n), dim3(256), 0, s, args...);
-}
-
-// The raw Bayer row conversion of n frames (layout 16 + pattern): one launch row per frame row; wide[] / any[]: the 16-column and the
-// byte-wise kernels of the four patterns.
-template <class K, class... Args>
-static void launch_rows_bayer_to_rgb(hipStream_t s, int layout, const K (&wide)[4], const K (&any)[4], size_t bits, int w, int r0, int r1, int n, Args... args) {
-    const unsigned rows = (unsigned)(r1 - r0);
-    if ((w & 15) == 0 && (bits & 15) == 0)
-        hipLaunchKernelGGL(wide[layout - 16], dim3((unsigned)((w / 16 + 63) / 64), rows, (unsigned)n), dim3(64), 0, s, args...);
-    else
-        hipLaunchKernelGGL(any[layout - 16], dim3((unsigned)((w + 255) / 256), rows, (unsigned)n), dim3(256), 0, s, args...);
+// The row conversion of n frames in `layout` (not 0), dense or from surfaces: the 16-column kernel where the width and every base and
+// pitch of the launch (`bits`: all of them ORed) are multiples of 16, the byte-wise one otherwise.
+template <bool SURF, class Src>
+static void launch_rows_to_rgb(hipStream_t s, int layout, const Src& src, size_t bits, YuvCoef k, uint8_t* rgb, size_t rgb_stride, int h, int w,
+                               int r0, int r1, int n) {
+    with_layout(layout, [&](auto l) {
+        constexpr int L = decltype(l)::value;
+        if constexpr (L != 0) {
+            typedef RowsOf<L> D;
+            const unsigned rows = (unsigned)(D::CHROMA_ROWS ? ((r1 + 1) >> 1) - (r0 >> 1) : r1 - r0);
+            if ((w & 15) == 0 && (bits & 15) == 0)
+                hipLaunchKernelGGL((k_rows_to_rgb<L, SURF, true>), dim3((unsigned)((w / 16 + 63) / 64), rows, (unsigned)n), dim3(64), 0, s,
+                                   src, rgb, rgb_stride, w, r0, r1, h, k);
+            else
+                hipLaunchKernelGGL((k_rows_to_rgb<L, SURF, false>), dim3((unsigned)((w / D::ANY_COLS + 255) / 256), rows, (unsigned)n), dim3(256), 0, s,
+                                   src, rgb, rgb_stride, w, r0, r1, h, k);
+        }
+    });
 }
 
 void launch_yuv_rows_to_rgb(hipStream_t s, int layout, const uint8_t* yuv, size_t yuv_stride, YuvCoef k, uint8_t* rgb,
                             size_t rgb_stride, int h, int w, int r0, int r1, int n) {
     if (n <= 0 || r1 <= r0) return;
-    if (layout >= 16) {
-        typedef void (*K)(const uint8_t*, size_t, uint8_t*, size_t, int, int, int);
-        static const K wide[4] = {k_bayer_rows_to_rgb<0>, k_bayer_rows_to_rgb<1>, k_bayer_rows_to_rgb<2>, k_bayer_rows_to_rgb<3>};
-        static const K any[4] = {k_bayer_rows_to_rgb_any<0>, k_bayer_rows_to_rgb_any<1>, k_bayer_rows_to_rgb_any<2>, k_bayer_rows_to_rgb_any<3>};
-        launch_rows_bayer_to_rgb(s, layout, wide, any, yuv_stride | rgb_stride | (size_t)(uintptr_t)yuv | (size_t)(uintptr_t)rgb, w, r0, r1, n,
-                                 yuv, yuv_stride, rgb, rgb_stride, h, w, r0);
-        return;
-    }
-    if (layout >= 5) {
-        typedef void (*K)(const uint8_t*, size_t, uint8_t*, size_t, int, int);
-        static const K wide[3] = {k_px_rows_to_rgb<5>, k_px_rows_to_rgb<6>, k_px_rows_to_rgb<7>};
-        static const K any[3] = {k_px_rows_to_rgb_any<5>, k_px_rows_to_rgb_any<6>, k_px_rows_to_rgb_any<7>};
-        launch_rows_px_to_rgb(s, layout, wide, any, yuv_stride | rgb_stride | (size_t)(uintptr_t)yuv | (size_t)(uintptr_t)rgb, w, r0, r1, n,
-                              yuv, yuv_stride, rgb, rgb_stride, w, r0);
-        return;
-    }
-    if (layout >= 3) {
-        launch_rows422_to_rgb(s, layout, k_yuv422_rows_to_rgb<0>, k_yuv422_rows_to_rgb<1>, k_yuv422_rows_to_rgb_any<0>, k_yuv422_rows_to_rgb_any<1>,
-                              yuv_stride | rgb_stride | (size_t)(uintptr_t)yuv | (size_t)(uintptr_t)rgb, w, r0, r1, n,
-                              yuv, yuv_stride, k, rgb, rgb_stride, w, r0);
-        return;
-    }
-    launch_rows_to_rgb(s, layout, k_yuv_rows_to_rgb<1>, k_yuv_rows_to_rgb<2>, k_yuv_rows_to_rgb_any<1>, k_yuv_rows_to_rgb_any<2>,
-                       yuv_stride | rgb_stride | (size_t)(uintptr_t)yuv | (size_t)(uintptr_t)rgb, w, r0, r1, n,
-                       yuv, yuv_stride, k, rgb, rgb_stride, h, w, r0, r1);
+    launch_rows_to_rgb<false>(s, layout, DenseFrames{yuv, yuv_stride}, yuv_stride | rgb_stride | (size_t)(uintptr_t)yuv | (size_t)(uintptr_t)rgb, k,
+                              rgb, rgb_stride, h, w, r0, r1, n);
 }
 
 void launch_write_surf_entries(hipStream_t s, SurfEntry* tab, int first, const SurfEntry* entries, int n) {
@@ -1559,22 +1257,8 @@ void launch_surf_rows_to_rgb(hipStream_t s, int layout, const SurfEntry* entries
                 hipLaunchKernelGGL(k_surf_copy_rows<true>, dim3((unsigned)((row_bytes / 16 + 255) / 256), (unsigned)(r1 - r0), (unsigned)m), dim3(256), 0, s, ch, dst, rgb_stride, row_bytes, r0);
             else
                 hipLaunchKernelGGL(k_surf_copy_rows<false>, dim3((unsigned)((row_bytes + 255) / 256), (unsigned)(r1 - r0), (unsigned)m), dim3(256), 0, s, ch, dst, rgb_stride, row_bytes, r0);
-        } else if (layout >= 16) {
-            typedef void (*K)(SurfChunk, uint8_t*, size_t, int, int, int);
-            static const K wide[4] = {k_surfbayer_rows_to_rgb<0>, k_surfbayer_rows_to_rgb<1>, k_surfbayer_rows_to_rgb<2>, k_surfbayer_rows_to_rgb<3>};
-            static const K any[4] = {k_surfbayer_rows_to_rgb_any<0>, k_surfbayer_rows_to_rgb_any<1>, k_surfbayer_rows_to_rgb_any<2>, k_surfbayer_rows_to_rgb_any<3>};
-            launch_rows_bayer_to_rgb(s, layout, wide, any, bits, w, r0, r1, m, ch, dst, rgb_stride, h, w, r0);
-        } else if (layout >= 5) {
-            typedef void (*K)(SurfChunk, uint8_t*, size_t, int, int);
-            static const K wide[3] = {k_surfpx_rows_to_rgb<5>, k_surfpx_rows_to_rgb<6>, k_surfpx_rows_to_rgb<7>};
-            static const K any[3] = {k_surfpx_rows_to_rgb_any<5>, k_surfpx_rows_to_rgb_any<6>, k_surfpx_rows_to_rgb_any<7>};
-            launch_rows_px_to_rgb(s, layout, wide, any, bits, w, r0, r1, m, ch, dst, rgb_stride, w, r0);
-        } else if (layout >= 3) {
-            launch_rows422_to_rgb(s, layout, k_surf422_rows_to_rgb<0>, k_surf422_rows_to_rgb<1>, k_surf422_rows_to_rgb_any<0>, k_surf422_rows_to_rgb_any<1>,
-                                  bits, w, r0, r1, m, ch, k, dst, rgb_stride, w, r0);
         } else {
-            launch_rows_to_rgb(s, layout, k_surf_rows_to_rgb<1>, k_surf_rows_to_rgb<2>, k_surf_rows_to_rgb_any<1>, k_surf_rows_to_rgb_any<2>,
-                               bits, w, r0, r1, m, ch, k, dst, rgb_stride, w, r0, r1);
+            launch_rows_to_rgb<true>(s, layout, ch, bits, k, dst, rgb_stride, h, w, r0, r1, m);
         }
     }
 }
@@ -1606,50 +1290,11 @@ static CalIds pack_ids(const uint8_t* ids, int m) {
 void launch_undistort_cal(hipStream_t s, FrameSource src, int layout, YuvCoef k, const CalTables* sets, const uint8_t* ids,
                           FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n) {
     if (n <= 0 || g.nrows <= 0) return;
-    const int remap = xcd_remap();
     for (int i = 0; i < n; i += CalIds::N) {
-        const int m = std::min(n - i, (int)CalIds::N), fs = first_slot + i;
-        const CalIds ci = pack_ids(ids + i, m);
-        const dim3 grid((g.img_w + 255) / 256, g.nrows, m), block(256);
-        const uint8_t* frames = src.tab ? nullptr : src.frames + (size_t)i * src.stride;
-        if (layout >= 16) {                  // raw Bayer, pattern layout - 16
-            typedef void (*KS)(const SurfEntry*, const CalTables*, CalIds, FrontEndGeom, uint32_t*, size_t, int, int, int);
-            typedef void (*KD)(const uint8_t*, size_t, const CalTables*, CalIds, FrontEndGeom, uint32_t*, size_t, int, int, int);
-            static const KS surf[4] = {k_undistort_bayer_cal_surf<0>, k_undistort_bayer_cal_surf<1>, k_undistort_bayer_cal_surf<2>, k_undistort_bayer_cal_surf<3>};
-            static const KD dense[4] = {k_undistort_bayer_cal<0>, k_undistort_bayer_cal<1>, k_undistort_bayer_cal<2>, k_undistort_bayer_cal<3>};
-            if (src.tab) hipLaunchKernelGGL(surf[layout - 16], grid, block, 0, s, src.tab, sets, ci, g, und, und_px, fs, m, remap);
-            else hipLaunchKernelGGL(dense[layout - 16], grid, block, 0, s, frames, src.stride, sets, ci, g, und, und_px, fs, m, remap);
-            continue;
-        }
-        if (src.tab) {
-            if (layout == 0) hipLaunchKernelGGL(k_undistort_cal_surf, grid, block, 0, s, src.tab, sets, ci, g, und, und_px, fs, m, remap);
-            else if (layout == 1) hipLaunchKernelGGL(k_undistort_cal_yuv_surf<1>, grid, block, 0, s, src.tab, k, sets, ci, g, und, und_px, fs, m, remap);
-            else if (layout == 2) hipLaunchKernelGGL(k_undistort_cal_yuv_surf<2>, grid, block, 0, s, src.tab, k, sets, ci, g, und, und_px, fs, m, remap);
-            else if (layout == 3) hipLaunchKernelGGL(k_undistort422_cal_surf<0>, grid, block, 0, s, src.tab, k, sets, ci, g, und, und_px, fs, m, remap);
-            else if (layout == 4) hipLaunchKernelGGL(k_undistort422_cal_surf<1>, grid, block, 0, s, src.tab, k, sets, ci, g, und, und_px, fs, m, remap);
-            else if (layout == 5) hipLaunchKernelGGL(k_undistort_px_cal_surf<5>, grid, block, 0, s, src.tab, sets, ci, g, und, und_px, fs, m, remap);
-            else if (layout == 6) hipLaunchKernelGGL(k_undistort_px_cal_surf<6>, grid, block, 0, s, src.tab, sets, ci, g, und, und_px, fs, m, remap);
-            else hipLaunchKernelGGL(k_undistort_px_cal_surf<7>, grid, block, 0, s, src.tab, sets, ci, g, und, und_px, fs, m, remap);
-        } else if (layout == 0) {
-            if (((uintptr_t)frames & 3) == 0 && (src.stride & 3) == 0 && src.stride < (1u << 30))
-                hipLaunchKernelGGL(k_undistort_cal<true>, grid, block, 0, s, frames, src.stride, sets, ci, g, und, und_px, fs, m, remap);
-            else
-                hipLaunchKernelGGL(k_undistort_cal<false>, grid, block, 0, s, frames, src.stride, sets, ci, g, und, und_px, fs, m, remap);
-        } else if (layout == 1) {
-            hipLaunchKernelGGL(k_undistort_cal_yuv<1>, grid, block, 0, s, frames, src.stride, k, sets, ci, g, und, und_px, fs, m, remap);
-        } else if (layout == 2) {
-            hipLaunchKernelGGL(k_undistort_cal_yuv<2>, grid, block, 0, s, frames, src.stride, k, sets, ci, g, und, und_px, fs, m, remap);
-        } else if (layout == 3) {
-            hipLaunchKernelGGL(k_undistort422_cal<0>, grid, block, 0, s, frames, src.stride, k, sets, ci, g, und, und_px, fs, m, remap);
-        } else if (layout == 4) {
-            hipLaunchKernelGGL(k_undistort422_cal<1>, grid, block, 0, s, frames, src.stride, k, sets, ci, g, und, und_px, fs, m, remap);
-        } else if (layout == 5) {
-            hipLaunchKernelGGL(k_undistort_px_cal<5>, grid, block, 0, s, frames, src.stride, sets, ci, g, und, und_px, fs, m, remap);
-        } else if (layout == 6) {
-            hipLaunchKernelGGL(k_undistort_px_cal<6>, grid, block, 0, s, frames, src.stride, sets, ci, g, und, und_px, fs, m, remap);
-        } else {
-            hipLaunchKernelGGL(k_undistort_px_cal<7>, grid, block, 0, s, frames, src.stride, sets, ci, g, und, und_px, fs, m, remap);
-        }
+        const int m = std::min(n - i, (int)CalIds::N);
+        const dim3 grid((g.img_w + 255) / 256, g.nrows, m);
+        const FrameSource part = src.tab ? src : FrameSource::slots(src.frames + (size_t)i * src.stride, src.stride);
+        launch_walk<true>(s, grid, part, layout, k, nullptr, nullptr, sets, pack_ids(ids + i, m), g, und, und_px, first_slot + i, m, 1, false);
     }
 }
 

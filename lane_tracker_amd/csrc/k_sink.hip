@@ -1,7 +1,7 @@
 // Device sinks: dense RGB frames of the library (the annotated frames of a context, d_annot) -> surfaces the caller owns, in the
 // caller's pixel format and pitches -- RGB (a pitched row copy), BGR / RGBA / BGRA (the same copy with permuted channels, alpha
 // written as 255), NV12 or I420 (sink_arith.h: OpenCV's RGB2YUV_I420 arithmetic,
-// chroma from the pixel at the even row and even column of each 2 x 2 block).  The mirror image of k_surf_rows_to_rgb /
+// chroma from the pixel at the even row and even column of each 2 x 2 block).  The mirror image of k_rows_to_rgb /
 // k_surf_copy_rows (k_frontend.hip).  The destinations of a launch travel as a SurfChunk kernel argument (frame blockIdx.z is
 // entry blockIdx.z).
 //

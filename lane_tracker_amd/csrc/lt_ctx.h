@@ -153,8 +153,8 @@ struct lt_ctx {
     uint8_t *d_frames = nullptr, *d_bev = nullptr;
     // Input that is not RGB (lt_set_input_format): the caller's layout, the five conversion coefficients (YUV), and per slot a staging frame
     // of yuv_bytes = h * w * 3 / 2 (4:2:0), h * w * 2 (packed 4:2:2), h * w * 3 (BGR), h * w * 4 (RGBA / BGRA) or h * w (raw Bayer) bytes in that layout, yuv_stride (a multiple of 16) apart, 16 bytes of padding behind the last
-    // one (k_undistort_rows_yuv reads aligned 8-byte windows).  The undistortion reads the staging frame; the RGB camera frame
-    // of a slot is written by k_yuv_rows_to_rgb behind the uploads that would have brought RGB rows for whoever shows the frame.
+    // one (k_undistort_rows reads aligned 8-byte windows).  The undistortion reads the staging frame; the RGB camera frame
+    // of a slot is written by k_rows_to_rgb behind the uploads that would have brought RGB rows for whoever shows the frame.
     int in_layout = 0;                        // LT_INPUT_RGB
     int32_t yuv_coef[5] = {0, 0, 0, 0, 0};
     bool input_locked = false;                // an upload has happened: the format stays

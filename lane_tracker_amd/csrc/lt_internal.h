@@ -57,7 +57,8 @@ void launch_warp_split(hipStream_t s, const uint32_t* und, size_t und_px, int fi
                        const uint16_t* wfrac, FrontEndGeom g, const uint16_t* gamma_tab, const uint16_t* cbrt_tab,
                        const int32_t* coeffs, bool lab_clamp_dead, uint8_t* planeR, uint8_t* planeB, size_t plane_stride, int n);
 // (YuvCoef, the five coefficients of the YUV 4:2:0 input's conversion: yuv_arith.h)
-// rows [r0, r1) of n 4:2:0 frames of h x w (h, w even) -> the same rows of n RGB frames
+// rows [r0, r1) of n dense frames of h x w in `layout` (any but 0; the layouts: launch_undistort_rows) -> the same rows of n RGB frames
+// (k_rows_to_rgb<layout, false, ..>)
 void launch_yuv_rows_to_rgb(hipStream_t s, int layout, const uint8_t* yuv, size_t yuv_stride, YuvCoef k, uint8_t* rgb,
                             size_t rgb_stride, int h, int w, int r0, int r1, int n);
 // Input frames of another size (lt_set_input_size; k_resize.hip): destination rows [a, b) of n RGB frames of width w, dst_stride apart, :=
@@ -89,7 +90,7 @@ struct FrameSource {
     static FrameSource surfaces(const SurfEntry* tab) { return FrameSource{tab, nullptr, 0}; }
 };
 // the undistorted rows of n frames (layout 0 = RGB, 1 = NV12, 2 = I420, 3 = YUY2, 4 = UYVY, 5 = BGR, 6 = RGBA, 7 = BGRA, 16 .. 19 = raw Bayer RGGB / GRBG / GBRG / BGGR; `k` is read for the YUV layouts only: every tap converted, then the
-// same blend); `und` is the base of the whole buffer, `first_slot` the absolute slot of frame 0 of the call
+// same blend); `und` is the base of the whole buffer, `first_slot` the absolute slot of frame 0 of the call (k_undistort_rows<layout, source, false>)
 void launch_undistort_rows(hipStream_t s, FrameSource src, int layout, YuvCoef k, const int16_t* uxy, const uint16_t* ufrac,
                            FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n);
 // Calibration sets (lt_add_calibration): the remap tables of one set as the table-per-slot front end finds them -- entry `id` of the
@@ -109,7 +110,7 @@ struct CalIds {                  // the sets of the slots of one launch
     uint32_t w[N / 4];
 };
 // The table-per-slot forms of the two launches above, for slots [first_slot, first_slot + n) whose sets are ids[0, n) (host memory):
-// every slot with the tables of its own set, one frame per walk; launches of up to CalIds::N slots.
+// every slot with the tables of its own set, one frame per walk; launches of up to CalIds::N slots (k_undistort_rows<layout, source, true>, k_warp_cal).
 void launch_undistort_cal(hipStream_t s, FrameSource src, int layout, YuvCoef k, const CalTables* sets, const uint8_t* ids,
                           FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n);
 void launch_warp_cal(hipStream_t s, const uint32_t* und, size_t und_px, int first_slot, const CalTables* sets, const uint8_t* ids,
@@ -118,7 +119,7 @@ void launch_warp_cal(hipStream_t s, const uint32_t* und, size_t und_px, int firs
 // entries[0, n) (host memory, consumed before the call returns) -> tab[first, first + n), stream-ordered
 void launch_write_surf_entries(hipStream_t s, SurfEntry* tab, int first, const SurfEntry* entries, int n);
 // rows [r0, r1) of the n surfaces of entries[] (host memory) -> the same rows of n RGB frames of h x w: a conversion (YUV, raw Bayer), a
-// permutation (BGR, RGBA, BGRA) or a pitched copy (RGB)
+// permutation (BGR, RGBA, BGRA) -- k_rows_to_rgb<layout, true, ..> -- or a pitched copy (RGB: k_surf_copy_rows)
 void launch_surf_rows_to_rgb(hipStream_t s, int layout, const SurfEntry* entries, YuvCoef k, uint8_t* rgb, size_t rgb_stride, int h, int w,
                              int r0, int r1, int n);
 // device sinks (k_sink.hip): n dense RGB frames of h x w, rgb_stride bytes apart -> the n surfaces of entries[] (host memory) in

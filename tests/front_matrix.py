@@ -4,7 +4,7 @@ are for; test_gpu_front_matrix.py runs them).
 
 Sizes (camera = bird's-eye size): A 64 x 48 (width a multiple of 4: k_warp_split4 / k_warp_cal<4>), B 66 x 50 (24-bit rows of 198
 bytes and a bird's-eye width that are no multiples of 4: k_warp_split1 / k_warp_cal<1>), C 37 x 21 (odd in both directions, frames
-2331 bytes apart: the unaligned forms of plain RGB; the RGB family only -- the YUV formats need even sizes).
+2331 bytes apart: the unaligned forms of plain RGB; the RGB family only -- the YUV and raw Bayer formats need even sizes).
 
 Four calibration sets per size: the identity (every row and column, so the rows of a context are the whole image), one with taps
 outside the image in both remaps, one whose bird's-eye view reads a narrow run of camera rows, one with a general affine view.
@@ -15,11 +15,12 @@ import functools
 
 import numpy as np
 
+import bayer_reference as RB
 import yuv422_reference as R422
 import yuv_reference as R420
 
 SIZES = {"A": (64, 48), "B": (66, 50), "C": (37, 21)}
-FORMATS = ("rgb", "nv12", "i420", "yuy2", "uyvy", "bgr", "rgba", "bgra")
+FORMATS = ("rgb", "nv12", "i420", "yuy2", "uyvy", "bgr", "rgba", "bgra") + RB.PATTERNS
 RGB_FAMILY = ("rgb", "bgr", "rgba", "bgra")
 BPP = {"rgb": 3, "bgr": 3, "rgba": 4, "bgra": 4}
 N_SETS = 4
@@ -78,6 +79,8 @@ def frame_shape(fmt, size):
     w, h = SIZES[size]
     if fmt in BPP:
         return (h, w, BPP[fmt])
+    if fmt in RB.PATTERNS:
+        return (h, w)
     return (h, w, 2) if fmt in R422.ORDERS else (h * 3 // 2, w)
 
 
@@ -99,6 +102,8 @@ def to_rgb(frames, fmt, matrix="bt601"):
     if fmt in BPP:
         pick = {"rgb": lambda a: a, "bgr": lambda a: a[..., ::-1], "rgba": lambda a: a[..., :3], "bgra": lambda a: a[..., 2::-1]}[fmt]
         return np.ascontiguousarray(pick(f))
+    if fmt in RB.PATTERNS:
+        return RB.bayer_to_rgb(f, fmt)
     one = (lambda a: R422.yuv422_to_rgb(a, fmt, matrix)) if fmt in R422.ORDERS else (lambda a: R420.yuv420_to_rgb(a, fmt, matrix))
     nd = 3 if fmt in R422.ORDERS else 2
     return one(f) if f.ndim == nd else np.stack([one(a) for a in f])
@@ -162,6 +167,8 @@ def surface_pitches(fmt, size):
         return BPP[fmt] * w + 5, None
     if fmt in R422.ORDERS:
         return 2 * w + 5, None
+    if fmt in RB.PATTERNS:
+        return w + 5, None
     return w + 5, (w if fmt == "nv12" else w // 2) + 5
 
 

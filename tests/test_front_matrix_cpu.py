@@ -6,6 +6,7 @@ import itertools
 import numpy as np
 import pytest
 
+import bayer_reference as RB
 import front_matrix as FM
 import yuv422_reference as R422
 import yuv_reference as R420
@@ -101,6 +102,9 @@ def test_the_reference_is_the_composition_the_format_suites_use(fmt, oracle):
             rgb = R422.yuv422_to_rgb(frame, fmt, m)
         elif fmt in ("nv12", "i420"):
             rgb = R420.yuv420_to_rgb(frame, fmt, m)
+        elif fmt in RB.PATTERNS:
+            rgb = RB.bayer_to_rgb(frame, fmt)
+            assert np.array_equal(rgb, RB.bayer_to_rgb_border(frame, fmt))
         elif fmt == "rgb":
             rgb = frame
         else:                                                           # the permutation that packs RGB into the format, undone

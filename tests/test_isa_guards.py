@@ -61,27 +61,39 @@ def _isa_split():
     return mod
 
 
-# DESIGN.md section 4, the budget of the undistortion walks: vector-memory instructions per kernel (table read 2, two tap rows of one
-# frame before the loop and of the next inside it -- 2 + 2 windows RGB, 4 + 4 NV12, 6 + 6 I420 -- and the store); the most
-# v_mul_lo_u32 (quarter rate) it may hold: the two of the block-index division in the RGB forms, none where the 4:2:0 conversion's
-# 24-bit multiplies would be the first to be widened; and the most VALU instructions inside the per-frame loop (the counts of the
-# kernels' former separate bodies, which the shared walk keeps with an empty asm in the blend: k_frontend.hip).
-UNDISTORT_BUDGET = {   # kernel: (vmem, mul_lo, loop VALU)
-    "k_undistort_rows<true>": (7, 2, 46),
-    "k_undistort_rows<false>": (7, 2, 46),
-    "k_undistort_rows_surf": (7, 2, 53),
-    "k_undistort_rows_yuv<1>": (11, 0, 134),
-    "k_undistort_rows_yuv<2>": (15, 0, 136),
-    "k_undistort_rows_yuv_surf<1>": (11, 0, 148),
-    "k_undistort_rows_yuv_surf<2>": (15, 0, 157),
+# DESIGN.md section 4, the budget of the undistortion walks -- the 50 instantiations of k_undistort_rows<LAYOUT, SRC, PER_SLOT>
+# (k_frontend.hip), from one compile.  Per layout and source (SRC 0: surfaces, 1 / 2: slots, dword-aligned / at any byte), for both table
+# forms: vector-memory instructions (2 table reads, the windows of two tap rows of one frame before the loop and of the next inside it --
+# 2 + 2 RGB family and 4:2:2, 4 + 4 NV12 and raw Bayer, 6 + 6 I420 -- and the store); the most v_mul_lo_u32 (quarter rate) it may hold: the
+# two of the block-index division in the 3-byte forms, none where a conversion's 24-bit multiplies would be the first to be widened; and
+# the most VALU instructions inside the per-frame loop (the compiler's own counts on the finished code, ROCm 7.2, no margin; the 4:2:0
+# ones are those of the kernels' former separate bodies, which the shared walk keeps with an empty asm in the blend).  The table-per-slot
+# forms have the caps of their one-table peers.
+RGB, BAYER = {0: (7, 2, 53), 1: (7, 2, 46), 2: (7, 2, 46)}, {0: (11, 0, 158), 1: (11, 0, 145)}
+PER_LAYOUT = {   # layout: {SRC: (vmem, mul_lo, loop VALU)}
+    0: RGB,
+    1: {0: (11, 0, 148), 1: (11, 0, 134)}, 2: {0: (15, 0, 157), 1: (15, 0, 136)},          # NV12, I420
+    3: {0: (7, 0, 114), 1: (7, 0, 107)}, 4: {0: (7, 0, 114), 1: (7, 0, 107)},              # YUY2, UYVY
+    5: {s: RGB[s] for s in (0, 1)}, 6: {s: RGB[s] for s in (0, 1)}, 7: {s: RGB[s] for s in (0, 1)},   # BGR, RGBA, BGRA: no more than RGB
+    16: BAYER, 17: BAYER, 18: BAYER, 19: BAYER,
 }
+UNDISTORT_BUDGET = {"k_undistort_rows<%d, %d, %s>" % (layout, src, per_slot): cap
+                    for layout, by_src in PER_LAYOUT.items() for src, cap in by_src.items() for per_slot in ("false", "true")}
 
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not found")
-def test_undistortion_walks_keep_their_instruction_budget():
-    table = _isa_split().table(_isa(os.path.join(CSRC, "k_frontend.hip")), "k_undistort_rows")
-    assert sorted(table) == sorted(UNDISTORT_BUDGET), sorted(table)
+@functools.lru_cache(maxsize=None)
+def _walks():
+    """-> (name -> counts, name -> instructions) of the walks, from the one compile of k_frontend.hip."""
+    split, isa = _isa_split(), _isa(os.path.join(CSRC, "k_frontend.hip"))
+    return split.table(isa, "k_undistort_rows"), {split.kernel_name(n): k["insts"] for n, k in split.kernels(isa).items()}
+
+
+def _hold(layouts, per_slot=("false", "true")):
+    """The walks of `layouts` in the table forms `per_slot` against their rows of the table -> [(name, counts)], for what a family adds."""
+    table, held = _walks()[0], []
     for name, (vmem, mul_lo, loop_valu) in UNDISTORT_BUDGET.items():
+        if int(name[name.index("<") + 1:name.index(",")]) not in layouts or name[name.rindex(" ") + 1:-1] not in per_slot:
+            continue
         st = table[name]
         print(name, st)
         assert st["vmem"] == vmem, "%s: %d vector-memory instructions, budget %d" % (name, st["vmem"], vmem)
@@ -89,3 +101,46 @@ def test_undistortion_walks_keep_their_instruction_budget():
         assert st["scratch"] == 0, "%s uses scratch" % name
         assert st["loop_valu"] is not None, "%s: no per-frame loop found" % name
         assert st["loop_valu"] <= loop_valu, "%s: %d VALU instructions per frame, budget %d" % (name, st["loop_valu"], loop_valu)
+        held.append((name, st))
+    return held
+
+
+needs_hipcc = pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not found")
+
+
+@needs_hipcc
+def test_undistortion_walks_keep_their_instruction_budget():
+    """The table lists exactly the walks that exist; RGB's one-table forms and 4:2:0's forms, one table and table per slot."""
+    assert len(UNDISTORT_BUDGET) == 50 and sorted(_walks()[0]) == sorted(UNDISTORT_BUDGET), sorted(_walks()[0])
+    assert len(_hold({0}, ("false",))) == 3 and len(_hold({1, 2})) == 8
+
+
+@needs_hipcc
+def test_rgb_table_per_slot_forms_keep_the_caps_of_the_one_table_forms():
+    assert len(_hold({0}, ("true",))) == 3
+
+
+@needs_hipcc
+def test_rgb_family_instantiations_cost_no_more_than_rgb():
+    assert len(_hold({5, 6, 7})) == 12
+
+
+@needs_hipcc
+def test_422_instantiations_keep_their_budget_and_eight_waves():
+    held = _hold({3, 4})
+    assert len(held) == 8
+    for name, st in held:                    # no quarter-rate multiply at all, and eight waves per SIMD
+        assert st["mul_lo"] == 0, "%s: %d v_mul_lo_u32" % (name, st["mul_lo"])
+        assert st["vgpr"] < 64, "%s: %d VGPRs" % (name, st["vgpr"])
+
+
+@needs_hipcc
+def test_bayer_instantiations_keep_their_counts_and_load_whole_dwords():
+    held = _hold({16, 17, 18, 19})
+    assert len(held) == 16
+    for name, _ in held:
+        # every window is the aligned dwords that hold it: no byte or short loads from the frames (the 16-bit loads are the two
+        # remap-table reads)
+        loads = [i for i in _walks()[1][name] if re.match(r"^(buffer|global|flat)_load", i)]
+        assert not any("ubyte" in i or "sbyte" in i for i in loads), (name, loads)
+        assert sum("buffer_load_dwordx2" in i for i in loads) == 8, (name, loads)

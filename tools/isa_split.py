@@ -36,8 +36,8 @@ def kernels(text):
 
 
 def kernel_name(mangled):
-    """k_name or k_name<true / false / N> of an Itanium-mangled kernel symbol (the project's kernels are all named k_*, with at most
-    one bool or int template argument); the symbol itself where that does not fit.  (No demangler is called: ROCm's llvm/bin has
+    """k_name or k_name<true / false / N, ...> of an Itanium-mangled kernel symbol (the project's kernels are all named k_*, with bool
+    and int template arguments only: k_undistort_rows<5, 1, false>); the symbol itself where that does not fit.  (No demangler is called: ROCm's llvm/bin has
     none, and a guard test should not hang on binutils being installed.)"""
     m = re.search(r"(\d+)k_", mangled)
     if not m:
@@ -48,9 +48,9 @@ def kernel_name(mangled):
     if n is None:
         return mangled
     name, rest = mangled[start:start + n], mangled[start + n:]
-    t = re.match(r"IL([bi])(\d+)EE", rest)
+    t = re.match(r"I((?:L[bi]\d+E)+)E", rest)
     if t:
-        name += "<%s>" % (("false", "true")[int(t.group(2))] if t.group(1) == "b" else t.group(2))
+        name += "<%s>" % ", ".join(("false", "true")[int(v)] if c == "b" else v for c, v in re.findall(r"L([bi])(\d+)E", t.group(1)))
     elif rest.startswith("I"):
         return mangled
     return name
