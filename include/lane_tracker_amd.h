@@ -61,7 +61,8 @@ extern "C" {
  *    lt_overlay_run_inplace_coeffs (lane and text drawn into the attached camera surfaces themselves); lt_overlay_run_to_surfaces +
  *    lt_last_overlay_launches (lane and text drawn on the way into device sinks, one launch whatever the slots' calibration sets);
  *    lt_set_input_size + lt_get_input_size + lt_get_input_rows (RGB camera frames of another size than the calibration's, resized on
- *    the device).  Nothing removed or changed. */
+ *    the device); lt_set_raw_lut + lt_get_raw_lut (black level, white balance and tone curve of raw Bayer input as one table per colour
+ *    phase, looked up on the device inside the undistortion and the row conversion).  Nothing removed or changed. */
 #define LT_ABI_VERSION 5
 
 typedef enum lt_status {
@@ -234,8 +235,23 @@ int  lt_set_streams(lt_ctx* ctx, int nstreams);
  * rows at the least); lt_set_direct_upload returns 0.  lt_bayer_to_rgb is the conversion alone, of one host frame of h x w (even,
  * 4 .. 16384 each) on the device: out_rgb = h * w * 3 bytes.  Raw Bayer is an INPUT format only: lt_rgb_to_surfaces,
  * lt_overlay_store_device and lt_overlay_run_to_surfaces return LT_ERR_INVALID for these layouts, lt_overlay_run_inplace* on such a
- * context and lt_set_input_size with such a format return LT_ERR_STATE; lt_yuv_to_rgb does not take them.  Not built: 10 / 12 / 16-bit
- * or companded raw, other demosaics, white balance or any other step of an image signal processor. */
+ * context and lt_set_input_size with such a format return LT_ERR_STATE; lt_yuv_to_rgb does not take them.
+ * A RAW TABLE conditions the samples before the demosaic: black-level subtraction, per-colour gains (white balance) and a tone curve are
+ * together one 256-entry table per colour of the mosaic.  `lut` is uint8[4][256] (1024 bytes), indexed by the colour phase of a site --
+ * 0: a red site, 1: green on a red row, 2: green on a blue row, 3: a blue site (phase = 2 * ((y ^ red_row) & 1) + ((x ^ red_col) & 1), the
+ * red sites of RGGB / GRBG / GBRG / BGGR at (row, column) parity (0,0) / (0,1) / (1,0) / (1,1)) -- and the conditioned mosaic is
+ *     s'(y, x) = lut[phase(y, x)][s(y, x)];
+ * everything above is computed on s', the demosaic and its border rule included.  Whatever a context with table L computes from frames F
+ * -- undistorted rows, planes, masks, records, camera frames, annotated frames, visualisations -- is bit for bit what the same context
+ * without a table computes from the frames conditioned on the host.  lt_set_raw_lut(ctx, lut) sets the table, NULL removes it; it is allowed
+ * before and after uploads, waits for everything the context has in flight (as lt_sync does), then writes the device copy, and governs every
+ * undistortion and row conversion launched afterwards (what was computed before stays as it is; a front end is not reused across the
+ * call).  It is a set-up call, or an occasional one -- an auto-white-balance step between windows -- NOT a per-frame call: it stalls the
+ * context.  With a table set the conditioned kernels run whatever the table holds, the identity included; with none, the plain ones.
+ * LT_ERR_STATE in a context whose input format is not raw Bayer; lt_set_input_format with a layout that is not raw Bayer removes the table.
+ * lt_get_raw_lut: *is_set := 0 / 1 and, where one is set, the table into `lut` (either may be NULL).  Slots, uploads and lt_bayer_to_rgb are
+ * unaffected.  Not built: 10 / 12 / 16-bit or companded raw, other demosaics, a colour-correction matrix, lens-shading correction, a table
+ * per slot. */
 enum lt_input_layout { LT_INPUT_RGB = 0, LT_INPUT_NV12 = 1, LT_INPUT_I420 = 2, LT_INPUT_YUY2 = 3, LT_INPUT_UYVY = 4,
                        LT_INPUT_BGR = 5, LT_INPUT_RGBA = 6, LT_INPUT_BGRA = 7,
                        LT_INPUT_BAYER_RGGB = 16, LT_INPUT_BAYER_GRBG = 17, LT_INPUT_BAYER_GBRG = 18, LT_INPUT_BAYER_BGGR = 19 };
@@ -245,6 +261,8 @@ int  lt_set_input_format(lt_ctx* ctx, int layout, const int32_t coeffs[5]);
 int  lt_get_input_format(lt_ctx* ctx, int* layout, int32_t coeffs[5]);
 int  lt_yuv_to_rgb(lt_ctx* ctx, const uint8_t* frame, int h, int w, int layout, const int32_t coeffs[5], uint8_t* out_rgb);
 int  lt_bayer_to_rgb(lt_ctx* ctx, const uint8_t* frame, int h, int w, int layout, uint8_t* out_rgb);
+int  lt_set_raw_lut(lt_ctx* ctx, const uint8_t* lut /* 1024 bytes, phase-major; NULL: none */);
+int  lt_get_raw_lut(lt_ctx* ctx, uint8_t* lut /* 1024 bytes */, int* is_set);
 /* Frames of another SIZE than the calibration's: a context with an input size of src_w x src_h takes RGB frames of src_h * src_w * 3
  * bytes and resizes them on the device to img_w x img_h -- cv2.resize(frame, (img_w, img_h)) with the default INTER_LINEAR, bit for bit:
  * half-pixel centres, 11-bit coefficients, OpenCV's two-stage rounding.  Everything the context computes, keeps and hands out is what a

@@ -234,6 +234,8 @@ _SIGNATURES = {
     "lt_get_input_rows": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "lt_yuv_to_rgb": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "lt_bayer_to_rgb": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "lt_set_raw_lut": (C.c_int, [_P, _P]),
+    "lt_get_raw_lut": (C.c_int, [_P, _P, C.POINTER(C.c_int)]),
     "lt_attach_device_frames": (C.c_int, [_P, _P, C.c_int, C.c_int]),
     "lt_device_frames_rest": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "lt_device_alloc": (C.c_int, [C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]),
@@ -349,6 +351,17 @@ def yuv_coeffs(matrix):
     if k.shape != (5,):
         raise ValueError("a conversion matrix is five integers")
     return k
+
+
+def checked_raw_lut(raw_lut, pixel_format):
+    """`raw_lut` of a tracker or group as the u8 (4, 256) array the device takes, or None; ValueError -- before any device call -- for a
+    table with a pixel format that is not raw Bayer, for another shape or another dtype."""
+    if raw_lut is None:
+        return None
+    from .utils import checked_raw_lut as _checked
+    if pixel_format not in BAYER_FORMATS:
+        raise ValueError("raw_lut conditions raw Bayer frames: pixel_format=%r takes none" % (pixel_format,))
+    return _checked(raw_lut)
 
 
 def checked_input_size(input_size, img_size, pixel_format="rgb"):
@@ -904,6 +917,19 @@ class Context:
         k = yuv_coeffs(matrix)
         _check(self.lib.lt_yuv_to_rgb(self._h, a.ctypes.data, h, w, pixel_format_id(layout), k.ctypes.data, out.ctypes.data))
         return out
+
+    def set_raw_lut(self, lut):
+        """The raw table of a raw Bayer context -- u8 (4, 256), `utils.raw_lut` -- or None for none (lt_set_raw_lut): every sample is
+        looked up in the row of its colour phase before the demosaic, in the undistortion and in the row conversion launched from now
+        on.  Waits for the context's outstanding work: a set-up or occasional call, not a per-frame one."""
+        a = checked_raw_lut(lut, self._pixel_format)
+        _check(self.lib.lt_set_raw_lut(self._h, None if a is None else a.ctypes.data))
+
+    def raw_lut(self):
+        """-> the raw table, u8 (4, 256), or None (lt_get_raw_lut)."""
+        out, is_set = np.zeros((4, 256), np.uint8), C.c_int(0)
+        _check(self.lib.lt_get_raw_lut(self._h, out.ctypes.data, C.byref(is_set)))
+        return out if is_set.value else None
 
     def bayer_to_rgb(self, frame, pattern="bayer_rggb"):
         """One 8-bit raw Bayer frame (H, W), H and W even and at least 4, -> RGB (H, W, 3): the bilinear demosaic, on the device

@@ -82,5 +82,21 @@ BA_HD uint32_t window_tap(uint32_t r0, uint32_t r1, uint32_t r2, uint32_t r3, in
     return demosaic(c, hs, vs, ds, ph);
 }
 
+// ---- raw tables (lt_set_raw_lut) -------------------------------------------------------------------------------------------------
+// A raw table is uint8[4][256], one row per colour phase: the conditioned mosaic is s'(y, x) = lut[phase(pattern, y, x)][s(y, x)] and
+// everything else is the arithmetic above on s'.  Along a row of the mosaic the phase alternates between the two of that row, so a run
+// of sites is conditioned with two row bases, that of its first site and that of the next.
+
+// byte offset of the table row of the site with row parity par_y and column parity par_x
+BA_HD constexpr int lut_row(int pattern, int par_y, int par_x) { return 256 * phase_of(pattern, par_y, par_x); }
+// The four bytes of dword w -- consecutive sites of one row of the mosaic, byte 0 the first -- conditioned: rowa / rowb are the table
+// rows (lut + lut_row(..)) of the sites at bytes 0, 2 and at bytes 1, 3.  The one expression of the kernels and the host test.
+BA_HD uint32_t condition4(uint32_t w, const uint8_t* rowa, const uint8_t* rowb) {
+    return (uint32_t)rowa[w & 255u] | ((uint32_t)rowb[(w >> 8) & 255u] << 8) | ((uint32_t)rowa[(w >> 16) & 255u] << 16) |
+           ((uint32_t)rowb[w >> 24] << 24);
+}
+// one site
+BA_HD uint32_t condition1(uint32_t s, const uint8_t* row) { return row[s & 255u]; }
+
 }  // namespace ba
 }  // namespace lt

@@ -11,6 +11,9 @@
 //   k_rows_to_rgb<LAYOUT, SURF, WIDE>  a run of rows of frames in LAYOUT (not 0) as RGB, for whoever shows the camera frame
 //                      (cv2.cvtColor(YUV2RGB_NV12 / _I420 / _YUY2 / _UYVY), a permutation, the demosaic), from a slot's staging frame / from
 //                      a surface (SURF): one 16-column (WIDE) and one byte-wise body per family of layouts; k_surf_copy_rows: RGB surfaces
+//   k_raw_walk_rows<PATTERN, SRC, PER_SLOT>, k_raw_rows_rgb<PATTERN, SURF, WIDE>  the two above for raw Bayer frames behind a raw table
+//                      (lt_set_raw_lut: black level, white balance and tone curve as one 256-entry table per colour phase, staged in
+//                      LDS): every byte looked up before it is demosaiced; launched in their place whenever a table is set
 //   k_warp_split       cv2.warpPerspective      lane_tracker.py:834
 //                      + img[:,:,0]             lane_tracker.py:207
 //                      + cvtColor(RGB2LAB)[:,:,2] lane_tracker.py:208
@@ -287,6 +290,37 @@ struct Bayer8 {
 template <class F> struct PlacesRows : std::false_type {};
 template <int PATTERN> struct PlacesRows<Bayer8<PATTERN>> : std::true_type {};
 
+// Raw Bayer behind a raw table (lt_set_raw_lut; bayer_arith.h: s' = lut[phase][s]): Bayer8 whose 16 window bytes are looked up before
+// they reach window_tap -- no extra pass over the frame, no extra byte from it.  The 1 KB table lies in LDS (`lut`), staged by the 256
+// threads of the workgroup, one dword each, before any of them leaves the walk.  Window byte (r, c) is site (by + r, bx + c), so rows 0, 2
+// and rows 1, 3 of the window have two table rows each: four LDS row bases, frame-independent, found once per walk (place_rows).
+template <int PATTERN>
+struct Bayer8Lut : Bayer8<PATTERN> {
+    typedef Bayer8<PATTERN> Base;
+    typedef typename Base::Taps Taps;
+    uint8_t* lut;                            // LDS, 1024 bytes
+    const uint32_t* table;                   // the context's table, device memory, 256 dwords
+    const uint8_t *ea, *eb, *oa, *ob;        // rows 0, 2 of the window: the table rows of columns 0, 2 / 1, 3; rows 1, 3: the same
+    __device__ __forceinline__ void stage() const {
+        reinterpret_cast<uint32_t*>(lut)[threadIdx.x] = table[threadIdx.x];
+        __syncthreads();
+    }
+    __device__ __forceinline__ void place_rows(int cy0, int cy1) {
+        Base::place_rows(cy0, cy1);
+        const int py = this->by & 1, px = this->bx & 1;
+        ea = lut + ba::lut_row(PATTERN, py, px), eb = lut + ba::lut_row(PATTERN, py, px ^ 1);
+        oa = lut + ba::lut_row(PATTERN, py ^ 1, px), ob = lut + ba::lut_row(PATTERN, py ^ 1, px ^ 1);
+    }
+    __device__ __forceinline__ void decode(const Taps& t, uint32_t& a0, uint32_t& a1, uint32_t& b0, uint32_t& b1) const {
+        const Taps c{ba::condition4(t.r0, ea, eb), ba::condition4(t.r1, oa, ob), ba::condition4(t.r2, ea, eb), ba::condition4(t.r3, oa, ob)};
+        Base::decode(c, a0, a1, b0, b1);
+    }
+};
+template <int PATTERN> struct PlacesRows<Bayer8Lut<PATTERN>> : std::true_type {};
+// a format that stages a table in LDS does so before any thread of the workgroup leaves the walk
+template <class F> struct StagesTable : std::false_type {};
+template <int PATTERN> struct StagesTable<Bayer8Lut<PATTERN>> : std::true_type {};
+
 // The slots' own frames: `stride` bytes apart, planes dense.  One buffer resource covers the frames [z0, z1) of the walk (a frame
 // is selected by the scalar offset of the load) plus the format's padding behind them; beyond that the resource returns 0.
 // 32-bit offsets (a walk stays below 2^30 bytes: launch_undistort_rows) keep the address math on full-rate 24-bit multiplies.
@@ -390,6 +424,7 @@ __device__ __forceinline__ void undistort_walk(const WalkArgs& a, Source src, Fo
     // work-group-size path -- a third v_mul_lo_u32 and a global_load_ushort in the prologue)
     const int x = bx * __builtin_amdgcn_workgroup_size_x() + threadIdx.x;
     const int row = by;  // relative to g.r0
+    if constexpr (StagesTable<Format>::value) fmt.stage();
     if (x >= g.img_w) return;
     const int z0 = bz * a.fpb, z1 = min(z0 + a.fpb, a.n);   // fpb frames per thread: table entry and offsets are frame-independent
     const size_t o = (size_t)row * g.img_w + x;
@@ -472,6 +507,24 @@ __global__ __launch_bounds__(256) void k_undistort_rows(const SurfEntry* __restr
     const WalkArgs a{uxy, ufrac, SlotTables{sets, &ids}, g, und, und_px, first_slot, n, PER_SLOT ? 1 : fpb, remap};
     if constexpr (SRC == SRC_SURFACES) undistort_walk<PER_SLOT>(a, SurfSource{tab}, format_of<LAYOUT>(g, k));
     else undistort_walk<PER_SLOT>(a, SlotSource<SRC == SRC_SLOTS>{frames, stride}, format_of<LAYOUT>(g, k));
+}
+
+// The walk over raw Bayer frames behind a raw table (lt_set_raw_lut): PATTERN x source (surfaces, dword-aligned slots) x table form, the
+// parameters of k_undistort_rows and the context's table; launched in its place, in the same stage, whenever a table is set -- the
+// identity included.
+template <int PATTERN, int SRC, bool PER_SLOT>
+__global__ __launch_bounds__(256) void k_raw_walk_rows(const SurfEntry* __restrict__ tab, const uint8_t* __restrict__ frames, size_t stride,
+                                                      const int16_t* __restrict__ uxy, const uint16_t* __restrict__ ufrac,
+                                                      const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
+                                                      uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb, int remap,
+                                                      const uint32_t* __restrict__ raw_lut) {
+    static_assert(SRC == SRC_SURFACES || SRC == SRC_SLOTS, "a raw Bayer staging frame is dword-aligned");
+    __shared__ alignas(16) uint8_t s_lut[1024];
+    const WalkArgs a{uxy, ufrac, SlotTables{sets, &ids}, g, und, und_px, first_slot, n, PER_SLOT ? 1 : fpb, remap};
+    Bayer8Lut<PATTERN> fmt{};
+    fmt.w = g.img_w, fmt.h = g.img_h, fmt.lut = s_lut, fmt.table = raw_lut;
+    if constexpr (SRC == SRC_SURFACES) undistort_walk<PER_SLOT>(a, SurfSource{tab}, fmt);
+    else undistort_walk<PER_SLOT>(a, SlotSource<true>{frames, stride}, fmt);
 }
 
 // ---- camera rows -> RGB rows ---------------------------------------------------------------------------------------------------
@@ -710,6 +763,53 @@ struct RowsBayer {
         store_rgb1(dst + ((size_t)y * w + x) * 3, v);
     }
 };
+// RowsBayer behind a raw table (lt_set_raw_lut; `lut`: the table in LDS): the same two bodies over the conditioned mosaic, every byte
+// looked up in the table row of its site (bayer_arith.h: condition4 / condition1) before it is summed -- 3 x 18 lookups per 16 pixels
+// (wide), 9 per pixel (any).  Bodies of their own, so that the plain ones above stay the code they were.
+template <int P>
+struct RowsBayerLut {
+    // the table row of the sites of row parity par_y and column parity par_x
+    __device__ __forceinline__ static const uint8_t* trow(const uint8_t* lut, int par_y, int par_x) { return lut + ba::lut_row(P, par_y, par_x); }
+    __device__ __forceinline__ static void wide(const Planes& s, const uint8_t* lut, uint8_t* dst, int h, int w, int y, int x0) {
+        if (x0 >= w) return;
+        const int cy = ba::tap_pos(y, h), xl = max(x0 - 1, 0), xr = min(x0 + 16, w - 1);
+        uint32_t m[3][4], left[3], right[3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const uint8_t* row = s.y + (size_t)(cy - 1 + r) * s.pitch;
+            const int py = (cy - 1 + r) & 1;
+            const uint8_t *ta = trow(lut, py, 0), *tb = trow(lut, py, 1);     // (x0 is even: byte 0 of every dword is an even column)
+            const uint4 q = *reinterpret_cast<const uint4*>(row + x0);
+            m[r][0] = ba::condition4(q.x, ta, tb); m[r][1] = ba::condition4(q.y, ta, tb);
+            m[r][2] = ba::condition4(q.z, ta, tb); m[r][3] = ba::condition4(q.w, ta, tb);
+            left[r] = ba::condition1(row[xl], trow(lut, py, xl & 1));
+            right[r] = ba::condition1(row[xr], trow(lut, py, xr & 1));
+        }
+        auto at = [&](int r, int j) { return j < 0 ? left[r] : j > 15 ? right[r] : (m[r][j >> 2] >> (8 * (j & 3))) & 255u; };
+        uint32_t px[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+            px[j] = ba::demosaic(at(1, j), at(1, j - 1) + at(1, j + 1), at(0, j) + at(2, j),
+                                 at(0, j - 1) + at(0, j + 1) + at(2, j - 1) + at(2, j + 1), ba::phase(P, cy, j));
+        if (x0 == 0) px[0] = px[1];
+        if (x0 + 16 == w) px[15] = px[14];
+        uint32_t d[12];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) pack_rgb4(px + 4 * j, d + 3 * j);
+        store_rgb16(dst + ((size_t)y * w + x0) * 3, d);
+    }
+    __device__ __forceinline__ static void any(const Planes& s, const uint8_t* lut, uint8_t* dst, int h, int w, int y, int x) {
+        if (x >= w) return;
+        const int cy = ba::tap_pos(y, h), cx = ba::tap_pos(x, w);
+        const uint8_t *up = s.y + (size_t)(cy - 1) * s.pitch + cx, *mid = up + s.pitch, *dn = mid + s.pitch;
+        const int py = cy & 1, px = cx & 1;      // the site's parities; a neighbour one step away has the other one
+        auto u = [&](int i) { return ba::condition1(up[i], trow(lut, py ^ 1, px ^ (i & 1))); };
+        auto m = [&](int i) { return ba::condition1(mid[i], trow(lut, py, px ^ (i & 1))); };
+        auto d = [&](int i) { return ba::condition1(dn[i], trow(lut, py ^ 1, px ^ (i & 1))); };
+        const uint32_t v = ba::demosaic(m(0), m(-1) + m(1), u(0) + d(0), u(-1) + u(1) + d(-1) + d(1), ba::phase(P, cy, cx));
+        store_rgb1(dst + ((size_t)y * w + x) * 3, v);
+    }
+};
 // the description of a layout (none for 0, plain RGB: its rows are shown as they are)
 template <int L>
 using RowsOf = std::conditional_t<L <= 2, Rows420<L>, std::conditional_t<L <= 4, Rows422<L - 3>, std::conditional_t<L <= 7, RowsPx<L>, RowsBayer<L - 16>>>>;
@@ -738,6 +838,27 @@ __global__ __launch_bounds__(256) void k_rows_to_rgb(std::conditional_t<SURF, Su
     const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x), row = (D::CHROMA_ROWS ? r0 >> 1 : r0) + (int)blockIdx.y;
     if constexpr (WIDE) D::wide(p, k, dst, h, w, r0, r1, row, i * 16);
     else D::any(p, k, dst, h, w, r0, r1, row, i);
+}
+
+// The raw Bayer row conversion behind a raw table (lt_set_raw_lut): k_rows_to_rgb's bodies over the conditioned mosaic, 3 x 18 lookups per
+// 16 pixels (wide) or 9 per pixel, the table staged in LDS by the whole workgroup before any thread leaves.  Launched in k_rows_to_rgb's
+// place whenever a table is set.
+template <int PATTERN, bool SURF, bool WIDE>
+__global__ __launch_bounds__(256) void k_raw_rows_rgb(std::conditional_t<SURF, SurfChunk, DenseFrames> src, uint8_t* __restrict__ rgb,
+                                                     size_t rgb_stride, int w, int r0, int h, const uint32_t* __restrict__ raw_lut) {
+    __shared__ alignas(16) uint8_t s_lut[1024];
+    // (the wide body is launched with 64 threads, 16 bytes of the table each; the byte-wise one with 256, a dword each)
+    if constexpr (WIDE) reinterpret_cast<uint4*>(s_lut)[threadIdx.x] = reinterpret_cast<const uint4*>(raw_lut)[threadIdx.x];
+    else reinterpret_cast<uint32_t*>(s_lut)[threadIdx.x] = raw_lut[threadIdx.x];
+    __syncthreads();
+    typedef RowsBayerLut<PATTERN> D;
+    Planes p;
+    if constexpr (SURF) p = surf_planes(src.e[blockIdx.z]);
+    else p = RowsBayer<PATTERN>::dense(src.p + (size_t)blockIdx.z * src.stride, h, w);
+    uint8_t* dst = rgb + (size_t)blockIdx.z * rgb_stride;
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x), row = r0 + (int)blockIdx.y;
+    if constexpr (WIDE) D::wide(p, s_lut, dst, h, w, row, i * 16);
+    else D::any(p, s_lut, dst, h, w, row, i);
 }
 
 // Rows [r0, r1) of RGB surfaces -> the same rows of the slots' camera frames (row_bytes = 3 w, dense): a pitched row copy, one
@@ -1175,7 +1296,7 @@ static void with_layout(int layout, F&& f) {
 template <bool PER_SLOT>
 static void launch_walk(hipStream_t s, dim3 grid, FrameSource src, int layout, YuvCoef k, const int16_t* uxy, const uint16_t* ufrac,
                         const CalTables* sets, const CalIds& ids, FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n, int fpb,
-                        bool any_byte) {
+                        bool any_byte, const uint32_t* raw_lut) {
     const bool aligned = !any_byte && ((uintptr_t)src.frames & 3) == 0 && (src.stride & 3) == 0 && src.stride < (1u << 30);
     const int remap = xcd_remap();
     with_layout(layout, [&](auto l) {
@@ -1183,6 +1304,13 @@ static void launch_walk(hipStream_t s, dim3 grid, FrameSource src, int layout, Y
         auto launch = [&](auto k_walk) {
             hipLaunchKernelGGL(k_walk, grid, dim3(256), 0, s, src.tab, src.frames, src.stride, k, uxy, ufrac, sets, ids, g, und, und_px, first_slot, n, fpb, remap);
         };
+        if constexpr (L >= 16) {
+            if (raw_lut) {                   // raw Bayer behind a raw table: the conditioned walk, whatever the table holds
+                auto k_raw = src.tab ? k_raw_walk_rows<L - 16, SRC_SURFACES, PER_SLOT> : k_raw_walk_rows<L - 16, SRC_SLOTS, PER_SLOT>;
+                hipLaunchKernelGGL(k_raw, grid, dim3(256), 0, s, src.tab, src.frames, src.stride, uxy, ufrac, sets, ids, g, und, und_px, first_slot, n, fpb, remap, raw_lut);
+                return;
+            }
+        }
         if (src.tab) launch(k_undistort_rows<L, SRC_SURFACES, PER_SLOT>);
         else if (L != 0 || aligned) launch(k_undistort_rows<L, SRC_SLOTS, PER_SLOT>);
         else launch(k_undistort_rows<0, SRC_SLOTS_ANY_BYTE, PER_SLOT>);
@@ -1190,7 +1318,7 @@ static void launch_walk(hipStream_t s, dim3 grid, FrameSource src, int layout, Y
 }
 
 void launch_undistort_rows(hipStream_t s, FrameSource src, int layout, YuvCoef k, const int16_t* uxy, const uint16_t* ufrac,
-                           FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n) {
+                           FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n, const uint32_t* raw_lut) {
     if (n <= 0 || g.nrows <= 0) return;
     int fpb = frames_per_thread(n);
     // the slots of a walk are addressed by a 32-bit offset into one buffer resource: a walk stays below 2^30 bytes (one frame
@@ -1198,19 +1326,30 @@ void launch_undistort_rows(hipStream_t s, FrameSource src, int layout, YuvCoef k
     if (!src.tab) fpb = (int)std::max<size_t>(1, std::min<size_t>((size_t)fpb, (((size_t)1 << 30) - 1) / src.stride));
     const dim3 grid((g.img_w + 255) / 256, g.nrows, (n + fpb - 1) / fpb);
     static const bool unaligned = [] { const char* e = LT_EXP_ENV("LT_UNDISTORT_UNALIGNED"); return e && e[0] == '1'; }();   // A/B
-    launch_walk<false>(s, grid, src, layout, k, uxy, ufrac, nullptr, CalIds{}, g, und, und_px, first_slot, n, fpb, unaligned);
+    launch_walk<false>(s, grid, src, layout, k, uxy, ufrac, nullptr, CalIds{}, g, und, und_px, first_slot, n, fpb, unaligned, raw_lut);
 }
 
 // The row conversion of n frames in `layout` (not 0), dense or from surfaces: the 16-column kernel where the width and every base and
 // pitch of the launch (`bits`: all of them ORed) are multiples of 16, the byte-wise one otherwise.
 template <bool SURF, class Src>
 static void launch_rows_to_rgb(hipStream_t s, int layout, const Src& src, size_t bits, YuvCoef k, uint8_t* rgb, size_t rgb_stride, int h, int w,
-                               int r0, int r1, int n) {
+                               int r0, int r1, int n, const uint32_t* raw_lut) {
     with_layout(layout, [&](auto l) {
         constexpr int L = decltype(l)::value;
         if constexpr (L != 0) {
             typedef RowsOf<L> D;
             const unsigned rows = (unsigned)(D::CHROMA_ROWS ? ((r1 + 1) >> 1) - (r0 >> 1) : r1 - r0);
+            if constexpr (L >= 16) {
+                if (raw_lut) {               // raw Bayer behind a raw table: the conditioned bodies, the same two launch shapes
+                    if ((w & 15) == 0 && (bits & 15) == 0)
+                        hipLaunchKernelGGL((k_raw_rows_rgb<L - 16, SURF, true>), dim3((unsigned)((w / 16 + 63) / 64), rows, (unsigned)n), dim3(64), 0, s,
+                                           src, rgb, rgb_stride, w, r0, h, raw_lut);
+                    else
+                        hipLaunchKernelGGL((k_raw_rows_rgb<L - 16, SURF, false>), dim3((unsigned)((w + 255) / 256), rows, (unsigned)n), dim3(256), 0, s,
+                                           src, rgb, rgb_stride, w, r0, h, raw_lut);
+                    return;
+                }
+            }
             if ((w & 15) == 0 && (bits & 15) == 0)
                 hipLaunchKernelGGL((k_rows_to_rgb<L, SURF, true>), dim3((unsigned)((w / 16 + 63) / 64), rows, (unsigned)n), dim3(64), 0, s,
                                    src, rgb, rgb_stride, w, r0, r1, h, k);
@@ -1222,10 +1361,10 @@ static void launch_rows_to_rgb(hipStream_t s, int layout, const Src& src, size_t
 }
 
 void launch_yuv_rows_to_rgb(hipStream_t s, int layout, const uint8_t* yuv, size_t yuv_stride, YuvCoef k, uint8_t* rgb,
-                            size_t rgb_stride, int h, int w, int r0, int r1, int n) {
+                            size_t rgb_stride, int h, int w, int r0, int r1, int n, const uint32_t* raw_lut) {
     if (n <= 0 || r1 <= r0) return;
     launch_rows_to_rgb<false>(s, layout, DenseFrames{yuv, yuv_stride}, yuv_stride | rgb_stride | (size_t)(uintptr_t)yuv | (size_t)(uintptr_t)rgb, k,
-                              rgb, rgb_stride, h, w, r0, r1, n);
+                              rgb, rgb_stride, h, w, r0, r1, n, raw_lut);
 }
 
 void launch_write_surf_entries(hipStream_t s, SurfEntry* tab, int first, const SurfEntry* entries, int n) {
@@ -1238,7 +1377,7 @@ void launch_write_surf_entries(hipStream_t s, SurfEntry* tab, int first, const S
 }
 
 void launch_surf_rows_to_rgb(hipStream_t s, int layout, const SurfEntry* entries, YuvCoef k, uint8_t* rgb, size_t rgb_stride, int h, int w,
-                             int r0, int r1, int n) {
+                             int r0, int r1, int n, const uint32_t* raw_lut) {
     if (n <= 0 || r1 <= r0) return;
     for (int i = 0; i < n; i += SurfChunk::N) {
         const int m = std::min(n - i, (int)SurfChunk::N);
@@ -1258,7 +1397,7 @@ void launch_surf_rows_to_rgb(hipStream_t s, int layout, const SurfEntry* entries
             else
                 hipLaunchKernelGGL(k_surf_copy_rows<false>, dim3((unsigned)((row_bytes + 255) / 256), (unsigned)(r1 - r0), (unsigned)m), dim3(256), 0, s, ch, dst, rgb_stride, row_bytes, r0);
         } else {
-            launch_rows_to_rgb<true>(s, layout, ch, bits, k, dst, rgb_stride, h, w, r0, r1, m);
+            launch_rows_to_rgb<true>(s, layout, ch, bits, k, dst, rgb_stride, h, w, r0, r1, m, raw_lut);
         }
     }
 }
@@ -1288,13 +1427,13 @@ static CalIds pack_ids(const uint8_t* ids, int m) {
 }
 
 void launch_undistort_cal(hipStream_t s, FrameSource src, int layout, YuvCoef k, const CalTables* sets, const uint8_t* ids,
-                          FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n) {
+                          FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n, const uint32_t* raw_lut) {
     if (n <= 0 || g.nrows <= 0) return;
     for (int i = 0; i < n; i += CalIds::N) {
         const int m = std::min(n - i, (int)CalIds::N);
         const dim3 grid((g.img_w + 255) / 256, g.nrows, m);
         const FrameSource part = src.tab ? src : FrameSource::slots(src.frames + (size_t)i * src.stride, src.stride);
-        launch_walk<true>(s, grid, part, layout, k, nullptr, nullptr, sets, pack_ids(ids + i, m), g, und, und_px, first_slot + i, m, 1, false);
+        launch_walk<true>(s, grid, part, layout, k, nullptr, nullptr, sets, pack_ids(ids + i, m), g, und, und_px, first_slot + i, m, 1, false, raw_lut);
     }
 }
 

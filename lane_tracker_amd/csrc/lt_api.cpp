@@ -715,6 +715,7 @@ void lt_destroy(lt_ctx* c) {
     dev_free(c->d_coef);
     dev_free(c->d_rs_xt);
     dev_free(c->d_rs_yt);
+    dev_free(c->d_raw_lut);
     dev_free(c->d_oxy);
     dev_free(c->d_ofrac);
     for (size_t i = 1; i < c->cal.size(); ++i) {     // (set 0's tables are the ones above)
@@ -901,6 +902,7 @@ int lt_set_input_format(lt_ctx* c, int layout, const int32_t* coeffs) {
         return fail(LT_ERR_STATE, "a context with an input size (lt_set_input_size) takes RGB frames only: frames of another format are not resized");
     if ((rc = set_device(c))) return rc;
     if ((rc = sync_all(c))) return rc;
+    if (!is_bayer(layout)) c->raw_lut_set = false;     // a raw table belongs to raw Bayer input
     if (layout == LT_INPUT_RGB) {
         dev_free(c->d_yuv);
     } else {
@@ -917,6 +919,32 @@ int lt_set_input_format(lt_ctx* c, int layout, const int32_t* coeffs) {
         if (!plain) std::memcpy(c->yuv_coef, coeffs, sizeof c->yuv_coef);
     }
     c->in_layout = layout;
+    return LT_OK;
+}
+
+// The raw table: set-up or occasional (between windows), behind everything the context has in flight; what is launched afterwards reads
+// the new one.  Planes and camera frames computed with the old one stay what they are: the slots' front ends are marked as not run, so
+// that a re-run (lt_mask_rerun) computes them again.
+int lt_set_raw_lut(lt_ctx* c, const uint8_t* lut) {
+    if (!c) return fail(LT_ERR_INVALID, "null context");
+    if (!is_bayer(c->in_layout)) return fail(LT_ERR_STATE, "a raw table conditions raw Bayer input: this context's input format is another layout");
+    int rc;
+    if ((rc = set_device(c))) return rc;
+    if ((rc = sync_all(c))) return rc;
+    if (lut) {
+        if (!c->d_raw_lut && (rc = dev_alloc(&c->d_raw_lut, 256))) return rc;
+        HIP_TRY(hipMemcpy(c->d_raw_lut, lut, sizeof c->raw_lut, hipMemcpyHostToDevice));
+        std::memcpy(c->raw_lut, lut, sizeof c->raw_lut);
+    }
+    c->raw_lut_set = lut != nullptr;
+    std::fill(c->front_ok.begin(), c->front_ok.end(), (uint8_t)0);
+    return LT_OK;
+}
+
+int lt_get_raw_lut(lt_ctx* c, uint8_t* lut, int* is_set) {
+    if (!c) return fail(LT_ERR_INVALID, "null context");
+    if (is_set) *is_set = c->raw_lut_set ? 1 : 0;
+    if (lut && c->raw_lut_set) std::memcpy(lut, c->raw_lut, sizeof c->raw_lut);
     return LT_OK;
 }
 
@@ -952,7 +980,7 @@ static inline int chroma_hi(int r0, int r1) { return r1 > r0 ? (r1 - 1) / 2 + 1 
 // rows [r0, r1) of the staging frames of slots [first, first + n) -> the same rows of their RGB camera frames, on `st`
 static void yuv_convert(lt_ctx* c, hipStream_t st, int first, int n, int r0, int r1) {
     launch_yuv_rows_to_rgb(st, c->in_layout, slot_yuv(c, first), c->yuv_stride, yuv_coef_of(c), slot_frame(c, first), c->frame_bytes,
-                           c->calib.img_h, c->calib.img_w, r0, r1, n);
+                           c->calib.img_h, c->calib.img_w, r0, r1, n, raw_lut_of(c));
 }
 
 // ---- input frames of another size (lt_set_input_size) ------------------------------------------------------------------------
@@ -1613,7 +1641,7 @@ int lt_device_frames_rest(lt_ctx* c, int first, int n, const int32_t* rows4) {
     const int32_t* r = rows4 ? rows4 : whole;
     for (int k = 0; k < 4; k += 2)
         launch_surf_rows_to_rgb(c->copy, c->in_layout, &c->surf[(size_t)first], yuv_coef_of(c), slot_frame(c, first), c->frame_bytes,
-                                c->calib.img_h, c->calib.img_w, r[k], r[k + 1], n);
+                                c->calib.img_h, c->calib.img_w, r[k], r[k + 1], n, raw_lut_of(c));
     HIP_TRY(hipGetLastError());
     if ((rc = note_range(c->readers, c->copy, first, first + n))) return rc;      // it reads the surfaces and writes the camera frames: the next upload waits
     if (!rows4) mark_frames(c, first, n, 1);
@@ -2289,8 +2317,8 @@ static int mask_run_impl(lt_ctx* c, int first, int n, const lt_filter_params* p,
                   const FrameSource src = att ? FrameSource::surfaces(c->d_surf)
                                           : c->in_layout != LT_INPUT_RGB ? FrameSource::slots(slot_yuv(c, a), c->yuv_stride)
                                                                          : FrameSource::slots(slot_frame(c, a), c->frame_bytes);
-                  if (mixed) launch_undistort_cal(st, src, c->in_layout, yuv_coef_of(c), c->d_cal, &c->slot_cal[(size_t)a], c->fe, c->d_und, c->und_px, a, b - a);
-                  else launch_undistort_rows(st, src, c->in_layout, yuv_coef_of(c), cs.d_uxy, cs.d_ufrac, c->fe, c->d_und, c->und_px, a, b - a);
+                  if (mixed) launch_undistort_cal(st, src, c->in_layout, yuv_coef_of(c), c->d_cal, &c->slot_cal[(size_t)a], c->fe, c->d_und, c->und_px, a, b - a, raw_lut_of(c));
+                  else launch_undistort_rows(st, src, c->in_layout, yuv_coef_of(c), cs.d_uxy, cs.d_ufrac, c->fe, c->d_und, c->und_px, a, b - a, raw_lut_of(c));
               } }
             { int mrc = n == 1 ? note_range_frame(c, c->readers, st, f0, f0 + m) : note_range(c->readers, st, f0, f0 + m); if (mrc) return mrc; }
             { StageScope t(c, ST_WARP_SPLIT, st);

@@ -160,6 +160,12 @@ struct lt_ctx {
     bool input_locked = false;                // an upload has happened: the format stays
     uint8_t* d_yuv = nullptr;
     size_t yuv_bytes = 0, yuv_stride = 0;
+    // The raw table of a raw Bayer context (lt_set_raw_lut): uint8[4][256], phase-major, on the host and -- allocated by the first set, kept --
+    // in device memory, where the conditioned walk and row conversion (k_raw_walk_rows, k_raw_rows_rgb) stage it in LDS.  raw_lut_set says
+    // which kernels are launched: the table's content never does.
+    bool raw_lut_set = false;
+    uint8_t raw_lut[1024] = {0};
+    uint32_t* d_raw_lut = nullptr;
     // Input frames of another size (lt_set_input_size): src_w x src_h RGB frames, resized on the device to the calibration's size
     // (cv2.resize, INTER_LINEAR).  Per slot a staging frame of src_bytes = src_h * src_w * 3 bytes, src_stride apart (a multiple of 16
     // with at least 16 bytes of padding behind every frame: k_resize_rows reads aligned dwords); the uploads copy source rows into it
@@ -350,6 +356,8 @@ inline uint8_t* slot_frame(const lt_ctx* c, int s) { return c->d_frames + (size_
 inline bool is_rgb_family(int layout) { return layout == LT_INPUT_BGR || layout == LT_INPUT_RGBA || layout == LT_INPUT_BGRA; }
 // 8-bit raw Bayer (RGGB, GRBG, GBRG, BGGR): one plane of one byte a pixel, an input format only
 inline bool is_bayer(int layout) { return layout >= LT_INPUT_BAYER_RGGB && layout <= LT_INPUT_BAYER_BGGR; }
+// the raw table the front end and the row conversion of `c` are launched with: null without one
+inline const uint32_t* raw_lut_of(const lt_ctx* c) { return c->raw_lut_set ? c->d_raw_lut : nullptr; }
 inline int packed_bpp(int layout) {
     return layout == LT_INPUT_RGB || layout == LT_INPUT_BGR ? 3 : layout == LT_INPUT_RGBA || layout == LT_INPUT_BGRA ? 4
            : layout == LT_INPUT_YUY2 || layout == LT_INPUT_UYVY ? 2 : is_bayer(layout) ? 1 : 0;

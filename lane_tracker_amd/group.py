@@ -52,6 +52,7 @@ class _GroupMember(LaneTracker):
     # (wraps: process()'s signature stays LaneTracker.process's -- _batch_arguments reads the keywords and defaults from it)
     process = functools.wraps(LaneTracker.process)(_not_owned)
     process_batch = process_stream = warm = _not_owned
+    set_raw_lut = _not_owned        # (one table for the whole group: LaneTrackerGroup.set_raw_lut)
     _owns_context = False           # close() leaves the group's context to LaneTrackerGroup.close
 
 
@@ -106,7 +107,7 @@ class LaneTrackerGroup:
 
     def __init__(self, k, img_size, warped_size, cam_matrix, dist_coeffs, warp_matrices, mpp_conversion, n_fail=8, n_reset=4,
                  n_average=2, print_frame_count=False, device=0, *, pixel_format='rgb', yuv_matrix='bt601', calibrations=None,
-                 input_size=None):
+                 input_size=None, raw_lut=None):
         k = int(k)
         if k < 1:
             raise ValueError("a group needs at least one stream")
@@ -123,6 +124,7 @@ class LaneTrackerGroup:
         self._resize_from = _native.checked_input_size(input_size, img_size, pixel_format)
         if self._resize_from is not None:
             self._frame_shape = (self._resize_from[1], self._resize_from[0], 3)
+        self._raw_lut = _native.checked_raw_lut(raw_lut, pixel_format)       # one raw table for the whole group (LaneTracker's raw_lut)
         self._ctx = _native.Context(img_size, warped_size, cam_matrix, dist_coeffs, warp_matrices[0], device=device, capacity=4 * k)
         self._tick = 0
         self._overlay_sets = set()           # the calibration sets whose overlay a member has configured
@@ -131,6 +133,8 @@ class LaneTrackerGroup:
                 self._ctx.set_input_format(pixel_format, yuv_matrix)
             if self._resize_from is not None:
                 self._ctx.set_input_size(self._resize_from)
+            if self._raw_lut is not None:
+                self._ctx.set_raw_lut(self._raw_lut)
             # the calibration sets of the context: 0 is the group's own, one more for every distinct calibration among the streams
             sets = {_table_key(dict(cam_matrix=cam_matrix, dist_coeffs=dist_coeffs, warp_matrices=warp_matrices)): 0}
             self._cal_ids = []
@@ -144,7 +148,8 @@ class LaneTrackerGroup:
                 self.trackers.append(_GroupMember(self, cal_id, img_size, warped_size, c["cam_matrix"], c["dist_coeffs"], c["warp_matrices"],
                                                   c["mpp_conversion"], n_fail=n_fail, n_reset=n_reset, n_average=n_average,
                                                   print_frame_count=print_frame_count, device=device,
-                                                  pixel_format=pixel_format, yuv_matrix=yuv_matrix, input_size=input_size))
+                                                  pixel_format=pixel_format, yuv_matrix=yuv_matrix, input_size=input_size,
+                                                  raw_lut=self._raw_lut))
         except BaseException:
             self.close()
             raise
@@ -154,6 +159,22 @@ class LaneTrackerGroup:
 
     def __exit__(self, *exc):
         self.close()
+
+    @property
+    def raw_lut(self):
+        """The group's raw table, u8 (4, 256), or None (`set_raw_lut`)."""
+        return None if self._raw_lut is None else self._raw_lut.copy()
+
+    def set_raw_lut(self, lut):
+        """Another raw table for every stream of the group, or None for none, between `process()` calls (LaneTracker.set_raw_lut)."""
+        lut = _native.checked_raw_lut(lut, self.pixel_format)
+        if self.pixel_format not in _native.BAYER_FORMATS:
+            return
+        self._ctx.set_raw_lut(lut)
+        self._raw_lut = lut
+        for t in self.trackers:
+            t._raw_lut = lut
+            t._resident = None
 
     def calibration_count(self):
         """The calibration sets the group's context holds (1: every stream has the group's own calibration)."""

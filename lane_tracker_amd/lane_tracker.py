@@ -66,7 +66,7 @@ class LaneTracker(StreamPipeline):
 
     def __init__(self, img_size, warped_size, cam_matrix, dist_coeffs, warp_matrices, mpp_conversion,
                  n_fail=8, n_reset=4, n_average=2, print_frame_count=False, device=0, *, pixel_format='rgb', yuv_matrix='bt601',
-                 input_size=None):
+                 input_size=None, raw_lut=None):
         # the camera's pixel format: 'rgb' frames (H, W, 3), YUV 4:2:0 as decoders hand it out -- 'nv12' / 'i420' frames
         # (H * 3 // 2, W) -- or packed 4:2:2 as cameras and capture cards do -- 'yuy2' / 'uyvy' frames (H, W, 2) -- converted on the
         # device with `yuv_matrix` ('bt601', 'bt709') -- or what users' own software holds: 'bgr' frames (H, W, 3) (OpenCV's order),
@@ -84,6 +84,9 @@ class LaneTracker(StreamPipeline):
         self._resize_from = _native.checked_input_size(input_size, img_size, pixel_format)     # None: frames come in img_size
         if self._resize_from is not None:
             self._frame_shape = (self._resize_from[1], self._resize_from[0], 3)
+        # raw Bayer only: the raw table (utils.raw_lut: black level, white balance, tone curve), u8 (4, 256) -- every sample looked up on the
+        # device before the demosaic; configuration like the format's matrix, not state
+        self._raw_lut = _native.checked_raw_lut(raw_lut, pixel_format)
         self.img_size = img_size
         self.warped_size = warped_size
         self.cam_matrix = cam_matrix
@@ -155,10 +158,33 @@ class LaneTracker(StreamPipeline):
                 ctx.set_input_format(self.pixel_format, self.yuv_matrix)
             if self._resize_from is not None:
                 ctx.set_input_size(self._resize_from)
+            if self._raw_lut is not None:
+                ctx.set_raw_lut(self._raw_lut)
         except BaseException:
             ctx.close()
             raise
         return ctx
+
+    @property
+    def raw_lut(self):
+        """The raw table of a raw Bayer tracker, u8 (4, 256), or None (`set_raw_lut`)."""
+        return None if self._raw_lut is None else self._raw_lut.copy()
+
+    def set_raw_lut(self, lut):
+        """Another raw table -- `utils.raw_lut(...)`, u8 (4, 256) -- or None for none, between frames or windows (an auto-white-balance
+        step): the frames processed from now on are conditioned with it.  It waits for the device; not a per-frame call, and not allowed
+        inside an active `process_stream()`.  ValueError for a tracker whose pixel format is not raw Bayer, another shape or dtype."""
+        lut = _native.checked_raw_lut(lut, self.pixel_format)
+        if self.pixel_format not in _native.BAYER_FORMATS:      # (None on a tracker that takes no table: nothing to do, nothing to ask the device)
+            return
+        if self._in_stream:
+            raise RuntimeError("set_raw_lut() inside an active process_stream(): exhaust or close the generator first")
+        self._apply_raw_lut(lut)
+
+    def _apply_raw_lut(self, lut):
+        self._ctx.set_raw_lut(lut)
+        self._raw_lut = lut
+        self._resident = None       # the camera frame the slot holds was converted with the table before
 
     def _check_frame(self, img, window=False):
         """A 4:2:0 / 4:2:2 tracker takes frames of its own shape only (nothing is uploaded before this has been looked at); an RGB tracker

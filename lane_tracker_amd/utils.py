@@ -123,6 +123,75 @@ def bayer_to_rgb(frame, pattern='bayer_rggb'):
     return out
 
 
+_BAYER_PATTERNS = ('bayer_rggb', 'bayer_grbg', 'bayer_gbrg', 'bayer_bggr')     # pattern p: its red sites at (row, column) parity (p >> 1, p & 1)
+
+
+def checked_raw_lut(lut):
+    """A raw table as the C-contiguous u8 array (4, 256) the device takes; ValueError for any other shape or dtype (nothing is cast: a
+    float table is a mistake, not a table)."""
+    a = np.asarray(lut)
+    if a.dtype != np.uint8 or a.shape != (4, 256):
+        raise ValueError("a raw table is a uint8 array of shape (4, 256), got %s %r" % (a.dtype, a.shape))
+    return np.ascontiguousarray(a)
+
+
+def raw_lut(black_level=0, white_level=255, gains=(1, 1, 1), gamma=1.0):
+    """The raw table -- u8 (4, 256), one row per colour phase: 0 red sites, 1 green on red rows, 2 green on blue rows, 3 blue sites --
+    of the three steps every raw pipeline applies before demosaicing: black-level subtraction, per-colour gains (white balance) and
+    a tone curve.  For a sample s = 0 .. 255 of the colour with gain g, in float64:
+
+        v = clip((s - black_level) / (white_level - black_level), 0, 1)
+        v = clip(v * g, 0, 1)
+        v = v ** (1 / gamma)           gamma='srgb':  12.92 v  if v <= 0.0031308  else  1.055 v ** (1 / 2.4) - 0.055
+        out = floor(255 v + 0.5)
+
+    `gains` is (R, G, B) or (R, Gr, Gb, B); `gamma` a positive number or 'srgb'.  The defaults give the identity.  What
+    `LaneTracker(..., pixel_format='bayer_*', raw_lut=...)` looks every sample up in; `apply_raw_lut` is the same on the host."""
+    black, white = float(black_level), float(white_level)
+    if not white > black:
+        raise ValueError("white_level must be above black_level, got %r <= %r" % (white_level, black_level))
+    g = [float(v) for v in gains]
+    if len(g) == 3:
+        g = [g[0], g[1], g[1], g[2]]
+    if len(g) != 4:
+        raise ValueError("gains are (R, G, B) or (R, Gr, Gb, B), got %d values" % len(g))
+    if any(not v >= 0 for v in g):
+        raise ValueError("gains must not be negative, got %r" % (tuple(gains),))
+    if gamma != 'srgb' and (isinstance(gamma, str) or not float(gamma) > 0):
+        raise ValueError("gamma is a positive number or 'srgb', got %r" % (gamma,))
+    s = np.arange(256, dtype=np.float64)
+    v = np.clip((s - black) / (white - black), 0.0, 1.0)
+    out = np.empty((4, 256), np.uint8)
+    for p in range(4):
+        t = np.clip(v * g[p], 0.0, 1.0)
+        if gamma == 'srgb':
+            t = np.where(t <= 0.0031308, 12.92 * t, 1.055 * t ** (1.0 / 2.4) - 0.055)
+        else:
+            t = t ** (1.0 / float(gamma))
+        out[p] = np.floor(255.0 * t + 0.5).astype(np.uint8)
+    return out
+
+
+def apply_raw_lut(frames, pattern, lut):
+    """The conditioned mosaic of 8-bit raw Bayer frames -- (H, W) or a stack (n, H, W) -- with `pattern` ('bayer_rggb', ...):
+    out[y, x] = lut[phase(y, x)][frames[y, x]], phase = 2 * ((y ^ red_row) & 1) + ((x ^ red_col) & 1) with the pattern's red sites at
+    (row, column) parity (red_row, red_col).  NumPy only.  This is the definition: a Bayer tracker with `raw_lut=lut` fed `frames`
+    computes, bit for bit, what one without a table computes from `apply_raw_lut(frames, pattern, lut)`."""
+    if pattern not in _BAYER_PATTERNS:
+        raise ValueError("pattern must be one of %s, got %r" % (", ".join(repr(n) for n in _BAYER_PATTERNS), pattern))
+    lut = checked_raw_lut(lut)
+    a = np.asarray(frames)
+    if a.dtype != np.uint8 or a.ndim not in (2, 3):
+        raise ValueError("raw Bayer frames are uint8 arrays (H, W) or (n, H, W), got %s %r" % (a.dtype, a.shape))
+    p = _BAYER_PATTERNS.index(pattern)
+    out = np.empty_like(a)
+    for py in range(2):
+        for px in range(2):
+            row = lut[2 * (py ^ (p >> 1)) + (px ^ (p & 1))]
+            out[..., py::2, px::2] = row[a[..., py::2, px::2]]
+    return out
+
+
 def rgb_to_yuv(frame, layout='nv12', matrix='bt601'):
     """The counterpart of `yuv_to_rgb`: an RGB frame (H, W, 3), H and W even, to YUV 4:2:0 as OpenCV holds it -- a u8 array
     (H * 3 // 2, W): the Y plane, then interleaved U,V rows ('nv12') or the U plane and the V plane ('i420') -- on the device,

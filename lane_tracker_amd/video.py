@@ -357,6 +357,25 @@ def _parse_size(text):
     return int(w), int(h)
 
 
+def _parse_gains(text):
+    try:
+        g = tuple(float(v) for v in text.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError("gains are numbers R,G,B or R,Gr,Gb,B, got %r" % (text,)) from None
+    if len(g) not in (3, 4):
+        raise argparse.ArgumentTypeError("gains are R,G,B or R,Gr,Gb,B, got %d values" % len(g))
+    return g
+
+
+def _parse_gamma(text):
+    if text == "srgb":
+        return text
+    try:
+        return float(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError("gamma is a positive number or 'srgb', got %r" % (text,)) from None
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Lane tracking over a frame sequence (process_video.py without moviepy)")
     ap.add_argument("input", help="directory of images, .npy (n,H,W,3), raw .rgb / .bgr / .rgba / .bgra, raw 4:2:0 (.nv12, .i420 / .yuv) or raw packed 4:2:2 (.yuy2, .uyvy)")
@@ -372,6 +391,11 @@ def main(argv=None):
                     help="pixel format of the input frames (default: by the input's name); must match a raw input's extension; a raw "
                          ".bayer input needs it: bayer_rggb / bayer_grbg / bayer_gbrg / bayer_bggr, the sensor's pattern")
     ap.add_argument("--yuv-matrix", choices=("bt601", "bt709"), default="bt601", help="conversion matrix of 4:2:0 / 4:2:2 input")
+    ap.add_argument("--raw-black-level", type=float, default=None, metavar="N", help="raw Bayer input: the sensor's black pedestal, 0 .. 255 (default 0)")
+    ap.add_argument("--raw-white-level", type=float, default=None, metavar="N", help="raw Bayer input: the sample value of full scale (default 255)")
+    ap.add_argument("--raw-gains", type=_parse_gains, default=None, metavar="R,G,B[,..]",
+                    help="raw Bayer input: white-balance gains R,G,B or R,Gr,Gb,B (default 1,1,1)")
+    ap.add_argument("--raw-gamma", type=_parse_gamma, default=None, metavar="G|srgb", help="raw Bayer input: tone curve, v ** (1 / G) or the sRGB encoding (default 1)")
     ap.add_argument("--out-format", choices=("rgb", "nv12", "i420") + _RGB_FAMILY, default=None,
                     help="write the annotated frames through a device sink in this pixel format: a raw .rgb / .nv12 / .i420 file for "
                          "4:2:0 (converted on the device, --out-yuv-matrix), a raw .bgr / .rgba / .bgra file (permuted on the device, "
@@ -386,6 +410,17 @@ def main(argv=None):
     ap.add_argument("--visualize-search", metavar="DIR", default=None,
                     help="a second sink (directory, .npy or raw .rgb) for the search visualisations, bird's-eye size")
     a = ap.parse_args(argv)
+    raw = {k: v for k, v in (("black_level", a.raw_black_level), ("white_level", a.raw_white_level), ("gains", a.raw_gains),
+                             ("gamma", a.raw_gamma)) if v is not None}
+    if raw and a.pixel_format not in _BAYER:
+        ap.error("--raw-black-level / --raw-white-level / --raw-gains / --raw-gamma condition raw Bayer samples: they need --pixel-format bayer_*")
+    raw_table = None
+    if raw:
+        from .utils import raw_lut
+        try:
+            raw_table = raw_lut(**raw)
+        except ValueError as e:
+            ap.error(str(e))
     if a.split_view and a.output == "-":
         ap.error("--split-view shows the annotated frames: it needs an output")
     if a.split_view and a.visualize_search:
@@ -412,7 +447,7 @@ def main(argv=None):
     lt = LaneTracker(img_size=image_wh, warped_size=warped_wh, cam_matrix=cam_matrix, dist_coeffs=dist_coeffs,
                      warp_matrices=(M, Minv), mpp_conversion=(mppv, mpph), n_fail=8, n_reset=4, n_average=2,
                      print_frame_count=a.frame_count, device=a.device, pixel_format=src.pixel_format, yuv_matrix=a.yuv_matrix,
-                     input_size=a.input_size)
+                     input_size=a.input_size, raw_lut=raw_table)
     try:
         out_size = src.size if a.input_size is None else tuple(int(v) for v in image_wh)
         if a.split_view:                 # the annotated frame on top, the pane strip below it
