@@ -62,7 +62,9 @@ extern "C" {
  *    lt_last_overlay_launches (lane and text drawn on the way into device sinks, one launch whatever the slots' calibration sets);
  *    lt_set_input_size + lt_get_input_size + lt_get_input_rows (RGB camera frames of another size than the calibration's, resized on
  *    the device); lt_set_raw_lut + lt_get_raw_lut (black level, white balance and tone curve of raw Bayer input as one table per colour
- *    phase, looked up on the device inside the undistortion and the row conversion).  Nothing removed or changed. */
+ *    phase, looked up on the device inside the undistortion and the row conversion); lt_set_raw_lut_wide + lt_get_raw_lut_wide +
+ *    lt_raw16_to_rgb (10- and 12-bit raw Bayer, layouts 32 .. 35 and 48 .. 51: 16-bit words looked up in a table of 1 << bits entries per
+ *    colour phase on their way into the 8-bit demosaic).  Nothing removed or changed. */
 #define LT_ABI_VERSION 5
 
 typedef enum lt_status {
@@ -250,11 +252,32 @@ int  lt_set_streams(lt_ctx* ctx, int nstreams);
  * context.  With a table set the conditioned kernels run whatever the table holds, the identity included; with none, the plain ones.
  * LT_ERR_STATE in a context whose input format is not raw Bayer; lt_set_input_format with a layout that is not raw Bayer removes the table.
  * lt_get_raw_lut: *is_set := 0 / 1 and, where one is set, the table into `lut` (either may be NULL).  Slots, uploads and lt_bayer_to_rgb are
- * unaffected.  Not built: 10 / 12 / 16-bit or companded raw, other demosaics, a colour-correction matrix, lens-shading correction, a table
- * per slot. */
+ * unaffected.  Not built: 14 / 16-bit or companded raw (10 and 12 bits: below), other demosaics, a colour-correction matrix, lens-shading correction, a table
+ * per slot.
+ *
+ * 10- AND 12-BIT RAW BAYER, as most raw sensors deliver it (GMSL / FPD-Link cameras in raw mode, BayerRG10 / BayerRG12, V4L2 SRGGB10 /
+ * SRGGB12) -- LT_INPUT_BAYER10_RGGB .. _BGGR (32 .. 35) and LT_INPUT_BAYER12_RGGB .. _BGGR (48 .. 51), the pattern is layout & 3 in the
+ * order above: one plane of img_h rows of img_w little-endian 16-bit words, 2 * img_h * img_w bytes a frame, numpy uint16 (H, W); img_w and
+ * img_h even and at least 4.  A sample is the LOW `bits` (10 / 12) bits of its word; THE BITS ABOVE ARE IGNORED (masked off, never
+ * checked).  Such a context ALWAYS has a table, `lut` = uint8[4][1 << bits], phase-major as above, and
+ *     s'(y, x) = lut[phase(y, x)][F(y, x) & ((1 << bits) - 1)]
+ * is an 8-bit mosaic: everything such a context computes from frames F is bit for bit what an 8-bit raw Bayer context of the same pattern
+ * without a table computes from s'.  The mask is what keeps every index inside the table, which the kernels hold in LDS (4 KB / 16 KB a
+ * workgroup).  lt_set_input_format(ctx, 32 .. 35 | 48 .. 51, NULL) applies the size rules of 8-bit raw Bayer, sizes the staging frames and
+ * installs the DEFAULT table, lut[p][s] = floor(255 * s / ((1 << bits) - 1) + 0.5) (full scale to full scale, rounded; no black level, no
+ * gains, no curve).  lt_set_raw_lut_wide(ctx, lut, entries) sets another one -- `entries` must be 1 << bits of the context's layout
+ * (LT_ERR_INVALID), lut = NULL restores the default --, lt_get_raw_lut_wide reads the table in effect back; both return LT_ERR_STATE in a
+ * context whose layout is not one of these, as lt_set_raw_lut does in a context whose layout is.  Like lt_set_raw_lut the setter waits for
+ * everything the context has in flight and is a set-up or occasional call, NOT a per-frame one.  Uploads (all of them) and attached surfaces
+ * work as for 8-bit raw Bayer with two bytes a pixel: pitch >= 2 * img_w, and the plane's address and the pitch must be EVEN
+ * (LT_ERR_INVALID).  lt_raw16_to_rgb is the conversion alone, lt_bayer_to_rgb's twin: one host frame of h x w words, `lut` = 4 << bits bytes
+ * or NULL for the default.  Input formats only, as 8-bit raw Bayer is, with the same refusals.  Not built: MIPI-packed RAW10 / RAW12, 14 and
+ * 16 bits, MSB-aligned containers, a table per stream. */
 enum lt_input_layout { LT_INPUT_RGB = 0, LT_INPUT_NV12 = 1, LT_INPUT_I420 = 2, LT_INPUT_YUY2 = 3, LT_INPUT_UYVY = 4,
                        LT_INPUT_BGR = 5, LT_INPUT_RGBA = 6, LT_INPUT_BGRA = 7,
-                       LT_INPUT_BAYER_RGGB = 16, LT_INPUT_BAYER_GRBG = 17, LT_INPUT_BAYER_GBRG = 18, LT_INPUT_BAYER_BGGR = 19 };
+                       LT_INPUT_BAYER_RGGB = 16, LT_INPUT_BAYER_GRBG = 17, LT_INPUT_BAYER_GBRG = 18, LT_INPUT_BAYER_BGGR = 19,
+                       LT_INPUT_BAYER10_RGGB = 32, LT_INPUT_BAYER10_GRBG = 33, LT_INPUT_BAYER10_GBRG = 34, LT_INPUT_BAYER10_BGGR = 35,
+                       LT_INPUT_BAYER12_RGGB = 48, LT_INPUT_BAYER12_GRBG = 49, LT_INPUT_BAYER12_GBRG = 50, LT_INPUT_BAYER12_BGGR = 51 };
 #define LT_YUV_BT601 {1220542, 1673527, -852492, -409993, 2116026}   /* video range; OpenCV's constants */
 #define LT_YUV_BT709 {1220542, 1880097, -558891, -223347, 2214593}   /* video range */
 int  lt_set_input_format(lt_ctx* ctx, int layout, const int32_t coeffs[5]);
@@ -263,6 +286,9 @@ int  lt_yuv_to_rgb(lt_ctx* ctx, const uint8_t* frame, int h, int w, int layout, 
 int  lt_bayer_to_rgb(lt_ctx* ctx, const uint8_t* frame, int h, int w, int layout, uint8_t* out_rgb);
 int  lt_set_raw_lut(lt_ctx* ctx, const uint8_t* lut /* 1024 bytes, phase-major; NULL: none */);
 int  lt_get_raw_lut(lt_ctx* ctx, uint8_t* lut /* 1024 bytes */, int* is_set);
+int  lt_set_raw_lut_wide(lt_ctx* ctx, const uint8_t* lut /* 4 * entries bytes, phase-major; NULL: the default */, size_t entries);
+int  lt_get_raw_lut_wide(lt_ctx* ctx, uint8_t* lut /* 4 * entries bytes */, size_t entries);
+int  lt_raw16_to_rgb(lt_ctx* ctx, const uint16_t* frame, int h, int w, int layout, const uint8_t* lut /* 4 << bits bytes; NULL: the default */, uint8_t* out_rgb);
 /* Frames of another SIZE than the calibration's: a context with an input size of src_w x src_h takes RGB frames of src_h * src_w * 3
  * bytes and resizes them on the device to img_w x img_h -- cv2.resize(frame, (img_w, img_h)) with the default INTER_LINEAR, bit for bit:
  * half-pixel centres, 11-bit coefficients, OpenCV's two-stage rounding.  Everything the context computes, keeps and hands out is what a

@@ -236,6 +236,9 @@ _SIGNATURES = {
     "lt_bayer_to_rgb": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "lt_set_raw_lut": (C.c_int, [_P, _P]),
     "lt_get_raw_lut": (C.c_int, [_P, _P, C.POINTER(C.c_int)]),
+    "lt_set_raw_lut_wide": (C.c_int, [_P, _P, C.c_size_t]),
+    "lt_get_raw_lut_wide": (C.c_int, [_P, _P, C.c_size_t]),
+    "lt_raw16_to_rgb": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "lt_attach_device_frames": (C.c_int, [_P, _P, C.c_int, C.c_int]),
     "lt_device_frames_rest": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "lt_device_alloc": (C.c_int, [C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]),
@@ -270,6 +273,11 @@ RGB_FAMILY = {"bgr": 5, "rgba": 6, "bgra": 7}
 # ... and 8-bit raw Bayer, as a sensor delivers it before any image signal processor: one plane of (H, W) bytes, named by the
 # sensor's top-left 2 x 2 block; demosaiced (bilinear) on the device.  Camera frames only.  Again a table of its own.
 BAYER_FORMATS = {"bayer_rggb": 16, "bayer_grbg": 17, "bayer_gbrg": 18, "bayer_bggr": 19}
+# ... and 10- / 12-bit raw Bayer, as most raw sensors deliver it: one plane of (H, W) uint16 -- the sample in the low 10 / 12 bits of a
+# little-endian 16-bit word, the bits above ignored -- looked up in a table u8 (4, 2**bits) on the device (utils.raw_lut(bits=..)), then
+# the 8-bit demosaic.  The pattern is id & 3, in BAYER_FORMATS' order.  Camera frames only; once more a table of its own.
+BAYER_WIDE_FORMATS = {"bayer10_rggb": 32, "bayer10_grbg": 33, "bayer10_gbrg": 34, "bayer10_bggr": 35,
+                      "bayer12_rggb": 48, "bayer12_grbg": 49, "bayer12_gbrg": 50, "bayer12_bggr": 51}
 YUV_MATRICES = {"bt601": (1220542, 1673527, -852492, -409993, 2116026),
                 "bt709": (1220542, 1880097, -558891, -223347, 2214593)}
 
@@ -306,19 +314,44 @@ def rgb_to_surfaces(rgb_ptr, frame_stride, img_size, sink, matrix="bt601", devic
                                      s.ctypes.data, layout, None if k is None else k.ctypes.data))
 
 
+def raw_bits(pixel_format):
+    """The sample bits of a raw Bayer format: 8, 10 or 12; 0 for every other format."""
+    if pixel_format in BAYER_WIDE_FORMATS:
+        return 10 if BAYER_WIDE_FORMATS[pixel_format] < 48 else 12
+    return 8 if pixel_format in BAYER_FORMATS else 0
+
+
+def frame_dtype(pixel_format):
+    """The dtype of a camera frame in `pixel_format`: uint16 for 10- / 12-bit raw Bayer, uint8 for everything else."""
+    return np.dtype(np.uint16) if pixel_format in BAYER_WIDE_FORMATS else np.dtype(np.uint8)
+
+
+def frames_array(frames, pixel_format):
+    """`frames` as a C-contiguous array of the format's dtype.  Between uint8 and uint16 nothing is cast: uint8 frames handed to a 10- /
+    12-bit raw Bayer tracker, and uint16 frames handed to any other, are a ValueError."""
+    want = frame_dtype(pixel_format)
+    have = getattr(frames, "dtype", None)
+    if have is not None and have != want and (want == np.uint16 or have == np.uint16):
+        raise ValueError("pixel_format=%r takes %s camera frames, got %s" % (pixel_format, want, have))
+    return np.ascontiguousarray(frames, want)
+
+
 def pixel_format_id(pixel_format):
     try:
         if pixel_format in INPUT_FORMATS:
             return INPUT_FORMATS[pixel_format]
+        if pixel_format in BAYER_WIDE_FORMATS:
+            return BAYER_WIDE_FORMATS[pixel_format]
         return RGB_FAMILY[pixel_format] if pixel_format in RGB_FAMILY else BAYER_FORMATS[pixel_format]
     except (KeyError, TypeError):
         raise ValueError("pixel_format must be 'rgb', 'nv12', 'i420', 'yuy2', 'uyvy', 'bgr', 'rgba', 'bgra' or 'bayer_rggb' / '_grbg' / '_gbrg' / "
-                         "'_bggr', got %r" % (pixel_format,)) from None
+                         "'_bggr' (10 / 12 bits: 'bayer10_*' / 'bayer12_*'), got %r" % (pixel_format,)) from None
 
 
 def format_name(layout):
     """The name of an lt_input_layout value."""
-    return {v: n for n, v in list(INPUT_FORMATS.items()) + list(RGB_FAMILY.items()) + list(BAYER_FORMATS.items())}[int(layout)]
+    return {v: n for n, v in list(INPUT_FORMATS.items()) + list(RGB_FAMILY.items()) + list(BAYER_FORMATS.items()) +
+            list(BAYER_WIDE_FORMATS.items())}[int(layout)]
 
 
 def is_yuv(layout):
@@ -328,7 +361,7 @@ def is_yuv(layout):
 
 def sink_format_id(pixel_format):
     """pixel_format_id for a destination of annotated frames: packed 4:2:2 and raw Bayer are input formats only."""
-    if pixel_format in PACKED_422 or pixel_format in BAYER_FORMATS:
+    if pixel_format in PACKED_422 or pixel_format in BAYER_FORMATS or pixel_format in BAYER_WIDE_FORMATS:
         raise ValueError("%r is an input format only: annotated frames go into 'rgb', 'bgr', 'rgba', 'bgra', 'nv12' or 'i420' surfaces" % (pixel_format,))
     return pixel_format_id(pixel_format)
 
@@ -359,9 +392,20 @@ def checked_raw_lut(raw_lut, pixel_format):
     if raw_lut is None:
         return None
     from .utils import checked_raw_lut as _checked
+    if pixel_format in BAYER_WIDE_FORMATS:               # u8 (4, 2**bits)
+        return _checked(raw_lut, raw_bits(pixel_format))
     if pixel_format not in BAYER_FORMATS:
         raise ValueError("raw_lut conditions raw Bayer frames: pixel_format=%r takes none" % (pixel_format,))
     return _checked(raw_lut)
+
+
+def effective_raw_lut(raw_lut, pixel_format):
+    """checked_raw_lut, and for the 10- / 12-bit formats -- which always have a table -- the default `utils.raw_lut(bits=..)` for None."""
+    lut = checked_raw_lut(raw_lut, pixel_format)
+    if lut is None and pixel_format in BAYER_WIDE_FORMATS:
+        from .utils import raw_lut as _default
+        lut = _default(bits=raw_bits(pixel_format))
+    return lut
 
 
 def checked_input_size(input_size, img_size, pixel_format="rgb"):
@@ -393,7 +437,7 @@ def frame_shape(img_size, pixel_format="rgb"):
         if w < 1 or h < 1:
             raise ValueError("empty %r frames: %dx%d" % (pixel_format, w, h))
         return (h, w, 3 if pixel_format == "bgr" else 4)
-    if pixel_format in BAYER_FORMATS:
+    if pixel_format in BAYER_FORMATS or pixel_format in BAYER_WIDE_FORMATS:
         if w % 2 or h % 2 or w < 4 or h < 4:
             raise ValueError("raw Bayer frames need an even width and height of at least 4, got %dx%d" % (w, h))
         return (h, w)
@@ -889,8 +933,9 @@ class Context:
         return format_name(layout.value), tuple(int(v) for v in k)
 
     def _frames(self, frames):
-        """`frames` as the C-contiguous u8 block (n,) + one frame's shape; ValueError for frames of another shape."""
-        f = _u8(frames)
+        """`frames` as the C-contiguous block (n,) + one frame's shape -- u8; uint16 for 10- / 12-bit raw Bayer --; ValueError for frames
+        of another shape."""
+        f = frames_array(frames, self._pixel_format)
         tail = self._frame_tail
         if f.shape[-len(tail):] != tail or f.ndim > len(tail) + 1:
             if self._pixel_format == "rgb" and self._input_size is None:
@@ -921,19 +966,41 @@ class Context:
     def set_raw_lut(self, lut):
         """The raw table of a raw Bayer context -- u8 (4, 256), `utils.raw_lut` -- or None for none (lt_set_raw_lut): every sample is
         looked up in the row of its colour phase before the demosaic, in the undistortion and in the row conversion launched from now
-        on.  Waits for the context's outstanding work: a set-up or occasional call, not a per-frame one."""
+        on.  Waits for the context's outstanding work: a set-up or occasional call, not a per-frame one.  A 10- / 12-bit context:
+        u8 (4, 2**bits), None for the default `utils.raw_lut(bits=..)` (lt_set_raw_lut_wide)."""
         a = checked_raw_lut(lut, self._pixel_format)
+        if self._pixel_format in BAYER_WIDE_FORMATS:
+            _check(self.lib.lt_set_raw_lut_wide(self._h, None if a is None else a.ctypes.data, 1 << raw_bits(self._pixel_format)))
+            return
         _check(self.lib.lt_set_raw_lut(self._h, None if a is None else a.ctypes.data))
 
     def raw_lut(self):
-        """-> the raw table, u8 (4, 256), or None (lt_get_raw_lut)."""
+        """-> the raw table, u8 (4, 256), or None (lt_get_raw_lut); a 10- / 12-bit context: the table in effect, u8 (4, 2**bits)
+        (lt_get_raw_lut_wide)."""
+        if self._pixel_format in BAYER_WIDE_FORMATS:
+            n = 1 << raw_bits(self._pixel_format)
+            out = np.zeros((4, n), np.uint8)
+            _check(self.lib.lt_get_raw_lut_wide(self._h, out.ctypes.data, n))
+            return out
         out, is_set = np.zeros((4, 256), np.uint8), C.c_int(0)
         _check(self.lib.lt_get_raw_lut(self._h, out.ctypes.data, C.byref(is_set)))
         return out if is_set.value else None
 
-    def bayer_to_rgb(self, frame, pattern="bayer_rggb"):
+    def bayer_to_rgb(self, frame, pattern="bayer_rggb", raw_lut=None):
         """One 8-bit raw Bayer frame (H, W), H and W even and at least 4, -> RGB (H, W, 3): the bilinear demosaic, on the device
-        (lt_bayer_to_rgb)."""
+        (lt_bayer_to_rgb).  A 10- / 12-bit pattern: one uint16 frame, every sample looked up in `raw_lut` -- u8 (4, 2**bits), None: the
+        default -- first (lt_raw16_to_rgb)."""
+        if pattern in BAYER_WIDE_FORMATS:
+            a = frames_array(frame, pattern)
+            lut = checked_raw_lut(raw_lut, pattern)
+            if a.ndim != 2 or a.shape[0] % 2 or a.shape[1] % 2 or a.shape[0] < 4 or a.shape[1] < 4:
+                raise ValueError("a raw Bayer frame is a 2-D array of shape (H, W) with H and W even and at least 4, got %r" % (a.shape,))
+            out = np.empty((a.shape[0], a.shape[1], 3), np.uint8)
+            _check(self.lib.lt_raw16_to_rgb(self._h, a.ctypes.data, a.shape[0], a.shape[1], BAYER_WIDE_FORMATS[pattern],
+                                            None if lut is None else lut.ctypes.data, out.ctypes.data))
+            return out
+        if raw_lut is not None:
+            raise ValueError("bayer_to_rgb takes a raw_lut with the 10- and 12-bit patterns only (8-bit: utils.apply_raw_lut first)")
         a = _u8(frame)
         if pattern not in BAYER_FORMATS:
             raise ValueError("pattern must be one of %s, got %r" % (", ".join(repr(n) for n in BAYER_FORMATS), pattern))
@@ -989,8 +1056,8 @@ class Context:
         """Stream-ordered upload_frame_rows (no host wait).  `frames` must be a C-contiguous u8 array that stays alive
         and unchanged until the next sync() -- use pinned_empty() for it; returns the array handed to the library."""
         f = np.asarray(frames)
-        if f.dtype != np.uint8 or not f.flags["C_CONTIGUOUS"]:
-            raise ValueError("upload_frame_rows_async needs a C-contiguous uint8 array (no hidden copy may be made)")
+        if f.dtype != frame_dtype(self._pixel_format) or not f.flags["C_CONTIGUOUS"]:
+            raise ValueError("upload_frame_rows_async needs a C-contiguous %s array (no hidden copy may be made)" % frame_dtype(self._pixel_format))
         f = self._frames(f)
         _check(self.lib.lt_upload_frame_rows_async(self._h, f.ctypes.data, first, f.shape[0]))
         return f
@@ -1024,7 +1091,7 @@ class Context:
         _check(self.lib.lt_device_frames_rest(self._h, first, int(n), rows))
 
     def _frame_list(self, frames):
-        fs = [_u8(f) for f in frames]
+        fs = [frames_array(f, self._pixel_format) for f in frames]
         for f in fs:
             if f.shape != self._frame_tail:
                 raise ValueError("expected frames of shape %r, got %r" % (self._frame_tail, f.shape))
@@ -1259,7 +1326,7 @@ class Context:
         k = None
         if self.input_format()[0] in PACKED_422:
             raise ValueError("packed 4:2:2 is an input format only: nothing is drawn into such surfaces")
-        if self.input_format()[0] in BAYER_FORMATS:
+        if self.input_format()[0] in BAYER_FORMATS or self.input_format()[0] in BAYER_WIDE_FORMATS:
             raise ValueError("raw Bayer is an input format only: nothing is drawn into such surfaces")
         if self.input_format()[0] in RGB_FAMILY:
             raise ValueError("nothing is drawn into 'bgr' / 'rgba' / 'bgra' surfaces in place: such sinks are written by store_overlay_device")

@@ -2,7 +2,8 @@
 // to compute; no OpenCV was at hand to check that, DESIGN.md 6.y.3 states the definition) -- as plain inline functions without HIP
 // types: k_frontend.hip (the undistortion's taps, the row conversion) runs exactly these expressions on the device, and a host
 // translation unit (tests/bayer_arith_host.cpp) compiles the same header with the system compiler, so the CPU tests check what the
-// GPU runs.
+// GPU runs.  10- and 12-bit frames (16-bit words) reach this arithmetic through their raw table, which yields bytes: the last section
+// (tests/bayer_wide_host.cpp).
 //
 // A frame is one plane of H rows of W bytes, H and W even and at least 4.  The pixel at (y, x) carries the colour at position
 // 2 (y & 1) + (x & 1) of the pattern's name.  An interior pixel (1 <= y <= H - 2, 1 <= x <= W - 2) is demosaiced from its 3 x 3
@@ -97,6 +98,22 @@ BA_HD uint32_t condition4(uint32_t w, const uint8_t* rowa, const uint8_t* rowb) 
 }
 // one site
 BA_HD uint32_t condition1(uint32_t s, const uint8_t* row) { return row[s & 255u]; }
+
+// ---- wide raw tables (lt_set_raw_lut_wide) ------------------------------------------------------------------------------------------
+// 10- and 12-bit raw Bayer: a site is the low `bits` bits of a little-endian 16-bit word, the table uint8[4][1 << bits], phase-major, and
+// the conditioned mosaic s'(y, x) = lut[phase(pattern, y, x)][s(y, x) & ((1 << bits) - 1)] is 8-bit: everything else is the arithmetic
+// above on s'.  The bits of a word above `bits` are ignored: the mask is what keeps every index inside the table.
+
+// byte offset of the table row of the site with row parity par_y and column parity par_x
+BA_HD constexpr int lut_row_wide(int bits, int pattern, int par_y, int par_x) { return (1 << bits) * phase_of(pattern, par_y, par_x); }
+// The four consecutive sites of one row of the mosaic that the dwords lo (sites 0, 1) and hi (sites 2, 3) hold, conditioned into the
+// dword of four bytes that window_tap takes: rowa / rowb are the table rows of sites 0, 2 and of sites 1, 3, mask = (1 << bits) - 1.
+BA_HD uint32_t condition4w(uint32_t lo, uint32_t hi, const uint8_t* rowa, const uint8_t* rowb, uint32_t mask) {
+    return (uint32_t)rowa[lo & mask] | ((uint32_t)rowb[(lo >> 16) & mask] << 8) | ((uint32_t)rowa[hi & mask] << 16) |
+           ((uint32_t)rowb[(hi >> 16) & mask] << 24);
+}
+// one site (a 16-bit word, or anything that holds it in its low 16 bits)
+BA_HD uint32_t condition1w(uint32_t s, const uint8_t* row, uint32_t mask) { return row[s & mask]; }
 
 }  // namespace ba
 }  // namespace lt

@@ -14,6 +14,10 @@
 //   k_raw_walk_rows<PATTERN, SRC, PER_SLOT>, k_raw_rows_rgb<PATTERN, SURF, WIDE>  the two above for raw Bayer frames behind a raw table
 //                      (lt_set_raw_lut: black level, white balance and tone curve as one 256-entry table per colour phase, staged in
 //                      LDS): every byte looked up before it is demosaiced; launched in their place whenever a table is set
+//   k_raw16_walk_rows<PATTERN, SRC, PER_SLOT>, k_raw16_rows_rgb<PATTERN, SURF, WIDE>  the same two for 10- / 12-bit raw Bayer frames (layouts
+//                      32 .. 35, 48 .. 51: 16-bit little-endian words, the sample in the low `bits` bits, a run-time argument), always
+//                      behind their wide raw table (lt_set_raw_lut_wide: 1 << bits entries per colour phase, 4 KB / 16 KB of dynamic LDS):
+//                      every site masked and looked up into the 8-bit window that the 8-bit demosaic takes
 //   k_warp_split       cv2.warpPerspective      lane_tracker.py:834
 //                      + img[:,:,0]             lane_tracker.py:207
 //                      + cvtColor(RGB2LAB)[:,:,2] lane_tracker.py:208
@@ -321,6 +325,51 @@ template <int PATTERN> struct PlacesRows<Bayer8Lut<PATTERN>> : std::true_type {}
 template <class F> struct StagesTable : std::false_type {};
 template <int PATTERN> struct StagesTable<Bayer8Lut<PATTERN>> : std::true_type {};
 
+// 10- / 12-bit raw Bayer (16-bit little-endian words, the sample in the low `bits` bits) behind its wide raw table (lt_set_raw_lut_wide;
+// bayer_arith.h: s' = lut[phase][s & mask]): Bayer8's placement, the 4 x 4 window of sites being four 8-byte windows at byte column 2 bx,
+// each one aligned 96-bit load (window_at<uint64_t>, as RGB); every site looked up on its way into the four dwords that Bayer8 decodes.
+// The table, 4 << bits bytes (4 KB / 16 KB), lies in dynamic LDS, staged by the workgroup's 256 threads in 16-byte pieces before any of
+// them leaves the walk.  `bits` is a run-time value: the mask and the table's row stride are scalars.
+template <int PATTERN>
+struct Bayer16Lut : Bayer8<PATTERN> {
+    typedef Bayer8<PATTERN> Base;
+    typedef uint64_t Window;
+    static constexpr int DENSE_PAD = 16;    // a slot's staging frame: 16 bytes of padding behind the last slot (the third dword of the last window's aligned load)
+    struct Taps { uint64_t r0, r1, r2, r3; };               // the window's four rows, four 16-bit sites each
+    uint8_t* lut;                            // LDS, 4 << bits bytes
+    const uint4* table;                      // the context's table, device memory
+    int bits;
+    uint32_t mask;                           // (1 << bits) - 1
+    const uint8_t *ea, *eb, *oa, *ob;        // as Bayer8Lut's
+    __device__ __forceinline__ void stage() const {
+        for (int i = threadIdx.x; i < (1 << (bits - 2)); i += 256) reinterpret_cast<uint4*>(lut)[i] = table[i];
+        __syncthreads();
+    }
+    __device__ __forceinline__ void place_rows(int cy0, int cy1) {
+        Base::place_rows(cy0, cy1);
+        const int py = this->by & 1, px = this->bx & 1;
+        ea = lut + ba::lut_row_wide(bits, PATTERN, py, px), eb = lut + ba::lut_row_wide(bits, PATTERN, py, px ^ 1);
+        oa = lut + ba::lut_row_wide(bits, PATTERN, py ^ 1, px), ob = lut + ba::lut_row_wide(bits, PATTERN, py ^ 1, px ^ 1);
+    }
+    __device__ __forceinline__ static PlaneGeom plane(const FrontEndGeom& g, int) { return PlaneGeom{g.img_h, g.img_w * 2, 0u}; }
+    template <class Source>
+    __device__ __forceinline__ Taps fetch(const Source& src, const typename Source::Frame& f, const FrontEndGeom& g, int, int) const {
+        const auto p0 = src.plane(f, plane(g, 0), 0);
+        const int col = 2 * this->bx;
+        return Taps{src.template window<Window>(p0, this->by, col), src.template window<Window>(p0, this->by + 1, col),
+                    src.template window<Window>(p0, this->by + 2, col), src.template window<Window>(p0, this->by + 3, col)};
+    }
+    __device__ __forceinline__ uint32_t cond(uint64_t r, const uint8_t* a, const uint8_t* b) const {
+        return ba::condition4w((uint32_t)r, (uint32_t)(r >> 32), a, b, mask);
+    }
+    __device__ __forceinline__ void decode(const Taps& t, uint32_t& a0, uint32_t& a1, uint32_t& b0, uint32_t& b1) const {
+        const typename Base::Taps c{cond(t.r0, ea, eb), cond(t.r1, oa, ob), cond(t.r2, ea, eb), cond(t.r3, oa, ob)};
+        Base::decode(c, a0, a1, b0, b1);
+    }
+};
+template <int PATTERN> struct PlacesRows<Bayer16Lut<PATTERN>> : std::true_type {};
+template <int PATTERN> struct StagesTable<Bayer16Lut<PATTERN>> : std::true_type {};
+
 // The slots' own frames: `stride` bytes apart, planes dense.  One buffer resource covers the frames [z0, z1) of the walk (a frame
 // is selected by the scalar offset of the load) plus the format's padding behind them; beyond that the resource returns 0.
 // 32-bit offsets (a walk stays below 2^30 bytes: launch_undistort_rows) keep the address math on full-rate 24-bit multiplies.
@@ -523,6 +572,24 @@ __global__ __launch_bounds__(256) void k_raw_walk_rows(const SurfEntry* __restri
     const WalkArgs a{uxy, ufrac, SlotTables{sets, &ids}, g, und, und_px, first_slot, n, PER_SLOT ? 1 : fpb, remap};
     Bayer8Lut<PATTERN> fmt{};
     fmt.w = g.img_w, fmt.h = g.img_h, fmt.lut = s_lut, fmt.table = raw_lut;
+    if constexpr (SRC == SRC_SURFACES) undistort_walk<PER_SLOT>(a, SurfSource{tab}, fmt);
+    else undistort_walk<PER_SLOT>(a, SlotSource<true>{frames, stride}, fmt);
+}
+
+// The walk over 10- / 12-bit raw Bayer frames (layouts 32 .. 35, 48 .. 51), always behind their wide raw table (lt_set_raw_lut_wide):
+// k_raw_walk_rows' forms and parameters plus `bits`; the table's 4 << bits bytes are the launch's dynamic LDS.
+extern __shared__ __attribute__((aligned(16))) uint8_t s_lut_wide[];
+template <int PATTERN, int SRC, bool PER_SLOT>
+__global__ __launch_bounds__(256) void k_raw16_walk_rows(const SurfEntry* __restrict__ tab, const uint8_t* __restrict__ frames, size_t stride,
+                                                        const int16_t* __restrict__ uxy, const uint16_t* __restrict__ ufrac,
+                                                        const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
+                                                        uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb, int remap,
+                                                        const uint32_t* __restrict__ raw_lut, int bits) {
+    static_assert(SRC == SRC_SURFACES || SRC == SRC_SLOTS, "a raw Bayer staging frame is dword-aligned");
+    const WalkArgs a{uxy, ufrac, SlotTables{sets, &ids}, g, und, und_px, first_slot, n, PER_SLOT ? 1 : fpb, remap};
+    Bayer16Lut<PATTERN> fmt{};
+    fmt.w = g.img_w, fmt.h = g.img_h, fmt.lut = s_lut_wide, fmt.table = reinterpret_cast<const uint4*>(raw_lut);
+    fmt.bits = bits, fmt.mask = (1u << bits) - 1u;
     if constexpr (SRC == SRC_SURFACES) undistort_walk<PER_SLOT>(a, SurfSource{tab}, fmt);
     else undistort_walk<PER_SLOT>(a, SlotSource<true>{frames, stride}, fmt);
 }
@@ -810,6 +877,55 @@ struct RowsBayerLut {
         store_rgb1(dst + ((size_t)y * w + x) * 3, v);
     }
 };
+// RowsBayerLut for 10- / 12-bit frames (16-bit words, pitch in bytes and even, `lut`: the wide table in LDS, 1 << bits bytes a row): the
+// same two bodies over the conditioned mosaic.  wide: the 16 columns from x0 are 32 bytes, two 16-byte loads a row; any: 2-byte accesses.
+template <int P>
+struct RowsBayer16Lut {
+    __device__ __forceinline__ static Planes dense(const uint8_t* frame, int, int w) { return Planes{frame, nullptr, nullptr, 2 * w, 0}; }
+    __device__ __forceinline__ static const uint8_t* trow(const uint8_t* lut, int bits, int par_y, int par_x) { return lut + ba::lut_row_wide(bits, P, par_y, par_x); }
+    __device__ __forceinline__ static uint32_t site(const uint8_t* row, int x) { return reinterpret_cast<const uint16_t*>(row)[x]; }
+    __device__ __forceinline__ static void wide(const Planes& s, const uint8_t* lut, int bits, uint8_t* dst, int h, int w, int y, int x0) {
+        if (x0 >= w) return;
+        const uint32_t mask = (1u << bits) - 1u;
+        const int cy = ba::tap_pos(y, h), xl = max(x0 - 1, 0), xr = min(x0 + 16, w - 1);
+        uint32_t m[3][4], left[3], right[3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const uint8_t* row = s.y + (size_t)(cy - 1 + r) * s.pitch;
+            const int py = (cy - 1 + r) & 1;
+            const uint8_t *ta = trow(lut, bits, py, 0), *tb = trow(lut, bits, py, 1);     // (x0 is even: site 0 of every dword pair is an even column)
+            const uint4 q0 = *reinterpret_cast<const uint4*>(row + 2 * x0), q1 = *reinterpret_cast<const uint4*>(row + 2 * x0 + 16);
+            m[r][0] = ba::condition4w(q0.x, q0.y, ta, tb, mask); m[r][1] = ba::condition4w(q0.z, q0.w, ta, tb, mask);
+            m[r][2] = ba::condition4w(q1.x, q1.y, ta, tb, mask); m[r][3] = ba::condition4w(q1.z, q1.w, ta, tb, mask);
+            left[r] = ba::condition1w(site(row, xl), trow(lut, bits, py, xl & 1), mask);
+            right[r] = ba::condition1w(site(row, xr), trow(lut, bits, py, xr & 1), mask);
+        }
+        auto at = [&](int r, int j) { return j < 0 ? left[r] : j > 15 ? right[r] : (m[r][j >> 2] >> (8 * (j & 3))) & 255u; };
+        uint32_t px[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+            px[j] = ba::demosaic(at(1, j), at(1, j - 1) + at(1, j + 1), at(0, j) + at(2, j),
+                                 at(0, j - 1) + at(0, j + 1) + at(2, j - 1) + at(2, j + 1), ba::phase(P, cy, j));
+        if (x0 == 0) px[0] = px[1];
+        if (x0 + 16 == w) px[15] = px[14];
+        uint32_t d[12];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) pack_rgb4(px + 4 * j, d + 3 * j);
+        store_rgb16(dst + ((size_t)y * w + x0) * 3, d);
+    }
+    __device__ __forceinline__ static void any(const Planes& s, const uint8_t* lut, int bits, uint8_t* dst, int h, int w, int y, int x) {
+        if (x >= w) return;
+        const uint32_t mask = (1u << bits) - 1u;
+        const int cy = ba::tap_pos(y, h), cx = ba::tap_pos(x, w);
+        const uint8_t *up = s.y + (size_t)(cy - 1) * s.pitch, *mid = up + s.pitch, *dn = mid + s.pitch;
+        const int py = cy & 1, px = cx & 1;      // the site's parities; a neighbour one step away has the other one
+        auto u = [&](int i) { return ba::condition1w(site(up, cx + i), trow(lut, bits, py ^ 1, px ^ (i & 1)), mask); };
+        auto m = [&](int i) { return ba::condition1w(site(mid, cx + i), trow(lut, bits, py, px ^ (i & 1)), mask); };
+        auto d = [&](int i) { return ba::condition1w(site(dn, cx + i), trow(lut, bits, py ^ 1, px ^ (i & 1)), mask); };
+        const uint32_t v = ba::demosaic(m(0), m(-1) + m(1), u(0) + d(0), u(-1) + u(1) + d(-1) + d(1), ba::phase(P, cy, cx));
+        store_rgb1(dst + ((size_t)y * w + x) * 3, v);
+    }
+};
 // the description of a layout (none for 0, plain RGB: its rows are shown as they are)
 template <int L>
 using RowsOf = std::conditional_t<L <= 2, Rows420<L>, std::conditional_t<L <= 4, Rows422<L - 3>, std::conditional_t<L <= 7, RowsPx<L>, RowsBayer<L - 16>>>>;
@@ -859,6 +975,24 @@ __global__ __launch_bounds__(256) void k_raw_rows_rgb(std::conditional_t<SURF, S
     const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x), row = r0 + (int)blockIdx.y;
     if constexpr (WIDE) D::wide(p, s_lut, dst, h, w, row, i * 16);
     else D::any(p, s_lut, dst, h, w, row, i);
+}
+
+// The row conversion of 10- / 12-bit raw Bayer frames behind their wide raw table (lt_set_raw_lut_wide): k_raw_rows_rgb's two launch shapes,
+// the table (4 << bits bytes, dynamic LDS) staged in 16-byte pieces by the workgroup's 64 (wide) or 256 threads before any of them leaves.
+template <int PATTERN, bool SURF, bool WIDE>
+__global__ __launch_bounds__(256) void k_raw16_rows_rgb(std::conditional_t<SURF, SurfChunk, DenseFrames> src, uint8_t* __restrict__ rgb,
+                                                       size_t rgb_stride, int w, int r0, int h, const uint32_t* __restrict__ raw_lut, int bits) {
+    constexpr int THREADS = WIDE ? 64 : 256;
+    for (int i = threadIdx.x; i < (1 << (bits - 2)); i += THREADS) reinterpret_cast<uint4*>(s_lut_wide)[i] = reinterpret_cast<const uint4*>(raw_lut)[i];
+    __syncthreads();
+    typedef RowsBayer16Lut<PATTERN> D;
+    Planes p;
+    if constexpr (SURF) p = surf_planes(src.e[blockIdx.z]);
+    else p = D::dense(src.p + (size_t)blockIdx.z * src.stride, h, w);
+    uint8_t* dst = rgb + (size_t)blockIdx.z * rgb_stride;
+    const int i = (int)(blockIdx.x * THREADS + threadIdx.x), row = r0 + (int)blockIdx.y;
+    if constexpr (WIDE) D::wide(p, s_lut_wide, bits, dst, h, w, row, i * 16);
+    else D::any(p, s_lut_wide, bits, dst, h, w, row, i);
 }
 
 // Rows [r0, r1) of RGB surfaces -> the same rows of the slots' camera frames (row_bytes = 3 w, dense): a pitched row copy, one
@@ -1291,6 +1425,18 @@ static void with_layout(int layout, F&& f) {
     }
 }
 
+// pattern (0 .. 3) -> f(std::integral_constant<int, pattern>{}): the 10- / 12-bit raw Bayer layouts, which have kernels of their own and
+// never go through with_layout
+template <class F>
+static void with_pattern(int pattern, F&& f) {
+    switch (pattern & 3) {
+        case 0: return f(std::integral_constant<int, 0>{});
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+    }
+}
+
 // One launch of the walk over the n frames of `src`.  Plain RGB frames of the slots that are not dword-aligned, dword-strided and below
 // 2^30 bytes (a larger frame: 64-bit addresses) -- or all of them, any_byte -- take the form that fetches at any byte.
 template <bool PER_SLOT>
@@ -1299,6 +1445,14 @@ static void launch_walk(hipStream_t s, dim3 grid, FrameSource src, int layout, Y
                         bool any_byte, const uint32_t* raw_lut) {
     const bool aligned = !any_byte && ((uintptr_t)src.frames & 3) == 0 && (src.stride & 3) == 0 && src.stride < (1u << 30);
     const int remap = xcd_remap();
+    if (const int bits = raw_wide_bits(layout)) {        // 10- / 12-bit raw Bayer: always behind its table, 4 << bits bytes of LDS
+        with_pattern(layout, [&](auto p) {
+            constexpr int P = decltype(p)::value;
+            auto k_raw = src.tab ? k_raw16_walk_rows<P, SRC_SURFACES, PER_SLOT> : k_raw16_walk_rows<P, SRC_SLOTS, PER_SLOT>;
+            hipLaunchKernelGGL(k_raw, grid, dim3(256), (size_t)4 << bits, s, src.tab, src.frames, src.stride, uxy, ufrac, sets, ids, g, und, und_px, first_slot, n, fpb, remap, raw_lut, bits);
+        });
+        return;
+    }
     with_layout(layout, [&](auto l) {
         constexpr int L = decltype(l)::value;
         auto launch = [&](auto k_walk) {
@@ -1334,6 +1488,19 @@ void launch_undistort_rows(hipStream_t s, FrameSource src, int layout, YuvCoef k
 template <bool SURF, class Src>
 static void launch_rows_to_rgb(hipStream_t s, int layout, const Src& src, size_t bits, YuvCoef k, uint8_t* rgb, size_t rgb_stride, int h, int w,
                                int r0, int r1, int n, const uint32_t* raw_lut) {
+    if (const int depth = raw_wide_bits(layout)) {       // 10- / 12-bit raw Bayer: always behind its table, the same two launch shapes
+        with_pattern(layout, [&](auto p) {
+            constexpr int P = decltype(p)::value;
+            const unsigned rows = (unsigned)(r1 - r0);
+            if ((w & 15) == 0 && (bits & 15) == 0)
+                hipLaunchKernelGGL((k_raw16_rows_rgb<P, SURF, true>), dim3((unsigned)((w / 16 + 63) / 64), rows, (unsigned)n), dim3(64), (size_t)4 << depth, s,
+                                   src, rgb, rgb_stride, w, r0, h, raw_lut, depth);
+            else
+                hipLaunchKernelGGL((k_raw16_rows_rgb<P, SURF, false>), dim3((unsigned)((w + 255) / 256), rows, (unsigned)n), dim3(256), (size_t)4 << depth, s,
+                                   src, rgb, rgb_stride, w, r0, h, raw_lut, depth);
+        });
+        return;
+    }
     with_layout(layout, [&](auto l) {
         constexpr int L = decltype(l)::value;
         if constexpr (L != 0) {

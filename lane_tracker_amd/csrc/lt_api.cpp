@@ -716,6 +716,7 @@ void lt_destroy(lt_ctx* c) {
     dev_free(c->d_rs_xt);
     dev_free(c->d_rs_yt);
     dev_free(c->d_raw_lut);
+    dev_free(c->d_raw_lut_wide);
     dev_free(c->d_oxy);
     dev_free(c->d_ofrac);
     for (size_t i = 1; i < c->cal.size(); ++i) {     // (set 0's tables are the ones above)
@@ -857,7 +858,7 @@ int lt_set_streams(lt_ctx* c, int nstreams) {
 static inline bool is_422(int layout) { return layout == LT_INPUT_YUY2 || layout == LT_INPUT_UYVY; }
 static int check_yuv_format(int layout, const int32_t* k, int h, int w) {
     if (layout != LT_INPUT_NV12 && layout != LT_INPUT_I420 && !is_422(layout))
-        return fail(LT_ERR_INVALID, "input layout must be RGB (0), NV12 (1), I420 (2), YUY2 (3), UYVY (4), BGR (5), RGBA (6), BGRA (7) or raw Bayer (16 .. 19)");
+        return fail(LT_ERR_INVALID, "input layout must be RGB (0), NV12 (1), I420 (2), YUY2 (3), UYVY (4), BGR (5), RGBA (6), BGRA (7) or raw Bayer (16 .. 19; 10-bit 32 .. 35, 12-bit 48 .. 51)");
     if (!k) return fail(LT_ERR_INVALID, "a YUV layout needs its five conversion coefficients");
     if (is_422(layout)) {
         // (two macropixels a row at the least: the 8-byte window of a tap row lies inside its row)
@@ -882,14 +883,40 @@ static int check_bayer_size(int h, int w) {
 static void staged_run(const lt_ctx* c, int* r0, int* r1) {
     *r0 = c->cam_r0;
     *r1 = c->cam_r1;
-    if (is_bayer(c->in_layout) && c->cam_r1 > c->cam_r0) ba::input_run(c->cam_r0, c->cam_r1, c->calib.img_h, r0, r1);
+    if (is_raw_mosaic(c->in_layout) && c->cam_r1 > c->cam_r0) ba::input_run(c->cam_r0, c->cam_r1, c->calib.img_h, r0, r1);
+}
+
+// 10- / 12-bit raw Bayer.  The default table: full scale to full scale, rounded -- utils.raw_lut(bits=..) with its defaults, in integers
+// (floor(255 s / m + 1 / 2) = (510 s + m) / (2 m), m = 2^bits - 1).
+static void default_wide_table(int bits, uint8_t* lut) {
+    const uint32_t n = 1u << bits, m = n - 1u;
+    for (uint32_t p = 0; p < 4; ++p)
+        for (uint32_t v = 0; v < n; ++v) lut[p * n + v] = (uint8_t)((510u * v + m) / (2u * m));
+}
+static int write_wide_table(lt_ctx* c, const uint8_t* lut) {
+    HIP_TRY(hipMemcpy(c->d_raw_lut_wide, lut, c->raw_lut_wide.size(), hipMemcpyHostToDevice));
+    if (lut != c->raw_lut_wide.data()) std::memcpy(c->raw_lut_wide.data(), lut, c->raw_lut_wide.size());
+    return LT_OK;
+}
+// the table of a context that is about to take `layout`: allocated once at the layout's size, the default in it
+static int install_wide_table(lt_ctx* c, int layout) {
+    const size_t bytes = (size_t)4 << raw_bits(layout);
+    int rc;
+    if (c->raw_lut_wide.size() != bytes) {
+        dev_free(c->d_raw_lut_wide);
+        c->raw_lut_wide.clear();
+    }
+    if (!c->d_raw_lut_wide && (rc = dev_alloc(&c->d_raw_lut_wide, bytes / 4))) return rc;
+    c->raw_lut_wide.resize(bytes);
+    default_wide_table(raw_bits(layout), c->raw_lut_wide.data());
+    return write_wide_table(c, c->raw_lut_wide.data());
 }
 
 int lt_set_input_format(lt_ctx* c, int layout, const int32_t* coeffs) {
     if (!c) return fail(LT_ERR_INVALID, "null context");
     int rc;
-    const bool plain = layout == LT_INPUT_RGB || is_rgb_family(layout) || is_bayer(layout);      // no coefficients: `coeffs` is not read
-    if (is_bayer(layout)) {
+    const bool plain = layout == LT_INPUT_RGB || is_rgb_family(layout) || is_raw_mosaic(layout);      // no coefficients: `coeffs` is not read
+    if (is_raw_mosaic(layout)) {
         if ((rc = check_bayer_size(c->calib.img_h, c->calib.img_w))) return rc;
     } else if (is_rgb_family(layout)) {
         // (the 8-byte window of a tap row starts at column min(x, W - 2): two pixels a row at the least)
@@ -906,8 +933,9 @@ int lt_set_input_format(lt_ctx* c, int layout, const int32_t* coeffs) {
     if (layout == LT_INPUT_RGB) {
         dev_free(c->d_yuv);
     } else {
-        // the staging frame of a slot: h w 3 / 2 bytes (4:2:0), h w 2 (4:2:2), h w 3 (BGR), h w 4 (RGBA / BGRA) or h w (raw Bayer), slots a
-        // multiple of 16 apart
+        // the staging frame of a slot: h w 3 / 2 bytes (4:2:0), h w 2 (4:2:2), h w 3 (BGR), h w 4 (RGBA / BGRA), h w (raw Bayer) or 2 h w (10- /
+        // 12-bit raw Bayer), slots a multiple of 16 apart
+        if (is_bayer_wide(layout) && (rc = install_wide_table(c, layout))) return rc;     // (before anything of the context changes)
         const size_t bytes = packed_bpp(layout) ? c->frame_bytes / 3 * (size_t)packed_bpp(layout) : c->frame_bytes / 2, stride = (bytes + 15) & ~(size_t)15;
         if (stride != c->yuv_stride) dev_free(c->d_yuv);
         c->yuv_bytes = bytes;
@@ -927,6 +955,7 @@ int lt_set_input_format(lt_ctx* c, int layout, const int32_t* coeffs) {
 // that a re-run (lt_mask_rerun) computes them again.
 int lt_set_raw_lut(lt_ctx* c, const uint8_t* lut) {
     if (!c) return fail(LT_ERR_INVALID, "null context");
+    if (is_bayer_wide(c->in_layout)) return fail(LT_ERR_STATE, "a 10- / 12-bit raw Bayer context takes its table through lt_set_raw_lut_wide");
     if (!is_bayer(c->in_layout)) return fail(LT_ERR_STATE, "a raw table conditions raw Bayer input: this context's input format is another layout");
     int rc;
     if ((rc = set_device(c))) return rc;
@@ -945,6 +974,35 @@ int lt_get_raw_lut(lt_ctx* c, uint8_t* lut, int* is_set) {
     if (!c) return fail(LT_ERR_INVALID, "null context");
     if (is_set) *is_set = c->raw_lut_set ? 1 : 0;
     if (lut && c->raw_lut_set) std::memcpy(lut, c->raw_lut, sizeof c->raw_lut);
+    return LT_OK;
+}
+
+static int check_wide(lt_ctx* c, size_t entries) {
+    if (!c) return fail(LT_ERR_INVALID, "null context");
+    if (!is_bayer_wide(c->in_layout)) return fail(LT_ERR_STATE, "a wide raw table belongs to 10- / 12-bit raw Bayer input: this context's input format is another layout");
+    if (entries != (size_t)1 << raw_bits(c->in_layout))
+        return fail(LT_ERR_INVALID, "a %d-bit raw table has %d entries per colour phase, got %zu", raw_bits(c->in_layout), 1 << raw_bits(c->in_layout), entries);
+    return LT_OK;
+}
+// As lt_set_raw_lut: behind everything in flight, and the slots' front ends are marked as not run.
+int lt_set_raw_lut_wide(lt_ctx* c, const uint8_t* lut, size_t entries) {
+    int rc = check_wide(c, entries);
+    if (rc) return rc;
+    if ((rc = set_device(c))) return rc;
+    if ((rc = sync_all(c))) return rc;
+    if (lut) rc = write_wide_table(c, lut);
+    else {
+        default_wide_table(raw_bits(c->in_layout), c->raw_lut_wide.data());
+        rc = write_wide_table(c, c->raw_lut_wide.data());
+    }
+    std::fill(c->front_ok.begin(), c->front_ok.end(), (uint8_t)0);
+    return rc;
+}
+
+int lt_get_raw_lut_wide(lt_ctx* c, uint8_t* lut, size_t entries) {
+    int rc = check_wide(c, entries);
+    if (rc) return rc;
+    if (lut) std::memcpy(lut, c->raw_lut_wide.data(), c->raw_lut_wide.size());
     return LT_OK;
 }
 
@@ -1417,7 +1475,7 @@ int lt_upload_frame_rest_rows(lt_ctx* c, const uint8_t* frames, int first, int n
         const int c0 = chroma_lo(lo), c1 = chroma_hi(lo, hi);
         for (int k = 0; k < 4; k += 2) {
             int ra = rows4[k], re = rows4[k + 1];
-            if (is_bayer(c->in_layout) && re > ra) ba::support_run(ra, re, H, &ra, &re);     // the rows the demosaic of the run reads
+            if (is_raw_mosaic(c->in_layout) && re > ra) ba::support_run(ra, re, H, &ra, &re);     // the rows the demosaic of the run reads
             const int a = ra, b = std::min(re, lo), d = std::max(ra, hi), e = re;
             if (b > a && (rc = yuv_copy(c, frames, first, n, a, b, chroma_lo(a), std::min(chroma_hi(a, b), c0), c->copy))) return rc;
             if (e > d && (rc = yuv_copy(c, frames, first, n, d, e, std::max(chroma_lo(d), c1), chroma_hi(d, e), c->copy))) return rc;
@@ -1569,6 +1627,8 @@ int check_surfaces(lt_ctx* c, const lt_device_surface* s, int n, SurfEntry* out)
         const lt_device_surface& f = s[k];
         if (f.pitch < row) return fail(LT_ERR_INVALID, "surface %d: pitch %d is below the row's %d bytes", k, (int)f.pitch, row);
         if (f.pitch > PITCH_MAX) return fail(LT_ERR_INVALID, "surface %d: pitch %d is too large", k, (int)f.pitch);
+        if (is_bayer_wide(layout) && (((uintptr_t)f.plane[0] | (uintptr_t)f.pitch) & 1))      // 16-bit words: read as such by the row conversion
+            return fail(LT_ERR_INVALID, "surface %d: a plane of 16-bit samples needs an even address and an even pitch, got %p and %d", k, f.plane[0], (int)f.pitch);
         const size_t ext = (size_t)f.pitch * (size_t)(H - 1) + (size_t)row;
         if (ext >= ((size_t)1 << 31) - 8) return fail(LT_ERR_INVALID, "surface %d: a plane of %zu bytes is too large", k, ext);
         int rc = check_plane(c->device, f.plane[0], ext, k, 0, memo);
@@ -2733,6 +2793,43 @@ int lt_bayer_to_rgb(lt_ctx* c, const uint8_t* frame, int h, int w, int layout, u
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     dev_free(d_in);
     dev_free(d_out);
+    if (e != hipSuccess) return fail(LT_ERR_HIP, "raw Bayer conversion failed: %s", hipGetErrorString(e));
+    return LT_OK;
+}
+
+// one 10- / 12-bit raw Bayer host frame (h w 16-bit words) -> RGB, on the device: every sample looked up in `lut` (null: the default table),
+// then the bilinear demosaic -- lt_bayer_to_rgb's twin
+int lt_raw16_to_rgb(lt_ctx* c, const uint16_t* frame, int h, int w, int layout, const uint8_t* lut, uint8_t* out_rgb) {
+    if (!c || !frame || !out_rgb) return fail(LT_ERR_INVALID, "null argument");
+    if (!is_bayer_wide(layout)) return fail(LT_ERR_INVALID, "lt_raw16_to_rgb takes the 10- and 12-bit raw Bayer layouts (32 .. 35, 48 .. 51)");
+    int rc = check_bayer_size(h, w);
+    if (rc) return rc;
+    if (h > 16384 || w > 16384) return fail(LT_ERR_INVALID, "bad image size (at most 16384 x 16384)");
+    if ((rc = set_device(c))) return rc;
+    const size_t px = (size_t)h * w, lut_bytes = (size_t)4 << raw_bits(layout);
+    std::vector<uint8_t> def;
+    if (!lut) {
+        def.resize(lut_bytes);
+        default_wide_table(raw_bits(layout), def.data());
+        lut = def.data();
+    }
+    uint8_t *d_in = nullptr, *d_out = nullptr;
+    uint32_t* d_lut = nullptr;
+    if ((rc = dev_alloc(&d_in, px * 2)) || (rc = dev_alloc(&d_out, px * 3)) || (rc = dev_alloc(&d_lut, lut_bytes / 4))) {
+        dev_free(d_in); dev_free(d_out); dev_free(d_lut);
+        return rc;
+    }
+    hipError_t e = hipMemcpyAsync(d_in, frame, px * 2, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_lut, lut, lut_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        launch_yuv_rows_to_rgb(c->stream, layout, d_in, px * 2, YuvCoef{}, d_out, px * 3, h, w, 0, h, 1, d_lut);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out_rgb, d_out, px * 3, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);     // (`def` and the caller's table have been read by then)
+    dev_free(d_in);
+    dev_free(d_out);
+    dev_free(d_lut);
     if (e != hipSuccess) return fail(LT_ERR_HIP, "raw Bayer conversion failed: %s", hipGetErrorString(e));
     return LT_OK;
 }

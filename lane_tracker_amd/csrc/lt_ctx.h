@@ -152,7 +152,7 @@ struct lt_ctx {
     size_t frame_bytes = 0, und_bytes = 0, bev_bytes = 0;
     uint8_t *d_frames = nullptr, *d_bev = nullptr;
     // Input that is not RGB (lt_set_input_format): the caller's layout, the five conversion coefficients (YUV), and per slot a staging frame
-    // of yuv_bytes = h * w * 3 / 2 (4:2:0), h * w * 2 (packed 4:2:2), h * w * 3 (BGR), h * w * 4 (RGBA / BGRA) or h * w (raw Bayer) bytes in that layout, yuv_stride (a multiple of 16) apart, 16 bytes of padding behind the last
+    // of yuv_bytes = h * w * 3 / 2 (4:2:0), h * w * 2 (packed 4:2:2), h * w * 3 (BGR), h * w * 4 (RGBA / BGRA), h * w (raw Bayer) or 2 * h * w (10- / 12-bit raw Bayer) bytes in that layout, yuv_stride (a multiple of 16) apart, 16 bytes of padding behind the last
     // one (k_undistort_rows reads aligned 8-byte windows).  The undistortion reads the staging frame; the RGB camera frame
     // of a slot is written by k_rows_to_rgb behind the uploads that would have brought RGB rows for whoever shows the frame.
     int in_layout = 0;                        // LT_INPUT_RGB
@@ -166,6 +166,10 @@ struct lt_ctx {
     bool raw_lut_set = false;
     uint8_t raw_lut[1024] = {0};
     uint32_t* d_raw_lut = nullptr;
+    // The table of a 10- / 12-bit raw Bayer context (lt_set_raw_lut_wide): uint8[4][1 << bits], always one (the default until another is set);
+    // the host copy sized by the layout, the device copy allocated once at that size when the layout is set.
+    std::vector<uint8_t> raw_lut_wide;
+    uint32_t* d_raw_lut_wide = nullptr;
     // Input frames of another size (lt_set_input_size): src_w x src_h RGB frames, resized on the device to the calibration's size
     // (cv2.resize, INTER_LINEAR).  Per slot a staging frame of src_bytes = src_h * src_w * 3 bytes, src_stride apart (a multiple of 16
     // with at least 16 bytes of padding behind every frame: k_resize_rows reads aligned dwords); the uploads copy source rows into it
@@ -356,11 +360,16 @@ inline uint8_t* slot_frame(const lt_ctx* c, int s) { return c->d_frames + (size_
 inline bool is_rgb_family(int layout) { return layout == LT_INPUT_BGR || layout == LT_INPUT_RGBA || layout == LT_INPUT_BGRA; }
 // 8-bit raw Bayer (RGGB, GRBG, GBRG, BGGR): one plane of one byte a pixel, an input format only
 inline bool is_bayer(int layout) { return layout >= LT_INPUT_BAYER_RGGB && layout <= LT_INPUT_BAYER_BGGR; }
-// the raw table the front end and the row conversion of `c` are launched with: null without one
-inline const uint32_t* raw_lut_of(const lt_ctx* c) { return c->raw_lut_set ? c->d_raw_lut : nullptr; }
+// 10- / 12-bit raw Bayer (layouts 32 .. 35, 48 .. 51): one plane of one 16-bit word a pixel, always behind a table; its sample bits
+inline int raw_bits(int layout) { return raw_wide_bits(layout); }
+inline bool is_bayer_wide(int layout) { return raw_bits(layout) != 0; }
+// any raw mosaic, whatever its samples: what is about the mosaic (sizes, row runs, input only) and not about bytes
+inline bool is_raw_mosaic(int layout) { return is_bayer(layout) || is_bayer_wide(layout); }
+// the raw table the front end and the row conversion of `c` are launched with: null without one (a wide context always has one)
+inline const uint32_t* raw_lut_of(const lt_ctx* c) { return is_bayer_wide(c->in_layout) ? c->d_raw_lut_wide : c->raw_lut_set ? c->d_raw_lut : nullptr; }
 inline int packed_bpp(int layout) {
     return layout == LT_INPUT_RGB || layout == LT_INPUT_BGR ? 3 : layout == LT_INPUT_RGBA || layout == LT_INPUT_BGRA ? 4
-           : layout == LT_INPUT_YUY2 || layout == LT_INPUT_UYVY ? 2 : is_bayer(layout) ? 1 : 0;
+           : layout == LT_INPUT_YUY2 || layout == LT_INPUT_UYVY || is_bayer_wide(layout) ? 2 : is_bayer(layout) ? 1 : 0;
 }
 inline uint8_t* slot_yuv(const lt_ctx* c, int s) { return c->d_yuv + (size_t)s * c->yuv_stride; }
 inline uint8_t* slot_src(const lt_ctx* c, int s) { return c->d_src + (size_t)s * c->src_stride; }

@@ -89,9 +89,12 @@ struct FrameSource {
     static FrameSource slots(const uint8_t* frames, size_t stride) { return FrameSource{nullptr, frames, stride}; }
     static FrameSource surfaces(const SurfEntry* tab) { return FrameSource{tab, nullptr, 0}; }
 };
+// The 10- / 12-bit raw Bayer layouts (32 .. 35, 48 .. 51; pattern = layout & 3): the bits of a sample, 0 for every other layout.  Their frames
+// are one plane of 16-bit little-endian words and they are always launched with a table, uint8[4][1 << bits] (lt_set_raw_lut_wide).
+inline int raw_wide_bits(int layout) { return layout >= 32 && layout <= 35 ? 10 : layout >= 48 && layout <= 51 ? 12 : 0; }
 // raw_lut (here and below; raw Bayer layouts only): the context's raw table in device memory (lt_set_raw_lut: uint8[4][256], phase-major, as
 // 256 dwords), or null: none.  With one, the conditioned kernels are launched (k_raw_walk_rows, k_raw_rows_rgb) in place of the plain ones.
-// the undistorted rows of n frames (layout 0 = RGB, 1 = NV12, 2 = I420, 3 = YUY2, 4 = UYVY, 5 = BGR, 6 = RGBA, 7 = BGRA, 16 .. 19 = raw Bayer RGGB / GRBG / GBRG / BGGR; `k` is read for the YUV layouts only: every tap converted, then the
+// the undistorted rows of n frames (layout 0 = RGB, 1 = NV12, 2 = I420, 3 = YUY2, 4 = UYVY, 5 = BGR, 6 = RGBA, 7 = BGRA, 16 .. 19 = raw Bayer RGGB / GRBG / GBRG / BGGR, 32 .. 35 / 48 .. 51 = the same at 10 / 12 bits, which need raw_lut (k_raw16_walk_rows); `k` is read for the YUV layouts only: every tap converted, then the
 // same blend); `und` is the base of the whole buffer, `first_slot` the absolute slot of frame 0 of the call (k_undistort_rows<layout, source, false>)
 void launch_undistort_rows(hipStream_t s, FrameSource src, int layout, YuvCoef k, const int16_t* uxy, const uint16_t* ufrac,
                            FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n, const uint32_t* raw_lut = nullptr);

@@ -849,7 +849,7 @@ static int inplace_impl(lt_ctx* c, int first, int n, const LaneInput& in, double
         return fail(LT_ERR_STATE, "lt_overlay_run_inplace: packed 4:2:2 (YUY2 / UYVY) is an input format only, nothing is drawn into such surfaces");
     if (is_rgb_family(c->in_layout))
         return fail(LT_ERR_STATE, "lt_overlay_run_inplace: nothing is drawn into BGR / RGBA / BGRA surfaces in place (lt_overlay_store_device writes such sinks)");
-    if (is_bayer(c->in_layout))
+    if (is_raw_mosaic(c->in_layout))
         return fail(LT_ERR_STATE, "lt_overlay_run_inplace: raw Bayer is an input format only, nothing is drawn into such surfaces");
     for (int i = first; i < first + n; ++i)
         if (i >= (int)c->attached.size() || !c->attached[(size_t)i])

@@ -12,7 +12,7 @@ refuses what its runtime does not know.  No framework is imported here.
 import numpy as np
 
 from . import _native
-from ._native import BAYER_FORMATS, SURFACE_DTYPE, frame_shape, pixel_format_id
+from ._native import BAYER_FORMATS, BAYER_WIDE_FORMATS, SURFACE_DTYPE, frame_dtype, frame_shape, pixel_format_id
 
 __all__ = ["DeviceBuffer", "DeviceFrames", "pack_host_frames", "feed_rows_list", "feed_rest_list"]
 
@@ -88,12 +88,23 @@ def _plane_rows(img_size, pixel_format):
 
 
 _PIXEL_BYTES = {0: 3, 3: 2, 4: 2, 5: 3, 6: 4, 7: 4, 16: 1, 17: 1, 18: 1, 19: 1}       # bytes a pixel of the layouts that are one plane of whole pixels
+_PIXEL_BYTES.update({v: 2 for v in BAYER_WIDE_FORMATS.values()})                       # (10- / 12-bit raw Bayer: one 16-bit word)
+_RAW_LAYOUTS = frozenset(BAYER_FORMATS.values()) | frozenset(BAYER_WIDE_FORMATS.values())
+
+
+def _check_word_planes(pixel_format, planes, pitches):
+    """10- / 12-bit raw Bayer: a plane of 16-bit words lies at an even address and has an even pitch (the library checks the same)."""
+    if pixel_format in BAYER_WIDE_FORMATS:
+        if any(int(p) % 2 for p in np.asarray(pitches).reshape(-1)):
+            raise ValueError("a plane of 16-bit samples needs an even pitch, got %r" % (np.asarray(pitches).reshape(-1).tolist(),))
+        if any(int(p) % 2 for p in np.asarray(planes).reshape(-1)):
+            raise ValueError("a plane of 16-bit samples needs an even address")
 
 
 def _frame_dims(layout):
     """-> (dimensions of one frame's array, its last axis or 0): RGB / BGR (H, W, 3), RGBA / BGRA (H, W, 4), packed 4:2:2 (H, W, 2),
     4:2:0 (H * 3 // 2, W); raw Bayer (H, W): no last axis, 1 stands for it."""
-    if _PIXEL_BYTES.get(layout) == 1:
+    if layout in _RAW_LAYOUTS:
         return 2, 1
     return (3, _PIXEL_BYTES[layout]) if layout in _PIXEL_BYTES else (2, 0)
 
@@ -144,9 +155,10 @@ def pack_host_frames(frames, pixel_format="rgb", pitch=None, chroma_pitch=None, 
     the first at `offset`; bytes between and around the rows are `fill`.  The block ends with the last byte of the last plane.
     -> (the block as a u8 array, surfaces with plane OFFSETS into it, img_size, whether `frames` was one frame)."""
     f = np.asarray(frames)
-    if f.dtype != np.uint8:
-        raise ValueError("camera frames are uint8, got %s" % f.dtype)
     layout = pixel_format_id(pixel_format)
+    if f.dtype != frame_dtype(pixel_format):
+        raise ValueError("%s, got %s" % ("camera frames are uint8" if f.dtype != np.uint16 and frame_dtype(pixel_format) == np.uint8
+                                         else "%r camera frames are %s" % (pixel_format, frame_dtype(pixel_format)), f.dtype))
     nd, last = _frame_dims(layout)
     if f.ndim not in (nd, nd + 1) or (last > 1 and f.shape[-1] != last):
         raise ValueError("expected camera frames of shape %s, got %r" % (_SHAPE_NAMES[last], f.shape))
@@ -160,8 +172,9 @@ def pack_host_frames(frames, pixel_format="rgb", pitch=None, chroma_pitch=None, 
         h, w = f.shape[1] // 3 * 2, f.shape[2]
     n = f.shape[0]
     total, surf, sizes = _layout_block(n, (w, h), pixel_format, pitch, chroma_pitch, offset)
+    _check_word_planes(pixel_format, surf["plane"][:, 0], surf["pitch"])
     block = np.full(total, fill, np.uint8)
-    flat = f.reshape(n, -1)
+    flat = np.ascontiguousarray(f).view(np.uint8).reshape(n, -1)          # (16-bit samples: their bytes as they lie, little-endian)
     for k in range(n):
         src = 0
         for i, (r, b, p) in enumerate(sizes):
@@ -210,6 +223,7 @@ class DeviceFrames:
                 raise ValueError("chroma pitch %d is below the row's %d bytes" % (cp.min(), chroma[1]))
         if n and max(p.max(), cp.max()) >= 1 << 23:
             raise ValueError("pitches must stay below 2**23")
+        _check_word_planes(pixel_format, rows_, p)
         surf["pitch"], surf["chroma_pitch"] = p, cp
         return cls(surf, img_size, pixel_format, owner=owner, single=single, stream=stream, device=device)
 
@@ -225,7 +239,10 @@ class DeviceFrames:
             raise ValueError("the object has no __cuda_array_interface__")
         if int(ai.get("version", 0)) < 2:
             raise ValueError("__cuda_array_interface__ version %r is not supported (2 or later)" % (ai.get("version"),))
-        if ai.get("typestr") != "|u1":
+        word = pixel_format in BAYER_WIDE_FORMATS          # 10- / 12-bit raw Bayer: '<u2', strides (frame, pitch, 2)
+        if word and ai.get("typestr") != "<u2":
+            raise ValueError("%r camera frames are little-endian uint16 ('<u2'), got typestr %r" % (pixel_format, ai.get("typestr"),))
+        if not word and ai.get("typestr") != "|u1":
             raise ValueError("camera frames are uint8 ('|u1'), got typestr %r" % (ai.get("typestr"),))
         if ai.get("mask") is not None:
             raise ValueError("masked arrays are not supported")
@@ -238,7 +255,7 @@ class DeviceFrames:
             raise ValueError("empty camera frames: shape %r" % (shape,))
         strides = ai.get("strides")
         if strides is None:
-            strides, acc = [], 1
+            strides, acc = [], 2 if word else 1
             for v in reversed(shape):
                 strides.insert(0, acc)
                 acc *= v
@@ -264,7 +281,9 @@ class DeviceFrames:
             pitch = strides[-3]
         elif last == 1:
             h, w = shape[-2], shape[-1]
-            if strides[-1] != 1:
+            if word and strides[-1] != 2:
+                raise ValueError("a %r plane holds one 16-bit word per pixel: a pixel stride of 2, got %d" % (pixel_format, strides[-1]))
+            if not word and strides[-1] != 1:
                 raise ValueError("a raw Bayer plane holds one byte per pixel: a pixel stride of 1, got %d" % strides[-1])
             pitch = strides[-2]
         else:
@@ -283,6 +302,7 @@ class DeviceFrames:
             raise ValueError("pitches must stay below 2**23")
         surf = np.zeros(n, SURFACE_DTYPE)
         base = ptr + np.arange(n, dtype=np.uint64) * np.uint64(fstride)
+        _check_word_planes(pixel_format, base, pitch)
         surf["plane"][:, 0] = base
         surf["pitch"] = pitch
         if layout == 1:
@@ -311,7 +331,7 @@ class DeviceFrames:
         out=)` and `utils.rgb_to_yuv` write into and `to_host()` reads back.  `fill`: a byte value the whole block is set to first
         (None: whatever the memory held)."""
         n = int(n)
-        if pixel_format in BAYER_FORMATS:
+        if pixel_format in BAYER_FORMATS or pixel_format in BAYER_WIDE_FORMATS:
             raise ValueError("%r is an input format only: annotated frames go into 'rgb', 'bgr', 'rgba', 'bgra', 'nv12' or 'i420' surfaces" % (pixel_format,))
         if n < 0:
             raise ValueError("a sink holds zero or more frames, got %d" % n)
@@ -368,7 +388,7 @@ class DeviceFrames:
         import ctypes as C
         lib = _native.load()
         tail = frame_shape(self.img_size, self.pixel_format)
-        out = np.empty((len(self), int(np.prod(tail))), np.uint8)
+        out = np.empty((len(self), int(np.prod(tail)) * frame_dtype(self.pixel_format).itemsize), np.uint8)
         for k, s in enumerate(self.surfaces):
             at = 0
             for i, (rows, rb, which) in enumerate(self._plane_sizes()):
@@ -377,7 +397,7 @@ class DeviceFrames:
                 _native._check(lib.lt_device_read(raw.ctypes.data, C.c_void_p(int(s["plane"][i])), raw.nbytes))
                 out[k, at:at + rows * rb] = np.lib.stride_tricks.as_strided(raw, shape=(rows, rb), strides=(pitch, 1)).reshape(-1)
                 at += rows * rb
-        out = out.reshape((len(self),) + tail)
+        out = out.view(frame_dtype(self.pixel_format)).reshape((len(self),) + tail)
         return out[0] if self.single else out
 
     def wait_for_producer(self):

@@ -124,7 +124,7 @@ class LaneTrackerGroup:
         self._resize_from = _native.checked_input_size(input_size, img_size, pixel_format)
         if self._resize_from is not None:
             self._frame_shape = (self._resize_from[1], self._resize_from[0], 3)
-        self._raw_lut = _native.checked_raw_lut(raw_lut, pixel_format)       # one raw table for the whole group (LaneTracker's raw_lut)
+        self._raw_lut = _native.effective_raw_lut(raw_lut, pixel_format)       # one raw table for the whole group (LaneTracker's raw_lut)
         self._ctx = _native.Context(img_size, warped_size, cam_matrix, dist_coeffs, warp_matrices[0], device=device, capacity=4 * k)
         self._tick = 0
         self._overlay_sets = set()           # the calibration sets whose overlay a member has configured
@@ -167,8 +167,8 @@ class LaneTrackerGroup:
 
     def set_raw_lut(self, lut):
         """Another raw table for every stream of the group, or None for none, between `process()` calls (LaneTracker.set_raw_lut)."""
-        lut = _native.checked_raw_lut(lut, self.pixel_format)
-        if self.pixel_format not in _native.BAYER_FORMATS:
+        lut = _native.effective_raw_lut(lut, self.pixel_format)
+        if not _native.raw_bits(self.pixel_format):
             return
         self._ctx.set_raw_lut(lut)
         self._raw_lut = lut
@@ -267,7 +267,7 @@ class LaneTrackerGroup:
         if not active:
             return outs
         shape = self._frame_shape
-        imgs = [frames[i] if isinstance(frames[i], DeviceFrames) else np.ascontiguousarray(frames[i], np.uint8) for i in active]
+        imgs = [frames[i] if isinstance(frames[i], DeviceFrames) else _native.frames_array(frames[i], self.pixel_format) for i in active]
         for img in imgs:
             if isinstance(img, DeviceFrames) and self._resize_from is not None:
                 raise ValueError("a group with input_size takes host frames only: frames in device memory are not resized")

@@ -86,7 +86,7 @@ class LaneTracker(StreamPipeline):
             self._frame_shape = (self._resize_from[1], self._resize_from[0], 3)
         # raw Bayer only: the raw table (utils.raw_lut: black level, white balance, tone curve), u8 (4, 256) -- every sample looked up on the
         # device before the demosaic; configuration like the format's matrix, not state
-        self._raw_lut = _native.checked_raw_lut(raw_lut, pixel_format)
+        self._raw_lut = _native.effective_raw_lut(raw_lut, pixel_format)   # (10 / 12 bits: u8 (4, 2**bits), always one -- None is the default)
         self.img_size = img_size
         self.warped_size = warped_size
         self.cam_matrix = cam_matrix
@@ -167,15 +167,15 @@ class LaneTracker(StreamPipeline):
 
     @property
     def raw_lut(self):
-        """The raw table of a raw Bayer tracker, u8 (4, 256), or None (`set_raw_lut`)."""
+        """The raw table of a raw Bayer tracker, u8 (4, 256), or None (`set_raw_lut`); 10- / 12-bit: the table in effect, u8 (4, 2**bits)."""
         return None if self._raw_lut is None else self._raw_lut.copy()
 
     def set_raw_lut(self, lut):
         """Another raw table -- `utils.raw_lut(...)`, u8 (4, 256) -- or None for none, between frames or windows (an auto-white-balance
         step): the frames processed from now on are conditioned with it.  It waits for the device; not a per-frame call, and not allowed
         inside an active `process_stream()`.  ValueError for a tracker whose pixel format is not raw Bayer, another shape or dtype."""
-        lut = _native.checked_raw_lut(lut, self.pixel_format)
-        if self.pixel_format not in _native.BAYER_FORMATS:      # (None on a tracker that takes no table: nothing to do, nothing to ask the device)
+        lut = _native.effective_raw_lut(lut, self.pixel_format)      # (10 / 12 bits: None restores the default table)
+        if not _native.raw_bits(self.pixel_format):      # (None on a tracker that takes no table: nothing to do, nothing to ask the device)
             return
         if self._in_stream:
             raise RuntimeError("set_raw_lut() inside an active process_stream(): exhaust or close the generator first")
@@ -202,6 +202,9 @@ class LaneTracker(StreamPipeline):
             if not window and len(img) != 1:
                 raise ValueError("process() takes one frame, got DeviceFrames of %d" % len(img))
             return
+        dtype, want_dtype = getattr(img, "dtype", None), _native.frame_dtype(self.pixel_format)
+        if dtype is not None and dtype != want_dtype and np.uint16 in (dtype, want_dtype):      # (nothing is cast between 8 and 16 bits)
+            raise ValueError("a %r tracker takes %s frames, got %s" % (self.pixel_format, want_dtype, dtype))
         if self.pixel_format == 'rgb':
             return
         shape = getattr(img, "shape", None)

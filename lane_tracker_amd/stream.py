@@ -620,7 +620,7 @@ class StreamPipeline:
                 raise ValueError("annotate='inplace' draws into RGB frames on the host: DeviceFrames have none there")
             self._check_frame(frames, window=True)
             return frames[0:1] if frames.single else frames
-        frames = np.ascontiguousarray(frames, np.uint8)
+        frames = _native.frames_array(frames, self.pixel_format)
         if self.pixel_format != 'rgb':
             if self._annotate_inplace:
                 raise ValueError("annotate='inplace' draws into RGB frames: a %r tracker has none on the host" % (self.pixel_format,))
@@ -646,7 +646,7 @@ class StreamPipeline:
             raise ValueError("out='inplace' draws into the frames handed in: a tracker with input_size returns frames of img_size")
         if self.pixel_format in _native.PACKED_422:
             raise ValueError("out='inplace' draws into RGB, NV12 or I420 surfaces: %r is an input format only" % (self.pixel_format,))
-        if self.pixel_format in _native.BAYER_FORMATS:
+        if _native.raw_bits(self.pixel_format):
             raise ValueError("out='inplace' draws into RGB, NV12 or I420 surfaces: %r is an input format only" % (self.pixel_format,))
         if self.pixel_format in _native.RGB_FAMILY:
             raise ValueError("out='inplace' draws into RGB, NV12 or I420 surfaces: %r frames go into an out= sink" % (self.pixel_format,))

@@ -101,44 +101,55 @@ def yuv_to_rgb(frame, layout='nv12', matrix='bt601'):
     return _context_for_module_functions().yuv_to_rgb(frame, layout, matrix)
 
 
-def bayer_to_rgb(frame, pattern='bayer_rggb'):
+def bayer_to_rgb(frame, pattern='bayer_rggb', raw_lut=None):
     """An 8-bit raw Bayer frame -- a u8 array (H, W), H and W even and at least 4, the sensor's mosaic with `pattern` ('bayer_rggb',
     'bayer_grbg', 'bayer_gbrg', 'bayer_bggr': its top-left 2 x 2 block) -- or a stack (n, H, W) of them, to RGB (H, W, 3) /
     (n, H, W, 3), on the device: the bilinear demosaic in integers, border pixels taking their interior neighbours' values.  This is
     what `cv2.cvtColor(frame, cv2.COLOR_BayerRGGB2RGB)` (GRBG / GBRG / BGGR) is understood to compute, which was not checked against
-    OpenCV.  What a `LaneTracker(..., pixel_format=pattern)` sees of the frame."""
+    OpenCV.  What a `LaneTracker(..., pixel_format=pattern)` sees of the frame.
+
+    The 10- and 12-bit patterns ('bayer10_rggb', ..., 'bayer12_bggr') take uint16 frames -- the sample in the low 10 / 12 bits of each
+    word, the bits above ignored -- and look every sample up in `raw_lut`, u8 (4, 2**bits), first (None: the default
+    `raw_lut(bits=...)`): the demosaic of `apply_raw_lut(frame, pattern, raw_lut)`.  `raw_lut` goes with these patterns only."""
     from . import _native
     from .lane_tracker import _context_for_module_functions
-    if pattern not in _native.BAYER_FORMATS:
-        raise ValueError("pattern must be one of %s, got %r" % (", ".join(repr(n) for n in _native.BAYER_FORMATS), pattern))
-    a = np.ascontiguousarray(frame, np.uint8)
+    wide = pattern in _native.BAYER_WIDE_FORMATS
+    if pattern not in _native.BAYER_FORMATS and not wide:
+        raise ValueError("pattern must be one of %s, got %r" % (", ".join(repr(n) for n in list(_native.BAYER_FORMATS) + list(_native.BAYER_WIDE_FORMATS)), pattern))
+    if raw_lut is not None and not wide:
+        raise ValueError("bayer_to_rgb takes a raw_lut with the 10- and 12-bit patterns only (8-bit: apply_raw_lut first)")
+    raw_lut = _native.checked_raw_lut(raw_lut, pattern)
+    a = _native.frames_array(frame, pattern)
+    convert = (lambda ctx, f: ctx.bayer_to_rgb(f, pattern, raw_lut)) if wide else (lambda ctx, f: ctx.bayer_to_rgb(f, pattern))
     if a.ndim == 2:
-        return _context_for_module_functions().bayer_to_rgb(a, pattern)
+        return convert(_context_for_module_functions(), a)
     if a.ndim != 3:
         raise ValueError("a raw Bayer frame is an array (H, W), a stack of them (n, H, W); got %r" % (a.shape,))
     ctx = _context_for_module_functions()
     out = np.empty(a.shape + (3,), np.uint8)
     for k in range(a.shape[0]):
-        out[k] = ctx.bayer_to_rgb(a[k], pattern)
+        out[k] = convert(ctx, a[k])
     return out
 
 
 _BAYER_PATTERNS = ('bayer_rggb', 'bayer_grbg', 'bayer_gbrg', 'bayer_bggr')     # pattern p: its red sites at (row, column) parity (p >> 1, p & 1)
+# the 10- and 12-bit forms: name -> (pattern p, bits)
+_BAYER_WIDE_PATTERNS = {'bayer%d_%s' % (b, n[6:]): (p, b) for b in (10, 12) for p, n in enumerate(_BAYER_PATTERNS)}
 
 
-def checked_raw_lut(lut):
-    """A raw table as the C-contiguous u8 array (4, 256) the device takes; ValueError for any other shape or dtype (nothing is cast: a
-    float table is a mistake, not a table)."""
+def checked_raw_lut(lut, bits=8):
+    """A raw table as the C-contiguous u8 array (4, 256) -- (4, 2**bits) for 10- / 12-bit samples -- the device takes; ValueError for any
+    other shape or dtype (nothing is cast: a float table is a mistake, not a table)."""
     a = np.asarray(lut)
-    if a.dtype != np.uint8 or a.shape != (4, 256):
-        raise ValueError("a raw table is a uint8 array of shape (4, 256), got %s %r" % (a.dtype, a.shape))
+    if a.dtype != np.uint8 or a.shape != (4, 1 << bits):
+        raise ValueError("a raw table is a uint8 array of shape (4, %d), got %s %r" % (1 << bits, a.dtype, a.shape))
     return np.ascontiguousarray(a)
 
 
-def raw_lut(black_level=0, white_level=255, gains=(1, 1, 1), gamma=1.0):
-    """The raw table -- u8 (4, 256), one row per colour phase: 0 red sites, 1 green on red rows, 2 green on blue rows, 3 blue sites --
+def raw_lut(black_level=0, white_level=None, gains=(1, 1, 1), gamma=1.0, bits=8):
+    """The raw table -- u8 (4, 2**bits), bits = 8 (the default), 10 or 12: (4, 256) for 8-bit samples --, one row per colour phase: 0 red sites, 1 green on red rows, 2 green on blue rows, 3 blue sites --
     of the three steps every raw pipeline applies before demosaicing: black-level subtraction, per-colour gains (white balance) and
-    a tone curve.  For a sample s = 0 .. 255 of the colour with gain g, in float64:
+    a tone curve.  For a sample s = 0 .. 2**bits - 1 of the colour with gain g, in float64 (white_level: 2**bits - 1 unless given):
 
         v = clip((s - black_level) / (white_level - black_level), 0, 1)
         v = clip(v * g, 0, 1)
@@ -147,9 +158,12 @@ def raw_lut(black_level=0, white_level=255, gains=(1, 1, 1), gamma=1.0):
 
     `gains` is (R, G, B) or (R, Gr, Gb, B); `gamma` a positive number or 'srgb'.  The defaults give the identity.  What
     `LaneTracker(..., pixel_format='bayer_*', raw_lut=...)` looks every sample up in; `apply_raw_lut` is the same on the host."""
-    black, white = float(black_level), float(white_level)
+    if bits not in (8, 10, 12):
+        raise ValueError("bits is 8, 10 or 12, got %r" % (bits,))
+    n = 1 << bits
+    black, white = float(black_level), float(n - 1 if white_level is None else white_level)
     if not white > black:
-        raise ValueError("white_level must be above black_level, got %r <= %r" % (white_level, black_level))
+        raise ValueError("white_level must be above black_level, got %r <= %r" % (n - 1 if white_level is None else white_level, black_level))
     g = [float(v) for v in gains]
     if len(g) == 3:
         g = [g[0], g[1], g[1], g[2]]
@@ -159,9 +173,9 @@ def raw_lut(black_level=0, white_level=255, gains=(1, 1, 1), gamma=1.0):
         raise ValueError("gains must not be negative, got %r" % (tuple(gains),))
     if gamma != 'srgb' and (isinstance(gamma, str) or not float(gamma) > 0):
         raise ValueError("gamma is a positive number or 'srgb', got %r" % (gamma,))
-    s = np.arange(256, dtype=np.float64)
+    s = np.arange(n, dtype=np.float64)
     v = np.clip((s - black) / (white - black), 0.0, 1.0)
-    out = np.empty((4, 256), np.uint8)
+    out = np.empty((4, n), np.uint8)
     for p in range(4):
         t = np.clip(v * g[p], 0.0, 1.0)
         if gamma == 'srgb':
@@ -176,19 +190,27 @@ def apply_raw_lut(frames, pattern, lut):
     """The conditioned mosaic of 8-bit raw Bayer frames -- (H, W) or a stack (n, H, W) -- with `pattern` ('bayer_rggb', ...):
     out[y, x] = lut[phase(y, x)][frames[y, x]], phase = 2 * ((y ^ red_row) & 1) + ((x ^ red_col) & 1) with the pattern's red sites at
     (row, column) parity (red_row, red_col).  NumPy only.  This is the definition: a Bayer tracker with `raw_lut=lut` fed `frames`
-    computes, bit for bit, what one without a table computes from `apply_raw_lut(frames, pattern, lut)`."""
-    if pattern not in _BAYER_PATTERNS:
-        raise ValueError("pattern must be one of %s, got %r" % (", ".join(repr(n) for n in _BAYER_PATTERNS), pattern))
-    lut = checked_raw_lut(lut)
+    computes, bit for bit, what one without a table computes from `apply_raw_lut(frames, pattern, lut)`.
+
+    The 10- and 12-bit patterns ('bayer10_rggb', ..., 'bayer12_bggr'): uint16 frames, a table u8 (4, 2**bits), and
+    out[y, x] = lut[phase(y, x)][frames[y, x] & (2**bits - 1)], a uint8 mosaic -- the bits of a word above `bits` are ignored.  A tracker in
+    'bayerNN_P' with table `lut` computes what the 8-bit 'bayer_P' tracker without a table computes from this."""
+    if pattern in _BAYER_WIDE_PATTERNS:
+        p, bits = _BAYER_WIDE_PATTERNS[pattern]
+        dtype = np.uint16
+    elif pattern in _BAYER_PATTERNS:
+        p, bits, dtype = _BAYER_PATTERNS.index(pattern), 8, np.uint8
+    else:
+        raise ValueError("pattern must be one of %s, got %r" % (", ".join(repr(n) for n in _BAYER_PATTERNS + tuple(_BAYER_WIDE_PATTERNS)), pattern))
+    lut = checked_raw_lut(lut, bits)
     a = np.asarray(frames)
-    if a.dtype != np.uint8 or a.ndim not in (2, 3):
-        raise ValueError("raw Bayer frames are uint8 arrays (H, W) or (n, H, W), got %s %r" % (a.dtype, a.shape))
-    p = _BAYER_PATTERNS.index(pattern)
-    out = np.empty_like(a)
+    if a.dtype != dtype or a.ndim not in (2, 3):
+        raise ValueError("%s frames are %s arrays (H, W) or (n, H, W), got %s %r" % (pattern, np.dtype(dtype), a.dtype, a.shape))
+    out = np.empty(a.shape, np.uint8)
     for py in range(2):
         for px in range(2):
             row = lut[2 * (py ^ (p >> 1)) + (px ^ (p & 1))]
-            out[..., py::2, px::2] = row[a[..., py::2, px::2]]
+            out[..., py::2, px::2] = row[a[..., py::2, px::2] & ((1 << bits) - 1)]
     return out
 
 

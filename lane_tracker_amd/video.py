@@ -58,10 +58,20 @@ def _yuv_layout(path):
 _RGB_FAMILY = ("bgr", "rgba", "bgra")
 # 8-bit raw Bayer: headerless `.bayer` files; the suffix cannot name the pattern, the caller does (FrameSource's pixel_format)
 _BAYER = ("bayer_rggb", "bayer_grbg", "bayer_gbrg", "bayer_bggr")
+# 10- / 12-bit raw Bayer: headerless `.bayer16` files of little-endian uint16, the sample in the low bits; the caller names depth and pattern
+_BAYER_WIDE = tuple("bayer%d_%s" % (b, n[6:]) for b in (10, 12) for n in _BAYER)
 
 
 def _is_bayer_file(path):
     return str(path).lower().endswith(".bayer")
+
+
+def _is_bayer16_file(path):
+    return str(path).lower().endswith(".bayer16")
+
+
+def _raw_format_bits(pixel_format):
+    return 8 if pixel_format in _BAYER else int(pixel_format[5:7])
 
 
 def _yuv_tail(pixel_format, width, height):
@@ -70,7 +80,7 @@ def _yuv_tail(pixel_format, width, height):
         if width < 2 or height < 1:
             raise ValueError(f"{pixel_format} frames need a width of at least 2, got {width}x{height}")
         return (height, width, 3 if pixel_format == "bgr" else 4), pixel_format.upper()
-    if pixel_format in _BAYER:
+    if pixel_format in _BAYER or pixel_format in _BAYER_WIDE:
         if width % 2 or height % 2 or width < 4 or height < 4:
             raise ValueError(f"raw Bayer frames need an even width and height of at least 4, got {width}x{height}")
         return (height, width), "raw Bayer"
@@ -112,6 +122,9 @@ class FrameSource:
         self.path = str(path)
         if pixel_format in _BAYER and not _is_bayer_file(self.path):
             raise ValueError(f"pixel_format={pixel_format!r} names the pattern of a raw .bayer file; {self.path!r} is none")
+        if pixel_format in _BAYER_WIDE and not _is_bayer16_file(self.path):
+            raise ValueError(f"pixel_format={pixel_format!r} names depth and pattern of a raw .bayer16 file; {self.path!r} is none")
+        self._dtype = np.dtype(np.uint8)
         self._files = None
         self._array = None
         self._tail = None                # shape of one frame
@@ -155,6 +168,23 @@ class FrameSource:
             self._n = nbytes // fb
             self._array = np.memmap(self.path, np.uint8, "r", shape=(self._n,) + self._tail) if self._n \
                 else np.zeros((0,) + self._tail, np.uint8)
+        elif _is_bayer16_file(self.path):
+            if pixel_format not in _BAYER_WIDE:
+                raise ValueError(f"{self.path}: a .bayer16 file holds 10- or 12-bit raw Bayer frames in 16-bit words and its suffix names neither "
+                                 "depth nor pattern: say which with --pixel-format bayer10_rggb ... bayer12_bggr (FrameSource's pixel_format=)")
+            if size is None:
+                raise ValueError("raw Bayer input needs size=(width, height)")
+            self.pixel_format = pixel_format
+            self._dtype = np.dtype("<u2")
+            self.width, self.height = int(size[0]), int(size[1])
+            self._tail, family = _yuv_tail(self.pixel_format, self.width, self.height)
+            fb = int(np.prod(self._tail)) * 2
+            nbytes = os.path.getsize(self.path)
+            if nbytes % fb:
+                raise ValueError(f"{self.path}: {nbytes} bytes is not a whole number of {self.width}x{self.height} 16-bit {family} frames")
+            self._n = nbytes // fb
+            self._array = np.memmap(self.path, self._dtype, "r", shape=(self._n,) + self._tail) if self._n \
+                else np.zeros((0,) + self._tail, np.uint16)
         elif _yuv_layout(self.path):
             if size is None:
                 raise ValueError("raw 4:2:0 input needs size=(width, height)" if _yuv_layout(self.path) in ("nv12", "i420")
@@ -171,21 +201,21 @@ class FrameSource:
             self._array = np.memmap(self.path, np.uint8, "r", shape=(self._n,) + self._tail) if self._n \
                 else np.zeros((0,) + self._tail, np.uint8)
         else:
-            raise ValueError(f"unsupported frame source {self.path!r} (directory of images, .npy, .rgb/.raw, .bgr, .rgba, .bgra, .nv12, .i420/.yuv, .yuy2, .uyvy, .bayer)")
+            raise ValueError(f"unsupported frame source {self.path!r} (directory of images, .npy, .rgb/.raw, .bgr, .rgba, .bgra, .nv12, .i420/.yuv, .yuy2, .uyvy, .bayer, .bayer16)")
         if self._tail is None:
             self._tail = (self.height, self.width, 3)
         if size is not None and (self.width, self.height) != (int(size[0]), int(size[1])):
             raise ValueError(f"frames are {self.width}x{self.height}, expected {size[0]}x{size[1]}")
 
     @staticmethod
-    def _buffer(shape):
+    def _buffer(shape, dtype=np.uint8):
         """Frames are read straight into page-locked memory when the library is there: the tracker's uploads then run
         at the PCIe rate instead of the pageable-copy rate."""
         try:
             from ._native import pinned_empty
-            return pinned_empty(shape)
+            return pinned_empty(shape, dtype)
         except Exception:
-            return np.empty(shape, np.uint8)
+            return np.empty(shape, dtype)
 
     @staticmethod
     def _read_image(path):
@@ -203,7 +233,8 @@ class FrameSource:
     def read(self, start, stop):
         """Frames [start, stop) as one contiguous array (n, H, W, 3) -- 4:2:0: (n, H * 3 // 2, W); 4:2:2: (n, H, W, 2)."""
         start, stop = max(0, start), min(self._n, stop)
-        out = self._buffer((max(stop - start, 0),) + self._tail)
+        out = self._buffer((max(stop - start, 0),) + self._tail) if self._dtype == np.uint8 else \
+            self._buffer((max(stop - start, 0),) + self._tail, np.uint16)
         if self._files is None:
             out[...] = self._array[start:stop]
             return out
@@ -387,12 +418,13 @@ def main(argv=None):
                     help="WxH of the input frames when that is not the calibration's size: raw RGB input is read in this size and the "
                          "tracker resizes the frames on the device (cv2.resize, INTER_LINEAR); what is written has the calibration's size")
     ap.add_argument("--window", type=int, default=64, help="frames per GPU batch")
-    ap.add_argument("--pixel-format", choices=("rgb", "nv12", "i420", "yuy2", "uyvy") + _RGB_FAMILY + _BAYER, default=None,
+    ap.add_argument("--pixel-format", choices=("rgb", "nv12", "i420", "yuy2", "uyvy") + _RGB_FAMILY + _BAYER + _BAYER_WIDE, default=None,
                     help="pixel format of the input frames (default: by the input's name); must match a raw input's extension; a raw "
-                         ".bayer input needs it: bayer_rggb / bayer_grbg / bayer_gbrg / bayer_bggr, the sensor's pattern")
+                         ".bayer input needs it: bayer_rggb / bayer_grbg / bayer_gbrg / bayer_bggr, the sensor's pattern; a raw .bayer16 input (10- / 12-bit samples in "
+                         "little-endian 16-bit words) needs depth and pattern: bayer10_rggb ... bayer12_bggr")
     ap.add_argument("--yuv-matrix", choices=("bt601", "bt709"), default="bt601", help="conversion matrix of 4:2:0 / 4:2:2 input")
-    ap.add_argument("--raw-black-level", type=float, default=None, metavar="N", help="raw Bayer input: the sensor's black pedestal, 0 .. 255 (default 0)")
-    ap.add_argument("--raw-white-level", type=float, default=None, metavar="N", help="raw Bayer input: the sample value of full scale (default 255)")
+    ap.add_argument("--raw-black-level", type=float, default=None, metavar="N", help="raw Bayer input: the sensor's black pedestal, in sample values (default 0)")
+    ap.add_argument("--raw-white-level", type=float, default=None, metavar="N", help="raw Bayer input: the sample value of full scale (default 255; 1023 / 4095 for 10- / 12-bit input)")
     ap.add_argument("--raw-gains", type=_parse_gains, default=None, metavar="R,G,B[,..]",
                     help="raw Bayer input: white-balance gains R,G,B or R,Gr,Gb,B (default 1,1,1)")
     ap.add_argument("--raw-gamma", type=_parse_gamma, default=None, metavar="G|srgb", help="raw Bayer input: tone curve, v ** (1 / G) or the sRGB encoding (default 1)")
@@ -412,13 +444,13 @@ def main(argv=None):
     a = ap.parse_args(argv)
     raw = {k: v for k, v in (("black_level", a.raw_black_level), ("white_level", a.raw_white_level), ("gains", a.raw_gains),
                              ("gamma", a.raw_gamma)) if v is not None}
-    if raw and a.pixel_format not in _BAYER:
+    if raw and a.pixel_format not in _BAYER + _BAYER_WIDE:
         ap.error("--raw-black-level / --raw-white-level / --raw-gains / --raw-gamma condition raw Bayer samples: they need --pixel-format bayer_*")
     raw_table = None
     if raw:
         from .utils import raw_lut
         try:
-            raw_table = raw_lut(**raw)
+            raw_table = raw_lut(**raw) if a.pixel_format in _BAYER else raw_lut(bits=_raw_format_bits(a.pixel_format), **raw)
         except ValueError as e:
             ap.error(str(e))
     if a.split_view and a.output == "-":
@@ -437,9 +469,9 @@ def main(argv=None):
     if a.input_size is not None and a.size is not None and tuple(a.size) != tuple(a.input_size):
         ap.error("--size %dx%d and --input-size %dx%d name two sizes for the input frames" % (tuple(a.size) + tuple(a.input_size)))
     try:
-        src = FrameSource(a.input, a.input_size or a.size or image_wh, pixel_format=a.pixel_format if a.pixel_format in _BAYER else None)
+        src = FrameSource(a.input, a.input_size or a.size or image_wh, pixel_format=a.pixel_format if a.pixel_format in _BAYER + _BAYER_WIDE else None)
     except ValueError as e:
-        if not (_is_bayer_file(a.input) or a.pixel_format in _BAYER):
+        if not (_is_bayer_file(a.input) or _is_bayer16_file(a.input) or a.pixel_format in _BAYER + _BAYER_WIDE):
             raise
         ap.error(str(e))
     if a.pixel_format is not None and a.pixel_format != src.pixel_format:
