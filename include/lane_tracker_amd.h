@@ -64,7 +64,8 @@ extern "C" {
  *    the device); lt_set_raw_lut + lt_get_raw_lut (black level, white balance and tone curve of raw Bayer input as one table per colour
  *    phase, looked up on the device inside the undistortion and the row conversion); lt_set_raw_lut_wide + lt_get_raw_lut_wide +
  *    lt_raw16_to_rgb (10- and 12-bit raw Bayer, layouts 32 .. 35 and 48 .. 51: 16-bit words looked up in a table of 1 << bits entries per
- *    colour phase on their way into the 8-bit demosaic).  Nothing removed or changed. */
+ *    colour phase on their way into the 8-bit demosaic); lt_set_raw_color + lt_get_raw_color + lt_raw_to_rgb_color (the colour stage of raw
+ *    Bayer input: a colour-correction matrix and an output curve on every demosaiced pixel, on the device).  Nothing removed or changed. */
 #define LT_ABI_VERSION 5
 
 typedef enum lt_status {
@@ -252,8 +253,8 @@ int  lt_set_streams(lt_ctx* ctx, int nstreams);
  * context.  With a table set the conditioned kernels run whatever the table holds, the identity included; with none, the plain ones.
  * LT_ERR_STATE in a context whose input format is not raw Bayer; lt_set_input_format with a layout that is not raw Bayer removes the table.
  * lt_get_raw_lut: *is_set := 0 / 1 and, where one is set, the table into `lut` (either may be NULL).  Slots, uploads and lt_bayer_to_rgb are
- * unaffected.  Not built: 14 / 16-bit or companded raw (10 and 12 bits: below), other demosaics, a colour-correction matrix, lens-shading correction, a table
- * per slot.
+ * unaffected.  Not built: 14 / 16-bit or companded raw (10 and 12 bits: below), other demosaics, lens-shading correction, a table
+ * per slot (the colour-correction matrix: THE COLOUR STAGE, below).
  *
  * 10- AND 12-BIT RAW BAYER, as most raw sensors deliver it (GMSL / FPD-Link cameras in raw mode, BayerRG10 / BayerRG12, V4L2 SRGGB10 /
  * SRGGB12) -- LT_INPUT_BAYER10_RGGB .. _BGGR (32 .. 35) and LT_INPUT_BAYER12_RGGB .. _BGGR (48 .. 51), the pattern is layout & 3 in the
@@ -272,7 +273,29 @@ int  lt_set_streams(lt_ctx* ctx, int nstreams);
  * work as for 8-bit raw Bayer with two bytes a pixel: pitch >= 2 * img_w, and the plane's address and the pitch must be EVEN
  * (LT_ERR_INVALID).  lt_raw16_to_rgb is the conversion alone, lt_bayer_to_rgb's twin: one host frame of h x w words, `lut` = 4 << bits bytes
  * or NULL for the default.  Input formats only, as 8-bit raw Bayer is, with the same refusals.  Not built: MIPI-packed RAW10 / RAW12, 14 and
- * 16 bits, MSB-aligned containers, a table per stream. */
+ * 16 bits, MSB-aligned containers, a table per stream.
+ *
+ * THE COLOUR STAGE of raw Bayer input, 8-, 10- and 12-bit alike: what an image signal processor does AFTER the demosaic, where the raw
+ * table cannot reach because it mixes channels -- a colour-correction matrix from sensor RGB to display RGB, then one output curve.  `ccm`
+ * is int16[9], row-major, in Q10 (1024 is 1.0; row c makes output channel c), `curve` uint8[256]; for a demosaiced pixel (R, G, B)
+ *     v[c]   = (ccm[3c] * R + ccm[3c + 1] * G + ccm[3c + 2] * B + 512) >> 10        (int32, arithmetic shift: floor)
+ *     out[c] = curve[min(max(v[c], 0), 255)]
+ * Any int16 matrix is legal (3 * 255 * 32768 < 2^31).  Everything a context with stage (ccm, curve) computes from frames F -- undistorted
+ * rows, planes, masks, records, camera frames, annotated frames, visualisations -- is bit for bit what an RGB context computes from the
+ * demosaiced (and, with a raw table, conditioned) frames taken through the two lines above on the host.  In the undistortion the stage is
+ * applied to each demosaiced tap BEFORE the bilinear blend (clamp and curve are not linear); taps outside the image are 0 after it, as ever.
+ * So the camera's order is expressible: black level and white balance in the raw table (linear, no tone curve there), demosaic, matrix on
+ * linear data, gamma in `curve`.  lt_set_raw_color(ctx, ccm, curve, enable): enable != 0 sets the stage, ccm = NULL the identity matrix
+ * (1024 on the diagonal), curve = NULL the identity curve; enable = 0 removes it (neither pointer is read) and the plain raw kernels run
+ * again.  With a stage set its kernels run whatever it holds, the identity included.  Like lt_set_raw_lut it waits for everything the context
+ * has in flight, governs what is launched afterwards, and is a set-up or occasional call, NOT a per-frame one; the raw table may be set or
+ * changed before or after it.  LT_ERR_STATE in a context whose input format is not raw Bayer; lt_set_input_format with another layout
+ * removes the stage.  lt_get_raw_color: *is_set := 0 / 1 and, where one is set, matrix and curve into `ccm` / `curve` (any may be NULL).
+ * lt_raw_to_rgb_color is the conversion alone with the stage, of one host frame of h x w in any of the twelve raw layouts (bytes, or 16-bit
+ * words for 10 / 12 bits): `lut` the raw table of 4 * lut_entries bytes (256, or 1 << bits; LT_ERR_INVALID otherwise) or NULL -- none
+ * for 8-bit, the default for 10 / 12 --, ccm / curve as above, out_rgb = h * w * 3 bytes.  Not built: lens-shading correction, a stage per
+ * slot or stream, a stage on input that is not raw Bayer, more than 8 bits between the demosaic and the matrix (a LINEAR 8-bit mosaic
+ * followed by an sRGB curve has coarse shadows: the curve's first steps are several output levels apart). */
 enum lt_input_layout { LT_INPUT_RGB = 0, LT_INPUT_NV12 = 1, LT_INPUT_I420 = 2, LT_INPUT_YUY2 = 3, LT_INPUT_UYVY = 4,
                        LT_INPUT_BGR = 5, LT_INPUT_RGBA = 6, LT_INPUT_BGRA = 7,
                        LT_INPUT_BAYER_RGGB = 16, LT_INPUT_BAYER_GRBG = 17, LT_INPUT_BAYER_GBRG = 18, LT_INPUT_BAYER_BGGR = 19,
@@ -289,6 +312,10 @@ int  lt_get_raw_lut(lt_ctx* ctx, uint8_t* lut /* 1024 bytes */, int* is_set);
 int  lt_set_raw_lut_wide(lt_ctx* ctx, const uint8_t* lut /* 4 * entries bytes, phase-major; NULL: the default */, size_t entries);
 int  lt_get_raw_lut_wide(lt_ctx* ctx, uint8_t* lut /* 4 * entries bytes */, size_t entries);
 int  lt_raw16_to_rgb(lt_ctx* ctx, const uint16_t* frame, int h, int w, int layout, const uint8_t* lut /* 4 << bits bytes; NULL: the default */, uint8_t* out_rgb);
+int  lt_set_raw_color(lt_ctx* ctx, const int16_t* ccm /* 9, row-major, Q10; NULL: identity */, const uint8_t* curve /* 256; NULL: identity */, int enable);
+int  lt_get_raw_color(lt_ctx* ctx, int16_t* ccm /* 9 */, uint8_t* curve /* 256 */, int* is_set);
+int  lt_raw_to_rgb_color(lt_ctx* ctx, const void* frame, int h, int w, int layout, const uint8_t* lut /* 4 * lut_entries bytes, or NULL */, size_t lut_entries,
+                         const int16_t* ccm /* 9; NULL: identity */, const uint8_t* curve /* 256; NULL: identity */, uint8_t* out_rgb);
 /* Frames of another SIZE than the calibration's: a context with an input size of src_w x src_h takes RGB frames of src_h * src_w * 3
  * bytes and resizes them on the device to img_w x img_h -- cv2.resize(frame, (img_w, img_h)) with the default INTER_LINEAR, bit for bit:
  * half-pixel centres, 11-bit coefficients, OpenCV's two-stage rounding.  Everything the context computes, keeps and hands out is what a

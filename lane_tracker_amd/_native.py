@@ -239,6 +239,9 @@ _SIGNATURES = {
     "lt_set_raw_lut_wide": (C.c_int, [_P, _P, C.c_size_t]),
     "lt_get_raw_lut_wide": (C.c_int, [_P, _P, C.c_size_t]),
     "lt_raw16_to_rgb": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "lt_set_raw_color": (C.c_int, [_P, _P, _P, C.c_int]),
+    "lt_get_raw_color": (C.c_int, [_P, _P, _P, C.POINTER(C.c_int)]),
+    "lt_raw_to_rgb_color": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P, _P, _P]),
     "lt_attach_device_frames": (C.c_int, [_P, _P, C.c_int, C.c_int]),
     "lt_device_frames_rest": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "lt_device_alloc": (C.c_int, [C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]),
@@ -406,6 +409,17 @@ def effective_raw_lut(raw_lut, pixel_format):
         from .utils import raw_lut as _default
         lut = _default(bits=raw_bits(pixel_format))
     return lut
+
+
+def checked_raw_color(ccm, curve, pixel_format):
+    """`raw_ccm` / `raw_curve` of a tracker or group as the int16 (3, 3) and u8 (256,) arrays the device takes (None stays None);
+    ValueError -- before any device call -- for a stage with a pixel format that is not raw Bayer, and for another shape or dtype."""
+    if ccm is None and curve is None:
+        return None, None
+    from .utils import checked_raw_ccm, checked_raw_curve
+    if pixel_format not in BAYER_FORMATS and pixel_format not in BAYER_WIDE_FORMATS:
+        raise ValueError("raw_ccm / raw_curve follow the demosaic of raw Bayer frames: pixel_format=%r takes none" % (pixel_format,))
+    return (None if ccm is None else checked_raw_ccm(ccm)), (None if curve is None else checked_raw_curve(curve))
 
 
 def checked_input_size(input_size, img_size, pixel_format="rgb"):
@@ -985,6 +999,36 @@ class Context:
         out, is_set = np.zeros((4, 256), np.uint8), C.c_int(0)
         _check(self.lib.lt_get_raw_lut(self._h, out.ctypes.data, C.byref(is_set)))
         return out if is_set.value else None
+
+    def set_raw_color(self, ccm=None, curve=None, enable=True):
+        """The colour stage of a raw Bayer context (lt_set_raw_color): `ccm` int16 (3, 3) in Q10 (`utils.raw_ccm`; None: the identity)
+        and `curve` u8 (256,) (`utils.raw_curve`; None: the identity) on every demosaiced pixel, in the undistortion and in the row
+        conversion launched from now on; enable=False removes it.  Waits for the context's outstanding work: a set-up or occasional
+        call, not a per-frame one."""
+        m, t = checked_raw_color(ccm, curve, self._pixel_format)
+        _check(self.lib.lt_set_raw_color(self._h, None if m is None else m.ctypes.data, None if t is None else t.ctypes.data, 1 if enable else 0))
+
+    def get_raw_color(self):
+        """-> (ccm int16 (3, 3), curve u8 (256,)) of the colour stage, or None without one (lt_get_raw_color)."""
+        m, t, is_set = np.zeros((3, 3), np.int16), np.zeros(256, np.uint8), C.c_int(0)
+        _check(self.lib.lt_get_raw_color(self._h, m.ctypes.data, t.ctypes.data, C.byref(is_set)))
+        return (m, t) if is_set.value else None
+
+    def raw_to_rgb_color(self, frame, pattern, raw_lut=None, ccm=None, curve=None):
+        """One raw Bayer frame (H, W) in any of the twelve raw patterns -> RGB (H, W, 3) with the colour stage, on the device
+        (lt_raw_to_rgb_color): looked up in `raw_lut` (None: none / the 10- / 12-bit default), demosaiced, matrix, curve."""
+        if pattern not in BAYER_FORMATS and pattern not in BAYER_WIDE_FORMATS:
+            raise ValueError("pattern must be one of %s, got %r" % (", ".join(repr(n) for n in list(BAYER_FORMATS) + list(BAYER_WIDE_FORMATS)), pattern))
+        a = frames_array(frame, pattern)
+        lut = checked_raw_lut(raw_lut, pattern)
+        m, t = checked_raw_color(ccm, curve, pattern)
+        if a.ndim != 2 or a.shape[0] % 2 or a.shape[1] % 2 or a.shape[0] < 4 or a.shape[1] < 4:
+            raise ValueError("a raw Bayer frame is a 2-D array of shape (H, W) with H and W even and at least 4, got %r" % (a.shape,))
+        out = np.empty((a.shape[0], a.shape[1], 3), np.uint8)
+        _check(self.lib.lt_raw_to_rgb_color(self._h, a.ctypes.data, a.shape[0], a.shape[1], pixel_format_id(pattern),
+                                            None if lut is None else lut.ctypes.data, 1 << raw_bits(pattern),
+                                            None if m is None else m.ctypes.data, None if t is None else t.ctypes.data, out.ctypes.data))
+        return out
 
     def bayer_to_rgb(self, frame, pattern="bayer_rggb", raw_lut=None):
         """One 8-bit raw Bayer frame (H, W), H and W even and at least 4, -> RGB (H, W, 3): the bilinear demosaic, on the device

@@ -2,13 +2,13 @@
 // to compute; no OpenCV was at hand to check that, DESIGN.md 6.y.3 states the definition) -- as plain inline functions without HIP
 // types: k_frontend.hip (the undistortion's taps, the row conversion) runs exactly these expressions on the device, and a host
 // translation unit (tests/bayer_arith_host.cpp) compiles the same header with the system compiler, so the CPU tests check what the
-// GPU runs.  10- and 12-bit frames (16-bit words) reach this arithmetic through their raw table, which yields bytes: the last section
-// (tests/bayer_wide_host.cpp).
+// GPU runs.  10- and 12-bit frames (16-bit words) reach this arithmetic through their raw table, which yields bytes (tests/
+// bayer_wide_host.cpp); what follows the demosaic, the colour stage, is the last section (tests/raw_color_host.cpp).
 //
 // A frame is one plane of H rows of W bytes, H and W even and at least 4.  The pixel at (y, x) carries the colour at position
 // 2 (y & 1) + (x & 1) of the pattern's name.  An interior pixel (1 <= y <= H - 2, 1 <= x <= W - 2) is demosaiced from its 3 x 3
 // neighbourhood; a border pixel takes the value of the interior pixel at (clamp(y, 1, H - 2), clamp(x, 1, W - 2)), that pixel's own
-// colour phase included.  Everything is sums of at most four bytes: no multiply at all.
+// colour phase included.  The demosaic is sums of at most four bytes: no multiply at all.
 #pragma once
 #include <cstdint>
 
@@ -114,6 +114,35 @@ BA_HD uint32_t condition4w(uint32_t lo, uint32_t hi, const uint8_t* rowa, const 
 }
 // one site (a 16-bit word, or anything that holds it in its low 16 bits)
 BA_HD uint32_t condition1w(uint32_t s, const uint8_t* row, uint32_t mask) { return row[s & mask]; }
+
+// ---- the colour stage (lt_set_raw_color) ---------------------------------------------------------------------------------------------
+// After the demosaic: a colour-correction matrix m, int16 3 x 3 in Q10 (1024 is 1.0; row c makes output channel c), row-major as nine
+// ints, then one 256-entry output curve:
+//     v[c]   = (m[3c] * R + m[3c + 1] * G + m[3c + 2] * B + 512) >> 10         int32, arithmetic shift (floor)
+//     out[c] = curve[min(max(v[c], 0), 255)]
+// Any int16 matrix is legal (3 * 255 * 32768 < 2^31).  Both factors of every product fit 24 bits signed, and the compiler is shown so:
+// on the device they are 24-bit multiply-adds with the coefficient a scalar operand, the clamp a median of three.
+
+// coefficient (an int16 value held in an int) times channel (0 .. 255): the sign extension from 16 bits changes nothing and is what
+// lets the product be a full-rate 24-bit one
+BA_HD int mul24s(int coef, int ch) { return (int)(int16_t)coef * ch; }
+// one channel before the curve: the clamped index 0 .. 255
+BA_HD uint32_t color_index(const int* m, int r, int g, int b) {
+    const int v = (mul24s(m[0], r) + mul24s(m[1], g) + mul24s(m[2], b) + 512) >> 10;
+    return (uint32_t)clampi(v, 0, 255);
+}
+// one pixel, R | G << 8 | B << 16 -> the same
+BA_HD uint32_t color_px(uint32_t px, const int* m, const uint8_t* curve) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    // Opaque to the optimiser, free at run time: the channels are cut out of the packed word here (byte selects of the multiplies)
+    // and are visibly 8 bits wide.  Without it the compiler multiplies the demosaic's own red value, whose range it does not see
+    // across the phase branches: a quarter-rate v_mul_lo_u32 per channel and tap.
+    asm("" : "+v"(px));
+#endif
+    const int r = (int)(px & 255u), g = (int)((px >> 8) & 255u), b = (int)((px >> 16) & 255u);
+    return (uint32_t)curve[color_index(m, r, g, b)] | ((uint32_t)curve[color_index(m + 3, r, g, b)] << 8) |
+           ((uint32_t)curve[color_index(m + 6, r, g, b)] << 16);
+}
 
 }  // namespace ba
 }  // namespace lt

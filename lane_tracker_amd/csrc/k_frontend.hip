@@ -18,6 +18,10 @@
 //                      32 .. 35, 48 .. 51: 16-bit little-endian words, the sample in the low `bits` bits, a run-time argument), always
 //                      behind their wide raw table (lt_set_raw_lut_wide: 1 << bits entries per colour phase, 4 KB / 16 KB of dynamic LDS):
 //                      every site masked and looked up into the 8-bit window that the 8-bit demosaic takes
+//   k_cc_walk_rows, k_cc16_walk_rows <PATTERN, SRC, PER_SLOT>, k_cc_rows_rgb, k_cc16_rows_rgb <PATTERN, SURF, WIDE>  the four above with
+//                      the colour stage of raw Bayer input (lt_set_raw_color) on every demosaiced tap / pixel: a colour-correction matrix
+//                      (Q10, nine scalar operands of 24-bit multiply-adds), a clamp and a 256-entry output curve staged in LDS with the
+//                      table; launched in their place whenever a stage is set
 //   k_warp_split       cv2.warpPerspective      lane_tracker.py:834
 //                      + img[:,:,0]             lane_tracker.py:207
 //                      + cvtColor(RGB2LAB)[:,:,2] lane_tracker.py:208
@@ -370,6 +374,39 @@ struct Bayer16Lut : Bayer8<PATTERN> {
 template <int PATTERN> struct PlacesRows<Bayer16Lut<PATTERN>> : std::true_type {};
 template <int PATTERN> struct StagesTable<Bayer16Lut<PATTERN>> : std::true_type {};
 
+// The colour stage of raw Bayer input (lt_set_raw_color; bayer_arith.h: color_px): a wrapper around the two table formats above whose
+// decode runs theirs and then takes each of the four demosaiced taps through the colour-correction matrix and the output curve -- before
+// the blend, because the clamp and the curve are not linear; the walk masks taps outside the image to 0 afterwards, as ever.  The nine
+// coefficients are a kernel argument: wave-uniform, so they stay in SGPRs and every product is a v_mul_i32_i24 / v_mad_i32_i24 with a
+// scalar operand (the 16-bit dot form would need the channels packed in pairs first: more instructions, not fewer).  The curve's 256
+// bytes lie in LDS right in front of the table -- at a fixed address whatever the table's size; in the 8-bit form, whose LDS is a static
+// array, a lookup's offset is an immediate -- and in device memory too (`table`: curve, then table), so that one load per thread and one barrier stage both.
+struct RawColorMat { int m[9]; };
+template <int PATTERN>
+__device__ __forceinline__ void stage_with_curve(const Bayer8Lut<PATTERN>& f, uint8_t* lds) {        // 1280 bytes: 8 from each of the first 160 threads
+    if (threadIdx.x < 160) reinterpret_cast<uint2*>(lds)[threadIdx.x] = reinterpret_cast<const uint2*>(f.table)[threadIdx.x];
+    __syncthreads();
+}
+template <int PATTERN>
+__device__ __forceinline__ void stage_with_curve(const Bayer16Lut<PATTERN>& f, uint8_t* lds) {       // 256 + (4 << bits) bytes in 16-byte pieces
+    for (int i = threadIdx.x; i < 16 + (1 << (f.bits - 2)); i += 256) reinterpret_cast<uint4*>(lds)[i] = f.table[i];
+    __syncthreads();
+}
+template <class Base>
+struct ColorStage : Base {
+    typedef typename Base::Taps Taps;
+    RawColorMat cm;
+    uint8_t* curve;                          // LDS: the curve's 256 bytes, then the table (Base::lut = curve + 256)
+    __device__ __forceinline__ void stage() const { stage_with_curve(static_cast<const Base&>(*this), curve); }
+    __device__ __forceinline__ void decode(const Taps& t, uint32_t& a0, uint32_t& a1, uint32_t& b0, uint32_t& b1) const {
+        Base::decode(t, a0, a1, b0, b1);
+        a0 = ba::color_px(a0, cm.m, curve), a1 = ba::color_px(a1, cm.m, curve);
+        b0 = ba::color_px(b0, cm.m, curve), b1 = ba::color_px(b1, cm.m, curve);
+    }
+};
+template <class B> struct PlacesRows<ColorStage<B>> : PlacesRows<B> {};
+template <class B> struct StagesTable<ColorStage<B>> : std::true_type {};
+
 // The slots' own frames: `stride` bytes apart, planes dense.  One buffer resource covers the frames [z0, z1) of the walk (a frame
 // is selected by the scalar offset of the load) plus the format's padding behind them; beyond that the resource returns 0.
 // 32-bit offsets (a walk stays below 2^30 bytes: launch_undistort_rows) keep the address math on full-rate 24-bit multiplies.
@@ -590,6 +627,41 @@ __global__ __launch_bounds__(256) void k_raw16_walk_rows(const SurfEntry* __rest
     Bayer16Lut<PATTERN> fmt{};
     fmt.w = g.img_w, fmt.h = g.img_h, fmt.lut = s_lut_wide, fmt.table = reinterpret_cast<const uint4*>(raw_lut);
     fmt.bits = bits, fmt.mask = (1u << bits) - 1u;
+    if constexpr (SRC == SRC_SURFACES) undistort_walk<PER_SLOT>(a, SurfSource{tab}, fmt);
+    else undistort_walk<PER_SLOT>(a, SlotSource<true>{frames, stride}, fmt);
+}
+
+// The two walks above with the colour stage (lt_set_raw_color) on every demosaiced tap: the same forms and parameters, `raw_cc` the
+// output curve followed by the table (device memory: 256 + 1024 bytes, or 256 + (4 << bits)) and `cm` the matrix.  An 8-bit context
+// without a raw table runs k_cc_walk_rows with the identity table.  Launched in the plain raw walks' place, in the same stage, whenever
+// a colour stage is set -- the identity included.
+template <int PATTERN, int SRC, bool PER_SLOT>
+__global__ __launch_bounds__(256) void k_cc_walk_rows(const SurfEntry* __restrict__ tab, const uint8_t* __restrict__ frames, size_t stride,
+                                                     const int16_t* __restrict__ uxy, const uint16_t* __restrict__ ufrac,
+                                                     const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
+                                                     uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb, int remap,
+                                                     const uint32_t* __restrict__ raw_cc, RawColorMat cm) {
+    static_assert(SRC == SRC_SURFACES || SRC == SRC_SLOTS, "a raw Bayer staging frame is dword-aligned");
+    __shared__ alignas(16) uint8_t s_cc[256 + 1024];
+    const WalkArgs a{uxy, ufrac, SlotTables{sets, &ids}, g, und, und_px, first_slot, n, PER_SLOT ? 1 : fpb, remap};
+    ColorStage<Bayer8Lut<PATTERN>> fmt{};
+    fmt.w = g.img_w, fmt.h = g.img_h, fmt.lut = s_cc + 256, fmt.table = raw_cc;
+    fmt.cm = cm, fmt.curve = s_cc;
+    if constexpr (SRC == SRC_SURFACES) undistort_walk<PER_SLOT>(a, SurfSource{tab}, fmt);
+    else undistort_walk<PER_SLOT>(a, SlotSource<true>{frames, stride}, fmt);
+}
+template <int PATTERN, int SRC, bool PER_SLOT>
+__global__ __launch_bounds__(256) void k_cc16_walk_rows(const SurfEntry* __restrict__ tab, const uint8_t* __restrict__ frames, size_t stride,
+                                                       const int16_t* __restrict__ uxy, const uint16_t* __restrict__ ufrac,
+                                                       const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
+                                                       uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb, int remap,
+                                                       const uint32_t* __restrict__ raw_cc, int bits, RawColorMat cm) {
+    static_assert(SRC == SRC_SURFACES || SRC == SRC_SLOTS, "a raw Bayer staging frame is dword-aligned");
+    const WalkArgs a{uxy, ufrac, SlotTables{sets, &ids}, g, und, und_px, first_slot, n, PER_SLOT ? 1 : fpb, remap};
+    ColorStage<Bayer16Lut<PATTERN>> fmt{};
+    fmt.w = g.img_w, fmt.h = g.img_h, fmt.lut = s_lut_wide + 256, fmt.table = reinterpret_cast<const uint4*>(raw_cc);
+    fmt.bits = bits, fmt.mask = (1u << bits) - 1u;
+    fmt.cm = cm, fmt.curve = s_lut_wide;
     if constexpr (SRC == SRC_SURFACES) undistort_walk<PER_SLOT>(a, SurfSource{tab}, fmt);
     else undistort_walk<PER_SLOT>(a, SlotSource<true>{frames, stride}, fmt);
 }
@@ -830,6 +902,14 @@ struct RowsBayer {
         store_rgb1(dst + ((size_t)y * w + x) * 3, v);
     }
 };
+// What the table bodies below do to a demosaiced pixel (R | G << 8 | B << 16) on its way out: nothing, or the colour stage
+// (lt_set_raw_color: matrix, then the output curve in LDS).
+struct NoPost { __device__ __forceinline__ uint32_t operator()(uint32_t v) const { return v; } };
+struct ColorPost {
+    RawColorMat cm;
+    const uint8_t* curve;
+    __device__ __forceinline__ uint32_t operator()(uint32_t v) const { return ba::color_px(v, cm.m, curve); }
+};
 // RowsBayer behind a raw table (lt_set_raw_lut; `lut`: the table in LDS): the same two bodies over the conditioned mosaic, every byte
 // looked up in the table row of its site (bayer_arith.h: condition4 / condition1) before it is summed -- 3 x 18 lookups per 16 pixels
 // (wide), 9 per pixel (any).  Bodies of their own, so that the plain ones above stay the code they were.
@@ -837,7 +917,8 @@ template <int P>
 struct RowsBayerLut {
     // the table row of the sites of row parity par_y and column parity par_x
     __device__ __forceinline__ static const uint8_t* trow(const uint8_t* lut, int par_y, int par_x) { return lut + ba::lut_row(P, par_y, par_x); }
-    __device__ __forceinline__ static void wide(const Planes& s, const uint8_t* lut, uint8_t* dst, int h, int w, int y, int x0) {
+    template <class Post = NoPost>
+    __device__ __forceinline__ static void wide(const Planes& s, const uint8_t* lut, uint8_t* dst, int h, int w, int y, int x0, Post post = Post{}) {
         if (x0 >= w) return;
         const int cy = ba::tap_pos(y, h), xl = max(x0 - 1, 0), xr = min(x0 + 16, w - 1);
         uint32_t m[3][4], left[3], right[3];
@@ -860,12 +941,15 @@ struct RowsBayerLut {
                                  at(0, j - 1) + at(0, j + 1) + at(2, j - 1) + at(2, j + 1), ba::phase(P, cy, j));
         if (x0 == 0) px[0] = px[1];
         if (x0 + 16 == w) px[15] = px[14];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) px[j] = post(px[j]);
         uint32_t d[12];
 #pragma unroll
         for (int j = 0; j < 4; ++j) pack_rgb4(px + 4 * j, d + 3 * j);
         store_rgb16(dst + ((size_t)y * w + x0) * 3, d);
     }
-    __device__ __forceinline__ static void any(const Planes& s, const uint8_t* lut, uint8_t* dst, int h, int w, int y, int x) {
+    template <class Post = NoPost>
+    __device__ __forceinline__ static void any(const Planes& s, const uint8_t* lut, uint8_t* dst, int h, int w, int y, int x, Post post = Post{}) {
         if (x >= w) return;
         const int cy = ba::tap_pos(y, h), cx = ba::tap_pos(x, w);
         const uint8_t *up = s.y + (size_t)(cy - 1) * s.pitch + cx, *mid = up + s.pitch, *dn = mid + s.pitch;
@@ -874,7 +958,7 @@ struct RowsBayerLut {
         auto m = [&](int i) { return ba::condition1(mid[i], trow(lut, py, px ^ (i & 1))); };
         auto d = [&](int i) { return ba::condition1(dn[i], trow(lut, py ^ 1, px ^ (i & 1))); };
         const uint32_t v = ba::demosaic(m(0), m(-1) + m(1), u(0) + d(0), u(-1) + u(1) + d(-1) + d(1), ba::phase(P, cy, cx));
-        store_rgb1(dst + ((size_t)y * w + x) * 3, v);
+        store_rgb1(dst + ((size_t)y * w + x) * 3, post(v));
     }
 };
 // RowsBayerLut for 10- / 12-bit frames (16-bit words, pitch in bytes and even, `lut`: the wide table in LDS, 1 << bits bytes a row): the
@@ -884,7 +968,8 @@ struct RowsBayer16Lut {
     __device__ __forceinline__ static Planes dense(const uint8_t* frame, int, int w) { return Planes{frame, nullptr, nullptr, 2 * w, 0}; }
     __device__ __forceinline__ static const uint8_t* trow(const uint8_t* lut, int bits, int par_y, int par_x) { return lut + ba::lut_row_wide(bits, P, par_y, par_x); }
     __device__ __forceinline__ static uint32_t site(const uint8_t* row, int x) { return reinterpret_cast<const uint16_t*>(row)[x]; }
-    __device__ __forceinline__ static void wide(const Planes& s, const uint8_t* lut, int bits, uint8_t* dst, int h, int w, int y, int x0) {
+    template <class Post = NoPost>
+    __device__ __forceinline__ static void wide(const Planes& s, const uint8_t* lut, int bits, uint8_t* dst, int h, int w, int y, int x0, Post post = Post{}) {
         if (x0 >= w) return;
         const uint32_t mask = (1u << bits) - 1u;
         const int cy = ba::tap_pos(y, h), xl = max(x0 - 1, 0), xr = min(x0 + 16, w - 1);
@@ -908,12 +993,15 @@ struct RowsBayer16Lut {
                                  at(0, j - 1) + at(0, j + 1) + at(2, j - 1) + at(2, j + 1), ba::phase(P, cy, j));
         if (x0 == 0) px[0] = px[1];
         if (x0 + 16 == w) px[15] = px[14];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) px[j] = post(px[j]);
         uint32_t d[12];
 #pragma unroll
         for (int j = 0; j < 4; ++j) pack_rgb4(px + 4 * j, d + 3 * j);
         store_rgb16(dst + ((size_t)y * w + x0) * 3, d);
     }
-    __device__ __forceinline__ static void any(const Planes& s, const uint8_t* lut, int bits, uint8_t* dst, int h, int w, int y, int x) {
+    template <class Post = NoPost>
+    __device__ __forceinline__ static void any(const Planes& s, const uint8_t* lut, int bits, uint8_t* dst, int h, int w, int y, int x, Post post = Post{}) {
         if (x >= w) return;
         const uint32_t mask = (1u << bits) - 1u;
         const int cy = ba::tap_pos(y, h), cx = ba::tap_pos(x, w);
@@ -923,7 +1011,7 @@ struct RowsBayer16Lut {
         auto m = [&](int i) { return ba::condition1w(site(mid, cx + i), trow(lut, bits, py, px ^ (i & 1)), mask); };
         auto d = [&](int i) { return ba::condition1w(site(dn, cx + i), trow(lut, bits, py ^ 1, px ^ (i & 1)), mask); };
         const uint32_t v = ba::demosaic(m(0), m(-1) + m(1), u(0) + d(0), u(-1) + u(1) + d(-1) + d(1), ba::phase(P, cy, cx));
-        store_rgb1(dst + ((size_t)y * w + x) * 3, v);
+        store_rgb1(dst + ((size_t)y * w + x) * 3, post(v));
     }
 };
 // the description of a layout (none for 0, plain RGB: its rows are shown as they are)
@@ -993,6 +1081,43 @@ __global__ __launch_bounds__(256) void k_raw16_rows_rgb(std::conditional_t<SURF,
     const int i = (int)(blockIdx.x * THREADS + threadIdx.x), row = r0 + (int)blockIdx.y;
     if constexpr (WIDE) D::wide(p, s_lut_wide, bits, dst, h, w, row, i * 16);
     else D::any(p, s_lut_wide, bits, dst, h, w, row, i);
+}
+
+// The two row conversions above with the colour stage (lt_set_raw_color) on every demosaiced pixel: the same bodies and launch shapes,
+// `raw_cc` the output curve followed by the table (k_cc_walk_rows), staged together.
+template <int PATTERN, bool SURF, bool WIDE>
+__global__ __launch_bounds__(256) void k_cc_rows_rgb(std::conditional_t<SURF, SurfChunk, DenseFrames> src, uint8_t* __restrict__ rgb,
+                                                    size_t rgb_stride, int w, int r0, int h, const uint32_t* __restrict__ raw_cc, RawColorMat cm) {
+    __shared__ alignas(16) uint8_t s_cc[256 + 1024];
+    constexpr int THREADS = WIDE ? 64 : 256;
+    for (int i = threadIdx.x; i < 80; i += THREADS) reinterpret_cast<uint4*>(s_cc)[i] = reinterpret_cast<const uint4*>(raw_cc)[i];
+    __syncthreads();
+    typedef RowsBayerLut<PATTERN> D;
+    Planes p;
+    if constexpr (SURF) p = surf_planes(src.e[blockIdx.z]);
+    else p = RowsBayer<PATTERN>::dense(src.p + (size_t)blockIdx.z * src.stride, h, w);
+    uint8_t* dst = rgb + (size_t)blockIdx.z * rgb_stride;
+    const int i = (int)(blockIdx.x * THREADS + threadIdx.x), row = r0 + (int)blockIdx.y;
+    const ColorPost post{cm, s_cc};
+    if constexpr (WIDE) D::wide(p, s_cc + 256, dst, h, w, row, i * 16, post);
+    else D::any(p, s_cc + 256, dst, h, w, row, i, post);
+}
+template <int PATTERN, bool SURF, bool WIDE>
+__global__ __launch_bounds__(256) void k_cc16_rows_rgb(std::conditional_t<SURF, SurfChunk, DenseFrames> src, uint8_t* __restrict__ rgb,
+                                                      size_t rgb_stride, int w, int r0, int h, const uint32_t* __restrict__ raw_cc, int bits,
+                                                      RawColorMat cm) {
+    constexpr int THREADS = WIDE ? 64 : 256;
+    for (int i = threadIdx.x; i < 16 + (1 << (bits - 2)); i += THREADS) reinterpret_cast<uint4*>(s_lut_wide)[i] = reinterpret_cast<const uint4*>(raw_cc)[i];
+    __syncthreads();
+    typedef RowsBayer16Lut<PATTERN> D;
+    Planes p;
+    if constexpr (SURF) p = surf_planes(src.e[blockIdx.z]);
+    else p = D::dense(src.p + (size_t)blockIdx.z * src.stride, h, w);
+    uint8_t* dst = rgb + (size_t)blockIdx.z * rgb_stride;
+    const int i = (int)(blockIdx.x * THREADS + threadIdx.x), row = r0 + (int)blockIdx.y;
+    const ColorPost post{cm, s_lut_wide};
+    if constexpr (WIDE) D::wide(p, s_lut_wide + 256, bits, dst, h, w, row, i * 16, post);
+    else D::any(p, s_lut_wide + 256, bits, dst, h, w, row, i, post);
 }
 
 // Rows [r0, r1) of RGB surfaces -> the same rows of the slots' camera frames (row_bytes = 3 w, dense): a pitched row copy, one
@@ -1425,6 +1550,13 @@ static void with_layout(int layout, F&& f) {
     }
 }
 
+// the matrix of a colour stage as the kernels' argument
+static RawColorMat color_mat(const RawColor& cc) {
+    RawColorMat m;
+    for (int i = 0; i < 9; ++i) m.m[i] = cc.m[i];
+    return m;
+}
+
 // pattern (0 .. 3) -> f(std::integral_constant<int, pattern>{}): the 10- / 12-bit raw Bayer layouts, which have kernels of their own and
 // never go through with_layout
 template <class F>
@@ -1442,12 +1574,17 @@ static void with_pattern(int pattern, F&& f) {
 template <bool PER_SLOT>
 static void launch_walk(hipStream_t s, dim3 grid, FrameSource src, int layout, YuvCoef k, const int16_t* uxy, const uint16_t* ufrac,
                         const CalTables* sets, const CalIds& ids, FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n, int fpb,
-                        bool any_byte, const uint32_t* raw_lut) {
+                        bool any_byte, const uint32_t* raw_lut, const RawColor* cc) {
     const bool aligned = !any_byte && ((uintptr_t)src.frames & 3) == 0 && (src.stride & 3) == 0 && src.stride < (1u << 30);
     const int remap = xcd_remap();
     if (const int bits = raw_wide_bits(layout)) {        // 10- / 12-bit raw Bayer: always behind its table, 4 << bits bytes of LDS
         with_pattern(layout, [&](auto p) {
             constexpr int P = decltype(p)::value;
+            if (cc) {                        // ... and a colour stage: the curve's 256 bytes in front of the table
+                auto k_cc = src.tab ? k_cc16_walk_rows<P, SRC_SURFACES, PER_SLOT> : k_cc16_walk_rows<P, SRC_SLOTS, PER_SLOT>;
+                hipLaunchKernelGGL(k_cc, grid, dim3(256), ((size_t)4 << bits) + 256, s, src.tab, src.frames, src.stride, uxy, ufrac, sets, ids, g, und, und_px, first_slot, n, fpb, remap, cc->table, bits, color_mat(*cc));
+                return;
+            }
             auto k_raw = src.tab ? k_raw16_walk_rows<P, SRC_SURFACES, PER_SLOT> : k_raw16_walk_rows<P, SRC_SLOTS, PER_SLOT>;
             hipLaunchKernelGGL(k_raw, grid, dim3(256), (size_t)4 << bits, s, src.tab, src.frames, src.stride, uxy, ufrac, sets, ids, g, und, und_px, first_slot, n, fpb, remap, raw_lut, bits);
         });
@@ -1459,6 +1596,11 @@ static void launch_walk(hipStream_t s, dim3 grid, FrameSource src, int layout, Y
             hipLaunchKernelGGL(k_walk, grid, dim3(256), 0, s, src.tab, src.frames, src.stride, k, uxy, ufrac, sets, ids, g, und, und_px, first_slot, n, fpb, remap);
         };
         if constexpr (L >= 16) {
+            if (cc) {                        // raw Bayer with a colour stage: its walk, behind the raw table or the identity table
+                auto k_cc = src.tab ? k_cc_walk_rows<L - 16, SRC_SURFACES, PER_SLOT> : k_cc_walk_rows<L - 16, SRC_SLOTS, PER_SLOT>;
+                hipLaunchKernelGGL(k_cc, grid, dim3(256), 0, s, src.tab, src.frames, src.stride, uxy, ufrac, sets, ids, g, und, und_px, first_slot, n, fpb, remap, cc->table, color_mat(*cc));
+                return;
+            }
             if (raw_lut) {                   // raw Bayer behind a raw table: the conditioned walk, whatever the table holds
                 auto k_raw = src.tab ? k_raw_walk_rows<L - 16, SRC_SURFACES, PER_SLOT> : k_raw_walk_rows<L - 16, SRC_SLOTS, PER_SLOT>;
                 hipLaunchKernelGGL(k_raw, grid, dim3(256), 0, s, src.tab, src.frames, src.stride, uxy, ufrac, sets, ids, g, und, und_px, first_slot, n, fpb, remap, raw_lut);
@@ -1472,7 +1614,7 @@ static void launch_walk(hipStream_t s, dim3 grid, FrameSource src, int layout, Y
 }
 
 void launch_undistort_rows(hipStream_t s, FrameSource src, int layout, YuvCoef k, const int16_t* uxy, const uint16_t* ufrac,
-                           FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n, const uint32_t* raw_lut) {
+                           FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n, const uint32_t* raw_lut, const RawColor* cc) {
     if (n <= 0 || g.nrows <= 0) return;
     int fpb = frames_per_thread(n);
     // the slots of a walk are addressed by a 32-bit offset into one buffer resource: a walk stays below 2^30 bytes (one frame
@@ -1480,18 +1622,27 @@ void launch_undistort_rows(hipStream_t s, FrameSource src, int layout, YuvCoef k
     if (!src.tab) fpb = (int)std::max<size_t>(1, std::min<size_t>((size_t)fpb, (((size_t)1 << 30) - 1) / src.stride));
     const dim3 grid((g.img_w + 255) / 256, g.nrows, (n + fpb - 1) / fpb);
     static const bool unaligned = [] { const char* e = LT_EXP_ENV("LT_UNDISTORT_UNALIGNED"); return e && e[0] == '1'; }();   // A/B
-    launch_walk<false>(s, grid, src, layout, k, uxy, ufrac, nullptr, CalIds{}, g, und, und_px, first_slot, n, fpb, unaligned, raw_lut);
+    launch_walk<false>(s, grid, src, layout, k, uxy, ufrac, nullptr, CalIds{}, g, und, und_px, first_slot, n, fpb, unaligned, raw_lut, cc);
 }
 
 // The row conversion of n frames in `layout` (not 0), dense or from surfaces: the 16-column kernel where the width and every base and
 // pitch of the launch (`bits`: all of them ORed) are multiples of 16, the byte-wise one otherwise.
 template <bool SURF, class Src>
 static void launch_rows_to_rgb(hipStream_t s, int layout, const Src& src, size_t bits, YuvCoef k, uint8_t* rgb, size_t rgb_stride, int h, int w,
-                               int r0, int r1, int n, const uint32_t* raw_lut) {
+                               int r0, int r1, int n, const uint32_t* raw_lut, const RawColor* cc) {
     if (const int depth = raw_wide_bits(layout)) {       // 10- / 12-bit raw Bayer: always behind its table, the same two launch shapes
         with_pattern(layout, [&](auto p) {
             constexpr int P = decltype(p)::value;
             const unsigned rows = (unsigned)(r1 - r0);
+            if (cc) {                        // ... and a colour stage
+                if ((w & 15) == 0 && (bits & 15) == 0)
+                    hipLaunchKernelGGL((k_cc16_rows_rgb<P, SURF, true>), dim3((unsigned)((w / 16 + 63) / 64), rows, (unsigned)n), dim3(64), ((size_t)4 << depth) + 256, s,
+                                       src, rgb, rgb_stride, w, r0, h, cc->table, depth, color_mat(*cc));
+                else
+                    hipLaunchKernelGGL((k_cc16_rows_rgb<P, SURF, false>), dim3((unsigned)((w + 255) / 256), rows, (unsigned)n), dim3(256), ((size_t)4 << depth) + 256, s,
+                                       src, rgb, rgb_stride, w, r0, h, cc->table, depth, color_mat(*cc));
+                return;
+            }
             if ((w & 15) == 0 && (bits & 15) == 0)
                 hipLaunchKernelGGL((k_raw16_rows_rgb<P, SURF, true>), dim3((unsigned)((w / 16 + 63) / 64), rows, (unsigned)n), dim3(64), (size_t)4 << depth, s,
                                    src, rgb, rgb_stride, w, r0, h, raw_lut, depth);
@@ -1507,6 +1658,15 @@ static void launch_rows_to_rgb(hipStream_t s, int layout, const Src& src, size_t
             typedef RowsOf<L> D;
             const unsigned rows = (unsigned)(D::CHROMA_ROWS ? ((r1 + 1) >> 1) - (r0 >> 1) : r1 - r0);
             if constexpr (L >= 16) {
+                if (cc) {                    // raw Bayer with a colour stage: its bodies, the same two launch shapes
+                    if ((w & 15) == 0 && (bits & 15) == 0)
+                        hipLaunchKernelGGL((k_cc_rows_rgb<L - 16, SURF, true>), dim3((unsigned)((w / 16 + 63) / 64), rows, (unsigned)n), dim3(64), 0, s,
+                                           src, rgb, rgb_stride, w, r0, h, cc->table, color_mat(*cc));
+                    else
+                        hipLaunchKernelGGL((k_cc_rows_rgb<L - 16, SURF, false>), dim3((unsigned)((w + 255) / 256), rows, (unsigned)n), dim3(256), 0, s,
+                                           src, rgb, rgb_stride, w, r0, h, cc->table, color_mat(*cc));
+                    return;
+                }
                 if (raw_lut) {               // raw Bayer behind a raw table: the conditioned bodies, the same two launch shapes
                     if ((w & 15) == 0 && (bits & 15) == 0)
                         hipLaunchKernelGGL((k_raw_rows_rgb<L - 16, SURF, true>), dim3((unsigned)((w / 16 + 63) / 64), rows, (unsigned)n), dim3(64), 0, s,
@@ -1528,10 +1688,10 @@ static void launch_rows_to_rgb(hipStream_t s, int layout, const Src& src, size_t
 }
 
 void launch_yuv_rows_to_rgb(hipStream_t s, int layout, const uint8_t* yuv, size_t yuv_stride, YuvCoef k, uint8_t* rgb,
-                            size_t rgb_stride, int h, int w, int r0, int r1, int n, const uint32_t* raw_lut) {
+                            size_t rgb_stride, int h, int w, int r0, int r1, int n, const uint32_t* raw_lut, const RawColor* cc) {
     if (n <= 0 || r1 <= r0) return;
     launch_rows_to_rgb<false>(s, layout, DenseFrames{yuv, yuv_stride}, yuv_stride | rgb_stride | (size_t)(uintptr_t)yuv | (size_t)(uintptr_t)rgb, k,
-                              rgb, rgb_stride, h, w, r0, r1, n, raw_lut);
+                              rgb, rgb_stride, h, w, r0, r1, n, raw_lut, cc);
 }
 
 void launch_write_surf_entries(hipStream_t s, SurfEntry* tab, int first, const SurfEntry* entries, int n) {
@@ -1544,7 +1704,7 @@ void launch_write_surf_entries(hipStream_t s, SurfEntry* tab, int first, const S
 }
 
 void launch_surf_rows_to_rgb(hipStream_t s, int layout, const SurfEntry* entries, YuvCoef k, uint8_t* rgb, size_t rgb_stride, int h, int w,
-                             int r0, int r1, int n, const uint32_t* raw_lut) {
+                             int r0, int r1, int n, const uint32_t* raw_lut, const RawColor* cc) {
     if (n <= 0 || r1 <= r0) return;
     for (int i = 0; i < n; i += SurfChunk::N) {
         const int m = std::min(n - i, (int)SurfChunk::N);
@@ -1564,7 +1724,7 @@ void launch_surf_rows_to_rgb(hipStream_t s, int layout, const SurfEntry* entries
             else
                 hipLaunchKernelGGL(k_surf_copy_rows<false>, dim3((unsigned)((row_bytes + 255) / 256), (unsigned)(r1 - r0), (unsigned)m), dim3(256), 0, s, ch, dst, rgb_stride, row_bytes, r0);
         } else {
-            launch_rows_to_rgb<true>(s, layout, ch, bits, k, dst, rgb_stride, h, w, r0, r1, m, raw_lut);
+            launch_rows_to_rgb<true>(s, layout, ch, bits, k, dst, rgb_stride, h, w, r0, r1, m, raw_lut, cc);
         }
     }
 }
@@ -1594,13 +1754,13 @@ static CalIds pack_ids(const uint8_t* ids, int m) {
 }
 
 void launch_undistort_cal(hipStream_t s, FrameSource src, int layout, YuvCoef k, const CalTables* sets, const uint8_t* ids,
-                          FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n, const uint32_t* raw_lut) {
+                          FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n, const uint32_t* raw_lut, const RawColor* cc) {
     if (n <= 0 || g.nrows <= 0) return;
     for (int i = 0; i < n; i += CalIds::N) {
         const int m = std::min(n - i, (int)CalIds::N);
         const dim3 grid((g.img_w + 255) / 256, g.nrows, m);
         const FrameSource part = src.tab ? src : FrameSource::slots(src.frames + (size_t)i * src.stride, src.stride);
-        launch_walk<true>(s, grid, part, layout, k, nullptr, nullptr, sets, pack_ids(ids + i, m), g, und, und_px, first_slot + i, m, 1, false, raw_lut);
+        launch_walk<true>(s, grid, part, layout, k, nullptr, nullptr, sets, pack_ids(ids + i, m), g, und, und_px, first_slot + i, m, 1, false, raw_lut, cc);
     }
 }
 

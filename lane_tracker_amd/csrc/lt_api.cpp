@@ -717,6 +717,7 @@ void lt_destroy(lt_ctx* c) {
     dev_free(c->d_rs_yt);
     dev_free(c->d_raw_lut);
     dev_free(c->d_raw_lut_wide);
+    dev_free(c->d_raw_cc);
     dev_free(c->d_oxy);
     dev_free(c->d_ofrac);
     for (size_t i = 1; i < c->cal.size(); ++i) {     // (set 0's tables are the ones above)
@@ -912,6 +913,34 @@ static int install_wide_table(lt_ctx* c, int layout) {
     return write_wide_table(c, c->raw_lut_wide.data());
 }
 
+// the 256 bytes of `curve` followed by table (table_bytes) -> *d (device memory, allocated here where it is null), for the k_cc* kernels;
+// and the matrix widened into cc, whose table becomes *d.  A null table: the 8-bit identity.
+static int make_raw_color(const uint8_t* table, size_t table_bytes, const int16_t* ccm, const uint8_t* curve, uint32_t** d, RawColor* cc) {
+    std::vector<uint8_t> host(table_bytes + 256);
+    std::memcpy(host.data(), curve, 256);
+    if (table) std::memcpy(host.data() + 256, table, table_bytes);
+    else for (size_t i = 0; i < table_bytes; ++i) host[256 + i] = (uint8_t)(i & 255u);
+    int rc;
+    if (!*d && (rc = dev_alloc(d, host.size() / 4))) return rc;
+    HIP_TRY(hipMemcpy(*d, host.data(), host.size(), hipMemcpyHostToDevice));
+    for (int i = 0; i < 9; ++i) cc->m[i] = ccm[i];
+    cc->table = *d;
+    return LT_OK;
+}
+// the context's colour stage (raw_ccm, raw_curve) and the table its layout is conditioned with, into d_raw_cc / raw_cc; nothing in flight
+static int write_raw_color(lt_ctx* c) {
+    const bool wide = is_bayer_wide(c->in_layout);
+    const size_t table_bytes = wide ? c->raw_lut_wide.size() : sizeof c->raw_lut;
+    if (c->raw_cc_bytes != table_bytes + 256) {
+        dev_free(c->d_raw_cc);
+        c->raw_cc_bytes = 0;
+    }
+    const int rc = make_raw_color(wide ? c->raw_lut_wide.data() : c->raw_lut_set ? c->raw_lut : nullptr, table_bytes, c->raw_ccm, c->raw_curve,
+                                  &c->d_raw_cc, &c->raw_cc);
+    if (rc == LT_OK) c->raw_cc_bytes = table_bytes + 256;
+    return rc;
+}
+
 int lt_set_input_format(lt_ctx* c, int layout, const int32_t* coeffs) {
     if (!c) return fail(LT_ERR_INVALID, "null context");
     int rc;
@@ -930,6 +959,7 @@ int lt_set_input_format(lt_ctx* c, int layout, const int32_t* coeffs) {
     if ((rc = set_device(c))) return rc;
     if ((rc = sync_all(c))) return rc;
     if (!is_bayer(layout)) c->raw_lut_set = false;     // a raw table belongs to raw Bayer input
+    c->raw_color_set = false;                          // ... and a colour stage to the layout it was set for
     if (layout == LT_INPUT_RGB) {
         dev_free(c->d_yuv);
     } else {
@@ -967,7 +997,7 @@ int lt_set_raw_lut(lt_ctx* c, const uint8_t* lut) {
     }
     c->raw_lut_set = lut != nullptr;
     std::fill(c->front_ok.begin(), c->front_ok.end(), (uint8_t)0);
-    return LT_OK;
+    return c->raw_color_set ? write_raw_color(c) : LT_OK;       // (the colour stage's kernels read the table from its buffer)
 }
 
 int lt_get_raw_lut(lt_ctx* c, uint8_t* lut, int* is_set) {
@@ -996,7 +1026,35 @@ int lt_set_raw_lut_wide(lt_ctx* c, const uint8_t* lut, size_t entries) {
         rc = write_wide_table(c, c->raw_lut_wide.data());
     }
     std::fill(c->front_ok.begin(), c->front_ok.end(), (uint8_t)0);
+    if (rc == LT_OK && c->raw_color_set) rc = write_raw_color(c);
     return rc;
+}
+
+// The colour stage: as the raw table, a setting between runs -- behind everything in flight, and the slots' front ends are marked as not
+// run.  enable = 0 removes it (ccm and curve are not read).
+int lt_set_raw_color(lt_ctx* c, const int16_t* ccm, const uint8_t* curve, int enable) {
+    if (!c) return fail(LT_ERR_INVALID, "null context");
+    if (!is_raw_mosaic(c->in_layout)) return fail(LT_ERR_STATE, "a colour stage follows the demosaic of raw Bayer input: this context's input format is another layout");
+    int rc;
+    if ((rc = set_device(c))) return rc;
+    if ((rc = sync_all(c))) return rc;
+    if (enable) {
+        static const int16_t ident[9] = {1024, 0, 0, 0, 1024, 0, 0, 0, 1024};
+        std::memcpy(c->raw_ccm, ccm ? ccm : ident, sizeof c->raw_ccm);
+        for (int i = 0; i < 256; ++i) c->raw_curve[i] = curve ? curve[i] : (uint8_t)i;
+        if ((rc = write_raw_color(c))) return rc;
+    }
+    c->raw_color_set = enable != 0;
+    std::fill(c->front_ok.begin(), c->front_ok.end(), (uint8_t)0);
+    return LT_OK;
+}
+
+int lt_get_raw_color(lt_ctx* c, int16_t* ccm, uint8_t* curve, int* is_set) {
+    if (!c) return fail(LT_ERR_INVALID, "null context");
+    if (is_set) *is_set = c->raw_color_set ? 1 : 0;
+    if (ccm && c->raw_color_set) std::memcpy(ccm, c->raw_ccm, sizeof c->raw_ccm);
+    if (curve && c->raw_color_set) std::memcpy(curve, c->raw_curve, sizeof c->raw_curve);
+    return LT_OK;
 }
 
 int lt_get_raw_lut_wide(lt_ctx* c, uint8_t* lut, size_t entries) {
@@ -1038,7 +1096,7 @@ static inline int chroma_hi(int r0, int r1) { return r1 > r0 ? (r1 - 1) / 2 + 1 
 // rows [r0, r1) of the staging frames of slots [first, first + n) -> the same rows of their RGB camera frames, on `st`
 static void yuv_convert(lt_ctx* c, hipStream_t st, int first, int n, int r0, int r1) {
     launch_yuv_rows_to_rgb(st, c->in_layout, slot_yuv(c, first), c->yuv_stride, yuv_coef_of(c), slot_frame(c, first), c->frame_bytes,
-                           c->calib.img_h, c->calib.img_w, r0, r1, n, raw_lut_of(c));
+                           c->calib.img_h, c->calib.img_w, r0, r1, n, raw_lut_of(c), raw_color_of(c));
 }
 
 // ---- input frames of another size (lt_set_input_size) ------------------------------------------------------------------------
@@ -1701,7 +1759,7 @@ int lt_device_frames_rest(lt_ctx* c, int first, int n, const int32_t* rows4) {
     const int32_t* r = rows4 ? rows4 : whole;
     for (int k = 0; k < 4; k += 2)
         launch_surf_rows_to_rgb(c->copy, c->in_layout, &c->surf[(size_t)first], yuv_coef_of(c), slot_frame(c, first), c->frame_bytes,
-                                c->calib.img_h, c->calib.img_w, r[k], r[k + 1], n, raw_lut_of(c));
+                                c->calib.img_h, c->calib.img_w, r[k], r[k + 1], n, raw_lut_of(c), raw_color_of(c));
     HIP_TRY(hipGetLastError());
     if ((rc = note_range(c->readers, c->copy, first, first + n))) return rc;      // it reads the surfaces and writes the camera frames: the next upload waits
     if (!rows4) mark_frames(c, first, n, 1);
@@ -2377,8 +2435,8 @@ static int mask_run_impl(lt_ctx* c, int first, int n, const lt_filter_params* p,
                   const FrameSource src = att ? FrameSource::surfaces(c->d_surf)
                                           : c->in_layout != LT_INPUT_RGB ? FrameSource::slots(slot_yuv(c, a), c->yuv_stride)
                                                                          : FrameSource::slots(slot_frame(c, a), c->frame_bytes);
-                  if (mixed) launch_undistort_cal(st, src, c->in_layout, yuv_coef_of(c), c->d_cal, &c->slot_cal[(size_t)a], c->fe, c->d_und, c->und_px, a, b - a, raw_lut_of(c));
-                  else launch_undistort_rows(st, src, c->in_layout, yuv_coef_of(c), cs.d_uxy, cs.d_ufrac, c->fe, c->d_und, c->und_px, a, b - a, raw_lut_of(c));
+                  if (mixed) launch_undistort_cal(st, src, c->in_layout, yuv_coef_of(c), c->d_cal, &c->slot_cal[(size_t)a], c->fe, c->d_und, c->und_px, a, b - a, raw_lut_of(c), raw_color_of(c));
+                  else launch_undistort_rows(st, src, c->in_layout, yuv_coef_of(c), cs.d_uxy, cs.d_ufrac, c->fe, c->d_und, c->und_px, a, b - a, raw_lut_of(c), raw_color_of(c));
               } }
             { int mrc = n == 1 ? note_range_frame(c, c->readers, st, f0, f0 + m) : note_range(c->readers, st, f0, f0 + m); if (mrc) return mrc; }
             { StageScope t(c, ST_WARP_SPLIT, st);
@@ -2830,6 +2888,51 @@ int lt_raw16_to_rgb(lt_ctx* c, const uint16_t* frame, int h, int w, int layout, 
     dev_free(d_in);
     dev_free(d_out);
     dev_free(d_lut);
+    if (e != hipSuccess) return fail(LT_ERR_HIP, "raw Bayer conversion failed: %s", hipGetErrorString(e));
+    return LT_OK;
+}
+
+// one raw Bayer host frame in any of the twelve raw layouts -> RGB with the colour stage, on the device: every sample looked up in `lut`
+// (8-bit: null is no table; 10 / 12 bits: null is the default table), demosaiced, then matrix and curve (null: the identity each) -- the
+// k_cc* row kernels alone
+int lt_raw_to_rgb_color(lt_ctx* c, const void* frame, int h, int w, int layout, const uint8_t* lut, size_t lut_entries, const int16_t* ccm,
+                        const uint8_t* curve, uint8_t* out_rgb) {
+    if (!c || !frame || !out_rgb) return fail(LT_ERR_INVALID, "null argument");
+    if (!is_raw_mosaic(layout)) return fail(LT_ERR_INVALID, "lt_raw_to_rgb_color takes the raw Bayer layouts (16 .. 19, 32 .. 35, 48 .. 51)");
+    const bool wide = is_bayer_wide(layout);
+    const size_t entries = wide ? (size_t)1 << raw_bits(layout) : 256;
+    if (lut && lut_entries != entries) return fail(LT_ERR_INVALID, "the raw table of this layout has %zu entries per colour phase, got %zu", entries, lut_entries);
+    int rc = check_bayer_size(h, w);
+    if (rc) return rc;
+    if (h > 16384 || w > 16384) return fail(LT_ERR_INVALID, "bad image size (at most 16384 x 16384)");
+    if ((rc = set_device(c))) return rc;
+    const size_t px = (size_t)h * w, in_bytes = wide ? px * 2 : px;
+    std::vector<uint8_t> def;
+    if (!lut && wide) {
+        def.resize(4 * entries);
+        default_wide_table(raw_bits(layout), def.data());
+        lut = def.data();
+    }
+    static const int16_t ident[9] = {1024, 0, 0, 0, 1024, 0, 0, 0, 1024};
+    uint8_t line[256];
+    for (int i = 0; i < 256; ++i) line[i] = curve ? curve[i] : (uint8_t)i;
+    uint8_t *d_in = nullptr, *d_out = nullptr;
+    uint32_t* d_cc = nullptr;
+    RawColor cc = {};
+    if ((rc = dev_alloc(&d_in, in_bytes)) || (rc = dev_alloc(&d_out, px * 3)) || (rc = make_raw_color(lut, 4 * entries, ccm ? ccm : ident, line, &d_cc, &cc))) {
+        dev_free(d_in); dev_free(d_out); dev_free(d_cc);
+        return rc;
+    }
+    hipError_t e = hipMemcpyAsync(d_in, frame, in_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        launch_yuv_rows_to_rgb(c->stream, layout, d_in, in_bytes, YuvCoef{}, d_out, px * 3, h, w, 0, h, 1, nullptr, &cc);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out_rgb, d_out, px * 3, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    dev_free(d_in);
+    dev_free(d_out);
+    dev_free(d_cc);
     if (e != hipSuccess) return fail(LT_ERR_HIP, "raw Bayer conversion failed: %s", hipGetErrorString(e));
     return LT_OK;
 }

@@ -170,6 +170,16 @@ struct lt_ctx {
     // the host copy sized by the layout, the device copy allocated once at that size when the layout is set.
     std::vector<uint8_t> raw_lut_wide;
     uint32_t* d_raw_lut_wide = nullptr;
+    // The colour stage of a raw Bayer context (lt_set_raw_color): the colour-correction matrix (Q10) and the output curve on the host, and
+    // in device memory ONE buffer for the k_cc* kernels -- the curve's 256 bytes followed by the table the frames are conditioned with (the
+    // 8-bit raw table, the identity where none is set, or the wide table) -- rewritten whenever the stage or the table changes while
+    // a stage is set (write_raw_color).  raw_color_set says which kernels are launched: the stage's content never does.
+    bool raw_color_set = false;
+    int16_t raw_ccm[9] = {1024, 0, 0, 0, 1024, 0, 0, 0, 1024};
+    uint8_t raw_curve[256] = {0};
+    lt::RawColor raw_cc = {};                     // what the launches take: the matrix widened, table = d_raw_cc
+    uint32_t* d_raw_cc = nullptr;
+    size_t raw_cc_bytes = 0;
     // Input frames of another size (lt_set_input_size): src_w x src_h RGB frames, resized on the device to the calibration's size
     // (cv2.resize, INTER_LINEAR).  Per slot a staging frame of src_bytes = src_h * src_w * 3 bytes, src_stride apart (a multiple of 16
     // with at least 16 bytes of padding behind every frame: k_resize_rows reads aligned dwords); the uploads copy source rows into it
@@ -367,6 +377,8 @@ inline bool is_bayer_wide(int layout) { return raw_bits(layout) != 0; }
 inline bool is_raw_mosaic(int layout) { return is_bayer(layout) || is_bayer_wide(layout); }
 // the raw table the front end and the row conversion of `c` are launched with: null without one (a wide context always has one)
 inline const uint32_t* raw_lut_of(const lt_ctx* c) { return is_bayer_wide(c->in_layout) ? c->d_raw_lut_wide : c->raw_lut_set ? c->d_raw_lut : nullptr; }
+// the colour stage they are launched with: null without one
+inline const lt::RawColor* raw_color_of(const lt_ctx* c) { return c->raw_color_set ? &c->raw_cc : nullptr; }
 inline int packed_bpp(int layout) {
     return layout == LT_INPUT_RGB || layout == LT_INPUT_BGR ? 3 : layout == LT_INPUT_RGBA || layout == LT_INPUT_BGRA ? 4
            : layout == LT_INPUT_YUY2 || layout == LT_INPUT_UYVY || is_bayer_wide(layout) ? 2 : is_bayer(layout) ? 1 : 0;

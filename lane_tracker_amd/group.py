@@ -53,6 +53,7 @@ class _GroupMember(LaneTracker):
     process = functools.wraps(LaneTracker.process)(_not_owned)
     process_batch = process_stream = warm = _not_owned
     set_raw_lut = _not_owned        # (one table for the whole group: LaneTrackerGroup.set_raw_lut)
+    set_raw_color = _not_owned      # (... and one colour stage: LaneTrackerGroup.set_raw_color)
     _owns_context = False           # close() leaves the group's context to LaneTrackerGroup.close
 
 
@@ -107,7 +108,7 @@ class LaneTrackerGroup:
 
     def __init__(self, k, img_size, warped_size, cam_matrix, dist_coeffs, warp_matrices, mpp_conversion, n_fail=8, n_reset=4,
                  n_average=2, print_frame_count=False, device=0, *, pixel_format='rgb', yuv_matrix='bt601', calibrations=None,
-                 input_size=None, raw_lut=None):
+                 input_size=None, raw_lut=None, raw_ccm=None, raw_curve=None):
         k = int(k)
         if k < 1:
             raise ValueError("a group needs at least one stream")
@@ -125,6 +126,7 @@ class LaneTrackerGroup:
         if self._resize_from is not None:
             self._frame_shape = (self._resize_from[1], self._resize_from[0], 3)
         self._raw_lut = _native.effective_raw_lut(raw_lut, pixel_format)       # one raw table for the whole group (LaneTracker's raw_lut)
+        self._raw_ccm, self._raw_curve = _native.checked_raw_color(raw_ccm, raw_curve, pixel_format)     # ... and one colour stage
         self._ctx = _native.Context(img_size, warped_size, cam_matrix, dist_coeffs, warp_matrices[0], device=device, capacity=4 * k)
         self._tick = 0
         self._overlay_sets = set()           # the calibration sets whose overlay a member has configured
@@ -135,6 +137,8 @@ class LaneTrackerGroup:
                 self._ctx.set_input_size(self._resize_from)
             if self._raw_lut is not None:
                 self._ctx.set_raw_lut(self._raw_lut)
+            if self._raw_ccm is not None or self._raw_curve is not None:
+                self._ctx.set_raw_color(self._raw_ccm, self._raw_curve)
             # the calibration sets of the context: 0 is the group's own, one more for every distinct calibration among the streams
             sets = {_table_key(dict(cam_matrix=cam_matrix, dist_coeffs=dist_coeffs, warp_matrices=warp_matrices)): 0}
             self._cal_ids = []
@@ -149,7 +153,7 @@ class LaneTrackerGroup:
                                                   c["mpp_conversion"], n_fail=n_fail, n_reset=n_reset, n_average=n_average,
                                                   print_frame_count=print_frame_count, device=device,
                                                   pixel_format=pixel_format, yuv_matrix=yuv_matrix, input_size=input_size,
-                                                  raw_lut=self._raw_lut))
+                                                  raw_lut=self._raw_lut, raw_ccm=self._raw_ccm, raw_curve=self._raw_curve))
         except BaseException:
             self.close()
             raise
@@ -174,6 +178,28 @@ class LaneTrackerGroup:
         self._raw_lut = lut
         for t in self.trackers:
             t._raw_lut = lut
+            t._resident = None
+
+    @property
+    def raw_ccm(self):
+        """The colour-correction matrix of the group's colour stage, int16 (3, 3) in Q10, or None (`set_raw_color`)."""
+        return None if self._raw_ccm is None else self._raw_ccm.copy()
+
+    @property
+    def raw_curve(self):
+        """The output curve of the group's colour stage, u8 (256,), or None (`set_raw_color`)."""
+        return None if self._raw_curve is None else self._raw_curve.copy()
+
+    def set_raw_color(self, ccm=None, curve=None):
+        """Another colour stage for every stream of the group, or (None, None) for none, between `process()` calls
+        (LaneTracker.set_raw_color)."""
+        ccm, curve = _native.checked_raw_color(ccm, curve, self.pixel_format)
+        if not _native.raw_bits(self.pixel_format):
+            return
+        self._ctx.set_raw_color(ccm, curve, enable=ccm is not None or curve is not None)
+        self._raw_ccm, self._raw_curve = ccm, curve
+        for t in self.trackers:
+            t._raw_ccm, t._raw_curve = ccm, curve
             t._resident = None
 
     def calibration_count(self):

@@ -66,7 +66,7 @@ class LaneTracker(StreamPipeline):
 
     def __init__(self, img_size, warped_size, cam_matrix, dist_coeffs, warp_matrices, mpp_conversion,
                  n_fail=8, n_reset=4, n_average=2, print_frame_count=False, device=0, *, pixel_format='rgb', yuv_matrix='bt601',
-                 input_size=None, raw_lut=None):
+                 input_size=None, raw_lut=None, raw_ccm=None, raw_curve=None):
         # the camera's pixel format: 'rgb' frames (H, W, 3), YUV 4:2:0 as decoders hand it out -- 'nv12' / 'i420' frames
         # (H * 3 // 2, W) -- or packed 4:2:2 as cameras and capture cards do -- 'yuy2' / 'uyvy' frames (H, W, 2) -- converted on the
         # device with `yuv_matrix` ('bt601', 'bt709') -- or what users' own software holds: 'bgr' frames (H, W, 3) (OpenCV's order),
@@ -87,6 +87,9 @@ class LaneTracker(StreamPipeline):
         # raw Bayer only: the raw table (utils.raw_lut: black level, white balance, tone curve), u8 (4, 256) -- every sample looked up on the
         # device before the demosaic; configuration like the format's matrix, not state
         self._raw_lut = _native.effective_raw_lut(raw_lut, pixel_format)   # (10 / 12 bits: u8 (4, 2**bits), always one -- None is the default)
+        # raw Bayer only: the colour stage behind the demosaic -- a colour-correction matrix, int16 (3, 3) in Q10 (utils.raw_ccm), then an
+        # output curve, u8 (256,) (utils.raw_curve) -- on the device; giving either turns the stage on (the other: the identity)
+        self._raw_ccm, self._raw_curve = _native.checked_raw_color(raw_ccm, raw_curve, pixel_format)
         self.img_size = img_size
         self.warped_size = warped_size
         self.cam_matrix = cam_matrix
@@ -160,6 +163,8 @@ class LaneTracker(StreamPipeline):
                 ctx.set_input_size(self._resize_from)
             if self._raw_lut is not None:
                 ctx.set_raw_lut(self._raw_lut)
+            if self._raw_ccm is not None or self._raw_curve is not None:
+                ctx.set_raw_color(self._raw_ccm, self._raw_curve)
         except BaseException:
             ctx.close()
             raise
@@ -185,6 +190,31 @@ class LaneTracker(StreamPipeline):
         self._ctx.set_raw_lut(lut)
         self._raw_lut = lut
         self._resident = None       # the camera frame the slot holds was converted with the table before
+
+    @property
+    def raw_ccm(self):
+        """The colour-correction matrix of a raw Bayer tracker's colour stage, int16 (3, 3) in Q10, or None (`set_raw_color`)."""
+        return None if self._raw_ccm is None else self._raw_ccm.copy()
+
+    @property
+    def raw_curve(self):
+        """The output curve of a raw Bayer tracker's colour stage, u8 (256,), or None (`set_raw_color`)."""
+        return None if self._raw_curve is None else self._raw_curve.copy()
+
+    def set_raw_color(self, ccm=None, curve=None):
+        """Another colour stage -- `ccm` from `utils.raw_ccm(...)`, int16 (3, 3) in Q10, `curve` from `utils.raw_curve(...)`, u8 (256,);
+        one given, the other is the identity -- or (None, None) for none, between frames or windows: the frames processed from now on go
+        through it after the demosaic.  It waits for the device; not a per-frame call, and not allowed inside an active
+        `process_stream()`.  ValueError for a tracker whose pixel format is not raw Bayer, another shape or dtype (a float matrix goes
+        through `utils.raw_ccm` first)."""
+        ccm, curve = _native.checked_raw_color(ccm, curve, self.pixel_format)
+        if not _native.raw_bits(self.pixel_format):      # ((None, None) on a tracker that takes no stage: nothing to do)
+            return
+        if self._in_stream:
+            raise RuntimeError("set_raw_color() inside an active process_stream(): exhaust or close the generator first")
+        self._ctx.set_raw_color(ccm, curve, enable=ccm is not None or curve is not None)
+        self._raw_ccm, self._raw_curve = ccm, curve
+        self._resident = None       # the camera frame the slot holds was converted with the stage before
 
     def _check_frame(self, img, window=False):
         """A 4:2:0 / 4:2:2 tracker takes frames of its own shape only (nothing is uploaded before this has been looked at); an RGB tracker

@@ -214,6 +214,104 @@ def apply_raw_lut(frames, pattern, lut):
     return out
 
 
+def checked_raw_ccm(ccm):
+    """A colour-correction matrix as the C-contiguous int16 array (3, 3) the device takes; ValueError for any other shape or dtype
+    (nothing is cast: a float matrix goes through `utils.raw_ccm` first)."""
+    a = np.asarray(ccm)
+    if a.dtype != np.int16 or a.shape != (3, 3):
+        raise ValueError("a colour-correction matrix is an int16 array of shape (3, 3) in Q10 -- utils.raw_ccm makes one of a float "
+                         "matrix --, got %s %r" % (a.dtype, a.shape))
+    return np.ascontiguousarray(a)
+
+
+def checked_raw_curve(curve):
+    """An output curve as the C-contiguous u8 array (256,) the device takes; ValueError for any other shape or dtype."""
+    a = np.asarray(curve)
+    if a.dtype != np.uint8 or a.shape != (256,):
+        raise ValueError("an output curve is a uint8 array of shape (256,), got %s %r" % (a.dtype, a.shape))
+    return np.ascontiguousarray(a)
+
+
+def raw_ccm(matrix, preserve_white=True):
+    """A colour-correction matrix -- float 3 x 3, sensor RGB to display RGB, row c making output channel c -- as the int16 (3, 3) in Q10
+    that the colour stage of a raw Bayer tracker takes (`LaneTracker(..., raw_ccm=...)`): rint(1024 m).  With `preserve_white` the
+    diagonal entry of every row is then adjusted so that the row sums to rint(1024 * sum(row)): a matrix whose rows sum to 1 keeps grey
+    grey, exactly.  ValueError for another shape, a value that is not finite, or an entry that leaves int16."""
+    m = np.asarray(matrix, dtype=np.float64)
+    if m.shape != (3, 3):
+        raise ValueError("a colour-correction matrix is 3 x 3, got %r" % (m.shape,))
+    if not np.all(np.isfinite(m)):
+        raise ValueError("a colour-correction matrix holds finite numbers, got %r" % (m.tolist(),))
+    q = np.rint(1024.0 * m)
+    if preserve_white:
+        for c in range(3):
+            q[c, c] += np.rint(1024.0 * m[c].sum()) - q[c].sum()
+    if q.min() < -32768 or q.max() > 32767:
+        raise ValueError("a colour-correction matrix in Q10 must fit int16 (entries -32 .. 31.999), got %r" % (m.tolist(),))
+    return q.astype(np.int16)
+
+
+def raw_curve(gamma=1.0):
+    """An output curve, u8 (256,), for the colour stage of a raw Bayer tracker (`LaneTracker(..., raw_curve=...)`): the tone step of
+    `raw_lut` on v = s / 255 --
+
+        v = v ** (1 / gamma)           gamma='srgb':  12.92 v  if v <= 0.0031308  else  1.055 v ** (1 / 2.4) - 0.055
+        out = floor(255 v + 0.5)
+
+    -- for s = 0 .. 255.  gamma = 1 is the identity."""
+    if gamma != 'srgb' and (isinstance(gamma, str) or not float(gamma) > 0):
+        raise ValueError("gamma is a positive number or 'srgb', got %r" % (gamma,))
+    t = np.arange(256, dtype=np.float64) / 255.0
+    if gamma == 'srgb':
+        t = np.where(t <= 0.0031308, 12.92 * t, 1.055 * t ** (1.0 / 2.4) - 0.055)
+    else:
+        t = t ** (1.0 / float(gamma))
+    return np.floor(255.0 * t + 0.5).astype(np.uint8)
+
+
+def apply_raw_color(rgb, ccm=None, curve=None):
+    """The colour stage of raw Bayer input on u8 RGB (..., 3): with M = `ccm`, int16 (3, 3) in Q10 (None: 1024 * I), and T = `curve`,
+    u8 (256,) (None: arange(256)),
+
+        v[c]   = (M[c][0] * R + M[c][1] * G + M[c][2] * B + 512) >> 10        int32, arithmetic shift (floor)
+        out[c] = T[min(max(v[c], 0), 255)]
+
+    NumPy only.  This is the definition: a raw Bayer tracker with `raw_ccm=M, raw_curve=T` (and, if set, raw table L) fed frames F
+    computes, bit for bit, what an RGB tracker computes from `apply_raw_color(bayer_to_rgb(apply_raw_lut(F, pattern, L), pattern), M, T)`."""
+    m = np.eye(3, dtype=np.int32) * 1024 if ccm is None else checked_raw_ccm(ccm).astype(np.int32)
+    t = np.arange(256, dtype=np.uint8) if curve is None else checked_raw_curve(curve)
+    a = np.asarray(rgb)
+    if a.dtype != np.uint8 or a.ndim < 1 or a.shape[-1] != 3:
+        raise ValueError("RGB pixels are a uint8 array (..., 3), got %s %r" % (a.dtype, a.shape))
+    p = a.astype(np.int32)
+    v = (p[..., None, :] * m).sum(axis=-1)                  # (..., 3): channel c from row c
+    return t[np.clip((v + 512) >> 10, 0, 255)]
+
+
+def bayer_to_rgb_color(frame, pattern, raw_lut=None, ccm=None, curve=None):
+    """A raw Bayer frame (H, W) or a stack (n, H, W) in any of the twelve raw patterns -- u8 for 'bayer_*', uint16 for 'bayer10_*' /
+    'bayer12_*' -- to RGB with the colour stage, on the device: every sample looked up in `raw_lut` (8-bit: u8 (4, 256), None: no
+    table; 10 / 12 bits: u8 (4, 2**bits), None: the default), demosaiced, then `apply_raw_color(.., ccm, curve)`.  What a
+    `LaneTracker(..., pixel_format=pattern, raw_lut=.., raw_ccm=.., raw_curve=..)` sees of the frame."""
+    from . import _native
+    from .lane_tracker import _context_for_module_functions
+    if pattern not in _native.BAYER_FORMATS and pattern not in _native.BAYER_WIDE_FORMATS:
+        raise ValueError("pattern must be one of %s, got %r" % (", ".join(repr(n) for n in list(_native.BAYER_FORMATS) + list(_native.BAYER_WIDE_FORMATS)), pattern))
+    raw_lut = _native.checked_raw_lut(raw_lut, pattern)
+    ccm = None if ccm is None else checked_raw_ccm(ccm)
+    curve = None if curve is None else checked_raw_curve(curve)
+    a = _native.frames_array(frame, pattern)
+    if a.ndim not in (2, 3):
+        raise ValueError("a raw Bayer frame is an array (H, W), a stack of them (n, H, W); got %r" % (a.shape,))
+    ctx = _context_for_module_functions()
+    if a.ndim == 2:
+        return ctx.raw_to_rgb_color(a, pattern, raw_lut, ccm, curve)
+    out = np.empty(a.shape + (3,), np.uint8)
+    for k in range(a.shape[0]):
+        out[k] = ctx.raw_to_rgb_color(a[k], pattern, raw_lut, ccm, curve)
+    return out
+
+
 def rgb_to_yuv(frame, layout='nv12', matrix='bt601'):
     """The counterpart of `yuv_to_rgb`: an RGB frame (H, W, 3), H and W even, to YUV 4:2:0 as OpenCV holds it -- a u8 array
     (H * 3 // 2, W): the Y plane, then interleaved U,V rows ('nv12') or the U plane and the V plane ('i420') -- on the device,

@@ -407,6 +407,16 @@ def _parse_gamma(text):
         raise argparse.ArgumentTypeError("gamma is a positive number or 'srgb', got %r" % (text,)) from None
 
 
+def _parse_ccm(text):
+    try:
+        m = tuple(float(v) for v in text.split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError("a colour-correction matrix is nine numbers m00,...,m22, got %r" % (text,)) from None
+    if len(m) != 9:
+        raise argparse.ArgumentTypeError("a colour-correction matrix is nine numbers m00,...,m22 (row-major), got %d values" % len(m))
+    return (m[0:3], m[3:6], m[6:9])
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Lane tracking over a frame sequence (process_video.py without moviepy)")
     ap.add_argument("input", help="directory of images, .npy (n,H,W,3), raw .rgb / .bgr / .rgba / .bgra, raw 4:2:0 (.nv12, .i420 / .yuv) or raw packed 4:2:2 (.yuy2, .uyvy)")
@@ -428,6 +438,11 @@ def main(argv=None):
     ap.add_argument("--raw-gains", type=_parse_gains, default=None, metavar="R,G,B[,..]",
                     help="raw Bayer input: white-balance gains R,G,B or R,Gr,Gb,B (default 1,1,1)")
     ap.add_argument("--raw-gamma", type=_parse_gamma, default=None, metavar="G|srgb", help="raw Bayer input: tone curve, v ** (1 / G) or the sRGB encoding (default 1)")
+    ap.add_argument("--raw-ccm", type=_parse_ccm, default=None, metavar="m00,...,m22",
+                    help="raw Bayer input: colour-correction matrix applied after the demosaic, nine numbers row-major (sensor RGB to display "
+                         "RGB; rounded to Q10, each row's sum kept)")
+    ap.add_argument("--raw-out-gamma", type=_parse_gamma, default=None, metavar="G|srgb",
+                    help="raw Bayer input: output curve applied after the matrix, v ** (1 / G) or the sRGB encoding (with it, keep --raw-gamma at 1)")
     ap.add_argument("--out-format", choices=("rgb", "nv12", "i420") + _RGB_FAMILY, default=None,
                     help="write the annotated frames through a device sink in this pixel format: a raw .rgb / .nv12 / .i420 file for "
                          "4:2:0 (converted on the device, --out-yuv-matrix), a raw .bgr / .rgba / .bgra file (permuted on the device, "
@@ -453,6 +468,18 @@ def main(argv=None):
             raw_table = raw_lut(**raw) if a.pixel_format in _BAYER else raw_lut(bits=_raw_format_bits(a.pixel_format), **raw)
         except ValueError as e:
             ap.error(str(e))
+    if (a.raw_ccm is not None or a.raw_out_gamma is not None) and a.pixel_format not in _BAYER + _BAYER_WIDE:
+        ap.error("--raw-ccm / --raw-out-gamma follow the demosaic of raw Bayer frames: they need --pixel-format bayer_*")
+    raw_matrix = raw_out_curve = None
+    try:
+        if a.raw_ccm is not None:
+            from .utils import raw_ccm
+            raw_matrix = raw_ccm(a.raw_ccm)
+        if a.raw_out_gamma is not None:
+            from .utils import raw_curve
+            raw_out_curve = raw_curve(a.raw_out_gamma)
+    except ValueError as e:
+        ap.error(str(e))
     if a.split_view and a.output == "-":
         ap.error("--split-view shows the annotated frames: it needs an output")
     if a.split_view and a.visualize_search:
@@ -479,7 +506,7 @@ def main(argv=None):
     lt = LaneTracker(img_size=image_wh, warped_size=warped_wh, cam_matrix=cam_matrix, dist_coeffs=dist_coeffs,
                      warp_matrices=(M, Minv), mpp_conversion=(mppv, mpph), n_fail=8, n_reset=4, n_average=2,
                      print_frame_count=a.frame_count, device=a.device, pixel_format=src.pixel_format, yuv_matrix=a.yuv_matrix,
-                     input_size=a.input_size, raw_lut=raw_table)
+                     input_size=a.input_size, raw_lut=raw_table, raw_ccm=raw_matrix, raw_curve=raw_out_curve)
     try:
         out_size = src.size if a.input_size is None else tuple(int(v) for v in image_wh)
         if a.split_view:                 # the annotated frame on top, the pane strip below it
