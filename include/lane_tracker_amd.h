@@ -65,7 +65,9 @@ extern "C" {
  *    phase, looked up on the device inside the undistortion and the row conversion); lt_set_raw_lut_wide + lt_get_raw_lut_wide +
  *    lt_raw16_to_rgb (10- and 12-bit raw Bayer, layouts 32 .. 35 and 48 .. 51: 16-bit words looked up in a table of 1 << bits entries per
  *    colour phase on their way into the 8-bit demosaic); lt_set_raw_color + lt_get_raw_color + lt_raw_to_rgb_color (the colour stage of raw
- *    Bayer input: a colour-correction matrix and an output curve on every demosaiced pixel, on the device).  Nothing removed or changed. */
+ *    Bayer input: a colour-correction matrix and an output curve on every demosaiced pixel, on the device); lt_set_raw_shading +
+ *    lt_get_raw_shading + lt_get_raw_shading_plane + lt_raw_to_rgb_shaded (lens-shading correction of raw Bayer input from a gain mesh, on
+ *    every sample in front of the raw table, on the device).  Nothing removed or changed. */
 #define LT_ABI_VERSION 5
 
 typedef enum lt_status {
@@ -253,7 +255,7 @@ int  lt_set_streams(lt_ctx* ctx, int nstreams);
  * context.  With a table set the conditioned kernels run whatever the table holds, the identity included; with none, the plain ones.
  * LT_ERR_STATE in a context whose input format is not raw Bayer; lt_set_input_format with a layout that is not raw Bayer removes the table.
  * lt_get_raw_lut: *is_set := 0 / 1 and, where one is set, the table into `lut` (either may be NULL).  Slots, uploads and lt_bayer_to_rgb are
- * unaffected.  Not built: 14 / 16-bit or companded raw (10 and 12 bits: below), other demosaics, lens-shading correction, a table
+ * unaffected.  Not built: 14 / 16-bit or companded raw (10 and 12 bits: below), other demosaics, a table
  * per slot (the colour-correction matrix: THE COLOUR STAGE, below).
  *
  * 10- AND 12-BIT RAW BAYER, as most raw sensors deliver it (GMSL / FPD-Link cameras in raw mode, BayerRG10 / BayerRG12, V4L2 SRGGB10 /
@@ -293,9 +295,35 @@ int  lt_set_streams(lt_ctx* ctx, int nstreams);
  * removes the stage.  lt_get_raw_color: *is_set := 0 / 1 and, where one is set, matrix and curve into `ccm` / `curve` (any may be NULL).
  * lt_raw_to_rgb_color is the conversion alone with the stage, of one host frame of h x w in any of the twelve raw layouts (bytes, or 16-bit
  * words for 10 / 12 bits): `lut` the raw table of 4 * lut_entries bytes (256, or 1 << bits; LT_ERR_INVALID otherwise) or NULL -- none
- * for 8-bit, the default for 10 / 12 --, ccm / curve as above, out_rgb = h * w * 3 bytes.  Not built: lens-shading correction, a stage per
+ * for 8-bit, the default for 10 / 12 --, ccm / curve as above, out_rgb = h * w * 3 bytes.  Not built: a stage per
  * slot or stream, a stage on input that is not raw Bayer, more than 8 bits between the demosaic and the matrix (a LINEAR 8-bit mosaic
- * followed by an sRGB curve has coarse shadows: the curve's first steps are several output levels apart). */
+ * followed by an sRGB curve has coarse shadows: the curve's first steps are several output levels apart).
+ *
+ * LENS SHADING of raw Bayer input, 8-, 10- and 12-bit alike: the gain that depends on the POSITION in the image (vignetting, the colour cast
+ * towards the corners), which neither the position-blind raw table nor the per-pixel matrix can correct.  It comes FIRST: shading, raw
+ * table, demosaic, colour stage; it maps a sample to a sample of the same depth.  `mesh` is uint16[4][mesh_h][mesh_w], phase-major as the
+ * raw table, gains in Q12 (4096 is 1.0; any uint16 is legal), 2 <= mesh_w, mesh_h <= 64, node (0, 0) on pixel (0, 0) and node (mesh_h - 1,
+ * mesh_w - 1) on pixel (img_h - 1, img_w - 1).  The gain of site (y, x), p its phase, in unsigned 32-bit integers:
+ *     u = x * (mesh_w - 1) * 256 / (img_w - 1);  j = min(u >> 8, mesh_w - 2);  a = u - (j << 8)
+ *     v = y * (mesh_h - 1) * 256 / (img_h - 1);  i = min(v >> 8, mesh_h - 2);  b = v - (i << 8)
+ *     G = ((256-a)*(256-b)*mesh[p][i][j] + a*(256-b)*mesh[p][i][j+1] + (256-a)*b*mesh[p][i+1][j] + a*b*mesh[p][i+1][j+1] + 32768) >> 16
+ * and a sample s (the byte, or the word masked to its bits) with the pedestal B = black[p], 0 <= B <= smax (255, or (1 << bits) - 1):
+ *     s' = min(max(B + (((s - B) * G + 2048) >> 12), 0), smax)                       (int32, arithmetic shift: floor)
+ * G = 4096 is the identity; the pedestal stays in place, so a raw table built with the same black level follows unchanged.  Everything a
+ * context with a map computes from frames F is bit for bit what the same context without one computes from the frames taken through the two
+ * lines above on the host (utils.apply_raw_shading).  lt_set_raw_shading(ctx, mesh, mesh_w, mesh_h, black, enable): enable != 0 sets the
+ * map -- the mesh is expanded on the device into a gain plane uint16[img_h][img_w], allocated by the first set --, enable = 0 removes it and
+ * frees the plane (no pointer is read); black = NULL is four zeros.  With a map set its kernels run whatever it holds, the identity
+ * included; a set that fails on the device leaves the context WITHOUT a map, whatever it had.  Like lt_set_raw_color it waits for everything the context has in flight, governs what is launched afterwards, and is a set-up
+ * or occasional call, NOT a per-frame one; raw table and colour stage may be set or changed before or after it.  LT_ERR_STATE in a context
+ * whose input format is not raw Bayer, LT_ERR_INVALID for a mesh dimension outside 2 .. 64 or a black value outside 0 .. smax;
+ * lt_set_input_format with another layout removes the map.  lt_get_raw_shading: *is_set := 0 / 1 and, where one is set, the mesh (4 *
+ * mesh_w * mesh_h values; at most 4 * 64 * 64), its dimensions and the black values (any pointer may be NULL).  lt_get_raw_shading_plane:
+ * the device's expanded plane, img_h * img_w values (LT_ERR_STATE without a map).  lt_raw_to_rgb_shaded is lt_raw_to_rgb_color behind a
+ * map: the conversion alone, of one host frame in any of the twelve raw layouts; mesh = NULL is no map, and with ccm = curve = NULL there
+ * is no colour stage either (the row kernels without one).  Not built: a map per stream or calibration set of a group, a map for input
+ * that is not raw Bayer, meshes above 64 x 64, radial or polynomial models (sample them into a mesh on the host), a map change inside a
+ * running stream. */
 enum lt_input_layout { LT_INPUT_RGB = 0, LT_INPUT_NV12 = 1, LT_INPUT_I420 = 2, LT_INPUT_YUY2 = 3, LT_INPUT_UYVY = 4,
                        LT_INPUT_BGR = 5, LT_INPUT_RGBA = 6, LT_INPUT_BGRA = 7,
                        LT_INPUT_BAYER_RGGB = 16, LT_INPUT_BAYER_GRBG = 17, LT_INPUT_BAYER_GBRG = 18, LT_INPUT_BAYER_BGGR = 19,
@@ -316,6 +344,12 @@ int  lt_set_raw_color(lt_ctx* ctx, const int16_t* ccm /* 9, row-major, Q10; NULL
 int  lt_get_raw_color(lt_ctx* ctx, int16_t* ccm /* 9 */, uint8_t* curve /* 256 */, int* is_set);
 int  lt_raw_to_rgb_color(lt_ctx* ctx, const void* frame, int h, int w, int layout, const uint8_t* lut /* 4 * lut_entries bytes, or NULL */, size_t lut_entries,
                          const int16_t* ccm /* 9; NULL: identity */, const uint8_t* curve /* 256; NULL: identity */, uint8_t* out_rgb);
+int  lt_set_raw_shading(lt_ctx* ctx, const uint16_t* mesh /* 4 * mesh_w * mesh_h, phase-major, Q12 */, int mesh_w, int mesh_h, const int32_t* black /* 4; NULL: zeros */, int enable);
+int  lt_get_raw_shading(lt_ctx* ctx, uint16_t* mesh, int* mesh_w, int* mesh_h, int32_t* black /* 4 */, int* is_set);
+int  lt_get_raw_shading_plane(lt_ctx* ctx, uint16_t* plane /* img_h * img_w */);
+int  lt_raw_to_rgb_shaded(lt_ctx* ctx, const void* frame, int h, int w, int layout, const uint8_t* lut /* 4 * lut_entries bytes, or NULL */, size_t lut_entries,
+                          const int16_t* ccm /* 9, or NULL */, const uint8_t* curve /* 256, or NULL */, const uint16_t* mesh /* or NULL: no map */, int mesh_w, int mesh_h,
+                          const int32_t* black /* 4; NULL: zeros */, uint8_t* out_rgb);
 /* Frames of another SIZE than the calibration's: a context with an input size of src_w x src_h takes RGB frames of src_h * src_w * 3
  * bytes and resizes them on the device to img_w x img_h -- cv2.resize(frame, (img_w, img_h)) with the default INTER_LINEAR, bit for bit:
  * half-pixel centres, 11-bit coefficients, OpenCV's two-stage rounding.  Everything the context computes, keeps and hands out is what a

@@ -242,6 +242,10 @@ _SIGNATURES = {
     "lt_set_raw_color": (C.c_int, [_P, _P, _P, C.c_int]),
     "lt_get_raw_color": (C.c_int, [_P, _P, _P, C.POINTER(C.c_int)]),
     "lt_raw_to_rgb_color": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P, _P, _P]),
+    "lt_set_raw_shading": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int]),
+    "lt_get_raw_shading": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), _P, C.POINTER(C.c_int)]),
+    "lt_get_raw_shading_plane": (C.c_int, [_P, _P]),
+    "lt_raw_to_rgb_shaded": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P, _P, _P, C.c_int, C.c_int, _P, _P]),
     "lt_attach_device_frames": (C.c_int, [_P, _P, C.c_int, C.c_int]),
     "lt_device_frames_rest": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "lt_device_alloc": (C.c_int, [C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]),
@@ -420,6 +424,18 @@ def checked_raw_color(ccm, curve, pixel_format):
     if pixel_format not in BAYER_FORMATS and pixel_format not in BAYER_WIDE_FORMATS:
         raise ValueError("raw_ccm / raw_curve follow the demosaic of raw Bayer frames: pixel_format=%r takes none" % (pixel_format,))
     return (None if ccm is None else checked_raw_ccm(ccm)), (None if curve is None else checked_raw_curve(curve))
+
+
+def checked_raw_shading(shading, pixel_format):
+    """`raw_shading` of a tracker or group as the utils.RawShading (mesh uint16 (4, mh, mw), black int32 (4,)) the device takes, or None;
+    ValueError -- before any device call -- for a map with a pixel format that is not raw Bayer, for a mesh of another shape or dtype
+    and for a black value above the format's largest sample."""
+    if shading is None:
+        return None
+    from .utils import checked_raw_shading as _checked
+    if pixel_format not in BAYER_FORMATS and pixel_format not in BAYER_WIDE_FORMATS:
+        raise ValueError("raw_shading corrects raw Bayer frames: pixel_format=%r takes none" % (pixel_format,))
+    return _checked(shading, raw_bits(pixel_format))
 
 
 def checked_input_size(input_size, img_size, pixel_format="rgb"):
@@ -1013,6 +1029,52 @@ class Context:
         m, t, is_set = np.zeros((3, 3), np.int16), np.zeros(256, np.uint8), C.c_int(0)
         _check(self.lib.lt_get_raw_color(self._h, m.ctypes.data, t.ctypes.data, C.byref(is_set)))
         return (m, t) if is_set.value else None
+
+    def set_raw_shading(self, shading):
+        """The lens-shading map of a raw Bayer context (lt_set_raw_shading): `shading` a `utils.RawShading` -- every sample corrected by
+        the gain of its position before the raw table, in the undistortion and in the row conversion launched from now on -- or None,
+        which removes it.  Waits for the context's outstanding work: a set-up or occasional call, not a per-frame one."""
+        s = checked_raw_shading(shading, self._pixel_format)
+        if s is None:
+            _check(self.lib.lt_set_raw_shading(self._h, None, 0, 0, None, 0))
+            return
+        _check(self.lib.lt_set_raw_shading(self._h, s.mesh.ctypes.data, s.mesh.shape[2], s.mesh.shape[1], s.black.ctypes.data, 1))
+
+    def get_raw_shading(self):
+        """-> the utils.RawShading of the context, or None without one (lt_get_raw_shading)."""
+        from .utils import RawShading
+        mw, mh, is_set = C.c_int(0), C.c_int(0), C.c_int(0)
+        _check(self.lib.lt_get_raw_shading(self._h, None, C.byref(mw), C.byref(mh), None, C.byref(is_set)))
+        if not is_set.value:
+            return None
+        mesh, black = np.zeros((4, mh.value, mw.value), np.uint16), np.zeros(4, np.int32)
+        _check(self.lib.lt_get_raw_shading(self._h, mesh.ctypes.data, None, None, black.ctypes.data, None))
+        return RawShading(mesh, black)
+
+    def raw_shading_plane(self):
+        """-> the gain plane the device expanded the context's shading mesh into, uint16 (H, W) (lt_get_raw_shading_plane)."""
+        out = np.empty((self.img_h, self.img_w), np.uint16)
+        _check(self.lib.lt_get_raw_shading_plane(self._h, out.ctypes.data))
+        return out
+
+    def raw_to_rgb_shaded(self, frame, pattern, shading, raw_lut=None, ccm=None, curve=None):
+        """`raw_to_rgb_color` behind the shading map `shading` (lt_raw_to_rgb_shaded); without `ccm` and `curve`: no colour stage."""
+        if pattern not in BAYER_FORMATS and pattern not in BAYER_WIDE_FORMATS:
+            raise ValueError("pattern must be one of %s, got %r" % (", ".join(repr(n) for n in list(BAYER_FORMATS) + list(BAYER_WIDE_FORMATS)), pattern))
+        a = frames_array(frame, pattern)
+        lut = checked_raw_lut(raw_lut, pattern)
+        m, t = checked_raw_color(ccm, curve, pattern)
+        s = checked_raw_shading(shading, pattern)
+        if s is None:
+            raise ValueError("raw_to_rgb_shaded takes a shading map (raw_to_rgb_color: the conversion without one)")
+        if a.ndim != 2 or a.shape[0] % 2 or a.shape[1] % 2 or a.shape[0] < 4 or a.shape[1] < 4:
+            raise ValueError("a raw Bayer frame is a 2-D array of shape (H, W) with H and W even and at least 4, got %r" % (a.shape,))
+        out = np.empty((a.shape[0], a.shape[1], 3), np.uint8)
+        _check(self.lib.lt_raw_to_rgb_shaded(self._h, a.ctypes.data, a.shape[0], a.shape[1], pixel_format_id(pattern),
+                                             None if lut is None else lut.ctypes.data, 1 << raw_bits(pattern),
+                                             None if m is None else m.ctypes.data, None if t is None else t.ctypes.data,
+                                             s.mesh.ctypes.data, s.mesh.shape[2], s.mesh.shape[1], s.black.ctypes.data, out.ctypes.data))
+        return out
 
     def raw_to_rgb_color(self, frame, pattern, raw_lut=None, ccm=None, curve=None):
         """One raw Bayer frame (H, W) in any of the twelve raw patterns -> RGB (H, W, 3) with the colour stage, on the device

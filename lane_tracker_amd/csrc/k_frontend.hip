@@ -22,6 +22,11 @@
 //                      the colour stage of raw Bayer input (lt_set_raw_color) on every demosaiced tap / pixel: a colour-correction matrix
 //                      (Q10, nine scalar operands of 24-bit multiply-adds), a clamp and a 256-entry output curve staged in LDS with the
 //                      table; launched in their place whenever a stage is set
+//   k_ls_walk_rows, k_ls16_walk_rows <PATTERN, SRC, PER_SLOT, CC>, k_ls_rows_rgb, k_ls16_rows_rgb <PATTERN, SURF, WIDE, CC>  the table forms
+//                      above, without and with (CC) the colour stage, behind the lens-shading correction of raw Bayer input
+//                      (lt_set_raw_shading; shade_arith.h): every sample corrected by the gain of its site before its table lookup.  The
+//                      gains lie in a plane that k_shade_expand makes of the map's mesh once; a walk loads the 16 of its window once and
+//                      keeps them across its frames; launched in the others' place whenever a map is set
 //   k_warp_split       cv2.warpPerspective      lane_tracker.py:834
 //                      + img[:,:,0]             lane_tracker.py:207
 //                      + cvtColor(RGB2LAB)[:,:,2] lane_tracker.py:208
@@ -45,6 +50,7 @@
 #include "bayer_arith.h"
 #include "front_arith.h"
 #include "lt_internal.h"
+#include "shade_arith.h"
 #include "yuv_arith.h"
 
 namespace lt {
@@ -407,6 +413,59 @@ struct ColorStage : Base {
 template <class B> struct PlacesRows<ColorStage<B>> : PlacesRows<B> {};
 template <class B> struct StagesTable<ColorStage<B>> : std::true_type {};
 
+// Lens-shading correction of raw Bayer input (lt_set_raw_shading; shade_arith.h: s' = B + (((s - B) G + 2048) >> 12), clamped): a wrapper
+// around the two table formats whose decode shades every site of the 4 x 4 window between its extraction and its table lookup.  The gain
+// plane (uint16[h][w], expanded from the mesh by k_shade_expand when the map is set) is fetched like a 16-bit mosaic, but ONCE per walk: the
+// window of sites does not depend on the frame, so place_rows loads its four rows -- four aligned 96-bit loads, window_at<uint64_t> -- and
+// the 16 gains stay in 8 VGPRs across the per-frame loop.  The four pedestals are a kernel argument (SGPRs); which of them the window's
+// even / odd rows and columns have follows from the window's parities, selected once per walk.  Per frame and site: a subtract, a 24-bit
+// multiply-add, a shift and a clamp; no vector-memory instruction, no LDS, no scratch.
+struct RawShadeBlack { int b[4]; };          // by colour phase
+// (all four read, then selected by value: a select between the ADDRESSES of two members would keep the struct that holds them in scratch)
+__device__ __forceinline__ int black_of(const RawShadeBlack& k, int ph) {
+    const int b0 = k.b[0], b1 = k.b[1], b2 = k.b[2], b3 = k.b[3];
+    const int lo = (ph & 1) ? b1 : b0, hi = (ph & 1) ? b3 : b2;
+    return (ph & 2) ? hi : lo;
+}
+template <class F> struct PatternOf;
+template <int P> struct PatternOf<Bayer8Lut<P>> : std::integral_constant<int, P> {};
+template <int P> struct PatternOf<Bayer16Lut<P>> : std::integral_constant<int, P> {};
+template <class Base>
+struct ShadeStage : Base {
+    typedef typename Base::Taps Taps;
+    static constexpr bool WIDE = sizeof(typename Base::Window) == 8;     // Bayer16Lut: 16-bit sites
+    static constexpr int PATTERN = PatternOf<Base>::value;
+    __amdgpu_buffer_rsrc_t grs;              // the gain plane and its 16 bytes of padding
+    RawShadeBlack blk;
+    uint64_t g0, g1, g2, g3;                 // the gains of the window's four rows, four 16-bit gains each
+    sa::Black2 ke, ko;                       // the pedestals of rows 0, 2 / 1, 3 of the window (columns 0, 2 and 1, 3)
+    __device__ __forceinline__ void shade_with(const uint16_t* gains, const RawShadeBlack& b) {
+        grs = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint16_t*>(gains), 0, __mul24(this->h, this->w) * 2 + 16, RSRC_RAW);
+        blk = b;
+    }
+    __device__ __forceinline__ void place_rows(int cy0, int cy1) {
+        Base::place_rows(cy0, cy1);
+        const int py = this->by & 1, px = this->bx & 1, pitch = 2 * this->w;
+        const uint32_t at = (uint32_t)(__mul24(this->by, pitch) + 2 * this->bx);
+        g0 = window_at<uint64_t>(grs, at, 0), g1 = window_at<uint64_t>(grs, at + (uint32_t)pitch, 0);
+        g2 = window_at<uint64_t>(grs, at + 2u * (uint32_t)pitch, 0), g3 = window_at<uint64_t>(grs, at + 3u * (uint32_t)pitch, 0);
+        ke = sa::black2(black_of(blk, ba::phase_of(PATTERN, py, px)), black_of(blk, ba::phase_of(PATTERN, py, px ^ 1)));
+        ko = sa::black2(black_of(blk, ba::phase_of(PATTERN, py ^ 1, px)), black_of(blk, ba::phase_of(PATTERN, py ^ 1, px ^ 1)));
+    }
+    template <class Row>
+    __device__ __forceinline__ uint32_t cond(Row r, uint64_t g, const sa::Black2& k, const uint8_t* a, const uint8_t* b) const {
+        if constexpr (WIDE) return sa::shade_condition4w((uint32_t)r, (uint32_t)(r >> 32), (uint32_t)g, (uint32_t)(g >> 32), k, a, b, this->mask);
+        else return sa::shade_condition4(r, (uint32_t)g, (uint32_t)(g >> 32), k, a, b);
+    }
+    __device__ __forceinline__ void decode(const Taps& t, uint32_t& a0, uint32_t& a1, uint32_t& b0, uint32_t& b1) const {
+        const typename Bayer8<PATTERN>::Taps c{cond(t.r0, g0, ke, this->ea, this->eb), cond(t.r1, g1, ko, this->oa, this->ob),
+                                               cond(t.r2, g2, ke, this->ea, this->eb), cond(t.r3, g3, ko, this->oa, this->ob)};
+        Bayer8<PATTERN>::decode(c, a0, a1, b0, b1);
+    }
+};
+template <class B> struct PlacesRows<ShadeStage<B>> : std::true_type {};
+template <class B> struct StagesTable<ShadeStage<B>> : std::true_type {};
+
 // The slots' own frames: `stride` bytes apart, planes dense.  One buffer resource covers the frames [z0, z1) of the walk (a frame
 // is selected by the scalar offset of the load) plus the format's padding behind them; beyond that the resource returns 0.
 // 32-bit offsets (a walk stays below 2^30 bytes: launch_undistort_rows) keep the address math on full-rate 24-bit multiplies.
@@ -664,6 +723,53 @@ __global__ __launch_bounds__(256) void k_cc16_walk_rows(const SurfEntry* __restr
     fmt.cm = cm, fmt.curve = s_lut_wide;
     if constexpr (SRC == SRC_SURFACES) undistort_walk<PER_SLOT>(a, SurfSource{tab}, fmt);
     else undistort_walk<PER_SLOT>(a, SlotSource<true>{frames, stride}, fmt);
+}
+
+// The four walks above behind the lens-shading correction (lt_set_raw_shading): the same forms and parameters, `table` what the wrapped
+// walk stages -- the raw table (an 8-bit context without one: the identity table), or (CC) the output curve followed by it -- `cm` the
+// matrix (read by the CC forms), `gains` the expanded gain plane and `blk` the four pedestals.  Launched in the wrapped walks' place, in the
+// same stage, whenever a map is set -- the identity included.
+template <int PATTERN, int SRC, bool PER_SLOT, bool CC>
+__global__ __launch_bounds__(256) void k_ls_walk_rows(const SurfEntry* __restrict__ tab, const uint8_t* __restrict__ frames, size_t stride,
+                                                     const int16_t* __restrict__ uxy, const uint16_t* __restrict__ ufrac,
+                                                     const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
+                                                     uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb, int remap,
+                                                     const uint32_t* __restrict__ table, RawColorMat cm, const uint16_t* __restrict__ gains,
+                                                     RawShadeBlack blk) {
+    static_assert(SRC == SRC_SURFACES || SRC == SRC_SLOTS, "a raw Bayer staging frame is dword-aligned");
+    __shared__ alignas(16) uint8_t s_ls[(CC ? 256 : 0) + 1024];
+    const WalkArgs a{uxy, ufrac, SlotTables{sets, &ids}, g, und, und_px, first_slot, n, PER_SLOT ? 1 : fpb, remap};
+    std::conditional_t<CC, ColorStage<ShadeStage<Bayer8Lut<PATTERN>>>, ShadeStage<Bayer8Lut<PATTERN>>> fmt{};
+    fmt.w = g.img_w, fmt.h = g.img_h, fmt.lut = s_ls + (CC ? 256 : 0), fmt.table = table;
+    if constexpr (CC) fmt.cm = cm, fmt.curve = s_ls;
+    fmt.shade_with(gains, blk);
+    if constexpr (SRC == SRC_SURFACES) undistort_walk<PER_SLOT>(a, SurfSource{tab}, fmt);
+    else undistort_walk<PER_SLOT>(a, SlotSource<true>{frames, stride}, fmt);
+}
+template <int PATTERN, int SRC, bool PER_SLOT, bool CC>
+__global__ __launch_bounds__(256) void k_ls16_walk_rows(const SurfEntry* __restrict__ tab, const uint8_t* __restrict__ frames, size_t stride,
+                                                       const int16_t* __restrict__ uxy, const uint16_t* __restrict__ ufrac,
+                                                       const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
+                                                       uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb, int remap,
+                                                       const uint32_t* __restrict__ table, int bits, RawColorMat cm,
+                                                       const uint16_t* __restrict__ gains, RawShadeBlack blk) {
+    static_assert(SRC == SRC_SURFACES || SRC == SRC_SLOTS, "a raw Bayer staging frame is dword-aligned");
+    const WalkArgs a{uxy, ufrac, SlotTables{sets, &ids}, g, und, und_px, first_slot, n, PER_SLOT ? 1 : fpb, remap};
+    std::conditional_t<CC, ColorStage<ShadeStage<Bayer16Lut<PATTERN>>>, ShadeStage<Bayer16Lut<PATTERN>>> fmt{};
+    fmt.w = g.img_w, fmt.h = g.img_h, fmt.lut = s_lut_wide + (CC ? 256 : 0), fmt.table = reinterpret_cast<const uint4*>(table);
+    fmt.bits = bits, fmt.mask = (1u << bits) - 1u;
+    if constexpr (CC) fmt.cm = cm, fmt.curve = s_lut_wide;
+    fmt.shade_with(gains, blk);
+    if constexpr (SRC == SRC_SURFACES) undistort_walk<PER_SLOT>(a, SurfSource{tab}, fmt);
+    else undistort_walk<PER_SLOT>(a, SlotSource<true>{frames, stride}, fmt);
+}
+
+// The expansion of a shading mesh (uint16[4][mh][mw], device memory) into the gain plane of an h x w image with `pattern`: one thread per
+// site, shade_arith.h's gain_at.  A set-up kernel (lt_set_raw_shading), so its one integer division per axis is left as it is.
+__global__ __launch_bounds__(256) void k_shade_expand(const uint16_t* __restrict__ mesh, int mw, int mh, int pattern, uint16_t* __restrict__ plane, int h, int w) {
+    const int x = (int)(blockIdx.x * 256 + threadIdx.x), y = (int)blockIdx.y;
+    if (x >= w) return;
+    plane[(size_t)y * w + x] = (uint16_t)sa::gain_at(mesh + (size_t)ba::phase(pattern, y, x) * mh * mw, mw, mh, y, x, h, w);
 }
 
 // ---- camera rows -> RGB rows ---------------------------------------------------------------------------------------------------
@@ -1014,6 +1120,82 @@ struct RowsBayer16Lut {
         store_rgb1(dst + ((size_t)y * w + x) * 3, post(v));
     }
 };
+// The two table bodies above behind the lens-shading correction (lt_set_raw_shading), for both sample widths (W16: 16-bit words; else bytes,
+// bits = 8 and the table's rows 256 bytes apart, which is what lut_row_wide(8, ..) says): every site shaded with the gain of its position,
+// read from the gain plane `gp` (uint16, w a row), and the pedestal of its phase before it is looked up.  wide: the 16 gains of a row's 16
+// columns are two 16-byte loads (w, x0 and the plane's base are multiples of 16).  Bodies of their own, so that the ones above stay the
+// code they were.
+template <int P, bool W16>
+struct RowsBayerShade {
+    __device__ __forceinline__ static const uint8_t* trow(const uint8_t* lut, int bits, int par_y, int par_x) { return lut + ba::lut_row_wide(bits, P, par_y, par_x); }
+    __device__ __forceinline__ static uint32_t site(const uint8_t* row, int x) {
+        if constexpr (W16) return reinterpret_cast<const uint16_t*>(row)[x];
+        else return row[x];
+    }
+    // site x of the row `row` of the mosaic (row parity py), whose gains are `grow`: shaded and looked up
+    __device__ __forceinline__ static uint32_t one(const uint8_t* row, const uint16_t* grow, int py, int x, const uint8_t* lut, int bits, uint32_t mask,
+                                                   const RawShadeBlack& blk) {
+        const int b = black_of(blk, ba::phase_of(P, py, x & 1));
+        return trow(lut, bits, py, x & 1)[sa::shade(site(row, x) & mask, b, sa::round_term(b), grow[x], (int)mask)];
+    }
+    template <class Post = NoPost>
+    __device__ __forceinline__ static void wide(const Planes& s, const uint8_t* lut, int bits, const uint16_t* gp, const RawShadeBlack& blk, uint8_t* dst,
+                                                int h, int w, int y, int x0, Post post = Post{}) {
+        if (x0 >= w) return;
+        const uint32_t mask = (1u << bits) - 1u;
+        const int cy = ba::tap_pos(y, h), xl = max(x0 - 1, 0), xr = min(x0 + 16, w - 1);
+        uint32_t m[3][4], left[3], right[3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            const uint8_t* row = s.y + (size_t)(cy - 1 + r) * s.pitch;
+            const uint16_t* grow = gp + (size_t)(cy - 1 + r) * w;
+            const int py = (cy - 1 + r) & 1;
+            const uint8_t *ta = trow(lut, bits, py, 0), *tb = trow(lut, bits, py, 1);     // (x0 is even: site 0 of every dword is an even column)
+            const sa::Black2 k = sa::black2(black_of(blk, ba::phase_of(P, py, 0)), black_of(blk, ba::phase_of(P, py, 1)));
+            const uint4 ga = *reinterpret_cast<const uint4*>(grow + x0), gb = *reinterpret_cast<const uint4*>(grow + x0 + 8);
+            if constexpr (W16) {
+                const uint4 q0 = *reinterpret_cast<const uint4*>(row + 2 * x0), q1 = *reinterpret_cast<const uint4*>(row + 2 * x0 + 16);
+                m[r][0] = sa::shade_condition4w(q0.x, q0.y, ga.x, ga.y, k, ta, tb, mask); m[r][1] = sa::shade_condition4w(q0.z, q0.w, ga.z, ga.w, k, ta, tb, mask);
+                m[r][2] = sa::shade_condition4w(q1.x, q1.y, gb.x, gb.y, k, ta, tb, mask); m[r][3] = sa::shade_condition4w(q1.z, q1.w, gb.z, gb.w, k, ta, tb, mask);
+            } else {
+                const uint4 q = *reinterpret_cast<const uint4*>(row + x0);
+                m[r][0] = sa::shade_condition4(q.x, ga.x, ga.y, k, ta, tb); m[r][1] = sa::shade_condition4(q.y, ga.z, ga.w, k, ta, tb);
+                m[r][2] = sa::shade_condition4(q.z, gb.x, gb.y, k, ta, tb); m[r][3] = sa::shade_condition4(q.w, gb.z, gb.w, k, ta, tb);
+            }
+            left[r] = one(row, grow, py, xl, lut, bits, mask, blk);
+            right[r] = one(row, grow, py, xr, lut, bits, mask, blk);
+        }
+        auto at = [&](int r, int j) { return j < 0 ? left[r] : j > 15 ? right[r] : (m[r][j >> 2] >> (8 * (j & 3))) & 255u; };
+        uint32_t px[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+            px[j] = ba::demosaic(at(1, j), at(1, j - 1) + at(1, j + 1), at(0, j) + at(2, j),
+                                 at(0, j - 1) + at(0, j + 1) + at(2, j - 1) + at(2, j + 1), ba::phase(P, cy, j));
+        if (x0 == 0) px[0] = px[1];
+        if (x0 + 16 == w) px[15] = px[14];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) px[j] = post(px[j]);
+        uint32_t d[12];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) pack_rgb4(px + 4 * j, d + 3 * j);
+        store_rgb16(dst + ((size_t)y * w + x0) * 3, d);
+    }
+    template <class Post = NoPost>
+    __device__ __forceinline__ static void any(const Planes& s, const uint8_t* lut, int bits, const uint16_t* gp, const RawShadeBlack& blk, uint8_t* dst,
+                                               int h, int w, int y, int x, Post post = Post{}) {
+        if (x >= w) return;
+        const uint32_t mask = (1u << bits) - 1u;
+        const int cy = ba::tap_pos(y, h), cx = ba::tap_pos(x, w);
+        const uint8_t *up = s.y + (size_t)(cy - 1) * s.pitch, *mid = up + s.pitch, *dn = mid + s.pitch;
+        const uint16_t *gu = gp + (size_t)(cy - 1) * w, *gm = gu + w, *gd = gm + w;
+        const int py = cy & 1;
+        auto u = [&](int i) { return one(up, gu, py ^ 1, cx + i, lut, bits, mask, blk); };
+        auto m = [&](int i) { return one(mid, gm, py, cx + i, lut, bits, mask, blk); };
+        auto d = [&](int i) { return one(dn, gd, py ^ 1, cx + i, lut, bits, mask, blk); };
+        const uint32_t v = ba::demosaic(m(0), m(-1) + m(1), u(0) + d(0), u(-1) + u(1) + d(-1) + d(1), ba::phase(P, cy, cx));
+        store_rgb1(dst + ((size_t)y * w + x) * 3, post(v));
+    }
+};
 // the description of a layout (none for 0, plain RGB: its rows are shown as they are)
 template <int L>
 using RowsOf = std::conditional_t<L <= 2, Rows420<L>, std::conditional_t<L <= 4, Rows422<L - 3>, std::conditional_t<L <= 7, RowsPx<L>, RowsBayer<L - 16>>>>;
@@ -1118,6 +1300,46 @@ __global__ __launch_bounds__(256) void k_cc16_rows_rgb(std::conditional_t<SURF, 
     const ColorPost post{cm, s_lut_wide};
     if constexpr (WIDE) D::wide(p, s_lut_wide + 256, bits, dst, h, w, row, i * 16, post);
     else D::any(p, s_lut_wide + 256, bits, dst, h, w, row, i, post);
+}
+
+// The four row conversions above behind the lens-shading correction (lt_set_raw_shading): RowsBayerShade's bodies in the same launch shapes;
+// `table`, `cm`, `gains`, `blk` as k_ls_walk_rows takes them, table (and curve) staged in 16-byte pieces.
+template <int PATTERN, bool SURF, bool WIDE, bool CC>
+__global__ __launch_bounds__(256) void k_ls_rows_rgb(std::conditional_t<SURF, SurfChunk, DenseFrames> src, uint8_t* __restrict__ rgb,
+                                                    size_t rgb_stride, int w, int r0, int h, const uint32_t* __restrict__ table, RawColorMat cm,
+                                                    const uint16_t* __restrict__ gains, RawShadeBlack blk) {
+    constexpr int THREADS = WIDE ? 64 : 256, CURVE = CC ? 256 : 0;
+    __shared__ alignas(16) uint8_t s_ls[CURVE + 1024];
+    for (int i = threadIdx.x; i < (CURVE + 1024) / 16; i += THREADS) reinterpret_cast<uint4*>(s_ls)[i] = reinterpret_cast<const uint4*>(table)[i];
+    __syncthreads();
+    typedef RowsBayerShade<PATTERN, false> D;
+    Planes p;
+    if constexpr (SURF) p = surf_planes(src.e[blockIdx.z]);
+    else p = RowsBayer<PATTERN>::dense(src.p + (size_t)blockIdx.z * src.stride, h, w);
+    uint8_t* dst = rgb + (size_t)blockIdx.z * rgb_stride;
+    const int i = (int)(blockIdx.x * THREADS + threadIdx.x), row = r0 + (int)blockIdx.y;
+    std::conditional_t<CC, ColorPost, NoPost> post{};
+    if constexpr (CC) post = ColorPost{cm, s_ls};
+    if constexpr (WIDE) D::wide(p, s_ls + CURVE, 8, gains, blk, dst, h, w, row, i * 16, post);
+    else D::any(p, s_ls + CURVE, 8, gains, blk, dst, h, w, row, i, post);
+}
+template <int PATTERN, bool SURF, bool WIDE, bool CC>
+__global__ __launch_bounds__(256) void k_ls16_rows_rgb(std::conditional_t<SURF, SurfChunk, DenseFrames> src, uint8_t* __restrict__ rgb,
+                                                      size_t rgb_stride, int w, int r0, int h, const uint32_t* __restrict__ table, int bits,
+                                                      RawColorMat cm, const uint16_t* __restrict__ gains, RawShadeBlack blk) {
+    constexpr int THREADS = WIDE ? 64 : 256, CURVE = CC ? 256 : 0;
+    for (int i = threadIdx.x; i < CURVE / 16 + (1 << (bits - 2)); i += THREADS) reinterpret_cast<uint4*>(s_lut_wide)[i] = reinterpret_cast<const uint4*>(table)[i];
+    __syncthreads();
+    typedef RowsBayerShade<PATTERN, true> D;
+    Planes p;
+    if constexpr (SURF) p = surf_planes(src.e[blockIdx.z]);
+    else p = RowsBayer16Lut<PATTERN>::dense(src.p + (size_t)blockIdx.z * src.stride, h, w);
+    uint8_t* dst = rgb + (size_t)blockIdx.z * rgb_stride;
+    const int i = (int)(blockIdx.x * THREADS + threadIdx.x), row = r0 + (int)blockIdx.y;
+    std::conditional_t<CC, ColorPost, NoPost> post{};
+    if constexpr (CC) post = ColorPost{cm, s_lut_wide};
+    if constexpr (WIDE) D::wide(p, s_lut_wide + CURVE, bits, gains, blk, dst, h, w, row, i * 16, post);
+    else D::any(p, s_lut_wide + CURVE, bits, gains, blk, dst, h, w, row, i, post);
 }
 
 // Rows [r0, r1) of RGB surfaces -> the same rows of the slots' camera frames (row_bytes = 3 w, dense): a pitched row copy, one
@@ -1556,6 +1778,9 @@ static RawColorMat color_mat(const RawColor& cc) {
     for (int i = 0; i < 9; ++i) m.m[i] = cc.m[i];
     return m;
 }
+// ... and the pedestals of a shading map; the matrix the k_ls* kernels are given (without a colour stage: none, never read)
+static RawShadeBlack shade_black(const RawShade& ls) { return RawShadeBlack{{ls.black[0], ls.black[1], ls.black[2], ls.black[3]}}; }
+static RawColorMat color_mat_of(const RawColor* cc) { return cc ? color_mat(*cc) : RawColorMat{}; }
 
 // pattern (0 .. 3) -> f(std::integral_constant<int, pattern>{}): the 10- / 12-bit raw Bayer layouts, which have kernels of their own and
 // never go through with_layout
@@ -1574,12 +1799,19 @@ static void with_pattern(int pattern, F&& f) {
 template <bool PER_SLOT>
 static void launch_walk(hipStream_t s, dim3 grid, FrameSource src, int layout, YuvCoef k, const int16_t* uxy, const uint16_t* ufrac,
                         const CalTables* sets, const CalIds& ids, FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n, int fpb,
-                        bool any_byte, const uint32_t* raw_lut, const RawColor* cc) {
+                        bool any_byte, const uint32_t* raw_lut, const RawColor* cc, const RawShade* ls) {
     const bool aligned = !any_byte && ((uintptr_t)src.frames & 3) == 0 && (src.stride & 3) == 0 && src.stride < (1u << 30);
     const int remap = xcd_remap();
     if (const int bits = raw_wide_bits(layout)) {        // 10- / 12-bit raw Bayer: always behind its table, 4 << bits bytes of LDS
         with_pattern(layout, [&](auto p) {
             constexpr int P = decltype(p)::value;
+            if (ls) {                        // ... and a shading map: the wrapped walk's LDS, with or without a colour stage
+                auto k_ls = cc ? (src.tab ? k_ls16_walk_rows<P, SRC_SURFACES, PER_SLOT, true> : k_ls16_walk_rows<P, SRC_SLOTS, PER_SLOT, true>)
+                               : (src.tab ? k_ls16_walk_rows<P, SRC_SURFACES, PER_SLOT, false> : k_ls16_walk_rows<P, SRC_SLOTS, PER_SLOT, false>);
+                hipLaunchKernelGGL(k_ls, grid, dim3(256), ((size_t)4 << bits) + (cc ? 256 : 0), s, src.tab, src.frames, src.stride, uxy, ufrac, sets, ids, g, und, und_px, first_slot, n, fpb, remap,
+                                   cc ? cc->table : raw_lut, bits, color_mat_of(cc), ls->plane, shade_black(*ls));
+                return;
+            }
             if (cc) {                        // ... and a colour stage: the curve's 256 bytes in front of the table
                 auto k_cc = src.tab ? k_cc16_walk_rows<P, SRC_SURFACES, PER_SLOT> : k_cc16_walk_rows<P, SRC_SLOTS, PER_SLOT>;
                 hipLaunchKernelGGL(k_cc, grid, dim3(256), ((size_t)4 << bits) + 256, s, src.tab, src.frames, src.stride, uxy, ufrac, sets, ids, g, und, und_px, first_slot, n, fpb, remap, cc->table, bits, color_mat(*cc));
@@ -1596,6 +1828,13 @@ static void launch_walk(hipStream_t s, dim3 grid, FrameSource src, int layout, Y
             hipLaunchKernelGGL(k_walk, grid, dim3(256), 0, s, src.tab, src.frames, src.stride, k, uxy, ufrac, sets, ids, g, und, und_px, first_slot, n, fpb, remap);
         };
         if constexpr (L >= 16) {
+            if (ls) {                        // raw Bayer with a shading map: its walk, behind the raw table (or the identity table) and the colour stage, if any
+                auto k_ls = cc ? (src.tab ? k_ls_walk_rows<L - 16, SRC_SURFACES, PER_SLOT, true> : k_ls_walk_rows<L - 16, SRC_SLOTS, PER_SLOT, true>)
+                               : (src.tab ? k_ls_walk_rows<L - 16, SRC_SURFACES, PER_SLOT, false> : k_ls_walk_rows<L - 16, SRC_SLOTS, PER_SLOT, false>);
+                hipLaunchKernelGGL(k_ls, grid, dim3(256), 0, s, src.tab, src.frames, src.stride, uxy, ufrac, sets, ids, g, und, und_px, first_slot, n, fpb, remap,
+                                   cc ? cc->table : raw_lut, color_mat_of(cc), ls->plane, shade_black(*ls));
+                return;
+            }
             if (cc) {                        // raw Bayer with a colour stage: its walk, behind the raw table or the identity table
                 auto k_cc = src.tab ? k_cc_walk_rows<L - 16, SRC_SURFACES, PER_SLOT> : k_cc_walk_rows<L - 16, SRC_SLOTS, PER_SLOT>;
                 hipLaunchKernelGGL(k_cc, grid, dim3(256), 0, s, src.tab, src.frames, src.stride, uxy, ufrac, sets, ids, g, und, und_px, first_slot, n, fpb, remap, cc->table, color_mat(*cc));
@@ -1614,7 +1853,7 @@ static void launch_walk(hipStream_t s, dim3 grid, FrameSource src, int layout, Y
 }
 
 void launch_undistort_rows(hipStream_t s, FrameSource src, int layout, YuvCoef k, const int16_t* uxy, const uint16_t* ufrac,
-                           FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n, const uint32_t* raw_lut, const RawColor* cc) {
+                           FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n, const uint32_t* raw_lut, const RawColor* cc, const RawShade* ls) {
     if (n <= 0 || g.nrows <= 0) return;
     int fpb = frames_per_thread(n);
     // the slots of a walk are addressed by a 32-bit offset into one buffer resource: a walk stays below 2^30 bytes (one frame
@@ -1622,18 +1861,27 @@ void launch_undistort_rows(hipStream_t s, FrameSource src, int layout, YuvCoef k
     if (!src.tab) fpb = (int)std::max<size_t>(1, std::min<size_t>((size_t)fpb, (((size_t)1 << 30) - 1) / src.stride));
     const dim3 grid((g.img_w + 255) / 256, g.nrows, (n + fpb - 1) / fpb);
     static const bool unaligned = [] { const char* e = LT_EXP_ENV("LT_UNDISTORT_UNALIGNED"); return e && e[0] == '1'; }();   // A/B
-    launch_walk<false>(s, grid, src, layout, k, uxy, ufrac, nullptr, CalIds{}, g, und, und_px, first_slot, n, fpb, unaligned, raw_lut, cc);
+    launch_walk<false>(s, grid, src, layout, k, uxy, ufrac, nullptr, CalIds{}, g, und, und_px, first_slot, n, fpb, unaligned, raw_lut, cc, ls);
 }
 
 // The row conversion of n frames in `layout` (not 0), dense or from surfaces: the 16-column kernel where the width and every base and
 // pitch of the launch (`bits`: all of them ORed) are multiples of 16, the byte-wise one otherwise.
 template <bool SURF, class Src>
 static void launch_rows_to_rgb(hipStream_t s, int layout, const Src& src, size_t bits, YuvCoef k, uint8_t* rgb, size_t rgb_stride, int h, int w,
-                               int r0, int r1, int n, const uint32_t* raw_lut, const RawColor* cc) {
+                               int r0, int r1, int n, const uint32_t* raw_lut, const RawColor* cc, const RawShade* ls) {
     if (const int depth = raw_wide_bits(layout)) {       // 10- / 12-bit raw Bayer: always behind its table, the same two launch shapes
         with_pattern(layout, [&](auto p) {
             constexpr int P = decltype(p)::value;
             const unsigned rows = (unsigned)(r1 - r0);
+            if (ls) {                        // ... and a shading map
+                const bool wide = (w & 15) == 0 && (bits & 15) == 0;
+                const dim3 grid(wide ? (unsigned)((w / 16 + 63) / 64) : (unsigned)((w + 255) / 256), rows, (unsigned)n), block(wide ? 64 : 256);
+                auto k_ls = cc ? (wide ? k_ls16_rows_rgb<P, SURF, true, true> : k_ls16_rows_rgb<P, SURF, false, true>)
+                               : (wide ? k_ls16_rows_rgb<P, SURF, true, false> : k_ls16_rows_rgb<P, SURF, false, false>);
+                hipLaunchKernelGGL(k_ls, grid, block, ((size_t)4 << depth) + (cc ? 256 : 0), s, src, rgb, rgb_stride, w, r0, h, cc ? cc->table : raw_lut, depth,
+                                   color_mat_of(cc), ls->plane, shade_black(*ls));
+                return;
+            }
             if (cc) {                        // ... and a colour stage
                 if ((w & 15) == 0 && (bits & 15) == 0)
                     hipLaunchKernelGGL((k_cc16_rows_rgb<P, SURF, true>), dim3((unsigned)((w / 16 + 63) / 64), rows, (unsigned)n), dim3(64), ((size_t)4 << depth) + 256, s,
@@ -1658,6 +1906,14 @@ static void launch_rows_to_rgb(hipStream_t s, int layout, const Src& src, size_t
             typedef RowsOf<L> D;
             const unsigned rows = (unsigned)(D::CHROMA_ROWS ? ((r1 + 1) >> 1) - (r0 >> 1) : r1 - r0);
             if constexpr (L >= 16) {
+                if (ls) {                    // raw Bayer with a shading map: its bodies, the same two launch shapes
+                    const bool wide = (w & 15) == 0 && (bits & 15) == 0;
+                    const dim3 grid(wide ? (unsigned)((w / 16 + 63) / 64) : (unsigned)((w + 255) / 256), rows, (unsigned)n), block(wide ? 64 : 256);
+                    auto k_ls = cc ? (wide ? k_ls_rows_rgb<L - 16, SURF, true, true> : k_ls_rows_rgb<L - 16, SURF, false, true>)
+                                   : (wide ? k_ls_rows_rgb<L - 16, SURF, true, false> : k_ls_rows_rgb<L - 16, SURF, false, false>);
+                    hipLaunchKernelGGL(k_ls, grid, block, 0, s, src, rgb, rgb_stride, w, r0, h, cc ? cc->table : raw_lut, color_mat_of(cc), ls->plane, shade_black(*ls));
+                    return;
+                }
                 if (cc) {                    // raw Bayer with a colour stage: its bodies, the same two launch shapes
                     if ((w & 15) == 0 && (bits & 15) == 0)
                         hipLaunchKernelGGL((k_cc_rows_rgb<L - 16, SURF, true>), dim3((unsigned)((w / 16 + 63) / 64), rows, (unsigned)n), dim3(64), 0, s,
@@ -1688,10 +1944,14 @@ static void launch_rows_to_rgb(hipStream_t s, int layout, const Src& src, size_t
 }
 
 void launch_yuv_rows_to_rgb(hipStream_t s, int layout, const uint8_t* yuv, size_t yuv_stride, YuvCoef k, uint8_t* rgb,
-                            size_t rgb_stride, int h, int w, int r0, int r1, int n, const uint32_t* raw_lut, const RawColor* cc) {
+                            size_t rgb_stride, int h, int w, int r0, int r1, int n, const uint32_t* raw_lut, const RawColor* cc, const RawShade* ls) {
     if (n <= 0 || r1 <= r0) return;
     launch_rows_to_rgb<false>(s, layout, DenseFrames{yuv, yuv_stride}, yuv_stride | rgb_stride | (size_t)(uintptr_t)yuv | (size_t)(uintptr_t)rgb, k,
-                              rgb, rgb_stride, h, w, r0, r1, n, raw_lut, cc);
+                              rgb, rgb_stride, h, w, r0, r1, n, raw_lut, cc, ls);
+}
+
+void launch_shade_expand(hipStream_t s, const uint16_t* mesh, int mw, int mh, int pattern, uint16_t* plane, int h, int w) {
+    hipLaunchKernelGGL(k_shade_expand, dim3((unsigned)((w + 255) / 256), (unsigned)h), dim3(256), 0, s, mesh, mw, mh, pattern & 3, plane, h, w);
 }
 
 void launch_write_surf_entries(hipStream_t s, SurfEntry* tab, int first, const SurfEntry* entries, int n) {
@@ -1704,7 +1964,7 @@ void launch_write_surf_entries(hipStream_t s, SurfEntry* tab, int first, const S
 }
 
 void launch_surf_rows_to_rgb(hipStream_t s, int layout, const SurfEntry* entries, YuvCoef k, uint8_t* rgb, size_t rgb_stride, int h, int w,
-                             int r0, int r1, int n, const uint32_t* raw_lut, const RawColor* cc) {
+                             int r0, int r1, int n, const uint32_t* raw_lut, const RawColor* cc, const RawShade* ls) {
     if (n <= 0 || r1 <= r0) return;
     for (int i = 0; i < n; i += SurfChunk::N) {
         const int m = std::min(n - i, (int)SurfChunk::N);
@@ -1724,7 +1984,7 @@ void launch_surf_rows_to_rgb(hipStream_t s, int layout, const SurfEntry* entries
             else
                 hipLaunchKernelGGL(k_surf_copy_rows<false>, dim3((unsigned)((row_bytes + 255) / 256), (unsigned)(r1 - r0), (unsigned)m), dim3(256), 0, s, ch, dst, rgb_stride, row_bytes, r0);
         } else {
-            launch_rows_to_rgb<true>(s, layout, ch, bits, k, dst, rgb_stride, h, w, r0, r1, m, raw_lut, cc);
+            launch_rows_to_rgb<true>(s, layout, ch, bits, k, dst, rgb_stride, h, w, r0, r1, m, raw_lut, cc, ls);
         }
     }
 }
@@ -1754,13 +2014,13 @@ static CalIds pack_ids(const uint8_t* ids, int m) {
 }
 
 void launch_undistort_cal(hipStream_t s, FrameSource src, int layout, YuvCoef k, const CalTables* sets, const uint8_t* ids,
-                          FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n, const uint32_t* raw_lut, const RawColor* cc) {
+                          FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n, const uint32_t* raw_lut, const RawColor* cc, const RawShade* ls) {
     if (n <= 0 || g.nrows <= 0) return;
     for (int i = 0; i < n; i += CalIds::N) {
         const int m = std::min(n - i, (int)CalIds::N);
         const dim3 grid((g.img_w + 255) / 256, g.nrows, m);
         const FrameSource part = src.tab ? src : FrameSource::slots(src.frames + (size_t)i * src.stride, src.stride);
-        launch_walk<true>(s, grid, part, layout, k, nullptr, nullptr, sets, pack_ids(ids + i, m), g, und, und_px, first_slot + i, m, 1, false, raw_lut, cc);
+        launch_walk<true>(s, grid, part, layout, k, nullptr, nullptr, sets, pack_ids(ids + i, m), g, und, und_px, first_slot + i, m, 1, false, raw_lut, cc, ls);
     }
 }
 

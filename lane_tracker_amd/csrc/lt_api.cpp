@@ -28,6 +28,7 @@
 #include "front_arith.h"
 #include "lt_ctx.h"
 #include "resize_arith.h"
+#include "shade_arith.h"
 
 using namespace lt;
 
@@ -718,6 +719,7 @@ void lt_destroy(lt_ctx* c) {
     dev_free(c->d_raw_lut);
     dev_free(c->d_raw_lut_wide);
     dev_free(c->d_raw_cc);
+    dev_free(c->d_raw_gain);
     dev_free(c->d_oxy);
     dev_free(c->d_ofrac);
     for (size_t i = 1; i < c->cal.size(); ++i) {     // (set 0's tables are the ones above)
@@ -941,6 +943,9 @@ static int write_raw_color(lt_ctx* c) {
     return rc;
 }
 
+static int write_identity_lut(lt_ctx* c);              // (lens shading, below)
+static void drop_raw_shading(lt_ctx* c);
+
 int lt_set_input_format(lt_ctx* c, int layout, const int32_t* coeffs) {
     if (!c) return fail(LT_ERR_INVALID, "null context");
     int rc;
@@ -960,6 +965,7 @@ int lt_set_input_format(lt_ctx* c, int layout, const int32_t* coeffs) {
     if ((rc = sync_all(c))) return rc;
     if (!is_bayer(layout)) c->raw_lut_set = false;     // a raw table belongs to raw Bayer input
     c->raw_color_set = false;                          // ... and a colour stage to the layout it was set for
+    drop_raw_shading(c);                               // ... as a shading map does
     if (layout == LT_INPUT_RGB) {
         dev_free(c->d_yuv);
     } else {
@@ -997,6 +1003,7 @@ int lt_set_raw_lut(lt_ctx* c, const uint8_t* lut) {
     }
     c->raw_lut_set = lut != nullptr;
     std::fill(c->front_ok.begin(), c->front_ok.end(), (uint8_t)0);
+    if (!lut && c->raw_shade_set && (rc = write_identity_lut(c))) return rc;       // (the shading kernels always stage a table)
     return c->raw_color_set ? write_raw_color(c) : LT_OK;       // (the colour stage's kernels read the table from its buffer)
 }
 
@@ -1057,6 +1064,101 @@ int lt_get_raw_color(lt_ctx* c, int16_t* ccm, uint8_t* curve, int* is_set) {
     return LT_OK;
 }
 
+// ---- lens shading (lt_set_raw_shading) ---------------------------------------------------------------------------------------
+static int check_shading(int layout, int mesh_w, int mesh_h, const int32_t* black) {
+    if (mesh_w < sa::MESH_MIN || mesh_w > sa::MESH_MAX || mesh_h < sa::MESH_MIN || mesh_h > sa::MESH_MAX)
+        return fail(LT_ERR_INVALID, "a shading mesh has 2 .. 64 nodes a side, got %d x %d", mesh_w, mesh_h);
+    const int smax = is_bayer_wide(layout) ? (1 << raw_bits(layout)) - 1 : 255;
+    for (int p = 0; black && p < 4; ++p)
+        if (black[p] < 0 || black[p] > smax) return fail(LT_ERR_INVALID, "black[%d] = %d is outside 0 .. %d", p, (int)black[p], smax);
+    return LT_OK;
+}
+// mesh (host) -> a gain plane of h x w sites and 16 bytes of padding at *plane (device memory, allocated here where it is null), on `st`
+static int expand_mesh(hipStream_t st, const uint16_t* mesh, int mesh_w, int mesh_h, int layout, int h, int w, uint16_t** plane) {
+    const size_t nodes = (size_t)4 * mesh_w * mesh_h;
+    uint16_t* d_mesh = nullptr;
+    int rc;
+    if ((rc = dev_alloc(&d_mesh, nodes))) return rc;
+    if (!*plane && (rc = dev_alloc(plane, (size_t)h * w + 8))) { dev_free(d_mesh); return rc; }
+    hipError_t e = hipMemcpyAsync(d_mesh, mesh, nodes * sizeof(uint16_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemsetAsync(*plane + (size_t)h * w, 0, 16, st);
+    if (e == hipSuccess) {
+        launch_shade_expand(st, d_mesh, mesh_w, mesh_h, layout & 3, *plane, h, w);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    dev_free(d_mesh);
+    if (e != hipSuccess) return fail(LT_ERR_HIP, "expanding the shading mesh failed: %s", hipGetErrorString(e));
+    return LT_OK;
+}
+// the identity table into d_raw_lut: what the k_ls* kernels of an 8-bit context without a raw table stage; nothing in flight
+static int write_identity_lut(lt_ctx* c) {
+    int rc;
+    if (!c->d_raw_lut && (rc = dev_alloc(&c->d_raw_lut, 256))) return rc;
+    uint8_t ident[1024];
+    for (int i = 0; i < 1024; ++i) ident[i] = (uint8_t)(i & 255);
+    HIP_TRY(hipMemcpy(c->d_raw_lut, ident, sizeof ident, hipMemcpyHostToDevice));
+    return LT_OK;
+}
+static void drop_raw_shading(lt_ctx* c) {
+    c->raw_shade_set = false;
+    dev_free(c->d_raw_gain);
+    c->raw_shade = {};
+    c->raw_mesh.clear();
+    c->raw_mesh_w = c->raw_mesh_h = 0;
+}
+
+// The shading map: as the colour stage, a setting between runs -- behind everything in flight, and the slots' front ends are marked as not
+// run.  enable = 0 removes it (mesh and black are not read) and frees the gain plane.
+int lt_set_raw_shading(lt_ctx* c, const uint16_t* mesh, int mesh_w, int mesh_h, const int32_t* black, int enable) {
+    if (!c) return fail(LT_ERR_INVALID, "null context");
+    if (!is_raw_mosaic(c->in_layout)) return fail(LT_ERR_STATE, "lens shading corrects raw Bayer input: this context's input format is another layout");
+    int rc;
+    if (enable) {
+        if (!mesh) return fail(LT_ERR_INVALID, "null mesh");
+        if ((rc = check_shading(c->in_layout, mesh_w, mesh_h, black))) return rc;
+    }
+    if ((rc = set_device(c))) return rc;
+    if ((rc = sync_all(c))) return rc;
+    if (enable) {
+        if (is_bayer(c->in_layout) && !c->raw_lut_set && (rc = write_identity_lut(c))) return rc;
+        if ((rc = expand_mesh(c->stream, mesh, mesh_w, mesh_h, c->in_layout, c->calib.img_h, c->calib.img_w, &c->d_raw_gain))) {
+            // the plane of a map that was set may hold part of the new one by now: no map is better than one the host and the device disagree on
+            drop_raw_shading(c);
+            std::fill(c->front_ok.begin(), c->front_ok.end(), (uint8_t)0);
+            return rc;
+        }
+        c->raw_mesh.assign(mesh, mesh + (size_t)4 * mesh_w * mesh_h);
+        c->raw_mesh_w = mesh_w, c->raw_mesh_h = mesh_h;
+        c->raw_shade.plane = c->d_raw_gain;
+        for (int p = 0; p < 4; ++p) c->raw_shade.black[p] = black ? black[p] : 0;
+        c->raw_shade_set = true;
+    } else {
+        drop_raw_shading(c);
+    }
+    std::fill(c->front_ok.begin(), c->front_ok.end(), (uint8_t)0);
+    return LT_OK;
+}
+
+int lt_get_raw_shading(lt_ctx* c, uint16_t* mesh, int* mesh_w, int* mesh_h, int32_t* black, int* is_set) {
+    if (!c) return fail(LT_ERR_INVALID, "null context");
+    if (is_set) *is_set = c->raw_shade_set ? 1 : 0;
+    if (mesh_w) *mesh_w = c->raw_mesh_w;
+    if (mesh_h) *mesh_h = c->raw_mesh_h;
+    if (mesh && c->raw_shade_set) std::memcpy(mesh, c->raw_mesh.data(), c->raw_mesh.size() * sizeof(uint16_t));
+    if (black && c->raw_shade_set) std::memcpy(black, c->raw_shade.black, sizeof c->raw_shade.black);
+    return LT_OK;
+}
+
+int lt_get_raw_shading_plane(lt_ctx* c, uint16_t* plane) {
+    if (!c || !plane) return fail(LT_ERR_INVALID, "null argument");
+    if (!c->raw_shade_set) return fail(LT_ERR_STATE, "this context has no shading map (lt_set_raw_shading)");
+    int rc;
+    if ((rc = set_device(c))) return rc;
+    HIP_TRY(hipMemcpy(plane, c->d_raw_gain, (size_t)c->calib.img_h * c->calib.img_w * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    return LT_OK;
+}
+
 int lt_get_raw_lut_wide(lt_ctx* c, uint8_t* lut, size_t entries) {
     int rc = check_wide(c, entries);
     if (rc) return rc;
@@ -1096,7 +1198,7 @@ static inline int chroma_hi(int r0, int r1) { return r1 > r0 ? (r1 - 1) / 2 + 1 
 // rows [r0, r1) of the staging frames of slots [first, first + n) -> the same rows of their RGB camera frames, on `st`
 static void yuv_convert(lt_ctx* c, hipStream_t st, int first, int n, int r0, int r1) {
     launch_yuv_rows_to_rgb(st, c->in_layout, slot_yuv(c, first), c->yuv_stride, yuv_coef_of(c), slot_frame(c, first), c->frame_bytes,
-                           c->calib.img_h, c->calib.img_w, r0, r1, n, raw_lut_of(c), raw_color_of(c));
+                           c->calib.img_h, c->calib.img_w, r0, r1, n, raw_lut_of(c), raw_color_of(c), raw_shade_of(c));
 }
 
 // ---- input frames of another size (lt_set_input_size) ------------------------------------------------------------------------
@@ -1759,7 +1861,7 @@ int lt_device_frames_rest(lt_ctx* c, int first, int n, const int32_t* rows4) {
     const int32_t* r = rows4 ? rows4 : whole;
     for (int k = 0; k < 4; k += 2)
         launch_surf_rows_to_rgb(c->copy, c->in_layout, &c->surf[(size_t)first], yuv_coef_of(c), slot_frame(c, first), c->frame_bytes,
-                                c->calib.img_h, c->calib.img_w, r[k], r[k + 1], n, raw_lut_of(c), raw_color_of(c));
+                                c->calib.img_h, c->calib.img_w, r[k], r[k + 1], n, raw_lut_of(c), raw_color_of(c), raw_shade_of(c));
     HIP_TRY(hipGetLastError());
     if ((rc = note_range(c->readers, c->copy, first, first + n))) return rc;      // it reads the surfaces and writes the camera frames: the next upload waits
     if (!rows4) mark_frames(c, first, n, 1);
@@ -2435,8 +2537,8 @@ static int mask_run_impl(lt_ctx* c, int first, int n, const lt_filter_params* p,
                   const FrameSource src = att ? FrameSource::surfaces(c->d_surf)
                                           : c->in_layout != LT_INPUT_RGB ? FrameSource::slots(slot_yuv(c, a), c->yuv_stride)
                                                                          : FrameSource::slots(slot_frame(c, a), c->frame_bytes);
-                  if (mixed) launch_undistort_cal(st, src, c->in_layout, yuv_coef_of(c), c->d_cal, &c->slot_cal[(size_t)a], c->fe, c->d_und, c->und_px, a, b - a, raw_lut_of(c), raw_color_of(c));
-                  else launch_undistort_rows(st, src, c->in_layout, yuv_coef_of(c), cs.d_uxy, cs.d_ufrac, c->fe, c->d_und, c->und_px, a, b - a, raw_lut_of(c), raw_color_of(c));
+                  if (mixed) launch_undistort_cal(st, src, c->in_layout, yuv_coef_of(c), c->d_cal, &c->slot_cal[(size_t)a], c->fe, c->d_und, c->und_px, a, b - a, raw_lut_of(c), raw_color_of(c), raw_shade_of(c));
+                  else launch_undistort_rows(st, src, c->in_layout, yuv_coef_of(c), cs.d_uxy, cs.d_ufrac, c->fe, c->d_und, c->und_px, a, b - a, raw_lut_of(c), raw_color_of(c), raw_shade_of(c));
               } }
             { int mrc = n == 1 ? note_range_frame(c, c->readers, st, f0, f0 + m) : note_range(c->readers, st, f0, f0 + m); if (mrc) return mrc; }
             { StageScope t(c, ST_WARP_SPLIT, st);
@@ -2933,6 +3035,58 @@ int lt_raw_to_rgb_color(lt_ctx* c, const void* frame, int h, int w, int layout, 
     dev_free(d_in);
     dev_free(d_out);
     dev_free(d_cc);
+    if (e != hipSuccess) return fail(LT_ERR_HIP, "raw Bayer conversion failed: %s", hipGetErrorString(e));
+    return LT_OK;
+}
+
+// lt_raw_to_rgb_color behind a shading map (mesh = null: none); without ccm and curve there is no colour stage either -- the k_ls* row
+// kernels alone, in all their forms
+int lt_raw_to_rgb_shaded(lt_ctx* c, const void* frame, int h, int w, int layout, const uint8_t* lut, size_t lut_entries, const int16_t* ccm,
+                         const uint8_t* curve, const uint16_t* mesh, int mesh_w, int mesh_h, const int32_t* black, uint8_t* out_rgb) {
+    if (!mesh) return lt_raw_to_rgb_color(c, frame, h, w, layout, lut, lut_entries, ccm, curve, out_rgb);
+    if (!c || !frame || !out_rgb) return fail(LT_ERR_INVALID, "null argument");
+    if (!is_raw_mosaic(layout)) return fail(LT_ERR_INVALID, "lt_raw_to_rgb_shaded takes the raw Bayer layouts (16 .. 19, 32 .. 35, 48 .. 51)");
+    const bool wide = is_bayer_wide(layout), color = ccm || curve;
+    const size_t entries = wide ? (size_t)1 << raw_bits(layout) : 256;
+    if (lut && lut_entries != entries) return fail(LT_ERR_INVALID, "the raw table of this layout has %zu entries per colour phase, got %zu", entries, lut_entries);
+    int rc = check_bayer_size(h, w);
+    if (rc) return rc;
+    if (h > 16384 || w > 16384) return fail(LT_ERR_INVALID, "bad image size (at most 16384 x 16384)");
+    if ((rc = check_shading(layout, mesh_w, mesh_h, black))) return rc;
+    if ((rc = set_device(c))) return rc;
+    const size_t px = (size_t)h * w, in_bytes = wide ? px * 2 : px;
+    std::vector<uint8_t> def;
+    if (!lut && wide) {
+        def.resize(4 * entries);
+        default_wide_table(raw_bits(layout), def.data());
+        lut = def.data();
+    }
+    static const int16_t ident[9] = {1024, 0, 0, 0, 1024, 0, 0, 0, 1024};
+    uint8_t line[256];
+    for (int i = 0; i < 256; ++i) line[i] = curve ? curve[i] : (uint8_t)i;
+    uint8_t *d_in = nullptr, *d_out = nullptr;
+    uint32_t* d_cc = nullptr;                // curve, then table; without a colour stage the kernels are handed the table behind the curve
+    RawColor cc = {};
+    RawShade ls = {};
+    uint16_t* d_gain = nullptr;
+    if ((rc = dev_alloc(&d_in, in_bytes)) || (rc = dev_alloc(&d_out, px * 3)) || (rc = make_raw_color(lut, 4 * entries, ccm ? ccm : ident, line, &d_cc, &cc)) ||
+        (rc = expand_mesh(c->stream, mesh, mesh_w, mesh_h, layout, h, w, &d_gain))) {
+        dev_free(d_in); dev_free(d_out); dev_free(d_cc); dev_free(d_gain);
+        return rc;
+    }
+    ls.plane = d_gain;
+    for (int p = 0; p < 4; ++p) ls.black[p] = black ? black[p] : 0;
+    hipError_t e = hipMemcpyAsync(d_in, frame, in_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        launch_yuv_rows_to_rgb(c->stream, layout, d_in, in_bytes, YuvCoef{}, d_out, px * 3, h, w, 0, h, 1, d_cc + 64, color ? &cc : nullptr, &ls);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out_rgb, d_out, px * 3, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    dev_free(d_in);
+    dev_free(d_out);
+    dev_free(d_cc);
+    dev_free(d_gain);
     if (e != hipSuccess) return fail(LT_ERR_HIP, "raw Bayer conversion failed: %s", hipGetErrorString(e));
     return LT_OK;
 }

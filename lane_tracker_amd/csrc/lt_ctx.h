@@ -180,6 +180,15 @@ struct lt_ctx {
     lt::RawColor raw_cc = {};                     // what the launches take: the matrix widened, table = d_raw_cc
     uint32_t* d_raw_cc = nullptr;
     size_t raw_cc_bytes = 0;
+    // The lens-shading correction of a raw Bayer context (lt_set_raw_shading): mesh and pedestals on the host, and in device memory the gain
+    // plane that k_shade_expand makes of the mesh -- uint16[img_h][img_w] and 16 bytes of padding, allocated by the first set, freed when the
+    // map is removed: a context that never sets one allocates nothing.  raw_shade_set says which kernels are launched: the map's content
+    // never does.  An 8-bit context without a raw table then keeps the identity table in d_raw_lut: the k_ls* kernels always stage one.
+    bool raw_shade_set = false;
+    std::vector<uint16_t> raw_mesh;
+    int raw_mesh_w = 0, raw_mesh_h = 0;
+    lt::RawShade raw_shade = {};                  // what the launches take: plane = d_raw_gain, the pedestals
+    uint16_t* d_raw_gain = nullptr;
     // Input frames of another size (lt_set_input_size): src_w x src_h RGB frames, resized on the device to the calibration's size
     // (cv2.resize, INTER_LINEAR).  Per slot a staging frame of src_bytes = src_h * src_w * 3 bytes, src_stride apart (a multiple of 16
     // with at least 16 bytes of padding behind every frame: k_resize_rows reads aligned dwords); the uploads copy source rows into it
@@ -376,9 +385,12 @@ inline bool is_bayer_wide(int layout) { return raw_bits(layout) != 0; }
 // any raw mosaic, whatever its samples: what is about the mosaic (sizes, row runs, input only) and not about bytes
 inline bool is_raw_mosaic(int layout) { return is_bayer(layout) || is_bayer_wide(layout); }
 // the raw table the front end and the row conversion of `c` are launched with: null without one (a wide context always has one)
-inline const uint32_t* raw_lut_of(const lt_ctx* c) { return is_bayer_wide(c->in_layout) ? c->d_raw_lut_wide : c->raw_lut_set ? c->d_raw_lut : nullptr; }
+// (with a shading map an 8-bit context always brings one: the identity where none is set, which lt_set_raw_shading keeps in d_raw_lut)
+inline const uint32_t* raw_lut_of(const lt_ctx* c) { return is_bayer_wide(c->in_layout) ? c->d_raw_lut_wide : c->raw_lut_set || c->raw_shade_set ? c->d_raw_lut : nullptr; }
 // the colour stage they are launched with: null without one
 inline const lt::RawColor* raw_color_of(const lt_ctx* c) { return c->raw_color_set ? &c->raw_cc : nullptr; }
+// the shading map they are launched with: null without one
+inline const lt::RawShade* raw_shade_of(const lt_ctx* c) { return c->raw_shade_set ? &c->raw_shade : nullptr; }
 inline int packed_bpp(int layout) {
     return layout == LT_INPUT_RGB || layout == LT_INPUT_BGR ? 3 : layout == LT_INPUT_RGBA || layout == LT_INPUT_BGRA ? 4
            : layout == LT_INPUT_YUY2 || layout == LT_INPUT_UYVY || is_bayer_wide(layout) ? 2 : is_bayer(layout) ? 1 : 0;

@@ -54,6 +54,7 @@ class _GroupMember(LaneTracker):
     process_batch = process_stream = warm = _not_owned
     set_raw_lut = _not_owned        # (one table for the whole group: LaneTrackerGroup.set_raw_lut)
     set_raw_color = _not_owned      # (... and one colour stage: LaneTrackerGroup.set_raw_color)
+    set_raw_shading = _not_owned    # (... and one lens-shading map: LaneTrackerGroup.set_raw_shading)
     _owns_context = False           # close() leaves the group's context to LaneTrackerGroup.close
 
 
@@ -108,7 +109,7 @@ class LaneTrackerGroup:
 
     def __init__(self, k, img_size, warped_size, cam_matrix, dist_coeffs, warp_matrices, mpp_conversion, n_fail=8, n_reset=4,
                  n_average=2, print_frame_count=False, device=0, *, pixel_format='rgb', yuv_matrix='bt601', calibrations=None,
-                 input_size=None, raw_lut=None, raw_ccm=None, raw_curve=None):
+                 input_size=None, raw_lut=None, raw_ccm=None, raw_curve=None, raw_shading=None):
         k = int(k)
         if k < 1:
             raise ValueError("a group needs at least one stream")
@@ -127,6 +128,7 @@ class LaneTrackerGroup:
             self._frame_shape = (self._resize_from[1], self._resize_from[0], 3)
         self._raw_lut = _native.effective_raw_lut(raw_lut, pixel_format)       # one raw table for the whole group (LaneTracker's raw_lut)
         self._raw_ccm, self._raw_curve = _native.checked_raw_color(raw_ccm, raw_curve, pixel_format)     # ... and one colour stage
+        self._raw_shading = _native.checked_raw_shading(raw_shading, pixel_format)      # ... and one lens-shading map
         self._ctx = _native.Context(img_size, warped_size, cam_matrix, dist_coeffs, warp_matrices[0], device=device, capacity=4 * k)
         self._tick = 0
         self._overlay_sets = set()           # the calibration sets whose overlay a member has configured
@@ -139,6 +141,8 @@ class LaneTrackerGroup:
                 self._ctx.set_raw_lut(self._raw_lut)
             if self._raw_ccm is not None or self._raw_curve is not None:
                 self._ctx.set_raw_color(self._raw_ccm, self._raw_curve)
+            if self._raw_shading is not None:
+                self._ctx.set_raw_shading(self._raw_shading)
             # the calibration sets of the context: 0 is the group's own, one more for every distinct calibration among the streams
             sets = {_table_key(dict(cam_matrix=cam_matrix, dist_coeffs=dist_coeffs, warp_matrices=warp_matrices)): 0}
             self._cal_ids = []
@@ -153,7 +157,8 @@ class LaneTrackerGroup:
                                                   c["mpp_conversion"], n_fail=n_fail, n_reset=n_reset, n_average=n_average,
                                                   print_frame_count=print_frame_count, device=device,
                                                   pixel_format=pixel_format, yuv_matrix=yuv_matrix, input_size=input_size,
-                                                  raw_lut=self._raw_lut, raw_ccm=self._raw_ccm, raw_curve=self._raw_curve))
+                                                  raw_lut=self._raw_lut, raw_ccm=self._raw_ccm, raw_curve=self._raw_curve,
+                                                  raw_shading=self._raw_shading))
         except BaseException:
             self.close()
             raise
@@ -200,6 +205,24 @@ class LaneTrackerGroup:
         self._raw_ccm, self._raw_curve = ccm, curve
         for t in self.trackers:
             t._raw_ccm, t._raw_curve = ccm, curve
+            t._resident = None
+
+    @property
+    def raw_shading(self):
+        """The group's lens-shading map, a utils.RawShading (a copy), or None (`set_raw_shading`)."""
+        s = self._raw_shading
+        return None if s is None else type(s)(s.mesh.copy(), s.black.copy())
+
+    def set_raw_shading(self, shading):
+        """Another lens-shading map for every stream of the group, or None for none, between `process()` calls
+        (LaneTracker.set_raw_shading)."""
+        shading = _native.checked_raw_shading(shading, self.pixel_format)
+        if not _native.raw_bits(self.pixel_format):
+            return
+        self._ctx.set_raw_shading(shading)
+        self._raw_shading = shading
+        for t in self.trackers:
+            t._raw_shading = shading
             t._resident = None
 
     def calibration_count(self):

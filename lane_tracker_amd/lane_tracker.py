@@ -66,7 +66,7 @@ class LaneTracker(StreamPipeline):
 
     def __init__(self, img_size, warped_size, cam_matrix, dist_coeffs, warp_matrices, mpp_conversion,
                  n_fail=8, n_reset=4, n_average=2, print_frame_count=False, device=0, *, pixel_format='rgb', yuv_matrix='bt601',
-                 input_size=None, raw_lut=None, raw_ccm=None, raw_curve=None):
+                 input_size=None, raw_lut=None, raw_ccm=None, raw_curve=None, raw_shading=None):
         # the camera's pixel format: 'rgb' frames (H, W, 3), YUV 4:2:0 as decoders hand it out -- 'nv12' / 'i420' frames
         # (H * 3 // 2, W) -- or packed 4:2:2 as cameras and capture cards do -- 'yuy2' / 'uyvy' frames (H, W, 2) -- converted on the
         # device with `yuv_matrix` ('bt601', 'bt709') -- or what users' own software holds: 'bgr' frames (H, W, 3) (OpenCV's order),
@@ -90,6 +90,9 @@ class LaneTracker(StreamPipeline):
         # raw Bayer only: the colour stage behind the demosaic -- a colour-correction matrix, int16 (3, 3) in Q10 (utils.raw_ccm), then an
         # output curve, u8 (256,) (utils.raw_curve) -- on the device; giving either turns the stage on (the other: the identity)
         self._raw_ccm, self._raw_curve = _native.checked_raw_color(raw_ccm, raw_curve, pixel_format)
+        # raw Bayer only: the lens-shading map in front of the raw table -- a utils.RawShading (utils.raw_shading: a mesh of gains and the
+        # pedestals) --, every sample corrected by the gain of its position on the device; configuration, not state
+        self._raw_shading = _native.checked_raw_shading(raw_shading, pixel_format)
         self.img_size = img_size
         self.warped_size = warped_size
         self.cam_matrix = cam_matrix
@@ -165,6 +168,8 @@ class LaneTracker(StreamPipeline):
                 ctx.set_raw_lut(self._raw_lut)
             if self._raw_ccm is not None or self._raw_curve is not None:
                 ctx.set_raw_color(self._raw_ccm, self._raw_curve)
+            if self._raw_shading is not None:
+                ctx.set_raw_shading(self._raw_shading)
         except BaseException:
             ctx.close()
             raise
@@ -215,6 +220,26 @@ class LaneTracker(StreamPipeline):
         self._ctx.set_raw_color(ccm, curve, enable=ccm is not None or curve is not None)
         self._raw_ccm, self._raw_curve = ccm, curve
         self._resident = None       # the camera frame the slot holds was converted with the stage before
+
+    @property
+    def raw_shading(self):
+        """The lens-shading map of a raw Bayer tracker, a utils.RawShading (a copy), or None (`set_raw_shading`)."""
+        s = self._raw_shading
+        return None if s is None else type(s)(s.mesh.copy(), s.black.copy())
+
+    def set_raw_shading(self, shading):
+        """Another lens-shading map -- `utils.raw_shading(...)` -- or None for none, between frames or windows: the samples of the frames
+        processed from now on are corrected with it before the raw table.  It waits for the device; not a per-frame call, and not
+        allowed inside an active `process_stream()`.  ValueError for a tracker whose pixel format is not raw Bayer, a mesh of another
+        shape or dtype, a black value above the format's largest sample."""
+        shading = _native.checked_raw_shading(shading, self.pixel_format)
+        if not _native.raw_bits(self.pixel_format):      # (None on a tracker that takes no map: nothing to do)
+            return
+        if self._in_stream:
+            raise RuntimeError("set_raw_shading() inside an active process_stream(): exhaust or close the generator first")
+        self._ctx.set_raw_shading(shading)
+        self._raw_shading = shading
+        self._resident = None       # the camera frame the slot holds was converted with the map before
 
     def _check_frame(self, img, window=False):
         """A 4:2:0 / 4:2:2 tracker takes frames of its own shape only (nothing is uploaded before this has been looked at); an RGB tracker

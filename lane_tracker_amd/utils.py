@@ -1,6 +1,7 @@
 """Calibration loaders with the reference's names and return values (reference utils.py:13-55).
 Pickle files written by the reference (`cam_calib.p`, `warp_params.p`) load as before; `.npz` files
 with the same keys load without unpickling anything."""
+import collections
 import pickle
 
 import numpy as np
@@ -288,11 +289,135 @@ def apply_raw_color(rgb, ccm=None, curve=None):
     return t[np.clip((v + 512) >> 10, 0, 255)]
 
 
-def bayer_to_rgb_color(frame, pattern, raw_lut=None, ccm=None, curve=None):
+RawShading = collections.namedtuple("RawShading", "mesh black")
+RawShading.__doc__ = """A lens-shading map of raw Bayer input: `mesh` uint16 (4, mh, mw), gains in Q12 (4096 is 1.0), one plane per colour
+phase (0 red sites, 1 green on red rows, 2 green on blue rows, 3 blue sites), 2 <= mh, mw <= 64, node (0, 0) on pixel (0, 0) and node
+(mh - 1, mw - 1) on the image's last pixel; `black` int32 (4,), the pedestal of each phase.  `utils.raw_shading` makes one."""
+_MESH_MIN, _MESH_MAX = 2, 64
+
+
+def _pattern_bits(pattern):
+    """-> (pattern p, bits, dtype of the frames) of one of the twelve raw patterns."""
+    if pattern in _BAYER_WIDE_PATTERNS:
+        return _BAYER_WIDE_PATTERNS[pattern] + (np.uint16,)
+    if pattern in _BAYER_PATTERNS:
+        return _BAYER_PATTERNS.index(pattern), 8, np.uint8
+    raise ValueError("pattern must be one of %s, got %r" % (", ".join(repr(n) for n in _BAYER_PATTERNS + tuple(_BAYER_WIDE_PATTERNS)), pattern))
+
+
+def checked_raw_shading(shading, bits=8):
+    """A shading map as RawShading(mesh C-contiguous uint16 (4, mh, mw), black int32 (4,)), as the device takes it; ValueError for
+    anything that is not a (mesh, black) pair, another dtype or shape of the mesh (nothing is cast: float gains go through
+    `utils.raw_shading` first), a mesh side outside 2 .. 64, or a black value outside 0 .. 2**bits - 1."""
+    try:
+        mesh, black = shading
+    except (TypeError, ValueError):
+        raise ValueError("a shading map is a utils.RawShading (mesh, black), got %r" % (type(shading).__name__,)) from None
+    m = np.asarray(mesh)
+    if m.dtype != np.uint16 or m.ndim != 3 or m.shape[0] != 4:
+        raise ValueError("a shading mesh is a uint16 array of shape (4, mh, mw) in Q12 -- utils.raw_shading makes one of float gains --, "
+                         "got %s %r" % (m.dtype, m.shape))
+    if not all(_MESH_MIN <= n <= _MESH_MAX for n in m.shape[1:]):
+        raise ValueError("a shading mesh has %d .. %d nodes a side, got %d x %d" % (_MESH_MIN, _MESH_MAX, m.shape[2], m.shape[1]))
+    b = np.asarray(black)
+    if b.shape != (4,) or b.dtype.kind not in "iu":
+        raise ValueError("the black values of a shading map are four integers, got %s %r" % (b.dtype, b.shape))
+    smax = (1 << bits) - 1
+    if b.min() < 0 or b.max() > smax:
+        raise ValueError("the black values of a shading map for %d-bit samples lie in 0 .. %d, got %r" % (bits, smax, b.tolist()))
+    return RawShading(np.ascontiguousarray(m), b.astype(np.int32))
+
+
+def raw_shading(gains, black_level=0, bits=8):
+    """A lens-shading map for raw Bayer input (`LaneTracker(..., raw_shading=...)`): `gains` is a float mesh (mh, mw) -- one gain for all
+    four colour phases -- or (4, mh, mw) -- a plane per phase: R, Gr, Gb, B --, 2 <= mh, mw <= 64, each gain in [0, 16), rounded to Q12:
+    rint(4096 g).  `black_level` is the sensor's pedestal, one integer or four (per phase), 0 .. 2**bits - 1, bits = 8, 10 or 12: the gain
+    acts on s - black and the pedestal stays in place, so a `raw_lut` built with the same black level follows unchanged.  A radial or
+    polynomial model is sampled into a mesh by the caller.  ValueError for a gain outside [0, 16) or not a number, another shape, or a
+    black level outside the samples' range.  -> RawShading(mesh uint16 (4, mh, mw), black int32 (4,))."""
+    if bits not in (8, 10, 12):
+        raise ValueError("bits is 8, 10 or 12, got %r" % (bits,))
+    g = np.asarray(gains, dtype=np.float64)
+    if g.ndim == 2:
+        g = np.broadcast_to(g, (4,) + g.shape)
+    if g.ndim != 3 or g.shape[0] != 4 or not all(_MESH_MIN <= n <= _MESH_MAX for n in g.shape[1:]):
+        raise ValueError("shading gains are a mesh (mh, mw) or (4, mh, mw) with %d .. %d nodes a side, got %r" % (_MESH_MIN, _MESH_MAX, np.shape(gains)))
+    if not np.all(np.isfinite(g)) or g.min() < 0 or not g.max() < 16:
+        raise ValueError("shading gains lie in [0, 16), got %r .. %r" % (float(np.nanmin(g)) if g.size else None, float(np.nanmax(g)) if g.size else None))
+    q = np.minimum(np.rint(4096.0 * g), 65535.0).astype(np.uint16)     # (15.9999 would round to 2^16)
+    b = np.asarray(black_level)
+    if b.dtype.kind not in "iu" or b.shape not in ((), (4,)):
+        raise ValueError("black_level is one integer or four (R, Gr, Gb, B), got %r" % (black_level,))
+    b = np.broadcast_to(b, (4,)).astype(np.int64)
+    if b.min() < 0 or b.max() > (1 << bits) - 1:
+        raise ValueError("black_level of %d-bit samples lies in 0 .. %d, got %r" % (bits, (1 << bits) - 1, black_level))
+    return RawShading(np.ascontiguousarray(q), b.astype(np.int32))
+
+
+def _mesh_nodes(n, m):
+    """One axis of the expansion: n samples under m nodes -> (node in front of each sample, weight 0 .. 256 of the next one), int64."""
+    u = np.arange(n, dtype=np.int64) * (m - 1) * 256 // (n - 1)
+    i = np.minimum(u >> 8, m - 2)
+    return i, u - (i << 8)
+
+
+def raw_shading_plane(shading, pattern, img_size):
+    """The gain of every site of an image of `img_size` = (W, H) with `pattern` under `shading`: uint16 (H, W), Q12.  With the mesh m of
+    the site's phase p,
+
+        u = x * (mw - 1) * 256 // (W - 1);  j = min(u >> 8, mw - 2);  a = u - (j << 8)
+        v = y * (mh - 1) * 256 // (H - 1);  i = min(v >> 8, mh - 2);  b = v - (i << 8)
+        G = ((256-a)*(256-b)*m[i][j] + a*(256-b)*m[i][j+1] + (256-a)*b*m[i+1][j] + a*b*m[i+1][j+1] + 32768) >> 16
+
+    NumPy only.  This is the definition of what the device expands the mesh into."""
+    p, bits, _ = _pattern_bits(pattern)
+    mesh, _black = checked_raw_shading(shading, bits)
+    w, h = int(img_size[0]), int(img_size[1])
+    if w < 2 or h < 2:
+        raise ValueError("img_size is (width, height), both at least 2, got %r" % (img_size,))
+    mh, mw = mesh.shape[1:]
+    (j, a), (i, b) = _mesh_nodes(w, mw), _mesh_nodes(h, mh)
+    i, b, j, a = i[:, None], b[:, None], j[None, :], a[None, :]
+    out = np.empty((h, w), np.uint16)
+    yy, xx = np.arange(h)[:, None], np.arange(w)[None, :]
+    phase = 2 * ((yy ^ (p >> 1)) & 1) + ((xx ^ (p & 1)) & 1)
+    for ph in range(4):
+        m = mesh[ph].astype(np.int64)
+        g = ((256 - a) * (256 - b) * m[i, j] + a * (256 - b) * m[i, j + 1] + (256 - a) * b * m[i + 1, j] + a * b * m[i + 1, j + 1] + 32768) >> 16
+        out[phase == ph] = g[phase == ph]
+    return out
+
+
+def apply_raw_shading(frames, pattern, shading):
+    """Raw Bayer frames -- (H, W) or a stack (n, H, W); u8 for 'bayer_*', uint16 for 'bayer10_*' / 'bayer12_*' -- with the lens shading
+    corrected: with G = `raw_shading_plane(shading, pattern, (W, H))`, B the black value of the site's phase, s the sample (a word masked
+    to its bits) and smax = 2**bits - 1,
+
+        s' = min(max(B + (((s - B) * G + 2048) >> 12), 0), smax)          int32, arithmetic shift (floor)
+
+    in the frames' dtype.  NumPy only.  This is the definition: a raw Bayer tracker with `raw_shading=S` fed frames F computes, bit for
+    bit, what the same tracker without a map computes from `apply_raw_shading(F, pattern, S)`."""
+    p, bits, dtype = _pattern_bits(pattern)
+    mesh, black = checked_raw_shading(shading, bits)
+    a = np.asarray(frames)
+    if a.dtype != dtype or a.ndim not in (2, 3):
+        raise ValueError("%s frames are %s arrays (H, W) or (n, H, W), got %s %r" % (pattern, np.dtype(dtype), a.dtype, a.shape))
+    h, w = a.shape[-2:]
+    gain = raw_shading_plane(RawShading(mesh, black), pattern, (w, h)).astype(np.int64)
+    yy, xx = np.arange(h)[:, None], np.arange(w)[None, :]
+    b = black.astype(np.int64)[2 * ((yy ^ (p >> 1)) & 1) + ((xx ^ (p & 1)) & 1)]
+    smax = (1 << bits) - 1
+    s = a.astype(np.int64) & smax
+    return np.clip(b + (((s - b) * gain + 2048) >> 12), 0, smax).astype(dtype)
+
+
+def bayer_to_rgb_color(frame, pattern, raw_lut=None, ccm=None, curve=None, shading=None):
     """A raw Bayer frame (H, W) or a stack (n, H, W) in any of the twelve raw patterns -- u8 for 'bayer_*', uint16 for 'bayer10_*' /
     'bayer12_*' -- to RGB with the colour stage, on the device: every sample looked up in `raw_lut` (8-bit: u8 (4, 256), None: no
     table; 10 / 12 bits: u8 (4, 2**bits), None: the default), demosaiced, then `apply_raw_color(.., ccm, curve)`.  What a
-    `LaneTracker(..., pixel_format=pattern, raw_lut=.., raw_ccm=.., raw_curve=..)` sees of the frame."""
+    `LaneTracker(..., pixel_format=pattern, raw_lut=.., raw_ccm=.., raw_curve=..)` sees of the frame.  `shading`: a `utils.RawShading`
+    applied to every sample first (`apply_raw_shading`), as `raw_shading=` of a tracker; with one and neither `ccm` nor `curve` there is
+    no colour stage."""
     from . import _native
     from .lane_tracker import _context_for_module_functions
     if pattern not in _native.BAYER_FORMATS and pattern not in _native.BAYER_WIDE_FORMATS:
@@ -300,15 +425,18 @@ def bayer_to_rgb_color(frame, pattern, raw_lut=None, ccm=None, curve=None):
     raw_lut = _native.checked_raw_lut(raw_lut, pattern)
     ccm = None if ccm is None else checked_raw_ccm(ccm)
     curve = None if curve is None else checked_raw_curve(curve)
+    shading = _native.checked_raw_shading(shading, pattern)
     a = _native.frames_array(frame, pattern)
     if a.ndim not in (2, 3):
         raise ValueError("a raw Bayer frame is an array (H, W), a stack of them (n, H, W); got %r" % (a.shape,))
     ctx = _context_for_module_functions()
+    convert = (lambda f: ctx.raw_to_rgb_color(f, pattern, raw_lut, ccm, curve)) if shading is None else \
+              (lambda f: ctx.raw_to_rgb_shaded(f, pattern, shading, raw_lut, ccm, curve))
     if a.ndim == 2:
-        return ctx.raw_to_rgb_color(a, pattern, raw_lut, ccm, curve)
+        return convert(a)
     out = np.empty(a.shape + (3,), np.uint8)
     for k in range(a.shape[0]):
-        out[k] = ctx.raw_to_rgb_color(a[k], pattern, raw_lut, ccm, curve)
+        out[k] = convert(a[k])
     return out
 
 

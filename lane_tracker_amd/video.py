@@ -443,6 +443,9 @@ def main(argv=None):
                          "RGB; rounded to Q10, each row's sum kept)")
     ap.add_argument("--raw-out-gamma", type=_parse_gamma, default=None, metavar="G|srgb",
                     help="raw Bayer input: output curve applied after the matrix, v ** (1 / G) or the sRGB encoding (with it, keep --raw-gamma at 1)")
+    ap.add_argument("--raw-shading", default=None, metavar="FILE.npy",
+                    help="raw Bayer input: lens-shading correction from a mesh of float gains, an .npy array (mh, mw) or (4, mh, mw) -- R, Gr, "
+                         "Gb, B --, 2 .. 64 nodes a side, corner nodes on the image's corners; the pedestal is --raw-black-level")
     ap.add_argument("--out-format", choices=("rgb", "nv12", "i420") + _RGB_FAMILY, default=None,
                     help="write the annotated frames through a device sink in this pixel format: a raw .rgb / .nv12 / .i420 file for "
                          "4:2:0 (converted on the device, --out-yuv-matrix), a raw .bgr / .rgba / .bgra file (permuted on the device, "
@@ -480,6 +483,17 @@ def main(argv=None):
             raw_out_curve = raw_curve(a.raw_out_gamma)
     except ValueError as e:
         ap.error(str(e))
+    raw_shade = None
+    if a.raw_shading is not None:
+        if a.pixel_format not in _BAYER + _BAYER_WIDE:
+            ap.error("--raw-shading corrects raw Bayer samples: it needs --pixel-format bayer_*")
+        import numpy as np
+        from .utils import raw_shading
+        try:
+            raw_shade = raw_shading(np.load(a.raw_shading, allow_pickle=False), black_level=int(round(a.raw_black_level or 0)),
+                                    bits=8 if a.pixel_format in _BAYER else _raw_format_bits(a.pixel_format))
+        except (OSError, ValueError) as e:
+            ap.error("--raw-shading %s: %s" % (a.raw_shading, e))
     if a.split_view and a.output == "-":
         ap.error("--split-view shows the annotated frames: it needs an output")
     if a.split_view and a.visualize_search:
@@ -506,7 +520,7 @@ def main(argv=None):
     lt = LaneTracker(img_size=image_wh, warped_size=warped_wh, cam_matrix=cam_matrix, dist_coeffs=dist_coeffs,
                      warp_matrices=(M, Minv), mpp_conversion=(mppv, mpph), n_fail=8, n_reset=4, n_average=2,
                      print_frame_count=a.frame_count, device=a.device, pixel_format=src.pixel_format, yuv_matrix=a.yuv_matrix,
-                     input_size=a.input_size, raw_lut=raw_table, raw_ccm=raw_matrix, raw_curve=raw_out_curve)
+                     input_size=a.input_size, raw_lut=raw_table, raw_ccm=raw_matrix, raw_curve=raw_out_curve, raw_shading=raw_shade)
     try:
         out_size = src.size if a.input_size is None else tuple(int(v) for v in image_wh)
         if a.split_view:                 # the annotated frame on top, the pane strip below it
