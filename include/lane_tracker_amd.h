@@ -1002,6 +1002,10 @@ const char* lt_stage_name(int stage);
  * one they have exercised. */
 #define LT_NO_CONTEXT (-2147483647 - 1)
 int  lt_last_threshold_path(lt_ctx* ctx);
+/* Which form of them: 0 = the tile kernel, 1 = the running-sum walks, 2 = the matrix-core form (the window sums as i8 band
+ * products; where lt_last_threshold_path says 1 and the walks' conditions hold), -1 = none yet; LT_NO_CONTEXT for a null
+ * context.  Forms 1 and 2 write identical partial planes; the greenery mask keeps its running-sum walk under either. */
+int  lt_last_threshold_form(lt_ctx* ctx);
 /* Which form of the batch top-hat walks the context's last lt_mask_run / lt_filter_run piece launched: bit 0 = the 29x29 pair
  * of launches, bit 1 = the 55x55 pair took the split-band form (every band walks its own rows only and boundary rows are
  * merged from the two neighbours' partial results); 0 = the bands walked their halos, or another top-hat route ran (one or two

@@ -224,6 +224,7 @@ _SIGNATURES = {
     "lt_set_download_method": (C.c_int, [_P, C.c_int]),
     "lt_download_stats": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "lt_last_threshold_path": (C.c_int, [_P]),
+    "lt_last_threshold_form": (C.c_int, [_P]),
     "lt_last_tophat_path": (C.c_int, [_P]),
     "lt_tophat_split_form": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "lt_last_adaptive_path": (C.c_int, [_P]),
@@ -1797,6 +1798,10 @@ class Context:
     def last_threshold_path(self):
         """1 = long-walk threshold kernels, 0 = tile kernel, -1 = no bilateral chain has run yet."""
         return int(self.lib.lt_last_threshold_path(self._h))
+
+    def last_threshold_form(self):
+        """0 = tile kernel, 1 = running-sum walks, 2 = matrix-core form (i8 band products), -1 = no bilateral chain has run yet."""
+        return int(self.lib.lt_last_threshold_form(self._h))
 
     def last_tophat_path(self):
         """Batch top-hat walks of the last mask chain: bit 0 = 29x29, bit 1 = 55x55 ran the split-band form; 0 = neither, -1 = none yet."""

@@ -207,6 +207,7 @@ void preload_k_filter(hipStream_t s);
 void preload_k_tophat(hipStream_t s);
 void preload_k_threshold(hipStream_t s);
 void preload_k_threshold_walk(hipStream_t s);
+void preload_k_threshold_mma(hipStream_t s);
 void preload_k_adaptive_walk(hipStream_t s);
 void preload_k_search(hipStream_t s);
 void preload_k_overlay(hipStream_t s);
@@ -310,6 +311,11 @@ bool bilateral_walk_supported(int k_r, int C_r, int k_b, int C_b, int h, int w, 
 int launch_bilateral_walk(hipStream_t s, const uint8_t* thr, int k_r, int C_r, const uint8_t* thb, int k_b, int C_b,
                           unsigned long long* merged, unsigned long long* s1, unsigned long long* s2, unsigned long long* s3,
                           int h, int w, int pitch, size_t plane_stride, size_t bits_stride, int n);
+// the same four partial planes, bit for bit, with the window sums as i8 matrix products (k_threshold_mma.hip), for the same calls:
+// 0 = ran, -1 = bilateral_walk_supported says no, 1 = switched off (experiments build: LT_THRESHOLD_MMA=0), take the walks
+int launch_bilateral_mma(hipStream_t s, const uint8_t* thr, int k_r, int C_r, const uint8_t* thb, int k_b, int C_b,
+                         unsigned long long* merged, unsigned long long* s1, unsigned long long* s2, unsigned long long* s3,
+                         int h, int w, int pitch, size_t plane_stride, size_t bits_stride, int n);
 // the merge alone, in place (k_or4_bits); nothing to do for a plane that is merged already
 void launch_or4_bits(hipStream_t s, const MergeInputs& in, int h, int w, size_t bits_stride, int n);
 // the greenery mask (lane_tracker.py:223-225) through the walking kernels: noise_h | noise_v = !inRange(b, thresh, 255) |

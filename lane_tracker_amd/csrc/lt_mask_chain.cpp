@@ -60,6 +60,7 @@ struct Chain {
                (!p->mask_noise || noise_walk_supported(p->ksize_noise, p->C_noise, h, w, a.th_pitch, a.th_pad_bytes));
         if (p->filter_type != 0) return LT_OK;
         if (env.threshold_path) *env.threshold_path = walk ? 1 : 0;
+        if (env.threshold_form) *env.threshold_form = walk ? 1 : 0;   // thresholds() says which of the two long forms
         for (int i = first; i < first + n && i < (int)a.th_padded.size(); ++i) a.th_padded[(size_t)i] = walk ? 1 : 0;
         if (!walk) return LT_OK;
         dpitch = a.th_pitch;
@@ -145,9 +146,14 @@ struct Chain {
             if (walk) {
                 // the long walks: four partial planes (R horizontal, R vertical, b horizontal, b vertical), and the greenery mask as two more
                 unsigned long long *tbits = a.d_bits_tmp + (size_t)first * bs, *ubits = a.d_bits_tmp2 + (size_t)first * bs;
-                if (launch_bilateral_walk(s, thRd, p->ksize_r, p->C_r, thBd, p->ksize_b, p->C_b, mbits, ebits, tbits, ubits, h, w, a.th_pitch,
-                                          a.th_pad_bytes, bs, n))
-                    return fail(LT_ERR_STATE, "the bilateral walk refused parameters its own predicate accepted");
+                // as i8 matrix products (k_threshold_mma.hip); the running-sum walks where that launcher stands aside
+                int rc = launch_bilateral_mma(s, thRd, p->ksize_r, p->C_r, thBd, p->ksize_b, p->C_b, mbits, ebits, tbits, ubits, h, w, a.th_pitch,
+                                              a.th_pad_bytes, bs, n);
+                if (env.threshold_form) *env.threshold_form = rc == 0 ? 2 : 1;
+                if (rc > 0)
+                    rc = launch_bilateral_walk(s, thRd, p->ksize_r, p->C_r, thBd, p->ksize_b, p->C_b, mbits, ebits, tbits, ubits, h, w, a.th_pitch,
+                                               a.th_pad_bytes, bs, n);
+                if (rc) return fail(LT_ERR_STATE, "the bilateral walk refused parameters its own predicate accepted");
                 in.more[0] = ebits, in.more[1] = tbits, in.more[2] = ubits, in.n_more = 3;
                 if (!noise) return LT_OK;
                 unsigned long long *n1 = a.d_bits_n1 + (size_t)first * bs, *n2 = a.d_bits_n2 + (size_t)first * bs;
