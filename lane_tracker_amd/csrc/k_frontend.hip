@@ -11,22 +11,18 @@
 //   k_rows_to_rgb<LAYOUT, SURF, WIDE>  a run of rows of frames in LAYOUT (not 0) as RGB, for whoever shows the camera frame
 //                      (cv2.cvtColor(YUV2RGB_NV12 / _I420 / _YUY2 / _UYVY), a permutation, the demosaic), from a slot's staging frame / from
 //                      a surface (SURF): one 16-column (WIDE) and one byte-wise body per family of layouts; k_surf_copy_rows: RGB surfaces
-//   k_raw_walk_rows<PATTERN, SRC, PER_SLOT>, k_raw_rows_rgb<PATTERN, SURF, WIDE>  the two above for raw Bayer frames behind a raw table
-//                      (lt_set_raw_lut: black level, white balance and tone curve as one 256-entry table per colour phase, staged in
-//                      LDS): every byte looked up before it is demosaiced; launched in their place whenever a table is set
-//   k_raw16_walk_rows<PATTERN, SRC, PER_SLOT>, k_raw16_rows_rgb<PATTERN, SURF, WIDE>  the same two for 10- / 12-bit raw Bayer frames (layouts
-//                      32 .. 35, 48 .. 51: 16-bit little-endian words, the sample in the low `bits` bits, a run-time argument), always
-//                      behind their wide raw table (lt_set_raw_lut_wide: 1 << bits entries per colour phase, 4 KB / 16 KB of dynamic LDS):
-//                      every site masked and looked up into the 8-bit window that the 8-bit demosaic takes
-//   k_cc_walk_rows, k_cc16_walk_rows <PATTERN, SRC, PER_SLOT>, k_cc_rows_rgb, k_cc16_rows_rgb <PATTERN, SURF, WIDE>  the four above with
-//                      the colour stage of raw Bayer input (lt_set_raw_color) on every demosaiced tap / pixel: a colour-correction matrix
-//                      (Q10, nine scalar operands of 24-bit multiply-adds), a clamp and a 256-entry output curve staged in LDS with the
-//                      table; launched in their place whenever a stage is set
-//   k_ls_walk_rows, k_ls16_walk_rows <PATTERN, SRC, PER_SLOT, CC>, k_ls_rows_rgb, k_ls16_rows_rgb <PATTERN, SURF, WIDE, CC>  the table forms
-//                      above, without and with (CC) the colour stage, behind the lens-shading correction of raw Bayer input
-//                      (lt_set_raw_shading; shade_arith.h): every sample corrected by the gain of its site before its table lookup.  The
-//                      gains lie in a plane that k_shade_expand makes of the map's mesh once; a walk loads the 16 of its window once and
-//                      keeps them across its frames; launched in the others' place whenever a map is set
+//   k_raw_walk_rows<PATTERN, SRC, PER_SLOT, STAGES>, k_raw_rows_rgb<PATTERN, SURF, WIDE, STAGES>  the two above for raw Bayer frames behind
+//                      a raw table staged in LDS, launched in their place whenever there is one; what else runs around the demosaic is
+//                      STAGES, and its operands one RawStages (lt_internal.h).  Bit 0: 10- / 12-bit frames (layouts 32 .. 35, 48 .. 51:
+//                      16-bit little-endian words, the sample in the low `bits` bits, a run-time argument) behind their wide table
+//                      (lt_set_raw_lut_wide: 1 << bits entries per colour phase, 4 KB / 16 KB of dynamic LDS), every site masked and looked
+//                      up into the 8-bit window that the 8-bit demosaic takes; else 8-bit frames behind lt_set_raw_lut's table (black level,
+//                      white balance and tone curve as 256 entries per colour phase), every byte looked up before it is demosaiced.  Bit 1:
+//                      the colour stage (lt_set_raw_color) on every demosaiced tap / pixel -- a colour-correction matrix (Q10, nine scalar
+//                      operands of 24-bit multiply-adds), a clamp and a 256-entry output curve staged in LDS with the table.  Bit 2: the
+//                      lens-shading correction (lt_set_raw_shading; shade_arith.h), every sample corrected by the gain of its site before
+//                      its table lookup; the gains lie in a plane that k_shade_expand makes of the map's mesh once, and a walk loads the
+//                      16 of its window once and keeps them across its frames
 //   k_warp_split       cv2.warpPerspective      lane_tracker.py:834
 //                      + img[:,:,0]             lane_tracker.py:207
 //                      + cvtColor(RGB2LAB)[:,:,2] lane_tracker.py:208
@@ -387,7 +383,6 @@ template <int PATTERN> struct StagesTable<Bayer16Lut<PATTERN>> : std::true_type 
 // scalar operand (the 16-bit dot form would need the channels packed in pairs first: more instructions, not fewer).  The curve's 256
 // bytes lie in LDS right in front of the table -- at a fixed address whatever the table's size; in the 8-bit form, whose LDS is a static
 // array, a lookup's offset is an immediate -- and in device memory too (`table`: curve, then table), so that one load per thread and one barrier stage both.
-struct RawColorMat { int m[9]; };
 template <int PATTERN>
 __device__ __forceinline__ void stage_with_curve(const Bayer8Lut<PATTERN>& f, uint8_t* lds) {        // 1280 bytes: 8 from each of the first 160 threads
     if (threadIdx.x < 160) reinterpret_cast<uint2*>(lds)[threadIdx.x] = reinterpret_cast<const uint2*>(f.table)[threadIdx.x];
@@ -420,7 +415,6 @@ template <class B> struct StagesTable<ColorStage<B>> : std::true_type {};
 // the 16 gains stay in 8 VGPRs across the per-frame loop.  The four pedestals are a kernel argument (SGPRs); which of them the window's
 // even / odd rows and columns have follows from the window's parities, selected once per walk.  Per frame and site: a subtract, a 24-bit
 // multiply-add, a shift and a clamp; no vector-memory instruction, no LDS, no scratch.
-struct RawShadeBlack { int b[4]; };          // by colour phase
 // (all four read, then selected by value: a select between the ADDRESSES of two members would keep the struct that holds them in scratch)
 __device__ __forceinline__ int black_of(const RawShadeBlack& k, int ph) {
     const int b0 = k.b[0], b1 = k.b[1], b2 = k.b[2], b3 = k.b[3];
@@ -654,112 +648,42 @@ __global__ __launch_bounds__(256) void k_undistort_rows(const SurfEntry* __restr
     else undistort_walk<PER_SLOT>(a, SlotSource<SRC == SRC_SLOTS>{frames, stride}, format_of<LAYOUT>(g, k));
 }
 
-// The walk over raw Bayer frames behind a raw table (lt_set_raw_lut): PATTERN x source (surfaces, dword-aligned slots) x table form, the
-// parameters of k_undistort_rows and the context's table; launched in its place, in the same stage, whenever a table is set -- the
-// identity included.
-template <int PATTERN, int SRC, bool PER_SLOT>
+// The walk over raw Bayer frames behind a raw table: PATTERN x source (surfaces, dword-aligned slots) x table form x STAGES -- bit 0: 16-bit
+// samples behind the wide table (else bytes), bit 1: the colour stage on every demosaiced tap, bit 2: the shading map in front of the
+// lookup.  k_undistort_rows' parameters without `k`, and what the stages read (lt_internal.h: RawStages; a member that a form does not
+// read is never loaded).  r.table is what the workgroup stages: the table, behind the curve's 256 bytes with a colour stage -- 1024 (+ 256)
+// bytes of static LDS for 8-bit samples, so that a lookup's offset is an immediate, the launch's dynamic LDS, 4 << bits (+ 256), for 16-bit
+// ones.  Launched in k_undistort_rows' place, in the same stage, whenever there is a table -- the identity included.
+template <int PATTERN, bool W16, bool CC, bool LS>
+struct RawFormatOf {
+    using Base = std::conditional_t<W16, Bayer16Lut<PATTERN>, Bayer8Lut<PATTERN>>;
+    using Shaded = std::conditional_t<LS, ShadeStage<Base>, Base>;
+    using type = std::conditional_t<CC, ColorStage<Shaded>, Shaded>;
+};
+extern __shared__ __attribute__((aligned(16))) uint8_t s_lut_wide[];
+template <int PATTERN, int SRC, bool PER_SLOT, int STAGES>
 __global__ __launch_bounds__(256) void k_raw_walk_rows(const SurfEntry* __restrict__ tab, const uint8_t* __restrict__ frames, size_t stride,
                                                       const int16_t* __restrict__ uxy, const uint16_t* __restrict__ ufrac,
                                                       const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
                                                       uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb, int remap,
-                                                      const uint32_t* __restrict__ raw_lut) {
+                                                      RawStages r) {
     static_assert(SRC == SRC_SURFACES || SRC == SRC_SLOTS, "a raw Bayer staging frame is dword-aligned");
-    __shared__ alignas(16) uint8_t s_lut[1024];
+    constexpr bool W16 = (STAGES & 1) != 0, CC = (STAGES & 2) != 0, LS = (STAGES & 4) != 0;
+    constexpr int CURVE = CC ? 256 : 0;
+    uint8_t* lds;
+    if constexpr (W16) {
+        lds = s_lut_wide;
+    } else {
+        __shared__ alignas(16) uint8_t s_tab[CURVE + 1024];
+        lds = s_tab;
+    }
     const WalkArgs a{uxy, ufrac, SlotTables{sets, &ids}, g, und, und_px, first_slot, n, PER_SLOT ? 1 : fpb, remap};
-    Bayer8Lut<PATTERN> fmt{};
-    fmt.w = g.img_w, fmt.h = g.img_h, fmt.lut = s_lut, fmt.table = raw_lut;
-    if constexpr (SRC == SRC_SURFACES) undistort_walk<PER_SLOT>(a, SurfSource{tab}, fmt);
-    else undistort_walk<PER_SLOT>(a, SlotSource<true>{frames, stride}, fmt);
-}
-
-// The walk over 10- / 12-bit raw Bayer frames (layouts 32 .. 35, 48 .. 51), always behind their wide raw table (lt_set_raw_lut_wide):
-// k_raw_walk_rows' forms and parameters plus `bits`; the table's 4 << bits bytes are the launch's dynamic LDS.
-extern __shared__ __attribute__((aligned(16))) uint8_t s_lut_wide[];
-template <int PATTERN, int SRC, bool PER_SLOT>
-__global__ __launch_bounds__(256) void k_raw16_walk_rows(const SurfEntry* __restrict__ tab, const uint8_t* __restrict__ frames, size_t stride,
-                                                        const int16_t* __restrict__ uxy, const uint16_t* __restrict__ ufrac,
-                                                        const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
-                                                        uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb, int remap,
-                                                        const uint32_t* __restrict__ raw_lut, int bits) {
-    static_assert(SRC == SRC_SURFACES || SRC == SRC_SLOTS, "a raw Bayer staging frame is dword-aligned");
-    const WalkArgs a{uxy, ufrac, SlotTables{sets, &ids}, g, und, und_px, first_slot, n, PER_SLOT ? 1 : fpb, remap};
-    Bayer16Lut<PATTERN> fmt{};
-    fmt.w = g.img_w, fmt.h = g.img_h, fmt.lut = s_lut_wide, fmt.table = reinterpret_cast<const uint4*>(raw_lut);
-    fmt.bits = bits, fmt.mask = (1u << bits) - 1u;
-    if constexpr (SRC == SRC_SURFACES) undistort_walk<PER_SLOT>(a, SurfSource{tab}, fmt);
-    else undistort_walk<PER_SLOT>(a, SlotSource<true>{frames, stride}, fmt);
-}
-
-// The two walks above with the colour stage (lt_set_raw_color) on every demosaiced tap: the same forms and parameters, `raw_cc` the
-// output curve followed by the table (device memory: 256 + 1024 bytes, or 256 + (4 << bits)) and `cm` the matrix.  An 8-bit context
-// without a raw table runs k_cc_walk_rows with the identity table.  Launched in the plain raw walks' place, in the same stage, whenever
-// a colour stage is set -- the identity included.
-template <int PATTERN, int SRC, bool PER_SLOT>
-__global__ __launch_bounds__(256) void k_cc_walk_rows(const SurfEntry* __restrict__ tab, const uint8_t* __restrict__ frames, size_t stride,
-                                                     const int16_t* __restrict__ uxy, const uint16_t* __restrict__ ufrac,
-                                                     const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
-                                                     uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb, int remap,
-                                                     const uint32_t* __restrict__ raw_cc, RawColorMat cm) {
-    static_assert(SRC == SRC_SURFACES || SRC == SRC_SLOTS, "a raw Bayer staging frame is dword-aligned");
-    __shared__ alignas(16) uint8_t s_cc[256 + 1024];
-    const WalkArgs a{uxy, ufrac, SlotTables{sets, &ids}, g, und, und_px, first_slot, n, PER_SLOT ? 1 : fpb, remap};
-    ColorStage<Bayer8Lut<PATTERN>> fmt{};
-    fmt.w = g.img_w, fmt.h = g.img_h, fmt.lut = s_cc + 256, fmt.table = raw_cc;
-    fmt.cm = cm, fmt.curve = s_cc;
-    if constexpr (SRC == SRC_SURFACES) undistort_walk<PER_SLOT>(a, SurfSource{tab}, fmt);
-    else undistort_walk<PER_SLOT>(a, SlotSource<true>{frames, stride}, fmt);
-}
-template <int PATTERN, int SRC, bool PER_SLOT>
-__global__ __launch_bounds__(256) void k_cc16_walk_rows(const SurfEntry* __restrict__ tab, const uint8_t* __restrict__ frames, size_t stride,
-                                                       const int16_t* __restrict__ uxy, const uint16_t* __restrict__ ufrac,
-                                                       const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
-                                                       uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb, int remap,
-                                                       const uint32_t* __restrict__ raw_cc, int bits, RawColorMat cm) {
-    static_assert(SRC == SRC_SURFACES || SRC == SRC_SLOTS, "a raw Bayer staging frame is dword-aligned");
-    const WalkArgs a{uxy, ufrac, SlotTables{sets, &ids}, g, und, und_px, first_slot, n, PER_SLOT ? 1 : fpb, remap};
-    ColorStage<Bayer16Lut<PATTERN>> fmt{};
-    fmt.w = g.img_w, fmt.h = g.img_h, fmt.lut = s_lut_wide + 256, fmt.table = reinterpret_cast<const uint4*>(raw_cc);
-    fmt.bits = bits, fmt.mask = (1u << bits) - 1u;
-    fmt.cm = cm, fmt.curve = s_lut_wide;
-    if constexpr (SRC == SRC_SURFACES) undistort_walk<PER_SLOT>(a, SurfSource{tab}, fmt);
-    else undistort_walk<PER_SLOT>(a, SlotSource<true>{frames, stride}, fmt);
-}
-
-// The four walks above behind the lens-shading correction (lt_set_raw_shading): the same forms and parameters, `table` what the wrapped
-// walk stages -- the raw table (an 8-bit context without one: the identity table), or (CC) the output curve followed by it -- `cm` the
-// matrix (read by the CC forms), `gains` the expanded gain plane and `blk` the four pedestals.  Launched in the wrapped walks' place, in the
-// same stage, whenever a map is set -- the identity included.
-template <int PATTERN, int SRC, bool PER_SLOT, bool CC>
-__global__ __launch_bounds__(256) void k_ls_walk_rows(const SurfEntry* __restrict__ tab, const uint8_t* __restrict__ frames, size_t stride,
-                                                     const int16_t* __restrict__ uxy, const uint16_t* __restrict__ ufrac,
-                                                     const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
-                                                     uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb, int remap,
-                                                     const uint32_t* __restrict__ table, RawColorMat cm, const uint16_t* __restrict__ gains,
-                                                     RawShadeBlack blk) {
-    static_assert(SRC == SRC_SURFACES || SRC == SRC_SLOTS, "a raw Bayer staging frame is dword-aligned");
-    __shared__ alignas(16) uint8_t s_ls[(CC ? 256 : 0) + 1024];
-    const WalkArgs a{uxy, ufrac, SlotTables{sets, &ids}, g, und, und_px, first_slot, n, PER_SLOT ? 1 : fpb, remap};
-    std::conditional_t<CC, ColorStage<ShadeStage<Bayer8Lut<PATTERN>>>, ShadeStage<Bayer8Lut<PATTERN>>> fmt{};
-    fmt.w = g.img_w, fmt.h = g.img_h, fmt.lut = s_ls + (CC ? 256 : 0), fmt.table = table;
-    if constexpr (CC) fmt.cm = cm, fmt.curve = s_ls;
-    fmt.shade_with(gains, blk);
-    if constexpr (SRC == SRC_SURFACES) undistort_walk<PER_SLOT>(a, SurfSource{tab}, fmt);
-    else undistort_walk<PER_SLOT>(a, SlotSource<true>{frames, stride}, fmt);
-}
-template <int PATTERN, int SRC, bool PER_SLOT, bool CC>
-__global__ __launch_bounds__(256) void k_ls16_walk_rows(const SurfEntry* __restrict__ tab, const uint8_t* __restrict__ frames, size_t stride,
-                                                       const int16_t* __restrict__ uxy, const uint16_t* __restrict__ ufrac,
-                                                       const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
-                                                       uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb, int remap,
-                                                       const uint32_t* __restrict__ table, int bits, RawColorMat cm,
-                                                       const uint16_t* __restrict__ gains, RawShadeBlack blk) {
-    static_assert(SRC == SRC_SURFACES || SRC == SRC_SLOTS, "a raw Bayer staging frame is dword-aligned");
-    const WalkArgs a{uxy, ufrac, SlotTables{sets, &ids}, g, und, und_px, first_slot, n, PER_SLOT ? 1 : fpb, remap};
-    std::conditional_t<CC, ColorStage<ShadeStage<Bayer16Lut<PATTERN>>>, ShadeStage<Bayer16Lut<PATTERN>>> fmt{};
-    fmt.w = g.img_w, fmt.h = g.img_h, fmt.lut = s_lut_wide + (CC ? 256 : 0), fmt.table = reinterpret_cast<const uint4*>(table);
-    fmt.bits = bits, fmt.mask = (1u << bits) - 1u;
-    if constexpr (CC) fmt.cm = cm, fmt.curve = s_lut_wide;
-    fmt.shade_with(gains, blk);
+    typename RawFormatOf<PATTERN, W16, CC, LS>::type fmt{};
+    fmt.w = g.img_w, fmt.h = g.img_h, fmt.lut = lds + CURVE;
+    if constexpr (W16) fmt.table = reinterpret_cast<const uint4*>(r.table), fmt.bits = r.bits, fmt.mask = (1u << r.bits) - 1u;
+    else fmt.table = r.table;
+    if constexpr (CC) fmt.cm = r.cm, fmt.curve = lds;
+    if constexpr (LS) fmt.shade_with(r.gains, r.blk);
     if constexpr (SRC == SRC_SURFACES) undistort_walk<PER_SLOT>(a, SurfSource{tab}, fmt);
     else undistort_walk<PER_SLOT>(a, SlotSource<true>{frames, stride}, fmt);
 }
@@ -1016,155 +940,77 @@ struct ColorPost {
     const uint8_t* curve;
     __device__ __forceinline__ uint32_t operator()(uint32_t v) const { return ba::color_px(v, cm.m, curve); }
 };
-// RowsBayer behind a raw table (lt_set_raw_lut; `lut`: the table in LDS): the same two bodies over the conditioned mosaic, every byte
-// looked up in the table row of its site (bayer_arith.h: condition4 / condition1) before it is summed -- 3 x 18 lookups per 16 pixels
-// (wide), 9 per pixel (any).  Bodies of their own, so that the plain ones above stay the code they were.
-template <int P>
-struct RowsBayerLut {
+// RowsBayer behind a raw table (`lut`: the table in LDS, 1 << bits bytes a row, bits = 8 for bytes): the same two bodies over the conditioned
+// mosaic, every site looked up in the table row of its phase before it is summed -- 3 x 18 lookups per 16 pixels (wide), 9 per pixel (any).
+// W16: the sites are 16-bit words (pitch in bytes and even), masked to `bits` bits; wide's 16 columns are then 32 bytes, two 16-byte loads a
+// row, any's accesses 2 bytes.  LS: behind the lens-shading correction, every site shaded with the gain of its position, read from the gain
+// plane `gp` (uint16, w a row), and the pedestal of its phase before it is looked up; the 16 gains of wide's 16 columns are two 16-byte loads
+// (w, x0 and the plane's base are multiples of 16).  The bodies differ in how one site (`one`) and the four conditioned dwords of 16 sites
+// (`row16`) are obtained, and in nothing else.  A body of its own, so that the plain one above stays the code it was.
+template <int P, bool W16, bool LS>
+struct RowsRaw {
+    const uint8_t* lut;
+    int bits;
+    uint32_t mask;                           // (1 << bits) - 1
+    const uint16_t* gp;                      // LS
+    RawShadeBlack blk;
+    __device__ __forceinline__ static Planes dense(const uint8_t* frame, int, int w) { return Planes{frame, nullptr, nullptr, W16 ? 2 * w : w, 0}; }
     // the table row of the sites of row parity par_y and column parity par_x
-    __device__ __forceinline__ static const uint8_t* trow(const uint8_t* lut, int par_y, int par_x) { return lut + ba::lut_row(P, par_y, par_x); }
-    template <class Post = NoPost>
-    __device__ __forceinline__ static void wide(const Planes& s, const uint8_t* lut, uint8_t* dst, int h, int w, int y, int x0, Post post = Post{}) {
-        if (x0 >= w) return;
-        const int cy = ba::tap_pos(y, h), xl = max(x0 - 1, 0), xr = min(x0 + 16, w - 1);
-        uint32_t m[3][4], left[3], right[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            const uint8_t* row = s.y + (size_t)(cy - 1 + r) * s.pitch;
-            const int py = (cy - 1 + r) & 1;
-            const uint8_t *ta = trow(lut, py, 0), *tb = trow(lut, py, 1);     // (x0 is even: byte 0 of every dword is an even column)
-            const uint4 q = *reinterpret_cast<const uint4*>(row + x0);
-            m[r][0] = ba::condition4(q.x, ta, tb); m[r][1] = ba::condition4(q.y, ta, tb);
-            m[r][2] = ba::condition4(q.z, ta, tb); m[r][3] = ba::condition4(q.w, ta, tb);
-            left[r] = ba::condition1(row[xl], trow(lut, py, xl & 1));
-            right[r] = ba::condition1(row[xr], trow(lut, py, xr & 1));
-        }
-        auto at = [&](int r, int j) { return j < 0 ? left[r] : j > 15 ? right[r] : (m[r][j >> 2] >> (8 * (j & 3))) & 255u; };
-        uint32_t px[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j)
-            px[j] = ba::demosaic(at(1, j), at(1, j - 1) + at(1, j + 1), at(0, j) + at(2, j),
-                                 at(0, j - 1) + at(0, j + 1) + at(2, j - 1) + at(2, j + 1), ba::phase(P, cy, j));
-        if (x0 == 0) px[0] = px[1];
-        if (x0 + 16 == w) px[15] = px[14];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) px[j] = post(px[j]);
-        uint32_t d[12];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) pack_rgb4(px + 4 * j, d + 3 * j);
-        store_rgb16(dst + ((size_t)y * w + x0) * 3, d);
-    }
-    template <class Post = NoPost>
-    __device__ __forceinline__ static void any(const Planes& s, const uint8_t* lut, uint8_t* dst, int h, int w, int y, int x, Post post = Post{}) {
-        if (x >= w) return;
-        const int cy = ba::tap_pos(y, h), cx = ba::tap_pos(x, w);
-        const uint8_t *up = s.y + (size_t)(cy - 1) * s.pitch + cx, *mid = up + s.pitch, *dn = mid + s.pitch;
-        const int py = cy & 1, px = cx & 1;      // the site's parities; a neighbour one step away has the other one
-        auto u = [&](int i) { return ba::condition1(up[i], trow(lut, py ^ 1, px ^ (i & 1))); };
-        auto m = [&](int i) { return ba::condition1(mid[i], trow(lut, py, px ^ (i & 1))); };
-        auto d = [&](int i) { return ba::condition1(dn[i], trow(lut, py ^ 1, px ^ (i & 1))); };
-        const uint32_t v = ba::demosaic(m(0), m(-1) + m(1), u(0) + d(0), u(-1) + u(1) + d(-1) + d(1), ba::phase(P, cy, cx));
-        store_rgb1(dst + ((size_t)y * w + x) * 3, post(v));
-    }
-};
-// RowsBayerLut for 10- / 12-bit frames (16-bit words, pitch in bytes and even, `lut`: the wide table in LDS, 1 << bits bytes a row): the
-// same two bodies over the conditioned mosaic.  wide: the 16 columns from x0 are 32 bytes, two 16-byte loads a row; any: 2-byte accesses.
-template <int P>
-struct RowsBayer16Lut {
-    __device__ __forceinline__ static Planes dense(const uint8_t* frame, int, int w) { return Planes{frame, nullptr, nullptr, 2 * w, 0}; }
-    __device__ __forceinline__ static const uint8_t* trow(const uint8_t* lut, int bits, int par_y, int par_x) { return lut + ba::lut_row_wide(bits, P, par_y, par_x); }
-    __device__ __forceinline__ static uint32_t site(const uint8_t* row, int x) { return reinterpret_cast<const uint16_t*>(row)[x]; }
-    template <class Post = NoPost>
-    __device__ __forceinline__ static void wide(const Planes& s, const uint8_t* lut, int bits, uint8_t* dst, int h, int w, int y, int x0, Post post = Post{}) {
-        if (x0 >= w) return;
-        const uint32_t mask = (1u << bits) - 1u;
-        const int cy = ba::tap_pos(y, h), xl = max(x0 - 1, 0), xr = min(x0 + 16, w - 1);
-        uint32_t m[3][4], left[3], right[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-            const uint8_t* row = s.y + (size_t)(cy - 1 + r) * s.pitch;
-            const int py = (cy - 1 + r) & 1;
-            const uint8_t *ta = trow(lut, bits, py, 0), *tb = trow(lut, bits, py, 1);     // (x0 is even: site 0 of every dword pair is an even column)
-            const uint4 q0 = *reinterpret_cast<const uint4*>(row + 2 * x0), q1 = *reinterpret_cast<const uint4*>(row + 2 * x0 + 16);
-            m[r][0] = ba::condition4w(q0.x, q0.y, ta, tb, mask); m[r][1] = ba::condition4w(q0.z, q0.w, ta, tb, mask);
-            m[r][2] = ba::condition4w(q1.x, q1.y, ta, tb, mask); m[r][3] = ba::condition4w(q1.z, q1.w, ta, tb, mask);
-            left[r] = ba::condition1w(site(row, xl), trow(lut, bits, py, xl & 1), mask);
-            right[r] = ba::condition1w(site(row, xr), trow(lut, bits, py, xr & 1), mask);
-        }
-        auto at = [&](int r, int j) { return j < 0 ? left[r] : j > 15 ? right[r] : (m[r][j >> 2] >> (8 * (j & 3))) & 255u; };
-        uint32_t px[16];
-#pragma unroll
-        for (int j = 0; j < 16; ++j)
-            px[j] = ba::demosaic(at(1, j), at(1, j - 1) + at(1, j + 1), at(0, j) + at(2, j),
-                                 at(0, j - 1) + at(0, j + 1) + at(2, j - 1) + at(2, j + 1), ba::phase(P, cy, j));
-        if (x0 == 0) px[0] = px[1];
-        if (x0 + 16 == w) px[15] = px[14];
-#pragma unroll
-        for (int j = 0; j < 16; ++j) px[j] = post(px[j]);
-        uint32_t d[12];
-#pragma unroll
-        for (int j = 0; j < 4; ++j) pack_rgb4(px + 4 * j, d + 3 * j);
-        store_rgb16(dst + ((size_t)y * w + x0) * 3, d);
-    }
-    template <class Post = NoPost>
-    __device__ __forceinline__ static void any(const Planes& s, const uint8_t* lut, int bits, uint8_t* dst, int h, int w, int y, int x, Post post = Post{}) {
-        if (x >= w) return;
-        const uint32_t mask = (1u << bits) - 1u;
-        const int cy = ba::tap_pos(y, h), cx = ba::tap_pos(x, w);
-        const uint8_t *up = s.y + (size_t)(cy - 1) * s.pitch, *mid = up + s.pitch, *dn = mid + s.pitch;
-        const int py = cy & 1, px = cx & 1;      // the site's parities; a neighbour one step away has the other one
-        auto u = [&](int i) { return ba::condition1w(site(up, cx + i), trow(lut, bits, py ^ 1, px ^ (i & 1)), mask); };
-        auto m = [&](int i) { return ba::condition1w(site(mid, cx + i), trow(lut, bits, py, px ^ (i & 1)), mask); };
-        auto d = [&](int i) { return ba::condition1w(site(dn, cx + i), trow(lut, bits, py ^ 1, px ^ (i & 1)), mask); };
-        const uint32_t v = ba::demosaic(m(0), m(-1) + m(1), u(0) + d(0), u(-1) + u(1) + d(-1) + d(1), ba::phase(P, cy, cx));
-        store_rgb1(dst + ((size_t)y * w + x) * 3, post(v));
-    }
-};
-// The two table bodies above behind the lens-shading correction (lt_set_raw_shading), for both sample widths (W16: 16-bit words; else bytes,
-// bits = 8 and the table's rows 256 bytes apart, which is what lut_row_wide(8, ..) says): every site shaded with the gain of its position,
-// read from the gain plane `gp` (uint16, w a row), and the pedestal of its phase before it is looked up.  wide: the 16 gains of a row's 16
-// columns are two 16-byte loads (w, x0 and the plane's base are multiples of 16).  Bodies of their own, so that the ones above stay the
-// code they were.
-template <int P, bool W16>
-struct RowsBayerShade {
-    __device__ __forceinline__ static const uint8_t* trow(const uint8_t* lut, int bits, int par_y, int par_x) { return lut + ba::lut_row_wide(bits, P, par_y, par_x); }
+    __device__ __forceinline__ const uint8_t* trow(int par_y, int par_x) const { return lut + ba::lut_row_wide(bits, P, par_y, par_x); }
     __device__ __forceinline__ static uint32_t site(const uint8_t* row, int x) {
         if constexpr (W16) return reinterpret_cast<const uint16_t*>(row)[x];
         else return row[x];
     }
-    // site x of the row `row` of the mosaic (row parity py), whose gains are `grow`: shaded and looked up
-    __device__ __forceinline__ static uint32_t one(const uint8_t* row, const uint16_t* grow, int py, int x, const uint8_t* lut, int bits, uint32_t mask,
-                                                   const RawShadeBlack& blk) {
-        const int b = black_of(blk, ba::phase_of(P, py, x & 1));
-        return trow(lut, bits, py, x & 1)[sa::shade(site(row, x) & mask, b, sa::round_term(b), grow[x], (int)mask)];
+    // site x of the row `row` of the mosaic (row parity py), whose gains are `grow`: (shaded and) looked up
+    __device__ __forceinline__ uint32_t one(const uint8_t* row, const uint16_t* grow, int py, int x) const {
+        const uint32_t s = site(row, x) & mask;
+        if constexpr (LS) {
+            const int b = black_of(blk, ba::phase_of(P, py, x & 1));
+            return trow(py, x & 1)[sa::shade(s, b, sa::round_term(b), grow[x], (int)mask)];
+        } else {
+            return trow(py, x & 1)[s];
+        }
     }
-    template <class Post = NoPost>
-    __device__ __forceinline__ static void wide(const Planes& s, const uint8_t* lut, int bits, const uint16_t* gp, const RawShadeBlack& blk, uint8_t* dst,
-                                                int h, int w, int y, int x0, Post post = Post{}) {
+    // the 16 sites from x0 (even: site 0 of every dword is an even column) of that row -> the four dwords of their conditioned bytes
+    __device__ __forceinline__ void row16(const uint8_t* row, const uint16_t* grow, int py, int x0, uint32_t (&m)[4]) const {
+        const uint8_t *ta = trow(py, 0), *tb = trow(py, 1);
+        sa::Black2 k = {};
+        uint32_t g[8] = {};                  // LS: the 16 gains, two a dword
+        if constexpr (LS) {
+            k = sa::black2(black_of(blk, ba::phase_of(P, py, 0)), black_of(blk, ba::phase_of(P, py, 1)));
+            const uint4 ga = *reinterpret_cast<const uint4*>(grow + x0), gb = *reinterpret_cast<const uint4*>(grow + x0 + 8);
+            g[0] = ga.x; g[1] = ga.y; g[2] = ga.z; g[3] = ga.w; g[4] = gb.x; g[5] = gb.y; g[6] = gb.z; g[7] = gb.w;
+        }
+        // four consecutive sites, one dword (bytes) or the two dwords lo, hi (words), whose gains are the two dwords from g[2 j]
+        auto four = [&](int j, uint32_t lo, uint32_t hi) {
+            if constexpr (W16 && LS) m[j] = sa::shade_condition4w(lo, hi, g[2 * j], g[2 * j + 1], k, ta, tb, mask);
+            else if constexpr (W16) m[j] = ba::condition4w(lo, hi, ta, tb, mask);
+            else if constexpr (LS) m[j] = sa::shade_condition4(lo, g[2 * j], g[2 * j + 1], k, ta, tb);
+            else m[j] = ba::condition4(lo, ta, tb);
+        };
+        if constexpr (W16) {
+            const uint4 q0 = *reinterpret_cast<const uint4*>(row + 2 * x0), q1 = *reinterpret_cast<const uint4*>(row + 2 * x0 + 16);
+            four(0, q0.x, q0.y); four(1, q0.z, q0.w); four(2, q1.x, q1.y); four(3, q1.z, q1.w);
+        } else {
+            const uint4 q = *reinterpret_cast<const uint4*>(row + x0);
+            four(0, q.x, 0); four(1, q.y, 0); four(2, q.z, 0); four(3, q.w, 0);
+        }
+    }
+    template <class Post>
+    __device__ __forceinline__ void wide(const Planes& s, uint8_t* dst, int h, int w, int y, int x0, Post post) const {
         if (x0 >= w) return;
-        const uint32_t mask = (1u << bits) - 1u;
         const int cy = ba::tap_pos(y, h), xl = max(x0 - 1, 0), xr = min(x0 + 16, w - 1);
         uint32_t m[3][4], left[3], right[3];
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
             const uint8_t* row = s.y + (size_t)(cy - 1 + r) * s.pitch;
-            const uint16_t* grow = gp + (size_t)(cy - 1 + r) * w;
+            const uint16_t* grow = LS ? gp + (size_t)(cy - 1 + r) * w : nullptr;
             const int py = (cy - 1 + r) & 1;
-            const uint8_t *ta = trow(lut, bits, py, 0), *tb = trow(lut, bits, py, 1);     // (x0 is even: site 0 of every dword is an even column)
-            const sa::Black2 k = sa::black2(black_of(blk, ba::phase_of(P, py, 0)), black_of(blk, ba::phase_of(P, py, 1)));
-            const uint4 ga = *reinterpret_cast<const uint4*>(grow + x0), gb = *reinterpret_cast<const uint4*>(grow + x0 + 8);
-            if constexpr (W16) {
-                const uint4 q0 = *reinterpret_cast<const uint4*>(row + 2 * x0), q1 = *reinterpret_cast<const uint4*>(row + 2 * x0 + 16);
-                m[r][0] = sa::shade_condition4w(q0.x, q0.y, ga.x, ga.y, k, ta, tb, mask); m[r][1] = sa::shade_condition4w(q0.z, q0.w, ga.z, ga.w, k, ta, tb, mask);
-                m[r][2] = sa::shade_condition4w(q1.x, q1.y, gb.x, gb.y, k, ta, tb, mask); m[r][3] = sa::shade_condition4w(q1.z, q1.w, gb.z, gb.w, k, ta, tb, mask);
-            } else {
-                const uint4 q = *reinterpret_cast<const uint4*>(row + x0);
-                m[r][0] = sa::shade_condition4(q.x, ga.x, ga.y, k, ta, tb); m[r][1] = sa::shade_condition4(q.y, ga.z, ga.w, k, ta, tb);
-                m[r][2] = sa::shade_condition4(q.z, gb.x, gb.y, k, ta, tb); m[r][3] = sa::shade_condition4(q.w, gb.z, gb.w, k, ta, tb);
-            }
-            left[r] = one(row, grow, py, xl, lut, bits, mask, blk);
-            right[r] = one(row, grow, py, xr, lut, bits, mask, blk);
+            row16(row, grow, py, x0, m[r]);
+            left[r] = one(row, grow, py, xl);
+            right[r] = one(row, grow, py, xr);
         }
+        // column x0 + j of row r of the three, j = -1 .. 16
         auto at = [&](int r, int j) { return j < 0 ? left[r] : j > 15 ? right[r] : (m[r][j >> 2] >> (8 * (j & 3))) & 255u; };
         uint32_t px[16];
 #pragma unroll
@@ -1180,18 +1026,16 @@ struct RowsBayerShade {
         for (int j = 0; j < 4; ++j) pack_rgb4(px + 4 * j, d + 3 * j);
         store_rgb16(dst + ((size_t)y * w + x0) * 3, d);
     }
-    template <class Post = NoPost>
-    __device__ __forceinline__ static void any(const Planes& s, const uint8_t* lut, int bits, const uint16_t* gp, const RawShadeBlack& blk, uint8_t* dst,
-                                               int h, int w, int y, int x, Post post = Post{}) {
+    template <class Post>
+    __device__ __forceinline__ void any(const Planes& s, uint8_t* dst, int h, int w, int y, int x, Post post) const {
         if (x >= w) return;
-        const uint32_t mask = (1u << bits) - 1u;
         const int cy = ba::tap_pos(y, h), cx = ba::tap_pos(x, w);
         const uint8_t *up = s.y + (size_t)(cy - 1) * s.pitch, *mid = up + s.pitch, *dn = mid + s.pitch;
-        const uint16_t *gu = gp + (size_t)(cy - 1) * w, *gm = gu + w, *gd = gm + w;
-        const int py = cy & 1;
-        auto u = [&](int i) { return one(up, gu, py ^ 1, cx + i, lut, bits, mask, blk); };
-        auto m = [&](int i) { return one(mid, gm, py, cx + i, lut, bits, mask, blk); };
-        auto d = [&](int i) { return one(dn, gd, py ^ 1, cx + i, lut, bits, mask, blk); };
+        const uint16_t *gu = LS ? gp + (size_t)(cy - 1) * w : nullptr, *gm = LS ? gu + w : nullptr, *gd = LS ? gm + w : nullptr;
+        const int py = cy & 1;               // the site's row parity; a neighbour one row away has the other one
+        auto u = [&](int i) { return one(up, gu, py ^ 1, cx + i); };
+        auto m = [&](int i) { return one(mid, gm, py, cx + i); };
+        auto d = [&](int i) { return one(dn, gd, py ^ 1, cx + i); };
         const uint32_t v = ba::demosaic(m(0), m(-1) + m(1), u(0) + d(0), u(-1) + u(1) + d(-1) + d(1), ba::phase(P, cy, cx));
         store_rgb1(dst + ((size_t)y * w + x) * 3, post(v));
     }
@@ -1226,120 +1070,36 @@ __global__ __launch_bounds__(256) void k_rows_to_rgb(std::conditional_t<SURF, Su
     else D::any(p, k, dst, h, w, r0, r1, row, i);
 }
 
-// The raw Bayer row conversion behind a raw table (lt_set_raw_lut): k_rows_to_rgb's bodies over the conditioned mosaic, 3 x 18 lookups per
-// 16 pixels (wide) or 9 per pixel, the table staged in LDS by the whole workgroup before any thread leaves.  Launched in k_rows_to_rgb's
-// place whenever a table is set.
-template <int PATTERN, bool SURF, bool WIDE>
+// The raw Bayer row conversion behind a raw table: RowsRaw's bodies in k_rows_to_rgb's two launch shapes (64 threads for the wide body, 256
+// for the byte-wise one), STAGES and `r` as k_raw_walk_rows takes them.  The table, and the curve in front of it, are staged in 16-byte
+// pieces by the whole workgroup before any thread leaves: static LDS for 8-bit samples, the launch's dynamic LDS for 16-bit ones.  Launched
+// in k_rows_to_rgb's place whenever there is a table.
+template <int PATTERN, bool SURF, bool WIDE, int STAGES>
 __global__ __launch_bounds__(256) void k_raw_rows_rgb(std::conditional_t<SURF, SurfChunk, DenseFrames> src, uint8_t* __restrict__ rgb,
-                                                     size_t rgb_stride, int w, int r0, int h, const uint32_t* __restrict__ raw_lut) {
-    __shared__ alignas(16) uint8_t s_lut[1024];
-    // (the wide body is launched with 64 threads, 16 bytes of the table each; the byte-wise one with 256, a dword each)
-    if constexpr (WIDE) reinterpret_cast<uint4*>(s_lut)[threadIdx.x] = reinterpret_cast<const uint4*>(raw_lut)[threadIdx.x];
-    else reinterpret_cast<uint32_t*>(s_lut)[threadIdx.x] = raw_lut[threadIdx.x];
+                                                     size_t rgb_stride, int w, int r0, int h, RawStages r) {
+    constexpr bool W16 = (STAGES & 1) != 0, CC = (STAGES & 2) != 0, LS = (STAGES & 4) != 0;
+    constexpr int THREADS = WIDE ? 64 : 256, CURVE = CC ? 256 : 0;
+    uint8_t* lds;
+    if constexpr (W16) {
+        lds = s_lut_wide;
+    } else {
+        __shared__ alignas(16) uint8_t s_tab[CURVE + 1024];
+        lds = s_tab;
+    }
+    const int bits = W16 ? r.bits : 8;
+    for (int i = threadIdx.x; i < CURVE / 16 + (1 << (bits - 2)); i += THREADS) reinterpret_cast<uint4*>(lds)[i] = reinterpret_cast<const uint4*>(r.table)[i];
     __syncthreads();
-    typedef RowsBayerLut<PATTERN> D;
-    Planes p;
-    if constexpr (SURF) p = surf_planes(src.e[blockIdx.z]);
-    else p = RowsBayer<PATTERN>::dense(src.p + (size_t)blockIdx.z * src.stride, h, w);
-    uint8_t* dst = rgb + (size_t)blockIdx.z * rgb_stride;
-    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x), row = r0 + (int)blockIdx.y;
-    if constexpr (WIDE) D::wide(p, s_lut, dst, h, w, row, i * 16);
-    else D::any(p, s_lut, dst, h, w, row, i);
-}
-
-// The row conversion of 10- / 12-bit raw Bayer frames behind their wide raw table (lt_set_raw_lut_wide): k_raw_rows_rgb's two launch shapes,
-// the table (4 << bits bytes, dynamic LDS) staged in 16-byte pieces by the workgroup's 64 (wide) or 256 threads before any of them leaves.
-template <int PATTERN, bool SURF, bool WIDE>
-__global__ __launch_bounds__(256) void k_raw16_rows_rgb(std::conditional_t<SURF, SurfChunk, DenseFrames> src, uint8_t* __restrict__ rgb,
-                                                       size_t rgb_stride, int w, int r0, int h, const uint32_t* __restrict__ raw_lut, int bits) {
-    constexpr int THREADS = WIDE ? 64 : 256;
-    for (int i = threadIdx.x; i < (1 << (bits - 2)); i += THREADS) reinterpret_cast<uint4*>(s_lut_wide)[i] = reinterpret_cast<const uint4*>(raw_lut)[i];
-    __syncthreads();
-    typedef RowsBayer16Lut<PATTERN> D;
+    typedef RowsRaw<PATTERN, W16, LS> D;
+    const D body{lds + CURVE, bits, (1u << bits) - 1u, r.gains, r.blk};
     Planes p;
     if constexpr (SURF) p = surf_planes(src.e[blockIdx.z]);
     else p = D::dense(src.p + (size_t)blockIdx.z * src.stride, h, w);
     uint8_t* dst = rgb + (size_t)blockIdx.z * rgb_stride;
     const int i = (int)(blockIdx.x * THREADS + threadIdx.x), row = r0 + (int)blockIdx.y;
-    if constexpr (WIDE) D::wide(p, s_lut_wide, bits, dst, h, w, row, i * 16);
-    else D::any(p, s_lut_wide, bits, dst, h, w, row, i);
-}
-
-// The two row conversions above with the colour stage (lt_set_raw_color) on every demosaiced pixel: the same bodies and launch shapes,
-// `raw_cc` the output curve followed by the table (k_cc_walk_rows), staged together.
-template <int PATTERN, bool SURF, bool WIDE>
-__global__ __launch_bounds__(256) void k_cc_rows_rgb(std::conditional_t<SURF, SurfChunk, DenseFrames> src, uint8_t* __restrict__ rgb,
-                                                    size_t rgb_stride, int w, int r0, int h, const uint32_t* __restrict__ raw_cc, RawColorMat cm) {
-    __shared__ alignas(16) uint8_t s_cc[256 + 1024];
-    constexpr int THREADS = WIDE ? 64 : 256;
-    for (int i = threadIdx.x; i < 80; i += THREADS) reinterpret_cast<uint4*>(s_cc)[i] = reinterpret_cast<const uint4*>(raw_cc)[i];
-    __syncthreads();
-    typedef RowsBayerLut<PATTERN> D;
-    Planes p;
-    if constexpr (SURF) p = surf_planes(src.e[blockIdx.z]);
-    else p = RowsBayer<PATTERN>::dense(src.p + (size_t)blockIdx.z * src.stride, h, w);
-    uint8_t* dst = rgb + (size_t)blockIdx.z * rgb_stride;
-    const int i = (int)(blockIdx.x * THREADS + threadIdx.x), row = r0 + (int)blockIdx.y;
-    const ColorPost post{cm, s_cc};
-    if constexpr (WIDE) D::wide(p, s_cc + 256, dst, h, w, row, i * 16, post);
-    else D::any(p, s_cc + 256, dst, h, w, row, i, post);
-}
-template <int PATTERN, bool SURF, bool WIDE>
-__global__ __launch_bounds__(256) void k_cc16_rows_rgb(std::conditional_t<SURF, SurfChunk, DenseFrames> src, uint8_t* __restrict__ rgb,
-                                                      size_t rgb_stride, int w, int r0, int h, const uint32_t* __restrict__ raw_cc, int bits,
-                                                      RawColorMat cm) {
-    constexpr int THREADS = WIDE ? 64 : 256;
-    for (int i = threadIdx.x; i < 16 + (1 << (bits - 2)); i += THREADS) reinterpret_cast<uint4*>(s_lut_wide)[i] = reinterpret_cast<const uint4*>(raw_cc)[i];
-    __syncthreads();
-    typedef RowsBayer16Lut<PATTERN> D;
-    Planes p;
-    if constexpr (SURF) p = surf_planes(src.e[blockIdx.z]);
-    else p = D::dense(src.p + (size_t)blockIdx.z * src.stride, h, w);
-    uint8_t* dst = rgb + (size_t)blockIdx.z * rgb_stride;
-    const int i = (int)(blockIdx.x * THREADS + threadIdx.x), row = r0 + (int)blockIdx.y;
-    const ColorPost post{cm, s_lut_wide};
-    if constexpr (WIDE) D::wide(p, s_lut_wide + 256, bits, dst, h, w, row, i * 16, post);
-    else D::any(p, s_lut_wide + 256, bits, dst, h, w, row, i, post);
-}
-
-// The four row conversions above behind the lens-shading correction (lt_set_raw_shading): RowsBayerShade's bodies in the same launch shapes;
-// `table`, `cm`, `gains`, `blk` as k_ls_walk_rows takes them, table (and curve) staged in 16-byte pieces.
-template <int PATTERN, bool SURF, bool WIDE, bool CC>
-__global__ __launch_bounds__(256) void k_ls_rows_rgb(std::conditional_t<SURF, SurfChunk, DenseFrames> src, uint8_t* __restrict__ rgb,
-                                                    size_t rgb_stride, int w, int r0, int h, const uint32_t* __restrict__ table, RawColorMat cm,
-                                                    const uint16_t* __restrict__ gains, RawShadeBlack blk) {
-    constexpr int THREADS = WIDE ? 64 : 256, CURVE = CC ? 256 : 0;
-    __shared__ alignas(16) uint8_t s_ls[CURVE + 1024];
-    for (int i = threadIdx.x; i < (CURVE + 1024) / 16; i += THREADS) reinterpret_cast<uint4*>(s_ls)[i] = reinterpret_cast<const uint4*>(table)[i];
-    __syncthreads();
-    typedef RowsBayerShade<PATTERN, false> D;
-    Planes p;
-    if constexpr (SURF) p = surf_planes(src.e[blockIdx.z]);
-    else p = RowsBayer<PATTERN>::dense(src.p + (size_t)blockIdx.z * src.stride, h, w);
-    uint8_t* dst = rgb + (size_t)blockIdx.z * rgb_stride;
-    const int i = (int)(blockIdx.x * THREADS + threadIdx.x), row = r0 + (int)blockIdx.y;
     std::conditional_t<CC, ColorPost, NoPost> post{};
-    if constexpr (CC) post = ColorPost{cm, s_ls};
-    if constexpr (WIDE) D::wide(p, s_ls + CURVE, 8, gains, blk, dst, h, w, row, i * 16, post);
-    else D::any(p, s_ls + CURVE, 8, gains, blk, dst, h, w, row, i, post);
-}
-template <int PATTERN, bool SURF, bool WIDE, bool CC>
-__global__ __launch_bounds__(256) void k_ls16_rows_rgb(std::conditional_t<SURF, SurfChunk, DenseFrames> src, uint8_t* __restrict__ rgb,
-                                                      size_t rgb_stride, int w, int r0, int h, const uint32_t* __restrict__ table, int bits,
-                                                      RawColorMat cm, const uint16_t* __restrict__ gains, RawShadeBlack blk) {
-    constexpr int THREADS = WIDE ? 64 : 256, CURVE = CC ? 256 : 0;
-    for (int i = threadIdx.x; i < CURVE / 16 + (1 << (bits - 2)); i += THREADS) reinterpret_cast<uint4*>(s_lut_wide)[i] = reinterpret_cast<const uint4*>(table)[i];
-    __syncthreads();
-    typedef RowsBayerShade<PATTERN, true> D;
-    Planes p;
-    if constexpr (SURF) p = surf_planes(src.e[blockIdx.z]);
-    else p = RowsBayer16Lut<PATTERN>::dense(src.p + (size_t)blockIdx.z * src.stride, h, w);
-    uint8_t* dst = rgb + (size_t)blockIdx.z * rgb_stride;
-    const int i = (int)(blockIdx.x * THREADS + threadIdx.x), row = r0 + (int)blockIdx.y;
-    std::conditional_t<CC, ColorPost, NoPost> post{};
-    if constexpr (CC) post = ColorPost{cm, s_lut_wide};
-    if constexpr (WIDE) D::wide(p, s_lut_wide + CURVE, bits, gains, blk, dst, h, w, row, i * 16, post);
-    else D::any(p, s_lut_wide + CURVE, bits, gains, blk, dst, h, w, row, i, post);
+    if constexpr (CC) post = ColorPost{r.cm, lds};
+    if constexpr (WIDE) body.wide(p, dst, h, w, row, i * 16, post);
+    else body.any(p, dst, h, w, row, i, post);
 }
 
 // Rows [r0, r1) of RGB surfaces -> the same rows of the slots' camera frames (row_bytes = 3 w, dense): a pitched row copy, one
@@ -1772,53 +1532,51 @@ static void with_layout(int layout, F&& f) {
     }
 }
 
-// the matrix of a colour stage as the kernels' argument
-static RawColorMat color_mat(const RawColor& cc) {
-    RawColorMat m;
-    for (int i = 0; i < 9; ++i) m.m[i] = cc.m[i];
-    return m;
-}
-// ... and the pedestals of a shading map; the matrix the k_ls* kernels are given (without a colour stage: none, never read)
-static RawShadeBlack shade_black(const RawShade& ls) { return RawShadeBlack{{ls.black[0], ls.black[1], ls.black[2], ls.black[3]}}; }
-static RawColorMat color_mat_of(const RawColor* cc) { return cc ? color_mat(*cc) : RawColorMat{}; }
-
-// pattern (0 .. 3) -> f(std::integral_constant<int, pattern>{}): the 10- / 12-bit raw Bayer layouts, which have kernels of their own and
-// never go through with_layout
+// the pattern of a raw Bayer layout (its low two bits) -> f(std::integral_constant<int, pattern>{}), for the raw kernels
 template <class F>
-static void with_pattern(int pattern, F&& f) {
-    switch (pattern & 3) {
+static void with_pattern(int layout, F&& f) {
+    switch (layout & 3) {
         case 0: return f(std::integral_constant<int, 0>{});
         case 1: return f(std::integral_constant<int, 1>{});
         case 2: return f(std::integral_constant<int, 2>{});
         case 3: return f(std::integral_constant<int, 3>{});
     }
 }
+// ... and what runs around their demosaic -> f(std::integral_constant<int, STAGES>{}): bit 0 16-bit samples, bit 1 the colour stage, bit 2 the
+// shading map
+template <class F>
+static void with_stages(const RawStages& raw, F&& f) {
+    switch ((raw.bits > 8 ? 1 : 0) | (raw.color ? 2 : 0) | (raw.gains ? 4 : 0)) {
+        case 0: return f(std::integral_constant<int, 0>{});
+        case 1: return f(std::integral_constant<int, 1>{});
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 5: return f(std::integral_constant<int, 5>{});
+        case 6: return f(std::integral_constant<int, 6>{});
+        case 7: return f(std::integral_constant<int, 7>{});
+    }
+}
+// the dynamic LDS of a raw kernel: the wide table, behind the curve where there is a colour stage (8-bit samples: static LDS)
+static size_t raw_dynamic_lds(const RawStages& raw) { return raw.bits > 8 ? ((size_t)4 << raw.bits) + (raw.color ? 256 : 0) : 0; }
 
-// One launch of the walk over the n frames of `src`.  Plain RGB frames of the slots that are not dword-aligned, dword-strided and below
-// 2^30 bytes (a larger frame: 64-bit addresses) -- or all of them, any_byte -- take the form that fetches at any byte.
+// One launch of the walk over the n frames of `src`: behind a raw table the raw walk, else the walk of the layout.  Plain RGB frames of the
+// slots that are not dword-aligned, dword-strided and below 2^30 bytes (a larger frame: 64-bit addresses) -- or all of them, any_byte --
+// take the form that fetches at any byte.
 template <bool PER_SLOT>
 static void launch_walk(hipStream_t s, dim3 grid, FrameSource src, int layout, YuvCoef k, const int16_t* uxy, const uint16_t* ufrac,
                         const CalTables* sets, const CalIds& ids, FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n, int fpb,
-                        bool any_byte, const uint32_t* raw_lut, const RawColor* cc, const RawShade* ls) {
+                        bool any_byte, const RawStages& raw) {
     const bool aligned = !any_byte && ((uintptr_t)src.frames & 3) == 0 && (src.stride & 3) == 0 && src.stride < (1u << 30);
     const int remap = xcd_remap();
-    if (const int bits = raw_wide_bits(layout)) {        // 10- / 12-bit raw Bayer: always behind its table, 4 << bits bytes of LDS
+    if (raw.table) {
         with_pattern(layout, [&](auto p) {
-            constexpr int P = decltype(p)::value;
-            if (ls) {                        // ... and a shading map: the wrapped walk's LDS, with or without a colour stage
-                auto k_ls = cc ? (src.tab ? k_ls16_walk_rows<P, SRC_SURFACES, PER_SLOT, true> : k_ls16_walk_rows<P, SRC_SLOTS, PER_SLOT, true>)
-                               : (src.tab ? k_ls16_walk_rows<P, SRC_SURFACES, PER_SLOT, false> : k_ls16_walk_rows<P, SRC_SLOTS, PER_SLOT, false>);
-                hipLaunchKernelGGL(k_ls, grid, dim3(256), ((size_t)4 << bits) + (cc ? 256 : 0), s, src.tab, src.frames, src.stride, uxy, ufrac, sets, ids, g, und, und_px, first_slot, n, fpb, remap,
-                                   cc ? cc->table : raw_lut, bits, color_mat_of(cc), ls->plane, shade_black(*ls));
-                return;
-            }
-            if (cc) {                        // ... and a colour stage: the curve's 256 bytes in front of the table
-                auto k_cc = src.tab ? k_cc16_walk_rows<P, SRC_SURFACES, PER_SLOT> : k_cc16_walk_rows<P, SRC_SLOTS, PER_SLOT>;
-                hipLaunchKernelGGL(k_cc, grid, dim3(256), ((size_t)4 << bits) + 256, s, src.tab, src.frames, src.stride, uxy, ufrac, sets, ids, g, und, und_px, first_slot, n, fpb, remap, cc->table, bits, color_mat(*cc));
-                return;
-            }
-            auto k_raw = src.tab ? k_raw16_walk_rows<P, SRC_SURFACES, PER_SLOT> : k_raw16_walk_rows<P, SRC_SLOTS, PER_SLOT>;
-            hipLaunchKernelGGL(k_raw, grid, dim3(256), (size_t)4 << bits, s, src.tab, src.frames, src.stride, uxy, ufrac, sets, ids, g, und, und_px, first_slot, n, fpb, remap, raw_lut, bits);
+            with_stages(raw, [&](auto st) {
+                constexpr int P = decltype(p)::value, ST = decltype(st)::value;
+                auto k_walk = src.tab ? k_raw_walk_rows<P, SRC_SURFACES, PER_SLOT, ST> : k_raw_walk_rows<P, SRC_SLOTS, PER_SLOT, ST>;
+                hipLaunchKernelGGL(k_walk, grid, dim3(256), raw_dynamic_lds(raw), s, src.tab, src.frames, src.stride, uxy, ufrac, sets, ids, g, und, und_px,
+                                   first_slot, n, fpb, remap, raw);
+            });
         });
         return;
     }
@@ -1827,25 +1585,6 @@ static void launch_walk(hipStream_t s, dim3 grid, FrameSource src, int layout, Y
         auto launch = [&](auto k_walk) {
             hipLaunchKernelGGL(k_walk, grid, dim3(256), 0, s, src.tab, src.frames, src.stride, k, uxy, ufrac, sets, ids, g, und, und_px, first_slot, n, fpb, remap);
         };
-        if constexpr (L >= 16) {
-            if (ls) {                        // raw Bayer with a shading map: its walk, behind the raw table (or the identity table) and the colour stage, if any
-                auto k_ls = cc ? (src.tab ? k_ls_walk_rows<L - 16, SRC_SURFACES, PER_SLOT, true> : k_ls_walk_rows<L - 16, SRC_SLOTS, PER_SLOT, true>)
-                               : (src.tab ? k_ls_walk_rows<L - 16, SRC_SURFACES, PER_SLOT, false> : k_ls_walk_rows<L - 16, SRC_SLOTS, PER_SLOT, false>);
-                hipLaunchKernelGGL(k_ls, grid, dim3(256), 0, s, src.tab, src.frames, src.stride, uxy, ufrac, sets, ids, g, und, und_px, first_slot, n, fpb, remap,
-                                   cc ? cc->table : raw_lut, color_mat_of(cc), ls->plane, shade_black(*ls));
-                return;
-            }
-            if (cc) {                        // raw Bayer with a colour stage: its walk, behind the raw table or the identity table
-                auto k_cc = src.tab ? k_cc_walk_rows<L - 16, SRC_SURFACES, PER_SLOT> : k_cc_walk_rows<L - 16, SRC_SLOTS, PER_SLOT>;
-                hipLaunchKernelGGL(k_cc, grid, dim3(256), 0, s, src.tab, src.frames, src.stride, uxy, ufrac, sets, ids, g, und, und_px, first_slot, n, fpb, remap, cc->table, color_mat(*cc));
-                return;
-            }
-            if (raw_lut) {                   // raw Bayer behind a raw table: the conditioned walk, whatever the table holds
-                auto k_raw = src.tab ? k_raw_walk_rows<L - 16, SRC_SURFACES, PER_SLOT> : k_raw_walk_rows<L - 16, SRC_SLOTS, PER_SLOT>;
-                hipLaunchKernelGGL(k_raw, grid, dim3(256), 0, s, src.tab, src.frames, src.stride, uxy, ufrac, sets, ids, g, und, und_px, first_slot, n, fpb, remap, raw_lut);
-                return;
-            }
-        }
         if (src.tab) launch(k_undistort_rows<L, SRC_SURFACES, PER_SLOT>);
         else if (L != 0 || aligned) launch(k_undistort_rows<L, SRC_SLOTS, PER_SLOT>);
         else launch(k_undistort_rows<0, SRC_SLOTS_ANY_BYTE, PER_SLOT>);
@@ -1853,7 +1592,7 @@ static void launch_walk(hipStream_t s, dim3 grid, FrameSource src, int layout, Y
 }
 
 void launch_undistort_rows(hipStream_t s, FrameSource src, int layout, YuvCoef k, const int16_t* uxy, const uint16_t* ufrac,
-                           FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n, const uint32_t* raw_lut, const RawColor* cc, const RawShade* ls) {
+                           FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n, const RawStages& raw) {
     if (n <= 0 || g.nrows <= 0) return;
     int fpb = frames_per_thread(n);
     // the slots of a walk are addressed by a 32-bit offset into one buffer resource: a walk stays below 2^30 bytes (one frame
@@ -1861,42 +1600,25 @@ void launch_undistort_rows(hipStream_t s, FrameSource src, int layout, YuvCoef k
     if (!src.tab) fpb = (int)std::max<size_t>(1, std::min<size_t>((size_t)fpb, (((size_t)1 << 30) - 1) / src.stride));
     const dim3 grid((g.img_w + 255) / 256, g.nrows, (n + fpb - 1) / fpb);
     static const bool unaligned = [] { const char* e = LT_EXP_ENV("LT_UNDISTORT_UNALIGNED"); return e && e[0] == '1'; }();   // A/B
-    launch_walk<false>(s, grid, src, layout, k, uxy, ufrac, nullptr, CalIds{}, g, und, und_px, first_slot, n, fpb, unaligned, raw_lut, cc, ls);
+    launch_walk<false>(s, grid, src, layout, k, uxy, ufrac, nullptr, CalIds{}, g, und, und_px, first_slot, n, fpb, unaligned, raw);
 }
 
 // The row conversion of n frames in `layout` (not 0), dense or from surfaces: the 16-column kernel where the width and every base and
-// pitch of the launch (`bits`: all of them ORed) are multiples of 16, the byte-wise one otherwise.
+// pitch of the launch (`bits`: all of them ORed) are multiples of 16, the byte-wise one otherwise; behind a raw table the raw kernel, in the
+// same two launch shapes.
 template <bool SURF, class Src>
 static void launch_rows_to_rgb(hipStream_t s, int layout, const Src& src, size_t bits, YuvCoef k, uint8_t* rgb, size_t rgb_stride, int h, int w,
-                               int r0, int r1, int n, const uint32_t* raw_lut, const RawColor* cc, const RawShade* ls) {
-    if (const int depth = raw_wide_bits(layout)) {       // 10- / 12-bit raw Bayer: always behind its table, the same two launch shapes
+                               int r0, int r1, int n, const RawStages& raw) {
+    const bool wide = (w & 15) == 0 && (bits & 15) == 0;
+    const dim3 block(wide ? 64 : 256);
+    if (raw.table) {
+        const dim3 grid((unsigned)(wide ? (w / 16 + 63) / 64 : (w + 255) / 256), (unsigned)(r1 - r0), (unsigned)n);
         with_pattern(layout, [&](auto p) {
-            constexpr int P = decltype(p)::value;
-            const unsigned rows = (unsigned)(r1 - r0);
-            if (ls) {                        // ... and a shading map
-                const bool wide = (w & 15) == 0 && (bits & 15) == 0;
-                const dim3 grid(wide ? (unsigned)((w / 16 + 63) / 64) : (unsigned)((w + 255) / 256), rows, (unsigned)n), block(wide ? 64 : 256);
-                auto k_ls = cc ? (wide ? k_ls16_rows_rgb<P, SURF, true, true> : k_ls16_rows_rgb<P, SURF, false, true>)
-                               : (wide ? k_ls16_rows_rgb<P, SURF, true, false> : k_ls16_rows_rgb<P, SURF, false, false>);
-                hipLaunchKernelGGL(k_ls, grid, block, ((size_t)4 << depth) + (cc ? 256 : 0), s, src, rgb, rgb_stride, w, r0, h, cc ? cc->table : raw_lut, depth,
-                                   color_mat_of(cc), ls->plane, shade_black(*ls));
-                return;
-            }
-            if (cc) {                        // ... and a colour stage
-                if ((w & 15) == 0 && (bits & 15) == 0)
-                    hipLaunchKernelGGL((k_cc16_rows_rgb<P, SURF, true>), dim3((unsigned)((w / 16 + 63) / 64), rows, (unsigned)n), dim3(64), ((size_t)4 << depth) + 256, s,
-                                       src, rgb, rgb_stride, w, r0, h, cc->table, depth, color_mat(*cc));
-                else
-                    hipLaunchKernelGGL((k_cc16_rows_rgb<P, SURF, false>), dim3((unsigned)((w + 255) / 256), rows, (unsigned)n), dim3(256), ((size_t)4 << depth) + 256, s,
-                                       src, rgb, rgb_stride, w, r0, h, cc->table, depth, color_mat(*cc));
-                return;
-            }
-            if ((w & 15) == 0 && (bits & 15) == 0)
-                hipLaunchKernelGGL((k_raw16_rows_rgb<P, SURF, true>), dim3((unsigned)((w / 16 + 63) / 64), rows, (unsigned)n), dim3(64), (size_t)4 << depth, s,
-                                   src, rgb, rgb_stride, w, r0, h, raw_lut, depth);
-            else
-                hipLaunchKernelGGL((k_raw16_rows_rgb<P, SURF, false>), dim3((unsigned)((w + 255) / 256), rows, (unsigned)n), dim3(256), (size_t)4 << depth, s,
-                                   src, rgb, rgb_stride, w, r0, h, raw_lut, depth);
+            with_stages(raw, [&](auto st) {
+                constexpr int P = decltype(p)::value, ST = decltype(st)::value;
+                auto k_rows = wide ? k_raw_rows_rgb<P, SURF, true, ST> : k_raw_rows_rgb<P, SURF, false, ST>;
+                hipLaunchKernelGGL(k_rows, grid, block, raw_dynamic_lds(raw), s, src, rgb, rgb_stride, w, r0, h, raw);
+            });
         });
         return;
     }
@@ -1905,49 +1627,18 @@ static void launch_rows_to_rgb(hipStream_t s, int layout, const Src& src, size_t
         if constexpr (L != 0) {
             typedef RowsOf<L> D;
             const unsigned rows = (unsigned)(D::CHROMA_ROWS ? ((r1 + 1) >> 1) - (r0 >> 1) : r1 - r0);
-            if constexpr (L >= 16) {
-                if (ls) {                    // raw Bayer with a shading map: its bodies, the same two launch shapes
-                    const bool wide = (w & 15) == 0 && (bits & 15) == 0;
-                    const dim3 grid(wide ? (unsigned)((w / 16 + 63) / 64) : (unsigned)((w + 255) / 256), rows, (unsigned)n), block(wide ? 64 : 256);
-                    auto k_ls = cc ? (wide ? k_ls_rows_rgb<L - 16, SURF, true, true> : k_ls_rows_rgb<L - 16, SURF, false, true>)
-                                   : (wide ? k_ls_rows_rgb<L - 16, SURF, true, false> : k_ls_rows_rgb<L - 16, SURF, false, false>);
-                    hipLaunchKernelGGL(k_ls, grid, block, 0, s, src, rgb, rgb_stride, w, r0, h, cc ? cc->table : raw_lut, color_mat_of(cc), ls->plane, shade_black(*ls));
-                    return;
-                }
-                if (cc) {                    // raw Bayer with a colour stage: its bodies, the same two launch shapes
-                    if ((w & 15) == 0 && (bits & 15) == 0)
-                        hipLaunchKernelGGL((k_cc_rows_rgb<L - 16, SURF, true>), dim3((unsigned)((w / 16 + 63) / 64), rows, (unsigned)n), dim3(64), 0, s,
-                                           src, rgb, rgb_stride, w, r0, h, cc->table, color_mat(*cc));
-                    else
-                        hipLaunchKernelGGL((k_cc_rows_rgb<L - 16, SURF, false>), dim3((unsigned)((w + 255) / 256), rows, (unsigned)n), dim3(256), 0, s,
-                                           src, rgb, rgb_stride, w, r0, h, cc->table, color_mat(*cc));
-                    return;
-                }
-                if (raw_lut) {               // raw Bayer behind a raw table: the conditioned bodies, the same two launch shapes
-                    if ((w & 15) == 0 && (bits & 15) == 0)
-                        hipLaunchKernelGGL((k_raw_rows_rgb<L - 16, SURF, true>), dim3((unsigned)((w / 16 + 63) / 64), rows, (unsigned)n), dim3(64), 0, s,
-                                           src, rgb, rgb_stride, w, r0, h, raw_lut);
-                    else
-                        hipLaunchKernelGGL((k_raw_rows_rgb<L - 16, SURF, false>), dim3((unsigned)((w + 255) / 256), rows, (unsigned)n), dim3(256), 0, s,
-                                           src, rgb, rgb_stride, w, r0, h, raw_lut);
-                    return;
-                }
-            }
-            if ((w & 15) == 0 && (bits & 15) == 0)
-                hipLaunchKernelGGL((k_rows_to_rgb<L, SURF, true>), dim3((unsigned)((w / 16 + 63) / 64), rows, (unsigned)n), dim3(64), 0, s,
-                                   src, rgb, rgb_stride, w, r0, r1, h, k);
-            else
-                hipLaunchKernelGGL((k_rows_to_rgb<L, SURF, false>), dim3((unsigned)((w / D::ANY_COLS + 255) / 256), rows, (unsigned)n), dim3(256), 0, s,
-                                   src, rgb, rgb_stride, w, r0, r1, h, k);
+            const dim3 grid((unsigned)(wide ? (w / 16 + 63) / 64 : (w / D::ANY_COLS + 255) / 256), rows, (unsigned)n);
+            auto k_rows = wide ? k_rows_to_rgb<L, SURF, true> : k_rows_to_rgb<L, SURF, false>;
+            hipLaunchKernelGGL(k_rows, grid, block, 0, s, src, rgb, rgb_stride, w, r0, r1, h, k);
         }
     });
 }
 
 void launch_yuv_rows_to_rgb(hipStream_t s, int layout, const uint8_t* yuv, size_t yuv_stride, YuvCoef k, uint8_t* rgb,
-                            size_t rgb_stride, int h, int w, int r0, int r1, int n, const uint32_t* raw_lut, const RawColor* cc, const RawShade* ls) {
+                            size_t rgb_stride, int h, int w, int r0, int r1, int n, const RawStages& raw) {
     if (n <= 0 || r1 <= r0) return;
     launch_rows_to_rgb<false>(s, layout, DenseFrames{yuv, yuv_stride}, yuv_stride | rgb_stride | (size_t)(uintptr_t)yuv | (size_t)(uintptr_t)rgb, k,
-                              rgb, rgb_stride, h, w, r0, r1, n, raw_lut, cc, ls);
+                              rgb, rgb_stride, h, w, r0, r1, n, raw);
 }
 
 void launch_shade_expand(hipStream_t s, const uint16_t* mesh, int mw, int mh, int pattern, uint16_t* plane, int h, int w) {
@@ -1964,7 +1655,7 @@ void launch_write_surf_entries(hipStream_t s, SurfEntry* tab, int first, const S
 }
 
 void launch_surf_rows_to_rgb(hipStream_t s, int layout, const SurfEntry* entries, YuvCoef k, uint8_t* rgb, size_t rgb_stride, int h, int w,
-                             int r0, int r1, int n, const uint32_t* raw_lut, const RawColor* cc, const RawShade* ls) {
+                             int r0, int r1, int n, const RawStages& raw) {
     if (n <= 0 || r1 <= r0) return;
     for (int i = 0; i < n; i += SurfChunk::N) {
         const int m = std::min(n - i, (int)SurfChunk::N);
@@ -1984,7 +1675,7 @@ void launch_surf_rows_to_rgb(hipStream_t s, int layout, const SurfEntry* entries
             else
                 hipLaunchKernelGGL(k_surf_copy_rows<false>, dim3((unsigned)((row_bytes + 255) / 256), (unsigned)(r1 - r0), (unsigned)m), dim3(256), 0, s, ch, dst, rgb_stride, row_bytes, r0);
         } else {
-            launch_rows_to_rgb<true>(s, layout, ch, bits, k, dst, rgb_stride, h, w, r0, r1, m, raw_lut, cc, ls);
+            launch_rows_to_rgb<true>(s, layout, ch, bits, k, dst, rgb_stride, h, w, r0, r1, m, raw);
         }
     }
 }
@@ -2014,13 +1705,13 @@ static CalIds pack_ids(const uint8_t* ids, int m) {
 }
 
 void launch_undistort_cal(hipStream_t s, FrameSource src, int layout, YuvCoef k, const CalTables* sets, const uint8_t* ids,
-                          FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n, const uint32_t* raw_lut, const RawColor* cc, const RawShade* ls) {
+                          FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n, const RawStages& raw) {
     if (n <= 0 || g.nrows <= 0) return;
     for (int i = 0; i < n; i += CalIds::N) {
         const int m = std::min(n - i, (int)CalIds::N);
         const dim3 grid((g.img_w + 255) / 256, g.nrows, m);
         const FrameSource part = src.tab ? src : FrameSource::slots(src.frames + (size_t)i * src.stride, src.stride);
-        launch_walk<true>(s, grid, part, layout, k, nullptr, nullptr, sets, pack_ids(ids + i, m), g, und, und_px, first_slot + i, m, 1, false, raw_lut, cc, ls);
+        launch_walk<true>(s, grid, part, layout, k, nullptr, nullptr, sets, pack_ids(ids + i, m), g, und, und_px, first_slot + i, m, 1, false, raw);
     }
 }
 

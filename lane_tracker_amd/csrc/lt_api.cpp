@@ -916,32 +916,30 @@ static int install_wide_table(lt_ctx* c, int layout) {
     return write_wide_table(c, c->raw_lut_wide.data());
 }
 
-// the 256 bytes of `curve` followed by table (table_bytes) -> *d (device memory, allocated here where it is null), for the k_cc* kernels;
-// and the matrix widened into cc, whose table becomes *d.  A null table: the 8-bit identity.
-static int make_raw_color(const uint8_t* table, size_t table_bytes, const int16_t* ccm, const uint8_t* curve, uint32_t** d, RawColor* cc) {
-    std::vector<uint8_t> host(table_bytes + 256);
-    std::memcpy(host.data(), curve, 256);
-    if (table) std::memcpy(host.data() + 256, table, table_bytes);
-    else for (size_t i = 0; i < table_bytes; ++i) host[256 + i] = (uint8_t)(i & 255u);
-    int rc;
-    if (!*d && (rc = dev_alloc(d, host.size() / 4))) return rc;
-    HIP_TRY(hipMemcpy(*d, host.data(), host.size(), hipMemcpyHostToDevice));
-    for (int i = 0; i < 9; ++i) cc->m[i] = ccm[i];
-    cc->table = *d;
-    return LT_OK;
+// What a raw kernel of `layout` stages (RawStages::table), on the host: the 256 bytes of `curve` (null: no colour stage, none), then the
+// table -- `lut`, or where that is null the 8-bit identity / the 10- and 12-bit default.
+static std::vector<uint8_t> staged_table(int layout, const uint8_t* lut, const uint8_t* curve) {
+    const size_t head = curve ? 256 : 0, bytes = is_bayer_wide(layout) ? (size_t)4 << raw_bits(layout) : 1024;
+    std::vector<uint8_t> t(head + bytes);
+    if (curve) std::memcpy(t.data(), curve, 256);
+    if (lut) std::memcpy(t.data() + head, lut, bytes);
+    else if (is_bayer_wide(layout)) default_wide_table(raw_bits(layout), t.data() + head);
+    else for (size_t i = 0; i < bytes; ++i) t[head + i] = (uint8_t)(i & 255u);
+    return t;
 }
-// the context's colour stage (raw_ccm, raw_curve) and the table its layout is conditioned with, into d_raw_cc / raw_cc; nothing in flight
+// the context's output curve and the table its layout is conditioned with, into d_raw_cc; nothing in flight
 static int write_raw_color(lt_ctx* c) {
-    const bool wide = is_bayer_wide(c->in_layout);
-    const size_t table_bytes = wide ? c->raw_lut_wide.size() : sizeof c->raw_lut;
-    if (c->raw_cc_bytes != table_bytes + 256) {
+    const std::vector<uint8_t> t = staged_table(c->in_layout, is_bayer_wide(c->in_layout) ? c->raw_lut_wide.data() : c->raw_lut_set ? c->raw_lut : nullptr,
+                                                c->raw_curve);
+    int rc;
+    if (c->raw_cc_bytes != t.size()) {
         dev_free(c->d_raw_cc);
         c->raw_cc_bytes = 0;
     }
-    const int rc = make_raw_color(wide ? c->raw_lut_wide.data() : c->raw_lut_set ? c->raw_lut : nullptr, table_bytes, c->raw_ccm, c->raw_curve,
-                                  &c->d_raw_cc, &c->raw_cc);
-    if (rc == LT_OK) c->raw_cc_bytes = table_bytes + 256;
-    return rc;
+    if (!c->d_raw_cc && (rc = dev_alloc(&c->d_raw_cc, t.size() / 4))) return rc;
+    c->raw_cc_bytes = t.size();
+    HIP_TRY(hipMemcpy(c->d_raw_cc, t.data(), t.size(), hipMemcpyHostToDevice));
+    return LT_OK;
 }
 
 static int write_identity_lut(lt_ctx* c);              // (lens shading, below)
@@ -1004,8 +1002,8 @@ int lt_set_raw_lut(lt_ctx* c, const uint8_t* lut) {
     }
     c->raw_lut_set = lut != nullptr;
     std::fill(c->front_ok.begin(), c->front_ok.end(), (uint8_t)0);
-    if (!lut && c->raw_shade_set && (rc = write_identity_lut(c))) return rc;       // (the shading kernels always stage a table)
-    return c->raw_color_set ? write_raw_color(c) : LT_OK;       // (the colour stage's kernels read the table from its buffer)
+    if (!lut && c->raw_shade_set && (rc = write_identity_lut(c))) return rc;       // (the raw kernels always stage a table)
+    return c->raw_color_set ? write_raw_color(c) : LT_OK;       // (with a colour stage the kernels stage the table from its buffer)
 }
 
 int lt_get_raw_lut(lt_ctx* c, uint8_t* lut, int* is_set) {
@@ -1092,19 +1090,18 @@ static int expand_mesh(hipStream_t st, const uint16_t* mesh, int mesh_w, int mes
     if (e != hipSuccess) return fail(LT_ERR_HIP, "expanding the shading mesh failed: %s", hipGetErrorString(e));
     return LT_OK;
 }
-// the identity table into d_raw_lut: what the k_ls* kernels of an 8-bit context without a raw table stage; nothing in flight
+// the identity table into d_raw_lut: what the raw kernels of an 8-bit context with a map and without a raw table stage; nothing in flight
 static int write_identity_lut(lt_ctx* c) {
     int rc;
     if (!c->d_raw_lut && (rc = dev_alloc(&c->d_raw_lut, 256))) return rc;
-    uint8_t ident[1024];
-    for (int i = 0; i < 1024; ++i) ident[i] = (uint8_t)(i & 255);
-    HIP_TRY(hipMemcpy(c->d_raw_lut, ident, sizeof ident, hipMemcpyHostToDevice));
+    const std::vector<uint8_t> ident = staged_table(LT_INPUT_BAYER_RGGB, nullptr, nullptr);
+    HIP_TRY(hipMemcpy(c->d_raw_lut, ident.data(), ident.size(), hipMemcpyHostToDevice));
     return LT_OK;
 }
 static void drop_raw_shading(lt_ctx* c) {
     c->raw_shade_set = false;
     dev_free(c->d_raw_gain);
-    c->raw_shade = {};
+    c->raw_black = {};
     c->raw_mesh.clear();
     c->raw_mesh_w = c->raw_mesh_h = 0;
 }
@@ -1131,8 +1128,7 @@ int lt_set_raw_shading(lt_ctx* c, const uint16_t* mesh, int mesh_w, int mesh_h, 
         }
         c->raw_mesh.assign(mesh, mesh + (size_t)4 * mesh_w * mesh_h);
         c->raw_mesh_w = mesh_w, c->raw_mesh_h = mesh_h;
-        c->raw_shade.plane = c->d_raw_gain;
-        for (int p = 0; p < 4; ++p) c->raw_shade.black[p] = black ? black[p] : 0;
+        for (int p = 0; p < 4; ++p) c->raw_black.b[p] = black ? black[p] : 0;
         c->raw_shade_set = true;
     } else {
         drop_raw_shading(c);
@@ -1147,7 +1143,7 @@ int lt_get_raw_shading(lt_ctx* c, uint16_t* mesh, int* mesh_w, int* mesh_h, int3
     if (mesh_w) *mesh_w = c->raw_mesh_w;
     if (mesh_h) *mesh_h = c->raw_mesh_h;
     if (mesh && c->raw_shade_set) std::memcpy(mesh, c->raw_mesh.data(), c->raw_mesh.size() * sizeof(uint16_t));
-    if (black && c->raw_shade_set) std::memcpy(black, c->raw_shade.black, sizeof c->raw_shade.black);
+    if (black && c->raw_shade_set) std::memcpy(black, c->raw_black.b, sizeof c->raw_black.b);
     return LT_OK;
 }
 
@@ -1199,7 +1195,7 @@ static inline int chroma_hi(int r0, int r1) { return r1 > r0 ? (r1 - 1) / 2 + 1 
 // rows [r0, r1) of the staging frames of slots [first, first + n) -> the same rows of their RGB camera frames, on `st`
 static void yuv_convert(lt_ctx* c, hipStream_t st, int first, int n, int r0, int r1) {
     launch_yuv_rows_to_rgb(st, c->in_layout, slot_yuv(c, first), c->yuv_stride, yuv_coef_of(c), slot_frame(c, first), c->frame_bytes,
-                           c->calib.img_h, c->calib.img_w, r0, r1, n, raw_lut_of(c), raw_color_of(c), raw_shade_of(c));
+                           c->calib.img_h, c->calib.img_w, r0, r1, n, raw_stages_of(c));
 }
 
 // ---- input frames of another size (lt_set_input_size) ------------------------------------------------------------------------
@@ -1862,7 +1858,7 @@ int lt_device_frames_rest(lt_ctx* c, int first, int n, const int32_t* rows4) {
     const int32_t* r = rows4 ? rows4 : whole;
     for (int k = 0; k < 4; k += 2)
         launch_surf_rows_to_rgb(c->copy, c->in_layout, &c->surf[(size_t)first], yuv_coef_of(c), slot_frame(c, first), c->frame_bytes,
-                                c->calib.img_h, c->calib.img_w, r[k], r[k + 1], n, raw_lut_of(c), raw_color_of(c), raw_shade_of(c));
+                                c->calib.img_h, c->calib.img_w, r[k], r[k + 1], n, raw_stages_of(c));
     HIP_TRY(hipGetLastError());
     if ((rc = note_range(c->readers, c->copy, first, first + n))) return rc;      // it reads the surfaces and writes the camera frames: the next upload waits
     if (!rows4) mark_frames(c, first, n, 1);
@@ -2538,8 +2534,8 @@ static int mask_run_impl(lt_ctx* c, int first, int n, const lt_filter_params* p,
                   const FrameSource src = att ? FrameSource::surfaces(c->d_surf)
                                           : c->in_layout != LT_INPUT_RGB ? FrameSource::slots(slot_yuv(c, a), c->yuv_stride)
                                                                          : FrameSource::slots(slot_frame(c, a), c->frame_bytes);
-                  if (mixed) launch_undistort_cal(st, src, c->in_layout, yuv_coef_of(c), c->d_cal, &c->slot_cal[(size_t)a], c->fe, c->d_und, c->und_px, a, b - a, raw_lut_of(c), raw_color_of(c), raw_shade_of(c));
-                  else launch_undistort_rows(st, src, c->in_layout, yuv_coef_of(c), cs.d_uxy, cs.d_ufrac, c->fe, c->d_und, c->und_px, a, b - a, raw_lut_of(c), raw_color_of(c), raw_shade_of(c));
+                  if (mixed) launch_undistort_cal(st, src, c->in_layout, yuv_coef_of(c), c->d_cal, &c->slot_cal[(size_t)a], c->fe, c->d_und, c->und_px, a, b - a, raw_stages_of(c));
+                  else launch_undistort_rows(st, src, c->in_layout, yuv_coef_of(c), cs.d_uxy, cs.d_ufrac, c->fe, c->d_und, c->und_px, a, b - a, raw_stages_of(c));
               } }
             { int mrc = n == 1 ? note_range_frame(c, c->readers, st, f0, f0 + m) : note_range(c->readers, st, f0, f0 + m); if (mrc) return mrc; }
             { StageScope t(c, ST_WARP_SPLIT, st);
@@ -2907,189 +2903,126 @@ int lt_bilateral_adaptive_threshold(lt_ctx* c, const uint8_t* img, int h, int w,
     return LT_OK;
 }
 
-// one 4:2:0 host frame of any even size (h w 3 / 2 bytes), or one packed 4:2:2 frame of any even width (h w 2 bytes) -> RGB, on the
-// device (cv2.cvtColor(frame, COLOR_YUV2RGB_NV12 / _I420 / _YUY2 / _UYVY) with the given matrix)
+// ---- one host frame -> RGB, on the device ---------------------------------------------------------------------------------------------
+// The one-shot converters below validate their arguments and describe their job; convert_once does the rest.
+struct OneShot {
+    const char* what;                        // for the error text
+    const void* frame;
+    size_t in_bytes;
+    int h, w, layout;
+    YuvCoef k;                               // the YUV layouts
+    // raw Bayer behind a table (RawStages): the table (null: the 8-bit identity / the wide default), the colour stage (curve not null: ccm
+    // and curve), the shading map (mesh not null)
+    bool raw_table;
+    const uint8_t* lut;
+    const int16_t* ccm;
+    const uint8_t* curve;
+    const uint16_t* mesh;
+    int mesh_w, mesh_h;
+    const int32_t* black;
+};
+static int convert_once(lt_ctx* c, const OneShot& j, uint8_t* out_rgb) {
+    int rc;
+    if ((rc = set_device(c))) return rc;
+    const size_t out_bytes = (size_t)j.h * j.w * 3;
+    DevBuf<uint8_t> d_in, d_out;
+    DevBuf<uint32_t> d_table;
+    DevBuf<uint16_t> d_gain;
+    std::vector<uint8_t> table;              // (read by the upload until the synchronise below)
+    RawStages raw;
+    if ((rc = d_in.alloc(j.in_bytes)) || (rc = d_out.alloc(out_bytes))) return rc;
+    hipError_t e = hipSuccess;
+    if (j.raw_table) {
+        table = staged_table(j.layout, j.lut, j.curve);
+        if ((rc = d_table.alloc(table.size() / 4))) return rc;
+        if (j.mesh && (rc = expand_mesh(c->stream, j.mesh, j.mesh_w, j.mesh_h, j.layout, j.h, j.w, &d_gain.p))) return rc;
+        raw.table = d_table.p;
+        raw.bits = is_bayer_wide(j.layout) ? raw_bits(j.layout) : 8;
+        raw.color = j.curve != nullptr;
+        for (int i = 0; raw.color && i < 9; ++i) raw.cm.m[i] = j.ccm[i];
+        raw.gains = d_gain.p;
+        for (int p = 0; j.mesh && p < 4; ++p) raw.blk.b[p] = j.black ? j.black[p] : 0;
+        e = hipMemcpyAsync(d_table.p, table.data(), table.size(), hipMemcpyHostToDevice, c->stream);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(d_in.p, j.frame, j.in_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        launch_yuv_rows_to_rgb(c->stream, j.layout, d_in.p, j.in_bytes, j.k, d_out.p, out_bytes, j.h, j.w, 0, j.h, 1, raw);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out_rgb, d_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) return fail(LT_ERR_HIP, "%s failed: %s", j.what, hipGetErrorString(e));
+    return LT_OK;
+}
+
+// one 4:2:0 host frame of any even size (h w 3 / 2 bytes), or one packed 4:2:2 frame of any even width (h w 2 bytes) -> RGB
+// (cv2.cvtColor(frame, COLOR_YUV2RGB_NV12 / _I420 / _YUY2 / _UYVY) with the given matrix)
 int lt_yuv_to_rgb(lt_ctx* c, const uint8_t* frame, int h, int w, int layout, const int32_t* coeffs, uint8_t* out_rgb) {
     if (!c || !frame || !out_rgb) return fail(LT_ERR_INVALID, "null argument");
     int rc = check_yuv_format(layout, coeffs, h, w);
     if (rc) return rc;
     if (h > 16384 || w > 16384) return fail(LT_ERR_INVALID, "bad image size (at most 16384 x 16384)");
-    if ((rc = set_device(c))) return rc;
-    const size_t px = (size_t)h * w, in_bytes = is_422(layout) ? px * 2 : px * 3 / 2;
-    uint8_t *d_in = nullptr, *d_out = nullptr;
-    if ((rc = dev_alloc(&d_in, in_bytes))) return rc;
-    if ((rc = dev_alloc(&d_out, px * 3))) { dev_free(d_in); return rc; }
-    hipError_t e = hipMemcpyAsync(d_in, frame, in_bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        launch_yuv_rows_to_rgb(c->stream, layout, d_in, in_bytes, YuvCoef{coeffs[0], coeffs[1], coeffs[2], coeffs[3], coeffs[4]}, d_out,
-                               px * 3, h, w, 0, h, 1);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out_rgb, d_out, px * 3, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    dev_free(d_in);
-    dev_free(d_out);
-    if (e != hipSuccess) return fail(LT_ERR_HIP, "YUV conversion failed: %s", hipGetErrorString(e));
-    return LT_OK;
+    const size_t px = (size_t)h * w;
+    OneShot j = {"YUV conversion", frame, is_422(layout) ? px * 2 : px * 3 / 2, h, w, layout};
+    j.k = YuvCoef{coeffs[0], coeffs[1], coeffs[2], coeffs[3], coeffs[4]};
+    return convert_once(c, j, out_rgb);
 }
 
-// one 8-bit raw Bayer host frame of any even size from 4 x 4 (h w bytes) -> RGB, on the device: the bilinear demosaic of bayer_arith.h
+// one 8-bit raw Bayer host frame of any even size from 4 x 4 (h w bytes) -> RGB: the bilinear demosaic of bayer_arith.h
 int lt_bayer_to_rgb(lt_ctx* c, const uint8_t* frame, int h, int w, int layout, uint8_t* out_rgb) {
     if (!c || !frame || !out_rgb) return fail(LT_ERR_INVALID, "null argument");
     if (!is_bayer(layout)) return fail(LT_ERR_INVALID, "lt_bayer_to_rgb takes the raw Bayer layouts (16 .. 19)");
     int rc = check_bayer_size(h, w);
     if (rc) return rc;
     if (h > 16384 || w > 16384) return fail(LT_ERR_INVALID, "bad image size (at most 16384 x 16384)");
-    if ((rc = set_device(c))) return rc;
-    const size_t px = (size_t)h * w;
-    uint8_t *d_in = nullptr, *d_out = nullptr;
-    if ((rc = dev_alloc(&d_in, px))) return rc;
-    if ((rc = dev_alloc(&d_out, px * 3))) { dev_free(d_in); return rc; }
-    hipError_t e = hipMemcpyAsync(d_in, frame, px, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        launch_yuv_rows_to_rgb(c->stream, layout, d_in, px, YuvCoef{}, d_out, px * 3, h, w, 0, h, 1);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out_rgb, d_out, px * 3, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    dev_free(d_in);
-    dev_free(d_out);
-    if (e != hipSuccess) return fail(LT_ERR_HIP, "raw Bayer conversion failed: %s", hipGetErrorString(e));
-    return LT_OK;
+    return convert_once(c, OneShot{"raw Bayer conversion", frame, (size_t)h * w, h, w, layout}, out_rgb);
 }
 
-// one 10- / 12-bit raw Bayer host frame (h w 16-bit words) -> RGB, on the device: every sample looked up in `lut` (null: the default table),
-// then the bilinear demosaic -- lt_bayer_to_rgb's twin
+// one 10- / 12-bit raw Bayer host frame (h w 16-bit words) -> RGB: every sample looked up in `lut` (null: the default table), then the
+// bilinear demosaic -- lt_bayer_to_rgb's twin
 int lt_raw16_to_rgb(lt_ctx* c, const uint16_t* frame, int h, int w, int layout, const uint8_t* lut, uint8_t* out_rgb) {
     if (!c || !frame || !out_rgb) return fail(LT_ERR_INVALID, "null argument");
     if (!is_bayer_wide(layout)) return fail(LT_ERR_INVALID, "lt_raw16_to_rgb takes the 10- and 12-bit raw Bayer layouts (32 .. 35, 48 .. 51)");
     int rc = check_bayer_size(h, w);
     if (rc) return rc;
     if (h > 16384 || w > 16384) return fail(LT_ERR_INVALID, "bad image size (at most 16384 x 16384)");
-    if ((rc = set_device(c))) return rc;
-    const size_t px = (size_t)h * w, lut_bytes = (size_t)4 << raw_bits(layout);
-    std::vector<uint8_t> def;
-    if (!lut) {
-        def.resize(lut_bytes);
-        default_wide_table(raw_bits(layout), def.data());
-        lut = def.data();
-    }
-    uint8_t *d_in = nullptr, *d_out = nullptr;
-    uint32_t* d_lut = nullptr;
-    if ((rc = dev_alloc(&d_in, px * 2)) || (rc = dev_alloc(&d_out, px * 3)) || (rc = dev_alloc(&d_lut, lut_bytes / 4))) {
-        dev_free(d_in); dev_free(d_out); dev_free(d_lut);
-        return rc;
-    }
-    hipError_t e = hipMemcpyAsync(d_in, frame, px * 2, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_lut, lut, lut_bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        launch_yuv_rows_to_rgb(c->stream, layout, d_in, px * 2, YuvCoef{}, d_out, px * 3, h, w, 0, h, 1, d_lut);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out_rgb, d_out, px * 3, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);     // (`def` and the caller's table have been read by then)
-    dev_free(d_in);
-    dev_free(d_out);
-    dev_free(d_lut);
-    if (e != hipSuccess) return fail(LT_ERR_HIP, "raw Bayer conversion failed: %s", hipGetErrorString(e));
-    return LT_OK;
+    return convert_once(c, OneShot{"raw Bayer conversion", frame, (size_t)h * w * 2, h, w, layout, YuvCoef{}, true, lut}, out_rgb);
 }
 
-// one raw Bayer host frame in any of the twelve raw layouts -> RGB with the colour stage, on the device: every sample looked up in `lut`
-// (8-bit: null is no table; 10 / 12 bits: null is the default table), demosaiced, then matrix and curve (null: the identity each) -- the
-// k_cc* row kernels alone
-int lt_raw_to_rgb_color(lt_ctx* c, const void* frame, int h, int w, int layout, const uint8_t* lut, size_t lut_entries, const int16_t* ccm,
-                        const uint8_t* curve, uint8_t* out_rgb) {
+// One raw Bayer host frame in any of the twelve raw layouts -> RGB behind its table, on behalf of `fn`: every sample shaded (mesh not null:
+// the map and its pedestals), looked up in `lut` (8-bit: null is the identity; 10 / 12 bits: null is the default table) and demosaiced, then
+// -- `color` -- matrix and curve (null: the identity each).
+static int raw_to_rgb(lt_ctx* c, const char* fn, const void* frame, int h, int w, int layout, const uint8_t* lut, size_t lut_entries, bool color,
+                      const int16_t* ccm, const uint8_t* curve, const uint16_t* mesh, int mesh_w, int mesh_h, const int32_t* black, uint8_t* out_rgb) {
     if (!c || !frame || !out_rgb) return fail(LT_ERR_INVALID, "null argument");
-    if (!is_raw_mosaic(layout)) return fail(LT_ERR_INVALID, "lt_raw_to_rgb_color takes the raw Bayer layouts (16 .. 19, 32 .. 35, 48 .. 51)");
+    if (!is_raw_mosaic(layout)) return fail(LT_ERR_INVALID, "%s takes the raw Bayer layouts (16 .. 19, 32 .. 35, 48 .. 51)", fn);
     const bool wide = is_bayer_wide(layout);
     const size_t entries = wide ? (size_t)1 << raw_bits(layout) : 256;
     if (lut && lut_entries != entries) return fail(LT_ERR_INVALID, "the raw table of this layout has %zu entries per colour phase, got %zu", entries, lut_entries);
     int rc = check_bayer_size(h, w);
     if (rc) return rc;
     if (h > 16384 || w > 16384) return fail(LT_ERR_INVALID, "bad image size (at most 16384 x 16384)");
-    if ((rc = set_device(c))) return rc;
-    const size_t px = (size_t)h * w, in_bytes = wide ? px * 2 : px;
-    std::vector<uint8_t> def;
-    if (!lut && wide) {
-        def.resize(4 * entries);
-        default_wide_table(raw_bits(layout), def.data());
-        lut = def.data();
-    }
+    if (mesh && (rc = check_shading(layout, mesh_w, mesh_h, black))) return rc;
     static const int16_t ident[9] = {1024, 0, 0, 0, 1024, 0, 0, 0, 1024};
     uint8_t line[256];
     for (int i = 0; i < 256; ++i) line[i] = curve ? curve[i] : (uint8_t)i;
-    uint8_t *d_in = nullptr, *d_out = nullptr;
-    uint32_t* d_cc = nullptr;
-    RawColor cc = {};
-    if ((rc = dev_alloc(&d_in, in_bytes)) || (rc = dev_alloc(&d_out, px * 3)) || (rc = make_raw_color(lut, 4 * entries, ccm ? ccm : ident, line, &d_cc, &cc))) {
-        dev_free(d_in); dev_free(d_out); dev_free(d_cc);
-        return rc;
-    }
-    hipError_t e = hipMemcpyAsync(d_in, frame, in_bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        launch_yuv_rows_to_rgb(c->stream, layout, d_in, in_bytes, YuvCoef{}, d_out, px * 3, h, w, 0, h, 1, nullptr, &cc);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out_rgb, d_out, px * 3, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    dev_free(d_in);
-    dev_free(d_out);
-    dev_free(d_cc);
-    if (e != hipSuccess) return fail(LT_ERR_HIP, "raw Bayer conversion failed: %s", hipGetErrorString(e));
-    return LT_OK;
+    const OneShot j = {"raw Bayer conversion", frame, (size_t)h * w * (wide ? 2 : 1), h, w, layout, YuvCoef{}, true, lut,
+                       ccm ? ccm : ident, color ? line : nullptr, mesh, mesh_w, mesh_h, black};
+    return convert_once(c, j, out_rgb);
 }
 
-// lt_raw_to_rgb_color behind a shading map (mesh = null: none); without ccm and curve there is no colour stage either -- the k_ls* row
-// kernels alone, in all their forms
+// lt_bayer_to_rgb / lt_raw16_to_rgb behind a raw table and with the colour stage: the raw row kernels with STAGES 2 and 3 alone
+int lt_raw_to_rgb_color(lt_ctx* c, const void* frame, int h, int w, int layout, const uint8_t* lut, size_t lut_entries, const int16_t* ccm,
+                        const uint8_t* curve, uint8_t* out_rgb) {
+    return raw_to_rgb(c, "lt_raw_to_rgb_color", frame, h, w, layout, lut, lut_entries, true, ccm, curve, nullptr, 0, 0, nullptr, out_rgb);
+}
+
+// lt_raw_to_rgb_color behind a shading map (mesh = null: none); without ccm and curve there is no colour stage either -- the raw row
+// kernels with STAGES 4 .. 7 alone
 int lt_raw_to_rgb_shaded(lt_ctx* c, const void* frame, int h, int w, int layout, const uint8_t* lut, size_t lut_entries, const int16_t* ccm,
                          const uint8_t* curve, const uint16_t* mesh, int mesh_w, int mesh_h, const int32_t* black, uint8_t* out_rgb) {
     if (!mesh) return lt_raw_to_rgb_color(c, frame, h, w, layout, lut, lut_entries, ccm, curve, out_rgb);
-    if (!c || !frame || !out_rgb) return fail(LT_ERR_INVALID, "null argument");
-    if (!is_raw_mosaic(layout)) return fail(LT_ERR_INVALID, "lt_raw_to_rgb_shaded takes the raw Bayer layouts (16 .. 19, 32 .. 35, 48 .. 51)");
-    const bool wide = is_bayer_wide(layout), color = ccm || curve;
-    const size_t entries = wide ? (size_t)1 << raw_bits(layout) : 256;
-    if (lut && lut_entries != entries) return fail(LT_ERR_INVALID, "the raw table of this layout has %zu entries per colour phase, got %zu", entries, lut_entries);
-    int rc = check_bayer_size(h, w);
-    if (rc) return rc;
-    if (h > 16384 || w > 16384) return fail(LT_ERR_INVALID, "bad image size (at most 16384 x 16384)");
-    if ((rc = check_shading(layout, mesh_w, mesh_h, black))) return rc;
-    if ((rc = set_device(c))) return rc;
-    const size_t px = (size_t)h * w, in_bytes = wide ? px * 2 : px;
-    std::vector<uint8_t> def;
-    if (!lut && wide) {
-        def.resize(4 * entries);
-        default_wide_table(raw_bits(layout), def.data());
-        lut = def.data();
-    }
-    static const int16_t ident[9] = {1024, 0, 0, 0, 1024, 0, 0, 0, 1024};
-    uint8_t line[256];
-    for (int i = 0; i < 256; ++i) line[i] = curve ? curve[i] : (uint8_t)i;
-    uint8_t *d_in = nullptr, *d_out = nullptr;
-    uint32_t* d_cc = nullptr;                // curve, then table; without a colour stage the kernels are handed the table behind the curve
-    RawColor cc = {};
-    RawShade ls = {};
-    uint16_t* d_gain = nullptr;
-    if ((rc = dev_alloc(&d_in, in_bytes)) || (rc = dev_alloc(&d_out, px * 3)) || (rc = make_raw_color(lut, 4 * entries, ccm ? ccm : ident, line, &d_cc, &cc)) ||
-        (rc = expand_mesh(c->stream, mesh, mesh_w, mesh_h, layout, h, w, &d_gain))) {
-        dev_free(d_in); dev_free(d_out); dev_free(d_cc); dev_free(d_gain);
-        return rc;
-    }
-    ls.plane = d_gain;
-    for (int p = 0; p < 4; ++p) ls.black[p] = black ? black[p] : 0;
-    hipError_t e = hipMemcpyAsync(d_in, frame, in_bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        launch_yuv_rows_to_rgb(c->stream, layout, d_in, in_bytes, YuvCoef{}, d_out, px * 3, h, w, 0, h, 1, d_cc + 64, color ? &cc : nullptr, &ls);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out_rgb, d_out, px * 3, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    dev_free(d_in);
-    dev_free(d_out);
-    dev_free(d_cc);
-    dev_free(d_gain);
-    if (e != hipSuccess) return fail(LT_ERR_HIP, "raw Bayer conversion failed: %s", hipGetErrorString(e));
-    return LT_OK;
+    return raw_to_rgb(c, "lt_raw_to_rgb_shaded", frame, h, w, layout, lut, lut_entries, ccm || curve, ccm, curve, mesh, mesh_w, mesh_h, black, out_rgb);
 }
 
 int lt_filter_lane_points(lt_ctx* c, const uint8_t* bev, int h, int w, const lt_filter_params* p, uint8_t* mask) {

@@ -161,7 +161,7 @@ struct lt_ctx {
     uint8_t* d_yuv = nullptr;
     size_t yuv_bytes = 0, yuv_stride = 0;
     // The raw table of a raw Bayer context (lt_set_raw_lut): uint8[4][256], phase-major, on the host and -- allocated by the first set, kept --
-    // in device memory, where the conditioned walk and row conversion (k_raw_walk_rows, k_raw_rows_rgb) stage it in LDS.  raw_lut_set says
+    // in device memory, where the raw walk and row conversion (k_raw_walk_rows, k_raw_rows_rgb) stage it in LDS.  raw_lut_set says
     // which kernels are launched: the table's content never does.
     bool raw_lut_set = false;
     uint8_t raw_lut[1024] = {0};
@@ -171,23 +171,22 @@ struct lt_ctx {
     std::vector<uint8_t> raw_lut_wide;
     uint32_t* d_raw_lut_wide = nullptr;
     // The colour stage of a raw Bayer context (lt_set_raw_color): the colour-correction matrix (Q10) and the output curve on the host, and
-    // in device memory ONE buffer for the k_cc* kernels -- the curve's 256 bytes followed by the table the frames are conditioned with (the
+    // in device memory ONE buffer for the raw kernels to stage -- the curve's 256 bytes followed by the table the frames are conditioned with (the
     // 8-bit raw table, the identity where none is set, or the wide table) -- rewritten whenever the stage or the table changes while
     // a stage is set (write_raw_color).  raw_color_set says which kernels are launched: the stage's content never does.
     bool raw_color_set = false;
     int16_t raw_ccm[9] = {1024, 0, 0, 0, 1024, 0, 0, 0, 1024};
     uint8_t raw_curve[256] = {0};
-    lt::RawColor raw_cc = {};                     // what the launches take: the matrix widened, table = d_raw_cc
     uint32_t* d_raw_cc = nullptr;
     size_t raw_cc_bytes = 0;
     // The lens-shading correction of a raw Bayer context (lt_set_raw_shading): mesh and pedestals on the host, and in device memory the gain
     // plane that k_shade_expand makes of the mesh -- uint16[img_h][img_w] and 16 bytes of padding, allocated by the first set, freed when the
     // map is removed: a context that never sets one allocates nothing.  raw_shade_set says which kernels are launched: the map's content
-    // never does.  An 8-bit context without a raw table then keeps the identity table in d_raw_lut: the k_ls* kernels always stage one.
+    // never does.  An 8-bit context without a raw table then keeps the identity table in d_raw_lut: the raw kernels always stage one.
     bool raw_shade_set = false;
     std::vector<uint16_t> raw_mesh;
     int raw_mesh_w = 0, raw_mesh_h = 0;
-    lt::RawShade raw_shade = {};                  // what the launches take: plane = d_raw_gain, the pedestals
+    lt::RawShadeBlack raw_black = {};             // the pedestals, by colour phase
     uint16_t* d_raw_gain = nullptr;
     // Input frames of another size (lt_set_input_size): src_w x src_h RGB frames, resized on the device to the calibration's size
     // (cv2.resize, INTER_LINEAR).  Per slot a staging frame of src_bytes = src_h * src_w * 3 bytes, src_stride apart (a multiple of 16
@@ -385,13 +384,22 @@ inline int raw_bits(int layout) { return raw_wide_bits(layout); }
 inline bool is_bayer_wide(int layout) { return raw_bits(layout) != 0; }
 // any raw mosaic, whatever its samples: what is about the mosaic (sizes, row runs, input only) and not about bytes
 inline bool is_raw_mosaic(int layout) { return is_bayer(layout) || is_bayer_wide(layout); }
-// the raw table the front end and the row conversion of `c` are launched with: null without one (a wide context always has one)
-// (with a shading map an 8-bit context always brings one: the identity where none is set, which lt_set_raw_shading keeps in d_raw_lut)
-inline const uint32_t* raw_lut_of(const lt_ctx* c) { return is_bayer_wide(c->in_layout) ? c->d_raw_lut_wide : c->raw_lut_set || c->raw_shade_set ? c->d_raw_lut : nullptr; }
-// the colour stage they are launched with: null without one
-inline const lt::RawColor* raw_color_of(const lt_ctx* c) { return c->raw_color_set ? &c->raw_cc : nullptr; }
-// the shading map they are launched with: null without one
-inline const lt::RawShade* raw_shade_of(const lt_ctx* c) { return c->raw_shade_set ? &c->raw_shade : nullptr; }
+// What the front end and the row conversion of `c` are launched with behind a raw table (lt_internal.h: RawStages) -- the one place that
+// knows which table that is: a wide context always has one; an 8-bit context has one when a raw table is set, or when a shading map is,
+// which brings the identity table where no raw table is set (lt_set_raw_shading keeps it in d_raw_lut); with a colour stage the staged
+// buffer is d_raw_cc, the curve in front of that same table (write_raw_color).  No table: the plain kernels of the layout.
+inline RawStages raw_stages_of(const lt_ctx* c) {
+    RawStages r;
+    if (!is_raw_mosaic(c->in_layout)) return r;
+    const bool wide = is_bayer_wide(c->in_layout);
+    r.bits = wide ? raw_bits(c->in_layout) : 8;
+    r.table = c->raw_color_set ? c->d_raw_cc : wide ? c->d_raw_lut_wide : c->raw_lut_set || c->raw_shade_set ? c->d_raw_lut : nullptr;
+    r.color = c->raw_color_set;
+    for (int i = 0; i < 9; ++i) r.cm.m[i] = c->raw_ccm[i];
+    r.gains = c->raw_shade_set ? c->d_raw_gain : nullptr;
+    r.blk = c->raw_black;
+    return r;
+}
 inline int packed_bpp(int layout) {
     return layout == LT_INPUT_RGB || layout == LT_INPUT_BGR ? 3 : layout == LT_INPUT_RGBA || layout == LT_INPUT_BGRA ? 4
            : layout == LT_INPUT_YUY2 || layout == LT_INPUT_UYVY || is_bayer_wide(layout) ? 2 : is_bayer(layout) ? 1 : 0;
@@ -477,6 +485,16 @@ void dev_free(T*& p) {
     if (p) cached_free(p);
     p = nullptr;
 }
+// a device buffer of one call: freed when its scope closes, on every path
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { dev_free(p); }
+    int alloc(size_t count) { return dev_alloc(&p, count); }
+};
 
 // ---- the mask chain's arena (MaskArena, above) ----------------------------------------------------------------
 inline void MaskArena::set_geometry(int h, int w) {

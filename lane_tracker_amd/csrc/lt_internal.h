@@ -57,22 +57,31 @@ void launch_warp_split(hipStream_t s, const uint32_t* und, size_t und_px, int fi
                        const uint16_t* wfrac, FrontEndGeom g, const uint16_t* gamma_tab, const uint16_t* cbrt_tab,
                        const int32_t* coeffs, bool lab_clamp_dead, uint8_t* planeR, uint8_t* planeB, size_t plane_stride, int n);
 // (YuvCoef, the five coefficients of the YUV 4:2:0 input's conversion: yuv_arith.h)
-// The colour stage of raw Bayer input (lt_set_raw_color; bayer_arith.h: color_px) as the front end's launches take it -- `cc` here and
-// below, null: none.  m: the colour-correction matrix, Q10, row-major; table: device memory, the 256 bytes of the output curve followed by
-// the raw table the frames are conditioned with (8-bit: uint8[4][256], the identity where the context has none; 10 / 12 bits:
-// uint8[4][1 << bits]).  With one, the k_cc* kernels are launched in place of the raw ones, and `raw_lut` is not read.
-struct RawColor { int32_t m[9]; const uint32_t* table; };
-// The lens-shading correction of raw Bayer input (lt_set_raw_shading; shade_arith.h) as the same launches take it -- `ls`, null: none.
-// plane: device memory, the gain of every site of the image, uint16[h][w] (Q12) and 16 bytes of padding, expanded from the mesh by
-// launch_shade_expand; black: the pedestal of each colour phase.  With one, the k_ls* kernels are launched in place of the others and stage
-// what those would: cc's table, or raw_lut -- which an 8-bit launch then has to bring, the identity table where the context has none.
-struct RawShade { const uint16_t* plane; int32_t black[4]; };
+// What a launch of the front end over raw Bayer frames runs around the demosaic (`raw`, here and below; lt_ctx.h: raw_stages_of), and the one
+// argument of the raw kernels -- k_raw_walk_rows, k_raw_rows_rgb<.., STAGES>, launched in place of the plain ones whenever there is a table:
+//   table  device memory, what the kernel stages in LDS: the raw table the samples are looked up in (lt_set_raw_lut: uint8[4][256], phase-major;
+//          lt_set_raw_lut_wide: uint8[4][1 << bits]), behind the 256 bytes of the output curve where there is a colour stage.  Null: no raw
+//          kernel, 8-bit frames go through the plain demosaic (10- / 12-bit frames always have a table)
+//   bits   of a sample: 8, or 10 / 12 (16-bit little-endian words)
+//   color  the colour stage (lt_set_raw_color; bayer_arith.h: color_px) on every demosaiced pixel; cm: its matrix, Q10, row-major
+//   gains  not null: the lens-shading correction (lt_set_raw_shading; shade_arith.h) of every sample before its lookup -- device memory, the
+//          gain of every site, uint16[h][w] (Q12) and 16 bytes of padding (launch_shade_expand); blk: the pedestal of each colour phase
+struct RawColorMat { int32_t m[9]; };
+struct RawShadeBlack { int32_t b[4]; };
+struct RawStages {
+    const uint32_t* table = nullptr;
+    int bits = 8;
+    bool color = false;
+    RawColorMat cm = {};
+    const uint16_t* gains = nullptr;
+    RawShadeBlack blk = {};
+};
 // mesh (device memory, uint16[4][mh][mw], phase-major) -> the gain plane of an h x w image whose layout has `pattern` (k_shade_expand)
 void launch_shade_expand(hipStream_t s, const uint16_t* mesh, int mw, int mh, int pattern, uint16_t* plane, int h, int w);
 // rows [r0, r1) of n dense frames of h x w in `layout` (any but 0; the layouts: launch_undistort_rows) -> the same rows of n RGB frames
-// (k_rows_to_rgb<layout, false, ..>)
+// (k_rows_to_rgb<layout, false, ..>; behind a raw table k_raw_rows_rgb<pattern, false, ..>)
 void launch_yuv_rows_to_rgb(hipStream_t s, int layout, const uint8_t* yuv, size_t yuv_stride, YuvCoef k, uint8_t* rgb,
-                            size_t rgb_stride, int h, int w, int r0, int r1, int n, const uint32_t* raw_lut = nullptr, const RawColor* cc = nullptr, const RawShade* ls = nullptr);
+                            size_t rgb_stride, int h, int w, int r0, int r1, int n, const RawStages& raw = RawStages());
 // Input frames of another size (lt_set_input_size; k_resize.hip): destination rows [a, b) of n RGB frames of width w, dst_stride apart, :=
 // cv2.resize(INTER_LINEAR) of n RGB staging frames of src_bytes (rows of src_w pixels), src_stride apart.  xt: two words per destination
 // column (resize_arith.h: pack_column), padded to a multiple of four columns; yt: (tap0, tap1, c0, c1) per destination row; device memory.
@@ -102,14 +111,14 @@ struct FrameSource {
     static FrameSource surfaces(const SurfEntry* tab) { return FrameSource{tab, nullptr, 0}; }
 };
 // The 10- / 12-bit raw Bayer layouts (32 .. 35, 48 .. 51; pattern = layout & 3): the bits of a sample, 0 for every other layout.  Their frames
-// are one plane of 16-bit little-endian words and they are always launched with a table, uint8[4][1 << bits] (lt_set_raw_lut_wide).
+// are one plane of 16-bit little-endian words and they are always launched with a table (RawStages).
 inline int raw_wide_bits(int layout) { return layout >= 32 && layout <= 35 ? 10 : layout >= 48 && layout <= 51 ? 12 : 0; }
-// raw_lut (here and below; raw Bayer layouts only): the context's raw table in device memory (lt_set_raw_lut: uint8[4][256], phase-major, as
-// 256 dwords), or null: none.  With one, the conditioned kernels are launched (k_raw_walk_rows, k_raw_rows_rgb) in place of the plain ones.
-// the undistorted rows of n frames (layout 0 = RGB, 1 = NV12, 2 = I420, 3 = YUY2, 4 = UYVY, 5 = BGR, 6 = RGBA, 7 = BGRA, 16 .. 19 = raw Bayer RGGB / GRBG / GBRG / BGGR, 32 .. 35 / 48 .. 51 = the same at 10 / 12 bits, which need raw_lut (k_raw16_walk_rows); `k` is read for the YUV layouts only: every tap converted, then the
-// same blend); `und` is the base of the whole buffer, `first_slot` the absolute slot of frame 0 of the call (k_undistort_rows<layout, source, false>)
+// the undistorted rows of n frames (layout 0 = RGB, 1 = NV12, 2 = I420, 3 = YUY2, 4 = UYVY, 5 = BGR, 6 = RGBA, 7 = BGRA, 16 .. 19 = raw Bayer RGGB /
+// GRBG / GBRG / BGGR, 32 .. 35 / 48 .. 51 = the same at 10 / 12 bits, which need raw.table; `k` is read for the YUV layouts only: every tap
+// converted, then the same blend); `und` is the base of the whole buffer, `first_slot` the absolute slot of frame 0 of the call
+// (k_undistort_rows<layout, source, false>; behind a raw table k_raw_walk_rows<pattern, source, false, stages>)
 void launch_undistort_rows(hipStream_t s, FrameSource src, int layout, YuvCoef k, const int16_t* uxy, const uint16_t* ufrac,
-                           FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n, const uint32_t* raw_lut = nullptr, const RawColor* cc = nullptr, const RawShade* ls = nullptr);
+                           FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n, const RawStages& raw = RawStages());
 // Calibration sets (lt_add_calibration): the remap tables of one set as the table-per-slot front end finds them -- entry `id` of the
 // context's set table (device memory, written when a set is added or rebuilt: before the context's first upload, with nothing in
 // flight).  Which set a slot of a launch has travels BY VALUE, one byte per slot of the launch (id of slot first_slot + z: byte z):
@@ -129,7 +138,7 @@ struct CalIds {                  // the sets of the slots of one launch
 // The table-per-slot forms of the two launches above, for slots [first_slot, first_slot + n) whose sets are ids[0, n) (host memory):
 // every slot with the tables of its own set, one frame per walk; launches of up to CalIds::N slots (k_undistort_rows<layout, source, true>, k_warp_cal).
 void launch_undistort_cal(hipStream_t s, FrameSource src, int layout, YuvCoef k, const CalTables* sets, const uint8_t* ids,
-                          FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n, const uint32_t* raw_lut = nullptr, const RawColor* cc = nullptr, const RawShade* ls = nullptr);
+                          FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n, const RawStages& raw = RawStages());
 void launch_warp_cal(hipStream_t s, const uint32_t* und, size_t und_px, int first_slot, const CalTables* sets, const uint8_t* ids,
                      FrontEndGeom g, const uint16_t* gamma_tab, const uint16_t* cbrt_tab, const int32_t* coeffs, uint8_t* planeR,
                      uint8_t* planeB, size_t plane_stride, int n);
@@ -138,7 +147,7 @@ void launch_write_surf_entries(hipStream_t s, SurfEntry* tab, int first, const S
 // rows [r0, r1) of the n surfaces of entries[] (host memory) -> the same rows of n RGB frames of h x w: a conversion (YUV, raw Bayer), a
 // permutation (BGR, RGBA, BGRA) -- k_rows_to_rgb<layout, true, ..> -- or a pitched copy (RGB: k_surf_copy_rows)
 void launch_surf_rows_to_rgb(hipStream_t s, int layout, const SurfEntry* entries, YuvCoef k, uint8_t* rgb, size_t rgb_stride, int h, int w,
-                             int r0, int r1, int n, const uint32_t* raw_lut = nullptr, const RawColor* cc = nullptr, const RawShade* ls = nullptr);
+                             int r0, int r1, int n, const RawStages& raw = RawStages());
 // device sinks (k_sink.hip): n dense RGB frames of h x w, rgb_stride bytes apart -> the n surfaces of entries[] (host memory) in
 // `layout`: a pitched copy (RGB) or a conversion with coeffs[8] (4:2:0; h and w even; sink_arith.h), 32 surfaces per launch
 void launch_rgb_to_surfaces(hipStream_t s, int layout, const uint8_t* rgb, size_t rgb_stride, int h, int w, const SurfEntry* entries,

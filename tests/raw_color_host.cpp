@@ -1,5 +1,5 @@
 // The colour stage's expression of csrc/bayer_arith.h (color_px: colour-correction matrix in Q10, clamp, output curve) on the host, as
-// the k_cc* walks and row conversions of k_frontend.hip run it on every demosaiced pixel.
+// the raw walks and row conversions of k_frontend.hip (k_raw_walk_rows, k_raw_rows_rgb with STAGES bit 1) run it on every demosaiced pixel.
 //
 //   raw_color_host IN.bin OUT.bin N
 //

@@ -1,4 +1,4 @@
-// The lens-shading expressions of csrc/shade_arith.h on the host, as k_shade_expand, the k_ls* walks and the k_ls* row conversions of
+// The lens-shading expressions of csrc/shade_arith.h on the host, as k_shade_expand, the raw walks and the raw row conversions with a map (STAGES bit 2) of
 // k_frontend.hip run them: the expansion of a mesh into the gain plane (gain_at), one sample (shade, and shade_plain: the definition as it
 // is written), and the four-site forms with the table lookup behind them (shade_condition4 / shade_condition4w).
 //

@@ -1,6 +1,6 @@
 """10- / 12-bit raw Bayer on the device: the invariant, bit for bit -- whatever a context, tracker or group in 'bayerNN_P' with table L
 computes from uint16 frames F is what the 8-bit 'bayer_P' object without a table computes from `utils.apply_raw_lut(F, 'bayerNN_P', L)`
--- for the wide walk (k_raw16_walk_rows), the wide row conversion (k_raw16_rows_rgb) and everything behind them.
+-- for the wide walk (k_raw_walk_rows, STAGES bit 0), the wide row conversion (k_raw_rows_rgb, the same bit) and everything behind them.
 
 Sizes A (64 x 48) and B (66 x 50) of front_matrix.py: the smallest that hit both the dword-multiple and the odd row bytes, the
 16-column and the site-wise body of the row conversion.  Frames: the 8-bit pool's mosaics shifted up by bits - 8 with random low bits,

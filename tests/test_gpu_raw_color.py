@@ -1,7 +1,7 @@
 """The colour stage of raw Bayer input on the device: the invariant, bit for bit -- whatever a raw Bayer context, tracker or group with
 stage (M, T) and, if set, raw table L computes from frames F is what an RGB one computes from
 `utils.apply_raw_color(bayer_to_rgb(apply_raw_lut(F, pattern, L), pattern), M, T)`, the frames converted on the host -- for the walks
-(k_cc_walk_rows, k_cc16_walk_rows), the row conversions (k_cc_rows_rgb, k_cc16_rows_rgb) and everything behind them.
+(k_raw_walk_rows with STAGES 2 and 3), the row conversions (k_raw_rows_rgb, the same) and everything behind them.
 
 Sizes A (64 x 48) and B (66 x 50) of front_matrix.py: the smallest that hit both the dword-multiple and the odd row bytes, the
 16-column and the any-width body of the row conversion.  Frames: the pools of test_gpu_bayer.py (front_matrix.frame_pool) and of

@@ -1,7 +1,7 @@
 """Lens-shading correction of raw Bayer input on the device: the invariant, bit for bit -- whatever a raw Bayer context, tracker or group
 with shading map S (and any raw table or colour stage) computes from frames F is what the same object without a map computes from
 `utils.apply_raw_shading(F, pattern, S)`, the frames shaded on the host -- for the expansion of the mesh (k_shade_expand), the walks
-(k_ls_walk_rows, k_ls16_walk_rows), the row conversions (k_ls_rows_rgb, k_ls16_rows_rgb) and everything behind them.
+(k_raw_walk_rows with STAGES 4 .. 7), the row conversions (k_raw_rows_rgb, the same) and everything behind them.
 
 Sizes A (64 x 48) and B (66 x 50) of front_matrix.py: the smallest that hit both the dword-multiple and the odd row bytes, the 16-column
 and the any-width body of the row conversion.  Frames: the pools of test_gpu_bayer.py (front_matrix.frame_pool) and of

@@ -1,5 +1,5 @@
-"""The instruction budget of the 10- / 12-bit raw Bayer walks -- k_raw16_walk_rows<PATTERN, SRC, PER_SLOT> (k_frontend.hip), DESIGN.md
-section 4 -- on the generated gfx950 code (hipcc cross-compiles; no GPU needed), from the one compile of k_frontend.hip that
+"""The instruction budget of the 10- / 12-bit raw Bayer walks -- k_raw_walk_rows<PATTERN, SRC, PER_SLOT, STAGES> with STAGES 1, the wide
+table alone (k_frontend.hip), DESIGN.md section 4 -- on the generated gfx950 code (hipcc cross-compiles; no GPU needed), from the one compile of k_frontend.hip that
 test_isa_guards.py makes and through the same tool, tools/isa_split.py.
 
 Per walk: 12 vector-memory instructions -- two remap-table reads, four 96-bit windows of one frame before the loop and four of the next
@@ -14,26 +14,26 @@ import re
 import pytest
 
 import test_isa_guards as G
+import test_raw_lut_isa as R
 
 pytestmark = G.needs_hipcc
 
-LOOP_VALU = {0: 210, 1: 197}             # SRC 0: surfaces, 1: the slots' dword-aligned staging frames
-BUDGET = {"k_raw16_walk_rows<%d, %d, %s>" % (p, src, per_slot): cap
-          for p in range(4) for src, cap in LOOP_VALU.items() for per_slot in ("false", "true")}
+assert R.STAGES_LOOP_VALU[1] == {0: 210, 1: 197}             # SRC 0: surfaces, 1: the slots' dword-aligned staging frames
+BUDGET = R.walk_budget([1])
 
 
 def _wide_walks():
     split, isa = G._isa_split(), G._isa(G.os.path.join(G.CSRC, "k_frontend.hip"))
-    return split, split.table(isa, "k_raw16_walk_rows"), {split.kernel_name(n): k["insts"] for n, k in split.kernels(isa).items()}
+    table = split.table(isa, "k_raw_walk_rows")
+    return split, {n: st for n, st in table.items() if R.stages_of(n) == 1}, {split.kernel_name(n): k["insts"] for n, k in split.kernels(isa).items()}
 
 
 def test_there_are_sixteen_wide_walks_beside_the_others():
     split, table, insts = _wide_walks()
     assert len(BUDGET) == 16 and sorted(table) == sorted(BUDGET), sorted(table)
-    assert len(G._walks()[0]) == 50                               # (a name that held k_undistort_rows would have been counted there)
-    assert len(split.table(G._isa(G.os.path.join(G.CSRC, "k_frontend.hip")), "k_raw_walk_rows")) == 16      # ... or here
-    rows = sorted(n for n in insts if n.startswith("k_raw16_rows_rgb<"))
-    assert rows == sorted("k_raw16_rows_rgb<%d, %s, %s>" % (p, s, w) for p in range(4) for s in ("false", "true") for w in ("false", "true"))
+    R.assert_raw_kernels_are_these(split.table(G._isa(G.os.path.join(G.CSRC, "k_frontend.hip"))), insts)   # 16 of each stage, the 50 plain walks
+    rows = sorted(n for n in insts if n.startswith("k_raw_rows_rgb<") and R.stages_of(n) == 1)
+    assert rows == R.row_names([1]) and len(rows) == 16
 
 
 def test_wide_walks_keep_their_budget():

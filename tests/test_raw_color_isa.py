@@ -1,5 +1,5 @@
-"""The instruction budget of the raw Bayer walks with a colour stage -- k_cc_walk_rows<PATTERN, SRC, PER_SLOT> over the 8-bit table form and
-k_cc16_walk_rows<PATTERN, SRC, PER_SLOT> over the 10- / 12-bit one (k_frontend.hip), DESIGN.md section 4 -- on the generated gfx950 code
+"""The instruction budget of the raw Bayer walks with a colour stage -- k_raw_walk_rows<PATTERN, SRC, PER_SLOT, STAGES> with STAGES 2, over the
+8-bit table form (STAGES 0), and STAGES 3, over the 10- / 12-bit one (STAGES 1) (k_frontend.hip), DESIGN.md section 4 -- on the generated gfx950 code
 (hipcc cross-compiles; no GPU needed), from the one compile of k_frontend.hip that test_isa_guards.py makes and through the same tool,
 tools/isa_split.py.
 
@@ -14,13 +14,17 @@ import re
 import pytest
 
 import test_isa_guards as G
+import test_raw_lut_isa as R
 
 pytestmark = G.needs_hipcc
 
-LOOP_VALU = {"k_cc_walk_rows": {0: 262, 1: 249}, "k_cc16_walk_rows": {0: 294, 1: 281}}      # SRC 0: surfaces, 1: the slots' staging frames
-WRAPPED = {"k_cc_walk_rows": "k_raw_walk_rows", "k_cc16_walk_rows": "k_raw16_walk_rows"}
-BUDGET = {"%s<%d, %d, %s>" % (k, p, src, per_slot): cap
-          for k, caps in LOOP_VALU.items() for p in range(4) for src, cap in caps.items() for per_slot in ("false", "true")}
+assert R.STAGES_LOOP_VALU[2] == {0: 262, 1: 249} and R.STAGES_LOOP_VALU[3] == {0: 294, 1: 281}      # SRC 0: surfaces, 1: the slots' staging frames
+WRAPPED = {2: 0, 3: 1}                   # STAGES of a colour walk -> STAGES of the table form it wraps
+BUDGET = R.walk_budget([2, 3])
+
+
+def _wrapped_name(name):
+    return name[:name.rindex(" ") + 1] + "%d>" % WRAPPED[R.stages_of(name)]
 
 
 def _front():
@@ -31,22 +35,18 @@ def _front():
 def test_the_colour_walks_are_these_and_the_others_are_what_they_were():
     split, table, insts = _front()
     assert len(BUDGET) == 32
-    assert sorted(n for n in table if n.startswith("k_cc")  and "_walk_rows" in n) == sorted(BUDGET)
-    rows = sorted(n for n in insts if n.startswith("k_cc") and "_rows_rgb<" in n)
-    assert rows == sorted("%s<%d, %s, %s>" % (k, p, s, w) for k in ("k_cc_rows_rgb", "k_cc16_rows_rgb") for p in range(4)
-                          for s in ("false", "true") for w in ("false", "true"))
-    assert sorted(n for n in insts if n.startswith("k_cc")) == sorted(list(BUDGET) + rows)        # nothing else under the prefix
-    # no name of the new kernels is counted among the walks that the other budget tests select
-    assert len(G._walks()[0]) == 50
-    assert sum("k_raw_walk_rows" in n for n in table) == 16 and sum("k_raw16_walk_rows" in n for n in table) == 16
-    assert sum(n.startswith("k_raw_rows_rgb<") for n in insts) == 16 and sum(n.startswith("k_raw16_rows_rgb<") for n in insts) == 16
+    assert sorted(n for n in table if "k_raw_walk_rows" in n and R.stages_of(n) in (2, 3)) == sorted(BUDGET)
+    rows = sorted(n for n in insts if n.startswith("k_raw_rows_rgb<") and R.stages_of(n) in (2, 3))
+    assert rows == R.row_names([2, 3]) and len(rows) == 32
+    # nothing else under the two names, 16 of each per stage, and none of them counted among the walks that the other budget tests select
+    R.assert_raw_kernels_are_these(table, insts)
 
 
 def test_colour_walks_keep_their_budget():
     split, table, insts = _front()
     for name, cap in BUDGET.items():
-        st, kind = table[name], name.split("<")[0]
-        wrapped = table[name.replace(kind, WRAPPED[kind])]
+        st = table[name]
+        wrapped = table[_wrapped_name(name)]
         print(name, st)
         assert st["vmem"] == wrapped["vmem"] == 12, "%s: %d vector-memory instructions, budget 12" % (name, st["vmem"])
         assert st["scratch"] == 0, "%s uses scratch" % name
@@ -65,5 +65,5 @@ def test_colour_walks_keep_their_budget():
         # the matrix: 36 products a frame, each a 24-bit multiply or multiply-add; the clamp a median of three per channel and tap
         # (the wrapped form's own 24-bit multiplies, the windows' addresses, come on top)
         mul24 = lambda body: sum(bool(re.match(r"^v_(mul|mad)_i32_i24", i)) for i in body)
-        assert mul24(loop) == mul24(split.store_loop(insts[name.replace(kind, WRAPPED[kind])])) + 36, name
+        assert mul24(loop) == mul24(split.store_loop(insts[_wrapped_name(name)])) + 36, name
         assert sum(i.startswith("v_med3_i32") for i in loop) == 12, name

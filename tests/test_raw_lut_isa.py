@@ -1,11 +1,15 @@
-"""The instruction budget of the conditioned raw Bayer walks -- k_raw_walk_rows<PATTERN, SRC, PER_SLOT> (k_frontend.hip), DESIGN.md
-section 4 -- on the generated gfx950 code (hipcc cross-compiles; no GPU needed), from the one compile of k_frontend.hip that
+"""The instruction budget of the conditioned raw Bayer walks -- k_raw_walk_rows<PATTERN, SRC, PER_SLOT, STAGES> with STAGES 0, the 8-bit
+table alone (k_frontend.hip), DESIGN.md section 4 -- on the generated gfx950 code (hipcc cross-compiles; no GPU needed), from the one compile of k_frontend.hip that
 test_isa_guards.py makes and through the same tool, tools/isa_split.py.
 
 Per walk: 12 vector-memory instructions -- raw Bayer's 11 (two remap-table reads, four windows of one frame before the loop and four of
 the next inside it, the store) and the one dword of the raw table that each of the workgroup's 256 threads brings to LDS; no scratch;
 no v_mul_lo_u32; the frames read in whole aligned dwords only; 16 one-byte LDS reads per frame, the lookups; and the VALU instructions
-inside the per-frame loop as the compiler gives them on the finished code (ROCm 7.2), no margin: plain raw Bayer's 158 / 145 plus 32."""
+inside the per-frame loop as the compiler gives them on the finished code (ROCm 7.2), no margin: plain raw Bayer's 158 / 145 plus 32.
+
+This file also holds what the budget files of the other stages (test_raw16_isa, test_raw_color_isa, test_raw_shading_isa) share: the names of
+the one raw walk and the one raw row kernel per STAGES value -- bit 0: 16-bit samples, bit 1: the colour stage, bit 2: the shading map -- and
+the walks' VALU instructions per frame."""
 import re
 
 import pytest
@@ -14,9 +18,43 @@ import test_isa_guards as G
 
 pytestmark = G.needs_hipcc
 
-LOOP_VALU = {0: 190, 1: 177}             # SRC 0: surfaces, 1: the slots' dword-aligned staging frames
-BUDGET = {"k_raw_walk_rows<%d, %d, %s>" % (p, src, per_slot): cap
-          for p in range(4) for src, cap in LOOP_VALU.items() for per_slot in ("false", "true")}
+# STAGES -> {SRC: VALU instructions inside the per-frame loop}; SRC 0: surfaces, 1: the slots' dword-aligned staging frames
+STAGES_LOOP_VALU = {0: {0: 190, 1: 177}, 1: {0: 210, 1: 197}, 2: {0: 262, 1: 249}, 3: {0: 294, 1: 281},
+                    4: {0: 262, 1: 249}, 5: {0: 290, 1: 277}, 6: {0: 334, 1: 321}, 7: {0: 374, 1: 361}}
+
+
+def walk_name(p, src, per_slot, stages):
+    return "k_raw_walk_rows<%d, %d, %s, %d>" % (p, src, per_slot, stages)
+
+
+def walk_budget(stages):
+    """name of a walk -> its loop VALU, for the 16 walks of each of `stages`"""
+    return {walk_name(p, src, per_slot, st): cap
+            for st in stages for p in range(4) for src, cap in STAGES_LOOP_VALU[st].items() for per_slot in ("false", "true")}
+
+
+def row_names(stages):
+    return sorted("k_raw_rows_rgb<%d, %s, %s, %d>" % (p, s, w, st) for st in stages for p in range(4) for s in ("false", "true") for w in ("false", "true"))
+
+
+def stages_of(name):
+    return int(name[name.rindex(" ") + 1:-1])
+
+
+def assert_raw_kernels_are_these(table, insts):
+    """16 walks and 16 row kernels per STAGES value, 128 of each in all, nothing else under the two names; the 50 plain walks beside them."""
+    walks = sorted(n for n in table if "k_raw_walk_rows" in n)
+    rows = sorted(n for n in insts if "k_raw_rows_rgb" in n)
+    assert walks == sorted(walk_budget(range(8))) and len(walks) == 128
+    assert rows == row_names(range(8)) and len(rows) == 128
+    for st in range(8):
+        assert sum(stages_of(n) == st for n in walks) == 16 and sum(stages_of(n) == st for n in rows) == 16, st
+    # the names the six-kernel families had are gone: everything raw is one of the two above
+    assert not [n for n in insts if re.match(r"k_(raw16|cc|cc16|ls|ls16)_", n)]
+    assert len(G._walks()[0]) == 50                               # (a name that held k_undistort_rows would have been counted there)
+
+
+BUDGET = walk_budget([0])
 
 
 def _raw_walks():
@@ -25,9 +63,9 @@ def _raw_walks():
 
 
 def test_there_are_sixteen_conditioned_walks_and_fifty_plain_ones():
-    _, table, _ = _raw_walks()
-    assert len(BUDGET) == 16 and sorted(table) == sorted(BUDGET), sorted(table)
-    assert len(G._walks()[0]) == 50                               # (a name that held k_undistort_rows would have been counted there)
+    _, table, insts = _raw_walks()
+    assert len(BUDGET) == 16 and sorted(n for n in table if stages_of(n) == 0) == sorted(BUDGET), sorted(table)
+    assert_raw_kernels_are_these(table, insts)
 
 
 def test_conditioned_walks_keep_their_budget():

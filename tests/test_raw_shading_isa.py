@@ -1,6 +1,7 @@
-"""The instruction budget of the raw Bayer walks behind the lens-shading correction -- k_ls_walk_rows<PATTERN, SRC, PER_SLOT, CC> over the
-8-bit table form and k_ls16_walk_rows<PATTERN, SRC, PER_SLOT, CC> over the 10- / 12-bit one, each without and with the colour stage
-(k_frontend.hip), DESIGN.md section 4 -- on the generated gfx950 code (hipcc cross-compiles; no GPU needed), from the one compile of
+"""The instruction budget of the raw Bayer walks behind the lens-shading correction -- k_raw_walk_rows<PATTERN, SRC, PER_SLOT, STAGES> with
+STAGES 4 over the 8-bit table form and 5 over the 10- / 12-bit one, 6 and 7 the same with the colour stage (k_frontend.hip; the names
+below are the ones these kernels had as families of their own: k_ls = 4, k_ls16 = 5, with CC 6 and 7, wrapping k_raw = 0, k_raw16 = 1,
+k_cc = 2, k_cc16 = 3), DESIGN.md section 4 -- on the generated gfx950 code (hipcc cross-compiles; no GPU needed), from the one compile of
 k_frontend.hip that test_isa_guards.py makes and through the same tool, tools/isa_split.py.
 
 Per walk, against the form it wraps (k_raw_walk_rows / k_raw16_walk_rows; CC: k_cc_walk_rows / k_cc16_walk_rows): 16 vector-memory
@@ -25,19 +26,21 @@ import re
 import pytest
 
 import test_isa_guards as G
+import test_raw_lut_isa as R
 
 pytestmark = G.needs_hipcc
 
-# (kernel, CC) -> the form it wraps, and {SRC: (loop VALU, VGPRs)}; SRC 0: surfaces, 1: the slots' staging frames
-FORMS = {("k_ls_walk_rows", "false"): ("k_raw_walk_rows", {0: (262, 77), 1: (249, 76)}),
-         ("k_ls_walk_rows", "true"): ("k_cc_walk_rows", {0: (334, 77), 1: (321, 76)}),
-         ("k_ls16_walk_rows", "false"): ("k_raw16_walk_rows", {0: (290, 78), 1: (277, 77)}),
-         ("k_ls16_walk_rows", "true"): ("k_cc16_walk_rows", {0: (374, 79), 1: (361, 78)})}
-WRAPPED_VALU = {"k_raw_walk_rows": {0: 190, 1: 177}, "k_cc_walk_rows": {0: 262, 1: 249}, "k_raw16_walk_rows": {0: 210, 1: 197},
-                "k_cc16_walk_rows": {0: 294, 1: 281}}
+# STAGES of a shading walk -> (STAGES of the form it wraps, {SRC: (loop VALU, VGPRs)}); SRC 0: surfaces, 1: the slots' staging frames
+FORMS = {4: (0, {0: (262, 77), 1: (249, 76)}),
+         6: (2, {0: (334, 77), 1: (321, 76)}),
+         5: (1, {0: (290, 78), 1: (277, 77)}),
+         7: (3, {0: (374, 79), 1: (361, 78)})}
+WRAPPED_VALU = {0: {0: 190, 1: 177}, 2: {0: 262, 1: 249}, 1: {0: 210, 1: 197}, 3: {0: 294, 1: 281}}
+assert all(R.STAGES_LOOP_VALU[w] == v for w, v in WRAPPED_VALU.items())
+assert all(R.STAGES_LOOP_VALU[st] == {src: valu for src, (valu, _) in caps.items()} for st, (_, caps) in FORMS.items())
 # name of a walk -> (name of the wrapped walk, loop VALU, VGPRs, the wrapped walk's loop VALU)
-BUDGET = {"%s<%d, %d, %s, %s>" % (k, p, src, per_slot, cc): ("%s<%d, %d, %s>" % (w, p, src, per_slot), valu, vgpr, WRAPPED_VALU[w][src])
-          for (k, cc), (w, caps) in FORMS.items() for p in range(4) for src, (valu, vgpr) in caps.items() for per_slot in ("false", "true")}
+BUDGET = {R.walk_name(p, src, per_slot, st): (R.walk_name(p, src, per_slot, w), valu, vgpr, WRAPPED_VALU[w][src])
+          for st, (w, caps) in FORMS.items() for p in range(4) for src, (valu, vgpr) in caps.items() for per_slot in ("false", "true")}
 
 
 def _front():
@@ -48,17 +51,14 @@ def _front():
 def test_the_shading_kernels_are_these_and_the_others_are_what_they_were():
     split, table, insts = _front()
     assert len(BUDGET) == 64
-    assert sorted(n for n in table if n.startswith("k_ls") and "_walk_rows" in n) == sorted(BUDGET)
-    rows = sorted(n for n in insts if n.startswith("k_ls") and "_rows_rgb<" in n)
-    assert rows == sorted("%s<%d, %s, %s, %s>" % (k, p, s, w, cc) for k in ("k_ls_rows_rgb", "k_ls16_rows_rgb") for p in range(4)
-                          for s in ("false", "true") for w in ("false", "true") for cc in ("false", "true"))
-    assert sorted(n for n in insts if n.startswith("k_ls")) == sorted(list(BUDGET) + rows)         # nothing else under the prefix
+    assert sorted(n for n in table if "k_raw_walk_rows" in n and R.stages_of(n) >= 4) == sorted(BUDGET)
+    rows = sorted(n for n in insts if n.startswith("k_raw_rows_rgb<") and R.stages_of(n) >= 4)
+    assert rows == R.row_names([4, 5, 6, 7]) and len(rows) == 64
     assert sum(n.startswith("k_shade_expand") for n in insts) == 1
-    # no name of the new kernels is counted among the kernels that the other budget tests select
-    assert len(G._walks()[0]) == 50
-    assert sum("k_raw_walk_rows" in n for n in table) == 16 and sum("k_raw16_walk_rows" in n for n in table) == 16
-    assert sum(n.startswith("k_raw_rows_rgb<") for n in insts) == 16 and sum(n.startswith("k_raw16_rows_rgb<") for n in insts) == 16
-    assert sum(n.startswith("k_cc") for n in insts) == 64
+    # nothing else under the two names; the forms without a map are the 16 walks and 16 row kernels of each of STAGES 0 .. 3 (64 with a
+    # colour stage or without); and no name of them is counted among the kernels that the other budget tests select
+    R.assert_raw_kernels_are_these(table, insts)
+    assert sum(R.stages_of(n) in (2, 3) for n in insts if "k_raw_walk_rows" in n or n.startswith("k_raw_rows_rgb<")) == 64
     # the row conversions: no scratch, no v_mul_lo_u32
     for n in rows:
         assert table[n]["scratch"] == 0 and table[n]["mul_lo"] == 0, (n, table[n])

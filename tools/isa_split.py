@@ -39,10 +39,11 @@ def kernel_name(mangled):
     """k_name or k_name<true / false / N, ...> of an Itanium-mangled kernel symbol (the project's kernels are all named k_*, with bool
     and int template arguments only: k_undistort_rows<5, 1, false>); the symbol itself where that does not fit.  (No demangler is called: ROCm's llvm/bin has
     none, and a guard test should not hang on binutils being installed.)"""
-    m = re.search(r"(\d+)k_", mangled)
+    m = re.search(r"(?:_GLOBAL__N_1)?(\d+)k_", mangled)
     if not m:
         return mangled
-    # (the length prefix follows the anonymous namespace's "_GLOBAL__N_1": take the digits that make the name end at 'E' / 'I')
+    # (the length prefix follows the anonymous namespace's "_GLOBAL__N_1", whose own 1 is not part of it -- a long symbol can have an 'E' at
+    # that distance too; elsewhere: take the digits that make the name end at 'E' / 'I')
     start, digits = m.end(1), m.group(1)
     n = next((int(digits[i:]) for i in range(len(digits)) if mangled[start + int(digits[i:]):start + int(digits[i:]) + 1] in ("E", "I")), None)
     if n is None:
