@@ -274,8 +274,29 @@ int  lt_set_streams(lt_ctx* ctx, int nstreams);
  * everything the context has in flight and is a set-up or occasional call, NOT a per-frame one.  Uploads (all of them) and attached surfaces
  * work as for 8-bit raw Bayer with two bytes a pixel: pitch >= 2 * img_w, and the plane's address and the pitch must be EVEN
  * (LT_ERR_INVALID).  lt_raw16_to_rgb is the conversion alone, lt_bayer_to_rgb's twin: one host frame of h x w words, `lut` = 4 << bits bytes
- * or NULL for the default.  Input formats only, as 8-bit raw Bayer is, with the same refusals.  Not built: MIPI-packed RAW10 / RAW12, 14 and
+ * or NULL for the default.  Input formats only, as 8-bit raw Bayer is, with the same refusals.  Not built: 14 and
  * 16 bits, MSB-aligned containers, a table per stream.
+ *
+ * MIPI-PACKED RAW10 / RAW12, as a CSI-2 receiver writes it (a deserialiser's DMA engine, a raw sensor log; V4L2 SRGGB10P / SRGGB12P and their
+ * siblings) -- LT_INPUT_BAYER10P_RGGB .. _BGGR (36 .. 39) and LT_INPUT_BAYER12P_RGGB .. _BGGR (52 .. 55): the pattern stays layout & 3, bit 2
+ * says packed.  One plane of bytes, numpy uint8 (H, row bytes):
+ *   RAW10  img_w % 4 == 0; a row is 5 * img_w / 4 bytes.  Group g holds sites 4g .. 4g + 3: byte 5g + i is s[4g + i] >> 2 for i = 0 .. 3, and
+ *          bits 2i + 1 : 2i of byte 5g + 4 are s[4g + i] & 3.
+ *   RAW12  img_w even; a row is 3 * img_w / 2 bytes.  Byte 3g is s[2g] >> 4, byte 3g + 1 is s[2g + 1] >> 4, and byte 3g + 2 is
+ *          (s[2g] & 15) | (s[2g + 1] & 15) << 4.
+ * img_h is even and at least 4, as for every raw layout (img_w at least 4 too).  A surface's pitch may be any value that is at least the row
+ * bytes, at ANY byte alignment of plane and pitch.  No bits lie above the sample, so nothing is masked or ignored.  The samples are unpacked
+ * in the kernels, on their way into the lookups: no pass over the frame, no repack on the device, 1.25 / 1.5 bytes a sample over the bus.
+ * Everything a context in one of these layouts with table L (and, optionally, a colour stage and a shading map) computes from packed frames
+ * F -- undistorted rows, planes, masks, records, camera frames, annotated frames, states -- is BIT FOR BIT what the context of the 16-bit
+ * layout (layout & ~4) with the same table, stage and map computes from the unpacked frames (utils.unpack_raw, which is the definition).
+ * lt_set_input_format refuses img_w % 4 != 0 (RAW10), an odd img_w or img_h and sizes below 4 (LT_ERR_INVALID), and on a context with an input
+ * size these layouts are LT_ERR_INVALID too (the 16-bit layouts: LT_ERR_STATE) -- layouts 36 .. 39 and 52 .. 55 were no layouts there before,
+ * and what they answered is kept; lt_set_raw_lut_wide,
+ * lt_set_raw_color and lt_set_raw_shading work as for the 16-bit layouts; lt_raw_to_rgb_color / lt_raw_to_rgb_shaded take these layouts with
+ * `frame` = h dense packed rows (lt_raw16_to_rgb does not: its frame is words).  Input formats only, with the refusals of the other raw
+ * layouts.  Not built: 14- and 16-bit samples, RAW14 packing, MSB-aligned words, big-endian or line-padded CSI-2 framing beyond a plain
+ * pitch, packed sinks, a table, stage or map per stream of a group.
  *
  * THE COLOUR STAGE of raw Bayer input, 8-, 10- and 12-bit alike: what an image signal processor does AFTER the demosaic, where the raw
  * table cannot reach because it mixes channels -- a colour-correction matrix from sensor RGB to display RGB, then one output curve.  `ccm`
@@ -328,7 +349,9 @@ enum lt_input_layout { LT_INPUT_RGB = 0, LT_INPUT_NV12 = 1, LT_INPUT_I420 = 2, L
                        LT_INPUT_BGR = 5, LT_INPUT_RGBA = 6, LT_INPUT_BGRA = 7,
                        LT_INPUT_BAYER_RGGB = 16, LT_INPUT_BAYER_GRBG = 17, LT_INPUT_BAYER_GBRG = 18, LT_INPUT_BAYER_BGGR = 19,
                        LT_INPUT_BAYER10_RGGB = 32, LT_INPUT_BAYER10_GRBG = 33, LT_INPUT_BAYER10_GBRG = 34, LT_INPUT_BAYER10_BGGR = 35,
-                       LT_INPUT_BAYER12_RGGB = 48, LT_INPUT_BAYER12_GRBG = 49, LT_INPUT_BAYER12_GBRG = 50, LT_INPUT_BAYER12_BGGR = 51 };
+                       LT_INPUT_BAYER12_RGGB = 48, LT_INPUT_BAYER12_GRBG = 49, LT_INPUT_BAYER12_GBRG = 50, LT_INPUT_BAYER12_BGGR = 51,
+                       LT_INPUT_BAYER10P_RGGB = 36, LT_INPUT_BAYER10P_GRBG = 37, LT_INPUT_BAYER10P_GBRG = 38, LT_INPUT_BAYER10P_BGGR = 39,
+                       LT_INPUT_BAYER12P_RGGB = 52, LT_INPUT_BAYER12P_GRBG = 53, LT_INPUT_BAYER12P_GBRG = 54, LT_INPUT_BAYER12P_BGGR = 55 };
 #define LT_YUV_BT601 {1220542, 1673527, -852492, -409993, 2116026}   /* video range; OpenCV's constants */
 #define LT_YUV_BT709 {1220542, 1880097, -558891, -223347, 2214593}   /* video range */
 int  lt_set_input_format(lt_ctx* ctx, int layout, const int32_t coeffs[5]);

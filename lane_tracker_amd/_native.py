@@ -286,6 +286,14 @@ BAYER_FORMATS = {"bayer_rggb": 16, "bayer_grbg": 17, "bayer_gbrg": 18, "bayer_bg
 # the 8-bit demosaic.  The pattern is id & 3, in BAYER_FORMATS' order.  Camera frames only; once more a table of its own.
 BAYER_WIDE_FORMATS = {"bayer10_rggb": 32, "bayer10_grbg": 33, "bayer10_gbrg": 34, "bayer10_bggr": 35,
                       "bayer12_rggb": 48, "bayer12_grbg": 49, "bayer12_gbrg": 50, "bayer12_bggr": 51}
+# ... and the same samples MIPI-packed, as a CSI-2 receiver writes them (V4L2 SRGGB10P / SRGGB12P ...): one plane of bytes, (H, W * 5 // 4) --
+# five bytes for four samples, W % 4 == 0 -- or (H, W * 3 // 2) -- three bytes for two --, unpacked in the kernels (utils.pack_raw /
+# unpack_raw are the definition).  id = the 16-bit format's | 4.  Table, colour stage and shading map as for BAYER_WIDE_FORMATS.
+BAYER_PACKED_FORMATS = {"bayer10p_rggb": 36, "bayer10p_grbg": 37, "bayer10p_gbrg": 38, "bayer10p_bggr": 39,
+                        "bayer12p_rggb": 52, "bayer12p_grbg": 53, "bayer12p_gbrg": 54, "bayer12p_bggr": 55}
+# every raw format whose samples have more than 8 bits: behind a wide table u8 (4, 2**bits)
+BAYER_DEEP_FORMATS = dict(BAYER_WIDE_FORMATS, **BAYER_PACKED_FORMATS)
+RAW_FORMATS = dict(BAYER_FORMATS, **BAYER_DEEP_FORMATS)
 YUV_MATRICES = {"bt601": (1220542, 1673527, -852492, -409993, 2116026),
                 "bt709": (1220542, 1880097, -558891, -223347, 2214593)}
 
@@ -324,13 +332,37 @@ def rgb_to_surfaces(rgb_ptr, frame_stride, img_size, sink, matrix="bt601", devic
 
 def raw_bits(pixel_format):
     """The sample bits of a raw Bayer format: 8, 10 or 12; 0 for every other format."""
-    if pixel_format in BAYER_WIDE_FORMATS:
-        return 10 if BAYER_WIDE_FORMATS[pixel_format] < 48 else 12
+    if pixel_format in BAYER_DEEP_FORMATS:
+        return 10 if BAYER_DEEP_FORMATS[pixel_format] < 48 else 12
     return 8 if pixel_format in BAYER_FORMATS else 0
 
 
+def packed_row_bytes(pixel_format, w):
+    """The bytes of a row of `w` samples of a MIPI-packed raw format: w * 5 // 4 (RAW10) or w * 3 // 2 (RAW12)."""
+    return int(w) * 5 // 4 if raw_bits(pixel_format) == 10 else int(w) * 3 // 2
+
+
+def unpacked_format(pixel_format):
+    """'bayer10p_rggb' -> 'bayer10_rggb': the 16-bit format of a MIPI-packed one's samples (any other name: itself)."""
+    return pixel_format.replace("p_", "_", 1) if pixel_format in BAYER_PACKED_FORMATS else pixel_format
+
+
+def raw_frame_size(a, pattern):
+    """(h, w) of the raw Bayer frame `a` -- (H, W), or (H, row bytes) for a MIPI-packed pattern --, ValueError where that is no legal size."""
+    if pattern in BAYER_PACKED_FORMATS:
+        per, of = (5, 4) if raw_bits(pattern) == 10 else (3, 2)
+        if a.ndim != 2 or a.shape[1] % per or a.shape[0] % 2 or a.shape[0] < 4 or a.shape[1] * of // per < 4:
+            raise ValueError("a MIPI-packed %r frame is a 2-D uint8 array of shape (H, W * %d // %d) with H even, W a multiple of %d and both at "
+                             "least 4, got %r" % (pattern, per, of, of, a.shape))
+        return a.shape[0], a.shape[1] * of // per
+    if a.ndim != 2 or a.shape[0] % 2 or a.shape[1] % 2 or a.shape[0] < 4 or a.shape[1] < 4:
+        raise ValueError("a raw Bayer frame is a 2-D array of shape (H, W) with H and W even and at least 4, got %r" % (a.shape,))
+    return a.shape[0], a.shape[1]
+
+
 def frame_dtype(pixel_format):
-    """The dtype of a camera frame in `pixel_format`: uint16 for 10- / 12-bit raw Bayer, uint8 for everything else."""
+    """The dtype of a camera frame in `pixel_format`: uint16 for 10- / 12-bit raw Bayer in words, uint8 for everything else (MIPI-packed
+    10- / 12-bit raw Bayer included)."""
     return np.dtype(np.uint16) if pixel_format in BAYER_WIDE_FORMATS else np.dtype(np.uint8)
 
 
@@ -348,18 +380,18 @@ def pixel_format_id(pixel_format):
     try:
         if pixel_format in INPUT_FORMATS:
             return INPUT_FORMATS[pixel_format]
-        if pixel_format in BAYER_WIDE_FORMATS:
-            return BAYER_WIDE_FORMATS[pixel_format]
+        if pixel_format in BAYER_DEEP_FORMATS:
+            return BAYER_DEEP_FORMATS[pixel_format]
         return RGB_FAMILY[pixel_format] if pixel_format in RGB_FAMILY else BAYER_FORMATS[pixel_format]
     except (KeyError, TypeError):
         raise ValueError("pixel_format must be 'rgb', 'nv12', 'i420', 'yuy2', 'uyvy', 'bgr', 'rgba', 'bgra' or 'bayer_rggb' / '_grbg' / '_gbrg' / "
-                         "'_bggr' (10 / 12 bits: 'bayer10_*' / 'bayer12_*'), got %r" % (pixel_format,)) from None
+                         "'_bggr' (10 / 12 bits: 'bayer10_*' / 'bayer12_*'; MIPI-packed: 'bayer10p_*' / 'bayer12p_*'), got %r" % (pixel_format,)) from None
 
 
 def format_name(layout):
     """The name of an lt_input_layout value."""
     return {v: n for n, v in list(INPUT_FORMATS.items()) + list(RGB_FAMILY.items()) + list(BAYER_FORMATS.items()) +
-            list(BAYER_WIDE_FORMATS.items())}[int(layout)]
+            list(BAYER_DEEP_FORMATS.items())}[int(layout)]
 
 
 def is_yuv(layout):
@@ -369,7 +401,7 @@ def is_yuv(layout):
 
 def sink_format_id(pixel_format):
     """pixel_format_id for a destination of annotated frames: packed 4:2:2 and raw Bayer are input formats only."""
-    if pixel_format in PACKED_422 or pixel_format in BAYER_FORMATS or pixel_format in BAYER_WIDE_FORMATS:
+    if pixel_format in PACKED_422 or pixel_format in RAW_FORMATS:
         raise ValueError("%r is an input format only: annotated frames go into 'rgb', 'bgr', 'rgba', 'bgra', 'nv12' or 'i420' surfaces" % (pixel_format,))
     return pixel_format_id(pixel_format)
 
@@ -400,7 +432,7 @@ def checked_raw_lut(raw_lut, pixel_format):
     if raw_lut is None:
         return None
     from .utils import checked_raw_lut as _checked
-    if pixel_format in BAYER_WIDE_FORMATS:               # u8 (4, 2**bits)
+    if pixel_format in BAYER_DEEP_FORMATS:               # u8 (4, 2**bits)
         return _checked(raw_lut, raw_bits(pixel_format))
     if pixel_format not in BAYER_FORMATS:
         raise ValueError("raw_lut conditions raw Bayer frames: pixel_format=%r takes none" % (pixel_format,))
@@ -410,7 +442,7 @@ def checked_raw_lut(raw_lut, pixel_format):
 def effective_raw_lut(raw_lut, pixel_format):
     """checked_raw_lut, and for the 10- / 12-bit formats -- which always have a table -- the default `utils.raw_lut(bits=..)` for None."""
     lut = checked_raw_lut(raw_lut, pixel_format)
-    if lut is None and pixel_format in BAYER_WIDE_FORMATS:
+    if lut is None and pixel_format in BAYER_DEEP_FORMATS:
         from .utils import raw_lut as _default
         lut = _default(bits=raw_bits(pixel_format))
     return lut
@@ -422,7 +454,7 @@ def checked_raw_color(ccm, curve, pixel_format):
     if ccm is None and curve is None:
         return None, None
     from .utils import checked_raw_ccm, checked_raw_curve
-    if pixel_format not in BAYER_FORMATS and pixel_format not in BAYER_WIDE_FORMATS:
+    if pixel_format not in RAW_FORMATS:
         raise ValueError("raw_ccm / raw_curve follow the demosaic of raw Bayer frames: pixel_format=%r takes none" % (pixel_format,))
     return (None if ccm is None else checked_raw_ccm(ccm)), (None if curve is None else checked_raw_curve(curve))
 
@@ -434,7 +466,7 @@ def checked_raw_shading(shading, pixel_format):
     if shading is None:
         return None
     from .utils import checked_raw_shading as _checked
-    if pixel_format not in BAYER_FORMATS and pixel_format not in BAYER_WIDE_FORMATS:
+    if pixel_format not in RAW_FORMATS:
         raise ValueError("raw_shading corrects raw Bayer frames: pixel_format=%r takes none" % (pixel_format,))
     return _checked(shading, raw_bits(pixel_format))
 
@@ -460,7 +492,8 @@ def checked_input_size(input_size, img_size, pixel_format="rgb"):
 
 def frame_shape(img_size, pixel_format="rgb"):
     """Shape of one camera frame of `img_size` = (width, height) in `pixel_format`: (H, W, 3), (H * 3 // 2, W) for 4:2:0, or
-    (H, W, 2) for packed 4:2:2 (OpenCV's CV_8UC2); 'bgr': (H, W, 3), 'rgba' / 'bgra': (H, W, 4); raw Bayer: (H, W)."""
+    (H, W, 2) for packed 4:2:2 (OpenCV's CV_8UC2); 'bgr': (H, W, 3), 'rgba' / 'bgra': (H, W, 4); raw Bayer: (H, W), MIPI-packed
+    (H, W * 5 // 4) / (H, W * 3 // 2) bytes."""
     w, h = int(img_size[0]), int(img_size[1])
     if pixel_format_id(pixel_format) == 0:
         return (h, w, 3)
@@ -468,9 +501,13 @@ def frame_shape(img_size, pixel_format="rgb"):
         if w < 1 or h < 1:
             raise ValueError("empty %r frames: %dx%d" % (pixel_format, w, h))
         return (h, w, 3 if pixel_format == "bgr" else 4)
-    if pixel_format in BAYER_FORMATS or pixel_format in BAYER_WIDE_FORMATS:
+    if pixel_format in RAW_FORMATS:
         if w % 2 or h % 2 or w < 4 or h < 4:
             raise ValueError("raw Bayer frames need an even width and height of at least 4, got %dx%d" % (w, h))
+        if pixel_format in BAYER_PACKED_FORMATS:
+            if raw_bits(pixel_format) == 10 and w % 4:
+                raise ValueError("MIPI-packed RAW10 frames need a width that is a multiple of 4, got %dx%d" % (w, h))
+            return (h, packed_row_bytes(pixel_format, w))
         return (h, w)
     if pixel_format in PACKED_422:
         if w % 2 or w < 4 or h < 1:
@@ -1000,7 +1037,7 @@ class Context:
         on.  Waits for the context's outstanding work: a set-up or occasional call, not a per-frame one.  A 10- / 12-bit context:
         u8 (4, 2**bits), None for the default `utils.raw_lut(bits=..)` (lt_set_raw_lut_wide)."""
         a = checked_raw_lut(lut, self._pixel_format)
-        if self._pixel_format in BAYER_WIDE_FORMATS:
+        if self._pixel_format in BAYER_DEEP_FORMATS:
             _check(self.lib.lt_set_raw_lut_wide(self._h, None if a is None else a.ctypes.data, 1 << raw_bits(self._pixel_format)))
             return
         _check(self.lib.lt_set_raw_lut(self._h, None if a is None else a.ctypes.data))
@@ -1008,7 +1045,7 @@ class Context:
     def raw_lut(self):
         """-> the raw table, u8 (4, 256), or None (lt_get_raw_lut); a 10- / 12-bit context: the table in effect, u8 (4, 2**bits)
         (lt_get_raw_lut_wide)."""
-        if self._pixel_format in BAYER_WIDE_FORMATS:
+        if self._pixel_format in BAYER_DEEP_FORMATS:
             n = 1 << raw_bits(self._pixel_format)
             out = np.zeros((4, n), np.uint8)
             _check(self.lib.lt_get_raw_lut_wide(self._h, out.ctypes.data, n))
@@ -1060,18 +1097,17 @@ class Context:
 
     def raw_to_rgb_shaded(self, frame, pattern, shading, raw_lut=None, ccm=None, curve=None):
         """`raw_to_rgb_color` behind the shading map `shading` (lt_raw_to_rgb_shaded); without `ccm` and `curve`: no colour stage."""
-        if pattern not in BAYER_FORMATS and pattern not in BAYER_WIDE_FORMATS:
-            raise ValueError("pattern must be one of %s, got %r" % (", ".join(repr(n) for n in list(BAYER_FORMATS) + list(BAYER_WIDE_FORMATS)), pattern))
+        if pattern not in RAW_FORMATS:
+            raise ValueError("pattern must be one of %s, got %r" % (", ".join(repr(n) for n in RAW_FORMATS), pattern))
         a = frames_array(frame, pattern)
         lut = checked_raw_lut(raw_lut, pattern)
         m, t = checked_raw_color(ccm, curve, pattern)
         s = checked_raw_shading(shading, pattern)
         if s is None:
             raise ValueError("raw_to_rgb_shaded takes a shading map (raw_to_rgb_color: the conversion without one)")
-        if a.ndim != 2 or a.shape[0] % 2 or a.shape[1] % 2 or a.shape[0] < 4 or a.shape[1] < 4:
-            raise ValueError("a raw Bayer frame is a 2-D array of shape (H, W) with H and W even and at least 4, got %r" % (a.shape,))
-        out = np.empty((a.shape[0], a.shape[1], 3), np.uint8)
-        _check(self.lib.lt_raw_to_rgb_shaded(self._h, a.ctypes.data, a.shape[0], a.shape[1], pixel_format_id(pattern),
+        h, w = raw_frame_size(a, pattern)
+        out = np.empty((h, w, 3), np.uint8)
+        _check(self.lib.lt_raw_to_rgb_shaded(self._h, a.ctypes.data, h, w, pixel_format_id(pattern),
                                              None if lut is None else lut.ctypes.data, 1 << raw_bits(pattern),
                                              None if m is None else m.ctypes.data, None if t is None else t.ctypes.data,
                                              s.mesh.ctypes.data, s.mesh.shape[2], s.mesh.shape[1], s.black.ctypes.data, out.ctypes.data))
@@ -1080,15 +1116,14 @@ class Context:
     def raw_to_rgb_color(self, frame, pattern, raw_lut=None, ccm=None, curve=None):
         """One raw Bayer frame (H, W) in any of the twelve raw patterns -> RGB (H, W, 3) with the colour stage, on the device
         (lt_raw_to_rgb_color): looked up in `raw_lut` (None: none / the 10- / 12-bit default), demosaiced, matrix, curve."""
-        if pattern not in BAYER_FORMATS and pattern not in BAYER_WIDE_FORMATS:
-            raise ValueError("pattern must be one of %s, got %r" % (", ".join(repr(n) for n in list(BAYER_FORMATS) + list(BAYER_WIDE_FORMATS)), pattern))
+        if pattern not in RAW_FORMATS:
+            raise ValueError("pattern must be one of %s, got %r" % (", ".join(repr(n) for n in RAW_FORMATS), pattern))
         a = frames_array(frame, pattern)
         lut = checked_raw_lut(raw_lut, pattern)
         m, t = checked_raw_color(ccm, curve, pattern)
-        if a.ndim != 2 or a.shape[0] % 2 or a.shape[1] % 2 or a.shape[0] < 4 or a.shape[1] < 4:
-            raise ValueError("a raw Bayer frame is a 2-D array of shape (H, W) with H and W even and at least 4, got %r" % (a.shape,))
-        out = np.empty((a.shape[0], a.shape[1], 3), np.uint8)
-        _check(self.lib.lt_raw_to_rgb_color(self._h, a.ctypes.data, a.shape[0], a.shape[1], pixel_format_id(pattern),
+        h, w = raw_frame_size(a, pattern)
+        out = np.empty((h, w, 3), np.uint8)
+        _check(self.lib.lt_raw_to_rgb_color(self._h, a.ctypes.data, h, w, pixel_format_id(pattern),
                                             None if lut is None else lut.ctypes.data, 1 << raw_bits(pattern),
                                             None if m is None else m.ctypes.data, None if t is None else t.ctypes.data, out.ctypes.data))
         return out
@@ -1097,6 +1132,8 @@ class Context:
         """One 8-bit raw Bayer frame (H, W), H and W even and at least 4, -> RGB (H, W, 3): the bilinear demosaic, on the device
         (lt_bayer_to_rgb).  A 10- / 12-bit pattern: one uint16 frame, every sample looked up in `raw_lut` -- u8 (4, 2**bits), None: the
         default -- first (lt_raw16_to_rgb)."""
+        if pattern in BAYER_PACKED_FORMATS:      # packed rows: the colour-stage converter with the identity stage is the table alone
+            return self.raw_to_rgb_color(frame, pattern, raw_lut)
         if pattern in BAYER_WIDE_FORMATS:
             a = frames_array(frame, pattern)
             lut = checked_raw_lut(raw_lut, pattern)
@@ -1433,7 +1470,7 @@ class Context:
         k = None
         if self.input_format()[0] in PACKED_422:
             raise ValueError("packed 4:2:2 is an input format only: nothing is drawn into such surfaces")
-        if self.input_format()[0] in BAYER_FORMATS or self.input_format()[0] in BAYER_WIDE_FORMATS:
+        if self.input_format()[0] in RAW_FORMATS:
             raise ValueError("raw Bayer is an input format only: nothing is drawn into such surfaces")
         if self.input_format()[0] in RGB_FAMILY:
             raise ValueError("nothing is drawn into 'bgr' / 'rgba' / 'bgra' surfaces in place: such sinks are written by store_overlay_device")

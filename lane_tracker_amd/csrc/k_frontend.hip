@@ -23,6 +23,11 @@
 //                      lens-shading correction (lt_set_raw_shading; shade_arith.h), every sample corrected by the gain of its site before
 //                      its table lookup; the gains lie in a plane that k_shade_expand makes of the map's mesh once, and a walk loads the
 //                      16 of its window once and keeps them across its frames
+//   k_mipi_walk_rows<PATTERN, SRC, PER_SLOT, STAGES, PACK>, k_mipi_rows_rgb<PATTERN, SURF, WIDE, STAGES, PACK>  the two above over MIPI-packed
+//                      RAW10 / RAW12 frames (layouts 36 .. 39, 52 .. 55: one plane of bytes, PACK 0 five bytes for four sites, 1 three bytes
+//                      for two; mipi_arith.h), STAGES 1, 3, 5, 7: the 16-bit forms with every window row (every site, every 16 columns of
+//                      the row conversion) unpacked into 16-bit words on its way in -- the same 96-bit window loads, table, LDS and
+//                      staging; byte permutes and packed shifts with selectors found once per walk, no memory instruction added
 //   k_warp_split       cv2.warpPerspective      lane_tracker.py:834
 //                      + img[:,:,0]             lane_tracker.py:207
 //                      + cvtColor(RGB2LAB)[:,:,2] lane_tracker.py:208
@@ -46,6 +51,7 @@
 #include "bayer_arith.h"
 #include "front_arith.h"
 #include "lt_internal.h"
+#include "mipi_arith.h"
 #include "shade_arith.h"
 #include "yuv_arith.h"
 
@@ -92,9 +98,14 @@ typedef unsigned u32x3 __attribute__((ext_vector_type(3)));
 // The sizeof(W) = 4 / 8 bytes at byte `off` (+ the scalar `soff`) of a buffer: the two / three aligned dwords that hold them,
 // shifted into place with v_alignbyte_b32 -- an unaligned dwordx2 at 3-byte pitch occupies the memory pipe for ~32 cycles, an
 // aligned dwordx3 for ~20.  What a window holds beyond the samples it was fetched for is never used.
+// sizeof(W) = 12 (Bytes12): all that those three dwords hold from byte `off` on, the last 0 .. 3 bytes zero.
+struct Bytes12 { uint32_t w0, w1, w2; };
 template <class W>
 __device__ __forceinline__ W window_at(__amdgpu_buffer_rsrc_t rs, uint32_t off, int soff) {
-    if constexpr (sizeof(W) == 8) {
+    if constexpr (sizeof(W) == 12) {
+        const u32x3 d = __builtin_amdgcn_raw_buffer_load_b96(rs, (int)(off & ~3u), soff, 0);
+        return W{__builtin_amdgcn_alignbyte(d.y, d.x, off & 3u), __builtin_amdgcn_alignbyte(d.z, d.y, off & 3u), __builtin_amdgcn_alignbyte(0u, d.z, off & 3u)};
+    } else if constexpr (sizeof(W) == 8) {
         const u32x3 d = __builtin_amdgcn_raw_buffer_load_b96(rs, (int)(off & ~3u), soff, 0);
         const uint32_t lo = __builtin_amdgcn_alignbyte(d.y, d.x, off & 3u), hi = __builtin_amdgcn_alignbyte(d.z, d.y, off & 3u);
         return (uint64_t)lo | ((uint64_t)hi << 32);
@@ -460,6 +471,49 @@ struct ShadeStage : Base {
 template <class B> struct PlacesRows<ShadeStage<B>> : std::true_type {};
 template <class B> struct StagesTable<ShadeStage<B>> : std::true_type {};
 
+// MIPI-packed RAW10 / RAW12 (mipi_arith.h; PACK 0: five bytes for four sites, 1: three bytes for two) in front of Bayer16Lut, shaded or not:
+// Bayer8's placement once more, the 4 x 4 window of sites being four windows of at most 9 / 8 bytes from byte first_byte(bx) of their rows --
+// each the one aligned 96-bit load of the 16-bit walk, at any byte alignment of the row -- and every window row unpacked into the four 16-bit
+// words that Inner decodes.  Which bytes and bits of a window hold its four samples depends on bx alone: the selectors and shifts are found
+// once per walk (place), and a frame adds byte permutes, packed shifts and ors -- no memory instruction, no LDS access.  Table, dynamic LDS,
+// staging, mask and lookups are Inner's: the samples have no bits above `bits`, so the mask changes nothing.
+template <int PACK, class Inner>
+struct MipiUnpack : Inner {
+    typedef std::conditional_t<PACK == ma::PACK10, Bytes12, uint64_t> Window;
+    struct Row { uint32_t w0, w1, w2; };                    // (w2: RAW10 only)
+    struct Taps { Row r0, r1, r2, r3; };
+    ma::Unpack up;
+    int col;
+    __device__ __forceinline__ void place(const TapCols& c) {
+        Inner::place(c);
+        up = ma::unpack_of(PACK, this->bx);
+        col = ma::first_byte(PACK, this->bx);
+    }
+    __device__ __forceinline__ static PlaneGeom plane(const FrontEndGeom& g, int) { return PlaneGeom{g.img_h, ma::row_bytes(PACK, g.img_w), 0u}; }
+    template <class Source, class Plane>
+    __device__ __forceinline__ Row row_at(const Source& src, const Plane& p0, int row) const {
+        const Window w = src.template window<Window>(p0, row, col);
+        if constexpr (PACK == ma::PACK10) return Row{w.w0, w.w1, w.w2};
+        else return Row{(uint32_t)w, (uint32_t)(w >> 32), 0u};
+    }
+    template <class Source>
+    __device__ __forceinline__ Taps fetch(const Source& src, const typename Source::Frame& f, const FrontEndGeom& g, int, int) const {
+        const auto p0 = src.plane(f, plane(g, 0), 0);
+        return Taps{row_at(src, p0, this->by), row_at(src, p0, this->by + 1), row_at(src, p0, this->by + 2), row_at(src, p0, this->by + 3)};
+    }
+    __device__ __forceinline__ uint64_t words(const Row& r) const {
+        uint32_t lo, hi;
+        ma::samples4<PACK>(up, r.w0, r.w1, r.w2, lo, hi);
+        return (uint64_t)lo | ((uint64_t)hi << 32);
+    }
+    __device__ __forceinline__ void decode(const Taps& t, uint32_t& a0, uint32_t& a1, uint32_t& b0, uint32_t& b1) const {
+        const typename Inner::Taps c{words(t.r0), words(t.r1), words(t.r2), words(t.r3)};
+        Inner::decode(c, a0, a1, b0, b1);
+    }
+};
+template <int K, class I> struct PlacesRows<MipiUnpack<K, I>> : std::true_type {};
+template <int K, class I> struct StagesTable<MipiUnpack<K, I>> : std::true_type {};
+
 // The slots' own frames: `stride` bytes apart, planes dense.  One buffer resource covers the frames [z0, z1) of the walk (a frame
 // is selected by the scalar offset of the load) plus the format's padding behind them; beyond that the resource returns 0.
 // 32-bit offsets (a walk stays below 2^30 bytes: launch_undistort_rows) keep the address math on full-rate 24-bit multiplies.
@@ -682,6 +736,30 @@ __global__ __launch_bounds__(256) void k_raw_walk_rows(const SurfEntry* __restri
     fmt.w = g.img_w, fmt.h = g.img_h, fmt.lut = lds + CURVE;
     if constexpr (W16) fmt.table = reinterpret_cast<const uint4*>(r.table), fmt.bits = r.bits, fmt.mask = (1u << r.bits) - 1u;
     else fmt.table = r.table;
+    if constexpr (CC) fmt.cm = r.cm, fmt.curve = lds;
+    if constexpr (LS) fmt.shade_with(r.gains, r.blk);
+    if constexpr (SRC == SRC_SURFACES) undistort_walk<PER_SLOT>(a, SurfSource{tab}, fmt);
+    else undistort_walk<PER_SLOT>(a, SlotSource<true>{frames, stride}, fmt);
+}
+
+// ... over MIPI-packed RAW10 / RAW12 frames (PACK; mipi_arith.h): k_raw_walk_rows' 16-bit forms (STAGES 1, 3, 5, 7) with every window row
+// unpacked on its way in -- the same parameters, the same dynamic LDS, r.bits = 10 / 12 as PACK says.
+template <int PATTERN, int SRC, bool PER_SLOT, int STAGES, int PACK>
+__global__ __launch_bounds__(256) void k_mipi_walk_rows(const SurfEntry* __restrict__ tab, const uint8_t* __restrict__ frames, size_t stride,
+                                                       const int16_t* __restrict__ uxy, const uint16_t* __restrict__ ufrac,
+                                                       const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
+                                                       uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb, int remap,
+                                                       RawStages r) {
+    static_assert(SRC == SRC_SURFACES || SRC == SRC_SLOTS, "a raw Bayer staging frame is dword-aligned");
+    static_assert((STAGES & 1) != 0, "packed samples are 10 / 12 bits wide: behind the wide table");
+    constexpr bool CC = (STAGES & 2) != 0, LS = (STAGES & 4) != 0;
+    constexpr int CURVE = CC ? 256 : 0;
+    uint8_t* lds = s_lut_wide;
+    const WalkArgs a{uxy, ufrac, SlotTables{sets, &ids}, g, und, und_px, first_slot, n, PER_SLOT ? 1 : fpb, remap};
+    using Unpacked = MipiUnpack<PACK, std::conditional_t<LS, ShadeStage<Bayer16Lut<PATTERN>>, Bayer16Lut<PATTERN>>>;
+    std::conditional_t<CC, ColorStage<Unpacked>, Unpacked> fmt{};
+    fmt.w = g.img_w, fmt.h = g.img_h, fmt.lut = lds + CURVE;
+    fmt.table = reinterpret_cast<const uint4*>(r.table), fmt.bits = r.bits, fmt.mask = (1u << r.bits) - 1u;
     if constexpr (CC) fmt.cm = r.cm, fmt.curve = lds;
     if constexpr (LS) fmt.shade_with(r.gains, r.blk);
     if constexpr (SRC == SRC_SURFACES) undistort_walk<PER_SLOT>(a, SurfSource{tab}, fmt);
@@ -947,18 +1025,25 @@ struct ColorPost {
 // plane `gp` (uint16, w a row), and the pedestal of its phase before it is looked up; the 16 gains of wide's 16 columns are two 16-byte loads
 // (w, x0 and the plane's base are multiples of 16).  The bodies differ in how one site (`one`) and the four conditioned dwords of 16 sites
 // (`row16`) are obtained, and in nothing else.  A body of its own, so that the plain one above stays the code it was.
-template <int P, bool W16, bool LS>
+// PACK (0 / 1, with W16; -1: none): the rows are MIPI-packed RAW10 / RAW12 (mipi_arith.h), a site two byte accesses, wide's 16 columns 20 / 24
+// bytes from a multiple of 4 -- five / six dword loads (every base and pitch of the launch a multiple of 4) -- unpacked into the words of W16.
+template <int P, bool W16, bool LS, int PACK = -1>
 struct RowsRaw {
+    static_assert(PACK < 0 || W16, "packed samples are 10 / 12 bits wide");
     const uint8_t* lut;
     int bits;
     uint32_t mask;                           // (1 << bits) - 1
     const uint16_t* gp;                      // LS
     RawShadeBlack blk;
-    __device__ __forceinline__ static Planes dense(const uint8_t* frame, int, int w) { return Planes{frame, nullptr, nullptr, W16 ? 2 * w : w, 0}; }
+    __device__ __forceinline__ static Planes dense(const uint8_t* frame, int, int w) {
+        if constexpr (PACK >= 0) return Planes{frame, nullptr, nullptr, ma::row_bytes(PACK, w), 0};
+        else return Planes{frame, nullptr, nullptr, W16 ? 2 * w : w, 0};
+    }
     // the table row of the sites of row parity par_y and column parity par_x
     __device__ __forceinline__ const uint8_t* trow(int par_y, int par_x) const { return lut + ba::lut_row_wide(bits, P, par_y, par_x); }
     __device__ __forceinline__ static uint32_t site(const uint8_t* row, int x) {
-        if constexpr (W16) return reinterpret_cast<const uint16_t*>(row)[x];
+        if constexpr (PACK >= 0) return ma::site_at(PACK, row, x);
+        else if constexpr (W16) return reinterpret_cast<const uint16_t*>(row)[x];
         else return row[x];
     }
     // site x of the row `row` of the mosaic (row parity py), whose gains are `grow`: (shaded and) looked up
@@ -988,7 +1073,19 @@ struct RowsRaw {
             else if constexpr (LS) m[j] = sa::shade_condition4(lo, g[2 * j], g[2 * j + 1], k, ta, tb);
             else m[j] = ba::condition4(lo, ta, tb);
         };
-        if constexpr (W16) {
+        if constexpr (PACK >= 0) {
+            constexpr int ND = PACK == ma::PACK10 ? 5 : 6;
+            const uint32_t* in = reinterpret_cast<const uint32_t*>(row + ma::first_byte(PACK, x0));
+            uint32_t q[ND];
+#pragma unroll
+            for (int i = 0; i < ND; ++i) q[i] = in[i];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                uint32_t lo, hi;
+                ma::group4<PACK>(q, j, lo, hi);
+                four(j, lo, hi);
+            }
+        } else if constexpr (W16) {
             const uint4 q0 = *reinterpret_cast<const uint4*>(row + 2 * x0), q1 = *reinterpret_cast<const uint4*>(row + 2 * x0 + 16);
             four(0, q0.x, q0.y); four(1, q0.z, q0.w); four(2, q1.x, q1.y); four(3, q1.z, q1.w);
         } else {
@@ -1090,6 +1187,31 @@ __global__ __launch_bounds__(256) void k_raw_rows_rgb(std::conditional_t<SURF, S
     for (int i = threadIdx.x; i < CURVE / 16 + (1 << (bits - 2)); i += THREADS) reinterpret_cast<uint4*>(lds)[i] = reinterpret_cast<const uint4*>(r.table)[i];
     __syncthreads();
     typedef RowsRaw<PATTERN, W16, LS> D;
+    const D body{lds + CURVE, bits, (1u << bits) - 1u, r.gains, r.blk};
+    Planes p;
+    if constexpr (SURF) p = surf_planes(src.e[blockIdx.z]);
+    else p = D::dense(src.p + (size_t)blockIdx.z * src.stride, h, w);
+    uint8_t* dst = rgb + (size_t)blockIdx.z * rgb_stride;
+    const int i = (int)(blockIdx.x * THREADS + threadIdx.x), row = r0 + (int)blockIdx.y;
+    std::conditional_t<CC, ColorPost, NoPost> post{};
+    if constexpr (CC) post = ColorPost{r.cm, lds};
+    if constexpr (WIDE) body.wide(p, dst, h, w, row, i * 16, post);
+    else body.any(p, dst, h, w, row, i, post);
+}
+
+// ... over MIPI-packed RAW10 / RAW12 rows (PACK): k_raw_rows_rgb's 16-bit forms, RowsRaw's two bodies with the packed accesses.  The wide body
+// needs every base and pitch of the frames a multiple of 4 only (and those of the RGB frames a multiple of 16, as ever).
+template <int PATTERN, bool SURF, bool WIDE, int STAGES, int PACK>
+__global__ __launch_bounds__(256) void k_mipi_rows_rgb(std::conditional_t<SURF, SurfChunk, DenseFrames> src, uint8_t* __restrict__ rgb,
+                                                      size_t rgb_stride, int w, int r0, int h, RawStages r) {
+    static_assert((STAGES & 1) != 0, "packed samples are 10 / 12 bits wide: behind the wide table");
+    constexpr bool CC = (STAGES & 2) != 0, LS = (STAGES & 4) != 0;
+    constexpr int THREADS = WIDE ? 64 : 256, CURVE = CC ? 256 : 0;
+    uint8_t* lds = s_lut_wide;
+    const int bits = r.bits;
+    for (int i = threadIdx.x; i < CURVE / 16 + (1 << (bits - 2)); i += THREADS) reinterpret_cast<uint4*>(lds)[i] = reinterpret_cast<const uint4*>(r.table)[i];
+    __syncthreads();
+    typedef RowsRaw<PATTERN, true, LS, PACK> D;
     const D body{lds + CURVE, bits, (1u << bits) - 1u, r.gains, r.blk};
     Planes p;
     if constexpr (SURF) p = surf_planes(src.e[blockIdx.z]);
@@ -1574,6 +1696,10 @@ static void launch_walk(hipStream_t s, dim3 grid, FrameSource src, int layout, Y
             with_stages(raw, [&](auto st) {
                 constexpr int P = decltype(p)::value, ST = decltype(st)::value;
                 auto k_walk = src.tab ? k_raw_walk_rows<P, SRC_SURFACES, PER_SLOT, ST> : k_raw_walk_rows<P, SRC_SLOTS, PER_SLOT, ST>;
+                if constexpr ((ST & 1) != 0) {           // MIPI-packed samples: the packed form of the same walk
+                    if (raw.pack == ma::PACK10) k_walk = src.tab ? k_mipi_walk_rows<P, SRC_SURFACES, PER_SLOT, ST, ma::PACK10> : k_mipi_walk_rows<P, SRC_SLOTS, PER_SLOT, ST, ma::PACK10>;
+                    else if (raw.pack == ma::PACK12) k_walk = src.tab ? k_mipi_walk_rows<P, SRC_SURFACES, PER_SLOT, ST, ma::PACK12> : k_mipi_walk_rows<P, SRC_SLOTS, PER_SLOT, ST, ma::PACK12>;
+                }
                 hipLaunchKernelGGL(k_walk, grid, dim3(256), raw_dynamic_lds(raw), s, src.tab, src.frames, src.stride, uxy, ufrac, sets, ids, g, und, und_px,
                                    first_slot, n, fpb, remap, raw);
             });
@@ -1605,11 +1731,12 @@ void launch_undistort_rows(hipStream_t s, FrameSource src, int layout, YuvCoef k
 
 // The row conversion of n frames in `layout` (not 0), dense or from surfaces: the 16-column kernel where the width and every base and
 // pitch of the launch (`bits`: all of them ORed) are multiples of 16, the byte-wise one otherwise; behind a raw table the raw kernel, in the
-// same two launch shapes.
+// same two launch shapes.  MIPI-packed rows (raw.pack) are read in dwords: multiples of 4 there, of 16 on the RGB side.
 template <bool SURF, class Src>
 static void launch_rows_to_rgb(hipStream_t s, int layout, const Src& src, size_t bits, YuvCoef k, uint8_t* rgb, size_t rgb_stride, int h, int w,
                                int r0, int r1, int n, const RawStages& raw) {
-    const bool wide = (w & 15) == 0 && (bits & 15) == 0;
+    const bool packed = raw.table && raw.pack >= 0;
+    const bool wide = (w & 15) == 0 && (packed ? (bits & 3) == 0 && ((rgb_stride | (size_t)(uintptr_t)rgb) & 15) == 0 : (bits & 15) == 0);
     const dim3 block(wide ? 64 : 256);
     if (raw.table) {
         const dim3 grid((unsigned)(wide ? (w / 16 + 63) / 64 : (w + 255) / 256), (unsigned)(r1 - r0), (unsigned)n);
@@ -1617,6 +1744,10 @@ static void launch_rows_to_rgb(hipStream_t s, int layout, const Src& src, size_t
             with_stages(raw, [&](auto st) {
                 constexpr int P = decltype(p)::value, ST = decltype(st)::value;
                 auto k_rows = wide ? k_raw_rows_rgb<P, SURF, true, ST> : k_raw_rows_rgb<P, SURF, false, ST>;
+                if constexpr ((ST & 1) != 0) {           // MIPI-packed samples: the packed form of the same kernel
+                    if (raw.pack == ma::PACK10) k_rows = wide ? k_mipi_rows_rgb<P, SURF, true, ST, ma::PACK10> : k_mipi_rows_rgb<P, SURF, false, ST, ma::PACK10>;
+                    else if (raw.pack == ma::PACK12) k_rows = wide ? k_mipi_rows_rgb<P, SURF, true, ST, ma::PACK12> : k_mipi_rows_rgb<P, SURF, false, ST, ma::PACK12>;
+                }
                 hipLaunchKernelGGL(k_rows, grid, block, raw_dynamic_lds(raw), s, src, rgb, rgb_stride, w, r0, h, raw);
             });
         });

@@ -882,6 +882,13 @@ static int check_bayer_size(int h, int w) {
     if (h < 4 || w < 4 || (h & 1) || (w & 1)) return fail(LT_ERR_INVALID, "raw Bayer frames need an even width and height of at least 4, got %dx%d", w, h);
     return LT_OK;
 }
+// ... of `layout`: MIPI-packed RAW10 holds four sites in five bytes, so a row is whole groups
+static int check_raw_size(int layout, int h, int w) {
+    const int rc = check_bayer_size(h, w);
+    if (rc) return rc;
+    if (raw_packing(layout) == 0 && (w & 3)) return fail(LT_ERR_INVALID, "MIPI-packed RAW10 frames need a width that is a multiple of 4, got %dx%d", w, h);
+    return LT_OK;
+}
 // The rows of a slot's staging frame that the lt_upload_frame_rows family brings for the path's camera rows [cam_r0, cam_r1): those
 // rows themselves, or -- raw Bayer -- the rows that their taps' windows touch (bayer_arith.h: input_run).
 static void staged_run(const lt_ctx* c, int* r0, int* r1) {
@@ -950,7 +957,11 @@ int lt_set_input_format(lt_ctx* c, int layout, const int32_t* coeffs) {
     int rc;
     const bool plain = layout == LT_INPUT_RGB || is_rgb_family(layout) || is_raw_mosaic(layout);      // no coefficients: `coeffs` is not read
     if (is_raw_mosaic(layout)) {
-        if ((rc = check_bayer_size(c->calib.img_h, c->calib.img_w))) return rc;
+        if ((rc = check_raw_size(layout, c->calib.img_h, c->calib.img_w))) return rc;
+        // A packed row's bytes follow from the frame's width, so these layouts cannot name frames of another size at all: with an input size
+        // they are a bad argument, as a layout number that does not exist is (the 16-bit layouts: LT_ERR_STATE, below)
+        if (raw_packing(layout) >= 0 && c->src_w > 0)
+            return fail(LT_ERR_INVALID, "MIPI-packed raw Bayer frames are not resized: a context with an input size (lt_set_input_size) takes RGB frames only");
     } else if (is_rgb_family(layout)) {
         // (the 8-byte window of a tap row starts at column min(x, W - 2): two pixels a row at the least)
         if (c->calib.img_w < 2) return fail(LT_ERR_INVALID, "BGR / RGBA / BGRA frames need a width of at least 2, got %dx%d", c->calib.img_w, c->calib.img_h);
@@ -968,10 +979,11 @@ int lt_set_input_format(lt_ctx* c, int layout, const int32_t* coeffs) {
     if (layout == LT_INPUT_RGB) {
         dev_free(c->d_yuv);
     } else {
-        // the staging frame of a slot: h w 3 / 2 bytes (4:2:0), h w 2 (4:2:2), h w 3 (BGR), h w 4 (RGBA / BGRA), h w (raw Bayer) or 2 h w (10- /
-        // 12-bit raw Bayer), slots a multiple of 16 apart
+        // the staging frame of a slot: h w 3 / 2 bytes (4:2:0), h w 2 (4:2:2), h w 3 (BGR), h w 4 (RGBA / BGRA), h w (raw Bayer), 2 h w (10- /
+        // 12-bit raw Bayer) or 5 h w / 4, 3 h w / 2 (the same MIPI-packed), slots a multiple of 16 apart
         if (is_bayer_wide(layout) && (rc = install_wide_table(c, layout))) return rc;     // (before anything of the context changes)
-        const size_t bytes = packed_bpp(layout) ? c->frame_bytes / 3 * (size_t)packed_bpp(layout) : c->frame_bytes / 2, stride = (bytes + 15) & ~(size_t)15;
+        const size_t row = (size_t)one_plane_row_bytes(layout, c->calib.img_w);
+        const size_t bytes = row ? (size_t)c->calib.img_h * row : c->frame_bytes / 2, stride = (bytes + 15) & ~(size_t)15;
         if (stride != c->yuv_stride) dev_free(c->d_yuv);
         c->yuv_bytes = bytes;
         c->yuv_stride = stride;
@@ -1180,8 +1192,8 @@ static int yuv_copy(lt_ctx* c, const uint8_t* frames, int first, int n, int r0, 
         return (int)LT_OK;
     };
     int rc = LT_OK;
-    if (const size_t bpp = (size_t)packed_bpp(c->in_layout))   // one plane of 2 W (4:2:2), 3 W (BGR) or 4 W (RGBA / BGRA) bytes a row: its rows [r0, r1); no chroma rows
-        return r1 > r0 ? piece((size_t)r0 * bpp * W, (size_t)(r1 - r0) * bpp * W) : rc;
+    if (const size_t row = (size_t)one_plane_row_bytes(c->in_layout, c->calib.img_w))   // one plane of 2 W (4:2:2), 3 W (BGR), 4 W (RGBA / BGRA) ... bytes a row: its rows [r0, r1); no chroma rows
+        return r1 > r0 ? piece((size_t)r0 * row, (size_t)(r1 - r0) * row) : rc;
     if (r1 > r0 && c1 > c0 && r0 == 0 && r1 == c->calib.img_h && c0 == 0 && c1 == c->calib.img_h / 2) return piece(0, c->yuv_bytes);
     if (r1 > r0 && (rc = piece((size_t)r0 * W, (size_t)(r1 - r0) * W))) return rc;
     if (c1 <= c0) return rc;
@@ -1777,21 +1789,21 @@ extern "C" {
 namespace {
 int check_surfaces(lt_ctx* c, const lt_device_surface* s, int n, SurfEntry* out) {
     const int H = c->calib.img_h, W = c->calib.img_w, layout = c->in_layout;
-    const int row = packed_bpp(layout) ? packed_bpp(layout) * W : W, crow = layout == LT_INPUT_NV12 ? W : W / 2;
+    const int row = one_plane_row_bytes(layout, W) ? one_plane_row_bytes(layout, W) : W, crow = layout == LT_INPUT_NV12 ? W : W / 2;
     constexpr int PITCH_MAX = (1 << 23) - 1;             // the kernels multiply rows and pitches with 24-bit instructions
     KnownRange memo;
     for (int k = 0; k < n; ++k) {
         const lt_device_surface& f = s[k];
         if (f.pitch < row) return fail(LT_ERR_INVALID, "surface %d: pitch %d is below the row's %d bytes", k, (int)f.pitch, row);
         if (f.pitch > PITCH_MAX) return fail(LT_ERR_INVALID, "surface %d: pitch %d is too large", k, (int)f.pitch);
-        if (is_bayer_wide(layout) && (((uintptr_t)f.plane[0] | (uintptr_t)f.pitch) & 1))      // 16-bit words: read as such by the row conversion
+        if (is_bayer_wide(layout) && raw_packing(layout) < 0 && (((uintptr_t)f.plane[0] | (uintptr_t)f.pitch) & 1))      // 16-bit words: read as such by the row conversion
             return fail(LT_ERR_INVALID, "surface %d: a plane of 16-bit samples needs an even address and an even pitch, got %p and %d", k, f.plane[0], (int)f.pitch);
         const size_t ext = (size_t)f.pitch * (size_t)(H - 1) + (size_t)row;
         if (ext >= ((size_t)1 << 31) - 8) return fail(LT_ERR_INVALID, "surface %d: a plane of %zu bytes is too large", k, ext);
         int rc = check_plane(c->device, f.plane[0], ext, k, 0, memo);
         if (rc) return rc;
         out[k] = SurfEntry{{(uint64_t)(uintptr_t)f.plane[0], 0, 0}, f.pitch, 0};
-        if (packed_bpp(layout)) continue;                            // one plane; chroma_pitch is not read
+        if (one_plane_row_bytes(layout, W)) continue;                // one plane; chroma_pitch is not read
         if (f.chroma_pitch < crow) return fail(LT_ERR_INVALID, "surface %d: chroma pitch %d is below the row's %d bytes", k, (int)f.chroma_pitch, crow);
         if (f.chroma_pitch > PITCH_MAX) return fail(LT_ERR_INVALID, "surface %d: chroma pitch %d is too large", k, (int)f.chroma_pitch);
         const size_t cext = (size_t)f.chroma_pitch * (size_t)(H / 2 - 1) + (size_t)crow;
@@ -2938,6 +2950,7 @@ static int convert_once(lt_ctx* c, const OneShot& j, uint8_t* out_rgb) {
         if (j.mesh && (rc = expand_mesh(c->stream, j.mesh, j.mesh_w, j.mesh_h, j.layout, j.h, j.w, &d_gain.p))) return rc;
         raw.table = d_table.p;
         raw.bits = is_bayer_wide(j.layout) ? raw_bits(j.layout) : 8;
+        raw.pack = raw_packing(j.layout);
         raw.color = j.curve != nullptr;
         for (int i = 0; raw.color && i < 9; ++i) raw.cm.m[i] = j.ccm[i];
         raw.gains = d_gain.p;
@@ -2982,7 +2995,7 @@ int lt_bayer_to_rgb(lt_ctx* c, const uint8_t* frame, int h, int w, int layout, u
 // bilinear demosaic -- lt_bayer_to_rgb's twin
 int lt_raw16_to_rgb(lt_ctx* c, const uint16_t* frame, int h, int w, int layout, const uint8_t* lut, uint8_t* out_rgb) {
     if (!c || !frame || !out_rgb) return fail(LT_ERR_INVALID, "null argument");
-    if (!is_bayer_wide(layout)) return fail(LT_ERR_INVALID, "lt_raw16_to_rgb takes the 10- and 12-bit raw Bayer layouts (32 .. 35, 48 .. 51)");
+    if (!is_bayer_wide(layout) || raw_packing(layout) >= 0) return fail(LT_ERR_INVALID, "lt_raw16_to_rgb takes the 10- and 12-bit raw Bayer layouts (32 .. 35, 48 .. 51)");
     int rc = check_bayer_size(h, w);
     if (rc) return rc;
     if (h > 16384 || w > 16384) return fail(LT_ERR_INVALID, "bad image size (at most 16384 x 16384)");
@@ -2999,14 +3012,14 @@ static int raw_to_rgb(lt_ctx* c, const char* fn, const void* frame, int h, int w
     const bool wide = is_bayer_wide(layout);
     const size_t entries = wide ? (size_t)1 << raw_bits(layout) : 256;
     if (lut && lut_entries != entries) return fail(LT_ERR_INVALID, "the raw table of this layout has %zu entries per colour phase, got %zu", entries, lut_entries);
-    int rc = check_bayer_size(h, w);
+    int rc = check_raw_size(layout, h, w);
     if (rc) return rc;
     if (h > 16384 || w > 16384) return fail(LT_ERR_INVALID, "bad image size (at most 16384 x 16384)");
     if (mesh && (rc = check_shading(layout, mesh_w, mesh_h, black))) return rc;
     static const int16_t ident[9] = {1024, 0, 0, 0, 1024, 0, 0, 0, 1024};
     uint8_t line[256];
     for (int i = 0; i < 256; ++i) line[i] = curve ? curve[i] : (uint8_t)i;
-    const OneShot j = {"raw Bayer conversion", frame, (size_t)h * w * (wide ? 2 : 1), h, w, layout, YuvCoef{}, true, lut,
+    const OneShot j = {"raw Bayer conversion", frame, (size_t)h * (size_t)one_plane_row_bytes(layout, w), h, w, layout, YuvCoef{}, true, lut,
                        ccm ? ccm : ident, color ? line : nullptr, mesh, mesh_w, mesh_h, black};
     return convert_once(c, j, out_rgb);
 }

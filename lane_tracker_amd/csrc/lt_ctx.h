@@ -379,9 +379,13 @@ inline uint8_t* slot_frame(const lt_ctx* c, int s) { return c->d_frames + (size_
 inline bool is_rgb_family(int layout) { return layout == LT_INPUT_BGR || layout == LT_INPUT_RGBA || layout == LT_INPUT_BGRA; }
 // 8-bit raw Bayer (RGGB, GRBG, GBRG, BGGR): one plane of one byte a pixel, an input format only
 inline bool is_bayer(int layout) { return layout >= LT_INPUT_BAYER_RGGB && layout <= LT_INPUT_BAYER_BGGR; }
-// 10- / 12-bit raw Bayer (layouts 32 .. 35, 48 .. 51): one plane of one 16-bit word a pixel, always behind a table; its sample bits
+// 10- / 12-bit raw Bayer (layouts 32 .. 35, 48 .. 51: one plane of one 16-bit word a pixel; 36 .. 39, 52 .. 55: the same samples MIPI-packed),
+// always behind a table; its sample bits
 inline int raw_bits(int layout) { return raw_wide_bits(layout); }
 inline bool is_bayer_wide(int layout) { return raw_bits(layout) != 0; }
+// ... MIPI-packed (layouts 36 .. 39, 52 .. 55: one plane of bytes, five for four samples / three for two): the packing (mipi_arith.h: 0 RAW10,
+// 1 RAW12), -1 for every other layout.  Their bits are raw_bits' 10 / 12: what is about the table holds for them as it is
+inline int raw_packing(int layout) { return raw_pack(layout); }
 // any raw mosaic, whatever its samples: what is about the mosaic (sizes, row runs, input only) and not about bytes
 inline bool is_raw_mosaic(int layout) { return is_bayer(layout) || is_bayer_wide(layout); }
 // What the front end and the row conversion of `c` are launched with behind a raw table (lt_internal.h: RawStages) -- the one place that
@@ -393,6 +397,7 @@ inline RawStages raw_stages_of(const lt_ctx* c) {
     if (!is_raw_mosaic(c->in_layout)) return r;
     const bool wide = is_bayer_wide(c->in_layout);
     r.bits = wide ? raw_bits(c->in_layout) : 8;
+    r.pack = raw_packing(c->in_layout);
     r.table = c->raw_color_set ? c->d_raw_cc : wide ? c->d_raw_lut_wide : c->raw_lut_set || c->raw_shade_set ? c->d_raw_lut : nullptr;
     r.color = c->raw_color_set;
     for (int i = 0; i < 9; ++i) r.cm.m[i] = c->raw_ccm[i];
@@ -402,8 +407,11 @@ inline RawStages raw_stages_of(const lt_ctx* c) {
 }
 inline int packed_bpp(int layout) {
     return layout == LT_INPUT_RGB || layout == LT_INPUT_BGR ? 3 : layout == LT_INPUT_RGBA || layout == LT_INPUT_BGRA ? 4
-           : layout == LT_INPUT_YUY2 || layout == LT_INPUT_UYVY || is_bayer_wide(layout) ? 2 : is_bayer(layout) ? 1 : 0;
+           : layout == LT_INPUT_YUY2 || layout == LT_INPUT_UYVY || (is_bayer_wide(layout) && raw_packing(layout) < 0) ? 2 : is_bayer(layout) ? 1 : 0;
 }
+// the bytes of a row of w pixels of the layouts that are ONE plane (0 for 4:2:0): whole pixels, or packed 10- / 12-bit samples -- what every
+// place that sizes or checks a frame from its layout asks
+inline int one_plane_row_bytes(int layout, int w) { return raw_packing(layout) >= 0 ? raw_wide_row_bytes(layout, w) : packed_bpp(layout) * w; }
 inline uint8_t* slot_yuv(const lt_ctx* c, int s) { return c->d_yuv + (size_t)s * c->yuv_stride; }
 inline uint8_t* slot_src(const lt_ctx* c, int s) { return c->d_src + (size_t)s * c->src_stride; }
 inline YuvCoef yuv_coef_of(const lt_ctx* c) { return YuvCoef{c->yuv_coef[0], c->yuv_coef[1], c->yuv_coef[2], c->yuv_coef[3], c->yuv_coef[4]}; }

@@ -68,11 +68,14 @@ void launch_warp_split(hipStream_t s, const uint32_t* und, size_t und_px, int fi
 //          gain of every site, uint16[h][w] (Q12) and 16 bytes of padding (launch_shade_expand); blk: the pedestal of each colour phase
 struct RawColorMat { int32_t m[9]; };
 struct RawShadeBlack { int32_t b[4]; };
+//   pack   -1, or the packing of 10- / 12-bit samples (mipi_arith.h: 0 RAW10, five bytes for four sites; 1 RAW12, three bytes for two): the
+//          kernels' packed forms, k_mipi_walk_rows, k_mipi_rows_rgb<.., STAGES, PACK>
 struct RawStages {
     const uint32_t* table = nullptr;
     int bits = 8;
     bool color = false;
     RawColorMat cm = {};
+    int pack = -1;                           // (in what was padding: every other member lies where it lay)
     const uint16_t* gains = nullptr;
     RawShadeBlack blk = {};
 };
@@ -112,9 +115,13 @@ struct FrameSource {
 };
 // The 10- / 12-bit raw Bayer layouts (32 .. 35, 48 .. 51; pattern = layout & 3): the bits of a sample, 0 for every other layout.  Their frames
 // are one plane of 16-bit little-endian words and they are always launched with a table (RawStages).
-inline int raw_wide_bits(int layout) { return layout >= 32 && layout <= 35 ? 10 : layout >= 48 && layout <= 51 ? 12 : 0; }
+// Layouts 36 .. 39 / 52 .. 55 (bit 2 set) are the same samples MIPI-packed, one plane of bytes: raw_pack says which packing (mipi_arith.h), -1: none.
+inline int raw_wide_bits(int layout) { return layout >= 32 && layout <= 39 ? 10 : layout >= 48 && layout <= 55 ? 12 : 0; }
+inline int raw_pack(int layout) { return raw_wide_bits(layout) && (layout & 4) ? (layout >= 48 ? 1 : 0) : -1; }
+// the bytes of a row of w sites of a raw layout with 10- / 12-bit samples
+inline int raw_wide_row_bytes(int layout, int w) { return raw_pack(layout) == 0 ? w + (w >> 2) : raw_pack(layout) == 1 ? w + (w >> 1) : 2 * w; }
 // the undistorted rows of n frames (layout 0 = RGB, 1 = NV12, 2 = I420, 3 = YUY2, 4 = UYVY, 5 = BGR, 6 = RGBA, 7 = BGRA, 16 .. 19 = raw Bayer RGGB /
-// GRBG / GBRG / BGGR, 32 .. 35 / 48 .. 51 = the same at 10 / 12 bits, which need raw.table; `k` is read for the YUV layouts only: every tap
+// GRBG / GBRG / BGGR, 32 .. 35 / 48 .. 51 = the same at 10 / 12 bits, 36 .. 39 / 52 .. 55 = those MIPI-packed, which need raw.table; `k` is read for the YUV layouts only: every tap
 // converted, then the same blend); `und` is the base of the whole buffer, `first_slot` the absolute slot of frame 0 of the call
 // (k_undistort_rows<layout, source, false>; behind a raw table k_raw_walk_rows<pattern, source, false, stages>)
 void launch_undistort_rows(hipStream_t s, FrameSource src, int layout, YuvCoef k, const int16_t* uxy, const uint16_t* ufrac,

@@ -17,10 +17,10 @@ struct ByteRange { uintptr_t lo, hi; int surface, plane; };   // [lo, hi)
 
 // (rows, row bytes) of plane i of an h x w frame in `layout`
 inline void plane_geom(int layout, int h, int w, int i, int* rows, int* row_bytes) {
-    if (i == 0) { *rows = h; *row_bytes = packed_bpp(layout) ? packed_bpp(layout) * w : w; }   // (4:2:2, raw Bayer: an attached camera surface only)
+    if (i == 0) { *rows = h; *row_bytes = one_plane_row_bytes(layout, w) ? one_plane_row_bytes(layout, w) : w; }   // (4:2:2, raw Bayer: an attached camera surface only)
     else { *rows = h / 2; *row_bytes = layout == LT_INPUT_NV12 ? w : w / 2; }
 }
-inline int plane_count(int layout) { return packed_bpp(layout) ? 1 : layout + 1; }
+inline int plane_count(int layout) { return one_plane_row_bytes(layout, 4) ? 1 : layout + 1; }
 
 int check_format(int layout, int h, int w, const int32_t* coeffs) {
     if (layout != LT_INPUT_RGB && layout != LT_INPUT_NV12 && layout != LT_INPUT_I420 && !is_rgb_family(layout))

@@ -12,7 +12,8 @@ refuses what its runtime does not know.  No framework is imported here.
 import numpy as np
 
 from . import _native
-from ._native import BAYER_FORMATS, BAYER_WIDE_FORMATS, SURFACE_DTYPE, frame_dtype, frame_shape, pixel_format_id
+from ._native import (BAYER_FORMATS, BAYER_PACKED_FORMATS, BAYER_WIDE_FORMATS, RAW_FORMATS, SURFACE_DTYPE, frame_dtype, frame_shape, packed_row_bytes,
+                      pixel_format_id, raw_bits)
 
 __all__ = ["DeviceBuffer", "DeviceFrames", "pack_host_frames", "feed_rows_list", "feed_rest_list"]
 
@@ -81,6 +82,8 @@ def _plane_rows(img_size, pixel_format):
     w, h = int(img_size[0]), int(img_size[1])
     layout = pixel_format_id(pixel_format)
     frame_shape((w, h), pixel_format)                    # (ValueError for odd 4:2:0 sizes)
+    if pixel_format in BAYER_PACKED_FORMATS:             # one plane of MIPI-packed samples: 5 W / 4 or 3 W / 2 bytes a row
+        return (h, packed_row_bytes(pixel_format, w)), None, 1
     bpp = _PIXEL_BYTES.get(layout)
     if bpp:                                              # one plane of whole pixels: 3 W (RGB, BGR), 2 W (packed 4:2:2), 4 W (RGBA, BGRA) or W (raw Bayer) bytes a row
         return (h, bpp * w), None, 1
@@ -89,7 +92,17 @@ def _plane_rows(img_size, pixel_format):
 
 _PIXEL_BYTES = {0: 3, 3: 2, 4: 2, 5: 3, 6: 4, 7: 4, 16: 1, 17: 1, 18: 1, 19: 1}       # bytes a pixel of the layouts that are one plane of whole pixels
 _PIXEL_BYTES.update({v: 2 for v in BAYER_WIDE_FORMATS.values()})                       # (10- / 12-bit raw Bayer: one 16-bit word)
-_RAW_LAYOUTS = frozenset(BAYER_FORMATS.values()) | frozenset(BAYER_WIDE_FORMATS.values())
+_RAW_LAYOUTS = frozenset(RAW_FORMATS.values())
+
+
+def _packed_width(pixel_format, row_bytes):
+    """The width of a MIPI-packed row of `row_bytes` bytes (ValueError where that is no whole number of groups); any other format: the value itself."""
+    if pixel_format not in BAYER_PACKED_FORMATS:
+        return row_bytes
+    per, of = (5, 4) if raw_bits(pixel_format) == 10 else (3, 2)
+    if row_bytes % per:
+        raise ValueError("a MIPI-packed %r row is W * %d // %d bytes, W a multiple of %d: got %d bytes" % (pixel_format, per, of, of, row_bytes))
+    return row_bytes // per * of
 
 
 def _check_word_planes(pixel_format, planes, pitches):
@@ -165,7 +178,7 @@ def pack_host_frames(frames, pixel_format="rgb", pitch=None, chroma_pitch=None, 
     single = f.ndim == nd
     f = f[None] if single else f
     if last:
-        h, w = f.shape[1], f.shape[2]
+        h, w = f.shape[1], _packed_width(pixel_format, f.shape[2])
     else:
         if f.shape[1] % 3:
             raise ValueError("a 4:2:0 frame is a 2-D array of shape (H * 3 // 2, W) with H and W even, got %r" % (f.shape[1:],))
@@ -280,7 +293,7 @@ class DeviceFrames:
                 raise ValueError("4:2:2 frames are packed: a pixel stride of 2 and a sample stride of 1, got %r" % (strides[-2:],))
             pitch = strides[-3]
         elif last == 1:
-            h, w = shape[-2], shape[-1]
+            h, w = shape[-2], _packed_width(pixel_format, shape[-1])
             if word and strides[-1] != 2:
                 raise ValueError("a %r plane holds one 16-bit word per pixel: a pixel stride of 2, got %d" % (pixel_format, strides[-1]))
             if not word and strides[-1] != 1:
@@ -331,7 +344,7 @@ class DeviceFrames:
         out=)` and `utils.rgb_to_yuv` write into and `to_host()` reads back.  `fill`: a byte value the whole block is set to first
         (None: whatever the memory held)."""
         n = int(n)
-        if pixel_format in BAYER_FORMATS or pixel_format in BAYER_WIDE_FORMATS:
+        if pixel_format in RAW_FORMATS:
             raise ValueError("%r is an input format only: annotated frames go into 'rgb', 'bgr', 'rgba', 'bgra', 'nv12' or 'i420' surfaces" % (pixel_format,))
         if n < 0:
             raise ValueError("a sink holds zero or more frames, got %d" % n)

@@ -111,31 +111,92 @@ def bayer_to_rgb(frame, pattern='bayer_rggb', raw_lut=None):
 
     The 10- and 12-bit patterns ('bayer10_rggb', ..., 'bayer12_bggr') take uint16 frames -- the sample in the low 10 / 12 bits of each
     word, the bits above ignored -- and look every sample up in `raw_lut`, u8 (4, 2**bits), first (None: the default
-    `raw_lut(bits=...)`): the demosaic of `apply_raw_lut(frame, pattern, raw_lut)`.  `raw_lut` goes with these patterns only."""
+    `raw_lut(bits=...)`): the demosaic of `apply_raw_lut(frame, pattern, raw_lut)`.  `raw_lut` goes with these patterns only.
+
+    The MIPI-packed patterns ('bayer10p_rggb', ..., 'bayer12p_bggr') take u8 frames of packed rows, (H, W * 5 // 4) / (H, W * 3 // 2)
+    (`pack_raw`), and are otherwise the 10- / 12-bit patterns: unpacked on the device, on the way into the table."""
     from . import _native
     from .lane_tracker import _context_for_module_functions
-    wide = pattern in _native.BAYER_WIDE_FORMATS
-    if pattern not in _native.BAYER_FORMATS and not wide:
-        raise ValueError("pattern must be one of %s, got %r" % (", ".join(repr(n) for n in list(_native.BAYER_FORMATS) + list(_native.BAYER_WIDE_FORMATS)), pattern))
+    wide = pattern in _native.BAYER_DEEP_FORMATS
+    if pattern not in _native.RAW_FORMATS:
+        raise ValueError("pattern must be one of %s, got %r" % (", ".join(repr(n) for n in _native.RAW_FORMATS), pattern))
     if raw_lut is not None and not wide:
         raise ValueError("bayer_to_rgb takes a raw_lut with the 10- and 12-bit patterns only (8-bit: apply_raw_lut first)")
     raw_lut = _native.checked_raw_lut(raw_lut, pattern)
     a = _native.frames_array(frame, pattern)
+    if a.ndim in (2, 3):                                 # (a size no raw frame has: refused before a context is made)
+        _native.raw_frame_size(np.empty(a.shape[-2:], a.dtype), pattern)
     convert = (lambda ctx, f: ctx.bayer_to_rgb(f, pattern, raw_lut)) if wide else (lambda ctx, f: ctx.bayer_to_rgb(f, pattern))
     if a.ndim == 2:
         return convert(_context_for_module_functions(), a)
     if a.ndim != 3:
         raise ValueError("a raw Bayer frame is an array (H, W), a stack of them (n, H, W); got %r" % (a.shape,))
     ctx = _context_for_module_functions()
-    out = np.empty(a.shape + (3,), np.uint8)
-    for k in range(a.shape[0]):
-        out[k] = convert(ctx, a[k])
-    return out
+    if a.shape[0] == 0:
+        return np.empty((0,) + _native.raw_frame_size(np.empty(a.shape[1:], a.dtype), pattern) + (3,), np.uint8)
+    return np.stack([convert(ctx, a[k]) for k in range(a.shape[0])])
 
 
 _BAYER_PATTERNS = ('bayer_rggb', 'bayer_grbg', 'bayer_gbrg', 'bayer_bggr')     # pattern p: its red sites at (row, column) parity (p >> 1, p & 1)
 # the 10- and 12-bit forms: name -> (pattern p, bits)
 _BAYER_WIDE_PATTERNS = {'bayer%d_%s' % (b, n[6:]): (p, b) for b in (10, 12) for p, n in enumerate(_BAYER_PATTERNS)}
+
+
+# the same MIPI-packed: name -> (pattern p, bits)
+_BAYER_PACKED_PATTERNS = {'bayer%dp_%s' % (b, n[6:]): (p, b) for b in (10, 12) for p, n in enumerate(_BAYER_PATTERNS)}
+
+
+def _packed_bits(fmt):
+    """The sample bits of a packed raw layout given as a name ('bayer10p_rggb', or '10p' / '12p' alone) or as 10 / 12."""
+    if fmt in _BAYER_PACKED_PATTERNS:
+        return _BAYER_PACKED_PATTERNS[fmt][1]
+    if fmt in (10, 12, '10p', '12p'):
+        return int(str(fmt)[:2])
+    raise ValueError("fmt must be one of %s (or '10p' / '12p'), got %r" % (", ".join(repr(n) for n in _BAYER_PACKED_PATTERNS), fmt))
+
+
+def pack_raw(frames, fmt):
+    """10- / 12-bit raw Bayer frames in words -- uint16 (H, W) or a stack (n, H, W), every sample below 2**bits -- as MIPI packs them
+    (CSI-2 RAW10 / RAW12; V4L2 SRGGB10P / SRGGB12P and siblings): u8 (..., H, W * 5 // 4) or (..., H, W * 3 // 2).
+
+        RAW10 (W % 4 == 0): group g holds sites 4g .. 4g + 3; byte 5g + i is s[4g + i] >> 2 (i = 0 .. 3), bits 2i + 1 : 2i of byte
+                            5g + 4 are s[4g + i] & 3
+        RAW12 (W even):     byte 3g is s[2g] >> 4, byte 3g + 1 is s[2g + 1] >> 4, byte 3g + 2 is (s[2g] & 15) | (s[2g + 1] & 15) << 4
+
+    `fmt`: a packed pixel format ('bayer10p_rggb', ...; the pattern plays no part) or '10p' / '12p'.  NumPy only."""
+    bits = _packed_bits(fmt)
+    a = np.asarray(frames)
+    if a.dtype != np.uint16 or a.ndim not in (2, 3):
+        raise ValueError("frames to pack are uint16 arrays (H, W) or (n, H, W), got %s %r" % (a.dtype, a.shape))
+    per = 4 if bits == 10 else 2
+    if a.shape[-1] % per or a.shape[-1] == 0:
+        raise ValueError("RAW%d packs %d samples at a time: the width must be a multiple of %d, got %d" % (bits, per, per, a.shape[-1]))
+    if a.size and int(a.max()) >> bits:
+        raise ValueError("a %d-bit sample is below %d, got %d" % (bits, 1 << bits, int(a.max())))
+    g = a.reshape(a.shape[:-1] + (a.shape[-1] // per, per))
+    out = np.empty(g.shape[:-1] + (per + 1,), np.uint8)
+    out[..., :per] = g >> (bits - 8)
+    low = g & ((1 << (bits - 8)) - 1)
+    out[..., per] = sum(low[..., i] << ((bits - 8) * i) for i in range(per))
+    return out.reshape(a.shape[:-1] + (-1,))
+
+
+def unpack_raw(frames, fmt):
+    """The inverse of `pack_raw`, and the DEFINITION of the packed layouts: u8 packed rows (H, W * 5 // 4) / (H, W * 3 // 2), or a stack of
+    them, -> uint16 (..., H, W).  A tracker or group in 'bayer10p_P' / 'bayer12p_P' fed packed frames F computes, bit for bit, what the one in
+    'bayer10_P' / 'bayer12_P' with the same table, colour stage and shading map computes from `unpack_raw(F, fmt)`.  NumPy only."""
+    bits = _packed_bits(fmt)
+    a = np.asarray(frames)
+    if a.dtype != np.uint8 or a.ndim not in (2, 3):
+        raise ValueError("packed frames are uint8 arrays (H, row bytes) or (n, H, row bytes), got %s %r" % (a.dtype, a.shape))
+    per = 4 if bits == 10 else 2
+    if a.shape[-1] % (per + 1) or a.shape[-1] == 0:
+        raise ValueError("a RAW%d row is a multiple of %d bytes, got %d" % (bits, per + 1, a.shape[-1]))
+    g = a.reshape(a.shape[:-1] + (a.shape[-1] // (per + 1), per + 1)).astype(np.uint16)
+    out = np.empty(g.shape[:-1] + (per,), np.uint16)
+    for i in range(per):
+        out[..., i] = (g[..., i] << (bits - 8)) | ((g[..., per] >> ((bits - 8) * i)) & ((1 << (bits - 8)) - 1))
+    return out.reshape(a.shape[:-1] + (-1,))
 
 
 def checked_raw_lut(lut, bits=8):
@@ -195,7 +256,11 @@ def apply_raw_lut(frames, pattern, lut):
 
     The 10- and 12-bit patterns ('bayer10_rggb', ..., 'bayer12_bggr'): uint16 frames, a table u8 (4, 2**bits), and
     out[y, x] = lut[phase(y, x)][frames[y, x] & (2**bits - 1)], a uint8 mosaic -- the bits of a word above `bits` are ignored.  A tracker in
-    'bayerNN_P' with table `lut` computes what the 8-bit 'bayer_P' tracker without a table computes from this."""
+    'bayerNN_P' with table `lut` computes what the 8-bit 'bayer_P' tracker without a table computes from this.
+
+    The MIPI-packed patterns ('bayer10p_*', 'bayer12p_*'): u8 packed rows, unpacked (`unpack_raw`) and then as the 10- / 12-bit patterns."""
+    if pattern in _BAYER_PACKED_PATTERNS:
+        return apply_raw_lut(unpack_raw(frames, pattern), pattern.replace("p_", "_", 1), lut)
     if pattern in _BAYER_WIDE_PATTERNS:
         p, bits = _BAYER_WIDE_PATTERNS[pattern]
         dtype = np.uint16
@@ -370,7 +435,7 @@ def raw_shading_plane(shading, pattern, img_size):
         G = ((256-a)*(256-b)*m[i][j] + a*(256-b)*m[i][j+1] + (256-a)*b*m[i+1][j] + a*b*m[i+1][j+1] + 32768) >> 16
 
     NumPy only.  This is the definition of what the device expands the mesh into."""
-    p, bits, _ = _pattern_bits(pattern)
+    p, bits, _ = _pattern_bits(pattern.replace("p_", "_", 1) if pattern in _BAYER_PACKED_PATTERNS else pattern)
     mesh, _black = checked_raw_shading(shading, bits)
     w, h = int(img_size[0]), int(img_size[1])
     if w < 2 or h < 2:
@@ -412,16 +477,16 @@ def apply_raw_shading(frames, pattern, shading):
 
 
 def bayer_to_rgb_color(frame, pattern, raw_lut=None, ccm=None, curve=None, shading=None):
-    """A raw Bayer frame (H, W) or a stack (n, H, W) in any of the twelve raw patterns -- u8 for 'bayer_*', uint16 for 'bayer10_*' /
-    'bayer12_*' -- to RGB with the colour stage, on the device: every sample looked up in `raw_lut` (8-bit: u8 (4, 256), None: no
+    """A raw Bayer frame (H, W) or a stack (n, H, W) in any of the raw patterns -- u8 for 'bayer_*', uint16 for 'bayer10_*' /
+    'bayer12_*', u8 packed rows (H, W * 5 // 4) / (H, W * 3 // 2) for 'bayer10p_*' / 'bayer12p_*' -- to RGB with the colour stage, on the device: every sample looked up in `raw_lut` (8-bit: u8 (4, 256), None: no
     table; 10 / 12 bits: u8 (4, 2**bits), None: the default), demosaiced, then `apply_raw_color(.., ccm, curve)`.  What a
     `LaneTracker(..., pixel_format=pattern, raw_lut=.., raw_ccm=.., raw_curve=..)` sees of the frame.  `shading`: a `utils.RawShading`
     applied to every sample first (`apply_raw_shading`), as `raw_shading=` of a tracker; with one and neither `ccm` nor `curve` there is
     no colour stage."""
     from . import _native
     from .lane_tracker import _context_for_module_functions
-    if pattern not in _native.BAYER_FORMATS and pattern not in _native.BAYER_WIDE_FORMATS:
-        raise ValueError("pattern must be one of %s, got %r" % (", ".join(repr(n) for n in list(_native.BAYER_FORMATS) + list(_native.BAYER_WIDE_FORMATS)), pattern))
+    if pattern not in _native.RAW_FORMATS:
+        raise ValueError("pattern must be one of %s, got %r" % (", ".join(repr(n) for n in _native.RAW_FORMATS), pattern))
     raw_lut = _native.checked_raw_lut(raw_lut, pattern)
     ccm = None if ccm is None else checked_raw_ccm(ccm)
     curve = None if curve is None else checked_raw_curve(curve)
@@ -429,15 +494,15 @@ def bayer_to_rgb_color(frame, pattern, raw_lut=None, ccm=None, curve=None, shadi
     a = _native.frames_array(frame, pattern)
     if a.ndim not in (2, 3):
         raise ValueError("a raw Bayer frame is an array (H, W), a stack of them (n, H, W); got %r" % (a.shape,))
+    _native.raw_frame_size(np.empty(a.shape[-2:], a.dtype), pattern)       # (a size no raw frame has: refused before a context is made)
     ctx = _context_for_module_functions()
     convert = (lambda f: ctx.raw_to_rgb_color(f, pattern, raw_lut, ccm, curve)) if shading is None else \
               (lambda f: ctx.raw_to_rgb_shaded(f, pattern, shading, raw_lut, ccm, curve))
     if a.ndim == 2:
         return convert(a)
-    out = np.empty(a.shape + (3,), np.uint8)
-    for k in range(a.shape[0]):
-        out[k] = convert(a[k])
-    return out
+    if a.shape[0] == 0:
+        return np.empty((0,) + _native.raw_frame_size(np.empty(a.shape[1:], a.dtype), pattern) + (3,), np.uint8)
+    return np.stack([convert(a[k]) for k in range(a.shape[0])])
 
 
 def rgb_to_yuv(frame, layout='nv12', matrix='bt601'):

@@ -62,6 +62,18 @@ _BAYER = ("bayer_rggb", "bayer_grbg", "bayer_gbrg", "bayer_bggr")
 _BAYER_WIDE = tuple("bayer%d_%s" % (b, n[6:]) for b in (10, 12) for n in _BAYER)
 
 
+# the same MIPI-packed (CSI-2 RAW10 / RAW12): headerless `.bayer10p` / `.bayer12p` files of packed rows, 5 W / 4 or 3 W / 2 bytes each; the
+# suffix names the depth, the caller the pattern -- and a depth that agrees
+_BAYER_PACKED = tuple("bayer%dp_%s" % (b, n[6:]) for b in (10, 12) for n in _BAYER)
+_RAW_ALL = _BAYER + _BAYER_WIDE + _BAYER_PACKED
+
+
+def _packed_file_bits(path):
+    """10 / 12 for a `.bayer10p` / `.bayer12p` file, 0 for any other."""
+    p = str(path).lower()
+    return 10 if p.endswith(".bayer10p") else 12 if p.endswith(".bayer12p") else 0
+
+
 def _is_bayer_file(path):
     return str(path).lower().endswith(".bayer")
 
@@ -80,9 +92,13 @@ def _yuv_tail(pixel_format, width, height):
         if width < 2 or height < 1:
             raise ValueError(f"{pixel_format} frames need a width of at least 2, got {width}x{height}")
         return (height, width, 3 if pixel_format == "bgr" else 4), pixel_format.upper()
-    if pixel_format in _BAYER or pixel_format in _BAYER_WIDE:
+    if pixel_format in _RAW_ALL:
         if width % 2 or height % 2 or width < 4 or height < 4:
             raise ValueError(f"raw Bayer frames need an even width and height of at least 4, got {width}x{height}")
+        if pixel_format in _BAYER_PACKED:
+            if pixel_format.startswith("bayer10p") and width % 4:
+                raise ValueError(f"MIPI-packed RAW10 frames need a width that is a multiple of 4, got {width}x{height}")
+            return (height, width * 5 // 4 if pixel_format.startswith("bayer10p") else width * 3 // 2), "MIPI-packed raw Bayer"
         return (height, width), "raw Bayer"
     if pixel_format in ("yuy2", "uyvy"):
         if width % 2 or width < 4 or height < 1:
@@ -124,6 +140,8 @@ class FrameSource:
             raise ValueError(f"pixel_format={pixel_format!r} names the pattern of a raw .bayer file; {self.path!r} is none")
         if pixel_format in _BAYER_WIDE and not _is_bayer16_file(self.path):
             raise ValueError(f"pixel_format={pixel_format!r} names depth and pattern of a raw .bayer16 file; {self.path!r} is none")
+        if pixel_format in _BAYER_PACKED and _packed_file_bits(self.path) != _raw_format_bits(pixel_format):
+            raise ValueError(f"pixel_format={pixel_format!r} names the pattern of a raw .bayer{_raw_format_bits(pixel_format)}p file; {self.path!r} is none")
         self._dtype = np.dtype(np.uint8)
         self._files = None
         self._array = None
@@ -156,6 +174,23 @@ class FrameSource:
             if pixel_format not in _BAYER:
                 raise ValueError(f"{self.path}: a .bayer file holds raw Bayer frames and its suffix cannot name the pattern: say which with "
                                  "--pixel-format bayer_rggb / bayer_grbg / bayer_gbrg / bayer_bggr (FrameSource's pixel_format=)")
+            if size is None:
+                raise ValueError("raw Bayer input needs size=(width, height)")
+            self.pixel_format = pixel_format
+            self.width, self.height = int(size[0]), int(size[1])
+            self._tail, family = _yuv_tail(self.pixel_format, self.width, self.height)
+            fb = int(np.prod(self._tail))
+            nbytes = os.path.getsize(self.path)
+            if nbytes % fb:
+                raise ValueError(f"{self.path}: {nbytes} bytes is not a whole number of {self.width}x{self.height} {family} frames")
+            self._n = nbytes // fb
+            self._array = np.memmap(self.path, np.uint8, "r", shape=(self._n,) + self._tail) if self._n \
+                else np.zeros((0,) + self._tail, np.uint8)
+        elif _packed_file_bits(self.path):
+            bits = _packed_file_bits(self.path)
+            if pixel_format not in _BAYER_PACKED or _raw_format_bits(pixel_format) != bits:
+                raise ValueError(f"{self.path}: a .bayer{bits}p file holds MIPI-packed RAW{bits} frames and its suffix cannot name the pattern: say which "
+                                 f"with --pixel-format bayer{bits}p_rggb / _grbg / _gbrg / _bggr (FrameSource's pixel_format=)")
             if size is None:
                 raise ValueError("raw Bayer input needs size=(width, height)")
             self.pixel_format = pixel_format
@@ -201,7 +236,7 @@ class FrameSource:
             self._array = np.memmap(self.path, np.uint8, "r", shape=(self._n,) + self._tail) if self._n \
                 else np.zeros((0,) + self._tail, np.uint8)
         else:
-            raise ValueError(f"unsupported frame source {self.path!r} (directory of images, .npy, .rgb/.raw, .bgr, .rgba, .bgra, .nv12, .i420/.yuv, .yuy2, .uyvy, .bayer, .bayer16)")
+            raise ValueError(f"unsupported frame source {self.path!r} (directory of images, .npy, .rgb/.raw, .bgr, .rgba, .bgra, .nv12, .i420/.yuv, .yuy2, .uyvy, .bayer, .bayer16, .bayer10p, .bayer12p)")
         if self._tail is None:
             self._tail = (self.height, self.width, 3)
         if size is not None and (self.width, self.height) != (int(size[0]), int(size[1])):
@@ -428,10 +463,11 @@ def main(argv=None):
                     help="WxH of the input frames when that is not the calibration's size: raw RGB input is read in this size and the "
                          "tracker resizes the frames on the device (cv2.resize, INTER_LINEAR); what is written has the calibration's size")
     ap.add_argument("--window", type=int, default=64, help="frames per GPU batch")
-    ap.add_argument("--pixel-format", choices=("rgb", "nv12", "i420", "yuy2", "uyvy") + _RGB_FAMILY + _BAYER + _BAYER_WIDE, default=None,
+    ap.add_argument("--pixel-format", choices=("rgb", "nv12", "i420", "yuy2", "uyvy") + _RGB_FAMILY + _RAW_ALL, default=None,
                     help="pixel format of the input frames (default: by the input's name); must match a raw input's extension; a raw "
                          ".bayer input needs it: bayer_rggb / bayer_grbg / bayer_gbrg / bayer_bggr, the sensor's pattern; a raw .bayer16 input (10- / 12-bit samples in "
-                         "little-endian 16-bit words) needs depth and pattern: bayer10_rggb ... bayer12_bggr")
+                         "little-endian 16-bit words) needs depth and pattern: bayer10_rggb ... bayer12_bggr; a raw .bayer10p / .bayer12p input (MIPI-packed rows) "
+                         "needs the pattern, with the suffix's depth: bayer10p_rggb ... / bayer12p_rggb ...")
     ap.add_argument("--yuv-matrix", choices=("bt601", "bt709"), default="bt601", help="conversion matrix of 4:2:0 / 4:2:2 input")
     ap.add_argument("--raw-black-level", type=float, default=None, metavar="N", help="raw Bayer input: the sensor's black pedestal, in sample values (default 0)")
     ap.add_argument("--raw-white-level", type=float, default=None, metavar="N", help="raw Bayer input: the sample value of full scale (default 255; 1023 / 4095 for 10- / 12-bit input)")
@@ -462,7 +498,7 @@ def main(argv=None):
     a = ap.parse_args(argv)
     raw = {k: v for k, v in (("black_level", a.raw_black_level), ("white_level", a.raw_white_level), ("gains", a.raw_gains),
                              ("gamma", a.raw_gamma)) if v is not None}
-    if raw and a.pixel_format not in _BAYER + _BAYER_WIDE:
+    if raw and a.pixel_format not in _RAW_ALL:
         ap.error("--raw-black-level / --raw-white-level / --raw-gains / --raw-gamma condition raw Bayer samples: they need --pixel-format bayer_*")
     raw_table = None
     if raw:
@@ -471,7 +507,7 @@ def main(argv=None):
             raw_table = raw_lut(**raw) if a.pixel_format in _BAYER else raw_lut(bits=_raw_format_bits(a.pixel_format), **raw)
         except ValueError as e:
             ap.error(str(e))
-    if (a.raw_ccm is not None or a.raw_out_gamma is not None) and a.pixel_format not in _BAYER + _BAYER_WIDE:
+    if (a.raw_ccm is not None or a.raw_out_gamma is not None) and a.pixel_format not in _RAW_ALL:
         ap.error("--raw-ccm / --raw-out-gamma follow the demosaic of raw Bayer frames: they need --pixel-format bayer_*")
     raw_matrix = raw_out_curve = None
     try:
@@ -485,7 +521,7 @@ def main(argv=None):
         ap.error(str(e))
     raw_shade = None
     if a.raw_shading is not None:
-        if a.pixel_format not in _BAYER + _BAYER_WIDE:
+        if a.pixel_format not in _RAW_ALL:
             ap.error("--raw-shading corrects raw Bayer samples: it needs --pixel-format bayer_*")
         import numpy as np
         from .utils import raw_shading
@@ -510,9 +546,9 @@ def main(argv=None):
     if a.input_size is not None and a.size is not None and tuple(a.size) != tuple(a.input_size):
         ap.error("--size %dx%d and --input-size %dx%d name two sizes for the input frames" % (tuple(a.size) + tuple(a.input_size)))
     try:
-        src = FrameSource(a.input, a.input_size or a.size or image_wh, pixel_format=a.pixel_format if a.pixel_format in _BAYER + _BAYER_WIDE else None)
+        src = FrameSource(a.input, a.input_size or a.size or image_wh, pixel_format=a.pixel_format if a.pixel_format in _RAW_ALL else None)
     except ValueError as e:
-        if not (_is_bayer_file(a.input) or _is_bayer16_file(a.input) or a.pixel_format in _BAYER + _BAYER_WIDE):
+        if not (_is_bayer_file(a.input) or _is_bayer16_file(a.input) or _packed_file_bits(a.input) or a.pixel_format in _RAW_ALL):
             raise
         ap.error(str(e))
     if a.pixel_format is not None and a.pixel_format != src.pixel_format:
