@@ -67,7 +67,8 @@ extern "C" {
  *    colour phase on their way into the 8-bit demosaic); lt_set_raw_color + lt_get_raw_color + lt_raw_to_rgb_color (the colour stage of raw
  *    Bayer input: a colour-correction matrix and an output curve on every demosaiced pixel, on the device); lt_set_raw_shading +
  *    lt_get_raw_shading + lt_get_raw_shading_plane + lt_raw_to_rgb_shaded (lens-shading correction of raw Bayer input from a gain mesh, on
- *    every sample in front of the raw table, on the device).  Nothing removed or changed. */
+ *    every sample in front of the raw table, on the device); lt_upload_mask_bits + lt_last_search_source (caller-supplied masks as
+ *    bit planes, searched by the bit-plane kernels).  Nothing removed or changed. */
 #define LT_ABI_VERSION 5
 
 typedef enum lt_status {
@@ -515,6 +516,13 @@ int  lt_device_read(void* dst_host, const void* src_device, size_t bytes);
 int  lt_device_stream_wait(int device, uintptr_t stream);
 /* masks: n * warp_h * warp_w bytes; lets the search stages run on caller-supplied binary images */
 int  lt_upload_masks(lt_ctx* ctx, const uint8_t* masks, int first_slot, int n);
+/* The same as bit planes, an eighth of the bytes: n * warp_h * wpr 64-bit words, wpr = (warp_w + 63) / 64, dense; pixel x of a row is
+ * bit x % 64 of the row's word x / 64, least significant bit first.  A set bit is a mask byte != 0: lt_download_masks gives 255
+ * for it.  Bits at columns >= warp_w need not be zero: the library clears them on the way in.  Slots filled this way are searched
+ * by the bit-plane kernels wherever those take the geometry (as behind lt_mask_run; lt_last_search_source tells), slots filled by
+ * lt_upload_masks by the u8 kernels.  The u8 kernels sum byte values where the bit-plane kernels count pixels; the sums are only
+ * compared and maximised, so both give the same lane pixels, centroids and fits for every mask whose non-zero bytes are all equal. */
+int  lt_upload_mask_bits(lt_ctx* ctx, const uint64_t* bits, int first_slot, int n);
 int  lt_download_masks(lt_ctx* ctx, int first_slot, int n, uint8_t* masks);
 int  lt_download_plane(lt_ctx* ctx, int plane, int first_slot, int n, uint8_t* out);
 /* the undistorted camera rows [src_row0, src_row1) as RGB interleaved: n * rows * img_w * 3 */
@@ -555,7 +563,9 @@ int  lt_filter_run(lt_ctx* ctx, int first_slot, int n, const lt_filter_params* p
  * Size limits, refused with LT_ERR_INVALID before anything is launched: a search that only the first-formulation kernels take
  * keeps its row counters in LDS, 150 KB at most -- a band search with bandwidth > 31 (a band wider than 64 columns), a width that
  * is no multiple of 4 or more than 4795 band rows, and any band search on an image taller than 8192 rows: at most 9590 image rows;
- * a sliding-window search outside k_sws_fit2's geometry: 16 * window_height + 8 * width bytes. */
+ * a sliding-window search outside k_sws_fit2's geometry: 16 * window_height + 8 * width bytes.  Likewise a sliding window wider
+ * than the image (2 * int(window_width / 2) > warp_w): the reference's window slice then wraps round the image edge and yields
+ * negative columns. */
 /* sliding_window_search() + fit_poly() (:242-447, :502-509) on the slots' masks */
 int  lt_sws_fit_run(lt_ctx* ctx, int first_slot, int n, const lt_search_params* p);
 /* band_search() + fit_poly() (:449-509); prev_coeffs: n * 6 doubles (last_left_coeffs, last_right_coeffs) */
@@ -1041,6 +1051,12 @@ int  lt_tophat_split_form(int h, int w, int k, int nbands);
 /* The same for the last 'neighborhood' call (cv2.adaptiveThreshold, lane_tracker.py:217-218): 1 = running box sums
  * (odd windows up to 63, width a multiple of 4, no greenery mask), 0 = the per-pixel window kernel, -1 = none yet. */
 int  lt_last_adaptive_path(lt_ctx* ctx);
+/* What the kernels of the context's last lt_sws_fit_run, lt_band_fit_run, lt_band_fit_chain_run or lt_search_fit_list read: 1 = the
+ * bit planes of every slot searched, 0 = the u8 mask of at least one (a slot filled by lt_upload_masks, a geometry the bit-plane
+ * kernels do not take -- a window or band wider than 64 columns, ... -- or a
+ * list whose slots are not all bit planes), -1 = none yet; a refused call or one over no slots does not change it; LT_NO_CONTEXT
+ * for a null context.  Both give identical results (above); tests use this to know which kernels they have exercised. */
+int  lt_last_search_source(lt_ctx* ctx);
 /* The lane-drawing kernel launches the most recent lt_overlay_run, lt_overlay_run_rows, lt_overlay_run_inplace,
  * lt_overlay_run_inplace_coeffs or lt_overlay_run_to_surfaces of the context enqueued (text and store launches are not counted):
  * 1 for a range of up to 64 slots (32 for lt_overlay_run_to_surfaces) whatever the slots' calibration sets -- a range that mixes

@@ -114,6 +114,7 @@ _SIGNATURES = {
     "lt_upload_frame_rest": (C.c_int, [_P, _P, C.c_int, C.c_int]),
     "lt_upload_frame_rest_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, _P]),
     "lt_upload_masks": (C.c_int, [_P, _P, C.c_int, C.c_int]),
+    "lt_upload_mask_bits": (C.c_int, [_P, _P, C.c_int, C.c_int]),
     "lt_download_masks": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "lt_download_plane": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, _P]),
     "lt_download_undistorted": (C.c_int, [_P, C.c_int, C.c_int, _P]),
@@ -226,6 +227,7 @@ _SIGNATURES = {
     "lt_last_threshold_path": (C.c_int, [_P]),
     "lt_last_threshold_form": (C.c_int, [_P]),
     "lt_last_tophat_path": (C.c_int, [_P]),
+    "lt_last_search_source": (C.c_int, [_P]),
     "lt_tophat_split_form": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "lt_last_adaptive_path": (C.c_int, [_P]),
     "lt_set_input_format": (C.c_int, [_P, C.c_int, _P]),
@@ -1282,6 +1284,15 @@ class Context:
         _check(self.lib.lt_upload_masks(self._h, m.ctypes.data, first, m.shape[0]))
         return m.shape[0]
 
+    def upload_mask_bits(self, masks, first=0):
+        """u8 or bool masks (n, warp_h, warp_w), a pixel set where != 0, uploaded as bit planes (lt_upload_mask_bits): the
+        searches over these slots take the bit-plane kernels."""
+        from .utils import pack_mask_bits
+        m = np.asarray(masks).reshape(-1, self.warp_h, self.warp_w)
+        bits = np.ascontiguousarray(pack_mask_bits(m))
+        _check(self.lib.lt_upload_mask_bits(self._h, bits.ctypes.data, first, m.shape[0]))
+        return m.shape[0]
+
     def upload_bev(self, bev, first=0):
         b = _u8(bev).reshape(-1, self.warp_h, self.warp_w, 3)
         _check(self.lib.lt_upload_bev(self._h, b.ctypes.data, first, b.shape[0]))
@@ -1843,6 +1854,10 @@ class Context:
     def last_tophat_path(self):
         """Batch top-hat walks of the last mask chain: bit 0 = 29x29, bit 1 = 55x55 ran the split-band form; 0 = neither, -1 = none yet."""
         return int(self.lib.lt_last_tophat_path(self._h))
+
+    def last_search_source(self):
+        """What the last search call read: 1 = bit planes only, 0 = the u8 mask of at least one slot, -1 = no search yet."""
+        return int(self.lib.lt_last_search_source(self._h))
 
     def last_adaptive_path(self):
         """'neighborhood' calls: 1 = running box sums, 0 = per-pixel windows, -1 = none yet."""

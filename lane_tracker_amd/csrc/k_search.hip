@@ -268,7 +268,7 @@ __global__ __launch_bounds__(BSB_NT) void k_band_sums_bits(MaskBits mb, SearchGe
     uint32_t* out = sums + ((size_t)frame * g.nbands + band) * g.w;
     constexpr int NW = BSB_NT / 64;
     const int wpr = mb.wpr, jpw = (wpr + NW - 1) / NW;     // words per row; words handled by each wave
-    uint32_t acc[4];                                       // jpw <= 4 (w <= 4096)
+    uint32_t acc[4];                                       // jpw <= 4 (w <= 4096: sws_fit_takes_bits)
 #pragma unroll
     for (int q = 0; q < 4; ++q) acc[q] = 0;
     for (int c0 = r0; c0 < r1; c0 += BSB_ROWS) {
@@ -1653,7 +1653,11 @@ bool search_launchable(const SearchGeom& g, bool band, size_t mask_stride) {
     return lds <= 48 * 1024 || (lds <= 150 * 1024 && first_big_lds());
 }
 
-bool sws_fit_takes_bits(const SearchGeom& g, size_t mask_stride) { return sws2_eligible(g, mask_stride) && !env_flag("LT_SEARCH_U8"); }
+// (k_band_sums_bits sums at most four words of a row per wave: a plane wider than 64 words would be searched from the u8 mask.
+// lt_create refuses a bird's-eye width above 4096 today, so this holds the kernel's own limit should that one ever move.)
+bool sws_fit_takes_bits(const SearchGeom& g, size_t mask_stride) {
+    return sws2_eligible(g, mask_stride) && g.w <= 64 * 4 * (BSB_NT / 64) && !env_flag("LT_SEARCH_U8");
+}
 bool band_fit_takes_bits(const SearchGeom& g, size_t mask_stride) { return band2_eligible(g, mask_stride) && !env_flag("LT_SEARCH_U8"); }
 
 void launch_sws_fit(hipStream_t s, const uint8_t* masks, size_t mask_stride, MaskBits mb, SearchGeom g, uint32_t* band_sums,

@@ -376,8 +376,11 @@ int make_search_geom(lt_ctx* c, const lt_search_params* p, bool band, SearchGeom
         g.band_top = (int)((double)h * (1.0 - p->partial));                   // :466 (2017 NumPy: int())
         if (g.band_top < 0) g.band_top = 0;
         const long long per_row = std::min<long long>(w, 2LL * p->bandwidth + 2);
-        long long need = (long long)std::max(g.band_bottom - g.band_top, 0) * per_row;
+        const int nrows = std::max(g.band_bottom - g.band_top, 0);
+        long long need = (long long)nrows * per_row;
         g.maxpix = (int)std::min<long long>(std::max<long long>(need, 64), (long long)h * w);
+        // (room for k_band_fit2's block whatever the bandwidth: which kernel runs must not depend on the searches before this one)
+        g.maxpix = (int)std::max<long long>(g.maxpix, band2_block_words(nrows));
         g.maxlev = 1;
         return LT_OK;
     }
@@ -387,6 +390,10 @@ int make_search_geom(lt_ctx* c, const lt_search_params* p, bool band, SearchGeom
     g.ww = p->window_width;
     g.wh = p->window_height;
     g.hw = (int)(p->window_width / 2.0);                                      // int(window_width/2)
+    // A window whose first column is negative is an empty NumPy slice (:299, :319, :371, :409) -- as long as the image is at least as wide as the
+    // window.  In a narrower image the negative start wraps round to columns of the right edge and the reference reports them with
+    // negative x: nothing the kernels (or a caller) can hold, so such a search is refused.
+    if (2 * g.hw > w) return fail(LT_ERR_INVALID, "window_width %d is wider than the image (%d columns)", p->window_width, w);
     g.img_center = (int)(w / 2.0);                                            // :278
     g.y_start = (int)((1.0 - p->start_slice) * g.img_height);                 // :279
     g.nlevels = (int)((p->partial * g.img_height) / p->window_height);        // :282
@@ -399,6 +406,8 @@ int make_search_geom(lt_ctx* c, const lt_search_params* p, bool band, SearchGeom
     g.mu = p->mu;
     const long long need = (long long)std::max(g.nlevels, 1) * g.wh * std::min(2 * g.hw, w);
     g.maxpix = (int)std::max<long long>(need, 64);
+    // (room for k_sws_fit2's block however narrow the window: which kernel runs must not depend on the searches before this one)
+    g.maxpix = (int)std::max<long long>(g.maxpix, sws2_block_words(std::max(g.nlevels, 1), g.wh));
     g.maxlev = std::max(g.nlevels, 1) + 1;
     g.nbands = std::max(g.nlevels, 1);
     return LT_OK;
@@ -1892,6 +1901,41 @@ int lt_upload_masks(lt_ctx* c, const uint8_t* masks, int first, int n) {
     return LT_OK;
 }
 
+// The same masks as bit planes, in the layout of d_bits_open (slot_bits): the searches then take their bit-plane kernels, and the
+// u8 mask is expanded from the plane when somebody asks for it (ensure_u8_masks).  Bits at columns >= w are cleared on the way:
+// every reader of the plane may rely on zero tails, as behind the mask chain.
+int lt_upload_mask_bits(lt_ctx* c, const uint64_t* bits, int first, int n) {
+    int rc = check_slots(c, first, n);
+    if (rc) return rc;
+    if (!bits) return fail(LT_ERR_INVALID, "null masks");
+    if ((rc = set_device(c))) return rc;
+    if ((rc = sync_all(c))) return rc;
+    if (!c->masks.d_bits_open) return fail(LT_ERR_STATE, "the context holds no bit planes");
+    if (n == 0) return LT_OK;
+    const int h = c->calib.warp_h, w = c->calib.warp_w, wpr = (w + 63) / 64;
+    const size_t words = (size_t)h * wpr, stride = c->masks.bits_stride;
+    const uint64_t* src = bits;
+    std::vector<uint64_t> stage;
+    if (w & 63) {
+        const uint64_t live = ((uint64_t)1 << (w & 63)) - 1;
+        stage.assign(bits, bits + (size_t)n * words);
+        for (size_t r = 0; r < (size_t)n * h; ++r) stage[r * wpr + (wpr - 1)] &= live;
+        src = stage.data();
+    }
+    unsigned long long* dst = c->masks.d_bits_open + (size_t)first * stride;
+    if (stride == words) {
+        HIP_TRY(hipMemcpyAsync(dst, src, (size_t)n * words * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
+    } else {
+        for (int i = 0; i < n; ++i)
+            HIP_TRY(hipMemcpyAsync(dst + (size_t)i * stride, src + (size_t)i * words, words * sizeof(unsigned long long),
+                                   hipMemcpyHostToDevice, c->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->have_mask = true;
+    mark_masks(c, first, n, 1, 0);
+    return LT_OK;
+}
+
 int lt_upload_bev(lt_ctx* c, const uint8_t* bev, int first, int n) {
     int rc = check_slots(c, first, n);
     if (rc) return rc;
@@ -2612,6 +2656,7 @@ int lt_sws_fit_run(lt_ctx* c, int first, int n, const lt_search_params* p) {
     if (n == 0) return LT_OK;
     const bool use_bits = slot_reads_bits(c, g, 0, first, n);
     if (!use_bits && (rc = ensure_u8_masks(c, first, n))) return rc;
+    c->last_search_source = use_bits ? 1 : 0;
     rc = for_each_slice(c, first, n, [&](hipStream_t st, int f0, int m) {
         StageScope t(c, ST_SWS_FIT, st);
         launch_sws_slots(c, st, g, slot_bits(c, f0, use_bits), f0, m);
@@ -2647,6 +2692,7 @@ int lt_band_fit_run(lt_ctx* c, int first, int n, const lt_search_params* p, cons
     }
     const bool use_bits = slot_reads_bits(c, g, 1, first, n);
     if (!use_bits && (rc = ensure_u8_masks(c, first, n))) return rc;
+    c->last_search_source = use_bits ? 1 : 0;
     rc = for_each_slice(c, first, n, [&](hipStream_t st, int f0, int m) {
         StageScope t(c, ST_BAND_FIT, st);
         const MaskBits mb = slot_bits(c, f0, use_bits);
@@ -2714,9 +2760,15 @@ int lt_search_fit_list(lt_ctx* c, int n, const lt_search_item* items, const lt_s
     for (const auto& it : list) bits = bits && masks_have_bits(c, it.slot, 1);
     const bool one_launch = bits && search_list_supported(n_sws > 0 ? &gs : nullptr, n_sws < n ? &gb : nullptr, c->masks.plane_bytes);
     auto geom = [&](const lt_search_item& it) -> const SearchGeom& { return it.mode == 0 ? gs : gb; };
+    // (lt_last_search_source: 1 only if no item reads a u8 mask)
+    bool all_bits = true;
     if (!one_launch)
         for (const auto& it : list)
-            if (!slot_reads_bits(c, geom(it), it.mode, it.slot, 1) && (rc = ensure_u8_masks(c, it.slot, 1))) return rc;
+            if (!slot_reads_bits(c, geom(it), it.mode, it.slot, 1)) {
+                all_bits = false;
+                if ((rc = ensure_u8_masks(c, it.slot, 1))) return rc;
+            }
+    c->last_search_source = all_bits ? 1 : 0;
     // the stream: the urgent one in urgent mode, else the stream of the first listed slot; the other slot streams in front of it
     const int k = slice_count(c);
     std::vector<uint8_t> touched((size_t)k, 0);
@@ -3152,6 +3204,11 @@ int lt_last_threshold_path(lt_ctx* c) {
 int lt_last_threshold_form(lt_ctx* c) {
     if (!c) { (void)fail(LT_ERR_INVALID, "null context"); return LT_NO_CONTEXT; }
     return c->last_threshold_form;
+}
+
+int lt_last_search_source(lt_ctx* c) {
+    if (!c) { (void)fail(LT_ERR_INVALID, "null context"); return LT_NO_CONTEXT; }
+    return c->last_search_source;
 }
 
 int lt_last_tophat_path(lt_ctx* c) {

@@ -79,6 +79,7 @@ int lt_band_fit_chain_run(lt_ctx* c, int first, int n, const lt_search_params* p
     }
     const bool use_bits = slot_reads_bits(c, g, 1, first, n);
     if (!use_bits && (rc = ensure_u8_masks(c, first, n))) return rc;
+    c->last_search_source = use_bits ? 1 : 0;
     // The chain runs on the context's search stream, behind whatever the slots' streams hold so far (the masks of these
     // slots, the search that wrote the seed record); those streams do not wait for it -- the mask chains of later frames run
     // beside it -- unless they touch its slots (for_each_slice).

@@ -217,6 +217,7 @@ struct lt_ctx {
     int last_tophat_path = -1;                    // lt_last_tophat_path
     int last_threshold_form = -1;                 // lt_last_threshold_form
     int last_adaptive_path = -1;                  // 'neighborhood' calls: 1 = running box sums (k_adaptive_walk.hip), 0 = per-pixel windows
+    int last_search_source = -1;                  // lt_last_search_source: 1 = the last search call read bit planes only, 0 = u8 masks
     // The walking threshold kernels are long serial walks (a wave covers half an image row or column): they win once a
     // call brings enough frames to fill the chip -- measured crossover 70-80 frames of 1100 x 1080 per call
     // (tools/threshold_crossover.py: 64 frames 232 vs 210 us, 96 frames 255 vs 304 us) -- and lose badly on a single

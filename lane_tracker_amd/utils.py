@@ -199,6 +199,35 @@ def unpack_raw(frames, fmt):
     return out.reshape(a.shape[:-1] + (-1,))
 
 
+def pack_mask_bits(masks):
+    """Binary masks (..., H, W), a pixel set where != 0 (u8 or bool), as the bit planes of `Context.upload_mask_bits`: uint64
+    (..., H, (W + 63) // 64); pixel x of a row is bit x % 64 of the row's word x // 64, least significant bit first; the bits at
+    columns >= W are zero.  NumPy only."""
+    a = np.asarray(masks)
+    if a.ndim < 2 or a.shape[-1] == 0:
+        raise ValueError("masks to pack are arrays (..., H, W) with W > 0, got %r" % (a.shape,))
+    w = a.shape[-1]
+    wpr = (w + 63) // 64
+    set_ = np.zeros(a.shape[:-1] + (wpr * 64,), np.uint8)
+    set_[..., :w] = a != 0
+    octets = set_.reshape(a.shape[:-1] + (wpr * 8, 8))
+    by = np.zeros(octets.shape[:-1], np.uint8)
+    for k in range(8):
+        by |= octets[..., k] << k
+    return np.ascontiguousarray(by).view('<u8').astype(np.uint64, copy=False).reshape(a.shape[:-1] + (wpr,))
+
+
+def unpack_mask_bits(bits, width, value=255):
+    """The inverse of `pack_mask_bits`: uint64 (..., H, wpr) -> u8 (..., H, width), `value` where the bit is set.  Bits at columns
+    >= width are dropped.  NumPy only."""
+    b = np.ascontiguousarray(np.asarray(bits, np.uint64).astype('<u8', copy=False))
+    if b.ndim < 2 or not 0 < width <= 64 * b.shape[-1] or width <= 64 * (b.shape[-1] - 1):
+        raise ValueError("a row of width %d is %d words, got %r" % (width, (width + 63) // 64, b.shape))
+    by = b.view(np.uint8).reshape(b.shape[:-1] + (b.shape[-1] * 8, 1))
+    set_ = (by >> np.arange(8, dtype=np.uint8)) & 1
+    return (set_.reshape(b.shape[:-1] + (-1,))[..., :width] * np.uint8(value)).astype(np.uint8)
+
+
 def checked_raw_lut(lut, bits=8):
     """A raw table as the C-contiguous u8 array (4, 256) -- (4, 2**bits) for 10- / 12-bit samples -- the device takes; ValueError for any
     other shape or dtype (nothing is cast: a float table is a mistake, not a table)."""

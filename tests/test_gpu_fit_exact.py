@@ -20,10 +20,10 @@ those follow from the rules of lt_api.cpp, which the bit-plane tests at the end 
                          searches behind it still read the bit plane
   one k_search_list launch: every listed slot has a bit plane && search_list_supported = both geometries take bit planes
   k_band_chain3:         bit planes && h <= 8192 (launch_band_chain; launch_band_fit_one for n = 1 with coefficients by value)
-What no test here reaches: a non-zero high word of sum dy^4 in k_band_chain3 (s_tot4h) and in the bit-plane *2 kernels.  Bit planes
-come from the mask chain, which these tests run at the reference 1100 x 1080 only, where sum dy^4 stays below 2^53; the carry path
-they share (wave_sum_u64_wide) is reached through the u8 variants of k_sws_fit2 and k_band_fit2 at 6600 and 8192 rows.  Reverting
-k_band_chain3's own two lines for the high word would fail no test."""
+The bit planes of the tests at the end of this file come from the mask chain, at the reference 1100 x 1080, where sum dy^4 stays below
+2^53.  The tall designs of this file run through the bit-plane *2 kernels and k_band_chain3 -- sum dy^4 above 2^63 -- in
+tests/test_gpu_search_bits.py (test_tall_sliding_window_from_bit_planes, test_tall_band_and_chain_from_bit_planes), on masks
+uploaded as bit planes (lt_upload_mask_bits; lt_last_search_source tells the variants apart where `_pad` does not)."""
 import ctypes as C
 from fractions import Fraction as F
 

@@ -7,7 +7,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import coeff_close, golden_files, params_of, unpack_mask
+from helpers import FIXTURE_BITS_SOURCE, coeff_close, golden_files, params_of, search_source, unpack_mask, upload
 
 pytestmark = pytest.mark.gpu
 
@@ -178,13 +178,17 @@ def plane_ctxs():
         c.close()
 
 
+# Every search test below runs from both forms of the mask: uploaded as bytes (lt_upload_masks: the u8 kernels) and as a bit plane
+# (lt_upload_mask_bits: the kernels every mask of the chain is searched by).  The tests keep their names for bytes; `_bits` is the
+# same body from bit planes.  lt_last_search_source says which kernels ran.
 @pytest.mark.parametrize("path", golden_files("sws_"), ids=os.path.basename)
-def test_sliding_window_search_vs_reference_fixture(nat, plane_ctxs, oracle, path):
+def test_sliding_window_search_vs_reference_fixture(nat, plane_ctxs, oracle, path, source="u8"):
     d = np.load(path)
     mask, p = unpack_mask(d), params_of(d)
     c = _ctx_for(nat, plane_ctxs, mask.shape)
-    c.upload_masks(mask)
+    upload(c, mask, source)
     c.sws_fit_run(1, nat.search_params(**p))
+    assert c.last_search_source() == search_source(source, FIXTURE_BITS_SOURCE[os.path.basename(path)])
     rec = c.download_records(1)[0]
     assert bool(rec["detected"]) == bool(d["detected"])
     o = oracle.sliding_window_search(mask, oracle.search_params(**p))
@@ -210,14 +214,20 @@ def test_sliding_window_search_vs_reference_fixture(nat, plane_ctxs, oracle, pat
     assert np.allclose(rec["left_coeffs"], d["left_coeffs"], rtol=1e-8, atol=1e-9)
 
 
+@pytest.mark.parametrize("path", golden_files("sws_"), ids=os.path.basename)
+def test_sliding_window_search_vs_reference_fixture_bits(nat, plane_ctxs, oracle, path):
+    test_sliding_window_search_vs_reference_fixture(nat, plane_ctxs, oracle, path, "bits")
+
+
 @pytest.mark.parametrize("path", golden_files("band"), ids=os.path.basename)
-def test_band_search_vs_reference_fixture(nat, plane_ctxs, path):
+def test_band_search_vs_reference_fixture(nat, plane_ctxs, path, source="u8"):
     d = np.load(path)
     mask, p = unpack_mask(d), params_of(d)
     c = _ctx_for(nat, plane_ctxs, mask.shape)
-    c.upload_masks(mask)
+    upload(c, mask, source)
     prev = np.concatenate([d["prev_left"], d["prev_right"]])
     c.band_fit_run(1, prev, nat.search_params(**p))
+    assert c.last_search_source() == search_source(source, FIXTURE_BITS_SOURCE[os.path.basename(path)])
     rec = c.download_records(1)[0]
     assert bool(rec["detected"]) == bool(d["detected"])
     assert int(rec["mode"]) == 1
@@ -231,8 +241,15 @@ def test_band_search_vs_reference_fixture(nat, plane_ctxs, path):
     assert np.allclose(rec["right_coeffs"], d["right_coeffs"], rtol=1e-8, atol=1e-9)
 
 
-def test_search_fuzz_vs_oracle(nat, plane_ctxs, oracle):
-    """Random masks/parameters (abort branches, borders, odd windows): GPU == oracle, bit for bit."""
+@pytest.mark.parametrize("path", golden_files("band"), ids=os.path.basename)
+def test_band_search_vs_reference_fixture_bits(nat, plane_ctxs, path):
+    test_band_search_vs_reference_fixture(nat, plane_ctxs, path, "bits")
+
+
+def test_search_fuzz_vs_oracle(nat, plane_ctxs, oracle, source="u8"):
+    """Random masks/parameters (abort branches, borders, odd windows): GPU == oracle, bit for bit.  The same 40 cases from bytes
+    and from bit planes; a bit plane is searched by the bit-plane kernels up to 64 columns of window or band (k_search.hip:
+    2 * int(window_width / 2) <= 64, 2 * bandwidth + 2 <= 64), beyond by the u8 kernels on the expanded mask."""
     from lane_tracker_amd import synth
     rng = np.random.default_rng(99)
     c = _ctx_for(nat, plane_ctxs, (1100, 1080))
@@ -254,8 +271,9 @@ def test_search_fuzz_vs_oracle(nat, plane_ctxs, oracle):
                  no_success_limit=int(rng.choice([8, 3, 50, 1])), start_slice=float(rng.choice([0.25, 0.1, 1.0])),
                  ignore_sides=int(rng.choice([360, 0, 100])), ignore_bottom=int(rng.choice([30, 0, 7])),
                  partial=float(rng.choice([1.0, 0.5, 0.3])))
-        c.upload_masks(m)
+        upload(c, m, source)
         c.sws_fit_run(1, nat.search_params(**p))
+        assert c.last_search_source() == search_source(source, 1 if 2 * (p["window_width"] // 2) <= 64 else 0), p
         o = oracle.sliding_window_search(m, oracle.search_params(**p))
         rec = c.download_records(1)[0]
         assert bool(rec["detected"]) == o["detected"], p
@@ -273,6 +291,7 @@ def test_search_fuzz_vs_oracle(nat, plane_ctxs, oracle):
         bp = dict(bandwidth=int(rng.choice([25, 30, 5, 80])), ignore_bottom=int(rng.choice([30, 0, 11])),
                   partial=float(rng.choice([1.0, 0.5])))
         c.band_fit_run(1, np.concatenate([lc, rc]), nat.search_params(**bp))
+        assert c.last_search_source() == search_source(source, 1 if 2 * bp["bandwidth"] + 2 <= 64 else 0), bp
         ob = oracle.band_search(m, lc, rc, oracle.search_params(**bp))
         rec = c.download_records(1)[0]
         assert bool(rec["detected"]) == ob["detected"], bp
@@ -280,6 +299,10 @@ def test_search_fuzz_vs_oracle(nat, plane_ctxs, oracle):
             for side, (ky, kx) in enumerate((("left_y", "left_x"), ("right_y", "right_x"))):
                 y, x = c.download_pixels(0, side)
                 assert_same(y, ob[ky], f"band {ky} {bp}"); assert_same(x, ob[kx], f"band {kx} {bp}")
+
+
+def test_search_fuzz_vs_oracle_bits(nat, plane_ctxs, oracle):
+    test_search_fuzz_vs_oracle(nat, plane_ctxs, oracle, "bits")
 
 
 def test_fit_rank_deficient_flag_and_host_answer(nat, plane_ctxs):
@@ -572,17 +595,22 @@ def test_source_row_upload_is_enough_for_the_path(nat, cal, frames):
         b.close()
 
 
-@pytest.mark.parametrize("ww,wh", [(64, 40), (65, 40), (66, 40), (32, 64), (33, 65), (20, 130), (4, 7)])
-def test_search_kernel_limits_both_versions(nat, plane_ctxs, oracle, ww, wh):
+SWS_LIMITS_BITS_SOURCE = {(64, 40): 1, (65, 40): 1, (66, 40): 0, (32, 64): 1, (33, 65): 1, (20, 130): 1, (4, 7): 0}
+
+
+@pytest.mark.parametrize("ww,wh", list(SWS_LIMITS_BITS_SOURCE))
+def test_search_kernel_limits_both_versions(nat, plane_ctxs, oracle, ww, wh, source="u8"):
     """Window sizes around the limits of k_sws_fit2 (2 * int(ww / 2) <= 64 columns; any height): whichever kernel the
-    launcher picks, the result is the oracle's."""
+    launcher picks, the result is the oracle's.  bits_source: whether a bit plane is searched as one (66 columns are too wide;
+    152 levels of 7 rows keep 2 bytes of LDS per level and column, 326 KB of the 150 a workgroup may ask for)."""
     from lane_tracker_amd import synth
     c = _ctx_for(nat, plane_ctxs, (1100, 1080))
     for seed in (5, 6):
         m = synth.synth_mask(seed, noise=2e-3, curv=2e-4, slope=0.1)[0]
         p = dict(window_width=ww, window_height=wh, search_range=25, ignore_sides=200)
-        c.upload_masks(m)
+        upload(c, m, source)
         c.sws_fit_run(1, nat.search_params(**p))
+        assert c.last_search_source() == search_source(source, SWS_LIMITS_BITS_SOURCE[(ww, wh)]), p
         o = oracle.sliding_window_search(m, oracle.search_params(**p))
         rec = c.download_records(1)[0]
         assert bool(rec["detected"]) == o["detected"], p
@@ -595,8 +623,16 @@ def test_search_kernel_limits_both_versions(nat, plane_ctxs, oracle, ww, wh):
             assert coeff_close(rec["right_coeffs"], oracle.polyfit2(o["right_y"], o["right_x"]))
 
 
-@pytest.mark.parametrize("bandwidth", [0, 1, 30, 31, 32, 200])
-def test_band_kernel_limits_both_versions(nat, plane_ctxs, oracle, bandwidth):
+@pytest.mark.parametrize("ww,wh", list(SWS_LIMITS_BITS_SOURCE))
+def test_search_kernel_limits_both_versions_bits(nat, plane_ctxs, oracle, ww, wh):
+    test_search_kernel_limits_both_versions(nat, plane_ctxs, oracle, ww, wh, "bits")
+
+
+BAND_LIMITS_BITS_SOURCE = {0: 1, 1: 1, 30: 1, 31: 1, 32: 0, 200: 0}
+
+
+@pytest.mark.parametrize("bandwidth", list(BAND_LIMITS_BITS_SOURCE))
+def test_band_kernel_limits_both_versions(nat, plane_ctxs, oracle, bandwidth, source="u8"):
     """Band widths around the 64-column limit of k_band_fit2 (2 * bandwidth + 2 <= 64)."""
     from lane_tracker_amd import synth
     c = _ctx_for(nat, plane_ctxs, (1100, 1080))
@@ -604,8 +640,9 @@ def test_band_kernel_limits_both_versions(nat, plane_ctxs, oracle, bandwidth):
     lc, rc = lc + np.array([0, 0, 0.4]), rc + np.array([0, 0, -0.6])
     for partial, ib in ((1.0, 30), (0.5, 0)):
         p = dict(bandwidth=bandwidth, ignore_bottom=ib, partial=partial)
-        c.upload_masks(m)
+        upload(c, m, source)
         c.band_fit_run(1, np.concatenate([lc, rc]), nat.search_params(**p))
+        assert c.last_search_source() == search_source(source, BAND_LIMITS_BITS_SOURCE[bandwidth]), p
         o = oracle.band_search(m, lc, rc, oracle.search_params(**p))
         rec = c.download_records(1)[0]
         assert bool(rec["detected"]) == o["detected"], p
@@ -614,6 +651,11 @@ def test_band_kernel_limits_both_versions(nat, plane_ctxs, oracle, bandwidth):
             assert_same(y, o[ky], f"{ky} {p}"); assert_same(x, o[kx], f"{kx} {p}")
         if o["detected"] and bandwidth > 0:
             assert coeff_close(rec["left_coeffs"], oracle.polyfit2(o["left_y"], o["left_x"]))
+
+
+@pytest.mark.parametrize("bandwidth", list(BAND_LIMITS_BITS_SOURCE))
+def test_band_kernel_limits_both_versions_bits(nat, plane_ctxs, oracle, bandwidth):
+    test_band_kernel_limits_both_versions(nat, plane_ctxs, oracle, bandwidth, "bits")
 
 
 def test_randomised_differential_run():
