@@ -68,7 +68,8 @@ extern "C" {
  *    Bayer input: a colour-correction matrix and an output curve on every demosaiced pixel, on the device); lt_set_raw_shading +
  *    lt_get_raw_shading + lt_get_raw_shading_plane + lt_raw_to_rgb_shaded (lens-shading correction of raw Bayer input from a gain mesh, on
  *    every sample in front of the raw table, on the device); lt_upload_mask_bits + lt_last_search_source (caller-supplied masks as
- *    bit planes, searched by the bit-plane kernels).  Nothing removed or changed. */
+ *    bit planes, searched by the bit-plane kernels); lt_last_open_form (which form of the 5x5 open a mask run's last slice took).
+ *    Nothing removed or changed. */
 #define LT_ABI_VERSION 5
 
 typedef enum lt_status {
@@ -1039,6 +1040,12 @@ int  lt_last_threshold_path(lt_ctx* ctx);
  * products; where lt_last_threshold_path says 1 and the walks' conditions hold), -1 = none yet; LT_NO_CONTEXT for a null
  * context.  Forms 1 and 2 write identical partial planes; the greenery mask keeps its running-sum walk under either. */
 int  lt_last_threshold_form(lt_ctx* ctx);
+/* Which form of the 5x5 open the last slice of the context's last lt_mask_run / lt_filter_run launched: 0 = the separate kernels
+ * (the merge, the erode and the dilate a launch each: 5 to 15 frames, and every plane that reaches the open merged already),
+ * 1 = the wave walk (merge + open in one pass, 16 frames or more), 2 = the small form (merge + open in one launch of small
+ * workgroups, up to 4 frames), -1 = none yet; LT_NO_CONTEXT for a null context.  All three give identical masks and merged
+ * planes; tests use this to know which one they have exercised.  (lt_filter_lane_points does not report here.) */
+int  lt_last_open_form(lt_ctx* ctx);
 /* Which form of the batch top-hat walks the context's last lt_mask_run / lt_filter_run piece launched: bit 0 = the 29x29 pair
  * of launches, bit 1 = the 55x55 pair took the split-band form (every band walks its own rows only and boundary rows are
  * merged from the two neighbours' partial results); 0 = the bands walked their halos, or another top-hat route ran (one or two

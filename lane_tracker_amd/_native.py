@@ -226,6 +226,7 @@ _SIGNATURES = {
     "lt_download_stats": (C.c_int, [_P, _P, _P, _P, _P, _P]),
     "lt_last_threshold_path": (C.c_int, [_P]),
     "lt_last_threshold_form": (C.c_int, [_P]),
+    "lt_last_open_form": (C.c_int, [_P]),
     "lt_last_tophat_path": (C.c_int, [_P]),
     "lt_last_search_source": (C.c_int, [_P]),
     "lt_tophat_split_form": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -1850,6 +1851,10 @@ class Context:
     def last_threshold_form(self):
         """0 = tile kernel, 1 = running-sum walks, 2 = matrix-core form (i8 band products), -1 = no bilateral chain has run yet."""
         return int(self.lib.lt_last_threshold_form(self._h))
+
+    def last_open_form(self):
+        """5x5 open of the last slice launched: 0 = separate kernels, 1 = wave walk (k_merge_open5), 2 = small form (k_or_open5_small), -1 = none yet."""
+        return int(self.lib.lt_last_open_form(self._h))
 
     def last_tophat_path(self):
         """Batch top-hat walks of the last mask chain: bit 0 = 29x29, bit 1 = 55x55 ran the split-band form; 0 = neither, -1 = none yet."""

@@ -336,7 +336,8 @@ static int ensure_mask_plane(lt_ctx* c) {
 // what the mask chain takes from the context besides the arena (lt_mask_chain.cpp)
 static ChainEnv chain_env(lt_ctx* c) {
     return ChainEnv{&c->se29, &c->se55, c->brute_tophat, c->walk_min_pixels, &c->streams, c->stage_timing ? c : nullptr,
-                    &c->last_threshold_path, &c->last_adaptive_path, &c->last_tophat_path, &c->last_threshold_form};
+                    &c->last_threshold_path, &c->last_adaptive_path, &c->last_tophat_path, &c->last_threshold_form,
+                    &c->last_open_form};
 }
 // make d_plane[P_MASK] current for the slots (expands the bit plane where only that exists)
 int ensure_u8_masks(lt_ctx* c, int first, int n) {
@@ -3204,6 +3205,11 @@ int lt_last_threshold_path(lt_ctx* c) {
 int lt_last_threshold_form(lt_ctx* c) {
     if (!c) { (void)fail(LT_ERR_INVALID, "null context"); return LT_NO_CONTEXT; }
     return c->last_threshold_form;
+}
+
+int lt_last_open_form(lt_ctx* c) {
+    if (!c) { (void)fail(LT_ERR_INVALID, "null context"); return LT_NO_CONTEXT; }
+    return c->last_open_form;
 }
 
 int lt_last_search_source(lt_ctx* c) {

@@ -216,6 +216,7 @@ struct lt_ctx {
     int last_threshold_path = -1;                 // lt_last_threshold_path
     int last_tophat_path = -1;                    // lt_last_tophat_path
     int last_threshold_form = -1;                 // lt_last_threshold_form
+    int last_open_form = -1;                      // lt_last_open_form
     int last_adaptive_path = -1;                  // 'neighborhood' calls: 1 = running box sums (k_adaptive_walk.hip), 0 = per-pixel windows
     int last_search_source = -1;                  // lt_last_search_source: 1 = the last search call read bit planes only, 0 = u8 masks
     // The walking threshold kernels are long serial walks (a wave covers half an image row or column): they win once a
@@ -719,6 +720,7 @@ struct ChainEnv {
     int *threshold_path = nullptr, *adaptive_path = nullptr;   // lt_last_threshold_path / lt_last_adaptive_path; null: nobody asks
     int* tophat_path = nullptr;                         // lt_last_tophat_path; null: nobody asks
     int* threshold_form = nullptr;                      // lt_last_threshold_form; null: nobody asks
+    int* open_form = nullptr;                           // lt_last_open_form; null: nobody asks
 };
 // filter_lane_points() (lane_tracker.py:210-238) on planes P_R / P_B of slots [first, first + n) of the arena, h x w pixels each, on
 // stream s; call_frames: the frames of the whole call this piece belongs to.  The opened mask lands in d_bits_open, or with

@@ -212,14 +212,16 @@ struct Chain {
         StageScope t(env.timing, ST_OPEN, s);
         const size_t bs = a.bits_stride;
         unsigned long long* obits = u8_mask ? nullptr : a.d_bits_open + (size_t)first * bs;
+        auto said = [&](int form) { if (env.open_form) *env.open_form = form; };   // lt_last_open_form: the branch taken
         // 16 frames or more: one pass over the words, a wave walking down the rows -- for partial planes.  A plane that is merged
         // already has never taken that kernel (it went to the launcher with the arena's two spare planes beside it, which the
         // launcher refuses): it takes the separate kernels below, and k_merge_open5<1> has no caller.  Kept as found: this file
         // launches what its predecessor launched.
-        if (!u8_mask && n >= 16 && in.n_more > 0 && launch_merge_open5(s, in, obits, h, w, bs, n)) return;
+        if (!u8_mask && n >= 16 && in.n_more > 0 && launch_merge_open5(s, in, obits, h, w, bs, n)) return said(1);
         // a few frames are latency-bound and better off with the wide, shallow kernels: the OR and the open in one launch of small
         // workgroups (the one-frame chain is made of launch gaps: three kernels of 5 us here)
-        if (!u8_mask && n <= 4 && launch_or_open5_small(s, in, obits, h, w, bs, n)) return;
+        if (!u8_mask && n <= 4 && launch_or_open5_small(s, in, obits, h, w, bs, n)) return said(2);
+        said(0);
         launch_or4_bits(s, in, h, w, bs, n);
         if (u8_mask) launch_open5_bits(s, in.dst, ebits, mask, h, w, ps, bs, n);
         else launch_open5_to_bits(s, in.dst, ebits, obits, h, w, bs, n);

@@ -25,8 +25,8 @@ def row(c, label, frames, **kw):
     c.mask_run(n, _native.filter_params(**kw))
     c.sync()
     ones = int(c.download_masks(n).astype(bool).sum())
-    print("%-58s frames %3d  threshold_path %2d  adaptive_path %2d  mask pixels %d" %
-          (label, n, c.last_threshold_path(), c.last_adaptive_path(), ones), flush=True)
+    print("%-58s frames %3d  threshold_path %2d  adaptive_path %2d  open_form %2d  mask pixels %d" %
+          (label, n, c.last_threshold_path(), c.last_adaptive_path(), c.last_open_form(), ones), flush=True)
 
 
 def routes():
