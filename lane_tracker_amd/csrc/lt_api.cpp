@@ -158,6 +158,27 @@ int wait_tail(lt_ctx* c, hipStream_t waiter, hipStream_t st) {
     return LT_OK;
 }
 
+// Fallback of the stream-ordered uploads when the ring of readers has overflowed: `waiter` waits for the tail of every stream
+// a kernel that reads camera frames can be on -- the slots' compute streams (undistortion), the presentation stream (overlays)
+// and the urgent stream.
+int wait_reader_tails(lt_ctx* c, hipStream_t waiter) {
+    const bool slices_only = !c->readers.overflow;     // (only `lazy`: the unrecorded readers are on the slots' streams)
+    auto tail = [&](hipStream_t st) { return !st || st == waiter ? (int)LT_OK : wait_tail(c, waiter, st); };
+    for (int i = 0; i < c->nstreams && i < (int)c->streams.size(); ++i) { const int rc = tail(c->streams[i]); if (rc) return rc; }
+    if (slices_only) return LT_OK;
+    int rc = tail(c->present);
+    if (!rc) rc = tail(c->urgent);
+    return rc;
+}
+// A stream-ordered copy into the camera rows of slots [first, first + n) waits on `st` for the kernels that still read them (slot-range
+// events), or -- where the ring does not know them all -- for the tails of every stream such a kernel can be on.
+int wait_camera_readers(lt_ctx* c, hipStream_t st, int first, int n) {
+    bool precise = true;
+    int rc = wait_range(c->readers, st, first, first + n, &precise);
+    if (!rc && !precise) rc = wait_reader_tails(c, st);
+    return rc;
+}
+
 hipEvent_t next_order_event(lt_ctx* c) {
     constexpr size_t RING = 64;
     if (c->order_events.size() < RING) {
@@ -258,11 +279,11 @@ int ensure_search_buffers(lt_ctx* c, int maxpix, int maxlev) {
 void mark_frames(lt_ctx* c, int first, int n, int full) {
     for (int i = first; i < first + n && i < (int)c->frame_full.size(); ++i) c->frame_full[(size_t)i] = (uint8_t)full;
 }
-static void front_stale(lt_ctx* c, int first, int n) {      // new camera rows in these slots: their planes are the old frames'
+void front_stale(lt_ctx* c, int first, int n) {             // new camera rows in these slots: their planes are the old frames'
     for (int i = first; i < first + n && i < (int)c->front_ok.size(); ++i) c->front_ok[(size_t)i] = 0;
 }
 // an upload of camera rows into these slots: their front end reads the slots' own frames again (lt_attach_device_frames)
-static void detach_slots(lt_ctx* c, int first, int n) {
+void detach_slots(lt_ctx* c, int first, int n) {
     for (int i = first; i < first + n && i < (int)c->attached.size(); ++i) c->attached[(size_t)i] = 0;
     for (int i = first; i < first + n && i < (int)c->drawn.size(); ++i) c->drawn[(size_t)i] = 0;
 }
@@ -899,13 +920,6 @@ static int check_raw_size(int layout, int h, int w) {
     if (raw_packing(layout) == 0 && (w & 3)) return fail(LT_ERR_INVALID, "MIPI-packed RAW10 frames need a width that is a multiple of 4, got %dx%d", w, h);
     return LT_OK;
 }
-// The rows of a slot's staging frame that the lt_upload_frame_rows family brings for the path's camera rows [cam_r0, cam_r1): those
-// rows themselves, or -- raw Bayer -- the rows that their taps' windows touch (bayer_arith.h: input_run).
-static void staged_run(const lt_ctx* c, int* r0, int* r1) {
-    *r0 = c->cam_r0;
-    *r1 = c->cam_r1;
-    if (is_raw_mosaic(c->in_layout) && c->cam_r1 > c->cam_r0) ba::input_run(c->cam_r0, c->cam_r1, c->calib.img_h, r0, r1);
-}
 
 // 10- / 12-bit raw Bayer.  The default table: full scale to full scale, rounded -- utils.raw_lut(bits=..) with its defaults, in integers
 // (floor(255 s / m + 1 / 2) = (510 s + m) / (2 m), m = 2^bits - 1).
@@ -1192,69 +1206,9 @@ int lt_get_input_format(lt_ctx* c, int* layout, int32_t* coeffs) {
     return LT_OK;
 }
 
-// Rows [r0, r1) of the Y plane and rows [c0, c1) of the chroma plane(s) of n host frames (yuv_bytes apart) into the staging
-// frames of slots [first, first + n), on `st`: one pitched copy per plane piece.
-static int yuv_copy(lt_ctx* c, const uint8_t* frames, int first, int n, int r0, int r1, int c0, int c1, hipStream_t st) {
-    const size_t W = (size_t)c->calib.img_w, plane = (size_t)c->calib.img_h * W;
-    uint8_t* dst = slot_yuv(c, first);
-    auto piece = [&](size_t off, size_t bytes) {
-        HIP_TRY(hipMemcpy2DAsync(dst + off, c->yuv_stride, frames + off, c->yuv_bytes, bytes, (size_t)n, hipMemcpyHostToDevice, st));
-        return (int)LT_OK;
-    };
-    int rc = LT_OK;
-    if (const size_t row = (size_t)one_plane_row_bytes(c->in_layout, c->calib.img_w))   // one plane of 2 W (4:2:2), 3 W (BGR), 4 W (RGBA / BGRA) ... bytes a row: its rows [r0, r1); no chroma rows
-        return r1 > r0 ? piece((size_t)r0 * row, (size_t)(r1 - r0) * row) : rc;
-    if (r1 > r0 && c1 > c0 && r0 == 0 && r1 == c->calib.img_h && c0 == 0 && c1 == c->calib.img_h / 2) return piece(0, c->yuv_bytes);
-    if (r1 > r0 && (rc = piece((size_t)r0 * W, (size_t)(r1 - r0) * W))) return rc;
-    if (c1 <= c0) return rc;
-    if (c->in_layout == LT_INPUT_NV12) return piece(plane + (size_t)c0 * W, (size_t)(c1 - c0) * W);
-    if ((rc = piece(plane + (size_t)c0 * (W / 2), (size_t)(c1 - c0) * (W / 2)))) return rc;
-    return piece(plane + plane / 4 + (size_t)c0 * (W / 2), (size_t)(c1 - c0) * (W / 2));
-}
-// chroma rows under the Y rows [r0, r1)
-static inline int chroma_lo(int r0) { return r0 / 2; }
-static inline int chroma_hi(int r0, int r1) { return r1 > r0 ? (r1 - 1) / 2 + 1 : r0 / 2; }
-// rows [r0, r1) of the staging frames of slots [first, first + n) -> the same rows of their RGB camera frames, on `st`
-static void yuv_convert(lt_ctx* c, hipStream_t st, int first, int n, int r0, int r1) {
-    launch_yuv_rows_to_rgb(st, c->in_layout, slot_yuv(c, first), c->yuv_stride, yuv_coef_of(c), slot_frame(c, first), c->frame_bytes,
-                           c->calib.img_h, c->calib.img_w, r0, r1, n, raw_stages_of(c));
-}
-
 // ---- input frames of another size (lt_set_input_size) ------------------------------------------------------------------------
 // The slots' staging frames hold the caller's src_w x src_h RGB frames (or the rows of them that have been uploaded); k_resize_rows
-// fills rows of the slots' RGB camera frames from them.  Which source rows a run of camera rows reads follows from the vertical tap
-// table (resize_arith.h: input_run).
-static inline bool resizes(const lt_ctx* c) { return c->src_w > 0; }
-static void rs_input_rows(const lt_ctx* c, int a, int b, int* s0, int* s1) {
-    if (b <= a) { *s0 = *s1 = 0; return; }
-    *s0 = c->rs_yt[4 * (size_t)a];
-    *s1 = c->rs_yt[4 * (size_t)(b - 1) + 1] + 1;
-}
-// source rows [s0, s1) of n host frames (src_bytes apart) into the staging frames of slots [first, first + n), on `st`
-static int rs_copy(lt_ctx* c, const uint8_t* frames, int first, int n, int s0, int s1, hipStream_t st) {
-    if (s1 <= s0) return LT_OK;
-    const size_t rb = (size_t)c->src_w * 3, off = (size_t)s0 * rb;
-    HIP_TRY(hipMemcpy2DAsync(slot_src(c, first) + off, c->src_stride, frames + off, c->src_bytes, (size_t)(s1 - s0) * rb, (size_t)n,
-                             hipMemcpyHostToDevice, st));
-    return LT_OK;
-}
-// ... those that camera rows [a, b) read and that the upload of the rows the path reads does not bring
-static int rs_copy_for(lt_ctx* c, const uint8_t* frames, int first, int n, int a, int b, hipStream_t st) {
-    int A, B, s0, s1;
-    rs_input_rows(c, a, b, &A, &B);
-    rs_input_rows(c, c->cam_r0, c->cam_r1, &s0, &s1);
-    if (s1 <= s0) return rs_copy(c, frames, first, n, A, B, st);
-    int rc = rs_copy(c, frames, first, n, A, std::min(B, s0), st);
-    return rc ? rc : rs_copy(c, frames, first, n, std::max(A, s1), B, st);
-}
-// rows [a, b) of the RGB camera frames of slots [first, first + n) := the resized rows of their staging frames, on `st`
-static int rs_resize(lt_ctx* c, hipStream_t st, int first, int n, int a, int b) {
-    launch_resize_rows(st, slot_src(c, first), c->src_stride, c->src_bytes, c->src_w, slot_frame(c, first), c->frame_bytes, c->calib.img_w,
-                       a, b, c->d_rs_xt, c->d_rs_yt, n);
-    HIP_TRY(hipGetLastError());
-    return LT_OK;
-}
-
+// fills rows of the slots' RGB camera frames from them (lt_ingest.cpp: the resized kind).
 int lt_set_input_size(lt_ctx* c, int src_w, int src_h) {
     if (!c) return fail(LT_ERR_INVALID, "null context");
     if (src_w < 1 || src_w > rz::SIZE_MAX_AXIS || src_h < 1 || src_h > rz::SIZE_MAX_AXIS)
@@ -1316,442 +1270,12 @@ int lt_get_input_size(lt_ctx* c, int* src_w, int* src_h) {
     return LT_OK;
 }
 
-int lt_get_input_rows(lt_ctx* c, int* row0, int* row1) {
-    if (!c || !row0 || !row1) return fail(LT_ERR_INVALID, "null argument");
-    if (resizes(c)) rs_input_rows(c, c->cam_r0, c->cam_r1, row0, row1);
-    else staged_run(c, row0, row1);
-    return LT_OK;
-}
-
-// ---- data movement -------------------------------------------------------------------------------
-int lt_upload_frames(lt_ctx* c, const uint8_t* frames, int first, int n) {
-    int rc = check_slots(c, first, n);
-    if (rc) return rc;
-    if (!frames) return fail(LT_ERR_INVALID, "null frames");
-    if ((rc = set_device(c))) return rc;
-    if ((rc = sync_all(c))) return rc;
-    if (n > 0) c->input_locked = true;
-    detach_slots(c, first, n);
-    if (c->in_layout != LT_INPUT_RGB) {
-        // 4:2:0: the frames into staging (what the undistortion reads), and their RGB form into the camera frames for whoever shows them
-        if (n > 0 && (rc = yuv_copy(c, frames, first, n, 0, c->calib.img_h, 0, c->calib.img_h / 2, c->stream))) return rc;
-        yuv_convert(c, c->stream, first, n, 0, c->calib.img_h);
-        HIP_TRY(hipGetLastError());
-    } else if (resizes(c)) {
-        // another size: the frames into staging, and their resized form into the camera frames (what everything else reads)
-        if (n > 0 && (rc = rs_copy(c, frames, first, n, 0, c->src_h, c->stream))) return rc;
-        if ((rc = rs_resize(c, c->stream, first, n, 0, c->calib.img_h))) return rc;
-    } else
-    HIP_TRY(hipMemcpyAsync(slot_frame(c, first), frames, (size_t)n * c->frame_bytes,
-                           hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    mark_frames(c, first, n, 1);
-    front_stale(c, first, n);
-    return LT_OK;
-}
-
+// ---- data movement (host frames into slots: lt_ingest.cpp) ----------------------------------------
 int lt_get_source_rows(lt_ctx* c, int* row0, int* row1) {
     if (!c || !row0 || !row1) return fail(LT_ERR_INVALID, "null argument");
     *row0 = c->cam_r0;
     *row1 = c->cam_r1;
     return LT_OK;
-}
-
-static int wait_reader_tails(lt_ctx* c, hipStream_t waiter);
-
-// The preamble of the uploads of camera rows into slots [first, first + n): slots and frames valid; the device current when there
-// is anything to copy.
-static int check_upload(lt_ctx* c, const uint8_t* frames, int first, int n) {
-    int rc = check_slots(c, first, n);
-    if (rc) return rc;
-    if (!frames) return fail(LT_ERR_INVALID, "null frames");
-    if (n > 0) c->input_locked = true;
-    detach_slots(c, first, n);
-    return n > 0 ? set_device(c) : LT_OK;
-}
-// A stream-ordered copy into the camera rows of slots [first, first + n) waits on `st` for the kernels that still read them (slot-range
-// events), or -- where the ring does not know them all -- for the tails of every stream such a kernel can be on.
-static int wait_camera_readers(lt_ctx* c, hipStream_t st, int first, int n) {
-    bool precise = true;
-    int rc = wait_range(c->readers, st, first, first + n, &precise);
-    if (!rc && !precise) rc = wait_reader_tails(c, st);
-    return rc;
-}
-
-// ---- one frame's rows through the PCIe aperture ----------------------------------------------------------------------------------
-// With a large BAR the whole device memory is mapped into the process, write-combining, at the addresses hipMalloc hands out: the
-// calling thread can store a frame's rows into the slot itself.  For the ONE frame of a LaneTracker.process() call that beats the
-// copy engine: hipMemcpy2DAsync costs the call 8-24 us (by box) before the engine even starts (23 us of copy + 6 us until the
-// first kernel behind it), the stores take the bus's 20 us for the 914 KB of a 1280x720 frame's rows and the undistortion can be
-// launched the moment they are out (tools/microbench/upload_latency.hip: rows out of cold memory + a dependent kernel 66 -> 43 us;
-// NOTES_r06 E.6 for the frame).  The bytes are the same bytes; only their way differs.
-// Ordering: the stores end with an sfence and are posted writes of the thread that then rings the launch's doorbell (or of
-// threads it has waited for); the kernels behind them start with an acquire that drops what the XCDs' L2s still hold of the
-// slot's previous frame (as between any two kernels), and the memory-side cache sees the bus's writes.  In front: nothing is
-// waited for -- the aperture is taken only when the library already KNOWS the slot's readers are done (camera_rows_known_idle).
-// Up to 1.5 MB per call: the 914 KB of a 1280x720 frame's rows take the calling thread (and two polling copy threads) 25 us against
-// the engine's 8 + 29 us; the 2.0 MB of a 1920x1080 frame's take them 52-60 us against the engine's 9 + 51 us, most of which the
-// engine spends beside the mask chain's launches -- no gain there, and a busy host (tools/process_points.py, NOTES_r06 E.6).
-constexpr size_t APERTURE_MAX_BYTES = (size_t)3 << 19;
-static bool host_has_mapped(const void* p, size_t n) {
-    const uintptr_t pg = (uintptr_t)sysconf(_SC_PAGESIZE);
-    unsigned char v = 0;
-    auto mapped = [&](uintptr_t a) { return mincore((void*)(a & ~(pg - 1)), 1, &v) == 0; };
-    return n > 0 && mapped((uintptr_t)p) && mapped((uintptr_t)p + n - 1);
-}
-static bool direct_upload_possible(lt_ctx* c) {
-    if (c->direct_upload < 0)
-        c->direct_upload = c->prop.isLargeBar && c->d_frames && host_has_mapped(c->d_frames, (size_t)c->capacity * c->frame_bytes) ? 1 : 0;
-    return c->direct_upload == 1 && c->direct_upload_wanted && c->in_layout == LT_INPUT_RGB && !resizes(c);   // (4:2:0 frames take the engine; so do frames of another size: their rows go to staging)
-}
-__attribute__((target("avx2"))) static void store_stream_avx2(uint8_t* dst, const uint8_t* src, size_t n) {
-    size_t head = (32 - ((uintptr_t)dst & 31)) & 31;
-    if (head > n) head = n;
-    if (head) { std::memcpy(dst, src, head); dst += head; src += head; n -= head; }
-    size_t i = 0;
-    for (; i + 128 <= n; i += 128) {
-        const __m256i a = _mm256_loadu_si256(reinterpret_cast<const __m256i*>(src + i));
-        const __m256i b = _mm256_loadu_si256(reinterpret_cast<const __m256i*>(src + i + 32));
-        const __m256i d = _mm256_loadu_si256(reinterpret_cast<const __m256i*>(src + i + 64));
-        const __m256i e = _mm256_loadu_si256(reinterpret_cast<const __m256i*>(src + i + 96));
-        _mm256_stream_si256(reinterpret_cast<__m256i*>(dst + i), a);
-        _mm256_stream_si256(reinterpret_cast<__m256i*>(dst + i + 32), b);
-        _mm256_stream_si256(reinterpret_cast<__m256i*>(dst + i + 64), d);
-        _mm256_stream_si256(reinterpret_cast<__m256i*>(dst + i + 96), e);
-    }
-    if (i < n) std::memcpy(dst + i, src + i, n - i);
-}
-static void store_piece(uint8_t* dst, const uint8_t* src, size_t n) {
-    static const bool avx2 = __builtin_cpu_supports("avx2");
-    if (avx2) store_stream_avx2(dst, src, n);
-    else std::memcpy(dst, src, n);
-    _mm_sfence();
-}
-// One thread moves a frame's rows at what it can READ from memory the caller's frame lies cold in (30 us for 914 KB); two or three
-// reach the bus's 20 us (tools/microbench/upload_latency.hip, COLD=1).  The copy threads that are polling for work at this moment
-// (LaneTracker.process() keeps two or three of them warm with the rows of its output frames) are offered a piece each; pieces
-// nobody has claimed when the calling thread is through with its own are the calling thread's again -- no piece waits for a
-// sleeper, and none for a queue another tracker has filled.
-static void store_through_aperture(uint8_t* dst, const uint8_t* src, size_t n) {
-    const int helpers = n >= ((size_t)256 << 10) ? std::min(host_copy_pollers(), 2) : 0;
-    if (helpers <= 0) { store_piece(dst, src, n); return; }
-    struct Split {
-        std::atomic<int> claimed[3];
-        std::atomic<int> done{0};
-        uint8_t* dst; const uint8_t* src; size_t lo[4];
-        void run(int k) { store_piece(dst + lo[k], src + lo[k], lo[k + 1] - lo[k]); done.fetch_add(1, std::memory_order_release); }
-    };
-    auto sp = std::make_shared<Split>();
-    const int pieces = helpers + 1;
-    sp->dst = dst; sp->src = src;
-    for (int k = 0; k <= pieces; ++k) sp->lo[k] = k == pieces ? n : (n * (size_t)k / (size_t)pieces) & ~(size_t)127;
-    for (int k = 0; k < 3; ++k) sp->claimed[k].store(0, std::memory_order_relaxed);
-    sp->claimed[0].store(1, std::memory_order_relaxed);
-    for (int k = 1; k < pieces; ++k)
-        if (host_submit_fn(0, [sp, k] { if (!sp->claimed[k].exchange(1, std::memory_order_acq_rel)) sp->run(k); }, false) != 0) break;   // (not submitted: claimed below)
-    sp->run(0);
-    for (int k = 1; k < pieces; ++k)
-        if (!sp->claimed[k].exchange(1, std::memory_order_acq_rel)) sp->run(k);
-    // (a helper that has claimed a piece finishes it in microseconds -- unless the scheduler has taken its core: then give ours up too)
-    for (unsigned spins = 0; sp->done.load(std::memory_order_acquire) < pieces; ++spins) {
-        if ((spins & 0xffffu) == 0xffffu) std::this_thread::yield(); else __builtin_ia32_pause();
-    }
-}
-// Does the host KNOW that no kernel reads the camera rows of slots [first, first + n) any more?  Asked without a call that could
-// cost the frame anything: hipStreamQuery on a stream whose last kernel carries no signal makes the runtime enqueue a marker and
-// wait for it (measured: process() 172 -> 198 us per frame with two such queries in front of the stores) -- so the answer comes
-// from what the library has seen itself: the recorded readers' events (a query of an existing signal), and for the unrecorded
-// ones of a one-frame context the completion word the host polled at the end of the previous frame (RangeEvents::lazy_seen).
-// "Not known" is not "busy": the caller then takes the engine's stream-ordered copy, which needs no answer.
-static bool camera_rows_known_idle(lt_ctx* c, int first, int n) {
-    const lt_ctx::RangeEvents& r = c->readers;
-    if (r.overflow || r.lazy_seen != r.lazy_seq) return false;
-    for (unsigned i = 0; i < r.count; ++i) {
-        const lt_ctx::RangeEvents::Entry& w = r.e[(r.head + i) % (unsigned)r.e.size()];
-        if (w.lo < first + n && w.hi > first && hipEventQuery(w.ev) != hipSuccess) { (void)hipGetLastError(); return false; }
-    }
-    return true;
-}
-
-int lt_set_direct_upload(lt_ctx* c, int on) {
-    if (!c) return fail(LT_ERR_INVALID, "null context");
-    if (on >= 0) c->direct_upload_wanted = on != 0;
-    return direct_upload_possible(c) ? 1 : 0;
-}
-unsigned long long lt_direct_upload_count(lt_ctx* c) { return c ? c->direct_uploads : 0; }
-
-static int upload_frame_rows_impl(lt_ctx* c, const uint8_t* frames, int first, int n, bool enqueue) {
-    int rc = check_upload(c, frames, first, n);
-    if (rc || n == 0 || c->cam_r1 <= c->cam_r0) return rc;
-    // The enqueued form waits for nothing on the host: the copy goes onto the slots' own streams (behind everything launched over
-    // these slots there) and, like lt_upload_frame_rows_async's, behind the kernels of OTHER streams that still read the slots'
-    // camera rows -- overlays on the presentation stream (slot-range events).  LT_UPLOAD_SYNC=1: wait for the whole context first, as
-    // lt_upload_frame_rows does (A/B; 5-10 us of a process() frame, on its critical path).
-    static const bool enqueue_syncs = [] { const char* e = LT_EXP_ENV("LT_UPLOAD_SYNC"); return e && e[0] == '1'; }();
-    if ((!enqueue || enqueue_syncs) && (rc = sync_all(c))) return rc;
-    mark_frames(c, first, n, 0);         // a new frame's rows: the others are the previous occupant's until lt_upload_frame_rest
-    front_stale(c, first, n);
-    if (c->in_layout != LT_INPUT_RGB) {
-        // 4:2:0: the same rows of the Y plane and the chroma rows under them, into staging; nothing is converted.  The enqueued
-        // copies are noted (yuv_rows): the conversion lt_upload_frame_rest puts on the copy stream reads these rows.
-        // (raw Bayer: the rows the taps' windows touch)
-        int sr0, sr1;
-        staged_run(c, &sr0, &sr1);
-        const int c0 = chroma_lo(sr0), c1 = chroma_hi(sr0, sr1);
-        if (enqueue)
-            return for_each_slice(c, first, n, [&](hipStream_t st, int f0, int m) {
-                int wrc = enqueue_syncs ? (int)LT_OK : wait_camera_readers(c, st, f0, m);
-                if (!wrc) wrc = yuv_copy(c, frames + (size_t)(f0 - first) * c->yuv_bytes, f0, m, sr0, sr1, c0, c1, st);
-                return wrc ? wrc : note_range(c->yuv_rows, st, f0, f0 + m);
-            });
-        if ((rc = yuv_copy(c, frames, first, n, sr0, sr1, c0, c1, c->stream))) return rc;
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        return LT_OK;
-    }
-    if (resizes(c)) {
-        // another size: the source rows the path's rows read, into staging, and k_resize_rows over the path's rows right behind the copy
-        // on the same stream -- ahead of whatever is launched over the slots next.  Both are noted: the resize reads staging (the next
-        // upload into it waits), and the rest's resize on the copy stream reads rows this copy brings (yuv_rows).
-        int s0, s1;
-        rs_input_rows(c, c->cam_r0, c->cam_r1, &s0, &s1);
-        if (enqueue)
-            return for_each_slice(c, first, n, [&](hipStream_t st, int f0, int m) {
-                int wrc = enqueue_syncs ? (int)LT_OK : wait_camera_readers(c, st, f0, m);
-                if (!wrc) wrc = rs_copy(c, frames + (size_t)(f0 - first) * c->src_bytes, f0, m, s0, s1, st);
-                if (!wrc) wrc = rs_resize(c, st, f0, m, c->cam_r0, c->cam_r1);
-                if (!wrc) wrc = note_range_frame(c, c->readers, st, f0, f0 + m);
-                return wrc ? wrc : note_range_frame(c, c->yuv_rows, st, f0, f0 + m);
-            });
-        if ((rc = rs_copy(c, frames, first, n, s0, s1, c->stream))) return rc;
-        if ((rc = rs_resize(c, c->stream, first, n, c->cam_r0, c->cam_r1))) return rc;
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        return LT_OK;
-    }
-    const size_t row_bytes = (size_t)c->calib.img_w * 3, off = (size_t)c->cam_r0 * row_bytes;
-    const size_t bytes = (size_t)(c->cam_r1 - c->cam_r0) * row_bytes;
-    // (one frame, measured in round 5 against this pitched copy, 279-286 us per frame of process(): a plain copy of the contiguous
-    // run 315-320; the rows onto page-locked staging by the copy threads and an asynchronous engine copy from there 295-329, a copy
-    // kernel from there 320 -- the runtime's pageable path is the fastest of the four)
-    // enqueue (lt_upload_frame_rows_enqueue): the copy on the slots' own streams, ahead of the kernels lt_mask_run puts there, and no
-    // wait.  From the caller's pageable frame the call returns once the runtime has the bytes on their way (22-27 us for one
-    // 1280x720 frame's rows against 49-54 with the wait: the engine's 18 us run under the mask chain's launches).
-    if (enqueue && !enqueue_syncs && (size_t)n * bytes <= APERTURE_MAX_BYTES && direct_upload_possible(c) && camera_rows_known_idle(c, first, n)) {
-        // a frame or two, and nothing left on the device that reads these slots' rows: by this thread's own stores (above); the
-        // caller's array is free again when the call returns
-        for (int k = 0; k < n; ++k)
-            store_through_aperture(slot_frame(c, first + k) + off, frames + (size_t)k * c->frame_bytes + off, bytes);
-        ++c->direct_uploads;
-        return LT_OK;
-    }
-    if (enqueue)
-        return for_each_slice(c, first, n, [&](hipStream_t st, int f0, int m) {
-            if (!enqueue_syncs) {
-                const int wrc = wait_camera_readers(c, st, f0, m);
-                if (wrc) return wrc;
-            }
-            // (the rows in two to four pieces, so that the engine's copy of one runs under the runtime's staging of the next: measured
-            // SLOWER, 195-218 against 183-186 us per 1280x720 frame -- every piece pays the call again; NOTES_r06 E.2)
-            HIP_TRY(hipMemcpy2DAsync(slot_frame(c, f0) + off, c->frame_bytes, frames + off, c->frame_bytes,
-                                     bytes, (size_t)m, hipMemcpyHostToDevice, st));
-            // (where a later small call could take the aperture, this copy counts as work on the slots' rows that the host has not
-            // seen finished: stores from the host must not be overtaken by it)
-            if (c->direct_upload == 1 && (size_t)m * bytes <= APERTURE_MAX_BYTES) return note_range_frame(c, c->readers, st, f0, f0 + m);
-            return (int)LT_OK;
-        });
-    HIP_TRY(hipMemcpy2DAsync(slot_frame(c, first) + off, c->frame_bytes, frames + off, c->frame_bytes,
-                             bytes, (size_t)n, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return LT_OK;
-}
-
-int lt_upload_frame_rows(lt_ctx* c, const uint8_t* frames, int first, int n) { return upload_frame_rows_impl(c, frames, first, n, false); }
-int lt_upload_frame_rows_enqueue(lt_ctx* c, const uint8_t* frames, int first, int n) { return upload_frame_rows_impl(c, frames, first, n, true); }
-
-// Fallback of the stream-ordered uploads when the ring of readers has overflowed: `waiter` waits for the tail of every stream
-// a kernel that reads camera frames can be on -- the slots' compute streams (undistortion), the presentation stream (overlays)
-// and the urgent stream.
-static int wait_reader_tails(lt_ctx* c, hipStream_t waiter) {
-    const bool slices_only = !c->readers.overflow;     // (only `lazy`: the unrecorded readers are on the slots' streams)
-    auto tail = [&](hipStream_t st) { return !st || st == waiter ? (int)LT_OK : wait_tail(c, waiter, st); };
-    for (int i = 0; i < c->nstreams && i < (int)c->streams.size(); ++i) { const int rc = tail(c->streams[i]); if (rc) return rc; }
-    if (slices_only) return LT_OK;
-    int rc = tail(c->present);
-    if (!rc) rc = tail(c->urgent);
-    return rc;
-}
-
-// The same rows, stream-ordered instead of synchronous: the copy runs on the copy stream after the work already
-// enqueued on the streams that own these slots (their previous occupants), and those streams wait for it before
-// anything enqueued later -- so the upload of one slot range overlaps the chain of every other slot range.
-int lt_upload_frame_rows_async(lt_ctx* c, const uint8_t* frames, int first, int n) {
-    int rc = check_upload(c, frames, first, n);
-    if (rc || n == 0 || c->cam_r1 <= c->cam_r0) return rc;
-    mark_frames(c, first, n, 0);
-    front_stale(c, first, n);
-    // the copy waits for the kernels that still read these slots' camera rows (the undistortion launches over these slots, the
-    // overlay) -- not for the rest of their mask chains, and not for launches over other slots
-    if ((rc = wait_camera_readers(c, c->copy, first, n))) return rc;
-    if (c->in_layout != LT_INPUT_RGB) {
-        int sr0, sr1;
-        staged_run(c, &sr0, &sr1);
-        if ((rc = yuv_copy(c, frames, first, n, sr0, sr1, chroma_lo(sr0), chroma_hi(sr0, sr1), c->copy))) return rc;
-    } else if (resizes(c)) {
-        // another size: copy and resize both on the copy stream, the slots' streams wait for the resize
-        int s0, s1;
-        rs_input_rows(c, c->cam_r0, c->cam_r1, &s0, &s1);
-        if ((rc = rs_copy(c, frames, first, n, s0, s1, c->copy))) return rc;
-        if ((rc = rs_resize(c, c->copy, first, n, c->cam_r0, c->cam_r1))) return rc;
-    } else {
-    const size_t row_bytes = (size_t)c->calib.img_w * 3, off = (size_t)c->cam_r0 * row_bytes;
-    HIP_TRY(hipMemcpy2DAsync(slot_frame(c, first) + off, c->frame_bytes, frames + off, c->frame_bytes,
-                             (size_t)(c->cam_r1 - c->cam_r0) * row_bytes, (size_t)n, hipMemcpyHostToDevice, c->copy));
-    }
-    hipEvent_t up = next_order_event(c);
-    if (!up) return fail(LT_ERR_HIP, "hipEventCreate failed");
-    HIP_TRY(hipEventRecord(up, c->copy));
-    return for_each_slice(c, first, n, [&](hipStream_t st, int, int) {
-        HIP_TRY(hipStreamWaitEvent(st, up, 0));
-        return (int)LT_OK;
-    });
-}
-
-// 4:2:0: the copy stream waits for the enqueued uploads of source rows into the staging frames of slots [first, first + n) (the
-// synchronous form has finished, the stream-ordered one is on the copy stream itself)
-static int wait_yuv_rows(lt_ctx* c, int first, int n) {
-    bool precise = true;
-    int rc = wait_range(c->yuv_rows, c->copy, first, first + n, &precise);
-    if (!rc && !precise) rc = wait_reader_tails(c, c->copy);
-    return rc;
-}
-
-// the overlay (on the presentation stream) waits for the copies into its own slots before it reads the frames (or, when the
-// ring of slot ranges has overflowed, for the most recent copy)
-static int rest_mark(lt_ctx* c, int first, int n) {
-    if (!c->rest_done && hipEventCreateWithFlags(&c->rest_done, hipEventDisableTiming) != hipSuccess) return fail(LT_ERR_HIP, "hipEventCreate failed");
-    HIP_TRY(hipEventRecord(c->rest_done, c->copy));
-    c->rest_pending = true;
-    return note_range(c->rests, c->copy, first, first + n);
-}
-
-int lt_upload_frame_rest_rows(lt_ctx* c, const uint8_t* frames, int first, int n, const int32_t* rows4) {
-    if (!rows4) return lt_upload_frame_rest(c, frames, first, n);
-    int rc = check_upload(c, frames, first, n);
-    if (rc) return rc;
-    const int H = c->calib.img_h;
-    if (!(0 <= rows4[0] && rows4[0] <= rows4[1] && rows4[1] <= rows4[2] && rows4[2] <= rows4[3] && rows4[3] <= H))
-        return fail(LT_ERR_INVALID, "row runs must be ordered and inside the frame");
-    if (n == 0) return LT_OK;
-    if ((rc = wait_camera_readers(c, c->copy, first, n))) return rc;
-    // of the two runs, the rows lt_upload_frame_rows has not brought: below the window of rows the path reads, and above it
-    const size_t row_bytes = (size_t)c->calib.img_w * 3;
-    int lo, hi;
-    staged_run(c, &lo, &hi);
-    if (hi <= lo) lo = hi = 0;
-    if (c->in_layout != LT_INPUT_RGB) {
-        // 4:2:0: those rows of the Y plane and the chroma rows under them that the source rows' upload has not brought either, into
-        // staging; then both runs whole -- the source rows they cover included, which lt_upload_frame_rows left in staging -- as RGB
-        // into the camera frame
-        const int c0 = chroma_lo(lo), c1 = chroma_hi(lo, hi);
-        for (int k = 0; k < 4; k += 2) {
-            int ra = rows4[k], re = rows4[k + 1];
-            if (is_raw_mosaic(c->in_layout) && re > ra) ba::support_run(ra, re, H, &ra, &re);     // the rows the demosaic of the run reads
-            const int a = ra, b = std::min(re, lo), d = std::max(ra, hi), e = re;
-            if (b > a && (rc = yuv_copy(c, frames, first, n, a, b, chroma_lo(a), std::min(chroma_hi(a, b), c0), c->copy))) return rc;
-            if (e > d && (rc = yuv_copy(c, frames, first, n, d, e, std::max(chroma_lo(d), c1), chroma_hi(d, e), c->copy))) return rc;
-        }
-        if ((rc = wait_yuv_rows(c, first, n))) return rc;
-        for (int k = 0; k < 4; k += 2) yuv_convert(c, c->copy, first, n, rows4[k], rows4[k + 1]);
-        HIP_TRY(hipGetLastError());
-        if ((rc = note_range(c->readers, c->copy, first, first + n))) return rc;     // the conversion reads staging: the next upload into it waits
-        return rest_mark(c, first, n);
-    }
-    if (resizes(c)) {
-        // another size: for those rows of the two runs, the source rows they read that staging does not hold yet; then, behind the
-        // enqueued uploads of the path's source rows (the rows next to the window read some of them), their resize
-        int pieces[4][2], np = 0;
-        for (int k = 0; k < 4; k += 2) {
-            const int piece[2][2] = {{rows4[k], std::min(rows4[k + 1], lo)}, {std::max(rows4[k], hi), rows4[k + 1]}};
-            for (const auto& pc : piece)
-                if (pc[1] > pc[0]) { pieces[np][0] = pc[0]; pieces[np][1] = pc[1]; ++np; }
-        }
-        for (int i = 0; i < np; ++i)
-            if ((rc = rs_copy_for(c, frames, first, n, pieces[i][0], pieces[i][1], c->copy))) return rc;
-        if ((rc = wait_yuv_rows(c, first, n))) return rc;
-        for (int i = 0; i < np; ++i)
-            if ((rc = rs_resize(c, c->copy, first, n, pieces[i][0], pieces[i][1]))) return rc;
-        if ((rc = note_range(c->readers, c->copy, first, first + n))) return rc;     // the resize reads staging: the next upload into it waits
-        return rest_mark(c, first, n);
-    }
-    uint8_t* dst = slot_frame(c, first);
-    for (int k = 0; k < 4; k += 2) {
-        const int piece[2][2] = {{rows4[k], std::min(rows4[k + 1], lo)}, {std::max(rows4[k], hi), rows4[k + 1]}};
-        for (const auto& pc : piece) {
-            if (pc[1] <= pc[0]) continue;
-            const size_t off = (size_t)pc[0] * row_bytes, bytes = (size_t)(pc[1] - pc[0]) * row_bytes;
-            HIP_TRY(hipMemcpy2DAsync(dst + off, c->frame_bytes, frames + off, c->frame_bytes, bytes, (size_t)n, hipMemcpyHostToDevice, c->copy));
-        }
-    }
-    return rest_mark(c, first, n);
-}
-
-int lt_upload_frame_rest(lt_ctx* c, const uint8_t* frames, int first, int n) {
-    int rc = check_upload(c, frames, first, n);
-    if (rc || n == 0) return rc;
-    // these rows are read by nobody but the overlay: the copy waits for the overlays still reading the frames it replaces
-    // (slot-range events; a stream of windows re-uses its slots), and the overlay of these slots waits for it
-    if ((rc = wait_camera_readers(c, c->copy, first, n))) return rc;
-    if (c->in_layout != LT_INPUT_RGB) {
-        // 4:2:0: the rows of the Y and chroma planes that lt_upload_frame_rows has not brought into staging, then the whole frame as
-        // RGB into the camera frame, behind both copies
-        const int H = c->calib.img_h;
-        int r0, r1;
-        staged_run(c, &r0, &r1);
-        if (r1 <= r0) {
-            if ((rc = yuv_copy(c, frames, first, n, 0, H, 0, H / 2, c->copy))) return rc;
-        } else {
-            if ((rc = yuv_copy(c, frames, first, n, 0, r0, 0, chroma_lo(r0), c->copy))) return rc;
-            if ((rc = yuv_copy(c, frames, first, n, r1, H, chroma_hi(r0, r1), H / 2, c->copy))) return rc;
-            if ((rc = wait_yuv_rows(c, first, n))) return rc;
-        }
-        yuv_convert(c, c->copy, first, n, 0, H);
-        HIP_TRY(hipGetLastError());
-        if ((rc = note_range(c->readers, c->copy, first, first + n))) return rc;     // the conversion reads staging: the next upload into it waits
-        mark_frames(c, first, n, 1);
-        return rest_mark(c, first, n);
-    }
-    if (resizes(c)) {
-        // another size: the source rows the rows above and below the path's window read and staging does not hold yet, then those rows
-        // resized into the camera frame, behind both copies
-        const int H = c->calib.img_h, r0 = c->cam_r1 > c->cam_r0 ? c->cam_r0 : 0, r1 = c->cam_r1 > c->cam_r0 ? c->cam_r1 : 0;
-        if (r1 <= r0) {
-            if ((rc = rs_copy(c, frames, first, n, 0, c->src_h, c->copy))) return rc;
-            if ((rc = rs_resize(c, c->copy, first, n, 0, H))) return rc;
-        } else {
-            if ((rc = rs_copy_for(c, frames, first, n, 0, r0, c->copy))) return rc;
-            if ((rc = rs_copy_for(c, frames, first, n, r1, H, c->copy))) return rc;
-            if ((rc = wait_yuv_rows(c, first, n))) return rc;
-            if ((rc = rs_resize(c, c->copy, first, n, 0, r0))) return rc;
-            if ((rc = rs_resize(c, c->copy, first, n, r1, H))) return rc;
-        }
-        if ((rc = note_range(c->readers, c->copy, first, first + n))) return rc;     // the resize reads staging: the next upload into it waits
-        mark_frames(c, first, n, 1);
-        return rest_mark(c, first, n);
-    }
-    const size_t row_bytes = (size_t)c->calib.img_w * 3;
-    const size_t head = (size_t)c->cam_r0 * row_bytes, tail0 = (size_t)c->cam_r1 * row_bytes;
-    uint8_t* dst = slot_frame(c, first);
-    if (c->cam_r1 <= c->cam_r0) {
-        HIP_TRY(hipMemcpyAsync(dst, frames, (size_t)n * c->frame_bytes, hipMemcpyHostToDevice, c->copy));
-        mark_frames(c, first, n, 1);
-        return rest_mark(c, first, n);
-    }
-    if (head)
-        HIP_TRY(hipMemcpy2DAsync(dst, c->frame_bytes, frames, c->frame_bytes, head, (size_t)n, hipMemcpyHostToDevice, c->copy));
-    if (tail0 < c->frame_bytes)
-        HIP_TRY(hipMemcpy2DAsync(dst + tail0, c->frame_bytes, frames + tail0, c->frame_bytes, c->frame_bytes - tail0, (size_t)n,
-                                 hipMemcpyHostToDevice, c->copy));
-    mark_frames(c, first, n, 1);
-    return rest_mark(c, first, n);
 }
 
 // ---- frames that are already in device memory ------------------------------------------------------------------------------------
@@ -1860,31 +1384,6 @@ int lt_attach_device_frames(lt_ctx* c, const lt_device_surface* surfaces, int fi
         HIP_TRY(hipGetLastError());
         return (int)LT_OK;
     });
-}
-
-int lt_device_frames_rest(lt_ctx* c, int first, int n, const int32_t* rows4) {
-    int rc = check_slots(c, first, n);
-    if (rc) return rc;
-    for (int i = first; i < first + n; ++i)
-        if (i >= (int)c->attached.size() || !c->attached[(size_t)i])
-            return fail(LT_ERR_STATE, i < (int)c->drawn.size() && c->drawn[(size_t)i] ? "slot %d: its surface was drawn into in place (lt_overlay_run_inplace) and holds no camera frame any more"
-                                                                                      : "slot %d has no device frame attached", i);
-    const int H = c->calib.img_h;
-    if (rows4 && !(0 <= rows4[0] && rows4[0] <= rows4[1] && rows4[1] <= rows4[2] && rows4[2] <= rows4[3] && rows4[3] <= H))
-        return fail(LT_ERR_INVALID, "row runs must be ordered and inside the frame");
-    if (n == 0) return LT_OK;
-    if ((rc = set_device(c))) return rc;
-    // as lt_upload_frame_rest: on the copy stream, behind the overlays that still read the camera frames these rows replace
-    if ((rc = wait_camera_readers(c, c->copy, first, n))) return rc;
-    const int32_t whole[4] = {0, H, H, H};
-    const int32_t* r = rows4 ? rows4 : whole;
-    for (int k = 0; k < 4; k += 2)
-        launch_surf_rows_to_rgb(c->copy, c->in_layout, &c->surf[(size_t)first], yuv_coef_of(c), slot_frame(c, first), c->frame_bytes,
-                                c->calib.img_h, c->calib.img_w, r[k], r[k + 1], n, raw_stages_of(c));
-    HIP_TRY(hipGetLastError());
-    if ((rc = note_range(c->readers, c->copy, first, first + n))) return rc;      // it reads the surfaces and writes the camera frames: the next upload waits
-    if (!rows4) mark_frames(c, first, n, 1);
-    return rest_mark(c, first, n);
 }
 
 int lt_upload_masks(lt_ctx* c, const uint8_t* masks, int first, int n) {
@@ -2844,25 +2343,6 @@ int lt_search_fit_list(lt_ctx* c, int n, const lt_search_item* items, const lt_s
         HIP_TRY(hipStreamWaitEvent(c->streams[(size_t)si], done, 0));
     }
     return LT_OK;
-}
-
-// the pointer-list forms: frames[k] into slot first + k by the one-frame form, once the whole list is checked
-static int upload_list(lt_ctx* c, const uint8_t* const* frames, int first, int n, const char* what,
-                       int (*one)(lt_ctx*, const uint8_t*, int, int)) {
-    int rc = check_slots(c, first, n);
-    if (rc) return rc;
-    if (n > 0 && !frames) return fail(LT_ERR_INVALID, "null frame list");
-    for (int k = 0; k < n; ++k)
-        if (!frames[k]) return fail(LT_ERR_INVALID, "%s: frame %d is null", what, k);
-    for (int k = 0; k < n; ++k)
-        if ((rc = one(c, frames[k], first + k, 1))) return rc;
-    return LT_OK;
-}
-int lt_upload_frame_rows_list(lt_ctx* c, const uint8_t* const* frames, int first, int n) {
-    return upload_list(c, frames, first, n, "lt_upload_frame_rows_list", lt_upload_frame_rows_enqueue);
-}
-int lt_upload_frame_rest_list(lt_ctx* c, const uint8_t* const* frames, int first, int n) {
-    return upload_list(c, frames, first, n, "lt_upload_frame_rest_list", lt_upload_frame_rest);
 }
 
 int lt_set_urgent(lt_ctx* c, int on) {

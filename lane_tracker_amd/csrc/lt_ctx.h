@@ -1,5 +1,6 @@
 // The context behind the C ABI (struct lt_ctx) and the helpers its translation units share:
-//   lt_api.cpp     -- create / destroy / reserve, uploads, downloads, the searches, measurement
+//   lt_api.cpp     -- create / destroy / reserve, input format and size, downloads, the searches, measurement
+//   lt_ingest.cpp  -- host frames into slots: lt_upload_frames, the row and rest uploads, lt_device_frames_rest (direct, staged, resized)
 //   lt_mask_chain.cpp -- the mask chain (top-hats, thresholds, merge + 5x5 open) and the arena that owns its device memory
 //   lt_memory.cpp  -- device-memory cache, page-locked host memory, the host copy threads
 //   lt_present.cpp -- presentation stage: lane overlay, text, annotated frames on their way back
@@ -416,6 +417,7 @@ inline int packed_bpp(int layout) {
 inline int one_plane_row_bytes(int layout, int w) { return raw_packing(layout) >= 0 ? raw_wide_row_bytes(layout, w) : packed_bpp(layout) * w; }
 inline uint8_t* slot_yuv(const lt_ctx* c, int s) { return c->d_yuv + (size_t)s * c->yuv_stride; }
 inline uint8_t* slot_src(const lt_ctx* c, int s) { return c->d_src + (size_t)s * c->src_stride; }
+inline bool resizes(const lt_ctx* c) { return c->src_w > 0; }   // the caller's frames have another size (lt_set_input_size)
 inline YuvCoef yuv_coef_of(const lt_ctx* c) { return YuvCoef{c->yuv_coef[0], c->yuv_coef[1], c->yuv_coef[2], c->yuv_coef[3], c->yuv_coef[4]}; }
 inline uint8_t* slot_mask(const lt_ctx* c, int s) { return c->masks.d_plane[P_MASK] + (size_t)s * c->masks.plane_bytes; }
 // the opened bit plane of slot s as the searches take it; use_bits = false: none (they read slot_mask)
@@ -595,6 +597,10 @@ int ensure_band_sums(lt_ctx* c, int nbands);
 int prepare_search(lt_ctx* c, const lt_search_params* p, bool band, SearchGeom& g);
 bool slot_reads_bits(const lt_ctx* c, const SearchGeom& g, int mode, int first, int n);
 void mark_frames(lt_ctx* c, int first, int n, int full);
+void front_stale(lt_ctx* c, int first, int n);                  // new camera rows in these slots: their planes are the old frames'
+void detach_slots(lt_ctx* c, int first, int n);                 // an upload into these slots: their front end reads the slots' own frames again
+int wait_camera_readers(lt_ctx* c, hipStream_t st, int first, int n);   // `st` waits for the kernels that still read the camera rows of these slots
+int wait_reader_tails(lt_ctx* c, hipStream_t waiter);           // ... for the tail of every stream such a kernel can be on
 void mark_annot(lt_ctx* c, int first, int n, int full);
 int first_partial(const std::vector<uint8_t>& v, int first, int n);
 // A plane of a caller's surface, checked on the host before anything is launched (lt_attach_device_frames, the device sinks): device
