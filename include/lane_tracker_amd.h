@@ -375,6 +375,41 @@ int  lt_get_raw_shading_plane(lt_ctx* ctx, uint16_t* plane /* img_h * img_w */);
 int  lt_raw_to_rgb_shaded(lt_ctx* ctx, const void* frame, int h, int w, int layout, const uint8_t* lut /* 4 * lut_entries bytes, or NULL */, size_t lut_entries,
                           const int16_t* ccm /* 9, or NULL */, const uint8_t* curve /* 256, or NULL */, const uint16_t* mesh /* or NULL: no map */, int mesh_w, int mesh_h,
                           const int32_t* black /* 4; NULL: zeros */, uint8_t* out_rgb);
+/* Raw Bayer STATISTICS: the measuring half of the raw front end -- what an auto-exposure, black-level or auto-white-balance step between
+ * windows reads before it builds the next raw table (lt_set_raw_lut / _wide).  lt_raw_stats takes them of what slots [first_slot, first_slot
+ * + n) hold -- the attached surfaces where a slot has them, the slot's staging frame otherwise -- on the device, of the samples AS THEY ENTER
+ * THE RAW TABLE: the byte (layouts 16 .. 19), the word masked to its low `bits` (32 .. 35, 48 .. 51), the unpacked sample (36 .. 39, 52 ..
+ * 55), each taken through the shading map first where one is set (s' above).  Table, demosaic and colour stage play no part: white-balance
+ * gains live in the table, so this is where a loop measures.  With p the phase of a site (0 R, 1 Gr, 2 Gb, 3 B, as the raw table's rows),
+ * smax = 2^bits - 1 and bins = 256 / 1 << bits:
+ *     rectangle   rows [row0, row1), columns [col0, col1), all even, inside the frame, not empty.  row1 == 0: the default rows -- the run
+ *                 lt_get_input_rows names, which every upload entry point brings, rounded inward to even: (r0 + 1) & ~1, r1 & ~1 --;
+ *                 col1 == 0: [0, img_w).  It is tiled by 2 x 2 cells anchored at even coordinates -- one site of each phase a cell --:
+ *                 ncy = (row1 - row0) / 2 by ncx = (col1 - col0) / 2 cells.
+ *     hist        uint32[n][4][bins]: hist[p][v] = the sites of phase p in the rectangle whose sample is v.  Every site counts.
+ *     zones       a grid of grid_h x grid_w, 1 <= grid_h <= min(64, ncy), 1 <= grid_w <= min(64, ncx); cell (cy, cx), counted inside the
+ *                 rectangle, lies in zone (cy * grid_h / ncy, cx * grid_w / ncx) (integer division).  A cell is VALID when all four of its
+ *                 samples satisfy lo[p] <= s_p <= hi[p] (each bound 0 .. smax; lo > hi is legal: no valid cell).
+ *     zone_count  uint32[n][grid_h][grid_w]: the valid cells of the zone.
+ *     zone_sum    uint64[n][grid_h][grid_w][4]: the per-phase sums of the samples of the zone's valid cells.
+ * Bit for bit utils.raw_stats (NumPy), whatever the order the device adds in: every quantity is an integer.  Any of the three outputs may
+ * be NULL; rect, if not NULL, receives the rectangle used.  Like lt_set_raw_lut it waits for everything the context has in flight, runs on
+ * the context's stream and the host waits for it: an occasional call, NOT a per-frame one.  Its device scratch is allocated by the first
+ * call and freed with the context.  It changes nothing a later call reads: staging, camera frames, planes, records, lt_last_* answers and
+ * attachments are as before.  LT_ERR_STATE in a context whose input format is not raw Bayer, and for a rectangle with rows outside the
+ * default run while one of the slots holds only the rows the path reads (lt_upload_frame_rows without the rest; attached slots are whole);
+ * LT_ERR_INVALID for NULL params, odd or out-of-frame bounds, a grid outside its limits, a bound outside 0 .. smax or a slot range outside
+ * the capacity; n == 0 is LT_OK.  Not built: statistics behind the table or the demosaic, focus statistics, statistics inside a running
+ * stream. */
+typedef struct lt_raw_stats_params {
+    int32_t row0, row1;      /* even; row1 == 0: the default rows */
+    int32_t col0, col1;      /* even; col1 == 0: [0, img_w) */
+    int32_t grid_h, grid_w;  /* 1 .. 64, at most the rectangle's cells per axis */
+    int32_t lo[4], hi[4];    /* by phase, 0 .. smax */
+} lt_raw_stats_params;
+int  lt_raw_stats(lt_ctx* ctx, int first_slot, int n, const lt_raw_stats_params* p, uint32_t* hist /* n * 4 * bins, or NULL */,
+                  uint32_t* zone_count /* n * grid_h * grid_w, or NULL */, uint64_t* zone_sum /* n * grid_h * grid_w * 4, or NULL */,
+                  int32_t rect[4] /* out: row0, row1, col0, col1 used; may be NULL */);
 /* Frames of another SIZE than the calibration's: a context with an input size of src_w x src_h takes RGB frames of src_h * src_w * 3
  * bytes and resizes them on the device to img_w x img_h -- cv2.resize(frame, (img_w, img_h)) with the default INTER_LINEAR, bit for bit:
  * half-pixel centres, 11-bit coefficients, OpenCV's two-stage rounding.  Everything the context computes, keeps and hands out is what a

@@ -94,6 +94,12 @@ class Info(C.Structure):
                 ("alg_bytes_search", C.c_int64), ("device_name", C.c_char * 64)]
 
 
+class RawStatsParams(C.Structure):
+    """lt_raw_stats_params: the rectangle, the zone grid and the validity bounds (by colour phase) of a statistics call."""
+    _fields_ = [("row0", C.c_int32), ("row1", C.c_int32), ("col0", C.c_int32), ("col1", C.c_int32), ("grid_h", C.c_int32), ("grid_w", C.c_int32),
+                ("lo", C.c_int32 * 4), ("hi", C.c_int32 * 4)]
+
+
 # name -> (restype, argtypes); every symbol include/lane_tracker_amd.h declares
 _P = C.c_void_p
 _SIGNATURES = {
@@ -250,6 +256,7 @@ _SIGNATURES = {
     "lt_get_raw_shading": (C.c_int, [_P, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), _P, C.POINTER(C.c_int)]),
     "lt_get_raw_shading_plane": (C.c_int, [_P, _P]),
     "lt_raw_to_rgb_shaded": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, C.c_size_t, _P, _P, _P, C.c_int, C.c_int, _P, _P]),
+    "lt_raw_stats": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(RawStatsParams), _P, _P, _P, _P]),
     "lt_attach_device_frames": (C.c_int, [_P, _P, C.c_int, C.c_int]),
     "lt_device_frames_rest": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "lt_device_alloc": (C.c_int, [C.c_int, C.c_size_t, C.POINTER(C.c_void_p)]),
@@ -472,6 +479,23 @@ def checked_raw_shading(shading, pixel_format):
     if pixel_format not in RAW_FORMATS:
         raise ValueError("raw_shading corrects raw Bayer frames: pixel_format=%r takes none" % (pixel_format,))
     return _checked(shading, raw_bits(pixel_format))
+
+
+def default_stats_rows(input_rows):
+    """The default rows of a statistics call: the run (r0, r1) the uploads bring (`Context.input_rows`), rounded inward to even."""
+    return (int(input_rows[0]) + 1) & ~1, int(input_rows[1]) & ~1
+
+
+def checked_raw_stats(pixel_format, img_size, input_rows, grid=(8, 8), rows=None, cols=None, lo=None, hi=None):
+    """The arguments of `Context.raw_stats` / `LaneTracker.raw_stats` as the lt_raw_stats_params the library takes -- the rectangle written
+    out, never the defaults' zeros; ValueError -- before any device call -- for a pixel format that is not raw Bayer, odd, empty or
+    out-of-frame bounds, a grid side outside 1 .. 64 or above the rectangle's cells, a bound outside 0 .. 2**bits - 1.  `input_rows`: the run
+    the uploads bring (`Context.input_rows()`), whose inward rounding to even rows is the default for rows=None."""
+    if pixel_format not in RAW_FORMATS:
+        raise ValueError("raw statistics are taken of raw Bayer frames: pixel_format=%r has none" % (pixel_format,))
+    from .utils import checked_raw_stats_args
+    r, c, g, lo, hi = checked_raw_stats_args(img_size, raw_bits(pixel_format), default_stats_rows(input_rows), grid, rows, cols, lo, hi)
+    return RawStatsParams(r[0], r[1], c[0], c[1], g[0], g[1], (C.c_int32 * 4)(*[int(v) for v in lo]), (C.c_int32 * 4)(*[int(v) for v in hi]))
 
 
 def checked_input_size(input_size, img_size, pixel_format="rgb"):
@@ -1097,6 +1121,24 @@ class Context:
         out = np.empty((self.img_h, self.img_w), np.uint16)
         _check(self.lib.lt_get_raw_shading_plane(self._h, out.ctypes.data))
         return out
+
+    def raw_stats(self, n, first=0, grid=(8, 8), rows=None, cols=None, lo=None, hi=None):
+        """Statistics of the raw Bayer frames slots first .. first + n hold -- the attached surfaces where a slot has them, what was uploaded
+        otherwise --, of the samples as they enter the raw table, behind the context's shading map where it has one (lt_raw_stats): what
+        `utils.raw_stats` defines, bit for bit, as a `utils.RawStats` with a leading frame axis.  rows=None: the rows every upload brings
+        (`input_rows()`, rounded inward to even); other rows need whole frames in the slots (upload_frames, attached frames).  Waits for the
+        context's outstanding work: an occasional call, not a per-frame one.  The arguments are checked before any device call (ValueError)."""
+        from .utils import RawStats
+        n, first = int(n), int(first)
+        if n < 0 or first < 0 or first + n > self.capacity:
+            raise ValueError("slots [%d, %d) outside the context's capacity %d" % (first, first + n, self.capacity))
+        p = checked_raw_stats(self._pixel_format, (self.img_w, self.img_h), self.input_rows(), grid, rows, cols, lo, hi)
+        zones = (p.grid_h, p.grid_w)
+        hist = np.zeros((n, 4, max(1 << raw_bits(self._pixel_format), 256)), np.uint32)
+        count, total = np.zeros((n,) + zones, np.uint32), np.zeros((n,) + zones + (4,), np.uint64)
+        rect = np.zeros(4, np.int32)
+        _check(self.lib.lt_raw_stats(self._h, first, n, C.byref(p), hist.ctypes.data, count.ctypes.data, total.ctypes.data, rect.ctypes.data))
+        return RawStats(hist, count, total, (int(rect[0]), int(rect[1])), (int(rect[2]), int(rect[3])))
 
     def raw_to_rgb_shaded(self, frame, pattern, shading, raw_lut=None, ccm=None, curve=None):
         """`raw_to_rgb_color` behind the shading map `shading` (lt_raw_to_rgb_shaded); without `ccm` and `curve`: no colour stage."""

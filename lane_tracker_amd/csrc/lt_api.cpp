@@ -29,6 +29,7 @@
 #include "lt_ctx.h"
 #include "resize_arith.h"
 #include "shade_arith.h"
+#include "stats_arith.h"
 
 using namespace lt;
 
@@ -752,6 +753,7 @@ void lt_destroy(lt_ctx* c) {
     dev_free(c->d_raw_lut_wide);
     dev_free(c->d_raw_cc);
     dev_free(c->d_raw_gain);
+    dev_free(c->d_stats);
     dev_free(c->d_oxy);
     dev_free(c->d_ofrac);
     for (size_t i = 1; i < c->cal.size(); ++i) {     // (set 0's tables are the ones above)
@@ -1189,6 +1191,76 @@ int lt_get_raw_shading_plane(lt_ctx* c, uint16_t* plane) {
     int rc;
     if ((rc = set_device(c))) return rc;
     HIP_TRY(hipMemcpy(plane, c->d_raw_gain, (size_t)c->calib.img_h * c->calib.img_w * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    return LT_OK;
+}
+
+// ---- raw statistics (lt_raw_stats) ---------------------------------------------------------------------------------------------
+// Occasional, like lt_set_raw_lut: behind everything the context has in flight, on the context's stream, and the host waits for it.  It
+// reads the slots' frames and writes its own scratch: nothing a later call reads changes.
+int lt_raw_stats(lt_ctx* c, int first, int n, const lt_raw_stats_params* p, uint32_t* hist, uint32_t* zone_count, uint64_t* zone_sum, int32_t* rect) {
+    if (!c) return fail(LT_ERR_INVALID, "null context");
+    if (!is_raw_mosaic(c->in_layout)) return fail(LT_ERR_STATE, "raw statistics are taken of raw Bayer input: this context's input format is another layout");
+    if (!p) return fail(LT_ERR_INVALID, "null parameters");
+    if (first < 0 || n < 0 || first > c->capacity || n > c->capacity - first)
+        return fail(LT_ERR_INVALID, "slots [%d, %d) outside reserved capacity %d", first, first + n, c->capacity);
+    const int H = c->calib.img_h, W = c->calib.img_w, bits = is_bayer_wide(c->in_layout) ? raw_bits(c->in_layout) : 8, smax = (1 << bits) - 1;
+    int in0 = 0, in1 = 0, d0 = 0, d1 = 0, rc;
+    if ((rc = lt_get_input_rows(c, &in0, &in1))) return rc;
+    st::default_rows(in0, in1, &d0, &d1);
+    const int row0 = p->row1 == 0 ? d0 : p->row0, row1 = p->row1 == 0 ? d1 : p->row1;
+    const int col0 = p->col1 == 0 ? 0 : p->col0, col1 = p->col1 == 0 ? W : p->col1;
+    if (((row0 | row1 | col0 | col1) & 1) || row0 < 0 || row0 >= row1 || row1 > H || col0 < 0 || col0 >= col1 || col1 > W)
+        return fail(LT_ERR_INVALID, "rows [%d, %d), columns [%d, %d): a rectangle of statistics has even bounds inside the %d x %d frame and is not empty",
+                    row0, row1, col0, col1, W, H);
+    const int ncy = (row1 - row0) / 2, ncx = (col1 - col0) / 2;
+    if (p->grid_h < 1 || p->grid_h > std::min(st::GRID_MAX, ncy) || p->grid_w < 1 || p->grid_w > std::min(st::GRID_MAX, ncx))
+        return fail(LT_ERR_INVALID, "a grid of %d x %d zones: each side is 1 .. 64 and at most the rectangle's %d x %d cells", p->grid_w, p->grid_h, ncx, ncy);
+    for (int k = 0; k < 4; ++k)
+        if (p->lo[k] < 0 || p->lo[k] > smax || p->hi[k] < 0 || p->hi[k] > smax)
+            return fail(LT_ERR_INVALID, "lo[%d] = %d, hi[%d] = %d: the bounds of %d-bit samples lie in 0 .. %d", k, (int)p->lo[k], k, (int)p->hi[k], bits, smax);
+    auto is_attached = [&](int i) { return i < (int)c->attached.size() && c->attached[(size_t)i] != 0; };
+    if (row0 < in0 || row1 > in1)
+        for (int i = first; i < first + n; ++i)
+            if (!is_attached(i) && !(i < (int)c->frame_full.size() && c->frame_full[(size_t)i]))
+                return fail(LT_ERR_STATE, "slot %d holds only the rows the path reads, [%d, %d): rows [%d, %d) were never uploaded into it", i, in0, in1, row0, row1);
+    if (rect) rect[0] = row0, rect[1] = row1, rect[2] = col0, rect[3] = col1;
+    if (n == 0) return LT_OK;
+    if ((rc = set_device(c))) return rc;
+    if ((rc = sync_all(c))) return rc;
+    const size_t bins = (size_t)1 << bits, zones = (size_t)p->grid_h * p->grid_w;
+    const size_t sum_bytes = (size_t)n * zones * 4 * sizeof(uint64_t), hist_bytes = (size_t)n * 4 * bins * sizeof(uint32_t),
+                 count_bytes = (size_t)n * zones * sizeof(uint32_t), need = sum_bytes + hist_bytes + count_bytes;
+    if (need > c->stats_bytes) {
+        dev_free(c->d_stats);
+        c->stats_bytes = 0;
+        if ((rc = dev_alloc(&c->d_stats, need))) return rc;
+        c->stats_bytes = need;
+    }
+    RawStatsJob job{};
+    job.pattern = c->in_layout & 3, job.bits = bits, job.pack = raw_packing(c->in_layout);
+    job.img_w = W;
+    job.row0 = row0, job.col0 = col0, job.ncy = ncy, job.ncx = ncx, job.grid_h = p->grid_h, job.grid_w = p->grid_w;
+    for (int k = 0; k < 4; ++k) job.lo[k] = p->lo[k], job.hi[k] = p->hi[k];
+    job.gains = c->raw_shade_set ? c->d_raw_gain : nullptr;
+    job.blk = c->raw_black;
+    unsigned long long* d_sum = reinterpret_cast<unsigned long long*>(c->d_stats);
+    uint32_t* d_hist = reinterpret_cast<uint32_t*>(c->d_stats + sum_bytes);
+    uint32_t* d_count = reinterpret_cast<uint32_t*>(c->d_stats + sum_bytes + hist_bytes);
+    HIP_TRY(hipMemsetAsync(c->d_stats, 0, need, c->stream));
+    for (int a = first; a < first + n;) {                        // runs of slots with one kind of source
+        int b = a + 1;
+        while (b < first + n && is_attached(b) == is_attached(a)) ++b;
+        job.zone_sum = d_sum + (size_t)(a - first) * zones * 4;
+        job.hist = d_hist + (size_t)(a - first) * 4 * bins;
+        job.zone_count = d_count + (size_t)(a - first) * zones;
+        launch_raw_stats(c->stream, is_attached(a) ? FrameSource::surfaces(c->d_surf) : FrameSource::slots(slot_yuv(c, a), c->yuv_stride), a, b - a, job);
+        a = b;
+    }
+    HIP_TRY(hipGetLastError());
+    if (zone_sum) HIP_TRY(hipMemcpyAsync(zone_sum, d_sum, sum_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (hist) HIP_TRY(hipMemcpyAsync(hist, d_hist, hist_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (zone_count) HIP_TRY(hipMemcpyAsync(zone_count, d_count, count_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return LT_OK;
 }
 

@@ -189,6 +189,10 @@ struct lt_ctx {
     int raw_mesh_w = 0, raw_mesh_h = 0;
     lt::RawShadeBlack raw_black = {};             // the pedestals, by colour phase
     uint16_t* d_raw_gain = nullptr;
+    // The device scratch of lt_raw_stats: the zone sums, histograms and zone counts of the call's slots, allocated by the first call (grown by
+    // one that needs more), freed with the context.
+    uint8_t* d_stats = nullptr;
+    size_t stats_bytes = 0;
     // Input frames of another size (lt_set_input_size): src_w x src_h RGB frames, resized on the device to the calibration's size
     // (cv2.resize, INTER_LINEAR).  Per slot a staging frame of src_bytes = src_h * src_w * 3 bytes, src_stride apart (a multiple of 16
     // with at least 16 bytes of padding behind every frame: k_resize_rows reads aligned dwords); the uploads copy source rows into it

@@ -81,6 +81,22 @@ struct RawStages {
 };
 // mesh (device memory, uint16[4][mh][mw], phase-major) -> the gain plane of an h x w image whose layout has `pattern` (k_shade_expand)
 void launch_shade_expand(hipStream_t s, const uint16_t* mesh, int mw, int mh, int pattern, uint16_t* plane, int h, int w);
+// Raw Bayer statistics (lt_raw_stats; k_raw_stats.hip, stats_arith.h): histograms and zone sums of the samples of slots [first_slot,
+// first_slot + n) as they enter the raw table, ADDED to hist / zone_count / zone_sum (device memory, zeroed by the caller; per slot 4 << bits
+// (8 bits: 1024) / grid_h * grid_w / 4 * grid_h * grid_w values apart, the launch's first slot at the pointers).  The frames: src.tab -- the
+// surface table, entries [first_slot, first_slot + n) -- or src.frames, the staging frame of first_slot, src.stride bytes a slot.  The
+// rectangle is ncy x ncx cells of 2 x 2 sites from (row0, col0), all even and inside the frame; 1 <= grid_h <= min(64, ncy), likewise grid_w;
+// lo / hi by phase; gains not null: the shading map's plane (RawStages::gains) and its pedestals blk.
+struct RawStatsJob {
+    int pattern, bits, pack;                 // layout & 3; 8, 10 or 12; raw_pack(layout)
+    int img_w;
+    int row0, col0, ncy, ncx, grid_h, grid_w;
+    int32_t lo[4], hi[4];
+    const uint16_t* gains = nullptr;
+    RawShadeBlack blk = {};
+    uint32_t *hist = nullptr, *zone_count = nullptr;
+    unsigned long long* zone_sum = nullptr;
+};
 // rows [r0, r1) of n dense frames of h x w in `layout` (any but 0; the layouts: launch_undistort_rows) -> the same rows of n RGB frames
 // (k_rows_to_rgb<layout, false, ..>; behind a raw table k_raw_rows_rgb<pattern, false, ..>)
 void launch_yuv_rows_to_rgb(hipStream_t s, int layout, const uint8_t* yuv, size_t yuv_stride, YuvCoef k, uint8_t* rgb,
@@ -113,6 +129,7 @@ struct FrameSource {
     static FrameSource slots(const uint8_t* frames, size_t stride) { return FrameSource{nullptr, frames, stride}; }
     static FrameSource surfaces(const SurfEntry* tab) { return FrameSource{tab, nullptr, 0}; }
 };
+void launch_raw_stats(hipStream_t s, FrameSource src, int first_slot, int n, const RawStatsJob& job);      // (RawStatsJob: above)
 // The 10- / 12-bit raw Bayer layouts (32 .. 35, 48 .. 51; pattern = layout & 3): the bits of a sample, 0 for every other layout.  Their frames
 // are one plane of 16-bit little-endian words and they are always launched with a table (RawStages).
 // Layouts 36 .. 39 / 52 .. 55 (bit 2 set) are the same samples MIPI-packed, one plane of bytes: raw_pack says which packing (mipi_arith.h), -1: none.

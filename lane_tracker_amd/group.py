@@ -55,6 +55,7 @@ class _GroupMember(LaneTracker):
     set_raw_lut = _not_owned        # (one table for the whole group: LaneTrackerGroup.set_raw_lut)
     set_raw_color = _not_owned      # (... and one colour stage: LaneTrackerGroup.set_raw_color)
     set_raw_shading = _not_owned    # (... and one lens-shading map: LaneTrackerGroup.set_raw_shading)
+    raw_stats = _not_owned          # (it uploads into slots: statistics are a tracker's, not a group member's)
     _owns_context = False           # close() leaves the group's context to LaneTrackerGroup.close
 
 

@@ -241,6 +241,57 @@ class LaneTracker(StreamPipeline):
         self._raw_shading = shading
         self._resident = None       # the camera frame the slot holds was converted with the map before
 
+    def raw_stats(self, frames, grid=(8, 8), rows=None, cols=None, lo=None, hi=None):
+        """Statistics of raw Bayer frames -- one frame, a stack, or `DeviceFrames`, in the tracker's pixel format -- taken on the device, of the
+        samples as they enter the raw table (behind the tracker's shading map, in front of its table): per-colour histograms and a grid of
+        per-colour sums over the cells inside [lo, hi] -- `utils.raw_stats` is the definition, this is it bit for bit -- as a
+        `utils.RawStats`.  rows=None: the rows the tracker's uploads bring (the road), rounded inward to even; cols=None: every column.  What
+        an auto-white-balance step between windows measures: `t.set_raw_lut(utils.raw_lut(black, white, utils.awb_gains(s, black), gamma,
+        bits))`.  Host frames are uploaded (the rows alone where the rectangle lies inside them), frames in device memory are attached and
+        read where they lie; a stack longer than the context's capacity goes in pieces.  It waits for the device and touches no tracking
+        state; not a per-frame call, and not allowed inside an active `process_stream()`.  ValueError for a tracker whose pixel format is
+        not raw Bayer, frames of another shape or dtype, and arguments outside their ranges."""
+        if not _native.raw_bits(self.pixel_format):
+            raise ValueError("raw statistics are taken of raw Bayer frames: a %r tracker has none" % (self.pixel_format,))
+        if self._in_stream:
+            raise RuntimeError("raw_stats() inside an active process_stream(): exhaust or close the generator first")
+        on_device = isinstance(frames, DeviceFrames)
+        if on_device:
+            single = frames.single
+            self._check_frame(frames, window=True)
+        else:
+            single = getattr(frames, "ndim", None) == len(self._frame_shape)
+            self._check_frame(frames, window=not single)
+            frames = _native.frames_array(frames, self.pixel_format).reshape((-1,) + tuple(self._frame_shape))
+        ctx = self._ctx
+        run = ctx.input_rows()
+        p = _native.checked_raw_stats(self.pixel_format, self.img_size, run, grid, rows, cols, lo, hi)      # (before anything is uploaded)
+        inside = run[0] <= p.row0 and p.row1 <= run[1]
+        self._all_copies_done()
+        self._resident = None       # the slots hold these frames now
+        parts, n, step = [], len(frames), max(int(ctx.capacity), 1)
+        for at in range(0, n, step):
+            piece = frames[at:at + step]
+            if on_device:
+                self._rows_keepalive = ctx.attach_device_frames(piece, first=0)
+            elif inside:
+                ctx.upload_frame_rows(piece, first=0)
+            else:
+                ctx.upload_frames(piece, first=0)
+            parts.append(ctx.raw_stats(len(piece), 0, (p.grid_h, p.grid_w), (p.row0, p.row1), (p.col0, p.col1), list(p.lo), list(p.hi)))
+        if on_device:
+            self._rows_keepalive = frames        # (the last piece's slots stay attached until an upload replaces the frames)
+        from .utils import RawStats
+        join = lambda k: np.concatenate([q[k] for q in parts]) if parts else None
+        if not parts:
+            bins = 1 << _native.raw_bits(self.pixel_format)
+            hist, count, total = np.zeros((0, 4, bins), np.uint32), np.zeros((0, p.grid_h, p.grid_w), np.uint32), np.zeros((0, p.grid_h, p.grid_w, 4), np.uint64)
+        else:
+            hist, count, total = join(0), join(1), join(2)
+        if single:
+            hist, count, total = hist[0], count[0], total[0]
+        return RawStats(hist, count, total, (p.row0, p.row1), (p.col0, p.col1))
+
     def _check_frame(self, img, window=False):
         """A 4:2:0 / 4:2:2 tracker takes frames of its own shape only (nothing is uploaded before this has been looked at); an RGB tracker
         takes what it always took.  Frames in device memory (device.DeviceFrames) must be the tracker's size and pixel format."""

@@ -505,6 +505,132 @@ def apply_raw_shading(frames, pattern, shading):
     return np.clip(b + (((s - b) * gain + 2048) >> 12), 0, smax).astype(dtype)
 
 
+RawStats = collections.namedtuple("RawStats", "hist zone_count zone_sum rows cols")
+RawStats.__doc__ = """Raw Bayer statistics (`utils.raw_stats`, `LaneTracker.raw_stats`): `hist` uint32 (4, bins) -- per colour phase (0 red sites, 1
+green on red rows, 2 green on blue rows, 3 blue sites) the number of sites of the rectangle with each sample value --, `zone_count` uint32
+(grid_h, grid_w) -- the valid 2 x 2 cells of each zone --, `zone_sum` uint64 (grid_h, grid_w, 4) -- the per-phase sums of their samples --,
+each with a leading frame axis for a stack; `rows` = (row0, row1) and `cols` = (col0, col1), the rectangle they were taken of."""
+_GRID_MAX = 64
+
+
+def _raw_stats_format(pixel_format):
+    """-> (the 16-bit or 8-bit format the samples are in once unpacked, pattern p, bits) of one of the twelve raw formats."""
+    fmt = pixel_format.replace("p_", "_", 1) if pixel_format in _BAYER_PACKED_PATTERNS else pixel_format
+    p, bits, _ = _pattern_bits(fmt)
+    return fmt, p, bits
+
+
+def checked_raw_stats_args(img_size, bits, default_rows, grid=(8, 8), rows=None, cols=None, lo=None, hi=None):
+    """The arguments of a statistics call over frames of `img_size` = (W, H) with `bits`-bit samples, checked and filled in:
+    -> ((row0, row1), (col0, col1), (grid_h, grid_w), lo int32 (4,), hi int32 (4,)).  rows=None: `default_rows`; cols=None: (0, W); lo / hi: one
+    integer or four (by phase), None: 0 / 2**bits - 1.  ValueError for odd, empty or out-of-frame bounds, a grid side outside 1 .. 64 or above
+    the rectangle's cells, a bound outside 0 .. 2**bits - 1."""
+    w, h = int(img_size[0]), int(img_size[1])
+    smax = (1 << bits) - 1
+
+    def span(v, default, n, what):
+        if v is None:
+            v = default
+        try:
+            a, b = (int(t) for t in v)
+            exact = all(int(t) == t for t in v)
+        except (TypeError, ValueError):
+            raise ValueError("%s is a pair of integers, got %r" % (what, v)) from None
+        if not exact or a % 2 or b % 2 or not 0 <= a < b <= n:
+            raise ValueError("%s = %r: both bounds are even, 0 <= first < last <= %d" % (what, tuple(v), n))
+        return a, b
+    r, c = span(rows, default_rows, h, "rows"), span(cols, (0, w), w, "cols")
+    ncy, ncx = (r[1] - r[0]) // 2, (c[1] - c[0]) // 2
+    try:
+        gh, gw = (int(t) for t in grid)
+        exact = all(int(t) == t for t in grid)
+    except (TypeError, ValueError):
+        raise ValueError("grid is (grid_h, grid_w), got %r" % (grid,)) from None
+    if not exact or not (1 <= gh <= min(_GRID_MAX, ncy) and 1 <= gw <= min(_GRID_MAX, ncx)):
+        raise ValueError("grid = %r: each side is 1 .. %d and at most the rectangle's cells, %d x %d (rows x columns)" % (tuple(grid), _GRID_MAX, ncy, ncx))
+
+    def bounds(v, default, what):
+        b = np.asarray(default if v is None else v)
+        if b.dtype.kind not in "iu" or b.shape not in ((), (4,)):
+            raise ValueError("%s is one integer or four (R, Gr, Gb, B), got %r" % (what, v))
+        b = np.broadcast_to(b, (4,)).astype(np.int64)
+        if b.min() < 0 or b.max() > smax:
+            raise ValueError("%s of %d-bit samples lies in 0 .. %d, got %r" % (what, bits, smax, v))
+        return b.astype(np.int32)
+    return r, c, (gh, gw), bounds(lo, 0, "lo"), bounds(hi, smax, "hi")
+
+
+def raw_stats(frames, pixel_format, grid=(8, 8), rows=None, cols=None, lo=None, hi=None, shading=None):
+    """Statistics of raw Bayer frames -- one frame or a stack, in any of the twelve raw formats (u8 (H, W) for 'bayer_*', uint16 for 'bayer10_*' /
+    'bayer12_*', u8 packed rows for 'bayer10p_*' / 'bayer12p_*') -- of the samples AS THEY ENTER THE RAW TABLE: the byte, the word masked to its
+    bits, the unpacked sample (`unpack_raw`); with `shading` (a `utils.RawShading`) that sample taken through `apply_raw_shading`.  Table,
+    demosaic and colour stage play no part: white-balance gains live in the table, so this is where an auto-white-balance loop measures.
+
+    The rectangle: rows [row0, row1), columns [col0, col1), all even (None: the whole frame -- a tracker's `raw_stats` defaults to the rows its
+    uploads bring), tiled by 2 x 2 cells anchored at even coordinates: ncy = (row1 - row0) // 2 by ncx = (col1 - col0) // 2 cells, each with one
+    site of every phase p (0 R, 1 Gr, 2 Gb, 3 B: `apply_raw_lut`'s).  With smax = 2**bits - 1 and bins = 256 / 2**bits:
+
+        hist[p][v]        uint32 (4, bins): the sites of phase p in the rectangle whose sample is v; every site counts
+        zone of a cell    (cy * grid_h // ncy, cx * grid_w // ncx), `grid` = (grid_h, grid_w), 1 <= grid_h <= min(64, ncy), likewise grid_w
+        a cell is valid   when all four of its samples satisfy lo[p] <= s_p <= hi[p] (one integer or four; None: 0 / smax; lo > hi: no cell)
+        zone_count        uint32 (grid_h, grid_w): the valid cells of the zone
+        zone_sum          uint64 (grid_h, grid_w, 4): the per-phase sums of the samples of the zone's valid cells
+
+    -> RawStats(hist, zone_count, zone_sum, rows, cols), the arrays with a leading frame axis for a stack.  NumPy only.  This is the definition:
+    `Context.raw_stats` / `LaneTracker.raw_stats` compute the same on the device, bit for bit."""
+    fmt, p, bits = _raw_stats_format(pixel_format)
+    a = unpack_raw(frames, pixel_format) if pixel_format in _BAYER_PACKED_PATTERNS else np.asarray(frames)
+    dtype = np.uint8 if bits == 8 else np.uint16
+    if a.dtype != dtype or a.ndim not in (2, 3):
+        raise ValueError("%s frames are %s arrays (H, W) or (n, H, W), got %s %r" % (pixel_format, np.dtype(dtype), a.dtype, a.shape))
+    h, w = a.shape[-2:]
+    if h % 2 or w % 2 or h < 2 or w < 2:
+        raise ValueError("a raw Bayer frame has an even height and width, got %r" % (a.shape,))
+    smax, bins = (1 << bits) - 1, 1 << bits
+    (row0, row1), (col0, col1), (gh, gw), lo, hi = checked_raw_stats_args((w, h), bits, (0, h), grid, rows, cols, lo, hi)
+    s = (apply_raw_shading(a, fmt, shading) if shading is not None else a).astype(np.int64) & smax
+    s = s.reshape((-1, h, w))[:, row0:row1, col0:col1]
+    n, ncy, ncx = s.shape[0], (row1 - row0) // 2, (col1 - col0) // 2
+    hist = np.zeros((n, 4, bins), np.uint32)
+    site, valid = [None] * 4, np.ones((n, ncy, ncx), bool)
+    for py in range(2):
+        for px in range(2):
+            ph = 2 * (py ^ (p >> 1)) + (px ^ (p & 1))
+            site[ph] = s[:, py::2, px::2]
+            for k in range(n):
+                hist[k, ph] = np.bincount(site[ph][k].ravel(), minlength=bins)
+            valid &= (site[ph] >= int(lo[ph])) & (site[ph] <= int(hi[ph]))
+    # the zones are runs of consecutive cells along each axis, none empty (grid <= cells): sums over runs, in integers
+    y0 = np.searchsorted(np.arange(ncy) * gh // ncy, np.arange(gh))
+    x0 = np.searchsorted(np.arange(ncx) * gw // ncx, np.arange(gw))
+    over_zones = lambda v: np.add.reduceat(np.add.reduceat(v.astype(np.uint64), y0, axis=1), x0, axis=2)
+    zone_count = over_zones(valid).astype(np.uint32)
+    zone_sum = np.stack([over_zones(np.where(valid, site[ph], 0)) for ph in range(4)], axis=-1)
+    if a.ndim == 2:
+        hist, zone_count, zone_sum = hist[0], zone_count[0], zone_sum[0]
+    return RawStats(hist, zone_count, zone_sum, (row0, row1), (col0, col1))
+
+
+def awb_gains(stats, black_level=0):
+    """The grey-world step that closes the loop: the white-balance gains (R, G, B) that make the means of `stats` (a RawStats, of one frame or a
+    stack: all valid cells of all frames count) grey.  With the pedestal `black_level` -- one integer or four (R, Gr, Gb, B) --, per phase
+    m_p = sum_p / count - black_p and g = (m_1 + m_2) / 2: -> (g / m_0, 1.0, g / m_3), floats: the `gains=` argument of `utils.raw_lut`.
+    ValueError when no cell is valid or a mean is not above the pedestal."""
+    b = np.asarray(black_level)
+    if b.dtype.kind not in "iu" or b.shape not in ((), (4,)):
+        raise ValueError("black_level is one integer or four (R, Gr, Gb, B), got %r" % (black_level,))
+    black = [int(v) for v in np.broadcast_to(b, (4,))]
+    count = int(np.asarray(stats.zone_count, np.uint64).sum())
+    if count == 0:
+        raise ValueError("no valid cell: the statistics hold no sample to balance on")
+    sums = [int(v) for v in np.asarray(stats.zone_sum, np.uint64).reshape(-1, 4).sum(axis=0)]
+    m = [sums[p] / count - black[p] for p in range(4)]
+    if min(m) <= 0:
+        raise ValueError("a colour's mean is not above its black level: means %r over black %r" % ([sums[p] / count for p in range(4)], black))
+    g = (m[1] + m[2]) / 2
+    return (g / m[0], 1.0, g / m[3])
+
+
 def bayer_to_rgb_color(frame, pattern, raw_lut=None, ccm=None, curve=None, shading=None):
     """A raw Bayer frame (H, W) or a stack (n, H, W) in any of the raw patterns -- u8 for 'bayer_*', uint16 for 'bayer10_*' /
     'bayer12_*', u8 packed rows (H, W * 5 // 4) / (H, W * 3 // 2) for 'bayer10p_*' / 'bayer12p_*' -- to RGB with the colour stage, on the device: every sample looked up in `raw_lut` (8-bit: u8 (4, 256), None: no
