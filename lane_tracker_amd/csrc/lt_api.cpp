@@ -24,12 +24,9 @@
 
 #include <hip/hip_ext.h>
 
-#include "bayer_arith.h"
 #include "front_arith.h"
 #include "lt_ctx.h"
 #include "resize_arith.h"
-#include "shade_arith.h"
-#include "stats_arith.h"
 
 using namespace lt;
 
@@ -749,10 +746,7 @@ void lt_destroy(lt_ctx* c) {
     dev_free(c->d_coef);
     dev_free(c->d_rs_xt);
     dev_free(c->d_rs_yt);
-    dev_free(c->d_raw_lut);
-    dev_free(c->d_raw_lut_wide);
-    dev_free(c->d_raw_cc);
-    dev_free(c->d_raw_gain);
+    raw_release(c->raw_dev);
     dev_free(c->d_stats);
     dev_free(c->d_oxy);
     dev_free(c->d_ofrac);
@@ -910,74 +904,6 @@ static int check_yuv_format(int layout, const int32_t* k, int h, int w) {
     return LT_OK;
 }
 
-// 8-bit raw Bayer: whole 2 x 2 blocks, and a 4 x 4 window of bytes (the neighbourhoods of a sample's four taps) inside the plane
-static int check_bayer_size(int h, int w) {
-    if (h < 4 || w < 4 || (h & 1) || (w & 1)) return fail(LT_ERR_INVALID, "raw Bayer frames need an even width and height of at least 4, got %dx%d", w, h);
-    return LT_OK;
-}
-// ... of `layout`: MIPI-packed RAW10 holds four sites in five bytes, so a row is whole groups
-static int check_raw_size(int layout, int h, int w) {
-    const int rc = check_bayer_size(h, w);
-    if (rc) return rc;
-    if (raw_packing(layout) == 0 && (w & 3)) return fail(LT_ERR_INVALID, "MIPI-packed RAW10 frames need a width that is a multiple of 4, got %dx%d", w, h);
-    return LT_OK;
-}
-
-// 10- / 12-bit raw Bayer.  The default table: full scale to full scale, rounded -- utils.raw_lut(bits=..) with its defaults, in integers
-// (floor(255 s / m + 1 / 2) = (510 s + m) / (2 m), m = 2^bits - 1).
-static void default_wide_table(int bits, uint8_t* lut) {
-    const uint32_t n = 1u << bits, m = n - 1u;
-    for (uint32_t p = 0; p < 4; ++p)
-        for (uint32_t v = 0; v < n; ++v) lut[p * n + v] = (uint8_t)((510u * v + m) / (2u * m));
-}
-static int write_wide_table(lt_ctx* c, const uint8_t* lut) {
-    HIP_TRY(hipMemcpy(c->d_raw_lut_wide, lut, c->raw_lut_wide.size(), hipMemcpyHostToDevice));
-    if (lut != c->raw_lut_wide.data()) std::memcpy(c->raw_lut_wide.data(), lut, c->raw_lut_wide.size());
-    return LT_OK;
-}
-// the table of a context that is about to take `layout`: allocated once at the layout's size, the default in it
-static int install_wide_table(lt_ctx* c, int layout) {
-    const size_t bytes = (size_t)4 << raw_bits(layout);
-    int rc;
-    if (c->raw_lut_wide.size() != bytes) {
-        dev_free(c->d_raw_lut_wide);
-        c->raw_lut_wide.clear();
-    }
-    if (!c->d_raw_lut_wide && (rc = dev_alloc(&c->d_raw_lut_wide, bytes / 4))) return rc;
-    c->raw_lut_wide.resize(bytes);
-    default_wide_table(raw_bits(layout), c->raw_lut_wide.data());
-    return write_wide_table(c, c->raw_lut_wide.data());
-}
-
-// What a raw kernel of `layout` stages (RawStages::table), on the host: the 256 bytes of `curve` (null: no colour stage, none), then the
-// table -- `lut`, or where that is null the 8-bit identity / the 10- and 12-bit default.
-static std::vector<uint8_t> staged_table(int layout, const uint8_t* lut, const uint8_t* curve) {
-    const size_t head = curve ? 256 : 0, bytes = is_bayer_wide(layout) ? (size_t)4 << raw_bits(layout) : 1024;
-    std::vector<uint8_t> t(head + bytes);
-    if (curve) std::memcpy(t.data(), curve, 256);
-    if (lut) std::memcpy(t.data() + head, lut, bytes);
-    else if (is_bayer_wide(layout)) default_wide_table(raw_bits(layout), t.data() + head);
-    else for (size_t i = 0; i < bytes; ++i) t[head + i] = (uint8_t)(i & 255u);
-    return t;
-}
-// the context's output curve and the table its layout is conditioned with, into d_raw_cc; nothing in flight
-static int write_raw_color(lt_ctx* c) {
-    const std::vector<uint8_t> t = staged_table(c->in_layout, is_bayer_wide(c->in_layout) ? c->raw_lut_wide.data() : c->raw_lut_set ? c->raw_lut : nullptr,
-                                                c->raw_curve);
-    int rc;
-    if (c->raw_cc_bytes != t.size()) {
-        dev_free(c->d_raw_cc);
-        c->raw_cc_bytes = 0;
-    }
-    if (!c->d_raw_cc && (rc = dev_alloc(&c->d_raw_cc, t.size() / 4))) return rc;
-    c->raw_cc_bytes = t.size();
-    HIP_TRY(hipMemcpy(c->d_raw_cc, t.data(), t.size(), hipMemcpyHostToDevice));
-    return LT_OK;
-}
-
-static int write_identity_lut(lt_ctx* c);              // (lens shading, below)
-static void drop_raw_shading(lt_ctx* c);
-
 int lt_set_input_format(lt_ctx* c, int layout, const int32_t* coeffs) {
     if (!c) return fail(LT_ERR_INVALID, "null context");
     int rc;
@@ -999,15 +925,12 @@ int lt_set_input_format(lt_ctx* c, int layout, const int32_t* coeffs) {
         return fail(LT_ERR_STATE, "a context with an input size (lt_set_input_size) takes RGB frames only: frames of another format are not resized");
     if ((rc = set_device(c))) return rc;
     if ((rc = sync_all(c))) return rc;
-    if (!is_bayer(layout)) c->raw_lut_set = false;     // a raw table belongs to raw Bayer input
-    c->raw_color_set = false;                          // ... and a colour stage to the layout it was set for
-    drop_raw_shading(c);                               // ... as a shading map does
+    if ((rc = raw_take_layout(c, layout))) return rc;  // (table, colour stage, shading map: before anything else of the context changes)
     if (layout == LT_INPUT_RGB) {
         dev_free(c->d_yuv);
     } else {
         // the staging frame of a slot: h w 3 / 2 bytes (4:2:0), h w 2 (4:2:2), h w 3 (BGR), h w 4 (RGBA / BGRA), h w (raw Bayer), 2 h w (10- /
         // 12-bit raw Bayer) or 5 h w / 4, 3 h w / 2 (the same MIPI-packed), slots a multiple of 16 apart
-        if (is_bayer_wide(layout) && (rc = install_wide_table(c, layout))) return rc;     // (before anything of the context changes)
         const size_t row = (size_t)one_plane_row_bytes(layout, c->calib.img_w);
         const size_t bytes = row ? (size_t)c->calib.img_h * row : c->frame_bytes / 2, stride = (bytes + 15) & ~(size_t)15;
         if (stride != c->yuv_stride) dev_free(c->d_yuv);
@@ -1015,259 +938,12 @@ int lt_set_input_format(lt_ctx* c, int layout, const int32_t* coeffs) {
         c->yuv_stride = stride;
         if (c->capacity > 0 && !c->d_yuv && (rc = dev_alloc(&c->d_yuv, (size_t)c->capacity * c->yuv_stride + 16))) {
             c->in_layout = LT_INPUT_RGB;     // (no staging: the context falls back to what needs none)
+            (void)raw_take_layout(c, LT_INPUT_RGB);
             return rc;
         }
         if (!plain) std::memcpy(c->yuv_coef, coeffs, sizeof c->yuv_coef);
     }
     c->in_layout = layout;
-    return LT_OK;
-}
-
-// The raw table: set-up or occasional (between windows), behind everything the context has in flight; what is launched afterwards reads
-// the new one.  Planes and camera frames computed with the old one stay what they are: the slots' front ends are marked as not run, so
-// that a re-run (lt_mask_rerun) computes them again.
-int lt_set_raw_lut(lt_ctx* c, const uint8_t* lut) {
-    if (!c) return fail(LT_ERR_INVALID, "null context");
-    if (is_bayer_wide(c->in_layout)) return fail(LT_ERR_STATE, "a 10- / 12-bit raw Bayer context takes its table through lt_set_raw_lut_wide");
-    if (!is_bayer(c->in_layout)) return fail(LT_ERR_STATE, "a raw table conditions raw Bayer input: this context's input format is another layout");
-    int rc;
-    if ((rc = set_device(c))) return rc;
-    if ((rc = sync_all(c))) return rc;
-    if (lut) {
-        if (!c->d_raw_lut && (rc = dev_alloc(&c->d_raw_lut, 256))) return rc;
-        HIP_TRY(hipMemcpy(c->d_raw_lut, lut, sizeof c->raw_lut, hipMemcpyHostToDevice));
-        std::memcpy(c->raw_lut, lut, sizeof c->raw_lut);
-    }
-    c->raw_lut_set = lut != nullptr;
-    std::fill(c->front_ok.begin(), c->front_ok.end(), (uint8_t)0);
-    if (!lut && c->raw_shade_set && (rc = write_identity_lut(c))) return rc;       // (the raw kernels always stage a table)
-    return c->raw_color_set ? write_raw_color(c) : LT_OK;       // (with a colour stage the kernels stage the table from its buffer)
-}
-
-int lt_get_raw_lut(lt_ctx* c, uint8_t* lut, int* is_set) {
-    if (!c) return fail(LT_ERR_INVALID, "null context");
-    if (is_set) *is_set = c->raw_lut_set ? 1 : 0;
-    if (lut && c->raw_lut_set) std::memcpy(lut, c->raw_lut, sizeof c->raw_lut);
-    return LT_OK;
-}
-
-static int check_wide(lt_ctx* c, size_t entries) {
-    if (!c) return fail(LT_ERR_INVALID, "null context");
-    if (!is_bayer_wide(c->in_layout)) return fail(LT_ERR_STATE, "a wide raw table belongs to 10- / 12-bit raw Bayer input: this context's input format is another layout");
-    if (entries != (size_t)1 << raw_bits(c->in_layout))
-        return fail(LT_ERR_INVALID, "a %d-bit raw table has %d entries per colour phase, got %zu", raw_bits(c->in_layout), 1 << raw_bits(c->in_layout), entries);
-    return LT_OK;
-}
-// As lt_set_raw_lut: behind everything in flight, and the slots' front ends are marked as not run.
-int lt_set_raw_lut_wide(lt_ctx* c, const uint8_t* lut, size_t entries) {
-    int rc = check_wide(c, entries);
-    if (rc) return rc;
-    if ((rc = set_device(c))) return rc;
-    if ((rc = sync_all(c))) return rc;
-    if (lut) rc = write_wide_table(c, lut);
-    else {
-        default_wide_table(raw_bits(c->in_layout), c->raw_lut_wide.data());
-        rc = write_wide_table(c, c->raw_lut_wide.data());
-    }
-    std::fill(c->front_ok.begin(), c->front_ok.end(), (uint8_t)0);
-    if (rc == LT_OK && c->raw_color_set) rc = write_raw_color(c);
-    return rc;
-}
-
-// The colour stage: as the raw table, a setting between runs -- behind everything in flight, and the slots' front ends are marked as not
-// run.  enable = 0 removes it (ccm and curve are not read).
-int lt_set_raw_color(lt_ctx* c, const int16_t* ccm, const uint8_t* curve, int enable) {
-    if (!c) return fail(LT_ERR_INVALID, "null context");
-    if (!is_raw_mosaic(c->in_layout)) return fail(LT_ERR_STATE, "a colour stage follows the demosaic of raw Bayer input: this context's input format is another layout");
-    int rc;
-    if ((rc = set_device(c))) return rc;
-    if ((rc = sync_all(c))) return rc;
-    if (enable) {
-        static const int16_t ident[9] = {1024, 0, 0, 0, 1024, 0, 0, 0, 1024};
-        std::memcpy(c->raw_ccm, ccm ? ccm : ident, sizeof c->raw_ccm);
-        for (int i = 0; i < 256; ++i) c->raw_curve[i] = curve ? curve[i] : (uint8_t)i;
-        if ((rc = write_raw_color(c))) return rc;
-    }
-    c->raw_color_set = enable != 0;
-    std::fill(c->front_ok.begin(), c->front_ok.end(), (uint8_t)0);
-    return LT_OK;
-}
-
-int lt_get_raw_color(lt_ctx* c, int16_t* ccm, uint8_t* curve, int* is_set) {
-    if (!c) return fail(LT_ERR_INVALID, "null context");
-    if (is_set) *is_set = c->raw_color_set ? 1 : 0;
-    if (ccm && c->raw_color_set) std::memcpy(ccm, c->raw_ccm, sizeof c->raw_ccm);
-    if (curve && c->raw_color_set) std::memcpy(curve, c->raw_curve, sizeof c->raw_curve);
-    return LT_OK;
-}
-
-// ---- lens shading (lt_set_raw_shading) ---------------------------------------------------------------------------------------
-static int check_shading(int layout, int mesh_w, int mesh_h, const int32_t* black) {
-    if (mesh_w < sa::MESH_MIN || mesh_w > sa::MESH_MAX || mesh_h < sa::MESH_MIN || mesh_h > sa::MESH_MAX)
-        return fail(LT_ERR_INVALID, "a shading mesh has 2 .. 64 nodes a side, got %d x %d", mesh_w, mesh_h);
-    const int smax = is_bayer_wide(layout) ? (1 << raw_bits(layout)) - 1 : 255;
-    for (int p = 0; black && p < 4; ++p)
-        if (black[p] < 0 || black[p] > smax) return fail(LT_ERR_INVALID, "black[%d] = %d is outside 0 .. %d", p, (int)black[p], smax);
-    return LT_OK;
-}
-// mesh (host) -> a gain plane of h x w sites and 16 bytes of padding at *plane (device memory, allocated here where it is null), on `st`
-static int expand_mesh(hipStream_t st, const uint16_t* mesh, int mesh_w, int mesh_h, int layout, int h, int w, uint16_t** plane) {
-    const size_t nodes = (size_t)4 * mesh_w * mesh_h;
-    uint16_t* d_mesh = nullptr;
-    int rc;
-    if ((rc = dev_alloc(&d_mesh, nodes))) return rc;
-    if (!*plane && (rc = dev_alloc(plane, (size_t)h * w + 8))) { dev_free(d_mesh); return rc; }
-    hipError_t e = hipMemcpyAsync(d_mesh, mesh, nodes * sizeof(uint16_t), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemsetAsync(*plane + (size_t)h * w, 0, 16, st);
-    if (e == hipSuccess) {
-        launch_shade_expand(st, d_mesh, mesh_w, mesh_h, layout & 3, *plane, h, w);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    dev_free(d_mesh);
-    if (e != hipSuccess) return fail(LT_ERR_HIP, "expanding the shading mesh failed: %s", hipGetErrorString(e));
-    return LT_OK;
-}
-// the identity table into d_raw_lut: what the raw kernels of an 8-bit context with a map and without a raw table stage; nothing in flight
-static int write_identity_lut(lt_ctx* c) {
-    int rc;
-    if (!c->d_raw_lut && (rc = dev_alloc(&c->d_raw_lut, 256))) return rc;
-    const std::vector<uint8_t> ident = staged_table(LT_INPUT_BAYER_RGGB, nullptr, nullptr);
-    HIP_TRY(hipMemcpy(c->d_raw_lut, ident.data(), ident.size(), hipMemcpyHostToDevice));
-    return LT_OK;
-}
-static void drop_raw_shading(lt_ctx* c) {
-    c->raw_shade_set = false;
-    dev_free(c->d_raw_gain);
-    c->raw_black = {};
-    c->raw_mesh.clear();
-    c->raw_mesh_w = c->raw_mesh_h = 0;
-}
-
-// The shading map: as the colour stage, a setting between runs -- behind everything in flight, and the slots' front ends are marked as not
-// run.  enable = 0 removes it (mesh and black are not read) and frees the gain plane.
-int lt_set_raw_shading(lt_ctx* c, const uint16_t* mesh, int mesh_w, int mesh_h, const int32_t* black, int enable) {
-    if (!c) return fail(LT_ERR_INVALID, "null context");
-    if (!is_raw_mosaic(c->in_layout)) return fail(LT_ERR_STATE, "lens shading corrects raw Bayer input: this context's input format is another layout");
-    int rc;
-    if (enable) {
-        if (!mesh) return fail(LT_ERR_INVALID, "null mesh");
-        if ((rc = check_shading(c->in_layout, mesh_w, mesh_h, black))) return rc;
-    }
-    if ((rc = set_device(c))) return rc;
-    if ((rc = sync_all(c))) return rc;
-    if (enable) {
-        if (is_bayer(c->in_layout) && !c->raw_lut_set && (rc = write_identity_lut(c))) return rc;
-        if ((rc = expand_mesh(c->stream, mesh, mesh_w, mesh_h, c->in_layout, c->calib.img_h, c->calib.img_w, &c->d_raw_gain))) {
-            // the plane of a map that was set may hold part of the new one by now: no map is better than one the host and the device disagree on
-            drop_raw_shading(c);
-            std::fill(c->front_ok.begin(), c->front_ok.end(), (uint8_t)0);
-            return rc;
-        }
-        c->raw_mesh.assign(mesh, mesh + (size_t)4 * mesh_w * mesh_h);
-        c->raw_mesh_w = mesh_w, c->raw_mesh_h = mesh_h;
-        for (int p = 0; p < 4; ++p) c->raw_black.b[p] = black ? black[p] : 0;
-        c->raw_shade_set = true;
-    } else {
-        drop_raw_shading(c);
-    }
-    std::fill(c->front_ok.begin(), c->front_ok.end(), (uint8_t)0);
-    return LT_OK;
-}
-
-int lt_get_raw_shading(lt_ctx* c, uint16_t* mesh, int* mesh_w, int* mesh_h, int32_t* black, int* is_set) {
-    if (!c) return fail(LT_ERR_INVALID, "null context");
-    if (is_set) *is_set = c->raw_shade_set ? 1 : 0;
-    if (mesh_w) *mesh_w = c->raw_mesh_w;
-    if (mesh_h) *mesh_h = c->raw_mesh_h;
-    if (mesh && c->raw_shade_set) std::memcpy(mesh, c->raw_mesh.data(), c->raw_mesh.size() * sizeof(uint16_t));
-    if (black && c->raw_shade_set) std::memcpy(black, c->raw_black.b, sizeof c->raw_black.b);
-    return LT_OK;
-}
-
-int lt_get_raw_shading_plane(lt_ctx* c, uint16_t* plane) {
-    if (!c || !plane) return fail(LT_ERR_INVALID, "null argument");
-    if (!c->raw_shade_set) return fail(LT_ERR_STATE, "this context has no shading map (lt_set_raw_shading)");
-    int rc;
-    if ((rc = set_device(c))) return rc;
-    HIP_TRY(hipMemcpy(plane, c->d_raw_gain, (size_t)c->calib.img_h * c->calib.img_w * sizeof(uint16_t), hipMemcpyDeviceToHost));
-    return LT_OK;
-}
-
-// ---- raw statistics (lt_raw_stats) ---------------------------------------------------------------------------------------------
-// Occasional, like lt_set_raw_lut: behind everything the context has in flight, on the context's stream, and the host waits for it.  It
-// reads the slots' frames and writes its own scratch: nothing a later call reads changes.
-int lt_raw_stats(lt_ctx* c, int first, int n, const lt_raw_stats_params* p, uint32_t* hist, uint32_t* zone_count, uint64_t* zone_sum, int32_t* rect) {
-    if (!c) return fail(LT_ERR_INVALID, "null context");
-    if (!is_raw_mosaic(c->in_layout)) return fail(LT_ERR_STATE, "raw statistics are taken of raw Bayer input: this context's input format is another layout");
-    if (!p) return fail(LT_ERR_INVALID, "null parameters");
-    if (first < 0 || n < 0 || first > c->capacity || n > c->capacity - first)
-        return fail(LT_ERR_INVALID, "slots [%d, %d) outside reserved capacity %d", first, first + n, c->capacity);
-    const int H = c->calib.img_h, W = c->calib.img_w, bits = is_bayer_wide(c->in_layout) ? raw_bits(c->in_layout) : 8, smax = (1 << bits) - 1;
-    int in0 = 0, in1 = 0, d0 = 0, d1 = 0, rc;
-    if ((rc = lt_get_input_rows(c, &in0, &in1))) return rc;
-    st::default_rows(in0, in1, &d0, &d1);
-    const int row0 = p->row1 == 0 ? d0 : p->row0, row1 = p->row1 == 0 ? d1 : p->row1;
-    const int col0 = p->col1 == 0 ? 0 : p->col0, col1 = p->col1 == 0 ? W : p->col1;
-    if (((row0 | row1 | col0 | col1) & 1) || row0 < 0 || row0 >= row1 || row1 > H || col0 < 0 || col0 >= col1 || col1 > W)
-        return fail(LT_ERR_INVALID, "rows [%d, %d), columns [%d, %d): a rectangle of statistics has even bounds inside the %d x %d frame and is not empty",
-                    row0, row1, col0, col1, W, H);
-    const int ncy = (row1 - row0) / 2, ncx = (col1 - col0) / 2;
-    if (p->grid_h < 1 || p->grid_h > std::min(st::GRID_MAX, ncy) || p->grid_w < 1 || p->grid_w > std::min(st::GRID_MAX, ncx))
-        return fail(LT_ERR_INVALID, "a grid of %d x %d zones: each side is 1 .. 64 and at most the rectangle's %d x %d cells", p->grid_w, p->grid_h, ncx, ncy);
-    for (int k = 0; k < 4; ++k)
-        if (p->lo[k] < 0 || p->lo[k] > smax || p->hi[k] < 0 || p->hi[k] > smax)
-            return fail(LT_ERR_INVALID, "lo[%d] = %d, hi[%d] = %d: the bounds of %d-bit samples lie in 0 .. %d", k, (int)p->lo[k], k, (int)p->hi[k], bits, smax);
-    auto is_attached = [&](int i) { return i < (int)c->attached.size() && c->attached[(size_t)i] != 0; };
-    if (row0 < in0 || row1 > in1)
-        for (int i = first; i < first + n; ++i)
-            if (!is_attached(i) && !(i < (int)c->frame_full.size() && c->frame_full[(size_t)i]))
-                return fail(LT_ERR_STATE, "slot %d holds only the rows the path reads, [%d, %d): rows [%d, %d) were never uploaded into it", i, in0, in1, row0, row1);
-    if (rect) rect[0] = row0, rect[1] = row1, rect[2] = col0, rect[3] = col1;
-    if (n == 0) return LT_OK;
-    if ((rc = set_device(c))) return rc;
-    if ((rc = sync_all(c))) return rc;
-    const size_t bins = (size_t)1 << bits, zones = (size_t)p->grid_h * p->grid_w;
-    const size_t sum_bytes = (size_t)n * zones * 4 * sizeof(uint64_t), hist_bytes = (size_t)n * 4 * bins * sizeof(uint32_t),
-                 count_bytes = (size_t)n * zones * sizeof(uint32_t), need = sum_bytes + hist_bytes + count_bytes;
-    if (need > c->stats_bytes) {
-        dev_free(c->d_stats);
-        c->stats_bytes = 0;
-        if ((rc = dev_alloc(&c->d_stats, need))) return rc;
-        c->stats_bytes = need;
-    }
-    RawStatsJob job{};
-    job.pattern = c->in_layout & 3, job.bits = bits, job.pack = raw_packing(c->in_layout);
-    job.img_w = W;
-    job.row0 = row0, job.col0 = col0, job.ncy = ncy, job.ncx = ncx, job.grid_h = p->grid_h, job.grid_w = p->grid_w;
-    for (int k = 0; k < 4; ++k) job.lo[k] = p->lo[k], job.hi[k] = p->hi[k];
-    job.gains = c->raw_shade_set ? c->d_raw_gain : nullptr;
-    job.blk = c->raw_black;
-    unsigned long long* d_sum = reinterpret_cast<unsigned long long*>(c->d_stats);
-    uint32_t* d_hist = reinterpret_cast<uint32_t*>(c->d_stats + sum_bytes);
-    uint32_t* d_count = reinterpret_cast<uint32_t*>(c->d_stats + sum_bytes + hist_bytes);
-    HIP_TRY(hipMemsetAsync(c->d_stats, 0, need, c->stream));
-    for (int a = first; a < first + n;) {                        // runs of slots with one kind of source
-        int b = a + 1;
-        while (b < first + n && is_attached(b) == is_attached(a)) ++b;
-        job.zone_sum = d_sum + (size_t)(a - first) * zones * 4;
-        job.hist = d_hist + (size_t)(a - first) * 4 * bins;
-        job.zone_count = d_count + (size_t)(a - first) * zones;
-        launch_raw_stats(c->stream, is_attached(a) ? FrameSource::surfaces(c->d_surf) : FrameSource::slots(slot_yuv(c, a), c->yuv_stride), a, b - a, job);
-        a = b;
-    }
-    HIP_TRY(hipGetLastError());
-    if (zone_sum) HIP_TRY(hipMemcpyAsync(zone_sum, d_sum, sum_bytes, hipMemcpyDeviceToHost, c->stream));
-    if (hist) HIP_TRY(hipMemcpyAsync(hist, d_hist, hist_bytes, hipMemcpyDeviceToHost, c->stream));
-    if (zone_count) HIP_TRY(hipMemcpyAsync(zone_count, d_count, count_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return LT_OK;
-}
-
-int lt_get_raw_lut_wide(lt_ctx* c, uint8_t* lut, size_t entries) {
-    int rc = check_wide(c, entries);
-    if (rc) return rc;
-    if (lut) std::memcpy(lut, c->raw_lut_wide.data(), c->raw_lut_wide.size());
     return LT_OK;
 }
 
@@ -2521,126 +2197,19 @@ int lt_bilateral_adaptive_threshold(lt_ctx* c, const uint8_t* img, int h, int w,
 }
 
 // ---- one host frame -> RGB, on the device ---------------------------------------------------------------------------------------------
-// The one-shot converters below validate their arguments and describe their job; convert_once does the rest.
-struct OneShot {
-    const char* what;                        // for the error text
-    const void* frame;
-    size_t in_bytes;
-    int h, w, layout;
-    YuvCoef k;                               // the YUV layouts
-    // raw Bayer behind a table (RawStages): the table (null: the 8-bit identity / the wide default), the colour stage (curve not null: ccm
-    // and curve), the shading map (mesh not null)
-    bool raw_table;
-    const uint8_t* lut;
-    const int16_t* ccm;
-    const uint8_t* curve;
-    const uint16_t* mesh;
-    int mesh_w, mesh_h;
-    const int32_t* black;
-};
-static int convert_once(lt_ctx* c, const OneShot& j, uint8_t* out_rgb) {
-    int rc;
-    if ((rc = set_device(c))) return rc;
-    const size_t out_bytes = (size_t)j.h * j.w * 3;
-    DevBuf<uint8_t> d_in, d_out;
-    DevBuf<uint32_t> d_table;
-    DevBuf<uint16_t> d_gain;
-    std::vector<uint8_t> table;              // (read by the upload until the synchronise below)
-    RawStages raw;
-    if ((rc = d_in.alloc(j.in_bytes)) || (rc = d_out.alloc(out_bytes))) return rc;
-    hipError_t e = hipSuccess;
-    if (j.raw_table) {
-        table = staged_table(j.layout, j.lut, j.curve);
-        if ((rc = d_table.alloc(table.size() / 4))) return rc;
-        if (j.mesh && (rc = expand_mesh(c->stream, j.mesh, j.mesh_w, j.mesh_h, j.layout, j.h, j.w, &d_gain.p))) return rc;
-        raw.table = d_table.p;
-        raw.bits = is_bayer_wide(j.layout) ? raw_bits(j.layout) : 8;
-        raw.pack = raw_packing(j.layout);
-        raw.color = j.curve != nullptr;
-        for (int i = 0; raw.color && i < 9; ++i) raw.cm.m[i] = j.ccm[i];
-        raw.gains = d_gain.p;
-        for (int p = 0; j.mesh && p < 4; ++p) raw.blk.b[p] = j.black ? j.black[p] : 0;
-        e = hipMemcpyAsync(d_table.p, table.data(), table.size(), hipMemcpyHostToDevice, c->stream);
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(d_in.p, j.frame, j.in_bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        launch_yuv_rows_to_rgb(c->stream, j.layout, d_in.p, j.in_bytes, j.k, d_out.p, out_bytes, j.h, j.w, 0, j.h, 1, raw);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out_rgb, d_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return fail(LT_ERR_HIP, "%s failed: %s", j.what, hipGetErrorString(e));
-    return LT_OK;
-}
-
+// (convert_once and the raw Bayer converters: lt_raw.cpp)
 // one 4:2:0 host frame of any even size (h w 3 / 2 bytes), or one packed 4:2:2 frame of any even width (h w 2 bytes) -> RGB
 // (cv2.cvtColor(frame, COLOR_YUV2RGB_NV12 / _I420 / _YUY2 / _UYVY) with the given matrix)
 int lt_yuv_to_rgb(lt_ctx* c, const uint8_t* frame, int h, int w, int layout, const int32_t* coeffs, uint8_t* out_rgb) {
     if (!c || !frame || !out_rgb) return fail(LT_ERR_INVALID, "null argument");
     int rc = check_yuv_format(layout, coeffs, h, w);
     if (rc) return rc;
-    if (h > 16384 || w > 16384) return fail(LT_ERR_INVALID, "bad image size (at most 16384 x 16384)");
+    if ((rc = check_one_shot_size(layout, h, w))) return rc;
     const size_t px = (size_t)h * w;
-    OneShot j = {"YUV conversion", frame, is_422(layout) ? px * 2 : px * 3 / 2, h, w, layout};
-    j.k = YuvCoef{coeffs[0], coeffs[1], coeffs[2], coeffs[3], coeffs[4]};
-    return convert_once(c, j, out_rgb);
-}
-
-// one 8-bit raw Bayer host frame of any even size from 4 x 4 (h w bytes) -> RGB: the bilinear demosaic of bayer_arith.h
-int lt_bayer_to_rgb(lt_ctx* c, const uint8_t* frame, int h, int w, int layout, uint8_t* out_rgb) {
-    if (!c || !frame || !out_rgb) return fail(LT_ERR_INVALID, "null argument");
-    if (!is_bayer(layout)) return fail(LT_ERR_INVALID, "lt_bayer_to_rgb takes the raw Bayer layouts (16 .. 19)");
-    int rc = check_bayer_size(h, w);
-    if (rc) return rc;
-    if (h > 16384 || w > 16384) return fail(LT_ERR_INVALID, "bad image size (at most 16384 x 16384)");
-    return convert_once(c, OneShot{"raw Bayer conversion", frame, (size_t)h * w, h, w, layout}, out_rgb);
-}
-
-// one 10- / 12-bit raw Bayer host frame (h w 16-bit words) -> RGB: every sample looked up in `lut` (null: the default table), then the
-// bilinear demosaic -- lt_bayer_to_rgb's twin
-int lt_raw16_to_rgb(lt_ctx* c, const uint16_t* frame, int h, int w, int layout, const uint8_t* lut, uint8_t* out_rgb) {
-    if (!c || !frame || !out_rgb) return fail(LT_ERR_INVALID, "null argument");
-    if (!is_bayer_wide(layout) || raw_packing(layout) >= 0) return fail(LT_ERR_INVALID, "lt_raw16_to_rgb takes the 10- and 12-bit raw Bayer layouts (32 .. 35, 48 .. 51)");
-    int rc = check_bayer_size(h, w);
-    if (rc) return rc;
-    if (h > 16384 || w > 16384) return fail(LT_ERR_INVALID, "bad image size (at most 16384 x 16384)");
-    return convert_once(c, OneShot{"raw Bayer conversion", frame, (size_t)h * w * 2, h, w, layout, YuvCoef{}, true, lut}, out_rgb);
-}
-
-// One raw Bayer host frame in any of the twelve raw layouts -> RGB behind its table, on behalf of `fn`: every sample shaded (mesh not null:
-// the map and its pedestals), looked up in `lut` (8-bit: null is the identity; 10 / 12 bits: null is the default table) and demosaiced, then
-// -- `color` -- matrix and curve (null: the identity each).
-static int raw_to_rgb(lt_ctx* c, const char* fn, const void* frame, int h, int w, int layout, const uint8_t* lut, size_t lut_entries, bool color,
-                      const int16_t* ccm, const uint8_t* curve, const uint16_t* mesh, int mesh_w, int mesh_h, const int32_t* black, uint8_t* out_rgb) {
-    if (!c || !frame || !out_rgb) return fail(LT_ERR_INVALID, "null argument");
-    if (!is_raw_mosaic(layout)) return fail(LT_ERR_INVALID, "%s takes the raw Bayer layouts (16 .. 19, 32 .. 35, 48 .. 51)", fn);
-    const bool wide = is_bayer_wide(layout);
-    const size_t entries = wide ? (size_t)1 << raw_bits(layout) : 256;
-    if (lut && lut_entries != entries) return fail(LT_ERR_INVALID, "the raw table of this layout has %zu entries per colour phase, got %zu", entries, lut_entries);
-    int rc = check_raw_size(layout, h, w);
-    if (rc) return rc;
-    if (h > 16384 || w > 16384) return fail(LT_ERR_INVALID, "bad image size (at most 16384 x 16384)");
-    if (mesh && (rc = check_shading(layout, mesh_w, mesh_h, black))) return rc;
-    static const int16_t ident[9] = {1024, 0, 0, 0, 1024, 0, 0, 0, 1024};
-    uint8_t line[256];
-    for (int i = 0; i < 256; ++i) line[i] = curve ? curve[i] : (uint8_t)i;
-    const OneShot j = {"raw Bayer conversion", frame, (size_t)h * (size_t)one_plane_row_bytes(layout, w), h, w, layout, YuvCoef{}, true, lut,
-                       ccm ? ccm : ident, color ? line : nullptr, mesh, mesh_w, mesh_h, black};
-    return convert_once(c, j, out_rgb);
-}
-
-// lt_bayer_to_rgb / lt_raw16_to_rgb behind a raw table and with the colour stage: the raw row kernels with STAGES 2 and 3 alone
-int lt_raw_to_rgb_color(lt_ctx* c, const void* frame, int h, int w, int layout, const uint8_t* lut, size_t lut_entries, const int16_t* ccm,
-                        const uint8_t* curve, uint8_t* out_rgb) {
-    return raw_to_rgb(c, "lt_raw_to_rgb_color", frame, h, w, layout, lut, lut_entries, true, ccm, curve, nullptr, 0, 0, nullptr, out_rgb);
-}
-
-// lt_raw_to_rgb_color behind a shading map (mesh = null: none); without ccm and curve there is no colour stage either -- the raw row
-// kernels with STAGES 4 .. 7 alone
-int lt_raw_to_rgb_shaded(lt_ctx* c, const void* frame, int h, int w, int layout, const uint8_t* lut, size_t lut_entries, const int16_t* ccm,
-                         const uint8_t* curve, const uint16_t* mesh, int mesh_w, int mesh_h, const int32_t* black, uint8_t* out_rgb) {
-    if (!mesh) return lt_raw_to_rgb_color(c, frame, h, w, layout, lut, lut_entries, ccm, curve, out_rgb);
-    return raw_to_rgb(c, "lt_raw_to_rgb_shaded", frame, h, w, layout, lut, lut_entries, ccm || curve, ccm, curve, mesh, mesh_w, mesh_h, black, out_rgb);
+    RawSetup none;
+    none.layout = layout;
+    return convert_once(c, "YUV conversion", frame, is_422(layout) ? px * 2 : px * 3 / 2, h, w, YuvCoef{coeffs[0], coeffs[1], coeffs[2], coeffs[3], coeffs[4]}, none,
+                        out_rgb);
 }
 
 int lt_filter_lane_points(lt_ctx* c, const uint8_t* bev, int h, int w, const lt_filter_params* p, uint8_t* mask) {

@@ -1,5 +1,7 @@
 // The context behind the C ABI (struct lt_ctx) and the helpers its translation units share:
 //   lt_api.cpp     -- create / destroy / reserve, input format and size, downloads, the searches, measurement
+//   lt_raw.cpp     -- what raw Bayer frames are conditioned with (raw table, colour stage, shading map: raw_setup.h), raw statistics, the
+//                     one-shot converters of a host frame to RGB
 //   lt_ingest.cpp  -- host frames into slots: lt_upload_frames, the row and rest uploads, lt_device_frames_rest (direct, staged, resized)
 //   lt_mask_chain.cpp -- the mask chain (top-hats, thresholds, merge + 5x5 open) and the arena that owns its device memory
 //   lt_memory.cpp  -- device-memory cache, page-locked host memory, the host copy threads
@@ -161,34 +163,12 @@ struct lt_ctx {
     bool input_locked = false;                // an upload has happened: the format stays
     uint8_t* d_yuv = nullptr;
     size_t yuv_bytes = 0, yuv_stride = 0;
-    // The raw table of a raw Bayer context (lt_set_raw_lut): uint8[4][256], phase-major, on the host and -- allocated by the first set, kept --
-    // in device memory, where the raw walk and row conversion (k_raw_walk_rows, k_raw_rows_rgb) stage it in LDS.  raw_lut_set says
-    // which kernels are launched: the table's content never does.
-    bool raw_lut_set = false;
-    uint8_t raw_lut[1024] = {0};
-    uint32_t* d_raw_lut = nullptr;
-    // The table of a 10- / 12-bit raw Bayer context (lt_set_raw_lut_wide): uint8[4][1 << bits], always one (the default until another is set);
-    // the host copy sized by the layout, the device copy allocated once at that size when the layout is set.
-    std::vector<uint8_t> raw_lut_wide;
-    uint32_t* d_raw_lut_wide = nullptr;
-    // The colour stage of a raw Bayer context (lt_set_raw_color): the colour-correction matrix (Q10) and the output curve on the host, and
-    // in device memory ONE buffer for the raw kernels to stage -- the curve's 256 bytes followed by the table the frames are conditioned with (the
-    // 8-bit raw table, the identity where none is set, or the wide table) -- rewritten whenever the stage or the table changes while
-    // a stage is set (write_raw_color).  raw_color_set says which kernels are launched: the stage's content never does.
-    bool raw_color_set = false;
-    int16_t raw_ccm[9] = {1024, 0, 0, 0, 1024, 0, 0, 0, 1024};
-    uint8_t raw_curve[256] = {0};
-    uint32_t* d_raw_cc = nullptr;
-    size_t raw_cc_bytes = 0;
-    // The lens-shading correction of a raw Bayer context (lt_set_raw_shading): mesh and pedestals on the host, and in device memory the gain
-    // plane that k_shade_expand makes of the mesh -- uint16[img_h][img_w] and 16 bytes of padding, allocated by the first set, freed when the
-    // map is removed: a context that never sets one allocates nothing.  raw_shade_set says which kernels are launched: the map's content
-    // never does.  An 8-bit context without a raw table then keeps the identity table in d_raw_lut: the raw kernels always stage one.
-    bool raw_shade_set = false;
-    std::vector<uint16_t> raw_mesh;
-    int raw_mesh_w = 0, raw_mesh_h = 0;
-    lt::RawShadeBlack raw_black = {};             // the pedestals, by colour phase
-    uint16_t* d_raw_gain = nullptr;
+    // What a raw Bayer context's frames are conditioned with (lt_raw.cpp: lt_set_raw_lut / _wide, lt_set_raw_color, lt_set_raw_shading, and
+    // lt_set_input_format, which starts it afresh): the host value and what it is on the device -- one buffer of what the raw kernels stage in
+    // LDS, and the gain plane of the shading map (raw_setup.h).  Every setter edits a copy of `raw`, raw_adopt writes that to the device and
+    // makes it the context's; raw_stages_of is what the launches read.  raw.layout is in_layout while that is a raw layout.
+    lt::RawSetup raw;
+    lt::RawDevice raw_dev;
     // The device scratch of lt_raw_stats: the zone sums, histograms and zone counts of the call's slots, allocated by the first call (grown by
     // one that needs more), freed with the context.
     uint8_t* d_stats = nullptr;
@@ -395,23 +375,8 @@ inline bool is_bayer_wide(int layout) { return raw_bits(layout) != 0; }
 inline int raw_packing(int layout) { return raw_pack(layout); }
 // any raw mosaic, whatever its samples: what is about the mosaic (sizes, row runs, input only) and not about bytes
 inline bool is_raw_mosaic(int layout) { return is_bayer(layout) || is_bayer_wide(layout); }
-// What the front end and the row conversion of `c` are launched with behind a raw table (lt_internal.h: RawStages) -- the one place that
-// knows which table that is: a wide context always has one; an 8-bit context has one when a raw table is set, or when a shading map is,
-// which brings the identity table where no raw table is set (lt_set_raw_shading keeps it in d_raw_lut); with a colour stage the staged
-// buffer is d_raw_cc, the curve in front of that same table (write_raw_color).  No table: the plain kernels of the layout.
-inline RawStages raw_stages_of(const lt_ctx* c) {
-    RawStages r;
-    if (!is_raw_mosaic(c->in_layout)) return r;
-    const bool wide = is_bayer_wide(c->in_layout);
-    r.bits = wide ? raw_bits(c->in_layout) : 8;
-    r.pack = raw_packing(c->in_layout);
-    r.table = c->raw_color_set ? c->d_raw_cc : wide ? c->d_raw_lut_wide : c->raw_lut_set || c->raw_shade_set ? c->d_raw_lut : nullptr;
-    r.color = c->raw_color_set;
-    for (int i = 0; i < 9; ++i) r.cm.m[i] = c->raw_ccm[i];
-    r.gains = c->raw_shade_set ? c->d_raw_gain : nullptr;
-    r.blk = c->raw_black;
-    return r;
-}
+// what the front end and the row conversion of `c` are launched with (raw_setup.h)
+inline RawStages raw_stages_of(const lt_ctx* c) { return raw_stages(c->raw, c->raw_dev); }
 inline int packed_bpp(int layout) {
     return layout == LT_INPUT_RGB || layout == LT_INPUT_BGR ? 3 : layout == LT_INPUT_RGBA || layout == LT_INPUT_BGRA ? 4
            : layout == LT_INPUT_YUY2 || layout == LT_INPUT_UYVY || (is_bayer_wide(layout) && raw_packing(layout) < 0) ? 2 : is_bayer(layout) ? 1 : 0;
@@ -445,6 +410,19 @@ inline int first_foreign(const lt_ctx* c, int first, int n) {
 int refuse_foreign(lt_ctx* c, int first, int n, const char* who);   // LT_ERR_STATE if one of the slots has another set than 0
 bool union_rows(lt_ctx* c);                                         // fe.r0 / fe.nrows, cam_r0 / cam_r1, ov_r0 / ov_r1 := the unions over the sets
 void refresh_cal0(lt_ctx* c);                                       // cal[0] := the context's own tables and rows
+
+// ---- raw Bayer conditioning, one-shot conversion (lt_raw.cpp) ----------------------------------------------------
+// `s` onto the device, for a context or for one call -- the only code that allocates or writes either buffer of `d`: the table buffer :=
+// raw_staged(s), and -- new_map -- the gain plane := the mesh expanded on `st` for frames of h x w (the host waits); no map: no plane.  An error
+// with nothing written leaves `d` as it was; a failed expansion has taken the map out of `s` AND `d` (better none than one they disagree on).
+int raw_commit(RawSetup& s, RawDevice& d, bool new_map, hipStream_t st, int h, int w);
+void raw_release(RawDevice& d);
+// lt_set_input_format: a raw table stays with 8-bit Bayer, stage and map go, a wide layout has its default staged -- before anything else changes
+int raw_take_layout(lt_ctx* c, int layout);
+int check_raw_size(int layout, int h, int w);                       // a frame of a raw layout: even sides from 4, RAW10 rows whole groups
+int check_one_shot_size(int layout, int h, int w);                  // ... and of a one-shot converter, any layout: at most 16384 a side
+// one host frame in raw.layout (any but RGB) -> RGB on the device, behind `raw` where that is a raw layout (committed here, for the call)
+int convert_once(lt_ctx* c, const char* what, const void* frame, size_t in_bytes, int h, int w, YuvCoef k, RawSetup raw, uint8_t* out_rgb);
 
 // ---- LT_TRACE_START=1 (lt_memory.cpp): one line per set-up phase on stderr -------------------------------
 //   lt_start <seconds on CLOCK_MONOTONIC, = Python's time.monotonic()> <what> <ms> [<bytes>]

@@ -10,6 +10,7 @@
 #include <cstdlib>
 
 #include "../../include/lane_tracker_amd.h"
+#include "raw_setup.h"
 #include "yuv_arith.h"
 
 // Measurement switches -- alternative kernels and launch shapes for A/B runs, each held bit-exact by the parity suite -- exist in
@@ -57,28 +58,7 @@ void launch_warp_split(hipStream_t s, const uint32_t* und, size_t und_px, int fi
                        const uint16_t* wfrac, FrontEndGeom g, const uint16_t* gamma_tab, const uint16_t* cbrt_tab,
                        const int32_t* coeffs, bool lab_clamp_dead, uint8_t* planeR, uint8_t* planeB, size_t plane_stride, int n);
 // (YuvCoef, the five coefficients of the YUV 4:2:0 input's conversion: yuv_arith.h)
-// What a launch of the front end over raw Bayer frames runs around the demosaic (`raw`, here and below; lt_ctx.h: raw_stages_of), and the one
-// argument of the raw kernels -- k_raw_walk_rows, k_raw_rows_rgb<.., STAGES>, launched in place of the plain ones whenever there is a table:
-//   table  device memory, what the kernel stages in LDS: the raw table the samples are looked up in (lt_set_raw_lut: uint8[4][256], phase-major;
-//          lt_set_raw_lut_wide: uint8[4][1 << bits]), behind the 256 bytes of the output curve where there is a colour stage.  Null: no raw
-//          kernel, 8-bit frames go through the plain demosaic (10- / 12-bit frames always have a table)
-//   bits   of a sample: 8, or 10 / 12 (16-bit little-endian words)
-//   color  the colour stage (lt_set_raw_color; bayer_arith.h: color_px) on every demosaiced pixel; cm: its matrix, Q10, row-major
-//   gains  not null: the lens-shading correction (lt_set_raw_shading; shade_arith.h) of every sample before its lookup -- device memory, the
-//          gain of every site, uint16[h][w] (Q12) and 16 bytes of padding (launch_shade_expand); blk: the pedestal of each colour phase
-struct RawColorMat { int32_t m[9]; };
-struct RawShadeBlack { int32_t b[4]; };
-//   pack   -1, or the packing of 10- / 12-bit samples (mipi_arith.h: 0 RAW10, five bytes for four sites; 1 RAW12, three bytes for two): the
-//          kernels' packed forms, k_mipi_walk_rows, k_mipi_rows_rgb<.., STAGES, PACK>
-struct RawStages {
-    const uint32_t* table = nullptr;
-    int bits = 8;
-    bool color = false;
-    RawColorMat cm = {};
-    int pack = -1;                           // (in what was padding: every other member lies where it lay)
-    const uint16_t* gains = nullptr;
-    RawShadeBlack blk = {};
-};
+// (RawStages -- `raw`, here and below -- and raw_wide_bits, raw_pack, raw_wide_row_bytes, what the raw layouts' numbers say: raw_setup.h)
 // mesh (device memory, uint16[4][mh][mw], phase-major) -> the gain plane of an h x w image whose layout has `pattern` (k_shade_expand)
 void launch_shade_expand(hipStream_t s, const uint16_t* mesh, int mw, int mh, int pattern, uint16_t* plane, int h, int w);
 // Raw Bayer statistics (lt_raw_stats; k_raw_stats.hip, stats_arith.h): histograms and zone sums of the samples of slots [first_slot,
@@ -130,13 +110,6 @@ struct FrameSource {
     static FrameSource surfaces(const SurfEntry* tab) { return FrameSource{tab, nullptr, 0}; }
 };
 void launch_raw_stats(hipStream_t s, FrameSource src, int first_slot, int n, const RawStatsJob& job);      // (RawStatsJob: above)
-// The 10- / 12-bit raw Bayer layouts (32 .. 35, 48 .. 51; pattern = layout & 3): the bits of a sample, 0 for every other layout.  Their frames
-// are one plane of 16-bit little-endian words and they are always launched with a table (RawStages).
-// Layouts 36 .. 39 / 52 .. 55 (bit 2 set) are the same samples MIPI-packed, one plane of bytes: raw_pack says which packing (mipi_arith.h), -1: none.
-inline int raw_wide_bits(int layout) { return layout >= 32 && layout <= 39 ? 10 : layout >= 48 && layout <= 55 ? 12 : 0; }
-inline int raw_pack(int layout) { return raw_wide_bits(layout) && (layout & 4) ? (layout >= 48 ? 1 : 0) : -1; }
-// the bytes of a row of w sites of a raw layout with 10- / 12-bit samples
-inline int raw_wide_row_bytes(int layout, int w) { return raw_pack(layout) == 0 ? w + (w >> 2) : raw_pack(layout) == 1 ? w + (w >> 1) : 2 * w; }
 // the undistorted rows of n frames (layout 0 = RGB, 1 = NV12, 2 = I420, 3 = YUY2, 4 = UYVY, 5 = BGR, 6 = RGBA, 7 = BGRA, 16 .. 19 = raw Bayer RGGB /
 // GRBG / GBRG / BGGR, 32 .. 35 / 48 .. 51 = the same at 10 / 12 bits, 36 .. 39 / 52 .. 55 = those MIPI-packed, which need raw.table; `k` is read for the YUV layouts only: every tap
 // converted, then the same blend); `und` is the base of the whole buffer, `first_slot` the absolute slot of frame 0 of the call
