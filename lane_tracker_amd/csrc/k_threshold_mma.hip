@@ -29,8 +29,10 @@
 //     load instruction covers two whole 128-byte lines -- and transposes 4 x 4 bytes with v_perm_b32 into four operands, one
 //     per column i of the dword.  The band is the B operand (n = output row).  MFMA set i yields columns 4c + i.
 //
-// No LDS, no barrier.  Window sizes 15, 20, 35 as in the walks; the greenery mask (window 65 with the range term) and
-// everything bilateral_walk_supported refuses stay on k_threshold_walk.hip / k_threshold.hip.
+// The products use no LDS and no barrier; a horizontal task collects its words in LDS for one contiguous store at its end.  A
+// tile whose own pixels are all <= C is written as "fails" without its products ("Dead tiles" below).  Window sizes 15, 20, 35
+// as in the walks; the greenery mask (window 65 with the range term) and everything bilateral_walk_supported refuses stay on
+// k_threshold_walk.hip / k_threshold.hip.
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
@@ -60,6 +62,8 @@ struct MmaArgs {
     int h, w, wpr;
     int pitch;                           // bytes per row of the plane (a multiple of 64 >= w)
     int C;
+    int lds_rows;                        // rows of wpr words a workgroup has in LDS: 32, or 0 when the rows are too wide
+    uint32_t live_k, live_all;           // the dead-tile test: 127 - C in every byte; 1 = every block counts as live (see `above`)
     int hgroups;                         // 32-row groups per frame (one horizontal task each)
     int vgroups, vsegs, vseg_len;        // 128-column strips, segments per strip and their length (a multiple of 32)
     int per_frame;                       // tasks per frame
@@ -137,7 +141,19 @@ struct PrefetchDepth {
     static constexpr int H = 2, V = 2;
 };
 
+extern __shared__ unsigned long long task_words[];   // a horizontal task's words, 32 rows of wpr (see mma_h_task)
+constexpr int MaxStagedWpr = 128;        // 32 KiB of LDS per wave at the most: wider rows are stored trip by trip
+
 constexpr uint32_t SIGN = 0x80808080u;   // p -> p - 128 in every byte; also pixel value 0 after the flip
+
+// Dead tiles.  C >= 0 and S >= 0, so a pixel p <= C fails K p > S + C K on every side, whatever its neighbours hold: a verdict
+// tile whose own pixels are all <= C is all "fails" and needs none of its MFMAs.  `above` collects, in bit 7 of every byte, "this
+// byte of x is > C" for C <= 127 (k = 127 - C in every byte: the low seven bits carry into bit 7 from C + 1 on, or bit 7 is set
+// already); `any_above` is the wave-uniform answer for the wave's block.  A larger C, or LT_THRESHOLD_SKIP=0 in the experiments
+// build, sets MmaArgs::live_all and every block counts as live.  The test runs on the raw bytes with the positions outside the
+// image already 0, so those are never live.
+__device__ __forceinline__ uint32_t above(uint32_t acc, uint32_t x, uint32_t k) { return acc | ((x & 0x7f7f7f7fu) + k) | x; }
+__device__ __forceinline__ uint32_t any_above(uint32_t acc) { return __builtin_amdgcn_ballot_w64((acc & SIGN) != 0u) != 0ull ? 1u : 0u; }
 
 // ---------------------------------------------------------------------------------------------------------------
 // Horizontal task: rows 32 grp .. + 31 of a frame, all of its columns.
@@ -158,29 +174,46 @@ __device__ __forceinline__ void mma_h_task(const MmaArgs& a, int frame, int grp)
     // (a block that lies outside the row's pitch is all masked: any block inside it stands in for its load)
     const int bmax = (a.pitch >> 5) - 1;
     auto fetch = [&](int b) -> v4i { return *reinterpret_cast<const v4i*>(src + 32 * min(max(b, 0), bmax) + lane_off); };
-    auto prep = [&](v4i raw, int b) -> v4i {
+    auto prep = [&](v4i raw, int b, uint32_t& live) -> v4i {      // live: some pixel of the wave's block is > C (wave-uniform)
         const int col = 32 * b + 16 * g;
-        v4i v;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = raw[q] ^ (int)SIGN;
         if (32 * b < 0 || 32 * b + 32 > w) {          // wave-uniform: a block that reaches over an image edge
 #pragma unroll
-            for (int q = 0; q < 4; ++q) v[q] = (col + 4 * q >= 0 && col + 4 * q < w) ? v[q] : (int)SIGN;
+            for (int q = 0; q < 4; ++q) raw[q] = (col + 4 * q >= 0 && col + 4 * q < w) ? raw[q] : 0;
         }
+        v4i v;
+        uint32_t acc = 0u;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            acc = above(acc, (uint32_t)raw[q], a.live_k);
+            v[q] = raw[q] ^ (int)SIGN;
+        }
+        live = any_above(acc) | a.live_all;
         return v;
     };
 
     // The window of trip S: blocks 4 S - NB .. 4 S + 3 + NB.  Each trip shifts it by four blocks and takes the four new ones from
     // loads issued D trips earlier: one trip is a few hundred cycles of matrix work, a load from memory takes several times that.
+    // Bit i of lv says that win[i] is live; it moves with the window.
     v4i win[W], pf[D][4];
+    uint32_t lv = 0u;
 #pragma unroll
-    for (int i = 4; i < W; ++i) win[i] = prep(fetch(i - 4 - NB), i - 4 - NB);
+    for (int i = 4; i < W; ++i) {
+        uint32_t live;
+        win[i] = prep(fetch(i - 4 - NB), i - 4 - NB, live);
+        lv |= live << i;
+    }
 #pragma unroll
     for (int i = 0; i < 4; ++i) win[i] = win[4];      // (shifted out before the first use)
 #pragma unroll
     for (int ph = 0; ph < D; ++ph)
 #pragma unroll
         for (int i = 0; i < 4; ++i) pf[ph][i] = fetch(4 * ph + NB + i);
+    // The task's words, 32 rows of wpr, are one contiguous piece of the bit plane.  A trip yields 16 bytes of each row: stored as
+    // they come, every store instruction touches 32 lines and every line is visited by nine trips microseconds apart.  They are
+    // collected in LDS in the plane's own layout instead and written out in one contiguous sweep at the end of the task
+    // (a.lds_rows = 0: the row is too wide for that, and the words are stored trip by trip).
+    const bool staged = a.lds_rows != 0;              // wave-uniform
+    unsigned long long* stage = task_words + (lane & 31) * a.wpr;
     const int trips = (w + 127) >> 7;
     for (int sb = 0; sb < trips; sb += D) {
         static_for([&](auto phc) {
@@ -189,33 +222,53 @@ __device__ __forceinline__ void mma_h_task(const MmaArgs& a, int frame, int grp)
             if (S < trips) {                          // wave-uniform
 #pragma unroll
                 for (int i = 0; i < 2 * NB; ++i) win[i] = win[i + 4];
+                lv >>= 4;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    win[2 * NB + i] = prep(pf[ph][i], 4 * S + NB + i);
+                    uint32_t live;
+                    win[2 * NB + i] = prep(pf[ph][i], 4 * S + NB + i, live);
+                    lv |= live << (2 * NB + i);
                     pf[ph][i] = fetch(4 * (S + D) + NB + i);      // (addresses clamped: any trip may ask)
                 }
-                uint32_t bits[2] = {0u, 0u};          // tiles (0, 1) and (2, 3) of the trip: first tile in the high half
-                static_for([&](auto uc) {
-                    constexpr int u = decltype(uc)::value;
-                    v16i accl = cinit, accr = cinit;
-                    static_for([&](auto ec) {
-                        constexpr int e = decltype(ec)::value;
-                        accl = mfma(bl[e], win[u + e], accl);
-                        accr = mfma(br[e], win[u + e + NB], accr);
-                    }, std::make_integer_sequence<int, NOP>{});
-                    // register i of lane half g = column 32 T + 16 g + i: shifted in from the top one, so that bit i is column i
+                // tiles (0, 1) and (2, 3) of the trip: first tile in the high half; a set bit is "fails"
+                uint32_t bits[2] = {0xffffffffu, 0xffffffffu};
+                if ((lv >> NB) & 15u) {               // wave-uniform: tile u's own block is win[u + NB]
+                    static_for([&](auto uc) {
+                        constexpr int u = decltype(uc)::value;
+                        if ((lv >> (u + NB)) & 1u) {  // wave-uniform
+                            v16i accl = cinit, accr = cinit;
+                            static_for([&](auto ec) {
+                                constexpr int e = decltype(ec)::value;
+                                accl = mfma(bl[e], win[u + e], accl);
+                                accr = mfma(br[e], win[u + e + NB], accr);
+                            }, std::make_integer_sequence<int, NOP>{});
+                            // register i of lane half g = column 32 T + 16 g + i: shifted in from the top one, so that bit i is column i
 #pragma unroll
-                    for (int i = 15; i >= 0; --i)
-                        bits[u >> 1] = __builtin_amdgcn_alignbit(bits[u >> 1], (uint32_t)(accl[i] | accr[i]), 31);
-                }, std::make_integer_sequence<int, 4>{});
+                            for (int i = 15; i >= 0; --i)
+                                bits[u >> 1] = __builtin_amdgcn_alignbit(bits[u >> 1], (uint32_t)(accl[i] | accr[i]), 31);
+                        } else {
+                            bits[u >> 1] = (bits[u >> 1] << 16) | 0xffffu;      // a dead tile: sixteen "fails"
+                        }
+                    }, std::make_integer_sequence<int, 4>{});
+                }
                 // lane half g writes word 2 S + g of its row: it keeps its own pair of tiles and gets the other half's
                 const uint32_t recv = other_half(g ? bits[0] : bits[1], lane);
                 const uint32_t p0 = g ? recv : bits[0], p1 = g ? bits[1] : recv;      // columns 0-15 | 16-31 of the two tiles
                 const uint32_t lo = __builtin_amdgcn_perm(p1, p0, 0x07060302u), hi = __builtin_amdgcn_perm(p1, p0, 0x05040100u);
                 const int word = 2 * S + g;
-                if (row < h && word < a.wpr) orow[word] = ~((unsigned long long)lo | ((unsigned long long)hi << 32));
+                const unsigned long long verdict = ~((unsigned long long)lo | ((unsigned long long)hi << 32));
+                if (word < a.wpr) {
+                    if (staged) stage[word] = verdict;
+                    else if (row < h) orow[word] = verdict;
+                }
             }
         }, std::make_integer_sequence<int, D>{});
+    }
+    if (staged) {
+        __syncthreads();                              // (the workgroup is this wave)
+        const int nwords = min(32, h - grp * 32) * a.wpr;
+        unsigned long long* dst = a.out_h + (size_t)frame * a.bits_stride + (size_t)(grp * 32) * a.wpr;
+        for (int i = lane; i < nwords; i += 64) dst[i] = task_words[i];
     }
 }
 
@@ -255,17 +308,20 @@ __device__ __forceinline__ void mma_v_task(const MmaArgs& a, int frame, int grp,
         }
         return x;
     };
-    auto prep = [&](const Raw& x, int b) -> Block {
+    auto prep = [&](const Raw& x, int b, uint32_t& live) -> Block {      // live: some pixel of the wave's block is > C (wave-uniform)
         Block o;
         const bool inside = 32 * b >= 0 && 32 * b + 32 <= h && grp * 128 + 128 <= w;      // wave-uniform
+        uint32_t acc = 0u;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             uint32_t r[4];
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 const int y = 32 * b + 16 * g + 4 * q + t;
-                r[t] = x.r[4 * q + t] ^ SIGN;
-                if (!inside) r[t] = (colok && y >= 0 && y < h) ? r[t] : SIGN;
+                uint32_t raw = x.r[4 * q + t];
+                if (!inside) raw = (colok && y >= 0 && y < h) ? raw : 0u;
+                acc = above(acc, raw, a.live_k);
+                r[t] = raw ^ SIGN;
             }
             // 4 x 4 byte transpose: rows r[0..3] with columns in their bytes -> columns with rows in their bytes
             const uint32_t a01 = __builtin_amdgcn_perm(r[1], r[0], 0x05010400u), b01 = __builtin_amdgcn_perm(r[1], r[0], 0x07030602u);
@@ -275,16 +331,22 @@ __device__ __forceinline__ void mma_v_task(const MmaArgs& a, int frame, int grp,
             o.op[2][q] = (int)__builtin_amdgcn_perm(b23, b01, 0x05040100u);
             o.op[3][q] = (int)__builtin_amdgcn_perm(b23, b01, 0x07060302u);
         }
+        live = any_above(acc) | a.live_all;
         return o;
     };
 
     // The window of tile T: blocks T - NB .. T + NB.  Each tile shifts it by one block and takes the new one from loads issued D
-    // tiles earlier (see the horizontal task).
+    // tiles earlier (see the horizontal task).  Bit i of lv says that win[i] is live; it moves with the window.
     const int t_first = y0 >> 5, t_end = (y1 + 31) >> 5;
     Block win[W];
     Raw pf[D];
+    uint32_t lv = 0u;
 #pragma unroll
-    for (int i = 1; i < W; ++i) win[i] = prep(fetch(t_first - NB + i - 1), t_first - NB + i - 1);
+    for (int i = 1; i < W; ++i) {
+        uint32_t live;
+        win[i] = prep(fetch(t_first - NB + i - 1), t_first - NB + i - 1, live);
+        lv |= live << i;
+    }
     win[0] = win[1];                                  // (shifted out before the first use)
 #pragma unroll
     for (int ph = 0; ph < D; ++ph) pf[ph] = fetch(t_first + NB + ph);
@@ -295,32 +357,38 @@ __device__ __forceinline__ void mma_v_task(const MmaArgs& a, int frame, int grp,
             if (T < t_end) {                          // wave-uniform
 #pragma unroll
                 for (int i = 0; i + 1 < W; ++i) win[i] = win[i + 1];
-                win[W - 1] = prep(pf[ph], T + NB);
+                uint32_t live;
+                win[W - 1] = prep(pf[ph], T + NB, live);
+                lv = (lv >> 1) | (live << (W - 1));
                 pf[ph] = fetch(T + NB + D);
-                uint32_t x = 0u, y = 0u;              // fail bits of columns 32 t + 16 g + 0..15: t = 0 | 1 << 16 in x, t = 2 | 3 << 16 in y
-                static_for([&](auto ic) {
-                    constexpr int i = decltype(ic)::value;
-                    v16i accl = cinit, accr = cinit;
-                    static_for([&](auto ec) {
-                        constexpr int e = decltype(ec)::value;
-                        accl = mfma(win[e].op[i], bl[e], accl);
-                        accr = mfma(win[e + NB].op[i], br[e], accr);
-                    }, std::make_integer_sequence<int, NOP>{});
-                    // register j of lane half g = dword column (j & 3) + 8 (j >> 2) + 4 g, i.e. column 32 (j >> 2) + 16 g + 4 (j & 3) + i
+                unsigned long long verdict = 0ull;    // a dead tile (its own block is win[NB]): nothing passes
+                if ((lv >> NB) & 1u) {                // wave-uniform
+                    uint32_t x = 0u, y = 0u;          // fail bits of columns 32 t + 16 g + 0..15: t = 0 | 1 << 16 in x, t = 2 | 3 << 16 in y
+                    static_for([&](auto ic) {
+                        constexpr int i = decltype(ic)::value;
+                        v16i accl = cinit, accr = cinit;
+                        static_for([&](auto ec) {
+                            constexpr int e = decltype(ec)::value;
+                            accl = mfma(win[e].op[i], bl[e], accl);
+                            accr = mfma(win[e + NB].op[i], br[e], accr);
+                        }, std::make_integer_sequence<int, NOP>{});
+                        // register j of lane half g = dword column (j & 3) + 8 (j >> 2) + 4 g, i.e. column 32 (j >> 2) + 16 g + 4 (j & 3) + i
 #pragma unroll
-                    for (int j = 0; j < 16; ++j) {
-                        const uint32_t s = (uint32_t)(accl[j] | accr[j]) >> 31;
-                        const int pos = 16 * ((j >> 2) & 1) + 4 * (j & 3) + i;
-                        if (j < 8) x |= s << pos;
-                        else y |= s << pos;
-                    }
-                }, std::make_integer_sequence<int, 4>{});
-                // lane half g writes word 2 grp + g of the row
-                const uint32_t recv = other_half(g ? x : y, lane);
-                const uint32_t p0 = g ? recv : x, p1 = g ? y : recv;
-                const uint32_t lo = __builtin_amdgcn_perm(p1, p0, 0x05040100u), hi = __builtin_amdgcn_perm(p1, p0, 0x07060302u);
+                        for (int j = 0; j < 16; ++j) {
+                            const uint32_t s = (uint32_t)(accl[j] | accr[j]) >> 31;
+                            const int pos = 16 * ((j >> 2) & 1) + 4 * (j & 3) + i;
+                            if (j < 8) x |= s << pos;
+                            else y |= s << pos;
+                        }
+                    }, std::make_integer_sequence<int, 4>{});
+                    // lane half g writes word 2 grp + g of the row
+                    const uint32_t recv = other_half(g ? x : y, lane);
+                    const uint32_t p0 = g ? recv : x, p1 = g ? y : recv;
+                    const uint32_t lo = __builtin_amdgcn_perm(p1, p0, 0x05040100u), hi = __builtin_amdgcn_perm(p1, p0, 0x07060302u);
+                    verdict = ~((unsigned long long)lo | ((unsigned long long)hi << 32));
+                }
                 const int row = 32 * T + (lane & 31), word = 2 * grp + g;
-                if (row < y1 && word < a.wpr) out[(size_t)row * a.wpr + word] = ~((unsigned long long)lo | ((unsigned long long)hi << 32));
+                if (row < y1 && word < a.wpr) out[(size_t)row * a.wpr + word] = verdict;
             }
         }, std::make_integer_sequence<int, D>{});
     }
@@ -343,13 +411,15 @@ __global__ __launch_bounds__(64, 2) void k_bilateral_mma_hv(MmaArgs a) {
 
 template <int K>
 void launch_mma(hipStream_t s, const uint8_t* src, int C, unsigned long long* out_h, unsigned long long* out_v, int h, int w, int pitch,
-                size_t plane_stride, size_t bits_stride, int n) {
+                size_t plane_stride, size_t bits_stride, int n, bool skip, bool stage) {
     MmaArgs a;
     a.src = src;
     a.out_h = out_h; a.out_v = out_v;
     a.h = h; a.w = w; a.wpr = (w + 63) / 64;
     a.pitch = pitch;
     a.C = C;
+    a.live_all = (skip && C <= 127) ? 0u : 1u;          // the byte test of `above` holds for C <= 127: beyond it nothing is skipped
+    a.live_k = a.live_all ? 0u : (uint32_t)(127 - C) * 0x01010101u;
     a.hgroups = (h + 31) / 32;
     a.vgroups = (w + 127) / 128;
     a.vsegs = h > 640 ? 2 : 1;                        // the walks' split of the rows, on 32-row tile boundaries
@@ -357,15 +427,16 @@ void launch_mma(hipStream_t s, const uint8_t* src, int C, unsigned long long* ou
     a.per_frame = a.hgroups + a.vgroups * a.vsegs;
     a.plane_stride = plane_stride;
     a.bits_stride = bits_stride;
-    hipLaunchKernelGGL((k_bilateral_mma_hv<K>), dim3((unsigned)(a.per_frame * n)), dim3(64), 0, s, a);
+    a.lds_rows = (stage && a.wpr <= MaxStagedWpr) ? 32 : 0;
+    hipLaunchKernelGGL((k_bilateral_mma_hv<K>), dim3((unsigned)(a.per_frame * n)), dim3(64), (size_t)a.lds_rows * a.wpr * sizeof(unsigned long long), s, a);
 }
 
 void dispatch_mma(int k, hipStream_t s, const uint8_t* src, int C, unsigned long long* out_h, unsigned long long* out_v, int h, int w,
-                  int pitch, size_t plane_stride, size_t bits_stride, int n) {
+                  int pitch, size_t plane_stride, size_t bits_stride, int n, bool skip, bool stage) {
     switch (k) {
-        case 15: launch_mma<15>(s, src, C, out_h, out_v, h, w, pitch, plane_stride, bits_stride, n); break;
-        case 20: launch_mma<20>(s, src, C, out_h, out_v, h, w, pitch, plane_stride, bits_stride, n); break;
-        default: launch_mma<35>(s, src, C, out_h, out_v, h, w, pitch, plane_stride, bits_stride, n); break;
+        case 15: launch_mma<15>(s, src, C, out_h, out_v, h, w, pitch, plane_stride, bits_stride, n, skip, stage); break;
+        case 20: launch_mma<20>(s, src, C, out_h, out_v, h, w, pitch, plane_stride, bits_stride, n, skip, stage); break;
+        default: launch_mma<35>(s, src, C, out_h, out_v, h, w, pitch, plane_stride, bits_stride, n, skip, stage); break;
     }
 }
 
@@ -379,8 +450,10 @@ int launch_bilateral_mma(hipStream_t s, const uint8_t* thr, int k_r, int C_r, co
     if (n <= 0 || !bilateral_walk_supported(k_r, C_r, k_b, C_b, h, w, pitch, plane_stride)) return -1;
     static const bool off = [] { const char* e = LT_EXP_ENV("LT_THRESHOLD_MMA"); return e && e[0] == '0'; }();
     if (off) return 1;
-    dispatch_mma(k_r, s, thr, C_r, merged, s1, h, w, pitch, plane_stride, bits_stride, n);
-    dispatch_mma(k_b, s, thb, C_b, s2, s3, h, w, pitch, plane_stride, bits_stride, n);
+    static const bool skip = [] { const char* e = LT_EXP_ENV("LT_THRESHOLD_SKIP"); return !(e && e[0] == '0'); }();   // A/B: 0 = every block live
+    static const bool stage = [] { const char* e = LT_EXP_ENV("LT_THRESHOLD_STAGE"); return !(e && e[0] == '0'); }();   // A/B: 0 = words stored trip by trip
+    dispatch_mma(k_r, s, thr, C_r, merged, s1, h, w, pitch, plane_stride, bits_stride, n, skip, stage);
+    dispatch_mma(k_b, s, thb, C_b, s2, s3, h, w, pitch, plane_stride, bits_stride, n, skip, stage);
     return 0;
 }
 
