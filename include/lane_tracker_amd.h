@@ -68,7 +68,10 @@ extern "C" {
  *    Bayer input: a colour-correction matrix and an output curve on every demosaiced pixel, on the device); lt_set_raw_shading +
  *    lt_get_raw_shading + lt_get_raw_shading_plane + lt_raw_to_rgb_shaded (lens-shading correction of raw Bayer input from a gain mesh, on
  *    every sample in front of the raw table, on the device); lt_upload_mask_bits + lt_last_search_source (caller-supplied masks as
- *    bit planes, searched by the bit-plane kernels); lt_last_open_form (which form of the 5x5 open a mask run's last slice took).
+ *    bit planes, searched by the bit-plane kernels); lt_last_open_form (which form of the 5x5 open a mask run's last slice took);
+ *    lt_add_raw_set + lt_raw_set_count + lt_set_slot_raw_sets + lt_get_slot_raw_sets + lt_set_raw_lut_of + lt_get_raw_lut_of +
+ *    lt_set_raw_color_of + lt_get_raw_color_of + lt_set_raw_shading_of + lt_get_raw_shading_of + lt_get_raw_shading_plane_of +
+ *    lt_last_raw_walk_form (raw table, colour stage and shading map per slot: several raw sets in one context).
  *    Nothing removed or changed. */
 #define LT_ABI_VERSION 5
 
@@ -372,6 +375,34 @@ int  lt_raw_to_rgb_color(lt_ctx* ctx, const void* frame, int h, int w, int layou
 int  lt_set_raw_shading(lt_ctx* ctx, const uint16_t* mesh /* 4 * mesh_w * mesh_h, phase-major, Q12 */, int mesh_w, int mesh_h, const int32_t* black /* 4; NULL: zeros */, int enable);
 int  lt_get_raw_shading(lt_ctx* ctx, uint16_t* mesh, int* mesh_w, int* mesh_h, int32_t* black /* 4 */, int* is_set);
 int  lt_get_raw_shading_plane(lt_ctx* ctx, uint16_t* plane /* img_h * img_w */);
+
+/* Raw sets: one raw table, colour stage and shading map per kind of camera, in ONE raw Bayer context -- held as calibration sets are.
+ * Set 0 is the context's own: every function above acts on it.  lt_add_raw_set: a new set, a copy of set 0's value at that moment (its id
+ * in *id; ids are bytes: at most 256 sets; LT_ERR_STATE in a context whose input format is not raw Bayer).  lt_set_input_format with
+ * another layout removes every set but 0.  lt_set_slot_raw_sets: slot first_slot + i gets set ids[i] (LT_ERR_INVALID for an id the context
+ * does not hold); cheap, a host table -- the launches carry the ids by value -- and a slot whose set changes has a stale front end.
+ * lt_reserve, when it grows the context, puts every slot back to set 0.  The *_of functions are the setters and getters above for set `id`
+ * (LT_ERR_INVALID for an id out of range): set-up or occasional calls behind everything in flight; the slots OF THAT SET get a stale front
+ * end, no other.  lt_set_raw_lut_of / lt_get_raw_lut_of take the table of any raw layout, entries = 1 << bits per colour phase (256, 1024,
+ * 4096; LT_ERR_INVALID for another count); NULL: none (8 bits) / the default (10, 12 bits); *is_set as lt_get_raw_lut's, 1 for 10 / 12 bits.
+ * A front end or row conversion over slots that all have one set -- whichever -- launches the kernels of a context with that set alone; over
+ * slots that mix sets it launches ONE set-per-slot kernel that runs the union of the parts the context's sets have, a set that lacks a part
+ * running that part's exact identity (identity table, matrix 1024 I with identity curve, unit gains with pedestals 0): every slot's pixels
+ * are those of a context with its set alone.  lt_raw_stats reads each slot's own map.  lt_last_raw_walk_form: which raw walks the front
+ * end of the last lt_mask_run / lt_mask_rerun launched -- 0 none, 1 the one-set forms, 2 the set-per-slot forms (in some slice), -1 = no
+ * run yet or a null context; tests use it to know which kernels they have exercised. */
+int  lt_add_raw_set(lt_ctx* ctx, int* id);
+int  lt_raw_set_count(lt_ctx* ctx, int* count);
+int  lt_set_slot_raw_sets(lt_ctx* ctx, int first_slot, int n, const int32_t* ids);
+int  lt_get_slot_raw_sets(lt_ctx* ctx, int first_slot, int n, int32_t* ids);
+int  lt_set_raw_lut_of(lt_ctx* ctx, int id, const uint8_t* lut /* 4 * entries, phase-major; NULL */, size_t entries);
+int  lt_get_raw_lut_of(lt_ctx* ctx, int id, uint8_t* lut, size_t entries, int* is_set);
+int  lt_set_raw_color_of(lt_ctx* ctx, int id, const int16_t* ccm, const uint8_t* curve, int enable);
+int  lt_get_raw_color_of(lt_ctx* ctx, int id, int16_t* ccm, uint8_t* curve, int* is_set);
+int  lt_set_raw_shading_of(lt_ctx* ctx, int id, const uint16_t* mesh, int mesh_w, int mesh_h, const int32_t* black, int enable);
+int  lt_get_raw_shading_of(lt_ctx* ctx, int id, uint16_t* mesh, int* mesh_w, int* mesh_h, int32_t* black, int* is_set);
+int  lt_get_raw_shading_plane_of(lt_ctx* ctx, int id, uint16_t* plane /* img_h * img_w */);
+int  lt_last_raw_walk_form(lt_ctx* ctx);
 int  lt_raw_to_rgb_shaded(lt_ctx* ctx, const void* frame, int h, int w, int layout, const uint8_t* lut /* 4 * lut_entries bytes, or NULL */, size_t lut_entries,
                           const int16_t* ccm /* 9, or NULL */, const uint8_t* curve /* 256, or NULL */, const uint16_t* mesh /* or NULL: no map */, int mesh_w, int mesh_h,
                           const int32_t* black /* 4; NULL: zeros */, uint8_t* out_rgb);

@@ -276,6 +276,18 @@ _SIGNATURES = {
     "lt_set_slot_calibrations": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "lt_get_slot_calibrations": (C.c_int, [_P, C.c_int, C.c_int, _P]),
     "lt_overlay_configure_set": (C.c_int, [_P, C.c_int, _P]),
+    "lt_add_raw_set": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "lt_raw_set_count": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "lt_set_slot_raw_sets": (C.c_int, [_P, C.c_int, C.c_int, _P]),
+    "lt_get_slot_raw_sets": (C.c_int, [_P, C.c_int, C.c_int, _P]),
+    "lt_set_raw_lut_of": (C.c_int, [_P, C.c_int, _P, C.c_size_t]),
+    "lt_get_raw_lut_of": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.POINTER(C.c_int)]),
+    "lt_set_raw_color_of": (C.c_int, [_P, C.c_int, _P, _P, C.c_int]),
+    "lt_get_raw_color_of": (C.c_int, [_P, C.c_int, _P, _P, C.POINTER(C.c_int)]),
+    "lt_set_raw_shading_of": (C.c_int, [_P, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int]),
+    "lt_get_raw_shading_of": (C.c_int, [_P, C.c_int, _P, C.POINTER(C.c_int), C.POINTER(C.c_int), _P, C.POINTER(C.c_int)]),
+    "lt_get_raw_shading_plane_of": (C.c_int, [_P, C.c_int, _P]),
+    "lt_last_raw_walk_form": (C.c_int, [_P]),
 }
 
 # camera-frame formats (lt_input_layout) and the conversion matrices {CY, CVR, CVG, CUG, CUB} of include/lane_tracker_amd.h
@@ -1058,20 +1070,29 @@ class Context:
         _check(self.lib.lt_yuv_to_rgb(self._h, a.ctypes.data, h, w, pixel_format_id(layout), k.ctypes.data, out.ctypes.data))
         return out
 
-    def set_raw_lut(self, lut):
+    def set_raw_lut(self, lut, raw_set=0):
         """The raw table of a raw Bayer context -- u8 (4, 256), `utils.raw_lut` -- or None for none (lt_set_raw_lut): every sample is
         looked up in the row of its colour phase before the demosaic, in the undistortion and in the row conversion launched from now
         on.  Waits for the context's outstanding work: a set-up or occasional call, not a per-frame one.  A 10- / 12-bit context:
-        u8 (4, 2**bits), None for the default `utils.raw_lut(bits=..)` (lt_set_raw_lut_wide)."""
+        u8 (4, 2**bits), None for the default `utils.raw_lut(bits=..)` (lt_set_raw_lut_wide).  `raw_set`: the raw set of the context
+        that takes it (`add_raw_set`; lt_set_raw_lut_of), 0: the context's own."""
         a = checked_raw_lut(lut, self._pixel_format)
+        if raw_set:
+            _check(self.lib.lt_set_raw_lut_of(self._h, int(raw_set), None if a is None else a.ctypes.data, 1 << raw_bits(self._pixel_format)))
+            return
         if self._pixel_format in BAYER_DEEP_FORMATS:
             _check(self.lib.lt_set_raw_lut_wide(self._h, None if a is None else a.ctypes.data, 1 << raw_bits(self._pixel_format)))
             return
         _check(self.lib.lt_set_raw_lut(self._h, None if a is None else a.ctypes.data))
 
-    def raw_lut(self):
+    def raw_lut(self, raw_set=0):
         """-> the raw table, u8 (4, 256), or None (lt_get_raw_lut); a 10- / 12-bit context: the table in effect, u8 (4, 2**bits)
-        (lt_get_raw_lut_wide)."""
+        (lt_get_raw_lut_wide).  `raw_set`: of that raw set (lt_get_raw_lut_of)."""
+        if raw_set:
+            n = 1 << raw_bits(self._pixel_format)
+            out, is_set = np.zeros((4, max(n, 1)), np.uint8), C.c_int(0)
+            _check(self.lib.lt_get_raw_lut_of(self._h, int(raw_set), out.ctypes.data, n, C.byref(is_set)))
+            return out if is_set.value else None
         if self._pixel_format in BAYER_DEEP_FORMATS:
             n = 1 << raw_bits(self._pixel_format)
             out = np.zeros((4, n), np.uint8)
@@ -1081,46 +1102,88 @@ class Context:
         _check(self.lib.lt_get_raw_lut(self._h, out.ctypes.data, C.byref(is_set)))
         return out if is_set.value else None
 
-    def set_raw_color(self, ccm=None, curve=None, enable=True):
+    def set_raw_color(self, ccm=None, curve=None, enable=True, raw_set=0):
         """The colour stage of a raw Bayer context (lt_set_raw_color): `ccm` int16 (3, 3) in Q10 (`utils.raw_ccm`; None: the identity)
         and `curve` u8 (256,) (`utils.raw_curve`; None: the identity) on every demosaiced pixel, in the undistortion and in the row
         conversion launched from now on; enable=False removes it.  Waits for the context's outstanding work: a set-up or occasional
         call, not a per-frame one."""
         m, t = checked_raw_color(ccm, curve, self._pixel_format)
-        _check(self.lib.lt_set_raw_color(self._h, None if m is None else m.ctypes.data, None if t is None else t.ctypes.data, 1 if enable else 0))
+        args = (None if m is None else m.ctypes.data, None if t is None else t.ctypes.data, 1 if enable else 0)
+        if raw_set:                          # of that raw set (lt_set_raw_color_of)
+            _check(self.lib.lt_set_raw_color_of(self._h, int(raw_set), *args))
+            return
+        _check(self.lib.lt_set_raw_color(self._h, *args))
 
-    def get_raw_color(self):
-        """-> (ccm int16 (3, 3), curve u8 (256,)) of the colour stage, or None without one (lt_get_raw_color)."""
+    def get_raw_color(self, raw_set=0):
+        """-> (ccm int16 (3, 3), curve u8 (256,)) of the colour stage, or None without one (lt_get_raw_color; `raw_set`: lt_get_raw_color_of)."""
         m, t, is_set = np.zeros((3, 3), np.int16), np.zeros(256, np.uint8), C.c_int(0)
+        if raw_set:
+            _check(self.lib.lt_get_raw_color_of(self._h, int(raw_set), m.ctypes.data, t.ctypes.data, C.byref(is_set)))
+            return (m, t) if is_set.value else None
         _check(self.lib.lt_get_raw_color(self._h, m.ctypes.data, t.ctypes.data, C.byref(is_set)))
         return (m, t) if is_set.value else None
 
-    def set_raw_shading(self, shading):
+    def set_raw_shading(self, shading, raw_set=0):
         """The lens-shading map of a raw Bayer context (lt_set_raw_shading): `shading` a `utils.RawShading` -- every sample corrected by
         the gain of its position before the raw table, in the undistortion and in the row conversion launched from now on -- or None,
         which removes it.  Waits for the context's outstanding work: a set-up or occasional call, not a per-frame one."""
         s = checked_raw_shading(shading, self._pixel_format)
-        if s is None:
-            _check(self.lib.lt_set_raw_shading(self._h, None, 0, 0, None, 0))
+        args = (None, 0, 0, None, 0) if s is None else (s.mesh.ctypes.data, s.mesh.shape[2], s.mesh.shape[1], s.black.ctypes.data, 1)
+        if raw_set:                          # of that raw set (lt_set_raw_shading_of)
+            _check(self.lib.lt_set_raw_shading_of(self._h, int(raw_set), *args))
             return
-        _check(self.lib.lt_set_raw_shading(self._h, s.mesh.ctypes.data, s.mesh.shape[2], s.mesh.shape[1], s.black.ctypes.data, 1))
+        _check(self.lib.lt_set_raw_shading(self._h, *args))
 
-    def get_raw_shading(self):
-        """-> the utils.RawShading of the context, or None without one (lt_get_raw_shading)."""
+    def get_raw_shading(self, raw_set=0):
+        """-> the utils.RawShading of the context, or None without one (lt_get_raw_shading; `raw_set`: lt_get_raw_shading_of)."""
         from .utils import RawShading
+        get = (lambda *a: self.lib.lt_get_raw_shading_of(self._h, int(raw_set), *a)) if raw_set else (lambda *a: self.lib.lt_get_raw_shading(self._h, *a))
         mw, mh, is_set = C.c_int(0), C.c_int(0), C.c_int(0)
-        _check(self.lib.lt_get_raw_shading(self._h, None, C.byref(mw), C.byref(mh), None, C.byref(is_set)))
+        _check(get(None, C.byref(mw), C.byref(mh), None, C.byref(is_set)))
         if not is_set.value:
             return None
         mesh, black = np.zeros((4, mh.value, mw.value), np.uint16), np.zeros(4, np.int32)
-        _check(self.lib.lt_get_raw_shading(self._h, mesh.ctypes.data, None, None, black.ctypes.data, None))
+        _check(get(mesh.ctypes.data, None, None, black.ctypes.data, None))
         return RawShading(mesh, black)
 
-    def raw_shading_plane(self):
-        """-> the gain plane the device expanded the context's shading mesh into, uint16 (H, W) (lt_get_raw_shading_plane)."""
+    def raw_shading_plane(self, raw_set=0):
+        """-> the gain plane the device expanded the context's shading mesh into, uint16 (H, W) (lt_get_raw_shading_plane; `raw_set`:
+        that set's, lt_get_raw_shading_plane_of)."""
         out = np.empty((self.img_h, self.img_w), np.uint16)
+        if raw_set:
+            _check(self.lib.lt_get_raw_shading_plane_of(self._h, int(raw_set), out.ctypes.data))
+            return out
         _check(self.lib.lt_get_raw_shading_plane(self._h, out.ctypes.data))
         return out
+
+    # -- raw sets: cameras of different raw tables, colour stages and shading maps in one context, one set per slot
+    def add_raw_set(self):
+        """A further raw set of the context, a copy of set 0's table, colour stage and shading map as they are now (lt_add_raw_set);
+        returns its id.  The setters and getters above take it as `raw_set`."""
+        i = C.c_int(0)
+        _check(self.lib.lt_add_raw_set(self._h, C.byref(i)))
+        return i.value
+
+    def raw_set_count(self):
+        n = C.c_int(0)
+        _check(self.lib.lt_raw_set_count(self._h, C.byref(n)))
+        return n.value
+
+    def set_slot_raw_sets(self, ids, first=0):
+        """Slot first + i takes raw set ids[i] (lt_set_slot_raw_sets)."""
+        a = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        _check(self.lib.lt_set_slot_raw_sets(self._h, int(first), a.shape[0], a.ctypes.data if a.shape[0] else None))
+
+    def slot_raw_sets(self, n=None, first=0):
+        """The raw sets of slots first, first + 1, ... (n of them; None: up to the capacity)."""
+        n = self.capacity - first if n is None else int(n)
+        a = np.zeros(max(n, 0), np.int32)
+        _check(self.lib.lt_get_slot_raw_sets(self._h, int(first), a.shape[0], a.ctypes.data if a.shape[0] else None))
+        return a
+
+    def last_raw_walk_form(self):
+        """Which raw walks the front end of the last mask_run launched: 0 none, 1 the one-set forms, 2 the set-per-slot forms; -1: no run yet."""
+        return int(self.lib.lt_last_raw_walk_form(self._h))
 
     def raw_stats(self, n, first=0, grid=(8, 8), rows=None, cols=None, lo=None, hi=None):
         """Statistics of the raw Bayer frames slots first .. first + n hold -- the attached surfaces where a slot has them, what was uploaded

@@ -28,6 +28,11 @@
 //                      for two; mipi_arith.h), STAGES 1, 3, 5, 7: the 16-bit forms with every window row (every site, every 16 columns of
 //                      the row conversion) unpacked into 16-bit words on its way in -- the same 96-bit window loads, table, LDS and
 //                      staging; byte permutes and packed shifts with selectors found once per walk, no memory instruction added
+//   k_rawset_walk_rows<PATTERN, SRC, STAGES>, k_packset_walk_rows<PATTERN, SRC, STAGES, PACK>, k_rawset_rows_rgb<PATTERN, SURF, WIDE, STAGES>,
+//   k_packset_rows_rgb<.., PACK>  the four raw kernels above for a launch whose slots mix raw sets (lt_add_raw_set): a workgroup serves one
+//                      slot and takes the operands the one-set kernels get as their RawStages from its slot's entry of the context's
+//                      table of raw sets (raw_setup.h: RawSetEntry), by scalar loads; STAGES is the union of what the sets have.  The
+//                      bodies are the one-set kernels', shared as device functions (raw_walk, mipi_walk, raw_rows)
 //   k_warp_split       cv2.warpPerspective      lane_tracker.py:834
 //                      + img[:,:,0]             lane_tracker.py:207
 //                      + cvtColor(RGB2LAB)[:,:,2] lane_tracker.py:208
@@ -715,23 +720,24 @@ struct RawFormatOf {
     using type = std::conditional_t<CC, ColorStage<Shaded>, Shaded>;
 };
 extern __shared__ __attribute__((aligned(16))) uint8_t s_lut_wide[];
-template <int PATTERN, int SRC, bool PER_SLOT, int STAGES>
-__global__ __launch_bounds__(256) void k_raw_walk_rows(const SurfEntry* __restrict__ tab, const uint8_t* __restrict__ frames, size_t stride,
-                                                      const int16_t* __restrict__ uxy, const uint16_t* __restrict__ ufrac,
-                                                      const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
-                                                      uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb, int remap,
-                                                      RawStages r) {
-    static_assert(SRC == SRC_SURFACES || SRC == SRC_SLOTS, "a raw Bayer staging frame is dword-aligned");
-    constexpr bool W16 = (STAGES & 1) != 0, CC = (STAGES & 2) != 0, LS = (STAGES & 4) != 0;
-    constexpr int CURVE = CC ? 256 : 0;
-    uint8_t* lds;
+// where a raw kernel stages: the launch's dynamic LDS (16-bit samples) or CURVE + 1024 bytes of static LDS
+template <bool W16, int CURVE>
+__device__ __forceinline__ uint8_t* raw_lds() {
     if constexpr (W16) {
-        lds = s_lut_wide;
+        return s_lut_wide;
     } else {
         __shared__ alignas(16) uint8_t s_tab[CURVE + 1024];
-        lds = s_tab;
+        return s_tab;
     }
-    const WalkArgs a{uxy, ufrac, SlotTables{sets, &ids}, g, und, und_px, first_slot, n, PER_SLOT ? 1 : fpb, remap};
+}
+// the bodies of the raw walks: the format of STAGES made of `r`, then the one walk.  Shared by the kernels that are given `r` and by those
+// that find it in their slot's raw set (k_rawset_walk_rows, k_packset_walk_rows)
+template <int PATTERN, int SRC, bool PER_SLOT, int STAGES>
+__device__ __forceinline__ void raw_walk(const WalkArgs& a, uint8_t* lds, const SurfEntry* __restrict__ tab, const uint8_t* __restrict__ frames,
+                                         size_t stride, const RawStages& r) {
+    constexpr bool W16 = (STAGES & 1) != 0, CC = (STAGES & 2) != 0, LS = (STAGES & 4) != 0;
+    constexpr int CURVE = CC ? 256 : 0;
+    const FrontEndGeom& g = a.g;
     typename RawFormatOf<PATTERN, W16, CC, LS>::type fmt{};
     fmt.w = g.img_w, fmt.h = g.img_h, fmt.lut = lds + CURVE;
     if constexpr (W16) fmt.table = reinterpret_cast<const uint4*>(r.table), fmt.bits = r.bits, fmt.mask = (1u << r.bits) - 1u;
@@ -740,6 +746,34 @@ __global__ __launch_bounds__(256) void k_raw_walk_rows(const SurfEntry* __restri
     if constexpr (LS) fmt.shade_with(r.gains, r.blk);
     if constexpr (SRC == SRC_SURFACES) undistort_walk<PER_SLOT>(a, SurfSource{tab}, fmt);
     else undistort_walk<PER_SLOT>(a, SlotSource<true>{frames, stride}, fmt);
+}
+template <int PATTERN, int SRC, bool PER_SLOT, int STAGES, int PACK>
+__device__ __forceinline__ void mipi_walk(const WalkArgs& a, const SurfEntry* __restrict__ tab, const uint8_t* __restrict__ frames, size_t stride,
+                                          const RawStages& r) {
+    static_assert((STAGES & 1) != 0, "packed samples are 10 / 12 bits wide: behind the wide table");
+    constexpr bool CC = (STAGES & 2) != 0, LS = (STAGES & 4) != 0;
+    constexpr int CURVE = CC ? 256 : 0;
+    uint8_t* lds = s_lut_wide;
+    const FrontEndGeom& g = a.g;
+    using Unpacked = MipiUnpack<PACK, std::conditional_t<LS, ShadeStage<Bayer16Lut<PATTERN>>, Bayer16Lut<PATTERN>>>;
+    std::conditional_t<CC, ColorStage<Unpacked>, Unpacked> fmt{};
+    fmt.w = g.img_w, fmt.h = g.img_h, fmt.lut = lds + CURVE;
+    fmt.table = reinterpret_cast<const uint4*>(r.table), fmt.bits = r.bits, fmt.mask = (1u << r.bits) - 1u;
+    if constexpr (CC) fmt.cm = r.cm, fmt.curve = lds;
+    if constexpr (LS) fmt.shade_with(r.gains, r.blk);
+    if constexpr (SRC == SRC_SURFACES) undistort_walk<PER_SLOT>(a, SurfSource{tab}, fmt);
+    else undistort_walk<PER_SLOT>(a, SlotSource<true>{frames, stride}, fmt);
+}
+template <int PATTERN, int SRC, bool PER_SLOT, int STAGES>
+__global__ __launch_bounds__(256) void k_raw_walk_rows(const SurfEntry* __restrict__ tab, const uint8_t* __restrict__ frames, size_t stride,
+                                                      const int16_t* __restrict__ uxy, const uint16_t* __restrict__ ufrac,
+                                                      const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
+                                                      uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb, int remap,
+                                                      RawStages r) {
+    static_assert(SRC == SRC_SURFACES || SRC == SRC_SLOTS, "a raw Bayer staging frame is dword-aligned");
+    constexpr bool W16 = (STAGES & 1) != 0, CC = (STAGES & 2) != 0;
+    const WalkArgs a{uxy, ufrac, SlotTables{sets, &ids}, g, und, und_px, first_slot, n, PER_SLOT ? 1 : fpb, remap};
+    raw_walk<PATTERN, SRC, PER_SLOT, STAGES>(a, raw_lds<W16, CC ? 256 : 0>(), tab, frames, stride, r);
 }
 
 // ... over MIPI-packed RAW10 / RAW12 frames (PACK; mipi_arith.h): k_raw_walk_rows' 16-bit forms (STAGES 1, 3, 5, 7) with every window row
@@ -751,19 +785,43 @@ __global__ __launch_bounds__(256) void k_mipi_walk_rows(const SurfEntry* __restr
                                                        uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int fpb, int remap,
                                                        RawStages r) {
     static_assert(SRC == SRC_SURFACES || SRC == SRC_SLOTS, "a raw Bayer staging frame is dword-aligned");
-    static_assert((STAGES & 1) != 0, "packed samples are 10 / 12 bits wide: behind the wide table");
-    constexpr bool CC = (STAGES & 2) != 0, LS = (STAGES & 4) != 0;
-    constexpr int CURVE = CC ? 256 : 0;
-    uint8_t* lds = s_lut_wide;
     const WalkArgs a{uxy, ufrac, SlotTables{sets, &ids}, g, und, und_px, first_slot, n, PER_SLOT ? 1 : fpb, remap};
-    using Unpacked = MipiUnpack<PACK, std::conditional_t<LS, ShadeStage<Bayer16Lut<PATTERN>>, Bayer16Lut<PATTERN>>>;
-    std::conditional_t<CC, ColorStage<Unpacked>, Unpacked> fmt{};
-    fmt.w = g.img_w, fmt.h = g.img_h, fmt.lut = lds + CURVE;
-    fmt.table = reinterpret_cast<const uint4*>(r.table), fmt.bits = r.bits, fmt.mask = (1u << r.bits) - 1u;
-    if constexpr (CC) fmt.cm = r.cm, fmt.curve = lds;
-    if constexpr (LS) fmt.shade_with(r.gains, r.blk);
-    if constexpr (SRC == SRC_SURFACES) undistort_walk<PER_SLOT>(a, SurfSource{tab}, fmt);
-    else undistort_walk<PER_SLOT>(a, SlotSource<true>{frames, stride}, fmt);
+    mipi_walk<PATTERN, SRC, PER_SLOT, STAGES, PACK>(a, tab, frames, stride, r);
+}
+
+// The set-per-slot forms of the two walks above, for a launch whose slots mix raw sets (lt_add_raw_set): a workgroup serves ONE slot -- the
+// table-per-slot geometry, one frame per walk, which these forms always have for the calibration as well -- and takes what the one-set
+// kernels take as `r` from its slot's entry of the table of raw sets (raw_setup.h: RawSetEntry).  The slot is wave-uniform, so its set's id
+// (a byte of the kernel argument `rids`, as CalIds) and the 80 bytes of the entry arrive by scalar loads: the staged-bytes pointer, which the
+// workgroup then stages THAT set's table (and curve) from, the gain plane's pointer, which the shading stage builds its resource from, the
+// matrix and the pedestals, which stay in SGPRs.  STAGES is the union of the parts the context's sets have; a set that lacks one has its
+// identity in its entry.  Behind that prologue the walk is the walk of the one-set form, instruction for instruction.
+__device__ __forceinline__ int walk_slot_z(int remap) {          // undistort_walk's bz (fpb == 1: the walk's frame)
+    const uint32_t per_z = gridDim.x * gridDim.y;
+    return (int)(xcd_block((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x, per_z * gridDim.z, remap) / per_z);
+}
+__device__ __forceinline__ RawStages stages_of_set(const RawSetEntry* __restrict__ rsets, const CalIds& rids, int z, int bits) {
+    const RawSetEntry& e = rsets[__builtin_amdgcn_readfirstlane((rids.w[z >> 2] >> (8 * (z & 3))) & 255u)];
+    RawStages r;
+    r.table = e.table, r.bits = bits, r.cm = e.cm, r.gains = e.gains, r.blk = e.blk;
+    return r;
+}
+template <int PATTERN, int SRC, int STAGES>
+__global__ __launch_bounds__(256) void k_rawset_walk_rows(const SurfEntry* __restrict__ tab, const uint8_t* __restrict__ frames, size_t stride,
+                                                         const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
+                                                         uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int remap,
+                                                         const RawSetEntry* __restrict__ rsets, CalIds rids, int bits) {
+    constexpr bool W16 = (STAGES & 1) != 0, CC = (STAGES & 2) != 0;
+    const WalkArgs a{nullptr, nullptr, SlotTables{sets, &ids}, g, und, und_px, first_slot, n, 1, remap};
+    raw_walk<PATTERN, SRC, true, STAGES>(a, raw_lds<W16, CC ? 256 : 0>(), tab, frames, stride, stages_of_set(rsets, rids, walk_slot_z(remap), bits));
+}
+template <int PATTERN, int SRC, int STAGES, int PACK>
+__global__ __launch_bounds__(256) void k_packset_walk_rows(const SurfEntry* __restrict__ tab, const uint8_t* __restrict__ frames, size_t stride,
+                                                          const CalTables* __restrict__ sets, CalIds ids, FrontEndGeom g,
+                                                          uint32_t* __restrict__ und, size_t und_px, int first_slot, int n, int remap,
+                                                          const RawSetEntry* __restrict__ rsets, CalIds rids, int bits) {
+    const WalkArgs a{nullptr, nullptr, SlotTables{sets, &ids}, g, und, und_px, first_slot, n, 1, remap};
+    mipi_walk<PATTERN, SRC, true, STAGES, PACK>(a, tab, frames, stride, stages_of_set(rsets, rids, walk_slot_z(remap), bits));
 }
 
 // The expansion of a shading mesh (uint16[4][mh][mw], device memory) into the gain plane of an h x w image with `pattern`: one thread per
@@ -1171,22 +1229,16 @@ __global__ __launch_bounds__(256) void k_rows_to_rgb(std::conditional_t<SURF, Su
 // for the byte-wise one), STAGES and `r` as k_raw_walk_rows takes them.  The table, and the curve in front of it, are staged in 16-byte
 // pieces by the whole workgroup before any thread leaves: static LDS for 8-bit samples, the launch's dynamic LDS for 16-bit ones.  Launched
 // in k_rows_to_rgb's place whenever there is a table.
-template <int PATTERN, bool SURF, bool WIDE, int STAGES>
-__global__ __launch_bounds__(256) void k_raw_rows_rgb(std::conditional_t<SURF, SurfChunk, DenseFrames> src, uint8_t* __restrict__ rgb,
-                                                     size_t rgb_stride, int w, int r0, int h, RawStages r) {
+// (the body: shared by the kernels that are given `r` and by those that find it in their frame's raw set, k_rawset_rows_rgb / k_packset_rows_rgb)
+template <int PATTERN, bool SURF, bool WIDE, int STAGES, int PACK>
+__device__ __forceinline__ void raw_rows(uint8_t* lds, const std::conditional_t<SURF, SurfChunk, DenseFrames>& src, uint8_t* __restrict__ rgb,
+                                         size_t rgb_stride, int w, int r0, int h, const RawStages& r) {
     constexpr bool W16 = (STAGES & 1) != 0, CC = (STAGES & 2) != 0, LS = (STAGES & 4) != 0;
     constexpr int THREADS = WIDE ? 64 : 256, CURVE = CC ? 256 : 0;
-    uint8_t* lds;
-    if constexpr (W16) {
-        lds = s_lut_wide;
-    } else {
-        __shared__ alignas(16) uint8_t s_tab[CURVE + 1024];
-        lds = s_tab;
-    }
     const int bits = W16 ? r.bits : 8;
     for (int i = threadIdx.x; i < CURVE / 16 + (1 << (bits - 2)); i += THREADS) reinterpret_cast<uint4*>(lds)[i] = reinterpret_cast<const uint4*>(r.table)[i];
     __syncthreads();
-    typedef RowsRaw<PATTERN, W16, LS> D;
+    typedef RowsRaw<PATTERN, W16, LS, PACK> D;
     const D body{lds + CURVE, bits, (1u << bits) - 1u, r.gains, r.blk};
     Planes p;
     if constexpr (SURF) p = surf_planes(src.e[blockIdx.z]);
@@ -1198,6 +1250,12 @@ __global__ __launch_bounds__(256) void k_raw_rows_rgb(std::conditional_t<SURF, S
     if constexpr (WIDE) body.wide(p, dst, h, w, row, i * 16, post);
     else body.any(p, dst, h, w, row, i, post);
 }
+template <int PATTERN, bool SURF, bool WIDE, int STAGES>
+__global__ __launch_bounds__(256) void k_raw_rows_rgb(std::conditional_t<SURF, SurfChunk, DenseFrames> src, uint8_t* __restrict__ rgb,
+                                                     size_t rgb_stride, int w, int r0, int h, RawStages r) {
+    constexpr bool W16 = (STAGES & 1) != 0, CC = (STAGES & 2) != 0;
+    raw_rows<PATTERN, SURF, WIDE, STAGES, -1>(raw_lds<W16, CC ? 256 : 0>(), src, rgb, rgb_stride, w, r0, h, r);
+}
 
 // ... over MIPI-packed RAW10 / RAW12 rows (PACK): k_raw_rows_rgb's 16-bit forms, RowsRaw's two bodies with the packed accesses.  The wide body
 // needs every base and pitch of the frames a multiple of 4 only (and those of the RGB frames a multiple of 16, as ever).
@@ -1205,23 +1263,22 @@ template <int PATTERN, bool SURF, bool WIDE, int STAGES, int PACK>
 __global__ __launch_bounds__(256) void k_mipi_rows_rgb(std::conditional_t<SURF, SurfChunk, DenseFrames> src, uint8_t* __restrict__ rgb,
                                                       size_t rgb_stride, int w, int r0, int h, RawStages r) {
     static_assert((STAGES & 1) != 0, "packed samples are 10 / 12 bits wide: behind the wide table");
-    constexpr bool CC = (STAGES & 2) != 0, LS = (STAGES & 4) != 0;
-    constexpr int THREADS = WIDE ? 64 : 256, CURVE = CC ? 256 : 0;
-    uint8_t* lds = s_lut_wide;
-    const int bits = r.bits;
-    for (int i = threadIdx.x; i < CURVE / 16 + (1 << (bits - 2)); i += THREADS) reinterpret_cast<uint4*>(lds)[i] = reinterpret_cast<const uint4*>(r.table)[i];
-    __syncthreads();
-    typedef RowsRaw<PATTERN, true, LS, PACK> D;
-    const D body{lds + CURVE, bits, (1u << bits) - 1u, r.gains, r.blk};
-    Planes p;
-    if constexpr (SURF) p = surf_planes(src.e[blockIdx.z]);
-    else p = D::dense(src.p + (size_t)blockIdx.z * src.stride, h, w);
-    uint8_t* dst = rgb + (size_t)blockIdx.z * rgb_stride;
-    const int i = (int)(blockIdx.x * THREADS + threadIdx.x), row = r0 + (int)blockIdx.y;
-    std::conditional_t<CC, ColorPost, NoPost> post{};
-    if constexpr (CC) post = ColorPost{r.cm, lds};
-    if constexpr (WIDE) body.wide(p, dst, h, w, row, i * 16, post);
-    else body.any(p, dst, h, w, row, i, post);
+    raw_rows<PATTERN, SURF, WIDE, STAGES, PACK>(s_lut_wide, src, rgb, rgb_stride, w, r0, h, r);
+}
+
+// The set-per-slot forms of the two row conversions above: frame blockIdx.z of the launch is conditioned with its slot's raw set -- id byte
+// blockIdx.z of `rids`, entry rsets[id], by scalar loads, as in k_rawset_walk_rows -- and the workgroup stages that set's table.
+template <int PATTERN, bool SURF, bool WIDE, int STAGES>
+__global__ __launch_bounds__(256) void k_rawset_rows_rgb(std::conditional_t<SURF, SurfChunk, DenseFrames> src, uint8_t* __restrict__ rgb,
+                                                        size_t rgb_stride, int w, int r0, int h, const RawSetEntry* __restrict__ rsets, CalIds rids, int bits) {
+    constexpr bool W16 = (STAGES & 1) != 0, CC = (STAGES & 2) != 0;
+    raw_rows<PATTERN, SURF, WIDE, STAGES, -1>(raw_lds<W16, CC ? 256 : 0>(), src, rgb, rgb_stride, w, r0, h, stages_of_set(rsets, rids, (int)blockIdx.z, bits));
+}
+template <int PATTERN, bool SURF, bool WIDE, int STAGES, int PACK>
+__global__ __launch_bounds__(256) void k_packset_rows_rgb(std::conditional_t<SURF, SurfChunk, DenseFrames> src, uint8_t* __restrict__ rgb,
+                                                         size_t rgb_stride, int w, int r0, int h, const RawSetEntry* __restrict__ rsets, CalIds rids, int bits) {
+    static_assert((STAGES & 1) != 0, "packed samples are 10 / 12 bits wide: behind the wide table");
+    raw_rows<PATTERN, SURF, WIDE, STAGES, PACK>(s_lut_wide, src, rgb, rgb_stride, w, r0, h, stages_of_set(rsets, rids, (int)blockIdx.z, bits));
 }
 
 // Rows [r0, r1) of RGB surfaces -> the same rows of the slots' camera frames (row_bytes = 3 w, dense): a pitched row copy, one
@@ -1682,15 +1739,38 @@ static void with_stages(const RawStages& raw, F&& f) {
 // the dynamic LDS of a raw kernel: the wide table, behind the curve where there is a colour stage (8-bit samples: static LDS)
 static size_t raw_dynamic_lds(const RawStages& raw) { return raw.bits > 8 ? ((size_t)4 << raw.bits) + (raw.color ? 256 : 0) : 0; }
 
+static CalIds pack_ids(const uint8_t* ids, int m) {
+    CalIds c{};
+    for (int i = 0; i < m; ++i) c.w[i >> 2] |= (uint32_t)ids[i] << (8 * (i & 3));
+    return c;
+}
+
 // One launch of the walk over the n frames of `src`: behind a raw table the raw walk, else the walk of the layout.  Plain RGB frames of the
 // slots that are not dword-aligned, dword-strided and below 2^30 bytes (a larger frame: 64-bit addresses) -- or all of them, any_byte --
 // take the form that fetches at any byte.
 template <bool PER_SLOT>
 static void launch_walk(hipStream_t s, dim3 grid, FrameSource src, int layout, YuvCoef k, const int16_t* uxy, const uint16_t* ufrac,
                         const CalTables* sets, const CalIds& ids, FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n, int fpb,
-                        bool any_byte, const RawStages& raw) {
+                        bool any_byte, const RawStages& raw, const RawSetEntry* rsets = nullptr, const CalIds& rids = CalIds{}) {
     const bool aligned = !any_byte && ((uintptr_t)src.frames & 3) == 0 && (src.stride & 3) == 0 && src.stride < (1u << 30);
     const int remap = xcd_remap();
+    if constexpr (PER_SLOT) {
+        if (raw.table && rsets) {            // the slots mix raw sets: the set-per-slot forms, `raw` saying which
+            with_pattern(layout, [&](auto p) {
+                with_stages(raw, [&](auto st) {
+                    constexpr int P = decltype(p)::value, ST = decltype(st)::value;
+                    auto k_walk = src.tab ? k_rawset_walk_rows<P, SRC_SURFACES, ST> : k_rawset_walk_rows<P, SRC_SLOTS, ST>;
+                    if constexpr ((ST & 1) != 0) {
+                        if (raw.pack == ma::PACK10) k_walk = src.tab ? k_packset_walk_rows<P, SRC_SURFACES, ST, ma::PACK10> : k_packset_walk_rows<P, SRC_SLOTS, ST, ma::PACK10>;
+                        else if (raw.pack == ma::PACK12) k_walk = src.tab ? k_packset_walk_rows<P, SRC_SURFACES, ST, ma::PACK12> : k_packset_walk_rows<P, SRC_SLOTS, ST, ma::PACK12>;
+                    }
+                    hipLaunchKernelGGL(k_walk, grid, dim3(256), raw_dynamic_lds(raw), s, src.tab, src.frames, src.stride, sets, ids, g, und, und_px,
+                                       first_slot, n, remap, rsets, rids, raw.bits);
+                });
+            });
+            return;
+        }
+    }
     if (raw.table) {
         with_pattern(layout, [&](auto p) {
             with_stages(raw, [&](auto st) {
@@ -1734,10 +1814,26 @@ void launch_undistort_rows(hipStream_t s, FrameSource src, int layout, YuvCoef k
 // same two launch shapes.  MIPI-packed rows (raw.pack) are read in dwords: multiples of 4 there, of 16 on the RGB side.
 template <bool SURF, class Src>
 static void launch_rows_to_rgb(hipStream_t s, int layout, const Src& src, size_t bits, YuvCoef k, uint8_t* rgb, size_t rgb_stride, int h, int w,
-                               int r0, int r1, int n, const RawStages& raw) {
+                               int r0, int r1, int n, const RawStages& raw, const RawSetEntry* rsets = nullptr, const uint8_t* rids = nullptr) {
     const bool packed = raw.table && raw.pack >= 0;
     const bool wide = (w & 15) == 0 && (packed ? (bits & 3) == 0 && ((rgb_stride | (size_t)(uintptr_t)rgb) & 15) == 0 : (bits & 15) == 0);
     const dim3 block(wide ? 64 : 256);
+    if (raw.table && rids) {                 // the frames mix raw sets (n <= CalIds::N): the set-per-slot forms, `raw` saying which
+        const dim3 grid((unsigned)(wide ? (w / 16 + 63) / 64 : (w + 255) / 256), (unsigned)(r1 - r0), (unsigned)n);
+        const CalIds ci = pack_ids(rids, n);
+        with_pattern(layout, [&](auto p) {
+            with_stages(raw, [&](auto st) {
+                constexpr int P = decltype(p)::value, ST = decltype(st)::value;
+                auto k_rows = wide ? k_rawset_rows_rgb<P, SURF, true, ST> : k_rawset_rows_rgb<P, SURF, false, ST>;
+                if constexpr ((ST & 1) != 0) {
+                    if (raw.pack == ma::PACK10) k_rows = wide ? k_packset_rows_rgb<P, SURF, true, ST, ma::PACK10> : k_packset_rows_rgb<P, SURF, false, ST, ma::PACK10>;
+                    else if (raw.pack == ma::PACK12) k_rows = wide ? k_packset_rows_rgb<P, SURF, true, ST, ma::PACK12> : k_packset_rows_rgb<P, SURF, false, ST, ma::PACK12>;
+                }
+                hipLaunchKernelGGL(k_rows, grid, block, raw_dynamic_lds(raw), s, src, rgb, rgb_stride, w, r0, h, rsets, ci, raw.bits);
+            });
+        });
+        return;
+    }
     if (raw.table) {
         const dim3 grid((unsigned)(wide ? (w / 16 + 63) / 64 : (w + 255) / 256), (unsigned)(r1 - r0), (unsigned)n);
         with_pattern(layout, [&](auto p) {
@@ -1766,8 +1862,18 @@ static void launch_rows_to_rgb(hipStream_t s, int layout, const Src& src, size_t
 }
 
 void launch_yuv_rows_to_rgb(hipStream_t s, int layout, const uint8_t* yuv, size_t yuv_stride, YuvCoef k, uint8_t* rgb,
-                            size_t rgb_stride, int h, int w, int r0, int r1, int n, const RawStages& raw) {
+                            size_t rgb_stride, int h, int w, int r0, int r1, int n, const RawStages& raw, const RawSetEntry* rsets, const uint8_t* rids) {
     if (n <= 0 || r1 <= r0) return;
+    if (raw.table && rids) {                 // the set-per-slot forms: CalIds::N frames per launch
+        for (int i = 0; i < n; i += CalIds::N) {
+            const int m = std::min(n - i, (int)CalIds::N);
+            const uint8_t* src = yuv + (size_t)i * yuv_stride;
+            uint8_t* dst = rgb + (size_t)i * rgb_stride;
+            launch_rows_to_rgb<false>(s, layout, DenseFrames{src, yuv_stride}, yuv_stride | rgb_stride | (size_t)(uintptr_t)src | (size_t)(uintptr_t)dst, k,
+                                      dst, rgb_stride, h, w, r0, r1, m, raw, rsets, rids + i);
+        }
+        return;
+    }
     launch_rows_to_rgb<false>(s, layout, DenseFrames{yuv, yuv_stride}, yuv_stride | rgb_stride | (size_t)(uintptr_t)yuv | (size_t)(uintptr_t)rgb, k,
                               rgb, rgb_stride, h, w, r0, r1, n, raw);
 }
@@ -1786,7 +1892,7 @@ void launch_write_surf_entries(hipStream_t s, SurfEntry* tab, int first, const S
 }
 
 void launch_surf_rows_to_rgb(hipStream_t s, int layout, const SurfEntry* entries, YuvCoef k, uint8_t* rgb, size_t rgb_stride, int h, int w,
-                             int r0, int r1, int n, const RawStages& raw) {
+                             int r0, int r1, int n, const RawStages& raw, const RawSetEntry* rsets, const uint8_t* rids) {
     if (n <= 0 || r1 <= r0) return;
     for (int i = 0; i < n; i += SurfChunk::N) {
         const int m = std::min(n - i, (int)SurfChunk::N);
@@ -1806,7 +1912,7 @@ void launch_surf_rows_to_rgb(hipStream_t s, int layout, const SurfEntry* entries
             else
                 hipLaunchKernelGGL(k_surf_copy_rows<false>, dim3((unsigned)((row_bytes + 255) / 256), (unsigned)(r1 - r0), (unsigned)m), dim3(256), 0, s, ch, dst, rgb_stride, row_bytes, r0);
         } else {
-            launch_rows_to_rgb<true>(s, layout, ch, bits, k, dst, rgb_stride, h, w, r0, r1, m, raw);
+            launch_rows_to_rgb<true>(s, layout, ch, bits, k, dst, rgb_stride, h, w, r0, r1, m, raw, rsets, rids ? rids + i : nullptr);
         }
     }
 }
@@ -1829,20 +1935,16 @@ void launch_warp_split(hipStream_t s, const uint32_t* und, size_t und_px, int fi
     }
 }
 
-static CalIds pack_ids(const uint8_t* ids, int m) {
-    CalIds c{};
-    for (int i = 0; i < m; ++i) c.w[i >> 2] |= (uint32_t)ids[i] << (8 * (i & 3));
-    return c;
-}
-
 void launch_undistort_cal(hipStream_t s, FrameSource src, int layout, YuvCoef k, const CalTables* sets, const uint8_t* ids,
-                          FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n, const RawStages& raw) {
+                          FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n, const RawStages& raw, const RawSetEntry* rsets,
+                          const uint8_t* rids) {
     if (n <= 0 || g.nrows <= 0) return;
     for (int i = 0; i < n; i += CalIds::N) {
         const int m = std::min(n - i, (int)CalIds::N);
         const dim3 grid((g.img_w + 255) / 256, g.nrows, m);
         const FrameSource part = src.tab ? src : FrameSource::slots(src.frames + (size_t)i * src.stride, src.stride);
-        launch_walk<true>(s, grid, part, layout, k, nullptr, nullptr, sets, pack_ids(ids + i, m), g, und, und_px, first_slot + i, m, 1, false, raw);
+        launch_walk<true>(s, grid, part, layout, k, nullptr, nullptr, sets, pack_ids(ids + i, m), g, und, und_px, first_slot + i, m, 1, false, raw,
+                          rids ? rsets : nullptr, rids ? pack_ids(rids + i, m) : CalIds{});
     }
 }
 

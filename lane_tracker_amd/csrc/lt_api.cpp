@@ -219,6 +219,7 @@ void free_slots(lt_ctx* c) {
     c->annot_full.clear();
     c->front_ok.clear();
     c->slot_cal.clear();
+    c->slot_raw.clear();
     dev_free(c->d_rec);
     dev_free(c->d_prev);
     dev_free(c->d_pix);
@@ -746,6 +747,7 @@ void lt_destroy(lt_ctx* c) {
     dev_free(c->d_coef);
     dev_free(c->d_rs_xt);
     dev_free(c->d_rs_yt);
+    raw_sets_release(c);
     raw_release(c->raw_dev);
     dev_free(c->d_stats);
     dev_free(c->d_oxy);
@@ -795,6 +797,7 @@ int lt_reserve(lt_ctx* c, int capacity) {
     c->annot_full.assign(n, 0);
     c->front_ok.assign(n, 0);
     c->slot_cal.assign(n, 0);            // every slot starts with set 0
+    c->slot_raw.assign(n, 0);            // ... and with raw set 0
     if ((rc = dev_alloc(&c->d_rec, n))) { free_slots(c); return rc; }
     if ((rc = dev_alloc(&c->d_prev, n * 6))) { free_slots(c); return rc; }
     c->capacity = capacity;
@@ -1665,6 +1668,21 @@ static int build_undistortion(const lt_calib& k, int r0, int r1, int U0, int U1,
     }
     return LT_OK;
 }
+// The set table for a context that has one calibration set only: the set-per-slot raw forms take the calibration's table per slot too.
+int ensure_cal_table(lt_ctx* c) {
+    if (c->d_cal) return LT_OK;
+    int rc = dev_alloc(&c->d_cal, (size_t)LT_MAX_CALIBRATIONS);
+    if (rc) return rc;
+    refresh_cal0(c);
+    const lt_ctx::CalSet& q = c->cal[0];
+    const CalTables t{q.d_uxy, q.d_ufrac, q.d_wxy, q.d_wfrac};
+    if (hipMemcpy(c->d_cal, &t, sizeof t, hipMemcpyHostToDevice) != hipSuccess) {
+        dev_free(c->d_cal);
+        return fail(LT_ERR_HIP, "table upload failed: %s", hipGetErrorString(hipGetLastError()));
+    }
+    return LT_OK;
+}
+
 }  // namespace lt
 extern "C" {
 
@@ -1818,6 +1836,8 @@ static int mask_run_impl(lt_ctx* c, int first, int n, const lt_filter_params* p,
     }
     const size_t ps = c->masks.plane_bytes;
     const ChainEnv env = chain_env(c);
+    if ((rc = raw_sets_ready(c))) return rc;
+    c->last_raw_walk_form = 0;
     rc = for_each_slice(c, first, n, [&](hipStream_t st, int f0, int m) {
         // the front end -- unless the caller asked for a RE-run (lt_mask_rerun: the second try of a frame, other filter parameters
         // over the same bird's-eye planes) and these slots' planes are those of the frames they hold
@@ -1838,8 +1858,12 @@ static int mask_run_impl(lt_ctx* c, int first, int n, const lt_filter_params* p,
                   const FrameSource src = att ? FrameSource::surfaces(c->d_surf)
                                           : c->in_layout != LT_INPUT_RGB ? FrameSource::slots(slot_yuv(c, a), c->yuv_stride)
                                                                          : FrameSource::slots(slot_frame(c, a), c->frame_bytes);
-                  if (mixed) launch_undistort_cal(st, src, c->in_layout, yuv_coef_of(c), c->d_cal, &c->slot_cal[(size_t)a], c->fe, c->d_und, c->und_px, a, b - a, raw_stages_of(c));
-                  else launch_undistort_rows(st, src, c->in_layout, yuv_coef_of(c), cs.d_uxy, cs.d_ufrac, c->fe, c->d_und, c->und_px, a, b - a, raw_stages_of(c));
+                  // One raw set in the run -- whichever -- : today's kernels with that set's stages; several: the set-per-slot forms, which
+                  // take the calibration's table per slot as well
+                  const RawRun raw = raw_run_of(c, a, b - a);
+                  if (raw.one.table) c->last_raw_walk_form = std::max(c->last_raw_walk_form, raw.ids ? 2 : 1);
+                  if (mixed || raw.ids) launch_undistort_cal(st, src, c->in_layout, yuv_coef_of(c), c->d_cal, &c->slot_cal[(size_t)a], c->fe, c->d_und, c->und_px, a, b - a, raw.one, raw.sets, raw.ids);
+                  else launch_undistort_rows(st, src, c->in_layout, yuv_coef_of(c), cs.d_uxy, cs.d_ufrac, c->fe, c->d_und, c->und_px, a, b - a, raw.one);
               } }
             { int mrc = n == 1 ? note_range_frame(c, c->readers, st, f0, f0 + m) : note_range(c->readers, st, f0, f0 + m); if (mrc) return mrc; }
             { StageScope t(c, ST_WARP_SPLIT, st);

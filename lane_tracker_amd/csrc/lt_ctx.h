@@ -169,6 +169,23 @@ struct lt_ctx {
     // makes it the context's; raw_stages_of is what the launches read.  raw.layout is in_layout while that is a raw layout.
     lt::RawSetup raw;
     lt::RawDevice raw_dev;
+    // Raw sets (lt_add_raw_set), held as calibration sets are: set 0 is `raw` / `raw_dev` above, sets 1 .. are raw_more[id - 1]; slot_raw: the
+    // set of every slot.  A launch whose slots have ONE set runs today's kernels with that set's RawStages (raw_stages_of); one that mixes sets
+    // runs the set-per-slot forms with the stages of the union of the sets (raw_union) and reads d_raw_sets, one RawSetEntry per set, written by
+    // raw_sets_refresh behind every change: a set whose own staged bytes are not the union's form has them again in that form (union_table),
+    // and the sets without a map share d_unit_gain, one plane of unit gains.
+    struct RawSet {
+        lt::RawSetup s;
+        lt::RawDevice d;
+    };
+    std::vector<RawSet> raw_more;
+    struct UnionTable { uint32_t* p = nullptr; size_t bytes = 0; };
+    std::vector<UnionTable> union_table;      // [id]; p null: the set's own staged bytes are in the union's form
+    std::vector<uint8_t> slot_raw;
+    lt::RawSetEntry* d_raw_sets = nullptr;
+    uint16_t* d_unit_gain = nullptr;
+    lt::RawUnion raw_union;
+    int last_raw_walk_form = -1;              // lt_last_raw_walk_form
     // The device scratch of lt_raw_stats: the zone sums, histograms and zone counts of the call's slots, allocated by the first call (grown by
     // one that needs more), freed with the context.
     uint8_t* d_stats = nullptr;
@@ -376,7 +393,32 @@ inline int raw_packing(int layout) { return raw_pack(layout); }
 // any raw mosaic, whatever its samples: what is about the mosaic (sizes, row runs, input only) and not about bytes
 inline bool is_raw_mosaic(int layout) { return is_bayer(layout) || is_bayer_wide(layout); }
 // what the front end and the row conversion of `c` are launched with (raw_setup.h)
-inline RawStages raw_stages_of(const lt_ctx* c) { return raw_stages(c->raw, c->raw_dev); }
+// of raw set `id` (0: the context's own, which is what everything that has no slot -- the one-shot converters -- keeps)
+inline int raw_set_count(const lt_ctx* c) { return 1 + (int)c->raw_more.size(); }
+inline const RawSetup& raw_set_of(const lt_ctx* c, int id) { return id > 0 ? c->raw_more[(size_t)id - 1].s : c->raw; }
+inline const RawDevice& raw_dev_of(const lt_ctx* c, int id) { return id > 0 ? c->raw_more[(size_t)id - 1].d : c->raw_dev; }
+inline RawStages raw_stages_of(const lt_ctx* c, int id = 0) { return raw_stages(raw_set_of(c, id), raw_dev_of(c, id)); }
+inline int slot_raw_set(const lt_ctx* c, int s) { return s >= 0 && s < (int)c->slot_raw.size() ? c->slot_raw[(size_t)s] : 0; }
+// How the raw kernels of a launch over slots [first, first + n) find their stages: all slots one set -- `ids` null, `one` that set's stages,
+// today's kernels -- or several sets: `one` says which kernel (the union's stages), sets / ids (one byte per slot, host memory) what each slot reads.
+struct RawRun {
+    RawStages one;
+    const RawSetEntry* sets = nullptr;
+    const uint8_t* ids = nullptr;
+};
+inline RawRun raw_run_of(const lt_ctx* c, int first, int n) {
+    RawRun r;
+    const int id0 = slot_raw_set(c, first);
+    bool mixed = false;
+    for (int i = first + 1; i < first + n && !mixed; ++i) mixed = slot_raw_set(c, i) != id0;
+    if (!mixed || !c->raw_union.staged || !c->d_raw_sets) {       // (sets that stage nothing differ in nothing a kernel reads)
+        r.one = raw_stages_of(c, mixed ? 0 : id0);
+        return r;
+    }
+    r.one = raw_union_stages(c->in_layout, c->raw_union, c->d_raw_sets);
+    r.sets = c->d_raw_sets, r.ids = &c->slot_raw[(size_t)first];
+    return r;
+}
 inline int packed_bpp(int layout) {
     return layout == LT_INPUT_RGB || layout == LT_INPUT_BGR ? 3 : layout == LT_INPUT_RGBA || layout == LT_INPUT_BGRA ? 4
            : layout == LT_INPUT_YUY2 || layout == LT_INPUT_UYVY || (is_bayer_wide(layout) && raw_packing(layout) < 0) ? 2 : is_bayer(layout) ? 1 : 0;
@@ -417,6 +459,14 @@ void refresh_cal0(lt_ctx* c);                                       // cal[0] :=
 // with nothing written leaves `d` as it was; a failed expansion has taken the map out of `s` AND `d` (better none than one they disagree on).
 int raw_commit(RawSetup& s, RawDevice& d, bool new_map, hipStream_t st, int h, int w);
 void raw_release(RawDevice& d);
+void raw_sets_release(lt_ctx* c);                                   // sets 1 .., the set table, the union forms, the plane of unit gains (lt_destroy)
+int ensure_cal_table(lt_ctx* c);                                    // lt_api.cpp: d_cal exists and holds set 0 (the set-per-slot raw forms read it)
+// before a launch that may mix raw sets: the set table is there (a failed rewrite took it away) and so is the calibrations' table
+inline int raw_sets_ready(lt_ctx* c) {
+    if (c->raw_more.empty()) return LT_OK;
+    if (!c->d_raw_sets) return fail(LT_ERR_STATE, "the table of raw sets could not be written when a set last changed: set one again");
+    return ensure_cal_table(c);
+}
 // lt_set_input_format: a raw table stays with 8-bit Bayer, stage and map go, a wide layout has its default staged -- before anything else changes
 int raw_take_layout(lt_ctx* c, int layout);
 int check_raw_size(int layout, int h, int w);                       // a frame of a raw layout: even sides from 4, RAW10 rows whole groups

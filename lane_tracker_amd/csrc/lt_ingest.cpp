@@ -113,10 +113,12 @@ struct Ingest {
 
     // Camera rows [a, b) of the RGB camera frames of slots [first, first + n) from what was copied, on `st`.
     int finish(hipStream_t st, int first, int n, int a, int b) const {
-        if (kind == STAGED)
+        if (kind == STAGED) {
+            if (int rc = raw_sets_ready(c)) return rc;
+            const RawRun raw = raw_run_of(c, first, n);
             launch_yuv_rows_to_rgb(st, c->in_layout, slot_yuv(c, first), c->yuv_stride, yuv_coef_of(c), slot_frame(c, first), c->frame_bytes,
-                                   c->calib.img_h, c->calib.img_w, a, b, n, raw_stages_of(c));
-        else if (kind == RESIZED)
+                                   c->calib.img_h, c->calib.img_w, a, b, n, raw.one, raw.sets, raw.ids);
+        } else if (kind == RESIZED)
             launch_resize_rows(st, slot_src(c, first), c->src_stride, c->src_bytes, c->src_w, slot_frame(c, first), c->frame_bytes, c->calib.img_w,
                                a, b, c->d_rs_xt, c->d_rs_yt, n);
         else
@@ -466,9 +468,11 @@ int lt_device_frames_rest(lt_ctx* c, int first, int n, const int32_t* rows4) {
     if ((rc = set_device(c))) return rc;
     // as lt_upload_frame_rest: on the copy stream, behind the overlays that still read the camera frames these rows replace
     if ((rc = wait_camera_readers(c, c->copy, first, n))) return rc;
+    if ((rc = raw_sets_ready(c))) return rc;
+    const RawRun raw = raw_run_of(c, first, n);
     for (int k = 0; k < 4; k += 2)
         launch_surf_rows_to_rgb(c->copy, c->in_layout, &c->surf[(size_t)first], yuv_coef_of(c), slot_frame(c, first), c->frame_bytes,
-                                c->calib.img_h, c->calib.img_w, runs.r[k], runs.r[k + 1], n, raw_stages_of(c));
+                                c->calib.img_h, c->calib.img_w, runs.r[k], runs.r[k + 1], n, raw.one, raw.sets, raw.ids);
     HIP_TRY(hipGetLastError());
     if ((rc = note_range(c->readers, c->copy, first, first + n))) return rc;      // it reads the surfaces and writes the camera frames: the next upload waits
     if (!rows4) mark_frames(c, first, n, 1);

@@ -80,7 +80,8 @@ struct RawStatsJob {
 // rows [r0, r1) of n dense frames of h x w in `layout` (any but 0; the layouts: launch_undistort_rows) -> the same rows of n RGB frames
 // (k_rows_to_rgb<layout, false, ..>; behind a raw table k_raw_rows_rgb<pattern, false, ..>)
 void launch_yuv_rows_to_rgb(hipStream_t s, int layout, const uint8_t* yuv, size_t yuv_stride, YuvCoef k, uint8_t* rgb,
-                            size_t rgb_stride, int h, int w, int r0, int r1, int n, const RawStages& raw = RawStages());
+                            size_t rgb_stride, int h, int w, int r0, int r1, int n, const RawStages& raw = RawStages(),
+                            const RawSetEntry* rsets = nullptr, const uint8_t* rids = nullptr);
 // Input frames of another size (lt_set_input_size; k_resize.hip): destination rows [a, b) of n RGB frames of width w, dst_stride apart, :=
 // cv2.resize(INTER_LINEAR) of n RGB staging frames of src_bytes (rows of src_w pixels), src_stride apart.  xt: two words per destination
 // column (resize_arith.h: pack_column), padded to a multiple of four columns; yt: (tap0, tap1, c0, c1) per destination row; device memory.
@@ -134,8 +135,12 @@ struct CalIds {                  // the sets of the slots of one launch
 };
 // The table-per-slot forms of the two launches above, for slots [first_slot, first_slot + n) whose sets are ids[0, n) (host memory):
 // every slot with the tables of its own set, one frame per walk; launches of up to CalIds::N slots (k_undistort_rows<layout, source, true>, k_warp_cal).
+// rids not null: the raw sets of the slots, ids of entries of `rsets` (raw_setup.h: RawSetEntry) -- the set-per-slot forms of the raw walk,
+// k_rawset_walk_rows / k_packset_walk_rows<pattern, source, stages>, `raw` saying which stages (those of the union of the sets) and nothing else;
+// likewise below and above for the row conversions (k_rawset_rows_rgb / k_packset_rows_rgb), rids[z] the set of frame z of the launch.
 void launch_undistort_cal(hipStream_t s, FrameSource src, int layout, YuvCoef k, const CalTables* sets, const uint8_t* ids,
-                          FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n, const RawStages& raw = RawStages());
+                          FrontEndGeom g, uint32_t* und, size_t und_px, int first_slot, int n, const RawStages& raw = RawStages(),
+                          const RawSetEntry* rsets = nullptr, const uint8_t* rids = nullptr);
 void launch_warp_cal(hipStream_t s, const uint32_t* und, size_t und_px, int first_slot, const CalTables* sets, const uint8_t* ids,
                      FrontEndGeom g, const uint16_t* gamma_tab, const uint16_t* cbrt_tab, const int32_t* coeffs, uint8_t* planeR,
                      uint8_t* planeB, size_t plane_stride, int n);
@@ -144,7 +149,8 @@ void launch_write_surf_entries(hipStream_t s, SurfEntry* tab, int first, const S
 // rows [r0, r1) of the n surfaces of entries[] (host memory) -> the same rows of n RGB frames of h x w: a conversion (YUV, raw Bayer), a
 // permutation (BGR, RGBA, BGRA) -- k_rows_to_rgb<layout, true, ..> -- or a pitched copy (RGB: k_surf_copy_rows)
 void launch_surf_rows_to_rgb(hipStream_t s, int layout, const SurfEntry* entries, YuvCoef k, uint8_t* rgb, size_t rgb_stride, int h, int w,
-                             int r0, int r1, int n, const RawStages& raw = RawStages());
+                             int r0, int r1, int n, const RawStages& raw = RawStages(), const RawSetEntry* rsets = nullptr,
+                             const uint8_t* rids = nullptr);
 // device sinks (k_sink.hip): n dense RGB frames of h x w, rgb_stride bytes apart -> the n surfaces of entries[] (host memory) in
 // `layout`: a pitched copy (RGB) or a conversion with coeffs[8] (4:2:0; h and w even; sink_arith.h), 32 surfaces per launch
 void launch_rgb_to_surfaces(hipStream_t s, int layout, const uint8_t* rgb, size_t rgb_stride, int h, int w, const SurfEntry* entries,

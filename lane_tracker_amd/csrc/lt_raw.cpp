@@ -91,22 +91,107 @@ void lt::raw_release(RawDevice& d) {
 // value.  Planes and camera frames computed with the old one stay what they are: the slots' front ends are marked as not run, so that a re-run
 // (lt_mask_rerun) computes them again.  c->raw := change(a copy of c->raw), on the device first (raw_commit: an error with nothing written
 // keeps the old value; a failed expansion has taken the map out of the copy, which is adopted).
-template <class F>
-static int edit(lt_ctx* c, bool new_map, F change) {
+// The table of raw sets as the set-per-slot kernels read it, := the sets as they are now -- behind every change of a set, with nothing in
+// flight.  One set: nothing to write.  An error leaves the context without a table (raw_sets_ok), so that a launch that mixes sets is refused
+// and none reads a stale entry.
+static int raw_sets_refresh(lt_ctx* c) {
+    const int k = raw_set_count(c);
+    RawUnion u;
+    for (int id = 0; id < k; ++id) raw_union_add(u, raw_set_of(c, id));
+    c->raw_union = u;
+    if (k == 1) return LT_OK;
+    auto drop = [&](int code) {
+        dev_free(c->d_raw_sets);
+        return code;
+    };
     int rc;
-    if ((rc = set_device(c))) return rc;
-    if ((rc = sync_all(c))) return rc;
-    RawSetup next = c->raw;
-    change(next);
-    rc = raw_commit(next, c->raw_dev, new_map, c->stream, c->calib.img_h, c->calib.img_w);
-    if (rc != LT_OK && !(new_map && !next.shade)) return rc;
-    c->raw = std::move(next);
-    std::fill(c->front_ok.begin(), c->front_ok.end(), (uint8_t)0);
-    return rc;
+    if (!c->d_raw_sets && (rc = dev_alloc(&c->d_raw_sets, (size_t)LT_MAX_CALIBRATIONS))) return rc;
+    const int H = c->calib.img_h, W = c->calib.img_w;
+    bool need_unit = false;
+    for (int id = 0; id < k; ++id) need_unit = need_unit || (u.shade && !raw_set_of(c, id).shade);
+    if (need_unit && !c->d_unit_gain) {                        // Q12 1.0 at every site (the 16 bytes of padding included: never used)
+        const std::vector<uint16_t> unit((size_t)H * W + 8, (uint16_t)4096);
+        if ((rc = dev_alloc(&c->d_unit_gain, unit.size()))) return drop(rc);
+        if (hipMemcpy(c->d_unit_gain, unit.data(), unit.size() * sizeof(uint16_t), hipMemcpyHostToDevice) != hipSuccess) {
+            dev_free(c->d_unit_gain);
+            return drop(fail(LT_ERR_HIP, "writing the plane of unit gains failed: %s", hipGetErrorString(hipGetLastError())));
+        }
+    }
+    if (!need_unit) dev_free(c->d_unit_gain);
+    c->union_table.resize((size_t)k);
+    std::vector<RawSetEntry> ent((size_t)k);
+    for (int id = 0; id < k; ++id) {
+        const RawSetup& s = raw_set_of(c, id);
+        const RawDevice& d = raw_dev_of(c, id);
+        lt_ctx::UnionTable& ut = c->union_table[(size_t)id];
+        const uint32_t* table = nullptr;
+        if (u.staged && s.color == u.color && raw_staged_size(s)) {     // its own bytes are the union's form
+            table = d.table;
+            dev_free(ut.p), ut.bytes = 0;
+        } else if (u.staged) {
+            const std::vector<uint8_t> t = raw_staged_as(s, u.color);
+            if (ut.bytes != t.size()) {
+                dev_free(ut.p), ut.bytes = 0;
+                if ((rc = dev_alloc(&ut.p, t.size() / 4))) return drop(rc);
+                ut.bytes = t.size();
+            }
+            if (hipMemcpy(ut.p, t.data(), t.size(), hipMemcpyHostToDevice) != hipSuccess)
+                return drop(fail(LT_ERR_HIP, "writing a raw set's table failed: %s", hipGetErrorString(hipGetLastError())));
+            table = ut.p;
+        }
+        ent[(size_t)id] = raw_set_entry(s, table, s.shade ? d.gain : c->d_unit_gain);
+    }
+    if (hipMemcpy(c->d_raw_sets, ent.data(), ent.size() * sizeof(RawSetEntry), hipMemcpyHostToDevice) != hipSuccess)
+        return drop(fail(LT_ERR_HIP, "writing the table of raw sets failed: %s", hipGetErrorString(hipGetLastError())));
+    return LT_OK;
 }
 
+void lt::raw_sets_release(lt_ctx* c) {
+    for (auto& q : c->raw_more) raw_release(q.d);
+    c->raw_more.clear();
+    for (auto& t : c->union_table) dev_free(t.p);
+    c->union_table.clear();
+    dev_free(c->d_raw_sets);
+    dev_free(c->d_unit_gain);
+    std::fill(c->slot_raw.begin(), c->slot_raw.end(), (uint8_t)0);
+    c->raw_union = RawUnion{};
+}
+
+static int check_set(lt_ctx* c, int id) {
+    if (!c) return fail(LT_ERR_INVALID, "null context");
+    if (id < 0 || id >= raw_set_count(c)) return fail(LT_ERR_INVALID, "raw set %d out of range (the context has %d)", id, raw_set_count(c));
+    return LT_OK;
+}
+
+// set `id` := change(a copy of it)
+template <class F>
+static int edit(lt_ctx* c, int id, bool new_map, F change) {
+    int rc;
+    if ((rc = check_set(c, id))) return rc;
+    if ((rc = set_device(c))) return rc;
+    if ((rc = sync_all(c))) return rc;
+    RawSetup& cur = id > 0 ? c->raw_more[(size_t)id - 1].s : c->raw;
+    RawDevice& dev = id > 0 ? c->raw_more[(size_t)id - 1].d : c->raw_dev;
+    RawSetup next = cur;
+    change(next);
+    rc = raw_commit(next, dev, new_map, c->stream, c->calib.img_h, c->calib.img_w);
+    if (rc != LT_OK && !(new_map && !next.shade)) return rc;
+    cur = std::move(next);
+    for (size_t i = 0; i < c->front_ok.size(); ++i)
+        if (slot_raw_set(c, (int)i) == id) c->front_ok[i] = 0;
+    const int rrc = raw_sets_refresh(c);
+    return rc ? rc : rrc;
+}
+
+// (the sets beyond 0 are of the old layout: they go)
 int lt::raw_take_layout(lt_ctx* c, int layout) {
-    return edit(c, false, [&](RawSetup& s) {
+    if (c && !c->raw_more.empty()) {
+        int rc;
+        if ((rc = set_device(c)) || (rc = sync_all(c))) return rc;
+        raw_sets_release(c);
+        std::fill(c->front_ok.begin(), c->front_ok.end(), (uint8_t)0);
+    }
+    return edit(c, 0, false, [&](RawSetup& s) {
         RawSetup next;
         next.layout = layout;
         if (is_bayer(layout) && is_bayer(s.layout) && s.has_table) next.table.swap(s.table), next.has_table = true;     // a raw table belongs to raw Bayer input
@@ -114,11 +199,102 @@ int lt::raw_take_layout(lt_ctx* c, int layout) {
     });
 }
 
+// ---- raw sets ------------------------------------------------------------------------------------------------------------------------------
+// A new set, a copy of set 0's value at this moment, committed to device buffers of its own.
+int lt_add_raw_set(lt_ctx* c, int* id) {
+    if (!c || !id) return fail(LT_ERR_INVALID, "null argument");
+    if (!is_raw_mosaic(c->in_layout)) return fail(LT_ERR_STATE, "raw sets condition raw Bayer input: this context's input format is another layout");
+    if (raw_set_count(c) >= LT_MAX_CALIBRATIONS) return fail(LT_ERR_CAPACITY, "a context holds at most %d raw sets", LT_MAX_CALIBRATIONS);
+    int rc;
+    if ((rc = set_device(c))) return rc;
+    if ((rc = sync_all(c))) return rc;
+    lt_ctx::RawSet q;
+    q.s = c->raw;
+    if ((rc = raw_commit(q.s, q.d, q.s.shade, c->stream, c->calib.img_h, c->calib.img_w))) {
+        raw_release(q.d);
+        return rc;
+    }
+    c->raw_more.push_back(std::move(q));
+    if ((rc = raw_sets_refresh(c))) {
+        raw_release(c->raw_more.back().d);
+        c->raw_more.pop_back();
+        (void)raw_sets_refresh(c);
+        return rc;
+    }
+    *id = raw_set_count(c) - 1;
+    return LT_OK;
+}
+
+int lt_raw_set_count(lt_ctx* c, int* count) {
+    if (!c || !count) return fail(LT_ERR_INVALID, "null argument");
+    *count = raw_set_count(c);
+    return LT_OK;
+}
+
+int lt_set_slot_raw_sets(lt_ctx* c, int first, int n, const int32_t* ids) {
+    int rc = check_slots(c, first, n);
+    if (rc) return rc;
+    if (n > 0 && !ids) return fail(LT_ERR_INVALID, "null ids");
+    for (int i = 0; i < n; ++i)
+        if (ids[i] < 0 || ids[i] >= raw_set_count(c))
+            return fail(LT_ERR_INVALID, "slot %d: raw set %d out of range (the context has %d)", first + i, ids[i], raw_set_count(c));
+    // (as lt_set_slot_calibrations: a launch carries the sets of its slots by value; a slot that changes set has planes made with another's)
+    for (int i = 0; i < n; ++i) {
+        const size_t s = (size_t)(first + i);
+        if (c->slot_raw[s] == (uint8_t)ids[i]) continue;
+        c->slot_raw[s] = (uint8_t)ids[i];
+        front_stale(c, first + i, 1);
+    }
+    return LT_OK;
+}
+
+int lt_get_slot_raw_sets(lt_ctx* c, int first, int n, int32_t* ids) {
+    int rc = check_slots(c, first, n);
+    if (rc) return rc;
+    if (n > 0 && !ids) return fail(LT_ERR_INVALID, "null ids");
+    for (int i = 0; i < n; ++i) ids[i] = slot_raw_set(c, first + i);
+    return LT_OK;
+}
+
+int lt_last_raw_walk_form(lt_ctx* c) { return c ? c->last_raw_walk_form : -1; }
+
+// ---- the setters and getters, of set `id`; the entry points without an id are set 0's -----------------------------------------------------
+// the table of any raw layout: uint8[4][entries], entries = 1 << bits
+static int check_entries(lt_ctx* c, size_t entries) {
+    if (!c) return fail(LT_ERR_INVALID, "null context");
+    if (is_bayer_wide(c->in_layout)) return check_wide(c, entries);
+    if (!is_bayer(c->in_layout)) return fail(LT_ERR_STATE, "a raw table conditions raw Bayer input: this context's input format is another layout");
+    if (entries != 256) return fail(LT_ERR_INVALID, "an 8-bit raw table has 256 entries per colour phase, got %zu", entries);
+    return LT_OK;
+}
+static int set_table(lt_ctx* c, int id, const uint8_t* lut) {
+    return edit(c, id, false, [&](RawSetup& s) { s.set_table(lut); });     // (8 bits, null under a map or a stage: the identity stays staged)
+}
+
+int lt_set_raw_lut_of(lt_ctx* c, int id, const uint8_t* lut, size_t entries) {
+    int rc = check_entries(c, entries);
+    if (!rc) rc = check_set(c, id);
+    return rc ? rc : set_table(c, id, lut);
+}
+
+// 8 bits: the table where one is set (is_set); 10 / 12 bits: the table in effect, is_set = 1
+int lt_get_raw_lut_of(lt_ctx* c, int id, uint8_t* lut, size_t entries, int* is_set) {
+    int rc = check_entries(c, entries);
+    if (!rc) rc = check_set(c, id);
+    if (rc) return rc;
+    const RawSetup& s = raw_set_of(c, id);
+    const bool wide = is_bayer_wide(c->in_layout);
+    if (is_set) *is_set = wide || s.has_table ? 1 : 0;
+    if (lut && s.has_table) std::memcpy(lut, s.table.data(), s.table.size());
+    else if (lut && wide) raw_default_table(s.bits(), lut);
+    return LT_OK;
+}
+
 int lt_set_raw_lut(lt_ctx* c, const uint8_t* lut) {
     if (!c) return fail(LT_ERR_INVALID, "null context");
     if (is_bayer_wide(c->in_layout)) return fail(LT_ERR_STATE, "a 10- / 12-bit raw Bayer context takes its table through lt_set_raw_lut_wide");
     if (!is_bayer(c->in_layout)) return fail(LT_ERR_STATE, "a raw table conditions raw Bayer input: this context's input format is another layout");
-    return edit(c, false, [&](RawSetup& s) { s.set_table(lut); });     // (null under a map or a stage: the identity stays staged)
+    return set_table(c, 0, lut);
 }
 
 int lt_get_raw_lut(lt_ctx* c, uint8_t* lut, int* is_set) {
@@ -132,37 +308,37 @@ int lt_get_raw_lut(lt_ctx* c, uint8_t* lut, int* is_set) {
 // The table of a 10- / 12-bit context: uint8[4][1 << bits], always one (null: the default again)
 int lt_set_raw_lut_wide(lt_ctx* c, const uint8_t* lut, size_t entries) {
     const int rc = check_wide(c, entries);
-    return rc ? rc : edit(c, false, [&](RawSetup& s) { s.set_table(lut); });
+    return rc ? rc : set_table(c, 0, lut);
 }
 
 int lt_get_raw_lut_wide(lt_ctx* c, uint8_t* lut, size_t entries) {
-    int rc = check_wide(c, entries);
-    if (rc) return rc;
-    if (lut && c->raw.has_table) std::memcpy(lut, c->raw.table.data(), c->raw.table.size());
-    else if (lut) raw_default_table(c->raw.bits(), lut);
-    return LT_OK;
+    const int rc = check_wide(c, entries);
+    return rc ? rc : lt_get_raw_lut_of(c, 0, lut, entries, nullptr);
 }
 
 // enable = 0 removes the stage (ccm and curve are not read)
-int lt_set_raw_color(lt_ctx* c, const int16_t* ccm, const uint8_t* curve, int enable) {
+int lt_set_raw_color_of(lt_ctx* c, int id, const int16_t* ccm, const uint8_t* curve, int enable) {
     if (!c) return fail(LT_ERR_INVALID, "null context");
     if (!is_raw_mosaic(c->in_layout)) return fail(LT_ERR_STATE, "a colour stage follows the demosaic of raw Bayer input: this context's input format is another layout");
-    return edit(c, false, [&](RawSetup& s) {
+    return edit(c, id, false, [&](RawSetup& s) {
         if (enable) s.set_color(ccm, curve);
         else s.color = false;
     });
 }
+int lt_set_raw_color(lt_ctx* c, const int16_t* ccm, const uint8_t* curve, int enable) { return lt_set_raw_color_of(c, 0, ccm, curve, enable); }
 
-int lt_get_raw_color(lt_ctx* c, int16_t* ccm, uint8_t* curve, int* is_set) {
-    if (!c) return fail(LT_ERR_INVALID, "null context");
-    if (is_set) *is_set = c->raw.color ? 1 : 0;
-    if (ccm && c->raw.color) std::memcpy(ccm, c->raw.ccm, sizeof c->raw.ccm);
-    if (curve && c->raw.color) std::memcpy(curve, c->raw.curve, sizeof c->raw.curve);
+int lt_get_raw_color_of(lt_ctx* c, int id, int16_t* ccm, uint8_t* curve, int* is_set) {
+    if (int rc = check_set(c, id)) return rc;
+    const RawSetup& s = raw_set_of(c, id);
+    if (is_set) *is_set = s.color ? 1 : 0;
+    if (ccm && s.color) std::memcpy(ccm, s.ccm, sizeof s.ccm);
+    if (curve && s.color) std::memcpy(curve, s.curve, sizeof s.curve);
     return LT_OK;
 }
+int lt_get_raw_color(lt_ctx* c, int16_t* ccm, uint8_t* curve, int* is_set) { return lt_get_raw_color_of(c, 0, ccm, curve, is_set); }
 
 // enable = 0 removes the map (mesh and black are not read) and frees the gain plane
-int lt_set_raw_shading(lt_ctx* c, const uint16_t* mesh, int mesh_w, int mesh_h, const int32_t* black, int enable) {
+int lt_set_raw_shading_of(lt_ctx* c, int id, const uint16_t* mesh, int mesh_w, int mesh_h, const int32_t* black, int enable) {
     if (!c) return fail(LT_ERR_INVALID, "null context");
     if (!is_raw_mosaic(c->in_layout)) return fail(LT_ERR_STATE, "lens shading corrects raw Bayer input: this context's input format is another layout");
     int rc;
@@ -170,15 +346,18 @@ int lt_set_raw_shading(lt_ctx* c, const uint16_t* mesh, int mesh_w, int mesh_h, 
         if (!mesh) return fail(LT_ERR_INVALID, "null mesh");
         if ((rc = check_shading(c->in_layout, mesh_w, mesh_h, black))) return rc;
     }
-    return edit(c, enable != 0, [&](RawSetup& s) {
+    return edit(c, id, enable != 0, [&](RawSetup& s) {
         if (enable) s.set_shading(mesh, mesh_w, mesh_h, black);
         else s.drop_shading();
     });
 }
+int lt_set_raw_shading(lt_ctx* c, const uint16_t* mesh, int mesh_w, int mesh_h, const int32_t* black, int enable) {
+    return lt_set_raw_shading_of(c, 0, mesh, mesh_w, mesh_h, black, enable);
+}
 
-int lt_get_raw_shading(lt_ctx* c, uint16_t* mesh, int* mesh_w, int* mesh_h, int32_t* black, int* is_set) {
-    if (!c) return fail(LT_ERR_INVALID, "null context");
-    const RawSetup& s = c->raw;
+int lt_get_raw_shading_of(lt_ctx* c, int id, uint16_t* mesh, int* mesh_w, int* mesh_h, int32_t* black, int* is_set) {
+    if (int rc = check_set(c, id)) return rc;
+    const RawSetup& s = raw_set_of(c, id);
     if (is_set) *is_set = s.shade ? 1 : 0;
     if (mesh_w) *mesh_w = s.mesh_w;
     if (mesh_h) *mesh_h = s.mesh_h;
@@ -186,15 +365,20 @@ int lt_get_raw_shading(lt_ctx* c, uint16_t* mesh, int* mesh_w, int* mesh_h, int3
     if (black && s.shade) std::memcpy(black, s.black.b, sizeof s.black.b);
     return LT_OK;
 }
+int lt_get_raw_shading(lt_ctx* c, uint16_t* mesh, int* mesh_w, int* mesh_h, int32_t* black, int* is_set) {
+    return lt_get_raw_shading_of(c, 0, mesh, mesh_w, mesh_h, black, is_set);
+}
 
-int lt_get_raw_shading_plane(lt_ctx* c, uint16_t* plane) {
+int lt_get_raw_shading_plane_of(lt_ctx* c, int id, uint16_t* plane) {
     if (!c || !plane) return fail(LT_ERR_INVALID, "null argument");
-    if (!c->raw.shade) return fail(LT_ERR_STATE, "this context has no shading map (lt_set_raw_shading)");
     int rc;
+    if ((rc = check_set(c, id))) return rc;
+    if (!raw_set_of(c, id).shade) return fail(LT_ERR_STATE, "this context has no shading map (lt_set_raw_shading)");
     if ((rc = set_device(c))) return rc;
-    HIP_TRY(hipMemcpy(plane, c->raw_dev.gain, (size_t)c->calib.img_h * c->calib.img_w * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(plane, raw_dev_of(c, id).gain, (size_t)c->calib.img_h * c->calib.img_w * sizeof(uint16_t), hipMemcpyDeviceToHost));
     return LT_OK;
 }
+int lt_get_raw_shading_plane(lt_ctx* c, uint16_t* plane) { return lt_get_raw_shading_plane_of(c, 0, plane); }
 
 // ---- raw statistics (lt_raw_stats) ---------------------------------------------------------------------------------------------
 // Occasional, like the setters: behind everything the context has in flight, on the context's stream, and the host waits for it.  It
@@ -238,21 +422,21 @@ int lt_raw_stats(lt_ctx* c, int first, int n, const lt_raw_stats_params* p, uint
         if ((rc = dev_alloc(&c->d_stats, need))) return rc;
         c->stats_bytes = need;
     }
-    const RawStages raw = raw_stages_of(c);                      // (the map as the front end reads it)
     RawStatsJob job{};
     job.pattern = c->in_layout & 3, job.bits = bits, job.pack = raw_packing(c->in_layout);
     job.img_w = W;
     job.row0 = row0, job.col0 = col0, job.ncy = ncy, job.ncx = ncx, job.grid_h = p->grid_h, job.grid_w = p->grid_w;
     for (int k = 0; k < 4; ++k) job.lo[k] = p->lo[k], job.hi[k] = p->hi[k];
-    job.gains = raw.gains;
-    job.blk = raw.blk;
     unsigned long long* d_sum = reinterpret_cast<unsigned long long*>(c->d_stats);
     uint32_t* d_hist = reinterpret_cast<uint32_t*>(c->d_stats + sum_bytes);
     uint32_t* d_count = reinterpret_cast<uint32_t*>(c->d_stats + sum_bytes + hist_bytes);
     HIP_TRY(hipMemsetAsync(c->d_stats, 0, need, c->stream));
-    for (int a = first; a < first + n;) {                        // runs of slots with one kind of source
+    for (int a = first; a < first + n;) {                        // runs of slots with one kind of source and one raw set
         int b = a + 1;
-        while (b < first + n && is_attached(b) == is_attached(a)) ++b;
+        while (b < first + n && is_attached(b) == is_attached(a) && slot_raw_set(c, b) == slot_raw_set(c, a)) ++b;
+        const RawStages raw = raw_stages_of(c, slot_raw_set(c, a));      // (the slots' map as the front end reads it)
+        job.gains = raw.gains;
+        job.blk = raw.blk;
         job.zone_sum = d_sum + (size_t)(a - first) * zones * 4;
         job.hist = d_hist + (size_t)(a - first) * 4 * bins;
         job.zone_count = d_count + (size_t)(a - first) * zones;

@@ -106,6 +106,65 @@ inline std::vector<uint8_t> raw_staged(const RawSetup& s) {
     return t;
 }
 
+// Raw sets (lt_add_raw_set): a context holds several RawSetups, one per kind of camera, and a launch whose slots mix sets runs ONE kernel --
+// the stages of the UNION of the parts the sets have.  A set that lacks a part runs that part's identity, each exact in the integer
+// definitions: the identity table (8 bits), the matrix 1024 I with the identity curve, a plane of unit gains (Q12 4096) with pedestals 0.
+struct RawUnion {
+    bool staged = false;                     // some set stages a table: the raw kernels run
+    bool color = false, shade = false;
+};
+inline void raw_union_add(RawUnion& u, const RawSetup& s) {
+    u.staged = u.staged || raw_staged_size(s) != 0;
+    u.color = u.color || s.color;
+    u.shade = u.shade || s.shade;
+}
+// the bytes a set-per-slot kernel stages for `s` in a launch with (or without) a colour stage: raw_staged's, the identity curve in front of
+// them where the launch has a stage and `s` has none, the identity table where `s` stages nothing of its own
+inline std::vector<uint8_t> raw_staged_as(const RawSetup& s, bool color) {
+    if (s.bits() == 0) return {};
+    if (s.color == color && raw_staged_size(s)) return raw_staged(s);
+    RawSetup u;                              // (without the mesh: nothing here reads it)
+    u.layout = s.layout, u.has_table = s.has_table, u.table = s.table;
+    if (s.color) u.set_color(s.ccm, s.curve);
+    else if (color) u.set_color(nullptr, nullptr);
+    std::vector<uint8_t> t((color ? 256 : 0) + u.table_bytes());
+    if (color) std::memcpy(t.data(), u.curve, 256);
+    if (u.has_table) std::memcpy(t.data() + (color ? 256 : 0), u.table.data(), u.table_bytes());
+    else raw_default_table(u.bits(), t.data() + (color ? 256 : 0));
+    return t;
+}
+// One set as the set-per-slot kernels find it: entry `id` of the context's table of raw sets (device memory, rewritten behind a full
+// synchronisation whenever a set changes).  What RawStages holds by value, per set: the staged bytes (raw_staged_as the union), the gain
+// plane (the set's, or the one plane of unit gains that all sets without a map share), the matrix and the pedestals.  A slot's set is
+// wave-uniform: an entry arrives by scalar loads.
+struct RawSetEntry {
+    const uint32_t* table;
+    const uint16_t* gains;
+    RawColorMat cm;
+    RawShadeBlack blk;
+    int32_t pad[3];
+};
+static_assert(sizeof(RawSetEntry) == 80, "RawSetEntry: 80 bytes");
+inline RawSetEntry raw_set_entry(const RawSetup& s, const uint32_t* table, const uint16_t* gains) {
+    RawSetEntry e{};
+    e.table = table, e.gains = gains;
+    for (int i = 0; i < 9; ++i) e.cm.m[i] = s.color ? s.ccm[i] : (i % 4 == 0 ? 1024 : 0);
+    if (s.shade) e.blk = s.black;
+    return e;
+}
+// What selects the kernel of a launch that mixes the sets of `u` (layout: the context's).  Its pointers only say "there is one" -- a
+// set-per-slot kernel reads its slot's entry, never them -- so both are the set table's address.
+inline RawStages raw_union_stages(int layout, const RawUnion& u, const RawSetEntry* sets) {
+    RawStages r;
+    if (raw_sample_bits(layout) == 0 || !u.staged) return r;
+    r.bits = raw_sample_bits(layout);
+    r.pack = raw_pack(layout);
+    r.table = reinterpret_cast<const uint32_t*>(sets);
+    r.color = u.color;
+    r.gains = u.shade ? reinterpret_cast<const uint16_t*>(sets) : nullptr;
+    return r;
+}
+
 // What a RawSetup is on the device: ONE buffer of what the kernels stage (raw_staged; reallocated only when that size changes, kept until the
 // owner goes -- also while nothing is staged) and the gain plane that k_shade_expand makes of the mesh -- uint16[h][w] and 16 bytes of
 // padding, allocated by the first map, freed when the map is removed.  Written by raw_commit and freed by raw_release alone (lt_raw.cpp).

@@ -52,10 +52,10 @@ class _GroupMember(LaneTracker):
     # (wraps: process()'s signature stays LaneTracker.process's -- _batch_arguments reads the keywords and defaults from it)
     process = functools.wraps(LaneTracker.process)(_not_owned)
     process_batch = process_stream = warm = _not_owned
-    set_raw_lut = _not_owned        # (one table for the whole group: LaneTrackerGroup.set_raw_lut)
-    set_raw_color = _not_owned      # (... and one colour stage: LaneTrackerGroup.set_raw_color)
-    set_raw_shading = _not_owned    # (... and one lens-shading map: LaneTrackerGroup.set_raw_shading)
-    raw_stats = _not_owned          # (it uploads into slots: statistics are a tracker's, not a group member's)
+    set_raw_lut = _not_owned        # (the group sets its streams' tables: LaneTrackerGroup.set_raw_lut(lut, stream=i))
+    set_raw_color = _not_owned      # (... and their colour stages: LaneTrackerGroup.set_raw_color)
+    set_raw_shading = _not_owned    # (... and their lens-shading maps: LaneTrackerGroup.set_raw_shading)
+    raw_stats = _not_owned          # (it uploads into slots, which are the group's: LaneTrackerGroup.raw_stats(frames, stream))
     _owns_context = False           # close() leaves the group's context to LaneTrackerGroup.close
 
 
@@ -86,6 +86,50 @@ def _stream_calibrations(calibrations, k, own):
     return out
 
 
+_RAW_SETUP_KEYS = ("raw_lut", "raw_ccm", "raw_curve", "raw_shading")
+
+
+def _checked_raw_setup(s, pixel_format):
+    """One stream's raw_lut / raw_ccm / raw_curve / raw_shading through the checks a tracker's go through (ValueError)."""
+    ccm, curve = _native.checked_raw_color(s["raw_ccm"], s["raw_curve"], pixel_format)
+    return dict(raw_lut=_native.effective_raw_lut(s["raw_lut"], pixel_format), raw_ccm=ccm, raw_curve=curve,
+                raw_shading=_native.checked_raw_shading(s["raw_shading"], pixel_format))
+
+
+def _stream_raw_setups(raw_setups, k, own, pixel_format):
+    """`raw_setups` of LaneTrackerGroup -> one complete, checked mapping per stream (missing keys: the group's own value; an explicit None:
+    none for this camera).  ValueError / TypeError for a pixel format that is not raw Bayer, a list of another length, an entry that is
+    no mapping, unknown keys, and whatever a tracker refuses of the values.  Touches no device."""
+    own = _checked_raw_setup(own, pixel_format)
+    if raw_setups is None:
+        return [dict(own) for _ in range(k)]
+    if not _native.raw_bits(pixel_format):
+        raise ValueError("raw_setups condition raw Bayer frames: pixel_format=%r takes none" % (pixel_format,))
+    setups = list(raw_setups)
+    if len(setups) != k:
+        raise ValueError("raw_setups: expected %d entries (None for the group's own setup), got %d" % (k, len(setups)))
+    out = []
+    for i, s in enumerate(setups):
+        full = dict(own)
+        if s is not None:
+            if not hasattr(s, "keys"):
+                raise TypeError("raw_setups[%d]: expected None or a mapping with any of %s" % (i, ", ".join(_RAW_SETUP_KEYS)))
+            unknown = sorted(set(s.keys()) - set(_RAW_SETUP_KEYS))
+            if unknown:
+                raise ValueError("raw_setups[%d]: unknown keys %s (known: %s)" % (i, ", ".join(map(repr, unknown)), ", ".join(_RAW_SETUP_KEYS)))
+            full.update(s)
+            full = _checked_raw_setup(full, pixel_format)
+        out.append(full)
+    return out
+
+
+def _raw_setup_key(s):
+    """What a raw set of the context is made of, byte for byte: streams with equal keys share a set."""
+    part = lambda a: b"-" if a is None else repr((a.shape, str(a.dtype))).encode() + np.ascontiguousarray(a).tobytes()
+    sh = s["raw_shading"]
+    return b"|".join([part(s["raw_lut"]), part(s["raw_ccm"]), part(s["raw_curve"]), b"-" if sh is None else part(sh.mesh) + part(sh.black)])
+
+
 def _table_key(c):
     """What a calibration set of the context is made of, byte for byte: entries with equal keys share a set."""
     d = np.asarray(c["dist_coeffs"], np.float64).reshape(-1)
@@ -103,6 +147,12 @@ class LaneTrackerGroup:
     intrinsics, distortion or mounting.  `img_size` / `warped_size` are the group's.  Entries whose arrays are equal byte for byte
     share one calibration set of the context (`calibration_count()`).
 
+    `raw_setups` (keyword only, raw Bayer pixel formats): one entry per stream -- None for the group's own raw_lut / raw_ccm / raw_curve /
+    raw_shading, or a mapping with any of those four keys (missing keys: the group's value; an explicit None: none for this camera) --
+    for sensors that differ in white balance, colour matrix or lens.  Streams whose effective setups are equal byte for byte share one
+    raw set of the context (`raw_set_count()`); `set_raw_lut` / `set_raw_color` / `set_raw_shading` with `stream=i` change one camera's,
+    `raw_stats(frames, stream)` measures one camera's frames, and `trackers[i].raw_lut` ... read its own values.
+
     For every stream i, the annotated frame and the whole tracker state after every call equal, bit for bit, what a solo
     `LaneTracker.process()` leaves when fed the same frames; a stream whose frame is None does not move.  `trackers[i]` is
     stream i's tracker (read its attributes, `get_state()` / `set_state()` to hand a camera over).  Not thread-safe, like
@@ -110,7 +160,7 @@ class LaneTrackerGroup:
 
     def __init__(self, k, img_size, warped_size, cam_matrix, dist_coeffs, warp_matrices, mpp_conversion, n_fail=8, n_reset=4,
                  n_average=2, print_frame_count=False, device=0, *, pixel_format='rgb', yuv_matrix='bt601', calibrations=None,
-                 input_size=None, raw_lut=None, raw_ccm=None, raw_curve=None, raw_shading=None):
+                 input_size=None, raw_lut=None, raw_ccm=None, raw_curve=None, raw_shading=None, raw_setups=None):
         k = int(k)
         if k < 1:
             raise ValueError("a group needs at least one stream")
@@ -127,9 +177,14 @@ class LaneTrackerGroup:
         self._resize_from = _native.checked_input_size(input_size, img_size, pixel_format)
         if self._resize_from is not None:
             self._frame_shape = (self._resize_from[1], self._resize_from[0], 3)
-        self._raw_lut = _native.effective_raw_lut(raw_lut, pixel_format)       # one raw table for the whole group (LaneTracker's raw_lut)
+        self._raw_lut = _native.effective_raw_lut(raw_lut, pixel_format)       # the group's own raw table (LaneTracker's raw_lut): what raw_setups leaves out
         self._raw_ccm, self._raw_curve = _native.checked_raw_color(raw_ccm, raw_curve, pixel_format)     # ... and one colour stage
         self._raw_shading = _native.checked_raw_shading(raw_shading, pixel_format)      # ... and one lens-shading map
+        # every stream's own setup (raw_setups), checked before any device call: set 0 of the context is the group's, one more for every
+        # distinct setup among the streams
+        setups = _stream_raw_setups(raw_setups, k, dict(raw_lut=self._raw_lut, raw_ccm=self._raw_ccm, raw_curve=self._raw_curve,
+                                                       raw_shading=self._raw_shading), pixel_format)
+        self._raw_ids, self._raw_sets_used = [0] * k, False
         self._ctx = _native.Context(img_size, warped_size, cam_matrix, dist_coeffs, warp_matrices[0], device=device, capacity=4 * k)
         self._tick = 0
         self._overlay_sets = set()           # the calibration sets whose overlay a member has configured
@@ -144,6 +199,12 @@ class LaneTrackerGroup:
                 self._ctx.set_raw_color(self._raw_ccm, self._raw_curve)
             if self._raw_shading is not None:
                 self._ctx.set_raw_shading(self._raw_shading)
+            raw_sets = {_raw_setup_key(dict(raw_lut=self._raw_lut, raw_ccm=self._raw_ccm, raw_curve=self._raw_curve, raw_shading=self._raw_shading)): 0}
+            for i, s in enumerate(setups):
+                key = _raw_setup_key(s)
+                if key not in raw_sets:
+                    raw_sets[key] = self._new_raw_set(s)
+                self._raw_ids[i] = raw_sets[key]
             # the calibration sets of the context: 0 is the group's own, one more for every distinct calibration among the streams
             sets = {_table_key(dict(cam_matrix=cam_matrix, dist_coeffs=dist_coeffs, warp_matrices=warp_matrices)): 0}
             self._cal_ids = []
@@ -153,13 +214,13 @@ class LaneTrackerGroup:
                     sets[key] = self._ctx.add_calibration(c["cam_matrix"], c["dist_coeffs"], c["warp_matrices"][0])
                 self._cal_ids.append(sets[key])
             self._many_sets = len(sets) > 1
-            for c, cal_id in zip(cals, self._cal_ids):
+            for c, cal_id, rs in zip(cals, self._cal_ids, setups):
                 self.trackers.append(_GroupMember(self, cal_id, img_size, warped_size, c["cam_matrix"], c["dist_coeffs"], c["warp_matrices"],
                                                   c["mpp_conversion"], n_fail=n_fail, n_reset=n_reset, n_average=n_average,
                                                   print_frame_count=print_frame_count, device=device,
                                                   pixel_format=pixel_format, yuv_matrix=yuv_matrix, input_size=input_size,
-                                                  raw_lut=self._raw_lut, raw_ccm=self._raw_ccm, raw_curve=self._raw_curve,
-                                                  raw_shading=self._raw_shading))
+                                                  raw_lut=rs["raw_lut"], raw_ccm=rs["raw_ccm"], raw_curve=rs["raw_curve"],
+                                                  raw_shading=rs["raw_shading"]))
         except BaseException:
             self.close()
             raise
@@ -170,19 +231,55 @@ class LaneTrackerGroup:
     def __exit__(self, *exc):
         self.close()
 
+    # -- raw sets: one raw table, colour stage and shading map per camera -------------------------------------------------------------
+    def _new_raw_set(self, setup):
+        """A further raw set of the context holding `setup` (a copy of set 0, then every part written); returns its id."""
+        ctx = self._ctx
+        rid = ctx.add_raw_set()
+        ctx.set_raw_lut(setup["raw_lut"], raw_set=rid)
+        ctx.set_raw_color(setup["raw_ccm"], setup["raw_curve"], enable=setup["raw_ccm"] is not None or setup["raw_curve"] is not None, raw_set=rid)
+        ctx.set_raw_shading(setup["raw_shading"], raw_set=rid)
+        self._raw_sets_used = True
+        return rid
+
+    def _raw_targets(self, stream):
+        """(raw set ids, trackers) a setter with `stream` changes: every set in use and every tracker (None), or stream i's own set --
+        split off first where other streams share it -- and tracker i."""
+        if stream is None:
+            return sorted(set(self._raw_ids)), self.trackers
+        i = int(stream)
+        if not 0 <= i < self.k:
+            raise ValueError("stream must be 0 .. %d, got %r" % (self.k - 1, stream))
+        t = self.trackers[i]
+        if self._raw_ids.count(self._raw_ids[i]) > 1:
+            self._raw_ids[i] = self._new_raw_set(dict(raw_lut=t._raw_lut, raw_ccm=t._raw_ccm, raw_curve=t._raw_curve, raw_shading=t._raw_shading))
+        return [self._raw_ids[i]], [t]
+
+    @staticmethod
+    def _of_set(rid):
+        return dict(raw_set=rid) if rid else {}      # (set 0 through the calls a group always made)
+
+    def raw_set_count(self):
+        """The raw sets the group's streams use (1: every stream is conditioned with the same table, colour stage and shading map)."""
+        return len(set(self._raw_ids))
+
     @property
     def raw_lut(self):
-        """The group's raw table, u8 (4, 256), or None (`set_raw_lut`)."""
+        """The group's raw table, u8 (4, 256), or None (`set_raw_lut`); a stream's own: `trackers[i].raw_lut`."""
         return None if self._raw_lut is None else self._raw_lut.copy()
 
-    def set_raw_lut(self, lut):
-        """Another raw table for every stream of the group, or None for none, between `process()` calls (LaneTracker.set_raw_lut)."""
+    def set_raw_lut(self, lut, stream=None):
+        """Another raw table for every stream of the group -- `stream=i`: for camera i alone, which gets a raw set of its own where it
+        shared one -- or None for none, between `process()` calls (LaneTracker.set_raw_lut)."""
         lut = _native.effective_raw_lut(lut, self.pixel_format)
         if not _native.raw_bits(self.pixel_format):
             return
-        self._ctx.set_raw_lut(lut)
-        self._raw_lut = lut
-        for t in self.trackers:
+        ids, ts = self._raw_targets(stream)
+        for rid in ids:
+            self._ctx.set_raw_lut(lut, **self._of_set(rid))
+        if stream is None:
+            self._raw_lut = lut
+        for t in ts:
             t._raw_lut = lut
             t._resident = None
 
@@ -196,15 +293,18 @@ class LaneTrackerGroup:
         """The output curve of the group's colour stage, u8 (256,), or None (`set_raw_color`)."""
         return None if self._raw_curve is None else self._raw_curve.copy()
 
-    def set_raw_color(self, ccm=None, curve=None):
-        """Another colour stage for every stream of the group, or (None, None) for none, between `process()` calls
-        (LaneTracker.set_raw_color)."""
+    def set_raw_color(self, ccm=None, curve=None, stream=None):
+        """Another colour stage for every stream of the group -- `stream=i`: for camera i alone -- or (None, None) for none, between
+        `process()` calls (LaneTracker.set_raw_color)."""
         ccm, curve = _native.checked_raw_color(ccm, curve, self.pixel_format)
         if not _native.raw_bits(self.pixel_format):
             return
-        self._ctx.set_raw_color(ccm, curve, enable=ccm is not None or curve is not None)
-        self._raw_ccm, self._raw_curve = ccm, curve
-        for t in self.trackers:
+        ids, ts = self._raw_targets(stream)
+        for rid in ids:
+            self._ctx.set_raw_color(ccm, curve, enable=ccm is not None or curve is not None, **self._of_set(rid))
+        if stream is None:
+            self._raw_ccm, self._raw_curve = ccm, curve
+        for t in ts:
             t._raw_ccm, t._raw_curve = ccm, curve
             t._resident = None
 
@@ -214,17 +314,37 @@ class LaneTrackerGroup:
         s = self._raw_shading
         return None if s is None else type(s)(s.mesh.copy(), s.black.copy())
 
-    def set_raw_shading(self, shading):
-        """Another lens-shading map for every stream of the group, or None for none, between `process()` calls
-        (LaneTracker.set_raw_shading)."""
+    def set_raw_shading(self, shading, stream=None):
+        """Another lens-shading map for every stream of the group -- `stream=i`: for camera i alone -- or None for none, between
+        `process()` calls (LaneTracker.set_raw_shading)."""
         shading = _native.checked_raw_shading(shading, self.pixel_format)
         if not _native.raw_bits(self.pixel_format):
             return
-        self._ctx.set_raw_shading(shading)
-        self._raw_shading = shading
-        for t in self.trackers:
+        ids, ts = self._raw_targets(stream)
+        for rid in ids:
+            self._ctx.set_raw_shading(shading, **self._of_set(rid))
+        if stream is None:
+            self._raw_shading = shading
+        for t in ts:
             t._raw_shading = shading
             t._resident = None
+
+    def raw_stats(self, frames, stream, grid=(8, 8), rows=None, cols=None, lo=None, hi=None):
+        """`LaneTracker.raw_stats` of camera `stream`'s frames -- one frame, a stack, or `DeviceFrames` --, behind that camera's shading
+        map: what its auto-white-balance step measures (`set_raw_lut(utils.raw_lut(..., utils.awb_gains(s, black), ...), stream=i)`).
+        Between `process()` calls; it runs in slots the group is not using and leaves every stream's state and counters untouched."""
+        if self._ctx is None:
+            raise RuntimeError("the group is closed")
+        if not _native.raw_bits(self.pixel_format):
+            raise ValueError("raw statistics are taken of raw Bayer frames: a %r group has none" % (self.pixel_format,))
+        i = int(stream)
+        if not 0 <= i < self.k:
+            raise ValueError("stream must be 0 .. %d, got %r" % (self.k - 1, stream))
+        base = (self._tick & 1) * self.k         # the slots the next tick's first tries take: their lists are fetched first, as process() does
+        self._free_slots(base, base + self.k)
+        if self._raw_sets_used:
+            self._ctx.set_slot_raw_sets([self._raw_ids[i]] * self.k, first=base)
+        return self.trackers[i]._raw_stats_in_slots(frames, base, self.k, grid, rows, cols, lo, hi)
 
     def calibration_count(self):
         """The calibration sets the group's context holds (1: every stream has the group's own calibration)."""
@@ -335,8 +455,10 @@ class LaneTrackerGroup:
         self._free_slots(base, base + m)
 
         # 1-3: camera rows of the m frames, one mask chain, one search launch
+        if self._raw_sets_used:                                          # every slot with its stream's raw set, ahead of its frame
+            ctx.set_slot_raw_sets([self._raw_ids[i] for i in active], first=base)
         keep = feed_rows_list(ctx, imgs, base)
-        if self._many_sets:                                              # every slot with its stream's calibration set
+        if self._many_sets:                                              # ... and with its stream's calibration set
             ctx.set_slot_calibrations([self._cal_ids[i] for i in active], first=base)
         ctx.mask_run(m, fp, first=base)
         keep_rest = None
@@ -362,6 +484,8 @@ class LaneTrackerGroup:
         if again:
             second = StreamPipeline._SECOND_TRY
             self._free_slots(spare, spare + len(again))
+            if self._raw_sets_used:
+                ctx.set_slot_raw_sets([self._raw_ids[active[j]] for j in again], first=spare)
             keep_again = feed_rows_list(ctx, [imgs[j] for j in again], spare)
             if self._many_sets:
                 ctx.set_slot_calibrations([self._cal_ids[active[j]] for j in again], first=spare)

@@ -255,6 +255,11 @@ class LaneTracker(StreamPipeline):
             raise ValueError("raw statistics are taken of raw Bayer frames: a %r tracker has none" % (self.pixel_format,))
         if self._in_stream:
             raise RuntimeError("raw_stats() inside an active process_stream(): exhaust or close the generator first")
+        return self._raw_stats_in_slots(frames, 0, int(self._ctx.capacity), grid, rows, cols, lo, hi)
+
+    def _raw_stats_in_slots(self, frames, first, count, grid, rows, cols, lo, hi):
+        """raw_stats through slots [first, first + count) of the context (a LaneTrackerGroup takes statistics of one stream's frames in
+        slots it is not using)."""
         on_device = isinstance(frames, DeviceFrames)
         if on_device:
             single = frames.single
@@ -269,16 +274,16 @@ class LaneTracker(StreamPipeline):
         inside = run[0] <= p.row0 and p.row1 <= run[1]
         self._all_copies_done()
         self._resident = None       # the slots hold these frames now
-        parts, n, step = [], len(frames), max(int(ctx.capacity), 1)
+        parts, n, step = [], len(frames), max(int(count), 1)
         for at in range(0, n, step):
             piece = frames[at:at + step]
             if on_device:
-                self._rows_keepalive = ctx.attach_device_frames(piece, first=0)
+                self._rows_keepalive = ctx.attach_device_frames(piece, first=first)
             elif inside:
-                ctx.upload_frame_rows(piece, first=0)
+                ctx.upload_frame_rows(piece, first=first)
             else:
-                ctx.upload_frames(piece, first=0)
-            parts.append(ctx.raw_stats(len(piece), 0, (p.grid_h, p.grid_w), (p.row0, p.row1), (p.col0, p.col1), list(p.lo), list(p.hi)))
+                ctx.upload_frames(piece, first=first)
+            parts.append(ctx.raw_stats(len(piece), first, (p.grid_h, p.grid_w), (p.row0, p.row1), (p.col0, p.col1), list(p.lo), list(p.hi)))
         if on_device:
             self._rows_keepalive = frames        # (the last piece's slots stay attached until an upload replaces the frames)
         from .utils import RawStats

@@ -12,6 +12,7 @@ pool of frames), annotated, process()'s default keywords:
   python tools/group_throughput.py [--ticks 60] [--warmup 8] [--out profiles/group_throughput.jsonl] [--no-solo]
                                    [--distinct-calibrations] [--front-end-times]
                                    [--frames-out host|sink|inplace] [--sink-format rgb|nv12|i420] [--device-frames]
+  python tools/group_throughput.py --raw-sets [--ks 8,32] [--ticks 40] [--rounds 3] [--out profiles/group_raw_sets.json]
 
 --frames-out: where a tick's annotated frames go -- `host` (the default: one download), `sink` (process(out=) a DeviceFrames of K
 surfaces in --sink-format: one lt_overlay_run_to_surfaces per tick) or `inplace` (process(out="inplace"): drawn into the frames
@@ -24,6 +25,12 @@ group's context holds K calibration sets and every slice of a tick mixes them (t
 the line says how many sets the group holds.  --front-end-times: a second, separate pass over the same ticks with the context's
 stage timers on (hipEvent pairs around every launch, which also serialise the slices: not for the tick times) -- undistort_ms /
 warp_ms per tick, the two front-end launches summed over a tick's slices and tries.
+
+--raw-sets: the raw-sets leg, a run of its own (one JSON document, not lines).  Raw Bayer groups of K cameras (1280 x 720; 8-bit and 12-bit
+samples; a table alone, and table + colour stage + shading map), ONE shared raw set (the one-set kernels, fpb frames per walk) against K
+distinct ones (every camera its own white-balance gains; with the full setup its own matrix and map too: the set-per-slot kernels).  Both
+groups of a cell are alive together and their runs ALTERNATE, --rounds times --ticks ticks each with the stage timers on: undistort_ms per
+tick (median over the rounds, and the range), the launches per tick, lt_last_raw_walk_form, and the untimed tick time of a separate pass.
 """
 import argparse
 import json
@@ -147,6 +154,79 @@ def run_solo(cal, pool, k, ticks, warmup):
             t.close()
 
 
+def raw_sets_leg(a):
+    """See the module's docstring: --raw-sets."""
+    from lane_tracker_amd import utils
+    cal = calib.reference_calibration()
+    W, H = cal["img_size"]
+    rgb = pool_frames(cal)
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import bayer_reference as RB
+    pattern = "bayer_rggb"
+    mosaic = RB.rgb_to_bayer(rgb, pattern)
+    cells = []
+    for bits in (8, 12):
+        fmt = pattern if bits == 8 else "bayer12_rggb"
+        frames = mosaic if bits == 8 else (mosaic.astype(np.uint16) << 4)
+        top = (1 << bits) - 1
+        lut = lambda i: utils.raw_lut(0, top, (1.0 + 0.01 * (i % 7), 1, 1.0 + 0.01 * (i % 5)), 1.0, bits=bits)
+        ccm = lambda i: utils.raw_ccm(np.eye(3) * (1.0 + 0.001 * i))
+        shade = lambda i: utils.raw_shading(np.full((4, 5, 7), 1.0 + 0.002 * i), black_level=0, bits=bits)
+        for full in (False, True):
+            own = dict(raw_lut=lut(0))
+            if full:
+                own.update(raw_ccm=ccm(0), raw_curve=utils.raw_curve(1.0), raw_shading=shade(0))
+            for k in [int(v) for v in a.ks.split(",") if v]:
+                setups = [dict(raw_lut=lut(i + 1), **(dict(raw_ccm=ccm(i + 1), raw_shading=shade(i + 1)) if full else {})) for i in range(k)]
+                groups = {"shared": LaneTrackerGroup(k, **cal, pixel_format=fmt, **own),
+                          "distinct": LaneTrackerGroup(k, **cal, pixel_format=fmt, raw_setups=setups, **own)}
+                cell = dict(bits=bits, stages="table + colour stage + shading map" if full else "table", k=k, ticks=a.ticks, rounds=a.rounds)
+                try:
+                    und = {m: [] for m in groups}
+                    launches, tick = {}, {}
+                    t = 0
+                    for m, g in groups.items():
+                        for _ in range(a.warmup):
+                            g.process([frames[(t + 11 * i) % POOL] for i in range(k)])
+                            t += 1
+                    for r in range(a.rounds):
+                        for m, g in groups.items():          # alternated: shared, distinct, shared, distinct, ...
+                            ctx = g._ctx
+                            ctx.sync()
+                            ctx.set_stage_timing(True)
+                            ctx.stage_reset()
+                            for j in range(a.ticks):
+                                g.process([frames[(r * a.ticks + j + 11 * i) % POOL] for i in range(k)])
+                            ctx.sync()
+                            ms = ctx.stage_ms()
+                            ctx.set_stage_timing(False)
+                            und[m].append(ms["undistort_rows"][0] / a.ticks)
+                            launches[m] = round(ms["undistort_rows"][1] / a.ticks, 2)
+                    for m, g in groups.items():
+                        times = []
+                        for j in range(a.ticks):
+                            fr = [frames[(j + 11 * i) % POOL] for i in range(k)]
+                            t0 = time.perf_counter()
+                            g.process(fr)
+                            times.append(time.perf_counter() - t0)
+                        tick[m] = round(float(np.median(times)) * 1e3, 3)
+                    for m, g in groups.items():
+                        cell[m] = dict(raw_sets=g.raw_set_count(), raw_walk_form=g._ctx.last_raw_walk_form(), undistort_ms=round(float(np.median(und[m])), 4),
+                                       undistort_ms_range=[round(min(und[m]), 4), round(max(und[m]), 4)], undistort_launches_per_tick=launches[m],
+                                       tick_ms_median=tick[m])
+                    cell["distinct_over_shared"] = round(cell["distinct"]["undistort_ms"] / cell["shared"]["undistort_ms"], 3)
+                finally:
+                    for g in groups.values():
+                        g.close()
+                print(json.dumps(cell), flush=True)
+                cells.append(cell)
+    doc = dict(tool="group_throughput --raw-sets", size="%dx%d" % (W, H), cells=cells)
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(doc, f, indent=1)
+            f.write("\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--ticks", type=int, default=60)
@@ -160,7 +240,11 @@ def main():
     ap.add_argument("--frames-out", choices=("host", "sink", "inplace"), default="host", help="where the annotated frames of a tick go")
     ap.add_argument("--sink-format", choices=("rgb", "nv12", "i420"), default="nv12", help="the pixel format of --frames-out sink")
     ap.add_argument("--device-frames", action="store_true", help="the inputs are DeviceFrames (what --frames-out inplace needs)")
+    ap.add_argument("--raw-sets", action="store_true", help="the raw-sets leg: one shared raw set against K distinct ones (see the docstring)")
+    ap.add_argument("--rounds", type=int, default=3, help="--raw-sets: alternated rounds per cell")
     a = ap.parse_args()
+    if a.raw_sets:
+        return raw_sets_leg(a)
     if a.frames_out == "inplace" and not a.device_frames:
         ap.error("--frames-out inplace draws into the frames handed in: it needs --device-frames")
     plan = [("1280x720", calib.reference_calibration(), [int(v) for v in a.ks.split(",") if v]),
