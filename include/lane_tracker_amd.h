@@ -712,6 +712,28 @@ int  lt_filter_lane_points(lt_ctx* ctx, const uint8_t* bev_rgb, int h, int w, co
  * morphologyEx (:210-211, :238).  k in {5, 29, 55}; op 0 erode, 1 dilate, 2 top-hat, 3 open.
  * direct != 0 evaluates the footprint tap by tap instead of using the run decomposition (k = 5 always does). */
 int  lt_morph_ellipse(lt_ctx* ctx, const uint8_t* img, int h, int w, int k, int op, int direct, uint8_t* out);
+/* Test hook: ONE call of the top-hat launchers on n dense h x w planes given by value, in buffers that live for this call only
+ * (source, intermediate, destination, copy plane, and the split-band form's zone scratch when n > 2, sized as the mask chain sizes it).
+ *   k       29 or 55
+ *   op      0 erode, 1 dilate, 2 top-hat (src - dilate(erode(src))), 3 top-hat that also stores its minuend into the copy plane
+ *   bands   0: the launcher's own rule; > 0: that many bands (k_morph_one and k_morph_one_pair keep even bands of at least 8 rows)
+ *   dpitch  0: a dense destination; otherwise (w + 63) & ~63, the pitch of the planes the threshold walks read (the last launch only)
+ *   route   0: launch_morph_runs; 1: launch_morph_one_pair on 2 n planes -- n for the 55x55 chain, then n for the 29x29 chain, n <= 2,
+ *           op 0 .. 2, k ignored beyond its check -- whose refusal of a geometry comes back as *launched = 0 (nothing ran)
+ * dst_out, mid_out (the eroded intermediate; required for op >= 2, dense) and copy_out (required for op 3) receive the WHOLE allocations:
+ * n + 2 planes per chain (route 1: the 55x55 chain's n + 2, then the 29x29 chain's), rows of dpitch bytes where dpitch != 0, every byte
+ * 0xA5 before the launch, the work in planes 1 .. n.  Whatever is not 0xA5 in planes 0 and n + 1 or in columns [w, dpitch) was stored
+ * out of place.  *report: what ran (the last launch of the call). */
+typedef struct lt_morph_report {
+    int32_t family;        /* 0 nothing, 1 k_morph_one, 2 k_morph_one_pair, 3 k_morph_runs2 (bands walk their halos), 4 k_morph_split, 5 k_morph_runs (one row) */
+    int32_t wide;          /* 1: rows moved as dwords; 0: the narrow (byte) form */
+    int32_t nbands, band_rows;
+    int32_t pair_strip;    /* 1: the last strip carries two frames per wave */
+    int32_t q;             /* waves per task of families 1 and 2, else 0 */
+    int32_t nbands29, band_rows29;   /* family 2: the 29x29 plane's cut (nbands / band_rows are the 55x55 plane's) */
+} lt_morph_report;
+int  lt_morph_planes(lt_ctx* ctx, const uint8_t* planes, int n, int h, int w, int k, int op, int bands, int dpitch, int route,
+                     uint8_t* dst_out, uint8_t* mid_out, uint8_t* copy_out, lt_morph_report* report, int* launched);
 /* cv2.resize(img, (dw, dh)) with the default INTER_LINEAR on a u8 image of 1 or 3 interleaved channels (host memory in and
  * out): half-pixel centres, 11-bit coefficients, OpenCV's two-stage fixed-point rounding. */
 int  lt_resize_linear_u8(lt_ctx* ctx, const uint8_t* img, int h, int w, int channels, int dh, int dw, uint8_t* out);

@@ -204,6 +204,7 @@ _SIGNATURES = {
                                                  C.c_int, _P]),
     "lt_filter_lane_points": (C.c_int, [_P, _P, C.c_int, C.c_int, C.POINTER(FilterParams), _P]),
     "lt_morph_ellipse": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "lt_morph_planes": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, _P]),
     "lt_fit_poly2": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
     "lt_calib_source_rows": (C.c_int, [C.POINTER(Calib), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "lt_calib_warp_table": (C.c_int, [C.POINTER(Calib), _P, _P]),
@@ -1923,6 +1924,35 @@ class Context:
         _check(self.lib.lt_morph_ellipse(self._h, a.ctypes.data, a.shape[0], a.shape[1], int(k), code,
                                          int(bool(direct)), out.ctypes.data))
         return out
+
+    MORPH_FAMILIES = ("none", "one", "one_pair", "runs2", "split", "one_row")
+    MORPH_OPS = {"erode": 0, "dilate": 1, "tophat": 2, "tophat_copy": 3}
+
+    def morph_planes(self, planes, k, op, bands=0, padded=False, route=0):
+        """Test hook (lt_morph_planes): one call of the top-hat launchers on `planes` (n, h, w) u8 -- route 1 (launch_morph_one_pair):
+        (2, n, h, w), the 55x55 chain's planes and the 29x29 chain's.  op: 'erode' | 'dilate' | 'tophat' | 'tophat_copy'; bands 0 is the
+        launcher's own rule; padded: a destination pitch of (w + 63) & ~63.  Returns a dict: `dst`, `mid` (the eroded intermediate of a
+        top-hat, else None) and `copy` -- the WHOLE allocations, (n + 2, h, pitch) each ((2, n + 2, h, pitch) for route 1), 0xA5 wherever
+        nothing was stored, the work in planes 1 .. n --, `launched`, and `report` (family, wide, nbands, band_rows, pair_strip, q,
+        nbands29, band_rows29)."""
+        a = _u8(planes)
+        if a.ndim != (4 if route else 3) or (route and a.shape[0] != 2):
+            raise ValueError("morph_planes expects (n, h, w) planes, or (2, n, h, w) for the pair route")
+        n, h, w = a.shape[-3:]
+        code = self.MORPH_OPS[op]
+        pitch = (w + 63) & ~63 if padded else w
+        lead = (2, n + 2) if route else (n + 2,)
+        dst = np.empty(lead + (h, pitch), np.uint8)
+        mid = np.empty(lead + (h, w), np.uint8)
+        cp = np.empty(lead + (h, pitch), np.uint8)
+        rep = (C.c_int32 * 8)()
+        launched = C.c_int(0)
+        _check(self.lib.lt_morph_planes(self._h, a.ctypes.data, n, h, w, int(k), code, int(bands), pitch if padded else 0, int(route),
+                                        dst.ctypes.data, mid.ctypes.data, cp.ctypes.data, rep, C.byref(launched)))
+        names = ("family", "wide", "nbands", "band_rows", "pair_strip", "q", "nbands29", "band_rows29")
+        report = dict(zip(names, (int(v) for v in rep)))
+        report["family"] = self.MORPH_FAMILIES[report["family"]]
+        return dict(dst=dst, mid=mid if code >= 2 else None, copy=cp, launched=bool(launched.value), report=report)
 
     def fit_poly2(self, ys, xs):
         """np.polyfit(ys, xs, 2) on the device; rank-deficient inputs get NumPy's minimum-norm answer."""

@@ -1170,12 +1170,13 @@ void launch_one(hipStream_t s, const uint8_t* src, uint8_t* dst, const uint8_t* 
 }
 
 // Bands of a one- or two-frame launch of k_morph_one: about `want_wgs` workgroups (default: two per CU), none shorter than 8 rows
-static void one_frame_bands(RunsGeom& g, int n, int want_wgs) {
+static void one_frame_bands(RunsGeom& g, int n, int want_wgs, int force_bands = 0) {
     int cus1 = 256, dev1 = 0;
     (void)hipGetDevice(&dev1);
     (void)hipDeviceGetAttribute(&cus1, hipDeviceAttributeMultiprocessorCount, dev1);
     const int target = want_wgs > 0 ? want_wgs : 2 * cus1;
     int nb = std::max(1, target / std::max(1, n * g.nstrips));
+    if (force_bands > 0) nb = force_bands;   // (tests: the band count by value; the rows stay even and at least 8)
     int rows = std::max((g.h + nb - 1) / nb, 8);
     rows = (rows + 1) & ~1;
     g.band_rows = rows;
@@ -1195,9 +1196,20 @@ bool table_matches(const EllipseSE& se) {
 
 template <class SE>
 bool launch_runs(hipStream_t s, const uint8_t* src, uint8_t* dst, const uint8_t* minuend, int h, int w, bool dilate,
-                 size_t plane_stride, int n, int dpitch, size_t dst_stride, uint8_t* copy_dst, const MorphZone& zone, int* form) {
+                 size_t plane_stride, int n, int dpitch, size_t dst_stride, uint8_t* copy_dst, const MorphZone& zone, int* form,
+                 int force_bands, MorphReport* report) {
     RunsGeom g;
     if (form) *form = 0;
+    // what ran, for the test hook (lt_morph_planes); family stays MORPH_NONE where nothing is launched
+    auto tell = [&](int family, bool wide_, bool pair_, int q) {
+        if (!report) return;
+        report->family = family;
+        report->wide = wide_ ? 1 : 0;
+        report->nbands = g.nbands;
+        report->band_rows = g.band_rows;
+        report->pair_strip = pair_ ? 1 : 0;
+        report->q = q;
+    };
     g.zone = nullptr;
     g.zone_stride = 0;
     g.copy_dst = copy_dst;
@@ -1217,9 +1229,10 @@ bool launch_runs(hipStream_t s, const uint8_t* src, uint8_t* dst, const uint8_t*
     static const int one_q = [] { const char* e = LT_EXP_ENV("LT_MORPH_ONE"); return e ? std::atoi(e) : 4; }();
     if (n <= 2 && (one_q == 4 || one_q == 8) && !one_row && wide && !copy_dst && ((uintptr_t)src & 3) == 0) {
         static const int want_wgs = [] { const char* e = LT_EXP_ENV("LT_MORPH_ONE_WGS"); return e ? std::atoi(e) : 0; }();
-        one_frame_bands(g, n, want_wgs);
+        one_frame_bands(g, n, want_wgs, force_bands);
         if (one_q == 8) launch_one<SE, 8>(s, src, dst, minuend, dilate, g);
         else launch_one<SE, 4>(s, src, dst, minuend, dilate, g);
+        tell(MORPH_ONE, true, false, one_q);
         return true;
     }
     // The split-band form (k_morph_split) for a cut into nb bands of `rows` rows: what the geometry rule accepts, with a zone scratch
@@ -1285,6 +1298,7 @@ bool launch_runs(hipStream_t s, const uint8_t* src, uint8_t* dst, const uint8_t*
         if (e && std::atoi(e) > 0) best_nb = std::atoi(e);
     }
 #endif
+    if (force_bands > 0) best_nb = force_bands;
     g.band_rows = (h + best_nb - 1) / best_nb;
     g.nbands = (h + g.band_rows - 1) / g.band_rows;
     // the last strip as a PAIR strip (two frames per wave) when it is at most 64 columns wide
@@ -1311,6 +1325,7 @@ bool launch_runs(hipStream_t s, const uint8_t* src, uint8_t* dst, const uint8_t*
         else if (dilate) hipLaunchKernelGGL((k_morph_split<SE, true, false>), grid_s, block_s, 0, s, src, dst, minuend, g);
         else hipLaunchKernelGGL((k_morph_split<SE, false, false>), grid_s, block_s, 0, s, src, dst, minuend, g);
         if (form) *form = 1;
+        tell(MORPH_SPLIT, true, pair_strip, 0);
         return true;
     }
     dim3 grid((g.ntasks + 3) / 4);
@@ -1319,6 +1334,7 @@ bool launch_runs(hipStream_t s, const uint8_t* src, uint8_t* dst, const uint8_t*
     if (one_row) {   // previous formulation (one row per iteration, u16 min/max), kept for A/B measurements
         if (dilate) hipLaunchKernelGGL((k_morph_runs<SE, true>), grid, dim3(256), 0, s, src, dst, minuend, g);
         else hipLaunchKernelGGL((k_morph_runs<SE, false>), grid, dim3(256), 0, s, src, dst, minuend, g);
+        tell(MORPH_ONE_ROW, false, false, 0);
     } else {
         static const int extra_lds = [] { const char* e = LT_EXP_ENV("LT_MORPH_EXTRA_LDS"); return e ? std::atoi(e) : 0; }();   // occupancy experiments
         const bool th = dilate && minuend != nullptr;
@@ -1326,6 +1342,7 @@ bool launch_runs(hipStream_t s, const uint8_t* src, uint8_t* dst, const uint8_t*
             if constexpr (SE::K == 55) {
                 if (!wide || !th || ((uintptr_t)copy_dst & 3)) return false;
                 hipLaunchKernelGGL((k_morph_runs2<SE, true, true, true, true>), grid2, block2, extra_lds, s, src, dst, minuend, g);
+                tell(MORPH_RUNS2, true, pair_strip, 0);
                 return true;
             } else
                 return false;
@@ -1341,6 +1358,7 @@ bool launch_runs(hipStream_t s, const uint8_t* src, uint8_t* dst, const uint8_t*
             else LT_LAUNCH(false, false, false);
         }
 #undef LT_LAUNCH
+        tell(MORPH_RUNS2, wide, pair_strip, 0);
     }
     return copy_dst == nullptr;
 }
@@ -1353,12 +1371,14 @@ bool tophat_tables_match(const EllipseSE& se29, const EllipseSE& se55) {
 }
 
 bool launch_morph_runs(hipStream_t s, const uint8_t* src, uint8_t* dst, const uint8_t* minuend, int h, int w, int k,
-                       bool dilate, size_t plane_stride, int n, int dpitch, size_t dst_stride, uint8_t* copy_dst, const MorphZone& zone, int* form) {
+                       bool dilate, size_t plane_stride, int n, int dpitch, size_t dst_stride, uint8_t* copy_dst, const MorphZone& zone, int* form,
+                       int force_bands, MorphReport* report) {
     if (form) *form = 0;
+    if (report) *report = MorphReport();
     if (n <= 0 || h <= 0 || w <= 0) return true;
     if (k == 55)
-        return launch_runs<SE55>(s, src, dst, minuend, h, w, dilate, plane_stride, n, dpitch, dst_stride, copy_dst, zone, form);
-    return launch_runs<SE29>(s, src, dst, minuend, h, w, dilate, plane_stride, n, dpitch, dst_stride, copy_dst, zone, form);
+        return launch_runs<SE55>(s, src, dst, minuend, h, w, dilate, plane_stride, n, dpitch, dst_stride, copy_dst, zone, form, force_bands, report);
+    return launch_runs<SE29>(s, src, dst, minuend, h, w, dilate, plane_stride, n, dpitch, dst_stride, copy_dst, zone, form, force_bands, report);
 }
 
 // The split-band form's precondition (k_morph_split): rows 4-byte aligned (`wide`), at most four bands -- the waves of one
@@ -1375,7 +1395,9 @@ bool tophat_split_form(int h, int w, int k, int band_rows, int nbands, bool wide
 // One or two frames: the same step (erode, or dilate / top-hat) of the 55x55 chain of one plane and of the 29x29 chain of another
 // in ONE launch (k_morph_one_pair).  false: not launched (a geometry k_morph_one does not take) -- the caller launches them one by one.
 bool launch_morph_one_pair(hipStream_t s, const uint8_t* src55, uint8_t* dst55, const uint8_t* min55, const uint8_t* src29, uint8_t* dst29,
-                           const uint8_t* min29, int h, int w, bool dilate, size_t plane_stride, int n, int dpitch, size_t dst_stride) {
+                           const uint8_t* min29, int h, int w, bool dilate, size_t plane_stride, int n, int dpitch, size_t dst_stride,
+                           int force_bands, MorphReport* report) {
+    if (report) *report = MorphReport();
     if (n <= 0 || n > 2 || h <= 0 || w < 4) return false;
     RunsGeom g;
     g.copy_dst = nullptr;
@@ -1401,8 +1423,18 @@ bool launch_morph_one_pair(hipStream_t s, const uint8_t* src55, uint8_t* dst55, 
     int cus = 256, dev = 0;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    one_frame_bands(g55, n, wgs55 > 0 ? wgs55 : cus);
-    one_frame_bands(g29, n, wgs29 > 0 ? wgs29 : cus + cus / 2);
+    one_frame_bands(g55, n, wgs55 > 0 ? wgs55 : cus, force_bands);
+    one_frame_bands(g29, n, wgs29 > 0 ? wgs29 : cus + cus / 2, force_bands);
+    auto tell = [&](int q) {
+        if (!report) return;
+        report->family = MORPH_ONE_PAIR;
+        report->wide = 1;
+        report->nbands = g55.nbands;
+        report->band_rows = g55.band_rows;
+        report->nbands29 = g29.nbands;
+        report->band_rows29 = g29.band_rows;
+        report->q = q;
+    };
     const dim3 grid(g55.ntasks + g29.ntasks);
 #define LT_PAIR(Q_)                                                                                                                              \
     do {                                                                                                                                         \
@@ -1412,11 +1444,12 @@ bool launch_morph_one_pair(hipStream_t s, const uint8_t* src55, uint8_t* dst55, 
         else hipLaunchKernelGGL((k_morph_one_pair<false, false, Q_>), grid, block, 0, s, src55, dst55, min55, g55, src29, dst29, min29, g29);                 \
     } while (0)
 #ifdef LT_EXPERIMENTS
-    if (pair_q == 8) { LT_PAIR(8); return true; }
+    if (pair_q == 8) { LT_PAIR(8); tell(8); return true; }
 #endif
     (void)pair_q;
     LT_PAIR(4);
 #undef LT_PAIR
+    tell(4);
     return true;
 }
 

@@ -2295,6 +2295,78 @@ int lt_morph_ellipse(lt_ctx* c, const uint8_t* img, int h, int w, int k, int op,
     return LT_OK;
 }
 
+// Test hook: ONE call of the top-hat launchers (k_tophat.hip) on planes given by value, in buffers of this call's own.  The destination,
+// the intermediate and the copy plane are n + 2 planes each, 0xA5 everywhere before the launch; the work goes to planes 1 .. n, so a
+// store outside them -- the pitch padding, the plane before, the PAIR strip's "frame n" behind -- comes back to the caller.
+int lt_morph_planes(lt_ctx* c, const uint8_t* planes, int n, int h, int w, int k, int op, int bands, int dpitch, int route,
+                    uint8_t* dst_out, uint8_t* mid_out, uint8_t* copy_out, lt_morph_report* report, int* launched) {
+    if (!c || !planes || !dst_out || !report || !launched) return fail(LT_ERR_INVALID, "null argument");
+    if (h < 1 || w < 1 || h > 4096 || w > 4096 || n < 1 || n > 16) return fail(LT_ERR_INVALID, "lt_morph_planes: 1 .. 16 planes of at most 4096 x 4096");
+    if (k != 29 && k != 55) return fail(LT_ERR_INVALID, "structuring element size must be 29 or 55");
+    if (op < 0 || op > 3) return fail(LT_ERR_INVALID, "op must be 0 erode, 1 dilate, 2 top-hat, 3 top-hat with minuend copy");
+    if (route != 0 && route != 1) return fail(LT_ERR_INVALID, "route must be 0 (launch_morph_runs) or 1 (launch_morph_one_pair)");
+    if (route == 1 && (n > 2 || op == 3)) return fail(LT_ERR_INVALID, "the pair launch takes one or two frames and has no minuend copy");
+    if (bands < 0 || (dpitch != 0 && dpitch != ((w + 63) & ~63))) return fail(LT_ERR_INVALID, "bands >= 0; dpitch is 0 or the width rounded up to 64");
+    if ((op >= 2) && !mid_out) return fail(LT_ERR_INVALID, "a top-hat returns its eroded intermediate: mid_out is null");
+    if (op == 3 && !copy_out) return fail(LT_ERR_INVALID, "copy_out is null");
+    int rc = set_device(c);
+    if (rc) return rc;
+    std::memset(report, 0, sizeof *report);
+    *launched = 0;
+    const int sets = route == 1 ? 2 : 1;                    // route 1: the 55x55 chain's planes, then the 29x29 chain's
+    const size_t ps = (size_t)h * w, pitch = dpitch ? (size_t)dpitch : (size_t)w, ds = (size_t)h * pitch;
+    const size_t src_bytes = (size_t)sets * n * ps, mid_bytes = (size_t)sets * (n + 2) * ps, dst_bytes = (size_t)sets * (n + 2) * ds;
+    DevBuf<uint8_t> d_src, d_mid, d_dst, d_copy;
+    DevBuf<uint32_t> d_zone;
+    MorphZone zone;
+    if ((rc = d_src.alloc(src_bytes)) || (rc = d_mid.alloc(mid_bytes)) || (rc = d_dst.alloc(dst_bytes)) || (rc = d_copy.alloc(dst_bytes))) return rc;
+    if (route == 0 && n > 2) {   // as MaskArena sizes it (set_geometry, ensure_zone_scratch): the 55x55 zones, per frame and strip
+        zone.stride_dwords = (size_t)((w + 127) / 128) * tophat_split_zone_dwords(55);
+        if ((rc = d_zone.alloc((size_t)n * zone.stride_dwords))) return rc;
+        zone.base = d_zone.p;
+    }
+    hipStream_t s = c->stream;
+    HIP_TRY(hipMemcpyAsync(d_src.p, planes, src_bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemsetAsync(d_mid.p, 0xA5, mid_bytes, s));
+    HIP_TRY(hipMemsetAsync(d_dst.p, 0xA5, dst_bytes, s));
+    HIP_TRY(hipMemsetAsync(d_copy.p, 0xA5, dst_bytes, s));
+    MorphReport rep;
+    bool ok = true;
+    if (route == 0) {
+        uint8_t *mid = d_mid.p + ps, *dst = d_dst.p + ds, *cp = d_copy.p + ds;
+        if (op == 0) ok = launch_morph_runs(s, d_src.p, dst, nullptr, h, w, k, false, ps, n, dpitch, ds, nullptr, zone, nullptr, bands, &rep);
+        else if (op == 1) ok = launch_morph_runs(s, d_src.p, dst, nullptr, h, w, k, true, ps, n, dpitch, ds, nullptr, zone, nullptr, bands, &rep);
+        else {
+            ok = launch_morph_runs(s, d_src.p, mid, nullptr, h, w, k, false, ps, n, 0, 0, nullptr, zone, nullptr, bands, &rep);
+            if (ok) ok = launch_morph_runs(s, mid, dst, d_src.p, h, w, k, true, ps, n, dpitch, ds, op == 3 ? cp : nullptr, zone, nullptr, bands, &rep);
+        }
+    } else {
+        const uint8_t *s55 = d_src.p, *s29 = d_src.p + (size_t)n * ps;
+        uint8_t *m55 = d_mid.p + ps, *m29 = d_mid.p + (size_t)(n + 2) * ps + ps, *o55 = d_dst.p + ds, *o29 = d_dst.p + (size_t)(n + 2) * ds + ds;
+        if (op == 0) ok = launch_morph_one_pair(s, s55, o55, nullptr, s29, o29, nullptr, h, w, false, ps, n, dpitch, ds, bands, &rep);
+        else if (op == 1) ok = launch_morph_one_pair(s, s55, o55, nullptr, s29, o29, nullptr, h, w, true, ps, n, dpitch, ds, bands, &rep);
+        else {
+            ok = launch_morph_one_pair(s, s55, m55, nullptr, s29, m29, nullptr, h, w, false, ps, n, 0, 0, bands, &rep);
+            if (ok) ok = launch_morph_one_pair(s, m55, o55, s55, m29, o29, s29, h, w, true, ps, n, dpitch, ds, bands, &rep);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(dst_out, d_dst.p, dst_bytes, hipMemcpyDeviceToHost, s));
+    if (mid_out) HIP_TRY(hipMemcpyAsync(mid_out, d_mid.p, mid_bytes, hipMemcpyDeviceToHost, s));
+    if (copy_out) HIP_TRY(hipMemcpyAsync(copy_out, d_copy.p, dst_bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    *launched = ok ? 1 : 0;
+    report->family = ok ? rep.family : 0;
+    report->wide = rep.wide;
+    report->nbands = rep.nbands;
+    report->band_rows = rep.band_rows;
+    report->pair_strip = rep.pair_strip;
+    report->q = rep.q;
+    report->nbands29 = rep.nbands29;
+    report->band_rows29 = rep.band_rows29;
+    return LT_OK;
+}
+
 int lt_fit_poly2(lt_ctx* c, const int32_t* ys, const int32_t* xs, int n, int h, int w, double coef[3], int* rank_deficient) {
     if (!c || !coef || !rank_deficient || n < 0 || (n > 0 && (!ys || !xs))) return fail(LT_ERR_INVALID, "bad argument");
     if (h < 1 || w < 1) return fail(LT_ERR_INVALID, "bad image size");

@@ -268,16 +268,24 @@ void launch_morph_ellipse(hipStream_t s, const uint8_t* src, uint8_t* dst, const
 // zone: scratch of the split-band form (k_tophat.hip: k_morph_split), `stride_dwords` per frame of the launch; without one, or for
 // a geometry tophat_split_form() refuses, the bands walk their halos (k_morph_runs2).  *form: 1 if the split-band form ran, else 0
 struct MorphZone { uint32_t* base = nullptr; size_t stride_dwords = 0; };
+// What a launcher call chose (lt_morph_planes, the test hook, hands it out): the kernel family, WIDE or narrow, the band cut, whether
+// the last strip is a PAIR strip, the waves per task of k_morph_one / k_morph_one_pair (0 elsewhere).  launch_morph_one_pair cuts its
+// two planes separately: nbands / band_rows are the 55x55 plane's, nbands29 / band_rows29 the 29x29 plane's (0 elsewhere).
+enum { MORPH_NONE = 0, MORPH_ONE = 1, MORPH_ONE_PAIR = 2, MORPH_RUNS2 = 3, MORPH_SPLIT = 4, MORPH_ONE_ROW = 5 };
+struct MorphReport { int family = MORPH_NONE, wide = 0, nbands = 0, band_rows = 0, pair_strip = 0, q = 0, nbands29 = 0, band_rows29 = 0; };
+// force_bands > 0: that many bands instead of the launcher's own rule (what LT_MORPH_NB_* does in the experiments build; k_morph_one's
+// bands stay even and at least 8 rows long)
 bool launch_morph_runs(hipStream_t s, const uint8_t* src, uint8_t* dst, const uint8_t* minuend, int h, int w, int k,
                        bool dilate, size_t plane_stride, int n, int dpitch = 0, size_t dst_stride = 0, uint8_t* copy_dst = nullptr,
-                       const MorphZone& zone = MorphZone(), int* form = nullptr);
+                       const MorphZone& zone = MorphZone(), int* form = nullptr, int force_bands = 0, MorphReport* report = nullptr);
 // geometry -> form: true where the split-band form takes (h, w) cut into `nbands` bands of `band_rows` rows (the last one shorter)
 bool tophat_split_form(int h, int w, int k, int band_rows, int nbands, bool wide);
 int tophat_split_zone_rows(int k);          // rows of a boundary zone: 56 (55x55), 28 (29x29)
 size_t tophat_split_zone_dwords(int k);     // scratch dwords per strip of a frame
 // one or two frames: the same step of the 55x55 chain of one plane and of the 29x29 chain of another in one launch; false: not launched
 bool launch_morph_one_pair(hipStream_t s, const uint8_t* src55, uint8_t* dst55, const uint8_t* min55, const uint8_t* src29, uint8_t* dst29,
-                           const uint8_t* min29, int h, int w, bool dilate, size_t plane_stride, int n, int dpitch, size_t dst_stride);
+                           const uint8_t* min29, int h, int w, bool dilate, size_t plane_stride, int n, int dpitch, size_t dst_stride,
+                           int force_bands = 0, MorphReport* report = nullptr);
 bool tophat_tables_match(const EllipseSE& se29, const EllipseSE& se55);
 void launch_bilateral(hipStream_t s, const uint8_t* src, uint8_t* dst, int h, int w, int ksize, int C, int mode,
                       int tv, int fv, size_t plane_stride, int n);

@@ -23,6 +23,11 @@ def test_new_names_are_declared_exported_and_bound():
         assert name in _native._SIGNATURES and name in _native.exported_symbols() and hasattr(lib, name), name
     for method in ("add_calibration", "set_slot_calibrations", "slot_calibrations", "calibration_count"):
         assert callable(getattr(_native.Context, method))
+    # the test hooks, which take planes or a fit by value: declared, exported and bound like everything else (additive: the ABI stays 5)
+    for name, method in (("lt_lane_spans_from_fit", "lane_spans_from_fit"), ("lt_morph_ellipse", "morph_ellipse"), ("lt_morph_planes", "morph_planes")):
+        assert re.search(r"\b%s\s*\(" % name, header), name
+        assert name in _native._SIGNATURES and name in _native.exported_symbols() and hasattr(lib, name), name
+        assert callable(getattr(_native.Context, method)), method
     # the header names every entry point that knows set 0 only
     for name in ("lt_present_frame", "lt_present_lane_async", "lt_present_lane_from_fit_async", "lt_present_finish", "lt_lane_spans_from_fit",
                  "lt_overlay_run_strip", "lt_overlay_run_strip_coeffs", "lt_search_viz_run", "lt_split_panes_run"):

@@ -24,6 +24,8 @@ def test_library_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in the header but not exported"
     assert sorted(_native.exported_symbols()) == declared
+    for hook in ("lt_lane_spans_from_fit", "lt_morph_ellipse", "lt_morph_planes"):      # the test hooks are part of the one list
+        assert hook in declared, hook
     assert lib.lt_abi_version() == _native.ABI_VERSION == 5
     assert int(re.search(r"#define LT_ABI_VERSION (\d+)", open(os.path.join(ROOT, "include", "lane_tracker_amd.h")).read()).group(1)) == 5
 
